@@ -10,15 +10,21 @@ largest batch the library forms) mixed-type queries per GPU, inputs resident in 
 steps are library calls over several batches each (N = 1: one call; N > 1: calls of ~K/4 batches, every batch's ids gathered to
 rank 0 over RCCL inside the timed region, under the next call's compute): consecutive batches of a call run on two lanes.
 Queries shard across ranks with no data-path collective (weak scaling: per-GPU work is fixed); value = queries all ranks
-answered / max-over-ranks time.
+answered / max-over-ranks time; ms_per_step = the timed region's wall time / K.
 
-Extra JSON objects: "roofline" for the dominant kernel (HIP-event kernel time measured live on the library's own streams),
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` if given and prints the result line with
+"roofline" for the dominant kernel (HIP-event kernel time measured live on the library's own streams during the timed steps)
+and, at N > 1, "collective".  `--dump-outputs DIR` writes what the last timed step returned for a fixed, seeded sample of its
+queries: DIR/ids.npy (float64), DIR/dists.npy (float32) and DIR/query_index.npy (float64, the sampled rows of the batch).
+
+`--full` adds the legs that take runs of their own (the --no-* options and --cpu-seconds 0 drop single ones):
 "end_to_end" (the same batches host memory -> host memory: the reference's own timing scope, PCIe-inclusive; never `value`),
 "fixed_q" (BASELINE's ONE 4x10^6-query set: N = 1 -- the shares of 1/2/4/8 ranks run on this GPU; N > 1 -- run for real: shares
 from host memory, RCCL gather to rank 0, sampled check on rank 0; strong scaling), "in_library" (N > 1 or --in-library: the same
-set through one hvs_create_multi context), "collective" (N > 1), "configs12" (BASELINE configs[1]/[2]: D = 10^6, Q = 10^4 on one
+set through one hvs_create_multi context), "configs12" (BASELINE configs[1]/[2]: D = 10^6, Q = 10^4 on one
 GPU, resident and host -> host), "cpu_baseline" (the oracle's reference-faithful threaded engine timed on this host's cores over
 a bounded query sample, rank 0 at N = 1 only) and "recall_at_100" of the GPU answers against that oracle sample.
+`--in-library`, `--in-library-only` and `--only-configs12` run their leg without `--full`.
 """
 import argparse
 import importlib
@@ -35,6 +41,26 @@ FP32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector = FP32 matrix peak
 BF16_PEAK_TFLOPS = 2500.0  # dense BF16 MFMA peak
 INT8_PEAK_TOPS = 5000.0    # dense INT8 MFMA peak (2x BF16 per clock)
 HBM_PEAK_GBS = 8000.0
+DUMP_QUERIES, DUMP_SEED = 16384, 0x5EED0D0  # --dump-outputs: sampled queries of the last timed batch (~20 MB in all)
+
+
+def dump_outputs(eng, np, batch0, nq, out_dir):
+    """Ids and distances of the k nearest rows for a fixed, seeded sample of the result rows [batch0, batch0 + nq): what a
+    caller of hvs_query_resident + hvs_download_results receives for those queries.  Ids as float64 (exact for any uint32)."""
+    m = min(DUMP_QUERIES, nq)
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(nq, size=m, replace=False)) if m < nq else np.arange(nq)
+    ids, dists = np.empty((m, eng.k), np.float64), np.empty((m, eng.k), np.float32)
+    chunk = 65536                                                       # (bounded host buffers: the batch is ~1.7 GB of results)
+    for c0 in range(0, nq, chunk):
+        lo, hi = np.searchsorted(sel, [c0, c0 + chunk])
+        if lo == hi:
+            continue
+        got_ids, got_d = eng.download_results(batch0 + c0, min(chunk, nq - c0))
+        ids[lo:hi], dists[lo:hi] = got_ids[sel[lo:hi] - c0], got_d[sel[lo:hi] - c0]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "dists.npy"), dists)
+    np.save(os.path.join(out_dir, "query_index.npy"), sel.astype(np.float64))
 
 
 def configs12_leg(pkg, T, np, steps=20, warmup=3):
@@ -151,7 +177,15 @@ def main():
     ap.add_argument("--only-configs12", action="store_true", help="run only that leg and print its object")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and run the result gather even with one rank (rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: end_to_end, fixed_q, cpu_baseline + recall, configs12, and "
+                         "in_library at N > 1 (a plain run times the K steps and prints the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the ids and distances the last timed step returned for a fixed, seeded "
+                         f"sample of {DUMP_QUERIES} of its queries as DIR/<name>.npy (float64 / float32)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -272,12 +306,14 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         elapsed, rank_ms_min = float(tt.item()), float(tmin.item()) * 1e3
     engine_id = int(eng.last_timing().engine)
+    if a.dump_outputs and rank == 0:                                    # before any leg below reuses the result buffer
+        dump_outputs(eng, np, (total_batches - 1) * a.batch, a.batch, a.dump_outputs)
     if use_dist and rank == 0 and world == 1:                          # --force-dist rehearsal: the gathered block is the local one
         got = eng.download_results((total_batches - 1) * a.batch, a.batch, want_dists=False)
         assert np.array_equal(gathered[0].cpu().numpy().view(np.uint32), got), "gathered ids differ from the local results"
     # the first timed batch: its answers are what the parity / end-to-end legs compare against
     first_timed_q = first_timed_ids = first_timed_dists = None
-    if rank == 0 or not a.no_e2e:
+    if a.full and (rank == 0 or not a.no_e2e):
         first_timed_q = eng.download_queries(a.warmup * a.batch, a.batch)
         first_timed_ids, first_timed_dists = eng.download_results(a.warmup * a.batch, a.batch)
 
@@ -351,7 +387,7 @@ def main():
     # ---- end-to-end leg: the reference's own timing scope (src/test.cpp:82-88: queries in host RAM -> ids in host
     # RAM).  The same a.steps batches as ONE hvs_query call from ordinary (pageable) host memory through the library's
     # pipeline (pinned staging, H2D one batch ahead, D2H under the next batch); never `value`.
-    if not a.no_e2e:
+    if a.full and not a.no_e2e:
         steps_e = min(a.steps, 4)                                       # (bounded: 4 batches of host buffers at most)
         nq_e = a.batch * steps_e
         q_host = eng.download_queries(a.warmup * a.batch, nq_e)
@@ -380,7 +416,7 @@ def main():
     # ---- fixed-Q leg (rank 0, N=1 only): BASELINE's metric is ONE query set of 4x10^6 (src/test.cpp:82-92 times one fixed
     # set), which an N-GPU run cuts into shares of 4x10^6 / N.  Each share is run on this GPU the way a rank would run it:
     # resident (one hvs_query_resident call) and from host memory (one hvs_query call, pageable buffers).
-    if rank == 0 and world == 1 and not a.no_fixed_q and a.n == 10_000_000 and a.profile == 1:
+    if a.full and rank == 0 and world == 1 and not a.no_fixed_q and a.n == 10_000_000 and a.profile == 1:
         peak_fq = {2: BF16_PEAK_TFLOPS, 3: INT8_PEAK_TOPS, 4: BF16_PEAK_TFLOPS}.get(engine_id, FP32_PEAK_TFLOPS)
         fixed = {"query_set": 4_000_000, "note": "one GPU running the share a rank of an N-GPU run gets (D replicated); "
                  "whole-node rate of such a run = N x the share's rate if every rank does the same", "shares": []}
@@ -414,7 +450,7 @@ def main():
     # its contiguous share (sharding.shard_range) FROM HOST MEMORY -- upload, one resident call, export -- and the ids are gathered
     # to rank 0 over RCCL inside the timed region; rank 0 then checks a sampled slice of every rank's share against its own
     # recomputation of those queries.
-    if use_dist and not a.no_fixed_q and a.n == 10_000_000 and a.profile == 1:
+    if a.full and use_dist and not a.no_fixed_q and a.n == 10_000_000 and a.profile == 1:
         QSET = 4_000_000
         f0, f1 = sharding.shard_range(QSET, rank, world)
         share, max_share = f1 - f0, -(-QSET // world)
@@ -460,7 +496,7 @@ def main():
         del q_host, send, recv
 
     # ---- CPU baseline + recall leg (rank 0, N=1 only; the oracle is the checker, never the product)
-    if rank == 0 and world == 1 and a.cpu_seconds > 0 and min(a.cpu_queries, a.batch) > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0 and min(a.cpu_queries, a.batch) > 0:
         nodes = eng.download_data(0, a.n)
         hw = os.cpu_count() or 1
         m_fixed = min(a.cpu_queries, a.batch)
@@ -522,12 +558,12 @@ def main():
     elif rank == 0:
         out["cpu_baseline"] = None
     eng.close()
-    if rank == 0 and world == 1 and not a.no_configs12:
+    if a.full and rank == 0 and world == 1 and not a.no_configs12:
         out["configs12"] = configs12_leg(pkg, T, np)
     # ---- in-library leg (--in-library; rank 0 after every rank has released its GPU): ONE context over all GPUs
     # (hvs_create_multi: what the vec_query seam and hvs_search.out use), one hvs_query of the whole 4x10^6-query set from
     # host memory to host memory -- the same job as the process-per-GPU fixed-Q leg, through the seam's own path.
-    if a.in_library or world > 1:
+    if a.in_library or (a.full and world > 1):
         # (host-side rendezvous through the process group's store: a collective barrier would leave a spinning RCCL kernel on
         # every GPU the in-library context is about to use)
         store = None

@@ -11,7 +11,7 @@ cd $ROOT
 PARTS="${*:-bench stats pmc lab}"
 B="python bench.py --cpu-seconds 0 --no-e2e --no-fixed-q --no-configs12"
 if [[ " $PARTS " == *" bench "* ]]; then
-python bench.py --steps 20 --warmup 5 > $OUT/bench_default_n1e7_b2097152_mixed_steps20.json 2> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default_n1e7_b2097152_mixed_steps20.json 2> $OUT/bench_default.err
 for t in 0 1 2 3; do $B --force-type $t > $OUT/bench_type${t}_n1e7_b2097152.json 2>/dev/null; done
 $B --force-type 0 --batch 262144 > $OUT/bench_type0_n1e7_b262144.json 2>/dev/null
 HVS_I8_SHAPE=32 $B > $OUT/bench_i8_32x32x32_n1e7_b2097152_mixed.json 2>/dev/null
@@ -21,8 +21,8 @@ $B --engine 1 --batch 16384 > $OUT/bench_exact_engine_n1e7_b16384_mixed.json 2>/
 $B --engine 1 --batch 16384 --force-type 0 > $OUT/bench_exact_engine_n1e7_b16384_type0.json 2>/dev/null
 for p in 2 3 4 5; do $B --profile $p > $OUT/bench_profile${p}_n1e7_b2097152_mixed.json 2>/dev/null; done
 python bench.py --only-configs12 > $OUT/bench_configs12.json 2>/dev/null
-python bench.py --n 100000000 --steps 2 --warmup 1 --cpu-seconds 0 --no-configs12 > $OUT/bench_n1e8_b2097152_mixed.json 2>/dev/null
-python bench.py --force-dist --steps 4 --warmup 1 --cpu-seconds 0 --no-e2e --no-configs12 --in-library --in-library-devices 0,0 > $OUT/bench_force_dist_rehearsal.json 2>/dev/null
+python bench.py --full --n 100000000 --steps 2 --warmup 1 --cpu-seconds 0 --no-configs12 > $OUT/bench_n1e8_b2097152_mixed.json 2>/dev/null
+python bench.py --full --force-dist --steps 4 --warmup 1 --cpu-seconds 0 --no-e2e --no-configs12 --in-library --in-library-devices 0,0 > $OUT/bench_force_dist_rehearsal.json 2>/dev/null
 HVS_LANES=0 $B > $OUT/bench_one_lane.json 2>/dev/null
 $B --per-step-calls > $OUT/bench_per_step_calls.json 2>/dev/null
 echo "bench lines done"

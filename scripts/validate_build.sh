@@ -10,7 +10,7 @@ tail -3 $OUT/tests_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -2 $OUT/smoke.log
 S=$(date +%s)
-python bench.py --steps 20 --warmup 5 > $OUT/bench_default_driver_flags.json 2>$OUT/bench_default.err || { tail -30 $OUT/bench_default.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default_driver_flags.json 2>$OUT/bench_default.err || { tail -30 $OUT/bench_default.err; exit 1; }
 echo "bench wall $(( $(date +%s) - S )) s"
 python - <<PY
 import json

@@ -182,5 +182,6 @@ def test_bench_command_line_parses_without_a_gpu():
     import sys
     r = subprocess.run([sys.executable, os.path.join(T.REPO, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-500:]
-    for flag in ("--gpus", "--steps", "--warmup", "--in-library", "--in-library-only", "--only-configs12", "--per-step-calls", "--force-dist"):
+    for flag in ("--gpus", "--steps", "--warmup", "--in-library", "--in-library-only", "--only-configs12", "--per-step-calls", "--force-dist",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout, flag
