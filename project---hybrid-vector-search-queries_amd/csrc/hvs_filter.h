@@ -2815,6 +2815,21 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 // ---------------------------------------------------------------------------------------------
 // (FINAL as a template parameter: the padding path's exact-order distance costs 70 VGPRs that would halve the
 // occupancy of the latency-bound merges before it)
+//
+// Mutant builds (tests/test_filter_bounds.py only; the default build defines neither switch and compiles the plain band):
+// -DHVS_MUTANT_BAND_SCALE=s multiplies the band by s, -DHVS_MUTANT_DROP=mask leaves terms out of it (1: the E_D term,
+// 2: the e_q term, 4: the clip term of a query outside the INT8 box, 8: rho).  A build with a band that is too small must
+// give wrong answers on the adversarial data sets of tests/bound_model.py -- that is what shows the tests would notice.
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+#ifndef HVS_MUTANT_BAND_SCALE
+#define HVS_MUTANT_BAND_SCALE 1.0
+#endif
+#ifndef HVS_MUTANT_DROP
+#define HVS_MUTANT_DROP 0
+#endif
+#define HVS_MUT_SCALE ((double)(HVS_MUTANT_BAND_SCALE))
+#define HVS_MUT_TERM(bit, x) (((HVS_MUTANT_DROP) & (bit)) ? 0.0 : (x))
+#endif
 template <bool FINAL, int CAP>
 __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, uint32_t n, const float* __restrict__ Q,
                                                    HvsBatch B, const HvsBounds* __restrict__ bounds, int pad,
@@ -2891,8 +2906,14 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
                     const double g = 20.0 * 5.9604644775390625e-08;
                     const double iu = qz->inv_sd * qz->inv_sd;  // 1 / sd^2
                     // (normq: the clip term of a query outside the data's box, see hvs_k_prep)
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+                    const double band = (HVS_MUT_TERM(1, (double)B.nqb[slot] * (double)bounds->e_d8) +
+                                         HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->n_d8) +
+                                         HVS_MUT_TERM(4, (double)B.normq[slot])) * (1.0 + 1e-6) * HVS_MUT_SCALE;
+#else
                     const double band = ((double)B.nqb[slot] * (double)bounds->e_d8 + (double)B.eq[slot] * (double)bounds->n_d8 +
                                          (double)B.normq[slot]) * (1.0 + 1e-6);
+#endif
                     // -2: one unit for nh = floor(.), one for the f64 evaluation of this expression (relative
                     // 1e-9 of the magnitudes on top)
                     double th = (0.5 * (B.qn[slot] * (1.0 - 1e-12) - (double)tau * (1.0 + 2.0 * g)) - band) * iu;
@@ -2909,8 +2930,13 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
                 const double g = 20.0 * 5.9604644775390625e-08;
                 const double sabs = (double)B.nqb[slot] * (double)bounds->nb_d + 1.02 * (double)bounds->hmax;
                 const double mu = 256.0 * 5.9604644775390625e-08 * sabs;
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+                const double band = (mu + HVS_MUT_TERM(8, (double)bounds->rho) + HVS_MUT_TERM(1, (double)B.normq[slot] * (double)bounds->e_d) +
+                                     HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->nb_d)) * HVS_MUT_SCALE;
+#else
                 const double band = mu + (double)bounds->rho + (double)B.normq[slot] * (double)bounds->e_d +
                                     (double)B.eq[slot] * (double)bounds->nb_d;
+#endif
                 // slack for the f64 evaluation itself: relative to the magnitudes involved (an absolute constant
                 // would swamp data whose distances are tiny, e.g. vectors scaled by 1e-3)
                 const double slack = 1e-9 * (B.qn[slot] + (double)tau + band);
