@@ -191,17 +191,13 @@ const uint32_t kBatchMfma = env_u32("HVS_MFMA_BATCH", 1u << 21, 128u, 1u << 21);
 const uint32_t kRescoreBlocks = env_u32("HVS_RESCORE_BLOCKS", 0u, 0u, 64u);  // 0: chosen per batch
 // small batches: level 0 (the exact seed kernel) is cut into chunks until about this many waves are in flight
 const uint32_t kSeedWaves = env_u32("HVS_SEED_WAVES", 16384u, 64u, 1u << 20);
-// exact full scan: rows through LDS (1) or through the scalar cache (0); HVS_SCAN_LDS overrides for A/B runs
-const bool kScanRowsThroughLds = env_u32("HVS_SCAN_LDS", 1u, 0u, 1u) != 0u;
 // INT8 tiles are built for v_mfma_i32_16x16x64_i8 (HVS_FMT_I8X16: 1.16x the pair rate of the 32x32x32 shape in the
 // filter loop, scripts/mfma_shape_lab.hip); HVS_I8_SHAPE=32 selects the 32x32x32 layout (HVS_FMT_I8) for A/B runs
 const int kI8Fmt = env_u32("HVS_I8_SHAPE", 16u, 16u, 32u) == 32u ? HVS_FMT_I8 : HVS_FMT_I8X16;
-// Level radices of the index (powers of two; see "Guessed thresholds" at hvs_k_merge): HVS_GUESS=0 restores round 2's
-// doubling levels with proven thresholds for A/B runs
-const bool kGuess = env_u32("HVS_GUESS", 1u, 0u, 1u) != 0u;
+// Level radices of the index (powers of two; see "Guessed thresholds" at hvs_k_merge)
 uint32_t pow2_floor(uint32_t x) { uint32_t p = 2u; while (p * 2u <= x) p *= 2u; return p; }
-const uint32_t kRadixLast = kGuess ? pow2_floor(env_u32("HVS_RADIX_LAST", HVS_RADIX_LAST, 2u, 64u)) : 2u;
-const uint32_t kRadixMid = kGuess ? pow2_floor(env_u32("HVS_RADIX_MID", HVS_RADIX_MID, 2u, 64u)) : 2u;
+const uint32_t kRadixLast = pow2_floor(env_u32("HVS_RADIX_LAST", HVS_RADIX_LAST, 2u, 64u));
+const uint32_t kRadixMid = pow2_floor(env_u32("HVS_RADIX_MID", HVS_RADIX_MID, 2u, 64u));
 // HVS_RADICES="4,8,32": the radices of the last levels, last level first (A/B runs); HVS_RADIX_MID continues behind them
 struct RadixPlan {
     uint32_t r[16] = {};
@@ -209,7 +205,7 @@ struct RadixPlan {
     RadixPlan()
     {
         const char* v = std::getenv("HVS_RADICES");
-        if (!v || !*v || !kGuess) return;
+        if (!v || !*v) return;
         int k = 0;
         bool ok = true;
         while (*v && k < 14) {
@@ -468,21 +464,12 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
         with_cap(c->cap, [&](auto CAPT) {
             constexpr int CAP = decltype(CAPT)::value;
-            if (kScanRowsThroughLds) {
-                if (c->scalar_order)
-                    hipLaunchKernelGGL((hvs_k_scan_exact_lds<true, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                       p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
-                else
-                    hipLaunchKernelGGL((hvs_k_scan_exact_lds<false, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                       p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
-            } else {
-                if (c->scalar_order)
-                    hipLaunchKernelGGL((hvs_k_scan_exact<true, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                       p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
-                else
-                    hipLaunchKernelGGL((hvs_k_scan_exact<false, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                       p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
-            }
+            if (c->scalar_order)
+                hipLaunchKernelGGL((hvs_k_scan_exact_lds<true, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
+                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
+            else
+                hipLaunchKernelGGL((hvs_k_scan_exact_lds<false, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
+                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
         });
     }
     kernel_timer_end(c, ev);
@@ -1052,7 +1039,7 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
 // Exact engine on top of the index.  Queries with a categorical predicate (types 1 and 3) scan only
 // their position range of the (C,T) ordering (hvs_k_scan_ranges): ~1 % / 0.25 % of the rows, 17-25x
 // faster than scanning everything.  Type-0 and type-2 queries keep the sequential full scan in original
-// row order (hvs_k_scan_exact streams D once through the scalar cache): a position range is a random
+// row order (hvs_k_scan_exact_lds streams D once, staged through LDS): a position range is a random
 // permutation of the rows, and measured on D=1e7 gathering 25 % of them (type 2) is slower than
 // streaming all of them (8.2 k vs 14 k queries/s).
 int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
@@ -1186,7 +1173,7 @@ uint32_t guess_m(double F, uint32_t k, double target)
     }
     return k;
 }
-// `proven` (retry batches; HVS_GUESS=0): m = k at every level -- the proven threshold, which cannot fail (a query that
+// `proven` (retry batches): m = k at every level -- the proven threshold, which cannot fail (a query that
 // failed under a guess did so because the rows it had seen were unlucky, and a larger guess from the same rows shares
 // that luck)
 HvsGuessTable plan_guess(uint32_t k, bool proven, uint32_t pfail)
@@ -1194,9 +1181,9 @@ HvsGuessTable plan_guess(uint32_t k, bool proven, uint32_t pfail)
     HvsGuessTable G{};
     const double target = std::pow(10.0, -(double)pfail);
     for (int i = 0; i < HVS_GUESS_STEPS; ++i)
-        G.m[i] = (uint16_t)((kGuess && !proven) ? guess_m(std::exp2(-(double)i / 8.0), k, target) : k);
-    G.floor_m = (uint16_t)std::min(k, (kGuess && !proven) ? kGuessMid : k);
-    G.last_m = (uint16_t)((proven || !kGuess) ? k : 0u);
+        G.m[i] = (uint16_t)(proven ? k : guess_m(std::exp2(-(double)i / 8.0), k, target));
+    G.floor_m = (uint16_t)std::min(k, proven ? k : kGuessMid);
+    G.last_m = (uint16_t)(proven ? k : 0u);
     return G;
 }
 
@@ -1242,7 +1229,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         c->guess_have[gslot] = true;
     }
     const HvsGuessTable G = c->guess_tab[gslot];
-    B.fail_code = (kGuess && !proven_last) ? HVS_FAIL_RETRY : HVS_FAIL_EXACT;
+    B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
     if (sn != n && !list)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
                            c->d_counters);
@@ -1469,14 +1456,6 @@ std::vector<uint32_t> batch_schedule(uint32_t nq, uint32_t step, bool ramp_allow
     // two / three equal batches 183.3 / 189.0 ms, resident 169 ms)
     const uint32_t edge = kBatchMfma / 8u;
     const bool ramp = ramp_allowed && edge >= 1024u && nq >= 4u * edge;
-    // (A/B, HVS_SPLIT_SMALL=1: a small call as two half batches on the two lanes, ungated -- see run_queries)
-    static const bool kSplitSmall = env_u32("HVS_SPLIT_SMALL", 0u, 0u, 1u) != 0u;
-    if (kSplitSmall && step == kBatchMfma && nq >= 4096u && nq <= 65536u) {
-        const uint32_t half = hvs_ceil_div(hvs_ceil_div(nq, 2u), 512u) * 512u;
-        out.push_back(half);
-        out.push_back(nq - half);
-        return out;
-    }
     if (!ramp) {
         for (uint32_t off = 0; off < nq; off += step) out.push_back(std::min(step, nq - off));
         return out;
@@ -1582,7 +1561,7 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
         if (two_lanes) {
             // this batch's preparation starts behind the previous batch's (other lane) second-to-last filter launch, its seed
             // behind the last one; it records its own two events
-            const bool have_prev = b > 0 && c->lv.K >= 1u && nq > 65536u;  // (small calls, HVS_SPLIT_SMALL: no gates)
+            const bool have_prev = b > 0 && c->lv.K >= 1u;
             if (have_prev) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->lv.K >= 2u ? c->ev_pdone[(b - 1u) & 1u] : c->ev_fdone[(b - 1u) & 1u], 0));
             c->gate_heavy = have_prev ? c->ev_fdone[(b - 1u) & 1u] : nullptr;
             c->ev_fdone_cur = c->ev_fdone[b & 1u];

@@ -894,24 +894,6 @@ __global__ void hvs_k_count_classes(const float* __restrict__ Q, uint32_t q0, ui
     }
 }
 
-#ifndef HVS_HIT_TREE
-#define HVS_HIT_TREE 1         // sub-block dispatch of a tile with hits through a tree of scalar ORs (0: linear; A/B: +1.2 % queries/s with the tree)
-#endif
-#ifndef HVS_FILTER_SETPRIO
-#define HVS_FILTER_SETPRIO 0  // hvs_k_filter_i8x16: s_setprio around the matrix block (A/B builds: 1 high while multiplying, 2 high in the
-                              // epilogue; measured again in round 3, with few survivors left: -0.4 % either way)
-#endif
-#ifndef HVS_H16_PREFETCH
-#define HVS_H16_PREFETCH 0    // hvs_k_filter_mfma: 1 = the next tile's LDS reads issue under this tile's epilogue, as in hvs_k_filter_i8x16
-                              // (measured on FP16 / BF16 tiles: 3 % SLOWER than reading them in front of the tile's own matrix block)
-#endif
-#ifndef HVS_ORDER_MORTON
-#define HVS_ORDER_MORTON 0   // 1: Z-order of (range start, range end) instead of start bins sorted by end (A/B builds; measured in
-                             // round 3: type-2 batches 597 vs 592 ms, mixed 675 vs 673 ms, 5 x 10^5-query batches equal: not adopted)
-#endif
-#ifndef HVS_BIN_QUERIES
-#define HVS_BIN_QUERIES 0u   // 0: sqrt rule below; otherwise a fixed number of queries per start-position bin (A/B builds)
-#endif
 // `counts`: the batch's class populations (hvs_k_count_classes) -- read on the device, so that forming a batch needs
 // no host round trip
 __global__ void hvs_k_query_keys2(const float* __restrict__ Q, uint32_t q0, uint32_t nq, const uint32_t* __restrict__ list,
@@ -930,34 +912,11 @@ __global__ void hvs_k_query_keys2(const float* __restrict__ Q, uint32_t q0, uint
     // two binary searches are done once per query and batch
     qa[i] = a;
     qb[i] = b;
-#if HVS_BIN_QUERIES
-    uint32_t nbins = counts[rk] / HVS_BIN_QUERIES;
-#else
     // as many start-position bins as there are quads of 512 queries per bin: a quad's spread of range STARTS (one bin) and of
     // range ENDS (its share of the bin, which is sorted by end) are then about the same fraction of the data
     uint32_t nbins = (uint32_t)__builtin_sqrtf((float)counts[rk] * (1.0f / (float)(HVS_WG_WAVES * HVS_GROUP)));
-#endif
     nbins = nbins < 1u ? 1u : (nbins > 4096u ? 4096u : nbins);
     const uint32_t abin = (uint32_t)(((uint64_t)a * nbins) / ((uint64_t)n + 1ull));
-#if HVS_ORDER_MORTON
-    // A/B: queries of a class along the Z-order curve of (range start, range end), 16 bits each: 128 consecutive queries
-    // then fill a compact cell of the (start, end) plane instead of a strip of one start bin
-    {
-        auto spread = [](uint32_t x) -> uint32_t {  // 16 bits -> every other bit of 32
-            x &= 0xFFFFu;
-            x = (x | (x << 8)) & 0x00FF00FFu;
-            x = (x | (x << 4)) & 0x0F0F0F0Fu;
-            x = (x | (x << 2)) & 0x33333333u;
-            x = (x | (x << 1)) & 0x55555555u;
-            return x;
-        };
-        const uint32_t a16 = (uint32_t)(((uint64_t)a << 16) / ((uint64_t)n + 1ull)), b16 = (uint32_t)(((uint64_t)b << 16) / ((uint64_t)n + 1ull));
-        (void)abin;
-        keys[i] = ((uint64_t)rk << 61) | ((uint64_t)((spread(a16) << 1) | spread(b16)) << 16) | (uint64_t)(b & 0xFFFFu);
-        idx[i] = i;
-        return;
-    }
-#endif
     keys[i] = ((uint64_t)rk << 61) | ((uint64_t)abin << 32) | (uint64_t)b;
     idx[i] = i;
 }
@@ -1276,14 +1235,11 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// hvs_k_seed_exact -- level 0 by the exact kernel (lane = query, wave-uniform rows through the
-// scalar cache, exactly like hvs_k_scan_exact) over the level-0 blocks of the group's range.
-// The per-lane predicate is the slot's own position range.  Survivors go to cand[slot].
-// One wave per 64 slots.
+// hvs_k_seed_exact -- level 0 by the exact kernel (lane = query, wave-uniform rows staged in LDS,
+// distances by hvs_exact_dist_pk_lds like hvs_k_scan_exact_lds) over the level-0 blocks of the
+// group's range.  The per-lane predicate is the slot's own position range.  Survivors go to
+// cand[slot].  One wave per 64 slots.
 // ---------------------------------------------------------------------------------------------
-#ifndef HVS_SEED_LDS
-#define HVS_SEED_LDS 1      // level-0 rows through a wave-private LDS image (0: one by one through the scalar cache; A/B builds)
-#endif
 #ifndef HVS_SEED_STAGE
 #define HVS_SEED_STAGE 16u  // rows per image (a power of two dividing 32)
 #endif
@@ -1292,10 +1248,6 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 #endif
 #define HVS_PRAGMA_(x) _Pragma(#x)
 #define HVS_PRAGMA(x) HVS_PRAGMA_(x)
-struct HvsUniformRowF2 {
-    const hvs_f2* __restrict__ p;
-    __device__ __forceinline__ hvs_f2 operator[](int i) const { return p[i]; }
-};
 
 template <int CAP>
 __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restrict__ D, uint32_t n, uint32_t sn,
@@ -1306,9 +1258,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
                                                            const uint32_t* __restrict__ bpos_t, HvsLevels L,
                                                            unsigned long long* __restrict__ counters, uint32_t nchunks)
 {
-#if HVS_SEED_LDS
     __shared__ float4 srow[4][HVS_SEED_STAGE][26];  // per wave: 16 data rows as 16-byte aligned images x0..x99 (+ pad)
-#endif
     // nchunks > 1 (small batches, level 0 of at most 1024 rows): grid.y waves share one 64-slot group, each
     // takes every nchunks-th level-0 block and appends to the slots' lists with atomics -- a single wave per
     // group walks ~1000 randomly placed rows one after the other and is latency-bound (2 ms at 10^4 queries)
@@ -1364,7 +1314,6 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
         for (uint32_t r = 0; r < 32u; ++r) {
             const uint32_t pos = b * 32u + r;
             if (pos >= n) break;
-#if HVS_SEED_LDS
             // The block's rows sit anywhere in D (perm): fetched one by one through the scalar cache, every row is a dependent
             // round trip to HBM (0.23 ms for 960 rows x 10^4 queries, a quarter of the exact engine's rate).  16 rows at a
             // time are gathered by the whole wave instead (800 8-byte loads in flight) into a wave-private LDS image and
@@ -1390,18 +1339,12 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
-#endif
             const bool pass = pos >= ra && pos < rb;
             if (__ballot(pass) == 0ull) continue;
             const uint32_t id = perm[pos];
             if (id >= sn) continue;  // sampled prefix: rows [0, sn) of the original order only
             nscan += 64u;
-#if HVS_SEED_LDS
             const float dist = hvs_exact_dist_pk_lds(&srow[threadIdx.x >> 6][r & (HVS_SEED_STAGE - 1u)][0], q2);
-#else
-            HvsUniformRowF2 dv{reinterpret_cast<const hvs_f2*>(D + (size_t)id * HVS_DCOLS + 2)};
-            const float dist = hvs_exact_dist_pk(dv, q2);
-#endif
             if (nchunks > 1u) {  // wave-uniform
                 if (pass && kk < kend) mylist[kk] = hvs_make_key(dist, id);
                 kk += pass ? 1u : 0u;
@@ -1433,13 +1376,19 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
 }
 
 // ---------------------------------------------------------------------------------------------
-// hvs_k_scan_ranges -- the exact engine on top of the index: the same lane-per-query, scalar-row
-// kernel as hvs_k_scan_exact, but a wave walks only the POSITION RANGE of its 64 queries (the
-// union of their predicate ranges in the (C,T) or T ordering) instead of all of D, and the per-lane
-// predicate is a position-range test.  Type-1/3 queries then touch ~1 % / 0.25 % of the rows and a
-// type-2 wave touches only rows that some of its queries want.  grid.y cuts the range into chunks.
+// hvs_k_scan_ranges -- the exact engine on top of the index: the lane-per-query kernel of
+// hvs_k_scan_exact_lds with wave-uniform rows read through the scalar cache, but a wave walks only
+// the POSITION RANGE of its 64 queries (the union of their predicate ranges in the (C,T) or T
+// ordering) instead of all of D, and the per-lane predicate is a position-range test.  Type-1/3
+// queries then touch ~1 % / 0.25 % of the rows and a type-2 wave touches only rows that some of
+// its queries want.  grid.y cuts the range into chunks.
 // With sn < n (sample_proportion < 1) rows whose original id is >= sn are skipped.
 // ---------------------------------------------------------------------------------------------
+struct HvsUniformRowF2 {
+    const hvs_f2* __restrict__ p;
+    __device__ __forceinline__ hvs_f2 operator[](int i) const { return p[i]; }
+};
+
 template <bool SCALAR_ORDER, int CAP>
 __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restrict__ D, uint32_t sn,
                                                             const float* __restrict__ Q, HvsBatch B,
@@ -1486,7 +1435,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         q2[2 * i + 1] = hvs_f2{v4.z, v4.w};
     }
     uint64_t* __restrict__ mylist = cand + ((size_t)chunk * B.nslots + slot) * (uint32_t)CAP;
-    float tau = __builtin_nanf("");  // admits every passing row until the first cut (see hvs_k_scan_exact)
+    float tau = __builtin_nanf("");  // admits every passing row until the first cut (see hvs_k_scan_exact_lds)
     uint32_t cnt = 0, nscan = 0;
     for (uint32_t pos = p0; pos < p1; ++pos) {
         const bool pass = pos >= ra && pos < rb;
@@ -1854,10 +1803,8 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
         }
     };
     auto stage_barrier = [&]() {
-#ifndef HVS_EXPERIMENT_NOSYNC
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA chunks have landed
         __syncthreads();
-#endif
     };
     // ---- the tile loop ---------------------------------------------------------------------------------------
     // Per tile: A fragments (+ INT8 accumulator inits) from LDS, the 4 chains (two pairs, each interleaved
@@ -1925,9 +1872,6 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
             for (int r = 3; r < 15; r += 2) m = F::max2(F::max2(m, acc[qb][r]), acc[qb][r + 1]);
             m = F::max2(m, acc[qb][15]);
             hm[qb] = __ballot(m >= theta[qb]);
-    #ifdef HVS_EXPERIMENT_NOHIT
-            hm[qb] = __ballot(m == (typename F::thr_t)12345678);  // keeps the max chain alive, (almost) never true: ceiling experiment
-    #endif
         }
     };
     // Survivors of one query block (about one wave-tile in ten at the top level, every tile at the low ones --
@@ -1976,18 +1920,12 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     // Tile t: [LDS reads of its fragments] [28 / 16 matrix instructions] [epilogues] [survivors, rarely].  Round 3 took over from
     // hvs_k_filter_i8x16: the wave's tile range per stage computed once, the stage slot stepped instead of derived, the range
     // tests of edge blocks behind one branch, the hit tests as a tree (+2.7 % on FP16 / BF16 tiles, +3.7 % on 32x32x32 INT8
-    // tiles); NOT its read order (HVS_H16_PREFETCH: the next tile's fragment reads under this tile's epilogue), which costs
-    // 3 % here -- 7 KiB of fragments per tile and wave instead of 4, and the compiler's staggered chains already start the first
+    // tiles); NOT its read order (the next tile's fragment reads under this tile's epilogue), which costs 3 % here
+    // -- 7 KiB of fragments per tile and wave instead of 4, and the compiler's staggered chains already start the first
     // epilogue under the last matrix instructions.
-    auto tile_body = [&](uint32_t bpx, bool inner, uint32_t inext, uint32_t slot_next) {
+    auto tile_body = [&](uint32_t bpx, bool inner) {
         chains(0);
         chains(1);
-#if HVS_H16_PREFETCH
-        __builtin_amdgcn_sched_barrier(0);
-        load_tile(slot_next);  // (always: a conditional load makes the compiler copy the fragment registers per tile)
-        load_bp(inext);
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         epilogue(0, bpx, inner);
         epilogue(1, bpx, inner);
         if (!inner) {  // blocks at the edge of some lane's own range: one small branch for the 8 per-lane range compares
@@ -2008,41 +1946,28 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
         }
     };
     for (uint32_t st = 0; st < nstage; ++st) {
-#ifndef HVS_EXPERIMENT_NODMA
         if (st + 1u < nstage) issue_stage((st & 1u) ^ 1u, I0 + (st + 1u) * STG);
-#endif
         // this wave's tiles of the stage: [t0, t1)
         const uint32_t s0 = I0 + st * STG;
         const uint32_t t0 = i0 > s0 ? i0 : s0;
         const uint32_t t1 = i1 < s0 + STG ? i1 : s0 + STG;  // (i1 <= I1)
         if (active && t0 < t1) {
             uint32_t slot = (st & 1u) * STG + (t0 - s0);
-#if HVS_H16_PREFETCH
-            load_tile(slot);
-            load_bp(t0);
-#endif
 #pragma unroll 1
             for (uint32_t i = t0; i < t1; ++i) {
                 ++nblocks;
-#if !HVS_H16_PREFETCH
                 // fragments and block position in front of the tile's own matrix block.  (Measured on FP16 tiles, against
                 // this order: the reads under the previous tile's epilogue -3 %; only the block position's scalar load
                 // under it -1 %, and -2.5 % more with a scheduling barrier between the matrix block and the epilogue -- the
                 // compiler starts the first chain's epilogue between the last matrix instructions of the other three.)
                 load_tile(slot);
                 load_bp(i);
-#endif
                 wcnt = __builtin_amdgcn_readfirstlane(wcnt);
                 const uint32_t bpx = bp;
                 const bool inner = bpx * 32u >= ra_max && bpx * 32u + 32u <= rb_min;
-                const bool more = i + 1u < t1;  // (last tile of the stage: re-read this one, unused)
-#if HVS_H16_PREFETCH
-                slot += more ? 1u : 0u;
-#else
                 slot += 1u;
-#endif
                 asm volatile("" : "+s"(slot));  // (otherwise the compiler re-derives it from i)
-                tile_body(bpx, inner, more ? i + 1u : i, slot);
+                tile_body(bpx, inner);
             }
         }
         stage_barrier();
@@ -2379,11 +2304,6 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     //     after >= 6 LDS reads and >= 28 vector instructions, far beyond the 4-pass result latency;
     //   * the fragment / init registers are overwritten only by LDS reads issued after the last matrix instruction.
     auto chains = [&]() {
-#if HVS_FILTER_SETPRIO == 1
-        __builtin_amdgcn_s_setprio(3);  // A/B: the multiplying wave keeps the matrix pipe
-#elif HVS_FILTER_SETPRIO == 2
-        __builtin_amdgcn_s_setprio(0);  // A/B: the wave in its epilogue goes first
-#endif
 #pragma unroll
         for (int j = 0; j < NSUB; ++j)
 #pragma unroll
@@ -2394,11 +2314,6 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 #pragma unroll
             for (int r2 = 0; r2 < 2; ++r2)
                 asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc[r2][j]) : "v"(af[2 * r2 + 1]), "v"(bq[j][1]));
-#if HVS_FILTER_SETPRIO == 1
-        __builtin_amdgcn_s_setprio(0);
-#elif HVS_FILTER_SETPRIO == 2
-        __builtin_amdgcn_s_setprio(3);
-#endif
         __builtin_amdgcn_sched_barrier(0);
     };
     auto imax = [](int a, int b) { return a > b ? a : b; };
@@ -2408,18 +2323,11 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     auto epilogue = [&](uint32_t bpx, bool inner) {
 #pragma unroll
         for (int j = 0; j < NSUB; ++j) {
-#ifdef HVS_EXPERIMENT_NOEPI
-            int m = imax(acc[0][j][0], acc[1][j][3]);  // ceiling experiment: 1 instead of 4 instructions per sub-block
-#else
             int m = imax(imax(acc[0][j][0], acc[0][j][1]), acc[0][j][2]);  // v_max3 chain
             m = imax(imax(m, acc[0][j][3]), acc[1][j][0]);
             m = imax(imax(m, acc[1][j][1]), acc[1][j][2]);
             m = imax(m, acc[1][j][3]);
-#endif
             hm[j] = __ballot(m >= theta[j]);
-#ifdef HVS_EXPERIMENT_NOHIT
-            hm[j] = __ballot(m == 0x7fffff37);  // keeps the max chain alive, (almost) never true: ceiling experiment
-#endif
             if (j == NSUB / 2 - 1) __builtin_amdgcn_sched_barrier(0);  // (the younger accumulators are read last)
         }
         if (!inner) {
@@ -2469,8 +2377,8 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
         load_tile(inext, slot_next);  // (always: a conditional load would make the compiler copy the 24 fragment registers per tile)
         __builtin_amdgcn_sched_barrier(0);
         epilogue(bpx, inner);
-#if HVS_HIT_TREE
         // most tiles with a hit have it in ONE sub-block: find it through a tree of scalar ORs (3 tests) instead of 8
+        // (+1.2 % queries/s against testing the 8 one after the other)
         static_assert(NSUB == 8, "the hit tree is written for 8 sub-blocks");
         const uint64_t h01 = hm[0] | hm[1], h23 = hm[2] | hm[3], h45 = hm[4] | hm[5], h67 = hm[6] | hm[7];
         const uint64_t lo = h01 | h23, hi = h45 | h67;
@@ -2496,16 +2404,6 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
                 }
             }
         }
-#else
-        uint64_t any = 0;
-#pragma unroll
-        for (int j = 0; j < NSUB; ++j) any |= hm[j];
-        if (any != 0ull) {
-#pragma unroll
-            for (int j = 0; j < NSUB; ++j)
-                if (hm[j] != 0ull) survivors(j, bpx);
-        }
-#endif
     };
     for (uint32_t st = 0; st < nstage; ++st) {
         if (st + 1u < nstage) issue_stage((st & 1u) ^ 1u, I0 + (st + 1u) * STG);

@@ -57,209 +57,70 @@ __global__ void hvs_k_query_keys(const float* __restrict__ Q, uint32_t q0, uint3
 }
 
 // ---------------------------------------------------------------------------------------------
-// hvs_k_scan_exact -- the reference's inner hot loop (optimized_parallel.hpp:100-139 +
+// hvs_k_scan_exact_lds -- the reference's inner hot loop (optimized_parallel.hpp:100-139 +
 // optimized_impl.h:54-125,284-311) re-shaped for a 64-wide wavefront:
 //
 //   * one LANE per QUERY: the query's 100 dims live in 100 VGPRs for the whole kernel, the
 //     running threshold tau and the list fill are per-lane registers;
-//   * the DATA ROW is wave-uniform: it is fetched through the scalar cache into SGPRs and fed
-//     to v_sub_f32 as the scalar operand, so one 408-byte row fetch serves 64 (query,row) pairs
-//     and costs no VGPRs, no LDS and no vector-memory instruction;
-//   * predicates (C == v, l <= T <= r) are evaluated per lane on the scalar C,T; a row no lane
+//   * the DATA ROWS are staged in LDS: the four waves of a workgroup (256 queries) walk the same
+//     row chunk, so a block of rows is copied once per workgroup (coalesced 16-B loads,
+//     double-buffered, one barrier per block) into a 16-B aligned image [x0..x99, C, T, pad, pad]
+//     and every wave reads it back with broadcast ds_read_b128;
+//   * predicates (C == v, l <= T <= r) are evaluated per lane on the row's C,T; a row no lane
 //     accepts is skipped by the whole wave (one ballot + scalar branch);
-//   * the distance is the reference's exact order (8 accumulators, no FMA), 300 VALU ops/pair;
+//   * the distance is the reference's exact order (8 accumulators, no FMA);
 //   * admission is the reference's strict `dist < worst` (optimized_impl.h:301): accepted pairs
 //     are appended to the lane's private list in global memory; a full list is cut back to its
 //     100 smallest (dist,id) keys by the whole wave (hvs_wave_select_prune), which also gives
 //     the new tau.  Rows are scanned in ascending id, so a later row with dist == tau can never
 //     displace a kept one under the canonical (dist asc, id asc) order.
 //
-// Grid: x = blocks of 4 query-waves (256 queries), y = row chunk.  Waves never synchronise
-// with each other.  Output: per (chunk, query slot) a list of <= HVS_CAND_CAP keys + its fill.
+// Grid: x = blocks of 4 query-waves (256 queries), y = row chunk.  Waves synchronise only at the
+// staging barriers.  Output: per (chunk, query slot) a list of <= HVS_CAND_CAP keys + its fill.
 // ---------------------------------------------------------------------------------------------
-struct HvsUniformRow2 {
-    const hvs_f2* __restrict__ p;  // row + 2 floats: 8-byte aligned (row stride 408 B)
-    __device__ __forceinline__ hvs_f2 operator[](int i) const { return p[i]; }
-};
-
-struct HvsUniformRow1 {
-    const float* __restrict__ p;
-    __device__ __forceinline__ float operator[](int i) const { return p[i]; }
-};
 struct HvsPairAsScalar {  // view the lane's 50 query pairs as 100 floats
     const hvs_f2* q2;
     __device__ __forceinline__ float operator[](int i) const { return (i & 1) ? q2[i >> 1].y : q2[i >> 1].x; }
 };
 
-// SCALAR_ORDER = false: the hot path's SIMD summation order (optimized_impl.h:96-125);
-// SCALAR_ORDER = true : the baseline engine's sequential order (baseline.hpp:53-64), BASELINE.json configs[0].
-// (three workgroups per CU: at four the 128-register budget spilled 10-22 registers of the 100 query components)
-template <bool SCALAR_ORDER, int CAP>
-__global__ __launch_bounds__(256, 3) void hvs_k_scan_exact(
-    const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
-    uint32_t nq_pad, uint32_t sn, uint32_t rows_per_chunk, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt,
-    unsigned long long* __restrict__ counters, uint32_t knn)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t qwave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const uint32_t slot = qwave * 64u + lane;
-    const uint32_t chunk = blockIdx.y;
-    if (qwave * 64u >= nq) return;  // wave-uniform
-
-    const bool have_q = slot < nq;
-    const uint32_t qi = qorder[have_q ? slot : nq - 1u];
-    const float* __restrict__ qrow = Q + (size_t)qi * HVS_QCOLS;
-    HvsQParams p = hvs_parse_query(qrow);
-    if (!have_q) p.type = 4u;
-
-    hvs_f2 q2[HVS_NDIM / 2];
-#pragma unroll
-    for (int i = 0; i < HVS_NDIM / 4; ++i) {
-        const float4 v4 = *reinterpret_cast<const float4*>(qrow + 4 + 4 * i);
-        q2[2 * i] = hvs_f2{v4.x, v4.y};
-        q2[2 * i + 1] = hvs_f2{v4.z, v4.w};
-    }
-
-    const uint32_t r0 = chunk * rows_per_chunk;
-    uint32_t r1 = r0 + rows_per_chunk;
-    if (r1 > sn || r1 < r0) r1 = sn;
-
-    uint64_t* __restrict__ mylist = cand + ((size_t)chunk * nq_pad + slot) * CAP;
-    // tau = NaN until the list has been cut back once: `!(dist >= tau)` then admits EVERY passing row, +inf and NaN
-    // distances included, as the reference does while its list is not full (optimized_impl.h:301-304)
-    float tau = __builtin_nanf("");
-    uint32_t cnt = 0;
-    uint32_t npass = 0, nscan = 0;  // per-wave statistics (uniform)
-
-    for (uint32_t j = r0; j < r1; ++j) {
-        const float* __restrict__ row = D + (size_t)j * HVS_DCOLS;
-        const float C = row[0];
-        const float T = row[1];
-        const bool pass = hvs_row_passes(p, C, T);
-        const uint64_t pmask = __ballot(pass);
-        if (pmask == 0ull) continue;
-        npass += (uint32_t)__popcll(pmask);
-        nscan += 64u;
-
-        HvsUniformRow2 dv{reinterpret_cast<const hvs_f2*>(row + 2)};
-        float dist;
-        if (SCALAR_ORDER) {
-            HvsUniformRow1 d1{row + 2};
-            HvsPairAsScalar q1{q2};
-            dist = hvs_scalar_order_dist(d1, q1);
-        } else {
-            dist = hvs_exact_dist_pk(dv, q2);
-        }
-
-        if (pass && !(dist >= tau)) {
-            mylist[cnt] = hvs_make_key(dist, j);
-            ++cnt;
-        }
-        uint64_t full = __ballot(cnt == (uint32_t)CAP);
-        if (full != 0ull) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            while (full != 0ull) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(full);
-                full &= full - 1ull;
-                uint64_t* lst = cand + ((size_t)chunk * nq_pad + (qwave * 64u + l)) * CAP;
-                const uint64_t kth = hvs_wave_select_prune<CAP / 64>(lst, (uint32_t)CAP, knn, lane);
-                if (lane == l) {
-                    cnt = knn;
-                    tau = hvs_key_dist(kth);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
-    }
-    if (have_q) cand_cnt[(size_t)chunk * nq_pad + slot] = cnt;
-    if (lane == 0u) {
-        atomicAdd(&counters[0], (unsigned long long)npass);
-        atomicAdd(&counters[1], (unsigned long long)nscan);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// hvs_k_scan_exact_lds -- the same scan with the data rows staged in LDS instead of SGPRs.
-// The four waves of a workgroup (256 queries) walk the same row chunk, so a block of 32 rows is
-// copied once per workgroup (coalesced 16-B loads, double-buffered, one barrier per 32 rows) into a
-// 16-B aligned image [x0..x99, C, T, pad, pad] and every wave reads it back with broadcast
-// ds_read_b128.  This removes the scalar-load round trips of hvs_k_scan_exact from the row loop
-// (two dependent s_load + s_waitcnt per row there); arithmetic and admission are identical.
-// ---------------------------------------------------------------------------------------------
 #ifndef HVS_LDS_ROWS
 #define HVS_LDS_ROWS 16   // rows per staged block (32: 8 more staging registers, which spill at three workgroups per CU)
 #endif
 #define HVS_LDS_ROW_F 104  // floats per staged row (416 B, 16-B aligned)
 
-struct HvsLdsRow2 {
-    const float4* p;  // 16-B aligned row image in LDS
-    __device__ __forceinline__ hvs_f2 operator[](int i) const
-    {
-        const float4 v = p[i >> 1];
-        return (i & 1) ? hvs_f2{v.z, v.w} : hvs_f2{v.x, v.y};
-    }
-};
-// Exact-order distance of an LDS-staged row, software-pipelined by hand: the row's 25 ds_read_b128 are issued two b-steps
-// (4 reads, 16 components) ahead of the packed arithmetic that consumes them, alternating between two register sets, so
-// that every group of 8 independent v_pk_add / v_pk_mul / v_pk_add triples runs while the next group's reads are in
-// flight.  (Left to the compiler the loop kept 2 reads in flight and waited for each: ~35 s_nop and 27 s_waitcnt per row.)
+// Exact-order distance of an LDS-staged row, software-pipelined by hand: the row's 25 ds_read_b128 rotate through three
+// register sets of one b-step each (2 reads, 8 components); a set is refilled for step b + 3 as soon as step b has consumed
+// it, so that six reads are in flight under every step's independent v_pk_add / v_pk_mul / v_pk_add triples.  (Left to the
+// compiler the loop kept 2 reads in flight and waited for each: ~35 s_nop and 27 s_waitcnt per row.  Two double-step sets,
+// 8 reads in flight, need 32 registers and two workgroups per CU: measured 0.216 against 0.237 of the FP32 peak on type-0.)
 // The arithmetic and its order per accumulator are hvs_exact_dist_pk's: acc2[k] takes dims (8b + 2k, 8b + 2k + 1) for
 // b = 0..11 in order, then the masked tail, then the hsum tree (optimized_impl.h:96-125, :37-47).
-// (ceiling experiments, never shipped: HVS_EXPERIMENT_EXACT=1 reads every other step's row data from LDS and re-uses the registers
-// for the steps between -- half the ds_read_b128 traffic, wrong distances; =2 drops the multiplications -- two thirds of the vector
-// arithmetic.  profiles/r04/exact_engine_ceiling.txt)
-#if defined(HVS_EXPERIMENT_EXACT) && HVS_EXPERIMENT_EXACT == 2
-#define HVS_LDS_SQ(t) t
-#else
-#define HVS_LDS_SQ(t) t * t
-#endif
 #define HVS_LDS_STEP(LO, HI, B)                                                                     \
     {                                                                                               \
         hvs_f2 t0 = hvs_f2{LO.x, LO.y} - q2[4 * (B) + 0], t1 = hvs_f2{LO.z, LO.w} - q2[4 * (B) + 1]; \
         hvs_f2 t2 = hvs_f2{HI.x, HI.y} - q2[4 * (B) + 2], t3 = hvs_f2{HI.z, HI.w} - q2[4 * (B) + 3]; \
-        t0 = HVS_LDS_SQ(t0);                                                                        \
-        t1 = HVS_LDS_SQ(t1);                                                                        \
-        t2 = HVS_LDS_SQ(t2);                                                                        \
-        t3 = HVS_LDS_SQ(t3);                                                                        \
+        t0 = t0 * t0;                                                                               \
+        t1 = t1 * t1;                                                                               \
+        t2 = t2 * t2;                                                                               \
+        t3 = t3 * t3;                                                                               \
         a0 = a0 + t0;                                                                               \
         a1 = a1 + t1;                                                                               \
         a2 = a2 + t2;                                                                               \
         a3 = a3 + t3;                                                                               \
     }
-// one group: two b-steps from registers (X0..X3), then the reads that refill them (float4 index NEXT.., or none)
-#define HVS_LDS_GROUP(X0, X1, X2, X3, B, NEXT)          \
-    HVS_LDS_STEP(X0, X1, (B))                           \
-    HVS_LDS_STEP(X2, X3, (B) + 1)                       \
-    __builtin_amdgcn_sched_barrier(0);                  \
-    if ((NEXT) >= 0 && (NEXT) + 3 < 24) {               \
-        X0 = rowp[(NEXT) >= 0 ? (NEXT) : 0];            \
-        X1 = rowp[(NEXT) >= 0 ? (NEXT) + 1 : 0];        \
-        X2 = rowp[(NEXT) >= 0 ? (NEXT) + 2 : 0];        \
-        X3 = rowp[(NEXT) >= 0 ? (NEXT) + 3 : 0];        \
-    }                                                   \
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef HVS_LDS_RING3
-#define HVS_LDS_RING3 1   // three single-step register sets (6 reads in flight, 24 registers); 0: two double-step sets (8 reads, 32
-                          // registers: needs two workgroups per CU -- measured 0.216 against 0.237 of the FP32 peak on type-0)
-#endif
-__device__ __forceinline__ float hvs_exact_dist_pk_lds(const float4* rowp, const hvs_f2* q2)
-{
-    hvs_f2 a0 = hvs_f2{0.0f, 0.0f}, a1 = a0, a2 = a0, a3 = a0;
-#if HVS_LDS_RING3
-    float4 A0 = rowp[0], A1 = rowp[1], B0 = rowp[2], B1 = rowp[3], C0 = rowp[4], C1 = rowp[5];
-    __builtin_amdgcn_sched_barrier(0);
-#if defined(HVS_EXPERIMENT_EXACT) && HVS_EXPERIMENT_EXACT == 1
-#define HVS_LDS_REFILL(NEXT) ((NEXT) >= 0 && (((NEXT) / 2) & 1) == 0)
-#else
-#define HVS_LDS_REFILL(NEXT) ((NEXT) >= 0)
-#endif
+// one step from registers (X0, X1), then the reads that refill them (float4 index NEXT.., or none)
 #define HVS_LDS_ONE(X0, X1, B, NEXT)                    \
     HVS_LDS_STEP(X0, X1, (B))                           \
     __builtin_amdgcn_sched_barrier(0);                  \
-    if (HVS_LDS_REFILL(NEXT)) {                         \
+    if ((NEXT) >= 0) {                                  \
         X0 = rowp[(NEXT) >= 0 ? (NEXT) : 0];            \
         if ((NEXT) + 1 < 25) X1 = rowp[(NEXT) >= 0 ? (NEXT) + 1 : 0]; \
     }                                                   \
+    __builtin_amdgcn_sched_barrier(0);
+__device__ __forceinline__ float hvs_exact_dist_pk_lds(const float4* rowp, const hvs_f2* q2)
+{
+    hvs_f2 a0 = hvs_f2{0.0f, 0.0f}, a1 = a0, a2 = a0, a3 = a0;
+    float4 A0 = rowp[0], A1 = rowp[1], B0 = rowp[2], B1 = rowp[3], C0 = rowp[4], C1 = rowp[5];
     __builtin_amdgcn_sched_barrier(0);
     HVS_LDS_ONE(A0, A1, 0, 6)
     HVS_LDS_ONE(B0, B1, 1, 8)
@@ -274,24 +135,6 @@ __device__ __forceinline__ float hvs_exact_dist_pk_lds(const float4* rowp, const
     HVS_LDS_ONE(B0, B1, 10, -1)
     HVS_LDS_ONE(C0, C1, 11, -1)
     const float4 TL = A0;
-#undef HVS_LDS_ONE
-#else
-    float4 A0 = rowp[0], A1 = rowp[1], A2 = rowp[2], A3 = rowp[3];
-    float4 B0 = rowp[4], B1 = rowp[5], B2 = rowp[6], B3 = rowp[7];
-    __builtin_amdgcn_sched_barrier(0);
-    HVS_LDS_GROUP(A0, A1, A2, A3, 0, 8)
-    HVS_LDS_GROUP(B0, B1, B2, B3, 2, 12)
-    HVS_LDS_GROUP(A0, A1, A2, A3, 4, 16)
-    HVS_LDS_GROUP(B0, B1, B2, B3, 6, 20)
-    float4 TL;
-    HVS_LDS_STEP(A0, A1, 8)
-    HVS_LDS_STEP(A2, A3, 9)
-    __builtin_amdgcn_sched_barrier(0);
-    TL = rowp[24];  // dims 96..99: the masked tail
-    __builtin_amdgcn_sched_barrier(0);
-    HVS_LDS_STEP(B0, B1, 10)
-    HVS_LDS_STEP(B2, B3, 11)
-#endif
     {
         hvs_f2 t2 = hvs_f2{TL.x, TL.y} - q2[48];
         hvs_f2 t3 = hvs_f2{TL.z, TL.w} - q2[49];
@@ -306,7 +149,7 @@ __device__ __forceinline__ float hvs_exact_dist_pk_lds(const float4* rowp, const
     const float b2 = s23.x + s23.y;
     return a + b2;
 }
-#undef HVS_LDS_GROUP
+#undef HVS_LDS_ONE
 #undef HVS_LDS_STEP
 
 struct HvsLdsRow1 {
@@ -319,6 +162,8 @@ struct HvsLdsRow1 {
 #ifndef HVS_LDS_SCAN_WGS
 #define HVS_LDS_SCAN_WGS 3
 #endif
+// SCALAR_ORDER = false: the hot path's SIMD summation order (optimized_impl.h:96-125);
+// SCALAR_ORDER = true : the baseline engine's sequential order (baseline.hpp:53-64), BASELINE.json configs[0].
 template <bool SCALAR_ORDER, int CAP>
 __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
@@ -382,7 +227,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     };
 
     uint64_t* __restrict__ mylist = cand + ((size_t)chunk * nq_pad + slot) * CAP;
-    float tau = __builtin_nanf("");  // (see hvs_k_scan_exact)
+    // tau = NaN until the list has been cut back once: `!(dist >= tau)` then admits EVERY passing row, +inf and NaN
+    // distances included, as the reference does while its list is not full (optimized_impl.h:301-304)
+    float tau = __builtin_nanf("");
     uint32_t cnt = 0;
     uint32_t npass = 0, nscan = 0;
     // queries are sorted by type: a wave of type-0 queries only (the exact engine's slowest class) skips the per-row predicate --
