@@ -199,6 +199,45 @@ uint32_t hvs_plan_batches(uint32_t nq, int host_pipeline, uint32_t *out, uint32_
 
 const char *hvs_version(void);
 
+/* ---- row deletion: a live-row mask (tombstones) ------------------------------------------ */
+
+/*
+ * "Deleted" means "as if the row had never been in D, with ids unchanged".  Let `live` be the ascending list of ids
+ * that are not deleted, n_live its length and D' the rows D[live] in that order: for every engine, distance order, k,
+ * padding mode and sample_proportion the answer of a call on (D, mask) is the answer of the same call on D' with every
+ * id j replaced by live[j].  So the rows searched are the first uint32(float(sample_proportion) * float(n_live)) live
+ * rows, padding appends live[n_live-1], live[n_live-2], ..., a deleted id appears in no output slot, and
+ * hvs_timing.pairs counts live rows only.  n_live >= k is required as n >= k is: a mask change (or hvs_set_k) that would
+ * break it returns HVS_EINVAL and leaves the context as it was.  hvs_load_data / hvs_gen_data reset the mask to "all
+ * live".  While no row is dead every call runs exactly the kernels it runs without these functions.
+ * All of them accept a multi-GPU context (the mask is replicated to every GPU, like D).  The D-sharded mode
+ * (sharding.py, hvs_merge_shards_device) knows nothing of masks: a shard context may carry a mask of its own, but the
+ * merge pads from the tail of the whole data set as before.
+ */
+typedef struct hvs_mask_info {
+    uint32_t n_live;         /* rows that are not deleted                                                            */
+    uint32_t n_dead;         /* rows that are                                                                        */
+    uint64_t tiles_patched;  /* rows whose filter-tile entry carries the format's never-hit encoding, summed over both
+                                orderings (2 n_dead once the tiles of a filter engine are built and patched)          */
+    uint64_t dead_survivors; /* last call: filter survivors the re-scoring front end dropped because the row is dead  */
+} hvs_mask_info;
+/* ids: host memory.  Duplicates and ids that are dead already are fine; an id >= n is HVS_EINVAL and nothing is applied. */
+int hvs_delete_rows(hvs_ctx *ctx, const uint32_t *ids, uint32_t count);
+/* live_bits: host memory, ceil(n / 64) words, bit (i & 63) of word (i >> 6) set = row i is live.  Replaces the whole
+ * mask (rows may come back).  NULL: all rows live. */
+int hvs_set_row_mask(hvs_ctx *ctx, const uint64_t *live_bits);
+int hvs_get_row_mask(hvs_ctx *ctx, uint64_t *live_bits);
+uint32_t hvs_num_live_rows(const hvs_ctx *ctx);
+/* Call after hvs_sync / hvs_query.  Multi-GPU context: the mask's and tiles' figures of one GPU (they are replicated),
+ * dead_survivors summed over the GPUs. */
+int hvs_mask_stats(hvs_ctx *ctx, hvs_mask_info *out);
+/* The host arithmetic of the contract (no GPU, no context; live_bits NULL = all live; any output may be NULL):
+ * n_live = popcount; cut = live[sn_live] with sn_live = uint32(float(sample_proportion) * float(n_live)), or n when
+ * sn_live == n_live -- the rows searched are "id < cut and live"; pad_ids[0..k) = the last k live ids in descending
+ * order (0xFFFFFFFF where n_live < k). */
+void hvs_mask_plan(const uint64_t *live_bits, uint32_t n, uint32_t k, float sample_proportion, uint32_t *n_live,
+                   uint32_t *cut, uint32_t *pad_ids);
+
 #ifdef __cplusplus
 }
 #endif

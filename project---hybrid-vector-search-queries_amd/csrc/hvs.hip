@@ -86,6 +86,21 @@ struct hvs_ctx : HvsLane {
     bool padding = true;        // pad answers with the last rows of D (off: partial answers of a data shard)
     std::string err;
 
+    // live-row mask (hvs_set_row_mask / hvs_delete_rows).  While n_dead == 0 every launch takes the unmasked
+    // instantiation of its kernel and none of the device buffers below is read.
+    std::vector<uint64_t> h_live;   // host copy: ceil(n / 64) words, bits past n clear (empty: no mask set, all rows live)
+    uint32_t n_dead = 0;
+    uint32_t* d_live = nullptr;     // the same bits as u32 words in HBM (allocated by the first mask call after a load)
+    uint32_t* d_pad_ids = nullptr;  // the last k live ids in descending order (HVS_KMAX entries)
+    uint32_t* d_mask_ids = nullptr; // id list of the running hvs_delete_rows
+    uint32_t mask_ids_cap = 0;
+    uint32_t *d_lp_ct = nullptr, *d_lp_t = nullptr;  // live rows in front of each position of the two orderings (hvs_k_live_flags)
+    bool lp_valid = false;
+    unsigned long long* d_mask_stat = nullptr;  // [0]: rows whose tile entry carries the never-hit encoding, both orderings
+    bool cut_valid = false;         // cut id of the sampled live prefix for sample_proportion cut_sp (hvs_mask_plan), cached
+    float cut_sp = 0.0f;
+    uint32_t cut_id = 0, cut_sn_live = 0;
+
     // data set, raw rows n x 102 (the io.h layout) resident in HBM
     float* d_data = nullptr;
     uint32_t n = 0;
@@ -355,6 +370,19 @@ void with_cap(int cap, F f)
         f(std::integral_constant<int, 256>{});
 }
 
+// ... and for the two forms of the kernels that read the live-row mask: `f` gets (capacity, masked) as compile-time constants;
+// masked only while at least one row is dead
+template <typename F>
+void with_cap_mask(const hvs_ctx* c, F f)
+{
+    with_cap(c->cap, [&](auto CAPT) {
+        if (c->n_dead)
+            f(CAPT, std::true_type{});
+        else
+            f(CAPT, std::false_type{});
+    });
+}
+
 // optimized_parallel.hpp:67: const uint32_t sn = uint32_t(sample_proportion * n);  (float product)
 uint32_t sample_rows(float sample_proportion, uint32_t n)
 {
@@ -462,25 +490,29 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
     if (sn > 0) {
         unsigned long long* stat = count_stats ? c->d_counters : c->d_counters + 4;
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
-        with_cap(c->cap, [&](auto CAPT) {
+        with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
+            constexpr bool M = decltype(MT)::value;
             if (c->scalar_order)
-                hipLaunchKernelGGL((hvs_k_scan_exact_lds<true, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
+                hipLaunchKernelGGL((hvs_k_scan_exact_lds<true, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
+                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k, c->d_live);
             else
-                hipLaunchKernelGGL((hvs_k_scan_exact_lds<false, CAP>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k);
+                hipLaunchKernelGGL((hvs_k_scan_exact_lds<false, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
+                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k, c->d_live);
         });
     }
     kernel_timer_end(c, ev);
-    with_cap(c->cap, [&](auto CAPT) {
+    with_cap_mask(c, [&](auto CAPT, auto MT) {
         constexpr int CAP = decltype(CAPT)::value;
+        constexpr bool M = decltype(MT)::value;
         if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_select<true, CAP>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k);
+            hipLaunchKernelGGL((hvs_k_select<true, CAP, M>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
+                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
+                               c->d_pad_ids);
         else
-            hipLaunchKernelGGL((hvs_k_select<false, CAP>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k);
+            hipLaunchKernelGGL((hvs_k_select<false, CAP, M>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
+                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
+                               c->d_pad_ids);
     });
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -501,6 +533,7 @@ void free_index(hvs_ctx* c)
     c->d_nrm_ct = c->d_nrm_t = nullptr;
     c->d_bpos_ct = c->d_bpos_t = nullptr;
     c->have_index = false;
+    c->lp_valid = false;  // (counts along the orderings that have just gone)
     c->tile_fmt = HVS_FMT_NONE;
     c->i8_usable = false;
     c->i8_rot = false;
@@ -601,6 +634,65 @@ int choose_format(hvs_ctx* c)
     return HVS_OK;
 }
 
+// hvs_timing.pairs under a mask: live rows in front of every position of both orderings (see hvs_k_live_flags); made on first
+// use after a mask change
+int ensure_live_prefix(hvs_ctx* c)
+{
+    if (c->lp_valid) return HVS_OK;
+    const uint32_t n = c->n;
+    int rc;
+    if (!c->d_lp_ct && (rc = dev_alloc(c, &c->d_lp_ct, (size_t)n + 1u))) return rc;
+    if (!c->d_lp_t && (rc = dev_alloc(c, &c->d_lp_t, (size_t)n + 1u))) return rc;
+    size_t tmp_bytes = 0;
+    HVS_HIP(c, rocprim::exclusive_scan(nullptr, tmp_bytes, c->d_lp_ct, c->d_lp_ct, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream));
+    void* tmp = nullptr;
+    HVS_HIP(c, hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
+    hipError_t e = hipSuccess;
+    for (int ord = 0; ord < 2 && e == hipSuccess; ++ord) {
+        uint32_t* lp = ord ? c->d_lp_t : c->d_lp_ct;
+        hipLaunchKernelGGL(hvs_k_live_flags, dim3(hvs_ceil_div(n + 1u, 256u)), dim3(256), 0, c->stream, c->d_live, ord ? c->d_perm_t : c->d_perm_ct,
+                           n, lp);
+        e = rocprim::exclusive_scan(tmp, tmp_bytes, lp, lp, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(c, HVS_EHIP, std::string("live-row counts: ") + hipGetErrorString(e));
+    c->lp_valid = true;
+    return HVS_OK;
+}
+
+// passing pairs of a batch under a mask (counters[0]): from the prefix counts, or row by row when a sampled prefix cuts in
+int count_masked_pairs(hvs_ctx* c, uint32_t sn)
+{
+    HvsBatch& B = c->fb;
+    if (sn == c->n) {
+        int rc = ensure_live_prefix(c);
+        if (rc) return rc;
+        hipLaunchKernelGGL(hvs_k_count_live_pairs, dim3(hvs_ceil_div(B.nslots, 256u)), dim3(256), 0, c->stream, B, c->d_lp_ct, c->d_lp_t,
+                           c->d_counters);
+    } else {
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<true>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+                           c->d_counters, c->d_live);
+    }
+    return HVS_OK;
+}
+
+// Tombstones (hvs_k_patch_tiles): the never-hit encoding over the tile entries of the dead rows, both orderings.  Called after
+// every mask change that only kills rows and at the end of every tile build while rows are dead.
+int patch_tiles(hvs_ctx* c)
+{
+    if (!c->n_dead || c->tile_fmt == HVS_FMT_NONE || !c->d_tiles_ct || !c->d_live || !c->d_mask_stat) return HVS_OK;
+    const HvsLevels L = c->lv;
+    HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    const dim3 grid((L.nblk + 3u) / 4u);
+    hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, c->d_perm_ct, c->n, L, c->d_bpos_ct, c->d_tiles_ct,
+                       reinterpret_cast<int*>(c->d_nrm_ct), c->tile_fmt, c->d_mask_stat);
+    hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, c->d_perm_t, c->n, L, c->d_bpos_t, c->d_tiles_t,
+                       reinterpret_cast<int*>(c->d_nrm_t), c->tile_fmt, c->d_mask_stat);
+    HVS_HIP(c, hipGetLastError());
+    return HVS_OK;
+}
+
 // (re)build the level-interleaved tiles of both orderings in format `fmt`; the orderings must exist
 int build_tiles(hvs_ctx* c, int fmt)
 {
@@ -609,6 +701,7 @@ int build_tiles(hvs_ctx* c, int fmt)
     int rc;
     c->tile_fmt = HVS_FMT_NONE;
     c->have_index = false;
+    if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
     // free first: the two formats never coexist (D = 1e8: 44.8 GB of BF16 tiles, 20.8 GB of INT8 tiles)
     if ((rc = dev_alloc(c, &c->d_tiles_ct, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->d_tiles_t, (size_t)0))) return rc;
@@ -672,7 +765,7 @@ int build_tiles(hvs_ctx* c, int fmt)
     c->tile_fmt = fmt;
     c->have_index = true;
     c->i8_rot_built = HVS_IS_I8(fmt) && c->i8_rot;
-    return HVS_OK;
+    return patch_tiles(c);  // (nothing while every row is live)
 }
 
 int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last);
@@ -1044,12 +1137,14 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
 // streaming all of them (8.2 k vs 14 k queries/s).
 int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
 {
-    int rc = prep_batch(c, q0, nqb, sn == c->n, HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
+    int rc = prep_batch(c, q0, nqb, sn == c->n && !c->n_dead, HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
     if (rc) return rc;
     HvsBatch& B = c->fb;
-    if (sn != c->n)
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
-                           c->d_counters);
+    if (c->n_dead) {
+        if ((rc = count_masked_pairs(c, sn))) return rc;
+    } else if (sn != c->n)
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+                           c->d_counters, c->d_live);
     // slot layout of hvs_k_layout: classes 0..3 padded to 32 slots each, then the T-ordering class (type 2)
     // from the next filter-workgroup boundary
     const uint32_t nq0 = c->class_counts[0], nq2 = c->class_counts[4];
@@ -1072,27 +1167,31 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     HVS_HIP(c, hipMemsetAsync(c->d_cand_cnt, 0, lists * sizeof(uint32_t), c->stream));
     const int ev = kernel_timer_begin(c);
     const dim3 grid((slot_end + 255u) / 256u, nchunks);
-    with_cap(c->cap, [&](auto CAPT) {
+    with_cap_mask(c, [&](auto CAPT, auto MT) {
         constexpr int CAP = decltype(CAPT)::value;
+        constexpr bool M = decltype(MT)::value;
         if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_scan_ranges<true, CAP>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
-                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters);
+            hipLaunchKernelGGL((hvs_k_scan_ranges<true, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
+                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters, c->d_live);
         else
-            hipLaunchKernelGGL((hvs_k_scan_ranges<false, CAP>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
-                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters);
+            hipLaunchKernelGGL((hvs_k_scan_ranges<false, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
+                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters, c->d_live);
     });
     kernel_timer_end(c, ev);
     const uint32_t nsel = slot_end - slot_begin;
     uint64_t* cand = c->d_cand + (size_t)slot_begin * (size_t)c->cap;
     uint32_t* cnt = c->d_cand_cnt + slot_begin;
-    with_cap(c->cap, [&](auto CAPT) {
+    with_cap_mask(c, [&](auto CAPT, auto MT) {
         constexpr int CAP = decltype(CAPT)::value;
+        constexpr bool M = decltype(MT)::value;
         if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_select<true, CAP>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k);
+            hipLaunchKernelGGL((hvs_k_select<true, CAP, M>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
+                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
+                               c->d_pad_ids);
         else
-            hipLaunchKernelGGL((hvs_k_select<false, CAP>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k);
+            hipLaunchKernelGGL((hvs_k_select<false, CAP, M>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
+                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
+                               c->d_pad_ids);
     });
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1212,7 +1311,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
 {
     const int fmt = c->tile_fmt;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
-    int rc = prep_batch(c, q0, nqb, sn == c->n && !list, fmt, false, list, want_fcap);
+    int rc = prep_batch(c, q0, nqb, sn == c->n && !list && !c->n_dead, fmt, false, list, want_fcap);
     if (rc) return rc;
     if ((rc = build_items(c))) return rc;
     HvsBatch& B = c->fb;
@@ -1230,9 +1329,11 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     }
     const HvsGuessTable G = c->guess_tab[gslot];
     B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
-    if (sn != n && !list)
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
-                           c->d_counters);
+    if (c->n_dead && !list) {
+        if ((rc = count_masked_pairs(c, sn))) return rc;
+    } else if (sn != n && !list)
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+                           c->d_counters, c->d_live);
 
     if (c->gate_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gate_heavy, 0));  // (two lanes: see hvs_ctx::ev_pdone)
     // level 0 by the exact kernel; small batches cut it into chunks so that enough waves are in flight
@@ -1240,21 +1341,22 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     const uint32_t seed_waves = hvs_ceil_div(B.nslots, 64u);
     uint32_t seed_chunks = 1u;
     if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = std::min(l0blocks, hvs_ceil_div(kSeedWaves, seed_waves));
-    with_cap(c->cap, [&](auto CAPT) {
-        hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value>), dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0,
-                           c->stream, c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_bpos_ct, c->d_bpos_t, L, c->d_counters,
-                           std::max(1u, seed_chunks));
+    with_cap_mask(c, [&](auto CAPT, auto MT) {
+        hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)),
+                           dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_bpos_ct, c->d_bpos_t, L,
+                           c->d_counters, std::max(1u, seed_chunks), c->d_live);
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
     auto launch_merge = [&](bool final, uint32_t next) {
-        with_cap(c->cap, [&](auto CAPT) {
+        with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
-            if (final)
-                hipLaunchKernelGGL((hvs_k_merge<true, CAP>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n, c->d_q, B,
-                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G);
+            if (final)  // (only the final merge pads: the merges in front of it have no masked form)
+                hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n,
+                                   c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G,
+                                   c->d_pad_ids);
             else
-                hipLaunchKernelGGL((hvs_k_merge<false, CAP>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n, c->d_q, B,
-                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G);
+                hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n, c->d_q, B,
+                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->d_pad_ids);
         });
     };
     launch_merge(L.K == 0u, 1u);
@@ -1291,12 +1393,15 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             if (level == L.K && c->ev_fdone_cur) HVS_HIP(c, hipEventRecord(c->ev_fdone_cur, c->stream));
             if (level + 1u == L.K && c->ev_pdone_cur) HVS_HIP(c, hipEventRecord(c->ev_pdone_cur, c->stream));
         }
-        if (fmt == HVS_FMT_I8X16)
-            hipLaunchKernelGGL(hvs_k_rescore<true>, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, n,
-                               sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters);
-        else
-            hipLaunchKernelGGL(hvs_k_rescore<false>, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, n,
-                               sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters);
+        with_cap_mask(c, [&](auto, auto MT) {
+            constexpr bool M = decltype(MT)::value;
+            if (fmt == HVS_FMT_I8X16)
+                hipLaunchKernelGGL((hvs_k_rescore<true, M>), dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream,
+                                   c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters, c->d_live);
+            else
+                hipLaunchKernelGGL((hvs_k_rescore<false, M>), dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream,
+                                   c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters, c->d_live);
+        });
         launch_merge(last == L.K, last + 1u);
     }
     // queries this batch could not answer go on the call's lists (retry with a proven threshold / exact engine); they
@@ -1488,11 +1593,26 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
         int rc = resolve_overflow(c);  // an earlier call whose results were never fetched
         if (rc) return rc;
     }
-    const uint32_t sn = sample_rows(sample_proportion, c->n);
+    uint32_t sn = sample_rows(sample_proportion, c->n);
+    uint32_t sampled = sn, of_rows = c->n;  // rows searched / rows there are (live ones under a mask)
+    if (c->n_dead) {
+        // live-row mask: the rows searched are the first sn_live live rows = "id < cut and live" (hvs_mask_plan); `sn` is the
+        // cut id from here on -- what every kernel's sampled-prefix test compares against
+        if (!c->cut_valid || std::memcmp(&c->cut_sp, &sample_proportion, sizeof(float)) != 0) {
+            uint32_t n_live = 0;
+            hvs_mask_plan(c->h_live.data(), c->n, c->k, sample_proportion, &n_live, &c->cut_id, nullptr);
+            c->cut_sn_live = sample_rows(sample_proportion, n_live);
+            c->cut_sp = sample_proportion;
+            c->cut_valid = true;
+        }
+        of_rows = c->n - c->n_dead;
+        sampled = c->cut_sn_live;
+        sn = sampled ? c->cut_id : 0u;
+    }
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
     // the exact engine answers.
-    bool mfma = c->have_index && sn >= c->n / 4u && sn > 0u && !c->scalar_order &&
+    bool mfma = c->have_index && sampled >= of_rows / 4u && sampled > 0u && !c->scalar_order &&
                 (c->engine == HVS_ENGINE_MFMA_FILTER || c->engine == HVS_ENGINE_MFMA_I8 || c->engine == HVS_ENGINE_MFMA_F16 ||
                  (c->engine == HVS_ENGINE_AUTO && c->n >= kMfmaMinRows && c->planned_fmt != HVS_FMT_NONE));
     if (mfma) {
@@ -1687,7 +1807,8 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
-                    c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list};
+                    c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->d_live, c->d_pad_ids, c->d_mask_ids,
+                    c->d_mask_stat, c->d_lp_ct, c->d_lp_t};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     free_index(c);
@@ -1787,6 +1908,14 @@ int begin_data(hvs_ctx* c, uint32_t n)
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = 0;
+    // a new data set starts with every row live
+    c->h_live.clear();
+    c->n_dead = 0;
+    c->cut_valid = false;
+    c->lp_valid = false;
+    if ((rc = dev_alloc(c, &c->d_live, (size_t)0))) return rc;
+    if ((rc = dev_alloc(c, &c->d_lp_ct, (size_t)0))) return rc;
+    if ((rc = dev_alloc(c, &c->d_lp_t, (size_t)0))) return rc;
     return dev_alloc(c, &c->d_data, (size_t)n * HVS_DCOLS);
 }
 
@@ -2274,6 +2403,103 @@ int leaf_last_timing(hvs_ctx* c, hvs_timing* out)
 }
 
 // ---------------------------------------------------------------------------------------------
+// live-row mask
+// ---------------------------------------------------------------------------------------------
+std::vector<uint64_t> all_live_words(uint32_t n)
+{
+    std::vector<uint64_t> w(((size_t)n + 63u) / 64u, ~0ull);
+    if (n & 63u) w.back() = (1ull << (n & 63u)) - 1ull;
+    return w;
+}
+
+// the device table of the k padding ids (the last k live rows, descending): after every mask or k change
+int refresh_pad_ids(hvs_ctx* c)
+{
+    if (!c->d_pad_ids || c->h_live.empty()) return HVS_OK;
+    uint32_t pad[HVS_KMAX];
+    hvs_mask_plan(c->h_live.data(), c->n, c->k, 1.0f, nullptr, nullptr, pad);
+    HVS_HIP(c, hipMemcpyAsync(c->d_pad_ids, pad, (size_t)c->k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`pad` is on this stack)
+    return HVS_OK;
+}
+
+// Install `words` (ceil(n / 64) words, bits past n clear, n_live bits set: checked by the caller) as the context's mask.
+// `del_ids` (host, ids < n): the new mask is the old one less these rows -- applied on the device by hvs_k_mask_delete
+// instead of a whole-mask upload.  Tiles: rows that died are patched; a mask that revives rows rebuilds the tiles through
+// build_tiles, which patches at its end.
+int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_live, const uint32_t* del_ids, uint32_t del_count)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);  // an earlier call's re-runs belong to the mask they were asked under
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = words.size() * sizeof(uint64_t);
+    if (!c->d_pad_ids && (rc = dev_alloc(c, &c->d_pad_ids, (size_t)HVS_KMAX))) return rc;
+    if (!c->d_mask_stat) {
+        if ((rc = dev_alloc(c, &c->d_mask_stat, (size_t)2))) return rc;
+        HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    }
+    if (c->h_live.empty()) c->h_live = all_live_words(c->n);
+    bool fresh = false;
+    if (!c->d_live) {
+        if ((rc = dev_alloc(c, &c->d_live, words.size() * 2u))) return rc;
+        fresh = true;
+    }
+    bool revived = false;
+    for (size_t i = 0; i < words.size(); ++i) revived = revived || (words[i] & ~c->h_live[i]) != 0ull;
+    if (del_ids) {
+        if (fresh) HVS_HIP(c, hipMemcpyAsync(c->d_live, c->h_live.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        if (del_count > c->mask_ids_cap) {
+            c->mask_ids_cap = 0;
+            if ((rc = dev_alloc(c, &c->d_mask_ids, (size_t)del_count))) return rc;
+            c->mask_ids_cap = del_count;
+        }
+        HVS_HIP(c, hipMemcpyAsync(c->d_mask_ids, del_ids, (size_t)del_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(hvs_k_mask_delete, dim3(hvs_ceil_div(del_count, 256u)), dim3(256), 0, c->stream, c->d_mask_ids, del_count, c->d_live);
+        HVS_HIP(c, hipGetLastError());
+    } else {
+        HVS_HIP(c, hipMemcpyAsync(c->d_live, words.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the sources are the caller's)
+    c->h_live = words;
+    c->n_dead = c->n - n_live;
+    c->cut_valid = false;
+    c->lp_valid = false;
+    if (c->have_index && c->tile_fmt != HVS_FMT_NONE) {
+        if (revived) {
+            const int fmt = c->tile_fmt;
+            if ((rc = build_tiles(c, fmt))) return rc;
+            if (!c->have_index) c->have_index = true;  // (cannot happen for a format that was usable: orderings only then)
+        } else if ((rc = patch_tiles(c))) {
+            return rc;
+        }
+    }
+    if ((rc = refresh_pad_ids(c))) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return HVS_OK;
+}
+
+int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
+{
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    out->n_live = c->n - c->n_dead;
+    out->n_dead = c->n_dead;
+    out->tiles_patched = 0;
+    out->dead_survivors = 0;
+    unsigned long long v = 0;
+    if (c->d_mask_stat) {
+        HVS_HIP(c, hipMemcpy(&v, c->d_mask_stat, sizeof(v), hipMemcpyDeviceToHost));
+        out->tiles_patched = v;
+    }
+    if (c->timing_valid) {
+        HVS_HIP(c, hipMemcpy(&v, c->d_counters + 8, sizeof(v), hipMemcpyDeviceToHost));
+        out->dead_survivors = v;
+    }
+    return HVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // multi-GPU root
 // ---------------------------------------------------------------------------------------------
 // contiguous, balanced range of part r of `world` (the first total % world parts get one more): sharding.shard_range
@@ -2536,7 +2762,7 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
         if (!rc) c->k = k;
         return rc;
     }
-    if (c->n && c->n < k) return fail(c, HVS_EINVAL, "hvs_set_k: the loaded data set has fewer than k rows");
+    if (c->n && c->n - c->n_dead < k) return fail(c, HVS_EINVAL, "hvs_set_k: the loaded data set has fewer than k (live) rows");
     if (k == c->k) return HVS_OK;
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
@@ -2549,6 +2775,8 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
     c->res_cap = 0;
     c->cand_lists = 0;
     c->timing_valid = false;
+    c->cut_valid = false;
+    if ((rc = refresh_pad_ids(c))) return rc;
     return had ? ensure_results(c, had) : HVS_OK;
 }
 
@@ -2869,6 +3097,128 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
     }
     if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
     agg.host_ms = c->host_ms;
+    *out = agg;
+    return HVS_OK;
+}
+
+// ---- live-row mask ---------------------------------------------------------------------------
+
+void hvs_mask_plan(const uint64_t* live_bits, uint32_t n, uint32_t k, float sample_proportion, uint32_t* n_live, uint32_t* cut,
+                   uint32_t* pad_ids)
+{
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) / 64u);
+    auto word = [&](uint32_t w) -> uint64_t {
+        uint64_t v = live_bits ? live_bits[w] : ~0ull;
+        if (w == words - 1u && (n & 63u)) v &= (1ull << (n & 63u)) - 1ull;
+        return v;
+    };
+    uint32_t nl = n;
+    if (live_bits) {
+        nl = 0;
+        for (uint32_t w = 0; w < words; ++w) nl += (uint32_t)__builtin_popcountll(word(w));
+    }
+    if (n_live) *n_live = nl;
+    if (cut) {
+        const uint32_t sn_live = sample_rows(sample_proportion, nl);
+        *cut = n;  // sn_live == n_live: no row is cut off
+        if (sn_live < nl) {
+            uint32_t seen = 0;  // the id of live row number sn_live (counting from 0)
+            for (uint32_t w = 0; w < words; ++w) {
+                uint64_t v = word(w);
+                const uint32_t pc = (uint32_t)__builtin_popcountll(v);
+                if (seen + pc <= sn_live) {
+                    seen += pc;
+                    continue;
+                }
+                for (; seen < sn_live; ++seen) v &= v - 1ull;
+                *cut = w * 64u + (uint32_t)__builtin_ctzll(v);
+                break;
+            }
+        }
+    }
+    if (pad_ids) {
+        uint32_t have = 0;
+        for (uint32_t w = words; w > 0u && have < k; --w) {
+            uint64_t v = word(w - 1u);
+            while (v && have < k) {
+                const uint32_t b = 63u - (uint32_t)__builtin_clzll(v);
+                pad_ids[have++] = (w - 1u) * 64u + b;
+                v &= ~(1ull << b);
+            }
+        }
+        for (; have < k; ++have) pad_ids[have] = 0xFFFFFFFFu;  // fewer than k live rows (no context accepts such a mask)
+    }
+}
+
+static hvs_ctx* mask_leaf(hvs_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
+
+static int apply_mask_everywhere(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_live, const uint32_t* del_ids,
+                                 uint32_t del_count)
+{
+    if (c->kids.empty()) return leaf_apply_mask(c, words, n_live, del_ids, del_count);
+    return for_each_leaf(c, [&](uint32_t r) { return leaf_apply_mask(c->kids[r], words, n_live, del_ids, del_count); });
+}
+
+int hvs_set_row_mask(hvs_ctx* c, const uint64_t* live_bits)
+{
+    if (!c) return HVS_EINVAL;
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_set_row_mask: no data set loaded");
+    std::vector<uint64_t> words = all_live_words(L->n);
+    if (live_bits)
+        for (size_t i = 0; i < words.size(); ++i) words[i] &= live_bits[i];
+    uint32_t n_live = 0;
+    for (uint64_t w : words) n_live += (uint32_t)__builtin_popcountll(w);
+    if (n_live < L->k) return fail(c, HVS_EINVAL, "hvs_set_row_mask: the mask leaves fewer than k live rows");
+    return apply_mask_everywhere(c, words, n_live, nullptr, 0u);
+}
+
+int hvs_delete_rows(hvs_ctx* c, const uint32_t* ids, uint32_t count)
+{
+    if (!c) return HVS_EINVAL;
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_delete_rows: no data set loaded");
+    if (count && !ids) return fail(c, HVS_EINVAL, "hvs_delete_rows: ids is NULL");
+    for (uint32_t i = 0; i < count; ++i)
+        if (ids[i] >= L->n) return fail(c, HVS_EINVAL, "hvs_delete_rows: id outside [0, n)");
+    if (!count) return HVS_OK;
+    std::vector<uint64_t> words = L->h_live.empty() ? all_live_words(L->n) : L->h_live;
+    for (uint32_t i = 0; i < count; ++i) words[ids[i] >> 6] &= ~(1ull << (ids[i] & 63u));
+    uint32_t n_live = 0;
+    for (uint64_t w : words) n_live += (uint32_t)__builtin_popcountll(w);
+    if (n_live < L->k) return fail(c, HVS_EINVAL, "hvs_delete_rows: fewer than k live rows would be left");
+    return apply_mask_everywhere(c, words, n_live, ids, count);
+}
+
+int hvs_get_row_mask(hvs_ctx* c, uint64_t* live_bits)
+{
+    if (!c || !live_bits) return HVS_EINVAL;
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_get_row_mask: no data set loaded");
+    const std::vector<uint64_t> words = L->h_live.empty() ? all_live_words(L->n) : L->h_live;
+    std::memcpy(live_bits, words.data(), words.size() * sizeof(uint64_t));
+    return HVS_OK;
+}
+
+uint32_t hvs_num_live_rows(const hvs_ctx* c)
+{
+    if (!c) return 0u;
+    const hvs_ctx* L = c->kids.empty() ? c : c->kids[0];
+    return L->n - L->n_dead;
+}
+
+int hvs_mask_stats(hvs_ctx* c, hvs_mask_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_mask_stats(c, out);
+    hvs_mask_info agg{};
+    for (size_t r = 0; r < c->kids.size(); ++r) {
+        hvs_mask_info m{};
+        const int rc = leaf_mask_stats(c->kids[r], &m);
+        if (rc) return fail(c, rc, c->kids[r]->err);
+        if (r == 0u) agg = m;  // (the mask and the tiles are replicated: one GPU's view)
+        else agg.dead_survivors += m.dead_survivors;  // a work counter of the call, summed like hvs_timing's
+    }
     *out = agg;
     return HVS_OK;
 }

@@ -742,6 +742,42 @@ __global__ __launch_bounds__(256) void hvs_k_build_tiles(const float* __restrict
     }
 }
 
+// hvs_k_patch_tiles -- tombstones (live-row mask).  One wave per storage block of one ordering, lane = (row, half)
+// as in hvs_k_build_tiles: pos -> perm[pos] -> dead?  A dead row's tile entry is overwritten with the encoding of a padding row,
+// which can never reach a finite threshold: the accumulator init HVS_I8_PAD_NORM in the INT8 formats; in the 16-bit float
+// formats the whole row image (components zero, h0 = the padding bias, h1 = h2 = 0) -- a dead row's own components would
+// otherwise add q.d to the bias.  Idempotent; rows only ever go from live to patched (a mask that revives rows rebuilds the
+// tiles first).  `patched` counts the rows that carry the encoding after the pass.  A performance measure only: the exact
+// stages test the mask themselves.
+__global__ __launch_bounds__(256) void hvs_k_patch_tiles(const uint32_t* __restrict__ live, const uint32_t* __restrict__ perm,
+                                                         uint32_t n, HvsLevels L, const uint32_t* __restrict__ blockpos,
+                                                         uint4* __restrict__ tiles, int* __restrict__ norms, int fmt,
+                                                         unsigned long long* __restrict__ patched)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t idx = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (idx >= L.nblk) return;
+    const uint32_t b = blockpos[idx];
+    const uint32_t r = lane & 31u, h = lane >> 5;
+    const uint32_t pos = b * 32u + r;
+    const bool dead = pos < n && !hvs_row_live(live, perm[pos]);
+    const uint64_t dm = __ballot(dead && h == 0u);
+    if (dm == 0ull) return;  // wave-uniform
+    if (lane == 0u) atomicAdd(patched, (unsigned long long)__popcll(dm));
+    if (!dead) return;
+    if (fmt == HVS_FMT_I8X16) {
+        if (h == 0u) norms[(size_t)idx * 32u + r] = HVS_I8_PAD_NORM;
+    } else if (fmt == HVS_FMT_I8) {
+        if (h == 0u) norms[(size_t)idx * 64u + 32u + r] = HVS_I8_PAD_NORM;
+    } else {
+        // element k = 16 s + 8 h + 2 p + e of the row: k = 100 (s = 6, h = 0, p = 2, e = 0) holds h0
+        const uint32_t h0 = hvs_h16_bits(fmt, fmt == HVS_FMT_F16 ? -65504.0f : -1.0e30f);
+#pragma unroll
+        for (int s = 0; s < HVS_KSTEPS; ++s)
+            tiles[((size_t)idx * HVS_KSTEPS + s) * 64u + lane] = make_uint4(0u, 0u, (s == 6 && h == 0u) ? h0 : 0u, 0u);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Per-batch query state (structure of arrays over PADDED SLOTS; slot = block*32 + i)
 // ---------------------------------------------------------------------------------------------
@@ -1249,14 +1285,16 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 #define HVS_PRAGMA_(x) _Pragma(#x)
 #define HVS_PRAGMA(x) HVS_PRAGMA_(x)
 
-template <int CAP>
+// MASKED (live-row mask, hvs_kernels.h): dead rows are dropped beside the sampled-prefix test; `sn` is the cut id then
+template <int CAP, bool MASKED>
 __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restrict__ D, uint32_t n, uint32_t sn,
                                                            const float* __restrict__ Q, HvsBatch B,
                                                            const uint32_t* __restrict__ perm_ct,
                                                            const uint32_t* __restrict__ perm_t,
                                                            const uint32_t* __restrict__ bpos_ct,
                                                            const uint32_t* __restrict__ bpos_t, HvsLevels L,
-                                                           unsigned long long* __restrict__ counters, uint32_t nchunks)
+                                                           unsigned long long* __restrict__ counters, uint32_t nchunks,
+                                                           const uint32_t* __restrict__ live)
 {
     __shared__ float4 srow[4][HVS_SEED_STAGE][26];  // per wave: 16 data rows as 16-byte aligned images x0..x99 (+ pad)
     // nchunks > 1 (small batches, level 0 of at most 1024 rows): grid.y waves share one 64-slot group, each
@@ -1294,11 +1332,16 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
         uint32_t kk = 0, kend = 0;  // chunked form: this lane's places [kk, kend) in its slot's list for the block's rows
         if (nchunks > 1u) {         // wave-uniform
             // ONE atomic per lane and block instead of one per row and lane: the rows of the block a lane takes are its
-            // range cut to the block, less those outside the sampled prefix
+            // range cut to the block, less those outside the sampled prefix (and, MASKED, the dead ones)
             const uint32_t p0 = b * 32u, p1 = (p0 + 32u < n) ? p0 + 32u : n;
             const uint32_t a = ra > p0 ? ra : p0, e = rb < p1 ? rb : p1;
             uint32_t mine = a < e ? e - a : 0u;
-            if (sn < n) {
+            if constexpr (MASKED) {
+                for (uint32_t pos = p0; pos < p1; ++pos) {
+                    const uint32_t idp = perm[pos];  // wave-uniform (scalar) loads, the mask word included
+                    if ((idp >= sn || !hvs_row_live(live, idp)) && pos >= ra && pos < rb) --mine;
+                }
+            } else if (sn < n) {
                 for (uint32_t pos = p0; pos < p1; ++pos)
                     if (perm[pos] >= sn && pos >= ra && pos < rb) --mine;  // perm[pos]: wave-uniform (scalar) load
             }
@@ -1343,6 +1386,9 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
             if (__ballot(pass) == 0ull) continue;
             const uint32_t id = perm[pos];
             if (id >= sn) continue;  // sampled prefix: rows [0, sn) of the original order only
+            if constexpr (MASKED) {
+                if (!hvs_row_live(live, id)) continue;  // (wave-uniform)
+            }
             nscan += 64u;
             const float dist = hvs_exact_dist_pk_lds(&srow[threadIdx.x >> 6][r & (HVS_SEED_STAGE - 1u)][0], q2);
             if (nchunks > 1u) {  // wave-uniform
@@ -1389,14 +1435,15 @@ struct HvsUniformRowF2 {
     __device__ __forceinline__ hvs_f2 operator[](int i) const { return p[i]; }
 };
 
-template <bool SCALAR_ORDER, int CAP>
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
 __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restrict__ D, uint32_t sn,
                                                             const float* __restrict__ Q, HvsBatch B,
                                                             const uint32_t* __restrict__ perm_ct,
                                                             const uint32_t* __restrict__ perm_t, uint32_t nchunks,
                                                             uint32_t slot_begin, uint32_t slot_end, uint64_t* __restrict__ cand,
                                                             uint32_t* __restrict__ cand_cnt,
-                                                            unsigned long long* __restrict__ counters)
+                                                            unsigned long long* __restrict__ counters,
+                                                            const uint32_t* __restrict__ live)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -1442,6 +1489,9 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         if (__ballot(pass) == 0ull) continue;
         const uint32_t id = perm[pos];
         if (id >= sn) continue;  // sampled prefix: rows [0, sn) of the original order only
+        if constexpr (MASKED) {
+            if (!hvs_row_live(live, id)) continue;  // (wave-uniform)
+        }
         nscan += 64u;
         const float* __restrict__ row = D + (size_t)id * HVS_DCOLS + 2;
         float dist;
@@ -1478,16 +1528,51 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
 }
 
 // passing pairs of a sampled prefix (sn < n): the position range over-counts, so count ids < sn exactly
+// (MASKED: live ids below the cut)
+template <bool MASKED>
 __global__ void hvs_k_count_prefix_pairs(HvsBatch B, const uint32_t* __restrict__ perm_ct, const uint32_t* __restrict__ perm_t,
-                                         uint32_t sn, unsigned long long* __restrict__ counters)
+                                         uint32_t sn, unsigned long long* __restrict__ counters, const uint32_t* __restrict__ live)
 {
     const uint32_t slot = blockIdx.x;
     if (B.qid[slot] == 0xFFFFFFFFu) return;
     const uint32_t* __restrict__ perm = B.gord[slot / HVS_GROUP] ? perm_t : perm_ct;
     uint32_t c = 0;
-    for (uint32_t pos = B.ra[slot] + threadIdx.x; pos < B.rb[slot]; pos += blockDim.x) c += perm[pos] < sn ? 1u : 0u;
+    for (uint32_t pos = B.ra[slot] + threadIdx.x; pos < B.rb[slot]; pos += blockDim.x) {
+        const uint32_t id = perm[pos];
+        if constexpr (MASKED)
+            c += (id < sn && hvs_row_live(live, id)) ? 1u : 0u;
+        else
+            c += id < sn ? 1u : 0u;
+    }
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63u) == 0u && c) atomicAdd(&counters[0], (unsigned long long)c);
+}
+
+// Live-row mask without a sampled prefix (cut = n): the live rows of a position range come from a prefix count over the
+// ordering, lp[pos] = live rows among positions [0, pos) (n + 1 entries per ordering, rebuilt after a mask change: this
+// kernel writes the flags, an exclusive scan turns them into counts) -- walking 10^7 positions per type-0 query to count
+// them (the kernel above) cost 35x the whole filter engine at 2.6 x 10^5 queries.
+__global__ void hvs_k_live_flags(const uint32_t* __restrict__ live, const uint32_t* __restrict__ perm, uint32_t n,
+                                 uint32_t* __restrict__ out)
+{
+    const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos > n) return;
+    out[pos] = (pos < n && hvs_row_live(live, perm[pos])) ? 1u : 0u;
+}
+
+__global__ void hvs_k_count_live_pairs(HvsBatch B, const uint32_t* __restrict__ lp_ct, const uint32_t* __restrict__ lp_t,
+                                       unsigned long long* __restrict__ counters)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = 0;
+    if (slot < B.nslots && B.qid[slot] != 0xFFFFFFFFu) {
+        const uint32_t* __restrict__ lp = B.gord[slot / HVS_GROUP] ? lp_t : lp_ct;
+        const uint32_t a = B.ra[slot], b = B.rb[slot];
+        if (b > a) c = lp[b] - lp[a];
+    }
+    unsigned long long s = c;
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(&counters[0], s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2452,11 +2537,14 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 // the vector and load instructions per pair.)
 // ---------------------------------------------------------------------------------------------
 // E16: entries of the 16x16 tile format (hvs_entry16_*) instead of the 32x32 formats' (hvs_entry_*)
-template <bool E16>
+// MASKED (live-row mask): a survivor whose row is dead is dropped beside the sampled-prefix test and counted in counters[8]
+// (hvs_mask_info.dead_survivors) -- the test that keeps dead rows out of every answer, whatever the tiles say
+template <bool E16, bool MASKED>
 __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const float* __restrict__ D, uint32_t n, uint32_t sn, const float* __restrict__ Q,
                                                      HvsBatch B, const uint32_t* __restrict__ perm_ct,
                                                      const uint32_t* __restrict__ perm_t,
-                                                     unsigned long long* __restrict__ counters)
+                                                     unsigned long long* __restrict__ counters,
+                                                     const uint32_t* __restrict__ live)
 {
     // the group's 128 query vectors are staged in LDS once per block (51 KB)
     __shared__ float sq[HVS_GROUP][HVS_NDIM];
@@ -2482,6 +2570,7 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     uint64_t* list = slist[w];
     uint32_t npairs = 0;  // wave-uniform
+    uint32_t ndead = 0;   // (MASKED) per lane: pairs dropped because the row is dead
     auto emask = [](uint64_t e) -> uint32_t { return E16 ? hvs_entry16_mask(e) : hvs_entry_mask(e); };
     auto epos = [](uint64_t e, uint32_t r) -> uint32_t { return E16 ? hvs_entry16_pos(e, r) : hvs_entry_pos(e, r); };
 
@@ -2529,6 +2618,11 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
                 id[u] = (uint32_t)pr;
                 // sampled prefix (sample_proportion < 1): the filter does not know about it
                 ok[u] = pi < cnt && id[u] < sn;
+                if constexpr (MASKED) {
+                    const bool dead = pi < cnt && !hvs_row_live(live, id[u]);
+                    ndead += (dead && t4 == 0u) ? 1u : 0u;
+                    ok[u] = ok[u] && !dead;
+                }
             }
     #pragma unroll
             for (int u = 0; u < kUn; ++u) {
@@ -2622,6 +2716,11 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
     }
     retire();
     if (lane == 0u && npairs) atomicAdd(&counters[2], (unsigned long long)npairs);
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ndead += __shfl_xor(ndead, o);
+        if (lane == 0u && ndead) atomicAdd(&counters[8], (unsigned long long)ndead);
+    }
 }
 
 // Order statistic of a guessed threshold as a function of the fraction F of the query's rows seen so far (host:
@@ -2728,12 +2827,13 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 #define HVS_MUT_SCALE ((double)(HVS_MUTANT_BAND_SCALE))
 #define HVS_MUT_TERM(bit, x) (((HVS_MUTANT_DROP) & (bit)) ? 0.0 : (x))
 #endif
-template <bool FINAL, int CAP>
+// MASKED (FINAL only, live-row mask): the padding ids come from `pad_ids`, the last k live rows in descending order
+template <bool FINAL, int CAP, bool MASKED>
 __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, uint32_t n, const float* __restrict__ Q,
                                                    HvsBatch B, const HvsBounds* __restrict__ bounds, int pad,
                                                    uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, int fmt,
                                                    const HvsQuant* __restrict__ qz, HvsLevels L, uint32_t level_next,
-                                                   HvsGuessTable G)
+                                                   HvsGuessTable G, const uint32_t* __restrict__ pad_ids)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -2863,7 +2963,8 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
     for (uint32_t base = cnt; base < knn; base += 64u) {
         const uint32_t e = base + lane;
         if (e < knn) {
-            const uint32_t id = n - 1u - (e - cnt);
+            uint32_t id = n - 1u - (e - cnt);
+            if constexpr (MASKED) id = pad_ids[e - cnt];
             const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
             // padding off (partial answers of a data shard): empty slots hold the largest key
             buf[e] = pad ? hvs_make_key(hvs_exact_dist(dv, qv), id) : ~0ull;

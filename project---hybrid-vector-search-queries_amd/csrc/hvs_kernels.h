@@ -8,6 +8,25 @@
 // CAP = 512 (k <= 256); k itself is a run-time argument
 
 // ---------------------------------------------------------------------------------------------
+// Live-row mask (hvs_set_row_mask / hvs_delete_rows): one bit per row in u32 words, bit id & 31 of word
+// id >> 5 set = row id is live.  Kernels that honour it are the MASKED = true instantiations of the exact-order kernels; the
+// host launches them only while at least one row is dead, so a context without dead rows runs the code it always ran.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool hvs_row_live(const uint32_t* __restrict__ live, uint32_t id)
+{
+    return ((live[id >> 5] >> (id & 31u)) & 1u) != 0u;
+}
+
+// hvs_delete_rows: clear the bits of an id list (ids < n, checked by the host; duplicates are fine)
+__global__ void hvs_k_mask_delete(const uint32_t* __restrict__ ids, uint32_t count, uint32_t* __restrict__ live)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t id = ids[i];
+    atomicAnd(&live[id >> 5], ~(1u << (id & 31u)));
+}
+
+// ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------
 __global__ void hvs_k_gen_data(float* __restrict__ out, uint64_t nelem, uint64_t seed, int profile, uint32_t ncat)
@@ -164,11 +183,13 @@ struct HvsLdsRow1 {
 #endif
 // SCALAR_ORDER = false: the hot path's SIMD summation order (optimized_impl.h:96-125);
 // SCALAR_ORDER = true : the baseline engine's sequential order (baseline.hpp:53-64), BASELINE.json configs[0].
-template <bool SCALAR_ORDER, int CAP>
+// MASKED: rows whose bit in `live` is clear are skipped (the row is wave-uniform: one scalar load and branch per row);
+// `sn` is then the cut id of the sampled live prefix (hvs_mask_plan)
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
 __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
     uint32_t nq_pad, uint32_t sn, uint32_t rows_per_chunk, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt,
-    unsigned long long* __restrict__ counters, uint32_t knn)
+    unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live)
 {
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     const uint32_t lane = threadIdx.x & 63u;
@@ -247,6 +268,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
         if (wave_active) {
             const uint32_t nrow = (r1 - j0) < HVS_LDS_ROWS ? (r1 - j0) : HVS_LDS_ROWS;
             for (uint32_t r = 0; r < nrow; ++r) {
+                if constexpr (MASKED) {
+                    if (!hvs_row_live(live, j0 + r)) continue;  // (wave-uniform)
+                }
                 const float4* rowp = &srow[buf][r * (HVS_LDS_ROW_F / 4)];
                 bool pass;
                 if (wave_all0) {  // (wave-uniform) a wave of pure k-NN queries takes every row: no attribute read, no predicate
@@ -309,11 +333,13 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
 // emit ids in ascending (dist, id) order (get_knn_sorted, optimized_impl.h:392-415).
 // One wave per query, 4 queries per 256-thread block, a 256-key LDS buffer per wave.
 // ---------------------------------------------------------------------------------------------
-template <bool SCALAR_ORDER, int CAP>
+// MASKED: the padding ids come from `pad_ids` (the last k live rows, descending) instead of n - 1, n - 2, ...
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
 __global__ __launch_bounds__(256) void hvs_k_select(
     const float* __restrict__ D, uint32_t n, const float* __restrict__ Q, const uint32_t* __restrict__ qorder,
     uint32_t nq, uint32_t nq_pad, uint32_t nchunks, const uint64_t* __restrict__ cand,
-    const uint32_t* __restrict__ cand_cnt, int pad, uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn)
+    const uint32_t* __restrict__ cand_cnt, int pad, uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+    const uint32_t* __restrict__ pad_ids)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -352,7 +378,8 @@ __global__ __launch_bounds__(256) void hvs_k_select(
     for (uint32_t base = cnt; base < knn; base += 64u) {
         const uint32_t e = base + lane;
         if (e < knn) {
-            const uint32_t id = n - 1u - (e - cnt);
+            uint32_t id = n - 1u - (e - cnt);
+            if constexpr (MASKED) id = pad_ids[e - cnt];
             const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
             buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id) : ~0ull;
         }

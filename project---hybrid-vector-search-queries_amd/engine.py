@@ -37,6 +37,14 @@ class Timing(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class MaskInfo(C.Structure):
+    """hvs_mask_info (include/hvs.h)."""
+    _fields_ = [("n_live", C.c_uint32), ("n_dead", C.c_uint32), ("tiles_patched", C.c_uint64), ("dead_survivors", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -107,7 +115,7 @@ def exported_symbols():
 
 
 _lib = None
-_f32p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+_f32p, _u32p, _u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 
 
 def library():
@@ -155,6 +163,12 @@ def library():
         "hvs_version": (C.c_char_p, []),
         "hvs_plan_guess_m": (C.c_uint32, [C.c_uint32, C.c_double, C.c_uint32]),
         "hvs_plan_batches": (C.c_uint32, [C.c_uint32, C.c_int, _u32p, C.c_uint32]),
+        "hvs_delete_rows": (C.c_int, [vp, _u32p, C.c_uint32]),
+        "hvs_set_row_mask": (C.c_int, [vp, _u64p]),
+        "hvs_get_row_mask": (C.c_int, [vp, _u64p]),
+        "hvs_num_live_rows": (C.c_uint32, [vp]),
+        "hvs_mask_stats": (C.c_int, [vp, C.POINTER(MaskInfo)]),
+        "hvs_mask_plan": (None, [_u64p, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -169,6 +183,34 @@ def _fp(a):
 
 def _up(a):
     return a.ctypes.data_as(_u32p)
+
+
+def pack_row_mask(live):
+    """bool array of n rows -> the ceil(n / 64) uint64 words of hvs_set_row_mask (bit i & 63 of word i >> 6 = row i)."""
+    live = np.ascontiguousarray(live, dtype=bool).ravel()
+    bits = np.zeros(((live.size + 63) // 64) * 64, np.uint8)
+    bits[:live.size] = live
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u8").astype(np.uint64))
+
+
+def unpack_row_mask(words, n):
+    """The inverse of pack_row_mask."""
+    words = np.ascontiguousarray(words, "<u8")
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def mask_plan(live, k, sample_proportion):
+    """hvs_mask_plan on a bool array (or None = all live, then `live` must be the row count): (n_live, cut, pad_ids)."""
+    if isinstance(live, (int, np.integer)):
+        n, words = int(live), None
+    else:
+        live = np.asarray(live, dtype=bool).ravel()
+        n, words = live.size, pack_row_mask(live)
+    n_live, cut = C.c_uint32(0), C.c_uint32(0)
+    pad = np.empty(int(k), np.uint32)
+    library().hvs_mask_plan(words.ctypes.data_as(_u64p) if words is not None else None, n, int(k), float(sample_proportion),
+                            C.byref(n_live), C.byref(cut), _up(pad))
+    return int(n_live.value), int(cut.value), pad
 
 
 class Engine:
@@ -256,6 +298,39 @@ class Engine:
     @property
     def n(self):
         return int(self._lib.hvs_num_rows(self._h))
+
+    # --- row deletion (the live-row mask; include/hvs.h "row deletion")
+    def delete_rows(self, ids):
+        """Mark rows as deleted: later answers are those of the data set without them, ids unchanged."""
+        ids = np.ascontiguousarray(np.asarray(ids).ravel(), np.uint32)
+        self._ck(self._lib.hvs_delete_rows(self._h, _up(ids), ids.size))
+
+    def set_row_mask(self, live):
+        """Replace the whole mask: `live` is a bool array of n rows (True = live) or None for "all rows live"."""
+        if live is None:
+            self._ck(self._lib.hvs_set_row_mask(self._h, None))
+            return
+        live = np.asarray(live, dtype=bool).ravel()
+        if live.size != self.n:
+            raise HvsError(-1, "the row mask must have one entry per row")
+        words = pack_row_mask(live)
+        self._ck(self._lib.hvs_set_row_mask(self._h, words.ctypes.data_as(_u64p)))
+
+    def row_mask(self):
+        """The current mask as a bool array of n rows."""
+        n = self.n
+        words = np.zeros((n + 63) // 64, np.uint64)
+        self._ck(self._lib.hvs_get_row_mask(self._h, words.ctypes.data_as(_u64p)))
+        return unpack_row_mask(words, n)
+
+    @property
+    def n_live(self):
+        return int(self._lib.hvs_num_live_rows(self._h))
+
+    def mask_stats(self):
+        m = MaskInfo()
+        self._ck(self._lib.hvs_mask_stats(self._h, C.byref(m)))
+        return m
 
     # --- the vec_query seam
     def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None):
