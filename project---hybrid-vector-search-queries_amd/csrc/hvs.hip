@@ -31,6 +31,50 @@ thread_local std::string g_global_err;
 
 }  // namespace
 
+// The index's per-ordering buffers: rows sorted by (C,T) or by T alone
+struct HvsOrdering {
+    uint64_t* keys = nullptr;  // sorted attribute keys
+    uint32_t* perm = nullptr;  // position -> original row id
+    uint4* tiles = nullptr;    // A-operand tiles (16-bit or INT8), level-interleaved
+    uint4* nrm = nullptr;      // INT8 formats: the tiles' side data (accumulator inits; 32x32x32: + dims 96..99)
+    uint32_t* bpos = nullptr;  // storage index -> block
+    // (not part of the index: sized by n alone, kept across free_index and freed with the context)
+    uint32_t* lp = nullptr;    // live rows in front of each position (hvs_k_live_flags), [n + 1]
+};
+
+// What the host needs to know of a tile format (HVS_FMT_*), in one place
+typedef void (*HvsFilterKernel)(const uint4*, const uint4*, const uint4*, const uint4*, const uint32_t*, const uint32_t*, HvsLevels, uint32_t,
+                                HvsBatch, HvsItems, unsigned long long*);
+typedef void (*HvsBuildI8Kernel)(const float*, uint32_t, const uint32_t*, HvsLevels, const HvsQuant*, uint4*, int*, uint32_t*, HvsBounds*);
+struct HvsHostFmt {
+    size_t tile_u4, nrm_u4;     // uint4 per 32-row tile: operands, side data (0: none)
+    HvsBuildI8Kernel build_i8;  // the INT8 formats' builder (null: hvs_k_build_tiles, which takes the 16-bit format as an argument)
+    HvsFilterKernel filter;
+};
+static HvsHostFmt hvs_host_fmt(int fmt, bool rotated)
+{
+    switch (fmt) {
+    case HVS_FMT_I8X16:
+        return {HVS_I8X16_TILE_U4, HVS_I8X16_NRM_U4, rotated ? hvs_k_build_tiles_i8x16_rot : hvs_k_build_tiles_i8x16, hvs_k_filter_i8x16};
+    case HVS_FMT_I8: return {HVS_I8_TILE_U4, HVS_I8_NRM_U4, hvs_k_build_tiles_i8, hvs_k_filter_mfma<HVS_FMT_I8>};
+    case HVS_FMT_F16: return {HVS_TILE_U4, 0, nullptr, hvs_k_filter_mfma<HVS_FMT_F16>};
+    default: return {HVS_TILE_U4, 0, nullptr, hvs_k_filter_mfma<HVS_FMT_BF16>};
+    }
+}
+// The error bound needs finite row norms: data with inf/NaN components (or |d|^2 overflowing f32) is answered by the
+// exact engine only
+static bool hvs_bounds_usable(int fmt, const HvsBounds& hb)
+{
+    if (HVS_IS_I8(fmt)) return std::isfinite(hb.e_d8) && std::isfinite(hb.n_d8) && hb.n_d8 < 1.0e15f;
+    const bool finite = std::isfinite(hb.e_d) && std::isfinite(hb.nb_d) && std::isfinite(hb.hmax) && std::isfinite(hb.rho);
+    // FP16: every component and the three pieces of -|d|^2/2 inside the half-precision range (denormal flushing is part of
+    // the bound: HVS_F16_FLUSH)
+    if (fmt == HVS_FMT_F16) return finite && hb.hmax < 6.0e4f;
+    // (norms near the f32 denormal range: BF16 operands might be flushed by the matrix pipe, which the
+    // error bound does not model)
+    return finite && !(hb.hmax > 1.0e30f) && !(hb.hmax > 0.0f && hb.hmax < 1.0e-20f);
+}
+
 // Workspace of ONE query batch and the stream it runs on -- a "lane".  A context owns two (round 4): the last level of batch b
 // ends with its re-scoring (HBM-bound gathers) and the final merge (latency-bound), both of which leave the matrix pipes idle,
 // and batch b+1 begins with preparation, the exact seed and two small filter levels that cannot fill the chip; with batch
@@ -94,7 +138,6 @@ struct hvs_ctx : HvsLane {
     uint32_t* d_pad_ids = nullptr;  // the last k live ids in descending order (HVS_KMAX entries)
     uint32_t* d_mask_ids = nullptr; // id list of the running hvs_delete_rows
     uint32_t mask_ids_cap = 0;
-    uint32_t *d_lp_ct = nullptr, *d_lp_t = nullptr;  // live rows in front of each position of the two orderings (hvs_k_live_flags)
     bool lp_valid = false;
     unsigned long long* d_mask_stat = nullptr;  // [0]: rows whose tile entry carries the never-hit encoding, both orderings
     bool cut_valid = false;         // cut id of the sampled live prefix for sample_proportion cut_sp (hvs_mask_plan), cached
@@ -118,11 +161,7 @@ struct hvs_ctx : HvsLane {
     // ---- MFMA engine: index over D (two orderings) ...
     bool have_index = false;
     HvsLevels lv{};                       // same block count for both orderings
-    uint64_t *d_keys_ct = nullptr, *d_keys_t = nullptr;   // sorted attribute keys
-    uint32_t *d_perm_ct = nullptr, *d_perm_t = nullptr;   // position -> original row id
-    uint4 *d_tiles_ct = nullptr, *d_tiles_t = nullptr;    // A-operand tiles (BF16 or INT8), level-interleaved
-    uint4 *d_nrm_ct = nullptr, *d_nrm_t = nullptr;        // INT8 format: the rows' accumulator inits, [nblk][32] int32
-    uint32_t *d_bpos_ct = nullptr, *d_bpos_t = nullptr;   // storage index -> block
+    HvsOrdering ord[2];  // [0] the (C,T) ordering, [1] the T ordering
     HvsBounds* d_bounds = nullptr;
     HvsQuant* d_quant = nullptr;                          // INT8 format: centre and scale
     int tile_fmt = HVS_FMT_NONE;                          // format of the tiles currently built
@@ -383,6 +422,30 @@ void with_cap_mask(const hvs_ctx* c, F f)
     });
 }
 
+// ... and for the exact engine's kernels, which also exist for the two summation orders: `f` gets (scalar order, capacity,
+// masked)
+template <typename F>
+void with_order_cap_mask(const hvs_ctx* c, F f)
+{
+    with_cap_mask(c, [&](auto CAPT, auto MT) {
+        if (c->scalar_order)
+            f(std::true_type{}, CAPT, MT);
+        else
+            f(std::false_type{}, CAPT, MT);
+    });
+}
+
+// the k best of every query's candidate lists to the output rows (hvs_k_select): `nsel` queries named by `qlist`, each with
+// `nchunks` lists of which list 0 of the first query is `cand` / `cnt` and consecutive queries' lists lie `stride` apart
+void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t stride, uint32_t nchunks, uint64_t* cand, uint32_t* cnt)
+{
+    with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+        hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((nsel + 3u) / 4u), dim3(256), 0,
+                           c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids,
+                           c->d_out_dists, c->k, c->d_pad_ids);
+    });
+}
+
 // optimized_parallel.hpp:67: const uint32_t sn = uint32_t(sample_proportion * n);  (float product)
 uint32_t sample_rows(float sample_proportion, uint32_t n)
 {
@@ -490,30 +553,14 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
     if (sn > 0) {
         unsigned long long* stat = count_stats ? c->d_counters : c->d_counters + 4;
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
-        with_cap_mask(c, [&](auto CAPT, auto MT) {
-            constexpr int CAP = decltype(CAPT)::value;
-            constexpr bool M = decltype(MT)::value;
-            if (c->scalar_order)
-                hipLaunchKernelGGL((hvs_k_scan_exact_lds<true, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k, c->d_live);
-            else
-                hipLaunchKernelGGL((hvs_k_scan_exact_lds<false, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb,
-                                   p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k, c->d_live);
+        with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+            hipLaunchKernelGGL((hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0,
+                               c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k,
+                               c->d_live);
         });
     }
     kernel_timer_end(c, ev);
-    with_cap_mask(c, [&](auto CAPT, auto MT) {
-        constexpr int CAP = decltype(CAPT)::value;
-        constexpr bool M = decltype(MT)::value;
-        if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_select<true, CAP, M>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
-                               c->d_pad_ids);
-        else
-            hipLaunchKernelGGL((hvs_k_select<false, CAP, M>), dim3((nqb + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
-                               c->d_pad_ids);
-    });
+    launch_select(c, qorder, nqb, p.nq_pad, p.nchunks, c->d_cand, c->d_cand_cnt);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -523,15 +570,14 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
 // ---------------------------------------------------------------------------------------------
 void free_index(hvs_ctx* c)
 {
-    void* ptrs[] = {c->d_keys_ct, c->d_keys_t, c->d_perm_ct, c->d_perm_t, c->d_tiles_ct, c->d_tiles_t,
-                    c->d_nrm_ct,  c->d_nrm_t,  c->d_bpos_ct, c->d_bpos_t};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    c->d_keys_ct = c->d_keys_t = nullptr;
-    c->d_perm_ct = c->d_perm_t = nullptr;
-    c->d_tiles_ct = c->d_tiles_t = nullptr;
-    c->d_nrm_ct = c->d_nrm_t = nullptr;
-    c->d_bpos_ct = c->d_bpos_t = nullptr;
+    for (HvsOrdering& o : c->ord) {
+        void* ptrs[] = {o.keys, o.perm, o.tiles, o.nrm, o.bpos};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        uint32_t* lp = o.lp;  // (the live-row counts' buffer outlives the index)
+        o = HvsOrdering{};
+        o.lp = lp;
+    }
     c->have_index = false;
     c->lp_valid = false;  // (counts along the orderings that have just gone)
     c->tile_fmt = HVS_FMT_NONE;
@@ -641,18 +687,17 @@ int ensure_live_prefix(hvs_ctx* c)
     if (c->lp_valid) return HVS_OK;
     const uint32_t n = c->n;
     int rc;
-    if (!c->d_lp_ct && (rc = dev_alloc(c, &c->d_lp_ct, (size_t)n + 1u))) return rc;
-    if (!c->d_lp_t && (rc = dev_alloc(c, &c->d_lp_t, (size_t)n + 1u))) return rc;
+    for (HvsOrdering& o : c->ord)
+        if (!o.lp && (rc = dev_alloc(c, &o.lp, (size_t)n + 1u))) return rc;
     size_t tmp_bytes = 0;
-    HVS_HIP(c, rocprim::exclusive_scan(nullptr, tmp_bytes, c->d_lp_ct, c->d_lp_ct, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream));
+    HVS_HIP(c, rocprim::exclusive_scan(nullptr, tmp_bytes, c->ord[0].lp, c->ord[0].lp, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream));
     void* tmp = nullptr;
     HVS_HIP(c, hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
     hipError_t e = hipSuccess;
-    for (int ord = 0; ord < 2 && e == hipSuccess; ++ord) {
-        uint32_t* lp = ord ? c->d_lp_t : c->d_lp_ct;
-        hipLaunchKernelGGL(hvs_k_live_flags, dim3(hvs_ceil_div(n + 1u, 256u)), dim3(256), 0, c->stream, c->d_live, ord ? c->d_perm_t : c->d_perm_ct,
-                           n, lp);
-        e = rocprim::exclusive_scan(tmp, tmp_bytes, lp, lp, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream);
+    for (const HvsOrdering& o : c->ord) {
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(hvs_k_live_flags, dim3(hvs_ceil_div(n + 1u, 256u)), dim3(256), 0, c->stream, c->d_live, o.perm, n, o.lp);
+        e = rocprim::exclusive_scan(tmp, tmp_bytes, o.lp, o.lp, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(tmp);
@@ -668,10 +713,10 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
     if (sn == c->n) {
         int rc = ensure_live_prefix(c);
         if (rc) return rc;
-        hipLaunchKernelGGL(hvs_k_count_live_pairs, dim3(hvs_ceil_div(B.nslots, 256u)), dim3(256), 0, c->stream, B, c->d_lp_ct, c->d_lp_t,
+        hipLaunchKernelGGL(hvs_k_count_live_pairs, dim3(hvs_ceil_div(B.nslots, 256u)), dim3(256), 0, c->stream, B, c->ord[0].lp, c->ord[1].lp,
                            c->d_counters);
     } else {
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<true>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<true>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
                            c->d_counters, c->d_live);
     }
     return HVS_OK;
@@ -681,14 +726,13 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
 // every mask change that only kills rows and at the end of every tile build while rows are dead.
 int patch_tiles(hvs_ctx* c)
 {
-    if (!c->n_dead || c->tile_fmt == HVS_FMT_NONE || !c->d_tiles_ct || !c->d_live || !c->d_mask_stat) return HVS_OK;
+    if (!c->n_dead || c->tile_fmt == HVS_FMT_NONE || !c->ord[0].tiles || !c->d_live || !c->d_mask_stat) return HVS_OK;
     const HvsLevels L = c->lv;
     HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
-    hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, c->d_perm_ct, c->n, L, c->d_bpos_ct, c->d_tiles_ct,
-                       reinterpret_cast<int*>(c->d_nrm_ct), c->tile_fmt, c->d_mask_stat);
-    hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, c->d_perm_t, c->n, L, c->d_bpos_t, c->d_tiles_t,
-                       reinterpret_cast<int*>(c->d_nrm_t), c->tile_fmt, c->d_mask_stat);
+    for (const HvsOrdering& o : c->ord)
+        hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, o.perm, c->n, L, o.bpos, o.tiles,
+                           reinterpret_cast<int*>(o.nrm), c->tile_fmt, c->d_mask_stat);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -703,61 +747,30 @@ int build_tiles(hvs_ctx* c, int fmt)
     c->have_index = false;
     if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
     // free first: the two formats never coexist (D = 1e8: 44.8 GB of BF16 tiles, 20.8 GB of INT8 tiles)
-    if ((rc = dev_alloc(c, &c->d_tiles_ct, (size_t)0))) return rc;
-    if ((rc = dev_alloc(c, &c->d_tiles_t, (size_t)0))) return rc;
-    if ((rc = dev_alloc(c, &c->d_nrm_ct, (size_t)0))) return rc;
-    if ((rc = dev_alloc(c, &c->d_nrm_t, (size_t)0))) return rc;
-    const size_t tile_u4 = fmt == HVS_FMT_I8 ? HVS_I8_TILE_U4 : fmt == HVS_FMT_I8X16 ? HVS_I8X16_TILE_U4 : HVS_TILE_U4;
-    if ((rc = dev_alloc(c, &c->d_tiles_ct, (size_t)L.nblk * tile_u4))) return rc;
-    if ((rc = dev_alloc(c, &c->d_tiles_t, (size_t)L.nblk * tile_u4))) return rc;
-    if (HVS_IS_I8(fmt)) {
-        const size_t nrm_u4 = fmt == HVS_FMT_I8 ? HVS_I8_NRM_U4 : HVS_I8X16_NRM_U4;
-        if ((rc = dev_alloc(c, &c->d_nrm_ct, (size_t)L.nblk * nrm_u4))) return rc;
-        if ((rc = dev_alloc(c, &c->d_nrm_t, (size_t)L.nblk * nrm_u4))) return rc;
+    for (HvsOrdering& o : c->ord) {
+        if ((rc = dev_alloc(c, &o.tiles, (size_t)0))) return rc;
+        if ((rc = dev_alloc(c, &o.nrm, (size_t)0))) return rc;
     }
-    if (!c->d_bpos_ct && (rc = dev_alloc(c, &c->d_bpos_ct, (size_t)L.nblk))) return rc;
-    if (!c->d_bpos_t && (rc = dev_alloc(c, &c->d_bpos_t, (size_t)L.nblk))) return rc;
+    const HvsHostFmt F = hvs_host_fmt(fmt, c->i8_rot);
+    for (HvsOrdering& o : c->ord) {
+        if ((rc = dev_alloc(c, &o.tiles, (size_t)L.nblk * F.tile_u4))) return rc;
+        if (F.nrm_u4 && (rc = dev_alloc(c, &o.nrm, (size_t)L.nblk * F.nrm_u4))) return rc;
+        if (!o.bpos && (rc = dev_alloc(c, &o.bpos, (size_t)L.nblk))) return rc;
+    }
     HVS_HIP(c, hipMemsetAsync(c->d_bounds, 0, sizeof(HvsBounds), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
-    if (fmt == HVS_FMT_I8X16 && c->i8_rot) {
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8x16_rot, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_ct, L, c->d_quant,
-                           c->d_tiles_ct, reinterpret_cast<int*>(c->d_nrm_ct), c->d_bpos_ct, c->d_bounds);
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8x16_rot, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_t, L, c->d_quant,
-                           c->d_tiles_t, reinterpret_cast<int*>(c->d_nrm_t), c->d_bpos_t, c->d_bounds);
-    } else if (fmt == HVS_FMT_I8X16) {
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8x16, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_ct, L, c->d_quant,
-                           c->d_tiles_ct, reinterpret_cast<int*>(c->d_nrm_ct), c->d_bpos_ct, c->d_bounds);
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8x16, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_t, L, c->d_quant,
-                           c->d_tiles_t, reinterpret_cast<int*>(c->d_nrm_t), c->d_bpos_t, c->d_bounds);
-    } else if (fmt == HVS_FMT_I8) {
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_ct, L, c->d_quant,
-                           c->d_tiles_ct, reinterpret_cast<int*>(c->d_nrm_ct), c->d_bpos_ct, c->d_bounds);
-        hipLaunchKernelGGL(hvs_k_build_tiles_i8, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_t, L, c->d_quant,
-                           c->d_tiles_t, reinterpret_cast<int*>(c->d_nrm_t), c->d_bpos_t, c->d_bounds);
-    } else {
-        hipLaunchKernelGGL(hvs_k_build_tiles, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_ct, L, c->d_tiles_ct,
-                           c->d_bpos_ct, c->d_bounds, fmt);
-        hipLaunchKernelGGL(hvs_k_build_tiles, grid, dim3(256), 0, c->stream, c->d_data, n, c->d_perm_t, L, c->d_tiles_t,
-                           c->d_bpos_t, c->d_bounds, fmt);
+    for (const HvsOrdering& o : c->ord) {
+        if (F.build_i8)
+            hipLaunchKernelGGL(F.build_i8, grid, dim3(256), 0, c->stream, c->d_data, n, o.perm, L, c->d_quant, o.tiles,
+                               reinterpret_cast<int*>(o.nrm), o.bpos, c->d_bounds);
+        else
+            hipLaunchKernelGGL(hvs_k_build_tiles, grid, dim3(256), 0, c->stream, c->d_data, n, o.perm, L, o.tiles, o.bpos, c->d_bounds, fmt);
     }
     HVS_HIP(c, hipGetLastError());
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    // the error bound needs finite row norms: data with inf/NaN components (or |d|^2 overflowing f32)
-    // is answered by the exact engine only
     HvsBounds hb{};
     HVS_HIP(c, hipMemcpy(&hb, c->d_bounds, sizeof(hb), hipMemcpyDeviceToHost));
-    bool ok;
-    if (HVS_IS_I8(fmt))
-        ok = std::isfinite(hb.e_d8) && std::isfinite(hb.n_d8) && hb.n_d8 < 1.0e15f;
-    else if (fmt == HVS_FMT_F16)
-        // every component and the three pieces of -|d|^2/2 inside the half-precision range (denormal flushing is part of
-        // the bound: HVS_F16_FLUSH)
-        ok = std::isfinite(hb.e_d) && std::isfinite(hb.nb_d) && std::isfinite(hb.hmax) && std::isfinite(hb.rho) && hb.hmax < 6.0e4f;
-    else
-        // (norms near the f32 denormal range: BF16 operands might be flushed by the matrix pipe, which the
-        // error bound does not model)
-        ok = std::isfinite(hb.e_d) && std::isfinite(hb.nb_d) && std::isfinite(hb.hmax) && std::isfinite(hb.rho) &&
-             !(hb.hmax > 1.0e30f) && !(hb.hmax > 0.0f && hb.hmax < 1.0e-20f);
+    const bool ok = hvs_bounds_usable(fmt, hb);
     if (kTrace)
         std::fprintf(stderr, "[hvs trace] tiles built: format %d usable %d e_d8 %.6g n_d8 %.6g e_d %.6g nb_d %.6g hmax %.6g rho %.6g\n", fmt, (int)ok,
                      (double)hb.e_d8, (double)hb.n_d8, (double)hb.e_d, (double)hb.nb_d, (double)hb.hmax, (double)hb.rho);
@@ -971,22 +984,22 @@ int build_index(hvs_ctx* c)
     HVS_TRY(dev_alloc(c, &k_ct, (size_t)n));
     HVS_TRY(dev_alloc(c, &k_t, (size_t)n));
     HVS_TRY(dev_alloc(c, &ids, (size_t)n));
-    HVS_TRY(dev_alloc(c, &c->d_keys_ct, (size_t)n));
-    HVS_TRY(dev_alloc(c, &c->d_keys_t, (size_t)n));
-    HVS_TRY(dev_alloc(c, &c->d_perm_ct, (size_t)n));
-    HVS_TRY(dev_alloc(c, &c->d_perm_t, (size_t)n));
+    for (HvsOrdering& o : c->ord) {
+        HVS_TRY(dev_alloc(c, &o.keys, (size_t)n));
+        HVS_TRY(dev_alloc(c, &o.perm, (size_t)n));
+    }
     hipLaunchKernelGGL(hvs_k_attr_keys, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, n, k_ct, k_t, ids);
     size_t tmp_bytes = 0, tmp_bytes_t = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_ct, c->d_keys_ct, ids, c->d_perm_ct, (size_t)n, 0, 64,
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64,
                                              c->stream);
     if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes_t, k_t, c->d_keys_t, ids, c->d_perm_t, (size_t)n, 0, 64, c->stream);
+        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes_t, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
     if (tmp_bytes_t > tmp_bytes) tmp_bytes = tmp_bytes_t;  // each call sizes its own algorithm
     if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes);
     if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_ct, c->d_keys_ct, ids, c->d_perm_ct, (size_t)n, 0, 64, c->stream);
+        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64, c->stream);
     if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_t, c->d_keys_t, ids, c->d_perm_t, (size_t)n, 0, 64, c->stream);
+        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         cleanup();
@@ -1114,8 +1127,8 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
         HVS_HIP(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < 5; ++k) c->class_counts[k] = counts[k];
     }
-    hipLaunchKernelGGL(hvs_k_query_keys2, dim3((nqb + 255u) / 256u), dim3(256), 0, c->stream, c->d_q, q0, nqb, list, c->d_keys_ct,
-                       c->d_keys_t, n, c->d_layout + 8, c->d_keys, c->d_qidx, c->d_qra, c->d_qrb);
+    hipLaunchKernelGGL(hvs_k_query_keys2, dim3((nqb + 255u) / 256u), dim3(256), 0, c->stream, c->d_q, q0, nqb, list, c->ord[0].keys,
+                       c->ord[1].keys, n, c->d_layout + 8, c->d_keys, c->d_qidx, c->d_qra, c->d_qrb);
     size_t tmp = c->sort_tmp_bytes;
     HVS_HIP(c, rocprim::radix_sort_pairs(c->d_sort_tmp, tmp, c->d_keys, c->d_keys_sorted, c->d_qidx, c->d_qorder,
                                          (size_t)nqb, 0, 64, c->stream));
@@ -1143,7 +1156,7 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     if (c->n_dead) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn != c->n)
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
                            c->d_counters, c->d_live);
     // slot layout of hvs_k_layout: classes 0..3 padded to 32 slots each, then the T-ordering class (type 2)
     // from the next filter-workgroup boundary
@@ -1167,32 +1180,15 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     HVS_HIP(c, hipMemsetAsync(c->d_cand_cnt, 0, lists * sizeof(uint32_t), c->stream));
     const int ev = kernel_timer_begin(c);
     const dim3 grid((slot_end + 255u) / 256u, nchunks);
-    with_cap_mask(c, [&](auto CAPT, auto MT) {
-        constexpr int CAP = decltype(CAPT)::value;
-        constexpr bool M = decltype(MT)::value;
-        if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_scan_ranges<true, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
-                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters, c->d_live);
-        else
-            hipLaunchKernelGGL((hvs_k_scan_ranges<false, CAP, M>), grid, dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->d_perm_ct,
-                               c->d_perm_t, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt, c->d_counters, c->d_live);
+    with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+        hipLaunchKernelGGL((hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0, c->stream,
+                           c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt,
+                           c->d_counters, c->d_live);
     });
     kernel_timer_end(c, ev);
     const uint32_t nsel = slot_end - slot_begin;
-    uint64_t* cand = c->d_cand + (size_t)slot_begin * (size_t)c->cap;
-    uint32_t* cnt = c->d_cand_cnt + slot_begin;
-    with_cap_mask(c, [&](auto CAPT, auto MT) {
-        constexpr int CAP = decltype(CAPT)::value;
-        constexpr bool M = decltype(MT)::value;
-        if (c->scalar_order)
-            hipLaunchKernelGGL((hvs_k_select<true, CAP, M>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
-                               c->d_pad_ids);
-        else
-            hipLaunchKernelGGL((hvs_k_select<false, CAP, M>), dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q,
-                               B.qid + slot_begin, nsel, B.nslots, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k,
-                               c->d_pad_ids);
-    });
+    launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks, c->d_cand + (size_t)slot_begin * (size_t)c->cap,
+                  c->d_cand_cnt + slot_begin);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -1332,7 +1328,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     if (c->n_dead && !list) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn != n && !list)
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->d_perm_ct, c->d_perm_t, sn,
+        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
                            c->d_counters, c->d_live);
 
     if (c->gate_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gate_heavy, 0));  // (two lanes: see hvs_ctx::ev_pdone)
@@ -1343,7 +1339,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = std::min(l0blocks, hvs_ceil_div(kSeedWaves, seed_waves));
     with_cap_mask(c, [&](auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)),
-                           dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_bpos_ct, c->d_bpos_t, L,
+                           dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L,
                            c->d_counters, std::max(1u, seed_chunks), c->d_live);
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
@@ -1368,6 +1364,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     // BASELINE configs[1]/[2], 10^4 queries: m (R - 1) = 1000 rows per query to the exact kernel instead of 2 x 60 for one
     // re-score + merge less -- was measured in round 3: 2.85 ms instead of 2.08 ms per 10^4 mixed queries.  Round 2 measured
     // the same for doubling levels.)
+    const HvsFilterKernel filter_kernel = hvs_host_fmt(fmt, c->i8_rot).filter;  // picked once per batch
     for (uint32_t level = 1; level <= L.K;) {
         const uint32_t last = level;
         // (the groups' entry counters are zero here: hvs_k_prep clears them for the first level, every merge for the next)
@@ -1377,30 +1374,17 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             static const uint32_t kWgsPerCu = env_u32("HVS_FILTER_WGS_PER_CU", 4u, 1u, 16u);
             const dim3 fgrid(kWgsPerCu * (uint32_t)c->num_cus);
             W.segsize = c->segs.seg[level];
-            if (fmt == HVS_FMT_I8X16)
-                hipLaunchKernelGGL(hvs_k_filter_i8x16, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->d_tiles_ct, c->d_tiles_t,
-                                   c->d_nrm_ct, c->d_nrm_t, c->d_bpos_ct, c->d_bpos_t, L, level, B, W, c->d_counters);
-            else if (fmt == HVS_FMT_I8)
-                hipLaunchKernelGGL(hvs_k_filter_mfma<HVS_FMT_I8>, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->d_tiles_ct,
-                                   c->d_tiles_t, c->d_nrm_ct, c->d_nrm_t, c->d_bpos_ct, c->d_bpos_t, L, level, B, W, c->d_counters);
-            else if (fmt == HVS_FMT_F16)
-                hipLaunchKernelGGL(hvs_k_filter_mfma<HVS_FMT_F16>, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->d_tiles_ct,
-                                   c->d_tiles_t, c->d_nrm_ct, c->d_nrm_t, c->d_bpos_ct, c->d_bpos_t, L, level, B, W, c->d_counters);
-            else
-                hipLaunchKernelGGL(hvs_k_filter_mfma<HVS_FMT_BF16>, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->d_tiles_ct,
-                                   c->d_tiles_t, c->d_nrm_ct, c->d_nrm_t, c->d_bpos_ct, c->d_bpos_t, L, level, B, W, c->d_counters);
+            hipLaunchKernelGGL(filter_kernel, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->ord[0].tiles, c->ord[1].tiles, c->ord[0].nrm,
+                               c->ord[1].nrm, c->ord[0].bpos, c->ord[1].bpos, L, level, B, W, c->d_counters);
             kernel_timer_end(c, ev);
             if (level == L.K && c->ev_fdone_cur) HVS_HIP(c, hipEventRecord(c->ev_fdone_cur, c->stream));
             if (level + 1u == L.K && c->ev_pdone_cur) HVS_HIP(c, hipEventRecord(c->ev_pdone_cur, c->stream));
         }
         with_cap_mask(c, [&](auto, auto MT) {
             constexpr bool M = decltype(MT)::value;
-            if (fmt == HVS_FMT_I8X16)
-                hipLaunchKernelGGL((hvs_k_rescore<true, M>), dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream,
-                                   c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters, c->d_live);
-            else
-                hipLaunchKernelGGL((hvs_k_rescore<false, M>), dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream,
-                                   c->d_data, n, sn, c->d_q, B, c->d_perm_ct, c->d_perm_t, c->d_counters, c->d_live);
+            const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;  // (entry format)
+            hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, n, sn,
+                               c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, c->d_live);
         });
         launch_merge(last == L.K, last + 1u);
     }
@@ -1806,12 +1790,13 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_in) (void)hipStreamSynchronize(c->s_in);
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
+    free_index(c);  // (keeps ord[].lp: freed here)
     void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
                     c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->d_live, c->d_pad_ids, c->d_mask_ids,
-                    c->d_mask_stat, c->d_lp_ct, c->d_lp_t};
+                    c->d_mask_stat, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    free_index(c);
+    c->ord[0].lp = c->ord[1].lp = nullptr;
     free_lane(c->spare);
     free_lane(static_cast<HvsLane&>(*c));
     if (c->ev_lane) (void)hipEventDestroy(c->ev_lane);
@@ -1914,8 +1899,8 @@ int begin_data(hvs_ctx* c, uint32_t n)
     c->cut_valid = false;
     c->lp_valid = false;
     if ((rc = dev_alloc(c, &c->d_live, (size_t)0))) return rc;
-    if ((rc = dev_alloc(c, &c->d_lp_ct, (size_t)0))) return rc;
-    if ((rc = dev_alloc(c, &c->d_lp_t, (size_t)0))) return rc;
+    if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
+    if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
     return dev_alloc(c, &c->d_data, (size_t)n * HVS_DCOLS);
 }
 

@@ -440,6 +440,33 @@ __device__ __forceinline__ int hvs_quant_i8(double x, double inv_sd)
     return (r == r) ? (int)r : 0;
 }
 
+// The INT8 tile builders' row arithmetic -- what the filter's soundness rests on -- written once.
+// |d'|^2 (nd) and the squared quantisation error (e2) of a plain (non-rotated) row, d' = row - centre
+__device__ __forceinline__ void hvs_i8_row_sums(const float* row, const HvsQuant* qz, double sd, double inv_sd,
+                                                double& nd, double& e2)
+{
+    nd = 0.0, e2 = 0.0;
+    for (int k = 0; k < HVS_NDIM; ++k) {
+        const double x = (double)row[k] - (double)qz->center[k];
+        const double xq = sd * (double)hvs_quant_i8(x, inv_sd);
+        nd += x * x;
+        e2 += (x - xq) * (x - xq);
+    }
+}
+// accumulator init of a row from (nd, e2): floor(-|d'|^2 / (2 sd^2)), a padding row's never-hit value when the row is not
+// valid; a valid row also raises the global row bounds e_d8 / n_d8 (rounded up)
+__device__ __forceinline__ int hvs_i8_row_init(double nd, double e2, bool valid, double inv_sd, HvsBounds* bounds)
+{
+    int nh = HVS_I8_PAD_NORM;
+    if (valid) {
+        const double v = floor(-0.5 * nd * inv_sd * inv_sd);
+        nh = v > -1.0e9 ? (int)v : HVS_I8_PAD_NORM;  // (|d'_k| <= 127 sd: v >= -806450 for 100 dimensions)
+        hvs_atomic_max_pos(&bounds->e_d8, hvs_round_up_f32(sqrt(e2) * (1.0 + 1e-9) + 1e-30));
+        hvs_atomic_max_pos(&bounds->n_d8, hvs_round_up_f32(sqrt(nd) * (1.0 + 1e-9) + 1e-30));
+    }
+    return nh;
+}
+
 // one wave per storage block: 3 KiB INT8 A-operand tile (lane l of k-step s: row l&31, k = 32 s + 16 (l>>5) + 0..15;
 // k-steps 0..2), 256 B of side data (dims 96..99 and the 32 accumulator inits) and the row bounds
 __global__ __launch_bounds__(256) void hvs_k_build_tiles_i8(const float* __restrict__ D, uint32_t n,
@@ -459,20 +486,9 @@ __global__ __launch_bounds__(256) void hvs_k_build_tiles_i8(const float* __restr
     const float* __restrict__ row = D + (size_t)(valid ? perm[pos] : 0u) * HVS_DCOLS + 2;
     const double sd = qz->sd, inv_sd = qz->inv_sd;
     if (h == 0u) {
-        double nd = 0.0, e2 = 0.0;
-        for (int k = 0; k < HVS_NDIM; ++k) {
-            const double x = (double)row[k] - (double)qz->center[k];
-            const double xq = sd * (double)hvs_quant_i8(x, inv_sd);
-            nd += x * x;
-            e2 += (x - xq) * (x - xq);
-        }
-        int nh = HVS_I8_PAD_NORM;
-        if (valid) {
-            const double v = floor(-0.5 * nd * inv_sd * inv_sd);
-            nh = v > -1.0e9 ? (int)v : HVS_I8_PAD_NORM;  // (|d'_k| <= 127 sd: v >= -806450)
-            hvs_atomic_max_pos(&bounds->e_d8, hvs_round_up_f32(sqrt(e2) * (1.0 + 1e-9) + 1e-30));
-            hvs_atomic_max_pos(&bounds->n_d8, hvs_round_up_f32(sqrt(nd) * (1.0 + 1e-9) + 1e-30));
-        }
+        double nd, e2;
+        hvs_i8_row_sums(row, qz, sd, inv_sd, nd, e2);
+        const int nh = hvs_i8_row_init(nd, e2, valid, inv_sd, bounds);
         // side data: the 4 real dimensions of the 4th k-step (the other 28 are zero padding and are not stored:
         // the filter rebuilds the fragment from this word), then the accumulator init
         uint32_t tail = 0;
@@ -522,21 +538,9 @@ __global__ __launch_bounds__(256) void hvs_k_build_tiles_i8x16(const float* __re
         const uint32_t pos = b * 32u + lane;
         const bool valid = pos < n;
         const float* __restrict__ row = D + (size_t)(valid ? perm[pos] : 0u) * HVS_DCOLS + 2;
-        double nd = 0.0, e2 = 0.0;
-        for (int k = 0; k < HVS_NDIM; ++k) {
-            const double x = (double)row[k] - (double)qz->center[k];
-            const double xq = sd * (double)hvs_quant_i8(x, inv_sd);
-            nd += x * x;
-            e2 += (x - xq) * (x - xq);
-        }
-        int nh = HVS_I8_PAD_NORM;
-        if (valid) {
-            const double v = floor(-0.5 * nd * inv_sd * inv_sd);
-            nh = v > -1.0e9 ? (int)v : HVS_I8_PAD_NORM;
-            hvs_atomic_max_pos(&bounds->e_d8, hvs_round_up_f32(sqrt(e2) * (1.0 + 1e-9) + 1e-30));
-            hvs_atomic_max_pos(&bounds->n_d8, hvs_round_up_f32(sqrt(nd) * (1.0 + 1e-9) + 1e-30));
-        }
-        norms[(size_t)idx * 32u + lane] = nh;
+        double nd, e2;
+        hvs_i8_row_sums(row, qz, sd, inv_sd, nd, e2);
+        norms[(size_t)idx * 32u + lane] = hvs_i8_row_init(nd, e2, valid, inv_sd, bounds);
     }
 #pragma unroll
     for (int f = 0; f < HVS_I8X16_FRAGS; ++f) {
@@ -601,16 +605,7 @@ __global__ __launch_bounds__(256) void hvs_k_build_tiles_i8x16_rot(const float* 
     __syncthreads();
     if (!live) return;
     if (lane < 32u) {
-        const bool valid = b * 32u + lane < n;
-        int nh = HVS_I8_PAD_NORM;
-        if (valid) {
-            const double nd = ssum[w][lane][0], e2 = ssum[w][lane][1];
-            const double v = floor(-0.5 * nd * inv_sd * inv_sd);
-            nh = v > -1.0e9 ? (int)v : HVS_I8_PAD_NORM;
-            hvs_atomic_max_pos(&bounds->e_d8, hvs_round_up_f32(sqrt(e2) * (1.0 + 1e-9) + 1e-30));
-            hvs_atomic_max_pos(&bounds->n_d8, hvs_round_up_f32(sqrt(nd) * (1.0 + 1e-9) + 1e-30));
-        }
-        norms[(size_t)idx * 32u + lane] = nh;
+        norms[(size_t)idx * 32u + lane] = hvs_i8_row_init(ssum[w][lane][0], ssum[w][lane][1], b * 32u + lane < n, inv_sd, bounds);
     }
 #pragma unroll
     for (int f = 0; f < HVS_I8X16_FRAGS; ++f) {
@@ -1669,6 +1664,197 @@ struct HvsItems {
     uint32_t segsize;        // row blocks per item at the level being launched (HvsSegs::seg)
 };
 
+// ---------------------------------------------------------------------------------------------
+// Scaffolding shared by the filter kernels hvs_k_filter_mfma<FMT> and hvs_k_filter_i8x16: pulling a work item, the
+// survivor buffer's flush, LDS-DMA staging, the positions every lane's range covers and the stage loop.  What the
+// kernels keep to themselves is what differs for measured reasons: operands, chains, epilogue, survivor entries and
+// the read order of the next tile.
+// ---------------------------------------------------------------------------------------------
+// Wave-uniform state of the work item a workgroup is on
+struct HvsFilterItem {
+    uint32_t g, gq;        // this wave's group; the first group of the workgroup's quad (it decides the ordering)
+    const uint4* tiles;    // the ordering's tiles, side data and block positions
+    const uint4* nrm;
+    const uint32_t* bpos;
+    uint32_t i0, i1;       // this wave's tiles [i0, i1) inside the segment (empty when i0 >= i1)
+    uint32_t I0, I1;       // the workgroup's: the union over its waves
+    bool active;           // i0 < i1
+};
+
+// Work items (HvsItems): a fixed crew of workgroups pulls (quad of groups, segment) pairs of this level, ordered
+// segment-major: consecutive items stream the same run of tiles for different queries, so a segment
+// is fetched from HBM about once and then served by the XCDs' L2s / the Infinity Cache.
+// The quad's 4 waves walk the segment together: every tile is fetched once per workgroup
+// into LDS and read from there by all 4 waves (ds_read_b128).  All groups of a quad use the
+// same ordering (the T-ordering part of a batch starts at a quad boundary).
+// hvs_filter_next: the next item's code from the level's part of W.list, [item0, item0 + nitems); false when the list is
+// exhausted.  hvs_filter_open: the item's state; false when it has no tiles (cannot happen with a well-formed list).
+// Both results are uniform over the workgroup.
+__device__ __forceinline__ bool hvs_filter_next(const HvsItems& W, uint32_t level, uint32_t item0, uint32_t nitems, uint32_t& sitem,
+                                                uint32_t& code)
+{
+    if (threadIdx.x == 0u) sitem = atomicAdd(&W.cursor[level], 1u);
+    __syncthreads();
+    const uint32_t item = __builtin_amdgcn_readfirstlane(sitem);
+    if (item >= nitems) return false;
+    code = __builtin_amdgcn_readfirstlane(W.list[item0 + item]);
+    return true;
+}
+__device__ __forceinline__ bool hvs_filter_open(const uint4* tiles_ct, const uint4* tiles_t,
+                                               const uint4* nrm_ct, const uint4* nrm_t,
+                                               const uint32_t* bpos_ct, const uint32_t* bpos_t,
+                                               const HvsLevels& L, uint32_t level, const HvsBatch& B, const HvsItems& W,
+                                               uint32_t code, uint32_t (&srange)[HVS_WG_WAVES][2], HvsFilterItem& it)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = threadIdx.x >> 6;
+    const uint32_t quad = code & ((1u << HVS_ITEM_QUAD_BITS) - 1u), segment = code >> HVS_ITEM_QUAD_BITS;
+    const uint32_t g = quad * HVS_WG_WAVES + wv;
+    const uint32_t gq = quad * HVS_WG_WAVES;
+    const uint32_t ord = B.gord[gq];
+    it.g = g;
+    it.gq = gq;
+    it.tiles = ord ? tiles_t : tiles_ct;
+    it.bpos = ord ? bpos_t : bpos_ct;
+    it.nrm = ord ? nrm_t : nrm_ct;
+    const uint32_t seg_lo = L.off[level] + segment * W.segsize;
+    uint32_t i0 = 0, i1 = 0;
+    if (g < B.ngroups && B.gord[g] == ord) {
+        uint32_t lo, hi;
+        hvs_level_run(L, level, B.gua[g] / 32u, hvs_ceil_div(B.gub[g], 32u), lo, hi);
+        if (seg_lo < hi && seg_lo + W.segsize > lo) {
+            i0 = seg_lo > lo ? seg_lo : lo;
+            i1 = (seg_lo + W.segsize) < hi ? (seg_lo + W.segsize) : hi;
+        }
+    }
+    // (computing all four groups' runs from scalars in every wave, without this LDS exchange and barrier,
+    // measured 1 % slower)
+    if (lane == 0u) {
+        srange[wv][0] = i0 < i1 ? i0 : 0xFFFFFFFFu;
+        srange[wv][1] = i0 < i1 ? i1 : 0u;
+    }
+    __syncthreads();
+    uint32_t I0 = srange[0][0], I1 = srange[0][1];
+#pragma unroll
+    for (int w = 1; w < HVS_WG_WAVES; ++w) {
+        I0 = srange[w][0] < I0 ? srange[w][0] : I0;
+        I1 = srange[w][1] > I1 ? srange[w][1] : I1;
+    }
+    if (I0 >= I1) return false;
+    it.I0 = __builtin_amdgcn_readfirstlane(I0);  // (read from LDS: tell the compiler they are scalars)
+    it.I1 = __builtin_amdgcn_readfirstlane(I1);
+    it.i0 = __builtin_amdgcn_readfirstlane(i0);  // wave-uniform by construction: keep the tile test scalar
+    it.i1 = __builtin_amdgcn_readfirstlane(i1);
+    it.active = it.i0 < it.i1;
+    return true;
+}
+
+// the wave's survivor buffer (wcnt entries, wave-uniform) to the group's part of B.pairs
+__device__ __forceinline__ void hvs_filter_flush(const HvsBatch& B, uint32_t g, uint32_t lane, const uint64_t* lbuf,
+                                                 uint32_t& wcnt)
+{
+    if (wcnt == 0u) return;
+    uint32_t base = 0;
+    if (lane == 0u) base = atomicAdd(&B.paircnt[g], wcnt);
+    base = __builtin_amdgcn_readfirstlane(base);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (base + wcnt <= B.gcap) {
+        for (uint32_t e = lane; e < wcnt; e += 64u) B.pairs[(size_t)g * B.gcap + base + e] = lbuf[e];
+    } else if (lane == 0u) {
+        B.goverflow[g] = 1u;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    wcnt = 0;
+}
+
+// Tiles reach LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no VGPRs); one call moves one
+// chunk: lane l's 16 bytes at `src` (per lane) to `dst` + 16 l (`dst` wave-uniform).  Stage s+1 is in flight while
+// stage s is multiplied; hvs_stage_barrier at the end of a stage both lands the next stage (every wave has
+// waited for its own chunks before any wave passes the barrier) and frees the current buffer
+// (every wave has finished its ds_reads of it).  One barrier per stage keeps the waves loosely coupled: a
+// wave that spends time on survivors of one tile catches up inside the stage.
+__device__ __forceinline__ void hvs_lds_dma(const uint4* src, const uint4* dst)
+{
+    // LDS byte address of the chunk (wave-uniform) goes to M0; the instruction adds lane*16.
+    // Issued as inline asm on purpose: hipcc orders every later ds_read behind a
+    // compiler-visible LDS-DMA with s_waitcnt vmcnt(0), which would serialise the prefetch
+    // with the multiply; here the only wait is the explicit one before the stage barrier.
+    const uint32_t lds_addr =
+        __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)dst);
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(lds_addr)
+                 : "memory");
+}
+__device__ __forceinline__ void hvs_stage_barrier()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA chunks have landed
+    __syncthreads();
+}
+
+// the positions every lane's range covers: [ra_max, rb_min) (lanes that can never hit do not count); wave-uniform
+template <int N>
+__device__ __forceinline__ void hvs_filter_common_range(const uint32_t (&ra)[N], const uint32_t (&rb)[N], uint32_t& ra_max,
+                                                        uint32_t& rb_min)
+{
+    ra_max = 0u, rb_min = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const bool live = rb[j] > ra[j];
+        ra_max = max(ra_max, live ? ra[j] : 0u);
+        rb_min = min(rb_min, live ? rb[j] : 0xFFFFFFFFu);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ra_max = max(ra_max, (uint32_t)__shfl_xor((int)ra_max, o));
+        rb_min = min(rb_min, (uint32_t)__shfl_xor((int)rb_min, o));
+    }
+    ra_max = __builtin_amdgcn_readfirstlane(ra_max);
+    rb_min = __builtin_amdgcn_readfirstlane(rb_min);
+}
+
+// The stage loop of a work item: issue_stage(buffer, first tile) starts the LDS-DMA of STG tiles,
+// run_tiles(t0, t1, slot) multiplies this wave's tiles [t0, t1) of the landed stage; `slot` = the place of t0 in the two
+// stage buffers (buffer * STG + tile within the stage), which the caller steps per tile with hvs_step_slot instead of
+// deriving it from the tile number (scalar instructions are not free in that loop).
+template <int STG, typename ISSUE, typename RUN>
+__device__ __forceinline__ void hvs_filter_stages(const HvsFilterItem& it, ISSUE&& issue_stage, RUN&& run_tiles)
+{
+    const uint32_t nstage = hvs_ceil_div(it.I1 - it.I0, STG);
+    issue_stage(0u, it.I0);
+    hvs_stage_barrier();
+    // Everything loaded so far (B fragments, thresholds, ranges) has landed -- the stage barrier waited for
+    // vmcnt(0) -- but the compiler cannot see through that inline asm and would re-wait for those loads at
+    // their first uses INSIDE the loop (`s_waitcnt vmcnt(0)` in the middle of every tile's MFMA block, which
+    // with the LDS-DMA prefetch of the next stage in flight exposes the DMA latency once per stage).  A wait
+    // the compiler does understand, once, here, clears its scoreboard.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    for (uint32_t st = 0; st < nstage; ++st) {
+        if (st + 1u < nstage) issue_stage((st & 1u) ^ 1u, it.I0 + (st + 1u) * STG);
+        // this wave's tiles of the stage: [t0, t1)
+        const uint32_t s0 = it.I0 + st * STG;
+        const uint32_t t0 = it.i0 > s0 ? it.i0 : s0;
+        const uint32_t t1 = it.i1 < s0 + STG ? it.i1 : s0 + STG;  // (i1 <= I1)
+        if (it.active && t0 < t1) run_tiles(t0, t1, (st & 1u) * STG + (t0 - s0));
+        hvs_stage_barrier();
+    }
+}
+__device__ __forceinline__ void hvs_step_slot(uint32_t& slot, uint32_t by)
+{
+    slot += by;
+    asm volatile("" : "+s"(slot));  // (otherwise the compiler re-derives it from the tile number: ~8 scalar instructions per tile)
+}
+// end of a work item (the last stage barrier has released the stage buffers): the survivors left and the pairs tested
+__device__ __forceinline__ void hvs_filter_finish(const HvsBatch& B, const HvsFilterItem& it, uint32_t lane,
+                                                  const uint64_t* lbuf, uint32_t& wcnt, uint32_t nblocks,
+                                                  unsigned long long* counters)
+{
+    if (!it.active) return;
+    hvs_filter_flush(B, it.g, lane, lbuf, wcnt);
+    if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nblocks * 32ull * HVS_GROUP);
+}
+
 // operand / accumulator types and the MFMA step of the two tile formats
 template <int FMT>
 struct HvsFmt;
@@ -1748,55 +1934,14 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     __shared__ uint32_t sitem;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = threadIdx.x >> 6;
-    // Work items (HvsItems): a fixed crew of workgroups pulls (quad of groups, segment) pairs of this level, ordered
-    // segment-major: consecutive items stream the same run of tiles for different queries, so a segment
-    // is fetched from HBM about once and then served by the XCDs' L2s / the Infinity Cache.
-    // The quad's 4 waves walk the segment together: every tile is fetched once per workgroup
-    // into LDS and read from there by all 4 waves (ds_read_b128).  All groups of a quad use the
-    // same ordering (the T-ordering part of a batch starts at a quad boundary).
     const uint32_t item0 = W.lvloff[level], nitems = W.lvloff[level + 1u] - item0;
-  for (;;) {
-    if (threadIdx.x == 0u) sitem = atomicAdd(&W.cursor[level], 1u);
-    __syncthreads();
-    const uint32_t item = __builtin_amdgcn_readfirstlane(sitem);
-    if (item >= nitems) break;  // uniform over the workgroup
-    const uint32_t code = __builtin_amdgcn_readfirstlane(W.list[item0 + item]);
-    const uint32_t quad = code & ((1u << HVS_ITEM_QUAD_BITS) - 1u), segment = code >> HVS_ITEM_QUAD_BITS;
-    const uint32_t g = quad * HVS_WG_WAVES + wv;
-    const uint32_t gq = quad * HVS_WG_WAVES;  // first group of the workgroup decides the ordering
-    const uint32_t ord = B.gord[gq];
-    const uint4* __restrict__ tiles = ord ? tiles_t : tiles_ct;
-    const uint32_t* __restrict__ bpos = ord ? bpos_t : bpos_ct;
-    const uint4* __restrict__ nrm = ord ? nrm_t : nrm_ct;
-    const uint32_t seg_lo = L.off[level] + segment * W.segsize;
-    uint32_t i0 = 0, i1 = 0;  // this wave's tiles [i0,i1) inside the segment (empty when i0 >= i1)
-    if (g < B.ngroups && B.gord[g] == ord) {
-        uint32_t lo, hi;
-        hvs_level_run(L, level, B.gua[g] / 32u, hvs_ceil_div(B.gub[g], 32u), lo, hi);
-        if (seg_lo < hi && seg_lo + W.segsize > lo) {
-            i0 = seg_lo > lo ? seg_lo : lo;
-            i1 = (seg_lo + W.segsize) < hi ? (seg_lo + W.segsize) : hi;
-        }
-    }
-    // (computing all four groups' runs from scalars in every wave, without this LDS exchange and barrier,
-    // measured 1 % slower)
-    if (lane == 0u) {
-        srange[wv][0] = i0 < i1 ? i0 : 0xFFFFFFFFu;
-        srange[wv][1] = i0 < i1 ? i1 : 0u;
-    }
-    __syncthreads();
-    uint32_t I0 = srange[0][0], I1 = srange[0][1];
-#pragma unroll
-    for (int w = 1; w < HVS_WG_WAVES; ++w) {
-        I0 = srange[w][0] < I0 ? srange[w][0] : I0;
-        I1 = srange[w][1] > I1 ? srange[w][1] : I1;
-    }
-    if (I0 >= I1) continue;  // uniform over the workgroup (cannot happen with a well-formed list)
-    I0 = __builtin_amdgcn_readfirstlane(I0);  // (read from LDS: tell the compiler they are scalars)
-    I1 = __builtin_amdgcn_readfirstlane(I1);
-    i0 = __builtin_amdgcn_readfirstlane(i0);  // wave-uniform by construction: keep the tile test scalar
-    i1 = __builtin_amdgcn_readfirstlane(i1);
-    const bool active = i0 < i1;
+  for (;;) {  // one work item per turn; every workgroup leaves when the level's list is exhausted
+    HvsFilterItem it;
+    uint32_t code;
+    if (!hvs_filter_next(W, level, item0, nitems, sitem, code)) break;
+    if (!hvs_filter_open(tiles_ct, tiles_t, nrm_ct, nrm_t, bpos_ct, bpos_t, L, level, B, W, code, srange, it)) continue;
+    const uint32_t g = it.g, gq = it.gq, I1 = it.I1;
+    const bool active = it.active;
 
     // resident query operands
     typename F::frag_t bq[HVS_QB][KS];
@@ -1819,51 +1964,16 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     uint32_t wcnt = 0;  // wave-uniform fill of lbuf
     uint32_t nblocks = 0;
 
-    auto flush = [&]() {
-        if (wcnt == 0u) return;
-        uint32_t base = 0;
-        if (lane == 0u) base = atomicAdd(&B.paircnt[g], wcnt);
-        base = __builtin_amdgcn_readfirstlane(base);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        if (base + wcnt <= B.gcap) {
-            for (uint32_t e = lane; e < wcnt; e += 64u) B.pairs[(size_t)g * B.gcap + base + e] = lbuf[e];
-        } else if (lane == 0u) {
-            B.goverflow[g] = 1u;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        wcnt = 0;
-    };
-
-    // Tiles reach LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no VGPRs): a
-    // stage = 4 tiles = 28 chunks, 7 per wave.  Stage s+1 is in flight while stage s is multiplied;
-    // s_waitcnt vmcnt(0) + barrier at the end of a stage both lands the next stage (every wave has
-    // waited for its own chunks before any wave passes the barrier) and frees the current buffer
-    // (every wave has finished its ds_reads of it).  One barrier per 4 tiles keeps the waves loosely coupled: a
-    // wave that spends time on survivors of one tile catches up inside the stage.
+    // LDS-DMA (hvs_lds_dma): a stage = 4 tiles = 28 chunks, 7 per wave (INT8: 8 tiles = 24 chunks, 6 per wave)
     constexpr int kChunksPerWave = (STG * KM + HVS_WG_WAVES - 1) / HVS_WG_WAVES;
-    auto issue_chunks = [&](uint32_t buf, uint32_t first_tile, int k0, int k1) {
-        for (int k = k0; k < k1; ++k) {
+    auto issue_stage = [&](uint32_t buf, uint32_t first_tile) {
+        for (int k = 0; k < kChunksPerWave; ++k) {
             const uint32_t c = __builtin_amdgcn_readfirstlane(wv) + (uint32_t)HVS_WG_WAVES * (uint32_t)k;  // chunk of the stage
             if (c >= STG * KM) break;
             uint32_t tile = first_tile + c / KM;
             if (tile >= I1) tile = I1 - 1u;  // tail of the last stage: re-read a valid tile, never used
-            const uint4* src = tiles + (size_t)tile * TILE_U4 + (c % KM) * 64u + lane;
-            const uint4* dst = &stile[buf][(c / KM) * TILE_U4 + (c % KM) * 64u];
-            // LDS byte address of the chunk (wave-uniform) goes to M0; the instruction adds lane*16.
-            // Issued as inline asm on purpose: hipcc orders every later ds_read behind a
-            // compiler-visible LDS-DMA with s_waitcnt vmcnt(0), which would serialise the prefetch
-            // with the multiply; here the only wait is the explicit one before the stage barrier.
-            const uint32_t lds_addr = __builtin_amdgcn_readfirstlane(
-                (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)dst);
-            uint32_t keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(src), "s"(lds_addr)
-                         : "memory");
+            hvs_lds_dma(it.tiles + (size_t)tile * TILE_U4 + (c % KM) * 64u + lane, &stile[buf][(c / KM) * TILE_U4 + (c % KM) * 64u]);
         }
-    };
-    auto issue_stage = [&](uint32_t buf, uint32_t first_tile) {
-        issue_chunks(buf, first_tile, 0, kChunksPerWave);
         if constexpr (kI8) {
             // the stage's side data (per tile 128 B of tail dimensions + 128 B of accumulator inits, contiguous in
             // storage order): STG * 16 uint4, 64 per wave-instruction, issued by the last waves
@@ -1874,22 +1984,9 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
                 const uint32_t u = a * 64u + lane;
                 uint32_t tile = first_tile + u / HVS_I8_NRM_U4;
                 if (tile >= I1) tile = I1 - 1u;
-                const uint4* src = nrm + (size_t)tile * HVS_I8_NRM_U4 + (u % HVS_I8_NRM_U4);
-                const uint32_t lds_addr = __builtin_amdgcn_readfirstlane(
-                    (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)&snrm[buf][a * 64u]);
-                if (u < STG * HVS_I8_NRM_U4) {
-                    uint32_t keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep)
-                                 : "v"(src), "s"(lds_addr)
-                                 : "memory");
-                }
+                if (u < STG * HVS_I8_NRM_U4) hvs_lds_dma(it.nrm + (size_t)tile * HVS_I8_NRM_U4 + (u % HVS_I8_NRM_U4), &snrm[buf][a * 64u]);
             }
         }
-    };
-    auto stage_barrier = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA chunks have landed
-        __syncthreads();
     };
     // ---- the tile loop ---------------------------------------------------------------------------------------
     // Per tile: A fragments (+ INT8 accumulator inits) from LDS, the 4 chains (two pairs, each interleaved
@@ -1934,7 +2031,7 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
         }
     };
     // the tile's block position: a scalar load (computing it -- runtime division by radix-1 -- measured 4 % slower)
-    auto load_bp = [&](uint32_t i) { bp = __builtin_amdgcn_readfirstlane(bpos[i]); };
+    auto load_bp = [&](uint32_t i) { bp = __builtin_amdgcn_readfirstlane(it.bpos[i]); };
     // the chains of one pair, interleaved k-step by k-step
     auto chains = [&](int pair) {
     #pragma unroll
@@ -1973,35 +2070,13 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
         const uint64_t nz = __ballot(mask != 0u);
         if (mask != 0u) lbuf[wcnt + hvs_prefix_count(nz)] = hvs_entry_make(slot, bpx, lane >> 5, mask);
         wcnt += (uint32_t)__popcll(nz);
-        if (wcnt > 192u) flush();
+        if (wcnt > 192u) hvs_filter_flush(B, g, lane, lbuf, wcnt);
     };
 
-    // the positions every lane's range covers: [ra_max, rb_min) (lanes that can never hit do not count)
-    uint32_t ra_max = 0u, rb_min = 0xFFFFFFFFu;
-    #pragma unroll
-    for (int qb = 0; qb < HVS_QB; ++qb) {
-        const bool live = rb[qb] > ra[qb];
-        ra_max = max(ra_max, live ? ra[qb] : 0u);
-        rb_min = min(rb_min, live ? rb[qb] : 0xFFFFFFFFu);
-    }
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ra_max = max(ra_max, (uint32_t)__shfl_xor((int)ra_max, o));
-        rb_min = min(rb_min, (uint32_t)__shfl_xor((int)rb_min, o));
-    }
-    ra_max = __builtin_amdgcn_readfirstlane(ra_max);
-    rb_min = __builtin_amdgcn_readfirstlane(rb_min);
+    uint32_t ra_max, rb_min;
+    hvs_filter_common_range(ra, rb, ra_max, rb_min);
 
     // tile at a time: four chains, four epilogues, survivors
-    const uint32_t nstage = hvs_ceil_div(I1 - I0, STG);
-    issue_stage(0u, I0);
-    stage_barrier();
-    // Everything loaded so far (B fragments, thresholds, ranges) has landed -- the stage barrier waited for
-    // vmcnt(0) -- but the compiler cannot see through that inline asm and would re-wait for those loads at
-    // their first uses INSIDE the loop (`s_waitcnt vmcnt(0)` in the middle of every tile's MFMA block, which
-    // with the LDS-DMA prefetch of the next stage in flight exposes the DMA latency once per stage).  A wait
-    // the compiler does understand, once, here, clears its scoreboard.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     // Tile t: [LDS reads of its fragments] [28 / 16 matrix instructions] [epilogues] [survivors, rarely].  Round 3 took over from
     // hvs_k_filter_i8x16: the wave's tile range per stage computed once, the stage slot stepped instead of derived, the range
     // tests of edge blocks behind one branch, the hit tests as a tree (+2.7 % on FP16 / BF16 tiles, +3.7 % on 32x32x32 INT8
@@ -2030,38 +2105,25 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
             }
         }
     };
-    for (uint32_t st = 0; st < nstage; ++st) {
-        if (st + 1u < nstage) issue_stage((st & 1u) ^ 1u, I0 + (st + 1u) * STG);
-        // this wave's tiles of the stage: [t0, t1)
-        const uint32_t s0 = I0 + st * STG;
-        const uint32_t t0 = i0 > s0 ? i0 : s0;
-        const uint32_t t1 = i1 < s0 + STG ? i1 : s0 + STG;  // (i1 <= I1)
-        if (active && t0 < t1) {
-            uint32_t slot = (st & 1u) * STG + (t0 - s0);
+    hvs_filter_stages<STG>(it, issue_stage, [&](uint32_t t0, uint32_t t1, uint32_t slot) {
 #pragma unroll 1
-            for (uint32_t i = t0; i < t1; ++i) {
-                ++nblocks;
-                // fragments and block position in front of the tile's own matrix block.  (Measured on FP16 tiles, against
-                // this order: the reads under the previous tile's epilogue -3 %; only the block position's scalar load
-                // under it -1 %, and -2.5 % more with a scheduling barrier between the matrix block and the epilogue -- the
-                // compiler starts the first chain's epilogue between the last matrix instructions of the other three.)
-                load_tile(slot);
-                load_bp(i);
-                wcnt = __builtin_amdgcn_readfirstlane(wcnt);
-                const uint32_t bpx = bp;
-                const bool inner = bpx * 32u >= ra_max && bpx * 32u + 32u <= rb_min;
-                slot += 1u;
-                asm volatile("" : "+s"(slot));  // (otherwise the compiler re-derives it from i)
-                tile_body(bpx, inner);
-            }
+        for (uint32_t i = t0; i < t1; ++i) {
+            ++nblocks;
+            // fragments and block position in front of the tile's own matrix block.  (Measured on FP16 tiles, against
+            // this order: the reads under the previous tile's epilogue -3 %; only the block position's scalar load
+            // under it -1 %, and -2.5 % more with a scheduling barrier between the matrix block and the epilogue -- the
+            // compiler starts the first chain's epilogue between the last matrix instructions of the other three.)
+            load_tile(slot);
+            load_bp(i);
+            wcnt = __builtin_amdgcn_readfirstlane(wcnt);
+            const uint32_t bpx = bp;
+            const bool inner = bpx * 32u >= ra_max && bpx * 32u + 32u <= rb_min;
+            hvs_step_slot(slot, 1u);
+            tile_body(bpx, inner);
         }
-        stage_barrier();
-    }
-    if (active) {
-        flush();
-        if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nblocks * 32ull * HVS_GROUP);
-    }
-  }  // next work item (the last stage barrier has released the stage buffers)
+    });
+    hvs_filter_finish(B, it, lane, lbuf, wcnt, nblocks, counters);
+  }  // next work item
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2253,6 +2315,10 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = threadIdx.x >> 6;
     const uint32_t item0 = W.lvloff[level], nitems = W.lvloff[level + 1u] - item0;
+  // This kernel shares hvs_lds_dma, hvs_stage_barrier and hvs_step_slot with hvs_k_filter_mfma but keeps its own copy of the
+  // item pull, flush, range reduction and stage loop (explained at hvs_filter_next ... hvs_filter_stages): with the shared
+  // helpers the matrix blocks stayed the same but the scalar side and the survivor blocks were laid out differently, and
+  // the default line measured 0.4 % slower (3.267 M against 3.280 M queries/s, two alternated pairs).
   for (;;) {  // one work item per turn; every workgroup leaves when the level's list is exhausted
     if (threadIdx.x == 0u) sitem = atomicAdd(&W.cursor[level], 1u);
     __syncthreads();
@@ -2329,15 +2395,6 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 
     // LDS-DMA: a stage = 8 tiles x 4 fragments = 32 chunks of 1 KiB (8 per wave) + 1 chunk of accumulator inits
     constexpr int kChunksPerWave = STG * HVS_I8X16_FRAGS / HVS_WG_WAVES;
-    auto dma = [&](const uint4* src, const uint4* dst) {
-        const uint32_t lds_addr =
-            __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)dst);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(lds_addr)
-                     : "memory");
-    };
     auto issue_stage = [&](uint32_t buf, uint32_t first_tile) {
         const uint32_t wvs = __builtin_amdgcn_readfirstlane(wv);
 #pragma unroll
@@ -2345,17 +2402,13 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
             const uint32_t c = wvs + (uint32_t)HVS_WG_WAVES * (uint32_t)k;
             uint32_t tile = first_tile + c / HVS_I8X16_FRAGS;
             if (tile >= I1) tile = I1 - 1u;  // tail of the last stage: re-read a valid tile, never used
-            dma(tiles + (size_t)tile * TILE_U4 + (c % HVS_I8X16_FRAGS) * 64u + lane, &stile[buf][c * 64u]);
+            hvs_lds_dma(tiles + (size_t)tile * TILE_U4 + (c % HVS_I8X16_FRAGS) * 64u + lane, &stile[buf][c * 64u]);
         }
         if (wvs == HVS_WG_WAVES - 1u) {
             uint32_t tile = first_tile + lane / NRM_U4;
             if (tile >= I1) tile = I1 - 1u;
-            dma(nrm + (size_t)tile * NRM_U4 + (lane % NRM_U4), &snrm[buf][0]);
+            hvs_lds_dma(nrm + (size_t)tile * NRM_U4 + (lane % NRM_U4), &snrm[buf][0]);
         }
-    };
-    auto stage_barrier = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
     };
 
     hvs_i32x4 af[HVS_I8X16_FRAGS];
@@ -2452,7 +2505,7 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 
     const uint32_t nstage = hvs_ceil_div(I1 - I0, STG);
     issue_stage(0u, I0);
-    stage_barrier();
+    hvs_stage_barrier();
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): clears the compiler's scoreboard (see hvs_k_filter_mfma)
     // Tile t: [32 matrix instructions] [LDS reads of tile t+1's fragments, when it sits in the same stage] [epilogue of
     // tile t] [survivors, rarely].  The fragment registers are dead once the last matrix instruction has issued, so the
@@ -2506,12 +2559,11 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
                 const uint32_t bpx = bp;
                 const bool inner = bpx * 32u >= ra_max && bpx * 32u + 32u <= rb_min;
                 const bool more = i + 1u < t1;  // (last tile of the stage: re-read this one, unused)
-                slot += more ? 1u : 0u;
-                asm volatile("" : "+s"(slot));  // (otherwise the compiler re-derives it from i: ~8 scalar instructions per tile)
+                hvs_step_slot(slot, more ? 1u : 0u);
                 tile_body(bpx, inner, more ? i + 1u : i, slot);
             }
         }
-        stage_barrier();
+        hvs_stage_barrier();
     }
     if (active) {
         flush();
