@@ -75,6 +75,17 @@ static bool hvs_bounds_usable(int fmt, const HvsBounds& hb)
     return finite && !(hb.hmax > 1.0e30f) && !(hb.hmax > 0.0f && hb.hmax < 1.0e-20f);
 }
 
+// Tile-format state of one data set's index: what is built, what the planner decided, what was rejected
+struct HvsFormatState {
+    int built = HVS_FMT_NONE;   // format of the tiles both orderings carry (HVS_FMT_NONE: no usable tiles)
+    bool built_rot = false;     // ... INT8 tiles, cut from the rotated vectors
+    int planned = HVS_FMT_BF16; // what HVS_ENGINE_AUTO uses for this data set (HVS_FMT_NONE: no filter beats the exact engine)
+    bool i8_usable = false;     // the INT8 quantiser has a finite, non-zero spread to work with
+    bool i8_rot = false;        // the INT8 centre / scale (d_quant) live in the rotated space (HvsQuant::rot): the next INT8 build is rotated
+    bool i8_rejected = false;   // the INT8 tiles were built and their bound was unusable: do not try again
+    bool f16_rejected = false;  // likewise the FP16 tiles (components beyond the half-precision range)
+};
+
 // Workspace of ONE query batch and the stream it runs on -- a "lane".  A context owns two (round 4): the last level of batch b
 // ends with its re-scoring (HBM-bound gathers) and the final merge (latency-bound), both of which leave the matrix pipes idle,
 // and batch b+1 begins with preparation, the exact seed and two small filter levels that cannot fill the chip; with batch
@@ -159,18 +170,14 @@ struct hvs_ctx : HvsLane {
     unsigned long long* d_counters = nullptr;
 
     // ---- MFMA engine: index over D (two orderings) ...
-    bool have_index = false;
+    // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
+    // `fmt.built != HVS_FMT_NONE` -- usable tiles exist on top of them.  Tiles imply orderings; free_index drops both.
+    bool have_order = false;
+    HvsFormatState fmt;
     HvsLevels lv{};                       // same block count for both orderings
     HvsOrdering ord[2];  // [0] the (C,T) ordering, [1] the T ordering
     HvsBounds* d_bounds = nullptr;
     HvsQuant* d_quant = nullptr;                          // INT8 format: centre and scale
-    int tile_fmt = HVS_FMT_NONE;                          // format of the tiles currently built
-    int planned_fmt = HVS_FMT_BF16;                       // what HVS_ENGINE_AUTO uses for this data set
-    bool i8_usable = false;
-    bool i8_rot = false;       // the INT8 centre / scale (d_quant) and tiles live in the rotated space (HvsQuant::rot)
-    bool i8_rot_built = false; // ... and the INT8 tiles currently built were cut from it
-    bool i8_rejected = false;  // the INT8 tiles were built and their bound was unusable: do not try again
-    bool f16_rejected = false; // likewise the FP16 tiles (components beyond the half-precision range)
     double index_ms = 0.0;
     bool index_too_large = false;  // more than 2^27 rows: no filter index (hvs_timing.flags says so)
     // (the per-batch state of the filter engines lives in the lanes)
@@ -369,6 +376,43 @@ int dev_alloc(hvs_ctx* c, T** p, size_t count)
     HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
     return HVS_OK;
 }
+
+// Device temporaries of one scope, freed when it ends, whichever way it ends.  `lend`: the temporary also stands in for one of
+// the context's long-lived buffers for that time (swapped into `*field` now, swapped back before it is freed).
+struct ScopedDevBufs {
+    void* buf[5] = {};
+    void** lent[5] = {};
+    int count = 0;
+    ScopedDevBufs() = default;
+    ScopedDevBufs(const ScopedDevBufs&) = delete;
+    ScopedDevBufs& operator=(const ScopedDevBufs&) = delete;
+    template <typename T>
+    hipError_t alloc(T** out, size_t n)
+    {
+        if (count == 5) return hipErrorInvalidValue;
+        const hipError_t e = hipMalloc(&buf[count], n * sizeof(T));
+        if (e != hipSuccess) return e;
+        *out = static_cast<T*>(buf[count++]);
+        return hipSuccess;
+    }
+    template <typename T>
+    hipError_t lend(T** field, size_t n)
+    {
+        T* mine = nullptr;
+        const hipError_t e = alloc(&mine, n);
+        if (e != hipSuccess) return e;
+        lent[count - 1] = reinterpret_cast<void**>(field);
+        std::swap(*lent[count - 1], buf[count - 1]);
+        return hipSuccess;
+    }
+    ~ScopedDevBufs()
+    {
+        while (count-- > 0) {
+            if (lent[count]) std::swap(*lent[count], buf[count]);
+            if (buf[count]) (void)hipFree(buf[count]);
+        }
+    }
+};
 
 // Event pair around one launch of the dominant kernel (HIP events on the library's own stream: bench.py's roofline
 // reads their sum).  begin returns the pair's index or -1 (events could not be created: the launch goes untimed).
@@ -578,13 +622,11 @@ void free_index(hvs_ctx* c)
         o = HvsOrdering{};
         o.lp = lp;
     }
-    c->have_index = false;
+    c->have_order = false;
     c->lp_valid = false;  // (counts along the orderings that have just gone)
-    c->tile_fmt = HVS_FMT_NONE;
-    c->i8_usable = false;
-    c->i8_rot = false;
-    c->i8_rejected = false;
-    c->f16_rejected = false;
+    // everything the last data set taught, `planned` and `built_rot` included: nothing reads those two before choose_format
+    // and build_tiles have written them for the next index
+    c->fmt = HvsFormatState{};
 }
 
 // Planner of HVS_ENGINE_AUTO, first guess: which tile format filters this data set more cheaply.  The INT8 filter runs
@@ -603,6 +645,12 @@ int rotate_policy()
     return std::atoi(v) != 0 ? 1 : 0;
 }
 
+// HVS_FILTER_FORMAT = "bf16" / "f16" / "i8": A/B override of the planner; set to anything, it also switches the probe off
+// (read per data set, like HVS_I8_ROTATE)
+const char* forced_format() { return std::getenv("HVS_FILTER_FORMAT"); }
+// HVS_PLAN_BF16_COST: what a 16-bit float filter launch costs in hundredths of an INT8 one, for the model and for the probe
+double plan_cost16() { return env_u32("HVS_PLAN_BF16_COST", 194u, 100u, 1000u) / 100.0; }
+
 // centre and scale of the INT8 format over the vector components (`rot` false) or over their rotated images (HvsQuant)
 int set_quant(hvs_ctx* c, bool rot)
 {
@@ -614,15 +662,15 @@ int set_quant(hvs_ctx* c, bool rot)
         hipLaunchKernelGGL(hvs_k_minmax, dim3(std::min(c->n, 4096u)), dim3(128), 0, c->stream, c->d_data, c->n, c->d_quant);
     hipLaunchKernelGGL(hvs_k_quant_params, dim3(1), dim3(128), 0, c->stream, c->d_quant);
     HVS_HIP(c, hipGetLastError());
-    c->i8_rot = rot;
+    c->fmt.i8_rot = rot;
     return HVS_OK;
 }
 
 int choose_format(hvs_ctx* c)
 {
     const uint32_t n = c->n;
-    c->planned_fmt = HVS_FMT_F16;
-    c->i8_usable = false;
+    c->fmt.planned = HVS_FMT_F16;
+    c->fmt.i8_usable = false;
     int rcq = set_quant(c, false);  // (the model below prices the plain INT8 format; HVS_I8_ROTATE=1 switches afterwards)
     if (rcq) return rcq;
     if (!c->d_bounds) HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_bounds), sizeof(HvsBounds)));
@@ -638,9 +686,9 @@ int choose_format(hvs_ctx* c)
     HVS_HIP(c, hipMemcpyAsync(&sd, reinterpret_cast<const char*>(c->d_quant) + offsetof(HvsQuant, sd), sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    c->i8_usable = sd > 0.0 && std::isfinite(sd);
+    c->fmt.i8_usable = sd > 0.0 && std::isfinite(sd);
     const bool f16_ok = std::isfinite(hb.nb_df) && std::isfinite(hb.e_df) && hb.hmax < 3.0e4f;
-    if (!f16_ok) c->planned_fmt = HVS_FMT_BF16;
+    if (!f16_ok) c->fmt.planned = HVS_FMT_BF16;
     if (hb.pair_n >= 16u) {
         const double mean = hb.pair_sum / hb.pair_n;
         const double var = hb.pair_sumsq / hb.pair_n - mean * mean;
@@ -659,17 +707,17 @@ int choose_format(hvs_ctx* c)
         // cost model in units of one INT8 filter launch: a 16-bit float filter takes kPlan16 times as long, re-scoring
         // kPlanRescore times at inflation 1 and grows with the candidates (HVS_PLAN_BF16_COST / HVS_PLAN_RESCORE_COST, in
         // hundredths, override the measured defaults of profiles/)
-        const double kPlan16 = env_u32("HVS_PLAN_BF16_COST", 194u, 100u, 1000u) / 100.0;
+        const double kPlan16 = plan_cost16();
         const double kPlanRescore = env_u32("HVS_PLAN_RESCORE_COST", 15u, 1u, 1000u) / 100.0;
         const double cost_f = kPlan16 + kPlanRescore * (f16_ok ? infl_f : infl_bf), cost8 = 1.0 + kPlanRescore * infl8;
-        if (c->i8_usable && cost8 < cost_f && infl8 < 6.0) c->planned_fmt = kI8Fmt;
+        if (c->fmt.i8_usable && cost8 < cost_f && infl8 < 6.0) c->fmt.planned = kI8Fmt;
     }
-    if (const char* f = std::getenv("HVS_FILTER_FORMAT")) {  // A/B override: "bf16" / "f16" / "i8"
-        if (!std::strcmp(f, "bf16")) c->planned_fmt = HVS_FMT_BF16;
-        if (!std::strcmp(f, "f16")) c->planned_fmt = HVS_FMT_F16;
-        if (!std::strcmp(f, "i8")) c->planned_fmt = kI8Fmt;
+    if (const char* f = forced_format()) {
+        if (!std::strcmp(f, "bf16")) c->fmt.planned = HVS_FMT_BF16;
+        if (!std::strcmp(f, "f16")) c->fmt.planned = HVS_FMT_F16;
+        if (!std::strcmp(f, "i8")) c->fmt.planned = kI8Fmt;
     }
-    if (rotate_policy() == 1 && kI8Fmt == HVS_FMT_I8X16 && c->i8_usable) {
+    if (rotate_policy() == 1 && kI8Fmt == HVS_FMT_I8X16 && c->fmt.i8_usable) {
         if ((rcq = set_quant(c, true))) return rcq;
         double sdr = 0.0;
         HVS_HIP(c, hipMemcpyAsync(&sdr, reinterpret_cast<const char*>(c->d_quant) + offsetof(HvsQuant, sd), sizeof(double),
@@ -726,32 +774,32 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
 // every mask change that only kills rows and at the end of every tile build while rows are dead.
 int patch_tiles(hvs_ctx* c)
 {
-    if (!c->n_dead || c->tile_fmt == HVS_FMT_NONE || !c->ord[0].tiles || !c->d_live || !c->d_mask_stat) return HVS_OK;
+    if (!c->n_dead || c->fmt.built == HVS_FMT_NONE || !c->ord[0].tiles || !c->d_live || !c->d_mask_stat) return HVS_OK;
     const HvsLevels L = c->lv;
     HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
     for (const HvsOrdering& o : c->ord)
         hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, o.perm, c->n, L, o.bpos, o.tiles,
-                           reinterpret_cast<int*>(o.nrm), c->tile_fmt, c->d_mask_stat);
+                           reinterpret_cast<int*>(o.nrm), c->fmt.built, c->d_mask_stat);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
 
-// (re)build the level-interleaved tiles of both orderings in format `fmt`; the orderings must exist
+// (re)build the level-interleaved tiles of both orderings in format `fmt`; the orderings must exist.  An unusable bound is no
+// error: fmt.built stays HVS_FMT_NONE
 int build_tiles(hvs_ctx* c, int fmt)
 {
     const HvsLevels L = c->lv;
     const uint32_t n = c->n;
     int rc;
-    c->tile_fmt = HVS_FMT_NONE;
-    c->have_index = false;
+    c->fmt.built = HVS_FMT_NONE;
     if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
     // free first: the two formats never coexist (D = 1e8: 44.8 GB of BF16 tiles, 20.8 GB of INT8 tiles)
     for (HvsOrdering& o : c->ord) {
         if ((rc = dev_alloc(c, &o.tiles, (size_t)0))) return rc;
         if ((rc = dev_alloc(c, &o.nrm, (size_t)0))) return rc;
     }
-    const HvsHostFmt F = hvs_host_fmt(fmt, c->i8_rot);
+    const HvsHostFmt F = hvs_host_fmt(fmt, c->fmt.i8_rot);
     for (HvsOrdering& o : c->ord) {
         if ((rc = dev_alloc(c, &o.tiles, (size_t)L.nblk * F.tile_u4))) return rc;
         if (F.nrm_u4 && (rc = dev_alloc(c, &o.nrm, (size_t)L.nblk * F.nrm_u4))) return rc;
@@ -774,15 +822,32 @@ int build_tiles(hvs_ctx* c, int fmt)
     if (kTrace)
         std::fprintf(stderr, "[hvs trace] tiles built: format %d usable %d e_d8 %.6g n_d8 %.6g e_d %.6g nb_d %.6g hmax %.6g rho %.6g\n", fmt, (int)ok,
                      (double)hb.e_d8, (double)hb.n_d8, (double)hb.e_d, (double)hb.nb_d, (double)hb.hmax, (double)hb.rho);
-    if (!ok) return HVS_OK;  // have_index stays false
-    c->tile_fmt = fmt;
-    c->have_index = true;
-    c->i8_rot_built = HVS_IS_I8(fmt) && c->i8_rot;
+    if (!ok) return HVS_OK;
+    c->fmt.built = fmt;
+    c->fmt.built_rot = HVS_IS_I8(fmt) && c->fmt.i8_rot;
     return patch_tiles(c);  // (nothing while every row is live)
 }
 
 int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last);
 HvsGuessTable plan_guess(uint32_t k, bool proven, uint32_t pfail);
+
+bool is_filter_engine(int engine) { return engine == HVS_ENGINE_MFMA_FILTER || engine == HVS_ENGINE_MFMA_I8 || engine == HVS_ENGINE_MFMA_F16; }
+// the engine setting asks for a filter: forced, or HVS_ENGINE_AUTO on a data set the planner found one for (the callers add
+// what else they need: orderings, the sampled prefix, the summation order)
+bool filter_engine_selected(const hvs_ctx* c)
+{
+    return is_filter_engine(c->engine) || (c->engine == HVS_ENGINE_AUTO && c->n >= kMfmaMinRows && c->fmt.planned != HVS_FMT_NONE);
+}
+// hvs_timing.engine of a call that the tiles of format `fmt` filtered
+int timing_engine_for(int fmt) { return HVS_IS_I8(fmt) ? HVS_ENGINE_MFMA_I8 : fmt == HVS_FMT_F16 ? HVS_ENGINE_MFMA_F16 : HVS_ENGINE_MFMA_FILTER; }
+
+// The precision chain INT8 -> FP16 -> BF16: the next format below `fmt` that this data set has not rejected (HVS_FMT_NONE
+// below BF16, the last resort, which is built whatever happened to it before)
+int next_format_down(const hvs_ctx* c, int fmt)
+{
+    if (HVS_IS_I8(fmt) && !c->fmt.f16_rejected) return HVS_FMT_F16;
+    return fmt == HVS_FMT_BF16 ? HVS_FMT_NONE : HVS_FMT_BF16;
+}
 
 // the tile format the context's engine setting asks for (HVS_FMT_NONE: HVS_ENGINE_AUTO found no filter worth running)
 int want_format(const hvs_ctx* c)
@@ -791,32 +856,25 @@ int want_format(const hvs_ctx* c)
     switch (c->engine) {
         case HVS_ENGINE_MFMA_FILTER: want = HVS_FMT_BF16; break;
         case HVS_ENGINE_MFMA_F16: want = HVS_FMT_F16; break;
-        case HVS_ENGINE_MFMA_I8: want = c->i8_usable ? kI8Fmt : HVS_FMT_F16; break;
-        default: want = c->planned_fmt; break;
+        case HVS_ENGINE_MFMA_I8: want = c->fmt.i8_usable ? kI8Fmt : HVS_FMT_F16; break;
+        default: want = c->fmt.planned; break;
     }
-    if (HVS_IS_I8(want) && c->i8_rejected) want = HVS_FMT_F16;
-    if (want == HVS_FMT_F16 && c->f16_rejected) want = HVS_FMT_BF16;
-    return want;
+    const bool rejected = HVS_IS_I8(want) ? c->fmt.i8_rejected : (want == HVS_FMT_F16 && c->fmt.f16_rejected);
+    return rejected ? next_format_down(c, want) : want;
 }
 
-// build `want`, or the next format down the chain INT8 -> FP16 -> BF16 whose bound is usable on this data set
-// (have_index stays false when none is)
+// build `want`, or the next format down the chain whose bound is usable on this data set (fmt.built stays HVS_FMT_NONE when
+// none is)
 int build_tiles_chain(hvs_ctx* c, int want)
 {
-    for (;;) {
+    for (; want != HVS_FMT_NONE; want = next_format_down(c, want)) {
         int rc = build_tiles(c, want);
         if (rc) return rc;
-        if (c->have_index) return HVS_OK;
-        if (HVS_IS_I8(want)) {
-            c->i8_rejected = true;
-            want = c->f16_rejected ? HVS_FMT_BF16 : HVS_FMT_F16;
-        } else if (want == HVS_FMT_F16) {
-            c->f16_rejected = true;
-            want = HVS_FMT_BF16;
-        } else {
-            return HVS_OK;
-        }
+        if (c->fmt.built != HVS_FMT_NONE) return HVS_OK;
+        if (HVS_IS_I8(want)) c->fmt.i8_rejected = true;
+        if (want == HVS_FMT_F16) c->fmt.f16_rejected = true;
     }
+    return HVS_OK;
 }
 
 // Planner of HVS_ENGINE_AUTO, second step: measure instead of model.  A probe batch of 1024 rows of D used as type-0
@@ -832,28 +890,15 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
 {
     constexpr uint32_t P = 1024;
     *cost = 1.0e9;
-    // the probe has its own query / result / re-run buffers: resident queries and results of the caller stay untouched
-    float *pq = nullptr, *pdist = nullptr;
-    uint32_t *pids = nullptr, *povf = nullptr, *pretry = nullptr;
-    auto release = [&]() {
-        void* bufs[] = {pq, pdist, pids, povf, pretry};
-        for (void* b : bufs)
-            if (b) (void)hipFree(b);
-    };
-    if (hipMalloc(reinterpret_cast<void**>(&pq), (size_t)P * HVS_QCOLS * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&pdist), (size_t)P * c->k * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&pids), (size_t)P * c->k * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&povf), (size_t)P * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&pretry), (size_t)P * sizeof(uint32_t)) != hipSuccess) {
+    // the probe has its own query / result / re-run buffers, in the context's fields while it runs: resident queries and
+    // results of the caller stay untouched
+    ScopedDevBufs own;
+    if (own.lend(&c->d_q, (size_t)P * HVS_QCOLS) != hipSuccess || own.lend(&c->d_out_dists, (size_t)P * c->k) != hipSuccess ||
+        own.lend(&c->d_out_ids, (size_t)P * c->k) != hipSuccess || own.lend(&c->d_ovf_list, (size_t)P) != hipSuccess ||
+        own.lend(&c->d_retry_list, (size_t)P) != hipSuccess) {
         (void)hipGetLastError();
-        release();
         return fail(c, HVS_ENOMEM, "planner probe: out of device memory");
     }
-    std::swap(c->d_q, pq);
-    std::swap(c->d_out_ids, pids);
-    std::swap(c->d_out_dists, pdist);
-    std::swap(c->d_ovf_list, povf);
-    std::swap(c->d_retry_list, pretry);
     const uint32_t step = std::max(1u, c->n / P);
     hipLaunchKernelGGL(hvs_k_probe_queries, dim3(hvs_ceil_div(P * HVS_QCOLS, 256u)), dim3(256), 0, c->stream, c->d_data, c->n, step, P, c->d_q);
     hipError_t e = hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream);
@@ -872,15 +917,9 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
         if (e != hipSuccess) rc = fail(c, HVS_EHIP, "planner probe: copy failed");
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, HVS_EHIP, "planner probe: synchronisation failed");
-    std::swap(c->d_q, pq);
-    std::swap(c->d_out_ids, pids);
-    std::swap(c->d_out_dists, pdist);
-    std::swap(c->d_ovf_list, povf);
-    std::swap(c->d_retry_list, pretry);
-    release();
     c->n_launch_events = 0;
     if (rc) return rc;
-    const double base = HVS_IS_I8(c->tile_fmt) ? 1.0 : env_u32("HVS_PLAN_BF16_COST", 194u, 100u, 1000u) / 100.0;
+    const double base = HVS_IS_I8(c->fmt.built) ? 1.0 : plan_cost16();
     *cost = base + 2650.0 / (double)c->n * ((double)h[2] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
     // what a filter without any error band would have handed over: m (radix - 1) rows per level under the guessed thresholds
     double ideal = 0.0;
@@ -904,51 +943,94 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
 // the precision chain; planned_fmt = HVS_FMT_NONE when no filter beats the exact engine
 int plan_by_probe(hvs_ctx* c)
 {
-    if (!env_u32("HVS_PLAN_PROBE", 1u, 0u, 1u) || std::getenv("HVS_FILTER_FORMAT")) return HVS_OK;
-    double cost = 0.0, infl = 0.0, failed = 0.0;
-    int rc = probe_format(c, &cost, &infl, &failed);
+    if (!env_u32("HVS_PLAN_PROBE", 1u, 0u, 1u) || forced_format()) return HVS_OK;
+    // probe the tiles that are built and say so in the trace (`ok` stays false when none are: nothing to compare)
+    struct Probed {
+        bool ok = false;
+        double cost = 0.0, infl = 0.0, failed = 0.0;
+    } p;
+    auto probe = [&](const char* tag) -> int {
+        p = Probed{};
+        if (c->fmt.built == HVS_FMT_NONE) return HVS_OK;
+        const int rc = probe_format(c, &p.cost, &p.infl, &p.failed);
+        if (rc) return rc;
+        p.ok = true;
+        if (kTrace)
+            std::fprintf(stderr, "[hvs trace] planner probe: format %d%s cost %.3f inflation %.2f failed %.4f\n", c->fmt.built, tag, p.cost, p.infl,
+                         p.failed);
+        return HVS_OK;
+    };
+    int rc = probe("");
     if (rc) return rc;
-    if (kTrace) std::fprintf(stderr, "[hvs trace] planner probe: format %d cost %.3f inflation %.2f failed %.4f\n", c->tile_fmt, cost, infl, failed);
-    int best = c->tile_fmt;
-    bool best_rot = c->i8_rot;
-    double best_cost = cost;
+    int best = c->fmt.built;
+    bool best_rot = c->fmt.i8_rot;
+    double best_cost = p.cost;
     // INT8 tiles stay unless their band visibly lets too much through on this data (the cost formula is not trusted to
     // split hairs between formats that both work: at small n everything is launch latency).  Otherwise the candidates are
     // probed in turn -- the rotated INT8 tiles (same filter rate; HvsQuant), then the FP16 tiles (half the rate, an 8x tighter
     // band) -- and the cheapest stays.
-    if (HVS_IS_I8(c->tile_fmt) && (infl > 2.5 || failed > 0.01)) {
-        const int had = c->tile_fmt;
-        const bool had_rot = c->i8_rot;
-        if (had == HVS_FMT_I8X16 && !had_rot && rotate_policy() != 0) {
+    if (HVS_IS_I8(c->fmt.built) && (p.infl > 2.5 || p.failed > 0.01)) {
+        const int had = c->fmt.built;
+        if (had == HVS_FMT_I8X16 && !c->fmt.i8_rot && rotate_policy() != 0) {
             if ((rc = set_quant(c, true))) return rc;
             if ((rc = build_tiles(c, had))) return rc;
-            if (c->have_index) {
-                if ((rc = probe_format(c, &cost, &infl, &failed))) return rc;
-                if (kTrace) std::fprintf(stderr, "[hvs trace] planner probe: format %d (rotated) cost %.3f inflation %.2f failed %.4f\n", c->tile_fmt, cost, infl, failed);
-                if (cost < best_cost) {
-                    best_rot = true;
-                    best_cost = cost;
-                }
+            if ((rc = probe(" (rotated)"))) return rc;
+            if (p.ok && p.cost < best_cost) {
+                best_rot = true;
+                best_cost = p.cost;
             }
         }
-        if (!c->f16_rejected) {
+        if (!c->fmt.f16_rejected) {
             if ((rc = build_tiles_chain(c, HVS_FMT_F16))) return rc;
-            if (c->have_index && (rc = probe_format(c, &cost, &infl, &failed))) return rc;
-            if (kTrace) std::fprintf(stderr, "[hvs trace] planner probe: format %d cost %.3f inflation %.2f failed %.4f\n", c->tile_fmt, cost, infl, failed);
-            if (c->have_index && cost < best_cost) {
-                best = c->tile_fmt;
-                best_cost = cost;
+            if ((rc = probe(""))) return rc;
+            if (p.ok && p.cost < best_cost) {
+                best = c->fmt.built;
+                best_cost = p.cost;
             }
         }
         if (HVS_IS_I8(best)) {  // an INT8 variant stays: its centre / scale and tiles come back if something else was built last
-            if (c->i8_rot != best_rot && (rc = set_quant(c, best_rot))) return rc;
-            if ((c->tile_fmt != best || !c->have_index || c->i8_rot_built != best_rot) && (rc = build_tiles_chain(c, had))) return rc;
-        } else if (c->i8_rot && (rc = set_quant(c, false))) {  // (a later change of engine finds the plain INT8 parameters)
+            if (c->fmt.i8_rot != best_rot && (rc = set_quant(c, best_rot))) return rc;
+            if ((c->fmt.built != best || c->fmt.built_rot != best_rot) && (rc = build_tiles_chain(c, had))) return rc;
+        } else if (c->fmt.i8_rot && (rc = set_quant(c, false))) {  // (a later change of engine finds the plain INT8 parameters)
             return rc;
         }
     }
     if (best_cost >= 140.0) best = HVS_FMT_NONE;  // no filter beats the exact engine's range scans here
-    c->planned_fmt = best;
+    c->fmt.planned = best;
+    return HVS_OK;
+}
+
+// keys and perm of both orderings: two radix sorts over temporaries that go when this returns
+int build_orderings(hvs_ctx* c)
+{
+    const uint32_t n = c->n;
+    int rc;
+    for (HvsOrdering& o : c->ord) {
+        if ((rc = dev_alloc(c, &o.keys, (size_t)n))) return rc;
+        if ((rc = dev_alloc(c, &o.perm, (size_t)n))) return rc;
+    }
+    ScopedDevBufs temps;
+    uint64_t *k_ct = nullptr, *k_t = nullptr;
+    uint32_t* ids = nullptr;
+    char* tmp = nullptr;
+    HVS_HIP(c, temps.alloc(&k_ct, (size_t)n));
+    HVS_HIP(c, temps.alloc(&k_t, (size_t)n));
+    HVS_HIP(c, temps.alloc(&ids, (size_t)n));
+    hipLaunchKernelGGL(hvs_k_attr_keys, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, n, k_ct, k_t, ids);
+    size_t tmp_bytes = 0, tmp_bytes_t = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64,
+                                             c->stream);
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes_t, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
+    if (tmp_bytes_t > tmp_bytes) tmp_bytes = tmp_bytes_t;  // each call sizes its own algorithm
+    if (e == hipSuccess) e = temps.alloc(&tmp, tmp_bytes);
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64, c->stream);
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? HVS_ENOMEM : HVS_EHIP, std::string("index sort: ") + hipGetErrorString(e));
+    c->have_order = true;
     return HVS_OK;
 }
 
@@ -963,76 +1045,21 @@ int build_index(hvs_ctx* c)
     c->index_too_large = L.nblk > HVS_ENTRY_MAX_BLOCKS;
     if (c->index_too_large) return HVS_OK;
     c->lv = L;
-    int rc;
-    uint64_t *k_ct = nullptr, *k_t = nullptr;
-    uint32_t* ids = nullptr;
-    void* tmp = nullptr;
-    auto cleanup = [&]() {
-        if (k_ct) (void)hipFree(k_ct);
-        if (k_t) (void)hipFree(k_t);
-        if (ids) (void)hipFree(ids);
-        if (tmp) (void)hipFree(tmp);
-    };
-#define HVS_TRY(expr)            \
-    do {                         \
-        if ((rc = (expr))) {     \
-            cleanup();           \
-            free_index(c);       \
-            return rc;           \
-        }                        \
-    } while (0)
-    HVS_TRY(dev_alloc(c, &k_ct, (size_t)n));
-    HVS_TRY(dev_alloc(c, &k_t, (size_t)n));
-    HVS_TRY(dev_alloc(c, &ids, (size_t)n));
-    for (HvsOrdering& o : c->ord) {
-        HVS_TRY(dev_alloc(c, &o.keys, (size_t)n));
-        HVS_TRY(dev_alloc(c, &o.perm, (size_t)n));
-    }
-    hipLaunchKernelGGL(hvs_k_attr_keys, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, n, k_ct, k_t, ids);
-    size_t tmp_bytes = 0, tmp_bytes_t = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64,
-                                             c->stream);
-    if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes_t, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
-    if (tmp_bytes_t > tmp_bytes) tmp_bytes = tmp_bytes_t;  // each call sizes its own algorithm
-    if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes);
-    if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_ct, c->ord[0].keys, ids, c->ord[0].perm, (size_t)n, 0, 64, c->stream);
-    if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_t, c->ord[1].keys, ids, c->ord[1].perm, (size_t)n, 0, 64, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        cleanup();
-        free_index(c);
-        return fail(c, e == hipErrorOutOfMemory ? HVS_ENOMEM : HVS_EHIP, std::string("index sort: ") + hipGetErrorString(e));
-    }
-    cleanup();
-    k_ct = k_t = nullptr;
-    ids = nullptr;
-    tmp = nullptr;
-#undef HVS_TRY
+    int rc = build_orderings(c);
     trace_mark(c, "orderings");
-    if ((rc = choose_format(c))) {
-        free_index(c);
-        return rc;
-    }
+    if (!rc) rc = choose_format(c);
     trace_mark(c, "format");
-    const int fmt = want_format(c);
-    if (fmt != HVS_FMT_NONE && (rc = build_tiles_chain(c, fmt))) {
-        free_index(c);
-        return rc;
-    }
+    if (!rc) rc = build_tiles_chain(c, want_format(c));  // (choose_format always plans a format)
     trace_mark(c, "tiles");
-    if (fmt != HVS_FMT_NONE && !c->have_index) free_index(c);  // no format has a usable bound: exact engine only
-    if (fmt == HVS_FMT_NONE) c->have_index = true;              // (orderings only: the exact engine's range scans)
-    if (c->have_index && c->tile_fmt != HVS_FMT_NONE && c->engine == HVS_ENGINE_AUTO && n >= kMfmaMinRows) {
-        if ((rc = plan_by_probe(c))) {
-            free_index(c);
-            return rc;
-        }
+    if (!rc && c->fmt.built != HVS_FMT_NONE && c->engine == HVS_ENGINE_AUTO && n >= kMfmaMinRows) {
+        rc = plan_by_probe(c);
         trace_mark(c, "probe");
     }
-    return HVS_OK;
+    // An error leaves no half-built index behind.  Nor does a data set on which no format has a usable bound (non-finite
+    // components, norms out of range): at load time the orderings go as well and the exact engine scans without ranges
+    // 
+    if (rc || c->fmt.built == HVS_FMT_NONE) free_index(c);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1305,7 +1332,7 @@ uint32_t proven_batch_step(const hvs_ctx* c)
 // `list` (retry batches: `proven_last`, failures go to the exact engine).
 int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last)
 {
-    const int fmt = c->tile_fmt;
+    const int fmt = c->fmt.built;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
     int rc = prep_batch(c, q0, nqb, sn == c->n && !list && !c->n_dead, fmt, false, list, want_fcap);
     if (rc) return rc;
@@ -1364,7 +1391,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     // BASELINE configs[1]/[2], 10^4 queries: m (R - 1) = 1000 rows per query to the exact kernel instead of 2 x 60 for one
     // re-score + merge less -- was measured in round 3: 2.85 ms instead of 2.08 ms per 10^4 mixed queries.  Round 2 measured
     // the same for doubling levels.)
-    const HvsFilterKernel filter_kernel = hvs_host_fmt(fmt, c->i8_rot).filter;  // picked once per batch
+    const HvsFilterKernel filter_kernel = hvs_host_fmt(fmt, c->fmt.i8_rot).filter;  // picked once per batch
     for (uint32_t level = 1; level <= L.K;) {
         const uint32_t last = level;
         // (the groups' entry counters are zero here: hvs_k_prep clears them for the first level, every merge for the next)
@@ -1445,7 +1472,7 @@ int resolve_overflow(hvs_ctx* c)
     // are built now -- for this call's list and for the calls to come -- instead of sending them all to the exact engine
     // at 1 % of a filter's rate.  The list moves aside (the filter batches append their own failures to the exact list).
     c->demoted_queries = 0;
-    if (c->engine == HVS_ENGINE_AUTO && HVS_IS_I8(c->tile_fmt) && novf >= std::max(256u, c->timing.nq / 50u) &&
+    if (c->engine == HVS_ENGINE_AUTO && HVS_IS_I8(c->fmt.built) && novf >= std::max(256u, c->timing.nq / 50u) &&
         env_u32("HVS_DEMOTE", 1u, 0u, 1u)) {
         if (c->demote_cap < c->res_cap) {
             int rc = dev_alloc(c, &c->d_demote_list, (size_t)c->res_cap);
@@ -1454,9 +1481,9 @@ int resolve_overflow(hvs_ctx* c)
         }
         // The 16-bit float tiles first: when HBM has no room for them next to D (they are 1.7x the INT8 tiles) the INT8
         // tiles come back and the exact engine answers the list as it always did -- slower, never an error.
-        const int had = c->tile_fmt;
-        int rc = build_tiles_chain(c, c->f16_rejected ? HVS_FMT_BF16 : HVS_FMT_F16);
-        if (rc == HVS_ENOMEM || (!rc && !c->have_index)) {
+        const int had = c->fmt.built;
+        int rc = build_tiles_chain(c, next_format_down(c, had));
+        if (rc == HVS_ENOMEM || (!rc && c->fmt.built == HVS_FMT_NONE)) {
             (void)hipGetLastError();
             c->err.clear();
             rc = build_tiles_chain(c, had);
@@ -1466,13 +1493,12 @@ int resolve_overflow(hvs_ctx* c)
                 rc = HVS_OK;
             }
             if (rc) return rc;
-            if (!c->have_index) c->have_index = true;  // (orderings only: the exact engine's range scans)
         } else if (rc) {
             return rc;
         } else {
             HVS_HIP(c, hipMemcpyAsync(c->d_demote_list, c->d_ovf_list, (size_t)novf * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
             HVS_HIP(c, hipMemsetAsync(c->d_ovf_count, 0, sizeof(uint32_t), c->stream));
-            c->planned_fmt = c->tile_fmt;
+            c->fmt.planned = c->fmt.built;
             const uint32_t step = proven_batch_step(c);
             uint32_t done = novf;
             for (uint32_t off = 0; off < novf; off += step) {
@@ -1490,7 +1516,7 @@ int resolve_overflow(hvs_ctx* c)
             HVS_HIP(c, hipStreamSynchronize(c->stream));
             novf = c->h_ovf[0];
             c->timing.flags |= HVS_TIMING_FORMAT_CHANGED;
-            c->timing.engine = c->tile_fmt == HVS_FMT_F16 ? HVS_ENGINE_MFMA_F16 : HVS_ENGINE_MFMA_FILTER;
+            c->timing.engine = timing_engine_for(c->fmt.built);
         }
     }
     c->fallback_queries = novf;
@@ -1596,20 +1622,15 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
     // the exact engine answers.
-    bool mfma = c->have_index && sampled >= of_rows / 4u && sampled > 0u && !c->scalar_order &&
-                (c->engine == HVS_ENGINE_MFMA_FILTER || c->engine == HVS_ENGINE_MFMA_I8 || c->engine == HVS_ENGINE_MFMA_F16 ||
-                 (c->engine == HVS_ENGINE_AUTO && c->n >= kMfmaMinRows && c->planned_fmt != HVS_FMT_NONE));
+    bool mfma = c->have_order && sampled >= of_rows / 4u && sampled > 0u && !c->scalar_order && filter_engine_selected(c);
     if (mfma) {
         // the tiles exist in one format at a time: an engine choice made after the load rebuilds them
         const int want = want_format(c);
-        if (want != c->tile_fmt) {
+        if (want != c->fmt.built) {
             int rc = build_tiles_chain(c, want);
             if (rc) return rc;
-            if (!c->have_index) {  // no usable bound at all: orderings only, the exact engine answers
-                c->have_index = true;
-                mfma = false;
-            }
         }
+        mfma = c->fmt.built != HVS_FMT_NONE;  // (no usable bound at all: the exact engine answers, on the orderings)
     }
     c->timing_valid = false;
     c->n_launch_events = 0;
@@ -1620,7 +1641,7 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
     HVS_HIP(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream));
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
-    const bool ranges = !mfma && c->have_index;  // exact engine: scan position ranges when the index exists
+    const bool ranges = !mfma && c->have_order;  // exact engine: scan position ranges when the orderings exist
     const std::vector<uint32_t> sched = batch_schedule(nq, mfma ? kBatchMfma : kBatch, host_pipeline && mfma);
     // Two lanes (HvsLane): every other batch of a filter-engine call runs on the spare lane's stream and workspace, so that
     // its preparation, seed and low levels share the chip with the previous batch's last re-scoring and final merge.  The
@@ -1690,11 +1711,10 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
     }
     c->timing = hvs_timing{};
     c->timing.nq = nq;
-    c->timing.engine = mfma ? (HVS_IS_I8(c->tile_fmt) ? HVS_ENGINE_MFMA_I8 : c->tile_fmt == HVS_FMT_F16 ? HVS_ENGINE_MFMA_F16 : HVS_ENGINE_MFMA_FILTER)
-                          : HVS_ENGINE_EXACT_SCAN;
+    c->timing.engine = mfma ? timing_engine_for(c->fmt.built) : HVS_ENGINE_EXACT_SCAN;
     c->timing.load_ms = c->load_ms;
     c->timing.n_gpus = 1;
-    c->timing.flags = (c->index_too_large ? HVS_TIMING_INDEX_TOO_LARGE : 0u) | (mfma && HVS_IS_I8(c->tile_fmt) && c->i8_rot_built ? HVS_TIMING_I8_ROTATED : 0u);
+    c->timing.flags = (c->index_too_large ? HVS_TIMING_INDEX_TOO_LARGE : 0u) | (mfma && HVS_IS_I8(c->fmt.built) && c->fmt.built_rot ? HVS_TIMING_I8_ROTATED : 0u);
     c->timing_valid = true;
     join_on_error.ok = true;
     return HVS_OK;
@@ -1849,10 +1869,7 @@ int leaf_reserve(hvs_ctx* c, uint32_t nq)
     }
     // (the filter workspace only when a filter engine is going to run: 4096 <= n < 32768 under AUTO has an index for the
     // range scans of the exact engine, whose batches are kBatch queries)
-    const bool filter_runs = c->have_index && (c->engine == HVS_ENGINE_MFMA_FILTER || c->engine == HVS_ENGINE_MFMA_I8 ||
-                                               c->engine == HVS_ENGINE_MFMA_F16 ||
-                                               (c->engine == HVS_ENGINE_AUTO && c->n >= kMfmaMinRows && c->planned_fmt != HVS_FMT_NONE));
-    if (filter_runs) {
+    if (c->have_order && filter_engine_selected(c)) {
         if ((rc = ensure_filter_workspace(c, std::min(nq, kBatchMfma)))) return rc;
         if ((rc = ensure_items(c))) return rc;
         // calls of two batches and more alternate between two lanes: the spare lane's largest batch under either schedule (the
@@ -1878,7 +1895,7 @@ int leaf_reserve(hvs_ctx* c, uint32_t nq)
         }
         return rc;
     }
-    if (c->have_index) return ensure_filter_workspace(c, std::min(nq, kBatch));
+    if (c->have_order) return ensure_filter_workspace(c, std::min(nq, kBatch));
     const uint32_t nqb = std::min(nq, kBatch);
     return ensure_batch_workspace(c, nqb, make_plan(nqb, c->n ? c->n : 1u));
 }
@@ -1912,9 +1929,7 @@ int finish_data(hvs_ctx* c)
     c->load_ms = ms;
     free_index(c);
     // the index (two orderings + tiles) serves both engines: the exact engine scans position ranges
-    if (c->n < kIndexMinRows && c->engine != HVS_ENGINE_MFMA_FILTER && c->engine != HVS_ENGINE_MFMA_I8 &&
-        c->engine != HVS_ENGINE_MFMA_F16)
-        return HVS_OK;
+    if (c->n < kIndexMinRows && !is_filter_engine(c->engine)) return HVS_OK;
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
     int rc = build_index(c);
     if (rc == HVS_ENOMEM) {
@@ -2450,11 +2465,9 @@ int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_l
     c->n_dead = c->n - n_live;
     c->cut_valid = false;
     c->lp_valid = false;
-    if (c->have_index && c->tile_fmt != HVS_FMT_NONE) {
+    if (c->fmt.built != HVS_FMT_NONE) {
         if (revived) {
-            const int fmt = c->tile_fmt;
-            if ((rc = build_tiles(c, fmt))) return rc;
-            if (!c->have_index) c->have_index = true;  // (cannot happen for a format that was usable: orderings only then)
+            if ((rc = build_tiles(c, c->fmt.built))) return rc;
         } else if ((rc = patch_tiles(c))) {
             return rc;
         }
@@ -2708,13 +2721,11 @@ const char* hvs_last_error(const hvs_ctx* c) { return c ? c->err.c_str() : "hvs:
 int hvs_set_engine(hvs_ctx* c, int engine)
 {
     if (!c) return HVS_EINVAL;
-    if (engine != HVS_ENGINE_AUTO && engine != HVS_ENGINE_EXACT_SCAN && engine != HVS_ENGINE_MFMA_FILTER &&
-        engine != HVS_ENGINE_MFMA_I8 && engine != HVS_ENGINE_MFMA_F16)
+    if (engine != HVS_ENGINE_AUTO && engine != HVS_ENGINE_EXACT_SCAN && !is_filter_engine(engine))
         return fail(c, HVS_EINVAL, "hvs_set_engine: unknown engine");
     c->engine = engine;
     if (!c->kids.empty()) return for_each_leaf(c, [&](uint32_t r) { return hvs_set_engine(c->kids[r], engine); });
-    if (c->d_data && !c->have_index &&
-        (engine == HVS_ENGINE_MFMA_FILTER || engine == HVS_ENGINE_MFMA_I8 || engine == HVS_ENGINE_MFMA_F16 || c->n >= kIndexMinRows)) {
+    if (c->d_data && !c->have_order && (is_filter_engine(engine) || c->n >= kIndexMinRows)) {
         HVS_HIP(c, hipSetDevice(c->device));
         return build_index(c);
     }

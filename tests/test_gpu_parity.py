@@ -810,6 +810,43 @@ def test_auto_engine_changes_tile_format_when_queries_leave_the_box():
     T.check_parity(nodes, outside[:64], want_out[0][:64], ref, got_dists=want_out[1][:64])
 
 
+def test_one_context_walks_through_the_index_and_tile_format_states():
+    """ONE context through every state of its index: AUTO's planned INT8 tiles, every forced format and the exact engine
+    on the same orderings, a data set on which no format has a usable bound (a few inf components: no index, the exact
+    engine answers, also when a filter engine is forced afterwards), then the clean rows again.  n is just above the size
+    from which AUTO plans and probes.  After every step: the oracle's ids and distance bits, the engine that ran, the flags."""
+    n, nq, ncat = 40_000, 96, 5
+    nodes = T.gen_data(n, 91, T.GEN_V1, ncat)
+    queries = T.gen_queries(nq, 92, T.GEN_V1, ncat)
+    bad = nodes.copy()
+    bad[[3, 777, 9_000, 20_001, 39_999], 40] = np.inf
+    refs = {id(d): T.oracle_query(d, queries) for d in (nodes, bad)}
+
+    def step(e, d, what, engine):
+        ids, dists = e.query(queries, 1.0)
+        t = e.last_timing()
+        print(what, "-> engine", t.engine, "flags", t.flags, "fallback", t.fallback_queries, "retried", t.retry_queries)
+        ref, refd = refs[id(d)]
+        T.check_parity(d, queries, ids, ref, got_dists=dists)
+        assert np.array_equal(dists.view(np.uint32), refd.view(np.uint32)), what
+        assert (t.engine, t.flags) == (engine, 0), (what, t.engine, t.flags)
+
+    with PKG.Engine(0) as e:
+        e.load_data(nodes)                                  # AUTO
+        step(e, nodes, "load under AUTO", PKG.ENGINE_MFMA_I8)
+        for engine, ran in ((PKG.ENGINE_MFMA_I8, 3), (PKG.ENGINE_MFMA_F16, 4), (PKG.ENGINE_MFMA_FILTER, 2),
+                            (PKG.ENGINE_EXACT_SCAN, 1), (PKG.ENGINE_AUTO, 3)):
+            e.set_engine(engine)
+            step(e, nodes, f"set_engine({engine})", ran)
+        e.load_data(bad)
+        step(e, bad, "non-finite rows under AUTO", PKG.ENGINE_EXACT_SCAN)
+        e.set_engine(PKG.ENGINE_MFMA_F16)
+        step(e, bad, "non-finite rows, FP16 filter forced", PKG.ENGINE_EXACT_SCAN)
+        e.set_engine(PKG.ENGINE_AUTO)
+        e.load_data(nodes)
+        step(e, nodes, "clean rows again under AUTO", PKG.ENGINE_MFMA_I8)
+
+
 _GUESS_CODE = r"""
 import importlib, os, sys, numpy as np
 sys.path.insert(0, 'tests'); sys.path.insert(0, '.')
