@@ -238,6 +238,54 @@ int hvs_mask_stats(hvs_ctx *ctx, hvs_mask_info *out);
 void hvs_mask_plan(const uint64_t *live_bits, uint32_t n, uint32_t k, float sample_proportion, uint32_t *n_live,
                    uint32_t *cut, uint32_t *pad_ids);
 
+/* ---- row append: new rows searchable at once, the index folded in later ---------------------- */
+
+/*
+ * After hvs_append_rows(ctx, rows, count, &first_id) the context behaves, in every later call on every engine, as a fresh
+ * context would after hvs_load_data of the old rows followed by the new ones under the same settings (engine, k, distance
+ * order, padding, and the mask extended with live rows): the same ids -- appended rows get n_old .. n_old + count - 1 --,
+ * bit-equal out_dists, the same (dist asc, id asc) tie rule, the same hvs_timing.pairs.  So
+ * sn = uint32(float(sample_proportion) * float(n_total)) is taken over the total, padding comes from n_total - 1,
+ * n_total - 2, ... (from the last live ids under a mask), hvs_num_rows / hvs_download_data see the new rows, appended rows
+ * start live, hvs_delete_rows / hvs_set_row_mask accept their ids and hvs_get_row_mask returns ceil(n_total / 64) words.
+ * The index (orderings, filter tiles) keeps covering the rows it was built over, ids [0, n_indexed); the rows behind it, the
+ * tail, are scanned in exact order for every batch that goes through the index.  An append that would leave more than
+ * tail_limit rows in the tail re-indexes over all rows before it returns; hvs_reindex does so on request; no query ever does.
+ * While the tail is empty -- or lies wholly behind sn -- every call runs exactly the kernels it runs without these
+ * functions.  Without an index (fewer than 4096 rows, or no room for one) appends only extend D, n_tail stays 0, and an
+ * index is built by the same limit rule once the data set allows one.
+ * count == 0: HVS_OK, nothing changes.  rows == NULL or more than 2^32 - 1 rows: HVS_EINVAL; no data loaded: HVS_ESTATE; no
+ * room: HVS_ENOMEM; in each of these cases the context, D, the mask and the index are as they were.  (Any other failure --
+ * a HIP error while the rows are copied or the index is rebuilt -- is reported as it is and may leave the context without an
+ * index, or the GPUs of a multi-GPU context with different row counts: load the data again.)  hvs_load_data /
+ * hvs_gen_data reset everything (tail empty, counters 0) but the limit.  All of these functions accept a multi-GPU context:
+ * rows and state are replicated like D and the mask, and room is secured on every GPU before any GPU changes.  The
+ * D-sharded mode (sharding.py, hvs_merge_shards_device) knows nothing of appends, as it knows nothing of masks.
+ */
+typedef struct hvs_append_info {
+    uint32_t n_indexed;     /* rows the orderings/tiles cover (0: no index, the exact engine scans everything) */
+    uint32_t n_tail;        /* rows behind them: n_total - n_indexed when an index exists, else 0              */
+    uint32_t tail_limit;    /* n_tail above which hvs_append_rows re-indexes before it returns                  */
+    uint32_t reindexes;     /* index builds caused by appends or hvs_reindex since the last load                */
+    uint64_t tail_pairs;    /* last call: (query, tail row) pairs the tail scan evaluated (re-run batches apart) */
+    uint64_t tail_admitted; /* last call: of those, keys that entered a candidate list                         */
+    double   reindex_ms;    /* last such build                                                                  */
+} hvs_append_info;
+int hvs_append_rows(hvs_ctx *ctx, const float *rows /* host, count x 102 */, uint32_t count, uint32_t *first_id /* may be NULL */);
+/* room for D (and the mask) to grow to n_capacity rows without a device-to-device move */
+int hvs_reserve_rows(hvs_ctx *ctx, uint32_t n_capacity);
+/* fold the tail into the index now (no-op when n_tail == 0) */
+int hvs_reindex(hvs_ctx *ctx);
+/* rows; 0: the default rule max(4096, n_indexed / 1024) */
+int hvs_set_tail_limit(hvs_ctx *ctx, uint32_t rows);
+/* Call after hvs_sync / hvs_query.  Multi-GPU context: one GPU's state (it is replicated), the two per-call counters summed. */
+int hvs_append_stats(hvs_ctx *ctx, hvs_append_info *out);
+/* The host arithmetic of the contract (no GPU, no context; any output may be NULL): for an index over n_indexed of n_total
+ * rows and a sample_proportion, sn and the id range [tail_lo, tail_hi) = [n_indexed, max(n_indexed, sn)) the tail scan covers
+ * (empty when sn <= n_indexed). */
+void hvs_append_plan(uint32_t n_indexed, uint32_t n_total, float sample_proportion, uint32_t *sn, uint32_t *tail_lo,
+                     uint32_t *tail_hi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,7 +158,15 @@ struct hvs_ctx : HvsLane {
     // data set, raw rows n x 102 (the io.h layout) resident in HBM
     float* d_data = nullptr;
     uint32_t n = 0;
+    uint32_t n_cap = 0;  // rows d_data has room for (hvs_reserve_rows / geometric growth of hvs_append_rows)
     double load_ms = 0.0;
+    // appended rows (hvs_append_rows): `n` counts the rows there are, `n_indexed` (below) the rows the index
+    // covers; ids [n_indexed, n) are the tail, scanned exactly by hvs_k_scan_tail for every batch that goes through the index
+    uint32_t tail_limit = 0;      // hvs_set_tail_limit (0: the default rule, tail_limit_of)
+    uint32_t reindexes = 0;       // index builds caused by appends or hvs_reindex since the last load
+    double reindex_ms = 0.0;      // the last of them
+    uint32_t index_tried_n = 0;   // no-index state: n at the last attempt to build one (0: none yet)
+    uint32_t live_cap = 0;        // u64 words d_live has room for
 
     // resident queries + results
     float* d_q = nullptr;
@@ -172,7 +180,10 @@ struct hvs_ctx : HvsLane {
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
     // `fmt.built != HVS_FMT_NONE` -- usable tiles exist on top of them.  Tiles imply orderings; free_index drops both.
+    // A third, beside them: `n_indexed` -- the rows both orderings (and the tiles) cover, = n at every index build and 0
+    // without orderings.  Everything built over POSITIONS (perm, bpos, tiles, lp, the level table) is sized by it.
     bool have_order = false;
+    uint32_t n_indexed = 0;
     HvsFormatState fmt;
     HvsLevels lv{};                       // same block count for both orderings
     HvsOrdering ord[2];  // [0] the (C,T) ordering, [1] the T ordering
@@ -623,6 +634,7 @@ void free_index(hvs_ctx* c)
         o.lp = lp;
     }
     c->have_order = false;
+    c->n_indexed = 0;
     c->lp_valid = false;  // (counts along the orderings that have just gone)
     // everything the last data set taught, `planned` and `built_rot` included: nothing reads those two before choose_format
     // and build_tiles have written them for the next index
@@ -657,9 +669,9 @@ int set_quant(hvs_ctx* c, bool rot)
     if (!c->d_quant) HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_quant), sizeof(HvsQuant)));
     hipLaunchKernelGGL(hvs_k_quant_reset, dim3(1), dim3(128), 0, c->stream, c->d_quant, rot ? 1u : 0u);
     if (rot)
-        hipLaunchKernelGGL(hvs_k_minmax_rot, dim3(std::min(c->n, 4096u)), dim3(128), 0, c->stream, c->d_data, c->n, c->d_quant);
+        hipLaunchKernelGGL(hvs_k_minmax_rot, dim3(std::min(c->n_indexed, 4096u)), dim3(128), 0, c->stream, c->d_data, c->n_indexed, c->d_quant);
     else
-        hipLaunchKernelGGL(hvs_k_minmax, dim3(std::min(c->n, 4096u)), dim3(128), 0, c->stream, c->d_data, c->n, c->d_quant);
+        hipLaunchKernelGGL(hvs_k_minmax, dim3(std::min(c->n_indexed, 4096u)), dim3(128), 0, c->stream, c->d_data, c->n_indexed, c->d_quant);
     hipLaunchKernelGGL(hvs_k_quant_params, dim3(1), dim3(128), 0, c->stream, c->d_quant);
     HVS_HIP(c, hipGetLastError());
     c->fmt.i8_rot = rot;
@@ -668,7 +680,7 @@ int set_quant(hvs_ctx* c, bool rot)
 
 int choose_format(hvs_ctx* c)
 {
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;
     c->fmt.planned = HVS_FMT_F16;
     c->fmt.i8_usable = false;
     int rcq = set_quant(c, false);  // (the model below prices the plain INT8 format; HVS_I8_ROTATE=1 switches afterwards)
@@ -733,7 +745,7 @@ int choose_format(hvs_ctx* c)
 int ensure_live_prefix(hvs_ctx* c)
 {
     if (c->lp_valid) return HVS_OK;
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;  // (positions)
     int rc;
     for (HvsOrdering& o : c->ord)
         if (!o.lp && (rc = dev_alloc(c, &o.lp, (size_t)n + 1u))) return rc;
@@ -758,7 +770,7 @@ int ensure_live_prefix(hvs_ctx* c)
 int count_masked_pairs(hvs_ctx* c, uint32_t sn)
 {
     HvsBatch& B = c->fb;
-    if (sn == c->n) {
+    if (sn >= c->n_indexed) {  // (no indexed row is cut off)
         int rc = ensure_live_prefix(c);
         if (rc) return rc;
         hipLaunchKernelGGL(hvs_k_count_live_pairs, dim3(hvs_ceil_div(B.nslots, 256u)), dim3(256), 0, c->stream, B, c->ord[0].lp, c->ord[1].lp,
@@ -779,7 +791,7 @@ int patch_tiles(hvs_ctx* c)
     HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
     for (const HvsOrdering& o : c->ord)
-        hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, o.perm, c->n, L, o.bpos, o.tiles,
+        hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, o.perm, c->n_indexed, L, o.bpos, o.tiles,
                            reinterpret_cast<int*>(o.nrm), c->fmt.built, c->d_mask_stat);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -790,7 +802,7 @@ int patch_tiles(hvs_ctx* c)
 int build_tiles(hvs_ctx* c, int fmt)
 {
     const HvsLevels L = c->lv;
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;
     int rc;
     c->fmt.built = HVS_FMT_NONE;
     if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
@@ -899,15 +911,16 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
         (void)hipGetLastError();
         return fail(c, HVS_ENOMEM, "planner probe: out of device memory");
     }
-    const uint32_t step = std::max(1u, c->n / P);
-    hipLaunchKernelGGL(hvs_k_probe_queries, dim3(hvs_ceil_div(P * HVS_QCOLS, 256u)), dim3(256), 0, c->stream, c->d_data, c->n, step, P, c->d_q);
+    // (rows of the indexed part, searched in the indexed part: the probe prices the index, and runs when it covers every row)
+    const uint32_t step = std::max(1u, c->n_indexed / P);
+    hipLaunchKernelGGL(hvs_k_probe_queries, dim3(hvs_ceil_div(P * HVS_QCOLS, 256u)), dim3(256), 0, c->stream, c->d_data, c->n_indexed, step, P, c->d_q);
     hipError_t e = hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
     // (the probe batch is small, but it stands for full batches: their failure target.  Its lists keep the production capacity:
     // PCA-like vectors at n = 10^7 hand ~1500 rows per type-0 query to the last level's list of 1024 -- INT8 tiles look 23 %
     // faster than FP16 tiles there only while a half-empty workspace doubles the lists, profiles/r04/nonuniform_int8.txt)
     c->force_pfail = guess_pfail_for(kBatchMfma);
-    int rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
+    int rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
     c->force_pfail = 0u;
     unsigned long long h[4] = {0, 0, 0, 0};
     uint32_t fails[2] = {0, 0};
@@ -920,7 +933,7 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     c->n_launch_events = 0;
     if (rc) return rc;
     const double base = HVS_IS_I8(c->fmt.built) ? 1.0 : plan_cost16();
-    *cost = base + 2650.0 / (double)c->n * ((double)h[2] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
+    *cost = base + 2650.0 / (double)c->n_indexed * ((double)h[2] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
     // what a filter without any error band would have handed over: m (radix - 1) rows per level under the guessed thresholds
     double ideal = 0.0;
     {
@@ -1003,7 +1016,7 @@ int plan_by_probe(hvs_ctx* c)
 // keys and perm of both orderings: two radix sorts over temporaries that go when this returns
 int build_orderings(hvs_ctx* c)
 {
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;
     int rc;
     for (HvsOrdering& o : c->ord) {
         if ((rc = dev_alloc(c, &o.keys, (size_t)n))) return rc;
@@ -1037,7 +1050,7 @@ int build_orderings(hvs_ctx* c)
 int build_index(hvs_ctx* c)
 {
     free_index(c);
-    const uint32_t n = c->n;
+    const uint32_t n = c->n;  // an index is always built over every row there is
     const HvsLevels L = hvs_make_levels(n, kRadixLast, kRadixMid, kRadixPlan.set ? kRadixPlan.r : nullptr);
     if (L.off[L.K + 1] != L.nblk) return fail(c, HVS_EINVAL, "internal: level table does not cover the blocks");
     // survivor entries carry the block position in 24 bits: above 2^29 rows per GPU the exact engine answers
@@ -1045,6 +1058,7 @@ int build_index(hvs_ctx* c)
     c->index_too_large = L.nblk > HVS_ENTRY_MAX_BLOCKS;
     if (c->index_too_large) return HVS_OK;
     c->lv = L;
+    c->n_indexed = n;  // (free_index takes it back when the build fails)
     int rc = build_orderings(c);
     trace_mark(c, "orderings");
     if (!rc) rc = choose_format(c);
@@ -1140,7 +1154,7 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
     int rc = ensure_filter_workspace(c, nqb, want_fcap);
     if (rc) return rc;
     HvsBatch& B = c->fb;
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;  // (positions of the orderings)
     // ~4096 queries of a predicate class per start-position bin (32 groups); inside a bin queries are
     // ordered by range end, so the 4 groups of a filter workgroup stream nearly the same run of tiles.  The class
     // populations stay on the device (hvs_k_query_keys2 reads them there); only the range-scan exact engine, whose
@@ -1169,6 +1183,18 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
     return HVS_OK;
 }
 
+// The tail of the batch in c->fb (hvs_k_scan_tail): ids [n_indexed, sn), if there are any.  `count`: the batch's pairs go
+// to the call's counters (not in re-run batches).
+bool have_tail(const hvs_ctx* c, uint32_t sn) { return c->have_order && sn > c->n_indexed; }
+void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
+{
+    const HvsBatch& B = c->fb;
+    with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+        hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
+                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters, count ? 1 : 0, c->d_live);
+    });
+}
+
 // Exact engine on top of the index.  Queries with a categorical predicate (types 1 and 3) scan only
 // their position range of the (C,T) ordering (hvs_k_scan_ranges): ~1 % / 0.25 % of the rows, 17-25x
 // faster than scanning everything.  Type-0 and type-2 queries keep the sequential full scan in original
@@ -1177,12 +1203,13 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
 // streaming all of them (8.2 k vs 14 k queries/s).
 int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
 {
-    int rc = prep_batch(c, q0, nqb, sn == c->n && !c->n_dead, HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
+    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !c->n_dead, HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
     if (rc) return rc;
     HvsBatch& B = c->fb;
+    const bool tail = have_tail(c, sn);  // rows behind the index: counted for every class, scanned here for the range classes
     if (c->n_dead) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
-    } else if (sn != c->n)
+    } else if (sn < c->n_indexed)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
                            c->d_counters, c->d_live);
     // slot layout of hvs_k_layout: classes 0..3 padded to 32 slots each, then the T-ordering class (type 2)
@@ -1194,11 +1221,17 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     const uint32_t slot2 = hvs_ceil_div(slot_end, HVS_WG_WAVES * HVS_GROUP) * (HVS_WG_WAVES * HVS_GROUP);
     if (nq0 && (rc = run_batch_exact(c, 0, nq0, sn, B.qid, false))) return rc;
     if (nq2 && (rc = run_batch_exact(c, 0, nq2, sn, B.qid + slot2, false))) return rc;
-    if (slot_begin >= slot_end) return HVS_OK;
+    if (slot_begin >= slot_end) {
+        if (tail) {  // (the full scans above walked the tail themselves: its pairs only)
+            launch_tail(c, sn, HvsTailOut{nullptr, nullptr, nullptr, 0u, 0u, 0u}, true);
+            HVS_HIP(c, hipGetLastError());
+        }
+        return HVS_OK;
+    }
     const uint32_t waves = (slot_end - slot_begin + 63u) / 64u;
     uint32_t nchunks = std::max(1u, std::min(64u, (8192u + waves - 1u) / waves));
     nchunks = std::min(nchunks, std::max(1u, (1u << 20) / B.nslots));  // candidate lists: at most 2 GB
-    const size_t lists = (size_t)B.nslots * nchunks;
+    const size_t lists = (size_t)B.nslots * (nchunks + (tail ? 1u : 0u));  // (the tail's keys: one more chunk of lists)
     if (lists > c->cand_lists) {
         if ((rc = dev_alloc(c, &c->d_cand, lists * (size_t)c->cap))) return rc;
         if ((rc = dev_alloc(c, &c->d_cand_cnt, lists))) return rc;
@@ -1213,8 +1246,11 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
                            c->d_counters, c->d_live);
     });
     kernel_timer_end(c, ev);
+    if (tail)
+        launch_tail(c, sn, HvsTailOut{c->d_cand + (size_t)nchunks * B.nslots * (size_t)c->cap, c->d_cand_cnt + (size_t)nchunks * B.nslots, nullptr,
+                                      (uint32_t)c->cap, slot_begin, slot_end}, true);
     const uint32_t nsel = slot_end - slot_begin;
-    launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks, c->d_cand + (size_t)slot_begin * (size_t)c->cap,
+    launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks + (tail ? 1u : 0u), c->d_cand + (size_t)slot_begin * (size_t)c->cap,
                   c->d_cand_cnt + slot_begin);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1334,13 +1370,13 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
 {
     const int fmt = c->fmt.built;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
-    int rc = prep_batch(c, q0, nqb, sn == c->n && !list && !c->n_dead, fmt, false, list, want_fcap);
+    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !list && !c->n_dead, fmt, false, list, want_fcap);
     if (rc) return rc;
     if ((rc = build_items(c))) return rc;
     HvsBatch& B = c->fb;
     const HvsLevels L = c->lv;
     HvsItems W{c->d_items, c->d_lvloff, c->d_cursor, HVS_SEG};
-    const uint32_t n = c->n;
+    const uint32_t n = c->n_indexed;  // positions of the orderings; the padding of the final merge counts from the end of D (c->n)
     if (c->guess_k != c->k) {  // (tables are made on first use: 168 x ~100 negative-binomial sums each, ~10 ms on the host)
         for (bool& h : c->guess_have) h = false;
         c->guess_k = c->k;
@@ -1354,7 +1390,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
     if (c->n_dead && !list) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
-    } else if (sn != n && !list)
+    } else if (sn < n && !list)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
                            c->d_counters, c->d_live);
 
@@ -1374,14 +1410,21 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
             if (final)  // (only the final merge pads: the merges in front of it have no masked form)
-                hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n,
+                hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n,
                                    c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G,
                                    c->d_pad_ids);
             else
-                hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, n, c->d_q, B,
+                hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
                                    c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->d_pad_ids);
         });
     };
+    // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
+    // last re-scoring filled -- every tail row with distance <= tau_last is then held beside every indexed one, which is all
+    // the final check needs.  The guessed thresholds never see these rows.
+    auto tail_before_final = [&]() {
+        if (have_tail(c, sn)) launch_tail(c, sn, HvsTailOut{B.cand, B.candcnt, B.tau, B.fcap, 0u, B.nslots}, !list);
+    };
+    if (L.K == 0u) tail_before_final();
     launch_merge(L.K == 0u, 1u);
     // re-scoring blocks per group: each block stages the group's 128 queries in LDS first, so large batches use
     // few long-lived blocks per group (2: -4 % of the step at 262144 queries) and small batches enough blocks to
@@ -1413,6 +1456,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, n, sn,
                                c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, c->d_live);
         });
+        if (last == L.K) tail_before_final();
         launch_merge(last == L.K, last + 1u);
     }
     // queries this batch could not answer go on the call's lists (retry with a proven threshold / exact engine); they
@@ -1910,6 +1954,11 @@ int begin_data(hvs_ctx* c, uint32_t n)
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = 0;
+    c->n_cap = 0;
+    c->live_cap = 0;
+    c->reindexes = 0;  // (the tail is empty: free_index in finish_data; the limit stays)
+    c->reindex_ms = 0.0;
+    c->index_tried_n = 0;
     // a new data set starts with every row live
     c->h_live.clear();
     c->n_dead = 0;
@@ -1918,18 +1967,29 @@ int begin_data(hvs_ctx* c, uint32_t n)
     if ((rc = dev_alloc(c, &c->d_live, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
-    return dev_alloc(c, &c->d_data, (size_t)n * HVS_DCOLS);
+    if ((rc = dev_alloc(c, &c->d_data, (size_t)n * HVS_DCOLS))) return rc;
+    c->n_cap = n;
+    return HVS_OK;
 }
 
 // upload/generation is timed by ev_q0..ev_q1; the index build (orderings + tiles) follows
+int index_data(hvs_ctx* c);
 int finish_data(hvs_ctx* c)
 {
     float ms = 0.f;
     HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
     c->load_ms = ms;
+    return index_data(c);
+}
+
+// the index over all rows of D as they are now: at the end of a load, and again when appended rows are folded in (reindex)
+int index_data(hvs_ctx* c)
+{
+    float ms = 0.f;
     free_index(c);
     // the index (two orderings + tiles) serves both engines: the exact engine scans position ranges
     if (c->n < kIndexMinRows && !is_filter_engine(c->engine)) return HVS_OK;
+    c->index_tried_n = c->n;
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
     int rc = build_index(c);
     if (rc == HVS_ENOMEM) {
@@ -2442,7 +2502,9 @@ int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_l
     if (c->h_live.empty()) c->h_live = all_live_words(c->n);
     bool fresh = false;
     if (!c->d_live) {
-        if ((rc = dev_alloc(c, &c->d_live, words.size() * 2u))) return rc;
+        const size_t cap64 = std::max(words.size(), ((size_t)c->n_cap + 63u) / 64u);  // (room for the rows D has room for)
+        if ((rc = dev_alloc(c, &c->d_live, cap64 * 2u))) return rc;
+        c->live_cap = (uint32_t)cap64;
         fresh = true;
     }
     bool revived = false;
@@ -2493,6 +2555,144 @@ int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
     if (c->timing_valid) {
         HVS_HIP(c, hipMemcpy(&v, c->d_counters + 8, sizeof(v), hipMemcpyDeviceToHost));
         out->dead_survivors = v;
+    }
+    return HVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// appended rows
+// ---------------------------------------------------------------------------------------------
+// n_tail above which an append re-indexes before it returns.  Default max(4096, n_indexed >> 10), derived and not yet
+// measured: if the tail scan evaluated pairs at the exact engine's rate, ~3.1 x 10^11 pairs/s on record, and the
+// filter engines answer a query of the flagship shape in ~310 ns, 10^4 tail rows (n_indexed = 10^7) cost ~32 ns, a tenth of
+// a query.
+uint32_t tail_limit_of(const hvs_ctx* c) { return c->tail_limit ? c->tail_limit : std::max(4096u, c->n_indexed >> 10); }
+uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
+
+// room for n_cap rows in D and in the device mask, contents kept (device-to-device copies); nothing a query sees changes
+int leaf_reserve_rows(hvs_ctx* c, uint32_t n_cap)
+{
+    if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);  // an earlier call's re-runs read D
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    if (n_cap > c->n_cap) {
+        float* bigger = nullptr;
+        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), (size_t)n_cap * HVS_DCOLS * sizeof(float)));
+        hipError_t e = hipMemcpyAsync(bigger, c->d_data, (size_t)c->n * HVS_DCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(bigger);
+            return fail(c, HVS_EHIP, std::string("hvs_reserve_rows: moving D: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(c->d_data);
+        c->d_data = bigger;
+        c->n_cap = n_cap;
+    }
+    const size_t cap64 = ((size_t)c->n_cap + 63u) / 64u;
+    if (c->d_live && cap64 > c->live_cap) {
+        uint32_t* bigger = nullptr;
+        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), cap64 * sizeof(uint64_t)));
+        hipError_t e = hipMemcpyAsync(bigger, c->d_live, (((size_t)c->n + 63u) / 64u) * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(bigger);
+            return fail(c, HVS_EHIP, std::string("hvs_reserve_rows: moving the mask: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(c->d_live);
+        c->d_live = bigger;
+        c->live_cap = (uint32_t)cap64;
+    }
+    return HVS_OK;
+}
+
+// first half of an append: capacity for `count` more rows (geometric growth), so that the second half cannot run out of
+// memory on one GPU of several
+int leaf_append_prepare(hvs_ctx* c, uint32_t count)
+{
+    const uint32_t need = c->n + count;  // (no overflow: checked by the caller)
+    uint32_t want = c->n_cap;
+    if (need > c->n_cap) want = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(need, (uint64_t)c->n_cap + c->n_cap / 2u));
+    int rc = leaf_reserve_rows(c, want);
+    if (rc == HVS_ENOMEM && want > need) {  // no room for the growth step: exactly what is needed
+        (void)hipGetLastError();
+        c->err.clear();
+        rc = leaf_reserve_rows(c, need);
+    }
+    return rc;
+}
+
+// fold the tail into the index: the load's own index build over all rows (the mask is re-applied by build_tiles' patch)
+int leaf_reindex(hvs_ctx* c, bool force)
+{
+    if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
+    if (!force && tail_rows(c) == 0u) return HVS_OK;
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    // (the live-row counts run along positions: their buffers are sized by the index that goes)
+    if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
+    if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
+    const double load_ms = c->load_ms;  // hvs_timing.load_ms stays the load's
+    c->index_ms = 0.0;
+    rc = index_data(c);
+    c->load_ms = load_ms;
+    if (rc) return rc;
+    c->reindexes += 1u;
+    c->reindex_ms = c->index_ms;
+    return HVS_OK;
+}
+
+// second half: the rows, the mask bits, n -- and the index when the tail has outgrown its limit
+int leaf_append_commit(hvs_ctx* c, const float* rows, uint32_t count)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    const uint32_t n_old = c->n, n_new = n_old + count;
+    int rc = upload_rows(c, c->d_data + (size_t)n_old * HVS_DCOLS, rows, (size_t)count * HVS_DCOLS);
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    if (!c->h_live.empty()) {  // a mask has been set: the new rows start live
+        std::vector<uint64_t> words = c->h_live;
+        words.resize(((size_t)n_new + 63u) / 64u, 0ull);
+        for (uint32_t i = n_old; i < n_new;) {
+            const uint32_t w = i >> 6, b = i & 63u, m = std::min(64u - b, n_new - i);
+            words[w] |= (m == 64u ? ~0ull : ((1ull << m) - 1ull)) << b;
+            i += m;
+        }
+        if (c->d_live) {
+            const size_t w0 = n_old >> 6;
+            HVS_HIP(c, hipMemcpyAsync(reinterpret_cast<uint64_t*>(c->d_live) + w0, words.data() + w0, (words.size() - w0) * sizeof(uint64_t),
+                                      hipMemcpyHostToDevice, c->stream));
+            HVS_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        c->h_live.swap(words);
+    }
+    c->n = n_new;
+    c->cut_valid = false;  // (the live-row counts along the orderings stand: they cover indexed positions only)
+    if ((rc = refresh_pad_ids(c))) return rc;
+    const bool can_index = c->have_order || ((n_new >= kIndexMinRows || is_filter_engine(c->engine)) && !c->index_too_large);
+    const uint32_t uncovered = c->have_order ? n_new - c->n_indexed : n_new - std::min(n_new, c->index_tried_n);
+    if (can_index && uncovered > tail_limit_of(c)) return leaf_reindex(c, true);
+    return HVS_OK;
+}
+
+int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
+{
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = hvs_append_info{};
+    out->n_indexed = c->n_indexed;
+    out->n_tail = tail_rows(c);
+    out->tail_limit = tail_limit_of(c);
+    out->reindexes = c->reindexes;
+    out->reindex_ms = c->reindex_ms;
+    if (c->timing_valid) {
+        unsigned long long v[2] = {0, 0};
+        HVS_HIP(c, hipMemcpy(v, c->d_counters + 9, sizeof(v), hipMemcpyDeviceToHost));
+        out->tail_pairs = v[0];
+        out->tail_admitted = v[1];
     }
     return HVS_OK;
 }
@@ -2592,6 +2792,14 @@ int for_each_resident_part(hvs_ctx* root, uint32_t q0, uint32_t nq, Fn fn)
         if (a >= b) return HVS_OK;
         return fn(root->kids[r], a - root->kid_q0[r], b - a, a - q0);
     });
+}
+
+// fn(leaf) on the context itself or on every GPU of a multi-GPU one
+template <typename Fn>
+int on_every_leaf(hvs_ctx* c, Fn fn)
+{
+    if (c->kids.empty()) return fn(c);
+    return for_each_leaf(c, [&](uint32_t r) { return fn(c->kids[r]); });
 }
 
 }  // namespace
@@ -3214,6 +3422,73 @@ int hvs_mask_stats(hvs_ctx* c, hvs_mask_info* out)
         if (rc) return fail(c, rc, c->kids[r]->err);
         if (r == 0u) agg = m;  // (the mask and the tiles are replicated: one GPU's view)
         else agg.dead_survivors += m.dead_survivors;  // a work counter of the call, summed like hvs_timing's
+    }
+    *out = agg;
+    return HVS_OK;
+}
+
+// ---- appended rows ---------------------------------------------------------------------------
+
+void hvs_append_plan(uint32_t n_indexed, uint32_t n_total, float sample_proportion, uint32_t* sn, uint32_t* tail_lo, uint32_t* tail_hi)
+{
+    const uint32_t s = sample_rows(sample_proportion, n_total);
+    if (sn) *sn = s;
+    if (tail_lo) *tail_lo = n_indexed;
+    if (tail_hi) *tail_hi = std::max(n_indexed, s);
+}
+
+int hvs_append_rows(hvs_ctx* c, const float* rows, uint32_t count, uint32_t* first_id)
+{
+    if (!c) return HVS_EINVAL;
+    if (count == 0u) return HVS_OK;
+    if (!rows) return fail(c, HVS_EINVAL, "hvs_append_rows: rows is NULL");
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_append_rows: no data set loaded");
+    if ((uint64_t)L->n + count > 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_append_rows: more than 2^32 - 1 rows");
+    const uint32_t first = L->n;
+    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
+    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_append_prepare(k, count); });
+    if (rc) return rc;
+    if ((rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_append_commit(k, rows, count); }))) return rc;
+    if (first_id) *first_id = first;
+    return HVS_OK;
+}
+
+int hvs_reserve_rows(hvs_ctx* c, uint32_t n_capacity)
+{
+    if (!c) return HVS_EINVAL;
+    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reserve_rows(k, n_capacity); });
+}
+
+int hvs_reindex(hvs_ctx* c)
+{
+    if (!c) return HVS_EINVAL;
+    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reindex(k, false); });
+}
+
+int hvs_set_tail_limit(hvs_ctx* c, uint32_t rows)
+{
+    if (!c) return HVS_EINVAL;
+    c->tail_limit = rows;
+    for (hvs_ctx* k : c->kids) k->tail_limit = rows;
+    return HVS_OK;
+}
+
+int hvs_append_stats(hvs_ctx* c, hvs_append_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_append_stats(c, out);
+    hvs_append_info agg{};
+    for (size_t r = 0; r < c->kids.size(); ++r) {
+        hvs_append_info m{};
+        const int rc = leaf_append_stats(c->kids[r], &m);
+        if (rc) return fail(c, rc, c->kids[r]->err);
+        if (r == 0u) {
+            agg = m;  // (rows and index are replicated: one GPU's view)
+        } else {
+            agg.tail_pairs += m.tail_pairs;  // work counters of the call, summed like hvs_timing's
+            agg.tail_admitted += m.tail_admitted;
+        }
     }
     *out = agg;
     return HVS_OK;

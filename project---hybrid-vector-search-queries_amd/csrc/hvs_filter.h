@@ -3069,3 +3069,182 @@ __global__ void hvs_k_collect_overflow(HvsBatch B, uint32_t* __restrict__ list_e
     else if (code == HVS_FAIL_RETRY)
         list_retry[atomicAdd(count_retry, 1u)] = B.qid[s];
 }
+
+// ---------------------------------------------------------------------------------------------
+// hvs_k_scan_tail -- rows the index does not cover (hvs_append_rows): the exact-order scan of ids
+// [tail_lo, tail_hi) for a batch in slot layout.  One lane per slot; the rows are contiguous in D, so they are staged
+// in LDS in blocks of HVS_LDS_ROWS by the whole workgroup and read back as broadcasts, the row loop of
+// hvs_k_scan_exact_lds.  The tail is not sorted by anything: the query's own predicate is applied per row (an invalid type
+// matches nothing), plus the dead-row test when MASKED.  A passing row whose distance is not above the slot's threshold
+// (none given, or still +inf: every passing row) has its key appended to the slot's list behind the keys already there.
+// The keys a lane adds form a segment of at most CAP keys; a segment that fills is cut back to its k smallest by the wave
+// (hvs_wave_select_prune), which also lowers the lane's threshold -- the k smallest of (list U tail) never lose a member.
+// A key that finds no room for such a cut (fewer than k + 1 free places behind the list) flags its query for a re-run instead
+// (hvs_flag_fail); a list that is full but is offered no key is left alone.
+// Filter batches: lists = B.cand (what hvs_k_rescore wrote at the last level), thresholds = B.tau, between the last
+// re-scoring and the final merge.  Range scans of the exact engine: lists = one more chunk of its candidate lists, no
+// thresholds, and only slots [slot_lo, slot_hi) take keys (the others' full scans walk the tail themselves).
+// counters (`count` != 0: not in re-run batches): [0] passing pairs, [9] pairs evaluated, [10] keys admitted.
+// ---------------------------------------------------------------------------------------------
+struct HvsTailOut {
+    uint64_t* lists;            // list of slot s: lists + s * stride
+    uint32_t* counts;           // [slot] keys in the list, on entry and on exit
+    const float* tau;           // [slot] admission threshold, or nullptr
+    uint32_t stride;            // keys a list has room for
+    uint32_t slot_lo, slot_hi;  // slots that take keys
+};
+
+// (__launch_bounds__' second argument is the least number of WAVES per SIMD; a workgroup of 256 threads is four waves, one
+// per SIMD, so here it is also workgroups per CU -- a change of the block size changes the register budget with it.  Two,
+// where hvs_k_scan_exact_lds has three: beside the exact engine's row loop a lane keeps its segment's place, room and fill,
+// which at three -- 168 registers -- spilled 4 to 8 of them; the kernel runs once per batch over a few thousand rows)
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
+__global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restrict__ D, const float* __restrict__ Q,
+                                                                         HvsBatch B, HvsTailOut O, uint32_t tail_lo, uint32_t tail_hi,
+                                                                         unsigned long long* __restrict__ counters, int count,
+                                                                         const uint32_t* __restrict__ live)
+{
+    __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t slot = w * 64u + lane;
+    const bool wave_active = w * 64u < B.nslots;  // inactive waves still help staging and meet the barriers
+    const uint32_t knn = B.knn;
+
+    const uint32_t qi = slot < B.nslots ? B.qid[slot] : 0xFFFFFFFFu;
+    const bool have_q = qi != 0xFFFFFFFFu;
+    const float* __restrict__ qrow = Q + (size_t)(have_q ? qi : 0u) * HVS_QCOLS;
+    HvsQParams p = hvs_parse_query(qrow);
+    if (!have_q) p.type = 4u;
+    hvs_f2 q2[HVS_NDIM / 2];
+#pragma unroll
+    for (int i = 0; i < HVS_NDIM / 4; ++i) {
+        const float4 v4 = *reinterpret_cast<const float4*>(qrow + 4 + 4 * i);
+        q2[2 * i] = hvs_f2{v4.x, v4.y};
+        q2[2 * i + 1] = hvs_f2{v4.z, v4.w};
+    }
+    // this lane's segment: places [s0, s0 + segcap) of its slot's list
+    bool takes = have_q && slot >= O.slot_lo && slot < O.slot_hi;
+    uint32_t s0 = takes ? O.counts[slot] : 0u;
+    if (s0 > O.stride) takes = false;  // (overflowed at the last level and flagged there: the list is not used)
+    if (!takes) s0 = 0u;
+    const bool owns = takes;  // this lane writes its list's new fill at the end
+    const uint32_t room = takes ? O.stride - s0 : 0u;
+    const uint32_t segcap = room < (uint32_t)CAP ? room : (uint32_t)CAP;  // (0: a full list -- flagged only if a key needs a place)
+    uint64_t* __restrict__ myseg = O.lists + (size_t)(takes ? slot : 0u) * O.stride + s0;
+    float tau = (takes && O.tau) ? O.tau[slot] : __builtin_inff();
+    uint32_t cnt = 0, npass = 0, nadm = 0, nrows = 0;
+
+    // staging: item e = (row r, piece c): c < 25 -> floats 2+4c..5+4c of the row, c == 25 -> (C, T, 0, 0)
+    constexpr uint32_t kItems = HVS_LDS_ROWS * 26u;
+    float4 stg[(kItems + 255u) / 256u];
+    auto load_block = [&](uint32_t j0) {
+#pragma unroll
+        for (uint32_t k = 0; k < (kItems + 255u) / 256u; ++k) {
+            const uint32_t e = threadIdx.x + 256u * k;
+            const uint32_t r = e / 26u, c = e % 26u;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < kItems && r < tail_hi - j0) {
+                const float* __restrict__ src = D + (size_t)(j0 + r) * HVS_DCOLS;
+                if (c < 25u) {
+                    const float2 a = *reinterpret_cast<const float2*>(src + 2 + 4 * c);
+                    const float2 b = *reinterpret_cast<const float2*>(src + 4 + 4 * c);
+                    v = make_float4(a.x, a.y, b.x, b.y);
+                } else {
+                    const float2 a = *reinterpret_cast<const float2*>(src);
+                    v = make_float4(a.x, a.y, 0.f, 0.f);
+                }
+            }
+            stg[k] = v;
+        }
+    };
+    auto store_block = [&](uint32_t buf) {
+#pragma unroll
+        for (uint32_t k = 0; k < (kItems + 255u) / 256u; ++k) {
+            const uint32_t e = threadIdx.x + 256u * k;
+            if (e < kItems) srow[buf][(e / 26u) * (HVS_LDS_ROW_F / 4) + (e % 26u)] = stg[k];
+        }
+    };
+
+    if (tail_lo >= tail_hi) return;  // uniform over the grid
+    load_block(tail_lo);
+    store_block(0u);
+    __syncthreads();
+    uint32_t buf = 0;
+    for (uint32_t j0 = tail_lo; j0 < tail_hi; j0 += HVS_LDS_ROWS) {
+        const bool more = tail_hi - j0 > HVS_LDS_ROWS;  // (no j0 + HVS_LDS_ROWS: ids run up to 2^32 - 1)
+        if (more) load_block(j0 + HVS_LDS_ROWS);
+        if (wave_active) {
+            const uint32_t nrow = (tail_hi - j0) < HVS_LDS_ROWS ? (tail_hi - j0) : HVS_LDS_ROWS;
+            for (uint32_t r = 0; r < nrow; ++r) {
+                if constexpr (MASKED) {
+                    if (!hvs_row_live(live, j0 + r)) continue;  // (wave-uniform)
+                }
+                nrows += 1u;
+                const float4* rowp = &srow[buf][r * (HVS_LDS_ROW_F / 4)];
+                const float4 attr = rowp[25];
+                const bool pass = hvs_row_passes(p, attr.x, attr.y);
+                const uint64_t pmask = __ballot(pass);
+                if (pmask == 0ull) continue;
+                npass += (uint32_t)__popcll(pmask);
+                // (wave-uniform) no lane that passes takes keys -- the pairs-only launch, the full-scan classes of the range
+                // scan: the row is counted, its distance is nobody's business
+                if (__ballot(pass && takes) == 0ull) continue;
+                float dist;
+                if (SCALAR_ORDER) {
+                    HvsLdsRow1 d1{reinterpret_cast<const float*>(rowp)};
+                    HvsPairAsScalar q1{q2};
+                    dist = hvs_scalar_order_dist(d1, q1);
+                } else {
+                    dist = hvs_exact_dist_pk_lds(rowp, q2);
+                }
+                bool want = pass && takes && !(dist > tau);
+                // a key that finds its segment full: the wave cuts the segment first (or flags the query when it cannot)
+                uint64_t full = __ballot(want && cnt == segcap);
+                if (full != 0ull) {
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                    while (full != 0ull) {
+                        const uint32_t l = (uint32_t)__builtin_ctzll(full);
+                        full &= full - 1ull;
+                        const uint32_t lcap = (uint32_t)__shfl((int)segcap, (int)l);
+                        if (lcap <= knn) {  // no room to cut in: the query is run again (larger lists, or the exact engine)
+                            if (lane == l) {
+                                hvs_flag_fail(B.fail_code, B.overflow, slot);
+                                takes = false;
+                            }
+                            continue;
+                        }
+                        const uint32_t ls0 = (uint32_t)__shfl((int)s0, (int)l);
+                        uint64_t* lst = O.lists + (size_t)(w * 64u + l) * O.stride + ls0;
+                        const uint64_t kth = hvs_wave_select_prune<CAP / 64>(lst, lcap, knn, lane);
+                        if (lane == l) {
+                            cnt = knn;
+                            tau = fminf(tau, hvs_key_dist(kth));  // (a NaN key leaves tau as it is)
+                        }
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                    want = want && takes && !(dist > tau);  // (against the threshold the cut has just set)
+                }
+                if (want) {
+                    myseg[cnt] = hvs_make_key(dist, j0 + r);
+                    ++cnt;
+                    ++nadm;
+                }
+            }
+        }
+        if (more) store_block(buf ^ 1u);
+        __syncthreads();
+        buf ^= 1u;
+    }
+    if (owns) O.counts[slot] = s0 + cnt;
+    if (count && wave_active) {
+        const uint64_t hm = __ballot(have_q);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nadm += __shfl_xor(nadm, o);
+        if (lane == 0u && hm != 0ull) {
+            atomicAdd(&counters[0], (unsigned long long)npass);
+            atomicAdd(&counters[9], (unsigned long long)nrows * (unsigned long long)__popcll(hm));
+            if (nadm) atomicAdd(&counters[10], (unsigned long long)nadm);
+        }
+    }
+}

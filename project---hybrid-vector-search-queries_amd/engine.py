@@ -45,6 +45,15 @@ class MaskInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class AppendInfo(C.Structure):
+    """hvs_append_info (include/hvs.h)."""
+    _fields_ = [("n_indexed", C.c_uint32), ("n_tail", C.c_uint32), ("tail_limit", C.c_uint32), ("reindexes", C.c_uint32),
+                ("tail_pairs", C.c_uint64), ("tail_admitted", C.c_uint64), ("reindex_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -169,6 +178,12 @@ def library():
         "hvs_num_live_rows": (C.c_uint32, [vp]),
         "hvs_mask_stats": (C.c_int, [vp, C.POINTER(MaskInfo)]),
         "hvs_mask_plan": (None, [_u64p, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
+        "hvs_append_rows": (C.c_int, [vp, _f32p, C.c_uint32, _u32p]),
+        "hvs_reserve_rows": (C.c_int, [vp, C.c_uint32]),
+        "hvs_reindex": (C.c_int, [vp]),
+        "hvs_set_tail_limit": (C.c_int, [vp, C.c_uint32]),
+        "hvs_append_stats": (C.c_int, [vp, C.POINTER(AppendInfo)]),
+        "hvs_append_plan": (None, [C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -211,6 +226,13 @@ def mask_plan(live, k, sample_proportion):
     library().hvs_mask_plan(words.ctypes.data_as(_u64p) if words is not None else None, n, int(k), float(sample_proportion),
                             C.byref(n_live), C.byref(cut), _up(pad))
     return int(n_live.value), int(cut.value), pad
+
+
+def append_plan(n_indexed, n_total, sample_proportion):
+    """hvs_append_plan: (sn, tail_lo, tail_hi) for an index over n_indexed of n_total rows."""
+    sn, lo, hi = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    library().hvs_append_plan(int(n_indexed), int(n_total), float(sample_proportion), C.byref(sn), C.byref(lo), C.byref(hi))
+    return int(sn.value), int(lo.value), int(hi.value)
 
 
 class Engine:
@@ -331,6 +353,33 @@ class Engine:
         m = MaskInfo()
         self._ck(self._lib.hvs_mask_stats(self._h, C.byref(m)))
         return m
+
+    # --- row append (include/hvs.h "row append")
+    def append_rows(self, rows):
+        """Append rows (count x 102 float32): searchable by the next call; returns the id of the first of them."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != DCOLS:
+            raise HvsError(-1, "data rows must be count x 102 float32")
+        first = C.c_uint32(self.n)
+        self._ck(self._lib.hvs_append_rows(self._h, _fp(rows), rows.shape[0], C.byref(first)))
+        return int(first.value)
+
+    def reserve_rows(self, n_capacity):
+        """Room for the data set to grow to n_capacity rows without a device-to-device move."""
+        self._ck(self._lib.hvs_reserve_rows(self._h, int(n_capacity)))
+
+    def reindex(self):
+        """Fold the appended rows into the index now."""
+        self._ck(self._lib.hvs_reindex(self._h))
+
+    def set_tail_limit(self, rows):
+        """Appended rows the index may lag behind before an append rebuilds it (0: the default rule)."""
+        self._ck(self._lib.hvs_set_tail_limit(self._h, int(rows)))
+
+    def append_stats(self):
+        a = AppendInfo()
+        self._ck(self._lib.hvs_append_stats(self._h, C.byref(a)))
+        return a
 
     # --- the vec_query seam
     def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None):

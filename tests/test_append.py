@@ -1,0 +1,444 @@
+"""Row append on the GPU: appended rows are searchable at once, on every engine, with the answers of a fresh load of the
+concatenated rows (include/hvs.h "row append").
+
+The expected answers come from the oracle on the concatenated rows (oracle_query + check_parity: distances bit-equal, ids
+equal up to equal-distance ties); the library is compared with itself only where "bit-equal to a fresh load" is the claim.
+Every test sets the tail limit far above its tail unless it is about the limit, and asserts append_stats().n_tail: a silent
+re-index cannot pass for a tail scan.
+"""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import hvs_testlib as T
+
+pytestmark = pytest.mark.gpu
+PKG = importlib.import_module("project---hybrid-vector-search-queries_amd")
+EXACT, BF, I8, F16 = PKG.ENGINE_EXACT_SCAN, PKG.ENGINE_MFMA_FILTER, PKG.ENGINE_MFMA_I8, PKG.ENGINE_MFMA_F16
+N, NQ, NCAT, MAXTAIL = 1 << 17, 224, 10, 2000
+FAR = 1 << 30                                                      # a tail limit no test reaches
+TAILS = (1, 15, 16, 17, 300, 2000)
+
+
+@pytest.fixture(scope="module")
+def data():
+    """N base rows and MAXTAIL more of the same generator (rows N.. are what the tests append), 224 queries."""
+    nodes = T.gen_data(N + MAXTAIL, 71, T.GEN_V1, NCAT)
+    queries = T.gen_queries(NQ, 72, T.GEN_V1, NCAT)
+    queries[-6:-3, 0] = 7.0          # invalid types: nothing matches, the answer is all padding
+    queries[-3:, 0] = -5.0
+    return nodes, queries
+
+
+_oracle_cache = {}
+
+
+def expected(nodes, queries, sp, k, engine="canonical", key=None):
+    ck = (key, nodes.shape[0], float(sp), k, engine) if key is not None else None
+    if ck is not None and ck in _oracle_cache:
+        return _oracle_cache[ck]
+    with T.oracle_k(k):
+        ref, _ = T.oracle_query(nodes, queries, sp, engine=engine)
+    if ck is not None:
+        _oracle_cache[ck] = ref
+    return ref
+
+
+def check(nodes, queries, ids, dists, sp, k, order="simd", engine="canonical", key=None):
+    ref = expected(nodes, queries, sp, k, engine, key)
+    assert ids.max() < nodes.shape[0], "id out of range"
+    with T.oracle_k(k):
+        return T.check_parity(nodes, queries, ids, ref, sp, got_dists=dists, order=order)
+
+
+_passing_cache = {}
+
+
+def passing(nodes, queries, sn, key=None):
+    """rows of [0, sn) passing each query's predicate"""
+    ck = (key, nodes.shape[0], sn)
+    if key is None or ck not in _passing_cache:
+        got = np.array([int(T._passes(nodes[:sn], q).sum()) for q in queries])
+        if key is None:
+            return got
+        _passing_cache[ck] = got
+    return _passing_cache[ck]
+
+
+def sp_for_sn(target, n_total):
+    """A float32 sample_proportion whose sn = uint32(float(sp) * float(n_total)) is `target`."""
+    sp = np.float32((target + 0.5) / n_total)
+    for _ in range(64):
+        sn = int(T.oracle().hvs_oracle_sn(float(sp), n_total))
+        if sn == target:
+            return float(sp)
+        sp = np.nextafter(sp, np.float32(2.0 if sn < target else 0.0))
+    raise AssertionError((target, n_total))
+
+
+def check_unpadded(ids, dists, ids_padded, k, matches, n_total):
+    """Padding off: the slots a padded answer fills with n-1, n-2, ... stay 0xFFFFFFFF / +inf, the others are its entries."""
+    for q in range(ids.shape[0]):
+        have = ids[q] != 0xFFFFFFFF
+        m = min(int(matches[q]), k)
+        assert int(have.sum()) == m and have[:m].all() and np.isinf(dists[q][m:]).all(), q
+        rest = sorted(ids_padded[q].tolist())
+        for x in ids[q][:m].tolist():
+            rest.remove(x)
+        assert rest == sorted(range(n_total - 1, n_total - 1 - (k - m), -1)), q
+
+
+def fresh(engine, rows, limit=FAR):
+    e = PKG.Engine(0)
+    e.set_engine(engine)
+    e.set_tail_limit(limit)
+    e.load_data(rows)
+    return e
+
+
+# ---- 1. every engine x tail size ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tail", TAILS)
+@pytest.mark.parametrize("engine", [EXACT, BF, I8, F16])
+def test_every_engine_and_tail_size(data, engine, tail, monkeypatch):
+    """sample_proportion 1, 0.5, 0.1 and one whose sn falls inside the tail x k = 8, 100, 256, padding on; off at 1."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, queries = data
+    nodes = nodes_all[:N + tail]
+    n_total = N + tail
+    sp_in = sp_for_sn(N + tail // 2, n_total)                       # sn inside the tail (tail 1: at its edge, nothing to scan)
+    with fresh(engine, nodes[:N]) as e:
+        assert e.append_rows(nodes[N:]) == N and e.n == n_total
+        a = e.append_stats()
+        assert (a.n_indexed, a.n_tail, a.reindexes) == (N, tail, 0)
+        assert np.array_equal(e.download_data(N - 1, tail + 1), nodes[N - 1:])
+        for k in (100, 8, 256):
+            e.set_k(k)
+            for sp in (1.0, 0.5, 0.1, sp_in):
+                ids, d = e.query(queries, sp)
+                t, a = e.last_timing(), e.append_stats()
+                st = check(nodes, queries, ids, d, sp, k, key="gen")
+                sn, lo, hi = PKG.append_plan(N, n_total, sp)
+                want_pairs = int(passing(nodes, queries, sn, "gen").sum())
+                print(engine, tail, k, sp, st, "ran", t.engine, "retry", t.retry_queries, "fallback", t.fallback_queries, a.as_dict())
+                assert a.n_tail == tail and a.n_indexed == N
+                assert t.pairs == want_pairs, (sp, k, t.pairs, want_pairs)
+                if t.engine != EXACT:
+                    assert a.tail_pairs == NQ * (hi - lo), (sp, k, a.tail_pairs, hi - lo)
+                if sp == 1.0:
+                    assert t.engine == engine, "the requested engine did not run"
+                    e.set_padding(False)
+                    ids0, d0 = e.query(queries, sp)
+                    e.set_padding(True)
+                    check_unpadded(ids0, d0, ids, k, passing(nodes, queries, sn, "gen"), n_total)
+
+
+# ---- 2. the answer lives in the tail -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, I8, F16])
+def test_the_answer_lives_in_the_tail(data, engine, monkeypatch):
+    """Appended rows = the queries' own vectors plus small noise; half carry attributes that pass their query's predicate, half
+    attributes that fail it: the passing half leads its query's answer, the failing half appears nowhere."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, queries = data
+    q = queries[:NQ - 6]                                            # (the invalid types match nothing)
+    rng = np.random.default_rng(5)
+    tail = np.empty((2 * q.shape[0], T.DCOLS), np.float32)
+    for half in (0, 1):                                             # rows 2i pass, rows 2i + 1 fail
+        rows = tail[half::2]
+        rows[:, 2:] = q[:, 4:] + rng.normal(0, 1e-3, (q.shape[0], 100)).astype(np.float32)
+        typ = q[:, 0].astype(int)
+        v, l, r = np.trunc(q[:, 1]), q[:, 2], q[:, 3]
+        rows[:, 0] = np.where(half == 0, v, v + 1)                  # C == v or not (matters to types 1, 3)
+        rows[:, 1] = np.where(half == 0, (l + r) / 2, r + 1)        # l <= T <= r or not (types 2, 3)
+        if half == 1:
+            rows[typ == 0, 2:] += 1e3                               # type 0 has no predicate to fail: these rows are far away
+    nodes = np.concatenate([nodes_all[:N], tail])
+    with fresh(engine, nodes[:N]) as e:
+        first = e.append_rows(tail)
+        ids, d = e.query(queries, 1.0)
+        assert e.append_stats().n_tail == tail.shape[0]
+        check(nodes, queries, ids, d, 1.0, 100)
+        own = first + 2 * np.arange(q.shape[0])
+        typ = q[:, 0].astype(int)
+        passes = np.array([bool(T._passes(tail[2 * i:2 * i + 1], q[i])[0]) for i in range(q.shape[0])])
+        fails = np.array([not T._passes(tail[2 * i + 1:2 * i + 2], q[i])[0] for i in range(q.shape[0])])
+        assert passes.mean() > 0.9 and fails[typ != 0].all()       # (a generated range with l > r admits no T at all)
+        # (padding appends the last rows of D whatever their attributes -- tail rows here: the two claims are about matches)
+        e.set_padding(False)
+        ids, _ = e.query(queries, 1.0)
+        assert np.array_equal(ids[:q.shape[0], 0][passes], own[passes]), "a query's own (passing) tail row is not its nearest neighbour"
+        for i in np.nonzero(typ != 0)[0]:
+            assert own[i] + 1 not in ids[i], i
+
+
+# ---- 3. infinite tau and overfull lists ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [100, 256])
+@pytest.mark.parametrize("engine", [I8, F16])
+def test_a_category_that_exists_in_the_tail_only(data, engine, k, monkeypatch):
+    """No base row has category 9, all 2000 tail rows have: type-1 / type-3 queries on v = 9 reach the tail scan with an
+    infinite threshold and admit every matching row -- more than the 256 / 512 keys a lane's segment holds, so the in-kernel
+    cut runs; nothing may fall back to the exact engine."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, _ = data
+    base = nodes_all[:N].copy()
+    base[base[:, 0] == np.float32(9), 0] = np.float32(8)
+    tail = nodes_all[N:N + 2000].copy()
+    tail[:, 0] = np.float32(9)
+    nodes = np.concatenate([base, tail])
+    queries = np.concatenate([T.gen_queries(64, 75, T.GEN_V1, NCAT, force_type=1), T.gen_queries(64, 76, T.GEN_V1, NCAT, force_type=3),
+                              T.gen_queries(64, 77, T.GEN_V1, NCAT)])
+    queries[:128, 1] = 9.0
+    lo, hi = np.quantile(tail[:, 1], [0.05, 0.95])
+    queries[64:128, 2], queries[64:128, 3] = lo, hi                 # type 3: ~1800 of the 2000 rows pass
+    with fresh(engine, base) as e:
+        e.set_k(k)
+        e.append_rows(tail)
+        ids, d = e.query(queries, 1.0)
+        t, a = e.last_timing(), e.append_stats()
+        print(engine, k, "retry", t.retry_queries, "fallback", t.fallback_queries, a.as_dict())
+        assert a.n_tail == 2000 and t.engine == engine
+        assert t.fallback_queries == 0
+        assert (ids[:128] >= N).all()
+        check(nodes, queries, ids, d, 1.0, k)
+        assert t.pairs == int(passing(nodes, queries, nodes.shape[0]).sum())
+
+
+# ---- 4. pieces, re-index, limit -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, I8])
+def test_pieces_reindex_and_limit(data, engine, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, queries = data
+    nodes = nodes_all[:N + 1064]
+    with fresh(engine, nodes[:N]) as e, fresh(engine, nodes[:N]) as f:
+        assert [e.append_rows(nodes[N:N + 1]), e.append_rows(nodes[N + 1:N + 64]), e.append_rows(nodes[N + 64:])] == [N, N + 1, N + 64]
+        assert e.append_rows(nodes[:0]) == e.n == N + 1064                       # count == 0: nothing changes
+        f.append_rows(nodes[N:])
+        got, want = e.query(queries, 1.0), f.query(queries, 1.0)
+        assert e.append_stats().n_tail == f.append_stats().n_tail == 1064
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+        check(nodes, queries, got[0], got[1], 1.0, 100, key="gen")
+        e.reindex()
+        a = e.append_stats()
+        assert (a.n_tail, a.n_indexed, a.reindexes) == (0, N + 1064, 1) and a.reindex_ms > 0
+        again = e.query(queries, 1.0)
+        assert again[0].tobytes() == got[0].tobytes() and again[1].tobytes() == got[1].tobytes()
+        assert e.append_stats().tail_pairs == 0 and e.last_timing().engine == engine
+        e.reindex()                                                                  # nothing to fold in: a no-op
+        assert e.append_stats().reindexes == 1
+    with fresh(engine, nodes[:N], limit=512) as e:
+        e.append_rows(nodes[N:N + 400])
+        a = e.append_stats()
+        assert (a.n_tail, a.n_indexed, a.reindexes, a.tail_limit) == (400, N, 0, 512)
+        e.append_rows(nodes[N + 400:N + 600])                                        # 600 > 512: re-indexed before it returns
+        a = e.append_stats()
+        assert (a.n_tail, a.n_indexed, a.reindexes) == (0, N + 600, 1)
+        ids, d = e.query(queries, 1.0)
+        check(nodes[:N + 600], queries, ids, d, 1.0, 100)
+        e.set_tail_limit(0)
+        assert e.append_stats().tail_limit == max(4096, (N + 600) >> 10)
+        e.load_data(nodes[:N])                                                       # a load resets all but the limit
+        a = e.append_stats()
+        assert (a.n_tail, a.n_indexed, a.reindexes, a.tail_limit) == (0, N, 0, 4096)
+
+
+# ---- 5. mask x tail -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, I8, F16])
+def test_mask_and_tail(data, engine, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, queries = data
+    import test_row_mask as M
+    n1, n2 = N + 1000, N + 1500
+    rng = np.random.default_rng(11)
+
+    def verify(e, live, nodes, sps=(1.0, 0.5)):
+        assert e.n_live == int(live.sum()) and np.array_equal(e.row_mask(), live) and e.row_mask().size == nodes.shape[0]
+        for sp in sps:
+            ids, d = e.query(queries, sp)
+            M.check(nodes, queries, live, ids, d, sp, 100)
+            assert e.last_timing().pairs == int(M.matches_in_live_prefix(nodes, queries, live, sp).sum()), sp
+        a, m = e.append_stats(), e.mask_stats()
+        assert a.n_indexed == N and a.n_tail == nodes.shape[0] - N
+        if engine != EXACT:
+            assert m.tiles_patched == 2 * int((~live[:N]).sum()), (m.tiles_patched, int((~live[:N]).sum()))
+
+    with fresh(engine, nodes_all[:N]) as e:
+        e.append_rows(nodes_all[N:n1])
+        live = np.ones(n1, bool)
+        dead = np.concatenate([rng.choice(N, 20_000, replace=False), N + rng.choice(700, 200, replace=False), np.arange(n1 - 300, n1)])
+        live[dead] = False
+        e.delete_rows(dead)                                                          # base and tail ids, the last 300 among them
+        verify(e, live, nodes_all[:n1])
+        live[rng.choice(dead, 5000, replace=False)] = True                           # rows come back, in the base and in the tail
+        e.set_row_mask(live)
+        verify(e, live, nodes_all[:n1], sps=(1.0,))
+        e.append_rows(nodes_all[n1:n2])                                              # appended rows start live
+        live = np.concatenate([live, np.ones(n2 - n1, bool)])
+        verify(e, live, nodes_all[:n2])
+        e.delete_rows(np.arange(n2 - 40, n2))
+        live[n2 - 40:] = False
+        verify(e, live, nodes_all[:n2], sps=(1.0,))
+
+
+# ---- 6. small sets -------------------------------------------------------------------------------------------------------------
+def test_a_small_set_grows_into_an_index(data):
+    """1000 rows have no index (the exact engine scans everything, appends only extend D); with the default limit one is built
+    by the append that takes the set past 4096 rows, and the next append leaves a tail behind it."""
+    nodes_all, queries = data
+    with PKG.Engine(0) as e:
+        e.load_data(nodes_all[:1000])
+        n = 1000
+        for step, want in ((500, (0, 0)), (1500, (0, 0)), (1000, (0, 0)), (2000, (6000, 0)), (1000, (6000, 1000))):
+            if n == 6000:
+                e.set_engine(I8)
+            assert e.append_rows(nodes_all[n:n + step]) == n
+            n += step
+            a = e.append_stats()
+            assert (a.n_indexed, a.n_tail) == want and e.n == n, (n, a.as_dict())
+            for sp in (1.0, 0.5):
+                ids, d = e.query(queries, sp)
+                check(nodes_all[:n], queries, ids, d, sp, 100)
+                assert e.last_timing().pairs == int(passing(nodes_all[:n], queries, PKG.append_plan(0, n, sp)[0]).sum())
+            if n > 6000:
+                e.query(queries, 1.0)
+                assert e.last_timing().engine == I8, "the requested filter engine did not run"
+        assert e.append_stats().reindexes == 1
+
+
+def test_a_set_of_5000_rows(data):
+    nodes_all, queries = data
+    with PKG.Engine(0) as e:
+        e.load_data(nodes_all[:5000])
+        n = 5000
+        for engine, step in ((EXACT, 500), (I8, 1500)):
+            e.set_engine(engine)
+            e.append_rows(nodes_all[n:n + step])
+            n += step
+            a = e.append_stats()
+            assert (a.n_indexed, a.n_tail, a.tail_limit) == (5000, n - 5000, 4096)
+            for sp in (1.0, 0.5):
+                ids, d = e.query(queries, sp)
+                check(nodes_all[:n], queries, ids, d, sp, 100)
+                assert e.last_timing().pairs == int(passing(nodes_all[:n], queries, PKG.append_plan(0, n, sp)[0]).sum())
+                assert e.last_timing().engine == engine
+
+
+# ---- 7. scalar distance order ---------------------------------------------------------------------------------------------------
+def test_scalar_distance_order_with_a_tail(data):
+    nodes_all, queries = data
+    nodes = nodes_all[:N + 300]
+    with fresh(EXACT, nodes[:N]) as e:
+        e.set_distance_order(1)
+        e.append_rows(nodes[N:])
+        for sp in (1.0, 0.5):
+            ids, d = e.query(queries, sp)
+            assert e.append_stats().n_tail == 300
+            check(nodes, queries, ids, d, sp, 100, order="scalar", engine="baseline")
+
+
+# ---- 8. multi-GPU context ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, I8])
+def test_multi_gpu_context_with_a_tail(data, engine, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, queries = data
+    nodes = nodes_all[:N + 300]
+    with PKG.Engine(0) as one, PKG.Engine(devices=[0, 0, 0]) as three:
+        for x in (one, three):
+            x.set_engine(engine)
+            x.set_tail_limit(FAR)
+            x.load_data(nodes[:N])
+            assert x.append_rows(nodes[N:]) == N and x.n == N + 300
+        for sp in (1.0, 0.5):
+            a, b = one.query(queries, sp), three.query(queries, sp)
+            assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), sp
+            check(nodes, queries, b[0], b[1], sp, 100, key="gen")
+            s1, s3 = one.append_stats(), three.append_stats()
+            assert (s3.n_indexed, s3.n_tail, s3.reindexes) == (s1.n_indexed, s1.n_tail, s1.reindexes) == (N, 300, 0)
+            assert s3.tail_pairs == s1.tail_pairs and one.last_timing().pairs == three.last_timing().pairs
+        for x in (one, three):
+            x.upload_queries(queries)
+            x.query_resident(10, 200, 1.0)
+            x.sync()
+        a, b = one.download_results(10, 200), three.download_results(10, 200)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+        three.reindex()
+        s3 = three.append_stats()
+        assert (s3.n_indexed, s3.n_tail, s3.reindexes) == (N + 300, 0, 1)
+        b = three.query(queries, 1.0)
+        check(nodes, queries, b[0], b[1], 1.0, 100, key="gen")
+
+
+# ---- 9. child processes (the environment is read at library load) -----------------------------------------------------------------
+_CHILD = r"""
+import importlib, os, sys, numpy as np
+sys.path.insert(0, 'tests'); sys.path.insert(0, '.')
+import hvs_testlib as T
+import test_append as A
+PKG = importlib.import_module('project---hybrid-vector-search-queries_amd')
+nodes = T.gen_data(A.N + 700, 71, T.GEN_V1, A.NCAT); queries = T.gen_queries(1500, 74, T.GEN_V1, A.NCAT)
+retries = 0
+for engine in (PKG.ENGINE_MFMA_I8, PKG.ENGINE_MFMA_F16, PKG.ENGINE_EXACT_SCAN):
+    with A.fresh(engine, nodes[:A.N]) as e:
+        e.append_rows(nodes[A.N:])
+        for sp in (1.0, 0.5):
+            ids, d = e.query(queries, sp)
+            t, a = e.last_timing(), e.append_stats()
+            assert a.n_tail == 700 and (t.engine == engine or sp < 1.0), (engine, t.engine, a.as_dict())
+            if engine == PKG.ENGINE_MFMA_I8 and sp == 1.0 and os.environ.get('HVS_I8_ROTATE') == '1':
+                assert t.flags & 4, 'the INT8 tiles were not cut from the rotated vectors'
+            st = A.check(nodes, queries, ids, d, sp, 100, key='child')
+            retries += t.retry_queries
+            print(engine, sp, st, 'launches', t.main_kernel_launches, 'retry', t.retry_queries, 'fallback', t.fallback_queries, a.as_dict())
+        e.upload_queries(queries); e.query_resident(100, 1300, 1.0); e.sync()
+        ri, rd = e.download_results(100, 1300)
+        A.check(nodes, queries[100:1400], ri, rd, 1.0, 100)
+if os.environ.get('HVS_GUESS_PFAIL') == '1':
+    assert retries > 0, 'no guessed threshold failed: the retry batch did not run'
+print('SUBPROCESS-OK')
+"""
+
+
+@pytest.mark.parametrize("env", [dict(HVS_I8_ROTATE="1", HVS_MFMA_BATCH="256", HVS_EXACT_BATCH="512"), dict(HVS_GUESS_PFAIL="1", HVS_I8_ROTATE="0")],
+                         ids=["many batches, two lanes, rotated tiles", "retry batches"])
+def test_child_process_with_a_tail(env):
+    r = subprocess.run([sys.executable, "-c", _CHILD], capture_output=True, text=True, env=dict(os.environ, **env), cwd=T.REPO, timeout=900)
+    print(r.stdout[-3000:])
+    assert "SUBPROCESS-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+# ---- 10. errors -----------------------------------------------------------------------------------------------------------------------
+def test_errors_leave_the_context_as_it_was(data):
+    nodes_all, queries = data
+    nodes = nodes_all[:N + 300]
+    lib = PKG.library()
+    with PKG.Engine(0) as e:
+        with pytest.raises(PKG.HvsError) as err:
+            e.append_rows(nodes[N:])                                                 # no data loaded
+        assert err.value.code == -4
+        assert lib.hvs_append_rows(e._h, None, 0, None) == 0                         # count == 0: fine, whatever else is wrong
+    with fresh(I8, nodes[:N]) as e:
+        e.append_rows(nodes[N:])
+        live = np.ones(N + 300, bool)
+        live[::7] = False
+        e.set_row_mask(live)
+        before, stats = e.query(queries, 1.0), e.append_stats().as_dict()
+        assert lib.hvs_append_rows(e._h, None, 5, None) == -1                        # NULL rows
+        assert lib.hvs_append_rows(e._h, nodes.ctypes.data_as(C.POINTER(C.c_float)), 0xFFFFFFFF - 10, None) == -1   # past 2^32 - 1 rows
+        assert e.n == N + 300 and np.array_equal(e.row_mask(), live)
+        after = e.query(queries, 1.0)
+        assert e.append_stats().as_dict() == stats
+        assert after[0].tobytes() == before[0].tobytes() and after[1].tobytes() == before[1].tobytes()
+    # an append between the steps of an earlier resident call: that call's results are its own
+    with fresh(I8, nodes[:N]) as e:
+        want = e.query(queries, 1.0)
+        e.upload_queries(queries)
+        e.query_resident(0, NQ, 1.0)
+        e.append_rows(nodes[N:])
+        got = e.download_results(0, NQ)
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+        check(nodes[:N], queries, got[0], got[1], 1.0, 100)
+        ids, d = e.query(queries, 1.0)
+        check(nodes, queries, ids, d, 1.0, 100, key="gen")
