@@ -286,6 +286,48 @@ int hvs_append_stats(hvs_ctx *ctx, hvs_append_info *out);
 void hvs_append_plan(uint32_t n_indexed, uint32_t n_total, float sample_proportion, uint32_t *sn, uint32_t *tail_lo,
                      uint32_t *tail_hi);
 
+/* ---- row update in place: ids kept, new contents searchable at once -------------------------- */
+
+/*
+ * After hvs_update_rows(ctx, ids, rows, count) the context behaves, in every later call on every engine, as a fresh context
+ * would after hvs_load_data of the current rows with row ids[i] replaced by rows[i], under the same settings (engine, k,
+ * distance order, padding, mask): the same ids, bit-equal out_dists, the same (dist asc, id asc) tie rule, the same
+ * hvs_timing.pairs.  All 102 floats of a row change, C and T included: an updated row may enter or leave any query's
+ * predicate.  Liveness does not change: a dead row stays dead with its new contents, and a later hvs_set_row_mask that
+ * revives it shows the new contents.  n, sn, the cut and the padding ids are untouched; hvs_download_data returns the new
+ * contents.  Duplicates in ids are applied in order: the last one wins.
+ * A row with id in [n_indexed, n) (the tail), or any row of a context without an index, is only overwritten in D.  An indexed
+ * row (id < n_indexed) that is updated becomes STALE: the orderings and tiles still describe its old contents, so the index
+ * treats it as dead (its tile entries are tombstoned like a deleted row's) and every batch that goes through the index scans
+ * the stale rows below sn by id, in exact order, next to the tail.  Queries never re-index.  The limit is shared with the
+ * tail: an update -- or an append -- that would leave n_tail + n_stale > tail_limit re-indexes over all rows before it
+ * returns; hvs_reindex does so on request (also when only stale rows are left to fold in); either clears the stale set and
+ * counts in hvs_append_info.reindexes.  hvs_load_data / hvs_gen_data reset the stale set.  While no indexed row is stale every
+ * call runs exactly the kernels it runs without this function.
+ * count == 0: HVS_OK, nothing changes.  ids == NULL, rows == NULL or any ids[i] >= n: HVS_EINVAL; no data loaded: HVS_ESTATE;
+ * no room: HVS_ENOMEM; in each of these cases the context, D, the mask and the index are as they were.  Any other failure is
+ * reported as hvs_append_rows reports it.  The call accepts a multi-GPU context: rows and state are replicated like D and the
+ * mask, and room is secured on every GPU before any GPU changes.  The D-sharded mode (sharding.py, hvs_merge_shards_device)
+ * knows nothing of updates, as it knows nothing of masks or appends.
+ * While rows are stale hvs_mask_info.tiles_patched counts their tile entries too, and dead_survivors keeps counting dead rows
+ * only: a survivor dropped because its row is stale (and live) is counted in stale_survivors.
+ */
+typedef struct hvs_update_info {
+    uint32_t n_stale;          /* indexed rows whose index entry describes old contents                              */
+    uint32_t limit;            /* n_tail + n_stale above which an update or append re-indexes (= tail_limit)         */
+    uint64_t stale_pairs;      /* last call: (query, stale row) pairs the stale scan evaluated (re-run batches apart) */
+    uint64_t stale_admitted;   /* last call: of those, keys that entered a candidate list                             */
+    uint64_t stale_survivors;  /* last call: filter survivors dropped because the row's index entry is stale          */
+} hvs_update_info;             /* 32 bytes */
+int hvs_update_rows(hvs_ctx *ctx, const uint32_t *ids, const float *rows /* host, count x 102 */, uint32_t count);
+/* Call after hvs_sync / hvs_query.  Multi-GPU context: one GPU's state (it is replicated), the three per-call counters summed. */
+int hvs_update_stats(hvs_ctx *ctx, hvs_update_info *out);
+/* host arithmetic, no GPU, no context: fold one call's ids into the ascending stale list.  Returns the new length, or
+ * 0xFFFFFFFF (nothing written) if any id >= n_total.  out_stale (room for n_stale + count): ascending, unique, ids >=
+ * n_indexed left out.  out_last[i] (count entries, may be NULL) = 1 where occurrence i is the last of its id. */
+uint32_t hvs_update_plan(const uint32_t *stale, uint32_t n_stale, const uint32_t *ids, uint32_t count,
+                         uint32_t n_indexed, uint32_t n_total, uint32_t *out_stale, uint8_t *out_last);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <iterator>
 #include <new>
 #include <string>
 #include <thread>
@@ -167,6 +168,20 @@ struct hvs_ctx : HvsLane {
     double reindex_ms = 0.0;      // the last of them
     uint32_t index_tried_n = 0;   // no-index state: n at the last attempt to build one (0: none yet)
     uint32_t live_cap = 0;        // u64 words d_live has room for
+    // updated rows (hvs_update_rows).  An indexed row whose contents changed is STALE: alive in D, dead as far as
+    // the index knows.  While there are such rows the launches that reach a row THROUGH THE INDEX take d_ilive (live AND NOT
+    // stale) where they take d_live otherwise, every masked kernel runs in its MASKED form, and hvs_k_scan_stale scans the
+    // stale rows by id for every batch that goes through the index.  Empty list: none of the buffers below is read.
+    std::vector<uint32_t> h_stale;  // ascending, unique, ids < n_indexed
+    uint32_t* d_stale_ids = nullptr;
+    uint32_t stale_cap = 0;         // ids d_stale_ids has room for
+    // two planes of W = 2 ceil(n_indexed / 64) u32 words: [0, W) live AND NOT stale, [W, 2W) the row mask's bits of the
+    // indexed rows (what hvs_k_rescore tells stale from dead by, HVS_RESCORE_TWO_MASKS)
+    uint32_t* d_ilive = nullptr;
+    uint32_t ilive_cap = 0;         // u32 words it has room for
+    float* d_upd_rows = nullptr;    // staging of the running hvs_update_rows: its rows, their ids, the staged row of each id
+    uint32_t *d_upd_ids = nullptr, *d_upd_from = nullptr;
+    uint32_t upd_cap = 0;
 
     // resident queries + results
     float* d_q = nullptr;
@@ -464,13 +479,19 @@ void with_cap(int cap, F f)
         f(std::integral_constant<int, 256>{});
 }
 
+// The two roles of the mask.  `masked`: some row is dead or some index entry is stale -- the MASKED kernels run,
+// pairs are counted the masked way, no host-side range counts.  Launches that reach a row by its id in D take c->d_live;
+// launches that reach it through the index (perm, tiles) take index_mask(c), which differs only while rows are stale.
+bool masked(const hvs_ctx* c) { return c->n_dead != 0u || !c->h_stale.empty(); }
+const uint32_t* index_mask(const hvs_ctx* c) { return c->h_stale.empty() ? c->d_live : c->d_ilive; }
+
 // ... and for the two forms of the kernels that read the live-row mask: `f` gets (capacity, masked) as compile-time constants;
-// masked only while at least one row is dead
+// masked only while at least one row is dead or stale
 template <typename F>
 void with_cap_mask(const hvs_ctx* c, F f)
 {
     with_cap(c->cap, [&](auto CAPT) {
-        if (c->n_dead)
+        if (masked(c))
             f(CAPT, std::true_type{});
         else
             f(CAPT, std::false_type{});
@@ -756,7 +777,7 @@ int ensure_live_prefix(hvs_ctx* c)
     hipError_t e = hipSuccess;
     for (const HvsOrdering& o : c->ord) {
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(hvs_k_live_flags, dim3(hvs_ceil_div(n + 1u, 256u)), dim3(256), 0, c->stream, c->d_live, o.perm, n, o.lp);
+        hipLaunchKernelGGL(hvs_k_live_flags, dim3(hvs_ceil_div(n + 1u, 256u)), dim3(256), 0, c->stream, index_mask(c), o.perm, n, o.lp);
         e = rocprim::exclusive_scan(tmp, tmp_bytes, o.lp, o.lp, 0u, (size_t)n + 1u, rocprim::plus<uint32_t>(), c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -777,21 +798,22 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
                            c->d_counters);
     } else {
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<true>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, c->d_live);
+                           c->d_counters, index_mask(c));
     }
     return HVS_OK;
 }
 
-// Tombstones (hvs_k_patch_tiles): the never-hit encoding over the tile entries of the dead rows, both orderings.  Called after
-// every mask change that only kills rows and at the end of every tile build while rows are dead.
+// Tombstones (hvs_k_patch_tiles): the never-hit encoding over the tile entries of the dead and the stale rows, both orderings.
+// Called after every mask change that only kills rows, after every update that makes rows stale, and at the end of every tile
+// build while rows are dead or stale.
 int patch_tiles(hvs_ctx* c)
 {
-    if (!c->n_dead || c->fmt.built == HVS_FMT_NONE || !c->ord[0].tiles || !c->d_live || !c->d_mask_stat) return HVS_OK;
+    if (!masked(c) || c->fmt.built == HVS_FMT_NONE || !c->ord[0].tiles || !index_mask(c) || !c->d_mask_stat) return HVS_OK;
     const HvsLevels L = c->lv;
     HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
     for (const HvsOrdering& o : c->ord)
-        hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, c->d_live, o.perm, c->n_indexed, L, o.bpos, o.tiles,
+        hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, index_mask(c), o.perm, c->n_indexed, L, o.bpos, o.tiles,
                            reinterpret_cast<int*>(o.nrm), c->fmt.built, c->d_mask_stat);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1195,6 +1217,22 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
     });
 }
 
+// The stale rows of the batch in c->fb (hvs_k_scan_stale): the prefix of the ascending stale list with id < sn
+// (under a mask sn is the cut).  0: nothing to launch.
+uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
+{
+    if (!c->have_order || c->h_stale.empty()) return 0u;
+    return (uint32_t)(std::lower_bound(c->h_stale.begin(), c->h_stale.end(), sn) - c->h_stale.begin());
+}
+void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
+{
+    const HvsBatch& B = c->fb;
+    with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+        hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
+                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->d_stale_ids, m, c->d_counters, count ? 1 : 0, c->d_live);
+    });
+}
+
 // Exact engine on top of the index.  Queries with a categorical predicate (types 1 and 3) scan only
 // their position range of the (C,T) ordering (hvs_k_scan_ranges): ~1 % / 0.25 % of the rows, 17-25x
 // faster than scanning everything.  Type-0 and type-2 queries keep the sequential full scan in original
@@ -1203,11 +1241,12 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
 // streaming all of them (8.2 k vs 14 k queries/s).
 int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
 {
-    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !c->n_dead, HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
+    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !masked(c), HVS_FMT_BF16, true);  // (the range scan uses the ranges only)
     if (rc) return rc;
     HvsBatch& B = c->fb;
     const bool tail = have_tail(c, sn);  // rows behind the index: counted for every class, scanned here for the range classes
-    if (c->n_dead) {
+    const uint32_t stale = stale_below(c, sn);  // likewise the indexed rows whose index entry is stale
+    if (masked(c)) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn < c->n_indexed)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
@@ -1222,16 +1261,19 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     if (nq0 && (rc = run_batch_exact(c, 0, nq0, sn, B.qid, false))) return rc;
     if (nq2 && (rc = run_batch_exact(c, 0, nq2, sn, B.qid + slot2, false))) return rc;
     if (slot_begin >= slot_end) {
-        if (tail) {  // (the full scans above walked the tail themselves: its pairs only)
-            launch_tail(c, sn, HvsTailOut{nullptr, nullptr, nullptr, 0u, 0u, 0u}, true);
-            HVS_HIP(c, hipGetLastError());
-        }
+        // (the full scans above walked the tail and the stale rows themselves: their pairs only)
+        if (tail) launch_tail(c, sn, HvsTailOut{nullptr, nullptr, nullptr, 0u, 0u, 0u}, true);
+        if (stale) launch_stale(c, stale, HvsTailOut{nullptr, nullptr, nullptr, 0u, 0u, 0u}, true);
+        if (tail || stale) HVS_HIP(c, hipGetLastError());
         return HVS_OK;
     }
     const uint32_t waves = (slot_end - slot_begin + 63u) / 64u;
     uint32_t nchunks = std::max(1u, std::min(64u, (8192u + waves - 1u) / waves));
     nchunks = std::min(nchunks, std::max(1u, (1u << 20) / B.nslots));  // candidate lists: at most 2 GB
-    const size_t lists = (size_t)B.nslots * (nchunks + (tail ? 1u : 0u));  // (the tail's keys: one more chunk of lists)
+    // (the tail's keys and the stale rows' keys: one more chunk of lists each -- a list of the exact engine holds c->cap keys,
+    // which is what one such scan may fill before it cuts its segment back to k)
+    const uint32_t xchunks = (tail ? 1u : 0u) + (stale ? 1u : 0u);
+    const size_t lists = (size_t)B.nslots * (nchunks + xchunks);
     if (lists > c->cand_lists) {
         if ((rc = dev_alloc(c, &c->d_cand, lists * (size_t)c->cap))) return rc;
         if ((rc = dev_alloc(c, &c->d_cand_cnt, lists))) return rc;
@@ -1243,14 +1285,18 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0, c->stream,
                            c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt,
-                           c->d_counters, c->d_live);
+                           c->d_counters, index_mask(c));
     });
     kernel_timer_end(c, ev);
     if (tail)
         launch_tail(c, sn, HvsTailOut{c->d_cand + (size_t)nchunks * B.nslots * (size_t)c->cap, c->d_cand_cnt + (size_t)nchunks * B.nslots, nullptr,
                                       (uint32_t)c->cap, slot_begin, slot_end}, true);
+    if (stale) {
+        const size_t at = (size_t)(nchunks + (tail ? 1u : 0u)) * B.nslots;
+        launch_stale(c, stale, HvsTailOut{c->d_cand + at * (size_t)c->cap, c->d_cand_cnt + at, nullptr, (uint32_t)c->cap, slot_begin, slot_end}, true);
+    }
     const uint32_t nsel = slot_end - slot_begin;
-    launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks + (tail ? 1u : 0u), c->d_cand + (size_t)slot_begin * (size_t)c->cap,
+    launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks + xchunks, c->d_cand + (size_t)slot_begin * (size_t)c->cap,
                   c->d_cand_cnt + slot_begin);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1370,7 +1416,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
 {
     const int fmt = c->fmt.built;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
-    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !list && !c->n_dead, fmt, false, list, want_fcap);
+    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !list && !masked(c), fmt, false, list, want_fcap);
     if (rc) return rc;
     if ((rc = build_items(c))) return rc;
     HvsBatch& B = c->fb;
@@ -1388,7 +1434,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     }
     const HvsGuessTable G = c->guess_tab[gslot];
     B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
-    if (c->n_dead && !list) {
+    if (masked(c) && !list) {
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn < n && !list)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
@@ -1403,7 +1449,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     with_cap_mask(c, [&](auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)),
                            dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L,
-                           c->d_counters, std::max(1u, seed_chunks), c->d_live);
+                           c->d_counters, std::max(1u, seed_chunks), index_mask(c));
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
     auto launch_merge = [&](bool final, uint32_t next) {
@@ -1421,8 +1467,10 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
     // last re-scoring filled -- every tail row with distance <= tau_last is then held beside every indexed one, which is all
     // the final check needs.  The guessed thresholds never see these rows.
+    // Likewise, right behind them, the indexed rows whose index entry is stale: no list holds one of them so far.
     auto tail_before_final = [&]() {
         if (have_tail(c, sn)) launch_tail(c, sn, HvsTailOut{B.cand, B.candcnt, B.tau, B.fcap, 0u, B.nslots}, !list);
+        if (const uint32_t m = stale_below(c, sn)) launch_stale(c, m, HvsTailOut{B.cand, B.candcnt, B.tau, B.fcap, 0u, B.nslots}, !list);
     };
     if (L.K == 0u) tail_before_final();
     launch_merge(L.K == 0u, 1u);
@@ -1453,8 +1501,10 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         with_cap_mask(c, [&](auto, auto MT) {
             constexpr bool M = decltype(MT)::value;
             const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;  // (entry format)
-            hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, n, sn,
-                               c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, c->d_live);
+            // (while rows are stale the front end gets both masks and tells stale from dead: HVS_RESCORE_TWO_MASKS)
+            hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data,
+                               c->h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS), sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters,
+                               index_mask(c));
         });
         if (last == L.K) tail_before_final();
         launch_merge(last == L.K, last + 1u);
@@ -1857,7 +1907,7 @@ void leaf_destroy(hvs_ctx* c)
     free_index(c);  // (keeps ord[].lp: freed here)
     void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
                     c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->d_live, c->d_pad_ids, c->d_mask_ids,
-                    c->d_mask_stat, c->ord[0].lp, c->ord[1].lp};
+                    c->d_mask_stat, c->ord[0].lp, c->ord[1].lp, c->d_stale_ids, c->d_ilive, c->d_upd_rows, c->d_upd_ids, c->d_upd_from};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->ord[0].lp = c->ord[1].lp = nullptr;
@@ -1957,6 +2007,7 @@ int begin_data(hvs_ctx* c, uint32_t n)
     c->n_cap = 0;
     c->live_cap = 0;
     c->reindexes = 0;  // (the tail is empty: free_index in finish_data; the limit stays)
+    c->h_stale.clear();  // (no row is stale; the device buffers stay for the next update)
     c->reindex_ms = 0.0;
     c->index_tried_n = 0;
     // a new data set starts with every row live
@@ -2483,6 +2534,29 @@ int refresh_pad_ids(hvs_ctx* c)
     return HVS_OK;
 }
 
+// The index-validity mask of a context with stale rows (hvs_ctx::d_ilive), from the host's mask and stale list; room for it
+// was secured by leaf_update_prepare.  No stale rows: nothing to do, index_mask(c) is d_live.
+int refresh_index_mask(hvs_ctx* c)
+{
+    if (c->h_stale.empty()) return HVS_OK;
+    const size_t W = 2u * (((size_t)c->n_indexed + 63u) / 64u);
+    if (!c->d_ilive || 2u * W > c->ilive_cap) return fail(c, HVS_ESTATE, "internal: no room for the index-validity mask");
+    std::vector<uint32_t> w(2u * W, 0u);
+    for (size_t i = 0; i < W; ++i) {
+        const uint64_t v = (i >> 1) < c->h_live.size() ? c->h_live[i >> 1] : 0ull;
+        w[i] = w[W + i] = (uint32_t)(v >> (32u * (i & 1u)));
+    }
+    if (c->n_indexed & 63u) {  // (bits of the tail's rows in the last word: not the index's business)
+        const uint64_t keep = (1ull << (c->n_indexed & 63u)) - 1ull;
+        w[W - 2u] &= (uint32_t)keep, w[W - 1u] &= (uint32_t)(keep >> 32);
+        w[2u * W - 2u] &= (uint32_t)keep, w[2u * W - 1u] &= (uint32_t)(keep >> 32);
+    }
+    for (uint32_t id : c->h_stale) w[id >> 5] &= ~(1u << (id & 31u));
+    HVS_HIP(c, hipMemcpyAsync(c->d_ilive, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`w` goes with this scope)
+    return HVS_OK;
+}
+
 // Install `words` (ceil(n / 64) words, bits past n clear, n_live bits set: checked by the caller) as the context's mask.
 // `del_ids` (host, ids < n): the new mask is the old one less these rows -- applied on the device by hvs_k_mask_delete
 // instead of a whole-mask upload.  Tiles: rows that died are patched; a mask that revives rows rebuilds the tiles through
@@ -2527,6 +2601,7 @@ int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_l
     c->n_dead = c->n - n_live;
     c->cut_valid = false;
     c->lp_valid = false;
+    if ((rc = refresh_index_mask(c))) return rc;  // (rows are stale: live AND NOT stale follows the new mask)
     if (c->fmt.built != HVS_FMT_NONE) {
         if (revived) {
             if ((rc = build_tiles(c, c->fmt.built))) return rc;
@@ -2562,7 +2637,8 @@ int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
 // ---------------------------------------------------------------------------------------------
 // appended rows
 // ---------------------------------------------------------------------------------------------
-// n_tail above which an append re-indexes before it returns.  Default max(4096, n_indexed >> 10), derived and not yet
+// n_tail + n_stale (the limit is shared with the updated rows) above which an append or an update re-indexes
+// before it returns.  Default max(4096, n_indexed >> 10), derived and not yet
 // measured: if the tail scan evaluated pairs at the exact engine's rate, ~3.1 x 10^11 pairs/s on record, and the
 // filter engines answer a query of the flagship shape in ~310 ns, 10^4 tail rows (n_indexed = 10^7) cost ~32 ns, a tenth of
 // a query.
@@ -2627,11 +2703,12 @@ int leaf_append_prepare(hvs_ctx* c, uint32_t count)
 int leaf_reindex(hvs_ctx* c, bool force)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
-    if (!force && tail_rows(c) == 0u) return HVS_OK;
+    if (!force && tail_rows(c) == 0u && c->h_stale.empty()) return HVS_OK;
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->h_stale.clear();  // (the new index describes every row as it is now)
     // (the live-row counts run along positions: their buffers are sized by the index that goes)
     if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
@@ -2674,7 +2751,7 @@ int leaf_append_commit(hvs_ctx* c, const float* rows, uint32_t count)
     if ((rc = refresh_pad_ids(c))) return rc;
     const bool can_index = c->have_order || ((n_new >= kIndexMinRows || is_filter_engine(c->engine)) && !c->index_too_large);
     const uint32_t uncovered = c->have_order ? n_new - c->n_indexed : n_new - std::min(n_new, c->index_tried_n);
-    if (can_index && uncovered > tail_limit_of(c)) return leaf_reindex(c, true);
+    if (can_index && (uint64_t)uncovered + c->h_stale.size() > tail_limit_of(c)) return leaf_reindex(c, true);  // (the limit is shared)
     return HVS_OK;
 }
 
@@ -2693,6 +2770,100 @@ int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
         HVS_HIP(c, hipMemcpy(v, c->d_counters + 9, sizeof(v), hipMemcpyDeviceToHost));
         out->tail_pairs = v[0];
         out->tail_admitted = v[1];
+    }
+    return HVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// updated rows
+// ---------------------------------------------------------------------------------------------
+// first half of an update: every device buffer the second half writes, so that it cannot run out of memory on one GPU of
+// several.  `n_stale_new`: length of the stale list after the update.  Nothing a query sees changes.
+int leaf_update_prepare(hvs_ctx* c, uint32_t count, uint32_t n_stale_new)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);  // an earlier call's re-runs read D as it was
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    if (count > c->upd_cap) {
+        c->upd_cap = 0;
+        if ((rc = dev_alloc(c, &c->d_upd_rows, (size_t)count * HVS_DCOLS))) return rc;
+        if ((rc = dev_alloc(c, &c->d_upd_ids, (size_t)count))) return rc;
+        if ((rc = dev_alloc(c, &c->d_upd_from, (size_t)count))) return rc;
+        c->upd_cap = count;
+    }
+    if (n_stale_new <= c->h_stale.size()) return HVS_OK;  // no row becomes stale
+    // the masked kernels are about to run: the mask's own buffers (an all-live mask where none has been set)
+    if (c->h_live.empty() || !c->d_live || !c->d_pad_ids || !c->d_mask_stat) {
+        const std::vector<uint64_t> words = c->h_live.empty() ? all_live_words(c->n) : c->h_live;
+        if ((rc = leaf_apply_mask(c, words, c->n - c->n_dead, nullptr, 0u))) return rc;
+    }
+    if (n_stale_new > c->stale_cap) {  // (the new buffer first: a failure leaves the old list in place)
+        const uint32_t want = (uint32_t)std::min<uint64_t>(c->n_indexed, std::max<uint64_t>(n_stale_new, 2ull * c->stale_cap));
+        uint32_t* bigger = nullptr;
+        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), (size_t)want * sizeof(uint32_t)));
+        hipError_t e = hipSuccess;
+        if (!c->h_stale.empty()) {
+            e = hipMemcpyAsync(bigger, c->h_stale.data(), c->h_stale.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(bigger);
+            return fail(c, HVS_EHIP, std::string("hvs_update_rows: moving the stale list: ") + hipGetErrorString(e));
+        }
+        if (c->d_stale_ids) (void)hipFree(c->d_stale_ids);
+        c->d_stale_ids = bigger;
+        c->stale_cap = want;
+    }
+    const size_t words2 = 4u * (((size_t)c->n_indexed + 63u) / 64u);  // two planes
+    if (words2 > c->ilive_cap) {  // (only while no row is stale: n_indexed does not change while one is)
+        c->ilive_cap = 0;
+        if ((rc = dev_alloc(c, &c->d_ilive, words2))) return rc;
+        c->ilive_cap = (uint32_t)words2;
+    }
+    return HVS_OK;
+}
+
+// second half: the rows (one staged H2D + hvs_k_scatter_rows), the stale list and what follows from it (index-validity mask,
+// tombstones, the live-row counts along the orderings) -- and the index when tail + stale rows have outgrown the limit.
+// `uids` / `from` (nu entries): every id once, with the staged row that holds its last contents.
+int leaf_update_commit(hvs_ctx* c, const float* rows, uint32_t count, const uint32_t* uids, const uint32_t* from, uint32_t nu,
+                       const std::vector<uint32_t>& stale_new)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = upload_rows(c, c->d_upd_rows, rows, (size_t)count * HVS_DCOLS);
+    if (rc) return rc;
+    HVS_HIP(c, hipMemcpyAsync(c->d_upd_ids, uids, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(c->d_upd_from, from, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const uint64_t nelem = (uint64_t)nu * HVS_DCOLS;
+    hipLaunchKernelGGL(hvs_k_scatter_rows, dim3((uint32_t)((nelem + 255u) / 256u)), dim3(256), 0, c->stream, c->d_upd_rows, c->d_upd_ids,
+                       c->d_upd_from, nu, c->d_data);
+    HVS_HIP(c, hipGetLastError());
+    if (stale_new.size() > c->h_stale.size()) {
+        HVS_HIP(c, hipMemcpyAsync(c->d_stale_ids, stale_new.data(), stale_new.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        c->h_stale = stale_new;
+        c->lp_valid = false;  // (the counts of valid rows along the orderings: rebuilt on first use, as after a mask change)
+        if ((rc = refresh_index_mask(c))) return rc;
+        if ((rc = patch_tiles(c))) return rc;
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the sources are the caller's)
+    if (c->have_order && (uint64_t)tail_rows(c) + c->h_stale.size() > tail_limit_of(c)) return leaf_reindex(c, true);
+    return HVS_OK;
+}
+
+int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
+{
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = hvs_update_info{};
+    out->n_stale = (uint32_t)c->h_stale.size();
+    out->limit = tail_limit_of(c);
+    if (c->timing_valid) {
+        unsigned long long v[3] = {0, 0, 0};
+        HVS_HIP(c, hipMemcpy(v, c->d_counters + 11, sizeof(v), hipMemcpyDeviceToHost));
+        out->stale_pairs = v[0];
+        out->stale_admitted = v[1];
+        out->stale_survivors = v[2];
     }
     return HVS_OK;
 }
@@ -3488,6 +3659,78 @@ int hvs_append_stats(hvs_ctx* c, hvs_append_info* out)
         } else {
             agg.tail_pairs += m.tail_pairs;  // work counters of the call, summed like hvs_timing's
             agg.tail_admitted += m.tail_admitted;
+        }
+    }
+    *out = agg;
+    return HVS_OK;
+}
+
+// ---- updated rows ----------------------------------------------------------------------------
+
+uint32_t hvs_update_plan(const uint32_t* stale, uint32_t n_stale, const uint32_t* ids, uint32_t count, uint32_t n_indexed, uint32_t n_total,
+                         uint32_t* out_stale, uint8_t* out_last)
+{
+    for (uint32_t i = 0; i < count; ++i)
+        if (ids[i] >= n_total) return 0xFFFFFFFFu;
+    // occurrences ordered by (id, place in the call): the last of every run is the one that wins
+    std::vector<uint64_t> occ(count);
+    for (uint32_t i = 0; i < count; ++i) occ[i] = ((uint64_t)ids[i] << 32) | i;
+    std::sort(occ.begin(), occ.end());
+    std::vector<uint32_t> fresh;
+    for (uint32_t j = 0; j < count; ++j) {
+        const bool last = j + 1u == count || (uint32_t)(occ[j + 1u] >> 32) != (uint32_t)(occ[j] >> 32);
+        if (out_last) out_last[(uint32_t)occ[j]] = last ? 1u : 0u;
+        if (last && (uint32_t)(occ[j] >> 32) < n_indexed) fresh.push_back((uint32_t)(occ[j] >> 32));
+    }
+    std::vector<uint32_t> merged;
+    merged.reserve((size_t)n_stale + fresh.size());
+    std::set_union(stale, stale + n_stale, fresh.begin(), fresh.end(), std::back_inserter(merged));
+    if (out_stale) std::copy(merged.begin(), merged.end(), out_stale);
+    return (uint32_t)merged.size();
+}
+
+int hvs_update_rows(hvs_ctx* c, const uint32_t* ids, const float* rows, uint32_t count)
+{
+    if (!c) return HVS_EINVAL;
+    if (count == 0u) return HVS_OK;
+    if (!ids) return fail(c, HVS_EINVAL, "hvs_update_rows: ids is NULL");
+    if (!rows) return fail(c, HVS_EINVAL, "hvs_update_rows: rows is NULL");
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_update_rows: no data set loaded");
+    std::vector<uint32_t> stale_new(L->h_stale.size() + (size_t)count);
+    std::vector<uint8_t> last(count);
+    const uint32_t len = hvs_update_plan(L->h_stale.data(), (uint32_t)L->h_stale.size(), ids, count, L->n_indexed, L->n, stale_new.data(),
+                                         last.data());
+    if (len == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_update_rows: id outside [0, n)");
+    stale_new.resize(len);
+    std::vector<uint32_t> uids, from;  // every id once, with the place of its last occurrence
+    for (uint32_t i = 0; i < count; ++i)
+        if (last[i]) {
+            uids.push_back(ids[i]);
+            from.push_back(i);
+        }
+    const uint32_t nu = (uint32_t)uids.size();
+    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
+    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_update_prepare(k, count, len); });
+    if (rc) return rc;
+    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_update_commit(k, rows, count, uids.data(), from.data(), nu, stale_new); });
+}
+
+int hvs_update_stats(hvs_ctx* c, hvs_update_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_update_stats(c, out);
+    hvs_update_info agg{};
+    for (size_t r = 0; r < c->kids.size(); ++r) {
+        hvs_update_info m{};
+        const int rc = leaf_update_stats(c->kids[r], &m);
+        if (rc) return fail(c, rc, c->kids[r]->err);
+        if (r == 0u) {
+            agg = m;  // (rows and state are replicated: one GPU's view)
+        } else {
+            agg.stale_pairs += m.stale_pairs;  // work counters of the call, summed like hvs_timing's
+            agg.stale_admitted += m.stale_admitted;
+            agg.stale_survivors += m.stale_survivors;
         }
     }
     *out = agg;

@@ -2590,7 +2590,11 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 // ---------------------------------------------------------------------------------------------
 // E16: entries of the 16x16 tile format (hvs_entry16_*) instead of the 32x32 formats' (hvs_entry_*)
 // MASKED (live-row mask): a survivor whose row is dead is dropped beside the sampled-prefix test and counted in counters[8]
-// (hvs_mask_info.dead_survivors) -- the test that keeps dead rows out of every answer, whatever the tiles say
+// (hvs_mask_info.dead_survivors) -- the test that keeps dead rows out of every answer, whatever the tiles say.
+// While rows are stale (hvs_update_rows) `live` is the index-validity mask, live AND NOT stale, in the two-plane
+// form of HVS_RESCORE_TWO_MASKS, which the host announces in bit 31 of `n` (an index covers at most 2^29 rows): a dropped
+// survivor whose row is live -- dropped for staleness alone -- goes to counters[13] (hvs_update_info.stale_survivors) instead.
+#define HVS_RESCORE_TWO_MASKS 0x80000000u  // in `n`: live[W + i] (W = 2 ceil(n / 64) words) holds the row mask's bits of the indexed rows
 template <bool E16, bool MASKED>
 __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const float* __restrict__ D, uint32_t n, uint32_t sn, const float* __restrict__ Q,
                                                      HvsBatch B, const uint32_t* __restrict__ perm_ct,
@@ -2602,6 +2606,13 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
     __shared__ float sq[HVS_GROUP][HVS_NDIM];
     __shared__ uint64_t slist[HVS_RESCORE_WAVES][64];  // wave-private (slot << 32 | position) pairs of one round
     const uint32_t g = blockIdx.y;
+    const uint32_t* __restrict__ rowmask = nullptr;  // (MASKED, two masks) the row mask's plane behind the validity mask
+    if constexpr (MASKED) {
+        if (n & HVS_RESCORE_TWO_MASKS) {
+            n &= ~HVS_RESCORE_TWO_MASKS;
+            rowmask = live + 2u * ((n + 63u) / 64u);
+        }
+    }
     uint32_t np = B.paircnt[g];
     // a group whose entry list overflowed holds unwritten entries past the failed flush: none of
     // them are used, all of its queries are re-run by the exact engine
@@ -2623,6 +2634,7 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
     uint64_t* list = slist[w];
     uint32_t npairs = 0;  // wave-uniform
     uint32_t ndead = 0;   // (MASKED) per lane: pairs dropped because the row is dead
+    uint32_t nstale = 0;  // (MASKED) ... because its index entry is stale and nothing else
     auto emask = [](uint64_t e) -> uint32_t { return E16 ? hvs_entry16_mask(e) : hvs_entry_mask(e); };
     auto epos = [](uint64_t e, uint32_t r) -> uint32_t { return E16 ? hvs_entry16_pos(e, r) : hvs_entry_pos(e, r); };
 
@@ -2672,7 +2684,9 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
                 ok[u] = pi < cnt && id[u] < sn;
                 if constexpr (MASKED) {
                     const bool dead = pi < cnt && !hvs_row_live(live, id[u]);
-                    ndead += (dead && t4 == 0u) ? 1u : 0u;
+                    const bool stale = dead && rowmask && hvs_row_live(rowmask, id[u]);  // (rare: tombstones keep these rows out)
+                    ndead += (dead && !stale && t4 == 0u) ? 1u : 0u;
+                    nstale += (stale && t4 == 0u) ? 1u : 0u;
                     ok[u] = ok[u] && !dead;
                 }
             }
@@ -2772,6 +2786,9 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ndead += __shfl_xor(ndead, o);
         if (lane == 0u && ndead) atomicAdd(&counters[8], (unsigned long long)ndead);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nstale += __shfl_xor(nstale, o);
+        if (lane == 0u && nstale) atomicAdd(&counters[13], (unsigned long long)nstale);
     }
 }
 
@@ -3094,17 +3111,20 @@ struct HvsTailOut {
     uint32_t slot_lo, slot_hi;  // slots that take keys
 };
 
-// (__launch_bounds__' second argument is the least number of WAVES per SIMD; a workgroup of 256 threads is four waves, one
-// per SIMD, so here it is also workgroups per CU -- a change of the block size changes the register budget with it.  Two,
-// where hvs_k_scan_exact_lds has three: beside the exact engine's row loop a lane keeps its segment's place, room and fill,
-// which at three -- 168 registers -- spilled 4 to 8 of them; the kernel runs once per batch over a few thousand rows)
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
-__global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restrict__ D, const float* __restrict__ Q,
-                                                                         HvsBatch B, HvsTailOut O, uint32_t tail_lo, uint32_t tail_hi,
-                                                                         unsigned long long* __restrict__ counters, int count,
-                                                                         const uint32_t* __restrict__ live)
+// What the tail scan and the stale scan (hvs_k_scan_stale, below) share: the whole lane-per-slot scan.  LIST = false: the
+// rows are ids [lo, hi) themselves; LIST = true: the rows are ids[lo .. hi), an ascending id list (the rows are scattered
+// over D).  CNT: the counter slot of the pairs evaluated, CNT + 1 that of the keys admitted.
+// LIST staging is the 16-row gather of hvs_k_seed_exact: the workgroup gathers a block of HVS_LDS_ROWS rows by id, one HBM
+// round trip per block -- the ids of a block are fetched one block earlier than its rows, so the dependent pair id -> row is
+// never paid in sequence inside the loop --, double-buffered like the contiguous form, the ids kept in LDS beside the rows.
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool LIST, int CNT>
+__device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict__ D, const float* __restrict__ Q, const HvsBatch B,
+                                                         const HvsTailOut O, const uint32_t* __restrict__ ids, uint32_t tail_lo,
+                                                         uint32_t tail_hi, unsigned long long* __restrict__ counters, int count,
+                                                         const uint32_t* __restrict__ live)
 {
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
+    __shared__ uint32_t sid[LIST ? 2 : 1][LIST ? HVS_LDS_ROWS : 1];  // (LIST) ids of the staged rows
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t slot = w * 64u + lane;
@@ -3138,6 +3158,15 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
     // staging: item e = (row r, piece c): c < 25 -> floats 2+4c..5+4c of the row, c == 25 -> (C, T, 0, 0)
     constexpr uint32_t kItems = HVS_LDS_ROWS * 26u;
     float4 stg[(kItems + 255u) / 256u];
+    uint32_t rid[(kItems + 255u) / 256u];  // (LIST) id of the row of this thread's items in the block to be loaded next
+    auto load_ids = [&](uint32_t j0) {
+#pragma unroll
+        for (uint32_t k = 0; k < (kItems + 255u) / 256u; ++k) {
+            const uint32_t e = threadIdx.x + 256u * k;
+            const uint32_t r = e / 26u;
+            rid[k] = (e < kItems && r < tail_hi - j0) ? ids[j0 + r] : 0xFFFFFFFFu;
+        }
+    };
     auto load_block = [&](uint32_t j0) {
 #pragma unroll
         for (uint32_t k = 0; k < (kItems + 255u) / 256u; ++k) {
@@ -3145,14 +3174,14 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
             const uint32_t r = e / 26u, c = e % 26u;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (e < kItems && r < tail_hi - j0) {
-                const float* __restrict__ src = D + (size_t)(j0 + r) * HVS_DCOLS;
+                const float* __restrict__ src = D + (size_t)(LIST ? rid[k] : j0 + r) * HVS_DCOLS;
                 if (c < 25u) {
                     const float2 a = *reinterpret_cast<const float2*>(src + 2 + 4 * c);
                     const float2 b = *reinterpret_cast<const float2*>(src + 4 + 4 * c);
                     v = make_float4(a.x, a.y, b.x, b.y);
                 } else {
                     const float2 a = *reinterpret_cast<const float2*>(src);
-                    v = make_float4(a.x, a.y, 0.f, 0.f);
+                    v = make_float4(a.x, a.y, 0.f, LIST ? __uint_as_float(rid[k]) : 0.f);  // (LIST: the id rides along to LDS)
                 }
             }
             stg[k] = v;
@@ -3163,22 +3192,34 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
         for (uint32_t k = 0; k < (kItems + 255u) / 256u; ++k) {
             const uint32_t e = threadIdx.x + 256u * k;
             if (e < kItems) srow[buf][(e / 26u) * (HVS_LDS_ROW_F / 4) + (e % 26u)] = stg[k];
+            if constexpr (LIST) {
+                if (e < kItems && e % 26u == 25u) sid[buf][e / 26u] = __float_as_uint(stg[k].w);
+            }
         }
     };
 
     if (tail_lo >= tail_hi) return;  // uniform over the grid
+    if constexpr (LIST) load_ids(tail_lo);
     load_block(tail_lo);
+    if constexpr (LIST) {
+        if (tail_hi - tail_lo > HVS_LDS_ROWS) load_ids(tail_lo + HVS_LDS_ROWS);
+    }
     store_block(0u);
     __syncthreads();
     uint32_t buf = 0;
     for (uint32_t j0 = tail_lo; j0 < tail_hi; j0 += HVS_LDS_ROWS) {
         const bool more = tail_hi - j0 > HVS_LDS_ROWS;  // (no j0 + HVS_LDS_ROWS: ids run up to 2^32 - 1)
         if (more) load_block(j0 + HVS_LDS_ROWS);
+        if constexpr (LIST) {  // (the ids of the block after that: in flight under this block's rows)
+            if (more && tail_hi - j0 > 2u * HVS_LDS_ROWS) load_ids(j0 + 2u * HVS_LDS_ROWS);
+        }
         if (wave_active) {
             const uint32_t nrow = (tail_hi - j0) < HVS_LDS_ROWS ? (tail_hi - j0) : HVS_LDS_ROWS;
             for (uint32_t r = 0; r < nrow; ++r) {
+                uint32_t id = j0 + r;
+                if constexpr (LIST) id = sid[buf][r];
                 if constexpr (MASKED) {
-                    if (!hvs_row_live(live, j0 + r)) continue;  // (wave-uniform)
+                    if (!hvs_row_live(live, id)) continue;  // (wave-uniform)
                 }
                 nrows += 1u;
                 const float4* rowp = &srow[buf][r * (HVS_LDS_ROW_F / 4)];
@@ -3226,7 +3267,7 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
                     want = want && takes && !(dist > tau);  // (against the threshold the cut has just set)
                 }
                 if (want) {
-                    myseg[cnt] = hvs_make_key(dist, j0 + r);
+                    myseg[cnt] = hvs_make_key(dist, id);
                     ++cnt;
                     ++nadm;
                 }
@@ -3243,8 +3284,39 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
         for (int o = 32; o > 0; o >>= 1) nadm += __shfl_xor(nadm, o);
         if (lane == 0u && hm != 0ull) {
             atomicAdd(&counters[0], (unsigned long long)npass);
-            atomicAdd(&counters[9], (unsigned long long)nrows * (unsigned long long)__popcll(hm));
-            if (nadm) atomicAdd(&counters[10], (unsigned long long)nadm);
+            atomicAdd(&counters[CNT], (unsigned long long)nrows * (unsigned long long)__popcll(hm));
+            if (nadm) atomicAdd(&counters[CNT + 1], (unsigned long long)nadm);
         }
     }
+}
+
+// (__launch_bounds__' second argument is the least number of WAVES per SIMD; a workgroup of 256 threads is four waves, one
+// per SIMD, so here it is also workgroups per CU -- a change of the block size changes the register budget with it.  Two,
+// where hvs_k_scan_exact_lds has three: beside the exact engine's row loop a lane keeps its segment's place, room and fill,
+// which at three -- 168 registers -- spilled 4 to 8 of them; the kernel runs once per batch over a few thousand rows)
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
+__global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restrict__ D, const float* __restrict__ Q,
+                                                                         HvsBatch B, HvsTailOut O, uint32_t tail_lo, uint32_t tail_hi,
+                                                                         unsigned long long* __restrict__ counters, int count,
+                                                                         const uint32_t* __restrict__ live)
+{
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, 9>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live);
+}
+
+// ---------------------------------------------------------------------------------------------
+// hvs_k_scan_stale -- indexed rows whose index entry describes old contents (hvs_update_rows): the exact-order
+// scan of the rows stale_ids[0 .. m) -- the ascending list's prefix of ids below the sampled prefix's end (under a mask: the
+// cut) -- for a batch in slot layout.  Everything but the staging is hvs_k_scan_tail's: admission, segments, cuts, failure
+// flags, HvsTailOut, and it is launched right behind it, so that a slot's list takes tail keys, then stale keys (a lane's
+// segment starts at the list's fill on entry).  The key carries the row's own id; MASKED tests the row mask (d_live: a stale
+// row is dead to the index only) on that id.
+// counters (`count` != 0): [0] passing pairs, [11] pairs evaluated, [12] keys admitted.
+// ---------------------------------------------------------------------------------------------
+template <bool SCALAR_ORDER, int CAP, bool MASKED>
+__global__ __launch_bounds__(256, 2) void hvs_k_scan_stale(const float* __restrict__ D, const float* __restrict__ Q, HvsBatch B,
+                                                           HvsTailOut O, const uint32_t* __restrict__ stale_ids, uint32_t m,
+                                                           unsigned long long* __restrict__ counters, int count,
+                                                           const uint32_t* __restrict__ live)
+{
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, 11>(D, Q, B, O, stale_ids, 0u, m, counters, count, live);
 }

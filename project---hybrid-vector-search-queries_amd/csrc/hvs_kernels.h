@@ -26,6 +26,17 @@ __global__ void hvs_k_mask_delete(const uint32_t* __restrict__ ids, uint32_t cou
     atomicAnd(&live[id >> 5], ~(1u << (id & 31u)));
 }
 
+// hvs_update_rows: rows src[from[j]] of a staged block over the rows D[ids[j]] (ids < n, checked by the host; every id once:
+// the host names only the last occurrence of a duplicate).  One thread per float.
+__global__ void hvs_k_scatter_rows(const float* __restrict__ src, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ from,
+                                   uint32_t count, float* __restrict__ D)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (uint64_t)count * HVS_DCOLS) return;
+    const uint32_t j = (uint32_t)(e / HVS_DCOLS), col = (uint32_t)(e - (uint64_t)j * HVS_DCOLS);
+    D[(size_t)ids[j] * HVS_DCOLS + col] = src[(size_t)from[j] * HVS_DCOLS + col];
+}
+
 // ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------

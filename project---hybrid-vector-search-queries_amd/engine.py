@@ -54,6 +54,15 @@ class AppendInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class UpdateInfo(C.Structure):
+    """hvs_update_info (include/hvs.h)."""
+    _fields_ = [("n_stale", C.c_uint32), ("limit", C.c_uint32), ("stale_pairs", C.c_uint64), ("stale_admitted", C.c_uint64),
+                ("stale_survivors", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -184,6 +193,9 @@ def library():
         "hvs_set_tail_limit": (C.c_int, [vp, C.c_uint32]),
         "hvs_append_stats": (C.c_int, [vp, C.POINTER(AppendInfo)]),
         "hvs_append_plan": (None, [C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
+        "hvs_update_rows": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
+        "hvs_update_stats": (C.c_int, [vp, C.POINTER(UpdateInfo)]),
+        "hvs_update_plan": (C.c_uint32, [_u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.POINTER(C.c_uint8)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -233,6 +245,23 @@ def append_plan(n_indexed, n_total, sample_proportion):
     sn, lo, hi = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     library().hvs_append_plan(int(n_indexed), int(n_total), float(sample_proportion), C.byref(sn), C.byref(lo), C.byref(hi))
     return int(sn.value), int(lo.value), int(hi.value)
+
+
+def update_plan(stale, ids, n_indexed, n_total, want_last=True):
+    """hvs_update_plan: fold one call's `ids` into the ascending stale list `stale`.  Returns (new stale list, last) with
+    last[i] = True where occurrence i is the last of its id (None when want_last is False), or (None, None) when an id is
+    >= n_total (nothing written)."""
+    stale = np.ascontiguousarray(stale, np.uint32).ravel()
+    ids = np.ascontiguousarray(ids, np.uint32).ravel()
+    out = np.full(stale.size + ids.size + 1, 0xFFFFFFFF, np.uint32)
+    last = np.full(ids.size + 1, 0xFF, np.uint8)
+    m = library().hvs_update_plan(_up(stale), stale.size, _up(ids), ids.size, int(n_indexed), int(n_total), _up(out),
+                                  last.ctypes.data_as(C.POINTER(C.c_uint8)) if want_last else None)
+    if m == 0xFFFFFFFF:
+        if (out != 0xFFFFFFFF).any() or (last != 0xFF).any():
+            raise HvsError(-1, "hvs_update_plan wrote its outputs although it refused the ids")
+        return None, None
+    return out[:m].copy(), (last[:ids.size].astype(bool) if want_last else None)
 
 
 class Engine:
@@ -380,6 +409,20 @@ class Engine:
         a = AppendInfo()
         self._ck(self._lib.hvs_append_stats(self._h, C.byref(a)))
         return a
+
+    # --- row update (include/hvs.h "row update in place")
+    def update_rows(self, ids, rows):
+        """Replace rows `ids` (uint32) by `rows` (count x 102 float32) in place: searchable by the next call, ids kept."""
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != DCOLS or rows.shape[0] != ids.size:
+            raise HvsError(-1, "update rows must be len(ids) x 102 float32")
+        self._ck(self._lib.hvs_update_rows(self._h, _up(ids), _fp(rows), ids.size))
+
+    def update_stats(self):
+        u = UpdateInfo()
+        self._ck(self._lib.hvs_update_stats(self._h, C.byref(u)))
+        return u
 
     # --- the vec_query seam
     def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None):
