@@ -328,6 +328,48 @@ int hvs_update_stats(hvs_ctx *ctx, hvs_update_info *out);
 uint32_t hvs_update_plan(const uint32_t *stale, uint32_t n_stale, const uint32_t *ids, uint32_t count,
                          uint32_t n_indexed, uint32_t n_total, uint32_t *out_stale, uint8_t *out_last);
 
+/* ---- row compaction: dead rows dropped from D, live rows renumbered, one index over them ------ */
+
+/*
+ * Let `live` be the ascending list of live ids and n_live its length.  After hvs_compact(ctx, map) returns HVS_OK the context
+ * behaves, in every later call on every engine, as a fresh context would after hvs_load_data of the current rows D[live] in
+ * that order under the same settings (engine, k, distance order, padding, tail limit) -- "current" meaning the contents
+ * hvs_update_rows left, appended rows included.  So row live[j] now has id j, out_dists are bit-equal to the fresh load's
+ * under the same (dist asc, id asc) tie rule, hvs_timing.pairs is the same, hvs_num_rows is n_live, sn and the padding ids
+ * are taken over the new n; the mask is "all live" (n_dead = 0: every call runs the unmasked kernels again, hvs_get_row_mask
+ * returns ceil(n_live / 64) words of ones); the stale set and the tail are empty under one index over all rows; and
+ * hvs_delete_rows, hvs_update_rows, hvs_append_rows (first new id = n_live) and hvs_download_data speak the new ids at once.
+ * map[j] = live[j] is written before anything on the device changes.  Results of earlier queries hold old ids and are
+ * dropped as hvs_set_k drops them; resident queries stay.  An earlier call's pending re-runs are resolved first, under the
+ * old mask.  The index build counts in hvs_append_info.reindexes / reindex_ms; hvs_timing.load_ms stays the load's.
+ * No dead row: HVS_OK and nothing changes -- tail and stale rows stay, no re-index, the map is the identity, `compactions`
+ * is not incremented.  Nothing compacts on its own: ids belong to the caller.
+ * The rows move in place (row live[j] to place j <= live[j], rows below the first dead id untouched) through a bounce buffer
+ * of one chunk of HVS_COMPACT_CHUNK source rows (default 65536), so the call needs no second copy of D.  The capacity of D
+ * (hvs_reserve_rows) is kept: the next appends need no growth.  hvs_trim_rows gives it back: D is re-allocated to exactly n
+ * rows (no-op when it has no spare room; needs n rows of spare room while it runs; HVS_ENOMEM: the context is as it was).
+ * No data loaded: HVS_ESTATE; no room for the scratch buffers: HVS_ENOMEM; in both cases the context, D, the mask and the
+ * index are as they were.  Any other failure is reported as hvs_append_rows reports it: load the data again.  Multi-GPU
+ * contexts are accepted: every GPU compacts its replica, and room is secured on every GPU before any GPU changes.  The
+ * D-sharded mode knows nothing of compaction.
+ */
+typedef struct hvs_compact_info {
+    uint32_t compactions;   /* since the last load                                            */
+    uint32_t n_before, n_after; /* last compaction                                            */
+    uint32_t first_moved;   /* last: smallest old id whose row changed place (= first dead id) */
+    uint32_t chunks;        /* last: gather launches                                          */
+    uint64_t rows_moved;    /* last: live rows with old id > first_moved                      */
+    double   move_ms;       /* last: device time of the row move (HIP events), index build apart */
+} hvs_compact_info;
+int  hvs_compact(hvs_ctx *ctx, uint32_t *new_to_old /* host, n_live entries, may be NULL */);
+/* Multi-GPU context: one GPU's figures. */
+int  hvs_compact_stats(hvs_ctx *ctx, hvs_compact_info *out);
+int  hvs_trim_rows(hvs_ctx *ctx);
+/* The host arithmetic (no GPU, no context; live_bits NULL = all live; any output may be NULL): n_live = popcount,
+ * first_dead = the first clear bit (n when there is none), new_to_old = the ascending live ids. */
+void hvs_compact_plan(const uint64_t *live_bits, uint32_t n, uint32_t *n_live, uint32_t *first_dead,
+                      uint32_t *new_to_old /* n_live entries, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

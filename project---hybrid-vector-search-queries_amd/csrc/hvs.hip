@@ -182,6 +182,12 @@ struct hvs_ctx : HvsLane {
     float* d_upd_rows = nullptr;    // staging of the running hvs_update_rows: its rows, their ids, the staged row of each id
     uint32_t *d_upd_ids = nullptr, *d_upd_from = nullptr;
     uint32_t upd_cap = 0;
+    // row compaction (hvs_compact): figures of the last one, and the scratch of the running one (bounce buffer of
+    // one chunk, rank table; allocated by leaf_compact_prepare, freed when the call ends) / of the running hvs_trim_rows
+    hvs_compact_info cstat{};
+    uint2* d_cmp_bounce = nullptr;
+    uint32_t* d_cmp_rank = nullptr;
+    float* d_trim = nullptr;
 
     // resident queries + results
     float* d_q = nullptr;
@@ -2010,6 +2016,7 @@ int begin_data(hvs_ctx* c, uint32_t n)
     c->h_stale.clear();  // (no row is stale; the device buffers stay for the next update)
     c->reindex_ms = 0.0;
     c->index_tried_n = 0;
+    c->cstat = hvs_compact_info{};
     // a new data set starts with every row live
     c->h_live.clear();
     c->n_dead = 0;
@@ -2865,6 +2872,142 @@ int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
         out->stale_admitted = v[1];
         out->stale_survivors = v[2];
     }
+    return HVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// row compaction
+// ---------------------------------------------------------------------------------------------
+// source rows per gather launch and rows of the bounce buffer; HVS_COMPACT_CHUNK overrides, read per call (any value >= 1)
+uint32_t compact_chunk() { return env_u32("HVS_COMPACT_CHUNK", 65536u, 1u, 0xFFFFFFFFu); }
+
+void compact_free_scratch(hvs_ctx* c)
+{
+    (void)hipSetDevice(c->device);
+    if (c->d_cmp_bounce) (void)hipFree(c->d_cmp_bounce);
+    if (c->d_cmp_rank) (void)hipFree(c->d_cmp_rank);
+    if (c->d_trim) (void)hipFree(c->d_trim);
+    c->d_cmp_bounce = nullptr;
+    c->d_cmp_rank = nullptr;
+    c->d_trim = nullptr;
+}
+
+// first half of a compaction: the earlier call's re-runs (they belong to the mask and the ids they were asked under) and the
+// two scratch buffers, so that the second half cannot run out of memory on one GPU of several.  Nothing a query sees changes.
+int leaf_compact_prepare(hvs_ctx* c, uint32_t first_dead, uint32_t chunk)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    if (!c->d_live) return fail(c, HVS_ESTATE, "internal: rows are dead and the device mask is missing");
+    const uint32_t bounce_rows = std::min(chunk, c->n - first_dead);
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cmp_bounce), (size_t)bounce_rows * HVS_DCOLS * sizeof(float)));
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cmp_rank), (((size_t)c->n + 31u) / 32u) * sizeof(uint32_t)));
+    return HVS_OK;
+}
+
+// second half: the move, chunk by chunk on the context's stream (hvs_k_compact_gather into the bounce buffer, then a
+// device-to-device copy to the rows' place: destination <= source, so a chunk's copy may overwrite its own source rows,
+// which the gather has read, and never a later chunk's), then the state of a fresh load of the live rows and its index.
+// `rank` (host): live rows in front of every 32-row mask word, ceil(n / 32) entries.
+int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t n_live, uint32_t first_dead, uint32_t chunk)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    const uint32_t n = c->n;
+    auto live_before = [&](uint32_t id) -> uint32_t {  // live rows with an id below `id` (id <= n)
+        if (id == n) return n_live;
+        const uint64_t word = c->h_live[id >> 6] >> (32u * ((id >> 5) & 1u));
+        return rank[id >> 5] + (uint32_t)__builtin_popcount((uint32_t)word & ((1u << (id & 31u)) - 1u));
+    };
+    HVS_HIP(c, hipMemcpyAsync(c->d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // HVS_TRACE: the gathers' and the copies' device time apart (an event between the two of every chunk)
+    std::vector<hipEvent_t> ev_mid;
+    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    uint32_t chunks = 0;
+    for (uint64_t a64 = first_dead; a64 < n; a64 += chunk, ++chunks) {
+        const uint32_t a = (uint32_t)a64, b = (uint32_t)std::min<uint64_t>(n, a64 + chunk);
+        const uint32_t ra = live_before(a), rb = live_before(b);
+        const uint32_t words = ((b - 1u) >> 5) - (a >> 5) + 1u;
+        if (kTrace) {
+            hipEvent_t e[2] = {nullptr, nullptr};
+            if (hipEventCreate(&e[0]) == hipSuccess && hipEventCreate(&e[1]) == hipSuccess) (void)hipEventRecord(e[0], c->stream);
+            ev_mid.push_back(e[0]);
+            ev_mid.push_back(e[1]);
+        }
+        hipLaunchKernelGGL(hvs_k_compact_gather, dim3(hvs_ceil_div(words, 4u)), dim3(256), 0, c->stream,
+                           reinterpret_cast<const uint2*>(c->d_data), c->d_live, c->d_cmp_rank, a, b, ra, c->d_cmp_bounce);
+        HVS_HIP(c, hipGetLastError());
+        if (kTrace && ev_mid.back()) (void)hipEventRecord(ev_mid.back(), c->stream);
+        if (rb > ra)
+            HVS_HIP(c, hipMemcpyAsync(c->d_data + (size_t)ra * HVS_DCOLS, c->d_cmp_bounce, (size_t)(rb - ra) * HVS_DCOLS * sizeof(float),
+                                      hipMemcpyDeviceToDevice, c->stream));
+    }
+    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
+    if (kTrace) {
+        double gather_ms = 0.0;
+        for (size_t i = 0; i + 1u < ev_mid.size(); i += 2u) {
+            float g = 0.f;
+            if (ev_mid[i] && ev_mid[i + 1u] && hipEventElapsedTime(&g, ev_mid[i], ev_mid[i + 1u]) == hipSuccess) gather_ms += g;
+        }
+        for (hipEvent_t e : ev_mid)
+            if (e) (void)hipEventDestroy(e);
+        std::fprintf(stderr, "[hvs trace] hvs_compact n=%u live=%u chunks=%u: move %.3f ms, gathers %.3f ms, copies %.3f ms\n", n, n_live, chunks,
+                     ms, gather_ms, ms - gather_ms);
+    }
+    compact_free_scratch(c);
+    c->cstat.compactions += 1u;
+    c->cstat.n_before = n;
+    c->cstat.n_after = n_live;
+    c->cstat.first_moved = first_dead;
+    c->cstat.chunks = chunks;
+    c->cstat.rows_moved = (uint64_t)n_live - first_dead;  // (every id below the first dead one is live)
+    c->cstat.move_ms = ms;
+    // what a fresh load of these rows leaves: every row live and no mask set, no stale row, no earlier result
+    c->n = n_live;
+    c->h_live.clear();
+    c->n_dead = 0;
+    c->live_cap = 0;
+    int rc = dev_alloc(c, &c->d_live, (size_t)0);  // (as after a load: the next mask call allocates it, all live, for the new n)
+    if (rc) return rc;
+    if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    if ((rc = refresh_pad_ids(c))) return rc;  // (no mask: nothing reads the table; the next mask call fills it)
+    c->h_stale.clear();
+    c->index_tried_n = 0;
+    c->cut_valid = false;
+    c->lp_valid = false;
+    c->timing_valid = false;
+    // one index over all rows -- or none, by the rule of a load (fewer than 4096 rows, or no room for one)
+    if (c->n >= kIndexMinRows || is_filter_engine(c->engine)) return leaf_reindex(c, true);
+    free_index(c);
+    return HVS_OK;
+}
+
+// hvs_trim_rows, first half: the smaller buffer; second half: the rows, and the swap
+int leaf_trim_prepare(hvs_ctx* c)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);  // an earlier call's re-runs read D
+    if (rc) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->n_cap == c->n) return HVS_OK;
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_trim), (size_t)c->n * HVS_DCOLS * sizeof(float)));
+    return HVS_OK;
+}
+
+int leaf_trim_commit(hvs_ctx* c)
+{
+    if (!c->d_trim) return HVS_OK;
+    HVS_HIP(c, hipSetDevice(c->device));
+    HVS_HIP(c, hipMemcpyAsync(c->d_trim, c->d_data, (size_t)c->n * HVS_DCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_data);
+    c->d_data = c->d_trim;
+    c->d_trim = nullptr;
+    c->n_cap = c->n;
     return HVS_OK;
 }
 
@@ -3735,6 +3878,77 @@ int hvs_update_stats(hvs_ctx* c, hvs_update_info* out)
     }
     *out = agg;
     return HVS_OK;
+}
+
+// ---- row compaction --------------------------------------------------------------------------
+
+void hvs_compact_plan(const uint64_t* live_bits, uint32_t n, uint32_t* n_live, uint32_t* first_dead, uint32_t* new_to_old)
+{
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) / 64u);
+    uint32_t nl = 0, fd = n;
+    for (uint32_t w = 0; w < words; ++w) {
+        const uint32_t in_word = w == words - 1u && (n & 63u) ? (n & 63u) : 64u;
+        const uint64_t valid = in_word == 64u ? ~0ull : (1ull << in_word) - 1ull;
+        uint64_t v = (live_bits ? live_bits[w] : ~0ull) & valid;
+        if (fd == n && v != valid) fd = w * 64u + (uint32_t)__builtin_ctzll(~v);
+        if (new_to_old) {
+            for (uint64_t t = v; t; t &= t - 1ull) new_to_old[nl++] = w * 64u + (uint32_t)__builtin_ctzll(t);
+        } else {
+            nl += (uint32_t)__builtin_popcountll(v);
+        }
+    }
+    if (n_live) *n_live = nl;
+    if (first_dead) *first_dead = fd;
+}
+
+int hvs_compact(hvs_ctx* c, uint32_t* new_to_old)
+{
+    if (!c) return HVS_EINVAL;
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_compact: no data set loaded");
+    const uint32_t n = L->n;
+    uint32_t n_live = 0, first_dead = 0;
+    hvs_compact_plan(L->h_live.empty() ? nullptr : L->h_live.data(), n, &n_live, &first_dead, new_to_old);
+    if (n_live == n) return HVS_OK;  // no dead row: nothing changes
+    // live rows in front of every 32-row word of the mask
+    std::vector<uint32_t> rank(((size_t)n + 31u) / 32u);
+    uint32_t seen = 0;
+    for (size_t w = 0; w < rank.size(); ++w) {
+        rank[w] = seen;
+        seen += (uint32_t)__builtin_popcount((uint32_t)(L->h_live[w >> 1] >> (32u * (w & 1u))));
+    }
+    const uint32_t chunk = compact_chunk();
+    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
+    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_compact_prepare(k, first_dead, chunk); });
+    if (!rc) rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_compact_commit(k, rank, n_live, first_dead, chunk); });
+    (void)on_every_leaf(c, [&](hvs_ctx* k) {
+        compact_free_scratch(k);
+        return HVS_OK;
+    });
+    if (rc) (void)hipGetLastError();
+    return rc;
+}
+
+int hvs_compact_stats(hvs_ctx* c, hvs_compact_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    *out = mask_leaf(c)->cstat;
+    return HVS_OK;
+}
+
+int hvs_trim_rows(hvs_ctx* c)
+{
+    if (!c) return HVS_EINVAL;
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_trim_rows: no data set loaded");
+    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_trim_prepare(k); });
+    if (!rc) rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_trim_commit(k); });
+    (void)on_every_leaf(c, [&](hvs_ctx* k) {
+        compact_free_scratch(k);
+        return HVS_OK;
+    });
+    if (rc) (void)hipGetLastError();
+    return rc;
 }
 
 }  // extern "C"

@@ -37,6 +37,58 @@ __global__ void hvs_k_scatter_rows(const float* __restrict__ src, const uint32_t
     D[(size_t)ids[j] * HVS_DCOLS + col] = src[(size_t)from[j] * HVS_DCOLS + col];
 }
 
+// hvs_compact: the live rows among the source rows [a, b) of one chunk, packed in id order into `bounce`
+// (the host then copies them device-to-device to their place in D).  Not in place on purpose: row live[j] goes to place
+// j <= live[j], so a chunk's destination range may overlap its OWN source range (whenever few rows before it are dead) and a
+// single kernel moving rows inside D would race with itself; it never reaches a later chunk's source rows.
+// One wave per 32-row mask word: the word's rows are 32 x 51 = 1632 consecutive 8-byte pieces of D (rows are 408 B, 8-byte
+// aligned), read 64 pieces per instruction in two rounds of 13 loads in flight; a lane whose piece belongs to a dead row
+// (or to a row outside [a, b)) sits out.  A live row's place: `rank[w]` = live rows in front of word w (host-built), plus
+// the popcount of the word's bits below the row, minus rank_a = live rows in front of a.  `live`: bits past n are clear
+// and b <= n (host), so nothing outside D is read; at most b - a rows of `bounce` are written.
+#define HVS_ROW_U2 (HVS_DCOLS / 2u)  // 8-byte pieces per row
+__global__ __launch_bounds__(256) void hvs_k_compact_gather(const uint2* __restrict__ D, const uint32_t* __restrict__ live,
+                                                           const uint32_t* __restrict__ rank, uint32_t a, uint32_t b, uint32_t rank_a,
+                                                           uint2* __restrict__ bounce)
+{
+    static_assert(HVS_DCOLS % 2u == 0u, "rows are moved in 8-byte pieces");
+    constexpr uint32_t E = 32u * HVS_ROW_U2, HALF = (E + 127u) / 128u;  // pieces per word; loads per round (2 rounds x 64 lanes)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w_first = a >> 5, w_last = (b - 1u) >> 5;
+    const uint32_t w = w_first + blockIdx.x * 4u + (threadIdx.x >> 6);  // (wave-uniform)
+    if (w > w_last) return;
+    const uint32_t bits = live[w];
+    uint32_t m = bits;  // the rows of this word the chunk moves
+    if (w == w_first) m &= ~0u << (a & 31u);
+    if (w == w_last && (b & 31u)) m &= (1u << (b & 31u)) - 1u;
+    if (m == 0u) return;
+    const uint32_t base = rank[w] - rank_a;  // (may wrap for the chunk's first word: the sum below does not)
+    const uint2* __restrict__ src = D + (size_t)w * E;
+#pragma unroll
+    for (uint32_t h = 0; h < 2u; ++h) {
+        uint2 v[HALF];
+        uint32_t ok = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < HALF; ++i) {
+            const uint32_t e = (h * HALF + i) * 64u + lane;
+            const uint32_t r = e < E ? e / HVS_ROW_U2 : 0u;
+            if (e < E && ((m >> r) & 1u)) {
+                v[i] = src[e];
+                ok |= 1u << i;
+            }
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < HALF; ++i) {
+            const uint32_t e = (h * HALF + i) * 64u + lane;
+            const uint32_t r = e < E ? e / HVS_ROW_U2 : 0u;
+            if ((ok >> i) & 1u) {
+                const uint32_t row = base + (uint32_t)__popc(bits & ((1u << r) - 1u));
+                bounce[(size_t)row * HVS_ROW_U2 + (e - r * HVS_ROW_U2)] = v[i];
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------

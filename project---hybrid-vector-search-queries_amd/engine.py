@@ -63,6 +63,15 @@ class UpdateInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CompactInfo(C.Structure):
+    """hvs_compact_info (include/hvs.h)."""
+    _fields_ = [("compactions", C.c_uint32), ("n_before", C.c_uint32), ("n_after", C.c_uint32), ("first_moved", C.c_uint32),
+                ("chunks", C.c_uint32), ("rows_moved", C.c_uint64), ("move_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -196,6 +205,10 @@ def library():
         "hvs_update_rows": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
         "hvs_update_stats": (C.c_int, [vp, C.POINTER(UpdateInfo)]),
         "hvs_update_plan": (C.c_uint32, [_u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.POINTER(C.c_uint8)]),
+        "hvs_compact": (C.c_int, [vp, _u32p]),
+        "hvs_compact_stats": (C.c_int, [vp, C.POINTER(CompactInfo)]),
+        "hvs_trim_rows": (C.c_int, [vp]),
+        "hvs_compact_plan": (None, [_u64p, C.c_uint32, _u32p, _u32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -262,6 +275,23 @@ def update_plan(stale, ids, n_indexed, n_total, want_last=True):
             raise HvsError(-1, "hvs_update_plan wrote its outputs although it refused the ids")
         return None, None
     return out[:m].copy(), (last[:ids.size].astype(bool) if want_last else None)
+
+
+def compact_plan(live, want_map=True):
+    """hvs_compact_plan on a bool array (or None = all live, then `live` must be the row count): (n_live, first_dead,
+    new_to_old) -- new_to_old is None when want_map is False."""
+    if isinstance(live, (int, np.integer)):
+        n, words = int(live), None
+    else:
+        live = np.asarray(live, dtype=bool).ravel()
+        n, words = live.size, pack_row_mask(live)
+    n_live, first_dead = C.c_uint32(0), C.c_uint32(0)
+    out = np.full(n + 1, 0xFFFFFFFF, np.uint32) if want_map else None
+    library().hvs_compact_plan(words.ctypes.data_as(_u64p) if words is not None else None, n, C.byref(n_live), C.byref(first_dead),
+                               _up(out) if want_map else None)
+    if want_map and (out[int(n_live.value):] != 0xFFFFFFFF).any():
+        raise HvsError(-1, "hvs_compact_plan wrote past n_live entries")
+    return int(n_live.value), int(first_dead.value), (out[:int(n_live.value)].copy() if want_map else None)
 
 
 class Engine:
@@ -423,6 +453,23 @@ class Engine:
         u = UpdateInfo()
         self._ck(self._lib.hvs_update_stats(self._h, C.byref(u)))
         return u
+
+    # --- row compaction (include/hvs.h "row compaction")
+    def compact(self):
+        """Drop the deleted rows from the data set and renumber the live ones in order: afterwards the context is that of
+        a fresh load of the live rows.  Returns new_to_old: the old id of every new id."""
+        new_to_old = np.empty(self.n_live, np.uint32)
+        self._ck(self._lib.hvs_compact(self._h, _up(new_to_old)))
+        return new_to_old
+
+    def compact_stats(self):
+        s = CompactInfo()
+        self._ck(self._lib.hvs_compact_stats(self._h, C.byref(s)))
+        return s
+
+    def trim_rows(self):
+        """Give back the spare room of the data set's buffer (re-allocates it to exactly n rows)."""
+        self._ck(self._lib.hvs_trim_rows(self._h))
 
     # --- the vec_query seam
     def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None):

@@ -1,0 +1,351 @@
+"""Row compaction on the GPU: hvs_compact drops the deleted rows from D, renumbers the live ones in order and re-indexes, and
+the context then is that of a fresh load of the live rows (include/hvs.h "row compaction").
+
+The expected answers come from the oracle on the live rows (oracle_query + check_parity: distances bit-equal, ids equal up to
+equal-distance ties); the library is compared with itself only where "bit-equal to a fresh load" is the claim.  The row move
+is checked on its own, byte for byte, on a small data set, for chunk sizes that make the chunk loop take
+many rounds (HVS_COMPACT_CHUNK is read per call).
+"""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import hvs_testlib as T
+import test_append as A
+
+pytestmark = pytest.mark.gpu
+PKG = importlib.import_module("project---hybrid-vector-search-queries_amd")
+EXACT, BF, I8, F16 = PKG.ENGINE_EXACT_SCAN, PKG.ENGINE_MFMA_FILTER, PKG.ENGINE_MFMA_I8, PKG.ENGINE_MFMA_F16
+N, NQ, NCAT, FAR = A.N, A.NQ, A.NCAT, A.FAR
+NS, DEFAULT_CHUNK = 5003, 65536                                    # rows of the move-only cases; HVS_COMPACT_CHUNK's default
+fresh, check, passing, check_unpadded = A.fresh, A.check, A.passing, A.check_unpadded
+
+
+@pytest.fixture(scope="module")
+def data():
+    """N base rows, 300 more and 40 replacement rows of the same generator, 224 queries (six of invalid type)."""
+    nodes = T.gen_data(N + 300, 71, T.GEN_V1, NCAT)
+    repl = T.gen_data(40, 173, T.GEN_V1, NCAT)
+    queries = T.gen_queries(NQ, 72, T.GEN_V1, NCAT)
+    queries[-6:-3, 0] = 7.0
+    queries[-3:, 0] = -5.0
+    return nodes, repl, queries
+
+
+def same(a, b):
+    return a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+
+
+def dead_30_percent(n=N):
+    """30 % random rows plus the first and the last one"""
+    dead = np.random.default_rng(7).choice(n, (n * 3) // 10, replace=False)
+    return np.union1d(dead, [0, n - 1]).astype(np.uint32)
+
+
+def sn_of(sp, n):
+    return PKG.append_plan(n, n, sp)[0]
+
+
+# ---- 1. the move alone ----------------------------------------------------------------------------------------------------------
+def dead_sets(n, k, chunk):
+    """name -> dead ids.  The chunks of a compaction start at its first dead id, `chunk` source rows each."""
+    ch = min(chunk, n)
+    sets = {"first row": [0], "last row": [n - 1], "one row in the middle": [2500], "every odd id": np.arange(1, n, 2)}
+    if ch < n:   # the second chunk (source rows 100 + ch ...) holds no live row; the first one holds ch - 1
+        sets["a whole chunk"] = np.concatenate([[100], np.arange(100 + ch, min(n, 100 + 2 * ch))])
+        edge = 7 + ch * max(1, 2500 // ch)                          # a chunk edge: chunks start at the first dead id, 7
+    else:        # one chunk from the first dead id to the end, all dead
+        sets["a whole chunk"] = np.arange(4000, n)
+        edge = 2528                                                 # no chunk edge inside D: a word edge alone
+    sets["100 ids over a chunk edge and word edges"] = np.concatenate([[7], np.arange(edge - 50, edge + 50)])
+    sets["all but the last k"] = np.arange(0, n - k)
+    sets["10 % random"] = np.random.default_rng(11).choice(n, n // 10, replace=False)
+    return {name: np.unique(np.asarray(ids)).astype(np.uint32) for name, ids in sets.items()}
+
+
+@pytest.mark.parametrize("chunk", [48, 4096, None], ids=["chunk 48", "chunk 4096", "default chunk"])
+def test_the_move_alone(data, chunk, monkeypatch):
+    """5003 rows (the call is the move and little else), exact engine: the rows, n, the map, the figures, the mask."""
+    if chunk is None:
+        monkeypatch.delenv("HVS_COMPACT_CHUNK", raising=False)
+    else:
+        monkeypatch.setenv("HVS_COMPACT_CHUNK", str(chunk))
+    ch = chunk or DEFAULT_CHUNK
+    nodes = data[0][:NS]
+    for name, dead in dead_sets(NS, 100, ch).items():
+        live = np.ones(NS, bool)
+        live[dead] = False
+        want_live = np.flatnonzero(live).astype(np.uint32)
+        n_live, first_dead, _ = PKG.compact_plan(live)
+        assert n_live == want_live.size and first_dead == dead[0]
+        with fresh(EXACT, nodes) as e:
+            e.delete_rows(dead)
+            new_to_old = e.compact()
+            s = e.compact_stats()
+            print(chunk, name, s.as_dict())
+            assert np.array_equal(new_to_old, want_live), name
+            assert e.n == n_live and e.n_live == n_live, name
+            assert e.download_data(0, n_live).tobytes() == nodes[want_live].tobytes(), name
+            assert (s.compactions, s.n_before, s.n_after) == (1, NS, n_live), name
+            assert (s.first_moved, s.rows_moved) == (first_dead, n_live - first_dead), name
+            assert s.chunks == -(-(NS - first_dead) // ch), name
+            assert s.move_ms >= 0.0
+            m = e.row_mask()
+            assert m.size == n_live and m.all() and e.mask_stats().n_dead == 0, name
+            with pytest.raises(PKG.HvsError):
+                e.download_data(n_live, 1)                          # the old ids behind the new n are gone
+
+
+def test_no_dead_row_is_a_noop(data, monkeypatch):
+    """Tail and stale rows stay, no re-index, the identity map, `compactions` stays 0 -- with no mask set and with an all-live one."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, repl, queries = data
+    ids = np.array([5, 70_000, N - 1], np.uint32)
+    with fresh(I8, nodes_all[:N]) as e:
+        e.append_rows(nodes_all[N:])
+        e.update_rows(ids, repl[:3])
+        before = e.query(queries, 1.0)
+        for step in range(2):
+            assert np.array_equal(e.compact(), np.arange(N + 300, dtype=np.uint32))
+            a, u, s = e.append_stats(), e.update_stats(), e.compact_stats()
+            assert (a.n_indexed, a.n_tail, a.reindexes, u.n_stale) == (N, 300, 0, 3)
+            assert (s.compactions, s.n_before, s.n_after) == (0, 0, 0) and e.n == N + 300
+            assert same(e.query(queries, 1.0), before)
+            e.set_row_mask(np.ones(N + 300, bool))                  # second round: a mask is set and every row is live
+        assert PKG.library().hvs_compact(e._h, None) == 0           # the map is optional
+
+
+# ---- 2. every engine --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, BF, I8, F16])
+def test_every_engine(data, engine, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, _, queries = data
+    nodes = nodes_all[:N]
+    dead = dead_30_percent()
+    live = np.ones(N, bool)
+    live[dead] = False
+    ids_live = np.flatnonzero(live).astype(np.uint32)
+    cur, n_live = nodes[ids_live], ids_live.size
+    with fresh(engine, nodes) as e:
+        e.delete_rows(dead)
+        assert np.array_equal(e.compact(), ids_live) and e.n == n_live
+        a, m = e.append_stats(), e.mask_stats()
+        assert (a.n_indexed, a.n_tail, a.reindexes) == (n_live, 0, 1) and a.reindex_ms > 0.0
+        assert (m.n_live, m.n_dead, m.tiles_patched) == (n_live, 0, 0)
+        assert e.update_stats().n_stale == 0
+        for k in (100, 8, 256):
+            e.set_k(k)
+            for sp in (1.0, 0.5, 0.1):
+                ids, d = e.query(queries, sp)
+                t = e.last_timing()
+                st = check(cur, queries, ids, d, sp, k, key="compact-30")
+                want_pairs = int(passing(cur, queries, sn_of(sp, n_live), "compact-30").sum())
+                print(engine, k, sp, st, "ran", t.engine, "retry", t.retry_queries, "fallback", t.fallback_queries)
+                assert t.pairs == want_pairs, (sp, k, t.pairs, want_pairs)
+                if sp == 1.0:
+                    assert t.engine == engine, "the requested engine did not run"
+                    e.set_padding(False)
+                    ids0, d0 = e.query(queries, sp)
+                    e.set_padding(True)
+                    check_unpadded(ids0, d0, ids, k, passing(cur, queries, n_live, "compact-30"), n_live)
+        m = e.mask_stats()
+        assert (m.n_dead, m.tiles_patched, m.dead_survivors) == (0, 0, 0)
+
+
+# ---- 3. bit-equal to a fresh load -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("multi", [False, True], ids=["one GPU", "two parts on GPU 0"])
+@pytest.mark.parametrize("engine", [EXACT, I8])
+def test_equals_a_fresh_load(data, engine, multi, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, _, queries = data
+    nodes = nodes_all[:N]
+    dead = dead_30_percent()
+    ids_live = np.setdiff1d(np.arange(N, dtype=np.uint32), dead)
+    with (PKG.Engine(devices=[0, 0]) if multi else PKG.Engine(0)) as e, fresh(engine, nodes[ids_live]) as f:
+        e.set_engine(engine)
+        e.set_tail_limit(FAR)
+        e.load_data(nodes)
+        e.delete_rows(dead)
+        assert np.array_equal(e.compact(), ids_live)
+        s = e.compact_stats()
+        assert (s.compactions, s.n_before, s.n_after, s.first_moved) == (1, N, ids_live.size, 0)
+        for k in (100, 256):
+            e.set_k(k)
+            f.set_k(k)
+            for sp in (1.0, 0.5):
+                assert same(e.query(queries, sp), f.query(queries, sp)), (k, sp)
+                assert e.last_timing().pairs == f.last_timing().pairs and e.last_timing().engine == f.last_timing().engine
+        assert e.download_data(0, ids_live.size).tobytes() == nodes[ids_live].tobytes()
+        e.upload_queries(queries)
+        f.upload_queries(queries)
+        for x in (e, f):
+            x.query_resident(10, 200, 1.0)
+            x.sync()
+        assert same(e.download_results(10, 200), f.download_results(10, 200))
+
+
+# ---- 4. tail and stale rows present -----------------------------------------------------------------------------------------------
+def mutate(e, nodes_all, repl):
+    """append 300 rows, update 17 indexed rows and 3 of the tail, delete 1000 rows (some stale, some of the tail); returns
+    the current rows and the live flags"""
+    cur = nodes_all.copy()
+    e.append_rows(nodes_all[N:])
+    rng = np.random.default_rng(23)
+    upd = np.concatenate([np.sort(rng.choice(N, 17, replace=False)), [N + 1, N + 150, N + 299]]).astype(np.uint32)
+    e.update_rows(upd, repl[:20])
+    cur[upd] = repl[:20]
+    dead = np.union1d(rng.choice(N + 300, 990, replace=False), np.concatenate([upd[:5], [N + 150, N + 7, N + 298, 0, N - 1]])).astype(np.uint32)
+    e.delete_rows(dead)
+    live = np.ones(N + 300, bool)
+    live[dead] = False
+    return cur, live, upd
+
+
+@pytest.mark.parametrize("engine", [EXACT, I8, F16])
+def test_with_tail_and_stale_rows(data, engine, monkeypatch):
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, repl, queries = data
+    with fresh(engine, nodes_all[:N]) as e:
+        cur, live, upd = mutate(e, nodes_all, repl)
+        assert (e.append_stats().n_tail, e.update_stats().n_stale, e.append_stats().reindexes) == (300, 17, 0)
+        ids_live = np.flatnonzero(live).astype(np.uint32)
+        assert np.array_equal(e.compact(), ids_live)
+        rows = cur[ids_live]
+        a = e.append_stats()
+        assert (a.n_indexed, a.n_tail, a.reindexes, e.update_stats().n_stale) == (ids_live.size, 0, 1, 0)
+        assert e.download_data(0, ids_live.size).tobytes() == rows.tobytes()
+        for sp in (1.0, 0.5):
+            ids, d = e.query(queries, sp)
+            check(rows, queries, ids, d, sp, 100, key="compact-tail-stale")
+            assert e.last_timing().pairs == int(passing(rows, queries, sn_of(sp, ids_live.size), "compact-tail-stale").sum())
+            assert sp < 1.0 or e.last_timing().engine == engine, "the requested engine did not run"
+
+
+# ---- 5. life goes on ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", [EXACT, I8])
+def test_life_goes_on(data, engine, monkeypatch):
+    """After a compaction the new ids are the ids: delete, append, update, compact again, trim -- each step against the oracle
+    on a host-side model of the rows."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, repl, queries = data
+    rng = np.random.default_rng(31)
+
+    def answers_match(e, rows, live, sp=1.0):
+        ids_live = np.flatnonzero(live)
+        got, d = e.query(queries, sp)
+        assert np.isin(got, ids_live).all(), "a dead or unknown id in an answer"
+        back = np.searchsorted(ids_live, got).astype(np.uint32)     # ids of the live rows -> places in rows[live]
+        check(rows[ids_live], queries, back, d, sp, 100)
+
+    with fresh(engine, nodes_all[:N]) as e:
+        e.delete_rows(dead_30_percent())
+        model = nodes_all[:N][e.compact()]
+        n1 = model.shape[0]
+        live = np.ones(n1, bool)
+        # delete by new ids
+        dead = rng.choice(n1, 500, replace=False).astype(np.uint32)
+        e.delete_rows(dead)
+        live[dead] = False
+        answers_match(e, model, live)
+        # append: the first new id is n, and the room the compaction left is used
+        assert e.append_rows(nodes_all[N:]) == n1 and e.n == n1 + 300
+        model, live = np.concatenate([model, nodes_all[N:]]), np.concatenate([live, np.ones(300, bool)])
+        # update, by new ids
+        upd = np.sort(rng.choice(n1 + 300, 40, replace=False)).astype(np.uint32)
+        e.update_rows(upd, repl)
+        model[upd] = repl
+        answers_match(e, model, live)
+        assert e.download_data(0, n1 + 300).tobytes() == model.tobytes()
+        # compact again
+        ids_live = np.flatnonzero(live).astype(np.uint32)
+        assert np.array_equal(e.compact(), ids_live)
+        model = model[ids_live]
+        n2 = model.shape[0]
+        s, a = e.compact_stats(), e.append_stats()
+        assert (s.compactions, s.n_before, s.n_after) == (2, n1 + 300, n2) and (a.n_indexed, a.n_tail, a.reindexes) == (n2, 0, 2)
+        before = e.query(queries, 1.0)
+        check(model, queries, before[0], before[1], 1.0, 100)
+        # trim: nothing a caller sees changes
+        e.trim_rows()
+        e.trim_rows()                                                # (no spare room left: a no-op)
+        assert same(e.query(queries, 1.0), before) and e.n == n2
+        assert e.download_data(0, n2).tobytes() == model.tobytes()
+        assert e.append_rows(nodes_all[:50]) == n2                   # D grows again
+        model = np.concatenate([model, nodes_all[:50]])
+        assert e.download_data(0, n2 + 50).tobytes() == model.tobytes()
+        answers_match(e, model, np.ones(n2 + 50, bool), 0.5)
+
+
+# ---- 6. errors ---------------------------------------------------------------------------------------------------------------------
+def test_errors(data):
+    nodes_all, _, queries = data
+    lib = PKG.library()
+    assert lib.hvs_compact(None, None) == -1 and lib.hvs_trim_rows(None) == -1 and lib.hvs_compact_stats(None, None) == -1
+    with PKG.Engine(0) as e, fresh(EXACT, nodes_all[:NS]) as other:
+        other.delete_rows(np.arange(10, 500, dtype=np.uint32))
+        before, rows = other.query(queries, 1.0), other.download_data(0, NS)
+        with pytest.raises(PKG.HvsError) as err:
+            e.compact()                                              # no data loaded
+        assert err.value.code == -4
+        with pytest.raises(PKG.HvsError) as err:
+            e.trim_rows()
+        assert err.value.code == -4
+        assert lib.hvs_compact_stats(e._h, None) == -1
+        assert e.compact_stats().compactions == 0
+        # a failing call next door changed nothing here
+        assert same(other.query(queries, 1.0), before) and other.download_data(0, NS).tobytes() == rows.tobytes()
+        assert other.n == NS and other.n_live == NS - 490 and other.compact_stats().compactions == 0
+    # a load resets the figures
+    with fresh(EXACT, nodes_all[:NS]) as e:
+        e.delete_rows([3])
+        e.compact()
+        assert e.compact_stats().compactions == 1
+        e.load_data(nodes_all[:NS])
+        assert e.compact_stats().compactions == 0 and e.n == NS
+
+
+_CHILD = r"""
+import importlib, os, sys, numpy as np
+sys.path.insert(0, 'tests'); sys.path.insert(0, '.')
+import hvs_testlib as T
+import test_append as A
+import test_compact as K
+PKG = importlib.import_module('project---hybrid-vector-search-queries_amd')
+nodes = T.gen_data(A.N, 71, T.GEN_V1, A.NCAT)
+queries = T.gen_queries(1500, 74, T.GEN_V1, A.NCAT)
+dead = K.dead_30_percent()
+ids_live = np.setdiff1d(np.arange(A.N, dtype=np.uint32), dead)
+with A.fresh(PKG.ENGINE_MFMA_I8, nodes) as e:
+    e.delete_rows(dead)
+    e.upload_queries(queries)
+    e.query_resident(0, 1500, 1.0); e.sync()
+    t = e.last_timing()
+    print('retry', t.retry_queries, 'fallback', t.fallback_queries)
+    assert t.retry_queries > 0, 'no guessed threshold failed: nothing is pending when the compaction starts'
+    want = e.download_results(0, 1500)
+    back = np.searchsorted(ids_live, want[0]).astype(np.uint32)
+    A.check(nodes[ids_live], queries, back, want[1], 1.0, 100, key='child-compact')
+    e.query_resident(0, 1500, 1.0)                     # the same call again: its re-runs are pending ...
+    assert np.array_equal(e.compact(), ids_live)       # ... and resolved, under the old mask and ids, before a row moves
+    assert e.download_data(0, ids_live.size).tobytes() == nodes[ids_live].tobytes()
+    got, d = e.query(queries, 1.0)
+    A.check(nodes[ids_live], queries, got, d, 1.0, 100, key='child-compact')
+    e.query_resident(0, 1500, 0.5); e.sync()           # resident queries stayed
+    ri, rd = e.download_results(0, 1500)
+    A.check(nodes[ids_live], queries, ri, rd, 0.5, 100)
+print('SUBPROCESS-OK')
+"""
+
+
+def test_pending_reruns_are_resolved_before_the_move():
+    """HVS_GUESS_PFAIL=1 (read when the library is loaded, hence the child process): guessed thresholds fail, so a resident call
+    that has not been synchronised leaves re-runs pending when hvs_compact starts."""
+    env = dict(os.environ, HVS_GUESS_PFAIL="1", HVS_I8_ROTATE="0")
+    r = subprocess.run([sys.executable, "-c", _CHILD], capture_output=True, text=True, env=env, cwd=T.REPO, timeout=900)
+    print(r.stdout[-3000:])
+    assert "SUBPROCESS-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
