@@ -87,6 +87,59 @@ struct HvsFormatState {
     bool f16_rejected = false;  // likewise the FP16 tiles (components beyond the half-precision range)
 };
 
+// Row-set state of one data set: which rows are live and which of them the index is right about -- all that
+// deletion, append, update and compaction maintain beside hvs_ctx's d_data, n, n_indexed and have_order.  The invariants:
+//   - h_live.empty()  <=>  no mask set: every row live, n_dead == 0, and no launch reads d_live, d_pad_ids or d_mask_stat
+//   - d_live, once allocated, has room for n_cap rows (live_cap >= ceil(n_cap / 64)); the first mask call after a reset makes it
+//   - h_stale is ascending, unique, below n_indexed, and mirrored in d_stale_ids[0 .. h_stale.size())
+//   - d_ilive is valid  <=>  !h_stale.empty(); while it is, n_indexed does not change
+struct HvsRowSet {
+    // -- live-row mask.  While nothing is masked (masked()) every launch takes its kernel's unmasked instantiation
+    std::vector<uint64_t> h_live;   // host copy: ceil(n / 64) words, bits past n clear
+    uint32_t* d_live = nullptr;     // the same bits as u32 words in HBM
+    uint32_t n_dead = 0, live_cap = 0;  // dead rows; u64 words d_live has room for
+    uint32_t* d_pad_ids = nullptr;  // the last k live ids in descending order (HVS_KMAX entries)
+    unsigned long long* d_mask_stat = nullptr;  // [0]: rows whose tile entry carries the never-hit encoding, both orderings
+    bool lp_valid = false;          // HvsOrdering::lp holds the counts of the current mask and stale set
+    bool cut_valid = false;         // cut id of the sampled live prefix for sample_proportion cut_sp (hvs_mask_plan), cached
+    float cut_sp = 0.0f;
+    uint32_t cut_id = 0, cut_sn_live = 0;
+    // -- capacity and tail: ids [n_indexed, n), scanned exactly by hvs_k_scan_tail for every batch that goes through the index
+    uint32_t n_cap = 0;             // rows d_data has room for (hvs_reserve_rows / geometric growth of hvs_append_rows)
+    uint32_t tail_limit = 0;        // hvs_set_tail_limit (0: the default rule, tail_limit_of); a setting, kept by every reset
+    uint32_t reindexes = 0;         // index builds caused by appends, updates, compactions or hvs_reindex since the last load
+    double reindex_ms = 0.0;        // the last of them
+    uint32_t index_tried_n = 0;     // no-index state: n at the last attempt to build one (0: none yet)
+    // -- stale set.  An indexed row whose contents changed is STALE: alive in D, dead as far as the index knows.
+    // While there are such rows the launches that reach a row THROUGH THE INDEX take d_ilive (index_mask()), every masked kernel
+    // runs in its MASKED form, and hvs_k_scan_stale scans the stale rows by id.  Empty list: none of the buffers is read.
+    std::vector<uint32_t> h_stale;
+    uint32_t* d_stale_ids = nullptr;
+    // two planes of W = 2 ceil(n_indexed / 64) u32 words: [0, W) live AND NOT stale, [W, 2W) the row mask's bits of the
+    // indexed rows (what hvs_k_rescore tells stale from dead by, HVS_RESCORE_TWO_MASKS)
+    uint32_t* d_ilive = nullptr;
+    uint32_t stale_cap = 0, ilive_cap = 0;  // ids d_stale_ids / u32 words d_ilive has room for
+    // -- staging, kept between calls: hvs_delete_rows' id list; hvs_update_rows' rows, ids and the staged row of each id.  Per-call
+    // buffers, freed when the call ends (free_call_scratch): hvs_compact's bounce buffer and rank table, hvs_trim_rows' smaller D
+    uint32_t *d_mask_ids = nullptr, *d_upd_ids = nullptr, *d_upd_from = nullptr;
+    float* d_upd_rows = nullptr;
+    uint32_t mask_ids_cap = 0, upd_cap = 0;
+    uint2* d_cmp_bounce = nullptr;
+    uint32_t* d_cmp_rank = nullptr;
+    float* d_trim = nullptr;
+    hvs_compact_info cstat{};       // figures of the last hvs_compact since the last load
+    // the device buffers this state owns, in two lists: the per-call ones, and all (D and HvsOrdering::lp are the context's)
+    template <typename... P>
+    static void drop(P*&... p) { (((void)(p ? hipFree(p) : hipSuccess), p = nullptr), ...); }
+    void free_call_buffers() { drop(d_cmp_bounce, d_cmp_rank, d_trim); }
+    void free_device()
+    {
+        drop(d_live, d_pad_ids, d_mask_stat, d_stale_ids, d_ilive, d_mask_ids, d_upd_rows, d_upd_ids, d_upd_from);
+        free_call_buffers();
+        live_cap = stale_cap = ilive_cap = mask_ids_cap = upd_cap = 0;
+    }
+};
+
 // Workspace of ONE query batch and the stream it runs on -- a "lane".  A context owns two (round 4): the last level of batch b
 // ends with its re-scoring (HBM-bound gathers) and the final merge (latency-bound), both of which leave the matrix pipes idle,
 // and batch b+1 begins with preparation, the exact seed and two small filter levels that cannot fill the chip; with batch
@@ -142,52 +195,11 @@ struct hvs_ctx : HvsLane {
     bool padding = true;        // pad answers with the last rows of D (off: partial answers of a data shard)
     std::string err;
 
-    // live-row mask (hvs_set_row_mask / hvs_delete_rows).  While n_dead == 0 every launch takes the unmasked
-    // instantiation of its kernel and none of the device buffers below is read.
-    std::vector<uint64_t> h_live;   // host copy: ceil(n / 64) words, bits past n clear (empty: no mask set, all rows live)
-    uint32_t n_dead = 0;
-    uint32_t* d_live = nullptr;     // the same bits as u32 words in HBM (allocated by the first mask call after a load)
-    uint32_t* d_pad_ids = nullptr;  // the last k live ids in descending order (HVS_KMAX entries)
-    uint32_t* d_mask_ids = nullptr; // id list of the running hvs_delete_rows
-    uint32_t mask_ids_cap = 0;
-    bool lp_valid = false;
-    unsigned long long* d_mask_stat = nullptr;  // [0]: rows whose tile entry carries the never-hit encoding, both orderings
-    bool cut_valid = false;         // cut id of the sampled live prefix for sample_proportion cut_sp (hvs_mask_plan), cached
-    float cut_sp = 0.0f;
-    uint32_t cut_id = 0, cut_sn_live = 0;
-
-    // data set, raw rows n x 102 (the io.h layout) resident in HBM
+    // data set, raw rows n x 102 (the io.h layout) resident in HBM; which of the n rows are live, stale or behind the index: `rs`
     float* d_data = nullptr;
     uint32_t n = 0;
-    uint32_t n_cap = 0;  // rows d_data has room for (hvs_reserve_rows / geometric growth of hvs_append_rows)
     double load_ms = 0.0;
-    // appended rows (hvs_append_rows): `n` counts the rows there are, `n_indexed` (below) the rows the index
-    // covers; ids [n_indexed, n) are the tail, scanned exactly by hvs_k_scan_tail for every batch that goes through the index
-    uint32_t tail_limit = 0;      // hvs_set_tail_limit (0: the default rule, tail_limit_of)
-    uint32_t reindexes = 0;       // index builds caused by appends or hvs_reindex since the last load
-    double reindex_ms = 0.0;      // the last of them
-    uint32_t index_tried_n = 0;   // no-index state: n at the last attempt to build one (0: none yet)
-    uint32_t live_cap = 0;        // u64 words d_live has room for
-    // updated rows (hvs_update_rows).  An indexed row whose contents changed is STALE: alive in D, dead as far as
-    // the index knows.  While there are such rows the launches that reach a row THROUGH THE INDEX take d_ilive (live AND NOT
-    // stale) where they take d_live otherwise, every masked kernel runs in its MASKED form, and hvs_k_scan_stale scans the
-    // stale rows by id for every batch that goes through the index.  Empty list: none of the buffers below is read.
-    std::vector<uint32_t> h_stale;  // ascending, unique, ids < n_indexed
-    uint32_t* d_stale_ids = nullptr;
-    uint32_t stale_cap = 0;         // ids d_stale_ids has room for
-    // two planes of W = 2 ceil(n_indexed / 64) u32 words: [0, W) live AND NOT stale, [W, 2W) the row mask's bits of the
-    // indexed rows (what hvs_k_rescore tells stale from dead by, HVS_RESCORE_TWO_MASKS)
-    uint32_t* d_ilive = nullptr;
-    uint32_t ilive_cap = 0;         // u32 words it has room for
-    float* d_upd_rows = nullptr;    // staging of the running hvs_update_rows: its rows, their ids, the staged row of each id
-    uint32_t *d_upd_ids = nullptr, *d_upd_from = nullptr;
-    uint32_t upd_cap = 0;
-    // row compaction (hvs_compact): figures of the last one, and the scratch of the running one (bounce buffer of
-    // one chunk, rank table; allocated by leaf_compact_prepare, freed when the call ends) / of the running hvs_trim_rows
-    hvs_compact_info cstat{};
-    uint2* d_cmp_bounce = nullptr;
-    uint32_t* d_cmp_rank = nullptr;
-    float* d_trim = nullptr;
+    HvsRowSet rs;
 
     // resident queries + results
     float* d_q = nullptr;
@@ -269,6 +281,49 @@ struct hvs_ctx : HvsLane {
 };
 
 namespace {
+
+// ---- readers of the row-set state (HvsRowSet).  The two roles of the mask.  `masked`: some row is dead or some
+// index entry is stale -- the MASKED kernels run, pairs are counted the masked way, no host-side range counts.  Launches that
+// reach a row by its id in D take rs.d_live; launches that reach it through the index (perm, tiles) take index_mask(c).
+bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empty(); }
+const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
+uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
+uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
+{
+    if (!c->have_order || c->rs.h_stale.empty()) return 0u;
+    return (uint32_t)(std::lower_bound(c->rs.h_stale.begin(), c->rs.h_stale.end(), sn) - c->rs.h_stale.begin());
+}
+// rows behind the index, stale rows aside: the tail -- or, without orderings, the rows that came after the last attempt to build one
+uint32_t rows_behind_index(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : c->n - std::min(c->n, c->rs.index_tried_n); }
+// rows_behind_index + n_stale above which an append or an update re-indexes before it returns (fold_if_over_limit).  Default
+// max(4096, n_indexed >> 10), derived, then measured at a loss of 15 % at the limit: if the tail scan evaluated pairs at the exact engine's rate, ~3.1 x 10^11
+// pairs/s on record, and the filter engines answer a flagship query in ~310 ns, 10^4 tail rows (n_indexed = 10^7) cost a tenth of a query.
+uint32_t tail_limit_of(const hvs_ctx* c) { return c->rs.tail_limit ? c->rs.tail_limit : std::max(4096u, c->n_indexed >> 10); }
+
+// ---- mask words: ceil(n / 64) u64 words, row i at bit i & 63 of word i >> 6 (the device reads the same bytes as u32 words)
+inline size_t mask_words(uint32_t n) { return ((size_t)n + 63u) / 64u; }
+// word w with the bits past n cleared (bits == nullptr: every row live)
+inline uint64_t masked_word(const uint64_t* bits, uint32_t n, size_t w)
+{
+    const uint64_t v = bits ? bits[w] : ~0ull;
+    return w + 1u == mask_words(n) && (n & 63u) ? v & ((1ull << (n & 63u)) - 1ull) : v;
+}
+inline uint32_t mask_popcount(const uint64_t* bits, uint32_t n)  // live rows among the n
+{
+    const size_t W = mask_words(n);
+    uint32_t live = 0;  // (whole words in a plain loop: every delete walks the whole mask, 1.6 x 10^5 words at 10^7 rows)
+    for (size_t w = 0; w + 1u < W; ++w) live += (uint32_t)__builtin_popcountll(bits[w]);
+    return W ? live + (uint32_t)__builtin_popcountll(masked_word(bits, n, W - 1u)) : live;
+}
+inline uint32_t mask_half(uint64_t word, size_t i) { return (uint32_t)(word >> (32u * (i & 1u))); }  // u32 word i of the device's view
+inline void mask_set_range(std::vector<uint64_t>& bits, uint32_t a, uint32_t b)  // rows [a, b) live
+{
+    for (uint32_t i = a; i < b;) {
+        const uint32_t at = i & 63u, m = std::min(64u - at, b - i);
+        bits[i >> 6] |= (m == 64u ? ~0ull : ((1ull << m) - 1ull)) << at;
+        i += m;
+    }
+}
 
 uint32_t env_u32(const char* name, uint32_t dflt, uint32_t lo, uint32_t hi)
 {
@@ -485,12 +540,6 @@ void with_cap(int cap, F f)
         f(std::integral_constant<int, 256>{});
 }
 
-// The two roles of the mask.  `masked`: some row is dead or some index entry is stale -- the MASKED kernels run,
-// pairs are counted the masked way, no host-side range counts.  Launches that reach a row by its id in D take c->d_live;
-// launches that reach it through the index (perm, tiles) take index_mask(c), which differs only while rows are stale.
-bool masked(const hvs_ctx* c) { return c->n_dead != 0u || !c->h_stale.empty(); }
-const uint32_t* index_mask(const hvs_ctx* c) { return c->h_stale.empty() ? c->d_live : c->d_ilive; }
-
 // ... and for the two forms of the kernels that read the live-row mask: `f` gets (capacity, masked) as compile-time constants;
 // masked only while at least one row is dead or stale
 template <typename F>
@@ -524,7 +573,7 @@ void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t st
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((nsel + 3u) / 4u), dim3(256), 0,
                            c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids,
-                           c->d_out_dists, c->k, c->d_pad_ids);
+                           c->d_out_dists, c->k, c->rs.d_pad_ids);
     });
 }
 
@@ -638,7 +687,7 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
         with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
             hipLaunchKernelGGL((hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0,
                                c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k,
-                               c->d_live);
+                               c->rs.d_live);
         });
     }
     kernel_timer_end(c, ev);
@@ -662,7 +711,7 @@ void free_index(hvs_ctx* c)
     }
     c->have_order = false;
     c->n_indexed = 0;
-    c->lp_valid = false;  // (counts along the orderings that have just gone)
+    c->rs.lp_valid = false;  // (counts along the orderings that have just gone)
     // everything the last data set taught, `planned` and `built_rot` included: nothing reads those two before choose_format
     // and build_tiles have written them for the next index
     c->fmt = HvsFormatState{};
@@ -771,7 +820,7 @@ int choose_format(hvs_ctx* c)
 // use after a mask change
 int ensure_live_prefix(hvs_ctx* c)
 {
-    if (c->lp_valid) return HVS_OK;
+    if (c->rs.lp_valid) return HVS_OK;
     const uint32_t n = c->n_indexed;  // (positions)
     int rc;
     for (HvsOrdering& o : c->ord)
@@ -789,7 +838,7 @@ int ensure_live_prefix(hvs_ctx* c)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(tmp);
     if (e != hipSuccess) return fail(c, HVS_EHIP, std::string("live-row counts: ") + hipGetErrorString(e));
-    c->lp_valid = true;
+    c->rs.lp_valid = true;
     return HVS_OK;
 }
 
@@ -814,13 +863,13 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
 // build while rows are dead or stale.
 int patch_tiles(hvs_ctx* c)
 {
-    if (!masked(c) || c->fmt.built == HVS_FMT_NONE || !c->ord[0].tiles || !index_mask(c) || !c->d_mask_stat) return HVS_OK;
+    if (!masked(c) || c->fmt.built == HVS_FMT_NONE || !c->ord[0].tiles || !index_mask(c) || !c->rs.d_mask_stat) return HVS_OK;
     const HvsLevels L = c->lv;
-    HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(c->rs.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const dim3 grid((L.nblk + 3u) / 4u);
     for (const HvsOrdering& o : c->ord)
         hipLaunchKernelGGL(hvs_k_patch_tiles, grid, dim3(256), 0, c->stream, index_mask(c), o.perm, c->n_indexed, L, o.bpos, o.tiles,
-                           reinterpret_cast<int*>(o.nrm), c->fmt.built, c->d_mask_stat);
+                           reinterpret_cast<int*>(o.nrm), c->fmt.built, c->rs.d_mask_stat);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -833,7 +882,7 @@ int build_tiles(hvs_ctx* c, int fmt)
     const uint32_t n = c->n_indexed;
     int rc;
     c->fmt.built = HVS_FMT_NONE;
-    if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
+    if (c->rs.d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->rs.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));  // fresh tiles: none patched
     // free first: the two formats never coexist (D = 1e8: 44.8 GB of BF16 tiles, 20.8 GB of INT8 tiles)
     for (HvsOrdering& o : c->ord) {
         if ((rc = dev_alloc(c, &o.tiles, (size_t)0))) return rc;
@@ -1219,23 +1268,18 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
-                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters, count ? 1 : 0, c->d_live);
+                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters, count ? 1 : 0, c->rs.d_live);
     });
 }
 
 // The stale rows of the batch in c->fb (hvs_k_scan_stale): the prefix of the ascending stale list with id < sn
-// (under a mask sn is the cut).  0: nothing to launch.
-uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
-{
-    if (!c->have_order || c->h_stale.empty()) return 0u;
-    return (uint32_t)(std::lower_bound(c->h_stale.begin(), c->h_stale.end(), sn) - c->h_stale.begin());
-}
+// (under a mask sn is the cut; stale_below).  0: nothing to launch.
 void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
-                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->d_stale_ids, m, c->d_counters, count ? 1 : 0, c->d_live);
+                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m, c->d_counters, count ? 1 : 0, c->rs.d_live);
     });
 }
 
@@ -1256,7 +1300,7 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn < c->n_indexed)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, c->d_live);
+                           c->d_counters, c->rs.d_live);
     // slot layout of hvs_k_layout: classes 0..3 padded to 32 slots each, then the T-ordering class (type 2)
     // from the next filter-workgroup boundary
     const uint32_t nq0 = c->class_counts[0], nq2 = c->class_counts[4];
@@ -1444,7 +1488,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn < n && !list)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, c->d_live);
+                           c->d_counters, c->rs.d_live);
 
     if (c->gate_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gate_heavy, 0));  // (two lanes: see hvs_ctx::ev_pdone)
     // level 0 by the exact kernel; small batches cut it into chunks so that enough waves are in flight
@@ -1464,10 +1508,10 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             if (final)  // (only the final merge pads: the merges in front of it have no masked form)
                 hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n,
                                    c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G,
-                                   c->d_pad_ids);
+                                   c->rs.d_pad_ids);
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
-                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->d_pad_ids);
+                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids);
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -1509,7 +1553,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;  // (entry format)
             // (while rows are stale the front end gets both masks and tells stale from dead: HVS_RESCORE_TWO_MASKS)
             hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data,
-                               c->h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS), sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters,
+                               c->rs.h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS), sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters,
                                index_mask(c));
         });
         if (last == L.K) tail_before_final();
@@ -1705,19 +1749,19 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
     }
     uint32_t sn = sample_rows(sample_proportion, c->n);
     uint32_t sampled = sn, of_rows = c->n;  // rows searched / rows there are (live ones under a mask)
-    if (c->n_dead) {
+    if (c->rs.n_dead) {
         // live-row mask: the rows searched are the first sn_live live rows = "id < cut and live" (hvs_mask_plan); `sn` is the
         // cut id from here on -- what every kernel's sampled-prefix test compares against
-        if (!c->cut_valid || std::memcmp(&c->cut_sp, &sample_proportion, sizeof(float)) != 0) {
+        if (!c->rs.cut_valid || std::memcmp(&c->rs.cut_sp, &sample_proportion, sizeof(float)) != 0) {
             uint32_t n_live = 0;
-            hvs_mask_plan(c->h_live.data(), c->n, c->k, sample_proportion, &n_live, &c->cut_id, nullptr);
-            c->cut_sn_live = sample_rows(sample_proportion, n_live);
-            c->cut_sp = sample_proportion;
-            c->cut_valid = true;
+            hvs_mask_plan(c->rs.h_live.data(), c->n, c->k, sample_proportion, &n_live, &c->rs.cut_id, nullptr);
+            c->rs.cut_sn_live = sample_rows(sample_proportion, n_live);
+            c->rs.cut_sp = sample_proportion;
+            c->rs.cut_valid = true;
         }
-        of_rows = c->n - c->n_dead;
-        sampled = c->cut_sn_live;
-        sn = sampled ? c->cut_id : 0u;
+        of_rows = c->n - c->rs.n_dead;
+        sampled = c->rs.cut_sn_live;
+        sn = sampled ? c->rs.cut_id : 0u;
     }
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
@@ -1912,10 +1956,10 @@ void leaf_destroy(hvs_ctx* c)
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
     void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
-                    c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->d_live, c->d_pad_ids, c->d_mask_ids,
-                    c->d_mask_stat, c->ord[0].lp, c->ord[1].lp, c->d_stale_ids, c->d_ilive, c->d_upd_rows, c->d_upd_ids, c->d_upd_from};
+                    c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    c->rs.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     free_lane(c->spare);
     free_lane(static_cast<HvsLane&>(*c));
@@ -2000,33 +2044,129 @@ int leaf_reserve(hvs_ctx* c, uint32_t nq)
     return ensure_batch_workspace(c, nqb, make_plan(nqb, c->n ? c->n : 1u));
 }
 
-int begin_data(hvs_ctx* c, uint32_t n)
+// ---- row-set state (HvsRowSet): what every call that changes it shares ----
+// Every call that changes the rows, the mask, the index or k starts here: an earlier call's pending re-runs belong to the rows,
+// the mask and the ids they were asked under, so they run first; then nothing on the device reads what is about to change.
+int begin_mutation(hvs_ctx* c)
 {
-    if (n < c->k)
-        return fail(c, HVS_EINVAL,
-                    "data set needs at least k (default 100) rows (the reference pads results with rows n-1, n-2, ...)");
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    c->n = 0;
-    c->n_cap = 0;
-    c->live_cap = 0;
-    c->reindexes = 0;  // (the tail is empty: free_index in finish_data; the limit stays)
-    c->h_stale.clear();  // (no row is stale; the device buffers stay for the next update)
-    c->reindex_ms = 0.0;
-    c->index_tried_n = 0;
-    c->cstat = hvs_compact_info{};
-    // a new data set starts with every row live
-    c->h_live.clear();
-    c->n_dead = 0;
-    c->cut_valid = false;
-    c->lp_valid = false;
-    if ((rc = dev_alloc(c, &c->d_live, (size_t)0))) return rc;
+    return HVS_OK;
+}
+
+// Room for `want` elements in *buf with its first `keep` elements preserved.  The new buffer is allocated before the old one
+// is released, so a failure leaves *buf and its contents as they were.  `what`: the start of the error text of a failed copy.
+// `mirror`: a host copy of the contents to take them from (else device to device, from the old buffer).
+template <typename T>
+int grow_keep(hvs_ctx* c, T** buf, size_t want, size_t keep, const char* what, const T* mirror = nullptr)
+{
+    T* bigger = nullptr;
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), want * sizeof(T)));
+    const hipMemcpyKind kind = mirror ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    hipError_t e = keep ? hipMemcpyAsync(bigger, mirror ? mirror : *buf, keep * sizeof(T), kind, c->stream) : hipSuccess;
+    if (keep && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(bigger);
+        return fail(c, HVS_EHIP, std::string(what) + hipGetErrorString(e));
+    }
+    if (*buf) (void)hipFree(*buf);
+    *buf = bigger;
+    return HVS_OK;
+}
+
+std::vector<uint64_t> all_live_words(uint32_t n)
+{
+    std::vector<uint64_t> w(mask_words(n));
+    for (size_t i = 0; i < w.size(); ++i) w[i] = masked_word(nullptr, n, i);
+    return w;
+}
+
+// the device table of the k padding ids (the last k live rows, descending)
+int refresh_pad_ids(hvs_ctx* c)
+{
+    if (!c->rs.d_pad_ids || c->rs.h_live.empty()) return HVS_OK;
+    uint32_t pad[HVS_KMAX];
+    hvs_mask_plan(c->rs.h_live.data(), c->n, c->k, 1.0f, nullptr, nullptr, pad);
+    HVS_HIP(c, hipMemcpyAsync(c->rs.d_pad_ids, pad, (size_t)c->k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`pad` is on this stack)
+    return HVS_OK;
+}
+
+// The index-validity mask of a context with stale rows (HvsRowSet::d_ilive), from the host's mask and stale list; room for it
+// was secured by leaf_update_prepare.  No stale rows: nothing to do, index_mask(c) is d_live.
+int refresh_index_mask(hvs_ctx* c)
+{
+    const HvsRowSet& s = c->rs;
+    if (s.h_stale.empty()) return HVS_OK;
+    const size_t W = 2u * mask_words(c->n_indexed);
+    if (!s.d_ilive || 2u * W > s.ilive_cap) return fail(c, HVS_ESTATE, "internal: no room for the index-validity mask");
+    std::vector<uint32_t> w(2u * W, 0u);
+    for (size_t i = 0; i < W; ++i) w[i] = w[W + i] = (i >> 1) < s.h_live.size() ? mask_half(s.h_live[i >> 1], i) : 0u;
+    const size_t last = W / 2u - 1u;  // (the bits of the tail's rows in the last word are not the index's business)
+    for (size_t i = 2u * last; i < W && last < s.h_live.size(); ++i) w[i] = w[W + i] = mask_half(masked_word(s.h_live.data(), c->n_indexed, last), i);
+    for (uint32_t id : s.h_stale) w[id >> 5] &= ~(1u << (id & 31u));
+    HVS_HIP(c, hipMemcpyAsync(s.d_ilive, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`w` goes with this scope)
+    return HVS_OK;
+}
+
+// What follows from a change of the row set, each case in this order (the table of DESIGN 3.9a); the caller has written the new
+// h_live / n_dead / h_stale / n.  MaskLostRows is also a mask set anew with no row changed.
+enum class RowChange { MaskLostRows, MaskRevivedRows, StaleGrew, RowsAppended, Renumbered };
+int row_set_changed(hvs_ctx* c, RowChange ch)
+{
+    HvsRowSet& s = c->rs;
+    int rc;
+    switch (ch) {
+    case RowChange::MaskLostRows:
+    case RowChange::MaskRevivedRows:  // (tiles: rebuilt, which patches at its end, or patched; nothing without tiles)
+        s.cut_valid = s.lp_valid = false;
+        if ((rc = refresh_index_mask(c))) return rc;
+        rc = ch == RowChange::MaskRevivedRows && c->fmt.built != HVS_FMT_NONE ? build_tiles(c, c->fmt.built) : patch_tiles(c);
+        return rc ? rc : refresh_pad_ids(c);
+    case RowChange::StaleGrew:  // (a stale row is live: the mask, the cut and the padding ids stand)
+        s.lp_valid = false;
+        return (rc = refresh_index_mask(c)) ? rc : patch_tiles(c);
+    case RowChange::RowsAppended:  // (counts, index mask and tiles cover indexed rows only)
+        s.cut_valid = false;
+        return refresh_pad_ids(c);
+    case RowChange::Renumbered:  // (reset_row_set: no mask and no stale row, and the caller re-indexes)
+        s.cut_valid = s.lp_valid = false;
+    }
+    return HVS_OK;
+}
+
+// The row-set state of a fresh load: every row live and no mask set (the next mask call allocates d_live for the rows there
+// are then), no stale row (its device buffers stay), no index attempted, nothing cached.  n, n_cap and D are the caller's:
+// a load (begin_data) or a compaction (leaf_compact_commit); what the two do differently is written at each call.
+int reset_row_set(hvs_ctx* c)
+{
+    HvsRowSet& s = c->rs;
+    s.h_live.clear();
+    s.h_stale.clear();
+    s.n_dead = s.index_tried_n = s.live_cap = 0;
+    const int rc = dev_alloc(c, &s.d_live, (size_t)0);
+    return rc ? rc : row_set_changed(c, RowChange::Renumbered);
+}
+
+int begin_data(hvs_ctx* c, uint32_t n)
+{
+    if (n < c->k) return fail(c, HVS_EINVAL, "data set needs at least k (default 100) rows (the reference pads results with rows n-1, n-2, ...)");
+    int rc = begin_mutation(c);
+    if (rc) return rc;
+    c->n = c->rs.n_cap = 0;
+    if ((rc = reset_row_set(c))) return rc;
+    // a load, unlike a compaction, starts the figures of the data set over (the tail limit is a setting and stays) ...
+    c->rs.reindexes = 0;
+    c->rs.reindex_ms = 0.0;
+    c->rs.cstat = hvs_compact_info{};
+    // ... and frees the live-row counts along the orderings itself (a compaction leaves that to leaf_reindex)
     if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->d_data, (size_t)n * HVS_DCOLS))) return rc;
-    c->n_cap = n;
+    c->rs.n_cap = n;
     return HVS_OK;
 }
 
@@ -2047,7 +2187,7 @@ int index_data(hvs_ctx* c)
     free_index(c);
     // the index (two orderings + tiles) serves both engines: the exact engine scans position ranges
     if (c->n < kIndexMinRows && !is_filter_engine(c->engine)) return HVS_OK;
-    c->index_tried_n = c->n;
+    c->rs.index_tried_n = c->n;
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
     int rc = build_index(c);
     if (rc == HVS_ENOMEM) {
@@ -2520,103 +2660,48 @@ int leaf_last_timing(hvs_ctx* c, hvs_timing* out)
     return HVS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// live-row mask
-// ---------------------------------------------------------------------------------------------
-std::vector<uint64_t> all_live_words(uint32_t n)
-{
-    std::vector<uint64_t> w(((size_t)n + 63u) / 64u, ~0ull);
-    if (n & 63u) w.back() = (1ull << (n & 63u)) - 1ull;
-    return w;
-}
-
-// the device table of the k padding ids (the last k live rows, descending): after every mask or k change
-int refresh_pad_ids(hvs_ctx* c)
-{
-    if (!c->d_pad_ids || c->h_live.empty()) return HVS_OK;
-    uint32_t pad[HVS_KMAX];
-    hvs_mask_plan(c->h_live.data(), c->n, c->k, 1.0f, nullptr, nullptr, pad);
-    HVS_HIP(c, hipMemcpyAsync(c->d_pad_ids, pad, (size_t)c->k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`pad` is on this stack)
-    return HVS_OK;
-}
-
-// The index-validity mask of a context with stale rows (hvs_ctx::d_ilive), from the host's mask and stale list; room for it
-// was secured by leaf_update_prepare.  No stale rows: nothing to do, index_mask(c) is d_live.
-int refresh_index_mask(hvs_ctx* c)
-{
-    if (c->h_stale.empty()) return HVS_OK;
-    const size_t W = 2u * (((size_t)c->n_indexed + 63u) / 64u);
-    if (!c->d_ilive || 2u * W > c->ilive_cap) return fail(c, HVS_ESTATE, "internal: no room for the index-validity mask");
-    std::vector<uint32_t> w(2u * W, 0u);
-    for (size_t i = 0; i < W; ++i) {
-        const uint64_t v = (i >> 1) < c->h_live.size() ? c->h_live[i >> 1] : 0ull;
-        w[i] = w[W + i] = (uint32_t)(v >> (32u * (i & 1u)));
-    }
-    if (c->n_indexed & 63u) {  // (bits of the tail's rows in the last word: not the index's business)
-        const uint64_t keep = (1ull << (c->n_indexed & 63u)) - 1ull;
-        w[W - 2u] &= (uint32_t)keep, w[W - 1u] &= (uint32_t)(keep >> 32);
-        w[2u * W - 2u] &= (uint32_t)keep, w[2u * W - 1u] &= (uint32_t)(keep >> 32);
-    }
-    for (uint32_t id : c->h_stale) w[id >> 5] &= ~(1u << (id & 31u));
-    HVS_HIP(c, hipMemcpyAsync(c->d_ilive, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (`w` goes with this scope)
-    return HVS_OK;
-}
-
+// ---- live-row mask ----
 // Install `words` (ceil(n / 64) words, bits past n clear, n_live bits set: checked by the caller) as the context's mask.
 // `del_ids` (host, ids < n): the new mask is the old one less these rows -- applied on the device by hvs_k_mask_delete
-// instead of a whole-mask upload.  Tiles: rows that died are patched; a mask that revives rows rebuilds the tiles through
-// build_tiles, which patches at its end.
+// instead of a whole-mask upload.
 int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_live, const uint32_t* del_ids, uint32_t del_count)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);  // an earlier call's re-runs belong to the mask they were asked under
+    HvsRowSet& s = c->rs;
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
     const size_t bytes = words.size() * sizeof(uint64_t);
-    if (!c->d_pad_ids && (rc = dev_alloc(c, &c->d_pad_ids, (size_t)HVS_KMAX))) return rc;
-    if (!c->d_mask_stat) {
-        if ((rc = dev_alloc(c, &c->d_mask_stat, (size_t)2))) return rc;
-        HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    if (!s.d_pad_ids && (rc = dev_alloc(c, &s.d_pad_ids, (size_t)HVS_KMAX))) return rc;
+    if (!s.d_mask_stat) {
+        if ((rc = dev_alloc(c, &s.d_mask_stat, (size_t)2))) return rc;
+        HVS_HIP(c, hipMemsetAsync(s.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     }
-    if (c->h_live.empty()) c->h_live = all_live_words(c->n);
+    if (s.h_live.empty()) s.h_live = all_live_words(c->n);
     bool fresh = false;
-    if (!c->d_live) {
-        const size_t cap64 = std::max(words.size(), ((size_t)c->n_cap + 63u) / 64u);  // (room for the rows D has room for)
-        if ((rc = dev_alloc(c, &c->d_live, cap64 * 2u))) return rc;
-        c->live_cap = (uint32_t)cap64;
+    if (!s.d_live) {
+        const size_t cap64 = std::max(words.size(), mask_words(s.n_cap));  // (room for the rows D has room for)
+        if ((rc = dev_alloc(c, &s.d_live, cap64 * 2u))) return rc;
+        s.live_cap = (uint32_t)cap64;
         fresh = true;
     }
     bool revived = false;
-    for (size_t i = 0; i < words.size(); ++i) revived = revived || (words[i] & ~c->h_live[i]) != 0ull;
+    for (size_t i = 0; i < words.size(); ++i) revived = revived || (words[i] & ~s.h_live[i]) != 0ull;
     if (del_ids) {
-        if (fresh) HVS_HIP(c, hipMemcpyAsync(c->d_live, c->h_live.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        if (del_count > c->mask_ids_cap) {
-            c->mask_ids_cap = 0;
-            if ((rc = dev_alloc(c, &c->d_mask_ids, (size_t)del_count))) return rc;
-            c->mask_ids_cap = del_count;
+        if (fresh) HVS_HIP(c, hipMemcpyAsync(s.d_live, s.h_live.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        if (del_count > s.mask_ids_cap) {
+            s.mask_ids_cap = 0;
+            if ((rc = dev_alloc(c, &s.d_mask_ids, (size_t)del_count))) return rc;
+            s.mask_ids_cap = del_count;
         }
-        HVS_HIP(c, hipMemcpyAsync(c->d_mask_ids, del_ids, (size_t)del_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(hvs_k_mask_delete, dim3(hvs_ceil_div(del_count, 256u)), dim3(256), 0, c->stream, c->d_mask_ids, del_count, c->d_live);
+        HVS_HIP(c, hipMemcpyAsync(s.d_mask_ids, del_ids, (size_t)del_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(hvs_k_mask_delete, dim3(hvs_ceil_div(del_count, 256u)), dim3(256), 0, c->stream, s.d_mask_ids, del_count, s.d_live);
         HVS_HIP(c, hipGetLastError());
     } else {
-        HVS_HIP(c, hipMemcpyAsync(c->d_live, words.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        HVS_HIP(c, hipMemcpyAsync(s.d_live, words.data(), bytes, hipMemcpyHostToDevice, c->stream));
     }
     HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the sources are the caller's)
-    c->h_live = words;
-    c->n_dead = c->n - n_live;
-    c->cut_valid = false;
-    c->lp_valid = false;
-    if ((rc = refresh_index_mask(c))) return rc;  // (rows are stale: live AND NOT stale follows the new mask)
-    if (c->fmt.built != HVS_FMT_NONE) {
-        if (revived) {
-            if ((rc = build_tiles(c, c->fmt.built))) return rc;
-        } else if ((rc = patch_tiles(c))) {
-            return rc;
-        }
-    }
-    if ((rc = refresh_pad_ids(c))) return rc;
+    s.h_live = words;
+    s.n_dead = c->n - n_live;
+    if ((rc = row_set_changed(c, revived ? RowChange::MaskRevivedRows : RowChange::MaskLostRows))) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return HVS_OK;
 }
@@ -2625,13 +2710,13 @@ int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
 {
     int rc = leaf_sync(c);
     if (rc) return rc;
-    out->n_live = c->n - c->n_dead;
-    out->n_dead = c->n_dead;
+    out->n_live = c->n - c->rs.n_dead;
+    out->n_dead = c->rs.n_dead;
     out->tiles_patched = 0;
     out->dead_survivors = 0;
     unsigned long long v = 0;
-    if (c->d_mask_stat) {
-        HVS_HIP(c, hipMemcpy(&v, c->d_mask_stat, sizeof(v), hipMemcpyDeviceToHost));
+    if (c->rs.d_mask_stat) {
+        HVS_HIP(c, hipMemcpy(&v, c->rs.d_mask_stat, sizeof(v), hipMemcpyDeviceToHost));
         out->tiles_patched = v;
     }
     if (c->timing_valid) {
@@ -2641,51 +2726,23 @@ int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
     return HVS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// appended rows
-// ---------------------------------------------------------------------------------------------
-// n_tail + n_stale (the limit is shared with the updated rows) above which an append or an update re-indexes
-// before it returns.  Default max(4096, n_indexed >> 10), derived and not yet
-// measured: if the tail scan evaluated pairs at the exact engine's rate, ~3.1 x 10^11 pairs/s on record, and the
-// filter engines answer a query of the flagship shape in ~310 ns, 10^4 tail rows (n_indexed = 10^7) cost ~32 ns, a tenth of
-// a query.
-uint32_t tail_limit_of(const hvs_ctx* c) { return c->tail_limit ? c->tail_limit : std::max(4096u, c->n_indexed >> 10); }
-uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
+// ---- appended rows ----
 
-// room for n_cap rows in D and in the device mask, contents kept (device-to-device copies); nothing a query sees changes
+// room for n_cap rows in D and in the device mask, contents kept; nothing a query sees changes
 int leaf_reserve_rows(hvs_ctx* c, uint32_t n_cap)
 {
+    HvsRowSet& s = c->rs;
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);  // an earlier call's re-runs read D
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    if (n_cap > c->n_cap) {
-        float* bigger = nullptr;
-        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), (size_t)n_cap * HVS_DCOLS * sizeof(float)));
-        hipError_t e = hipMemcpyAsync(bigger, c->d_data, (size_t)c->n * HVS_DCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(bigger);
-            return fail(c, HVS_EHIP, std::string("hvs_reserve_rows: moving D: ") + hipGetErrorString(e));
-        }
-        (void)hipFree(c->d_data);
-        c->d_data = bigger;
-        c->n_cap = n_cap;
+    if (n_cap > s.n_cap) {
+        if ((rc = grow_keep(c, &c->d_data, (size_t)n_cap * HVS_DCOLS, (size_t)c->n * HVS_DCOLS, "hvs_reserve_rows: moving D: "))) return rc;
+        s.n_cap = n_cap;
     }
-    const size_t cap64 = ((size_t)c->n_cap + 63u) / 64u;
-    if (c->d_live && cap64 > c->live_cap) {
-        uint32_t* bigger = nullptr;
-        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), cap64 * sizeof(uint64_t)));
-        hipError_t e = hipMemcpyAsync(bigger, c->d_live, (((size_t)c->n + 63u) / 64u) * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(bigger);
-            return fail(c, HVS_EHIP, std::string("hvs_reserve_rows: moving the mask: ") + hipGetErrorString(e));
-        }
-        (void)hipFree(c->d_live);
-        c->d_live = bigger;
-        c->live_cap = (uint32_t)cap64;
+    const size_t cap64 = mask_words(s.n_cap);
+    if (s.d_live && cap64 > s.live_cap) {  // (u32 words on the device: two to a word)
+        if ((rc = grow_keep(c, &s.d_live, cap64 * 2u, mask_words(c->n) * 2u, "hvs_reserve_rows: moving the mask: "))) return rc;
+        s.live_cap = (uint32_t)cap64;
     }
     return HVS_OK;
 }
@@ -2695,8 +2752,8 @@ int leaf_reserve_rows(hvs_ctx* c, uint32_t n_cap)
 int leaf_append_prepare(hvs_ctx* c, uint32_t count)
 {
     const uint32_t need = c->n + count;  // (no overflow: checked by the caller)
-    uint32_t want = c->n_cap;
-    if (need > c->n_cap) want = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(need, (uint64_t)c->n_cap + c->n_cap / 2u));
+    uint32_t want = c->rs.n_cap;
+    if (need > c->rs.n_cap) want = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(need, (uint64_t)c->rs.n_cap + c->rs.n_cap / 2u));
     int rc = leaf_reserve_rows(c, want);
     if (rc == HVS_ENOMEM && want > need) {  // no room for the growth step: exactly what is needed
         (void)hipGetLastError();
@@ -2706,16 +2763,15 @@ int leaf_append_prepare(hvs_ctx* c, uint32_t count)
     return rc;
 }
 
-// fold the tail into the index: the load's own index build over all rows (the mask is re-applied by build_tiles' patch)
+// fold the tail and the stale rows into the index: the load's own index build over all rows (the mask is re-applied by
+// build_tiles' patch)
 int leaf_reindex(hvs_ctx* c, bool force)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
-    if (!force && tail_rows(c) == 0u && c->h_stale.empty()) return HVS_OK;
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);
+    if (!force && tail_rows(c) == 0u && c->rs.h_stale.empty()) return HVS_OK;
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    c->h_stale.clear();  // (the new index describes every row as it is now)
+    c->rs.h_stale.clear();  // (the new index describes every row as it is now)
     // (the live-row counts run along positions: their buffers are sized by the index that goes)
     if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
     if ((rc = dev_alloc(c, &c->ord[1].lp, (size_t)0))) return rc;
@@ -2724,42 +2780,44 @@ int leaf_reindex(hvs_ctx* c, bool force)
     rc = index_data(c);
     c->load_ms = load_ms;
     if (rc) return rc;
-    c->reindexes += 1u;
-    c->reindex_ms = c->index_ms;
+    c->rs.reindexes += 1u;
+    c->rs.reindex_ms = c->index_ms;
+    return HVS_OK;
+}
+
+// The one rule by which an append or an update ends with an index build: the rows behind the index plus the stale rows have
+// outgrown the limit, and an index may be built at all (there is one; or the rule of a load allows a first one)
+int fold_if_over_limit(hvs_ctx* c)
+{
+    const bool can_index = c->have_order || ((c->n >= kIndexMinRows || is_filter_engine(c->engine)) && !c->index_too_large);
+    if (can_index && (uint64_t)rows_behind_index(c) + c->rs.h_stale.size() > tail_limit_of(c)) return leaf_reindex(c, true);
     return HVS_OK;
 }
 
 // second half: the rows, the mask bits, n -- and the index when the tail has outgrown its limit
 int leaf_append_commit(hvs_ctx* c, const float* rows, uint32_t count)
 {
+    HvsRowSet& s = c->rs;
     HVS_HIP(c, hipSetDevice(c->device));
     const uint32_t n_old = c->n, n_new = n_old + count;
     int rc = upload_rows(c, c->d_data + (size_t)n_old * HVS_DCOLS, rows, (size_t)count * HVS_DCOLS);
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    if (!c->h_live.empty()) {  // a mask has been set: the new rows start live
-        std::vector<uint64_t> words = c->h_live;
-        words.resize(((size_t)n_new + 63u) / 64u, 0ull);
-        for (uint32_t i = n_old; i < n_new;) {
-            const uint32_t w = i >> 6, b = i & 63u, m = std::min(64u - b, n_new - i);
-            words[w] |= (m == 64u ? ~0ull : ((1ull << m) - 1ull)) << b;
-            i += m;
-        }
-        if (c->d_live) {
+    if (!s.h_live.empty()) {  // a mask has been set: the new rows start live
+        std::vector<uint64_t> words = s.h_live;
+        words.resize(mask_words(n_new), 0ull);
+        mask_set_range(words, n_old, n_new);
+        if (s.d_live) {
             const size_t w0 = n_old >> 6;
-            HVS_HIP(c, hipMemcpyAsync(reinterpret_cast<uint64_t*>(c->d_live) + w0, words.data() + w0, (words.size() - w0) * sizeof(uint64_t),
+            HVS_HIP(c, hipMemcpyAsync(reinterpret_cast<uint64_t*>(s.d_live) + w0, words.data() + w0, (words.size() - w0) * sizeof(uint64_t),
                                       hipMemcpyHostToDevice, c->stream));
             HVS_HIP(c, hipStreamSynchronize(c->stream));
         }
-        c->h_live.swap(words);
+        s.h_live.swap(words);
     }
     c->n = n_new;
-    c->cut_valid = false;  // (the live-row counts along the orderings stand: they cover indexed positions only)
-    if ((rc = refresh_pad_ids(c))) return rc;
-    const bool can_index = c->have_order || ((n_new >= kIndexMinRows || is_filter_engine(c->engine)) && !c->index_too_large);
-    const uint32_t uncovered = c->have_order ? n_new - c->n_indexed : n_new - std::min(n_new, c->index_tried_n);
-    if (can_index && (uint64_t)uncovered + c->h_stale.size() > tail_limit_of(c)) return leaf_reindex(c, true);  // (the limit is shared)
-    return HVS_OK;
+    if ((rc = row_set_changed(c, RowChange::RowsAppended))) return rc;
+    return fold_if_over_limit(c);
 }
 
 int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
@@ -2770,8 +2828,8 @@ int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
     out->n_indexed = c->n_indexed;
     out->n_tail = tail_rows(c);
     out->tail_limit = tail_limit_of(c);
-    out->reindexes = c->reindexes;
-    out->reindex_ms = c->reindex_ms;
+    out->reindexes = c->rs.reindexes;
+    out->reindex_ms = c->rs.reindex_ms;
     if (c->timing_valid) {
         unsigned long long v[2] = {0, 0};
         HVS_HIP(c, hipMemcpy(v, c->d_counters + 9, sizeof(v), hipMemcpyDeviceToHost));
@@ -2781,52 +2839,37 @@ int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
     return HVS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// updated rows
-// ---------------------------------------------------------------------------------------------
+// ---- updated rows ----
 // first half of an update: every device buffer the second half writes, so that it cannot run out of memory on one GPU of
 // several.  `n_stale_new`: length of the stale list after the update.  Nothing a query sees changes.
 int leaf_update_prepare(hvs_ctx* c, uint32_t count, uint32_t n_stale_new)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);  // an earlier call's re-runs read D as it was
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    if (count > c->upd_cap) {
-        c->upd_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_upd_rows, (size_t)count * HVS_DCOLS))) return rc;
-        if ((rc = dev_alloc(c, &c->d_upd_ids, (size_t)count))) return rc;
-        if ((rc = dev_alloc(c, &c->d_upd_from, (size_t)count))) return rc;
-        c->upd_cap = count;
+    if (count > c->rs.upd_cap) {
+        c->rs.upd_cap = 0;
+        if ((rc = dev_alloc(c, &c->rs.d_upd_rows, (size_t)count * HVS_DCOLS))) return rc;
+        if ((rc = dev_alloc(c, &c->rs.d_upd_ids, (size_t)count))) return rc;
+        if ((rc = dev_alloc(c, &c->rs.d_upd_from, (size_t)count))) return rc;
+        c->rs.upd_cap = count;
     }
-    if (n_stale_new <= c->h_stale.size()) return HVS_OK;  // no row becomes stale
+    if (n_stale_new <= c->rs.h_stale.size()) return HVS_OK;  // no row becomes stale
     // the masked kernels are about to run: the mask's own buffers (an all-live mask where none has been set)
-    if (c->h_live.empty() || !c->d_live || !c->d_pad_ids || !c->d_mask_stat) {
-        const std::vector<uint64_t> words = c->h_live.empty() ? all_live_words(c->n) : c->h_live;
-        if ((rc = leaf_apply_mask(c, words, c->n - c->n_dead, nullptr, 0u))) return rc;
+    if (c->rs.h_live.empty() || !c->rs.d_live || !c->rs.d_pad_ids || !c->rs.d_mask_stat) {
+        const std::vector<uint64_t> words = c->rs.h_live.empty() ? all_live_words(c->n) : c->rs.h_live;
+        if ((rc = leaf_apply_mask(c, words, c->n - c->rs.n_dead, nullptr, 0u))) return rc;
     }
-    if (n_stale_new > c->stale_cap) {  // (the new buffer first: a failure leaves the old list in place)
-        const uint32_t want = (uint32_t)std::min<uint64_t>(c->n_indexed, std::max<uint64_t>(n_stale_new, 2ull * c->stale_cap));
-        uint32_t* bigger = nullptr;
-        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&bigger), (size_t)want * sizeof(uint32_t)));
-        hipError_t e = hipSuccess;
-        if (!c->h_stale.empty()) {
-            e = hipMemcpyAsync(bigger, c->h_stale.data(), c->h_stale.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(bigger);
-            return fail(c, HVS_EHIP, std::string("hvs_update_rows: moving the stale list: ") + hipGetErrorString(e));
-        }
-        if (c->d_stale_ids) (void)hipFree(c->d_stale_ids);
-        c->d_stale_ids = bigger;
-        c->stale_cap = want;
+    if (n_stale_new > c->rs.stale_cap) {
+        const uint32_t want = (uint32_t)std::min<uint64_t>(c->n_indexed, std::max<uint64_t>(n_stale_new, 2ull * c->rs.stale_cap));
+        // (the list is kept: this call may end before its second half, e.g. for want of room on another GPU)
+        if ((rc = grow_keep(c, &c->rs.d_stale_ids, (size_t)want, c->rs.h_stale.size(), "hvs_update_rows: moving the stale list: ", c->rs.h_stale.data()))) return rc;
+        c->rs.stale_cap = want;
     }
-    const size_t words2 = 4u * (((size_t)c->n_indexed + 63u) / 64u);  // two planes
-    if (words2 > c->ilive_cap) {  // (only while no row is stale: n_indexed does not change while one is)
-        c->ilive_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_ilive, words2))) return rc;
-        c->ilive_cap = (uint32_t)words2;
+    const size_t words2 = 4u * mask_words(c->n_indexed);  // two planes
+    if (words2 > c->rs.ilive_cap) {  // (only while no row is stale: n_indexed does not change while one is)
+        c->rs.ilive_cap = 0;
+        if ((rc = dev_alloc(c, &c->rs.d_ilive, words2))) return rc;
+        c->rs.ilive_cap = (uint32_t)words2;
     }
     return HVS_OK;
 }
@@ -2838,24 +2881,22 @@ int leaf_update_commit(hvs_ctx* c, const float* rows, uint32_t count, const uint
                        const std::vector<uint32_t>& stale_new)
 {
     HVS_HIP(c, hipSetDevice(c->device));
-    int rc = upload_rows(c, c->d_upd_rows, rows, (size_t)count * HVS_DCOLS);
+    int rc = upload_rows(c, c->rs.d_upd_rows, rows, (size_t)count * HVS_DCOLS);
     if (rc) return rc;
-    HVS_HIP(c, hipMemcpyAsync(c->d_upd_ids, uids, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HVS_HIP(c, hipMemcpyAsync(c->d_upd_from, from, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(c->rs.d_upd_ids, uids, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(c->rs.d_upd_from, from, (size_t)nu * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     const uint64_t nelem = (uint64_t)nu * HVS_DCOLS;
-    hipLaunchKernelGGL(hvs_k_scatter_rows, dim3((uint32_t)((nelem + 255u) / 256u)), dim3(256), 0, c->stream, c->d_upd_rows, c->d_upd_ids,
-                       c->d_upd_from, nu, c->d_data);
+    hipLaunchKernelGGL(hvs_k_scatter_rows, dim3((uint32_t)((nelem + 255u) / 256u)), dim3(256), 0, c->stream, c->rs.d_upd_rows, c->rs.d_upd_ids,
+                       c->rs.d_upd_from, nu, c->d_data);
     HVS_HIP(c, hipGetLastError());
-    if (stale_new.size() > c->h_stale.size()) {
-        HVS_HIP(c, hipMemcpyAsync(c->d_stale_ids, stale_new.data(), stale_new.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        c->h_stale = stale_new;
-        c->lp_valid = false;  // (the counts of valid rows along the orderings: rebuilt on first use, as after a mask change)
-        if ((rc = refresh_index_mask(c))) return rc;
-        if ((rc = patch_tiles(c))) return rc;
+    if (stale_new.size() > c->rs.h_stale.size()) {
+        HVS_HIP(c, hipMemcpyAsync(c->rs.d_stale_ids, stale_new.data(), stale_new.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        c->rs.h_stale = stale_new;
+        if ((rc = row_set_changed(c, RowChange::StaleGrew))) return rc;
     }
     HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the sources are the caller's)
-    if (c->have_order && (uint64_t)tail_rows(c) + c->h_stale.size() > tail_limit_of(c)) return leaf_reindex(c, true);
-    return HVS_OK;
+    // (without orderings no row is stale and an update never builds the first index: that is an append's or hvs_reindex's to do)
+    return c->have_order ? fold_if_over_limit(c) : HVS_OK;
 }
 
 int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
@@ -2863,7 +2904,7 @@ int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
     int rc = leaf_sync(c);
     if (rc) return rc;
     *out = hvs_update_info{};
-    out->n_stale = (uint32_t)c->h_stale.size();
+    out->n_stale = (uint32_t)c->rs.h_stale.size();
     out->limit = tail_limit_of(c);
     if (c->timing_valid) {
         unsigned long long v[3] = {0, 0, 0};
@@ -2875,35 +2916,27 @@ int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
     return HVS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// row compaction
-// ---------------------------------------------------------------------------------------------
+// ---- row compaction ----
 // source rows per gather launch and rows of the bounce buffer; HVS_COMPACT_CHUNK overrides, read per call (any value >= 1)
 uint32_t compact_chunk() { return env_u32("HVS_COMPACT_CHUNK", 65536u, 1u, 0xFFFFFFFFu); }
 
-void compact_free_scratch(hvs_ctx* c)
+int free_call_scratch(hvs_ctx* c)  // of hvs_compact / hvs_trim_rows
 {
     (void)hipSetDevice(c->device);
-    if (c->d_cmp_bounce) (void)hipFree(c->d_cmp_bounce);
-    if (c->d_cmp_rank) (void)hipFree(c->d_cmp_rank);
-    if (c->d_trim) (void)hipFree(c->d_trim);
-    c->d_cmp_bounce = nullptr;
-    c->d_cmp_rank = nullptr;
-    c->d_trim = nullptr;
+    c->rs.free_call_buffers();
+    return HVS_OK;
 }
 
 // first half of a compaction: the earlier call's re-runs (they belong to the mask and the ids they were asked under) and the
 // two scratch buffers, so that the second half cannot run out of memory on one GPU of several.  Nothing a query sees changes.
 int leaf_compact_prepare(hvs_ctx* c, uint32_t first_dead, uint32_t chunk)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    if (!c->d_live) return fail(c, HVS_ESTATE, "internal: rows are dead and the device mask is missing");
+    if (!c->rs.d_live) return fail(c, HVS_ESTATE, "internal: rows are dead and the device mask is missing");
     const uint32_t bounce_rows = std::min(chunk, c->n - first_dead);
-    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cmp_bounce), (size_t)bounce_rows * HVS_DCOLS * sizeof(float)));
-    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cmp_rank), (((size_t)c->n + 31u) / 32u) * sizeof(uint32_t)));
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_cmp_bounce), (size_t)bounce_rows * HVS_DCOLS * sizeof(float)));
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_cmp_rank), (((size_t)c->n + 31u) / 32u) * sizeof(uint32_t)));
     return HVS_OK;
 }
 
@@ -2917,10 +2950,9 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     const uint32_t n = c->n;
     auto live_before = [&](uint32_t id) -> uint32_t {  // live rows with an id below `id` (id <= n)
         if (id == n) return n_live;
-        const uint64_t word = c->h_live[id >> 6] >> (32u * ((id >> 5) & 1u));
-        return rank[id >> 5] + (uint32_t)__builtin_popcount((uint32_t)word & ((1u << (id & 31u)) - 1u));
+        return rank[id >> 5] + (uint32_t)__builtin_popcount(mask_half(c->rs.h_live[id >> 6], id >> 5) & ((1u << (id & 31u)) - 1u));
     };
-    HVS_HIP(c, hipMemcpyAsync(c->d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(c->rs.d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     // HVS_TRACE: the gathers' and the copies' device time apart (an event between the two of every chunk)
     std::vector<hipEvent_t> ev_mid;
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
@@ -2936,11 +2968,11 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
             ev_mid.push_back(e[1]);
         }
         hipLaunchKernelGGL(hvs_k_compact_gather, dim3(hvs_ceil_div(words, 4u)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const uint2*>(c->d_data), c->d_live, c->d_cmp_rank, a, b, ra, c->d_cmp_bounce);
+                           reinterpret_cast<const uint2*>(c->d_data), c->rs.d_live, c->rs.d_cmp_rank, a, b, ra, c->rs.d_cmp_bounce);
         HVS_HIP(c, hipGetLastError());
         if (kTrace && ev_mid.back()) (void)hipEventRecord(ev_mid.back(), c->stream);
         if (rb > ra)
-            HVS_HIP(c, hipMemcpyAsync(c->d_data + (size_t)ra * HVS_DCOLS, c->d_cmp_bounce, (size_t)(rb - ra) * HVS_DCOLS * sizeof(float),
+            HVS_HIP(c, hipMemcpyAsync(c->d_data + (size_t)ra * HVS_DCOLS, c->rs.d_cmp_bounce, (size_t)(rb - ra) * HVS_DCOLS * sizeof(float),
                                       hipMemcpyDeviceToDevice, c->stream));
     }
     HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
@@ -2958,27 +2990,22 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
         std::fprintf(stderr, "[hvs trace] hvs_compact n=%u live=%u chunks=%u: move %.3f ms, gathers %.3f ms, copies %.3f ms\n", n, n_live, chunks,
                      ms, gather_ms, ms - gather_ms);
     }
-    compact_free_scratch(c);
-    c->cstat.compactions += 1u;
-    c->cstat.n_before = n;
-    c->cstat.n_after = n_live;
-    c->cstat.first_moved = first_dead;
-    c->cstat.chunks = chunks;
-    c->cstat.rows_moved = (uint64_t)n_live - first_dead;  // (every id below the first dead one is live)
-    c->cstat.move_ms = ms;
-    // what a fresh load of these rows leaves: every row live and no mask set, no stale row, no earlier result
+    free_call_scratch(c);
+    c->rs.cstat.compactions += 1u;
+    c->rs.cstat.n_before = n;
+    c->rs.cstat.n_after = n_live;
+    c->rs.cstat.first_moved = first_dead;
+    c->rs.cstat.chunks = chunks;
+    c->rs.cstat.rows_moved = (uint64_t)n_live - first_dead;  // (every id below the first dead one is live)
+    c->rs.cstat.move_ms = ms;
+    // from here on the state of a fresh load of the live rows, in the room D has (n_cap stays)
     c->n = n_live;
-    c->h_live.clear();
-    c->n_dead = 0;
-    c->live_cap = 0;
-    int rc = dev_alloc(c, &c->d_live, (size_t)0);  // (as after a load: the next mask call allocates it, all live, for the new n)
+    int rc = reset_row_set(c);
     if (rc) return rc;
-    if (c->d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
-    if ((rc = refresh_pad_ids(c))) return rc;  // (no mask: nothing reads the table; the next mask call fills it)
-    c->h_stale.clear();
-    c->index_tried_n = 0;
-    c->cut_valid = false;
-    c->lp_valid = false;
+    // a compaction, unlike a load, keeps the data set's figures (reindexes, reindex_ms; cstat it has just bumped), starts the
+    // count of patched tile entries over even where no tile build will, and leaves no earlier call's timing to ask for.
+    // NOTE: a load does neither of the last two; whether that is meant is not recorded (hvs_mask_info.tiles_patched, hvs_last_timing)
+    if (c->rs.d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->rs.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     c->timing_valid = false;
     // one index over all rows -- or none, by the rule of a load (fewer than 4096 rows, or no room for one)
     if (c->n >= kIndexMinRows || is_filter_engine(c->engine)) return leaf_reindex(c, true);
@@ -2989,25 +3016,23 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
 // hvs_trim_rows, first half: the smaller buffer; second half: the rows, and the swap
 int leaf_trim_prepare(hvs_ctx* c)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);  // an earlier call's re-runs read D
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->n_cap == c->n) return HVS_OK;
-    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_trim), (size_t)c->n * HVS_DCOLS * sizeof(float)));
+    if (c->rs.n_cap == c->n) return HVS_OK;
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_trim), (size_t)c->n * HVS_DCOLS * sizeof(float)));
     return HVS_OK;
 }
 
 int leaf_trim_commit(hvs_ctx* c)
 {
-    if (!c->d_trim) return HVS_OK;
+    if (!c->rs.d_trim) return HVS_OK;
     HVS_HIP(c, hipSetDevice(c->device));
-    HVS_HIP(c, hipMemcpyAsync(c->d_trim, c->d_data, (size_t)c->n * HVS_DCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(c->rs.d_trim, c->d_data, (size_t)c->n * HVS_DCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     (void)hipFree(c->d_data);
-    c->d_data = c->d_trim;
-    c->d_trim = nullptr;
-    c->n_cap = c->n;
+    c->d_data = c->rs.d_trim;
+    c->rs.d_trim = nullptr;
+    c->rs.n_cap = c->n;
     return HVS_OK;
 }
 
@@ -3114,6 +3139,48 @@ int on_every_leaf(hvs_ctx* c, Fn fn)
 {
     if (c->kids.empty()) return fn(c);
     return for_each_leaf(c, [&](uint32_t r) { return fn(c->kids[r]); });
+}
+
+// the leaf whose row-set state speaks for the whole context (rows, mask and index are replicated)
+const hvs_ctx* mask_leaf(const hvs_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
+// ... for an entry point `fn` that needs a data set; nullptr (HVS_ESTATE, with the error text set) when there is none
+const hvs_ctx* loaded_leaf(hvs_ctx* c, const char* fn)
+{
+    const hvs_ctx* L = mask_leaf(c);
+    if (!L->d_data || !L->n) fail(c, HVS_ESTATE, std::string(fn) + ": no data set loaded");
+    return L->d_data && L->n ? L : nullptr;
+}
+
+// A change in two halves: `prepare` secures on every GPU what `commit` needs before any GPU changes, so a failure so far
+// leaves every context as it was.  `cleanup`, where there is one, frees the call's scratch on every GPU whichever way the
+// call ends.  A failed call's error is taken off HIP's last-error slot.
+template <typename Prepare, typename Commit>
+int two_phase(hvs_ctx* c, Prepare prepare, Commit commit, int (*cleanup)(hvs_ctx*) = nullptr)
+{
+    int rc = on_every_leaf(c, prepare);
+    if (!rc) rc = on_every_leaf(c, commit);
+    if (cleanup) (void)on_every_leaf(c, cleanup);
+    if (rc) (void)hipGetLastError();  // (HIP's last error is the failed call's: the next call must not trip over it)
+    return rc;
+}
+
+// Figures of a multi-GPU context: leaf 0's view (rows, mask and index are replicated) plus, through `add(sum, leaf's)`, the
+// other leaves' work counters of the last call, summed like hvs_timing's
+template <typename Info, typename Add>
+int leaf0_stats(hvs_ctx* c, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add add)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_stats(c, out);
+    Info agg{};
+    for (size_t r = 0; r < c->kids.size(); ++r) {
+        Info m{};
+        const int rc = leaf_stats(c->kids[r], &m);
+        if (rc) return fail(c, rc, c->kids[r]->err);
+        if (r == 0u) agg = m;
+        else add(agg, m);
+    }
+    *out = agg;
+    return HVS_OK;
 }
 
 }  // namespace
@@ -3280,12 +3347,10 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
         if (!rc) c->k = k;
         return rc;
     }
-    if (c->n && c->n - c->n_dead < k) return fail(c, HVS_EINVAL, "hvs_set_k: the loaded data set has fewer than k (live) rows");
+    if (c->n && c->n - c->rs.n_dead < k) return fail(c, HVS_EINVAL, "hvs_set_k: the loaded data set has fewer than k (live) rows");
     if (k == c->k) return HVS_OK;
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);
+    int rc = begin_mutation(c);
     if (rc) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->k = k;
     c->cap = k <= 128u ? 256 : 512;
     // result rows change size: resident queries stay, their results do not; list workspaces are re-sized on demand
@@ -3293,7 +3358,7 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
     c->res_cap = 0;
     c->cand_lists = 0;
     c->timing_valid = false;
-    c->cut_valid = false;
+    c->rs.cut_valid = false;
     if ((rc = refresh_pad_ids(c))) return rc;
     return had ? ensure_results(c, had) : HVS_OK;
 }
@@ -3624,17 +3689,9 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
 void hvs_mask_plan(const uint64_t* live_bits, uint32_t n, uint32_t k, float sample_proportion, uint32_t* n_live, uint32_t* cut,
                    uint32_t* pad_ids)
 {
-    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) / 64u);
-    auto word = [&](uint32_t w) -> uint64_t {
-        uint64_t v = live_bits ? live_bits[w] : ~0ull;
-        if (w == words - 1u && (n & 63u)) v &= (1ull << (n & 63u)) - 1ull;
-        return v;
-    };
-    uint32_t nl = n;
-    if (live_bits) {
-        nl = 0;
-        for (uint32_t w = 0; w < words; ++w) nl += (uint32_t)__builtin_popcountll(word(w));
-    }
+    const uint32_t words = (uint32_t)mask_words(n);
+    auto word = [&](uint32_t w) { return masked_word(live_bits, n, w); };
+    const uint32_t nl = live_bits ? mask_popcount(live_bits, n) : n;
     if (n_live) *n_live = nl;
     if (cut) {
         const uint32_t sn_live = sample_rows(sample_proportion, nl);
@@ -3668,8 +3725,6 @@ void hvs_mask_plan(const uint64_t* live_bits, uint32_t n, uint32_t k, float samp
     }
 }
 
-static hvs_ctx* mask_leaf(hvs_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
-
 static int apply_mask_everywhere(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_live, const uint32_t* del_ids,
                                  uint32_t del_count)
 {
@@ -3680,13 +3735,12 @@ static int apply_mask_everywhere(hvs_ctx* c, const std::vector<uint64_t>& words,
 int hvs_set_row_mask(hvs_ctx* c, const uint64_t* live_bits)
 {
     if (!c) return HVS_EINVAL;
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_set_row_mask: no data set loaded");
+    const hvs_ctx* L = loaded_leaf(c, "hvs_set_row_mask");
+    if (!L) return HVS_ESTATE;
     std::vector<uint64_t> words = all_live_words(L->n);
     if (live_bits)
         for (size_t i = 0; i < words.size(); ++i) words[i] &= live_bits[i];
-    uint32_t n_live = 0;
-    for (uint64_t w : words) n_live += (uint32_t)__builtin_popcountll(w);
+    const uint32_t n_live = mask_popcount(words.data(), L->n);
     if (n_live < L->k) return fail(c, HVS_EINVAL, "hvs_set_row_mask: the mask leaves fewer than k live rows");
     return apply_mask_everywhere(c, words, n_live, nullptr, 0u);
 }
@@ -3694,16 +3748,15 @@ int hvs_set_row_mask(hvs_ctx* c, const uint64_t* live_bits)
 int hvs_delete_rows(hvs_ctx* c, const uint32_t* ids, uint32_t count)
 {
     if (!c) return HVS_EINVAL;
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_delete_rows: no data set loaded");
+    const hvs_ctx* L = loaded_leaf(c, "hvs_delete_rows");
+    if (!L) return HVS_ESTATE;
     if (count && !ids) return fail(c, HVS_EINVAL, "hvs_delete_rows: ids is NULL");
     for (uint32_t i = 0; i < count; ++i)
         if (ids[i] >= L->n) return fail(c, HVS_EINVAL, "hvs_delete_rows: id outside [0, n)");
     if (!count) return HVS_OK;
-    std::vector<uint64_t> words = L->h_live.empty() ? all_live_words(L->n) : L->h_live;
+    std::vector<uint64_t> words = L->rs.h_live.empty() ? all_live_words(L->n) : L->rs.h_live;
     for (uint32_t i = 0; i < count; ++i) words[ids[i] >> 6] &= ~(1ull << (ids[i] & 63u));
-    uint32_t n_live = 0;
-    for (uint64_t w : words) n_live += (uint32_t)__builtin_popcountll(w);
+    const uint32_t n_live = mask_popcount(words.data(), L->n);
     if (n_live < L->k) return fail(c, HVS_EINVAL, "hvs_delete_rows: fewer than k live rows would be left");
     return apply_mask_everywhere(c, words, n_live, ids, count);
 }
@@ -3711,34 +3764,21 @@ int hvs_delete_rows(hvs_ctx* c, const uint32_t* ids, uint32_t count)
 int hvs_get_row_mask(hvs_ctx* c, uint64_t* live_bits)
 {
     if (!c || !live_bits) return HVS_EINVAL;
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_get_row_mask: no data set loaded");
-    const std::vector<uint64_t> words = L->h_live.empty() ? all_live_words(L->n) : L->h_live;
+    const hvs_ctx* L = loaded_leaf(c, "hvs_get_row_mask");
+    if (!L) return HVS_ESTATE;
+    const std::vector<uint64_t> words = L->rs.h_live.empty() ? all_live_words(L->n) : L->rs.h_live;
     std::memcpy(live_bits, words.data(), words.size() * sizeof(uint64_t));
     return HVS_OK;
 }
 
 uint32_t hvs_num_live_rows(const hvs_ctx* c)
 {
-    if (!c) return 0u;
-    const hvs_ctx* L = c->kids.empty() ? c : c->kids[0];
-    return L->n - L->n_dead;
+    return c ? mask_leaf(c)->n - mask_leaf(c)->rs.n_dead : 0u;
 }
 
 int hvs_mask_stats(hvs_ctx* c, hvs_mask_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_mask_stats(c, out);
-    hvs_mask_info agg{};
-    for (size_t r = 0; r < c->kids.size(); ++r) {
-        hvs_mask_info m{};
-        const int rc = leaf_mask_stats(c->kids[r], &m);
-        if (rc) return fail(c, rc, c->kids[r]->err);
-        if (r == 0u) agg = m;  // (the mask and the tiles are replicated: one GPU's view)
-        else agg.dead_survivors += m.dead_survivors;  // a work counter of the call, summed like hvs_timing's
-    }
-    *out = agg;
-    return HVS_OK;
+    return leaf0_stats(c, out, leaf_mask_stats, [](hvs_mask_info& sum, const hvs_mask_info& m) { sum.dead_survivors += m.dead_survivors; });
 }
 
 // ---- appended rows ---------------------------------------------------------------------------
@@ -3756,14 +3796,12 @@ int hvs_append_rows(hvs_ctx* c, const float* rows, uint32_t count, uint32_t* fir
     if (!c) return HVS_EINVAL;
     if (count == 0u) return HVS_OK;
     if (!rows) return fail(c, HVS_EINVAL, "hvs_append_rows: rows is NULL");
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_append_rows: no data set loaded");
+    const hvs_ctx* L = loaded_leaf(c, "hvs_append_rows");
+    if (!L) return HVS_ESTATE;
     if ((uint64_t)L->n + count > 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_append_rows: more than 2^32 - 1 rows");
     const uint32_t first = L->n;
-    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
-    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_append_prepare(k, count); });
+    const int rc = two_phase(c, [&](hvs_ctx* k) { return leaf_append_prepare(k, count); }, [&](hvs_ctx* k) { return leaf_append_commit(k, rows, count); });
     if (rc) return rc;
-    if ((rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_append_commit(k, rows, count); }))) return rc;
     if (first_id) *first_id = first;
     return HVS_OK;
 }
@@ -3771,7 +3809,9 @@ int hvs_append_rows(hvs_ctx* c, const float* rows, uint32_t count, uint32_t* fir
 int hvs_reserve_rows(hvs_ctx* c, uint32_t n_capacity)
 {
     if (!c) return HVS_EINVAL;
-    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reserve_rows(k, n_capacity); });
+    const int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reserve_rows(k, n_capacity); });
+    if (rc) (void)hipGetLastError();  // (as two_phase does)
+    return rc;
 }
 
 int hvs_reindex(hvs_ctx* c)
@@ -3783,29 +3823,17 @@ int hvs_reindex(hvs_ctx* c)
 int hvs_set_tail_limit(hvs_ctx* c, uint32_t rows)
 {
     if (!c) return HVS_EINVAL;
-    c->tail_limit = rows;
-    for (hvs_ctx* k : c->kids) k->tail_limit = rows;
+    c->rs.tail_limit = rows;
+    for (hvs_ctx* k : c->kids) k->rs.tail_limit = rows;
     return HVS_OK;
 }
 
 int hvs_append_stats(hvs_ctx* c, hvs_append_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_append_stats(c, out);
-    hvs_append_info agg{};
-    for (size_t r = 0; r < c->kids.size(); ++r) {
-        hvs_append_info m{};
-        const int rc = leaf_append_stats(c->kids[r], &m);
-        if (rc) return fail(c, rc, c->kids[r]->err);
-        if (r == 0u) {
-            agg = m;  // (rows and index are replicated: one GPU's view)
-        } else {
-            agg.tail_pairs += m.tail_pairs;  // work counters of the call, summed like hvs_timing's
-            agg.tail_admitted += m.tail_admitted;
-        }
-    }
-    *out = agg;
-    return HVS_OK;
+    return leaf0_stats(c, out, leaf_append_stats, [](hvs_append_info& sum, const hvs_append_info& m) {
+        sum.tail_pairs += m.tail_pairs;
+        sum.tail_admitted += m.tail_admitted;
+    });
 }
 
 // ---- updated rows ----------------------------------------------------------------------------
@@ -3838,11 +3866,11 @@ int hvs_update_rows(hvs_ctx* c, const uint32_t* ids, const float* rows, uint32_t
     if (count == 0u) return HVS_OK;
     if (!ids) return fail(c, HVS_EINVAL, "hvs_update_rows: ids is NULL");
     if (!rows) return fail(c, HVS_EINVAL, "hvs_update_rows: rows is NULL");
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_update_rows: no data set loaded");
-    std::vector<uint32_t> stale_new(L->h_stale.size() + (size_t)count);
+    const hvs_ctx* L = loaded_leaf(c, "hvs_update_rows");
+    if (!L) return HVS_ESTATE;
+    std::vector<uint32_t> stale_new(L->rs.h_stale.size() + (size_t)count);
     std::vector<uint8_t> last(count);
-    const uint32_t len = hvs_update_plan(L->h_stale.data(), (uint32_t)L->h_stale.size(), ids, count, L->n_indexed, L->n, stale_new.data(),
+    const uint32_t len = hvs_update_plan(L->rs.h_stale.data(), (uint32_t)L->rs.h_stale.size(), ids, count, L->n_indexed, L->n, stale_new.data(),
                                          last.data());
     if (len == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_update_rows: id outside [0, n)");
     stale_new.resize(len);
@@ -3853,43 +3881,27 @@ int hvs_update_rows(hvs_ctx* c, const uint32_t* ids, const float* rows, uint32_t
             from.push_back(i);
         }
     const uint32_t nu = (uint32_t)uids.size();
-    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
-    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_update_prepare(k, count, len); });
-    if (rc) return rc;
-    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_update_commit(k, rows, count, uids.data(), from.data(), nu, stale_new); });
+    return two_phase(c, [&](hvs_ctx* k) { return leaf_update_prepare(k, count, len); },
+                     [&](hvs_ctx* k) { return leaf_update_commit(k, rows, count, uids.data(), from.data(), nu, stale_new); });
 }
 
 int hvs_update_stats(hvs_ctx* c, hvs_update_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_update_stats(c, out);
-    hvs_update_info agg{};
-    for (size_t r = 0; r < c->kids.size(); ++r) {
-        hvs_update_info m{};
-        const int rc = leaf_update_stats(c->kids[r], &m);
-        if (rc) return fail(c, rc, c->kids[r]->err);
-        if (r == 0u) {
-            agg = m;  // (rows and state are replicated: one GPU's view)
-        } else {
-            agg.stale_pairs += m.stale_pairs;  // work counters of the call, summed like hvs_timing's
-            agg.stale_admitted += m.stale_admitted;
-            agg.stale_survivors += m.stale_survivors;
-        }
-    }
-    *out = agg;
-    return HVS_OK;
+    return leaf0_stats(c, out, leaf_update_stats, [](hvs_update_info& sum, const hvs_update_info& m) {
+        sum.stale_pairs += m.stale_pairs;
+        sum.stale_admitted += m.stale_admitted;
+        sum.stale_survivors += m.stale_survivors;
+    });
 }
 
 // ---- row compaction --------------------------------------------------------------------------
 
 void hvs_compact_plan(const uint64_t* live_bits, uint32_t n, uint32_t* n_live, uint32_t* first_dead, uint32_t* new_to_old)
 {
-    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) / 64u);
+    const uint32_t words = (uint32_t)mask_words(n);
     uint32_t nl = 0, fd = n;
     for (uint32_t w = 0; w < words; ++w) {
-        const uint32_t in_word = w == words - 1u && (n & 63u) ? (n & 63u) : 64u;
-        const uint64_t valid = in_word == 64u ? ~0ull : (1ull << in_word) - 1ull;
-        uint64_t v = (live_bits ? live_bits[w] : ~0ull) & valid;
+        const uint64_t valid = masked_word(nullptr, n, w), v = masked_word(live_bits, n, w);
         if (fd == n && v != valid) fd = w * 64u + (uint32_t)__builtin_ctzll(~v);
         if (new_to_old) {
             for (uint64_t t = v; t; t &= t - 1ull) new_to_old[nl++] = w * 64u + (uint32_t)__builtin_ctzll(t);
@@ -3904,51 +3916,36 @@ void hvs_compact_plan(const uint64_t* live_bits, uint32_t n, uint32_t* n_live, u
 int hvs_compact(hvs_ctx* c, uint32_t* new_to_old)
 {
     if (!c) return HVS_EINVAL;
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_compact: no data set loaded");
+    const hvs_ctx* L = loaded_leaf(c, "hvs_compact");
+    if (!L) return HVS_ESTATE;
     const uint32_t n = L->n;
     uint32_t n_live = 0, first_dead = 0;
-    hvs_compact_plan(L->h_live.empty() ? nullptr : L->h_live.data(), n, &n_live, &first_dead, new_to_old);
+    hvs_compact_plan(L->rs.h_live.empty() ? nullptr : L->rs.h_live.data(), n, &n_live, &first_dead, new_to_old);
     if (n_live == n) return HVS_OK;  // no dead row: nothing changes
     // live rows in front of every 32-row word of the mask
     std::vector<uint32_t> rank(((size_t)n + 31u) / 32u);
     uint32_t seen = 0;
     for (size_t w = 0; w < rank.size(); ++w) {
         rank[w] = seen;
-        seen += (uint32_t)__builtin_popcount((uint32_t)(L->h_live[w >> 1] >> (32u * (w & 1u))));
+        seen += (uint32_t)__builtin_popcount(mask_half(L->rs.h_live[w >> 1], w));
     }
     const uint32_t chunk = compact_chunk();
-    // room on every GPU before any GPU changes: a failure so far leaves every context as it was
-    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_compact_prepare(k, first_dead, chunk); });
-    if (!rc) rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_compact_commit(k, rank, n_live, first_dead, chunk); });
-    (void)on_every_leaf(c, [&](hvs_ctx* k) {
-        compact_free_scratch(k);
-        return HVS_OK;
-    });
-    if (rc) (void)hipGetLastError();
-    return rc;
+    return two_phase(c, [&](hvs_ctx* k) { return leaf_compact_prepare(k, first_dead, chunk); },
+                     [&](hvs_ctx* k) { return leaf_compact_commit(k, rank, n_live, first_dead, chunk); }, free_call_scratch);
 }
 
 int hvs_compact_stats(hvs_ctx* c, hvs_compact_info* out)
 {
     if (!c || !out) return HVS_EINVAL;
-    *out = mask_leaf(c)->cstat;
+    *out = mask_leaf(c)->rs.cstat;
     return HVS_OK;
 }
 
 int hvs_trim_rows(hvs_ctx* c)
 {
     if (!c) return HVS_EINVAL;
-    const hvs_ctx* L = mask_leaf(c);
-    if (!L->d_data || !L->n) return fail(c, HVS_ESTATE, "hvs_trim_rows: no data set loaded");
-    int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_trim_prepare(k); });
-    if (!rc) rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_trim_commit(k); });
-    (void)on_every_leaf(c, [&](hvs_ctx* k) {
-        compact_free_scratch(k);
-        return HVS_OK;
-    });
-    if (rc) (void)hipGetLastError();
-    return rc;
+    if (!loaded_leaf(c, "hvs_trim_rows")) return HVS_ESTATE;
+    return two_phase(c, leaf_trim_prepare, leaf_trim_commit, free_call_scratch);
 }
 
 }  // extern "C"

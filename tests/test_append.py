@@ -442,3 +442,26 @@ def test_errors_leave_the_context_as_it_was(data):
         check(nodes[:N], queries, got[0], got[1], 1.0, 100)
         ids, d = e.query(queries, 1.0)
         check(nodes, queries, ids, d, 1.0, 100, key="gen")
+
+
+def test_no_room_for_the_rows_asked_for(data):
+    """hvs_reserve_rows for 2^32 - 1 rows (1.75 TB of D): HVS_ENOMEM with the failed allocation in the message (the text is that
+    of the one helper every growing buffer goes through), and D, n, the mask and the answers stay as they were -- the new
+    buffer is asked for before the old one is released."""
+    nodes_all, queries = data
+    nodes = nodes_all[:5003]
+    with fresh(EXACT, nodes) as e:
+        live = np.ones(5003, bool)
+        live[::5] = False
+        e.set_row_mask(live)
+        before = e.query(queries, 1.0)
+        with pytest.raises(PKG.HvsError) as err:
+            e.reserve_rows(0xFFFFFFFF)
+        print(err.value)
+        assert err.value.code == -2 and "hipMalloc(" in str(err.value)
+        assert e.n == 5003 and np.array_equal(e.row_mask(), live)
+        assert e.download_data(0, 5003).tobytes() == nodes.tobytes()
+        after = e.query(queries, 1.0)
+        assert after[0].tobytes() == before[0].tobytes() and after[1].tobytes() == before[1].tobytes()
+        assert e.append_rows(nodes_all[N:N + 20]) == 5003 and e.n == 5023     # and the context goes on
+        assert e.download_data(5003, 20).tobytes() == nodes_all[N:N + 20].tobytes()

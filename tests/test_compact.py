@@ -281,7 +281,97 @@ def test_life_goes_on(data, engine, monkeypatch):
         answers_match(e, model, np.ones(n2 + 50, bool), 0.5)
 
 
-# ---- 6. errors ---------------------------------------------------------------------------------------------------------------------
+# ---- 6. the two resets --------------------------------------------------------------------------------------------------------------
+def stats_of(e):
+    """append, update and mask figures as dicts, less reindex_ms (a wall time)"""
+    a = e.append_stats().as_dict()
+    a.pop("reindex_ms")
+    return a, e.update_stats().as_dict(), e.mask_stats().as_dict()
+
+
+@pytest.mark.parametrize("engine", [EXACT, I8])
+def test_compaction_and_load_leave_the_same_state(data, engine, monkeypatch):
+    """One context, the same rows twice: through delete / append / update / compact (the compaction's reset) and through a load
+    of the live rows followed by the same append and update (the load's reset, on a context that has been through the first
+    path).  Same answers byte for byte, with the second path's tail and stale rows still outside the index and again after
+    they are folded in; from then on the same figures (reindex_ms aside).  Then a load of another, smaller data set into the
+    context with dead, tail and stale rows: nothing of them is left."""
+    monkeypatch.setenv("HVS_I8_ROTATE", "0")
+    nodes_all, repl, queries = data
+    dead = dead_30_percent()
+    live_base = np.setdiff1d(np.arange(N, dtype=np.uint32), dead)
+    rng = np.random.default_rng(41)
+    upd = np.sort(np.concatenate([rng.choice(live_base, 37, replace=False), [N + 2, N + 150, N + 299]])).astype(np.uint32)
+    cur = nodes_all.copy()
+    cur[upd] = repl
+    cases = [(100, 1.0), (256, 1.0), (100, 0.5)]
+
+    def answers(e):
+        out = []
+        for k, sp in cases:
+            e.set_k(k)
+            out.append(e.query(queries, sp))
+        e.set_k(100)
+        return out
+
+    with fresh(engine, nodes_all[:N]) as e:
+        # first path
+        e.delete_rows(dead)
+        assert e.append_rows(nodes_all[N:]) == N
+        e.update_rows(upd, repl)
+        new_to_old = e.compact()
+        assert e.compact_stats().compactions == 1 and e.append_stats().reindexes == 1   # a compaction counts as a re-index
+        assert np.array_equal(new_to_old, np.concatenate([live_base, np.arange(N, N + 300, dtype=np.uint32)]))
+        n1 = new_to_old.size
+        rows = cur[new_to_old]
+        first = answers(e)
+        first_stats = stats_of(e)
+        print(engine, "compacted", first_stats, e.compact_stats().as_dict())
+        assert e.download_data(0, n1).tobytes() == rows.tobytes()
+        check(rows, queries, first[0][0], first[0][1], 1.0, 100, key="two-resets")
+        # second path, same context: the live base rows as they were loaded, then the same append and update by the new ids
+        e.load_data(nodes_all[:N][live_base])
+        assert e.compact_stats().compactions == 0 and e.append_stats().reindexes == 0
+        assert e.append_rows(nodes_all[N:]) == live_base.size
+        upd_new = np.searchsorted(new_to_old, upd).astype(np.uint32)
+        assert np.array_equal(new_to_old[upd_new], upd)
+        e.update_rows(upd_new, repl)
+        a, u = e.append_stats(), e.update_stats()
+        assert (a.n_indexed, a.n_tail, a.reindexes, u.n_stale) == (live_base.size, 300, 0, 37)
+        assert e.download_data(0, n1).tobytes() == rows.tobytes()
+        second = answers(e)
+        print(engine, "loaded", stats_of(e))
+        for (k, sp), x, y in zip(cases, first, second):
+            assert same(x, y), ("tail and stale rows outside the index", k, sp)
+        e.reindex()
+        second = answers(e)
+        for (k, sp), x, y in zip(cases, first, second):
+            assert same(x, y), ("folded in", k, sp)
+        second_stats = stats_of(e)
+        print(engine, "loaded and folded in", second_stats)
+        assert second_stats == first_stats
+        # dead, tail and stale rows again, then another data set
+        e.delete_rows(np.arange(5, 900, 7, dtype=np.uint32))
+        e.append_rows(nodes_all[:50])
+        e.update_rows(np.array([3, 70_000], np.uint32), repl[:2])
+        assert (e.mask_stats().n_dead, e.append_stats().n_tail, e.update_stats().n_stale) == (128, 50, 2)
+        other = T.gen_data(NS, 91, T.GEN_V1, NCAT)
+        e.load_data(other)
+        a, u, m = e.append_stats(), e.update_stats(), e.mask_stats()
+        assert e.n == NS and e.n_live == NS and e.row_mask().all() and (m.n_live, m.n_dead) == (NS, 0)
+        assert (u.n_stale, a.n_tail, a.reindexes, a.tail_limit, u.limit) == (0, 0, 0, FAR, FAR)
+        assert e.compact_stats().compactions == 0
+        ids, d = e.query(queries, 1.0)
+        check(other, queries, ids, d, 1.0, 100, key="two-resets-other")
+        assert e.last_timing().engine == engine, "the requested engine did not run"
+        if engine != EXACT:                                          # the oracle on the exact engine as well
+            e.set_engine(EXACT)
+            ids, d = e.query(queries, 1.0)
+            check(other, queries, ids, d, 1.0, 100, key="two-resets-other")
+            assert e.last_timing().engine == EXACT
+
+
+# ---- 7. errors ---------------------------------------------------------------------------------------------------------------------
 def test_errors(data):
     nodes_all, _, queries = data
     lib = PKG.library()
