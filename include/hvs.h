@@ -181,7 +181,10 @@ int hvs_stream_wait(hvs_ctx *ctx, void *stream);
 int hvs_merge_shards_device(hvs_ctx *ctx, uint32_t nshards, uint32_t nq, const uint32_t *d_ids_all,
                             const float *d_dists_all, const uint64_t *shard_row0, uint32_t n_total,
                             const float *d_pad_dists, uint32_t *d_out_ids, float *d_out_dists);
-/* Timing of the last hvs_query / hvs_query_resident (call after hvs_sync). */
+/* Timing of the last hvs_query / hvs_query_resident (call after hvs_sync).  HVS_ESTATE when there is none to report: before
+ * the first call, after hvs_set_k and hvs_compact, and after any index build in which the planner of HVS_ENGINE_AUTO ran its
+ * probe batch (a load, hvs_reindex or a fold of 32768 rows and more): the probe uses the call's counters, and the per-call
+ * figures of hvs_mask_stats / hvs_append_stats / hvs_update_stats read zero until the next call. */
 int hvs_last_timing(hvs_ctx *ctx, hvs_timing *out);
 /* Diagnostics: which queries of the last call were answered a second time (call after hvs_sync / hvs_query).
  * which = 0: the exact engine's list (hvs_timing.fallback_queries), 1: the retry list (hvs_timing.retry_queries).

@@ -1008,6 +1008,10 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, HVS_EHIP, "planner probe: synchronisation failed");
     c->n_launch_events = 0;
+    // the probe ran through the call counters and the launch timers: what they held of the caller's last query is gone, so
+    // there is no last call to report until the next one (hvs_last_timing: HVS_ESTATE; the per-call figures of hvs_mask_stats,
+    // hvs_append_stats and hvs_update_stats: zero) -- as after a compaction, instead of the probe's figures under that call's name
+    c->timing_valid = false;
     if (rc) return rc;
     const double base = HVS_IS_I8(c->fmt.built) ? 1.0 : plan_cost16();
     *cost = base + 2650.0 / (double)c->n_indexed * ((double)h[2] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
@@ -1225,8 +1229,11 @@ int ensure_filter_workspace(hvs_ctx* c, uint32_t nqb, uint32_t want_fcap = HVS_F
 
 // slot layout, position ranges, norms and B fragments of one batch (shared by the MFMA engine and the
 // range-based exact engine)
+// `count_sn` (filter batches under a mask or a sampled prefix, where hvs_k_prep's own count of whole ranges does not do): the
+// batch's passing pairs among ids < *count_sn are counted here, between the layout and hvs_k_prep -- hvs_k_prep empties the
+// range of a query that has no usable bound, and that query's pairs count like any other's.
 int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt, bool host_counts = false,
-               const uint32_t* list = nullptr, uint32_t want_fcap = HVS_FCAP)
+               const uint32_t* list = nullptr, uint32_t want_fcap = HVS_FCAP, const uint32_t* count_sn = nullptr)
 {
     int rc = ensure_filter_workspace(c, nqb, want_fcap);
     if (rc) return rc;
@@ -1252,6 +1259,14 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
                                          (size_t)nqb, 0, 64, c->stream));
     hipLaunchKernelGGL(hvs_k_layout, dim3(std::min(hvs_ceil_div(B.nslots, 1024u), 1024u)), dim3(1024), 0, c->stream, c->d_keys_sorted, c->d_qorder, nqb, B.nslots, q0, list,
                        c->d_qra, c->d_qrb, B.qid, B.rank, B.ra, B.rb, c->d_layout);
+    if (count_sn) {
+        if (masked(c)) {
+            if ((rc = count_masked_pairs(c, *count_sn))) return rc;
+        } else {
+            hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, *count_sn,
+                               c->d_counters, c->rs.d_live);
+        }
+    }
     // (last argument: the batch is for a filter engine -- `host_counts` is the exact engine's range scan, which answers every
     // query itself, non-finite ones included)
     hipLaunchKernelGGL(hvs_k_prep, dim3(B.ngroups), dim3(4 * HVS_GROUP), 0, c->stream, c->d_q, B, count_pairs ? 1 : 0, c->d_counters,
@@ -1466,7 +1481,8 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
 {
     const int fmt = c->fmt.built;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
-    int rc = prep_batch(c, q0, nqb, sn >= c->n_indexed && !list && !masked(c), fmt, false, list, want_fcap);
+    const bool count_in_prep = sn >= c->n_indexed && !list && !masked(c);  // whole ranges: hvs_k_prep counts them as it goes
+    int rc = prep_batch(c, q0, nqb, count_in_prep, fmt, false, list, want_fcap, !list && !count_in_prep ? &sn : nullptr);
     if (rc) return rc;
     if ((rc = build_items(c))) return rc;
     HvsBatch& B = c->fb;
@@ -1484,11 +1500,6 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     }
     const HvsGuessTable G = c->guess_tab[gslot];
     B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
-    if (masked(c) && !list) {
-        if ((rc = count_masked_pairs(c, sn))) return rc;
-    } else if (sn < n && !list)
-        hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, c->rs.d_live);
 
     if (c->gate_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gate_heavy, 0));  // (two lanes: see hvs_ctx::ev_pdone)
     // level 0 by the exact kernel; small batches cut it into chunks so that enough waves are in flight
@@ -3010,7 +3021,10 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     // one index over all rows -- or none, by the rule of a load (fewer than 4096 rows, or no room for one)
     if (c->n >= kIndexMinRows || is_filter_engine(c->engine)) return leaf_reindex(c, true);
     free_index(c);
-    return HVS_OK;
+    // (no leaf_reindex here to free the live-row counts along the orderings that have gone: the next index -- hvs_set_engine
+    // builds one without coming through leaf_reindex -- may cover more rows than they have room for)
+    if ((rc = dev_alloc(c, &c->ord[0].lp, (size_t)0))) return rc;
+    return dev_alloc(c, &c->ord[1].lp, (size_t)0);
 }
 
 // hvs_trim_rows, first half: the smaller buffer; second half: the rows, and the swap

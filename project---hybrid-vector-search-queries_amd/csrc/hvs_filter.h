@@ -1530,7 +1530,8 @@ __global__ void hvs_k_count_prefix_pairs(HvsBatch B, const uint32_t* __restrict_
 {
     const uint32_t slot = blockIdx.x;
     if (B.qid[slot] == 0xFFFFFFFFu) return;
-    const uint32_t* __restrict__ perm = B.gord[slot / HVS_GROUP] ? perm_t : perm_ct;
+    // (launched between hvs_k_layout and hvs_k_prep: the group's ordering is read the way hvs_k_prep derives B.gord)
+    const uint32_t* __restrict__ perm = B.rank[(slot / HVS_GROUP) * HVS_GROUP] == 4u ? perm_t : perm_ct;
     uint32_t c = 0;
     for (uint32_t pos = B.ra[slot] + threadIdx.x; pos < B.rb[slot]; pos += blockDim.x) {
         const uint32_t id = perm[pos];
@@ -1561,7 +1562,7 @@ __global__ void hvs_k_count_live_pairs(HvsBatch B, const uint32_t* __restrict__ 
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t c = 0;
     if (slot < B.nslots && B.qid[slot] != 0xFFFFFFFFu) {
-        const uint32_t* __restrict__ lp = B.gord[slot / HVS_GROUP] ? lp_t : lp_ct;
+        const uint32_t* __restrict__ lp = B.rank[(slot / HVS_GROUP) * HVS_GROUP] == 4u ? lp_t : lp_ct;  // (as above)
         const uint32_t a = B.ra[slot], b = B.rb[slot];
         if (b > a) c = lp[b] - lp[a];
     }
