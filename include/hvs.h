@@ -373,6 +373,52 @@ int  hvs_trim_rows(hvs_ctx *ctx);
 void hvs_compact_plan(const uint64_t *live_bits, uint32_t n, uint32_t *n_live, uint32_t *first_dead,
                       uint32_t *new_to_old /* n_live entries, may be NULL */);
 
+/* ---- row-partitioned context: one D cut over the GPUs -------------------------------------------- */
+
+/*
+ * hvs_create_multi / hvs_create_on_devices keep all of D on every GPU and cut the queries.  A row-partitioned context cuts D:
+ * part r (one GPU; a device index may repeat, "virtual ranks") holds the contiguous global rows [row0[r], row0[r+1]) =
+ * shard_range(n, r, n_parts) and nothing else of D but a replica of its last min(n, 256) rows; every part holds all resident
+ * queries and answers all of them on its rows.  The resident queries are cut into one owner range per part (the same
+ * shard_range rule); after the parts have finished a call, each owner copies the other parts' partial lists of its queries
+ * (device-to-device copies, no collective), merges them by the key order (dist asc, id asc) and applies the reference's
+ * padding once.  So a data set may be n_parts times what one GPU holds, and the filter index covers 2^29 rows PER PART.
+ *
+ * The contract: after hvs_load_data / hvs_gen_data on a partitioned context, every later hvs_query, hvs_query_resident +
+ * hvs_download_results returns what a one-GPU context (hvs_create) returns for the same rows under the same settings (engine,
+ * k, distance order, padding): the same ids, bit-equal out_dists, the same hvs_timing.pairs.
+ *  - Sampled prefix: sn = uint32(float(sample_proportion) * float(n)) is taken over the whole n; part r searches its first
+ *    local_sn[r] rows (hvs_partition_plan); a part with local_sn == 0 launches nothing.  The rule "filter engines only while
+ *    the prefix is at least a quarter of the rows" holds per part: every engine gives the same answers.
+ *  - Padding comes from global rows n-1, n-2, ..., duplicates of matched rows included, exactly as on one GPU; with
+ *    hvs_set_padding(ctx, 0) unmatched slots are 0xFFFFFFFF / +inf.
+ *  - hvs_num_rows returns n, hvs_num_gpus n_parts, hvs_num_live_rows n; hvs_download_data serves ranges that cross parts;
+ *    hvs_upload_queries / hvs_gen_queries / hvs_query put all queries on every part; hvs_reserve(nq) sizes every part for all
+ *    nq queries plus the exchange buffers; hvs_query_resident blocks the host until the merged answers exist (the call's one
+ *    synchronisation); hvs_last_timing reports the slowest part's query_ms plus exchange_ms plus merge_ms, nq of the call,
+ *    counters summed over the parts, flags OR-ed.
+ *  - Every part must hold at least k rows: a load with n < n_parts * k, or an hvs_set_k that would break the rule, returns
+ *    HVS_EINVAL and leaves the context as it was.
+ *  - Not supported (yet) on a partitioned context, HVS_ESTATE and nothing changes: row deletion, append, update and compaction
+ *    (hvs_delete_rows, hvs_set_row_mask, hvs_get_row_mask, hvs_append_rows, hvs_reserve_rows, hvs_reindex, hvs_set_tail_limit,
+ *    hvs_update_rows, hvs_compact, hvs_trim_rows), their *_stats functions, and hvs_set_gather.  The functions that say
+ *    "single-GPU contexts only" refuse it as they refuse any multi-GPU context.
+ *  - A call that fails half-way reports the failing part like any multi-GPU call and leaves no kernel running.
+ */
+int hvs_create_partitioned(hvs_ctx **out, const int *devices, int n_parts);   /* 1..16 parts; an index may repeat (virtual ranks) */
+typedef struct hvs_partition_info {
+    uint32_t n_parts;
+    uint32_t row0[17];          /* part r holds global rows [row0[r], row0[r+1]) -- shard_range(n, r, n_parts) */
+    uint32_t padded_queries;    /* last call: queries that matched fewer than k rows in all parts together      */
+    uint64_t exchanged_bytes;   /* last call: bytes of partial lists copied between parts                       */
+    double   exchange_ms, merge_ms; /* last call: slowest part's device time of the list copies / of the merge kernel */
+} hvs_partition_info;
+int hvs_partition_stats(hvs_ctx *ctx, hvs_partition_info *out);   /* HVS_ESTATE on a context that is not partitioned */
+/* host arithmetic, no GPU, no context; any output may be NULL: row0[0..n_parts] = the parts' first rows, sn = uint32(float(sp) * float(n)),
+   local_sn[r] = min(max(sn, row0[r]), row0[r+1]) - row0[r] = rows of part r inside the sampled prefix.  Returns 0, or HVS_EINVAL
+   (n_parts outside 1..16, or a part with fewer than k rows). */
+int hvs_partition_plan(uint32_t n, uint32_t n_parts, uint32_t k, float sample_proportion, uint32_t *row0, uint32_t *sn, uint32_t *local_sn);
+
 #ifdef __cplusplus
 }
 #endif

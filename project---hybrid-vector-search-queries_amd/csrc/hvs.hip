@@ -172,6 +172,23 @@ struct HvsLane {
     uint32_t class_counts[5] = {0, 0, 0, 0, 0};  // queries per predicate class in the current batch
 };
 
+// What a leaf of a row-partitioned context (hvs_create_partitioned) holds beside its part of D: a replica of the last
+// rows of the whole D to pad from, and -- as the owner of a range of the resident queries -- the other parts' partial answers
+// for that range (gather buffers, (n_parts - 1) blocks of `own` rows) and the merged answers (`own` rows), own = queries it owns
+struct HvsPart {
+    float* d_tail = nullptr;  // kPartTailRows x 102
+    uint32_t *d_gx_ids = nullptr, *d_m_ids = nullptr;
+    float *d_gx_dists = nullptr, *d_m_dists = nullptr;
+    size_t gx_cap = 0, m_cap = 0;  // entries
+    unsigned long long* d_padded = nullptr;
+    hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m1 = nullptr;  // around the list copies and the merge kernel of the last call
+    // last call
+    double exchange_ms = 0.0, merge_ms = 0.0;
+    uint64_t bytes = 0;
+    unsigned long long padded = 0;
+};
+constexpr uint32_t kPartTailRows = HVS_KMAX;  // rows of the tail replica: the most a query can be padded with
+
 struct hvs_ctx : HvsLane {
     int device = 0;
     HvsLane spare;                 // the second lane (its buffers are allocated by the first call that has two batches)
@@ -278,6 +295,16 @@ struct hvs_ctx : HvsLane {
     std::vector<hvs_ctx*> kids;
     std::vector<uint32_t> kid_q0;  // resident queries: first global index of each leaf's range (kids.size() + 1 entries)
     int gather_mode = 0;           // HVS_GATHER_DIRECT / HVS_GATHER_PEER
+
+    // row-partitioned root (hvs_create_partitioned): leaf r holds global rows [part_row0[r], part_row0[r + 1]) as ITS rows 0..,
+    // with padding off; every leaf holds all resident queries and kid_q0 cuts them into owner ranges
+    bool partitioned = false;
+    uint32_t part_n = 0;               // rows of the whole D (0: no data set loaded)
+    std::vector<uint32_t> part_row0;   // kids.size() + 1 entries
+    hvs_partition_info pinfo{};
+    bool part_timing_valid = false;
+    uint32_t part_call_nq = 0;         // queries of the last call
+    HvsPart part;                      // (of a leaf of such a root)
 };
 
 namespace {
@@ -1743,23 +1770,18 @@ std::vector<uint32_t> batch_schedule(uint32_t nq, uint32_t step, bool ramp_allow
     return out;
 }
 
-// Hooks of run_queries: `before(off, nqb)` is called before the kernels of a batch are enqueued (hvs_query makes the
-// compute stream wait for the batch's queries there: a batch never starts before its input is on the device);
-// `after(off, nqb, next_nqb)` after they have been enqueued (the host pipeline of hvs_query hangs its copies there);
-// queries [q0 + off, q0 + off + nqb) are complete on the stream at that point, except for overflowed ones
-// (resolve_overflow).
-template <typename Hooks>
-int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, Hooks hooks, bool host_pipeline = false)
+// The sampled prefix of one call: `sn` is what every kernel's sampled-prefix test compares ids against, `sampled` of `of_rows`
+// rows are searched (live ones under a mask).  The public entry points derive it from the caller's sample_proportion
+// (cut_for); a part of a row-partitioned context is handed its share of the whole data set's prefix as a row count
+// (cut_rows): no fraction expresses a cut inside a part.
+struct RowCut {
+    uint32_t sn, sampled, of_rows;
+};
+RowCut cut_rows(const hvs_ctx* c, uint32_t rows) { return RowCut{rows, rows, c->n}; }
+RowCut cut_for(hvs_ctx* c, float sample_proportion)
 {
-    if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
-    if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
-    HVS_HIP(c, hipSetDevice(c->device));
-    {
-        int rc = resolve_overflow(c);  // an earlier call whose results were never fetched
-        if (rc) return rc;
-    }
     uint32_t sn = sample_rows(sample_proportion, c->n);
-    uint32_t sampled = sn, of_rows = c->n;  // rows searched / rows there are (live ones under a mask)
+    uint32_t sampled = sn, of_rows = c->n;
     if (c->rs.n_dead) {
         // live-row mask: the rows searched are the first sn_live live rows = "id < cut and live" (hvs_mask_plan); `sn` is the
         // cut id from here on -- what every kernel's sampled-prefix test compares against
@@ -1774,6 +1796,25 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
         sampled = c->rs.cut_sn_live;
         sn = sampled ? c->rs.cut_id : 0u;
     }
+    return RowCut{sn, sampled, of_rows};
+}
+
+// Hooks of run_queries: `before(off, nqb)` is called before the kernels of a batch are enqueued (hvs_query makes the
+// compute stream wait for the batch's queries there: a batch never starts before its input is on the device);
+// `after(off, nqb, next_nqb)` after they have been enqueued (the host pipeline of hvs_query hangs its copies there);
+// queries [q0 + off, q0 + off + nqb) are complete on the stream at that point, except for overflowed ones
+// (resolve_overflow).
+template <typename Hooks>
+int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hooks, bool host_pipeline = false)
+{
+    if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
+    if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
+    HVS_HIP(c, hipSetDevice(c->device));
+    {
+        int rc = resolve_overflow(c);  // an earlier call whose results were never fetched
+        if (rc) return rc;
+    }
+    const uint32_t sn = cut.sn, sampled = cut.sampled, of_rows = cut.of_rows;
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
     // the exact engine answers.
@@ -1875,6 +1916,12 @@ int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, H
     return HVS_OK;
 }
 
+template <typename Hooks>
+int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, Hooks hooks, bool host_pipeline = false)
+{
+    return run_queries_cut(c, q0, nq, cut_for(c, sample_proportion), hooks, host_pipeline);
+}
+
 // ---------------------------------------------------------------------------------------------
 // leaf (one GPU) implementations of the C ABI; the multi-GPU root dispatches to them
 // ---------------------------------------------------------------------------------------------
@@ -1972,6 +2019,12 @@ void leaf_destroy(hvs_ctx* c)
         if (p) (void)hipFree(p);
     c->rs.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
+    {
+        HvsPart& P = c->part;
+        HvsRowSet::drop(P.d_tail, P.d_gx_ids, P.d_m_ids, P.d_gx_dists, P.d_m_dists, P.d_padded);
+        for (hipEvent_t ev : {P.ev_x0, P.ev_x1, P.ev_m1})
+            if (ev) (void)hipEventDestroy(ev);
+    }
     free_lane(c->spare);
     free_lane(static_cast<HvsLane&>(*c));
     if (c->ev_lane) (void)hipEventDestroy(c->ev_lane);
@@ -2353,13 +2406,14 @@ int leaf_load_data_from_peer(hvs_ctx* c, const hvs_ctx* src)
     return finish_data(c);
 }
 
-int leaf_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t ncat)
+// (`first_row`: the place of the context's row 0 in the gen-v1 stream -- a part of a row-partitioned context)
+int leaf_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t ncat, uint64_t first_row = 0)
 {
     int rc = begin_data(c, n);
     if (rc) return rc;
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
     hipLaunchKernelGGL(hvs_k_gen_data, dim3(256 * 8), dim3(256), 0, c->stream, c->d_data, (uint64_t)n * HVS_DCOLS,
-                       seed, profile, ncat);
+                       seed, profile, ncat, first_row);
     HVS_HIP(c, hipGetLastError());
     HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
@@ -3061,6 +3115,14 @@ void shard_range(uint32_t total, uint32_t r, uint32_t world, uint32_t& a, uint32
     b = a + base + (r < rem ? 1u : 0u);
 }
 
+// the resident queries of a multi-GPU root, cut into one range per leaf: the queries a leaf holds (replicated D) or owns (row parts)
+void cut_queries(hvs_ctx* root, uint32_t nq)
+{
+    const uint32_t N = (uint32_t)root->kids.size();
+    root->kid_q0.assign(N + 1u, 0u);
+    for (uint32_t r = 0; r < N; ++r) shard_range(nq, r, N, root->kid_q0[r], root->kid_q0[r + 1]);
+}
+
 // CPUs of the NUMA node of a GPU: PCI bus id -> /sys/bus/pci/devices/<id>/numa_node -> /sys/devices/system/node/node<k>/cpulist
 // (best effort: empty when the platform does not say)
 std::vector<int> device_node_cpus(int device)
@@ -3197,6 +3259,217 @@ int leaf0_stats(hvs_ctx* c, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add a
     return HVS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// row-partitioned root (hvs_create_partitioned; include/hvs.h "row-partitioned context")
+// ---------------------------------------------------------------------------------------------
+#define HVS_NOT_PARTITIONED(c, fn) \
+    if ((c)->partitioned) return fail((c), HVS_ESTATE, fn ": not supported on a row-partitioned context")
+
+uint32_t part_tail_rows(const hvs_ctx* root) { return std::min(root->part_n, kPartTailRows); }
+
+// gather and merge buffers of part r as the owner of `own` resident queries
+int part_ensure_buffers(hvs_ctx* root, uint32_t r, uint32_t own)
+{
+    hvs_ctx* k = root->kids[r];
+    HvsPart& P = k->part;
+    const size_t need_m = (size_t)own * root->k, need_gx = need_m * (root->kids.size() - 1u);
+    int rc;
+    if (need_m > P.m_cap) {
+        P.m_cap = 0;
+        if ((rc = dev_alloc(k, &P.d_m_ids, need_m)) || (rc = dev_alloc(k, &P.d_m_dists, need_m))) return rc;
+        P.m_cap = need_m;
+    }
+    if (need_gx > P.gx_cap) {
+        P.gx_cap = 0;
+        if ((rc = dev_alloc(k, &P.d_gx_ids, need_gx)) || (rc = dev_alloc(k, &P.d_gx_dists, need_gx))) return rc;
+        P.gx_cap = need_gx;
+    }
+    return HVS_OK;
+}
+
+// the plan of a data set of n rows in the root's books (no call has run on it yet)
+void part_set_plan(hvs_ctx* root, uint32_t n)
+{
+    const uint32_t N = (uint32_t)root->kids.size();
+    root->part_n = n;
+    root->part_row0.assign(N + 1u, 0u);
+    for (uint32_t r = 0; r < N && n; ++r) shard_range(n, r, N, root->part_row0[r], root->part_row0[r + 1]);
+    root->pinfo = hvs_partition_info{};
+    root->pinfo.n_parts = N;
+    std::copy(root->part_row0.begin(), root->part_row0.end(), root->pinfo.row0);
+    root->part_timing_valid = false;
+}
+
+// after a failure: nothing of this call is left running on any part (best effort)
+void part_quiesce(hvs_ctx* root)
+{
+    for (hvs_ctx* k : root->kids) {
+        (void)hipSetDevice(k->device);
+        if (k->stream) (void)hipStreamSynchronize(k->stream);
+        if (k->spare.stream) (void)hipStreamSynchronize(k->spare.stream);
+    }
+    (void)hipGetLastError();
+}
+
+// Resident queries [q0, q0 + nq) on every part's rows, then exchange and merge by owner.  Blocks until the merged answers exist.
+int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
+{
+    const uint32_t N = (uint32_t)c->kids.size(), K = c->k;
+    if (!c->part_n) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
+    if (c->kid_q0.size() != N + 1u || (uint64_t)q0 + nq > c->kid_q0.back())
+        return fail(c, HVS_EINVAL, "query range outside the resident query set");
+    c->part_timing_valid = false;
+    if (nq == 0u) return HVS_OK;
+    uint32_t local_sn[16];
+    if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
+    // every part answers all the queries on its rows (its overflow re-runs included): the call's one synchronisation
+    int rc = for_each_leaf(c, [&](uint32_t r) -> int {
+        hvs_ctx* k = c->kids[r];
+        HVS_HIP(k, hipSetDevice(k->device));
+        int r2 = part_ensure_buffers(c, r, c->kid_q0[r + 1] - c->kid_q0[r]);
+        if (r2) return r2;
+        if (local_sn[r] == 0u) {  // nothing of the sampled prefix in this part: empty lists, no launch
+            k->timing_valid = false;
+            HVS_HIP(k, hipMemsetAsync(k->d_out_ids + (size_t)q0 * K, 0xFF, (size_t)nq * K * sizeof(uint32_t), k->stream));
+            HVS_HIP(k, hipStreamSynchronize(k->stream));
+            return HVS_OK;
+        }
+        if ((r2 = run_queries_cut(k, q0, nq, cut_rows(k, local_sn[r]), NoHook{}))) return r2;
+        return leaf_sync(k);
+    });
+    // owner r: the other parts' rows of its queries into its gather buffer, its own rows in place, one merge launch
+    if (!rc)
+        rc = for_each_leaf(c, [&](uint32_t r) -> int {
+            hvs_ctx* k = c->kids[r];
+            HvsPart& P = k->part;
+            P.exchange_ms = P.merge_ms = 0.0;
+            P.bytes = 0;
+            P.padded = 0;
+            const uint32_t a = std::max(q0, c->kid_q0[r]), b = std::min(q0 + nq, c->kid_q0[r + 1]);
+            if (a >= b) return HVS_OK;
+            const uint32_t own = c->kid_q0[r + 1] - c->kid_q0[r], lo = a - c->kid_q0[r], m = b - a;
+            const size_t cnt = (size_t)m * K;
+            HVS_HIP(k, hipSetDevice(k->device));
+            HVS_HIP(k, hipMemsetAsync(P.d_padded, 0, sizeof(unsigned long long), k->stream));
+            HVS_HIP(k, hipEventRecord(P.ev_x0, k->stream));
+            HvsPartLists L{};
+            uint32_t slot = 0;
+            for (uint32_t p = 0; p < N; ++p) {
+                L.row0[p] = c->part_row0[p];
+                if (p == r) {
+                    L.ids[p] = k->d_out_ids + (size_t)a * K;
+                    L.dists[p] = k->d_out_dists + (size_t)a * K;
+                    continue;
+                }
+                const hvs_ctx* src = c->kids[p];
+                uint32_t* gi = P.d_gx_ids + ((size_t)slot * own + lo) * K;
+                float* gd = P.d_gx_dists + ((size_t)slot * own + lo) * K;
+                HVS_HIP(k, hipMemcpyPeerAsync(gi, k->device, src->d_out_ids + (size_t)a * K, src->device, cnt * sizeof(uint32_t), k->stream));
+                HVS_HIP(k, hipMemcpyPeerAsync(gd, k->device, src->d_out_dists + (size_t)a * K, src->device, cnt * sizeof(float), k->stream));
+                L.ids[p] = gi;
+                L.dists[p] = gd;
+                P.bytes += cnt * (sizeof(uint32_t) + sizeof(float));
+                ++slot;
+            }
+            HVS_HIP(k, hipEventRecord(P.ev_x1, k->stream));
+            const uint32_t tail_rows = part_tail_rows(c);
+            with_cap(K <= 128u ? 256 : 512, [&](auto CAPT) {
+                auto launch = [&](auto ST) {
+                    hipLaunchKernelGGL((hvs_k_merge_parts<decltype(ST)::value, decltype(CAPT)::value>), dim3((m + 3u) / 4u), dim3(256), 0, k->stream, L, N,
+                                       m, k->d_q + (size_t)a * HVS_QCOLS, P.d_tail, tail_rows, c->part_n, c->padding ? 1 : 0,
+                                       P.d_m_ids + (size_t)lo * K, P.d_m_dists + (size_t)lo * K, K, P.d_padded);
+                };
+                if (c->scalar_order)
+                    launch(std::true_type{});
+                else
+                    launch(std::false_type{});
+            });
+            HVS_HIP(k, hipGetLastError());
+            HVS_HIP(k, hipEventRecord(P.ev_m1, k->stream));
+            HVS_HIP(k, hipMemcpyAsync(&P.padded, P.d_padded, sizeof(unsigned long long), hipMemcpyDeviceToHost, k->stream));
+            HVS_HIP(k, hipStreamSynchronize(k->stream));
+            float ms = 0.f;
+            HVS_HIP(k, hipEventElapsedTime(&ms, P.ev_x0, P.ev_x1));
+            P.exchange_ms = ms;
+            HVS_HIP(k, hipEventElapsedTime(&ms, P.ev_x1, P.ev_m1));
+            P.merge_ms = ms;
+            return HVS_OK;
+        });
+    if (rc) {
+        part_quiesce(c);
+        return rc;
+    }
+    hvs_partition_info& I = c->pinfo;
+    I.padded_queries = 0;
+    I.exchanged_bytes = 0;
+    I.exchange_ms = I.merge_ms = 0.0;
+    for (const hvs_ctx* k : c->kids) {
+        I.padded_queries += (uint32_t)k->part.padded;
+        I.exchanged_bytes += k->part.bytes;
+        I.exchange_ms = std::max(I.exchange_ms, k->part.exchange_ms);
+        I.merge_ms = std::max(I.merge_ms, k->part.merge_ms);
+    }
+    c->part_timing_valid = true;
+    c->part_call_nq = nq;
+    return HVS_OK;
+}
+
+// merged answers of resident queries [q0, q0 + nq), by owner range, to host memory
+int part_download_results(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* out_ids, float* out_dists)
+{
+    const uint32_t K = c->k;
+    for (size_t r = 0; r < c->kids.size() && c->kid_q0.size() == c->kids.size() + 1u; ++r) {
+        const uint32_t a = std::max(q0, c->kid_q0[r]), b = std::min(q0 + nq, c->kid_q0[r + 1]);
+        if (a < b && c->kids[r]->part.m_cap < (size_t)(c->kid_q0[r + 1] - c->kid_q0[r]) * K)
+            return fail(c, HVS_ESTATE, "hvs_download_results: no results (hvs_query_resident has not run)");
+    }
+    return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t off) -> int {
+        HVS_HIP(k, hipSetDevice(k->device));
+        HVS_HIP(k, hipMemcpyAsync(out_ids + (size_t)off * K, k->part.d_m_ids + (size_t)lq0 * K, (size_t)m * K * sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, k->stream));
+        if (out_dists)
+            HVS_HIP(k, hipMemcpyAsync(out_dists + (size_t)off * K, k->part.d_m_dists + (size_t)lq0 * K, (size_t)m * K * sizeof(float),
+                                      hipMemcpyDeviceToHost, k->stream));
+        HVS_HIP(k, hipStreamSynchronize(k->stream));
+        return HVS_OK;
+    });
+}
+
+// the tail replica of every part after its rows are in place: from the caller's rows, or generated
+int part_fill_tail(hvs_ctx* root, hvs_ctx* k, const float* rows, uint64_t seed, int profile, uint32_t ncat)
+{
+    const uint32_t n = root->part_n, t = part_tail_rows(root);
+    if (rows) {
+        const int rc = upload_rows(k, k->part.d_tail, rows + (size_t)(n - t) * HVS_DCOLS, (size_t)t * HVS_DCOLS);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(hvs_k_gen_data, dim3(hvs_ceil_div(t * HVS_DCOLS, 256u)), dim3(256), 0, k->stream, k->part.d_tail,
+                           (uint64_t)t * HVS_DCOLS, seed, profile, ncat, (uint64_t)(n - t));
+        HVS_HIP(k, hipGetLastError());
+    }
+    HVS_HIP(k, hipStreamSynchronize(k->stream));
+    return HVS_OK;
+}
+
+// hvs_load_data (rows != nullptr) / hvs_gen_data of a partitioned context: part r takes ITS rows over its own link
+int part_load(hvs_ctx* c, const float* rows, uint32_t n, uint64_t seed, int profile, uint32_t ncat)
+{
+    const uint32_t N = (uint32_t)c->kids.size();
+    if (n / N < c->k) return fail(c, HVS_EINVAL, "row-partitioned context: every part needs at least k rows (n >= n_parts * k)");
+    part_set_plan(c, n);
+    const int rc = for_each_leaf(c, [&](uint32_t r) -> int {
+        hvs_ctx* k = c->kids[r];
+        const uint32_t a = c->part_row0[r], cnt = c->part_row0[r + 1] - a;
+        const int r2 = rows ? leaf_load_data(k, rows + (size_t)a * HVS_DCOLS, cnt) : leaf_gen_data(k, cnt, seed, profile, ncat, a);
+        return r2 ? r2 : part_fill_tail(c, k, rows, seed, profile, ncat);
+    });
+    if (rc) {
+        part_quiesce(c);
+        c->part_n = 0;  // (parts may hold different data sets now: load again)
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3291,6 +3564,59 @@ int hvs_create_multi(hvs_ctx** out, int n_gpus)
     return hvs_create_on_devices(out, devs.data(), n_gpus);
 }
 
+int hvs_create_partitioned(hvs_ctx** out, const int* devices, int n_parts)
+{
+    if (!out || !devices || n_parts < 1 || n_parts > 16) {
+        g_global_err = "hvs_create_partitioned: bad argument (1..16 device indices)";
+        if (out) *out = nullptr;
+        return HVS_EINVAL;
+    }
+    int rc = hvs_create_on_devices(out, devices, n_parts);
+    if (rc) return rc;
+    hvs_ctx* root = *out;
+    root->partitioned = true;
+    part_set_plan(root, 0u);
+    for (hvs_ctx* k : root->kids) {
+        k->padding = false;  // partial answers: the merge pads once, from the tail of the whole D
+        HvsPart& P = k->part;
+        hipError_t e = hipSetDevice(k->device);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&P.d_tail), (size_t)kPartTailRows * HVS_DCOLS * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&P.d_padded), sizeof(unsigned long long));
+        for (hipEvent_t* ev : {&P.ev_x0, &P.ev_x1, &P.ev_m1})
+            if (e == hipSuccess) e = hipEventCreate(ev);
+        if (e != hipSuccess) {
+            g_global_err = std::string("hvs_create_partitioned: ") + hipGetErrorString(e);
+            hvs_destroy(root);
+            *out = nullptr;
+            return e == hipErrorOutOfMemory ? HVS_ENOMEM : HVS_EHIP;
+        }
+    }
+    (void)hipSetDevice(devices[0]);
+    return HVS_OK;
+}
+
+int hvs_partition_stats(hvs_ctx* c, hvs_partition_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (!c->partitioned) return fail(c, HVS_ESTATE, "hvs_partition_stats: not a row-partitioned context");
+    *out = c->pinfo;
+    return HVS_OK;
+}
+
+int hvs_partition_plan(uint32_t n, uint32_t n_parts, uint32_t k, float sample_proportion, uint32_t* row0, uint32_t* sn, uint32_t* local_sn)
+{
+    if (n_parts < 1u || n_parts > 16u || n / n_parts < k) return HVS_EINVAL;
+    const uint32_t s = sample_rows(sample_proportion, n);
+    if (sn) *sn = s;
+    for (uint32_t r = 0; r < n_parts; ++r) {
+        uint32_t a, b;
+        shard_range(n, r, n_parts, a, b);
+        if (row0) row0[r] = a, row0[r + 1] = b;
+        if (local_sn) local_sn[r] = std::min(std::max(s, a), b) - a;
+    }
+    return HVS_OK;
+}
+
 int hvs_num_gpus(const hvs_ctx* c) { return !c ? 0 : (c->kids.empty() ? 1 : (int)c->kids.size()); }
 
 int hvs_device_count(void)
@@ -3306,6 +3632,7 @@ int hvs_device_count(void)
 int hvs_set_gather(hvs_ctx* c, int mode)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_set_gather");
     if (mode != HVS_GATHER_DIRECT && mode != HVS_GATHER_PEER) return fail(c, HVS_EINVAL, "hvs_set_gather: unknown mode");
     c->gather_mode = mode;
     return HVS_OK;
@@ -3339,7 +3666,7 @@ int hvs_set_padding(hvs_ctx* c, int enabled)
 {
     if (!c) return HVS_EINVAL;
     c->padding = enabled != 0;
-    for (hvs_ctx* k : c->kids) k->padding = c->padding;
+    for (hvs_ctx* k : c->kids) k->padding = c->padding && !c->partitioned;  // (parts never pad: the merge does)
     return HVS_OK;
 }
 
@@ -3356,9 +3683,12 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
 {
     if (!c) return HVS_EINVAL;
     if (k < 8u || k > HVS_KMAX) return fail(c, HVS_EINVAL, "hvs_set_k: k outside 8..256 (the reference asserts KNN_LIMIT >= 8)");
+    if (c->partitioned && c->part_n && c->part_n / (uint32_t)c->kids.size() < k)
+        return fail(c, HVS_EINVAL, "hvs_set_k: a part of the row-partitioned data set has fewer than k rows");
     if (!c->kids.empty()) {
         const int rc = for_each_leaf(c, [&](uint32_t r) { return hvs_set_k(c->kids[r], k); });
         if (!rc) c->k = k;
+        c->part_timing_valid = false;  // (result rows change size: nothing of the last call is left to report)
         return rc;
     }
     if (c->n && c->n - c->rs.n_dead < k) return fail(c, HVS_EINVAL, "hvs_set_k: the loaded data set has fewer than k (live) rows");
@@ -3379,13 +3709,18 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
 
 uint32_t hvs_get_k(const hvs_ctx* c) { return c ? c->k : 0u; }
 
-uint32_t hvs_num_rows(const hvs_ctx* c) { return !c ? 0u : (c->kids.empty() ? c->n : c->kids[0]->n); }
+uint32_t hvs_num_rows(const hvs_ctx* c) { return !c ? 0u : (c->partitioned ? c->part_n : c->kids.empty() ? c->n : c->kids[0]->n); }
 
 int hvs_reserve(hvs_ctx* c, uint32_t nq)
 {
     if (!c) return HVS_EINVAL;
     if (c->kids.empty()) return leaf_reserve(c, nq);
     const uint32_t N = (uint32_t)c->kids.size();
+    if (c->partitioned)  // every part answers all nq queries and owns shard_range(nq, r, N) of them
+        return for_each_leaf(c, [&](uint32_t r) -> int {
+            const int rc = leaf_reserve(c->kids[r], nq);
+            return rc ? rc : part_ensure_buffers(c, r, hvs_ceil_div(nq, N));
+        });
     return for_each_leaf(c, [&](uint32_t r) { return leaf_reserve(c->kids[r], hvs_ceil_div(nq, N)); });
 }
 
@@ -3394,6 +3729,7 @@ int hvs_load_data(hvs_ctx* c, const float* rows, uint32_t n)
     if (!c) return HVS_EINVAL;
     if (!rows) return fail(c, HVS_EINVAL, "hvs_load_data: rows is NULL");
     if (c->kids.empty()) return leaf_load_data(c, rows, n);
+    if (c->partitioned) return part_load(c, rows, n, 0u, 0, 0u);
     // D reaches the GPUs in two parallel phases: every GPU uploads ITS slice of the rows over its own PCIe link, then takes
     // the other slices from its peers over xGMI (each pair has its own link) -- an all-gather by peer copies -- and builds
     // its index.  (Round 2 uploaded everything to GPU 0 and let 7 peers pull 4 GB each from it after its index build;
@@ -3445,12 +3781,24 @@ int hvs_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t nc
     if (!c) return HVS_EINVAL;
     if (ncat == 0) return fail(c, HVS_EINVAL, "hvs_gen_data: ncat must be > 0");
     if (c->kids.empty()) return leaf_gen_data(c, n, seed, profile, ncat);
+    if (c->partitioned) return part_load(c, nullptr, n, seed, profile, ncat);
     return for_each_leaf(c, [&](uint32_t r) { return leaf_gen_data(c->kids[r], n, seed, profile, ncat); });
 }
 
 int hvs_download_data(hvs_ctx* c, uint32_t row0, uint32_t nrows, float* out_rows)
 {
     if (!c) return HVS_EINVAL;
+    if (c->partitioned) {
+        if (!c->part_n) return fail(c, HVS_ESTATE, "no data set loaded");
+        if (!out_rows || (uint64_t)row0 + nrows > c->part_n) return fail(c, HVS_EINVAL, "hvs_download_data: bad range");
+        for (size_t r = 0; r < c->kids.size(); ++r) {  // the parts the range crosses
+            const uint32_t a = std::max(row0, c->part_row0[r]), b = std::min(row0 + nrows, c->part_row0[r + 1]);
+            if (a >= b) continue;
+            const int rc = hvs_download_data(c->kids[r], a - c->part_row0[r], b - a, out_rows + (size_t)(a - row0) * HVS_DCOLS);
+            if (rc) return fail(c, rc, c->kids[r]->err);
+        }
+        return HVS_OK;
+    }
     if (!c->kids.empty()) {
         const int rc = hvs_download_data(c->kids[0], row0, nrows, out_rows);
         return rc ? fail(c, rc, c->kids[0]->err) : HVS_OK;
@@ -3469,9 +3817,11 @@ int hvs_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
     if (!c) return HVS_EINVAL;
     if (!q_rows && nq) return fail(c, HVS_EINVAL, "hvs_upload_queries: q_rows is NULL");
     if (c->kids.empty()) return leaf_upload_queries(c, q_rows, nq);
-    const uint32_t N = (uint32_t)c->kids.size();
-    c->kid_q0.assign(N + 1u, 0u);
-    for (uint32_t r = 0; r < N; ++r) shard_range(nq, r, N, c->kid_q0[r], c->kid_q0[r + 1]);
+    if (c->partitioned) {  // all queries on every part; the ranges are the owners'
+        cut_queries(c, nq);
+        return for_each_leaf(c, [&](uint32_t r) { return leaf_upload_queries(c->kids[r], q_rows, nq); });
+    }
+    cut_queries(c, nq);
     return for_each_leaf(c, [&](uint32_t r) {
         return leaf_upload_queries(c->kids[r], q_rows + (size_t)c->kid_q0[r] * HVS_QCOLS, c->kid_q0[r + 1] - c->kid_q0[r]);
     });
@@ -3483,9 +3833,11 @@ int hvs_gen_queries(hvs_ctx* c, uint32_t nq, uint64_t seed, int profile, uint32_
     if (!c) return HVS_EINVAL;
     if (ncat == 0 || force_type > 3) return fail(c, HVS_EINVAL, "hvs_gen_queries: bad ncat / force_type");
     if (c->kids.empty()) return leaf_gen_queries(c, nq, seed, profile, ncat, force_type, first_row);
-    const uint32_t N = (uint32_t)c->kids.size();
-    c->kid_q0.assign(N + 1u, 0u);
-    for (uint32_t r = 0; r < N; ++r) shard_range(nq, r, N, c->kid_q0[r], c->kid_q0[r + 1]);
+    if (c->partitioned) {
+        cut_queries(c, nq);
+        return for_each_leaf(c, [&](uint32_t r) { return leaf_gen_queries(c->kids[r], nq, seed, profile, ncat, force_type, first_row); });
+    }
+    cut_queries(c, nq);
     return for_each_leaf(c, [&](uint32_t r) {
         return leaf_gen_queries(c->kids[r], c->kid_q0[r + 1] - c->kid_q0[r], seed, profile, ncat, force_type, first_row + c->kid_q0[r]);
     });
@@ -3494,6 +3846,10 @@ int hvs_gen_queries(hvs_ctx* c, uint32_t nq, uint64_t seed, int profile, uint32_
 int hvs_download_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float* out_rows)
 {
     if (!c) return HVS_EINVAL;
+    if (c->partitioned) {  // (every part holds them all)
+        const int rc = hvs_download_queries(c->kids[0], q0, nq, out_rows);
+        return rc ? fail(c, rc, c->kids[0]->err) : HVS_OK;
+    }
     if (!c->kids.empty())
         return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t off) {
             return hvs_download_queries(k, lq0, m, out_rows + (size_t)off * HVS_QCOLS);
@@ -3509,6 +3865,7 @@ int hvs_download_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float* out_rows)
 int hvs_query_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
 {
     if (!c) return HVS_EINVAL;
+    if (c->partitioned) return part_run(c, q0, nq, sample_proportion);
     if (!c->kids.empty())
         return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t) {
             return run_queries(k, lq0, m, sample_proportion, NoHook{});
@@ -3528,6 +3885,7 @@ int hvs_download_results(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* out_ids
     if (!c) return HVS_EINVAL;
     if (!c->kids.empty()) {
         if (!out_ids) return fail(c, HVS_EINVAL, "hvs_download_results: out_ids is NULL");
+        if (c->partitioned) return part_download_results(c, q0, nq, out_ids, out_dists);
         return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t off) {
             return leaf_download_results(k, lq0, m, out_ids + (size_t)off * c->k, out_dists ? out_dists + (size_t)off * c->k : nullptr);
         });
@@ -3571,9 +3929,15 @@ int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proport
     if (nq == 0) return HVS_OK;
     if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query: q_rows / out_ids is NULL");
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t N = (uint32_t)c->kids.size();
-    c->kid_q0.assign(N + 1u, 0u);
-    for (uint32_t r = 0; r < N; ++r) shard_range(nq, r, N, c->kid_q0[r], c->kid_q0[r + 1]);
+    if (c->partitioned) {
+        // all queries to every part over its own link, the resident call, each owner's merged slice home
+        int rc = hvs_upload_queries(c, q_rows, nq);
+        if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
+        if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
+        c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    }
+    cut_queries(c, nq);
     int rc;
     if (c->gather_mode == HVS_GATHER_DIRECT) {
         // zero-collective path: every GPU's pipeline reads its slice of the caller's queries and writes its slice of
@@ -3668,6 +4032,7 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
 {
     if (!c || !out) return HVS_EINVAL;
     if (c->kids.empty()) return leaf_last_timing(c, out);
+    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
     // whole-job view: device time = the slowest GPU's, work counters summed over the GPUs that took part
     hvs_timing agg{};
     bool any = false;
@@ -3690,6 +4055,14 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
         agg.load_ms = std::max(agg.load_ms, t.load_ms);
         agg.engine = t.engine;
         agg.n_gpus += 1;
+        any = true;
+    }
+    if (c->partitioned) {
+        // every part answered all the queries (a part outside the sampled prefix launched nothing); exchange and merge follow the slowest
+        agg.query_ms += c->pinfo.exchange_ms + c->pinfo.merge_ms;
+        agg.nq = c->part_call_nq;
+        agg.n_gpus = (uint32_t)c->kids.size();
+        if (!any) agg.engine = HVS_ENGINE_EXACT_SCAN;
         any = true;
     }
     if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
@@ -3749,6 +4122,7 @@ static int apply_mask_everywhere(hvs_ctx* c, const std::vector<uint64_t>& words,
 int hvs_set_row_mask(hvs_ctx* c, const uint64_t* live_bits)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_set_row_mask");
     const hvs_ctx* L = loaded_leaf(c, "hvs_set_row_mask");
     if (!L) return HVS_ESTATE;
     std::vector<uint64_t> words = all_live_words(L->n);
@@ -3762,6 +4136,7 @@ int hvs_set_row_mask(hvs_ctx* c, const uint64_t* live_bits)
 int hvs_delete_rows(hvs_ctx* c, const uint32_t* ids, uint32_t count)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_delete_rows");
     const hvs_ctx* L = loaded_leaf(c, "hvs_delete_rows");
     if (!L) return HVS_ESTATE;
     if (count && !ids) return fail(c, HVS_EINVAL, "hvs_delete_rows: ids is NULL");
@@ -3778,6 +4153,7 @@ int hvs_delete_rows(hvs_ctx* c, const uint32_t* ids, uint32_t count)
 int hvs_get_row_mask(hvs_ctx* c, uint64_t* live_bits)
 {
     if (!c || !live_bits) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_get_row_mask");
     const hvs_ctx* L = loaded_leaf(c, "hvs_get_row_mask");
     if (!L) return HVS_ESTATE;
     const std::vector<uint64_t> words = L->rs.h_live.empty() ? all_live_words(L->n) : L->rs.h_live;
@@ -3787,11 +4163,13 @@ int hvs_get_row_mask(hvs_ctx* c, uint64_t* live_bits)
 
 uint32_t hvs_num_live_rows(const hvs_ctx* c)
 {
+    if (c && c->partitioned) return c->part_n;
     return c ? mask_leaf(c)->n - mask_leaf(c)->rs.n_dead : 0u;
 }
 
 int hvs_mask_stats(hvs_ctx* c, hvs_mask_info* out)
 {
+    if (c) HVS_NOT_PARTITIONED(c, "hvs_mask_stats");
     return leaf0_stats(c, out, leaf_mask_stats, [](hvs_mask_info& sum, const hvs_mask_info& m) { sum.dead_survivors += m.dead_survivors; });
 }
 
@@ -3808,6 +4186,7 @@ void hvs_append_plan(uint32_t n_indexed, uint32_t n_total, float sample_proporti
 int hvs_append_rows(hvs_ctx* c, const float* rows, uint32_t count, uint32_t* first_id)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_append_rows");
     if (count == 0u) return HVS_OK;
     if (!rows) return fail(c, HVS_EINVAL, "hvs_append_rows: rows is NULL");
     const hvs_ctx* L = loaded_leaf(c, "hvs_append_rows");
@@ -3823,6 +4202,7 @@ int hvs_append_rows(hvs_ctx* c, const float* rows, uint32_t count, uint32_t* fir
 int hvs_reserve_rows(hvs_ctx* c, uint32_t n_capacity)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_reserve_rows");
     const int rc = on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reserve_rows(k, n_capacity); });
     if (rc) (void)hipGetLastError();  // (as two_phase does)
     return rc;
@@ -3831,12 +4211,14 @@ int hvs_reserve_rows(hvs_ctx* c, uint32_t n_capacity)
 int hvs_reindex(hvs_ctx* c)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_reindex");
     return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_reindex(k, false); });
 }
 
 int hvs_set_tail_limit(hvs_ctx* c, uint32_t rows)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_set_tail_limit");
     c->rs.tail_limit = rows;
     for (hvs_ctx* k : c->kids) k->rs.tail_limit = rows;
     return HVS_OK;
@@ -3844,6 +4226,7 @@ int hvs_set_tail_limit(hvs_ctx* c, uint32_t rows)
 
 int hvs_append_stats(hvs_ctx* c, hvs_append_info* out)
 {
+    if (c) HVS_NOT_PARTITIONED(c, "hvs_append_stats");
     return leaf0_stats(c, out, leaf_append_stats, [](hvs_append_info& sum, const hvs_append_info& m) {
         sum.tail_pairs += m.tail_pairs;
         sum.tail_admitted += m.tail_admitted;
@@ -3877,6 +4260,7 @@ uint32_t hvs_update_plan(const uint32_t* stale, uint32_t n_stale, const uint32_t
 int hvs_update_rows(hvs_ctx* c, const uint32_t* ids, const float* rows, uint32_t count)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_update_rows");
     if (count == 0u) return HVS_OK;
     if (!ids) return fail(c, HVS_EINVAL, "hvs_update_rows: ids is NULL");
     if (!rows) return fail(c, HVS_EINVAL, "hvs_update_rows: rows is NULL");
@@ -3901,6 +4285,7 @@ int hvs_update_rows(hvs_ctx* c, const uint32_t* ids, const float* rows, uint32_t
 
 int hvs_update_stats(hvs_ctx* c, hvs_update_info* out)
 {
+    if (c) HVS_NOT_PARTITIONED(c, "hvs_update_stats");
     return leaf0_stats(c, out, leaf_update_stats, [](hvs_update_info& sum, const hvs_update_info& m) {
         sum.stale_pairs += m.stale_pairs;
         sum.stale_admitted += m.stale_admitted;
@@ -3930,6 +4315,7 @@ void hvs_compact_plan(const uint64_t* live_bits, uint32_t n, uint32_t* n_live, u
 int hvs_compact(hvs_ctx* c, uint32_t* new_to_old)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_compact");
     const hvs_ctx* L = loaded_leaf(c, "hvs_compact");
     if (!L) return HVS_ESTATE;
     const uint32_t n = L->n;
@@ -3951,6 +4337,7 @@ int hvs_compact(hvs_ctx* c, uint32_t* new_to_old)
 int hvs_compact_stats(hvs_ctx* c, hvs_compact_info* out)
 {
     if (!c || !out) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_compact_stats");
     *out = mask_leaf(c)->rs.cstat;
     return HVS_OK;
 }
@@ -3958,6 +4345,7 @@ int hvs_compact_stats(hvs_ctx* c, hvs_compact_info* out)
 int hvs_trim_rows(hvs_ctx* c)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_trim_rows");
     if (!loaded_leaf(c, "hvs_trim_rows")) return HVS_ESTATE;
     return two_phase(c, leaf_trim_prepare, leaf_trim_commit, free_call_scratch);
 }

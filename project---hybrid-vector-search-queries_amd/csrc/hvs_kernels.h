@@ -92,13 +92,14 @@ __global__ __launch_bounds__(256) void hvs_k_compact_gather(const uint2* __restr
 // ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------
-__global__ void hvs_k_gen_data(float* __restrict__ out, uint64_t nelem, uint64_t seed, int profile, uint32_t ncat)
+// `first_row`: out[0] is element 0 of that row of the stream (a part of a row-partitioned context generates its own rows)
+__global__ void hvs_k_gen_data(float* __restrict__ out, uint64_t nelem, uint64_t seed, int profile, uint32_t ncat, uint64_t first_row)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nelem; e += stride) {
         const uint64_t row = e / HVS_DCOLS;
         const uint32_t col = (uint32_t)(e - row * HVS_DCOLS);
-        out[e] = hvs_gen_data_elem(seed, profile, ncat, row, col);
+        out[e] = hvs_gen_data_elem(seed, profile, ncat, first_row + row, col);
     }
 }
 
@@ -474,6 +475,30 @@ struct HvsShardRows {
     uint64_t row0[16];  // first global row of each shard
 };
 
+// One part's result row of one query -- `knn` slots, ids local to the part (0xFFFFFFFF = empty slot) -- appended to the wave's
+// key buffer as (dist bits << 32 | row0 + id); `cnt` keys are held, the new count is returned.  The buffer is cut back to its
+// knn smallest keys whenever the next 64 slots might not fit.  Shared by the two merges over row parts below.
+template <int CAP>
+__device__ __forceinline__ uint32_t hvs_gather_list_keys(uint64_t* buf, uint32_t* hist, uint32_t cnt, const uint32_t* __restrict__ ids,
+                                                         const float* __restrict__ dists, uint64_t row0, uint32_t knn, uint32_t lane)
+{
+    for (uint32_t off = 0; off < knn; off += 64u) {
+        if (cnt + 64u > (uint32_t)CAP) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, hist);
+            cnt = knn;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+        const uint32_t e = off + lane;
+        const uint32_t id = e < knn ? ids[e] : 0xFFFFFFFFu;
+        const bool have = id != 0xFFFFFFFFu;
+        const uint64_t m = __ballot(have);
+        if (have) buf[cnt + hvs_prefix_count(m)] = hvs_make_key(dists[e], (uint32_t)(row0 + id));
+        cnt += (uint32_t)__popcll(m);
+    }
+    return cnt;
+}
+
 template <int CAP>
 __global__ __launch_bounds__(256) void hvs_k_merge_shards(const uint32_t* __restrict__ ids_all,
                                                           const float* __restrict__ dists_all, uint32_t nshards,
@@ -491,20 +516,7 @@ __global__ __launch_bounds__(256) void hvs_k_merge_shards(const uint32_t* __rest
     uint32_t cnt = 0;
     for (uint32_t s = 0; s < nshards; ++s) {
         const size_t base = ((size_t)s * nq + q) * knn;
-        for (uint32_t off = 0; off < knn; off += 64u) {
-            if (cnt + 64u > (uint32_t)CAP) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-                cnt = knn;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            }
-            const uint32_t e = off + lane;
-            const uint32_t id = e < knn ? ids_all[base + e] : 0xFFFFFFFFu;
-            const bool have = id != 0xFFFFFFFFu;
-            const uint64_t m = __ballot(have);
-            if (have) buf[cnt + hvs_prefix_count(m)] = hvs_make_key(dists_all[base + e], (uint32_t)(rows.row0[s] + id));
-            cnt += (uint32_t)__popcll(m);
-        }
+        cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, ids_all + base, dists_all + base, rows.row0[s], knn, lane);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (cnt > knn) {
@@ -530,3 +542,67 @@ __global__ __launch_bounds__(256) void hvs_k_merge_shards(const uint32_t* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// hvs_k_merge_parts -- row-partitioned context (include/hvs.h "row-partitioned context"): the owner of a query range
+// merges the parts' partial answers for its queries and applies the reference's padding once.  Every part answered the
+// queries on its own rows with padding off: ids part-local, 0xFFFFFFFF = empty slot.  `parts` names, per part, its result rows
+// of the owner's queries (row i = query i of the range: the owner's own result buffer, or the gather buffer the other parts'
+// rows were copied into) and its first global row.  Per query (one wave): the keys (dist bits << 32 | global id) of all parts
+// are reduced to the knn smallest -- the global top-k, because every part's list holds its own knn smallest keys.  Only a
+// query with fewer than knn keys pays for distances: slot cnt + s takes global row n_total - 1 - s, duplicates of matched
+// rows included, as hvs_k_select / hvs_k_merge pad on one GPU (optimized_parallel.hpp:149-157), with the distance computed
+// here from `tail` -- the part's replica of the last `tail_rows` rows of the whole D (tail_rows >= knn: host) -- by the engines'
+// own exact-order function; pad == 0 leaves the largest key there.  `padded` counts the under-full queries either way.
+// ---------------------------------------------------------------------------------------------
+struct HvsPartLists {
+    const uint32_t* ids[16];
+    const float* dists[16];
+    uint32_t row0[16];
+};
+
+template <bool SCALAR_ORDER, int CAP>
+__global__ __launch_bounds__(256) void hvs_k_merge_parts(HvsPartLists parts, uint32_t nparts, uint32_t nq, const float* __restrict__ Q,
+                                                         const float* __restrict__ tail, uint32_t tail_rows, uint32_t n_total, int pad,
+                                                         uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+                                                         unsigned long long* __restrict__ padded)
+{
+    __shared__ uint64_t sbuf[4][CAP];
+    __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t q = blockIdx.x * 4u + w;
+    if (q >= nq) return;  // wave-uniform
+    uint64_t* buf = sbuf[w];
+    uint32_t cnt = 0;
+    for (uint32_t s = 0; s < nparts; ++s)
+        cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, parts.ids[s] + (size_t)q * knn, parts.dists[s] + (size_t)q * knn, parts.row0[s], knn,
+                                        lane);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (cnt < knn && lane == 0u) atomicAdd(padded, 1ull);
+    const float* __restrict__ qv = Q + (size_t)q * HVS_QCOLS + 4;
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) {
+            const uint32_t s = e - cnt;  // (< knn <= tail_rows)
+            const float* __restrict__ dv = tail + (size_t)(tail_rows - 1u - s) * HVS_DCOLS + 2;
+            buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), n_total - 1u - s) : ~0ull;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

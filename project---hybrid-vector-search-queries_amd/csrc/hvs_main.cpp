@@ -76,7 +76,12 @@ int main(int argc, char** argv)
     if (const char* e = std::getenv("HVS_GPUS"))
         if (std::atoi(e) >= 1) use = std::min(std::atoi(e), gpus);
     hvs_ctx* ctx = nullptr;
-    if (hvs_create_multi(&ctx, use) != HVS_OK) {
+    // HVS_PARTITION=1: D is cut over those GPUs (a row-partitioned context) instead of replicated; same output files
+    const char* part_env = std::getenv("HVS_PARTITION");
+    const bool partition = part_env && std::atoi(part_env) == 1;
+    std::vector<int> devs((size_t)std::min(use, 16));
+    for (size_t i = 0; i < devs.size(); ++i) devs[i] = (int)i;
+    if ((partition ? hvs_create_partitioned(&ctx, devs.data(), (int)devs.size()) : hvs_create_multi(&ctx, use)) != HVS_OK) {
         std::cerr << hvs_last_global_error() << "\n";
         return 3;
     }
@@ -104,7 +109,7 @@ int main(int argc, char** argv)
     hvs_timing tm{};
     if (nq) hvs_last_timing(ctx, &tm);
     std::cerr << "Vector Search took " << std::chrono::duration<double, std::milli>(t1 - t0).count() << " ms"
-              << " (" << hvs_num_gpus(ctx) << " GPU(s): query host->host " << tm.host_ms << " ms, of it on the device " << tm.query_ms
+              << " (" << hvs_num_gpus(ctx) << (partition ? " GPU(s), D row-partitioned: query host->host " : " GPU(s): query host->host ") << tm.host_ms << " ms, of it on the device " << tm.query_ms
               << " ms; data upload+index " << tm.load_ms << " ms)" << std::endl;
     hvs_destroy(ctx);
 

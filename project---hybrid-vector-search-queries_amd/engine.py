@@ -72,6 +72,17 @@ class CompactInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class PartitionInfo(C.Structure):
+    """hvs_partition_info (include/hvs.h)."""
+    _fields_ = [("n_parts", C.c_uint32), ("row0", C.c_uint32 * 17), ("padded_queries", C.c_uint32), ("exchanged_bytes", C.c_uint64),
+                ("exchange_ms", C.c_double), ("merge_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["row0"] = list(self.row0[:self.n_parts + 1])
+        return d
+
+
 def library_path():
     return _LIB
 
@@ -209,6 +220,9 @@ def library():
         "hvs_compact_stats": (C.c_int, [vp, C.POINTER(CompactInfo)]),
         "hvs_trim_rows": (C.c_int, [vp]),
         "hvs_compact_plan": (None, [_u64p, C.c_uint32, _u32p, _u32p, _u32p]),
+        "hvs_create_partitioned": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_int), C.c_int]),
+        "hvs_partition_stats": (C.c_int, [vp, C.POINTER(PartitionInfo)]),
+        "hvs_partition_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -294,15 +308,39 @@ def compact_plan(live, want_map=True):
     return int(n_live.value), int(first_dead.value), (out[:int(n_live.value)].copy() if want_map else None)
 
 
+def partition_plan(n, n_parts, k, sample_proportion):
+    """hvs_partition_plan: (row0[n_parts + 1], sn, local_sn[n_parts]) of a row-partitioned context over n rows, or None
+    when the plan is refused (n_parts outside 1..16, or a part with fewer than k rows; nothing is written then)."""
+    m = max(0, min(int(n_parts), 16))
+    row0 = np.full(m + 2, 0xFFFFFFFF, np.uint32)
+    local = np.full(m + 1, 0xFFFFFFFF, np.uint32)
+    sn = C.c_uint32(0xFFFFFFFF)
+    rc = library().hvs_partition_plan(int(n), int(n_parts), int(k), float(sample_proportion), _up(row0), C.byref(sn), _up(local))
+    if rc != 0:
+        if (row0 != 0xFFFFFFFF).any() or (local != 0xFFFFFFFF).any() or sn.value != 0xFFFFFFFF:
+            raise HvsError(-1, "hvs_partition_plan wrote its outputs although it refused the plan")
+        return None
+    if row0[m + 1] != 0xFFFFFFFF or local[m] != 0xFFFFFFFF:
+        raise HvsError(-1, "hvs_partition_plan wrote past its outputs")
+    return row0[:m + 1].copy(), int(sn.value), local[:m].copy()
+
+
 class Engine:
     """One hvs_ctx.  Engine(device): one GPU.  Engine(n_gpus=N) (0 = all visible) or Engine(devices=[...]): the
     multi-GPU context of hvs_create_multi / hvs_create_on_devices -- D replicated, the queries of a call partitioned,
-    every GPU writing its slice of the result (a device index may repeat: virtual ranks on one GPU)."""
+    every GPU writing its slice of the result (a device index may repeat: virtual ranks on one GPU).
+    Engine(devices=[...], partition=True): the row-partitioned context of hvs_create_partitioned -- D cut into one row range per
+    entry of `devices`, every part answering all queries, the partial answers merged (same answers as one GPU)."""
 
-    def __init__(self, device=-1, n_gpus=None, devices=None):
+    def __init__(self, device=-1, n_gpus=None, devices=None, partition=False):
         self._lib = library()
         h = C.c_void_p()
-        if devices is not None:
+        if partition:
+            if devices is None:
+                raise HvsError(-1, "partition=True needs devices=[...]")
+            arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+            rc = self._lib.hvs_create_partitioned(C.byref(h), arr, len(devices))
+        elif devices is not None:
             arr = (C.c_int * len(devices))(*[int(d) for d in devices])
             rc = self._lib.hvs_create_on_devices(C.byref(h), arr, len(devices))
         elif n_gpus is not None:
@@ -320,6 +358,12 @@ class Engine:
     def set_gather(self, mode):
         """0 = every GPU copies its block into its slice of the caller's array, 1 = peer gather to GPU 0 first."""
         self._ck(self._lib.hvs_set_gather(self._h, int(mode)))
+
+    def partition_stats(self):
+        """hvs_partition_stats: the row plan and the exchange / merge figures of the last call (partitioned contexts only)."""
+        p = PartitionInfo()
+        self._ck(self._lib.hvs_partition_stats(self._h, C.byref(p)))
+        return p
 
     def reserve(self, nq):
         """Allocate query/result buffers and the batch workspace for calls of up to nq queries now."""
