@@ -27,10 +27,7 @@ Wrong queries per mutant, of 64 per set (MI355X; the production library: none):
                                                   DROP=4 (clip)  b 63
 """
 import importlib
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -77,8 +74,6 @@ for name, engine, rot in spec['runs']:
 print('RESULT ' + json.dumps(out))
 """
 
-_stopped = []   # set once a child ended abnormally: nothing more is started
-
 
 def _tag(name, engine, rot):
     return "%s-%d-%s" % (name, engine, rot)
@@ -98,31 +93,10 @@ def sets(tmp_path_factory):
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """The mutant builds, compiled in parallel: engine.HIPCC_FLAGS plus the switch."""
-    d = tmp_path_factory.mktemp("mutants")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = os.path.join(os.path.dirname(PKG.library_path()), "hvs.hip")
-    procs = {}
-    for name, (flags, _) in MUTANTS.items():
-        lib = str(d / ("libhvs_%s.so" % name))
-        cmd = [hipcc] + PKG.engine.HIPCC_FLAGS + flags + [src, "-o", lib]
-        procs[name] = (lib, subprocess.Popen(cmd, cwd=os.path.dirname(src), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                                             text=True))
-    libs = {}
-    for name, (lib, p) in procs.items():
-        try:
-            log, _ = p.communicate(timeout=900)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            p.communicate()
-            pytest.fail("building mutant %s timed out" % name)
-        assert p.returncode == 0 and os.path.exists(lib), (name, log[-2000:])
-        libs[name] = lib
-    return libs
+    return T.build_variant_libs(tmp_path_factory.mktemp("mutants"), {name: flags for name, (flags, _) in MUTANTS.items()})
 
 
 def _run_child(sets, runs, lib=None, shape="16"):
-    if _stopped:
-        pytest.fail("an earlier child process ended abnormally (%s); nothing more is started" % _stopped[0])
     data_dir, _ = sets
     out_dir = data_dir / ("out_%s_%s" % (os.path.basename(lib) if lib else "production", shape))
     out_dir.mkdir(exist_ok=True)
@@ -132,20 +106,7 @@ def _run_child(sets, runs, lib=None, shape="16"):
         env["HVS_LIB"] = lib
     else:
         env.pop("HVS_LIB", None)
-    spec = json.dumps(dict(dir=str(data_dir), out=str(out_dir), runs=runs))
-    try:
-        r = subprocess.run([sys.executable, "-c", _CHILD, spec], capture_output=True, text=True, env=env, cwd=T.REPO,
-                           timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stopped.append("time limit, %s" % (lib or "production"))
-        pytest.fail("child process timed out (%s)" % (lib or "production"))
-    if r.returncode != 0:
-        if r.returncode < 0 or r.returncode > 128:
-            _stopped.append("exit %d, %s" % (r.returncode, lib or "production"))
-        pytest.fail("child exited %d:\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
-    line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
-    assert line, r.stdout[-2000:]
-    timing = json.loads(line[-1][7:])
+    timing = T.run_child(_CHILD, dict(dir=str(data_dir), out=str(out_dir), runs=runs), env, lib or "production", CHILD_TIMEOUT)
     res = {}
     for name, engine, rot in runs:
         tag = _tag(name, engine, rot)

@@ -1,0 +1,233 @@
+"""The filters' selectivity: `rescored_pairs` and `retry_queries` of every filter engine against the host model of
+tests/selectivity_model.py (what the model restates and how its bracket is made: that module's docstring; why the assertions
+below are sharp: tests/test_selectivity_model_cpu.py, conditions (a) to (e)).
+
+Every answer of every engine is pinned bit for bit elsewhere; a band that is too small is caught by tests/test_filter_bounds.py.
+A band that is too WIDE, a threshold one level late, an order statistic from the wrong grid point, a seen fraction counted from
+the radices instead of the query's own range or a merge that forgets to lower tau returns identical bits and only hands more
+rows to hvs_k_rescore, or sends more queries through a retry batch.  Here, per case (selectivity_model.CASES: gen-v1 rows at
+n = 32768 (K = 2) and n = 70001 (K = 3, ragged last block), k = 37, sample_proportion = 0.5, queries outside the INT8 box, FP16
+on PCA-like rows; 96 queries of all four types plus 16 type-3 queries of 150-400 rows), engine (INT8 plain in both operand
+layouts, INT8 rotated, BF16, FP16) and regime:
+
+* the requested engine ran, HVS_TIMING_I8_ROTATED is as asked, the answers are bit-equal to the oracle -- counts are asserted
+  only after that;
+* proven thresholds (HVS_GUESS_MID=256): no retry, `fallback_queries` = the model's exact list, sum lo <= rescored_pairs <= sum hi;
+* guessed thresholds, at the batch's default target and at HVS_GUESS_PFAIL=1: `retry_queries` and hvs_last_reruns equal the
+  model's retry set exactly (it depends on exact distances only), rescored_pairs lies in the bracket summed over the first
+  pass and the retry pass;
+* a build with -DHVS_MUTANT_BAND_SCALE=1.25 answers every case correctly, lands ABOVE the production bracket and inside the
+  model's own bracket for that band: the production assertions would fail on a filter that is merely too generous.  FP16 is
+  left out of it (the band x 1.25 moves its count by 2 bracket widths: test_conditions_of_the_gpu_cases has the numbers).
+
+Queries on a grid edge of the guess table (model: `excluded`) are not sent.  Each context reserves room for RESERVE_NQ queries
+(hvs_reserve) before its call, so that a batch of 112 gets lists of 4096 keys: under proven thresholds a type-0 query appends
+up to 1920 keys at the radix-16 level, and a fresh context's 1024 would send it to a retry batch for its list's sake.
+
+Every library and environment runs in a child process of its own (the settings are read when the library loads), one at a
+time, under a time limit; after a child that died or timed out nothing more is started.
+
+Measured against modelled (MI355X), rescored_pairs [sum lo, sum hi] and retried queries, INT8 in the 16x16x64 layout:
+  case    format   proven                      default                    reckless (retried)
+  v1_32k  i8      193548 [193545, 193551]     39473 [39470, 39473]        57940 [57937, 57943] (21)
+  v1_32k  i8_rot  227981 [227956, 228012]     54184 [54171, 54196]        73277 [73269, 73293] (21)
+  v1_32k  bf16    183801 [183748, 183858]     35638 [35620, 35658]        53918 [53896, 53940] (21)
+  v1_70k  i8      207561 [207556, 207567]     41778 [41774, 41779]        49671 [49669, 49673] (15)
+  v1_70k  i8_rot  262205 [262164, 262255]     60571 [60555, 60586]        68580 [68566, 68599] (15)
+  v1_70k  bf16    192775 [192693, 192867]     37212 [37188, 37244]        44908 [44877, 44932] (15)
+  k37     i8      78691 [78691, 78693]        -                           -
+  k37     bf16    72998 [72961, 73024]        -                           -
+  half    i8      323962 [323957, 323967]     75568 [75567, 75570]        71975 [71973, 71978] (9)
+  half    i8_rot  370205 [370170, 370230]     99727 [99709, 99739]        92186 [92168, 92191] (9)
+  half    bf16    310637 [310566, 310702]     69146 [69112, 69189]        66580 [66552, 66619] (9)
+  out     i8      188871 [188868, 188873]     -                           54671 [54670, 54674] (19)
+  f16     f16     182691 [182656, 182725]     34715 [34698, 34735]        48746 [48728, 48767] (18)
+(the 32x32x32 layout gave the same counts in every plain INT8 case; proven and default retried none; the out case's 4 far queries
+went to the exact engine in every regime)
+Band x 1.25 build, measured and [sum lo, sum hi] of the model with that band:
+  v1_32k  i8      198176 [198174, 198180]     41403 [41401, 41405]
+  v1_32k  i8_rot  243133 [243105, 243157]     61280 [61266, 61293]
+  v1_32k  bf16    185848 [185794, 185893]     36390 [36368, 36413]
+  v1_70k  i8      214703 [214700, 214710]     44063 [44062, 44065]
+  v1_70k  i8_rot  286977 [286922, 287021]     69950 [69930, 69965]
+  v1_70k  bf16    195834 [195752, 195929]     38141 [38116, 38171]
+  k37     i8      81416 [81414, 81417]        -
+  k37     bf16    74225 [74180, 74264]        -
+  half    i8      330344 [330339, 330350]     78852 [78849, 78853]
+  half    i8_rot  390100 [390074, 390135]     110944 [110927, 110972]
+  half    bf16    313516 [313433, 313584]     70431 [70390, 70459]
+  out     i8      194342 [194339, 194344]     -
+"""
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import bound_model as BM
+import hvs_testlib as T
+import selectivity_model as SM
+
+pytestmark = pytest.mark.gpu
+PKG = importlib.import_module("project---hybrid-vector-search-queries_amd")
+ENGINE = {BM.PLAIN_I8: (PKG.ENGINE_MFMA_I8, "0"), BM.ROT_I8: (PKG.ENGINE_MFMA_I8, "1"), BM.BF16: (PKG.ENGINE_MFMA_FILTER, None),
+          BM.FP16: (PKG.ENGINE_MFMA_F16, None)}
+HVS_TIMING_I8_ROTATED = 4
+CHILD_TIMEOUT = 300
+
+_CHILD = r"""
+import importlib, json, os, sys, numpy as np
+sys.path.insert(0, '.')
+PKG = importlib.import_module('project---hybrid-vector-search-queries_amd')
+spec = json.loads(sys.argv[1])
+out = {}
+for tag, data, engine, rot, k, sp in spec['runs']:
+    z = np.load(os.path.join(spec['dir'], data + '.npz'))
+    keep = np.load(os.path.join(spec['dir'], tag + '.keep.npy'))
+    if rot is None:
+        os.environ.pop('HVS_I8_ROTATE', None)
+    else:
+        os.environ['HVS_I8_ROTATE'] = rot
+    with PKG.Engine(0) as e:
+        e.set_engine(engine)
+        e.set_k(k)
+        e.load_data(z['nodes'])
+        e.reserve(spec['reserve'])
+        ids, d = e.query(z['queries'][keep], sp)
+        t = e.last_timing()
+        reruns = [e.last_reruns(0).tolist(), e.last_reruns(1).tolist()]
+    np.savez(os.path.join(spec['out'], tag + '.npz'), ids=ids, dists=d)
+    out[tag] = dict(engine=int(t.engine), fallback=int(t.fallback_queries), retry=int(t.retry_queries), flags=int(t.flags),
+                    rescored=int(t.rescored_pairs), exact_list=reruns[0], retry_list=reruns[1])
+print('RESULT ' + json.dumps(out))
+"""
+
+
+@pytest.fixture(scope="module")
+def work_dir(tmp_path_factory):
+    d = tmp_path_factory.mktemp("selectivity")
+    for case in SM.CASES:
+        nodes, queries = SM.case_data(case)
+        np.savez(d / (case.name + ".npz"), nodes=nodes, queries=queries)
+    return d
+
+
+@pytest.fixture(scope="module")
+def wide_band_lib(tmp_path_factory):
+    """The one extra build: the library's own source with the band x 1.25, through the existing switch."""
+    return T.build_variant_libs(tmp_path_factory.mktemp("wide_band"), {"band_scale_1.25": ["-DHVS_MUTANT_BAND_SCALE=%s" % SM.MUTANT_SCALE]})["band_scale_1.25"]
+
+
+_refs = {}
+
+
+def _reference(case):
+    """The oracle's answers of a case, computed once."""
+    if case.name not in _refs:
+        nodes, queries = SM.case_data(case)
+        with T.oracle_k(case.k):
+            _refs[case.name] = T.oracle_query(nodes, queries, case.sp)
+    return _refs[case.name]
+
+
+def _runs(regime, shape, mutant):
+    runs = []
+    for case in SM.CASES:
+        if regime not in case.regimes:
+            continue
+        for fmt in case.fmts:
+            if (shape == "32" and fmt != BM.PLAIN_I8) or (mutant and fmt == BM.FP16):
+                continue
+            runs.append((case, fmt))
+    return runs
+
+
+def _run(work_dir, regime, shape, lib=None):
+    """One child: every (case, format) of the regime; returns [(case, fmt, keep, model walk, ids, dists, timing)]."""
+    runs = _runs(regime, shape, lib is not None)
+    label = "%s-%s-%s" % ("wide" if lib else "production", regime, shape)
+    out_dir = work_dir / label
+    out_dir.mkdir(exist_ok=True)
+    spec_runs, keeps = [], []
+    for case, fmt in runs:
+        w = SM.case_walk(case, fmt, regime)            # the production model decides what is sent, for either library
+        keep = np.nonzero(~w["excluded"])[0]
+        tag = "%s-%s-%s" % (label, case.name, fmt)
+        np.save(work_dir / (tag + ".keep.npy"), keep)
+        engine, rot = ENGINE[fmt]
+        spec_runs.append((tag, case.name, engine, rot, case.k, case.sp))
+        keeps.append((tag, keep, w))
+    env = dict(os.environ, HVS_I8_SHAPE=shape)
+    for name in ("HVS_I8_ROTATE", "HVS_LIB", "HVS_GUESS_MID", "HVS_GUESS_PFAIL", "HVS_RADICES"):
+        env.pop(name, None)
+    env.update(SM.REGIMES[regime]["env"])
+    if lib:
+        env["HVS_LIB"] = lib
+    timing = T.run_child(_CHILD, dict(dir=str(work_dir), out=str(out_dir), runs=spec_runs, reserve=SM.RESERVE_NQ), env, label, CHILD_TIMEOUT)
+    res = []
+    for (case, fmt), (tag, keep, w) in zip(runs, keeps):
+        z = np.load(out_dir / (tag + ".npz"))
+        res.append((case, fmt, keep, w, z["ids"], z["dists"], timing[tag]))
+    return res
+
+
+def _check_answers(case, fmt, keep, ids, dists, t):
+    """The requested engine, the rotation flag, and answers bit-equal to the oracle's."""
+    nodes, queries = SM.case_data(case)
+    ref_ids, ref_d = _reference(case)
+    engine, rot = ENGINE[fmt]
+    assert t["engine"] == engine, (case.name, fmt, t)
+    if rot is not None:
+        assert bool(t["flags"] & HVS_TIMING_I8_ROTATED) == (rot == "1"), (case.name, fmt, t)
+    assert np.array_equal(np.sort(dists, axis=1).view(np.uint32), ref_d[keep].view(np.uint32)), (case.name, fmt)
+    with T.oracle_k(case.k):
+        T.check_parity(nodes, queries[keep], ids, ref_ids[keep], case.sp, got_dists=dists)
+
+
+def _check_reruns(case, fmt, regime, keep, w, t):
+    """retry_queries / fallback_queries and the two re-run lists against the model's sets (indices of the call sent)."""
+    want_retry = np.nonzero(w["retry"][keep])[0].tolist()
+    want_exact = np.nonzero(w["exact"][keep])[0].tolist()
+    if regime == "proven":
+        assert t["retry"] == 0 and not want_retry, (case.name, fmt, t["retry"], want_retry)
+    assert sorted(t["retry_list"]) == want_retry and t["retry"] == len(want_retry), (case.name, fmt, regime, sorted(t["retry_list"]), want_retry)
+    assert sorted(t["exact_list"]) == want_exact and t["fallback"] == len(want_exact), (case.name, fmt, regime, sorted(t["exact_list"]), want_exact)
+
+
+@pytest.mark.parametrize("shape", ["16", "32"])
+@pytest.mark.parametrize("regime", ["proven", "default", "reckless"])
+def test_production_counts_lie_in_the_model_bracket(work_dir, regime, shape):
+    results = _run(work_dir, regime, shape)
+    bad = []
+    for case, fmt, keep, w, ids, dists, t in results:
+        _check_answers(case, fmt, keep, ids, dists, t)
+    for case, fmt, keep, w, ids, dists, t in results:
+        lo, hi = SM.totals(w)
+        inside = lo <= t["rescored"] <= hi
+        print("%-8s I8_SHAPE=%s %-7s %-6s rescored %7d  model [%7d, %7d]  retried %2d (model %2d)  exact %d (model %d)  sent %d%s"
+              % (regime, shape, case.name, fmt, t["rescored"], lo, hi, t["retry"], int(w["retry"][keep].sum()), t["fallback"],
+                 int(w["exact"][keep].sum()), keep.size, "" if inside else "   <-- OUTSIDE"))
+        _check_reruns(case, fmt, regime, keep, w, t)
+        if not inside:
+            bad.append((case.name, fmt, t["rescored"], lo, hi))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("regime", ["proven", "default"])
+def test_a_band_too_wide_is_seen(work_dir, wide_band_lib, regime):
+    """-DHVS_MUTANT_BAND_SCALE=1.25 answers correctly and re-scores more than the production bracket allows."""
+    results = _run(work_dir, regime, "16", lib=wide_band_lib)
+    for case, fmt, keep, w, ids, dists, t in results:
+        _check_answers(case, fmt, keep, ids, dists, t)
+    bad = []
+    for case, fmt, keep, w, ids, dists, t in results:
+        m = SM.case_walk(case, fmt, regime, SM.MUTANT_SCALE)
+        lo, hi = SM.totals(w)
+        mlo, mhi = SM.totals(m, ~w["excluded"])
+        ok = hi < t["rescored"] and mlo <= t["rescored"] <= mhi
+        print("band x %.2f %-8s %-7s %-6s rescored %7d  production model [%7d, %7d]  model of the wide band [%7d, %7d]%s"
+              % (SM.MUTANT_SCALE, regime, case.name, fmt, t["rescored"], lo, hi, mlo, mhi, "" if ok else "   <-- NOT AS MODELLED"))
+        _check_reruns(case, fmt, regime, keep, m, t)
+        if not ok:
+            bad.append((case.name, fmt, t["rescored"], (lo, hi), (mlo, mhi)))
+    assert not bad, bad
