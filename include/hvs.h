@@ -401,7 +401,7 @@ void hvs_compact_plan(const uint64_t *live_bits, uint32_t n, uint32_t *n_live, u
  *    HVS_EINVAL and leaves the context as it was.
  *  - Not supported (yet) on a partitioned context, HVS_ESTATE and nothing changes: row deletion, append, update and compaction
  *    (hvs_delete_rows, hvs_set_row_mask, hvs_get_row_mask, hvs_append_rows, hvs_reserve_rows, hvs_reindex, hvs_set_tail_limit,
- *    hvs_update_rows, hvs_compact, hvs_trim_rows), their *_stats functions, and hvs_set_gather.  The functions that say
+ *    hvs_update_rows, hvs_compact, hvs_trim_rows), their *_stats functions, hvs_set_queries_from_rows and hvs_set_gather.  The functions that say
  *    "single-GPU contexts only" refuse it as they refuse any multi-GPU context.
  *  - A call that fails half-way reports the failing part like any multi-GPU call and leaves no kernel running.
  */
@@ -418,6 +418,59 @@ int hvs_partition_stats(hvs_ctx *ctx, hvs_partition_info *out);   /* HVS_ESTATE 
    local_sn[r] = min(max(sn, row0[r]), row0[r+1]) - row0[r] = rows of part r inside the sampled prefix.  Returns 0, or HVS_EINVAL
    (n_parts outside 1..16, or a part with fewer than k rows). */
 int hvs_partition_plan(uint32_t n, uint32_t n_parts, uint32_t k, float sample_proportion, uint32_t *row0, uint32_t *sn, uint32_t *local_sn);
+
+/* ---- device-resident inputs: D and queries from GPU memory, queries from stored rows ------------- */
+
+/*
+ * The input side of the device-resident calls above (hvs_query_resident, hvs_export_results_device, hvs_stream_wait): rows that
+ * already sit in HBM -- a model's embeddings, a collective's receive buffer, another kernel's output -- enter the context
+ * without a round trip through host memory.  Every context kind accepts the two *_device calls.
+ *
+ * The buffer: plain device memory (hipMalloc and what is built on it) of ANY GPU visible to the process; the call finds the GPU
+ * with hipPointerGetAttributes, and the pointer may lie anywhere inside an allocation.  Host memory of any kind -- pageable,
+ * pinned, managed -- is HVS_EINVAL: nothing changes (resident queries, results and D are as they were) and the runtime's own
+ * error is cleared, the next call does not trip over it.  `stream`: a hipStream_t of the buffer's GPU, NULL = its null stream;
+ * the work enqueued on it so far is complete before the buffer is read.  The calls block: they return when the copies are done
+ * (as hvs_upload_queries / hvs_load_data do), the buffer is only read and is the caller's again on return.
+ *
+ * hvs_set_queries_device(ctx, d_q_rows, nq, stream): afterwards the context is in every respect the context after
+ * hvs_upload_queries of the same bytes -- the same hvs_download_queries, the same owner ranges on a multi-GPU context, the same
+ * answers from hvs_query_resident.  One GPU: one device-to-device (or peer) copy; hvs_create_multi contexts: every GPU takes its
+ * range of the queries straight from the buffer; row-partitioned contexts: every part takes all nq rows.  nq == 0: HVS_OK and an
+ * empty resident set (the pointer is not looked at); d_q_rows == NULL with nq > 0: HVS_EINVAL.
+ *
+ * hvs_load_data_device(ctx, d_rows, n, stream): afterwards the context is the context after hvs_load_data of the same bytes --
+ * the same checks before anything changes (n >= k; n >= n_parts * k on a partitioned context), the same resets (mask, tail,
+ * stale set, counters, hvs_last_timing), the same index; hvs_timing.load_ms is the copy plus the index build.  Every GPU copies
+ * from the buffer itself: all n rows, or, as part r of a partitioned context, its rows shard_range(n, r, n_parts) and its replica
+ * of the last min(n, 256) rows.
+ *
+ * hvs_set_queries_from_rows(ctx, ids, first_id, nq, type, dt): "the neighbours of rows I already stored".  Resident query i is
+ * built on the device from row ids[i] (ids == NULL: row first_id + i) as D holds it NOW -- the contents hvs_update_rows left,
+ * appended rows included, the new ids after hvs_compact --: its 100 vector floats are the row's, bit for bit, and its
+ * attributes follow the row's category C and timestamp T by `type`, each of l = T - dt and r = T + dt being one IEEE f32
+ * operation (a NaN that comes out of it has an unspecified payload: such a query matches nothing either way).  The query set is
+ * a snapshot: a later change of D does not touch it.  The answers are those of hvs_upload_queries of the rows hvs_row_query
+ * builds from hvs_download_data.  Self-matches are not removed: the row is in D, so with HVS_ROWQ_KNN a live row with finite
+ * components is its own nearest neighbour at distance 0, and the other types find it whenever it lies inside the sampled prefix.
+ * ids: HOST memory, duplicates are fine.  HVS_EINVAL and nothing changes (resident queries and results are as they were): type
+ * outside 0..3, dt negative or NaN, an id >= n, an id that is deleted under the live-row mask ("as if it had never been in D").
+ * No data loaded: HVS_ESTATE.  nq == 0: HVS_OK and an empty resident set.  hvs_create_multi contexts: every GPU builds its range
+ * of the queries from its own replica.  Row-partitioned contexts: HVS_ESTATE, not supported (yet) -- a query's source row lives
+ * on one part and every part needs every query; that exchange is a later step.
+ *
+ * hvs_row_query: the host arithmetic of that rule for one row (no GPU, no context; type in 0..3) -- the same function the kernel
+ * calls for the four attribute floats.
+ */
+int hvs_set_queries_device(hvs_ctx *ctx, const float *d_q_rows /* device, nq x 104 */, uint32_t nq, void *stream);
+int hvs_load_data_device(hvs_ctx *ctx, const float *d_rows /* device, n x 102 */, uint32_t n, void *stream);
+#define HVS_ROWQ_KNN      0   /* [0, -1, -1, -1]          */
+#define HVS_ROWQ_SAME_C   1   /* [1,  C, -1, -1]          */
+#define HVS_ROWQ_T_WINDOW 2   /* [2, -1, T - dt, T + dt]  */
+#define HVS_ROWQ_BOTH     3   /* [3,  C, T - dt, T + dt]  */
+int hvs_set_queries_from_rows(hvs_ctx *ctx, const uint32_t *ids /* host, nq entries, or NULL */, uint32_t first_id, uint32_t nq,
+                              int type, float dt);
+void hvs_row_query(const float *row /* 102 */, int type, float dt, float *out_q /* 104 */);
 
 #ifdef __cplusplus
 }

@@ -2406,6 +2406,50 @@ int leaf_load_data_from_peer(hvs_ctx* c, const hvs_ctx* src)
     return finish_data(c);
 }
 
+// ---- inputs from device memory (include/hvs.h "device-resident inputs") ----
+// A caller's buffer: plain device memory of a visible GPU (its index goes to *dev), anywhere inside an allocation.  Host memory
+// -- pageable, pinned or managed -- is refused before anything changes, and the runtime's error for a pointer it does not know
+// is taken off HIP's last-error slot.
+int device_of_buffer(hvs_ctx* c, const void* p, const char* fn, int* dev)
+{
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.isManaged)
+        return fail(c, HVS_EINVAL, std::string(fn) + ": the buffer is not plain device memory (host, pinned and managed memory go through the host entry points)");
+    *dev = a.device;
+    return HVS_OK;
+}
+
+// ... and the work the caller has enqueued on `stream` (a stream of that GPU; NULL: its null stream) is complete: the buffer
+// holds what the copies are about to read.  A host wait: the calls block until their copies are done anyway.
+int wait_for_producer(hvs_ctx* c, int dev, void* stream)
+{
+    HVS_HIP(c, hipSetDevice(dev));
+    HVS_HIP(c, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return HVS_OK;
+}
+
+// `bytes` from a device buffer of GPU `src_dev` to this context's GPU, on its stream (same GPU: a device-to-device copy)
+int copy_from_device(hvs_ctx* c, void* dst, const void* src, int src_dev, size_t bytes)
+{
+    if (bytes) HVS_HIP(c, hipMemcpyPeerAsync(dst, c->device, src, src_dev, bytes, c->stream));
+    return HVS_OK;
+}
+
+// hvs_load_data_device: leaf_load_data_from_peer with the caller's buffer in the place of a peer's D
+int leaf_load_data_device(hvs_ctx* c, const float* d_rows, int src_dev, uint32_t n)
+{
+    int rc = begin_data(c, n);
+    if (rc) return rc;
+    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    if ((rc = copy_from_device(c, c->d_data, d_rows, src_dev, (size_t)n * HVS_DCOLS * sizeof(float)))) return rc;
+    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->n = n;
+    return finish_data(c);
+}
+
 // (`first_row`: the place of the context's row 0 in the gen-v1 stream -- a part of a row-partitioned context)
 int leaf_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t ncat, uint64_t first_row = 0)
 {
@@ -2437,6 +2481,43 @@ int leaf_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
     if (rc) return rc;
     if ((rc = upload_rows(c, c->d_q, q_rows, (size_t)nq * HVS_QCOLS))) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->nq = nq;
+    return HVS_OK;
+}
+
+// hvs_set_queries_device: the same from a device buffer of GPU `src_dev` (checked and waited for by the caller)
+int leaf_set_queries_device(hvs_ctx* c, const float* d_q_rows, int src_dev, uint32_t nq)
+{
+    int rc = leaf_begin_queries(c, nq);
+    if (rc) return rc;
+    if ((rc = copy_from_device(c, c->d_q, d_q_rows, src_dev, (size_t)nq * HVS_QCOLS * sizeof(float)))) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->nq = nq;
+    return HVS_OK;
+}
+
+// hvs_set_queries_from_rows: query j from row ids[j] (ids == nullptr: row first_id + j) of D as it is now; ids, type and dt
+// checked by the caller.  The id list travels through the staging buffer of hvs_delete_rows' id lists.
+int leaf_set_queries_from_rows(hvs_ctx* c, const uint32_t* ids, uint32_t first_id, uint32_t nq, int type, float dt)
+{
+    HvsRowSet& s = c->rs;
+    int rc = leaf_begin_queries(c, nq);
+    if (rc) return rc;
+    if (nq) {
+        if (ids) {
+            if (nq > s.mask_ids_cap) {
+                s.mask_ids_cap = 0;
+                if ((rc = dev_alloc(c, &s.d_mask_ids, (size_t)nq))) return rc;
+                s.mask_ids_cap = nq;
+            }
+            HVS_HIP(c, hipMemcpyAsync(s.d_mask_ids, ids, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        }
+        hipLaunchKernelGGL(hvs_k_queries_from_rows, dim3(hvs_ceil_div(nq, 4u * HVS_ROWQ_WAVE_ROWS)), dim3(256), 0, c->stream,
+                           reinterpret_cast<const uint2*>(c->d_data), ids ? s.d_mask_ids : nullptr, first_id, nq, type, dt,
+                           reinterpret_cast<uint2*>(c->d_q));
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the id list is the caller's)
     c->nq = nq;
     return HVS_OK;
 }
@@ -3435,12 +3516,15 @@ int part_download_results(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* out_id
     });
 }
 
-// the tail replica of every part after its rows are in place: from the caller's rows, or generated
-int part_fill_tail(hvs_ctx* root, hvs_ctx* k, const float* rows, uint64_t seed, int profile, uint32_t ncat)
+// the tail replica of every part after its rows are in place: from the caller's rows (host memory, or a device buffer of GPU
+// src_dev >= 0), or generated
+int part_fill_tail(hvs_ctx* root, hvs_ctx* k, const float* rows, int src_dev, uint64_t seed, int profile, uint32_t ncat)
 {
     const uint32_t n = root->part_n, t = part_tail_rows(root);
     if (rows) {
-        const int rc = upload_rows(k, k->part.d_tail, rows + (size_t)(n - t) * HVS_DCOLS, (size_t)t * HVS_DCOLS);
+        const float* last = rows + (size_t)(n - t) * HVS_DCOLS;
+        const int rc = src_dev >= 0 ? copy_from_device(k, k->part.d_tail, last, src_dev, (size_t)t * HVS_DCOLS * sizeof(float))
+                                    : upload_rows(k, k->part.d_tail, last, (size_t)t * HVS_DCOLS);
         if (rc) return rc;
     } else {
         hipLaunchKernelGGL(hvs_k_gen_data, dim3(hvs_ceil_div(t * HVS_DCOLS, 256u)), dim3(256), 0, k->stream, k->part.d_tail,
@@ -3451,8 +3535,9 @@ int part_fill_tail(hvs_ctx* root, hvs_ctx* k, const float* rows, uint64_t seed, 
     return HVS_OK;
 }
 
-// hvs_load_data (rows != nullptr) / hvs_gen_data of a partitioned context: part r takes ITS rows over its own link
-int part_load(hvs_ctx* c, const float* rows, uint32_t n, uint64_t seed, int profile, uint32_t ncat)
+// hvs_load_data (rows != nullptr) / hvs_load_data_device (rows in a device buffer of GPU src_dev >= 0) / hvs_gen_data of a
+// partitioned context: part r takes ITS rows over its own link
+int part_load(hvs_ctx* c, const float* rows, int src_dev, uint32_t n, uint64_t seed, int profile, uint32_t ncat)
 {
     const uint32_t N = (uint32_t)c->kids.size();
     if (n / N < c->k) return fail(c, HVS_EINVAL, "row-partitioned context: every part needs at least k rows (n >= n_parts * k)");
@@ -3460,8 +3545,10 @@ int part_load(hvs_ctx* c, const float* rows, uint32_t n, uint64_t seed, int prof
     const int rc = for_each_leaf(c, [&](uint32_t r) -> int {
         hvs_ctx* k = c->kids[r];
         const uint32_t a = c->part_row0[r], cnt = c->part_row0[r + 1] - a;
-        const int r2 = rows ? leaf_load_data(k, rows + (size_t)a * HVS_DCOLS, cnt) : leaf_gen_data(k, cnt, seed, profile, ncat, a);
-        return r2 ? r2 : part_fill_tail(c, k, rows, seed, profile, ncat);
+        const float* mine = rows ? rows + (size_t)a * HVS_DCOLS : nullptr;
+        const int r2 = !rows ? leaf_gen_data(k, cnt, seed, profile, ncat, a)
+                             : src_dev >= 0 ? leaf_load_data_device(k, mine, src_dev, cnt) : leaf_load_data(k, mine, cnt);
+        return r2 ? r2 : part_fill_tail(c, k, rows, src_dev, seed, profile, ncat);
     });
     if (rc) {
         part_quiesce(c);
@@ -3729,7 +3816,7 @@ int hvs_load_data(hvs_ctx* c, const float* rows, uint32_t n)
     if (!c) return HVS_EINVAL;
     if (!rows) return fail(c, HVS_EINVAL, "hvs_load_data: rows is NULL");
     if (c->kids.empty()) return leaf_load_data(c, rows, n);
-    if (c->partitioned) return part_load(c, rows, n, 0u, 0, 0u);
+    if (c->partitioned) return part_load(c, rows, -1, n, 0u, 0, 0u);
     // D reaches the GPUs in two parallel phases: every GPU uploads ITS slice of the rows over its own PCIe link, then takes
     // the other slices from its peers over xGMI (each pair has its own link) -- an all-gather by peer copies -- and builds
     // its index.  (Round 2 uploaded everything to GPU 0 and let 7 peers pull 4 GB each from it after its index build;
@@ -3776,12 +3863,27 @@ int hvs_load_data(hvs_ctx* c, const float* rows, uint32_t n)
     });
 }
 
+// Every GPU takes the rows straight from the caller's buffer (a part of a partitioned context: its own rows and the tail
+// replica): one copy per GPU over its own link to the source, no hop through a leaf that has them already.
+int hvs_load_data_device(hvs_ctx* c, const float* d_rows, uint32_t n, void* stream)
+{
+    if (!c) return HVS_EINVAL;
+    if (!d_rows) return fail(c, HVS_EINVAL, "hvs_load_data_device: d_rows is NULL");
+    int dev = 0;
+    int rc = device_of_buffer(c, d_rows, "hvs_load_data_device", &dev);
+    if (!rc) rc = wait_for_producer(c, dev, stream);
+    if (rc) return rc;
+    if (c->kids.empty()) return leaf_load_data_device(c, d_rows, dev, n);
+    if (c->partitioned) return part_load(c, d_rows, dev, n, 0u, 0, 0u);
+    return for_each_leaf(c, [&](uint32_t r) { return leaf_load_data_device(c->kids[r], d_rows, dev, n); });
+}
+
 int hvs_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t ncat)
 {
     if (!c) return HVS_EINVAL;
     if (ncat == 0) return fail(c, HVS_EINVAL, "hvs_gen_data: ncat must be > 0");
     if (c->kids.empty()) return leaf_gen_data(c, n, seed, profile, ncat);
-    if (c->partitioned) return part_load(c, nullptr, n, seed, profile, ncat);
+    if (c->partitioned) return part_load(c, nullptr, -1, n, seed, profile, ncat);
     return for_each_leaf(c, [&](uint32_t r) { return leaf_gen_data(c->kids[r], n, seed, profile, ncat); });
 }
 
@@ -3824,6 +3926,56 @@ int hvs_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
     cut_queries(c, nq);
     return for_each_leaf(c, [&](uint32_t r) {
         return leaf_upload_queries(c->kids[r], q_rows + (size_t)c->kid_q0[r] * HVS_QCOLS, c->kid_q0[r + 1] - c->kid_q0[r]);
+    });
+}
+
+int hvs_set_queries_device(hvs_ctx* c, const float* d_q_rows, uint32_t nq, void* stream)
+{
+    if (!c) return HVS_EINVAL;
+    if (!d_q_rows && nq) return fail(c, HVS_EINVAL, "hvs_set_queries_device: d_q_rows is NULL");
+    int dev = 0;
+    if (nq) {  // (an empty set reads nothing)
+        int rc = device_of_buffer(c, d_q_rows, "hvs_set_queries_device", &dev);
+        if (!rc) rc = wait_for_producer(c, dev, stream);
+        if (rc) return rc;
+    }
+    if (c->kids.empty()) return leaf_set_queries_device(c, d_q_rows, dev, nq);
+    cut_queries(c, nq);
+    if (c->partitioned)  // all queries on every part; the ranges are the owners'
+        return for_each_leaf(c, [&](uint32_t r) { return leaf_set_queries_device(c->kids[r], d_q_rows, dev, nq); });
+    return for_each_leaf(c, [&](uint32_t r) {
+        return leaf_set_queries_device(c->kids[r], d_q_rows + (size_t)c->kid_q0[r] * HVS_QCOLS, dev, c->kid_q0[r + 1] - c->kid_q0[r]);
+    });
+}
+
+void hvs_row_query(const float* row, int type, float dt, float* out_q)
+{
+    if (!row || !out_q) return;
+    hvs_row_query_attrs(row[0], row[1], type, dt, out_q[0], out_q[1], out_q[2], out_q[3]);
+    std::memcpy(out_q + 4, row + 2, (HVS_DCOLS - 2u) * sizeof(float));
+}
+
+int hvs_set_queries_from_rows(hvs_ctx* c, const uint32_t* ids, uint32_t first_id, uint32_t nq, int type, float dt)
+{
+    if (!c) return HVS_EINVAL;
+    HVS_NOT_PARTITIONED(c, "hvs_set_queries_from_rows");
+    if (type < HVS_ROWQ_KNN || type > HVS_ROWQ_BOTH) return fail(c, HVS_EINVAL, "hvs_set_queries_from_rows: type outside 0..3");
+    if (!(dt >= 0.0f)) return fail(c, HVS_EINVAL, "hvs_set_queries_from_rows: dt is negative or NaN");
+    const hvs_ctx* L = loaded_leaf(c, "hvs_set_queries_from_rows");
+    if (!L) return HVS_ESTATE;
+    if (!ids && (uint64_t)first_id + nq > L->n) return fail(c, HVS_EINVAL, "hvs_set_queries_from_rows: id outside [0, n)");
+    const std::vector<uint64_t>& live = L->rs.h_live;  // (empty: no mask set, every row live)
+    for (uint32_t i = 0; i < nq && (ids || !live.empty()); ++i) {
+        const uint32_t id = ids ? ids[i] : first_id + i;
+        if (id >= L->n) return fail(c, HVS_EINVAL, "hvs_set_queries_from_rows: id outside [0, n)");
+        if (!live.empty() && !((live[id >> 6] >> (id & 63u)) & 1ull))
+            return fail(c, HVS_EINVAL, "hvs_set_queries_from_rows: row " + std::to_string(id) + " is deleted");
+    }
+    if (c->kids.empty()) return leaf_set_queries_from_rows(c, ids, first_id, nq, type, dt);
+    cut_queries(c, nq);
+    return for_each_leaf(c, [&](uint32_t r) {  // each leaf builds its slice from its replica
+        const uint32_t a = c->kid_q0[r];
+        return leaf_set_queries_from_rows(c->kids[r], ids ? ids + a : nullptr, first_id + a, c->kid_q0[r + 1] - a, type, dt);
     });
 }
 

@@ -37,6 +37,56 @@ __global__ void hvs_k_scatter_rows(const float* __restrict__ src, const uint32_t
     D[(size_t)ids[j] * HVS_DCOLS + col] = src[(size_t)from[j] * HVS_DCOLS + col];
 }
 
+// hvs_set_queries_from_rows: the four attribute floats [type, v, l, r] of the query built from a row with
+// category C and timestamp T -- v = C where the type filters by category, l = T - dt and r = T + dt where it filters by time
+// (one IEEE f32 operation each), -1 where it does not.  `type` in 0..3 (host).  hvs_row_query (host) and
+// hvs_k_queries_from_rows (device) both go through here.
+__host__ __device__ __forceinline__ void hvs_row_query_attrs(float C, float T, int type, float dt, float& qt, float& v, float& l, float& r)
+{
+    qt = (float)type;
+    v = (type & 1) ? C : -1.0f;
+    l = (type & 2) ? T - dt : -1.0f;
+    r = (type & 2) ? T + dt : -1.0f;
+}
+
+// hvs_set_queries_from_rows: query j = [type, v, l, r, x0..x99] from row ids[j] of D (ids == nullptr: row first_id + j; ids < n
+// and live, checked by the host).  A gather of 408-byte rows into 416-byte rows in 8-byte pieces: of a query's 52 pieces the
+// first two are the attributes (computed from the row's piece 0 = [C, T]) and piece p >= 2 is the row's piece p - 1, bit for bit.
+// One wave per HVS_ROWQ_WAVE_ROWS consecutive queries, one piece per lane and query, every load issued before the first
+// store; the id is the same for the whole wave (a scalar load).  Lanes 52..63 sit out.
+#define HVS_ROW_U2 (HVS_DCOLS / 2u)   // 8-byte pieces per row
+#define HVS_QROW_U2 (HVS_QCOLS / 2u)  // ... per query row
+#define HVS_ROWQ_WAVE_ROWS 4u
+__global__ __launch_bounds__(256) void hvs_k_queries_from_rows(const uint2* __restrict__ D, const uint32_t* __restrict__ ids, uint32_t first_id,
+                                                              uint32_t nq, int type, float dt, uint2* __restrict__ Q)
+{
+    static_assert(HVS_DCOLS % 2u == 0u && HVS_QCOLS == HVS_DCOLS + 2u && HVS_QROW_U2 <= 64u, "rows are moved in 8-byte pieces, one per lane");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4u + (threadIdx.x >> 6)) * HVS_ROWQ_WAVE_ROWS);  // (wave-uniform)
+    if (q0 >= nq || lane >= HVS_QROW_U2) return;
+    const uint32_t piece = lane < 2u ? 0u : lane - 1u;
+    uint2 v[HVS_ROWQ_WAVE_ROWS];
+#pragma unroll
+    for (uint32_t i = 0; i < HVS_ROWQ_WAVE_ROWS; ++i) {
+        if (q0 + i < nq) {
+            const uint32_t id = ids ? ids[q0 + i] : first_id + q0 + i;
+            v[i] = D[(size_t)id * HVS_ROW_U2 + piece];
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < HVS_ROWQ_WAVE_ROWS; ++i) {
+        if (q0 + i < nq) {
+            uint2 o = v[i];
+            if (lane < 2u) {
+                float qt, qv, ql, qr;
+                hvs_row_query_attrs(__uint_as_float(v[i].x), __uint_as_float(v[i].y), type, dt, qt, qv, ql, qr);
+                o = lane == 0u ? make_uint2(__float_as_uint(qt), __float_as_uint(qv)) : make_uint2(__float_as_uint(ql), __float_as_uint(qr));
+            }
+            Q[(size_t)(q0 + i) * HVS_QROW_U2 + lane] = o;
+        }
+    }
+}
+
 // hvs_compact: the live rows among the source rows [a, b) of one chunk, packed in id order into `bounce`
 // (the host then copies them device-to-device to their place in D).  Not in place on purpose: row live[j] goes to place
 // j <= live[j], so a chunk's destination range may overlap its OWN source range (whenever few rows before it are dead) and a
@@ -46,7 +96,6 @@ __global__ void hvs_k_scatter_rows(const float* __restrict__ src, const uint32_t
 // (or to a row outside [a, b)) sits out.  A live row's place: `rank[w]` = live rows in front of word w (host-built), plus
 // the popcount of the word's bits below the row, minus rank_a = live rows in front of a.  `live`: bits past n are clear
 // and b <= n (host), so nothing outside D is read; at most b - a rows of `bounce` are written.
-#define HVS_ROW_U2 (HVS_DCOLS / 2u)  // 8-byte pieces per row
 __global__ __launch_bounds__(256) void hvs_k_compact_gather(const uint2* __restrict__ D, const uint32_t* __restrict__ live,
                                                            const uint32_t* __restrict__ rank, uint32_t a, uint32_t b, uint32_t rank_a,
                                                            uint2* __restrict__ bounce)

@@ -223,6 +223,10 @@ def library():
         "hvs_create_partitioned": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_int), C.c_int]),
         "hvs_partition_stats": (C.c_int, [vp, C.POINTER(PartitionInfo)]),
         "hvs_partition_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _u32p, _u32p]),
+        "hvs_set_queries_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
+        "hvs_load_data_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
+        "hvs_set_queries_from_rows": (C.c_int, [vp, _u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float]),
+        "hvs_row_query": (None, [_f32p, C.c_int, C.c_float, _f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -323,6 +327,46 @@ def partition_plan(n, n_parts, k, sample_proportion):
     if row0[m + 1] != 0xFFFFFFFF or local[m] != 0xFFFFFFFF:
         raise HvsError(-1, "hvs_partition_plan wrote past its outputs")
     return row0[:m + 1].copy(), int(sn.value), local[:m].copy()
+
+
+ROWQ_KNN, ROWQ_SAME_C, ROWQ_T_WINDOW, ROWQ_BOTH = 0, 1, 2, 3
+
+
+def row_query(row, type, dt):
+    """hvs_row_query: the query hvs_set_queries_from_rows builds from one data row (102 float32) -- [type, v, l, r] by `type`
+    (0: k-NN, 1: same category, 2: T within +-dt, 3: both) and the row's 100 vector floats, as 104 float32."""
+    row = np.ascontiguousarray(row, np.float32).ravel()
+    if row.size != DCOLS or int(type) not in (0, 1, 2, 3):
+        raise HvsError(-1, "row_query takes one row of 102 float32 and a type in 0..3")
+    out = np.empty(QCOLS, np.float32)
+    library().hvs_row_query(_fp(row), int(type), float(dt), _fp(out))
+    return out
+
+
+def _device_rows(x, count, cols, what):
+    """(pointer, rows) of a device buffer given as a raw pointer plus a row count, or as an object with data_ptr() and shape
+    (a torch tensor): float32, contiguous, on a GPU, rows of `cols` floats."""
+    if not (hasattr(x, "data_ptr") and hasattr(x, "shape")):
+        if count is None:
+            raise HvsError(-1, f"{what}: a raw pointer needs its row count")
+        return int(x), int(count)
+    import torch  # (only here: the package imports without it)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise HvsError(-1, f"{what}: the tensor must be float32, contiguous and on a GPU")
+    if x.numel() % cols or (x.dim() == 2 and x.shape[1] != cols) or x.dim() > 2:
+        raise HvsError(-1, f"{what}: the tensor must hold rows of {cols} float32")
+    rows = x.numel() // cols
+    if count is not None and int(count) > rows:
+        raise HvsError(-1, f"{what}: the tensor holds {rows} rows, fewer than the {int(count)} asked for")
+    return int(x.data_ptr()), rows if count is None else int(count)
+
+
+def _stream_ptr(stream):
+    """A hipStream_t from None (the null stream), a raw handle, or an object with `cuda_stream` (a torch stream)."""
+    if stream is None:
+        return None
+    h = int(getattr(stream, "cuda_stream", stream))
+    return C.c_void_p(h) if h else None
 
 
 class Engine:
@@ -536,6 +580,33 @@ class Engine:
     def upload_queries(self, q_rows):
         q = np.ascontiguousarray(q_rows, np.float32)
         self._ck(self._lib.hvs_upload_queries(self._h, _fp(q), q.shape[0]))
+
+    # --- inputs that are on the GPU already (include/hvs.h "device-resident inputs")
+    def set_queries_device(self, ptr_or_tensor, nq=None, stream=None):
+        """hvs_set_queries_device: resident queries from device memory (nq x 104 float32) of any visible GPU -- a raw pointer
+        with `nq`, or a torch tensor.  `stream`: the stream that produced the buffer (a raw hipStream_t or a torch stream;
+        None = the null stream).  Blocks until the copy is done."""
+        ptr, nq = _device_rows(ptr_or_tensor, nq, QCOLS, "set_queries_device")
+        self._ck(self._lib.hvs_set_queries_device(self._h, C.c_void_p(ptr) if ptr else None, nq, _stream_ptr(stream)))
+
+    def load_data_device(self, ptr_or_tensor, n=None, stream=None):
+        """hvs_load_data_device: the data set from device memory (n x 102 float32) of any visible GPU; arguments as for
+        set_queries_device.  The context is that of load_data of the same rows."""
+        ptr, n = _device_rows(ptr_or_tensor, n, DCOLS, "load_data_device")
+        self._ck(self._lib.hvs_load_data_device(self._h, C.c_void_p(ptr) if ptr else None, n, _stream_ptr(stream)))
+
+    def set_queries_from_rows(self, ids=None, first_id=0, nq=None, type=0, dt=0.0):
+        """hvs_set_queries_from_rows: resident query i built on the device from stored row ids[i] (or, without ids, row
+        first_id + i for i < nq) as D holds it now; `type` 0..3 and `dt` as in row_query."""
+        if ids is not None:
+            ids = np.ascontiguousarray(np.asarray(ids).ravel(), np.uint32)
+            if nq is not None and int(nq) != ids.size:
+                raise HvsError(-1, "set_queries_from_rows: nq does not match len(ids)")
+            nq = ids.size
+        elif nq is None:
+            raise HvsError(-1, "set_queries_from_rows needs ids, or first_id and nq")
+        self._ck(self._lib.hvs_set_queries_from_rows(self._h, _up(ids) if ids is not None else None, int(first_id), int(nq),
+                                                     int(type), float(dt)))
 
     def gen_queries(self, nq, seed, profile=1, ncat=100, force_type=-1, first_row=0):
         self._ck(self._lib.hvs_gen_queries(self._h, nq, seed, profile, ncat, force_type, first_row))
