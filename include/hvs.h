@@ -396,7 +396,10 @@ void hvs_compact_plan(const uint64_t *live_bits, uint32_t n, uint32_t *n_live, u
  *    hvs_upload_queries / hvs_gen_queries / hvs_query put all queries on every part; hvs_reserve(nq) sizes every part for all
  *    nq queries plus the exchange buffers; hvs_query_resident blocks the host until the merged answers exist (the call's one
  *    synchronisation); hvs_last_timing reports the slowest part's query_ms plus exchange_ms plus merge_ms, nq of the call,
- *    counters summed over the parts, flags OR-ed.
+ *    counters summed over the parts, flags OR-ed.  Every part picks engine, index and tile format from ITS rows, so the parts of
+ *    one call may run different engines: hvs_timing.engine is that of the last part (highest r) that searched rows in the call
+ *    (HVS_ENGINE_EXACT_SCAN when none did), fallback_queries, retry_queries and rescored_pairs are the parts' sums -- none of
+ *    these need equal a one-GPU context's figures; ids, out_dists and pairs do.
  *  - Every part must hold at least k rows: a load with n < n_parts * k, or an hvs_set_k that would break the rule, returns
  *    HVS_EINVAL and leaves the context as it was.
  *  - Not supported (yet) on a partitioned context, HVS_ESTATE and nothing changes: row deletion, append, update and compaction
