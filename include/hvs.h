@@ -475,6 +475,61 @@ int hvs_set_queries_from_rows(hvs_ctx *ctx, const uint32_t *ids /* host, nq entr
                               int type, float dt);
 void hvs_row_query(const float *row /* 102 */, int type, float dt, float *out_q /* 104 */);
 
+/* ---- per-query distance caps: the k nearest rows within a radius ---------------------------------- */
+
+/*
+ * "The k nearest rows that pass the predicate -- and are no farther than r": a cap is one f32 per resident query, max_d2[q], a
+ * SQUARED L2 distance, compared with the engine's exact-order f32 distance as `dist <= max_d2[q]` in IEEE arithmetic.  The output
+ * stays [nq][k]; the cap is a third predicate beside C and T.
+ *  - A row takes part in query q's answer only if it passes the query's predicate, lies in the sampled prefix, is live and is
+ *    within the cap.  Everything else is as if the rows beyond the cap did not match: the slots they leave are padded from n-1,
+ *    n-2, ... (from the last live ids under a mask) -- pad rows need not be within the cap, as they need not pass the predicate --
+ *    and with hvs_set_padding(ctx, 0) those slots are empty (0xFFFFFFFF / +inf).  The tie rule (dist asc, id asc), the ids and
+ *    the distance bits are unchanged, and hvs_timing.pairs keeps counting predicate-passing rows: it does not look at the cap.
+ *  - The matched rows of a query in key order have the rows within the cap as a prefix.  So the capped answer with padding off
+ *    is the uncapped answer with padding off with every slot where !(dist <= cap) made empty; with padding on those slots are
+ *    then filled by the padding rule (hvs_within_plan is that arithmetic).
+ *  - A row whose distance is NaN is within no cap, +inf included.  A cap that is NaN or negative matches nothing.
+ *  - "No cap" is expressed by not setting caps (or removing them), NOT by a cap of +inf: the two differ exactly for rows whose
+ *    distance is NaN, which an uncapped query may return and a cap of +inf excludes.
+ * While no caps are set every call runs exactly the kernels it runs without these functions.  The caps are a PROVEN threshold the
+ * filter engines start from (instead of +inf): a tight radius prunes at every level.  Every engine, both distance orders, every
+ * k, the live-row mask, appended and updated rows compose with caps; the D-sharded mode (sharding.py) knows nothing of them.
+ *
+ * hvs_set_max_dist2(ctx, max_d2, nq): attaches caps (HOST memory, nq floats) to the resident query set.  nq must equal the
+ * number of resident queries: otherwise HVS_EINVAL and nothing changes (caps already set stay in force).  max_d2 == NULL removes
+ * the caps (nq is not looked at).  Any call that replaces the resident set removes them too -- hvs_upload_queries,
+ * hvs_gen_queries, hvs_set_queries_device, hvs_set_queries_from_rows and hvs_query -- so every call sequence without these
+ * functions behaves as before.  Results of earlier calls stay in place.  Multi-GPU contexts cut the caps by the queries' owner
+ * ranges; a row-partitioned context puts all caps on every part (the parts' lists then hold keys within the cap only and the
+ * merge pads as it always does).
+ * hvs_set_max_dist2_device: the same from DEVICE memory, by the rules of hvs_set_queries_device -- plain device memory of any
+ * visible GPU, `stream` = the stream that produced it (NULL: the null stream), host memory of any kind is HVS_EINVAL with the
+ * runtime's error cleared, the call blocks until the copy is done.
+ * hvs_query_within: hvs_query with caps (host, nq floats: 4 bytes per query, sent whole before the pipeline starts); the caps
+ * stay attached to the call's queries afterwards.  max_d2 == NULL behaves exactly as hvs_query.
+ * hvs_within_stats: figures of the last call (after hvs_sync / hvs_query); HVS_ESTATE where hvs_last_timing has none to report.
+ * Multi-GPU contexts: summed.  Row-partitioned contexts: capped_queries is the call's, underfull_queries the merge's count of
+ * queries with fewer than k keys in all parts together, and within_slots the sum of the PARTS' non-pad slots -- every part
+ * answers every query on its rows, so a query whose parts hold more than k rows within the cap between them counts more than k.
+ */
+typedef struct hvs_within_info {
+    uint32_t capped_queries;    /* queries of the last call that carried a cap (all of them, or none)  */
+    uint32_t underfull_queries; /* of those, queries with fewer than k rows within their cap           */
+    uint64_t within_slots;      /* non-pad slots over all capped queries                               */
+} hvs_within_info;
+int hvs_set_max_dist2(hvs_ctx *ctx, const float *max_d2 /* host, nq */, uint32_t nq);
+int hvs_set_max_dist2_device(hvs_ctx *ctx, const float *d_max_d2 /* device, nq */, uint32_t nq, void *stream);
+int hvs_query_within(hvs_ctx *ctx, const float *q_rows, const float *max_d2, uint32_t nq, float sample_proportion, uint32_t *out_ids,
+                     float *out_dists);
+int hvs_within_stats(hvs_ctx *ctx, hvs_within_info *out);
+/* The host arithmetic of the contract for one answer row (no GPU, no context; any output may be NULL).  ids / dists: k slots of
+ * an UNCAPPED, UNPADDED answer (empty slots 0xFFFFFFFF / +inf); pad_ids / pad_dists: the first k padding rows (ids n-1, n-2, ...
+ * or the last live ids, and their exact-order distances; unused, may be NULL, when `padding` is 0).  out_ids / out_dists: the
+ * capped row -- the slots within the cap, then padding or empty slots, in (dist asc, id asc) order; n_within: slots within. */
+void hvs_within_plan(const uint32_t *ids, const float *dists, uint32_t k, float max_d2, const uint32_t *pad_ids, const float *pad_dists,
+                     int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_within);
+
 #ifdef __cplusplus
 }
 #endif

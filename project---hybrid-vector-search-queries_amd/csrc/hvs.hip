@@ -221,6 +221,11 @@ struct hvs_ctx : HvsLane {
     // resident queries + results
     float* d_q = nullptr;
     uint32_t nq = 0, nq_cap = 0;
+    // per-query distance caps of the resident set (hvs_set_max_dist2): one f32 per query beside d_q, normalised by
+    // hvs_k_norm_caps.  While `caps_set` is false no launch reads d_max_d2 and every call takes its kernels' plain forms.
+    float* d_max_d2 = nullptr;
+    bool caps_set = false;
+    bool call_capped = false;  // the last call ran with caps (hvs_within_stats)
     uint32_t* d_out_ids = nullptr;
     float* d_out_dists = nullptr;
     uint32_t res_cap = 0;
@@ -313,6 +318,8 @@ namespace {
 // index entry is stale -- the MASKED kernels run, pairs are counted the masked way, no host-side range counts.  Launches that
 // reach a row by its id in D take rs.d_live; launches that reach it through the index (perm, tiles) take index_mask(c).
 bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empty(); }
+// the resident queries carry distance caps: the CAPPED kernels run (with_capped)
+bool capped(const hvs_ctx* c) { return c->caps_set; }
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
 uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
 uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
@@ -593,14 +600,27 @@ void with_order_cap_mask(const hvs_ctx* c, F f)
     });
 }
 
+// ... and for the kernels that have a capped form: `f` gets "capped" as one more compile-time constant, true only
+// while the resident queries carry caps
+template <typename F>
+void with_capped(const hvs_ctx* c, F f)
+{
+    if (capped(c))
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
 // the k best of every query's candidate lists to the output rows (hvs_k_select): `nsel` queries named by `qlist`, each with
 // `nchunks` lists of which list 0 of the first query is `cand` / `cnt` and consecutive queries' lists lie `stride` apart
 void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t stride, uint32_t nchunks, uint64_t* cand, uint32_t* cnt)
 {
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((nsel + 3u) / 4u), dim3(256), 0,
-                           c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt, c->padding ? 1 : 0, c->d_out_ids,
-                           c->d_out_dists, c->k, c->rs.d_pad_ids);
+        with_capped(c, [&](auto WT) {
+            hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>),
+                               dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt,
+                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->d_max_d2, c->d_counters);
+        });
     });
 }
 
@@ -630,7 +650,9 @@ int ensure_queries(hvs_ctx* c, uint32_t nq)
 {
     if (nq > c->nq_cap) {
         int rc;
+        c->nq_cap = 0;  // (the two buffers grow together: a failure between them leaves neither in use)
         if ((rc = dev_alloc(c, &c->d_q, (size_t)nq * HVS_QCOLS))) return rc;
+        if ((rc = dev_alloc(c, &c->d_max_d2, (size_t)nq))) return rc;
         c->nq_cap = nq;
     }
     return ensure_results(c, nq);
@@ -712,9 +734,11 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
         unsigned long long* stat = count_stats ? c->d_counters : c->d_counters + 4;
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
         with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-            hipLaunchKernelGGL((hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0,
-                               c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat, c->k,
-                               c->rs.d_live);
+            with_capped(c, [&](auto WT) {
+                hipLaunchKernelGGL((hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>), grid,
+                                   dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt,
+                                   stat, c->k, c->rs.d_live, c->d_max_d2);
+            });
         });
     }
     kernel_timer_end(c, ev);
@@ -1024,7 +1048,10 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     // PCA-like vectors at n = 10^7 hand ~1500 rows per type-0 query to the last level's list of 1024 -- INT8 tiles look 23 %
     // faster than FP16 tiles there only while a half-empty workspace doubles the lists, profiles/r04/nonuniform_int8.txt)
     c->force_pfail = guess_pfail_for(kBatchMfma);
+    const bool caps_were_set = c->caps_set;  // (the caps belong to the caller's queries, not to the probe's)
+    c->caps_set = false;
     int rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
+    c->caps_set = caps_were_set;
     c->force_pfail = 0u;
     unsigned long long h[4] = {0, 0, 0, 0};
     uint32_t fails[2] = {0, 0};
@@ -1296,8 +1323,10 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
     }
     // (last argument: the batch is for a filter engine -- `host_counts` is the exact engine's range scan, which answers every
     // query itself, non-finite ones included)
-    hipLaunchKernelGGL(hvs_k_prep, dim3(B.ngroups), dim3(4 * HVS_GROUP), 0, c->stream, c->d_q, B, count_pairs ? 1 : 0, c->d_counters,
-                       fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1);
+    with_capped(c, [&](auto WT) {  // (capped: the slots' thresholds start at the queries' caps)
+        hipLaunchKernelGGL(hvs_k_prep<decltype(WT)::value>, dim3(B.ngroups), dim3(4 * HVS_GROUP), 0, c->stream, c->d_q, B, count_pairs ? 1 : 0,
+                           c->d_counters, fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1, c->d_max_d2);
+    });
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -1375,17 +1404,21 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     const int ev = kernel_timer_begin(c);
     const dim3 grid((slot_end + 255u) / 256u, nchunks);
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        hipLaunchKernelGGL((hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), grid, dim3(256), 0, c->stream,
-                           c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand, c->d_cand_cnt,
-                           c->d_counters, index_mask(c));
+        with_capped(c, [&](auto WT) {
+            hipLaunchKernelGGL((hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>), grid,
+                               dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end,
+                               c->d_cand, c->d_cand_cnt, c->d_counters, index_mask(c));
+        });
     });
     kernel_timer_end(c, ev);
+    // (under caps the tail and stale scans admit against the slots' thresholds, which hvs_k_prep set to the caps)
+    const float* scan_tau = capped(c) ? B.tau : nullptr;
     if (tail)
-        launch_tail(c, sn, HvsTailOut{c->d_cand + (size_t)nchunks * B.nslots * (size_t)c->cap, c->d_cand_cnt + (size_t)nchunks * B.nslots, nullptr,
+        launch_tail(c, sn, HvsTailOut{c->d_cand + (size_t)nchunks * B.nslots * (size_t)c->cap, c->d_cand_cnt + (size_t)nchunks * B.nslots, scan_tau,
                                       (uint32_t)c->cap, slot_begin, slot_end}, true);
     if (stale) {
         const size_t at = (size_t)(nchunks + (tail ? 1u : 0u)) * B.nslots;
-        launch_stale(c, stale, HvsTailOut{c->d_cand + at * (size_t)c->cap, c->d_cand_cnt + at, nullptr, (uint32_t)c->cap, slot_begin, slot_end}, true);
+        launch_stale(c, stale, HvsTailOut{c->d_cand + at * (size_t)c->cap, c->d_cand_cnt + at, scan_tau, (uint32_t)c->cap, slot_begin, slot_end}, true);
     }
     const uint32_t nsel = slot_end - slot_begin;
     launch_select(c, B.qid + slot_begin, nsel, B.nslots, nchunks + xchunks, c->d_cand + (size_t)slot_begin * (size_t)c->cap,
@@ -1535,21 +1568,27 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     uint32_t seed_chunks = 1u;
     if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = std::min(l0blocks, hvs_ceil_div(kSeedWaves, seed_waves));
     with_cap_mask(c, [&](auto CAPT, auto MT) {
-        hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)),
-                           dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L,
-                           c->d_counters, std::max(1u, seed_chunks), index_mask(c));
+        with_capped(c, [&](auto WT) {
+            hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>),
+                               dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B,
+                               c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->d_counters, std::max(1u, seed_chunks),
+                               index_mask(c));
+        });
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
     auto launch_merge = [&](bool final, uint32_t next) {
         with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
-            if (final)  // (only the final merge pads: the merges in front of it have no masked form)
-                hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n,
-                                   c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G,
-                                   c->rs.d_pad_ids);
+            if (final)  // (only the final merge pads and drops keys beyond a cap: the merges in front of it have no masked or capped form)
+                with_capped(c, [&](auto WT) {
+                    hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0,
+                                       c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt,
+                                       c->d_quant, L, next, G, c->rs.d_pad_ids, c->d_max_d2, c->d_counters);
+                });
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
-                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids);
+                                   c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids,
+                                   c->d_max_d2, c->d_counters);
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -1829,6 +1868,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
         mfma = c->fmt.built != HVS_FMT_NONE;  // (no usable bound at all: the exact engine answers, on the orderings)
     }
     c->timing_valid = false;
+    c->call_capped = capped(c);
     c->n_launch_events = 0;
     c->untimed_launches = 0;
     c->fallback_queries = 0;
@@ -2013,7 +2053,7 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
-    void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
+    void* ptrs[] = {c->d_data, c->d_q, c->d_max_d2, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
                     c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2472,7 +2512,33 @@ int leaf_begin_queries(hvs_ctx* c, uint32_t nq)
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = 0;
+    c->caps_set = false;  // (caps belong to a resident set: every call that replaces the set removes them)
     return ensure_queries(c, nq);
+}
+
+// hvs_set_max_dist2 / hvs_set_max_dist2_device on one GPU: `count` caps from host memory (src_dev < 0) or from a device buffer of
+// GPU src_dev, attached to the resident queries (count == c->nq: checked by the caller), or removed (src == nullptr).  Results of
+// earlier calls stay; an earlier call's pending re-runs are resolved first, under the caps they were asked under.
+int leaf_set_caps(hvs_ctx* c, const float* src, int src_dev, uint32_t count)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);
+    if (rc) return rc;
+    if (!src) {
+        c->caps_set = false;
+        return HVS_OK;
+    }
+    if (count) {
+        if (src_dev < 0)
+            HVS_HIP(c, hipMemcpyAsync(c->d_max_d2, src, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else if ((rc = copy_from_device(c, c->d_max_d2, src, src_dev, (size_t)count * sizeof(float))))
+            return rc;
+        hipLaunchKernelGGL(hvs_k_norm_caps, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, c->d_max_d2, count);
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the buffer is the caller's again)
+    c->caps_set = true;
+    return HVS_OK;
 }
 
 int leaf_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
@@ -2575,8 +2641,10 @@ struct PeerSink {
     bool want_dists;
 };
 
+// `max_d2` (hvs_query_within): the queries' distance caps, nq floats of host memory -- 4 bytes per query, sent whole before the
+// pipeline starts.
 int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists,
-               const PeerSink* sink = nullptr)
+               const PeerSink* sink = nullptr, const float* max_d2 = nullptr)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if (nq == 0) return HVS_OK;
@@ -2592,6 +2660,7 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     if ((rc = ensure_staging(c, out_dists != nullptr && !sink, in_pinned ? 0u : nq, out_pinned ? 0u : nq))) return rc;
     tr.mark("staging");
     c->nq = nq;
+    if (max_d2 && (rc = leaf_set_caps(c, max_d2, -1, nq))) return rc;
     const bool sink_dists = sink && sink->want_dists;
     constexpr uint32_t SQ = hvs_ctx::kStageQ;
     constexpr int R = hvs_ctx::kRing;
@@ -3400,6 +3469,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     if (c->kid_q0.size() != N + 1u || (uint64_t)q0 + nq > c->kid_q0.back())
         return fail(c, HVS_EINVAL, "query range outside the resident query set");
     c->part_timing_valid = false;
+    c->call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -4076,14 +4146,21 @@ int hvs_stream_wait(hvs_ctx* c, void* stream)
 int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids,
               float* out_dists)
 {
+    return hvs_query_within(c, q_rows, nullptr, nq, sample_proportion, out_ids, out_dists);
+}
+
+int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint32_t nq, float sample_proportion, uint32_t* out_ids,
+                     float* out_dists)
+{
     if (!c) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
+    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists, nullptr, max_d2);
     if (nq == 0) return HVS_OK;
     if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query: q_rows / out_ids is NULL");
     const auto t0 = std::chrono::steady_clock::now();
     if (c->partitioned) {
         // all queries to every part over its own link, the resident call, each owner's merged slice home
         int rc = hvs_upload_queries(c, q_rows, nq);
+        if (!rc && max_d2) rc = hvs_set_max_dist2(c, max_d2, nq);
         if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
         if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
         c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -4101,7 +4178,7 @@ int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proport
                 return HVS_OK;
             }
             return leaf_query(c->kids[r], q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, out_ids + (size_t)a * c->k,
-                              out_dists ? out_dists + (size_t)a * c->k : nullptr);
+                              out_dists ? out_dists + (size_t)a * c->k : nullptr, nullptr, max_d2 ? max_d2 + a : nullptr);
         });
     } else {
         // peer gather (A/B partner of the direct path): every GPU runs the same host pipeline on its slice of the caller's
@@ -4123,11 +4200,12 @@ int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proport
                 if (r == 0u) {  // its results are already where the gather wants them: plain resident run of its slice
                     int r2 = leaf_upload_queries(k, q_rows, m);
                     if (r2) return r2;
+                    if (max_d2 && (r2 = leaf_set_caps(k, max_d2, -1, m))) return r2;
                     if ((r2 = run_queries(k, 0, m, sample_proportion, NoHook{}))) return r2;
                     return leaf_sync(k);
                 }
                 const PeerSink sink{k0, a, out_dists != nullptr};
-                return leaf_query(k, q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, nullptr, nullptr, &sink);
+                return leaf_query(k, q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, nullptr, nullptr, &sink, max_d2 ? max_d2 + a : nullptr);
             });
         if (!rc) {
             (void)hipSetDevice(k0->device);
@@ -4221,6 +4299,134 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
     agg.host_ms = c->host_ms;
     *out = agg;
     return HVS_OK;
+}
+
+// ---- per-query distance caps (include/hvs.h "distance caps") --------------------
+
+// resident queries of the whole context
+static uint32_t resident_count(const hvs_ctx* c)
+{
+    if (c->kids.empty()) return c->nq;
+    return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
+}
+// caps (host memory: src_dev < 0; device memory of GPU src_dev otherwise) to every leaf: its range of them, or, on a
+// row-partitioned context, all of them
+static int set_caps_everywhere(hvs_ctx* c, const float* src, int src_dev, uint32_t nq)
+{
+    if (c->kids.empty()) return leaf_set_caps(c, src, src_dev, nq);
+    return for_each_leaf(c, [&](uint32_t r) {
+        if (!src) return leaf_set_caps(c->kids[r], nullptr, -1, 0u);
+        if (c->partitioned) return leaf_set_caps(c->kids[r], src, src_dev, nq);
+        return leaf_set_caps(c->kids[r], src + c->kid_q0[r], src_dev, c->kid_q0[r + 1] - c->kid_q0[r]);
+    });
+}
+
+int hvs_set_max_dist2(hvs_ctx* c, const float* max_d2, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!max_d2) return set_caps_everywhere(c, nullptr, -1, 0u);
+    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_max_dist2: nq is not the number of resident queries");
+    return set_caps_everywhere(c, max_d2, -1, nq);
+}
+
+int hvs_set_max_dist2_device(hvs_ctx* c, const float* d_max_d2, uint32_t nq, void* stream)
+{
+    if (!c) return HVS_EINVAL;
+    if (!d_max_d2) return set_caps_everywhere(c, nullptr, -1, 0u);
+    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_max_dist2_device: nq is not the number of resident queries");
+    int dev = 0;
+    if (nq) {  // (an empty set reads nothing)
+        int rc = device_of_buffer(c, d_max_d2, "hvs_set_max_dist2_device", &dev);
+        if (!rc) rc = wait_for_producer(c, dev, stream);
+        if (rc) return rc;
+    }
+    return set_caps_everywhere(c, d_max_d2, dev, nq);
+}
+
+static int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
+{
+    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = hvs_within_info{};
+    if (!c->call_capped) return HVS_OK;
+    unsigned long long v[2] = {0, 0};
+    HVS_HIP(c, hipMemcpy(v, c->d_counters + 14, sizeof(v), hipMemcpyDeviceToHost));
+    out->capped_queries = c->timing.nq;
+    out->within_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    return HVS_OK;
+}
+
+int hvs_within_stats(hvs_ctx* c, hvs_within_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_within_stats(c, out);
+    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    hvs_within_info agg{};
+    bool any = false;
+    for (hvs_ctx* k : c->kids) {
+        if (!k->timing_valid) continue;  // (took no part in the last call)
+        hvs_within_info m{};
+        const int rc = leaf_within_stats(k, &m);
+        if (rc) return fail(c, rc, k->err);
+        agg.capped_queries += m.capped_queries;
+        agg.underfull_queries += m.underfull_queries;
+        agg.within_slots += m.within_slots;
+        any = true;
+    }
+    if (c->partitioned) {
+        // every part answered all the queries: the parts' slots are summed, the queries are the call's, and a query is under-full
+        // when the merge found fewer than k keys in all parts together
+        agg.capped_queries = c->call_capped ? c->part_call_nq : 0u;
+        agg.underfull_queries = c->call_capped ? c->pinfo.padded_queries : 0u;
+        any = true;
+    }
+    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
+    *out = agg;
+    return HVS_OK;
+}
+
+void hvs_within_plan(const uint32_t* ids, const float* dists, uint32_t k, float max_d2, const uint32_t* pad_ids, const float* pad_dists,
+                     int padding, uint32_t* out_ids, float* out_dists, uint32_t* n_within)
+{
+    if (!ids || !dists) return;
+    const float cap = hvs_norm_cap(max_d2);
+    // key order of the engines: distance bits (NaN canonical, above +inf), then id; equal keys keep their slots' order
+    struct Slot {
+        uint64_t key;
+        uint32_t id;
+        float dist;
+    };
+    std::vector<Slot> row;
+    row.reserve(k);
+    for (uint32_t j = 0; j < k; ++j)
+        if (ids[j] != 0xFFFFFFFFu && dists[j] <= cap) {
+            uint32_t bits;
+            std::memcpy(&bits, &dists[j], sizeof(bits));
+            row.push_back(Slot{((uint64_t)bits << 32) | ids[j], ids[j], dists[j]});
+        }
+    const uint32_t within = (uint32_t)row.size();
+    if (n_within) *n_within = within;
+    for (uint32_t s = 0; within + s < k; ++s) {
+        if (padding && pad_ids && pad_dists) {
+            float d = pad_dists[s];
+            uint32_t bits;
+            std::memcpy(&bits, &d, sizeof(bits));
+            if (d != d) {  // (the engines' keys carry one NaN)
+                bits = 0x7FC00000u;
+                std::memcpy(&d, &bits, sizeof(d));
+            }
+            row.push_back(Slot{((uint64_t)bits << 32) | pad_ids[s], pad_ids[s], d});
+        } else {
+            row.push_back(Slot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
+        }
+    }
+    std::stable_sort(row.begin(), row.end(), [](const Slot& a, const Slot& b) { return a.key < b.key; });
+    for (uint32_t j = 0; j < k; ++j) {
+        if (out_ids) out_ids[j] = row[j].id;
+        if (out_dists) out_dists[j] = row[j].dist;
+    }
 }
 
 // ---- live-row mask ---------------------------------------------------------------------------

@@ -1007,6 +1007,77 @@ __global__ __launch_bounds__(1024) void hvs_k_layout(const uint64_t* __restrict_
     }
 }
 
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+#ifndef HVS_MUTANT_BAND_SCALE
+#define HVS_MUTANT_BAND_SCALE 1.0
+#endif
+#ifndef HVS_MUTANT_DROP
+#define HVS_MUTANT_DROP 0
+#endif
+#define HVS_MUT_SCALE ((double)(HVS_MUTANT_BAND_SCALE))
+#define HVS_MUT_TERM(bit, x) (((HVS_MUTANT_DROP) & (bit)) ? 0.0 : (x))
+#endif
+
+// The filter threshold theta that belongs to a slot's distance threshold tau -- the derivation is at hvs_k_merge ("theta").
+// One function per operand family, called wherever a tau is set: by hvs_k_merge for the next level, and by hvs_k_prep<true>
+// for a tau that starts at the caller's cap.  `tau` = +inf (no cut yet) keeps every row of the range; a slot with
+// an empty range matches nothing.  Reads the slot's norms from B (written by hvs_k_prep).
+// INT8 formats (see "INT8 filter" above): S = qq.dq + nh is exact, the band has no accumulation term.
+__device__ __forceinline__ int hvs_theta_i8(const HvsBatch& B, uint32_t slot, float tau, const HvsBounds* __restrict__ bounds,
+                                            const HvsQuant* __restrict__ qz)
+{
+    int ti = B.rb[slot] > B.ra[slot] ? (int)0x80000000 : 0x7FFFFFFF;
+    if (tau < __builtin_inff()) {
+        const double g = 20.0 * 5.9604644775390625e-08;
+        const double iu = qz->inv_sd * qz->inv_sd;  // 1 / sd^2
+        // (normq: the clip term of a query outside the data's box, see hvs_k_prep)
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+        const double band = (HVS_MUT_TERM(1, (double)B.nqb[slot] * (double)bounds->e_d8) +
+                             HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->n_d8) +
+                             HVS_MUT_TERM(4, (double)B.normq[slot])) * (1.0 + 1e-6) * HVS_MUT_SCALE;
+#else
+        const double band = ((double)B.nqb[slot] * (double)bounds->e_d8 + (double)B.eq[slot] * (double)bounds->n_d8 +
+                             (double)B.normq[slot]) * (1.0 + 1e-6);
+#endif
+        // -2: one unit for nh = floor(.), one for the f64 evaluation of this expression (relative
+        // 1e-9 of the magnitudes on top)
+        double th = (0.5 * (B.qn[slot] * (1.0 - 1e-12) - (double)tau * (1.0 + 2.0 * g)) - band) * iu;
+        th -= 2.0 + 1e-9 * (B.qn[slot] + (double)tau + band) * iu;
+        th = floor(th);
+        ti = th >= 2147483647.0 ? 0x7FFFFFFF : (th <= -2147483647.0 ? (int)0x80000001 : (int)th);
+        if (!(th == th)) ti = (int)0x80000001;  // NaN cannot happen with finite inputs; keep everything
+    }
+    return ti;
+}
+// 16-bit float formats
+__device__ __forceinline__ float hvs_theta_h16(const HvsBatch& B, uint32_t slot, float tau, const HvsBounds* __restrict__ bounds)
+{
+    float theta = B.rb[slot] > B.ra[slot] ? -__builtin_inff() : __builtin_inff();
+    if (tau < __builtin_inff()) {
+        const double g = 20.0 * 5.9604644775390625e-08;
+        const double sabs = (double)B.nqb[slot] * (double)bounds->nb_d + 1.02 * (double)bounds->hmax;
+        const double mu = 256.0 * 5.9604644775390625e-08 * sabs;
+#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
+        const double band = (mu + HVS_MUT_TERM(8, (double)bounds->rho) + HVS_MUT_TERM(1, (double)B.normq[slot] * (double)bounds->e_d) +
+                             HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->nb_d)) * HVS_MUT_SCALE;
+#else
+        const double band = mu + (double)bounds->rho + (double)B.normq[slot] * (double)bounds->e_d +
+                            (double)B.eq[slot] * (double)bounds->nb_d;
+#endif
+        // slack for the f64 evaluation itself: relative to the magnitudes involved (an absolute constant
+        // would swamp data whose distances are tiny, e.g. vectors scaled by 1e-3)
+        const double slack = 1e-9 * (B.qn[slot] + (double)tau + band);
+        const double th = 0.5 * (B.qn[slot] * (1.0 - 1e-12) - (double)tau * (1.0 + 2.0 * g)) - band * (1.0 + 1e-6) - slack;
+        float tf = (float)th;
+        if ((double)tf > th) {  // round down
+            if (tf == 0.0f) tf = -1.0e-30f;
+            else tf = __uint_as_float(__float_as_uint(tf) + (tf < 0.0f ? 1u : 0xFFFFFFFFu));
+        }
+        theta = tf;
+    }
+    return theta;
+}
+
 // hvs_k_prep -- one 512-thread block per group of 128 slots (round 4: the per-slot and the per-group preparation were two
 // kernels, the first with ONE lane per slot walking the query's 100 dimensions and repeating the binary searches of
 // hvs_k_query_keys2: 45 + 25 us of a 10^4-query batch whose whole step is 1.9 ms).
@@ -1021,10 +1092,15 @@ __global__ __launch_bounds__(1024) void hvs_k_layout(const uint64_t* __restrict_
 // dimensions only.  The sum is kept per slot (`normq`, which the INT8 band does not use otherwise) and hvs_k_merge adds it
 // to the band: a query a little outside the box costs a wider band, not the exact engine.  Far outside (the clip term
 // above 4x the rest of the band) the filter would let most rows through: the exact engine answers.
+//
+// CAPPED (`caps` is not read otherwise): the slot's threshold starts at the query's cap instead of +inf, and the filter
+// threshold of level 1 is the one that belongs to it -- a query whose level 0 admits nothing (a tight radius) never reaches
+// the part of hvs_k_merge that would set it, and would filter level 1 with "keep everything".
+template <bool CAPPED = false>
 __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restrict__ Q, HvsBatch B, int count_pairs,
                                                             unsigned long long* __restrict__ counters, int fmt,
                                                             const HvsQuant* __restrict__ qz, const HvsBounds* __restrict__ bounds,
-                                                            int for_filter)
+                                                            int for_filter, const float* __restrict__ caps)
 {
     __shared__ uint32_t smin[HVS_GROUP], smax[HVS_GROUP];
     __shared__ unsigned long long spairs;
@@ -1146,12 +1222,23 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
         B.topcnt[s] = 0;
         B.candcnt[s] = 0;
         B.overflow[s] = hopeless ? HVS_FAIL_EXACT : 0u;
-        B.tau[s] = __builtin_inff();
-        // -inf: everything in range is a candidate until a threshold is set; +inf: nothing can ever match
-        if (HVS_IS_I8(fmt))
-            B.thetai[s] = b > a ? (int)0x80000000 : 0x7FFFFFFF;
-        else
-            B.theta[s] = b > a ? -__builtin_inff() : __builtin_inff();
+        if constexpr (CAPPED) {
+            // (a padding slot has no query: +inf, like the plain form.  The norms the functions read are the ones stored above.)
+            const float cap = qi != 0xFFFFFFFFu ? caps[qi] : __builtin_inff();
+            const bool nothing = cap == HVS_CAP_NOTHING;  // no row is within this cap: the filter keeps none
+            B.tau[s] = cap;
+            if (HVS_IS_I8(fmt))
+                B.thetai[s] = nothing ? 0x7FFFFFFF : hvs_theta_i8(B, s, cap, bounds, qz);
+            else
+                B.theta[s] = nothing ? __builtin_inff() : hvs_theta_h16(B, s, cap, bounds);
+        } else {
+            B.tau[s] = __builtin_inff();
+            // -inf: everything in range is a candidate until a threshold is set; +inf: nothing can ever match
+            if (HVS_IS_I8(fmt))
+                B.thetai[s] = b > a ? (int)0x80000000 : 0x7FFFFFFF;
+            else
+                B.theta[s] = b > a ? -__builtin_inff() : __builtin_inff();
+        }
         smin[sl] = a < b ? a : 0xFFFFFFFFu;
         smax[sl] = a < b ? b : 0u;
     }
@@ -1281,7 +1368,10 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 #define HVS_PRAGMA(x) HVS_PRAGMA_(x)
 
 // MASKED (live-row mask, hvs_kernels.h): dead rows are dropped beside the sampled-prefix test; `sn` is the cut id then
-template <int CAP, bool MASKED>
+// CAPPED: the lane's threshold starts at the slot's tau -- the query's cap, set by hvs_k_prep<true> --
+// instead of +inf.  The chunked form writes its keys without a threshold test, as it always did: keys beyond the cap that it
+// leaves in a list never raise a threshold (hvs_k_merge takes min(tau, .)) and are dropped by the final merge.
+template <int CAP, bool MASKED, bool CAPPED = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restrict__ D, uint32_t n, uint32_t sn,
                                                            const float* __restrict__ Q, HvsBatch B,
                                                            const uint32_t* __restrict__ perm_ct,
@@ -1321,6 +1411,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
     }
     uint64_t* __restrict__ mylist = B.cand + (size_t)slot * B.fcap;
     float tau = __builtin_inff();
+    if constexpr (CAPPED) tau = B.tau[slot];
     uint32_t cnt = 0, nscan = 0;
     for (uint32_t i = lo + blockIdx.y; i < hi; i += nchunks) {
         const uint32_t b = bpos[i];
@@ -1430,7 +1521,10 @@ struct HvsUniformRowF2 {
     __device__ __forceinline__ hvs_f2 operator[](int i) const { return p[i]; }
 };
 
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
+// CAPPED: admission gains `dist <= cap` beside the threshold test; the cap is the slot's tau, where
+// hvs_k_prep<true> put it (nothing lowers it in the exact engine).  The lane's own threshold keeps its "NaN admits every row
+// until the first cut" start: the cap is a second test, not its initial value.
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restrict__ D, uint32_t sn,
                                                             const float* __restrict__ Q, HvsBatch B,
                                                             const uint32_t* __restrict__ perm_ct,
@@ -1478,6 +1572,8 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
     }
     uint64_t* __restrict__ mylist = cand + ((size_t)chunk * B.nslots + slot) * (uint32_t)CAP;
     float tau = __builtin_nanf("");  // admits every passing row until the first cut (see hvs_k_scan_exact_lds)
+    float cap = 0.0f;
+    if constexpr (CAPPED) cap = have_q ? B.tau[slot] : HVS_CAP_NOTHING;
     uint32_t cnt = 0, nscan = 0;
     for (uint32_t pos = p0; pos < p1; ++pos) {
         const bool pass = pos >= ra && pos < rb;
@@ -1498,7 +1594,9 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
             HvsUniformRowF2 dv{reinterpret_cast<const hvs_f2*>(row)};
             dist = hvs_exact_dist_pk(dv, q2);
         }
-        if (pass && !(dist > tau)) {  // ids are not monotone along a position range: keep ties, the keys sort them out
+        bool admit = pass && !(dist > tau);  // ids are not monotone along a position range: keep ties, the keys sort them out
+        if constexpr (CAPPED) admit = admit && dist <= cap;
+        if (admit) {
             mylist[cnt] = hvs_make_key(dist, id);
             ++cnt;
         }
@@ -2887,23 +2985,24 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 // -DHVS_MUTANT_BAND_SCALE=s multiplies the band by s, -DHVS_MUTANT_DROP=mask leaves terms out of it (1: the E_D term,
 // 2: the e_q term, 4: the clip term of a query outside the INT8 box, 8: rho).  A build with a band that is too small must
 // give wrong answers on the adversarial data sets of tests/bound_model.py -- that is what shows the tests would notice.
-#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
-#ifndef HVS_MUTANT_BAND_SCALE
-#define HVS_MUTANT_BAND_SCALE 1.0
-#endif
-#ifndef HVS_MUTANT_DROP
-#define HVS_MUTANT_DROP 0
-#endif
-#define HVS_MUT_SCALE ((double)(HVS_MUTANT_BAND_SCALE))
-#define HVS_MUT_TERM(bit, x) (((HVS_MUTANT_DROP) & (bit)) ? 0.0 : (x))
-#endif
+// (the switches are read by hvs_theta_i8 / hvs_theta_h16, in front of hvs_k_prep)
 // MASKED (FINAL only, live-row mask): the padding ids come from `pad_ids`, the last k live rows in descending order
-template <bool FINAL, int CAP, bool MASKED>
+//
+// CAPPED (FINAL only; `caps` and `counters` are not read otherwise).  The slot's tau started at the query's cap (hvs_k_prep<true>) instead
+// of +inf and only ever decreased, so everything above holds with "+inf" read as "the cap": after the last level the list holds
+// every row of the range with distance <= tau_last <= cap.  The answer is verified iff tau_last still IS the cap (nothing but
+// what the caller does not want was ever discarded: every row within the cap is held, or was cut by k smaller keys), or k keys
+// are held and the k-th is <= tau_last -- the plain rule with its `tau == +inf` generalised.  An under-full list under a tau
+// that a guess lowered is a retry, as before.  Then the keys beyond the cap leave (hvs_keep_within: the chunked seed and the
+// tail scans may have let some in, and rows with NaN distances) and the padding fills what they leave.  The merges in front
+// of the final one have no capped form: min(tau, m-th smallest held) never exceeds the cap tau started from.
+template <bool FINAL, int CAP, bool MASKED, bool CAPPED = false>
 __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, uint32_t n, const float* __restrict__ Q,
                                                    HvsBatch B, const HvsBounds* __restrict__ bounds, int pad,
                                                    uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, int fmt,
                                                    const HvsQuant* __restrict__ qz, HvsLevels L, uint32_t level_next,
-                                                   HvsGuessTable G, const uint32_t* __restrict__ pad_ids)
+                                                   HvsGuessTable G, const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps,
+                                                   unsigned long long* __restrict__ counters)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -2963,59 +3062,15 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
         if (lane == 0u) {
             B.topcnt[slot] = cnt;
             B.candcnt[slot] = 0;
-            float tau = B.tau[slot];  // (+inf until the first cut)
+            float tau = B.tau[slot];  // (+inf, or the caller's cap, until the first cut)
             if (cnt >= mn) tau = fminf(tau, __uint_as_float(mth_bits));  // (a NaN key leaves tau as it is)
-            const bool cut = tau < __builtin_inff();
-            float theta = B.rb[slot] > B.ra[slot] ? -__builtin_inff() : __builtin_inff();
             if (HVS_IS_I8(fmt)) {
-                // INT8 formats (see "INT8 filter" above): S = qq.dq + nh is exact, the band has no accumulation term
-                int ti = B.rb[slot] > B.ra[slot] ? (int)0x80000000 : 0x7FFFFFFF;
-                if (cut) {
-                    const double g = 20.0 * 5.9604644775390625e-08;
-                    const double iu = qz->inv_sd * qz->inv_sd;  // 1 / sd^2
-                    // (normq: the clip term of a query outside the data's box, see hvs_k_prep)
-#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
-                    const double band = (HVS_MUT_TERM(1, (double)B.nqb[slot] * (double)bounds->e_d8) +
-                                         HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->n_d8) +
-                                         HVS_MUT_TERM(4, (double)B.normq[slot])) * (1.0 + 1e-6) * HVS_MUT_SCALE;
-#else
-                    const double band = ((double)B.nqb[slot] * (double)bounds->e_d8 + (double)B.eq[slot] * (double)bounds->n_d8 +
-                                         (double)B.normq[slot]) * (1.0 + 1e-6);
-#endif
-                    // -2: one unit for nh = floor(.), one for the f64 evaluation of this expression (relative
-                    // 1e-9 of the magnitudes on top)
-                    double th = (0.5 * (B.qn[slot] * (1.0 - 1e-12) - (double)tau * (1.0 + 2.0 * g)) - band) * iu;
-                    th -= 2.0 + 1e-9 * (B.qn[slot] + (double)tau + band) * iu;
-                    th = floor(th);
-                    ti = th >= 2147483647.0 ? 0x7FFFFFFF : (th <= -2147483647.0 ? (int)0x80000001 : (int)th);
-                    if (!(th == th)) ti = (int)0x80000001;  // NaN cannot happen with finite inputs; keep everything
-                }
+                const int ti = hvs_theta_i8(B, slot, tau, bounds, qz);
                 B.tau[slot] = tau;
                 B.thetai[slot] = ti;
                 return;
             }
-            if (cut) {
-                const double g = 20.0 * 5.9604644775390625e-08;
-                const double sabs = (double)B.nqb[slot] * (double)bounds->nb_d + 1.02 * (double)bounds->hmax;
-                const double mu = 256.0 * 5.9604644775390625e-08 * sabs;
-#if defined(HVS_MUTANT_BAND_SCALE) || defined(HVS_MUTANT_DROP)
-                const double band = (mu + HVS_MUT_TERM(8, (double)bounds->rho) + HVS_MUT_TERM(1, (double)B.normq[slot] * (double)bounds->e_d) +
-                                     HVS_MUT_TERM(2, (double)B.eq[slot] * (double)bounds->nb_d)) * HVS_MUT_SCALE;
-#else
-                const double band = mu + (double)bounds->rho + (double)B.normq[slot] * (double)bounds->e_d +
-                                    (double)B.eq[slot] * (double)bounds->nb_d;
-#endif
-                // slack for the f64 evaluation itself: relative to the magnitudes involved (an absolute constant
-                // would swamp data whose distances are tiny, e.g. vectors scaled by 1e-3)
-                const double slack = 1e-9 * (B.qn[slot] + (double)tau + band);
-                const double th = 0.5 * (B.qn[slot] * (1.0 - 1e-12) - (double)tau * (1.0 + 2.0 * g)) - band * (1.0 + 1e-6) - slack;
-                float tf = (float)th;
-                if ((double)tf > th) {  // round down
-                    if (tf == 0.0f) tf = -1.0e-30f;
-                    else tf = __uint_as_float(__float_as_uint(tf) + (tf < 0.0f ? 1u : 0xFFFFFFFFu));
-                }
-                theta = tf;
-            }
+            const float theta = hvs_theta_h16(B, slot, tau, bounds);
             B.tau[slot] = tau;
             B.theta[slot] = theta;
         }
@@ -3023,10 +3078,23 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
     }
     // ---- final: verify.  Every row of the range with distance <= tau_last is held (see "Guessed thresholds"): the k
     // smallest keys held are the answer iff the k-th of them is <= tau_last, or nothing was ever discarded (tau = +inf).
-    if (lane == 0u) {
-        const uint32_t tau_bits = __float_as_uint(B.tau[slot]);
-        const bool verified = tau_bits == 0x7F800000u || (cnt >= knn && dmax_bits <= tau_bits);
-        if (!verified) hvs_flag_fail(B.fail_code, B.overflow, slot);
+    if constexpr (!CAPPED) {
+        if (lane == 0u) {
+            const uint32_t tau_bits = __float_as_uint(B.tau[slot]);
+            const bool verified = tau_bits == 0x7F800000u || (cnt >= knn && dmax_bits <= tau_bits);
+            if (!verified) hvs_flag_fail(B.fail_code, B.overflow, slot);
+        }
+    } else {
+        const float cap = caps[qi];
+        uint32_t failed = 0u;
+        if (lane == 0u) {
+            const uint32_t tau_bits = __float_as_uint(B.tau[slot]);
+            const bool verified = tau_bits == __float_as_uint(cap) || (cnt >= knn && dmax_bits <= tau_bits);
+            if (!verified) hvs_flag_fail(B.fail_code, B.overflow, slot);
+            failed = B.overflow[slot];  // (also a list that overflowed at some level: the query is answered again, and counted then)
+        }
+        failed = (uint32_t)__shfl((int)failed, 0);
+        cnt = hvs_keep_within(buf, cnt, cap, knn, lane, counters, failed == 0u);
     }
     // ---- final: pad, rank-sort, write
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;

@@ -139,6 +139,22 @@ __global__ __launch_bounds__(256) void hvs_k_compact_gather(const uint2* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-query distance caps (hvs_set_max_dist2 / hvs_query_within): one f32 per resident query, a squared L2
+// distance; a row takes part in the query's answer only if `dist <= cap` holds for its exact-order distance (so a row with
+// a NaN distance is within no cap, +inf included).  A cap that is NaN or negative matches nothing: hvs_k_norm_caps turns both
+// into HVS_CAP_NOTHING once, when the caps are attached, so that every kernel needs the one compare.  Kernels that honour
+// caps are the CAPPED = true instantiations of the kernels concerned (the MASKED pattern above); the host launches them only
+// while caps are set, so a context without caps runs the code it always ran.
+// ---------------------------------------------------------------------------------------------
+#define HVS_CAP_NOTHING (-1.0f)  // `dist <= -1` is false for every distance (distances are >= 0 or NaN)
+__host__ __device__ __forceinline__ float hvs_norm_cap(float c) { return c >= 0.0f ? c : HVS_CAP_NOTHING; }  // (-0 stays: 0 <= -0)
+__global__ void hvs_k_norm_caps(float* __restrict__ caps, uint32_t nq)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) caps[i] = hvs_norm_cap(caps[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------
 // `first_row`: out[0] is element 0 of that row of the stream (a part of a row-partitioned context generates its own rows)
@@ -298,11 +314,12 @@ struct HvsLdsRow1 {
 // SCALAR_ORDER = true : the baseline engine's sequential order (baseline.hpp:53-64), BASELINE.json configs[0].
 // MASKED: rows whose bit in `live` is clear are skipped (the row is wave-uniform: one scalar load and branch per row);
 // `sn` is then the cut id of the sampled live prefix (hvs_mask_plan)
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
+// CAPPED: admission gains `dist <= caps[query]` beside the threshold test (`caps` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
 __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
     uint32_t nq_pad, uint32_t sn, uint32_t rows_per_chunk, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt,
-    unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live)
+    unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live, const float* __restrict__ caps)
 {
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     const uint32_t lane = threadIdx.x & 63u;
@@ -364,6 +381,8 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     // tau = NaN until the list has been cut back once: `!(dist >= tau)` then admits EVERY passing row, +inf and NaN
     // distances included, as the reference does while its list is not full (optimized_impl.h:301-304)
     float tau = __builtin_nanf("");
+    float cap = 0.0f;
+    if constexpr (CAPPED) cap = caps[qi];
     uint32_t cnt = 0;
     uint32_t npass = 0, nscan = 0;
     // queries are sorted by type: a wave of type-0 queries only (the exact engine's slowest class) skips the per-row predicate --
@@ -406,7 +425,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
                     // packed f32 math: measured 14.0 k type-0 queries/s at D=1e7 against 12.5 k with the 300 unpacked ops
                     dist = hvs_exact_dist_pk_lds(rowp, q2);
                 }
-                if (pass && !(dist >= tau)) {
+                bool admit = pass && !(dist >= tau);
+                if constexpr (CAPPED) admit = admit && dist <= cap;
+                if (admit) {
                     mylist[cnt] = hvs_make_key(dist, j0 + r);
                     ++cnt;
                 }
@@ -446,13 +467,41 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
 // emit ids in ascending (dist, id) order (get_knn_sorted, optimized_impl.h:392-415).
 // One wave per query, 4 queries per 256-thread block, a 256-key LDS buffer per wave.
 // ---------------------------------------------------------------------------------------------
+// The final kernels' share of the caps (hvs_k_select, hvs_k_merge with CAPPED): of the wave's keys buf[0 .. cnt) -- the k
+// smallest the query's rows gave -- those with `dist <= cap` are kept, packed in place in their order; returns their number.
+// The keys within the cap are a prefix of the query's keys in key order, so what is left is the capped answer's matched part
+// and the slots behind it are padded like any under-full answer's.  Whatever the stages in front admitted, no key beyond the
+// cap passes here (nor a NaN distance: `NaN <= cap` is false).
+// counters[14] += slots kept, counters[15] += 1 for an under-full query (hvs_within_info).
+__device__ __forceinline__ uint32_t hvs_keep_within(uint64_t* buf, uint32_t cnt, float cap, uint32_t knn, uint32_t lane,
+                                                    unsigned long long* __restrict__ counters, bool count)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    uint32_t kept = 0;
+    for (uint32_t off = 0; off < cnt; off += 64u) {  // (wave-uniform; a chunk's keys land at or below their own places)
+        const uint32_t e = off + lane;
+        const uint64_t key = e < cnt ? buf[e] : 0ull;
+        const bool in = e < cnt && hvs_key_dist(key) <= cap;
+        const uint64_t m = __ballot(in);
+        if (in) buf[kept + hvs_prefix_count(m)] = key;
+        kept += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (count && lane == 0u) {
+        if (kept) atomicAdd(&counters[14], (unsigned long long)kept);
+        if (kept < knn) atomicAdd(&counters[15], 1ull);
+    }
+    return kept;
+}
+
 // MASKED: the padding ids come from `pad_ids` (the last k live rows, descending) instead of n - 1, n - 2, ...
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
+// CAPPED: keys beyond caps[query] leave before the padding (hvs_keep_within; `caps` and `counters` are not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
 __global__ __launch_bounds__(256) void hvs_k_select(
     const float* __restrict__ D, uint32_t n, const float* __restrict__ Q, const uint32_t* __restrict__ qorder,
     uint32_t nq, uint32_t nq_pad, uint32_t nchunks, const uint64_t* __restrict__ cand,
     const uint32_t* __restrict__ cand_cnt, int pad, uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
-    const uint32_t* __restrict__ pad_ids)
+    const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps, unsigned long long* __restrict__ counters)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -486,6 +535,7 @@ __global__ __launch_bounds__(256) void hvs_k_select(
         cnt = knn;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
+    if constexpr (CAPPED) cnt = hvs_keep_within(buf, cnt, caps[qi], knn, lane, counters, true);
     // padding: fewer than 100 matching rows in [0,sn)
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
     for (uint32_t base = cnt; base < knn; base += 64u) {

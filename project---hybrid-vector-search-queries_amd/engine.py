@@ -83,6 +83,14 @@ class PartitionInfo(C.Structure):
         return d
 
 
+class WithinInfo(C.Structure):
+    """hvs_within_info (include/hvs.h)."""
+    _fields_ = [("capped_queries", C.c_uint32), ("underfull_queries", C.c_uint32), ("within_slots", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -227,6 +235,11 @@ def library():
         "hvs_load_data_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
         "hvs_set_queries_from_rows": (C.c_int, [vp, _u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float]),
         "hvs_row_query": (None, [_f32p, C.c_int, C.c_float, _f32p]),
+        "hvs_set_max_dist2": (C.c_int, [vp, _f32p, C.c_uint32]),
+        "hvs_set_max_dist2_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
+        "hvs_query_within": (C.c_int, [vp, _f32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_within_stats": (C.c_int, [vp, C.POINTER(WithinInfo)]),
+        "hvs_within_plan": (None, [_u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -341,6 +354,25 @@ def row_query(row, type, dt):
     out = np.empty(QCOLS, np.float32)
     library().hvs_row_query(_fp(row), int(type), float(dt), _fp(out))
     return out
+
+
+def within_plan(ids, dists, max_d2, pad_ids=None, pad_dists=None, padding=True):
+    """hvs_within_plan: one uncapped, unpadded answer row (k ids, k distances; empty slots 0xFFFFFFFF / +inf) and a cap ->
+    (ids, dists, n_within) of the capped row, padded from pad_ids / pad_dists (the first k padding rows) when `padding`."""
+    ids = np.ascontiguousarray(ids, np.uint32).ravel()
+    dists = np.ascontiguousarray(dists, np.float32).ravel()
+    k = ids.size
+    if dists.size != k:
+        raise HvsError(-1, "within_plan: ids and dists must have k entries each")
+    if padding:
+        pad_ids = np.ascontiguousarray(pad_ids, np.uint32).ravel()
+        pad_dists = np.ascontiguousarray(pad_dists, np.float32).ravel()
+        if pad_ids.size < k or pad_dists.size < k:
+            raise HvsError(-1, "within_plan: padding needs k pad ids and k pad distances")
+    out_ids, out_d, n_in = np.empty(k, np.uint32), np.empty(k, np.float32), C.c_uint32(0)
+    library().hvs_within_plan(_up(ids), _fp(dists), k, C.c_float(max_d2), _up(pad_ids) if padding else None,
+                              _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids), _fp(out_d), C.byref(n_in))
+    return out_ids, out_d, int(n_in.value)
 
 
 def _device_rows(x, count, cols, what):
@@ -560,9 +592,10 @@ class Engine:
         self._ck(self._lib.hvs_trim_rows(self._h))
 
     # --- the vec_query seam
-    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None):
+    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None):
         """hvs_query: host rows in, host ids (and distances) out.  `out_ids` / `out_dists`: caller-provided arrays
-        (e.g. views of pinned memory) to be filled instead of fresh ones."""
+        (e.g. views of pinned memory) to be filled instead of fresh ones.  `max_dist2`: one squared-distance cap per query
+        (hvs_query_within: the k nearest rows within it); None = no caps."""
         q = np.ascontiguousarray(q_rows, np.float32)
         if q.ndim != 2 or q.shape[1] != QCOLS:
             raise HvsError(-1, "query rows must be nq x 104 float32")
@@ -573,8 +606,35 @@ class Engine:
             raise HvsError(-1, "out_ids must be a C-contiguous nq x k uint32 array")
         if d is not None and (d.shape != (nq, K) or d.dtype != np.float32 or not d.flags.c_contiguous):
             raise HvsError(-1, "out_dists must be a C-contiguous nq x k float32 array")
-        self._ck(self._lib.hvs_query(self._h, _fp(q), nq, sample_proportion, _up(ids), _fp(d) if d is not None else None))
+        if max_dist2 is None:
+            self._ck(self._lib.hvs_query(self._h, _fp(q), nq, sample_proportion, _up(ids), _fp(d) if d is not None else None))
+        else:
+            caps = np.ascontiguousarray(max_dist2, np.float32).ravel()
+            if caps.size != nq:
+                raise HvsError(-1, "max_dist2 must hold one float32 per query")
+            self._ck(self._lib.hvs_query_within(self._h, _fp(q), _fp(caps), nq, sample_proportion, _up(ids),
+                                                _fp(d) if d is not None else None))
         return (ids, d) if d is not None else ids
+
+    # --- per-query distance caps (include/hvs.h "per-query distance caps")
+    def set_max_dist2(self, caps, stream=None):
+        """Attach one squared-distance cap per resident query: a float32 array (hvs_set_max_dist2), a float32 GPU tensor
+        (hvs_set_max_dist2_device; `stream` as for set_queries_device), or None to remove the caps.  Any call that replaces the
+        resident queries removes them too."""
+        if caps is None:
+            self._ck(self._lib.hvs_set_max_dist2(self._h, None, 0))
+        elif hasattr(caps, "data_ptr") and hasattr(caps, "shape"):
+            ptr, n = _device_rows(caps, None, 1, "set_max_dist2")
+            self._ck(self._lib.hvs_set_max_dist2_device(self._h, C.c_void_p(ptr) if ptr else None, n, _stream_ptr(stream)))
+        else:
+            caps = np.ascontiguousarray(caps, np.float32).ravel()
+            self._ck(self._lib.hvs_set_max_dist2(self._h, _fp(caps), caps.size))
+
+    def within_stats(self):
+        """hvs_within_stats: capped / under-full queries and non-pad slots of the last call."""
+        w = WithinInfo()
+        self._ck(self._lib.hvs_within_stats(self._h, C.byref(w)))
+        return w
 
     # --- resident variant
     def upload_queries(self, q_rows):
