@@ -530,6 +530,74 @@ int hvs_within_stats(hvs_ctx *ctx, hvs_within_info *out);
 void hvs_within_plan(const uint32_t *ids, const float *dists, uint32_t k, float max_d2, const uint32_t *pad_ids, const float *pad_dists,
                      int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_within);
 
+/* ---- per-query result cursors: the k nearest rows after a given key -------------------------------- */
+
+/*
+ * "The k nearest rows that pass the predicate -- and come AFTER this key": a cursor is one key per resident query, the pair
+ * (after_dist f32, after_id u32), compared in the engines' own key order: distance bits ascending, then id ascending; +inf
+ * after every finite value, the canonical NaN (0x7FC00000) after +inf.  It is the lower bound that the distance cap is the
+ * upper bound of, and with it top-K for any K is a loop of pages of k, each of them exact.
+ *  - A row takes part in query q's answer only if it passes the query's predicate, lies in the sampled prefix, is live, is
+ *    within the cap if caps are set, and its key (dist, id) is STRICTLY greater than the cursor's.  Everything else is as if
+ *    the rows at or before the cursor did not match: the slots they leave are padded from n-1, n-2, ... (from the last live ids
+ *    under a mask) or are empty (0xFFFFFFFF / +inf) with hvs_set_padding(ctx, 0).  hvs_timing.pairs keeps counting
+ *    predicate-passing rows: it does not look at cursors.  Ids, distance bits and the tie rule are unchanged.
+ *  - The paging law.  Let full(q) be all matched keys of query q in key order.  The answer with cursor c and padding off is the
+ *    first k keys of full(q) that are > c, then empty slots.  So page p+1, run with the cursor set to the last slot of page p,
+ *    continues full(q) exactly where page p stopped: the concatenation of pages 1..P is the first P*k keys of full(q), with no
+ *    gap and no repeat -- rows with equal distances and duplicate rows included, the id decides.
+ *  - A cursor with after_id == 0xFFFFFFFF means "exhausted" and matches nothing, whatever its distance: that is what the last
+ *    slot of an under-full, unpadded page holds, so feeding each row's last slot back is always right with padding off, and an
+ *    exhausted query stays exhausted.  A NaN after_dist is taken as the canonical NaN key.
+ *  - "No cursor" is expressed by not setting cursors (or removing them), never by a special value.  While no cursors are set
+ *    every call runs exactly the kernels it runs without these functions.
+ *  - The cursor is a key, not a row reference: the row it names may have been deleted or updated since.
+ * Cursors compose with caps, the live-row mask, appended and updated rows, every engine, both distance orders and every k; the
+ * D-sharded mode (sharding.py) knows nothing of them.  They belong to the resident query set exactly as caps do: any call that
+ * replaces the set -- hvs_upload_queries, hvs_gen_queries, hvs_set_queries_device, hvs_set_queries_from_rows, hvs_query --
+ * removes them.  Results of earlier calls stay in place.  A cursor gives the filter engines nothing to prune with (it bounds
+ * the distance from below); it is tested wherever a key enters a candidate list.
+ *
+ * hvs_set_after(ctx, after_dists, after_ids, nq): attaches cursors (HOST memory, nq entries each).  nq must equal the number
+ * of resident queries: otherwise HVS_EINVAL and nothing changes.  Both pointers NULL removes the cursors (nq is not looked
+ * at); exactly one NULL is HVS_EINVAL.  Multi-GPU contexts cut the cursors by the queries' owner ranges; a row-partitioned
+ * context puts all of them on every part (after_id is a GLOBAL row id; each part translates it to its own rows).
+ * hvs_set_after_device: the same from DEVICE memory, by the rules of hvs_set_max_dist2_device -- plain device memory of any
+ * visible GPU (both buffers on the same one), `stream` = the stream that produced them (NULL: the null stream), host memory of
+ * any kind is HVS_EINVAL with the runtime's error cleared, the call blocks until the copies are done.
+ * hvs_set_after_from_results: every resident query's cursor becomes slot k-1 of its current result row, on the device, with
+ * no host round trip.  Requires that results for ALL resident queries exist (with the current k) and that padding is off --
+ * with padding on the last slot may be a pad row --, otherwise HVS_ESTATE and nothing changes.  Replicated multi-GPU context:
+ * each GPU does its own range.  Row-partitioned context: each owner's last slots travel to every part by device-to-device
+ * copies on the parts' streams (8 bytes per query).
+ * hvs_query_after: hvs_query with cursors, and optionally caps (max_d2 may be NULL), sent whole before the pipeline starts;
+ * they stay attached to the call's queries afterwards.  Both after_* NULL behaves as hvs_query_within; exactly one NULL is
+ * HVS_EINVAL.
+ * hvs_after_stats: figures of the last call (after hvs_sync / hvs_query); HVS_ESTATE where hvs_last_timing has none to report.
+ * Summed over a multi-GPU context; on a row-partitioned one by the rules of hvs_within_stats (cursor_queries the call's,
+ * underfull_queries the merge's, after_slots the sum of the parts' non-pad slots), exhausted_queries counted once.
+ */
+typedef struct hvs_after_info {
+    uint32_t cursor_queries;    /* queries of the last call that carried a cursor (all of them, or none) */
+    uint32_t exhausted_queries; /* of those, queries whose cursor was exhausted (after_id 0xFFFFFFFF)    */
+    uint32_t underfull_queries; /* of those, queries with fewer than k rows after their cursor           */
+    uint64_t after_slots;       /* non-pad slots over all queries with a cursor                          */
+} hvs_after_info;
+int hvs_set_after(hvs_ctx *ctx, const float *after_dists /* host, nq */, const uint32_t *after_ids /* host, nq */, uint32_t nq);
+int hvs_set_after_device(hvs_ctx *ctx, const float *d_after_dists /* device, nq */, const uint32_t *d_after_ids /* device, nq */, uint32_t nq,
+                         void *stream);
+int hvs_set_after_from_results(hvs_ctx *ctx);
+int hvs_query_after(hvs_ctx *ctx, const float *q_rows, const float *after_dists, const uint32_t *after_ids, const float *max_d2 /* may be NULL */,
+                    uint32_t nq, float sample_proportion, uint32_t *out_ids, float *out_dists);
+int hvs_after_stats(hvs_ctx *ctx, hvs_after_info *out);
+/* The host arithmetic of the contract for one query (no GPU, no context; any output may be NULL).  ids / dists: the query's m
+ * matched keys in key order (full(q), or a prefix of it that reaches k keys past the cursor); pad_ids / pad_dists: the first k
+ * padding rows and their exact-order distances (unused, may be NULL, when `padding` is 0).  out_ids / out_dists: the k slots of
+ * the page behind the cursor -- the first k keys > (after_dist, after_id), then padding or empty slots, in (dist asc, id asc)
+ * order; n_after: the non-pad slots. */
+void hvs_after_plan(const uint32_t *ids, const float *dists, uint32_t m, uint32_t k, float after_dist, uint32_t after_id, const uint32_t *pad_ids,
+                    const float *pad_dists, int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_after);
+
 #ifdef __cplusplus
 }
 #endif

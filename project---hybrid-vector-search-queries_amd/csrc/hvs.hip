@@ -189,6 +189,7 @@ struct HvsPart {
 };
 constexpr uint32_t kPartTailRows = HVS_KMAX;  // rows of the tail replica: the most a query can be padded with
 
+#define HVS_NCOUNTERS 20  // ([14], [15]: hvs_keep_within; [16] .. [18]: hvs_keep_after)
 struct hvs_ctx : HvsLane {
     int device = 0;
     HvsLane spare;                 // the second lane (its buffers are allocated by the first call that has two batches)
@@ -226,11 +227,25 @@ struct hvs_ctx : HvsLane {
     float* d_max_d2 = nullptr;
     bool caps_set = false;
     bool call_capped = false;  // the last call ran with caps (hvs_within_stats)
+    // per-query result cursors of the resident set (hvs_set_after): d_after_lo[q] = the cursor's key + 1, built by
+    // hvs_k_norm_after from the raw (distance, id) pairs in d_after_dist / d_after_id.  Allocated by the first call that sets
+    // cursors; while `after_set` is false no launch reads them and every call takes its kernels' plain forms.
+    uint64_t* d_after_lo = nullptr;
+    float* d_after_dist = nullptr;
+    uint32_t* d_after_id = nullptr;
+    uint32_t after_cap = 0;
+    bool after_set = false;
+    bool call_after = false;   // the last call ran with cursors (hvs_after_stats)
+    // results of the resident set: queries [res_lo, res_hi) have been answered with `res_k` slots since the set was installed
+    // (hvs_set_after_from_results needs all of them)
+    uint32_t res_lo = 0, res_hi = 0, res_k = 0;
+    uint32_t set_gen = 0;  // counts the resident sets this GPU has held (a row-partitioned root tells by it whose results it has: res_gen)
+    uint32_t res_gen = 0;
     uint32_t* d_out_ids = nullptr;
     float* d_out_dists = nullptr;
     uint32_t res_cap = 0;
 
-    unsigned long long* d_counters = nullptr;
+    unsigned long long* d_counters = nullptr;  // HVS_NCOUNTERS of them, zeroed at the start of every call
 
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
@@ -320,6 +335,8 @@ namespace {
 bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empty(); }
 // the resident queries carry distance caps: the CAPPED kernels run (with_capped)
 bool capped(const hvs_ctx* c) { return c->caps_set; }
+// ... carry result cursors: the AFTER kernels run (with_capped_after)
+bool has_after(const hvs_ctx* c) { return c->after_set; }
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
 uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
 uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
@@ -611,15 +628,36 @@ void with_capped(const hvs_ctx* c, F f)
         f(std::false_type{});
 }
 
+// ... and for the kernels that also have a cursor form: `f` gets (capped, after); after only while the resident
+// queries carry cursors
+template <typename F>
+void with_capped_after(const hvs_ctx* c, F f)
+{
+    with_capped(c, [&](auto WT) {
+        if (has_after(c))
+            f(WT, std::true_type{});
+        else
+            f(WT, std::false_type{});
+    });
+}
+template <typename F>
+void with_after(const hvs_ctx* c, F f)
+{
+    if (has_after(c))
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
 // the k best of every query's candidate lists to the output rows (hvs_k_select): `nsel` queries named by `qlist`, each with
 // `nchunks` lists of which list 0 of the first query is `cand` / `cnt` and consecutive queries' lists lie `stride` apart
 void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t stride, uint32_t nchunks, uint64_t* cand, uint32_t* cnt)
 {
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_capped(c, [&](auto WT) {
-            hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>),
+        with_capped_after(c, [&](auto WT, auto AT) {
+            hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt,
-                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->d_max_d2, c->d_counters);
+                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->d_max_d2, c->d_counters, c->d_after_lo);
         });
     });
 }
@@ -734,10 +772,11 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
         unsigned long long* stat = count_stats ? c->d_counters : c->d_counters + 4;
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
         with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-            with_capped(c, [&](auto WT) {
-                hipLaunchKernelGGL((hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>), grid,
-                                   dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt,
-                                   stat, c->k, c->rs.d_live, c->d_max_d2);
+            with_capped_after(c, [&](auto WT, auto AT) {
+                hipLaunchKernelGGL(
+                    (hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+                    grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat,
+                    c->k, c->rs.d_live, c->d_max_d2, c->d_after_lo);
             });
         });
     }
@@ -1042,16 +1081,19 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     // (rows of the indexed part, searched in the indexed part: the probe prices the index, and runs when it covers every row)
     const uint32_t step = std::max(1u, c->n_indexed / P);
     hipLaunchKernelGGL(hvs_k_probe_queries, dim3(hvs_ceil_div(P * HVS_QCOLS, 256u)), dim3(256), 0, c->stream, c->d_data, c->n_indexed, step, P, c->d_q);
-    hipError_t e = hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream);
+    hipError_t e = hipMemsetAsync(c->d_counters, 0, HVS_NCOUNTERS * sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
     // (the probe batch is small, but it stands for full batches: their failure target.  Its lists keep the production capacity:
     // PCA-like vectors at n = 10^7 hand ~1500 rows per type-0 query to the last level's list of 1024 -- INT8 tiles look 23 %
     // faster than FP16 tiles there only while a half-empty workspace doubles the lists, profiles/r04/nonuniform_int8.txt)
     c->force_pfail = guess_pfail_for(kBatchMfma);
     const bool caps_were_set = c->caps_set;  // (the caps belong to the caller's queries, not to the probe's)
+    const bool after_was_set = c->after_set;  // (so do the cursors)
     c->caps_set = false;
+    c->after_set = false;
     int rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
     c->caps_set = caps_were_set;
+    c->after_set = after_was_set;
     c->force_pfail = 0u;
     unsigned long long h[4] = {0, 0, 0, 0};
     uint32_t fails[2] = {0, 0};
@@ -1338,8 +1380,11 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
-                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters, count ? 1 : 0, c->rs.d_live);
+        with_after(c, [&](auto AT) {
+            hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
+                               dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters,
+                               count ? 1 : 0, c->rs.d_live, c->d_after_lo);
+        });
     });
 }
 
@@ -1349,8 +1394,11 @@ void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value>), dim3((B.nslots + 255u) / 256u),
-                           dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m, c->d_counters, count ? 1 : 0, c->rs.d_live);
+        with_after(c, [&](auto AT) {
+            hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
+                               dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m,
+                               c->d_counters, count ? 1 : 0, c->rs.d_live, c->d_after_lo);
+        });
     });
 }
 
@@ -1404,10 +1452,11 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     const int ev = kernel_timer_begin(c);
     const dim3 grid((slot_end + 255u) / 256u, nchunks);
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_capped(c, [&](auto WT) {
-            hipLaunchKernelGGL((hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>), grid,
-                               dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end,
-                               c->d_cand, c->d_cand_cnt, c->d_counters, index_mask(c));
+        with_capped_after(c, [&](auto WT, auto AT) {
+            hipLaunchKernelGGL(
+                (hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>), grid,
+                dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand,
+                c->d_cand_cnt, c->d_counters, index_mask(c), c->d_after_lo);
         });
     });
     kernel_timer_end(c, ev);
@@ -1568,11 +1617,11 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     uint32_t seed_chunks = 1u;
     if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = std::min(l0blocks, hvs_ceil_div(kSeedWaves, seed_waves));
     with_cap_mask(c, [&](auto CAPT, auto MT) {
-        with_capped(c, [&](auto WT) {
-            hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value>),
+        with_capped_after(c, [&](auto WT, auto AT) {
+            hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B,
                                c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->d_counters, std::max(1u, seed_chunks),
-                               index_mask(c));
+                               index_mask(c), c->d_after_lo);
         });
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
@@ -1580,15 +1629,16 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
             if (final)  // (only the final merge pads and drops keys beyond a cap: the merges in front of it have no masked or capped form)
-                with_capped(c, [&](auto WT) {
-                    hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value>), dim3((B.nslots + 3u) / 4u), dim3(256), 0,
-                                       c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt,
-                                       c->d_quant, L, next, G, c->rs.d_pad_ids, c->d_max_d2, c->d_counters);
+                with_capped_after(c, [&](auto WT, auto AT) {
+                    hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+                                       dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds,
+                                       c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids, c->d_max_d2,
+                                       c->d_counters, c->d_after_lo);
                 });
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
                                    c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids,
-                                   c->d_max_d2, c->d_counters);
+                                   c->d_max_d2, c->d_counters, c->d_after_lo);
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -1626,12 +1676,21 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             if (level + 1u == L.K && c->ev_pdone_cur) HVS_HIP(c, hipEventRecord(c->ev_pdone_cur, c->stream));
         }
         with_cap_mask(c, [&](auto, auto MT) {
-            constexpr bool M = decltype(MT)::value;
-            const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;  // (entry format)
-            // (while rows are stale the front end gets both masks and tells stale from dead: HVS_RESCORE_TWO_MASKS)
-            hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data,
-                               c->rs.h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS), sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters,
-                               index_mask(c));
+            with_after(c, [&](auto AT) {
+                constexpr bool M = decltype(MT)::value;
+                // (while rows are stale the front end gets both masks and tells stale from dead: HVS_RESCORE_TWO_MASKS)
+                const uint32_t nn = c->rs.h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS);
+                if constexpr (decltype(AT)::value) {
+                    const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M, const uint64_t*> : hvs_k_rescore<false, M, const uint64_t*>;  // (entry format)
+                    hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
+                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, index_mask(c),
+                                       static_cast<const uint64_t*>(c->d_after_lo));
+                } else {
+                    const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;
+                    hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
+                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, index_mask(c));
+                }
+            });
         });
         if (last == L.K) tail_before_final();
         launch_merge(last == L.K, last + 1u);
@@ -1869,12 +1928,22 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
     }
     c->timing_valid = false;
     c->call_capped = capped(c);
+    c->call_after = has_after(c);
+    // (the results the resident set has: this call's range joins the ranges answered so far if it touches them)
+    if (c->res_k != c->k || c->res_lo >= c->res_hi || q0 > c->res_hi || q0 + nq < c->res_lo) {
+        c->res_lo = q0;
+        c->res_hi = q0 + nq;
+        c->res_k = c->k;
+    } else {
+        c->res_lo = std::min(c->res_lo, q0);
+        c->res_hi = std::max(c->res_hi, q0 + nq);
+    }
     c->n_launch_events = 0;
     c->untimed_launches = 0;
     c->fallback_queries = 0;
     c->retry_queries = 0;
     c->demoted_queries = 0;  // (a list of an earlier call must never be scattered into this call's results)
-    HVS_HIP(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(c->d_counters, 0, HVS_NCOUNTERS * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream));
     HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
     const bool ranges = !mfma && c->have_order;  // exact engine: scan position ranges when the orderings exist
@@ -2020,7 +2089,7 @@ int leaf_create(hvs_ctx** out, int device)
         if ((e = hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     }
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), 16 * sizeof(unsigned long long))) != hipSuccess)
+    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), HVS_NCOUNTERS * sizeof(unsigned long long))) != hipSuccess)
         return bail("hipMalloc", e);
     if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_ovf_count), 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_layout), 16 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
@@ -2053,7 +2122,7 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
-    void* ptrs[] = {c->d_data, c->d_q, c->d_max_d2, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
+    void* ptrs[] = {c->d_data, c->d_q, c->d_max_d2, c->d_after_lo, c->d_after_dist, c->d_after_id, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
                     c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2513,6 +2582,9 @@ int leaf_begin_queries(hvs_ctx* c, uint32_t nq)
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = 0;
     c->caps_set = false;  // (caps belong to a resident set: every call that replaces the set removes them)
+    c->after_set = false;  // (and cursors)
+    c->res_lo = c->res_hi = 0;
+    ++c->set_gen;
     return ensure_queries(c, nq);
 }
 
@@ -2540,6 +2612,76 @@ int leaf_set_caps(hvs_ctx* c, const float* src, int src_dev, uint32_t count)
     c->caps_set = true;
     return HVS_OK;
 }
+
+// room for `nq` cursors (allocated by the first call that sets any: contexts that never page pay nothing)
+int ensure_after(hvs_ctx* c, uint32_t nq)
+{
+    if (nq <= c->after_cap) return HVS_OK;
+    int rc;
+    c->after_cap = 0;
+    c->after_set = false;  // (the buffers are about to change hands)
+    if ((rc = dev_alloc(c, &c->d_after_lo, (size_t)nq)) || (rc = dev_alloc(c, &c->d_after_dist, (size_t)nq)) ||
+        (rc = dev_alloc(c, &c->d_after_id, (size_t)nq)))
+        return rc;
+    c->after_cap = nq;
+    return HVS_OK;
+}
+
+// the raw cursors in d_after_dist / d_after_id become the resident queries' cursors; `row0`: the part's first global row
+int leaf_commit_after(hvs_ctx* c, uint32_t count, uint32_t row0)
+{
+    if (count) {
+        hipLaunchKernelGGL(hvs_k_norm_after, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, c->d_after_dist, c->d_after_id, count, row0,
+                           c->d_after_lo);
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
+    c->after_set = true;
+    return HVS_OK;
+}
+
+// hvs_set_after / hvs_set_after_device on one GPU, the counterpart of leaf_set_caps: `count` cursors (distance, id) from host
+// memory (src_dev < 0) or from device buffers of GPU src_dev, attached to the resident queries (count == c->nq: checked by the
+// caller), or removed (dists == nullptr).  An earlier call's pending re-runs are resolved first, under the cursors they were
+// asked under.
+int leaf_set_after(hvs_ctx* c, const float* dists, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);
+    if (rc) return rc;
+    if (!dists) {
+        c->after_set = false;
+        return HVS_OK;
+    }
+    if ((rc = ensure_after(c, std::max(count, 1u)))) return rc;
+    if (count) {
+        if (src_dev < 0) {
+            HVS_HIP(c, hipMemcpyAsync(c->d_after_dist, dists, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+            HVS_HIP(c, hipMemcpyAsync(c->d_after_id, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        } else if ((rc = copy_from_device(c, c->d_after_dist, dists, src_dev, (size_t)count * sizeof(float))) ||
+                   (rc = copy_from_device(c, c->d_after_id, ids, src_dev, (size_t)count * sizeof(uint32_t)))) {
+            return rc;
+        }
+    }
+    return leaf_commit_after(c, count, row0);
+}
+
+// hvs_set_after_from_results on one GPU that holds its own results (a single context, a leaf of a replicated one): checked by
+// the caller -- results of all resident queries exist with the current k, padding is off
+int leaf_after_from_results(hvs_ctx* c)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc = resolve_overflow(c);  // (the last slots of re-run queries too)
+    if (rc) return rc;
+    if ((rc = ensure_after(c, std::max(c->nq, 1u)))) return rc;
+    if (c->nq) {
+        hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, c->d_out_ids, c->d_out_dists, c->nq,
+                           c->k, c->d_after_dist, c->d_after_id);
+        HVS_HIP(c, hipGetLastError());
+    }
+    return leaf_commit_after(c, c->nq, 0u);
+}
+bool leaf_has_all_results(const hvs_ctx* c) { return c->res_k == c->k && c->res_lo == 0u && c->res_hi >= c->nq && (c->nq == 0u || c->res_hi > 0u); }
 
 int leaf_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
 {
@@ -2644,7 +2786,7 @@ struct PeerSink {
 // `max_d2` (hvs_query_within): the queries' distance caps, nq floats of host memory -- 4 bytes per query, sent whole before the
 // pipeline starts.
 int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists,
-               const PeerSink* sink = nullptr, const float* max_d2 = nullptr)
+               const PeerSink* sink = nullptr, const float* max_d2 = nullptr, const float* after_d = nullptr, const uint32_t* after_i = nullptr)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if (nq == 0) return HVS_OK;
@@ -2661,6 +2803,7 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     tr.mark("staging");
     c->nq = nq;
     if (max_d2 && (rc = leaf_set_caps(c, max_d2, -1, nq))) return rc;
+    if (after_d && (rc = leaf_set_after(c, after_d, after_i, -1, nq, 0u))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too)
     const bool sink_dists = sink && sink->want_dists;
     constexpr uint32_t SQ = hvs_ctx::kStageQ;
     constexpr int R = hvs_ctx::kRing;
@@ -3470,6 +3613,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         return fail(c, HVS_EINVAL, "query range outside the resident query set");
     c->part_timing_valid = false;
     c->call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
+    c->call_after = has_after(c->kids[0]);  // (likewise the cursors)
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -3562,6 +3706,16 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     }
     c->part_timing_valid = true;
     c->part_call_nq = nq;
+    // (the merged results the resident set has, as run_queries_cut keeps them for one GPU)
+    if (c->res_gen != c->kids[0]->set_gen || c->res_k != K || c->res_lo >= c->res_hi || q0 > c->res_hi || q0 + nq < c->res_lo) {
+        c->res_gen = c->kids[0]->set_gen;
+        c->res_lo = q0;
+        c->res_hi = q0 + nq;
+        c->res_k = K;
+    } else {
+        c->res_lo = std::min(c->res_lo, q0);
+        c->res_hi = std::max(c->res_hi, q0 + nq);
+    }
     return HVS_OK;
 }
 
@@ -4146,14 +4300,21 @@ int hvs_stream_wait(hvs_ctx* c, void* stream)
 int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids,
               float* out_dists)
 {
-    return hvs_query_within(c, q_rows, nullptr, nq, sample_proportion, out_ids, out_dists);
+    return hvs_query_after(c, q_rows, nullptr, nullptr, nullptr, nq, sample_proportion, out_ids, out_dists);
 }
 
 int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint32_t nq, float sample_proportion, uint32_t* out_ids,
                      float* out_dists)
 {
+    return hvs_query_after(c, q_rows, nullptr, nullptr, max_d2, nq, sample_proportion, out_ids, out_dists);
+}
+
+int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const uint32_t* after_i, const float* max_d2, uint32_t nq,
+                    float sample_proportion, uint32_t* out_ids, float* out_dists)
+{
     if (!c) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists, nullptr, max_d2);
+    if ((after_d == nullptr) != (after_i == nullptr)) return fail(c, HVS_EINVAL, "hvs_query_after: one of after_dists / after_ids is NULL");
+    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists, nullptr, max_d2, after_d, after_i);
     if (nq == 0) return HVS_OK;
     if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query: q_rows / out_ids is NULL");
     const auto t0 = std::chrono::steady_clock::now();
@@ -4161,6 +4322,7 @@ int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint3
         // all queries to every part over its own link, the resident call, each owner's merged slice home
         int rc = hvs_upload_queries(c, q_rows, nq);
         if (!rc && max_d2) rc = hvs_set_max_dist2(c, max_d2, nq);
+        if (!rc && after_d) rc = hvs_set_after(c, after_d, after_i, nq);
         if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
         if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
         c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -4178,7 +4340,8 @@ int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint3
                 return HVS_OK;
             }
             return leaf_query(c->kids[r], q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, out_ids + (size_t)a * c->k,
-                              out_dists ? out_dists + (size_t)a * c->k : nullptr, nullptr, max_d2 ? max_d2 + a : nullptr);
+                              out_dists ? out_dists + (size_t)a * c->k : nullptr, nullptr, max_d2 ? max_d2 + a : nullptr,
+                              after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr);
         });
     } else {
         // peer gather (A/B partner of the direct path): every GPU runs the same host pipeline on its slice of the caller's
@@ -4201,11 +4364,13 @@ int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint3
                     int r2 = leaf_upload_queries(k, q_rows, m);
                     if (r2) return r2;
                     if (max_d2 && (r2 = leaf_set_caps(k, max_d2, -1, m))) return r2;
+                    if (after_d && (r2 = leaf_set_after(k, after_d, after_i, -1, m, 0u))) return r2;
                     if ((r2 = run_queries(k, 0, m, sample_proportion, NoHook{}))) return r2;
                     return leaf_sync(k);
                 }
                 const PeerSink sink{k0, a, out_dists != nullptr};
-                return leaf_query(k, q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, nullptr, nullptr, &sink, max_d2 ? max_d2 + a : nullptr);
+                return leaf_query(k, q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, nullptr, nullptr, &sink, max_d2 ? max_d2 + a : nullptr,
+                                  after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr);
             });
         if (!rc) {
             (void)hipSetDevice(k0->device);
@@ -4421,6 +4586,191 @@ void hvs_within_plan(const uint32_t* ids, const float* dists, uint32_t k, float 
         } else {
             row.push_back(Slot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
         }
+    }
+    std::stable_sort(row.begin(), row.end(), [](const Slot& a, const Slot& b) { return a.key < b.key; });
+    for (uint32_t j = 0; j < k; ++j) {
+        if (out_ids) out_ids[j] = row[j].id;
+        if (out_dists) out_dists[j] = row[j].dist;
+    }
+}
+
+// ---- per-query result cursors (include/hvs.h "per-query result cursors") --------
+
+// cursors (host memory: src_dev < 0; device memory of GPU src_dev otherwise) to every leaf: its range of them, or, on a
+// row-partitioned context, all of them, seen from the part's first row
+static int set_after_everywhere(hvs_ctx* c, const float* dists, const uint32_t* ids, int src_dev, uint32_t nq)
+{
+    if (c->kids.empty()) return leaf_set_after(c, dists, ids, src_dev, nq, 0u);
+    return for_each_leaf(c, [&](uint32_t r) {
+        if (!dists) return leaf_set_after(c->kids[r], nullptr, nullptr, -1, 0u, 0u);
+        if (c->partitioned) return leaf_set_after(c->kids[r], dists, ids, src_dev, nq, c->part_row0.size() > r ? c->part_row0[r] : 0u);
+        return leaf_set_after(c->kids[r], dists + c->kid_q0[r], ids + c->kid_q0[r], src_dev, c->kid_q0[r + 1] - c->kid_q0[r], 0u);
+    });
+}
+
+int hvs_set_after(hvs_ctx* c, const float* after_dists, const uint32_t* after_ids, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!after_dists && !after_ids) return set_after_everywhere(c, nullptr, nullptr, -1, 0u);
+    if (!after_dists || !after_ids) return fail(c, HVS_EINVAL, "hvs_set_after: one of after_dists / after_ids is NULL");
+    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_after: nq is not the number of resident queries");
+    return set_after_everywhere(c, after_dists, after_ids, -1, nq);
+}
+
+int hvs_set_after_device(hvs_ctx* c, const float* d_after_dists, const uint32_t* d_after_ids, uint32_t nq, void* stream)
+{
+    if (!c) return HVS_EINVAL;
+    if (!d_after_dists && !d_after_ids) return set_after_everywhere(c, nullptr, nullptr, -1, 0u);
+    if (!d_after_dists || !d_after_ids) return fail(c, HVS_EINVAL, "hvs_set_after_device: one of d_after_dists / d_after_ids is NULL");
+    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_after_device: nq is not the number of resident queries");
+    int dev = 0, dev2 = 0;
+    if (nq) {  // (an empty set reads nothing)
+        int rc = device_of_buffer(c, d_after_dists, "hvs_set_after_device", &dev);
+        if (!rc) rc = device_of_buffer(c, d_after_ids, "hvs_set_after_device", &dev2);
+        if (!rc && dev != dev2) rc = fail(c, HVS_EINVAL, "hvs_set_after_device: the two buffers are on different GPUs");
+        if (!rc) rc = wait_for_producer(c, dev, stream);
+        if (rc) return rc;
+    }
+    return set_after_everywhere(c, d_after_dists, d_after_ids, dev, nq);
+}
+
+int hvs_set_after_from_results(hvs_ctx* c)
+{
+    if (!c) return HVS_EINVAL;
+    if (c->padding) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: padding is on (the last slot may be a pad row)");
+    if (c->kids.empty()) {
+        if (!leaf_has_all_results(c)) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no results for all resident queries");
+        return leaf_after_from_results(c);
+    }
+    const uint32_t N = (uint32_t)c->kids.size();
+    if (c->kid_q0.size() != N + 1u) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no resident queries");
+    if (!c->partitioned) {
+        for (hvs_ctx* k : c->kids)
+            if (!leaf_has_all_results(k)) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no results for all resident queries");
+        return for_each_leaf(c, [&](uint32_t r) { return leaf_after_from_results(c->kids[r]); });
+    }
+    // row-partitioned: the merged rows of an owner's queries live on the owner (d_m_ids / d_m_dists, global ids).  Every owner
+    // takes its queries' last slots, every part fetches each owner's piece with device-to-device copies on its own stream
+    // (8 bytes per query, like the list exchange) and builds its cursors as seen from its first row.
+    const uint32_t nq = c->kid_q0.back(), K = c->k;
+    if (!c->part_timing_valid || c->res_gen != c->kids[0]->set_gen || c->res_k != K || c->res_lo != 0u || c->res_hi < nq)
+        return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no results for all resident queries");
+    int rc = for_each_leaf(c, [&](uint32_t r) -> int {
+        hvs_ctx* k = c->kids[r];
+        HVS_HIP(k, hipSetDevice(k->device));
+        int r2 = ensure_after(k, std::max(nq, 1u));
+        if (r2) return r2;
+        const uint32_t a = c->kid_q0[r], own = c->kid_q0[r + 1] - a;
+        if (own) {
+            hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(own, 256u)), dim3(256), 0, k->stream, k->part.d_m_ids, k->part.d_m_dists,
+                               own, K, k->d_after_dist + a, k->d_after_id + a);
+            HVS_HIP(k, hipGetLastError());
+        }
+        HVS_HIP(k, hipStreamSynchronize(k->stream));
+        return HVS_OK;
+    });
+    if (!rc)
+        rc = for_each_leaf(c, [&](uint32_t r) -> int {
+            hvs_ctx* k = c->kids[r];
+            HVS_HIP(k, hipSetDevice(k->device));
+            for (uint32_t p = 0; p < N; ++p) {
+                const uint32_t a = c->kid_q0[p], own = c->kid_q0[p + 1] - a;
+                if (p == r || own == 0u) continue;
+                const hvs_ctx* src = c->kids[p];
+                HVS_HIP(k, hipMemcpyPeerAsync(k->d_after_dist + a, k->device, src->d_after_dist + a, src->device, (size_t)own * sizeof(float), k->stream));
+                HVS_HIP(k, hipMemcpyPeerAsync(k->d_after_id + a, k->device, src->d_after_id + a, src->device, (size_t)own * sizeof(uint32_t), k->stream));
+            }
+            return leaf_commit_after(k, nq, c->part_row0[r]);
+        });
+    if (rc) {
+        part_quiesce(c);
+        for (hvs_ctx* k : c->kids) k->after_set = false;  // (some parts may hold the new cursors and some the old: none is in force)
+    }
+    return rc;
+}
+
+static int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
+{
+    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = hvs_after_info{};
+    if (!c->call_after) return HVS_OK;
+    unsigned long long v[3] = {0, 0, 0};
+    HVS_HIP(c, hipMemcpy(v, c->d_counters + 16, sizeof(v), hipMemcpyDeviceToHost));
+    out->cursor_queries = c->timing.nq;
+    out->after_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    out->exhausted_queries = (uint32_t)v[2];
+    return HVS_OK;
+}
+
+int hvs_after_stats(hvs_ctx* c, hvs_after_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_after_stats(c, out);
+    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    hvs_after_info agg{};
+    uint32_t part_exhausted = 0;
+    bool any = false;
+    for (hvs_ctx* k : c->kids) {
+        if (!k->timing_valid) continue;  // (took no part in the last call)
+        hvs_after_info m{};
+        const int rc = leaf_after_stats(k, &m);
+        if (rc) return fail(c, rc, k->err);
+        agg.cursor_queries += m.cursor_queries;
+        agg.exhausted_queries += m.exhausted_queries;
+        agg.underfull_queries += m.underfull_queries;
+        agg.after_slots += m.after_slots;
+        part_exhausted = std::max(part_exhausted, m.exhausted_queries);
+        any = true;
+    }
+    if (c->partitioned) {
+        // the rules of hvs_within_stats: the parts' slots are summed, the queries are the call's, a query is under-full when the
+        // merge found fewer than k keys in all parts together; every part saw every cursor, so one part's count of exhausted ones
+        const bool on = c->call_after;
+        agg.cursor_queries = on ? c->part_call_nq : 0u;
+        agg.underfull_queries = on ? c->pinfo.padded_queries : 0u;
+        agg.exhausted_queries = on ? part_exhausted : 0u;
+        any = true;
+    }
+    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
+    *out = agg;
+    return HVS_OK;
+}
+
+void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_t k, float after_dist, uint32_t after_id, const uint32_t* pad_ids,
+                    const float* pad_dists, int padding, uint32_t* out_ids, float* out_dists, uint32_t* n_after)
+{
+    if (m && (!ids || !dists)) return;
+    const uint64_t lo = hvs_after_lo(after_dist, after_id, 0u);
+    struct Slot {
+        uint64_t key;
+        uint32_t id;
+        float dist;
+    };
+    auto slot_of = [](float d, uint32_t id) {
+        uint32_t bits;
+        std::memcpy(&bits, &d, sizeof(bits));
+        if (d != d) {  // (the engines' keys carry one NaN)
+            bits = 0x7FC00000u;
+            std::memcpy(&d, &bits, sizeof(d));
+        }
+        return Slot{((uint64_t)bits << 32) | id, id, d};
+    };
+    std::vector<Slot> row;
+    row.reserve(k);
+    for (uint32_t j = 0; j < m && row.size() < k; ++j) {  // (key order: the first k behind the cursor)
+        const Slot s = slot_of(dists[j], ids[j]);
+        if (ids[j] != 0xFFFFFFFFu && s.key >= lo) row.push_back(s);
+    }
+    const uint32_t after = (uint32_t)row.size();
+    if (n_after) *n_after = after;
+    for (uint32_t s = 0; after + s < k; ++s) {
+        if (padding && pad_ids && pad_dists)
+            row.push_back(slot_of(pad_dists[s], pad_ids[s]));
+        else
+            row.push_back(Slot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
     }
     std::stable_sort(row.begin(), row.end(), [](const Slot& a, const Slot& b) { return a.key < b.key; });
     for (uint32_t j = 0; j < k; ++j) {

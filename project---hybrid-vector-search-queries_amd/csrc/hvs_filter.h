@@ -1371,7 +1371,10 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 // CAPPED: the lane's threshold starts at the slot's tau -- the query's cap, set by hvs_k_prep<true> --
 // instead of +inf.  The chunked form writes its keys without a threshold test, as it always did: keys beyond the cap that it
 // leaves in a list never raise a threshold (hvs_k_merge takes min(tau, .)) and are dropped by the final merge.
-template <int CAP, bool MASKED, bool CAPPED = false>
+// AFTER (result cursors; `after_lo` is not read otherwise): only keys >= after_lo[query] are admitted.  The chunked
+// form cannot reserve a block's places from the ranges alone then -- how many of a block's rows lie behind the cursor is known
+// only once their distances are --, so it takes one place per admitted key with an atomic of its own.
+template <int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restrict__ D, uint32_t n, uint32_t sn,
                                                            const float* __restrict__ Q, HvsBatch B,
                                                            const uint32_t* __restrict__ perm_ct,
@@ -1379,7 +1382,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
                                                            const uint32_t* __restrict__ bpos_ct,
                                                            const uint32_t* __restrict__ bpos_t, HvsLevels L,
                                                            unsigned long long* __restrict__ counters, uint32_t nchunks,
-                                                           const uint32_t* __restrict__ live)
+                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
     __shared__ float4 srow[4][HVS_SEED_STAGE][26];  // per wave: 16 data rows as 16-byte aligned images x0..x99 (+ pad)
     // nchunks > 1 (small batches, level 0 of at most 1024 rows): grid.y waves share one 64-slot group, each
@@ -1412,11 +1415,13 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
     uint64_t* __restrict__ mylist = B.cand + (size_t)slot * B.fcap;
     float tau = __builtin_inff();
     if constexpr (CAPPED) tau = B.tau[slot];
+    uint64_t key_lo = 0ull;
+    if constexpr (AFTER) key_lo = have_q ? after_lo[qi] : HVS_AFTER_NOTHING;
     uint32_t cnt = 0, nscan = 0;
     for (uint32_t i = lo + blockIdx.y; i < hi; i += nchunks) {
         const uint32_t b = bpos[i];
         uint32_t kk = 0, kend = 0;  // chunked form: this lane's places [kk, kend) in its slot's list for the block's rows
-        if (nchunks > 1u) {         // wave-uniform
+        if (!AFTER && nchunks > 1u) {  // wave-uniform
             // ONE atomic per lane and block instead of one per row and lane: the rows of the block a lane takes are its
             // range cut to the block, less those outside the sampled prefix (and, MASKED, the dead ones)
             const uint32_t p0 = b * 32u, p1 = (p0 + 32u < n) ? p0 + 32u : n;
@@ -1477,6 +1482,23 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
             }
             nscan += 64u;
             const float dist = hvs_exact_dist_pk_lds(&srow[threadIdx.x >> 6][r & (HVS_SEED_STAGE - 1u)][0], q2);
+            if constexpr (AFTER) {
+                if (nchunks > 1u) {  // wave-uniform: one place per key behind the cursor (see AFTER above)
+                    const uint64_t key = hvs_make_key(dist, id);
+                    if (pass && key >= key_lo) {
+                        const uint32_t at = atomicAdd(&B.candcnt[slot], 1u);
+                        if (at < B.fcap)
+                            mylist[at] = key;
+                        else
+                            hvs_flag_fail(B.fail_code, B.overflow, slot);
+                    }
+                    continue;
+                }
+                if (pass && dist <= tau && hvs_make_key(dist, id) >= key_lo) {
+                    mylist[cnt] = hvs_make_key(dist, id);
+                    ++cnt;
+                }
+            } else {
             if (nchunks > 1u) {  // wave-uniform
                 if (pass && kk < kend) mylist[kk] = hvs_make_key(dist, id);
                 kk += pass ? 1u : 0u;
@@ -1485,6 +1507,7 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
             if (pass && dist <= tau) {
                 mylist[cnt] = hvs_make_key(dist, id);
                 ++cnt;
+            }
             }
             uint64_t full = __ballot(cnt == (uint32_t)CAP);
             if (full != 0ull) {
@@ -1524,7 +1547,8 @@ struct HvsUniformRowF2 {
 // CAPPED: admission gains `dist <= cap` beside the threshold test; the cap is the slot's tau, where
 // hvs_k_prep<true> put it (nothing lowers it in the exact engine).  The lane's own threshold keeps its "NaN admits every row
 // until the first cut" start: the cap is a second test, not its initial value.
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
+// AFTER: ... and `key >= after_lo[query]` (result cursors; `after_lo` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restrict__ D, uint32_t sn,
                                                             const float* __restrict__ Q, HvsBatch B,
                                                             const uint32_t* __restrict__ perm_ct,
@@ -1532,7 +1556,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
                                                             uint32_t slot_begin, uint32_t slot_end, uint64_t* __restrict__ cand,
                                                             uint32_t* __restrict__ cand_cnt,
                                                             unsigned long long* __restrict__ counters,
-                                                            const uint32_t* __restrict__ live)
+                                                            const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -1574,6 +1598,8 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
     float tau = __builtin_nanf("");  // admits every passing row until the first cut (see hvs_k_scan_exact_lds)
     float cap = 0.0f;
     if constexpr (CAPPED) cap = have_q ? B.tau[slot] : HVS_CAP_NOTHING;
+    uint64_t key_lo = 0ull;
+    if constexpr (AFTER) key_lo = have_q ? after_lo[qi] : HVS_AFTER_NOTHING;
     uint32_t cnt = 0, nscan = 0;
     for (uint32_t pos = p0; pos < p1; ++pos) {
         const bool pass = pos >= ra && pos < rb;
@@ -1596,6 +1622,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         }
         bool admit = pass && !(dist > tau);  // ids are not monotone along a position range: keep ties, the keys sort them out
         if constexpr (CAPPED) admit = admit && dist <= cap;
+        if constexpr (AFTER) admit = admit && hvs_make_key(dist, id) >= key_lo;
         if (admit) {
             mylist[cnt] = hvs_make_key(dist, id);
             ++cnt;
@@ -2694,13 +2721,20 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 // form of HVS_RESCORE_TWO_MASKS, which the host announces in bit 31 of `n` (an index covers at most 2^29 rows): a dropped
 // survivor whose row is live -- dropped for staleness alone -- goes to counters[13] (hvs_update_info.stale_survivors) instead.
 #define HVS_RESCORE_TWO_MASKS 0x80000000u  // in `n`: live[W + i] (W = 2 ceil(n / 64) words) holds the row mask's bits of the indexed rows
-template <bool E16, bool MASKED>
+// AFTER (result cursors; `after_lo` is not read otherwise): a pair's key is appended only if it is >= after_lo of its
+// slot's query -- beside the threshold test, which it does not replace.  The kernel reads its launch dimensions, which lie
+// behind the arguments, so one more argument would move them for the plain form too: the cursor form takes `after_lo` as the
+// one member of the argument pack AFTER (const uint64_t*), and the plain form, with an empty pack, keeps its argument block.
+template <typename T>
+__device__ __forceinline__ T hvs_only_arg(T a) { return a; }
+template <bool E16, bool MASKED, typename... AFTER>
 __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const float* __restrict__ D, uint32_t n, uint32_t sn, const float* __restrict__ Q,
                                                      HvsBatch B, const uint32_t* __restrict__ perm_ct,
                                                      const uint32_t* __restrict__ perm_t,
                                                      unsigned long long* __restrict__ counters,
-                                                     const uint32_t* __restrict__ live)
+                                                     const uint32_t* __restrict__ live, AFTER... after_lo)
 {
+    static_assert(sizeof...(AFTER) <= 1, "AFTER is empty, or the cursors' const uint64_t*");
     // the group's 128 query vectors are staged in LDS once per block (51 KB)
     __shared__ float sq[HVS_GROUP][HVS_NDIM];
     __shared__ uint64_t slist[HVS_RESCORE_WAVES][64];  // wave-private (slot << 32 | position) pairs of one round
@@ -2820,6 +2854,13 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
                 pend[u] = ok[u] && t4 == 0u && dist <= B.tau[slot[u]];
                 pend_slot[u] = slot[u];
                 pend_key[u] = hvs_make_key(dist, id[u]);
+                if constexpr (sizeof...(AFTER) != 0) {
+                    if (pend[u]) {
+                        const uint64_t* __restrict__ lo = hvs_only_arg(after_lo...);
+                        const uint32_t qa = B.qid[slot[u]];
+                        pend[u] = qa != 0xFFFFFFFFu && pend_key[u] >= lo[qa];
+                    }
+                }
                 if (pend[u]) pend_k[u] = atomicAdd(&B.candcnt[slot[u]], 1u);  // (result used by the next retire)
             }
         }
@@ -2996,13 +3037,17 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 // that a guess lowered is a retry, as before.  Then the keys beyond the cap leave (hvs_keep_within: the chunked seed and the
 // tail scans may have let some in, and rows with NaN distances) and the padding fills what they leave.  The merges in front
 // of the final one have no capped form: min(tau, m-th smallest held) never exceeds the cap tau started from.
-template <bool FINAL, int CAP, bool MASKED, bool CAPPED = false>
+//
+// AFTER (FINAL only, result cursors; `after_lo` is not read otherwise).  Every list the levels filled holds keys behind
+// the query's cursor only (seed, re-scoring, tail and stale scans test it at admission), so "the range's rows" above reads "the
+// range's rows behind the cursor" throughout and the verification is the plain one.  hvs_keep_after tests once more and counts.
+template <bool FINAL, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
 __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, uint32_t n, const float* __restrict__ Q,
                                                    HvsBatch B, const HvsBounds* __restrict__ bounds, int pad,
                                                    uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, int fmt,
                                                    const HvsQuant* __restrict__ qz, HvsLevels L, uint32_t level_next,
                                                    HvsGuessTable G, const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps,
-                                                   unsigned long long* __restrict__ counters)
+                                                   unsigned long long* __restrict__ counters, const uint64_t* __restrict__ after_lo)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -3096,6 +3141,12 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
         failed = (uint32_t)__shfl((int)failed, 0);
         cnt = hvs_keep_within(buf, cnt, cap, knn, lane, counters, failed == 0u);
     }
+    if constexpr (AFTER) {
+        // (after the verification above has flagged what it flags: a failed query is answered again, and counted then)
+        uint32_t failed = lane == 0u ? B.overflow[slot] : 0u;
+        failed = (uint32_t)__shfl((int)failed, 0);
+        cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, failed == 0u);
+    }
     // ---- final: pad, rank-sort, write
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
     for (uint32_t base = cnt; base < knn; base += 64u) {
@@ -3186,11 +3237,12 @@ struct HvsTailOut {
 // LIST staging is the 16-row gather of hvs_k_seed_exact: the workgroup gathers a block of HVS_LDS_ROWS rows by id, one HBM
 // round trip per block -- the ids of a block are fetched one block earlier than its rows, so the dependent pair id -> row is
 // never paid in sequence inside the loop --, double-buffered like the contiguous form, the ids kept in LDS beside the rows.
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool LIST, int CNT>
+// AFTER (result cursors; `after_lo` is not read otherwise): a key is wanted only if it is >= after_lo[query].
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool LIST, int CNT, bool AFTER = false>
 __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict__ D, const float* __restrict__ Q, const HvsBatch B,
                                                          const HvsTailOut O, const uint32_t* __restrict__ ids, uint32_t tail_lo,
                                                          uint32_t tail_hi, unsigned long long* __restrict__ counters, int count,
-                                                         const uint32_t* __restrict__ live)
+                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo = nullptr)
 {
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     __shared__ uint32_t sid[LIST ? 2 : 1][LIST ? HVS_LDS_ROWS : 1];  // (LIST) ids of the staged rows
@@ -3222,6 +3274,8 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
     const uint32_t segcap = room < (uint32_t)CAP ? room : (uint32_t)CAP;  // (0: a full list -- flagged only if a key needs a place)
     uint64_t* __restrict__ myseg = O.lists + (size_t)(takes ? slot : 0u) * O.stride + s0;
     float tau = (takes && O.tau) ? O.tau[slot] : __builtin_inff();
+    uint64_t key_lo = 0ull;
+    if constexpr (AFTER) key_lo = have_q ? after_lo[qi] : HVS_AFTER_NOTHING;
     uint32_t cnt = 0, npass = 0, nadm = 0, nrows = 0;
 
     // staging: item e = (row r, piece c): c < 25 -> floats 2+4c..5+4c of the row, c == 25 -> (C, T, 0, 0)
@@ -3309,6 +3363,7 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
                     dist = hvs_exact_dist_pk_lds(rowp, q2);
                 }
                 bool want = pass && takes && !(dist > tau);
+                if constexpr (AFTER) want = want && hvs_make_key(dist, id) >= key_lo;
                 // a key that finds its segment full: the wave cuts the segment first (or flags the query when it cannot)
                 uint64_t full = __ballot(want && cnt == segcap);
                 if (full != 0ull) {
@@ -3363,13 +3418,13 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
 // per SIMD, so here it is also workgroups per CU -- a change of the block size changes the register budget with it.  Two,
 // where hvs_k_scan_exact_lds has three: beside the exact engine's row loop a lane keeps its segment's place, room and fill,
 // which at three -- 168 registers -- spilled 4 to 8 of them; the kernel runs once per batch over a few thousand rows)
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false>
 __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restrict__ D, const float* __restrict__ Q,
                                                                          HvsBatch B, HvsTailOut O, uint32_t tail_lo, uint32_t tail_hi,
                                                                          unsigned long long* __restrict__ counters, int count,
-                                                                         const uint32_t* __restrict__ live)
+                                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, 9>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, 9, AFTER>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live, after_lo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3381,11 +3436,11 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
 // row is dead to the index only) on that id.
 // counters (`count` != 0): [0] passing pairs, [11] pairs evaluated, [12] keys admitted.
 // ---------------------------------------------------------------------------------------------
-template <bool SCALAR_ORDER, int CAP, bool MASKED>
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false>
 __global__ __launch_bounds__(256, 2) void hvs_k_scan_stale(const float* __restrict__ D, const float* __restrict__ Q, HvsBatch B,
                                                            HvsTailOut O, const uint32_t* __restrict__ stale_ids, uint32_t m,
                                                            unsigned long long* __restrict__ counters, int count,
-                                                           const uint32_t* __restrict__ live)
+                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, 11>(D, Q, B, O, stale_ids, 0u, m, counters, count, live);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, 11, AFTER>(D, Q, B, O, stale_ids, 0u, m, counters, count, live, after_lo);
 }

@@ -155,6 +155,44 @@ __global__ void hvs_k_norm_caps(float* __restrict__ caps, uint32_t nq)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-query result cursors (hvs_set_after / hvs_query_after): one key (after_dist, after_id) per resident query;
+// a row takes part in the query's answer only if its key (hvs_make_key: distance bits, then id) is strictly greater.  The
+// device keeps `lo[q]` = the cursor's key + 1, so that the whole test is `key >= lo[q]`, one 64-bit compare; an exhausted
+// cursor (after_id = 0xFFFFFFFF) gives lo = ~0, the empty-slot key, which no row has.  hvs_k_norm_after builds lo once, when
+// the cursors are attached.  `row0`: the first global row of a part of a row-partitioned context (0 otherwise) -- the cursor
+// names a GLOBAL id and the part's keys carry local ones, so a cursor row in front of the part admits every local row at the
+// cursor's distance (local id 0 on) and one inside or behind it admits the local ids above after_id - row0.
+// Kernels that honour cursors are the AFTER = true instantiations of the kernels concerned (the MASKED / CAPPED pattern
+// above); the host launches them only while cursors are set.  Unlike a cap a cursor is tested at EVERY admission into a
+// candidate list: a list that admitted keys in front of the cursor would keep exactly those and prune the wanted ones.
+// ---------------------------------------------------------------------------------------------
+#define HVS_AFTER_NOTHING (~0ull)
+__host__ __device__ __forceinline__ uint64_t hvs_after_lo(float dist, uint32_t id, uint32_t row0)
+{
+    if (id == 0xFFFFFFFFu) return HVS_AFTER_NOTHING;
+    const uint32_t bits = (dist != dist) ? 0x7FC00000u : __builtin_bit_cast(uint32_t, dist);
+    if (id < row0) return (uint64_t)bits << 32;
+    return (((uint64_t)bits << 32) | (uint64_t)(id - row0)) + 1ull;  // (id - row0 < 0xFFFFFFFF: no carry into the distance)
+}
+__global__ void hvs_k_norm_after(const float* __restrict__ dists, const uint32_t* __restrict__ ids, uint32_t nq, uint32_t row0,
+                                 uint64_t* __restrict__ lo)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) lo[i] = hvs_after_lo(dists[i], ids[i], row0);
+}
+// hvs_set_after_from_results: the last slot of `nq` result rows of `knn` slots (padding off: the largest key held, or the
+// empty slot 0xFFFFFFFF / +inf of an under-full row -- an exhausted cursor) as raw cursors, for hvs_k_norm_after
+__global__ void hvs_k_after_from_results(const uint32_t* __restrict__ out_ids, const float* __restrict__ out_dists, uint32_t nq,
+                                         uint32_t knn, float* __restrict__ dists, uint32_t* __restrict__ ids)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const size_t last = (size_t)i * knn + (knn - 1u);
+    ids[i] = out_ids[last];
+    dists[i] = out_dists[last];
+}
+
+// ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------
 // `first_row`: out[0] is element 0 of that row of the stream (a part of a row-partitioned context generates its own rows)
@@ -315,11 +353,13 @@ struct HvsLdsRow1 {
 // MASKED: rows whose bit in `live` is clear are skipped (the row is wave-uniform: one scalar load and branch per row);
 // `sn` is then the cut id of the sampled live prefix (hvs_mask_plan)
 // CAPPED: admission gains `dist <= caps[query]` beside the threshold test (`caps` is not read otherwise)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
+// AFTER: ... and `key >= after_lo[query]` (result cursors; `after_lo` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
 __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
     uint32_t nq_pad, uint32_t sn, uint32_t rows_per_chunk, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt,
-    unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live, const float* __restrict__ caps)
+    unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live, const float* __restrict__ caps,
+    const uint64_t* __restrict__ after_lo)
 {
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     const uint32_t lane = threadIdx.x & 63u;
@@ -383,6 +423,8 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     float tau = __builtin_nanf("");
     float cap = 0.0f;
     if constexpr (CAPPED) cap = caps[qi];
+    uint64_t lo = 0ull;
+    if constexpr (AFTER) lo = after_lo[qi];
     uint32_t cnt = 0;
     uint32_t npass = 0, nscan = 0;
     // queries are sorted by type: a wave of type-0 queries only (the exact engine's slowest class) skips the per-row predicate --
@@ -427,6 +469,7 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
                 }
                 bool admit = pass && !(dist >= tau);
                 if constexpr (CAPPED) admit = admit && dist <= cap;
+                if constexpr (AFTER) admit = admit && hvs_make_key(dist, j0 + r) >= lo;
                 if (admit) {
                     mylist[cnt] = hvs_make_key(dist, j0 + r);
                     ++cnt;
@@ -494,14 +537,41 @@ __device__ __forceinline__ uint32_t hvs_keep_within(uint64_t* buf, uint32_t cnt,
     return kept;
 }
 
+// The final kernels' share of the cursors (hvs_k_select, hvs_k_merge with AFTER): every stage in front admits keys >= lo only,
+// so this drops nothing -- it tests defensively, as hvs_keep_within does, and counts for hvs_after_info:
+// counters[16] += slots kept, counters[17] += 1 for an under-full query, counters[18] += 1 for an exhausted cursor.
+__device__ __forceinline__ uint32_t hvs_keep_after(uint64_t* buf, uint32_t cnt, uint64_t lo, uint32_t knn, uint32_t lane,
+                                                   unsigned long long* __restrict__ counters, bool count)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    uint32_t kept = 0;
+    for (uint32_t off = 0; off < cnt; off += 64u) {  // (wave-uniform; a chunk's keys land at or below their own places)
+        const uint32_t e = off + lane;
+        const uint64_t key = e < cnt ? buf[e] : 0ull;
+        const bool in = e < cnt && key >= lo;
+        const uint64_t m = __ballot(in);
+        if (in) buf[kept + hvs_prefix_count(m)] = key;
+        kept += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (count && lane == 0u) {
+        if (kept) atomicAdd(&counters[16], (unsigned long long)kept);
+        if (kept < knn) atomicAdd(&counters[17], 1ull);
+        if (lo == HVS_AFTER_NOTHING) atomicAdd(&counters[18], 1ull);
+    }
+    return kept;
+}
+
 // MASKED: the padding ids come from `pad_ids` (the last k live rows, descending) instead of n - 1, n - 2, ...
 // CAPPED: keys beyond caps[query] leave before the padding (hvs_keep_within; `caps` and `counters` are not read otherwise)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false>
+// AFTER: keys in front of after_lo[query] likewise (hvs_keep_after; `after_lo` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
 __global__ __launch_bounds__(256) void hvs_k_select(
     const float* __restrict__ D, uint32_t n, const float* __restrict__ Q, const uint32_t* __restrict__ qorder,
     uint32_t nq, uint32_t nq_pad, uint32_t nchunks, const uint64_t* __restrict__ cand,
     const uint32_t* __restrict__ cand_cnt, int pad, uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
-    const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps, unsigned long long* __restrict__ counters)
+    const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps, unsigned long long* __restrict__ counters,
+    const uint64_t* __restrict__ after_lo)
 {
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
@@ -536,6 +606,7 @@ __global__ __launch_bounds__(256) void hvs_k_select(
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
     if constexpr (CAPPED) cnt = hvs_keep_within(buf, cnt, caps[qi], knn, lane, counters, true);
+    if constexpr (AFTER) cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, true);
     // padding: fewer than 100 matching rows in [0,sn)
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
     for (uint32_t base = cnt; base < knn; base += 64u) {

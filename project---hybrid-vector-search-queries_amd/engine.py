@@ -91,6 +91,15 @@ class WithinInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class AfterInfo(C.Structure):
+    """hvs_after_info (include/hvs.h)."""
+    _fields_ = [("cursor_queries", C.c_uint32), ("exhausted_queries", C.c_uint32), ("underfull_queries", C.c_uint32),
+                ("after_slots", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def library_path():
     return _LIB
 
@@ -240,6 +249,12 @@ def library():
         "hvs_query_within": (C.c_int, [vp, _f32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
         "hvs_within_stats": (C.c_int, [vp, C.POINTER(WithinInfo)]),
         "hvs_within_plan": (None, [_u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
+        "hvs_set_after": (C.c_int, [vp, _f32p, _u32p, C.c_uint32]),
+        "hvs_set_after_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "hvs_set_after_from_results": (C.c_int, [vp]),
+        "hvs_query_after": (C.c_int, [vp, _f32p, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_after_stats": (C.c_int, [vp, C.POINTER(AfterInfo)]),
+        "hvs_after_plan": (None, [_u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -375,6 +390,35 @@ def within_plan(ids, dists, max_d2, pad_ids=None, pad_dists=None, padding=True):
     return out_ids, out_d, int(n_in.value)
 
 
+def after_plan(ids, dists, k, after_dist, after_id, pad_ids=None, pad_dists=None, padding=True):
+    """hvs_after_plan: a query's matched keys in key order (m ids, m distances) and a cursor -> (ids, dists, n_after) of the
+    page of k slots behind the cursor, padded from pad_ids / pad_dists (the first k padding rows) when `padding`."""
+    ids = np.ascontiguousarray(ids, np.uint32).ravel()
+    dists = np.ascontiguousarray(dists, np.float32).ravel()
+    m, k = ids.size, int(k)
+    if dists.size != m:
+        raise HvsError(-1, "after_plan: ids and dists must have the same number of entries")
+    if padding:
+        pad_ids = np.ascontiguousarray(pad_ids, np.uint32).ravel()
+        pad_dists = np.ascontiguousarray(pad_dists, np.float32).ravel()
+        if pad_ids.size < k or pad_dists.size < k:
+            raise HvsError(-1, "after_plan: padding needs k pad ids and k pad distances")
+    out_ids, out_d, n_after = np.empty(k, np.uint32), np.empty(k, np.float32), C.c_uint32(0)
+    library().hvs_after_plan(_up(ids) if m else None, _fp(dists) if m else None, m, k, C.c_float(after_dist), int(after_id) & 0xFFFFFFFF,
+                             _up(pad_ids) if padding else None, _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids),
+                             _fp(out_d), C.byref(n_after))
+    return out_ids, out_d, int(n_after.value)
+
+
+def _device_u32(x, what):
+    """(pointer, entries) of a GPU tensor of 32-bit integers (torch.uint32 or torch.int32: the bits are the ids)."""
+    import torch
+    ok = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+    if not isinstance(x, torch.Tensor) or x.dtype not in ok or not x.is_cuda or not x.is_contiguous():
+        raise HvsError(-1, f"{what}: the id tensor must be int32 / uint32, contiguous and on a GPU")
+    return int(x.data_ptr()), x.numel()
+
+
 def _device_rows(x, count, cols, what):
     """(pointer, rows) of a device buffer given as a raw pointer plus a row count, or as an object with data_ptr() and shape
     (a torch tensor): float32, contiguous, on a GPU, rows of `cols` floats."""
@@ -426,6 +470,7 @@ class Engine:
         if rc != 0:
             raise HvsError(rc, self._lib.hvs_last_global_error().decode())
         self._h = h
+        self._padding = True  # (what set_padding last asked for: query_pages restores it)
 
     @property
     def num_gpus(self):
@@ -480,6 +525,7 @@ class Engine:
     def set_padding(self, enabled):
         """Off: answers of a data shard keep id 0xFFFFFFFF / distance +inf in unmatched slots."""
         self._ck(self._lib.hvs_set_padding(self._h, int(bool(enabled))))
+        self._padding = bool(enabled)
 
     # --- data
     def load_data(self, rows):
@@ -592,10 +638,11 @@ class Engine:
         self._ck(self._lib.hvs_trim_rows(self._h))
 
     # --- the vec_query seam
-    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None):
+    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None):
         """hvs_query: host rows in, host ids (and distances) out.  `out_ids` / `out_dists`: caller-provided arrays
         (e.g. views of pinned memory) to be filled instead of fresh ones.  `max_dist2`: one squared-distance cap per query
-        (hvs_query_within: the k nearest rows within it); None = no caps."""
+        (hvs_query_within: the k nearest rows within it); None = no caps.  `after`: (dists, ids), one result cursor per query
+        (hvs_query_after: the k nearest rows after that key); None = no cursors."""
         q = np.ascontiguousarray(q_rows, np.float32)
         if q.ndim != 2 or q.shape[1] != QCOLS:
             raise HvsError(-1, "query rows must be nq x 104 float32")
@@ -606,12 +653,21 @@ class Engine:
             raise HvsError(-1, "out_ids must be a C-contiguous nq x k uint32 array")
         if d is not None and (d.shape != (nq, K) or d.dtype != np.float32 or not d.flags.c_contiguous):
             raise HvsError(-1, "out_dists must be a C-contiguous nq x k float32 array")
-        if max_dist2 is None:
-            self._ck(self._lib.hvs_query(self._h, _fp(q), nq, sample_proportion, _up(ids), _fp(d) if d is not None else None))
-        else:
+        caps = None
+        if max_dist2 is not None:
             caps = np.ascontiguousarray(max_dist2, np.float32).ravel()
             if caps.size != nq:
                 raise HvsError(-1, "max_dist2 must hold one float32 per query")
+        if after is not None:
+            ad = np.ascontiguousarray(after[0], np.float32).ravel()
+            ai = np.ascontiguousarray(after[1], np.uint32).ravel()
+            if ad.size != nq or ai.size != nq:
+                raise HvsError(-1, "after must be (dists, ids) with one entry per query each")
+            self._ck(self._lib.hvs_query_after(self._h, _fp(q), _fp(ad), _up(ai), _fp(caps) if caps is not None else None, nq,
+                                               sample_proportion, _up(ids), _fp(d) if d is not None else None))
+        elif caps is None:
+            self._ck(self._lib.hvs_query(self._h, _fp(q), nq, sample_proportion, _up(ids), _fp(d) if d is not None else None))
+        else:
             self._ck(self._lib.hvs_query_within(self._h, _fp(q), _fp(caps), nq, sample_proportion, _up(ids),
                                                 _fp(d) if d is not None else None))
         return (ids, d) if d is not None else ids
@@ -635,6 +691,64 @@ class Engine:
         w = WithinInfo()
         self._ck(self._lib.hvs_within_stats(self._h, C.byref(w)))
         return w
+
+    # --- per-query result cursors (include/hvs.h "per-query result cursors")
+    def set_after(self, dists, ids, stream=None):
+        """Attach one result cursor (after_dist, after_id) per resident query: two host arrays (hvs_set_after), two GPU tensors
+        (hvs_set_after_device: float32 distances, int32 / uint32 ids; `stream` as for set_queries_device), or None, None to
+        remove the cursors.  Any call that replaces the resident queries removes them too."""
+        if dists is None and ids is None:
+            self._ck(self._lib.hvs_set_after(self._h, None, None, 0))
+        elif dists is None or ids is None:
+            raise HvsError(-1, "set_after: give both dists and ids, or None for both")
+        elif hasattr(dists, "data_ptr") and hasattr(ids, "data_ptr"):
+            pd, n = _device_rows(dists, None, 1, "set_after")
+            pi, ni = _device_u32(ids, "set_after")
+            if ni != n:
+                raise HvsError(-1, "set_after: dists and ids must have one entry per query each")
+            self._ck(self._lib.hvs_set_after_device(self._h, C.c_void_p(pd) if pd else None, C.c_void_p(pi) if pi else None, n,
+                                                    _stream_ptr(stream)))
+        else:
+            ad = np.ascontiguousarray(dists, np.float32).ravel()
+            ai = np.ascontiguousarray(ids, np.uint32).ravel()
+            if ad.size != ai.size:
+                raise HvsError(-1, "set_after: dists and ids must have one entry per query each")
+            self._ck(self._lib.hvs_set_after(self._h, _fp(ad), _up(ai), ad.size))
+
+    def set_after_from_results(self):
+        """hvs_set_after_from_results: every resident query's cursor becomes the last slot of its current result row, on the
+        device (padding must be off, results of all resident queries must exist)."""
+        self._ck(self._lib.hvs_set_after_from_results(self._h))
+
+    def after_stats(self):
+        """hvs_after_stats: queries with a cursor, exhausted and under-full ones, and non-pad slots of the last call."""
+        a = AfterInfo()
+        self._ck(self._lib.hvs_after_stats(self._h, C.byref(a)))
+        return a
+
+    def query_pages(self, q_rows, pages, sample_proportion=1.0, max_dist2=None):
+        """The pages * k nearest rows of every query, k at a time: page 1 by query(), pages 2.. by set_after_from_results +
+        query_resident.  Padding is off for the call (and restored): unpadded [nq][pages * k] ids and distances, empty slots
+        0xFFFFFFFF / +inf behind a query's last match."""
+        pages = int(pages)
+        if pages < 1:
+            raise HvsError(-1, "query_pages: pages must be at least 1")
+        was = self._padding
+        self.set_padding(False)
+        try:
+            ids, d = self.query(q_rows, sample_proportion, max_dist2=max_dist2)
+            nq, K = ids.shape
+            out_i = np.empty((nq, pages * K), np.uint32)
+            out_d = np.empty((nq, pages * K), np.float32)
+            out_i[:, :K], out_d[:, :K] = ids, d
+            for p in range(1, pages):
+                self.set_after_from_results()
+                self.query_resident(0, nq, sample_proportion)
+                pi, pd = self.download_results(0, nq)
+                out_i[:, p * K:(p + 1) * K], out_d[:, p * K:(p + 1) * K] = pi, pd
+            return out_i, out_d
+        finally:
+            self.set_padding(was)
 
     # --- resident variant
     def upload_queries(self, q_rows):
