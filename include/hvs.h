@@ -598,6 +598,74 @@ int hvs_after_stats(hvs_ctx *ctx, hvs_after_info *out);
 void hvs_after_plan(const uint32_t *ids, const float *dists, uint32_t m, uint32_t k, float after_dist, uint32_t after_id, const uint32_t *pad_ids,
                     const float *pad_dists, int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_after);
 
+/* ---- category sets: the k nearest rows whose C is in a per-query set ------------------------------ */
+
+/*
+ * "The k nearest rows whose category is one of s_1 .. s_m": a category set is a list of f32 values attached to one resident
+ * query, given for all queries at once in CSR form -- set_offsets[nq + 1] (u32, ascending, set_offsets[0] == 0) and
+ * set_values[set_offsets[nq]].
+ *  - Types 1 and 3 with a non-empty set: the test `C == v` becomes "`C == s` for some s of the set"; the query's own v is
+ *    ignored, the T window of type 3 stays.  A value is read as the engines read v (reference optimized_parallel.hpp:93-96: an
+ *    int32 truncation, compared with C by IEEE ==): 5.9 names category 5, +0.0 and -0.0 one category; NaN and values outside
+ *    the int32 range match nothing and are dropped; values that name the same category count once.
+ *  - Any other query keeps its meaning: a query with an empty set, and a query of type 0, 2 or an invalid type whatever its set.
+ *  - Everything else is the query's usual contract with the wider predicate: sampled prefix, live-row mask, caps, cursors, both
+ *    distance orders, every k, the (dist asc, id asc) tie rule, padding from n-1, n-2, ... (or the last live ids) applied ONCE,
+ *    0xFFFFFFFF / +inf in unmatched slots with hvs_set_padding(ctx, 0).  Ids and distance bits are those of a plain type-1/3
+ *    query with v = v* on a copy of D in which every C of the set has been rewritten to a fresh value v*.  hvs_timing.pairs
+ *    counts the rows that pass the set predicate in the prefix.
+ *  - At most HVS_IN_MAX_VALUES distinct categories per query, and at most 2^32 - 1 sub-queries (below) in all: otherwise
+ *    HVS_EINVAL and nothing changes, as for nq != the number of resident queries and for malformed offsets.
+ * How: the index gives a query ONE position range of the (C,T) ordering, a set is a union of ranges.  So a query with m distinct
+ * values is answered as m ordinary SUB-QUERIES over the same D with padding off, and one kernel merges their top-k lists by
+ * key and pads once.  Rows of different categories are disjoint: the k smallest keys of the union of the lists are exactly
+ * the set predicate's top-k.  The engines see the expanded query set -- nsub x (416 + 8k) bytes of queries and results beside
+ * the user's -- and run exactly the kernels they run for plain queries.
+ * Lifetime: sets belong to the resident query set as caps and cursors do: hvs_upload_queries, hvs_gen_queries,
+ * hvs_set_queries_device, hvs_set_queries_from_rows and hvs_query remove them, and so does hvs_set_category_sets(ctx, NULL,
+ * NULL, 0) (a no-op while none are attached).  Attaching or removing sets drops earlier results (as hvs_set_k does) and
+ * removes caps and cursors: attach those afterwards, they stay one per USER query.  Every resident query index -- in
+ * hvs_query_resident, hvs_download_results, hvs_export_results_device, hvs_download_queries (which keeps returning the user's
+ * rows), hvs_set_max_dist2*, hvs_set_after* -- is the user's; hvs_set_after_from_results reads slot k-1 of the MERGED rows;
+ * hvs_reserve(nq) sizes for the sub-queries of the first nq queries; hvs_last_timing reports the user's nq and a query_ms that
+ * includes the merge; hvs_within_stats / hvs_after_stats follow the row-partitioned rules with "sub-query" for "part" (queries
+ * the call's, under-full the merge's, slots summed over the sub-lists).  Only hvs_last_reruns speaks of the EXPANDED set: its
+ * indices are sub-query indices.  hvs_query_resident resolves the sub-queries' filter re-runs before the merge is enqueued
+ * (one host synchronisation, as on a row-partitioned context).  While no sets are attached every call runs exactly the
+ * kernels, with exactly the arguments, it runs without these functions.
+ * One GPU and replicated multi-GPU contexts (each GPU takes its owner range's slice of the CSR); a row-partitioned context
+ * returns HVS_ESTATE, not supported (yet), and changes nothing; the D-sharded mode knows nothing of sets.  No data set loaded:
+ * HVS_ESTATE.  The CSR is HOST memory; the queries themselves may have come from anywhere (the library reads their types back).
+ *
+ * hvs_query_in: hvs_upload_queries + hvs_set_category_sets + hvs_query_resident + hvs_download_results in one call.  It is NOT
+ * the pipeline hvs_query is: the steps run one after the other.  Both set pointers NULL: exactly hvs_query.
+ * hvs_in_stats: figures of the last call (after hvs_sync); HVS_ESTATE where hvs_last_timing has none to report; all zero when
+ * the last call ran without sets.  Multi-GPU contexts: summed, max_set the largest, expand_ms / merge_ms the slowest GPU's.
+ * hvs_in_plan: the host arithmetic (no GPU, no context; any output may be NULL).  q_rows (nq x 104, NULL = every query of type
+ * 1) tells which queries test C.  A query without an effective set (empty set, or a type that does not test C) takes ONE
+ * sub-query, itself; any other takes one per distinct category, values ascending, or one with value NaN (matches nothing)
+ * when no value is left.  sub_offsets[nq + 1]; parent[nsub] and value[nsub]: sub-query j belongs to query parent[j] and
+ * carries value[j] (a query without an effective set: its own v where q_rows is given, NaN otherwise).  Returns nsub, or
+ * 0xFFFFFFFF (nothing written) for set_offsets[0] != 0, descending offsets, a set of more than HVS_IN_MAX_VALUES distinct
+ * categories, or more than 2^32 - 2 sub-queries.
+ */
+#define HVS_IN_MAX_VALUES 64
+typedef struct hvs_in_info {
+    uint32_t set_queries;       /* queries of the last call that were answered through their set             */
+    uint32_t sub_queries;       /* sub-queries the engines answered for the call's queries                   */
+    uint32_t max_set;           /* most sub-queries of one query of the call                                 */
+    uint32_t underfull_queries; /* queries with fewer than k keys in all their sub-lists together            */
+    uint64_t merged_keys;       /* non-empty slots of the sub-lists the merge read                           */
+    double   expand_ms;         /* device time of the expansion when the sets were attached                  */
+    double   merge_ms;          /* device time of the call's merge kernel                                    */
+} hvs_in_info;
+int hvs_set_category_sets(hvs_ctx *ctx, const uint32_t *set_offsets /* host, nq+1 */, const float *set_values /* host */, uint32_t nq);
+int hvs_query_in(hvs_ctx *ctx, const float *q_rows, const uint32_t *set_offsets, const float *set_values, uint32_t nq,
+                 float sample_proportion, uint32_t *out_ids, float *out_dists);
+int hvs_in_stats(hvs_ctx *ctx, hvs_in_info *out);
+uint32_t hvs_in_plan(const float *q_rows /* nq x 104, may be NULL = all type 1 */, const uint32_t *set_offsets, const float *set_values, uint32_t nq,
+                     uint32_t *sub_offsets /* nq+1 */, uint32_t *parent, float *value /* NaN-free but for "matches nothing"; both may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,45 @@ struct HvsPart {
 };
 constexpr uint32_t kPartTailRows = HVS_KMAX;  // rows of the tail replica: the most a query can be padded with
 
+// Category sets of one GPU's resident queries (hvs_set_category_sets).  While `active`, the engines' resident set
+// (hvs_ctx::d_q, nq, d_out_*, d_max_d2, d_after_*) is the EXPANDED one -- `nq` sub-queries -- and this struct holds the user's
+// side of it: the user's `nuq` query rows, the plan that ties a user query to its sub-queries [h_sub_off[p], h_sub_off[p + 1]),
+// the user's caps and cursors (one per user query; gathered into the engines' arrays by hvs_k_expand_per_query) and the merged
+// result rows.  Every resident index of the C ABI is a user index; in_* functions below translate.  Not active: nothing here is
+// read, and the buffers are kept for the next attach.
+struct HvsInSet {
+    bool active = false;
+    uint32_t nuq = 0;
+    std::vector<uint32_t> h_sub_off;   // nuq + 1
+    std::vector<uint8_t> h_eff;        // nuq: the query is answered through its set (tests C, non-empty set)
+    float* d_uq = nullptr;             // the user's rows, nuq x 104
+    uint32_t *d_sub_off = nullptr, *d_set_off = nullptr, *d_parent = nullptr;  // nuq + 1, nuq + 1 (the caller's CSR offsets), nsub
+    float* d_value = nullptr;          // nsub
+    uint32_t uq_cap = 0, sub_cap = 0;  // user queries / sub-queries the buffers above have room for
+    float* d_caps = nullptr;           // the user's caps (normalised), cursors (raw pair and normalised key): nuq each
+    uint64_t* d_after_lo = nullptr;
+    float* d_after_dist = nullptr;
+    uint32_t* d_after_id = nullptr;
+    uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
+    float* d_m_dists = nullptr;
+    size_t m_cap = 0;                  // entries
+    unsigned long long* d_stat = nullptr;  // [0] under-full queries, [1] keys read: of the last merge
+    hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;  // around the expansion / the last merge
+    double expand_ms = 0.0;
+    // last call
+    bool call = false;                 // it ran under sets
+    uint32_t call_set_queries = 0, call_sub = 0, call_max_set = 0;
+    void free_device()
+    {
+        HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_caps, d_after_lo, d_after_dist, d_after_id, d_m_ids, d_m_dists, d_stat);
+        for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
+            if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
+        uq_cap = sub_cap = 0;
+        m_cap = 0;
+        active = false;
+    }
+};
+
 #define HVS_NCOUNTERS 20  // ([14], [15]: hvs_keep_within; [16] .. [18]: hvs_keep_after)
 struct hvs_ctx : HvsLane {
     int device = 0;
@@ -244,6 +283,7 @@ struct hvs_ctx : HvsLane {
     uint32_t* d_out_ids = nullptr;
     float* d_out_dists = nullptr;
     uint32_t res_cap = 0;
+    HvsInSet in;  // category sets of the resident queries (while in.active, everything above is the expanded set)
 
     unsigned long long* d_counters = nullptr;  // HVS_NCOUNTERS of them, zeroed at the start of every call
 
@@ -337,6 +377,11 @@ bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empt
 bool capped(const hvs_ctx* c) { return c->caps_set; }
 // ... carry result cursors: the AFTER kernels run (with_capped_after)
 bool has_after(const hvs_ctx* c) { return c->after_set; }
+// the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
+uint32_t user_nq(const hvs_ctx* c) { return c->in.active ? c->in.nuq : c->nq; }
+const float* user_queries(const hvs_ctx* c) { return c->in.active ? c->in.d_uq : c->d_q; }
+const uint32_t* user_ids(const hvs_ctx* c) { return c->in.active ? c->in.d_m_ids : c->d_out_ids; }
+const float* user_dists(const hvs_ctx* c) { return c->in.active ? c->in.d_m_dists : c->d_out_dists; }
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
 uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
 uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
@@ -1929,6 +1974,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
     c->timing_valid = false;
     c->call_capped = capped(c);
     c->call_after = has_after(c);
+    c->in.call = false;  // (in_run sets it once the merge is enqueued)
     // (the results the resident set has: this call's range joins the ranges answered so far if it touches them)
     if (c->res_k != c->k || c->res_lo >= c->res_hi || q0 > c->res_hi || q0 + nq < c->res_lo) {
         c->res_lo = q0;
@@ -2127,6 +2173,7 @@ void leaf_destroy(hvs_ctx* c)
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->rs.free_device();
+    c->in.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     {
         HvsPart& P = c->part;
@@ -2165,6 +2212,10 @@ int ensure_staging(hvs_ctx* c, bool dists, uint64_t nq_in, uint64_t nq_out);
 int leaf_reserve(hvs_ctx* c, uint32_t nq)
 {
     HVS_HIP(c, hipSetDevice(c->device));
+    if (c->in.active) {  // category sets: the engines answer the sub-queries of the first nq queries (one each beyond the resident ones)
+        const uint32_t in_set = std::min(nq, c->in.nuq);
+        nq = (uint32_t)std::min<uint64_t>((uint64_t)c->in.h_sub_off[in_set] + (nq - in_set), 0xFFFFFFFFull);
+    }
     c->reserve_nq = std::max(c->reserve_nq, nq);
     if (nq == 0u) return HVS_OK;
     int rc = ensure_queries(c, nq);
@@ -2581,6 +2632,7 @@ int leaf_begin_queries(hvs_ctx* c, uint32_t nq)
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = 0;
+    c->in.active = false;  // (category sets belong to a resident set too: the engines' set is the user's again)
     c->caps_set = false;  // (caps belong to a resident set: every call that replaces the set removes them)
     c->after_set = false;  // (and cursors)
     c->res_lo = c->res_hi = 0;
@@ -2601,12 +2653,18 @@ int leaf_set_caps(hvs_ctx* c, const float* src, int src_dev, uint32_t count)
         return HVS_OK;
     }
     if (count) {
+        float* dst = c->in.active ? c->in.d_caps : c->d_max_d2;  // (under category sets: the user's caps, one per user query)
         if (src_dev < 0)
-            HVS_HIP(c, hipMemcpyAsync(c->d_max_d2, src, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        else if ((rc = copy_from_device(c, c->d_max_d2, src, src_dev, (size_t)count * sizeof(float))))
+            HVS_HIP(c, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else if ((rc = copy_from_device(c, dst, src, src_dev, (size_t)count * sizeof(float))))
             return rc;
-        hipLaunchKernelGGL(hvs_k_norm_caps, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, c->d_max_d2, count);
+        hipLaunchKernelGGL(hvs_k_norm_caps, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, dst, count);
         HVS_HIP(c, hipGetLastError());
+        if (c->in.active) {  // ... and every sub-query takes its parent's
+            hipLaunchKernelGGL(hvs_k_expand_per_query, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, c->in.d_parent, c->nq, dst, c->d_max_d2,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            HVS_HIP(c, hipGetLastError());
+        }
     }
     HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the buffer is the caller's again)
     c->caps_set = true;
@@ -2630,7 +2688,15 @@ int ensure_after(hvs_ctx* c, uint32_t nq)
 // the raw cursors in d_after_dist / d_after_id become the resident queries' cursors; `row0`: the part's first global row
 int leaf_commit_after(hvs_ctx* c, uint32_t count, uint32_t row0)
 {
-    if (count) {
+    if (count && c->in.active) {
+        // under category sets the raw cursors are the user's (HvsInSet): normalised there, then every sub-query takes its parent's
+        const HvsInSet& S = c->in;
+        hipLaunchKernelGGL(hvs_k_norm_after, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, S.d_after_dist, S.d_after_id, count, row0,
+                           S.d_after_lo);
+        hipLaunchKernelGGL(hvs_k_expand_per_query, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, S.d_parent, c->nq, nullptr, nullptr,
+                           S.d_after_lo, S.d_after_dist, S.d_after_id, c->d_after_lo, c->d_after_dist, c->d_after_id);
+        HVS_HIP(c, hipGetLastError());
+    } else if (count) {
         hipLaunchKernelGGL(hvs_k_norm_after, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, c->d_after_dist, c->d_after_id, count, row0,
                            c->d_after_lo);
         HVS_HIP(c, hipGetLastError());
@@ -2653,13 +2719,15 @@ int leaf_set_after(hvs_ctx* c, const float* dists, const uint32_t* ids, int src_
         c->after_set = false;
         return HVS_OK;
     }
-    if ((rc = ensure_after(c, std::max(count, 1u)))) return rc;
+    if ((rc = ensure_after(c, std::max(std::max(count, c->in.active ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
     if (count) {
+        float* dd = c->in.active ? c->in.d_after_dist : c->d_after_dist;
+        uint32_t* di = c->in.active ? c->in.d_after_id : c->d_after_id;
         if (src_dev < 0) {
-            HVS_HIP(c, hipMemcpyAsync(c->d_after_dist, dists, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            HVS_HIP(c, hipMemcpyAsync(c->d_after_id, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        } else if ((rc = copy_from_device(c, c->d_after_dist, dists, src_dev, (size_t)count * sizeof(float))) ||
-                   (rc = copy_from_device(c, c->d_after_id, ids, src_dev, (size_t)count * sizeof(uint32_t)))) {
+            HVS_HIP(c, hipMemcpyAsync(dd, dists, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+            HVS_HIP(c, hipMemcpyAsync(di, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        } else if ((rc = copy_from_device(c, dd, dists, src_dev, (size_t)count * sizeof(float))) ||
+                   (rc = copy_from_device(c, di, ids, src_dev, (size_t)count * sizeof(uint32_t)))) {
             return rc;
         }
     }
@@ -2674,6 +2742,15 @@ int leaf_after_from_results(hvs_ctx* c)
     int rc = resolve_overflow(c);  // (the last slots of re-run queries too)
     if (rc) return rc;
     if ((rc = ensure_after(c, std::max(c->nq, 1u)))) return rc;
+    if (c->in.active) {  // category sets: slot k-1 of the MERGED rows, one cursor per user query
+        const HvsInSet& S = c->in;
+        if (S.nuq) {
+            hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(S.nuq, 256u)), dim3(256), 0, c->stream, S.d_m_ids, S.d_m_dists, S.nuq, c->k,
+                               S.d_after_dist, S.d_after_id);
+            HVS_HIP(c, hipGetLastError());
+        }
+        return leaf_commit_after(c, S.nuq, 0u);
+    }
     if (c->nq) {
         hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, c->d_out_ids, c->d_out_dists, c->nq,
                            c->k, c->d_after_dist, c->d_after_id);
@@ -2755,15 +2832,259 @@ int leaf_sync(hvs_ctx* c)
 
 int leaf_download_results(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* out_ids, float* out_dists)
 {
-    if (!out_ids || (uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "hvs_download_results: bad range");
+    if (!out_ids || (uint64_t)q0 + nq > user_nq(c)) return fail(c, HVS_EINVAL, "hvs_download_results: bad range");
     int rc = leaf_sync(c);
     if (rc) return rc;
-    HVS_HIP(c, hipMemcpyAsync(out_ids, c->d_out_ids + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
+    if (c->in.active && c->in.m_cap < (size_t)c->in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_download_results: no results (hvs_query_resident has not run)");
+    HVS_HIP(c, hipMemcpyAsync(out_ids, user_ids(c) + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
                               hipMemcpyDeviceToHost, c->stream));
     if (out_dists)
-        HVS_HIP(c, hipMemcpyAsync(out_dists, c->d_out_dists + (size_t)q0 * c->k,
+        HVS_HIP(c, hipMemcpyAsync(out_dists, user_dists(c) + (size_t)q0 * c->k,
                                   (size_t)nq * c->k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return HVS_OK;
+}
+
+// ---- category sets (include/hvs.h "category sets"): the user's side of an expanded resident set ----
+
+// hvs_in_plan's arithmetic; `types`: the queries' type floats, `stride` floats apart (nullptr: every query tests C), `own_v`
+// likewise their own v (nullptr: none known).  A value names the category the engines would read from it (hvs_parse_query).
+uint32_t in_plan_core(const float* types, const float* own_v, size_t stride, const uint32_t* off, const float* vals, uint32_t nq, uint32_t* sub_off,
+                      uint32_t* parent, float* value, uint8_t* eff)
+{
+    if (nq && !off) return 0xFFFFFFFFu;
+    if (nq && off[0] != 0u) return 0xFFFFFFFFu;
+    for (uint32_t p = 0; p < nq; ++p)
+        if (off[p + 1] < off[p]) return 0xFFFFFFFFu;
+    if (nq && off[nq] && !vals) return 0xFFFFFFFFu;
+    const float nan = __builtin_nanf("");
+    // two passes: nothing is written unless the whole plan is good
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t nsub = 0;
+        std::vector<float> cat;
+        for (uint32_t p = 0; p < nq; ++p) {
+            const bool has_c = !types || hvs_in_type_has_c(types[(size_t)p * stride]);
+            const bool effective = has_c && off[p + 1] > off[p];
+            cat.clear();
+            for (uint32_t i = off[p]; i < off[p + 1]; ++i) {
+                const float s = vals[i];
+                if (s >= -2147483648.0f && s < 2147483648.0f) cat.push_back((float)(int32_t)s);  // (NaN fails both compares)
+            }
+            std::sort(cat.begin(), cat.end());
+            cat.erase(std::unique(cat.begin(), cat.end()), cat.end());
+            // (the limit is the set's own: it holds whatever the query's type)
+            if (cat.size() > HVS_IN_MAX_VALUES) return 0xFFFFFFFFu;
+            const uint32_t m = effective ? std::max<uint32_t>((uint32_t)cat.size(), 1u) : 1u;
+            if (pass) {
+                if (sub_off) sub_off[p] = (uint32_t)nsub;
+                if (eff) eff[p] = effective ? 1u : 0u;
+                for (uint32_t j = 0; j < m; ++j) {
+                    if (parent) parent[nsub + j] = p;
+                    if (value) value[nsub + j] = effective ? (cat.empty() ? nan : cat[j]) : (own_v ? own_v[(size_t)p * stride] : nan);
+                }
+            }
+            nsub += m;
+        }
+        if (nsub >= 0xFFFFFFFFull) return 0xFFFFFFFFu;
+        if (pass) {
+            if (sub_off) sub_off[nq] = (uint32_t)nsub;
+            return (uint32_t)nsub;
+        }
+    }
+    return 0u;
+}
+
+int in_ensure_events(hvs_ctx* c)
+{
+    for (hipEvent_t* ev : {&c->in.ev_x0, &c->in.ev_x1, &c->in.ev_m0, &c->in.ev_m1})
+        if (!*ev) HVS_HIP(c, hipEventCreate(ev));
+    return HVS_OK;
+}
+
+// hvs_set_category_sets(NULL, NULL, 0) on one GPU: the resident set becomes the user's again (a no-op while no sets are attached)
+int in_detach(hvs_ctx* c)
+{
+    HvsInSet& S = c->in;
+    if (!S.active) return HVS_OK;
+    int rc = begin_mutation(c);
+    if (rc) return rc;
+    if (S.nuq) HVS_HIP(c, hipMemcpyAsync(c->d_q, S.d_uq, (size_t)S.nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->nq = S.nuq;  // (nq_cap >= the sub-queries >= the user's queries)
+    S.active = false;
+    c->caps_set = c->after_set = false;
+    c->res_lo = c->res_hi = 0;
+    c->timing_valid = false;
+    return HVS_OK;
+}
+
+// hvs_set_category_sets on one GPU: `off` = the caller's offsets of this GPU's `nuq` resident queries (off[0] need not be 0:
+// a slice of a multi-GPU context's CSR), `vals` the whole value array; validated by the caller (format, limits, nuq = the
+// resident queries).  The user's rows move aside (they may have come from device memory: their types are read back), the
+// plan is made, the engines' set becomes the expanded one.  A failure half-way (no room) leaves the context without sets, and
+// without resident queries if the query buffer itself could not grow.  On a replicated context the root then detaches every
+// other GPU too (hvs_set_category_sets): sets are attached on all GPUs or on none.
+int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
+{
+    HvsInSet& S = c->in;
+    int rc = begin_mutation(c);
+    if (!rc) rc = in_ensure_events(c);
+    if (rc) return rc;
+    if (!S.d_stat && (rc = dev_alloc(c, &S.d_stat, (size_t)2))) return rc;
+    // the user's rows: already aside when sets are replaced
+    if (!S.active) {
+        if (!S.d_sub_off || nuq > S.uq_cap) {
+            S.uq_cap = 0;
+            if ((rc = dev_alloc(c, &S.d_uq, (size_t)nuq * HVS_QCOLS)) || (rc = dev_alloc(c, &S.d_sub_off, (size_t)nuq + 1u)) ||
+                (rc = dev_alloc(c, &S.d_set_off, (size_t)nuq + 1u)) || (rc = dev_alloc(c, &S.d_caps, (size_t)nuq)) ||
+                (rc = dev_alloc(c, &S.d_after_lo, (size_t)nuq)) || (rc = dev_alloc(c, &S.d_after_dist, (size_t)nuq)) ||
+                (rc = dev_alloc(c, &S.d_after_id, (size_t)nuq)))
+                return rc;
+            S.uq_cap = nuq;
+        }
+        HVS_HIP(c, hipMemcpyAsync(S.d_uq, c->d_q, (size_t)nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HVS_HIP(c, hipStreamSynchronize(c->stream));
+        S.nuq = nuq;
+    }
+    std::vector<float> tv(2u * (size_t)nuq);  // [type, v] of every user query
+    if (nuq)
+        HVS_HIP(c, hipMemcpy2D(tv.data(), 2u * sizeof(float), S.d_uq, HVS_QCOLS * sizeof(float), 2u * sizeof(float), nuq, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> set_off((size_t)nuq + 1u);
+    for (uint32_t p = 0; p <= nuq; ++p) set_off[p] = off[p] - off[0];
+    const float* v0 = vals ? vals + off[0] : nullptr;
+    std::vector<uint32_t> sub_off((size_t)nuq + 1u);
+    std::vector<uint8_t> eff(nuq);
+    const uint32_t nsub = in_plan_core(tv.data(), tv.data() + 1, 2u, set_off.data(), v0, nuq, sub_off.data(), nullptr, nullptr, eff.data());
+    if (nsub == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed sets");
+    std::vector<uint32_t> parent(nsub);
+    std::vector<float> value(nsub);
+    (void)in_plan_core(tv.data(), tv.data() + 1, 2u, set_off.data(), v0, nuq, nullptr, parent.data(), value.data(), nullptr);
+    // from here on the context changes
+    auto lost = [&](int code) {
+        S.active = false;
+        c->caps_set = c->after_set = false;
+        c->res_lo = c->res_hi = 0;
+        c->timing_valid = false;
+        if (c->nq_cap < nuq) c->nq = 0;
+        else if (hipMemcpy(c->d_q, S.d_uq, (size_t)nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess) c->nq = nuq;
+        else c->nq = 0;
+        return code;
+    };
+    if (nsub > S.sub_cap) {
+        S.sub_cap = 0;
+        if ((rc = dev_alloc(c, &S.d_parent, (size_t)nsub)) || (rc = dev_alloc(c, &S.d_value, (size_t)nsub))) return lost(rc);
+        S.sub_cap = nsub;
+    }
+    if ((rc = ensure_queries(c, nsub))) return lost(rc);
+    if (c->after_cap && c->after_cap < nsub) c->after_cap = 0;  // (ensure_after re-allocates for the sub-queries when cursors come)
+    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    if (up(S.d_sub_off, sub_off.data(), sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_set_off, set_off.data(), set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_parent, parent.data(), parent.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_value, value.data(), value.size() * sizeof(float)) != hipSuccess)
+        return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
+    (void)hipEventRecord(S.ev_x0, c->stream);
+    if (nsub) {
+        const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
+        hipLaunchKernelGGL(hvs_k_expand_in, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq),
+                           S.d_parent, S.d_value, S.d_set_off, nsub, reinterpret_cast<float4*>(c->d_q));
+    }
+    (void)hipEventRecord(S.ev_x1, c->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)  // (the host arrays go with this scope)
+        return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: the expansion failed"));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
+    S.expand_ms = ms;
+    S.h_sub_off.swap(sub_off);
+    S.h_eff.swap(eff);
+    S.active = true;
+    c->nq = nsub;
+    c->caps_set = c->after_set = false;  // (caps and cursors are attached after the sets; earlier results are dropped)
+    c->res_lo = c->res_hi = 0;
+    c->timing_valid = false;
+    return HVS_OK;
+}
+
+// hvs_query_resident under category sets: user queries [q0, q0 + nq) = sub-queries [sub_off[q0], sub_off[q0 + nq)), answered by
+// the engines with padding off FOR THIS CALL (the user's setting is the merge's), their re-runs resolved (the call's one host
+// synchronisation, as part_run has), then one merge launch into the merged rows q0 .. q0 + nq.
+int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
+{
+    HvsInSet& S = c->in;
+    if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
+    if ((uint64_t)q0 + nq > S.nuq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
+    HVS_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if (nq == 0u) return run_queries(c, S.h_sub_off[q0], 0u, sample_proportion, NoHook{});  // (nothing to merge)
+    if (S.m_cap < (size_t)S.nuq * c->k) {
+        S.m_cap = 0;
+        if ((rc = dev_alloc(c, &S.d_m_ids, (size_t)S.nuq * c->k)) || (rc = dev_alloc(c, &S.d_m_dists, (size_t)S.nuq * c->k))) return rc;
+        S.m_cap = (size_t)S.nuq * c->k;
+    }
+    const uint32_t s0 = S.h_sub_off[q0], s1 = S.h_sub_off[q0 + nq];
+    {
+        struct PaddingOff {  // a per-call override: the sub-queries' lists are partial answers
+            hvs_ctx* c;
+            bool was;
+            ~PaddingOff() { c->padding = was; }
+        } off{c, c->padding};
+        c->padding = false;
+        if ((rc = run_queries(c, s0, s1 - s0, sample_proportion, NoHook{}))) return rc;
+        if ((rc = resolve_overflow(c))) return rc;
+    }
+    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipEventRecord(S.ev_m0, c->stream));
+    if (nq) {
+        with_cap(c->cap, [&](auto CAPT) {
+            auto launch = [&](auto ST) {
+                hipLaunchKernelGGL((hvs_k_merge_in<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream, S.d_sub_off,
+                                   q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, S.d_uq, c->padding ? 1 : 0,
+                                   masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
+            };
+            if (c->scalar_order)
+                launch(std::true_type{});
+            else
+                launch(std::false_type{});
+        });
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipEventRecord(S.ev_m1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));  // (the merge belongs to the call's device time)
+    c->timing.nq = nq;  // (the user's)
+    S.call = true;
+    S.call_sub = s1 - s0;
+    S.call_set_queries = S.call_max_set = 0;
+    for (uint32_t p = q0; p < q0 + nq; ++p) {
+        S.call_set_queries += S.h_eff[p];
+        S.call_max_set = std::max(S.call_max_set, S.h_sub_off[p + 1] - S.h_sub_off[p]);
+    }
+    return HVS_OK;
+}
+
+int leaf_run_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
+{
+    return c->in.active ? in_run(c, q0, nq, sample_proportion) : run_queries(c, q0, nq, sample_proportion, NoHook{});
+}
+
+int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
+{
+    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = hvs_in_info{};
+    const HvsInSet& S = c->in;
+    if (!S.call) return HVS_OK;
+    unsigned long long v[2] = {0, 0};
+    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HVS_HIP(c, hipEventElapsedTime(&ms, S.ev_m0, S.ev_m1));
+    out->set_queries = S.call_set_queries;
+    out->sub_queries = S.call_sub;
+    out->max_set = S.call_max_set;
+    out->underfull_queries = (uint32_t)v[0];
+    out->merged_keys = v[1];
+    out->expand_ms = S.expand_ms;
+    out->merge_ms = ms;
     return HVS_OK;
 }
 
@@ -4011,6 +4332,7 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
     // result rows change size: resident queries stay, their results do not; list workspaces are re-sized on demand
     const uint32_t had = c->res_cap;
     c->res_cap = 0;
+    c->in.m_cap = 0;  // (the merged rows of category sets likewise: re-allocated by the next call)
     c->cand_lists = 0;
     c->timing_valid = false;
     c->rs.cut_valid = false;
@@ -4230,9 +4552,9 @@ int hvs_download_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float* out_rows)
         return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t off) {
             return hvs_download_queries(k, lq0, m, out_rows + (size_t)off * HVS_QCOLS);
         });
-    if (!out_rows || (uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "hvs_download_queries: bad range");
+    if (!out_rows || (uint64_t)q0 + nq > user_nq(c)) return fail(c, HVS_EINVAL, "hvs_download_queries: bad range");
     HVS_HIP(c, hipSetDevice(c->device));
-    HVS_HIP(c, hipMemcpyAsync(out_rows, c->d_q + (size_t)q0 * HVS_QCOLS, (size_t)nq * HVS_QCOLS * sizeof(float),
+    HVS_HIP(c, hipMemcpyAsync(out_rows, user_queries(c) + (size_t)q0 * HVS_QCOLS, (size_t)nq * HVS_QCOLS * sizeof(float),
                               hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return HVS_OK;
@@ -4244,9 +4566,9 @@ int hvs_query_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_propor
     if (c->partitioned) return part_run(c, q0, nq, sample_proportion);
     if (!c->kids.empty())
         return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t) {
-            return run_queries(k, lq0, m, sample_proportion, NoHook{});
+            return leaf_run_resident(k, lq0, m, sample_proportion);
         });
-    return run_queries(c, q0, nq, sample_proportion, NoHook{});
+    return leaf_run_resident(c, q0, nq, sample_proportion);
 }
 
 int hvs_sync(hvs_ctx* c)
@@ -4273,14 +4595,15 @@ int hvs_export_results_device(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* d_
 {
     if (!c) return HVS_EINVAL;
     if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_export_results_device: single-GPU contexts only (device pointers belong to one GPU)");
-    if (!d_ids || (uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "hvs_export_results_device: bad range");
+    if (!d_ids || (uint64_t)q0 + nq > user_nq(c)) return fail(c, HVS_EINVAL, "hvs_export_results_device: bad range");
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
     if (rc) return rc;
-    HVS_HIP(c, hipMemcpyAsync(d_ids, c->d_out_ids + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
+    if (c->in.active && c->in.m_cap < (size_t)c->in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_export_results_device: no results (hvs_query_resident has not run)");
+    HVS_HIP(c, hipMemcpyAsync(d_ids, user_ids(c) + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, c->stream));
     if (d_dists)
-        HVS_HIP(c, hipMemcpyAsync(d_dists, c->d_out_dists + (size_t)q0 * c->k,
+        HVS_HIP(c, hipMemcpyAsync(d_dists, user_dists(c) + (size_t)q0 * c->k,
                                   (size_t)nq * c->k * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return HVS_OK;
 }
@@ -4471,7 +4794,7 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
 // resident queries of the whole context
 static uint32_t resident_count(const hvs_ctx* c)
 {
-    if (c->kids.empty()) return c->nq;
+    if (c->kids.empty()) return user_nq(c);
     return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
 }
 // caps (host memory: src_dev < 0; device memory of GPU src_dev otherwise) to every leaf: its range of them, or, on a
@@ -4520,6 +4843,11 @@ static int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
     out->capped_queries = c->timing.nq;
     out->within_slots = v[0];
     out->underfull_queries = (uint32_t)v[1];
+    if (c->in.call) {  // category sets: the slots are the sub-lists', a query is under-full when the merge found fewer than k keys
+        hvs_in_info I{};
+        if ((rc = leaf_in_stats(c, &I))) return rc;
+        out->underfull_queries = I.underfull_queries;
+    }
     return HVS_OK;
 }
 
@@ -4702,6 +5030,11 @@ static int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
     out->after_slots = v[0];
     out->underfull_queries = (uint32_t)v[1];
     out->exhausted_queries = (uint32_t)v[2];
+    if (c->in.call) {  // category sets, by the rules of leaf_within_stats (exhausted cursors are counted per sub-query, as the slots are)
+        hvs_in_info I{};
+        if ((rc = leaf_in_stats(c, &I))) return rc;
+        out->underfull_queries = I.underfull_queries;
+    }
     return HVS_OK;
 }
 
@@ -4777,6 +5110,86 @@ void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_
         if (out_ids) out_ids[j] = row[j].id;
         if (out_dists) out_dists[j] = row[j].dist;
     }
+}
+
+// ---- category sets (include/hvs.h "category sets") -------------------------------
+
+uint32_t hvs_in_plan(const float* q_rows, const uint32_t* set_offsets, const float* set_values, uint32_t nq, uint32_t* sub_offsets, uint32_t* parent,
+                     float* value)
+{
+    return in_plan_core(q_rows, q_rows ? q_rows + 1 : nullptr, HVS_QCOLS, set_offsets, set_values, nq, sub_offsets, parent, value, nullptr);
+}
+
+int hvs_set_category_sets(hvs_ctx* c, const uint32_t* set_offsets, const float* set_values, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets: not supported (yet) on a row-partitioned context");
+    if (!set_offsets && !set_values) return on_every_leaf(c, in_detach);
+    if (!loaded_leaf(c, "hvs_set_category_sets")) return HVS_ESTATE;
+    if (!set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets: set_offsets is NULL");
+    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_category_sets: nq is not the number of resident queries");
+    if (nq == 0u) return on_every_leaf(c, in_detach);
+    // format and limits hold whatever the queries' types; the sub-query count is the largest when every query tests C
+    if (hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
+        return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
+    if (c->kids.empty()) return in_attach(c, set_offsets, set_values, nq);
+    const int rc = for_each_leaf(c, [&](uint32_t r) {  // owner ranges stay cut by user queries: each GPU takes its slice of the CSR
+        return in_attach(c->kids[r], set_offsets + c->kid_q0[r], set_values, c->kid_q0[r + 1] - c->kid_q0[r]);
+    });
+    if (rc) {
+        // one GPU could not attach (no room): no GPU stays under sets -- the context answers plain queries on every GPU whose
+        // query buffer survived (in_attach), and the failing GPU's error is the call's
+        const std::string err = c->err;
+        for (hvs_ctx* k : c->kids) (void)in_detach(k);
+        (void)hipGetLastError();
+        c->err = err;
+    }
+    return rc;
+}
+
+int hvs_query_in(hvs_ctx* c, const float* q_rows, const uint32_t* set_offsets, const float* set_values, uint32_t nq, float sample_proportion,
+                 uint32_t* out_ids, float* out_dists)
+{
+    if (!c) return HVS_EINVAL;
+    if (!set_offsets && !set_values) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_in: not supported (yet) on a row-partitioned context");
+    if (!loaded_leaf(c, "hvs_query_in")) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_in: q_rows / out_ids is NULL");
+    // checked before the resident set is replaced: a refused call changes nothing
+    if (!set_offsets || hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
+        return fail(c, HVS_EINVAL, "hvs_query_in: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc) rc = hvs_set_category_sets(c, set_offsets, set_values, nq);
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+
+int hvs_in_stats(hvs_ctx* c, hvs_in_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_in_stats(c, out);
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_in_stats: not supported (yet) on a row-partitioned context");
+    hvs_in_info agg{};
+    bool any = false;
+    for (hvs_ctx* k : c->kids) {
+        if (!k->timing_valid) continue;  // (took no part in the last call)
+        hvs_in_info m{};
+        const int rc = leaf_in_stats(k, &m);
+        if (rc) return fail(c, rc, k->err);
+        agg.set_queries += m.set_queries;
+        agg.sub_queries += m.sub_queries;
+        agg.max_set = std::max(agg.max_set, m.max_set);
+        agg.underfull_queries += m.underfull_queries;
+        agg.merged_keys += m.merged_keys;
+        agg.expand_ms = std::max(agg.expand_ms, m.expand_ms);
+        agg.merge_ms = std::max(agg.merge_ms, m.merge_ms);
+        any = true;
+    }
+    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
+    *out = agg;
+    return HVS_OK;
 }
 
 // ---- live-row mask ---------------------------------------------------------------------------

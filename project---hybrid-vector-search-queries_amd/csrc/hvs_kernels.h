@@ -776,3 +776,119 @@ __global__ __launch_bounds__(256) void hvs_k_merge_parts(HvsPartLists parts, uin
         if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Category sets (hvs_set_category_sets / hvs_query_in): a query of type 1 or 3 whose predicate reads "C is one of
+// s_1 .. s_m" is answered as m ordinary SUB-QUERIES over the same D, one per distinct value, with padding off; rows of different
+// categories are disjoint, so the k smallest keys of the union of the sub-queries' top-k lists are the set predicate's top-k.
+// The engines see the expanded query set and know nothing of sets.  Host arrays (hvs_in_plan): sub_off[nq + 1] -- user query p
+// owns sub-queries [sub_off[p], sub_off[p + 1]) (at least one) --, parent[nsub], value[nsub].
+// ---------------------------------------------------------------------------------------------
+// the engines' reading of a query's type float (hvs_parse_query): does it test C at all?
+__host__ __device__ __forceinline__ bool hvs_in_type_has_c(float t)
+{
+    if (!(t > -1.0f && t < 4.0f)) return false;
+    const uint32_t type = (uint32_t)(int32_t)t;
+    return type == 1u || type == 3u;
+}
+
+// Sub-query j = the 104 floats of user query parent[j], bit for bit, with float 1 (v) replaced by value[j] -- only where the
+// parent tests C (type 1 or 3) and carries a non-empty set (set_off[p + 1] > set_off[p], the caller's CSR offsets); every
+// other parent has one sub-query, itself.  One thread per float4 of a row (26 of them), consecutive threads consecutive float4s.
+__global__ __launch_bounds__(256) void hvs_k_expand_in(const float4* __restrict__ Qu, const uint32_t* __restrict__ parent, const float* __restrict__ value,
+                                                      const uint32_t* __restrict__ set_off, uint32_t nsub, float4* __restrict__ Qx)
+{
+    static_assert(HVS_QCOLS % 4u == 0u, "query rows are moved in 16-byte pieces");
+    constexpr uint32_t P = HVS_QCOLS / 4u;
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (uint64_t)nsub * P) return;
+    const uint32_t j = (uint32_t)(e / P), c = (uint32_t)(e - (uint64_t)j * P);
+    const uint32_t p = parent[j];
+    float4 v = Qu[(size_t)p * P + c];
+    if (c == 0u && hvs_in_type_has_c(v.x) && set_off[p + 1u] > set_off[p]) v.y = value[j];
+    Qx[e] = v;
+}
+
+// Caps and cursors stay one per USER query: sub-query j takes its parent's (the normalised forms hvs_k_norm_caps /
+// hvs_k_norm_after leave).  A null input skips its output.
+__global__ __launch_bounds__(256) void hvs_k_expand_per_query(const uint32_t* __restrict__ parent, uint32_t nsub, const float* __restrict__ caps_in, float* __restrict__ caps_out,
+                                       const uint64_t* __restrict__ lo_in, const float* __restrict__ dist_in, const uint32_t* __restrict__ id_in,
+                                       uint64_t* __restrict__ lo_out, float* __restrict__ dist_out, uint32_t* __restrict__ id_out)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nsub) return;
+    const uint32_t p = parent[j];
+    if (caps_in) caps_out[j] = caps_in[p];
+    if (lo_in) {
+        lo_out[j] = lo_in[p];
+        dist_out[j] = dist_in[p];
+        id_out[j] = id_in[p];
+    }
+}
+
+// hvs_k_merge_in -- per user query (one wave, four per workgroup): the result rows of its sub-queries, rows [sub_off[q],
+// sub_off[q + 1]) x knn of the engines' own result buffer (padding off: 0xFFFFFFFF = empty slot, ids global), are streamed
+// through the wave's key buffer (hvs_gather_list_keys cuts it back to the knn smallest whenever the next 64 slots might not
+// fit: that is how 64 lists pass through 256 / 512 keys) and reduced to the knn smallest keys.  The keys are distinct: the
+// sub-queries' categories are (hvs_in_plan de-duplicates).  Caps and cursors were applied by the sub-queries.  Padding as
+// hvs_k_select does it on one GPU: slot cnt + s takes row n - 1 - s, or pad_ids[s] (the last live ids) where pad_ids is not
+// null, with the distance computed here from D by the engines' own exact-order function; pad == 0 leaves the largest key.
+// stat[0] += 1 for an under-full query, stat[1] += keys gathered.  Queries [q0, q0 + nq) of the user's set; Q: the user's rows.
+template <bool SCALAR_ORDER, int CAP>
+__global__ __launch_bounds__(256) void hvs_k_merge_in(const uint32_t* __restrict__ sub_off, uint32_t q0, uint32_t nq, const uint32_t* __restrict__ sub_ids,
+                                                      const float* __restrict__ sub_dists, const float* __restrict__ D, uint32_t n,
+                                                      const float* __restrict__ Q, int pad, const uint32_t* __restrict__ pad_ids,
+                                                      uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+                                                      unsigned long long* __restrict__ stat)
+{
+    __shared__ uint64_t sbuf[4][CAP];
+    __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 4u + w;
+    if (i >= nq) return;  // wave-uniform
+    const uint32_t q = q0 + i;
+    uint64_t* buf = sbuf[w];
+    const uint32_t s0 = sub_off[q], s1 = sub_off[q + 1u];
+    uint32_t cnt = 0, seen = 0;
+    for (uint32_t s = s0; s < s1; ++s) {
+        const uint32_t* __restrict__ ids = sub_ids + (size_t)s * knn;
+        // (hvs_in_info.merged_keys costs this second pass over the list's ids, an L2 hit: the gather may cut the buffer back in
+        // mid-list, so its own count does not say what a list held)
+        for (uint32_t off = 0; off < knn; off += 64u)
+            seen += (uint32_t)__popcll(__ballot(off + lane < knn && ids[off + lane] != 0xFFFFFFFFu));
+        cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, ids, sub_dists + (size_t)s * knn, 0ull, knn, lane);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (lane == 0u) {
+        if (cnt < knn) atomicAdd(&stat[0], 1ull);
+        if (seen) atomicAdd(&stat[1], (unsigned long long)seen);
+    }
+    const float* __restrict__ qv = Q + (size_t)q * HVS_QCOLS + 4;
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) {
+            const uint32_t s = e - cnt;  // (< knn <= live rows: host)
+            const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
+            const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
+            buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id) : ~0ull;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

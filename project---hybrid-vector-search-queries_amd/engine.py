@@ -100,6 +100,18 @@ class AfterInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class InInfo(C.Structure):
+    """hvs_in_info (include/hvs.h)."""
+    _fields_ = [("set_queries", C.c_uint32), ("sub_queries", C.c_uint32), ("max_set", C.c_uint32), ("underfull_queries", C.c_uint32),
+                ("merged_keys", C.c_uint64), ("expand_ms", C.c_double), ("merge_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+IN_MAX_VALUES = 64
+
+
 def library_path():
     return _LIB
 
@@ -255,6 +267,10 @@ def library():
         "hvs_query_after": (C.c_int, [vp, _f32p, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
         "hvs_after_stats": (C.c_int, [vp, C.POINTER(AfterInfo)]),
         "hvs_after_plan": (None, [_u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
+        "hvs_set_category_sets": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
+        "hvs_query_in": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_in_stats": (C.c_int, [vp, C.POINTER(InInfo)]),
+        "hvs_in_plan": (C.c_uint32, [_f32p, _u32p, _f32p, C.c_uint32, _u32p, _u32p, _f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -408,6 +424,47 @@ def after_plan(ids, dists, k, after_dist, after_id, pad_ids=None, pad_dists=None
                              _up(pad_ids) if padding else None, _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids),
                              _fp(out_d), C.byref(n_after))
     return out_ids, out_d, int(n_after.value)
+
+
+def _sets_csr(sets):
+    """Category sets as (offsets uint32[nq + 1], values float32): from a LIST of per-query sequences, or a TUPLE (offsets,
+    values) of an integer numpy array and the values, passed through as it is (so that a malformed CSR reaches the library)."""
+    if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray) and sets[0].dtype.kind in "iu":
+        off = np.ascontiguousarray(sets[0], np.uint32).ravel()
+        vals = np.ascontiguousarray(sets[1], np.float32).ravel()
+        return off, vals
+    lens = [len(s) for s in sets]
+    off = np.zeros(len(lens) + 1, np.uint32)
+    off[1:] = np.cumsum(lens, dtype=np.uint64)
+    vals = np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).ravel() for s in sets]) if lens else [], np.float32)
+    return off, vals
+
+
+def in_plan(q_rows, sets, want=True):
+    """hvs_in_plan: (nsub, sub_offsets, parent, value) of the expansion of `sets` (see _sets_csr) over `q_rows` (nq x 104, or
+    None = every query of type 1); the three arrays are None when `want` is False, and the whole result is None when the plan
+    is refused (malformed offsets, a set of more than 64 distinct categories; nothing is written then)."""
+    off, vals = _sets_csr(sets)
+    nq = max(off.size, 1) - 1
+    q = None
+    if q_rows is not None:
+        q = np.ascontiguousarray(q_rows, np.float32)
+        if q.ndim != 2 or q.shape != (nq, QCOLS):
+            raise HvsError(-1, "in_plan: query rows must be nq x 104 float32, one per set")
+    lib = library()
+    args = (_fp(q) if q is not None else None, _up(off) if off.size else None, _fp(vals) if vals.size else None, nq)
+    nsub = lib.hvs_in_plan(*args, None, None, None)
+    if nsub == 0xFFFFFFFF:
+        return None
+    if not want:
+        return int(nsub), None, None, None
+    sub = np.full(nq + 2, 0xFFFFFFFF, np.uint32)
+    parent = np.full(nsub + 1, 0xFFFFFFFF, np.uint32)
+    value = np.full(nsub + 1, -12345.0, np.float32)
+    if lib.hvs_in_plan(*args, _up(sub), _up(parent), _fp(value)) != nsub or sub[nq + 1] != 0xFFFFFFFF or parent[nsub] != 0xFFFFFFFF \
+            or value[nsub] != np.float32(-12345.0):
+        raise HvsError(-1, "hvs_in_plan wrote past its outputs")
+    return int(nsub), sub[:nq + 1].copy(), parent[:nsub].copy(), value[:nsub].copy()
 
 
 def _device_u32(x, what):
@@ -749,6 +806,40 @@ class Engine:
             return out_i, out_d
         finally:
             self.set_padding(was)
+
+    # --- category sets (include/hvs.h "category sets")
+    def set_category_sets(self, sets):
+        """Attach one category set per resident query -- a list of per-query sequences of category values (an empty one leaves
+        the query as it is), or an (offsets, values) CSR pair -- or None to remove the sets.  A query of type 1 or 3 with a
+        non-empty set then matches the rows whose C is any of its values.  Caps and cursors are attached afterwards."""
+        if sets is None:
+            self._ck(self._lib.hvs_set_category_sets(self._h, None, None, 0))
+            return
+        off, vals = _sets_csr(sets)
+        self._ck(self._lib.hvs_set_category_sets(self._h, _up(off) if off.size else None, _fp(vals) if vals.size else None,
+                                                 max(off.size, 1) - 1))
+
+    def query_in(self, q_rows, sets, sample_proportion=1.0, want_dists=True):
+        """hvs_query_in: host rows and their category sets in, host ids (and distances) out; sets = None is query()."""
+        q = np.ascontiguousarray(q_rows, np.float32)
+        if q.ndim != 2 or q.shape[1] != QCOLS:
+            raise HvsError(-1, "query rows must be nq x 104 float32")
+        nq, K = q.shape[0], self.k
+        ids = np.empty((nq, K), np.uint32)
+        d = np.empty((nq, K), np.float32) if want_dists else None
+        off, vals = (None, None) if sets is None else _sets_csr(sets)
+        if off is not None and off.size != nq + 1:
+            raise HvsError(-1, "query_in: one set per query")
+        self._ck(self._lib.hvs_query_in(self._h, _fp(q), _up(off) if off is not None else None,
+                                        _fp(vals) if vals is not None and vals.size else None, nq, sample_proportion, _up(ids),
+                                        _fp(d) if want_dists else None))
+        return (ids, d) if want_dists else ids
+
+    def in_stats(self):
+        """hvs_in_stats: queries answered through their sets, sub-queries, under-full queries, merge time of the last call."""
+        s = InInfo()
+        self._ck(self._lib.hvs_in_stats(self._h, C.byref(s)))
+        return s
 
     # --- resident variant
     def upload_queries(self, q_rows):
