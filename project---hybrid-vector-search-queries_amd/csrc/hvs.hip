@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <functional>
 #include <iterator>
 #include <new>
 #include <string>
@@ -189,8 +190,25 @@ struct HvsPart {
 };
 constexpr uint32_t kPartTailRows = HVS_KMAX;  // rows of the tail replica: the most a query can be padded with
 
+// One value of each kind per query of a set: its distance cap, normalised by hvs_k_norm_caps, and its result cursor
+// -- the raw (distance, id) pair and d_after_lo = the cursor's key + 1, built from the pair by hvs_k_norm_after.
+// HvsQuerySet holds two of these: the engines' and, under category sets, the user's.  Caps and cursors are sized apart
+// (per_query_room): the engines' caps grow with d_q, their cursors with the first call that sets any.
+struct HvsPerQuery {
+    float* d_max_d2 = nullptr;
+    uint64_t* d_after_lo = nullptr;
+    float* d_after_dist = nullptr;
+    uint32_t* d_after_id = nullptr;
+    uint32_t caps_cap = 0, after_cap = 0;  // entries d_max_d2 / each of the three cursor arrays has room for
+    void free_device()
+    {
+        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id);
+        caps_cap = after_cap = 0;
+    }
+};
+
 // Category sets of one GPU's resident queries (hvs_set_category_sets).  While `active`, the engines' resident set
-// (hvs_ctx::d_q, nq, d_out_*, d_max_d2, d_after_*) is the EXPANDED one -- `nq` sub-queries -- and this struct holds the user's
+// (hvs_ctx::d_q, nq, d_out_*, HvsQuerySet::eng) is the EXPANDED one -- `nq` sub-queries -- and this struct holds the user's
 // side of it: the user's `nuq` query rows, the plan that ties a user query to its sub-queries [h_sub_off[p], h_sub_off[p + 1]),
 // the user's caps and cursors (one per user query; gathered into the engines' arrays by hvs_k_expand_per_query) and the merged
 // result rows.  Every resident index of the C ABI is a user index; in_* functions below translate.  Not active: nothing here is
@@ -204,10 +222,7 @@ struct HvsInSet {
     uint32_t *d_sub_off = nullptr, *d_set_off = nullptr, *d_parent = nullptr;  // nuq + 1, nuq + 1 (the caller's CSR offsets), nsub
     float* d_value = nullptr;          // nsub
     uint32_t uq_cap = 0, sub_cap = 0;  // user queries / sub-queries the buffers above have room for
-    float* d_caps = nullptr;           // the user's caps (normalised), cursors (raw pair and normalised key): nuq each
-    uint64_t* d_after_lo = nullptr;
-    float* d_after_dist = nullptr;
-    uint32_t* d_after_id = nullptr;
+    HvsPerQuery user;                  // the user's caps and cursors: room for uq_cap each, allocated at attach
     uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
     float* d_m_dists = nullptr;
     size_t m_cap = 0;                  // entries
@@ -219,7 +234,8 @@ struct HvsInSet {
     uint32_t call_set_queries = 0, call_sub = 0, call_max_set = 0;
     void free_device()
     {
-        HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_caps, d_after_lo, d_after_dist, d_after_id, d_m_ids, d_m_dists, d_stat);
+        HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_m_ids, d_m_dists, d_stat);
+        user.free_device();
         for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
             if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
         uq_cap = sub_cap = 0;
@@ -228,7 +244,47 @@ struct HvsInSet {
     }
 };
 
+// What is ATTACHED to the resident queries of one GPU: caps, cursors, category sets and the range of queries that
+// have a result row.  The engines' own buffers -- d_q, nq, nq_cap, d_out_ids, d_out_dists, res_cap, d_ovf_list, d_retry_list --
+// stay in hvs_ctx: every launch reads them and the planner probe lends them out.  The invariants:
+//   - while caps_set is false no launch reads eng.d_max_d2, while after_set is false none reads eng.d_after_*
+//   - eng.d_max_d2 grows with d_q; the cursor arrays, once allocated, have room for eng.after_cap entries, >= nq whenever after_set
+//   - while in.active, `eng` holds the EXPANDED values, one entry per sub-query, and in.user one entry per user query
+//   - queries [res_lo, res_hi) have been answered with res_k slots since the set was installed (empty: none)
+// It changes through the transitions below the readers and through leaf_attach.  A row-partitioned ROOT uses the same fields for
+// what it keeps itself: the range of merged rows, res_gen and the two call flags.
+struct HvsQuerySet {
+    HvsPerQuery eng;           // what the launches read: one entry per resident query (under sets: per sub-query)
+    bool caps_set = false, after_set = false;
+    bool call_capped = false, call_after = false;  // the last call ran with caps / with cursors (hvs_within_stats, hvs_after_stats)
+    uint32_t res_lo = 0, res_hi = 0, res_k = 0;
+    uint32_t set_gen = 0;      // counts the resident sets this GPU has held
+    uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
+    HvsInSet in;               // category sets of the resident queries
+    void free_device() { eng.free_device(), in.free_device(); }
+    void drop_attached()  // caps off, cursors off, no results: they belonged to a set that is no longer the engines'
+    {
+        caps_set = after_set = false;
+        res_lo = res_hi = 0;
+    }
+    // a call answered [q0, q0 + nq) of set `gen` with k slots: its range joins the ranges answered so far if it touches them
+    void answered(uint32_t q0, uint32_t nq, uint32_t k, uint32_t gen)
+    {
+        if (res_gen != gen || res_k != k || res_lo >= res_hi || q0 > res_hi || q0 + nq < res_lo) {
+            res_gen = gen;
+            res_lo = q0;
+            res_hi = q0 + nq;
+            res_k = k;
+        } else {
+            res_lo = std::min(res_lo, q0);
+            res_hi = std::max(res_hi, q0 + nq);
+        }
+    }
+    bool covers(uint32_t nq, uint32_t k) const { return res_k == k && res_lo == 0u && res_hi >= nq; }
+};
+
 #define HVS_NCOUNTERS 20  // ([14], [15]: hvs_keep_within; [16] .. [18]: hvs_keep_after)
+constexpr uint32_t kCountersWithin = 14, kCountersAfter = 16;  // first slot of the figures of hvs_within_stats / hvs_after_stats
 struct hvs_ctx : HvsLane {
     int device = 0;
     HvsLane spare;                 // the second lane (its buffers are allocated by the first call that has two batches)
@@ -258,32 +314,13 @@ struct hvs_ctx : HvsLane {
     double load_ms = 0.0;
     HvsRowSet rs;
 
-    // resident queries + results
+    // resident queries + results; what is attached to them -- caps, cursors, category sets, the answered range: `qs`
     float* d_q = nullptr;
     uint32_t nq = 0, nq_cap = 0;
-    // per-query distance caps of the resident set (hvs_set_max_dist2): one f32 per query beside d_q, normalised by
-    // hvs_k_norm_caps.  While `caps_set` is false no launch reads d_max_d2 and every call takes its kernels' plain forms.
-    float* d_max_d2 = nullptr;
-    bool caps_set = false;
-    bool call_capped = false;  // the last call ran with caps (hvs_within_stats)
-    // per-query result cursors of the resident set (hvs_set_after): d_after_lo[q] = the cursor's key + 1, built by
-    // hvs_k_norm_after from the raw (distance, id) pairs in d_after_dist / d_after_id.  Allocated by the first call that sets
-    // cursors; while `after_set` is false no launch reads them and every call takes its kernels' plain forms.
-    uint64_t* d_after_lo = nullptr;
-    float* d_after_dist = nullptr;
-    uint32_t* d_after_id = nullptr;
-    uint32_t after_cap = 0;
-    bool after_set = false;
-    bool call_after = false;   // the last call ran with cursors (hvs_after_stats)
-    // results of the resident set: queries [res_lo, res_hi) have been answered with `res_k` slots since the set was installed
-    // (hvs_set_after_from_results needs all of them)
-    uint32_t res_lo = 0, res_hi = 0, res_k = 0;
-    uint32_t set_gen = 0;  // counts the resident sets this GPU has held (a row-partitioned root tells by it whose results it has: res_gen)
-    uint32_t res_gen = 0;
     uint32_t* d_out_ids = nullptr;
     float* d_out_dists = nullptr;
     uint32_t res_cap = 0;
-    HvsInSet in;  // category sets of the resident queries (while in.active, everything above is the expanded set)
+    HvsQuerySet qs;
 
     unsigned long long* d_counters = nullptr;  // HVS_NCOUNTERS of them, zeroed at the start of every call
 
@@ -374,14 +411,54 @@ namespace {
 // reach a row by its id in D take rs.d_live; launches that reach it through the index (perm, tiles) take index_mask(c).
 bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empty(); }
 // the resident queries carry distance caps: the CAPPED kernels run (with_capped)
-bool capped(const hvs_ctx* c) { return c->caps_set; }
+bool capped(const hvs_ctx* c) { return c->qs.caps_set; }
 // ... carry result cursors: the AFTER kernels run (with_capped_after)
-bool has_after(const hvs_ctx* c) { return c->after_set; }
+bool has_after(const hvs_ctx* c) { return c->qs.after_set; }
 // the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
-uint32_t user_nq(const hvs_ctx* c) { return c->in.active ? c->in.nuq : c->nq; }
-const float* user_queries(const hvs_ctx* c) { return c->in.active ? c->in.d_uq : c->d_q; }
-const uint32_t* user_ids(const hvs_ctx* c) { return c->in.active ? c->in.d_m_ids : c->d_out_ids; }
-const float* user_dists(const hvs_ctx* c) { return c->in.active ? c->in.d_m_dists : c->d_out_dists; }
+uint32_t user_nq(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.nuq : c->nq; }
+const float* user_queries(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_uq : c->d_q; }
+const uint32_t* user_ids(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_m_ids : c->d_out_ids; }
+const float* user_dists(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_m_dists : c->d_out_dists; }
+// every resident query has a result row with the current k (hvs_set_after_from_results needs all of them)
+bool leaf_has_all_results(const hvs_ctx* c) { return c->qs.covers(c->nq, c->k); }
+
+// ---- transitions of the resident-query state (HvsQuerySet; DESIGN 3.13a has the table) ----
+// a call replaces the resident set: sets, caps and cursors belonged to the old one, and so did its results
+void resident_set_replaced(hvs_ctx* c)
+{
+    c->qs.in.active = false;
+    c->qs.drop_attached();
+    ++c->qs.set_gen;
+}
+// category sets attached (`on`), detached, or lost half-way through an attach: the engines' set changed under everything else
+// that was attached -- caps and cursors come after the sets, earlier results are dropped, the last call's figures with them
+void sets_changed(hvs_ctx* c, bool on)
+{
+    c->qs.in.active = on;
+    c->qs.drop_attached();
+    c->timing_valid = false;
+}
+// k changed: no result row and no merged row has the new size (the range itself is told by res_k), nothing of the last call is
+// left to report.  Returns the queries the result buffers had room for: hvs_set_k re-sizes them at once.
+uint32_t k_changed(hvs_ctx* c)
+{
+    const uint32_t had = c->res_cap;
+    c->res_cap = 0;
+    c->qs.in.m_cap = 0;  // (the merged rows of category sets are re-allocated by the next call)
+    c->timing_valid = false;
+    return had;
+}
+// the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
+struct DetachedForProbe {
+    HvsQuerySet& s;
+    const bool caps, after;
+    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set) { s.caps_set = s.after_set = false; }
+    ~DetachedForProbe()
+    {
+        s.caps_set = caps;
+        s.after_set = after;
+    }
+};
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
 uint32_t tail_rows(const hvs_ctx* c) { return c->have_order ? c->n - c->n_indexed : 0u; }
 uint32_t stale_below(const hvs_ctx* c, uint32_t sn)
@@ -560,6 +637,26 @@ int dev_alloc(hvs_ctx* c, T** p, size_t count)
     return HVS_OK;
 }
 
+// room for n caps and / or n cursors in `v` (contents are not kept; a failure leaves the capacity at 0)
+enum : unsigned { kCaps = 1u, kCursors = 2u };
+int per_query_room(hvs_ctx* c, HvsPerQuery& v, unsigned which, uint32_t n)
+{
+    int rc;
+    if ((which & kCaps) && n > v.caps_cap) {
+        v.caps_cap = 0;
+        if ((rc = dev_alloc(c, &v.d_max_d2, (size_t)n))) return rc;
+        v.caps_cap = n;
+    }
+    if ((which & kCursors) && n > v.after_cap) {
+        v.after_cap = 0;
+        if ((rc = dev_alloc(c, &v.d_after_lo, (size_t)n)) || (rc = dev_alloc(c, &v.d_after_dist, (size_t)n)) ||
+            (rc = dev_alloc(c, &v.d_after_id, (size_t)n)))
+            return rc;
+        v.after_cap = n;
+    }
+    return HVS_OK;
+}
+
 // Device temporaries of one scope, freed when it ends, whichever way it ends.  `lend`: the temporary also stands in for one of
 // the context's long-lived buffers for that time (swapped into `*field` now, swapped back before it is freed).
 struct ScopedDevBufs {
@@ -702,7 +799,7 @@ void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t st
         with_capped_after(c, [&](auto WT, auto AT) {
             hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt,
-                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->d_max_d2, c->d_counters, c->d_after_lo);
+                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->qs.eng.d_max_d2, c->d_counters, c->qs.eng.d_after_lo);
         });
     });
 }
@@ -735,7 +832,7 @@ int ensure_queries(hvs_ctx* c, uint32_t nq)
         int rc;
         c->nq_cap = 0;  // (the two buffers grow together: a failure between them leaves neither in use)
         if ((rc = dev_alloc(c, &c->d_q, (size_t)nq * HVS_QCOLS))) return rc;
-        if ((rc = dev_alloc(c, &c->d_max_d2, (size_t)nq))) return rc;
+        if ((rc = per_query_room(c, c->qs.eng, kCaps, nq))) return rc;
         c->nq_cap = nq;
     }
     return ensure_results(c, nq);
@@ -821,7 +918,7 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
                 hipLaunchKernelGGL(
                     (hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                     grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat,
-                    c->k, c->rs.d_live, c->d_max_d2, c->d_after_lo);
+                    c->k, c->rs.d_live, c->qs.eng.d_max_d2, c->qs.eng.d_after_lo);
             });
         });
     }
@@ -1132,13 +1229,11 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     // PCA-like vectors at n = 10^7 hand ~1500 rows per type-0 query to the last level's list of 1024 -- INT8 tiles look 23 %
     // faster than FP16 tiles there only while a half-empty workspace doubles the lists, profiles/r04/nonuniform_int8.txt)
     c->force_pfail = guess_pfail_for(kBatchMfma);
-    const bool caps_were_set = c->caps_set;  // (the caps belong to the caller's queries, not to the probe's)
-    const bool after_was_set = c->after_set;  // (so do the cursors)
-    c->caps_set = false;
-    c->after_set = false;
-    int rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
-    c->caps_set = caps_were_set;
-    c->after_set = after_was_set;
+    int rc;
+    {
+        const DetachedForProbe probe(c->qs);
+        rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
+    }
     c->force_pfail = 0u;
     unsigned long long h[4] = {0, 0, 0, 0};
     uint32_t fails[2] = {0, 0};
@@ -1412,7 +1507,7 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
     // query itself, non-finite ones included)
     with_capped(c, [&](auto WT) {  // (capped: the slots' thresholds start at the queries' caps)
         hipLaunchKernelGGL(hvs_k_prep<decltype(WT)::value>, dim3(B.ngroups), dim3(4 * HVS_GROUP), 0, c->stream, c->d_q, B, count_pairs ? 1 : 0,
-                           c->d_counters, fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1, c->d_max_d2);
+                           c->d_counters, fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1, c->qs.eng.d_max_d2);
     });
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1428,7 +1523,7 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
         with_after(c, [&](auto AT) {
             hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters,
-                               count ? 1 : 0, c->rs.d_live, c->d_after_lo);
+                               count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
         });
     });
 }
@@ -1442,7 +1537,7 @@ void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
         with_after(c, [&](auto AT) {
             hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m,
-                               c->d_counters, count ? 1 : 0, c->rs.d_live, c->d_after_lo);
+                               c->d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
         });
     });
 }
@@ -1501,7 +1596,7 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
             hipLaunchKernelGGL(
                 (hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>), grid,
                 dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand,
-                c->d_cand_cnt, c->d_counters, index_mask(c), c->d_after_lo);
+                c->d_cand_cnt, c->d_counters, index_mask(c), c->qs.eng.d_after_lo);
         });
     });
     kernel_timer_end(c, ev);
@@ -1666,7 +1761,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B,
                                c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->d_counters, std::max(1u, seed_chunks),
-                               index_mask(c), c->d_after_lo);
+                               index_mask(c), c->qs.eng.d_after_lo);
         });
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
@@ -1677,13 +1772,13 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
                 with_capped_after(c, [&](auto WT, auto AT) {
                     hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                        dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds,
-                                       c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids, c->d_max_d2,
-                                       c->d_counters, c->d_after_lo);
+                                       c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids, c->qs.eng.d_max_d2,
+                                       c->d_counters, c->qs.eng.d_after_lo);
                 });
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
                                    c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids,
-                                   c->d_max_d2, c->d_counters, c->d_after_lo);
+                                   c->qs.eng.d_max_d2, c->d_counters, c->qs.eng.d_after_lo);
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -1729,7 +1824,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
                     const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M, const uint64_t*> : hvs_k_rescore<false, M, const uint64_t*>;  // (entry format)
                     hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
                                        c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, index_mask(c),
-                                       static_cast<const uint64_t*>(c->d_after_lo));
+                                       static_cast<const uint64_t*>(c->qs.eng.d_after_lo));
                 } else {
                     const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;
                     hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
@@ -1972,18 +2067,10 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
         mfma = c->fmt.built != HVS_FMT_NONE;  // (no usable bound at all: the exact engine answers, on the orderings)
     }
     c->timing_valid = false;
-    c->call_capped = capped(c);
-    c->call_after = has_after(c);
-    c->in.call = false;  // (in_run sets it once the merge is enqueued)
-    // (the results the resident set has: this call's range joins the ranges answered so far if it touches them)
-    if (c->res_k != c->k || c->res_lo >= c->res_hi || q0 > c->res_hi || q0 + nq < c->res_lo) {
-        c->res_lo = q0;
-        c->res_hi = q0 + nq;
-        c->res_k = c->k;
-    } else {
-        c->res_lo = std::min(c->res_lo, q0);
-        c->res_hi = std::max(c->res_hi, q0 + nq);
-    }
+    c->qs.call_capped = capped(c);
+    c->qs.call_after = has_after(c);
+    c->qs.in.call = false;  // (in_run sets it once the merge is enqueued)
+    c->qs.answered(q0, nq, c->k, c->qs.set_gen);
     c->n_launch_events = 0;
     c->untimed_launches = 0;
     c->fallback_queries = 0;
@@ -2168,12 +2255,12 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
-    void* ptrs[] = {c->d_data, c->d_q, c->d_max_d2, c->d_after_lo, c->d_after_dist, c->d_after_id, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
+    void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
                     c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->rs.free_device();
-    c->in.free_device();
+    c->qs.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     {
         HvsPart& P = c->part;
@@ -2206,15 +2293,16 @@ void leaf_destroy(hvs_ctx* c)
 }
 
 int ensure_staging(hvs_ctx* c, bool dists, uint64_t nq_in, uint64_t nq_out);
+int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq);
 
 // query / result buffers and the batch workspace for calls of up to nq queries (hvs_reserve, hvs_query): keeps the
 // ~34 GB of per-batch state of a 2^21-query batch out of the first query's own time
 int leaf_reserve(hvs_ctx* c, uint32_t nq)
 {
     HVS_HIP(c, hipSetDevice(c->device));
-    if (c->in.active) {  // category sets: the engines answer the sub-queries of the first nq queries (one each beyond the resident ones)
-        const uint32_t in_set = std::min(nq, c->in.nuq);
-        nq = (uint32_t)std::min<uint64_t>((uint64_t)c->in.h_sub_off[in_set] + (nq - in_set), 0xFFFFFFFFull);
+    if (c->qs.in.active) {  // category sets: the engines answer the sub-queries of the first nq queries (one each beyond the resident ones)
+        const uint32_t in_set = std::min(nq, c->qs.in.nuq);
+        nq = (uint32_t)std::min<uint64_t>((uint64_t)c->qs.in.h_sub_off[in_set] + (nq - in_set), 0xFFFFFFFFull);
     }
     c->reserve_nq = std::max(c->reserve_nq, nq);
     if (nq == 0u) return HVS_OK;
@@ -2632,133 +2720,100 @@ int leaf_begin_queries(hvs_ctx* c, uint32_t nq)
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = 0;
-    c->in.active = false;  // (category sets belong to a resident set too: the engines' set is the user's again)
-    c->caps_set = false;  // (caps belong to a resident set: every call that replaces the set removes them)
-    c->after_set = false;  // (and cursors)
-    c->res_lo = c->res_hi = 0;
-    ++c->set_gen;
+    resident_set_replaced(c);
     return ensure_queries(c, nq);
 }
 
-// hvs_set_max_dist2 / hvs_set_max_dist2_device on one GPU: `count` caps from host memory (src_dev < 0) or from a device buffer of
-// GPU src_dev, attached to the resident queries (count == c->nq: checked by the caller), or removed (src == nullptr).  Results of
-// earlier calls stay; an earlier call's pending re-runs are resolved first, under the caps they were asked under.
-int leaf_set_caps(hvs_ctx* c, const float* src, int src_dev, uint32_t count)
+// ---- attaching per-query values to the resident queries (HvsQuerySet) ----
+enum class PerQuery { Caps, Cursors };
+// Where the values come from.  `f`: the caps, or the cursors' distances; `u`: the cursors' ids.
+struct PerQuerySource {
+    enum Kind {
+        Remove,    // nothing: the values are taken off
+        Host,      // host memory
+        Device,    // device buffers of GPU `dev` (checked and waited for by the caller)
+        LastSlot,  // cursors only: slot k-1 of the result rows f (distances) / u (ids), k slots each
+        InPlace    // cursors only: the raw pairs are in the arrays already (a row-partitioned context's exchange put them there)
+    } kind = Remove;
+    const float* f = nullptr;
+    const uint32_t* u = nullptr;
+    int dev = -1;
+};
+// a caller's arrays: host memory (src_dev < 0) or device memory of GPU src_dev; f == nullptr: remove
+PerQuerySource caller_values(const float* f, const uint32_t* u, int src_dev)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);
-    if (rc) return rc;
-    if (!src) {
-        c->caps_set = false;
-        return HVS_OK;
-    }
-    if (count) {
-        float* dst = c->in.active ? c->in.d_caps : c->d_max_d2;  // (under category sets: the user's caps, one per user query)
-        if (src_dev < 0)
-            HVS_HIP(c, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        else if ((rc = copy_from_device(c, dst, src, src_dev, (size_t)count * sizeof(float))))
-            return rc;
-        hipLaunchKernelGGL(hvs_k_norm_caps, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, dst, count);
-        HVS_HIP(c, hipGetLastError());
-        if (c->in.active) {  // ... and every sub-query takes its parent's
-            hipLaunchKernelGGL(hvs_k_expand_per_query, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, c->in.d_parent, c->nq, dst, c->d_max_d2,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-            HVS_HIP(c, hipGetLastError());
-        }
-    }
-    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the buffer is the caller's again)
-    c->caps_set = true;
-    return HVS_OK;
+    return PerQuerySource{!f ? PerQuerySource::Remove : src_dev < 0 ? PerQuerySource::Host : PerQuerySource::Device, f, u, src_dev};
 }
 
-// room for `nq` cursors (allocated by the first call that sets any: contexts that never page pay nothing)
+// room for `nq` cursors in the engines' arrays (allocated by the first call that sets any: contexts that never page pay nothing)
 int ensure_after(hvs_ctx* c, uint32_t nq)
 {
-    if (nq <= c->after_cap) return HVS_OK;
+    if (nq <= c->qs.eng.after_cap) return HVS_OK;
+    c->qs.after_set = false;  // (the buffers are about to change hands)
+    return per_query_room(c, c->qs.eng, kCursors, nq);
+}
+
+// The one way caps or cursors reach the resident queries of one GPU: `count` values from `src` (count = the user's resident
+// queries: checked by the caller) are attached, or the values are removed.  Under category sets they are the user's, one per user
+// query: copied and normalised on the user's side (HvsInSet::user), then every sub-query takes its parent's.  `row0` (cursors):
+// the first global row of this GPU's part.  An earlier call's pending re-runs are resolved first, under the values they were
+// asked under; results of earlier calls stay.  The call returns when the caller's buffers are the caller's again.
+int leaf_attach(hvs_ctx* c, PerQuery what, const PerQuerySource& src, uint32_t count, uint32_t row0)
+{
+    HvsQuerySet& s = c->qs;
+    const bool caps = what == PerQuery::Caps, sets = s.in.active;
     int rc;
-    c->after_cap = 0;
-    c->after_set = false;  // (the buffers are about to change hands)
-    if ((rc = dev_alloc(c, &c->d_after_lo, (size_t)nq)) || (rc = dev_alloc(c, &c->d_after_dist, (size_t)nq)) ||
-        (rc = dev_alloc(c, &c->d_after_id, (size_t)nq)))
-        return rc;
-    c->after_cap = nq;
-    return HVS_OK;
-}
-
-// the raw cursors in d_after_dist / d_after_id become the resident queries' cursors; `row0`: the part's first global row
-int leaf_commit_after(hvs_ctx* c, uint32_t count, uint32_t row0)
-{
-    if (count && c->in.active) {
-        // under category sets the raw cursors are the user's (HvsInSet): normalised there, then every sub-query takes its parent's
-        const HvsInSet& S = c->in;
-        hipLaunchKernelGGL(hvs_k_norm_after, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, S.d_after_dist, S.d_after_id, count, row0,
-                           S.d_after_lo);
-        hipLaunchKernelGGL(hvs_k_expand_per_query, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, S.d_parent, c->nq, nullptr, nullptr,
-                           S.d_after_lo, S.d_after_dist, S.d_after_id, c->d_after_lo, c->d_after_dist, c->d_after_id);
-        HVS_HIP(c, hipGetLastError());
-    } else if (count) {
-        hipLaunchKernelGGL(hvs_k_norm_after, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, c->d_after_dist, c->d_after_id, count, row0,
-                           c->d_after_lo);
-        HVS_HIP(c, hipGetLastError());
-    }
-    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
-    c->after_set = true;
-    return HVS_OK;
-}
-
-// hvs_set_after / hvs_set_after_device on one GPU, the counterpart of leaf_set_caps: `count` cursors (distance, id) from host
-// memory (src_dev < 0) or from device buffers of GPU src_dev, attached to the resident queries (count == c->nq: checked by the
-// caller), or removed (dists == nullptr).  An earlier call's pending re-runs are resolved first, under the cursors they were
-// asked under.
-int leaf_set_after(hvs_ctx* c, const float* dists, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0)
-{
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);
-    if (rc) return rc;
-    if (!dists) {
-        c->after_set = false;
-        return HVS_OK;
-    }
-    if ((rc = ensure_after(c, std::max(std::max(count, c->in.active ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
-    if (count) {
-        float* dd = c->in.active ? c->in.d_after_dist : c->d_after_dist;
-        uint32_t* di = c->in.active ? c->in.d_after_id : c->d_after_id;
-        if (src_dev < 0) {
-            HVS_HIP(c, hipMemcpyAsync(dd, dists, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            HVS_HIP(c, hipMemcpyAsync(di, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        } else if ((rc = copy_from_device(c, dd, dists, src_dev, (size_t)count * sizeof(float))) ||
-                   (rc = copy_from_device(c, di, ids, src_dev, (size_t)count * sizeof(uint32_t)))) {
-            return rc;
+    if (src.kind != PerQuerySource::InPlace) {
+        HVS_HIP(c, hipSetDevice(c->device));
+        if ((rc = resolve_overflow(c))) return rc;  // (for LastSlot: the last slots of re-run queries too)
+        if (src.kind == PerQuerySource::Remove) {
+            (caps ? s.caps_set : s.after_set) = false;
+            return HVS_OK;
         }
+        if (!caps && (rc = ensure_after(c, std::max(std::max(count, sets ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
     }
-    return leaf_commit_after(c, count, row0);
+    if (count) {
+        const HvsPerQuery& dst = sets ? s.in.user : s.eng;
+        const dim3 grid(hvs_ceil_div(count, 256u)), sub_grid(hvs_ceil_div(c->nq, 256u));
+        auto copy = [&](void* to, const void* from, size_t bytes) -> int {
+            if (src.kind == PerQuerySource::Device) return copy_from_device(c, to, from, src.dev, bytes);
+            HVS_HIP(c, hipMemcpyAsync(to, from, bytes, hipMemcpyHostToDevice, c->stream));
+            return HVS_OK;
+        };
+        if (caps) {
+            if ((rc = copy(dst.d_max_d2, src.f, (size_t)count * sizeof(float)))) return rc;
+            hipLaunchKernelGGL(hvs_k_norm_caps, grid, dim3(256), 0, c->stream, dst.d_max_d2, count);
+            HVS_HIP(c, hipGetLastError());
+            if (sets)
+                hipLaunchKernelGGL(hvs_k_expand_per_query, sub_grid, dim3(256), 0, c->stream, s.in.d_parent, c->nq, dst.d_max_d2, s.eng.d_max_d2, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, nullptr);
+        } else {
+            if (src.kind == PerQuerySource::LastSlot) {
+                hipLaunchKernelGGL(hvs_k_after_from_results, grid, dim3(256), 0, c->stream, src.u, src.f, count, c->k, dst.d_after_dist, dst.d_after_id);
+                HVS_HIP(c, hipGetLastError());
+            } else if (src.kind != PerQuerySource::InPlace) {
+                if ((rc = copy(dst.d_after_dist, src.f, (size_t)count * sizeof(float))) || (rc = copy(dst.d_after_id, src.u, (size_t)count * sizeof(uint32_t))))
+                    return rc;
+            }
+            hipLaunchKernelGGL(hvs_k_norm_after, grid, dim3(256), 0, c->stream, dst.d_after_dist, dst.d_after_id, count, row0, dst.d_after_lo);
+            if (sets)
+                hipLaunchKernelGGL(hvs_k_expand_per_query, sub_grid, dim3(256), 0, c->stream, s.in.d_parent, c->nq, nullptr, nullptr, dst.d_after_lo,
+                                   dst.d_after_dist, dst.d_after_id, s.eng.d_after_lo, s.eng.d_after_dist, s.eng.d_after_id);
+        }
+        if (!caps || sets) HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    (caps ? s.caps_set : s.after_set) = true;
+    return HVS_OK;
 }
 
 // hvs_set_after_from_results on one GPU that holds its own results (a single context, a leaf of a replicated one): checked by
-// the caller -- results of all resident queries exist with the current k, padding is off
+// the caller -- results of all resident queries exist with the current k, padding is off.  Under category sets: slot k-1 of the
+// MERGED rows, one cursor per user query.
 int leaf_after_from_results(hvs_ctx* c)
 {
-    HVS_HIP(c, hipSetDevice(c->device));
-    int rc = resolve_overflow(c);  // (the last slots of re-run queries too)
-    if (rc) return rc;
-    if ((rc = ensure_after(c, std::max(c->nq, 1u)))) return rc;
-    if (c->in.active) {  // category sets: slot k-1 of the MERGED rows, one cursor per user query
-        const HvsInSet& S = c->in;
-        if (S.nuq) {
-            hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(S.nuq, 256u)), dim3(256), 0, c->stream, S.d_m_ids, S.d_m_dists, S.nuq, c->k,
-                               S.d_after_dist, S.d_after_id);
-            HVS_HIP(c, hipGetLastError());
-        }
-        return leaf_commit_after(c, S.nuq, 0u);
-    }
-    if (c->nq) {
-        hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, c->d_out_ids, c->d_out_dists, c->nq,
-                           c->k, c->d_after_dist, c->d_after_id);
-        HVS_HIP(c, hipGetLastError());
-    }
-    return leaf_commit_after(c, c->nq, 0u);
+    return leaf_attach(c, PerQuery::Cursors, PerQuerySource{PerQuerySource::LastSlot, user_dists(c), user_ids(c), -1}, user_nq(c), 0u);
 }
-bool leaf_has_all_results(const hvs_ctx* c) { return c->res_k == c->k && c->res_lo == 0u && c->res_hi >= c->nq && (c->nq == 0u || c->res_hi > 0u); }
 
 int leaf_upload_queries(hvs_ctx* c, const float* q_rows, uint32_t nq)
 {
@@ -2835,7 +2890,7 @@ int leaf_download_results(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* out_id
     if (!out_ids || (uint64_t)q0 + nq > user_nq(c)) return fail(c, HVS_EINVAL, "hvs_download_results: bad range");
     int rc = leaf_sync(c);
     if (rc) return rc;
-    if (c->in.active && c->in.m_cap < (size_t)c->in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_download_results: no results (hvs_query_resident has not run)");
+    if (c->qs.in.active && c->qs.in.m_cap < (size_t)c->qs.in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_download_results: no results (hvs_query_resident has not run)");
     HVS_HIP(c, hipMemcpyAsync(out_ids, user_ids(c) + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
                               hipMemcpyDeviceToHost, c->stream));
     if (out_dists)
@@ -2896,7 +2951,7 @@ uint32_t in_plan_core(const float* types, const float* own_v, size_t stride, con
 
 int in_ensure_events(hvs_ctx* c)
 {
-    for (hipEvent_t* ev : {&c->in.ev_x0, &c->in.ev_x1, &c->in.ev_m0, &c->in.ev_m1})
+    for (hipEvent_t* ev : {&c->qs.in.ev_x0, &c->qs.in.ev_x1, &c->qs.in.ev_m0, &c->qs.in.ev_m1})
         if (!*ev) HVS_HIP(c, hipEventCreate(ev));
     return HVS_OK;
 }
@@ -2904,17 +2959,14 @@ int in_ensure_events(hvs_ctx* c)
 // hvs_set_category_sets(NULL, NULL, 0) on one GPU: the resident set becomes the user's again (a no-op while no sets are attached)
 int in_detach(hvs_ctx* c)
 {
-    HvsInSet& S = c->in;
+    HvsInSet& S = c->qs.in;
     if (!S.active) return HVS_OK;
     int rc = begin_mutation(c);
     if (rc) return rc;
     if (S.nuq) HVS_HIP(c, hipMemcpyAsync(c->d_q, S.d_uq, (size_t)S.nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = S.nuq;  // (nq_cap >= the sub-queries >= the user's queries)
-    S.active = false;
-    c->caps_set = c->after_set = false;
-    c->res_lo = c->res_hi = 0;
-    c->timing_valid = false;
+    sets_changed(c, false);
     return HVS_OK;
 }
 
@@ -2926,7 +2978,7 @@ int in_detach(hvs_ctx* c)
 // other GPU too (hvs_set_category_sets): sets are attached on all GPUs or on none.
 int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
 {
-    HvsInSet& S = c->in;
+    HvsInSet& S = c->qs.in;
     int rc = begin_mutation(c);
     if (!rc) rc = in_ensure_events(c);
     if (rc) return rc;
@@ -2936,9 +2988,7 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
         if (!S.d_sub_off || nuq > S.uq_cap) {
             S.uq_cap = 0;
             if ((rc = dev_alloc(c, &S.d_uq, (size_t)nuq * HVS_QCOLS)) || (rc = dev_alloc(c, &S.d_sub_off, (size_t)nuq + 1u)) ||
-                (rc = dev_alloc(c, &S.d_set_off, (size_t)nuq + 1u)) || (rc = dev_alloc(c, &S.d_caps, (size_t)nuq)) ||
-                (rc = dev_alloc(c, &S.d_after_lo, (size_t)nuq)) || (rc = dev_alloc(c, &S.d_after_dist, (size_t)nuq)) ||
-                (rc = dev_alloc(c, &S.d_after_id, (size_t)nuq)))
+                (rc = dev_alloc(c, &S.d_set_off, (size_t)nuq + 1u)) || (rc = per_query_room(c, S.user, kCaps | kCursors, nuq)))
                 return rc;
             S.uq_cap = nuq;
         }
@@ -2961,10 +3011,7 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
     (void)in_plan_core(tv.data(), tv.data() + 1, 2u, set_off.data(), v0, nuq, nullptr, parent.data(), value.data(), nullptr);
     // from here on the context changes
     auto lost = [&](int code) {
-        S.active = false;
-        c->caps_set = c->after_set = false;
-        c->res_lo = c->res_hi = 0;
-        c->timing_valid = false;
+        sets_changed(c, false);
         if (c->nq_cap < nuq) c->nq = 0;
         else if (hipMemcpy(c->d_q, S.d_uq, (size_t)nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess) c->nq = nuq;
         else c->nq = 0;
@@ -2975,8 +3022,7 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
         if ((rc = dev_alloc(c, &S.d_parent, (size_t)nsub)) || (rc = dev_alloc(c, &S.d_value, (size_t)nsub))) return lost(rc);
         S.sub_cap = nsub;
     }
-    if ((rc = ensure_queries(c, nsub))) return lost(rc);
-    if (c->after_cap && c->after_cap < nsub) c->after_cap = 0;  // (ensure_after re-allocates for the sub-queries when cursors come)
+    if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
     if (up(S.d_sub_off, sub_off.data(), sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
         up(S.d_set_off, set_off.data(), set_off.size() * sizeof(uint32_t)) != hipSuccess ||
@@ -2997,11 +3043,8 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
     S.expand_ms = ms;
     S.h_sub_off.swap(sub_off);
     S.h_eff.swap(eff);
-    S.active = true;
     c->nq = nsub;
-    c->caps_set = c->after_set = false;  // (caps and cursors are attached after the sets; earlier results are dropped)
-    c->res_lo = c->res_hi = 0;
-    c->timing_valid = false;
+    sets_changed(c, true);
     return HVS_OK;
 }
 
@@ -3010,7 +3053,7 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
 // synchronisation, as part_run has), then one merge launch into the merged rows q0 .. q0 + nq.
 int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
 {
-    HvsInSet& S = c->in;
+    HvsInSet& S = c->qs.in;
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if ((uint64_t)q0 + nq > S.nuq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
@@ -3063,7 +3106,7 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
 
 int leaf_run_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
 {
-    return c->in.active ? in_run(c, q0, nq, sample_proportion) : run_queries(c, q0, nq, sample_proportion, NoHook{});
+    return c->qs.in.active ? in_run(c, q0, nq, sample_proportion) : run_queries(c, q0, nq, sample_proportion, NoHook{});
 }
 
 int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
@@ -3072,7 +3115,7 @@ int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
     int rc = leaf_sync(c);
     if (rc) return rc;
     *out = hvs_in_info{};
-    const HvsInSet& S = c->in;
+    const HvsInSet& S = c->qs.in;
     if (!S.call) return HVS_OK;
     unsigned long long v[2] = {0, 0};
     HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
@@ -3123,8 +3166,7 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     if ((rc = ensure_staging(c, out_dists != nullptr && !sink, in_pinned ? 0u : nq, out_pinned ? 0u : nq))) return rc;
     tr.mark("staging");
     c->nq = nq;
-    if (max_d2 && (rc = leaf_set_caps(c, max_d2, -1, nq))) return rc;
-    if (after_d && (rc = leaf_set_after(c, after_d, after_i, -1, nq, 0u))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too)
+    if ((rc = attach_for_call(c, max_d2, after_d, after_i, nq))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too)
     const bool sink_dists = sink && sink->want_dists;
     constexpr uint32_t SQ = hvs_ctx::kStageQ;
     constexpr int R = hvs_ctx::kRing;
@@ -3831,6 +3873,34 @@ int on_every_leaf(hvs_ctx* c, Fn fn)
     return for_each_leaf(c, [&](uint32_t r) { return fn(c->kids[r]); });
 }
 
+// Each leaf's share of an array with one entry per resident query, `nq` of them: fn(leaf, first entry, entries, row0).  On a
+// replicated context the share is the leaf's range of the queries (kid_q0) and row0 = 0; on a row-partitioned one every part
+// takes the whole array, and row0 is the part's first global row.  (No resident queries: every share is empty.)
+template <typename Fn>
+int for_each_share(hvs_ctx* c, uint32_t nq, Fn fn)
+{
+    if (c->kids.empty()) return fn(c, 0u, nq, 0u);
+    const bool cut = c->kid_q0.size() == c->kids.size() + 1u;
+    return for_each_leaf(c, [&](uint32_t r) -> int {
+        if (c->partitioned) return fn(c->kids[r], 0u, nq, c->part_row0.size() > r ? c->part_row0[r] : 0u);
+        return fn(c->kids[r], cut ? c->kid_q0[r] : 0u, cut ? c->kid_q0[r + 1] - c->kid_q0[r] : 0u, 0u);
+    });
+}
+// the caller's caps or cursors (caller_values) to every leaf (hvs_set_max_dist2*, hvs_set_after*), or, f == nullptr, off every leaf
+int attach_everywhere(hvs_ctx* c, PerQuery what, const float* f, const uint32_t* u, int src_dev, uint32_t nq)
+{
+    return for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t row0) {
+        return leaf_attach(k, what, caller_values(f ? f + first : f, u ? u + first : u, src_dev), m, row0);
+    });
+}
+// hvs_query_after / hvs_query_within: the call's caps and cursors (host memory, `nq` each; nullptr: none) onto the queries just installed
+int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq)
+{
+    int rc = max_d2 ? attach_everywhere(c, PerQuery::Caps, max_d2, nullptr, -1, nq) : HVS_OK;
+    if (!rc && after_d) rc = attach_everywhere(c, PerQuery::Cursors, after_d, after_i, -1, nq);
+    return rc;
+}
+
 // the leaf whose row-set state speaks for the whole context (rows, mask and index are replicated)
 const hvs_ctx* mask_leaf(const hvs_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
 // ... for an entry point `fn` that needs a data set; nullptr (HVS_ESTATE, with the error text set) when there is none
@@ -3869,6 +3939,31 @@ int leaf0_stats(hvs_ctx* c, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add a
         if (r == 0u) agg = m;
         else add(agg, m);
     }
+    *out = agg;
+    return HVS_OK;
+}
+
+// Per-call figures of a multi-GPU context: the leaves that took part in the last call, combined by `add(sum, leaf's)`.  On a
+// row-partitioned context every part answered all the queries: `partitioned(sum)`, where given, puts the call's own figures
+// in the place of the sums that would count a query once per part.
+template <typename Info, typename Add>
+int call_stats(hvs_ctx* c, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add add, const std::function<void(Info&)>& partitioned = nullptr)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_stats(c, out);
+    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    Info agg{};
+    bool any = c->partitioned;
+    for (hvs_ctx* k : c->kids) {
+        if (!k->timing_valid) continue;  // (took no part in the last call)
+        Info m{};
+        const int rc = leaf_stats(k, &m);
+        if (rc) return fail(c, rc, k->err);
+        add(agg, m);
+        any = true;
+    }
+    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
+    if (c->partitioned && partitioned) partitioned(agg);
     *out = agg;
     return HVS_OK;
 }
@@ -3933,8 +4028,8 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     if (c->kid_q0.size() != N + 1u || (uint64_t)q0 + nq > c->kid_q0.back())
         return fail(c, HVS_EINVAL, "query range outside the resident query set");
     c->part_timing_valid = false;
-    c->call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
-    c->call_after = has_after(c->kids[0]);  // (likewise the cursors)
+    c->qs.call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
+    c->qs.call_after = has_after(c->kids[0]);  // (likewise the cursors)
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -4027,16 +4122,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     }
     c->part_timing_valid = true;
     c->part_call_nq = nq;
-    // (the merged results the resident set has, as run_queries_cut keeps them for one GPU)
-    if (c->res_gen != c->kids[0]->set_gen || c->res_k != K || c->res_lo >= c->res_hi || q0 > c->res_hi || q0 + nq < c->res_lo) {
-        c->res_gen = c->kids[0]->set_gen;
-        c->res_lo = q0;
-        c->res_hi = q0 + nq;
-        c->res_k = K;
-    } else {
-        c->res_lo = std::min(c->res_lo, q0);
-        c->res_hi = std::max(c->res_hi, q0 + nq);
-    }
+    c->qs.answered(q0, nq, K, c->kids[0]->qs.set_gen);  // (the merged rows the resident set has, as run_queries_cut keeps them for one GPU)
     return HVS_OK;
 }
 
@@ -4100,6 +4186,115 @@ int part_load(hvs_ctx* c, const float* rows, int src_dev, uint32_t n, uint64_t s
         c->part_n = 0;  // (parts may hold different data sets now: load again)
     }
     return rc;
+}
+
+// ---- what the entry points of caps, cursors and category sets share ----
+// resident queries of the whole context
+uint32_t resident_count(const hvs_ctx* c)
+{
+    if (c->kids.empty()) return user_nq(c);
+    return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
+}
+// what the four entry points that attach per-query values check alike: `nq` is the number of resident queries ...
+int check_resident_count(hvs_ctx* c, uint32_t nq, const char* fn)
+{
+    return nq == resident_count(c) ? HVS_OK : fail(c, HVS_EINVAL, std::string(fn) + ": nq is not the number of resident queries");
+}
+// ... and device buffers (`b`: a second one, or nullptr) are plain device memory of one GPU, *dev, on which the caller's work on
+// `stream` is complete
+int check_device_buffers(hvs_ctx* c, const void* a, const void* b, void* stream, const char* fn, int* dev)
+{
+    int dev2 = 0;
+    int rc = device_of_buffer(c, a, fn, dev);
+    if (!rc && b) rc = device_of_buffer(c, b, fn, &dev2);
+    if (!rc && b && *dev != dev2) rc = fail(c, HVS_EINVAL, std::string(fn) + ": the two buffers are on different GPUs");
+    return rc ? rc : wait_for_producer(c, *dev, stream);
+}
+
+// What hvs_within_stats and hvs_after_stats start with on one GPU: the call is over, *out is zeroed, and, if the call ran with the
+// feature (`on`), v holds its counters from slot `first` on
+template <typename Info, size_t N>
+int leaf_call_counters(hvs_ctx* c, Info* out, bool on, uint32_t first, unsigned long long (&v)[N])
+{
+    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    *out = Info{};
+    if (on) HVS_HIP(c, hipMemcpy(v, c->d_counters + first, sizeof(v), hipMemcpyDeviceToHost));
+    return HVS_OK;
+}
+// ... and end with: under category sets the counted slots are the sub-lists', and a query is under-full when the merge found
+// fewer than k keys
+int in_underfull(hvs_ctx* c, uint32_t* underfull)
+{
+    if (!c->qs.in.call) return HVS_OK;
+    hvs_in_info I{};
+    const int rc = leaf_in_stats(c, &I);
+    if (!rc) *underfull = I.underfull_queries;
+    return rc;
+}
+
+int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
+{
+    unsigned long long v[2] = {0, 0};
+    const int rc = leaf_call_counters(c, out, c->qs.call_capped, kCountersWithin, v);
+    if (rc || !c->qs.call_capped) return rc;
+    out->capped_queries = c->timing.nq;
+    out->within_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    return in_underfull(c, &out->underfull_queries);
+}
+
+int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
+{
+    unsigned long long v[3] = {0, 0, 0};
+    const int rc = leaf_call_counters(c, out, c->qs.call_after, kCountersAfter, v);
+    if (rc || !c->qs.call_after) return rc;
+    out->cursor_queries = c->timing.nq;
+    out->after_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    out->exhausted_queries = (uint32_t)v[2];  // (under category sets: counted per sub-query, as the slots are)
+    return in_underfull(c, &out->underfull_queries);
+}
+
+// ---- hvs_within_plan / hvs_after_plan: one row as the engines would leave it ----
+// key order of the engines: distance bits (one NaN, above +inf), then id; equal keys keep their slots' order
+struct PlanSlot {
+    uint64_t key;
+    uint32_t id;
+    float dist;
+};
+PlanSlot plan_slot(float d, uint32_t id)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &d, sizeof(bits));
+    if (d != d) {  // (the engines' keys carry one NaN)
+        bits = 0x7FC00000u;
+        std::memcpy(&d, &bits, sizeof(d));
+    }
+    return PlanSlot{((uint64_t)bits << 32) | id, id, d};
+}
+// the first k of the m slots (in key order, empty ones aside) that `keep` accepts, filled up to k with the pad rows or with empty
+// slots, sorted; returns how many were kept
+template <typename Keep>
+uint32_t plan_row(const uint32_t* ids, const float* dists, uint32_t m, uint32_t k, Keep keep, const uint32_t* pad_ids, const float* pad_dists,
+                  int padding, uint32_t* out_ids, float* out_dists)
+{
+    std::vector<PlanSlot> row;
+    row.reserve(k);
+    for (uint32_t j = 0; j < m && row.size() < k; ++j) {
+        const PlanSlot s = plan_slot(dists[j], ids[j]);
+        if (ids[j] != 0xFFFFFFFFu && keep(s)) row.push_back(s);
+    }
+    const uint32_t kept = (uint32_t)row.size();
+    for (uint32_t s = 0; kept + s < k; ++s)
+        row.push_back(padding && pad_ids && pad_dists ? plan_slot(pad_dists[s], pad_ids[s]) : PlanSlot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
+    std::stable_sort(row.begin(), row.end(), [](const PlanSlot& a, const PlanSlot& b) { return a.key < b.key; });
+    for (uint32_t j = 0; j < k; ++j) {
+        if (out_ids) out_ids[j] = row[j].id;
+        if (out_dists) out_dists[j] = row[j].dist;
+    }
+    return kept;
 }
 
 }  // namespace
@@ -4330,11 +4525,8 @@ int hvs_set_k(hvs_ctx* c, uint32_t k)
     c->k = k;
     c->cap = k <= 128u ? 256 : 512;
     // result rows change size: resident queries stay, their results do not; list workspaces are re-sized on demand
-    const uint32_t had = c->res_cap;
-    c->res_cap = 0;
-    c->in.m_cap = 0;  // (the merged rows of category sets likewise: re-allocated by the next call)
+    const uint32_t had = k_changed(c);
     c->cand_lists = 0;
-    c->timing_valid = false;
     c->rs.cut_valid = false;
     if ((rc = refresh_pad_ids(c))) return rc;
     return had ? ensure_results(c, had) : HVS_OK;
@@ -4599,7 +4791,7 @@ int hvs_export_results_device(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t* d_
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
     if (rc) return rc;
-    if (c->in.active && c->in.m_cap < (size_t)c->in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_export_results_device: no results (hvs_query_resident has not run)");
+    if (c->qs.in.active && c->qs.in.m_cap < (size_t)c->qs.in.nuq * c->k) return fail(c, HVS_ESTATE, "hvs_export_results_device: no results (hvs_query_resident has not run)");
     HVS_HIP(c, hipMemcpyAsync(d_ids, user_ids(c) + (size_t)q0 * c->k, (size_t)nq * c->k * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, c->stream));
     if (d_dists)
@@ -4644,8 +4836,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
     if (c->partitioned) {
         // all queries to every part over its own link, the resident call, each owner's merged slice home
         int rc = hvs_upload_queries(c, q_rows, nq);
-        if (!rc && max_d2) rc = hvs_set_max_dist2(c, max_d2, nq);
-        if (!rc && after_d) rc = hvs_set_after(c, after_d, after_i, nq);
+        if (!rc) rc = attach_for_call(c, max_d2, after_d, after_i, nq);
         if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
         if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
         c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -4686,8 +4877,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
                 if (r == 0u) {  // its results are already where the gather wants them: plain resident run of its slice
                     int r2 = leaf_upload_queries(k, q_rows, m);
                     if (r2) return r2;
-                    if (max_d2 && (r2 = leaf_set_caps(k, max_d2, -1, m))) return r2;
-                    if (after_d && (r2 = leaf_set_after(k, after_d, after_i, -1, m, 0u))) return r2;
+                    if ((r2 = attach_for_call(k, max_d2, after_d, after_i, m))) return r2;
                     if ((r2 = run_queries(k, 0, m, sample_proportion, NoHook{}))) return r2;
                     return leaf_sync(k);
                 }
@@ -4748,136 +4938,70 @@ int hvs_last_reruns(hvs_ctx* c, int which, uint32_t* out_idx, uint32_t cap)
 
 int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_last_timing(c, out);
-    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
     // whole-job view: device time = the slowest GPU's, work counters summed over the GPUs that took part
-    hvs_timing agg{};
-    bool any = false;
-    for (hvs_ctx* k : c->kids) {
-        if (!k->timing_valid) continue;
-        hvs_timing t{};
-        const int rc = leaf_last_timing(k, &t);
-        if (rc) return fail(c, rc, k->err);
-        agg.query_ms = std::max(agg.query_ms, t.query_ms);
-        agg.main_kernel_ms += t.main_kernel_ms;
-        agg.main_kernel_launches += t.main_kernel_launches;
-        agg.nq += t.nq;
-        agg.pairs += t.pairs;
-        agg.scanned_pairs += t.scanned_pairs;
-        agg.rescored_pairs += t.rescored_pairs;
-        agg.fallback_queries += t.fallback_queries;
-        agg.retry_queries += t.retry_queries;
-        agg.flags |= t.flags;
-        agg.untimed_launches += t.untimed_launches;
-        agg.load_ms = std::max(agg.load_ms, t.load_ms);
-        agg.engine = t.engine;
-        agg.n_gpus += 1;
-        any = true;
-    }
-    if (c->partitioned) {
-        // every part answered all the queries (a part outside the sampled prefix launched nothing); exchange and merge follow the slowest
-        agg.query_ms += c->pinfo.exchange_ms + c->pinfo.merge_ms;
-        agg.nq = c->part_call_nq;
-        agg.n_gpus = (uint32_t)c->kids.size();
-        if (!any) agg.engine = HVS_ENGINE_EXACT_SCAN;
-        any = true;
-    }
-    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
-    agg.host_ms = c->host_ms;
-    *out = agg;
-    return HVS_OK;
+    return call_stats<hvs_timing>(
+        c, out, leaf_last_timing,
+        [&](hvs_timing& agg, const hvs_timing& t) {
+            agg.query_ms = std::max(agg.query_ms, t.query_ms);
+            agg.main_kernel_ms += t.main_kernel_ms;
+            agg.main_kernel_launches += t.main_kernel_launches;
+            agg.nq += t.nq;
+            agg.pairs += t.pairs;
+            agg.scanned_pairs += t.scanned_pairs;
+            agg.rescored_pairs += t.rescored_pairs;
+            agg.fallback_queries += t.fallback_queries;
+            agg.retry_queries += t.retry_queries;
+            agg.flags |= t.flags;
+            agg.untimed_launches += t.untimed_launches;
+            agg.load_ms = std::max(agg.load_ms, t.load_ms);
+            agg.engine = t.engine;
+            agg.n_gpus += 1;
+            agg.host_ms = c->host_ms;
+        },
+        [&](hvs_timing& agg) {
+            // every part answered all the queries (a part outside the sampled prefix launched nothing); exchange and merge follow the slowest
+            agg.query_ms += c->pinfo.exchange_ms + c->pinfo.merge_ms;
+            agg.nq = c->part_call_nq;
+            if (!agg.n_gpus) agg.engine = HVS_ENGINE_EXACT_SCAN;
+            agg.n_gpus = (uint32_t)c->kids.size();
+            agg.host_ms = c->host_ms;
+        });
 }
 
 // ---- per-query distance caps (include/hvs.h "distance caps") --------------------
 
-// resident queries of the whole context
-static uint32_t resident_count(const hvs_ctx* c)
-{
-    if (c->kids.empty()) return user_nq(c);
-    return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
-}
-// caps (host memory: src_dev < 0; device memory of GPU src_dev otherwise) to every leaf: its range of them, or, on a
-// row-partitioned context, all of them
-static int set_caps_everywhere(hvs_ctx* c, const float* src, int src_dev, uint32_t nq)
-{
-    if (c->kids.empty()) return leaf_set_caps(c, src, src_dev, nq);
-    return for_each_leaf(c, [&](uint32_t r) {
-        if (!src) return leaf_set_caps(c->kids[r], nullptr, -1, 0u);
-        if (c->partitioned) return leaf_set_caps(c->kids[r], src, src_dev, nq);
-        return leaf_set_caps(c->kids[r], src + c->kid_q0[r], src_dev, c->kid_q0[r + 1] - c->kid_q0[r]);
-    });
-}
-
 int hvs_set_max_dist2(hvs_ctx* c, const float* max_d2, uint32_t nq)
 {
     if (!c) return HVS_EINVAL;
-    if (!max_d2) return set_caps_everywhere(c, nullptr, -1, 0u);
-    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_max_dist2: nq is not the number of resident queries");
-    return set_caps_everywhere(c, max_d2, -1, nq);
+    if (!max_d2) return attach_everywhere(c, PerQuery::Caps, nullptr, nullptr, -1, 0u);
+    if (int rc = check_resident_count(c, nq, "hvs_set_max_dist2")) return rc;
+    return attach_everywhere(c, PerQuery::Caps, max_d2, nullptr, -1, nq);
 }
 
 int hvs_set_max_dist2_device(hvs_ctx* c, const float* d_max_d2, uint32_t nq, void* stream)
 {
     if (!c) return HVS_EINVAL;
-    if (!d_max_d2) return set_caps_everywhere(c, nullptr, -1, 0u);
-    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_max_dist2_device: nq is not the number of resident queries");
-    int dev = 0;
-    if (nq) {  // (an empty set reads nothing)
-        int rc = device_of_buffer(c, d_max_d2, "hvs_set_max_dist2_device", &dev);
-        if (!rc) rc = wait_for_producer(c, dev, stream);
-        if (rc) return rc;
-    }
-    return set_caps_everywhere(c, d_max_d2, dev, nq);
-}
-
-static int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
-{
-    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    int rc = leaf_sync(c);
-    if (rc) return rc;
-    *out = hvs_within_info{};
-    if (!c->call_capped) return HVS_OK;
-    unsigned long long v[2] = {0, 0};
-    HVS_HIP(c, hipMemcpy(v, c->d_counters + 14, sizeof(v), hipMemcpyDeviceToHost));
-    out->capped_queries = c->timing.nq;
-    out->within_slots = v[0];
-    out->underfull_queries = (uint32_t)v[1];
-    if (c->in.call) {  // category sets: the slots are the sub-lists', a query is under-full when the merge found fewer than k keys
-        hvs_in_info I{};
-        if ((rc = leaf_in_stats(c, &I))) return rc;
-        out->underfull_queries = I.underfull_queries;
-    }
-    return HVS_OK;
+    if (!d_max_d2) return attach_everywhere(c, PerQuery::Caps, nullptr, nullptr, -1, 0u);
+    int dev = 0, rc = check_resident_count(c, nq, "hvs_set_max_dist2_device");
+    if (!rc && nq) rc = check_device_buffers(c, d_max_d2, nullptr, stream, "hvs_set_max_dist2_device", &dev);  // (an empty set reads nothing)
+    return rc ? rc : attach_everywhere(c, PerQuery::Caps, d_max_d2, nullptr, dev, nq);
 }
 
 int hvs_within_stats(hvs_ctx* c, hvs_within_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_within_stats(c, out);
-    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    hvs_within_info agg{};
-    bool any = false;
-    for (hvs_ctx* k : c->kids) {
-        if (!k->timing_valid) continue;  // (took no part in the last call)
-        hvs_within_info m{};
-        const int rc = leaf_within_stats(k, &m);
-        if (rc) return fail(c, rc, k->err);
-        agg.capped_queries += m.capped_queries;
-        agg.underfull_queries += m.underfull_queries;
-        agg.within_slots += m.within_slots;
-        any = true;
-    }
-    if (c->partitioned) {
-        // every part answered all the queries: the parts' slots are summed, the queries are the call's, and a query is under-full
-        // when the merge found fewer than k keys in all parts together
-        agg.capped_queries = c->call_capped ? c->part_call_nq : 0u;
-        agg.underfull_queries = c->call_capped ? c->pinfo.padded_queries : 0u;
-        any = true;
-    }
-    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
-    *out = agg;
-    return HVS_OK;
+    return call_stats<hvs_within_info>(
+        c, out, leaf_within_stats,
+        [](hvs_within_info& sum, const hvs_within_info& m) {
+            sum.capped_queries += m.capped_queries;
+            sum.underfull_queries += m.underfull_queries;
+            sum.within_slots += m.within_slots;
+        },
+        [&](hvs_within_info& sum) {
+            // the parts' slots are summed, the queries are the call's, and a query is under-full when the merge found fewer than
+            // k keys in all parts together
+            sum.capped_queries = c->qs.call_capped ? c->part_call_nq : 0u;
+            sum.underfull_queries = c->qs.call_capped ? c->pinfo.padded_queries : 0u;
+        });
 }
 
 void hvs_within_plan(const uint32_t* ids, const float* dists, uint32_t k, float max_d2, const uint32_t* pad_ids, const float* pad_dists,
@@ -4885,81 +5009,29 @@ void hvs_within_plan(const uint32_t* ids, const float* dists, uint32_t k, float 
 {
     if (!ids || !dists) return;
     const float cap = hvs_norm_cap(max_d2);
-    // key order of the engines: distance bits (NaN canonical, above +inf), then id; equal keys keep their slots' order
-    struct Slot {
-        uint64_t key;
-        uint32_t id;
-        float dist;
-    };
-    std::vector<Slot> row;
-    row.reserve(k);
-    for (uint32_t j = 0; j < k; ++j)
-        if (ids[j] != 0xFFFFFFFFu && dists[j] <= cap) {
-            uint32_t bits;
-            std::memcpy(&bits, &dists[j], sizeof(bits));
-            row.push_back(Slot{((uint64_t)bits << 32) | ids[j], ids[j], dists[j]});
-        }
-    const uint32_t within = (uint32_t)row.size();
+    const uint32_t within = plan_row(ids, dists, k, k, [&](const PlanSlot& s) { return s.dist <= cap; }, pad_ids, pad_dists, padding, out_ids, out_dists);
     if (n_within) *n_within = within;
-    for (uint32_t s = 0; within + s < k; ++s) {
-        if (padding && pad_ids && pad_dists) {
-            float d = pad_dists[s];
-            uint32_t bits;
-            std::memcpy(&bits, &d, sizeof(bits));
-            if (d != d) {  // (the engines' keys carry one NaN)
-                bits = 0x7FC00000u;
-                std::memcpy(&d, &bits, sizeof(d));
-            }
-            row.push_back(Slot{((uint64_t)bits << 32) | pad_ids[s], pad_ids[s], d});
-        } else {
-            row.push_back(Slot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
-        }
-    }
-    std::stable_sort(row.begin(), row.end(), [](const Slot& a, const Slot& b) { return a.key < b.key; });
-    for (uint32_t j = 0; j < k; ++j) {
-        if (out_ids) out_ids[j] = row[j].id;
-        if (out_dists) out_dists[j] = row[j].dist;
-    }
 }
 
 // ---- per-query result cursors (include/hvs.h "per-query result cursors") --------
 
-// cursors (host memory: src_dev < 0; device memory of GPU src_dev otherwise) to every leaf: its range of them, or, on a
-// row-partitioned context, all of them, seen from the part's first row
-static int set_after_everywhere(hvs_ctx* c, const float* dists, const uint32_t* ids, int src_dev, uint32_t nq)
-{
-    if (c->kids.empty()) return leaf_set_after(c, dists, ids, src_dev, nq, 0u);
-    return for_each_leaf(c, [&](uint32_t r) {
-        if (!dists) return leaf_set_after(c->kids[r], nullptr, nullptr, -1, 0u, 0u);
-        if (c->partitioned) return leaf_set_after(c->kids[r], dists, ids, src_dev, nq, c->part_row0.size() > r ? c->part_row0[r] : 0u);
-        return leaf_set_after(c->kids[r], dists + c->kid_q0[r], ids + c->kid_q0[r], src_dev, c->kid_q0[r + 1] - c->kid_q0[r], 0u);
-    });
-}
-
 int hvs_set_after(hvs_ctx* c, const float* after_dists, const uint32_t* after_ids, uint32_t nq)
 {
     if (!c) return HVS_EINVAL;
-    if (!after_dists && !after_ids) return set_after_everywhere(c, nullptr, nullptr, -1, 0u);
+    if (!after_dists && !after_ids) return attach_everywhere(c, PerQuery::Cursors, nullptr, nullptr, -1, 0u);
     if (!after_dists || !after_ids) return fail(c, HVS_EINVAL, "hvs_set_after: one of after_dists / after_ids is NULL");
-    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_after: nq is not the number of resident queries");
-    return set_after_everywhere(c, after_dists, after_ids, -1, nq);
+    if (int rc = check_resident_count(c, nq, "hvs_set_after")) return rc;
+    return attach_everywhere(c, PerQuery::Cursors, after_dists, after_ids, -1, nq);
 }
 
 int hvs_set_after_device(hvs_ctx* c, const float* d_after_dists, const uint32_t* d_after_ids, uint32_t nq, void* stream)
 {
     if (!c) return HVS_EINVAL;
-    if (!d_after_dists && !d_after_ids) return set_after_everywhere(c, nullptr, nullptr, -1, 0u);
+    if (!d_after_dists && !d_after_ids) return attach_everywhere(c, PerQuery::Cursors, nullptr, nullptr, -1, 0u);
     if (!d_after_dists || !d_after_ids) return fail(c, HVS_EINVAL, "hvs_set_after_device: one of d_after_dists / d_after_ids is NULL");
-    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_after_device: nq is not the number of resident queries");
-    int dev = 0, dev2 = 0;
-    if (nq) {  // (an empty set reads nothing)
-        int rc = device_of_buffer(c, d_after_dists, "hvs_set_after_device", &dev);
-        if (!rc) rc = device_of_buffer(c, d_after_ids, "hvs_set_after_device", &dev2);
-        if (!rc && dev != dev2) rc = fail(c, HVS_EINVAL, "hvs_set_after_device: the two buffers are on different GPUs");
-        if (!rc) rc = wait_for_producer(c, dev, stream);
-        if (rc) return rc;
-    }
-    return set_after_everywhere(c, d_after_dists, d_after_ids, dev, nq);
+    int dev = 0, rc = check_resident_count(c, nq, "hvs_set_after_device");
+    if (!rc && nq) rc = check_device_buffers(c, d_after_dists, d_after_ids, stream, "hvs_set_after_device", &dev);  // (an empty set reads nothing)
+    return rc ? rc : attach_everywhere(c, PerQuery::Cursors, d_after_dists, d_after_ids, dev, nq);
 }
 
 int hvs_set_after_from_results(hvs_ctx* c)
@@ -4981,7 +5053,7 @@ int hvs_set_after_from_results(hvs_ctx* c)
     // takes its queries' last slots, every part fetches each owner's piece with device-to-device copies on its own stream
     // (8 bytes per query, like the list exchange) and builds its cursors as seen from its first row.
     const uint32_t nq = c->kid_q0.back(), K = c->k;
-    if (!c->part_timing_valid || c->res_gen != c->kids[0]->set_gen || c->res_k != K || c->res_lo != 0u || c->res_hi < nq)
+    if (!c->part_timing_valid || c->qs.res_gen != c->kids[0]->qs.set_gen || !c->qs.covers(nq, K))
         return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no results for all resident queries");
     int rc = for_each_leaf(c, [&](uint32_t r) -> int {
         hvs_ctx* k = c->kids[r];
@@ -4991,7 +5063,7 @@ int hvs_set_after_from_results(hvs_ctx* c)
         const uint32_t a = c->kid_q0[r], own = c->kid_q0[r + 1] - a;
         if (own) {
             hipLaunchKernelGGL(hvs_k_after_from_results, dim3(hvs_ceil_div(own, 256u)), dim3(256), 0, k->stream, k->part.d_m_ids, k->part.d_m_dists,
-                               own, K, k->d_after_dist + a, k->d_after_id + a);
+                               own, K, k->qs.eng.d_after_dist + a, k->qs.eng.d_after_id + a);
             HVS_HIP(k, hipGetLastError());
         }
         HVS_HIP(k, hipStreamSynchronize(k->stream));
@@ -5005,71 +5077,37 @@ int hvs_set_after_from_results(hvs_ctx* c)
                 const uint32_t a = c->kid_q0[p], own = c->kid_q0[p + 1] - a;
                 if (p == r || own == 0u) continue;
                 const hvs_ctx* src = c->kids[p];
-                HVS_HIP(k, hipMemcpyPeerAsync(k->d_after_dist + a, k->device, src->d_after_dist + a, src->device, (size_t)own * sizeof(float), k->stream));
-                HVS_HIP(k, hipMemcpyPeerAsync(k->d_after_id + a, k->device, src->d_after_id + a, src->device, (size_t)own * sizeof(uint32_t), k->stream));
+                HVS_HIP(k, hipMemcpyPeerAsync(k->qs.eng.d_after_dist + a, k->device, src->qs.eng.d_after_dist + a, src->device, (size_t)own * sizeof(float), k->stream));
+                HVS_HIP(k, hipMemcpyPeerAsync(k->qs.eng.d_after_id + a, k->device, src->qs.eng.d_after_id + a, src->device, (size_t)own * sizeof(uint32_t), k->stream));
             }
-            return leaf_commit_after(k, nq, c->part_row0[r]);
+            return leaf_attach(k, PerQuery::Cursors, PerQuerySource{PerQuerySource::InPlace}, nq, c->part_row0[r]);
         });
     if (rc) {
         part_quiesce(c);
-        for (hvs_ctx* k : c->kids) k->after_set = false;  // (some parts may hold the new cursors and some the old: none is in force)
+        for (hvs_ctx* k : c->kids) k->qs.after_set = false;  // (some parts may hold the new cursors and some the old: none is in force)
     }
     return rc;
 }
 
-static int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
-{
-    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    int rc = leaf_sync(c);
-    if (rc) return rc;
-    *out = hvs_after_info{};
-    if (!c->call_after) return HVS_OK;
-    unsigned long long v[3] = {0, 0, 0};
-    HVS_HIP(c, hipMemcpy(v, c->d_counters + 16, sizeof(v), hipMemcpyDeviceToHost));
-    out->cursor_queries = c->timing.nq;
-    out->after_slots = v[0];
-    out->underfull_queries = (uint32_t)v[1];
-    out->exhausted_queries = (uint32_t)v[2];
-    if (c->in.call) {  // category sets, by the rules of leaf_within_stats (exhausted cursors are counted per sub-query, as the slots are)
-        hvs_in_info I{};
-        if ((rc = leaf_in_stats(c, &I))) return rc;
-        out->underfull_queries = I.underfull_queries;
-    }
-    return HVS_OK;
-}
-
 int hvs_after_stats(hvs_ctx* c, hvs_after_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_after_stats(c, out);
-    if (c->partitioned && !c->part_timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    hvs_after_info agg{};
     uint32_t part_exhausted = 0;
-    bool any = false;
-    for (hvs_ctx* k : c->kids) {
-        if (!k->timing_valid) continue;  // (took no part in the last call)
-        hvs_after_info m{};
-        const int rc = leaf_after_stats(k, &m);
-        if (rc) return fail(c, rc, k->err);
-        agg.cursor_queries += m.cursor_queries;
-        agg.exhausted_queries += m.exhausted_queries;
-        agg.underfull_queries += m.underfull_queries;
-        agg.after_slots += m.after_slots;
-        part_exhausted = std::max(part_exhausted, m.exhausted_queries);
-        any = true;
-    }
-    if (c->partitioned) {
-        // the rules of hvs_within_stats: the parts' slots are summed, the queries are the call's, a query is under-full when the
-        // merge found fewer than k keys in all parts together; every part saw every cursor, so one part's count of exhausted ones
-        const bool on = c->call_after;
-        agg.cursor_queries = on ? c->part_call_nq : 0u;
-        agg.underfull_queries = on ? c->pinfo.padded_queries : 0u;
-        agg.exhausted_queries = on ? part_exhausted : 0u;
-        any = true;
-    }
-    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
-    *out = agg;
-    return HVS_OK;
+    return call_stats<hvs_after_info>(
+        c, out, leaf_after_stats,
+        [&](hvs_after_info& sum, const hvs_after_info& m) {
+            sum.cursor_queries += m.cursor_queries;
+            sum.exhausted_queries += m.exhausted_queries;
+            sum.underfull_queries += m.underfull_queries;
+            sum.after_slots += m.after_slots;
+            part_exhausted = std::max(part_exhausted, m.exhausted_queries);
+        },
+        [&](hvs_after_info& sum) {
+            // the rules of hvs_within_stats; every part saw every cursor, so one part's count of exhausted ones
+            const bool on = c->qs.call_after;
+            sum.cursor_queries = on ? c->part_call_nq : 0u;
+            sum.underfull_queries = on ? c->pinfo.padded_queries : 0u;
+            sum.exhausted_queries = on ? part_exhausted : 0u;
+        });
 }
 
 void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_t k, float after_dist, uint32_t after_id, const uint32_t* pad_ids,
@@ -5077,39 +5115,8 @@ void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_
 {
     if (m && (!ids || !dists)) return;
     const uint64_t lo = hvs_after_lo(after_dist, after_id, 0u);
-    struct Slot {
-        uint64_t key;
-        uint32_t id;
-        float dist;
-    };
-    auto slot_of = [](float d, uint32_t id) {
-        uint32_t bits;
-        std::memcpy(&bits, &d, sizeof(bits));
-        if (d != d) {  // (the engines' keys carry one NaN)
-            bits = 0x7FC00000u;
-            std::memcpy(&d, &bits, sizeof(d));
-        }
-        return Slot{((uint64_t)bits << 32) | id, id, d};
-    };
-    std::vector<Slot> row;
-    row.reserve(k);
-    for (uint32_t j = 0; j < m && row.size() < k; ++j) {  // (key order: the first k behind the cursor)
-        const Slot s = slot_of(dists[j], ids[j]);
-        if (ids[j] != 0xFFFFFFFFu && s.key >= lo) row.push_back(s);
-    }
-    const uint32_t after = (uint32_t)row.size();
+    const uint32_t after = plan_row(ids, dists, m, k, [&](const PlanSlot& s) { return s.key >= lo; }, pad_ids, pad_dists, padding, out_ids, out_dists);
     if (n_after) *n_after = after;
-    for (uint32_t s = 0; after + s < k; ++s) {
-        if (padding && pad_ids && pad_dists)
-            row.push_back(slot_of(pad_dists[s], pad_ids[s]));
-        else
-            row.push_back(Slot{~0ull, 0xFFFFFFFFu, __builtin_inff()});
-    }
-    std::stable_sort(row.begin(), row.end(), [](const Slot& a, const Slot& b) { return a.key < b.key; });
-    for (uint32_t j = 0; j < k; ++j) {
-        if (out_ids) out_ids[j] = row[j].id;
-        if (out_dists) out_dists[j] = row[j].dist;
-    }
 }
 
 // ---- category sets (include/hvs.h "category sets") -------------------------------
@@ -5127,16 +5134,14 @@ int hvs_set_category_sets(hvs_ctx* c, const uint32_t* set_offsets, const float* 
     if (!set_offsets && !set_values) return on_every_leaf(c, in_detach);
     if (!loaded_leaf(c, "hvs_set_category_sets")) return HVS_ESTATE;
     if (!set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets: set_offsets is NULL");
-    if (nq != resident_count(c)) return fail(c, HVS_EINVAL, "hvs_set_category_sets: nq is not the number of resident queries");
+    if (int rc = check_resident_count(c, nq, "hvs_set_category_sets")) return rc;
     if (nq == 0u) return on_every_leaf(c, in_detach);
     // format and limits hold whatever the queries' types; the sub-query count is the largest when every query tests C
     if (hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
         return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
-    if (c->kids.empty()) return in_attach(c, set_offsets, set_values, nq);
-    const int rc = for_each_leaf(c, [&](uint32_t r) {  // owner ranges stay cut by user queries: each GPU takes its slice of the CSR
-        return in_attach(c->kids[r], set_offsets + c->kid_q0[r], set_values, c->kid_q0[r + 1] - c->kid_q0[r]);
-    });
-    if (rc) {
+    // owner ranges stay cut by user queries: each GPU takes its slice of the CSR
+    const int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return in_attach(k, set_offsets + first, set_values, m); });
+    if (rc && !c->kids.empty()) {
         // one GPU could not attach (no room): no GPU stays under sets -- the context answers plain queries on every GPU whose
         // query buffer survived (in_attach), and the failing GPU's error is the call's
         const std::string err = c->err;
@@ -5168,28 +5173,16 @@ int hvs_query_in(hvs_ctx* c, const float* q_rows, const uint32_t* set_offsets, c
 
 int hvs_in_stats(hvs_ctx* c, hvs_in_info* out)
 {
-    if (!c || !out) return HVS_EINVAL;
-    if (c->kids.empty()) return leaf_in_stats(c, out);
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_in_stats: not supported (yet) on a row-partitioned context");
-    hvs_in_info agg{};
-    bool any = false;
-    for (hvs_ctx* k : c->kids) {
-        if (!k->timing_valid) continue;  // (took no part in the last call)
-        hvs_in_info m{};
-        const int rc = leaf_in_stats(k, &m);
-        if (rc) return fail(c, rc, k->err);
-        agg.set_queries += m.set_queries;
-        agg.sub_queries += m.sub_queries;
-        agg.max_set = std::max(agg.max_set, m.max_set);
-        agg.underfull_queries += m.underfull_queries;
-        agg.merged_keys += m.merged_keys;
-        agg.expand_ms = std::max(agg.expand_ms, m.expand_ms);
-        agg.merge_ms = std::max(agg.merge_ms, m.merge_ms);
-        any = true;
-    }
-    if (!any) return fail(c, HVS_ESTATE, "no query has run yet");
-    *out = agg;
-    return HVS_OK;
+    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_in_stats: not supported (yet) on a row-partitioned context");
+    return call_stats<hvs_in_info>(c, out, leaf_in_stats, [](hvs_in_info& sum, const hvs_in_info& m) {
+        sum.set_queries += m.set_queries;
+        sum.sub_queries += m.sub_queries;
+        sum.max_set = std::max(sum.max_set, m.max_set);
+        sum.underfull_queries += m.underfull_queries;
+        sum.merged_keys += m.merged_keys;
+        sum.expand_ms = std::max(sum.expand_ms, m.expand_ms);
+        sum.merge_ms = std::max(sum.merge_ms, m.merge_ms);
+    });
 }
 
 // ---- live-row mask ---------------------------------------------------------------------------

@@ -1,0 +1,81 @@
+"""What is attached to the resident queries, as a pure function (DESIGN 3.13a "Resident-query state"): the transition table
+of the host's HvsQuerySet restated over four facts -- category sets, distance caps, result cursors, and whether every resident
+query has a result row at the current k -- and a fifth beside them: whether the last call's figures can still be asked for.
+tests/test_queryset_model_cpu.py pins the table row by row; tests/test_queryset_walk.py walks one GPU context through it and
+compares every answer with a fresh context given only what the model says is attached.
+
+A call is a tuple:
+    ("upload", tag)            hvs_upload_queries of the query rows named `tag`
+    ("query", tag)             hvs_query: the same, and all of them answered
+    ("sets", tag | None)       hvs_set_category_sets (None: detach)
+    ("bad_sets",)              ... with sets the library refuses (HVS_EINVAL)
+    ("caps", tag | None)       hvs_set_max_dist2
+    ("after", tag | None)      hvs_set_after
+    ("after_from_results",)    hvs_set_after_from_results (padding off)
+    ("set_k", k)               hvs_set_k
+    ("run", q0, nq)            hvs_query_resident
+
+`step` returns the next state and the call's status: OK, EINVAL or ESTATE.  A refused call leaves the state as it was.
+
+Three cells of the table that are easy to get wrong, read from the code:
+  - detaching sets from a context that has none is a no-op: caps, cursors and results stay;
+  - caps and cursors survive hvs_set_k, the results do not;
+  - attaching or removing caps or cursors leaves the result range alone (the rows are still those of the earlier call), so
+    hvs_set_after_from_results may follow them.
+The result range is one interval: a call's range joins it when the two touch and replaces it otherwise.  (A multi-GPU context
+keeps one interval per GPU, in that GPU's own query numbers: the walks stay clear of sequences where that shows.  The library
+tells a k that changed by comparing the range's k with the current one, so k -> k' -> k without a call in between would find
+the old range again; the model calls the results gone, and no walk goes there.)"""
+from collections import namedtuple
+
+OK, EINVAL, ESTATE = 0, -1, -4
+FROM_RESULTS = "from results"   # cursors: the last slot of each query's current result row
+
+# queries: tag of the resident rows; nq: their number; sets / caps / cursors: tag of what is attached (None: nothing);
+# k: slots per result row; res: the answered interval (lo, hi) at this k, or None
+# timed: the last call's figures (hvs_last_timing, hvs_within_stats, ...) can be asked for
+State = namedtuple("State", "queries nq sets caps cursors k res timed", defaults=[True])
+
+
+def initial(k=100):
+    return State(None, 0, None, None, None, k, None, False)
+
+
+def full(s):
+    """every resident query has a result row at the current k (what hvs_set_after_from_results needs); at least one query"""
+    return s.res is not None and s.res[0] == 0 and s.res[1] >= s.nq
+
+
+def _answered(s, q0, nq):
+    lo, hi = q0, q0 + nq
+    if s.res is not None and s.res[0] < s.res[1] and not (lo > s.res[1] or hi < s.res[0]):
+        lo, hi = min(lo, s.res[0]), max(hi, s.res[1])
+    return s._replace(res=(lo, hi), timed=True)
+
+
+def step(s, call, nq_of=None):
+    """(state, call) -> (state, status).  `nq_of`: tag -> number of query rows (for "upload" / "query")."""
+    op = call[0]
+    if op in ("upload", "query"):
+        n = nq_of[call[1]] if nq_of else s.nq
+        s = s._replace(queries=call[1], nq=n, sets=None, caps=None, cursors=None, res=None)
+        return (_answered(s, 0, n) if op == "query" else s), OK
+    if op == "sets":
+        if call[1] is None and s.sets is None:
+            return s, OK
+        return s._replace(sets=call[1], caps=None, cursors=None, res=None, timed=False), OK
+    if op == "bad_sets":
+        return s, EINVAL
+    if op == "caps":
+        return s._replace(caps=call[1]), OK
+    if op == "after":
+        return s._replace(cursors=call[1]), OK
+    if op == "after_from_results":
+        return (s._replace(cursors=FROM_RESULTS), OK) if full(s) else (s, ESTATE)
+    if op == "set_k":
+        return (s, OK) if call[1] == s.k else (s._replace(k=call[1], res=None, timed=False), OK)
+    if op == "run":
+        if call[1] + call[2] > s.nq:
+            return s, EINVAL
+        return _answered(s, call[1], call[2]), OK
+    raise ValueError(f"unknown call {call!r}")

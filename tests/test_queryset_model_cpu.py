@@ -1,0 +1,107 @@
+"""The transition table of the resident-query state, pinned row by row on tests/queryset_model.py."""
+import pytest
+
+import queryset_model as M
+
+NQ = {"Q": 80, "Q2": 80, "short": 30}
+EVERYTHING = M.State("Q", 80, "S", "C", "A", 8, (0, 80))       # sets, caps, cursors, full results
+PLAIN_FULL = M.State("Q", 80, None, None, None, 8, (0, 80))
+
+
+def go(s, *calls):
+    for call in calls:
+        s, rc = M.step(s, call, NQ)
+        assert rc == M.OK, call
+    return s
+
+
+def attached(s):
+    return (s.sets, s.caps, s.cursors, M.full(s))
+
+
+def test_the_start():
+    s = M.initial()
+    assert attached(s) == (None, None, None, False) and s.k == 100 and not s.timed
+
+
+@pytest.mark.parametrize("call", [("upload", "Q2"), ("upload", "short")])
+def test_row_resident_set_replaced(call):
+    s = go(EVERYTHING, call)
+    assert attached(s) == (None, None, None, False)
+    assert (s.queries, s.nq, s.k) == (call[1], NQ[call[1]], 8)
+    assert s.timed                                               # (the last call's figures outlive its queries)
+
+
+def test_row_hvs_query_replaces_the_set_and_answers_it():
+    s = go(EVERYTHING, ("query", "short"))
+    assert attached(s) == (None, None, None, True) and s.nq == 30
+
+
+def test_row_sets_attached():
+    s = go(EVERYTHING, ("sets", "S2"))
+    assert attached(s) == ("S2", None, None, False) and not s.timed
+    s = go(M.State("Q", 80, None, "C", "A", 8, (0, 80)), ("sets", "S"))
+    assert attached(s) == ("S", None, None, False)
+
+
+def test_row_sets_detached():
+    s = go(EVERYTHING, ("sets", None))
+    assert attached(s) == (None, None, None, False) and not s.timed
+
+
+def test_row_detach_without_sets_is_a_no_op():
+    s = M.State("Q", 80, None, "C", "A", 8, (0, 80))
+    assert go(s, ("sets", None)) == s
+
+
+def test_row_refused_sets_change_nothing():
+    for s in (EVERYTHING, PLAIN_FULL, M.initial()):
+        assert M.step(s, ("bad_sets",), NQ) == (s, M.EINVAL)
+
+
+def test_rows_caps_and_cursors_touch_only_themselves():
+    s = go(EVERYTHING, ("caps", "C2"))
+    assert s == EVERYTHING._replace(caps="C2")
+    s = go(EVERYTHING, ("caps", None))
+    assert s == EVERYTHING._replace(caps=None)
+    s = go(EVERYTHING, ("after", "A2"))
+    assert s == EVERYTHING._replace(cursors="A2")
+    s = go(EVERYTHING, ("after", None))
+    assert s == EVERYTHING._replace(cursors=None)
+
+
+def test_row_k_changed():
+    s = go(EVERYTHING, ("set_k", 100))
+    assert attached(s) == ("S", "C", "A", False) and s.k == 100 and not s.timed
+    assert go(s, ("run", 0, 80)).timed
+    assert go(EVERYTHING, ("set_k", 8)) == EVERYTHING            # (the same k: nothing happens)
+
+
+def test_row_call_answered_joins_or_replaces():
+    s = go(PLAIN_FULL, ("upload", "Q"))
+    s = go(s, ("run", 20, 30))
+    assert s.res == (20, 50) and not M.full(s)
+    assert go(s, ("run", 50, 30)).res == (20, 80)                # touches at the end: joined
+    assert go(s, ("run", 0, 20)).res == (0, 50)                  # touches at the start: joined
+    assert go(s, ("run", 30, 40)).res == (20, 70)                # overlaps: joined
+    assert go(s, ("run", 60, 20)).res == (60, 80)                # apart: replaced
+    assert go(s, ("run", 0, 10)).res == (0, 10)
+    t = go(s, ("run", 50, 30), ("run", 0, 20))
+    assert t.res == (0, 80) and M.full(t)
+    assert attached(go(EVERYTHING, ("run", 10, 5))) == ("S", "C", "A", True)   # a call keeps what is attached, and the rows it had
+    assert M.step(PLAIN_FULL, ("run", 70, 11), NQ) == (PLAIN_FULL, M.EINVAL)
+
+
+def test_row_cursors_from_results():
+    s, rc = M.step(EVERYTHING, ("after_from_results",), NQ)
+    assert rc == M.OK and s == EVERYTHING._replace(cursors=M.FROM_RESULTS)
+    for t in (go(EVERYTHING, ("set_k", 100)), go(EVERYTHING, ("sets", None)), go(EVERYTHING, ("upload", "Q")),
+              go(PLAIN_FULL, ("upload", "Q"), ("run", 20, 30)), M.initial()._replace(queries="Q", nq=80)):
+        assert M.step(t, ("after_from_results",), NQ) == (t, M.ESTATE)
+    # caps and cursors do not take the results away
+    assert M.step(go(PLAIN_FULL, ("caps", "C"), ("after", "A")), ("after_from_results",), NQ)[1] == M.OK
+
+
+def test_unknown_call():
+    with pytest.raises(ValueError):
+        M.step(M.initial(), ("nonsense",))
