@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cctype>
 #include <cstdio>
@@ -245,8 +246,8 @@ struct HvsInSet {
 };
 
 // What is ATTACHED to the resident queries of one GPU: caps, cursors, category sets and the range of queries that
-// have a result row.  The engines' own buffers -- d_q, nq, nq_cap, d_out_ids, d_out_dists, res_cap, d_ovf_list, d_retry_list --
-// stay in hvs_ctx: every launch reads them and the planner probe lends them out.  The invariants:
+// have a result row.  The engines' own buffers -- d_q, nq, nq_cap, d_out_ids, d_out_dists, res_cap -- stay in hvs_ctx: every
+// launch reads them and the planner probe lends them out (with the two re-run lists, which HvsCallState owns).  The invariants:
 //   - while caps_set is false no launch reads eng.d_max_d2, while after_set is false none reads eng.d_after_*
 //   - eng.d_max_d2 grows with d_q; the cursor arrays, once allocated, have room for eng.after_cap entries, >= nq whenever after_set
 //   - while in.active, `eng` holds the EXPANDED values, one entry per sub-query, and in.user one entry per user query
@@ -283,8 +284,46 @@ struct HvsQuerySet {
     bool covers(uint32_t nq, uint32_t k) const { return res_k == k && res_lo == 0u && res_hi >= nq; }
 };
 
-#define HVS_NCOUNTERS 20  // ([14], [15]: hvs_keep_within; [16] .. [18]: hvs_keep_after)
-constexpr uint32_t kCountersWithin = 14, kCountersAfter = 16;  // first slot of the figures of hvs_within_stats / hvs_after_stats
+// What a call LEAVES BEHIND on one GPU until the next one: the device counters its kernels added to, the queries
+// it could not answer with their re-runs, and the report that hvs_last_timing and the *_stats calls read.  The invariants:
+//   - `valid`: a call has been enqueued (call_enqueued) since the last event that forgets it (call_forgotten, or a later call that
+//     failed half-way).  While it is false every per-call figure reads as zero or HVS_ESTATE (call_counters, call_required);
+//     hvs_last_reruns alone does not ask.
+//   - `pending`: from "a call is enqueued on a filter engine" until resolve_overflow has run.  While it is true h_ovf may not have
+//     arrived, pend_sn is the cut the re-runs use, and nothing reads timing.fallback_queries / retry_queries (the only copy of the
+//     re-run counts) or demoted_queries.  What changes rows, index or k -- so every planner probe -- resolves first.
+//   - d_ovf_list and d_retry_list hold resident query indices, with room for hvs_ctx::res_cap (ensure_results grows them with the
+//     result rows); d_demote_list has room for demote_cap; d_ovf_count[0..1] are the two lists' lengths on the device.  The
+//     planner probe lends d_q, d_out_* and the two lists for its own batch: the caller's survive it.
+//   - d_counters (HVS_CNT_COUNT slots, hvs_device.h) are zeroed by call_begin and by the probe (counters_begin), by nothing else.
+//     The filters' re-run batches add to SCANNED, RESCORED and the slots of caps and cursors (the retry pass is the call's work),
+//     not to PAIRS nor to the tail and stale slots; the exact engine's re-runs send PAIRS and SCANNED to HVS_CNT_RERUN_SINK.
+// It changes through call_begin, call_enqueued, call_forgotten, resolve_overflow and the launch timers.  ev_q0 / ev_q1 are also the
+// stopwatch of loads, index builds and compactions.  A ROOT (multi-GPU or row-partitioned) uses host_ms and nothing else.
+struct HvsCallState {
+    unsigned long long* d_counters = nullptr;
+    // queries without a usable bound or whose lists overflowed (-> exact engine) and queries whose guessed threshold failed its
+    // check (-> a filter batch with proven thresholds), collected over all batches of a call on the device
+    uint32_t *d_ovf_list = nullptr, *d_retry_list = nullptr, *d_ovf_count = nullptr;
+    uint32_t* d_demote_list = nullptr;  // a call's exact list, moved aside when the tile format changes under it
+    uint32_t demote_cap = 0, demoted_queries = 0;
+    uint32_t* h_ovf = nullptr;  // pinned: [0] exact, [1] retry
+    bool pending = false;
+    uint32_t pend_sn = 0;
+    hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+    std::vector<hipEvent_t> ev_k;  // start/stop pairs around the dominant kernel's launches (grown on demand: 10^7 queries are 10 batches x 14 levels)
+    int n_launch_events = 0;       // pairs used by the current call
+    bool valid = false;
+    hvs_timing timing{};
+    double host_ms = 0.0;  // wall time of the last hvs_query (host memory in -> host memory out)
+    // the queries the last call answered a second time as (device list, length), in the order their rows are fetched
+    using Reruns = std::pair<const uint32_t*, uint32_t>;
+    std::array<Reruns, 3> reruns() const  // exact, retry, demoted
+    {
+        return {{{d_ovf_list, timing.fallback_queries}, {d_retry_list, timing.retry_queries}, {d_demote_list, demoted_queries}}};
+    }
+};
+
 struct hvs_ctx : HvsLane {
     int device = 0;
     HvsLane spare;                 // the second lane (its buffers are allocated by the first call that has two batches)
@@ -321,8 +360,7 @@ struct hvs_ctx : HvsLane {
     float* d_out_dists = nullptr;
     uint32_t res_cap = 0;
     HvsQuerySet qs;
-
-    unsigned long long* d_counters = nullptr;  // HVS_NCOUNTERS of them, zeroed at the start of every call
+    HvsCallState call;  // what the last call left behind: counters, re-run lists, the report
 
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
@@ -340,31 +378,9 @@ struct hvs_ctx : HvsLane {
     bool index_too_large = false;  // more than 2^27 rows: no filter index (hvs_timing.flags says so)
     // (the per-batch state of the filter engines lives in the lanes)
     int num_cus = 256;
-    uint32_t *d_ovf_list = nullptr, *d_ovf_count = nullptr;      // queries for the exact engine; d_ovf_count[0..1] = exact, retry
-    uint32_t* d_retry_list = nullptr;                            // queries whose guessed threshold was not verified
-    uint32_t* d_demote_list = nullptr;                           // a call's exact list, moved aside when the tile format changes under it
-    uint32_t demote_cap = 0, demoted_queries = 0;
-    uint32_t fallback_queries = 0, retry_queries = 0;
     HvsGuessTable guess_tab[13]{};  // order statistics of the guessed thresholds for k = guess_k: [0] proven (retry batches),
     bool guess_have[13] = {};       // [p] failure target 10^-p
     uint32_t guess_k = 0;
-
-    hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
-    // start/stop event pairs around the dominant kernel's launches of the current call (grown on demand: a call
-    // of 10^7 queries is 10 batches x 14 levels)
-    std::vector<hipEvent_t> ev_k;
-    int n_launch_events = 0;  // pairs used by the current call
-    uint32_t untimed_launches = 0;
-    bool timing_valid = false;
-    hvs_timing timing{};
-    double host_ms = 0.0;     // wall time of the last hvs_query (host memory in -> host memory out)
-
-    // queries whose candidate lists overflowed (-> exact engine) or whose guessed threshold failed its check (-> a filter
-    // batch with a proven last threshold), collected over all batches of a call; they are re-run when the call's results
-    // are first needed (resolve_overflow) -- no host synchronisation inside a batch
-    uint32_t* h_ovf = nullptr;  // pinned: [0] exact, [1] retry
-    bool ovf_pending = false;
-    uint32_t pend_sn = 0;
 
     // host <-> device pipeline of hvs_query: copy streams + rings of pinned staging slots
     hipStream_t s_in = nullptr, s_out = nullptr;
@@ -422,6 +438,18 @@ const float* user_dists(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_
 // every resident query has a result row with the current k (hvs_set_after_from_results needs all of them)
 bool leaf_has_all_results(const hvs_ctx* c) { return c->qs.covers(c->nq, c->k); }
 
+// ---- HvsCallState's smallest transition (DESIGN 3.5a has the table; the others follow the launch timers).  Nothing of the last
+// call is left to report until the next one (hvs_last_timing: HVS_ESTATE; the per-call figures of hvs_mask_stats,
+// hvs_append_stats and hvs_update_stats: zero): category sets, a new k or a compaction re-sized or renumbered what it answered;
+// the planner probe ran its own batch through the call counters and the launch timers, and the probe's figures must not be
+// reported under the caller's last query's name; a multi-GPU call gave this GPU no queries, or no row of the sampled prefix.
+int call_forgotten(hvs_ctx* c)
+{
+    c->call.valid = false;
+    c->call.n_launch_events = 0;  // (the launch timers are free again)
+    return HVS_OK;
+}
+
 // ---- transitions of the resident-query state (HvsQuerySet; DESIGN 3.13a has the table) ----
 // a call replaces the resident set: sets, caps and cursors belonged to the old one, and so did its results
 void resident_set_replaced(hvs_ctx* c)
@@ -436,7 +464,7 @@ void sets_changed(hvs_ctx* c, bool on)
 {
     c->qs.in.active = on;
     c->qs.drop_attached();
-    c->timing_valid = false;
+    call_forgotten(c);
 }
 // k changed: no result row and no merged row has the new size (the range itself is told by res_k), nothing of the last call is
 // left to report.  Returns the queries the result buffers had room for: hvs_set_k re-sizes them at once.
@@ -445,7 +473,7 @@ uint32_t k_changed(hvs_ctx* c)
     const uint32_t had = c->res_cap;
     c->res_cap = 0;
     c->qs.in.m_cap = 0;  // (the merged rows of category sets are re-allocated by the next call)
-    c->timing_valid = false;
+    call_forgotten(c);
     return had;
 }
 // the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
@@ -698,29 +726,90 @@ struct ScopedDevBufs {
 // reads their sum).  begin returns the pair's index or -1 (events could not be created: the launch goes untimed).
 int kernel_timer_begin(hvs_ctx* c)
 {
-    const size_t need = 2u * (size_t)(c->n_launch_events + 1);
-    while (c->ev_k.size() < need) {
+    HvsCallState& s = c->call;
+    const int ev = s.n_launch_events;
+    while (s.ev_k.size() < 2u * (size_t)(ev + 1)) {
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) {
-            c->untimed_launches++;
-            return -1;
-        }
-        c->ev_k.push_back(e);
+        if (hipEventCreate(&e) != hipSuccess) return s.timing.untimed_launches++, -1;
+        s.ev_k.push_back(e);
     }
-    const int ev = c->n_launch_events;
-    if (hipEventRecord(c->ev_k[2 * ev], c->stream) != hipSuccess) {
-        c->untimed_launches++;
-        return -1;
-    }
+    if (hipEventRecord(s.ev_k[2 * ev], c->stream) != hipSuccess) return s.timing.untimed_launches++, -1;
     return ev;
 }
 void kernel_timer_end(hvs_ctx* c, int ev)
 {
     if (ev < 0) return;
-    if (hipEventRecord(c->ev_k[2 * ev + 1], c->stream) == hipSuccess)
-        c->n_launch_events = ev + 1;
+    if (hipEventRecord(c->call.ev_k[2 * ev + 1], c->stream) == hipSuccess)
+        c->call.n_launch_events = ev + 1;
     else
-        c->untimed_launches++;  // (main_kernel_ms is then a lower bound: bench.py refuses to price a roofline from it)
+        c->call.timing.untimed_launches++;  // (main_kernel_ms is then a lower bound: bench.py refuses to price a roofline from it)
+}
+
+// ---- transitions and readers of the call state (HvsCallState; DESIGN 3.5a has the table) ----
+// the counters start a batch's worth of counting at zero: a call's, or the planner probe's own batch
+int counters_begin(hvs_ctx* c)
+{
+    HVS_HIP(c, hipMemsetAsync(c->call.d_counters, 0, HVS_CNT_COUNT * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(c->call.d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream));
+    return HVS_OK;
+}
+// A call begins (the one before it is resolved): no report until it is enqueued, no launch timed, no re-run counted (a list of
+// an earlier call must never be scattered into this call's results), the counters at zero; ev_q0 opens its device time.
+int call_begin(hvs_ctx* c)
+{
+    HvsCallState& s = c->call;
+    s.valid = false;
+    s.n_launch_events = 0;
+    s.timing = hvs_timing{};
+    s.demoted_queries = 0;
+    if (int rc = counters_begin(c)) return rc;
+    HVS_HIP(c, hipEventRecord(s.ev_q0, c->stream));
+    return HVS_OK;
+}
+// hvs_timing.engine of a call that the tiles of format `fmt` filtered
+int timing_engine_for(int fmt) { return HVS_IS_I8(fmt) ? HVS_ENGINE_MFMA_I8 : fmt == HVS_FMT_F16 ? HVS_ENGINE_MFMA_F16 : HVS_ENGINE_MFMA_FILTER; }
+// The call's `nq` queries are enqueued: ev_q1 closes its device time (resolve_overflow moves it behind the re-runs), a filter
+// engine's fail counts are on their way to h_ovf (`filtered`; `sn`: the cut its re-runs will use), there is a call to report.
+int call_enqueued(hvs_ctx* c, uint32_t nq, bool filtered, uint32_t sn)
+{
+    HvsCallState& s = c->call;
+    HVS_HIP(c, hipEventRecord(s.ev_q1, c->stream));
+    if (filtered) {
+        HVS_HIP(c, hipMemcpyAsync(s.h_ovf, s.d_ovf_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        s.pending = true;
+        s.pend_sn = sn;
+    }
+    s.timing.nq = nq;
+    s.timing.engine = filtered ? timing_engine_for(c->fmt.built) : HVS_ENGINE_EXACT_SCAN;
+    s.timing.load_ms = c->load_ms;
+    s.timing.n_gpus = 1;
+    s.timing.flags = (c->index_too_large ? HVS_TIMING_INDEX_TOO_LARGE : 0u) | (filtered && HVS_IS_I8(c->fmt.built) && c->fmt.built_rot ? HVS_TIMING_I8_ROTATED : 0u);
+    s.valid = true;
+    return HVS_OK;
+}
+// the exact list's length (and the retry list's) as the device has it now, through h_ovf -- nothing is pending; waits for the stream
+int fetch_fail_counts(hvs_ctx* c, uint32_t* exact, uint32_t* retry = nullptr)
+{
+    HVS_HIP(c, hipMemcpyAsync(c->call.h_ovf, c->call.d_ovf_count, (retry ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    *exact = c->call.h_ovf[0];
+    if (retry) *retry = c->call.h_ovf[1];
+    return HVS_OK;
+}
+// where an exact-engine batch adds its PAIRS and SCANNED: the call's counters, or the sink (re-runs; sub-batches counted beforehand)
+unsigned long long* exact_batch_counters(hvs_ctx* c, bool counted) { return c->call.d_counters + (counted ? 0 : HVS_CNT_RERUN_SINK); }
+// how hvs_last_timing, hvs_within_stats, hvs_after_stats and hvs_in_stats begin: there is a last call to report (else HVS_ESTATE),
+// and it is resolved and complete
+int leaf_sync(hvs_ctx* c);
+int call_required(hvs_ctx* c) { return c->call.valid ? leaf_sync(c) : fail(c, HVS_ESTATE, "no query has run yet"); }
+// The one reader of the counters: slots [first, first + N) of the last call, or zeros when there is none to report (as
+// hvs_mask_stats, hvs_append_stats and hvs_update_stats say it).  `own_batch`: the planner probe reads its own batch's.
+template <size_t N>
+int call_counters(hvs_ctx* c, int first, unsigned long long (&v)[N], bool own_batch = false)
+{
+    std::fill(v, v + N, 0ull);
+    if (c->call.valid || own_batch) HVS_HIP(c, hipMemcpy(v, c->call.d_counters + first, sizeof(v), hipMemcpyDeviceToHost));
+    return HVS_OK;
 }
 
 // the select / merge / scan kernels exist for two list capacities; `f` gets the capacity as a compile-time constant
@@ -799,7 +888,7 @@ void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t st
         with_capped_after(c, [&](auto WT, auto AT) {
             hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt,
-                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->qs.eng.d_max_d2, c->d_counters, c->qs.eng.d_after_lo);
+                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo);
         });
     });
 }
@@ -820,8 +909,8 @@ int ensure_results(hvs_ctx* c, uint32_t nq)
     int rc;
     if ((rc = dev_alloc(c, &c->d_out_ids, (size_t)nq * c->k))) return rc;
     if ((rc = dev_alloc(c, &c->d_out_dists, (size_t)nq * c->k))) return rc;
-    if ((rc = dev_alloc(c, &c->d_ovf_list, (size_t)nq))) return rc;
-    if ((rc = dev_alloc(c, &c->d_retry_list, (size_t)nq))) return rc;
+    if ((rc = dev_alloc(c, &c->call.d_ovf_list, (size_t)nq))) return rc;
+    if ((rc = dev_alloc(c, &c->call.d_retry_list, (size_t)nq))) return rc;
     c->res_cap = nq;
     return HVS_OK;
 }
@@ -911,7 +1000,7 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
 
     const int ev = record_events ? kernel_timer_begin(c) : -1;
     if (sn > 0) {
-        unsigned long long* stat = count_stats ? c->d_counters : c->d_counters + 4;
+        unsigned long long* stat = exact_batch_counters(c, count_stats);
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
         with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
             with_capped_after(c, [&](auto WT, auto AT) {
@@ -1074,7 +1163,7 @@ int ensure_live_prefix(hvs_ctx* c)
     return HVS_OK;
 }
 
-// passing pairs of a batch under a mask (counters[0]): from the prefix counts, or row by row when a sampled prefix cuts in
+// passing pairs of a batch under a mask (HVS_CNT_PAIRS): from the prefix counts, or row by row when a sampled prefix cuts in
 int count_masked_pairs(hvs_ctx* c, uint32_t sn)
 {
     HvsBatch& B = c->fb;
@@ -1082,10 +1171,10 @@ int count_masked_pairs(hvs_ctx* c, uint32_t sn)
         int rc = ensure_live_prefix(c);
         if (rc) return rc;
         hipLaunchKernelGGL(hvs_k_count_live_pairs, dim3(hvs_ceil_div(B.nslots, 256u)), dim3(256), 0, c->stream, B, c->ord[0].lp, c->ord[1].lp,
-                           c->d_counters);
+                           c->call.d_counters);
     } else {
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<true>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, index_mask(c));
+                           c->call.d_counters, index_mask(c));
     }
     return HVS_OK;
 }
@@ -1159,8 +1248,6 @@ bool filter_engine_selected(const hvs_ctx* c)
 {
     return is_filter_engine(c->engine) || (c->engine == HVS_ENGINE_AUTO && c->n >= kMfmaMinRows && c->fmt.planned != HVS_FMT_NONE);
 }
-// hvs_timing.engine of a call that the tiles of format `fmt` filtered
-int timing_engine_for(int fmt) { return HVS_IS_I8(fmt) ? HVS_ENGINE_MFMA_I8 : fmt == HVS_FMT_F16 ? HVS_ENGINE_MFMA_F16 : HVS_ENGINE_MFMA_FILTER; }
 
 // The precision chain INT8 -> FP16 -> BF16: the next format below `fmt` that this data set has not rejected (HVS_FMT_NONE
 // below BF16, the last resort, which is built whatever happened to it before)
@@ -1211,46 +1298,38 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
 {
     constexpr uint32_t P = 1024;
     *cost = 1.0e9;
+    if (c->call.pending) return fail(c, HVS_ESTATE, "internal: planner probe while a call's re-runs are pending");  // (h_ovf and the counts are that call's)
     // the probe has its own query / result / re-run buffers, in the context's fields while it runs: resident queries and
     // results of the caller stay untouched
     ScopedDevBufs own;
     if (own.lend(&c->d_q, (size_t)P * HVS_QCOLS) != hipSuccess || own.lend(&c->d_out_dists, (size_t)P * c->k) != hipSuccess ||
-        own.lend(&c->d_out_ids, (size_t)P * c->k) != hipSuccess || own.lend(&c->d_ovf_list, (size_t)P) != hipSuccess ||
-        own.lend(&c->d_retry_list, (size_t)P) != hipSuccess) {
+        own.lend(&c->d_out_ids, (size_t)P * c->k) != hipSuccess || own.lend(&c->call.d_ovf_list, (size_t)P) != hipSuccess ||
+        own.lend(&c->call.d_retry_list, (size_t)P) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, HVS_ENOMEM, "planner probe: out of device memory");
     }
     // (rows of the indexed part, searched in the indexed part: the probe prices the index, and runs when it covers every row)
     const uint32_t step = std::max(1u, c->n_indexed / P);
     hipLaunchKernelGGL(hvs_k_probe_queries, dim3(hvs_ceil_div(P * HVS_QCOLS, 256u)), dim3(256), 0, c->stream, c->d_data, c->n_indexed, step, P, c->d_q);
-    hipError_t e = hipMemsetAsync(c->d_counters, 0, HVS_NCOUNTERS * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
     // (the probe batch is small, but it stands for full batches: their failure target.  Its lists keep the production capacity:
     // PCA-like vectors at n = 10^7 hand ~1500 rows per type-0 query to the last level's list of 1024 -- INT8 tiles look 23 %
     // faster than FP16 tiles there only while a half-empty workspace doubles the lists, profiles/r04/nonuniform_int8.txt)
     c->force_pfail = guess_pfail_for(kBatchMfma);
-    int rc;
-    {
+    int rc = counters_begin(c);
+    if (!rc) {
         const DetachedForProbe probe(c->qs);
-        rc = e == hipSuccess ? run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false) : fail(c, HVS_EHIP, "planner probe: memset failed");
+        rc = run_batch_mfma(c, 0, P, c->n_indexed, nullptr, false);
     }
     c->force_pfail = 0u;
-    unsigned long long h[4] = {0, 0, 0, 0};
+    unsigned long long rescored[1] = {0};
     uint32_t fails[2] = {0, 0};
-    if (!rc) {
-        e = hipMemcpyAsync(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(fails, c->d_ovf_count, sizeof(fails), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, HVS_EHIP, "planner probe: copy failed");
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, HVS_EHIP, "planner probe: synchronisation failed");
-    c->n_launch_events = 0;
-    // the probe ran through the call counters and the launch timers: what they held of the caller's last query is gone, so
-    // there is no last call to report until the next one (hvs_last_timing: HVS_ESTATE; the per-call figures of hvs_mask_stats,
-    // hvs_append_stats and hvs_update_stats: zero) -- as after a compaction, instead of the probe's figures under that call's name
-    c->timing_valid = false;
+    if (!rc) rc = fetch_fail_counts(c, &fails[0], &fails[1]);  // (waits for the batch)
+    if (!rc) rc = call_counters(c, HVS_CNT_RESCORED, rescored, true);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // (the lent buffers go when this returns)
+    call_forgotten(c);
     if (rc) return rc;
     const double base = HVS_IS_I8(c->fmt.built) ? 1.0 : plan_cost16();
-    *cost = base + 2650.0 / (double)c->n_indexed * ((double)h[2] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
+    *cost = base + 2650.0 / (double)c->n_indexed * ((double)rescored[0] / P) + 3.0 * fails[1] / P + 142.0 * fails[0] / P;
     // what a filter without any error band would have handed over: m (radix - 1) rows per level under the guessed thresholds
     double ideal = 0.0;
     {
@@ -1264,7 +1343,7 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
             ideal += std::min(m, (double)c->k) * ((double)c->lv.radix[j] - 1.0);
         }
     }
-    *inflation = ideal > 0.0 ? ((double)h[2] / P) / ideal : 1.0;
+    *inflation = ideal > 0.0 ? ((double)rescored[0] / P) / ideal : 1.0;
     *failed = (double)(fails[0] + fails[1]) / P;
     return HVS_OK;
 }
@@ -1500,14 +1579,14 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
             if ((rc = count_masked_pairs(c, *count_sn))) return rc;
         } else {
             hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, *count_sn,
-                               c->d_counters, c->rs.d_live);
+                               c->call.d_counters, c->rs.d_live);
         }
     }
     // (last argument: the batch is for a filter engine -- `host_counts` is the exact engine's range scan, which answers every
     // query itself, non-finite ones included)
     with_capped(c, [&](auto WT) {  // (capped: the slots' thresholds start at the queries' caps)
         hipLaunchKernelGGL(hvs_k_prep<decltype(WT)::value>, dim3(B.ngroups), dim3(4 * HVS_GROUP), 0, c->stream, c->d_q, B, count_pairs ? 1 : 0,
-                           c->d_counters, fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1, c->qs.eng.d_max_d2);
+                           c->call.d_counters, fmt, c->d_quant, c->d_bounds, host_counts ? 0 : 1, c->qs.eng.d_max_d2);
     });
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
@@ -1522,7 +1601,7 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         with_after(c, [&](auto AT) {
             hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
-                               dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->d_counters,
+                               dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->call.d_counters,
                                count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
         });
     });
@@ -1537,7 +1616,7 @@ void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
         with_after(c, [&](auto AT) {
             hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m,
-                               c->d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
+                               c->call.d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
         });
     });
 }
@@ -1559,7 +1638,7 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
         if ((rc = count_masked_pairs(c, sn))) return rc;
     } else if (sn < c->n_indexed)
         hipLaunchKernelGGL(hvs_k_count_prefix_pairs<false>, dim3(B.nslots), dim3(64), 0, c->stream, B, c->ord[0].perm, c->ord[1].perm, sn,
-                           c->d_counters, c->rs.d_live);
+                           c->call.d_counters, c->rs.d_live);
     // slot layout of hvs_k_layout: classes 0..3 padded to 32 slots each, then the T-ordering class (type 2)
     // from the next filter-workgroup boundary
     const uint32_t nq0 = c->class_counts[0], nq2 = c->class_counts[4];
@@ -1596,7 +1675,7 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
             hipLaunchKernelGGL(
                 (hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>), grid,
                 dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand,
-                c->d_cand_cnt, c->d_counters, index_mask(c), c->qs.eng.d_after_lo);
+                c->d_cand_cnt, c->call.d_counters, index_mask(c), c->qs.eng.d_after_lo);
         });
     });
     kernel_timer_end(c, ev);
@@ -1760,7 +1839,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         with_capped_after(c, [&](auto WT, auto AT) {
             hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B,
-                               c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->d_counters, std::max(1u, seed_chunks),
+                               c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->call.d_counters, std::max(1u, seed_chunks),
                                index_mask(c), c->qs.eng.d_after_lo);
         });
     });
@@ -1773,12 +1852,12 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
                     hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
                                        dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds,
                                        c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids, c->qs.eng.d_max_d2,
-                                       c->d_counters, c->qs.eng.d_after_lo);
+                                       c->call.d_counters, c->qs.eng.d_after_lo);
                 });
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
                                    c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids,
-                                   c->qs.eng.d_max_d2, c->d_counters, c->qs.eng.d_after_lo);
+                                   c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo);
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -1810,7 +1889,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             const dim3 fgrid(kWgsPerCu * (uint32_t)c->num_cus);
             W.segsize = c->segs.seg[level];
             hipLaunchKernelGGL(filter_kernel, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->ord[0].tiles, c->ord[1].tiles, c->ord[0].nrm,
-                               c->ord[1].nrm, c->ord[0].bpos, c->ord[1].bpos, L, level, B, W, c->d_counters);
+                               c->ord[1].nrm, c->ord[0].bpos, c->ord[1].bpos, L, level, B, W, c->call.d_counters);
             kernel_timer_end(c, ev);
             if (level == L.K && c->ev_fdone_cur) HVS_HIP(c, hipEventRecord(c->ev_fdone_cur, c->stream));
             if (level + 1u == L.K && c->ev_pdone_cur) HVS_HIP(c, hipEventRecord(c->ev_pdone_cur, c->stream));
@@ -1823,12 +1902,12 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
                 if constexpr (decltype(AT)::value) {
                     const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M, const uint64_t*> : hvs_k_rescore<false, M, const uint64_t*>;  // (entry format)
                     hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
-                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, index_mask(c),
+                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->call.d_counters, index_mask(c),
                                        static_cast<const uint64_t*>(c->qs.eng.d_after_lo));
                 } else {
                     const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M> : hvs_k_rescore<false, M>;
                     hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
-                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->d_counters, index_mask(c));
+                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->call.d_counters, index_mask(c));
                 }
             });
         });
@@ -1837,8 +1916,8 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     }
     // queries this batch could not answer go on the call's lists (retry with a proven threshold / exact engine); they
     // are answered again when the call's results are first needed (resolve_overflow) -- the batch never waits for the host
-    hipLaunchKernelGGL(hvs_k_collect_overflow, dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, B, c->d_ovf_list,
-                       c->d_ovf_count, c->d_retry_list, c->d_ovf_count + 1);
+    hipLaunchKernelGGL(hvs_k_collect_overflow, dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, B, c->call.d_ovf_list,
+                       c->call.d_ovf_count, c->call.d_retry_list, c->call.d_ovf_count + 1);
     HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
@@ -1850,54 +1929,49 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
 // one stream synchronisation per call (two more when there is something to re-run).
 int resolve_overflow(hvs_ctx* c)
 {
-    if (!c->ovf_pending) return HVS_OK;
+    if (!c->call.pending) return HVS_OK;
     HVS_HIP(c, hipSetDevice(c->device));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    c->ovf_pending = false;
-    c->demoted_queries = 0;
-    uint32_t novf = c->h_ovf[0];
-    const uint32_t nretry = c->h_ovf[1];
+    c->call.pending = false;
+    uint32_t novf = c->call.h_ovf[0];
+    const uint32_t nretry = c->call.h_ovf[1];
     if (novf == 0u && nretry == 0u) return HVS_OK;
-    // what is left of a list when a re-run batch cannot get its workspace: appended to the exact engine's list, which needs none
-    auto rest_to_exact = [&](const uint32_t* list, uint32_t count) -> int {
-        (void)hipGetLastError();
-        HVS_HIP(c, hipMemcpyAsync(c->h_ovf, c->d_ovf_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HVS_HIP(c, hipStreamSynchronize(c->stream));
-        const uint32_t have = c->h_ovf[0];
-        HVS_HIP(c, hipMemcpyAsync(c->d_ovf_list + have, list, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        const uint32_t total = have + count;
-        HVS_HIP(c, hipMemcpyAsync(c->d_ovf_count, &total, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HVS_HIP(c, hipStreamSynchronize(c->stream));
-        c->err.clear();
-        return HVS_OK;
-    };
-    if (nretry) {
-        c->retry_queries = nretry;
+    // A list through filter batches with proven thresholds, then the exact list's new length.  *done: the queries that got a
+    // batch -- what is left when one cannot get its workspace is appended to the exact engine's list, which needs none.
+    auto rerun_proven = [&](const uint32_t* list, uint32_t count, uint32_t* done) -> int {
         const uint32_t step = proven_batch_step(c);
-        for (uint32_t off = 0; off < nretry; off += step) {
-            const uint32_t m = std::min(step, nretry - off);
-            int rc = run_batch_mfma(c, 0, m, c->pend_sn, c->d_retry_list + off, true);
+        for (*done = 0; *done < count; *done += std::min(step, count - *done)) {
+            int rc = run_batch_mfma(c, 0, std::min(step, count - *done), c->call.pend_sn, list + *done, true);
             if (rc == HVS_ENOMEM) {
-                if ((rc = rest_to_exact(c->d_retry_list + off, nretry - off))) return rc;
+                (void)hipGetLastError();
+                uint32_t have = 0;
+                if ((rc = fetch_fail_counts(c, &have))) return rc;
+                const uint32_t rest = count - *done, total = have + rest;
+                HVS_HIP(c, hipMemcpyAsync(c->call.d_ovf_list + have, list + *done, (size_t)rest * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+                HVS_HIP(c, hipMemcpyAsync(c->call.d_ovf_count, &total, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+                HVS_HIP(c, hipStreamSynchronize(c->stream));
+                c->err.clear();
                 break;
             }
             if (rc) return rc;
         }
-        HVS_HIP(c, hipMemcpyAsync(c->h_ovf, c->d_ovf_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HVS_HIP(c, hipStreamSynchronize(c->stream));
-        novf = c->h_ovf[0];
+        return fetch_fail_counts(c, &novf);
+    };
+    if (nretry) {
+        uint32_t done = 0;
+        c->call.timing.retry_queries = nretry;
+        if (int rc = rerun_proven(c->call.d_retry_list, nretry, &done)) return rc;
     }
     // Many queries without a usable INT8 bound in one call (the planner's probe uses rows of D as queries: real queries can
     // lie far outside the data's box, where the clip term drowns the band): under HVS_ENGINE_AUTO the 16-bit float tiles
     // are built now -- for this call's list and for the calls to come -- instead of sending them all to the exact engine
     // at 1 % of a filter's rate.  The list moves aside (the filter batches append their own failures to the exact list).
-    c->demoted_queries = 0;
-    if (c->engine == HVS_ENGINE_AUTO && HVS_IS_I8(c->fmt.built) && novf >= std::max(256u, c->timing.nq / 50u) &&
+    if (c->engine == HVS_ENGINE_AUTO && HVS_IS_I8(c->fmt.built) && novf >= std::max(256u, c->call.timing.nq / 50u) &&
         env_u32("HVS_DEMOTE", 1u, 0u, 1u)) {
-        if (c->demote_cap < c->res_cap) {
-            int rc = dev_alloc(c, &c->d_demote_list, (size_t)c->res_cap);
+        if (c->call.demote_cap < c->res_cap) {
+            int rc = dev_alloc(c, &c->call.d_demote_list, (size_t)c->res_cap);
             if (rc) return rc;
-            c->demote_cap = c->res_cap;
+            c->call.demote_cap = c->res_cap;
         }
         // The 16-bit float tiles first: when HBM has no room for them next to D (they are 1.7x the INT8 tiles) the INT8
         // tiles come back and the exact engine answers the list as it always did -- slower, never an error.
@@ -1916,38 +1990,21 @@ int resolve_overflow(hvs_ctx* c)
         } else if (rc) {
             return rc;
         } else {
-            HVS_HIP(c, hipMemcpyAsync(c->d_demote_list, c->d_ovf_list, (size_t)novf * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-            HVS_HIP(c, hipMemsetAsync(c->d_ovf_count, 0, sizeof(uint32_t), c->stream));
+            HVS_HIP(c, hipMemcpyAsync(c->call.d_demote_list, c->call.d_ovf_list, (size_t)novf * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            HVS_HIP(c, hipMemsetAsync(c->call.d_ovf_count, 0, sizeof(uint32_t), c->stream));
             c->fmt.planned = c->fmt.built;
-            const uint32_t step = proven_batch_step(c);
-            uint32_t done = novf;
-            for (uint32_t off = 0; off < novf; off += step) {
-                const uint32_t m = std::min(step, novf - off);
-                rc = run_batch_mfma(c, 0, m, c->pend_sn, c->d_demote_list + off, true);
-                if (rc == HVS_ENOMEM) {
-                    if ((rc = rest_to_exact(c->d_demote_list + off, novf - off))) return rc;
-                    done = off;
-                    break;
-                }
-                if (rc) return rc;
-            }
-            c->demoted_queries = done;
-            HVS_HIP(c, hipMemcpyAsync(c->h_ovf, c->d_ovf_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HVS_HIP(c, hipStreamSynchronize(c->stream));
-            novf = c->h_ovf[0];
-            c->timing.flags |= HVS_TIMING_FORMAT_CHANGED;
-            c->timing.engine = timing_engine_for(c->fmt.built);
+            if ((rc = rerun_proven(c->call.d_demote_list, novf, &c->call.demoted_queries))) return rc;
+            c->call.timing.flags |= HVS_TIMING_FORMAT_CHANGED;
+            c->call.timing.engine = timing_engine_for(c->fmt.built);
         }
     }
-    c->fallback_queries = novf;
-    c->timing.fallback_queries = novf;
-    c->timing.retry_queries = nretry;
+    c->call.timing.fallback_queries = novf;
     for (uint32_t off = 0; off < novf; off += kBatch) {
         const uint32_t m = std::min(kBatch, novf - off);
-        int rc = run_batch_exact(c, 0, m, c->pend_sn, c->d_ovf_list + off, false, false);
+        int rc = run_batch_exact(c, 0, m, c->call.pend_sn, c->call.d_ovf_list + off, false, false);
         if (rc) return rc;
     }
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));  // the re-runs belong to the call's device time
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));  // the re-runs belong to the call's device time
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return HVS_OK;
 }
@@ -2048,10 +2105,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
-    {
-        int rc = resolve_overflow(c);  // an earlier call whose results were never fetched
-        if (rc) return rc;
-    }
+    if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
     const uint32_t sn = cut.sn, sampled = cut.sampled, of_rows = cut.of_rows;
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
@@ -2066,19 +2120,11 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
         }
         mfma = c->fmt.built != HVS_FMT_NONE;  // (no usable bound at all: the exact engine answers, on the orderings)
     }
-    c->timing_valid = false;
     c->qs.call_capped = capped(c);
     c->qs.call_after = has_after(c);
     c->qs.in.call = false;  // (in_run sets it once the merge is enqueued)
     c->qs.answered(q0, nq, c->k, c->qs.set_gen);
-    c->n_launch_events = 0;
-    c->untimed_launches = 0;
-    c->fallback_queries = 0;
-    c->retry_queries = 0;
-    c->demoted_queries = 0;  // (a list of an earlier call must never be scattered into this call's results)
-    HVS_HIP(c, hipMemsetAsync(c->d_counters, 0, HVS_NCOUNTERS * sizeof(unsigned long long), c->stream));
-    HVS_HIP(c, hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream));
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    if (int rc = call_begin(c)) return rc;
     const bool ranges = !mfma && c->have_order;  // exact engine: scan position ranges when the orderings exist
     const std::vector<uint32_t> sched = batch_schedule(nq, mfma ? kBatchMfma : kBatch, host_pipeline && mfma);
     // Two lanes (HvsLane): every other batch of a filter-engine call runs on the spare lane's stream and workspace, so that
@@ -2117,7 +2163,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
             } else if (rcw) {
                 return rcw;
             } else if (!spare_used) {
-                HVS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_q0, 0));
+                HVS_HIP(c, hipStreamWaitEvent(c->stream, c->call.ev_q0, 0));
                 spare_used = true;
             }
         }
@@ -2141,21 +2187,9 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
         off += nqb;
     }
     if (spare_used) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_lane, 0));
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
-    if (mfma) {
-        HVS_HIP(c, hipMemcpyAsync(c->h_ovf, c->d_ovf_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        c->ovf_pending = true;
-        c->pend_sn = sn;
-    }
-    c->timing = hvs_timing{};
-    c->timing.nq = nq;
-    c->timing.engine = mfma ? timing_engine_for(c->fmt.built) : HVS_ENGINE_EXACT_SCAN;
-    c->timing.load_ms = c->load_ms;
-    c->timing.n_gpus = 1;
-    c->timing.flags = (c->index_too_large ? HVS_TIMING_INDEX_TOO_LARGE : 0u) | (mfma && HVS_IS_I8(c->fmt.built) && c->fmt.built_rot ? HVS_TIMING_I8_ROTATED : 0u);
-    c->timing_valid = true;
-    join_on_error.ok = true;
-    return HVS_OK;
+    const int rc = call_enqueued(c, nq, mfma, sn);
+    join_on_error.ok = rc == HVS_OK;
+    return rc;
 }
 
 template <typename Hooks>
@@ -2214,31 +2248,31 @@ int leaf_create(hvs_ctx** out, int device)
         if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipEventCreate(&c->ev_q0)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreate(&c->ev_q1)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreate(&c->call.ev_q0)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreate(&c->call.ev_q1)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     for (int i = 0; i < hvs_ctx::kRing; ++i) {
         if ((e = hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     }
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), HVS_NCOUNTERS * sizeof(unsigned long long))) != hipSuccess)
+    if ((e = hipMalloc(reinterpret_cast<void**>(&c->call.d_counters), HVS_CNT_COUNT * sizeof(unsigned long long))) != hipSuccess)
         return bail("hipMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_ovf_count), 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = hipMalloc(reinterpret_cast<void**>(&c->call.d_ovf_count), 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_layout), 16 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_ovf), 2 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
+    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->call.h_ovf), 2 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
         return bail("hipHostMalloc", e);
-    c->h_ovf[0] = c->h_ovf[1] = 0u;
+    c->call.h_ovf[0] = c->call.h_ovf[1] = 0u;
     // The first operation on a stream creates its hardware queue (and the first copy in each direction its DMA path): a few
     // milliseconds that belong here, not inside the first query (round 3's cold hvs_query of 10^4 queries took 8 ms for 2 ms
     // of device work).
-    (void)hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
+    (void)hipMemsetAsync(c->call.d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipMemsetAsync(c->d_ovf_count, 0, 2 * sizeof(uint32_t), c->spare.stream);
+    (void)hipMemsetAsync(c->call.d_ovf_count, 0, 2 * sizeof(uint32_t), c->spare.stream);
     (void)hipStreamSynchronize(c->spare.stream);
-    (void)hipMemcpyAsync(c->d_ovf_count, c->h_ovf, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_in);
+    (void)hipMemcpyAsync(c->call.d_ovf_count, c->call.h_ovf, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_in);
     (void)hipStreamSynchronize(c->s_in);
-    (void)hipMemcpyAsync(c->h_ovf, c->d_ovf_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_out);
+    (void)hipMemcpyAsync(c->call.h_ovf, c->call.d_ovf_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_out);
     (void)hipEventRecord(c->ev_batch, c->stream);
     (void)hipStreamWaitEvent(c->s_out, c->ev_batch, 0);
     (void)hipStreamSynchronize(c->s_out);
@@ -2255,8 +2289,8 @@ void leaf_destroy(hvs_ctx* c)
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
-    void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->d_counters, c->d_bounds, c->d_quant,
-                    c->d_ovf_list, c->d_ovf_count, c->d_retry_list, c->d_demote_list, c->ord[0].lp, c->ord[1].lp};
+    void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->call.d_counters, c->d_bounds, c->d_quant,
+                    c->call.d_ovf_list, c->call.d_ovf_count, c->call.d_retry_list, c->call.d_demote_list, c->ord[0].lp, c->ord[1].lp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->rs.free_device();
@@ -2275,7 +2309,7 @@ void leaf_destroy(hvs_ctx* c)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_pdone)
         if (ev) (void)hipEventDestroy(ev);
-    if (c->h_ovf) (void)hipHostFree(c->h_ovf);
+    if (c->call.h_ovf) (void)hipHostFree(c->call.h_ovf);
     for (int i = 0; i < hvs_ctx::kRing; ++i) {
         if (c->h_in[i]) (void)hipHostFree(c->h_in[i]);
         if (c->h_out_ids[i]) (void)hipHostFree(c->h_out_ids[i]);
@@ -2285,9 +2319,9 @@ void leaf_destroy(hvs_ctx* c)
     }
     if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
     if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
-    if (c->ev_q0) (void)hipEventDestroy(c->ev_q0);
-    if (c->ev_q1) (void)hipEventDestroy(c->ev_q1);
-    for (hipEvent_t e : c->ev_k) (void)hipEventDestroy(e);
+    if (c->call.ev_q0) (void)hipEventDestroy(c->call.ev_q0);
+    if (c->call.ev_q1) (void)hipEventDestroy(c->call.ev_q1);
+    for (hipEvent_t e : c->call.ev_k) (void)hipEventDestroy(e);
     if (c->s_in) (void)hipStreamDestroy(c->s_in);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
 }
@@ -2487,7 +2521,7 @@ int index_data(hvs_ctx* c);
 int finish_data(hvs_ctx* c)
 {
     float ms = 0.f;
-    HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_q0, c->call.ev_q1));
     c->load_ms = ms;
     return index_data(c);
 }
@@ -2500,7 +2534,7 @@ int index_data(hvs_ctx* c)
     // the index (two orderings + tiles) serves both engines: the exact engine scans position ranges
     if (c->n < kIndexMinRows && !is_filter_engine(c->engine)) return HVS_OK;
     c->rs.index_tried_n = c->n;
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     int rc = build_index(c);
     if (rc == HVS_ENOMEM) {
         // not enough HBM for the index next to D: the data set stays usable through the exact engine
@@ -2510,9 +2544,9 @@ int index_data(hvs_ctx* c)
         rc = HVS_OK;
     }
     if (rc) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_q0, c->call.ev_q1));
     c->index_ms = ms;
     c->load_ms += ms;
     trace_mark(c, "index");
@@ -2619,9 +2653,9 @@ int leaf_upload_data(hvs_ctx* c, const float* rows, uint32_t n)
     int rc = begin_data(c, n);
     if (rc) return rc;
     trace_mark(c, "alloc");
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     if ((rc = upload_rows(c, c->d_data, rows, (size_t)n * HVS_DCOLS))) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = n;
     return HVS_OK;
@@ -2646,9 +2680,9 @@ int leaf_load_data_from_peer(hvs_ctx* c, const hvs_ctx* src)
     const uint32_t n = src->n;
     int rc = begin_data(c, n);
     if (rc) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     HVS_HIP(c, hipMemcpyPeerAsync(c->d_data, c->device, src->d_data, src->device, (size_t)n * HVS_DCOLS * sizeof(float), c->stream));
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = n;
     return finish_data(c);
@@ -2690,9 +2724,9 @@ int leaf_load_data_device(hvs_ctx* c, const float* d_rows, int src_dev, uint32_t
 {
     int rc = begin_data(c, n);
     if (rc) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     if ((rc = copy_from_device(c, c->d_data, d_rows, src_dev, (size_t)n * HVS_DCOLS * sizeof(float)))) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = n;
     return finish_data(c);
@@ -2703,11 +2737,11 @@ int leaf_gen_data(hvs_ctx* c, uint32_t n, uint64_t seed, int profile, uint32_t n
 {
     int rc = begin_data(c, n);
     if (rc) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     hipLaunchKernelGGL(hvs_k_gen_data, dim3(256 * 8), dim3(256), 0, c->stream, c->d_data, (uint64_t)n * HVS_DCOLS,
                        seed, profile, ncat, first_row);
     HVS_HIP(c, hipGetLastError());
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->n = n;
     return finish_data(c);
@@ -3092,8 +3126,8 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         HVS_HIP(c, hipGetLastError());
     }
     HVS_HIP(c, hipEventRecord(S.ev_m1, c->stream));
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));  // (the merge belongs to the call's device time)
-    c->timing.nq = nq;  // (the user's)
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));  // (the merge belongs to the call's device time)
+    c->call.timing.nq = nq;  // (the user's)
     S.call = true;
     S.call_sub = s1 - s0;
     S.call_set_queries = S.call_max_set = 0;
@@ -3111,8 +3145,7 @@ int leaf_run_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proport
 
 int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
 {
-    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    int rc = leaf_sync(c);
+    int rc = call_required(c);
     if (rc) return rc;
     *out = hvs_in_info{};
     const HvsInSet& S = c->qs.in;
@@ -3146,6 +3179,55 @@ struct PeerSink {
     uint32_t row0;
     bool want_dists;
 };
+
+// The rows of the queries a call answered a second time (HvsCallState::reruns, resolved) leave again: to the peer sink row by
+// row, or to the caller's arrays.
+int fetch_rerun_rows(hvs_ctx* c, const PeerSink* sink, uint32_t* out_ids, float* out_dists)
+{
+    std::vector<uint32_t> list;
+    for (const auto& [d_list, len] : c->call.reruns()) {
+        list.resize(list.size() + len);
+        if (len) HVS_HIP(c, hipMemcpy(&list[list.size() - len], d_list, (size_t)len * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    const size_t cnt = list.size(), words = cnt * c->k, row_bytes = c->k * sizeof(uint32_t);
+    if (!cnt) return HVS_OK;
+    // The rows are packed on the device (the idle candidate workspace is the scratch), leave in ONE copy and are scattered here:
+    // thousands of 400-byte copies cost ~10 us each.  Row by row all the same: to a peer sink, and without room for the packing.
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(c->fb.cand);
+    const bool fits = scratch && 2u * words * sizeof(uint32_t) <= c->fb_cand_entries * sizeof(uint64_t);
+    if (sink || !fits) {
+        for (uint32_t qi : list) {
+            const size_t src = (size_t)qi * c->k, dst = sink ? ((size_t)sink->row0 + qi) * c->k : src;
+            if (sink) {
+                HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_ids + dst, sink->ctx->device, c->d_out_ids + src, c->device, row_bytes, c->stream));
+                if (sink->want_dists)
+                    HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_dists + dst, sink->ctx->device, c->d_out_dists + src, c->device, row_bytes, c->stream));
+            } else {
+                HVS_HIP(c, hipMemcpyAsync(out_ids + dst, c->d_out_ids + src, row_bytes, hipMemcpyDeviceToHost, c->stream));
+                if (out_dists) HVS_HIP(c, hipMemcpyAsync(out_dists + dst, c->d_out_dists + src, row_bytes, hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        HVS_HIP(c, hipStreamSynchronize(c->stream));
+        return HVS_OK;
+    }
+    uint32_t* d_list = scratch + 2u * words;  // (the list itself rides behind the rows when there is room)
+    ScopedDevBufs tmp;
+    if ((2u * words + cnt) * sizeof(uint32_t) > c->fb_cand_entries * sizeof(uint64_t)) HVS_HIP(c, tmp.alloc(&d_list, cnt));
+    std::vector<uint32_t> packed(words * (out_dists ? 2u : 1u));
+    HVS_HIP(c, hipMemcpyAsync(d_list, list.data(), cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const dim3 grid(hvs_ceil_div((uint32_t)words, 256u));
+    hipLaunchKernelGGL(hvs_k_gather_rows, grid, dim3(256), 0, c->stream, d_list, (uint32_t)cnt, c->d_out_ids, c->k, scratch);
+    if (out_dists)
+        hipLaunchKernelGGL(hvs_k_gather_rows, grid, dim3(256), 0, c->stream, d_list, (uint32_t)cnt, reinterpret_cast<const uint32_t*>(c->d_out_dists),
+                           c->k, scratch + words);
+    HVS_HIP(c, hipMemcpyAsync(packed.data(), scratch, packed.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < cnt; ++i) {
+        std::memcpy(out_ids + (size_t)list[i] * c->k, packed.data() + i * c->k, row_bytes);
+        if (out_dists) std::memcpy(out_dists + (size_t)list[i] * c->k, packed.data() + words + i * c->k, row_bytes);
+    }
+    return HVS_OK;
+}
 
 // `max_d2` (hvs_query_within): the queries' distance caps, nq floats of host memory -- 4 bytes per query, sent whole before the
 // pipeline starts.
@@ -3281,72 +3363,12 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     tr.mark("drained");
     HVS_HIP(c, hipStreamSynchronize(c->s_out));
     tr.mark("s_out");
-    // overflowed queries: re-run by the exact engine, their rows fetched again
-    const bool had_ovf = c->ovf_pending;
+    // queries answered a second time: re-run now, their rows fetched again
+    const bool had_ovf = c->call.pending;
     if ((rc = resolve_overflow(c))) return rc;
     tr.mark("resolved");
-    if (had_ovf && (c->fallback_queries || c->retry_queries || c->demoted_queries)) {
-        const uint32_t novf = c->fallback_queries, nretry = c->retry_queries, ndem = c->demoted_queries;
-        std::vector<uint32_t> list((size_t)novf + nretry + ndem);
-        if (novf) HVS_HIP(c, hipMemcpy(list.data(), c->d_ovf_list, (size_t)novf * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (nretry)
-            HVS_HIP(c, hipMemcpy(list.data() + novf, c->d_retry_list, (size_t)nretry * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (ndem)
-            HVS_HIP(c, hipMemcpy(list.data() + novf + nretry, c->d_demote_list, (size_t)ndem * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (sink) {
-            for (uint32_t qi : list) {
-                const size_t dst = ((size_t)sink->row0 + qi) * c->k;
-                HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_ids + dst, sink->ctx->device, c->d_out_ids + (size_t)qi * c->k, c->device,
-                                              c->k * sizeof(uint32_t), c->stream));
-                if (sink_dists)
-                    HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_dists + dst, sink->ctx->device, c->d_out_dists + (size_t)qi * c->k,
-                                                  c->device, c->k * sizeof(float), c->stream));
-            }
-            HVS_HIP(c, hipStreamSynchronize(c->stream));
-        } else {
-            // the re-run rows are packed on the device (the idle candidate workspace is the scratch), leave in ONE copy and
-            // are scattered here: thousands of 400-byte copies cost ~10 us each
-            const size_t cnt = list.size(), words = cnt * c->k;
-            uint32_t* scratch = reinterpret_cast<uint32_t*>(c->fb.cand);
-            const bool fits = scratch && 2u * words * sizeof(uint32_t) <= c->fb_cand_entries * sizeof(uint64_t);
-            if (fits) {
-                uint32_t* d_list = scratch + 2u * words;  // (the list itself rides behind the rows when there is room)
-                const bool list_fits = (2u * words + cnt) * sizeof(uint32_t) <= c->fb_cand_entries * sizeof(uint64_t);
-                uint32_t* d_list_tmp = nullptr;
-                if (!list_fits) {
-                    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&d_list_tmp), cnt * sizeof(uint32_t)));
-                    d_list = d_list_tmp;
-                }
-                std::vector<uint32_t> packed(words * (out_dists ? 2u : 1u));
-                hipError_t e = hipMemcpyAsync(d_list, list.data(), cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(hvs_k_gather_rows, dim3(hvs_ceil_div((uint32_t)words, 256u)), dim3(256), 0, c->stream, d_list, (uint32_t)cnt,
-                                       c->d_out_ids, c->k, scratch);
-                    if (out_dists)
-                        hipLaunchKernelGGL(hvs_k_gather_rows, dim3(hvs_ceil_div((uint32_t)words, 256u)), dim3(256), 0, c->stream, d_list,
-                                           (uint32_t)cnt, reinterpret_cast<const uint32_t*>(c->d_out_dists), c->k, scratch + words);
-                    e = hipMemcpyAsync(packed.data(), scratch, packed.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-                }
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (d_list_tmp) (void)hipFree(d_list_tmp);
-                if (e != hipSuccess) return fail(c, HVS_EHIP, std::string("hvs_query: fetching the re-run rows: ") + hipGetErrorString(e));
-                for (size_t i = 0; i < cnt; ++i) {
-                    std::memcpy(out_ids + (size_t)list[i] * c->k, packed.data() + i * c->k, c->k * sizeof(uint32_t));
-                    if (out_dists) std::memcpy(out_dists + (size_t)list[i] * c->k, packed.data() + words + i * c->k, c->k * sizeof(float));
-                }
-            } else {
-                for (uint32_t qi : list) {
-                    HVS_HIP(c, hipMemcpyAsync(out_ids + (size_t)qi * c->k, c->d_out_ids + (size_t)qi * c->k, c->k * sizeof(uint32_t),
-                                              hipMemcpyDeviceToHost, c->stream));
-                    if (out_dists)
-                        HVS_HIP(c, hipMemcpyAsync(out_dists + (size_t)qi * c->k, c->d_out_dists + (size_t)qi * c->k,
-                                                  c->k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-                }
-                HVS_HIP(c, hipStreamSynchronize(c->stream));
-            }
-        }
-    }
-    c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    if (had_ovf && (rc = fetch_rerun_rows(c, sink, out_ids, out_dists))) return rc;
+    c->call.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
     tr.mark("done");
     tr.flush("hvs_query", nq);
     return HVS_OK;
@@ -3354,30 +3376,26 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
 
 int leaf_last_timing(hvs_ctx* c, hvs_timing* out)
 {
-    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    int rc = leaf_sync(c);
+    int rc = call_required(c);
     if (rc) return rc;
-    HVS_HIP(c, hipEventSynchronize(c->ev_q1));
+    HVS_HIP(c, hipEventSynchronize(c->call.ev_q1));
     float ms = 0.f;
-    HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
-    c->timing.query_ms = ms;
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_q0, c->call.ev_q1));
+    c->call.timing.query_ms = ms;
     double k = 0.0;
-    for (int i = 0; i < c->n_launch_events; ++i) {
-        HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_k[2 * i], c->ev_k[2 * i + 1]));
+    for (int i = 0; i < c->call.n_launch_events; ++i) {
+        HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_k[2 * i], c->call.ev_k[2 * i + 1]));
         k += ms;
     }
-    c->timing.main_kernel_ms = k;
-    c->timing.main_kernel_launches = (uint32_t)c->n_launch_events;
-    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HVS_HIP(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-    c->timing.pairs = h[0];
-    c->timing.scanned_pairs = h[1];
-    c->timing.rescored_pairs = h[2];
-    c->timing.fallback_queries = c->fallback_queries;
-    c->timing.retry_queries = c->retry_queries;
-    c->timing.untimed_launches = c->untimed_launches;
-    c->timing.host_ms = c->host_ms;
-    *out = c->timing;
+    c->call.timing.main_kernel_ms = k;
+    c->call.timing.main_kernel_launches = (uint32_t)c->call.n_launch_events;
+    unsigned long long h[3];
+    if ((rc = call_counters(c, HVS_CNT_PAIRS, h))) return rc;
+    c->call.timing.pairs = h[0];
+    c->call.timing.scanned_pairs = h[1];
+    c->call.timing.rescored_pairs = h[2];
+    c->call.timing.host_ms = c->call.host_ms;
+    *out = c->call.timing;
     return HVS_OK;
 }
 
@@ -3433,17 +3451,11 @@ int leaf_mask_stats(hvs_ctx* c, hvs_mask_info* out)
     if (rc) return rc;
     out->n_live = c->n - c->rs.n_dead;
     out->n_dead = c->rs.n_dead;
-    out->tiles_patched = 0;
-    out->dead_survivors = 0;
-    unsigned long long v = 0;
-    if (c->rs.d_mask_stat) {
-        HVS_HIP(c, hipMemcpy(&v, c->rs.d_mask_stat, sizeof(v), hipMemcpyDeviceToHost));
-        out->tiles_patched = v;
-    }
-    if (c->timing_valid) {
-        HVS_HIP(c, hipMemcpy(&v, c->d_counters + 8, sizeof(v), hipMemcpyDeviceToHost));
-        out->dead_survivors = v;
-    }
+    unsigned long long v[1] = {0};
+    if (c->rs.d_mask_stat) HVS_HIP(c, hipMemcpy(v, c->rs.d_mask_stat, sizeof(v), hipMemcpyDeviceToHost));
+    out->tiles_patched = v[0];
+    if ((rc = call_counters(c, HVS_CNT_DEAD_SURVIVORS, v))) return rc;
+    out->dead_survivors = v[0];
     return HVS_OK;
 }
 
@@ -3551,12 +3563,10 @@ int leaf_append_stats(hvs_ctx* c, hvs_append_info* out)
     out->tail_limit = tail_limit_of(c);
     out->reindexes = c->rs.reindexes;
     out->reindex_ms = c->rs.reindex_ms;
-    if (c->timing_valid) {
-        unsigned long long v[2] = {0, 0};
-        HVS_HIP(c, hipMemcpy(v, c->d_counters + 9, sizeof(v), hipMemcpyDeviceToHost));
-        out->tail_pairs = v[0];
-        out->tail_admitted = v[1];
-    }
+    unsigned long long v[2];
+    if ((rc = call_counters(c, HVS_CNT_TAIL_PAIRS, v))) return rc;
+    out->tail_pairs = v[0];
+    out->tail_admitted = v[1];
     return HVS_OK;
 }
 
@@ -3627,13 +3637,11 @@ int leaf_update_stats(hvs_ctx* c, hvs_update_info* out)
     *out = hvs_update_info{};
     out->n_stale = (uint32_t)c->rs.h_stale.size();
     out->limit = tail_limit_of(c);
-    if (c->timing_valid) {
-        unsigned long long v[3] = {0, 0, 0};
-        HVS_HIP(c, hipMemcpy(v, c->d_counters + 11, sizeof(v), hipMemcpyDeviceToHost));
-        out->stale_pairs = v[0];
-        out->stale_admitted = v[1];
-        out->stale_survivors = v[2];
-    }
+    unsigned long long v[3];
+    if ((rc = call_counters(c, HVS_CNT_STALE_PAIRS, v))) return rc;
+    out->stale_pairs = v[0];
+    out->stale_admitted = v[1];
+    out->stale_survivors = v[2];
     return HVS_OK;
 }
 
@@ -3676,7 +3684,7 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     HVS_HIP(c, hipMemcpyAsync(c->rs.d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     // HVS_TRACE: the gathers' and the copies' device time apart (an event between the two of every chunk)
     std::vector<hipEvent_t> ev_mid;
-    HVS_HIP(c, hipEventRecord(c->ev_q0, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
     uint32_t chunks = 0;
     for (uint64_t a64 = first_dead; a64 < n; a64 += chunk, ++chunks) {
         const uint32_t a = (uint32_t)a64, b = (uint32_t)std::min<uint64_t>(n, a64 + chunk);
@@ -3696,10 +3704,10 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
             HVS_HIP(c, hipMemcpyAsync(c->d_data + (size_t)ra * HVS_DCOLS, c->rs.d_cmp_bounce, (size_t)(rb - ra) * HVS_DCOLS * sizeof(float),
                                       hipMemcpyDeviceToDevice, c->stream));
     }
-    HVS_HIP(c, hipEventRecord(c->ev_q1, c->stream));
+    HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    HVS_HIP(c, hipEventElapsedTime(&ms, c->ev_q0, c->ev_q1));
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_q0, c->call.ev_q1));
     if (kTrace) {
         double gather_ms = 0.0;
         for (size_t i = 0; i + 1u < ev_mid.size(); i += 2u) {
@@ -3727,7 +3735,7 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     // count of patched tile entries over even where no tile build will, and leaves no earlier call's timing to ask for.
     // NOTE: a load does neither of the last two; whether that is meant is not recorded (hvs_mask_info.tiles_patched, hvs_last_timing)
     if (c->rs.d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->rs.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
-    c->timing_valid = false;
+    call_forgotten(c);
     // one index over all rows -- or none, by the rule of a load (fewer than 4096 rows, or no room for one)
     if (c->n >= kIndexMinRows || is_filter_engine(c->engine)) return leaf_reindex(c, true);
     free_index(c);
@@ -3955,7 +3963,7 @@ int call_stats(hvs_ctx* c, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add ad
     Info agg{};
     bool any = c->partitioned;
     for (hvs_ctx* k : c->kids) {
-        if (!k->timing_valid) continue;  // (took no part in the last call)
+        if (!k->call.valid) continue;  // (took no part in the last call)
         Info m{};
         const int rc = leaf_stats(k, &m);
         if (rc) return fail(c, rc, k->err);
@@ -4040,7 +4048,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         int r2 = part_ensure_buffers(c, r, c->kid_q0[r + 1] - c->kid_q0[r]);
         if (r2) return r2;
         if (local_sn[r] == 0u) {  // nothing of the sampled prefix in this part: empty lists, no launch
-            k->timing_valid = false;
+            call_forgotten(k);
             HVS_HIP(k, hipMemsetAsync(k->d_out_ids + (size_t)q0 * K, 0xFF, (size_t)nq * K * sizeof(uint32_t), k->stream));
             HVS_HIP(k, hipStreamSynchronize(k->stream));
             return HVS_OK;
@@ -4214,14 +4222,12 @@ int check_device_buffers(hvs_ctx* c, const void* a, const void* b, void* stream,
 // What hvs_within_stats and hvs_after_stats start with on one GPU: the call is over, *out is zeroed, and, if the call ran with the
 // feature (`on`), v holds its counters from slot `first` on
 template <typename Info, size_t N>
-int leaf_call_counters(hvs_ctx* c, Info* out, bool on, uint32_t first, unsigned long long (&v)[N])
+int leaf_call_counters(hvs_ctx* c, Info* out, bool on, int first, unsigned long long (&v)[N])
 {
-    if (!c->timing_valid) return fail(c, HVS_ESTATE, "no query has run yet");
-    int rc = leaf_sync(c);
+    int rc = call_required(c);
     if (rc) return rc;
     *out = Info{};
-    if (on) HVS_HIP(c, hipMemcpy(v, c->d_counters + first, sizeof(v), hipMemcpyDeviceToHost));
-    return HVS_OK;
+    return on ? call_counters(c, first, v) : HVS_OK;
 }
 // ... and end with: under category sets the counted slots are the sub-lists', and a query is under-full when the merge found
 // fewer than k keys
@@ -4237,9 +4243,9 @@ int in_underfull(hvs_ctx* c, uint32_t* underfull)
 int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
 {
     unsigned long long v[2] = {0, 0};
-    const int rc = leaf_call_counters(c, out, c->qs.call_capped, kCountersWithin, v);
+    const int rc = leaf_call_counters(c, out, c->qs.call_capped, HVS_CNT_WITHIN_SLOTS, v);
     if (rc || !c->qs.call_capped) return rc;
-    out->capped_queries = c->timing.nq;
+    out->capped_queries = c->call.timing.nq;
     out->within_slots = v[0];
     out->underfull_queries = (uint32_t)v[1];
     return in_underfull(c, &out->underfull_queries);
@@ -4248,9 +4254,9 @@ int leaf_within_stats(hvs_ctx* c, hvs_within_info* out)
 int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
 {
     unsigned long long v[3] = {0, 0, 0};
-    const int rc = leaf_call_counters(c, out, c->qs.call_after, kCountersAfter, v);
+    const int rc = leaf_call_counters(c, out, c->qs.call_after, HVS_CNT_AFTER_SLOTS, v);
     if (rc || !c->qs.call_after) return rc;
-    out->cursor_queries = c->timing.nq;
+    out->cursor_queries = c->call.timing.nq;
     out->after_slots = v[0];
     out->underfull_queries = (uint32_t)v[1];
     out->exhausted_queries = (uint32_t)v[2];  // (under category sets: counted per sub-query, as the slots are)
@@ -4577,7 +4583,7 @@ int hvs_load_data(hvs_ctx* c, const float* rows, uint32_t n)
         hvs_ctx* k = c->kids[r];
         int r2 = begin_data(k, n);
         if (r2) return r2;
-        HVS_HIP(k, hipEventRecord(k->ev_q0, k->stream));
+        HVS_HIP(k, hipEventRecord(k->call.ev_q0, k->stream));
         const size_t off = (size_t)r0[r] * HVS_DCOLS, cnt = (size_t)(r0[r + 1] - r0[r]) * HVS_DCOLS;
         if ((r2 = upload_rows(k, k->d_data + off, rows + off, cnt))) return r2;
         HVS_HIP(k, hipStreamSynchronize(k->stream));
@@ -4594,7 +4600,7 @@ int hvs_load_data(hvs_ctx* c, const float* rows, uint32_t n)
                 HVS_HIP(k, hipMemcpyPeerAsync(k->d_data + off, k->device, c->kids[p]->d_data + off, c->kids[p]->device, cnt * sizeof(float),
                                               k->stream));
         }
-        HVS_HIP(k, hipEventRecord(k->ev_q1, k->stream));
+        HVS_HIP(k, hipEventRecord(k->call.ev_q1, k->stream));
         HVS_HIP(k, hipStreamSynchronize(k->stream));
         k->n = n;
         return finish_data(k);
@@ -4839,7 +4845,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
         if (!rc) rc = attach_for_call(c, max_d2, after_d, after_i, nq);
         if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
         if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
-        c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->call.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return rc;
     }
     cut_queries(c, nq);
@@ -4849,10 +4855,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
         // the caller's result arrays
         rc = for_each_leaf(c, [&](uint32_t r) -> int {
             const uint32_t a = c->kid_q0[r], m = c->kid_q0[r + 1] - a;
-            if (m == 0u) {
-                c->kids[r]->timing_valid = false;
-                return HVS_OK;
-            }
+            if (m == 0u) return call_forgotten(c->kids[r]);
             return leaf_query(c->kids[r], q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, out_ids + (size_t)a * c->k,
                               out_dists ? out_dists + (size_t)a * c->k : nullptr, nullptr, max_d2 ? max_d2 + a : nullptr,
                               after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr);
@@ -4870,10 +4873,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
             rc = for_each_leaf(c, [&](uint32_t r) -> int {
                 const uint32_t a = c->kid_q0[r], m = c->kid_q0[r + 1] - a;
                 hvs_ctx* k = c->kids[r];
-                if (m == 0u) {
-                    k->timing_valid = false;
-                    return HVS_OK;
-                }
+                if (m == 0u) return call_forgotten(k);
                 if (r == 0u) {  // its results are already where the gather wants them: plain resident run of its slice
                     int r2 = leaf_upload_queries(k, q_rows, m);
                     if (r2) return r2;
@@ -4894,7 +4894,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
                 rc = fail(c, HVS_EHIP, "hvs_query: download of the gathered results failed");
         }
     }
-    c->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->call.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }
 
@@ -4929,10 +4929,9 @@ int hvs_last_reruns(hvs_ctx* c, int which, uint32_t* out_idx, uint32_t cap)
     if (which != 0 && which != 1) return fail(c, HVS_EINVAL, "hvs_last_reruns: which is 0 (exact) or 1 (retry)");
     int rc = leaf_sync(c);
     if (rc) return rc;
-    const uint32_t len = which ? c->retry_queries : c->fallback_queries;
+    const auto [d_list, len] = c->call.reruns()[which];  // (whether or not there is a last call to report: DESIGN 3.5a)
     const uint32_t m = std::min(len, cap);
-    if (m && out_idx)
-        HVS_HIP(c, hipMemcpy(out_idx, which ? c->d_retry_list : c->d_ovf_list, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (m && out_idx) HVS_HIP(c, hipMemcpy(out_idx, d_list, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return (int)len;
 }
 
@@ -4956,7 +4955,7 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
             agg.load_ms = std::max(agg.load_ms, t.load_ms);
             agg.engine = t.engine;
             agg.n_gpus += 1;
-            agg.host_ms = c->host_ms;
+            agg.host_ms = c->call.host_ms;
         },
         [&](hvs_timing& agg) {
             // every part answered all the queries (a part outside the sampled prefix launched nothing); exchange and merge follow the slowest
@@ -4964,7 +4963,7 @@ int hvs_last_timing(hvs_ctx* c, hvs_timing* out)
             agg.nq = c->part_call_nq;
             if (!agg.n_gpus) agg.engine = HVS_ENGINE_EXACT_SCAN;
             agg.n_gpus = (uint32_t)c->kids.size();
-            agg.host_ms = c->host_ms;
+            agg.host_ms = c->call.host_ms;
         });
 }
 

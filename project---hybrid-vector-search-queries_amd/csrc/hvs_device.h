@@ -16,6 +16,44 @@
 #define HVS_WAVE 64
 
 // ---------------------------------------------------------------------------------------------
+// The per-call device counters (u64 each; host side: HvsCallState::d_counters, DESIGN 3.5a has the table of writers and
+// readers).  Kernels add to `counters[slot]`, the host reads runs of slots by the same names.  The numbers are fixed: a slot
+// that nothing uses is a gap, never re-used by renumbering.
+// ---------------------------------------------------------------------------------------------
+enum HvsCounter : int {
+    HVS_CNT_PAIRS = 0,              // (query, row) pairs that pass the predicate          -> hvs_timing.pairs
+    HVS_CNT_SCANNED = 1,            // pairs a kernel evaluated or filtered                -> hvs_timing.scanned_pairs
+    HVS_CNT_RESCORED = 2,           // filter survivors handed to the exact re-scoring     -> hvs_timing.rescored_pairs
+    HVS_CNT_UNUSED_3 = 3,
+    // base handed to the exact engine's batches whose pairs must not reach the report (re-runs of the exact list; sub-batches
+    // whose pairs were counted beforehand): their PAIRS and SCANNED land in slots 4 and 5, which nothing reads
+    HVS_CNT_RERUN_SINK = 4,
+    HVS_CNT_RERUN_SINK_SCANNED = 5,
+    HVS_CNT_UNUSED_6 = 6,
+    HVS_CNT_UNUSED_7 = 7,
+    HVS_CNT_DEAD_SURVIVORS = 8,     // survivors dropped because the row is dead           -> hvs_mask_info.dead_survivors
+    HVS_CNT_TAIL_PAIRS = 9,         // rows behind the index: pairs evaluated              -> hvs_append_info.tail_pairs
+    HVS_CNT_TAIL_KEYS = 10,         // ... keys admitted                                   -> hvs_append_info.tail_admitted
+    HVS_CNT_STALE_PAIRS = 11,       // stale rows: pairs evaluated                         -> hvs_update_info.stale_pairs
+    HVS_CNT_STALE_KEYS = 12,        // ... keys admitted                                   -> hvs_update_info.stale_admitted
+    HVS_CNT_STALE_SURVIVORS = 13,   // survivors dropped for staleness alone               -> hvs_update_info.stale_survivors
+    HVS_CNT_WITHIN_SLOTS = 14,      // distance caps: slots kept                           -> hvs_within_info.within_slots
+    HVS_CNT_WITHIN_UNDERFULL = 15,  // ... queries left with fewer than k                  -> hvs_within_info.underfull_queries
+    HVS_CNT_AFTER_SLOTS = 16,       // result cursors: slots kept                          -> hvs_after_info.after_slots
+    HVS_CNT_AFTER_UNDERFULL = 17,   // ... queries left with fewer than k                  -> hvs_after_info.underfull_queries
+    HVS_CNT_AFTER_EXHAUSTED = 18,   // ... cursors behind every key                        -> hvs_after_info.exhausted_queries
+    HVS_CNT_UNUSED_19 = 19,
+    HVS_CNT_COUNT = 20
+};
+// the host reads these as runs (one copy each), and hvs_scan_rows_into_lists writes slots CNT and CNT + 1
+static_assert(HVS_CNT_SCANNED == HVS_CNT_PAIRS + 1 && HVS_CNT_RESCORED == HVS_CNT_PAIRS + 2, "hvs_timing's three counts are one run");
+static_assert(HVS_CNT_RERUN_SINK_SCANNED == HVS_CNT_RERUN_SINK + HVS_CNT_SCANNED, "the sink takes a batch's PAIRS and SCANNED");
+static_assert(HVS_CNT_TAIL_KEYS == HVS_CNT_TAIL_PAIRS + 1, "hvs_scan_rows_into_lists: keys admitted follow pairs evaluated");
+static_assert(HVS_CNT_STALE_KEYS == HVS_CNT_STALE_PAIRS + 1 && HVS_CNT_STALE_SURVIVORS == HVS_CNT_STALE_PAIRS + 2, "one run, and CNT + 1");
+static_assert(HVS_CNT_WITHIN_UNDERFULL == HVS_CNT_WITHIN_SLOTS + 1, "hvs_within_stats reads one run");
+static_assert(HVS_CNT_AFTER_UNDERFULL == HVS_CNT_AFTER_SLOTS + 1 && HVS_CNT_AFTER_EXHAUSTED == HVS_CNT_AFTER_SLOTS + 2, "hvs_after_stats reads one run");
+
+// ---------------------------------------------------------------------------------------------
 // Query parameters: reference include/optimized_parallel.hpp:93-96
 //   query_type = uint32(q[0]); v = int32(q[1]) (truncation); l = q[2]; r = q[3]
 // `nodes[j][0] == v` compares the row's float with float(v).  uint32(t) truncates toward zero, so t in (-1, 0) is

@@ -1257,7 +1257,7 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
         B.gord[g] = B.rank[g * HVS_GROUP] == 4u ? 1u : 0u;
         B.paircnt[g] = 0;
         B.goverflow[g] = 0;
-        if (count_pairs && spairs) atomicAdd(&counters[0], spairs);
+        if (count_pairs && spairs) atomicAdd(&counters[HVS_CNT_PAIRS], spairs);
     }
     if (rot) {
         // B fragments cut from the int8 image of the rotated queries (all 128 K slots carry data)
@@ -1527,7 +1527,7 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
         }
     }
     if (nchunks == 1u) B.candcnt[slot] = cnt;
-    if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nscan);
+    if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1644,7 +1644,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         }
     }
     if (have_q) cand_cnt[(size_t)chunk * B.nslots + slot] = cnt;
-    if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nscan);
+    if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
 }
 
 // passing pairs of a sampled prefix (sn < n): the position range over-counts, so count ids < sn exactly
@@ -1666,7 +1666,7 @@ __global__ void hvs_k_count_prefix_pairs(HvsBatch B, const uint32_t* __restrict_
             c += id < sn ? 1u : 0u;
     }
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63u) == 0u && c) atomicAdd(&counters[0], (unsigned long long)c);
+    if ((threadIdx.x & 63u) == 0u && c) atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)c);
 }
 
 // Live-row mask without a sampled prefix (cut = n): the live rows of a position range come from a prefix count over the
@@ -1693,7 +1693,7 @@ __global__ void hvs_k_count_live_pairs(HvsBatch B, const uint32_t* __restrict__ 
     }
     unsigned long long s = c;
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(&counters[0], s);
+    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(&counters[HVS_CNT_PAIRS], s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1978,7 +1978,7 @@ __device__ __forceinline__ void hvs_filter_finish(const HvsBatch& B, const HvsFi
 {
     if (!it.active) return;
     hvs_filter_flush(B, it.g, lane, lbuf, wcnt);
-    if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nblocks * 32ull * HVS_GROUP);
+    if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nblocks * 32ull * HVS_GROUP);
 }
 
 // operand / accumulator types and the MFMA step of the two tile formats
@@ -2693,7 +2693,7 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
     }
     if (active) {
         flush();
-        if (lane == 0u) atomicAdd(&counters[1], (unsigned long long)nblocks * 32ull * HVS_GROUP);
+        if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nblocks * 32ull * HVS_GROUP);
     }
   }  // next work item (the last stage barrier has released the stage buffers)
 }
@@ -2715,11 +2715,11 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 // the vector and load instructions per pair.)
 // ---------------------------------------------------------------------------------------------
 // E16: entries of the 16x16 tile format (hvs_entry16_*) instead of the 32x32 formats' (hvs_entry_*)
-// MASKED (live-row mask): a survivor whose row is dead is dropped beside the sampled-prefix test and counted in counters[8]
+// MASKED (live-row mask): a survivor whose row is dead is dropped beside the sampled-prefix test and counted in HVS_CNT_DEAD_SURVIVORS
 // (hvs_mask_info.dead_survivors) -- the test that keeps dead rows out of every answer, whatever the tiles say.
 // While rows are stale (hvs_update_rows) `live` is the index-validity mask, live AND NOT stale, in the two-plane
 // form of HVS_RESCORE_TWO_MASKS, which the host announces in bit 31 of `n` (an index covers at most 2^29 rows): a dropped
-// survivor whose row is live -- dropped for staleness alone -- goes to counters[13] (hvs_update_info.stale_survivors) instead.
+// survivor whose row is live -- dropped for staleness alone -- goes to HVS_CNT_STALE_SURVIVORS (hvs_update_info.stale_survivors) instead.
 #define HVS_RESCORE_TWO_MASKS 0x80000000u  // in `n`: live[W + i] (W = 2 ceil(n / 64) words) holds the row mask's bits of the indexed rows
 // AFTER (result cursors; `after_lo` is not read otherwise): a pair's key is appended only if it is >= after_lo of its
 // slot's query -- beside the threshold test, which it does not replace.  The kernel reads its launch dimensions, which lie
@@ -2921,14 +2921,14 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
         cur = nxt;
     }
     retire();
-    if (lane == 0u && npairs) atomicAdd(&counters[2], (unsigned long long)npairs);
+    if (lane == 0u && npairs) atomicAdd(&counters[HVS_CNT_RESCORED], (unsigned long long)npairs);
     if constexpr (MASKED) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ndead += __shfl_xor(ndead, o);
-        if (lane == 0u && ndead) atomicAdd(&counters[8], (unsigned long long)ndead);
+        if (lane == 0u && ndead) atomicAdd(&counters[HVS_CNT_DEAD_SURVIVORS], (unsigned long long)ndead);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nstale += __shfl_xor(nstale, o);
-        if (lane == 0u && nstale) atomicAdd(&counters[13], (unsigned long long)nstale);
+        if (lane == 0u && nstale) atomicAdd(&counters[HVS_CNT_STALE_SURVIVORS], (unsigned long long)nstale);
     }
 }
 
@@ -3221,7 +3221,7 @@ __global__ void hvs_k_collect_overflow(HvsBatch B, uint32_t* __restrict__ list_e
 // Filter batches: lists = B.cand (what hvs_k_rescore wrote at the last level), thresholds = B.tau, between the last
 // re-scoring and the final merge.  Range scans of the exact engine: lists = one more chunk of its candidate lists, no
 // thresholds, and only slots [slot_lo, slot_hi) take keys (the others' full scans walk the tail themselves).
-// counters (`count` != 0: not in re-run batches): [0] passing pairs, [9] pairs evaluated, [10] keys admitted.
+// counters (`count` != 0: not in re-run batches): HVS_CNT_PAIRS passing pairs, HVS_CNT_TAIL_PAIRS pairs evaluated, HVS_CNT_TAIL_KEYS keys admitted.
 // ---------------------------------------------------------------------------------------------
 struct HvsTailOut {
     uint64_t* lists;            // list of slot s: lists + s * stride
@@ -3407,7 +3407,7 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nadm += __shfl_xor(nadm, o);
         if (lane == 0u && hm != 0ull) {
-            atomicAdd(&counters[0], (unsigned long long)npass);
+            atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)npass);
             atomicAdd(&counters[CNT], (unsigned long long)nrows * (unsigned long long)__popcll(hm));
             if (nadm) atomicAdd(&counters[CNT + 1], (unsigned long long)nadm);
         }
@@ -3424,7 +3424,7 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
                                                                          unsigned long long* __restrict__ counters, int count,
                                                                          const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, 9, AFTER>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live, after_lo);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, HVS_CNT_TAIL_PAIRS, AFTER>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live, after_lo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3434,7 +3434,7 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
 // flags, HvsTailOut, and it is launched right behind it, so that a slot's list takes tail keys, then stale keys (a lane's
 // segment starts at the list's fill on entry).  The key carries the row's own id; MASKED tests the row mask (d_live: a stale
 // row is dead to the index only) on that id.
-// counters (`count` != 0): [0] passing pairs, [11] pairs evaluated, [12] keys admitted.
+// counters (`count` != 0): HVS_CNT_PAIRS passing pairs, HVS_CNT_STALE_PAIRS pairs evaluated, HVS_CNT_STALE_KEYS keys admitted.
 // ---------------------------------------------------------------------------------------------
 template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false>
 __global__ __launch_bounds__(256, 2) void hvs_k_scan_stale(const float* __restrict__ D, const float* __restrict__ Q, HvsBatch B,
@@ -3442,5 +3442,5 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_stale(const float* __restri
                                                            unsigned long long* __restrict__ counters, int count,
                                                            const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, 11, AFTER>(D, Q, B, O, stale_ids, 0u, m, counters, count, live, after_lo);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, HVS_CNT_STALE_PAIRS, AFTER>(D, Q, B, O, stale_ids, 0u, m, counters, count, live, after_lo);
 }

@@ -497,8 +497,8 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     }
     if (have_q) cand_cnt[(size_t)chunk * nq_pad + slot] = cnt;
     if (wave_active && lane == 0u) {
-        atomicAdd(&counters[0], (unsigned long long)npass);
-        atomicAdd(&counters[1], (unsigned long long)nscan);
+        atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)npass);
+        atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
     }
 }
 
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
 // The keys within the cap are a prefix of the query's keys in key order, so what is left is the capped answer's matched part
 // and the slots behind it are padded like any under-full answer's.  Whatever the stages in front admitted, no key beyond the
 // cap passes here (nor a NaN distance: `NaN <= cap` is false).
-// counters[14] += slots kept, counters[15] += 1 for an under-full query (hvs_within_info).
+// HVS_CNT_WITHIN_SLOTS += slots kept, HVS_CNT_WITHIN_UNDERFULL += 1 for an under-full query (hvs_within_info).
 __device__ __forceinline__ uint32_t hvs_keep_within(uint64_t* buf, uint32_t cnt, float cap, uint32_t knn, uint32_t lane,
                                                     unsigned long long* __restrict__ counters, bool count)
 {
@@ -531,15 +531,15 @@ __device__ __forceinline__ uint32_t hvs_keep_within(uint64_t* buf, uint32_t cnt,
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (count && lane == 0u) {
-        if (kept) atomicAdd(&counters[14], (unsigned long long)kept);
-        if (kept < knn) atomicAdd(&counters[15], 1ull);
+        if (kept) atomicAdd(&counters[HVS_CNT_WITHIN_SLOTS], (unsigned long long)kept);
+        if (kept < knn) atomicAdd(&counters[HVS_CNT_WITHIN_UNDERFULL], 1ull);
     }
     return kept;
 }
 
 // The final kernels' share of the cursors (hvs_k_select, hvs_k_merge with AFTER): every stage in front admits keys >= lo only,
 // so this drops nothing -- it tests defensively, as hvs_keep_within does, and counts for hvs_after_info:
-// counters[16] += slots kept, counters[17] += 1 for an under-full query, counters[18] += 1 for an exhausted cursor.
+// HVS_CNT_AFTER_SLOTS += slots kept, HVS_CNT_AFTER_UNDERFULL += 1 for an under-full query, HVS_CNT_AFTER_EXHAUSTED += 1 for an exhausted cursor.
 __device__ __forceinline__ uint32_t hvs_keep_after(uint64_t* buf, uint32_t cnt, uint64_t lo, uint32_t knn, uint32_t lane,
                                                    unsigned long long* __restrict__ counters, bool count)
 {
@@ -555,9 +555,9 @@ __device__ __forceinline__ uint32_t hvs_keep_after(uint64_t* buf, uint32_t cnt, 
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (count && lane == 0u) {
-        if (kept) atomicAdd(&counters[16], (unsigned long long)kept);
-        if (kept < knn) atomicAdd(&counters[17], 1ull);
-        if (lo == HVS_AFTER_NOTHING) atomicAdd(&counters[18], 1ull);
+        if (kept) atomicAdd(&counters[HVS_CNT_AFTER_SLOTS], (unsigned long long)kept);
+        if (kept < knn) atomicAdd(&counters[HVS_CNT_AFTER_UNDERFULL], 1ull);
+        if (lo == HVS_AFTER_NOTHING) atomicAdd(&counters[HVS_CNT_AFTER_EXHAUSTED], 1ull);
     }
     return kept;
 }

@@ -2,7 +2,7 @@
 functions of the data, the queries and the thresholds (csrc/hvs_filter.h: hvs_k_merge, hvs_k_rescore, hvs_guess_m; csrc/hvs.hip:
 run_batch_mfma, resolve_overflow).  numpy only; nothing here reads a count from the device.
 
-What the device counts.  hvs_k_rescore adds one to counters[2] for every set bit of a survivor entry whose position lies in
+What the device counts.  hvs_k_rescore adds one to counters[HVS_CNT_RESCORED] for every set bit of a survivor entry whose position lies in
 the slot's own range [ra, rb) -- before the sampled-prefix test `id < sn` and before any liveness test.  For one batch
 
     rescored_pairs = sum over queries, levels j = 1..K of  #{pos in [ra, rb): block_level(pos / 32) = j, S(q, perm[pos]) >= theta_j(q)}
