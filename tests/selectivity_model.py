@@ -40,6 +40,55 @@ and `hi` est >= theta - mu_q, theta rounded down to f32 as the kernel does.
 
 Grid edges.  The device takes log2((b - a) / seen) with __log2f; a query whose 8 log2(.) - 0.02 lies within 1e-3 of an integer
 at any level where the guess table is consulted is `excluded`: the model cannot say which grid point the device read.
+
+Attachments (walk's caps=, after=, live=; all None: the walk above, to the unit).  Each rule with the code it restates:
+
+Caps.
+* hvs_k_norm_caps stores hvs_norm_cap(cap) (`c >= 0.0f ? c : HVS_CAP_NOTHING`): a NaN or negative cap is -1.  hvs_k_prep<true>
+  starts the slot there (`B.tau[s] = cap;`) in every batch of the call, the retry batch included (prep_batch launches the same
+  kernel for a list), and sets level 1's theta from it (`nothing ? 0x7FFFFFFF : hvs_theta_i8(B, s, cap, bounds, qz)`), also for a
+  range that misses level 0.  hvs_theta_* treat +inf as before (`if (tau < __builtin_inff())`): a cap of +inf is no cap.
+* HVS_CAP_NOTHING: theta is "nothing" from hvs_k_prep on and stays so while the merges return early.  A merge that RUNS re-derives
+  theta from tau = -1 by the closed expression (hvs_k_merge: `hvs_theta_i8(B, slot, tau, bounds, qz)`, no `nothing` branch there),
+  which no row of the test cases reaches either; the model follows the code, not the shorthand "nothing at every level".
+* Final check (hvs_k_merge<FINAL, ., ., CAPPED>): `tau_bits == __float_as_uint(cap) || (cnt >= knn && dmax_bits <= tau_bits)`, then
+  hvs_keep_within drops the keys beyond the cap.
+* Which seed form.  run_batch_mfma: `if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = min(l0blocks, ...)` --
+  a batch of 112 queries has a handful of seed waves against kSeedWaves = 16384 and 16 or 18 level-0 blocks against fcap / 32 =
+  128: the CHUNKED form, in the first pass and in the retry pass.  It appends every row of the range at level 0 without a threshold
+  test (`if (pass && kk < kend) mylist[kk] = ...`; with cursors `if (pass && key >= key_lo)`), so cand[0] and the overflow test count
+  them all.  The tau trajectory is the same as the unchunked form's (`pass && dist <= tau`): keys beyond the cap are the largest of
+  a list, tau_next = min(tau, m-th smallest held) <= cap ignores them (fewer than m within the cap: the m-th is beyond it and the
+  minimum is tau; at least m: the m-th is the same key), the top-k truncation drops them first, hvs_k_rescore admits none
+  (`dist <= B.tau[slot]`), and in the final check k keys held with one beyond tau fail exactly where fewer than k held would.
+  The one difference: a list that took only keys beyond the cap makes the merge run (see HVS_CAP_NOTHING above).
+
+Cursors.
+* hvs_k_norm_after stores hvs_after_lo = the cursor's key + 1, ~0 for an exhausted cursor (`id == 0xFFFFFFFFu`); the key is
+  hvs_make_key's (distance bits, id).  Admission is the old test AND `key >= lo`: hvs_k_seed_exact (`key >= key_lo`), hvs_k_rescore
+  (`pend[u] = qa != 0xFFFFFFFFu && pend_key[u] >= lo[qa]`, behind `dist <= B.tau[slot[u]]`), hvs_keep_after in the final merge.
+* HVS_CNT_RESCORED is added per round (`npairs += cnt`) in front of score_list, i.e. before admission: rows in front of the cursor
+  with S >= theta count.  hvs_guess_m and hvs_rows_seen_before take ra, rb only: F stays the range's own.
+* An exhausted cursor admits nothing, every merge returns early, tau never leaves its start: with no cap every row of the range
+  is a survivor at every level >= 1.  The retry pass runs the same AFTER kernels: proven over the keys behind the cursor.
+
+Mask.
+* A dead row enters no list: hvs_k_seed_exact (`if (!hvs_row_live(live, id)) continue;`), hvs_k_rescore (`ok[u] = ok[u] && !dead`).
+* hvs_k_patch_tiles gives its tile entry the padding encoding: INT8 `norms[...] = HVS_I8_PAD_NORM`, the row's int8 components stay
+  (S = qq.dq - 2^30); 16-bit floats: components zero and h0 = -1e30 (BF16) / -65504 (FP16).  Such a row is a survivor exactly
+  where theta is "keep everything" (tau still +inf) or clamped there by a cap like 3e38 (`th <= -2147483647.0 ? 0x80000001`).
+  rescored_pairs counts it (`npairs += cnt` is in front of the liveness test) and HVS_CNT_DEAD_SURVIVORS counts it
+  (`ndead += (dead && !stale && t4 == 0u)`), both before `id < sn`: dead_lo / dead_hi, which coincide in every case here.
+* hvs_rows_seen_before counts positions, not live rows.  The sampled prefix is `id < cut`, cut = the id of live row number
+  sn_live (hvs_mask_plan through cut_for): mask_cut.
+* Bounds and quantisation are NOT recomputed when rows die or revive: build_tiles launches the build kernels over all rows of D
+  (`c->d_data, n, o.perm`, no mask) and patch_tiles runs behind it; set_quant's hvs_k_minmax / hvs_k_quant_params walk all
+  indexed rows likewise.  bound_model is therefore fed all rows, whatever the mask.
+
+Wrong rules (walk's wrong=, one of WRONG; tests/test_selectivity_model_cpu.py shows that each would be seen): cap_ignored (tau
+starts at +inf, the final kernel still drops), cap_retry_from_inf, cap_check_inf (`tau == +inf` in the capped check),
+cap_level1_only (theta falls back to "keep everything" behind a merge that returned early), after_in_lists, after_F_behind,
+mask_unpatched, mask_F_live, mask_in_stat.
 """
 from __future__ import annotations
 
@@ -209,16 +258,17 @@ def plan_guess_m(k, idx, pfail):
     return _m_cache[key]
 
 
-def guess_m(L, level, a, b, k, guess, pfail, mid):
-    """hvs_guess_m for the threshold of `level`: (m, on_edge).  guess = "proven": m = k at every level."""
+def guess_m(L, level, a, b, k, guess, pfail, mid, counted=None):
+    """hvs_guess_m for the threshold of `level`: (m, on_edge).  guess = "proven": m = k at every level.
+    counted = (rows, seen): a WRONG rule's counts in place of the positions' (the walk's wrong= rules only)."""
     if guess == "proven":
         return k, False
     if b - a <= k:
         return k, False
-    seen = L.seen_before(level, a, b)
+    rows, seen = (b - a, L.seen_before(level, a, b)) if counted is None else counted
     if seen == 0:
         return k, False
-    lf = np.log2(np.float32(b - a) / np.float32(seen), dtype=np.float32)
+    lf = np.log2(np.float32(rows) / np.float32(seen), dtype=np.float32)
     x = np.float32(8.0) * lf - np.float32(0.02)
     edge = abs(float(x) - round(float(x))) < EDGE_TOL
     idx = min(max(int(np.ceil(x)), 0), GUESS_STEPS - 1)
@@ -274,6 +324,13 @@ class Prepared:
         self.ord = orderings(nodes)
         self.ranges = [self.ord.query_range(q) for q in np.asarray(queries, np.float32)]
 
+    def dead_score(self, q, ids):
+        """What the filter computes for a row that carries the tombstone of hvs_k_patch_tiles.  INT8: the row keeps its int8
+        components, its accumulator init is HVS_I8_PAD_NORM.  16-bit floats: components zero, h0 = the padding bias."""
+        if self.i8:
+            return self.score[q, ids] - np.asarray(self.info["nh"])[ids] + float(HVS_I8_PAD_NORM)
+        return np.full(len(ids), -65504.0 if self.fmt == BM.FP16 else -1.0e30)
+
     def theta(self, q, tau, scale):
         """hvs_k_merge's threshold of query q for tau, in its operation order: (theta, half width of the bracket)."""
         if not np.isfinite(tau):
@@ -297,77 +354,181 @@ class Prepared:
         return float(tf), float(info["mu"][q])
 
 
-def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap):
-    """One batch's walk of query q: dict(lo, hi [K], cand [K + 1], fails, overflow, edge, held)."""
+HVS_I8_PAD_NORM = -(1 << 30)
+HVS_CAP_NOTHING = np.float32(-1.0)
+HVS_AFTER_NOTHING = 0xFFFFFFFFFFFFFFFF
+NAN_BITS = 0x7FC00000
+WRONG = ("cap_ignored", "cap_retry_from_inf", "cap_check_inf", "cap_level1_only", "after_in_lists", "after_F_behind", "mask_unpatched",
+         "mask_F_live", "mask_in_stat")
+
+
+def norm_cap(c):
+    """hvs_norm_cap: a NaN or negative cap is HVS_CAP_NOTHING."""
+    c = np.float32(c)
+    return c if c >= 0.0 else HVS_CAP_NOTHING
+
+
+def make_keys(dist, ids):
+    """hvs_make_key: (distance bits, one NaN) << 32 | id."""
+    d = np.ascontiguousarray(dist, np.float32)
+    bits = np.where(np.isnan(d), np.uint32(NAN_BITS), d.view(np.uint32)).astype(np.uint64)
+    return (bits << np.uint64(32)) | np.asarray(ids).astype(np.uint64)
+
+
+def key_dists(keys):
+    return (np.asarray(keys, np.uint64) >> np.uint64(32)).astype(np.uint32).view(np.float32)
+
+
+def key_ids(keys):
+    return (np.asarray(keys, np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def after_lo(dist, rid):
+    """hvs_after_lo with row0 = 0: the cursor's key + 1; ~0 for an exhausted cursor."""
+    if int(rid) == 0xFFFFFFFF:
+        return HVS_AFTER_NOTHING
+    return int(make_keys(np.array([dist], np.float32), np.array([rid], np.uint32))[0]) + 1
+
+
+def _f32_bits(x):
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None, live=None, wrong=None, retry=False):
+    """One batch's walk of query q: dict(lo, hi, dead_lo, dead_hi [K], cand [K + 1], fails, overflow, edge, keys).
+    cap: the query's cap as the caller gave it, or None; lo_key: hvs_after_lo of its cursor, or None; live: bool [n], or None."""
     ordn, a, b = P.ranges[q]
     K = L.K
-    out = dict(lo=np.zeros(K, np.int64), hi=np.zeros(K, np.int64), cand=np.zeros(K + 1, np.int64), fails=False, overflow=False,
-               edge=False, held=np.empty(0, np.float32))
+    out = dict(lo=np.zeros(K, np.int64), hi=np.zeros(K, np.int64), dead_lo=np.zeros(K, np.int64), dead_hi=np.zeros(K, np.int64),
+               cand=np.zeros(K + 1, np.int64), fails=False, overflow=False, edge=False, keys=np.empty(0, np.uint64))
     if P.hopeless[q] or b <= a:
         return out
     ids = (P.ord.perm_t if ordn else P.ord.perm_ct)[a:b]
     lvl = L.block_level(np.arange(a, b) // 32)
-    dist, score, live = P.dist[q, ids], P.score[q, ids], ids < sn
-    tau = np.inf
-    held = np.empty(0, np.float32)
+    dist, score = P.dist[q, ids], P.score[q, ids]
+    keys = make_keys(dist, ids)
+    alive = np.ones(ids.size, bool) if live is None else live[ids]
+    if live is not None and wrong != "mask_unpatched":
+        score = np.where(alive, score, P.dead_score(q, ids))
+    adm = ids < sn                                        # who may enter a list at all
+    if wrong != "mask_in_stat":
+        adm = adm & alive
+    behind = np.ones(ids.size, bool) if lo_key is None else keys >= np.uint64(lo_key)
+    if wrong != "after_in_lists":
+        adm = adm & behind
+    capf = None if cap is None else norm_cap(cap)
+    walk_cap = capf                                       # the cap as far as thresholds and the final check know it
+    if wrong == "cap_ignored" or (retry and wrong == "cap_retry_from_inf"):
+        walk_cap = None
+    tau = np.inf if walk_cap is None else float(walk_cap)
+    nothing = walk_cap is not None and walk_cap == HVS_CAP_NOTHING      # hvs_k_prep<true>: theta = "nothing" until a merge re-derives it
+    forgot = False
+    held = np.empty(0, np.uint64)
     for j in range(K + 1):
         at = lvl == j
-        if j > 0:
-            th, w = P.theta(q, tau, scale)
-            out["lo"][j - 1] = int((score[at] >= th + w).sum())
-            out["hi"][j - 1] = int((score[at] >= th - w).sum())
-        new = dist[at & live & (dist <= tau)]
-        out["cand"][j] = new.size
-        out["overflow"] |= new.size > fcap
-        held = np.sort(np.concatenate([held, new]))[:k]
-        if j < K and new.size > 0:          # (hvs_k_merge: nothing new at this level -> tau and theta stand)
-            m, edge = guess_m(L, j + 1, a, b, k, guess, pfail, mid)
-            out["edge"] |= edge
-            if held.size >= m:
-                tau = min(tau, float(held[m - 1]))
-    out["fails"] = bool(np.isfinite(tau) and not (held.size >= k and float(held[k - 1]) <= tau))
-    out["held"] = held
+        if j > 0 and not nothing:
+            th, w = P.theta(q, np.inf if forgot else tau, scale)
+            s_at = score[at]
+            out["lo"][j - 1] = int((s_at >= th + w).sum())
+            out["hi"][j - 1] = int((s_at >= th - w).sum())
+            d_at = score[at & ~alive]
+            out["dead_lo"][j - 1] = int((d_at >= th + w).sum())
+            out["dead_hi"][j - 1] = int((d_at >= th - w).sum())
+        within = at & adm & (dist <= tau)
+        # level 0: the chunked seed (a batch of 112 queries: seed_chunks > 1) appends without a threshold test
+        out["cand"][j] = int((at & adm).sum()) if j == 0 else int(within.sum())
+        out["overflow"] |= out["cand"][j] > fcap
+        held = np.sort(np.concatenate([held, keys[within]]))[:k]
+        if j < K:
+            if out["cand"][j] > 0:      # (hvs_k_merge: nothing new at this level -> tau and theta stand)
+                nothing = forgot = False
+                counted = None
+                if wrong == "mask_F_live":
+                    counted = (int(alive.sum()), int((alive & (lvl < j + 1)).sum()))
+                elif wrong == "after_F_behind":
+                    counted = (int(behind.sum()), int((behind & (lvl < j + 1)).sum()))
+                m, edge = guess_m(L, j + 1, a, b, k, guess, pfail, mid, counted)
+                out["edge"] |= edge
+                if held.size >= m:
+                    tau = min(tau, float(key_dists(held[m - 1:m])[0]))
+            elif wrong == "cap_level1_only" and walk_cap is not None:
+                forgot = True
+    full = held.size >= k and float(key_dists(held[k - 1:k])[0]) <= tau
+    if walk_cap is None or wrong == "cap_check_inf":
+        untouched = tau == np.inf
+    else:
+        untouched = _f32_bits(tau) == _f32_bits(walk_cap)
+    out["fails"] = not (untouched or full)
+    if capf is not None:                # hvs_keep_within
+        held = held[key_dists(held) <= capf]
+    if lo_key is not None:              # hvs_keep_after
+        held = held[held >= np.uint64(lo_key)]
+    out["keys"] = held
     return out
 
 
-def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS_FCAP, prep=None, plan=None):
+def mask_cut(live, sp, n):
+    """`sn` of a call: hvs_oracle_sn without a mask; under one the cut id of hvs_mask_plan (cut_for): the id of live row number
+    sn_live, n when no live row is cut off, 0 when none is sampled."""
+    if live is None or live.all():
+        return int(T.oracle().hvs_oracle_sn(sp, n))
+    at = np.flatnonzero(live)
+    sn_live = int(T.oracle().hvs_oracle_sn(sp, at.size))
+    if sn_live == 0:
+        return 0
+    return n if sn_live >= at.size else int(at[sn_live])
+
+
+def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS_FCAP, prep=None, plan=None, caps=None, after=None,
+         live=None, wrong=None):
     """The model of one call.  Returns a dict of per-query arrays:
       lo, hi [nq, K]      survivor bracket per level of the first pass;      cand [nq, K + 1] keys appended per level
+      dead_lo, dead_hi    the part of lo, hi that dead rows make up (hvs_mask_info.dead_survivors)
       fails [nq]          the final check sends the query to a retry batch;  overflow [nq] a list above `fcap` does
-      retry_lo, retry_hi  the same bracket for the retry pass of the retried queries (zero rows elsewhere)
+      retry_lo, retry_hi, retry_dead_lo, retry_dead_hi   the same brackets for the retry pass of the retried queries (zero elsewhere)
       excluded [nq]       on a grid edge of the guess table;                 exact [nq] answered by the exact engine
       held                list of the final held distances per query (the k smallest of its range when verified)
-    guess: "proven" (HVS_GUESS_MID=256) or "guess" with `pfail` (None: the batch's default) and `mid` (HVS_GUESS_MID)."""
+      held_keys           ... as keys (distance bits << 32 | id): the answer's matched slots, in key order
+    guess: "proven" (HVS_GUESS_MID=256) or "guess" with `pfail` (None: the batch's default) and `mid` (HVS_GUESS_MID).
+    caps [nq] f32, after = (dists [nq], ids [nq]), live bool [n]: the attachments; wrong: one of WRONG (the CPU test only)."""
+    assert wrong is None or wrong in WRONG, wrong
     P = prep if prep is not None else Prepared(fmt, nodes, queries)
     L = levels(P.n, plan=plan)
-    sn = int(T.oracle().hvs_oracle_sn(sp, P.n))
+    live = None if live is None else np.asarray(live, bool)
+    sn = mask_cut(live, sp, P.n)
     if pfail is None:
         pfail = default_pfail(P.nq)
     nq, K = P.nq, L.K
-    res = dict(lo=np.zeros((nq, K), np.int64), hi=np.zeros((nq, K), np.int64), cand=np.zeros((nq, K + 1), np.int64),
-               retry_lo=np.zeros((nq, K), np.int64), retry_hi=np.zeros((nq, K), np.int64), retry_cand=np.zeros((nq, K + 1), np.int64),
+    z = lambda *s: np.zeros(s, np.int64)
+    res = dict(lo=z(nq, K), hi=z(nq, K), cand=z(nq, K + 1), retry_lo=z(nq, K), retry_hi=z(nq, K), retry_cand=z(nq, K + 1),
+               dead_lo=z(nq, K), dead_hi=z(nq, K), retry_dead_lo=z(nq, K), retry_dead_hi=z(nq, K),
                fails=np.zeros(nq, bool), overflow=np.zeros(nq, bool), excluded=np.zeros(nq, bool), exact=P.hopeless.copy(), held=[],
-               K=K, sn=sn)
+               held_keys=[], K=K, sn=sn)
     for q in range(nq):
-        r = _pass(P, L, q, k, sn, guess, pfail, mid, band_scale, fcap)
-        res["lo"][q], res["hi"][q], res["cand"][q] = r["lo"], r["hi"], r["cand"]
+        att = dict(cap=None if caps is None else caps[q], lo_key=None if after is None else after_lo(after[0][q], after[1][q]),
+                   live=live, wrong=wrong)
+        r = _pass(P, L, q, k, sn, guess, pfail, mid, band_scale, fcap, **att)
+        for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
+            res[name][q] = r[name]
         res["fails"][q], res["overflow"][q], res["excluded"][q] = r["fails"], r["overflow"], r["edge"]
-        held = r["held"]
+        keys = r["keys"]
         if r["fails"] or r["overflow"]:     # retry batch: proven at every level (plan_guess(k, true, .)), longer lists
-            r2 = _pass(P, L, q, k, sn, "proven", pfail, mid, band_scale, 1 << 30)
-            assert not r2["fails"], "a proven threshold cannot fail its check"
-            res["retry_lo"][q], res["retry_hi"][q], res["retry_cand"][q] = r2["lo"], r2["hi"], r2["cand"]
-            held = r2["held"]
-        res["held"].append(held)
+            r2 = _pass(P, L, q, k, sn, "proven", pfail, mid, band_scale, 1 << 30, retry=True, **att)
+            assert wrong is not None or not r2["fails"], "a proven threshold cannot fail its check"
+            for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
+                res["retry_" + name][q] = r2[name]
+            keys = r2["keys"]
+        res["held_keys"].append(keys)
+        res["held"].append(key_dists(keys))
     res["retry"] = res["fails"] | res["overflow"]
     return res
 
 
-def totals(res, keep=None):
-    """(sum lo, sum hi) over both passes of the queries in `keep` (default: the non-excluded ones)."""
+def totals(res, keep=None, what=""):
+    """(sum lo, sum hi) over both passes of the queries in `keep` (default: the non-excluded ones); what = "dead_": of the dead rows."""
     keep = ~res["excluded"] if keep is None else keep
-    lo = int(res["lo"][keep].sum() + res["retry_lo"][keep].sum())
-    hi = int(res["hi"][keep].sum() + res["retry_hi"][keep].sum())
+    lo = int(res[what + "lo"][keep].sum() + res["retry_" + what + "lo"][keep].sum())
+    hi = int(res[what + "hi"][keep].sum() + res["retry_" + what + "hi"][keep].sum())
     return lo, hi
 
 
@@ -463,12 +624,176 @@ def case_prep(case, fmt):
     return _prep_cache[key]
 
 
-def case_walk(case, fmt, regime, band_scale=1.0):
-    """The model of the case's call in a context that reserved RESERVE_NQ queries."""
-    key = (case.name, fmt, regime, band_scale)
+def case_walk(case, fmt, regime, band_scale=1.0, attach=None, wrong=None):
+    """The model of the case's call in a context that reserved RESERVE_NQ queries; attach: a name of ATTACH, or None."""
+    key = (case.name, fmt, regime, band_scale, attach, wrong)
     if key not in _walk_cache:
         r = REGIMES[regime]
         nodes, queries = case_data(case)
+        att = attachment(case, attach) if attach else {}
         _walk_cache[key] = walk(fmt, nodes, queries, case.k, case.sp, r["guess"], r["pfail"], r["mid"], band_scale,
-                                list_capacity(RESERVE_NQ, queries.shape[0]), prep=case_prep(case, fmt))
+                                list_capacity(RESERVE_NQ, queries.shape[0]), prep=case_prep(case, fmt), caps=att.get("caps"),
+                                after=att.get("after"), live=att.get("live"), wrong=wrong)
     return _walk_cache[key]
+
+
+# --------------------------------------------------------------------------- attachments of the cases
+
+ATTACH = ("cap_kth", "cap_mixed", "after_p2", "after_deep", "mask", "cap_after", "all")
+# what the GPU test runs under attachments: (case, formats, attachments, regimes, HVS_I8_SHAPE, the band x 1.25 build)
+ATTACH_MATRIX = [
+    ("v1_32k", ALL_I8, ATTACH, ("proven", "default", "reckless"), "16", False),
+    ("v1_32k", (BM.PLAIN_I8,), ATTACH, ("default",), "32", False),
+    ("v1_70k", (BM.PLAIN_I8,), ("cap_mixed", "after_p2", "mask", "all"), ("default", "reckless"), "16", False),
+    ("half", (BM.PLAIN_I8,), ("mask", "all"), ("default",), "16", False),
+    ("f16", (BM.FP16,), ("cap_kth", "after_p2", "mask"), ("default",), "16", False),
+    ("v1_32k", (BM.PLAIN_I8, BM.BF16), ("cap_kth", "after_p2", "mask"), ("default",), "16", True),
+]
+
+
+def attach_cells(regime=None, shape=None, wide=None):
+    """The (case, format, regime, attachment) cells of ATTACH_MATRIX, each once, in matrix order; optionally one child's share."""
+    seen, out = set(), []
+    for name, fmts, attaches, regimes, shp, wd in ATTACH_MATRIX:
+        if (shape is not None and shp != shape) or (wide is not None and wd != wide):
+            continue
+        for fmt in fmts:
+            for rg in regimes:
+                for att in attaches:
+                    cell = (name, fmt, rg, att)
+                    if (regime is None or rg == regime) and cell not in seen:
+                        seen.add(cell)
+                        out.append((case_by_name(name), fmt, rg, att))
+    return out
+CAP_KINDS = ("below_nearest", "quarter", "above_quarter", "kth", "inf", "3e38", "nan", "minus_one")
+EXHAUSTED = (np.float32(np.inf), np.uint32(0xFFFFFFFF))
+MASK_SEED, MASK_SHARE, MASK_NEAR_QUERIES, MASK_BLOCK_QUERIES = 4242, 0.15, range(0, 16), range(64, 72)
+ALL_CAP_RANK = 3             # `all`: the cap is the (3 k)-th matched distance, see attachment()
+
+_full_cache, _attach_cache = {}, {}
+
+
+def case_fulls(case, live=None):
+    """full(q) of every query of the case: the keys of its matched rows -- rows that pass its predicate (hvs_testlib._passes), lie
+    in the sampled prefix and are live -- in key order, from the oracle's exact-order distances."""
+    key = (case.name, None if live is None else live.tobytes())
+    if key not in _full_cache:
+        nodes, queries = case_data(case)
+        dist = case_prep(case, case.fmts[0]).dist
+        sn = mask_cut(live, case.sp, case.n)
+        ok = np.arange(case.n) < sn
+        if live is not None:
+            ok &= live
+        out = []
+        for q in range(queries.shape[0]):
+            ids = np.flatnonzero(T._passes(nodes, queries[q]) & ok)
+            out.append(np.sort(make_keys(dist[q, ids], ids)))
+        _full_cache[key] = out
+    return _full_cache[key]
+
+
+def expected_keys(case, att):
+    """The matched slots of the answers under an attachment, by the laws of tests/within_model.py and tests/after_model.py on
+    full(q) of the live rows: the cap first (after_model.cap_full), then the first k keys behind the cursor (after_model.page)."""
+    import after_model as AM
+    fulls = case_fulls(case, att.get("live"))
+    out = []
+    for q, keys in enumerate(fulls):
+        full = (key_ids(keys), key_dists(keys))
+        if "caps" in att:
+            full = AM.cap_full(full, att["caps"][q])
+        cur = (att["after"][0][q], att["after"][1][q]) if "after" in att else None
+        ids, d, take = AM.page(full, cur, case.k)
+        out.append(make_keys(d[:take], ids[:take]))
+    return out
+
+
+def expected_answers(case, att):
+    """The padded answers under an attachment, as the library returns them with padding on: expected_keys' matched slots, the
+    empty ones filled from the pad rows (n - 1, n - 2, ..., or the last k live rows under a mask: hvs_mask_plan), all k in key
+    order.  -> (ids [nq, k], dists [nq, k], matched [nq])"""
+    import after_model as AM
+    k, live = case.k, att.get("live")
+    dist = case_prep(case, case.fmts[0]).dist
+    pad_ids = (np.arange(case.n) if live is None else np.flatnonzero(live))[::-1][:k].astype(np.uint32)
+    want = expected_keys(case, att)
+    nq = len(want)
+    ids, d, taken = np.empty((nq, k), np.uint32), np.empty((nq, k), np.float32), np.zeros(nq, np.int64)
+    for q, keys in enumerate(want):
+        ids[q], d[q], taken[q] = AM.page((key_ids(keys), key_dists(keys)), None, k, (pad_ids, dist[q, pad_ids]), padding=True)
+    return ids, d, taken
+
+
+def attachment(case, name):
+    """The attachment `name` of a case: dict with some of caps [nq] f32, after = (dists [nq] f32, ids [nq] u32), live [n] bool --
+    and, for the conditions of tests/test_selectivity_model_cpu.py, cap_kind [nq] (index into CAP_KINDS).  Everything is derived
+    from full(q) of the unmasked case (the oracle's exact-order distances, every matched key and not only the nearest 256: key
+    3 k of after_deep lies behind them) and from the fixed seed MASK_SEED.
+
+    Changed against the plain reading, and why: `all` takes the (3 k)-th matched distance as its cap instead of the k-th.  With
+    the k-th, no key behind the page-2 cursor lies within the cap (but for ties): no list ever takes a key, tau never leaves the
+    cap, and nothing can be retried -- condition (e') could not hold and the run would check nothing of the three together."""
+    key = (case.name, name)
+    if key in _attach_cache:
+        return _attach_cache[key]
+    nodes, queries = case_data(case)
+    nq, k = queries.shape[0], case.k
+    fulls = case_fulls(case)
+    at = lambda q, rank: fulls[q][min(rank, fulls[q].size) - 1]          # key number `rank` (from 1), or the last one
+    dist_at = lambda q, rank: np.float32(key_dists(fulls[q][min(rank, fulls[q].size) - 1:][:1])[0]) if fulls[q].size else np.float32(1.0)
+    f32 = np.float32
+
+    def caps_kth(rank):
+        return np.array([dist_at(q, rank) for q in range(nq)], f32)
+
+    def caps_mixed():
+        quarter = -(-k // 4)
+        caps, kind = np.empty(nq, f32), np.arange(nq) % 8
+        for q in range(nq):
+            caps[q] = (np.nextafter(dist_at(q, 1), f32(-np.inf)), dist_at(q, quarter), np.nextafter(dist_at(q, quarter), f32(np.inf)),
+                       dist_at(q, k), f32(np.inf), f32(3e38), f32(np.nan), f32(-1.0))[kind[q]]
+        return caps, kind
+
+    def cursor(q, rank):
+        if fulls[q].size == 0:
+            return EXHAUSTED
+        key_ = at(q, rank)
+        return key_dists([key_])[0], key_ids([key_])[0]
+
+    def cursors(pick):
+        c = [pick(q) for q in range(nq)]
+        return np.array([x[0] for x in c], f32), np.array([x[1] for x in c], np.uint32)
+
+    def mask():
+        rng = np.random.default_rng(MASK_SEED)
+        live = rng.random(case.n) >= MASK_SHARE
+        for q in MASK_NEAR_QUERIES:                                      # the nearest rows of queries 0-15
+            live[key_ids(fulls[q][:-(-k // 2)])] = False
+        P, L, taken = case_prep(case, case.fmts[0]), levels(case.n), set()
+        for q in MASK_BLOCK_QUERIES:                                     # one whole level-0 block inside the range of each of 64-71
+            ordn, a, b = P.ranges[q]
+            blocks = np.arange(-(-a // 32), b // 32)
+            blocks = [int(x) for x in blocks[L.block_level(blocks) == 0] if int(x) not in taken]
+            assert blocks, (case.name, q)
+            blk = blocks[len(blocks) // 2]
+            taken.add(blk)
+            live[(P.ord.perm_t if ordn else P.ord.perm_ct)[blk * 32:blk * 32 + 32]] = False
+        assert len(taken) == len(MASK_BLOCK_QUERIES)
+        return live
+
+    att = {}
+    if name in ("cap_kth",):
+        att["caps"] = caps_kth(k)
+    if name in ("cap_mixed", "cap_after"):
+        att["caps"], att["cap_kind"] = caps_mixed()
+    if name == "all":
+        att["caps"] = caps_kth(ALL_CAP_RANK * k)
+    if name in ("after_p2", "cap_after", "all"):
+        att["after"] = cursors(lambda q: cursor(q, k))
+    if name == "after_deep":
+        att["after"] = cursors(lambda q: (cursor(q, 3 * k), cursor(q, k), EXHAUSTED, (f32(0.0), np.uint32(0)))[q % 4])
+    if name in ("mask", "all"):
+        att["live"] = mask()
+    assert att, name
+    _attach_cache[key] = att
+    return att

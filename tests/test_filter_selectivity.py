@@ -57,6 +57,60 @@ Band x 1.25 build, measured and [sum lo, sum hi] of the model with that band:
   half    i8_rot  390100 [390074, 390135]     110944 [110927, 110972]
   half    bf16    313516 [313433, 313584]     70431 [70390, 70459]
   out     i8      194342 [194339, 194344]     -
+
+Caps, cursors and a row mask (selectivity_model.ATTACH over ATTACH_MATRIX; what the walk restates of each: that module's
+docstring, "Attachments").  Each changes a threshold, a list's contents or a retry decision, so a mistake there -- a cap-derived
+theta with a band too wide, a retry batch that starts from +inf, a final check that reads `tau == +inf`, a level whose theta
+forgets the cap, keys in front of a cursor in the order statistic, tombstones that do not hold in one tile format, a tau thinned
+by dead rows that retries the wrong queries -- returns identical bits.  The attachments come as .npy files and go through the
+public API (Engine.set_row_mask, Engine.query(max_dist2=, after=)), padding on; one engine per (case, format) answers its cells
+one call each, the cells with the mask last (it is set once and stays).  Per cell, answers first: ids and distance bits equal
+to the padded answers the features' own host models give (selectivity_model.expected_answers; the key order is total, so nothing
+is loosened for ties), hvs_within_info / hvs_after_info as those answers imply; then `retry_queries`, `fallback_queries` and both
+re-run lists exactly, `rescored_pairs` in [sum lo, sum hi] over both passes, `dead_survivors` in the model's bracket for the dead
+rows (which is one number in every cell; 0 without a mask).  The band x 1.25 build lands above the production bracket and inside
+the model's for that band under cap_kth, after_p2 and mask.
+
+Measured against modelled (MI355X), rescored_pairs [sum lo, sum hi], retried queries in parentheses, `dead` = dead_survivors
+(measured = modelled):
+  case    format  attachment  proven                      default                    reckless (retried)
+  v1_32k  i8      cap_kth      14003 [ 14003,  14004]     14003 [14003, 14004]        16201 [16201, 16202] (21)
+  v1_32k  i8      cap_mixed    49537 [ 49535,  49539]     12157 [12156, 12158]        15272 [15271, 15273] (5)
+  v1_32k  i8      after_p2    204390 [204388, 204393]     51680 [51676, 51681]        76243 [76240, 76244] (22)
+  v1_32k  i8      after_deep  662150 [662147, 662155]    547561 [547557, 547563]     550070 [550069, 550070] (9)
+  v1_32k  i8      mask        279251 [279249, 279252]     58249 [58245, 58250]        53340 [53337, 53341] (10)
+  v1_32k  i8      cap_after    52132 [ 52132,  52133]     15034 [15033, 15035]        23146 [23146, 23147] (6)
+  v1_32k  i8      all          31291 [ 31291,  31293]     31190 [31190, 31192]        30819 [30818, 30823] (12)
+  v1_32k  i8_rot  cap_kth      20473 [ 20466,  20478]     20473 [20466, 20478]        23782 [23775, 23787] (21)
+  v1_32k  i8_rot  cap_mixed    59221 [ 59216,  59231]     17170 [17166, 17176]        20120 [20117, 20130] (5)
+  v1_32k  i8_rot  after_p2    241478 [241456, 241505]     70381 [70369, 70393]        96826 [96811, 96836] (22)
+  v1_32k  i8_rot  after_deep  690497 [690475, 690514]    562010 [561998, 562024]     563570 [563563, 563579] (9)
+  v1_32k  i8_rot  mask        312515 [312491, 312540]     76341 [76332, 76355]        67198 [67190, 67208] (10)
+  v1_32k  i8_rot  cap_after    62502 [ 62490,  62515]     21028 [21023, 21036]        29888 [29882, 29897] (6)
+  v1_32k  i8_rot  all          43730 [ 43723,  43740]     43606 [43599, 43618]        43546 [43535, 43554] (12)
+  v1_32k  bf16    cap_kth      12298 [ 12290,  12304]     12298 [12290, 12304]        14218 [14209, 14224] (21)
+  v1_32k  bf16    cap_mixed    46781 [ 46764,  46795]     10860 [10850, 10868]        13992 [13985, 14000] (5)
+  v1_32k  bf16    after_p2    193814 [193757, 193864]     46855 [46824, 46882]        70815 [70777, 70844] (22)
+  v1_32k  bf16    after_deep  654060 [654015, 654120]    543727 [543711, 543743]     546506 [546491, 546529] (9)
+  v1_32k  bf16    mask        269315 [269261, 269366]     53452 [53411, 53474]        49686 [49662, 49709] (10)
+  v1_32k  bf16    cap_after    49139 [ 49116,  49147]     13508 [13500, 13517]        21409 [21396, 21417] (6)
+  v1_32k  bf16    all          28018 [ 28001,  28036]     27935 [27919, 27952]        27615 [27597, 27629] (12)
+  v1_70k  i8      cap_mixed   -                           13648 [13646, 13648]        17376 [17375, 17376] (8)
+  v1_70k  i8      after_p2    -                           54554 [54552, 54555]        80078 [80076, 80084] (22)
+  v1_70k  i8      mask        -                           47154 [47153, 47156]        49523 [49520, 49525] (10)
+  v1_70k  i8      all         -                           32751 [32750, 32753]        33009 [33009, 33010] (15)
+  half    i8      mask        -                          118391 [118388, 118394]      -
+  half    i8      all         -                           59016 [59014, 59019]        -
+  f16     f16     cap_kth     -                           11193 [11189, 11197]        -
+  f16     f16     after_p2    -                           45212 [45191, 45237]        -
+  f16     f16     mask        -                           50992 [50964, 51012]        -
+(proven and default retried none, no cell sent a query to the exact engine; the 32x32x32 layout gave the 16x16x64 counts in all
+seven default cells of v1_32k i8.  dead under `mask`: v1_32k 10213 / 283 / 1203 (proven / default / reckless) in all three
+formats, v1_70k 296 / 200 (default / reckless), half 2435, f16 1071; 0 in every cell without a mask and under `all`, whose cap
+keeps every theta finite)
+Band x 1.25 build under attachments, default thresholds, measured and [sum lo, sum hi] of the model with that band:
+  v1_32k  i8      cap_kth      14791 [14790, 14791]      after_p2  54133 [54128, 54137]      mask  60635 [60633, 60636]
+  v1_32k  bf16    cap_kth      12668 [12660, 12681]      after_p2  47893 [47863, 47924]      mask  54460 [54434, 54485]
 """
 import importlib
 import os
@@ -210,6 +264,155 @@ def test_production_counts_lie_in_the_model_bracket(work_dir, regime, shape):
         _check_reruns(case, fmt, regime, keep, w, t)
         if not inside:
             bad.append((case.name, fmt, t["rescored"], lo, hi))
+    assert not bad, bad
+
+
+# --------------------------------------------------------------------------- caps, cursors and a row mask
+
+_CHILD_ATTACHED = r"""
+import importlib, json, os, sys, numpy as np
+sys.path.insert(0, '.')
+PKG = importlib.import_module('project---hybrid-vector-search-queries_amd')
+spec = json.loads(sys.argv[1])
+out = {}
+for data, engine, rot, k, sp, cells in spec['engines']:
+    z = np.load(os.path.join(spec['dir'], data + '.npz'))
+    if rot is None:
+        os.environ.pop('HVS_I8_ROTATE', None)
+    else:
+        os.environ['HVS_I8_ROTATE'] = rot
+    with PKG.Engine(0) as e:
+        e.set_engine(engine)
+        e.set_k(k)
+        e.load_data(z['nodes'])
+        e.reserve(spec['reserve'])
+        masked = False
+        for tag in cells:      # (the cells with a mask come last: the mask is set once and stays)
+            get = lambda part: np.load(os.path.join(spec['dir'], tag + '.' + part + '.npy')) if os.path.exists(os.path.join(spec['dir'], tag + '.' + part + '.npy')) else None
+            keep, caps, after_d, after_i, live = get('keep'), get('caps'), get('after_d'), get('after_i'), get('live')
+            assert not (masked and live is None)
+            if live is not None and not masked:
+                e.set_row_mask(live)
+                masked = True
+            ids, d = e.query(z['queries'][keep], sp, max_dist2=None if caps is None else caps[keep],
+                             after=None if after_d is None else (after_d[keep], after_i[keep]))
+            t = e.last_timing()
+            reruns = [e.last_reruns(0).tolist(), e.last_reruns(1).tolist()]
+            m, w, a = e.mask_stats(), e.within_stats(), e.after_stats()
+            np.savez(os.path.join(spec['out'], tag + '.npz'), ids=ids, dists=d)
+            out[tag] = dict(engine=int(t.engine), fallback=int(t.fallback_queries), retry=int(t.retry_queries), flags=int(t.flags),
+                            rescored=int(t.rescored_pairs), exact_list=reruns[0], retry_list=reruns[1], dead_survivors=int(m.dead_survivors),
+                            n_dead=int(m.n_dead), within=w.as_dict(), after=a.as_dict())
+print('RESULT ' + json.dumps(out))
+"""
+_MASK_LAST = {name: (name in ("mask", "all"), i) for i, name in enumerate(SM.ATTACH)}
+
+
+def _run_attached(work_dir, regime, shape, lib=None):
+    """One child: every attached cell of (regime, HVS_I8_SHAPE, library), one engine per (case, format), its cells one call each.
+    Returns [(case, fmt, name, attachment, keep, production walk, ids, dists, counts)]."""
+    cells = SM.attach_cells(regime, shape, lib is not None)
+    label = "%s-attached-%s-%s" % ("wide" if lib else "production", regime, shape)
+    out_dir = work_dir / label
+    out_dir.mkdir(exist_ok=True)
+    engines, runs = {}, []
+    for case, fmt, _, name in sorted(cells, key=lambda c: (c[0].name, c[1], _MASK_LAST[c[3]])):
+        att = SM.attachment(case, name)
+        w = SM.case_walk(case, fmt, regime, attach=name)         # the production model decides what is sent, for either library
+        keep = np.nonzero(~w["excluded"])[0]
+        tag = "%s-%s-%s-%s" % (label, case.name, fmt, name)
+        np.save(work_dir / (tag + ".keep.npy"), keep)
+        if "caps" in att:
+            np.save(work_dir / (tag + ".caps.npy"), att["caps"])
+        if "after" in att:
+            np.save(work_dir / (tag + ".after_d.npy"), att["after"][0])
+            np.save(work_dir / (tag + ".after_i.npy"), att["after"][1])
+        if "live" in att:
+            np.save(work_dir / (tag + ".live.npy"), att["live"])
+        engine, rot = ENGINE[fmt]
+        engines.setdefault((case.name, engine, rot, case.k, case.sp), []).append(tag)
+        runs.append((case, fmt, name, att, keep, w, tag))
+    env = dict(os.environ, HVS_I8_SHAPE=shape)
+    for var in ("HVS_I8_ROTATE", "HVS_LIB", "HVS_GUESS_MID", "HVS_GUESS_PFAIL", "HVS_RADICES"):
+        env.pop(var, None)
+    env.update(SM.REGIMES[regime]["env"])
+    if lib:
+        env["HVS_LIB"] = lib
+    spec = dict(dir=str(work_dir), out=str(out_dir), engines=[list(key) + [tags] for key, tags in engines.items()], reserve=SM.RESERVE_NQ)
+    counts = T.run_child(_CHILD_ATTACHED, spec, env, label, CHILD_TIMEOUT)
+    res = []
+    for case, fmt, name, att, keep, w, tag in runs:
+        z = np.load(out_dir / (tag + ".npz"))
+        res.append((case, fmt, name, att, keep, w, z["ids"], z["dists"], counts[tag]))
+    return res
+
+
+_expected = {}
+
+
+def _check_attached_answers(case, fmt, name, att, keep, ids, dists, t):
+    """The requested engine, the rotation flag, answers equal to the attachment's expected ones in ids and distance bits (the key
+    order is total: nothing is loosened for ties, as in tests/test_after.py), and the features' own counts of those answers."""
+    if (case.name, name) not in _expected:
+        _expected[(case.name, name)] = SM.expected_answers(case, att)
+    ref_ids, ref_d, matched = _expected[(case.name, name)]
+    engine, rot = ENGINE[fmt]
+    where = (case.name, fmt, name)
+    assert t["engine"] == engine, (where, t)
+    if rot is not None:
+        assert bool(t["flags"] & HVS_TIMING_I8_ROTATED) == (rot == "1"), (where, t)
+    bad = np.nonzero((dists.view(np.uint32) != ref_d[keep].view(np.uint32)).any(1) | (ids != ref_ids[keep]).any(1))[0]
+    assert bad.size == 0, (where, "queries (of those sent) with another answer:", bad[:10].tolist())
+    slots, underfull = int(matched[keep].sum()), int((matched[keep] < case.k).sum())
+    if "caps" in att:
+        assert (t["within"]["within_slots"], t["within"]["underfull_queries"]) == (slots, underfull), (where, t["within"], slots, underfull)
+    if "after" in att:
+        exhausted = int((att["after"][1][keep] == 0xFFFFFFFF).sum())
+        assert (t["after"]["after_slots"], t["after"]["underfull_queries"], t["after"]["exhausted_queries"]) == (slots, underfull, exhausted), \
+            (where, t["after"], slots, underfull, exhausted)
+    assert t["n_dead"] == (int((~att["live"]).sum()) if "live" in att else 0), (where, t["n_dead"])
+
+
+def _attached_line(label, case, fmt, name, t, lo, hi, dlo, dhi, keep, w, ok):
+    return "%-18s %-7s %-6s %-10s rescored %7d  model [%7d, %7d]  dead %5d [%5d, %5d]  retried %2d (model %2d)  exact %d  sent %d%s" % (
+        label, case.name, fmt, name, t["rescored"], lo, hi, t["dead_survivors"], dlo, dhi, t["retry"], int(w["retry"][keep].sum()),
+        t["fallback"], keep.size, "" if ok else "   <-- OUTSIDE")
+
+
+@pytest.mark.parametrize("regime,shape", [("proven", "16"), ("default", "16"), ("reckless", "16"), ("default", "32")])
+def test_attached_counts_lie_in_the_model_bracket(work_dir, regime, shape):
+    """Caps, cursors and a row mask (selectivity_model.ATTACH over ATTACH_MATRIX): answers first, then retry and exact lists
+    exactly, rescored_pairs and dead_survivors inside the model's brackets."""
+    results = _run_attached(work_dir, regime, shape)
+    for case, fmt, name, att, keep, w, ids, dists, t in results:
+        _check_attached_answers(case, fmt, name, att, keep, ids, dists, t)
+    bad = []
+    for case, fmt, name, att, keep, w, ids, dists, t in results:
+        (lo, hi), (dlo, dhi) = SM.totals(w), SM.totals(w, what="dead_")
+        inside = lo <= t["rescored"] <= hi and dlo <= t["dead_survivors"] <= dhi
+        print(_attached_line("%s I8_SHAPE=%s" % (regime, shape), case, fmt, name, t, lo, hi, dlo, dhi, keep, w, inside))
+        _check_reruns(case, fmt + "/" + name, regime, keep, w, t)
+        if not inside:
+            bad.append((case.name, fmt, name, t["rescored"], lo, hi, t["dead_survivors"], dlo, dhi))
+    assert not bad, bad
+
+
+def test_a_band_too_wide_is_seen_under_attachments(work_dir, wide_band_lib):
+    """The band x 1.25 build under cap_kth, after_p2 and mask: right answers, above the production bracket, inside the model's
+    bracket for that band."""
+    results = _run_attached(work_dir, "default", "16", lib=wide_band_lib)
+    for case, fmt, name, att, keep, w, ids, dists, t in results:
+        _check_attached_answers(case, fmt, name, att, keep, ids, dists, t)
+    bad = []
+    for case, fmt, name, att, keep, w, ids, dists, t in results:
+        m = SM.case_walk(case, fmt, "default", SM.MUTANT_SCALE, attach=name)
+        lo, hi = SM.totals(w)
+        (mlo, mhi), (dlo, dhi) = SM.totals(m, ~w["excluded"]), SM.totals(m, ~w["excluded"], what="dead_")
+        ok = hi < t["rescored"] and mlo <= t["rescored"] <= mhi and dlo <= t["dead_survivors"] <= dhi
+        print(_attached_line("band x %.2f" % SM.MUTANT_SCALE, case, fmt, name, t, mlo, mhi, dlo, dhi, keep, m, ok) + "  production model [%d, %d]" % (lo, hi))
+        _check_reruns(case, fmt + "/" + name, "default", keep, m, t)
+        if not ok:
+            bad.append((case.name, fmt, name, t["rescored"], (lo, hi), (mlo, mhi)))
     assert not bad, bad
 
 

@@ -12,6 +12,12 @@ every GPU case, format and regime:
   (e) the reckless run's retry set is non-empty and under half of the queries.
 
 These are properties of the inputs: a GPU assertion that rests on them cannot be vacuous.
+
+The attached cells of the GPU test (selectivity_model.ATTACH_MATRIX: distance caps, result cursors, a row mask) get the same
+treatment: the walk without attachments is the committed one to the unit, its held keys are the answers the features' own
+host models give, (a), (b), (d) hold, and (c'), (e'), (g), (h), (i) of test_conditions_of_the_attached_gpu_cases; (f) each
+wrong reading of the code that selectivity_model.WRONG names would leave the bracket or change the retry set somewhere.
+The Prepared objects and walks come from selectivity_model's caches, shared by all tests of the module.
 """
 import os
 import subprocess
@@ -185,3 +191,135 @@ def test_conditions_of_the_gpu_cases():
                     assert case.k < 100 or w["cand"].max() > SM.HVS_FCAP
                 if regime == "reckless":
                     assert 0 < w["retry"].sum() < nq / 2, "(e)"
+
+
+# --------------------------------------------------------------------------- the attachments: caps, cursors, a row mask
+
+def test_no_attachment_is_the_committed_walk():
+    """caps = after = live = None: the totals of the table in tests/test_filter_selectivity.py's docstring, to the unit; a cap of
+    +inf on every query, a cursor in front of every key and a mask without a dead row change nothing either."""
+    case = SM.CASES[0]
+    nodes, queries = SM.case_data(case)
+    want = {"proven": (193545, 193551, 0), "default": (39470, 39473, 0), "reckless": (57937, 57943, 21)}
+    nq = queries.shape[0]
+    for regime, (lo, hi, retried) in want.items():
+        w = SM.case_walk(case, BM.PLAIN_I8, regime)
+        assert SM.totals(w) == (lo, hi) and int(w["retry"].sum()) == retried and not w["excluded"].any(), (regime, SM.totals(w))
+        r = SM.REGIMES[regime]
+        # (a mask without a dead row is no mask: hvs_ctx::rs.n_dead == 0 runs the plain kernels)
+        same = SM.walk(BM.PLAIN_I8, nodes, queries, case.k, case.sp, r["guess"], r["pfail"], r["mid"], 1.0,
+                       SM.list_capacity(SM.RESERVE_NQ, nq), prep=SM.case_prep(case, BM.PLAIN_I8), caps=np.full(nq, np.inf, np.float32),
+                       after=(np.zeros(nq, np.float32), np.zeros(nq, np.uint32)), live=np.ones(case.n, bool))
+        for name in ("lo", "hi", "cand", "retry_lo", "retry_hi", "retry", "dead_hi"):
+            assert np.array_equal(same[name], w[name]), (regime, name)
+        assert all(np.array_equal(x, y) for x, y in zip(same["held_keys"], w["held_keys"]))
+
+
+def _cell_walks():
+    """[(case, fmt, regime, attachment name, attachment, walk)] of every cell the GPU test runs under attachments."""
+    return [(case, fmt, regime, name, SM.attachment(case, name), SM.case_walk(case, fmt, regime, attach=name))
+            for case, fmt, regime, name in SM.attach_cells()]
+
+
+def test_attached_walks_are_consistent():
+    """Every attached cell: lo <= hi, dead <= all, proven thresholds retry nobody, no dead survivor without a mask, and the final
+    held keys are bit for bit what the laws of tests/within_model.py and tests/after_model.py give on full(q) of the live rows
+    (SM.expected_keys) -- also behind a failed guess and its retry.  Under `mask` alone the distances also equal the oracle's
+    answer on D[live] wherever k live rows match (ids mapped back through `live`)."""
+    oracle_checked = set()
+    for case, fmt, regime, name, att, w in _cell_walks():
+        for p in ("", "retry_"):
+            assert (w[p + "lo"] <= w[p + "hi"]).all() and (w[p + "dead_lo"] <= w[p + "dead_hi"]).all(), (case.name, fmt, regime, name)
+            assert (w[p + "dead_hi"] <= w[p + "hi"]).all() and (w[p + "dead_lo"] <= w[p + "lo"]).all()
+            if "live" not in att:
+                assert not w[p + "dead_hi"].any()
+        if regime == "proven":
+            assert not w["retry"].any(), (case.name, fmt, name)
+        assert not w["exact"].any()
+        want = SM.expected_keys(case, att)
+        for q, (got, exp) in enumerate(zip(w["held_keys"], want)):
+            assert np.array_equal(got, exp), (case.name, fmt, regime, name, q, got.size, exp.size)
+        if name == "mask" and case.sp == 1.0 and case.name not in oracle_checked:
+            oracle_checked.add(case.name)
+            nodes, queries = SM.case_data(case)
+            back = np.flatnonzero(att["live"])
+            with T.oracle_k(case.k):
+                ref_ids, ref_d = T.oracle_query(nodes[back], queries, case.sp)
+            full = 0
+            for q, exp in enumerate(want):
+                if exp.size == case.k:
+                    full += 1
+                    assert np.array_equal(SM.key_dists(exp).view(np.uint32), ref_d[q].view(np.uint32)), (case.name, q)
+                    assert np.array_equal(np.sort(SM.key_ids(exp)), np.sort(back[ref_ids[q]])) or \
+                        np.unique(ref_d[q]).size < case.k, (case.name, q)
+            assert full >= 100
+
+
+def test_conditions_of_the_attached_gpu_cases():
+    """Conditions (a), (b), (d) as above and (c'), (e'), (g), (h), (i) of the attachments, for every attached cell of the GPU test:
+
+      (c') the band x 1.25 lifts sum lo by at least 10 bracket widths above the production sum hi, for the non-FP16 formats under
+           cap_kth, after_p2 and mask;
+      (e') under `reckless` every attachment except cap_mixed retries more than 0 and fewer than half of the queries;
+      (g)  under `mask`, in every regime, some dead row is a survivor (sum dead_hi > 0): `dead_survivors` is not asserted to be 0;
+      (h)  cap_mixed has at least 8 queries of each of its eight kinds;
+      (i)  after_deep has at least 4 exhausted cursors and at least 4 more queries whose page behind the cursor is under-full."""
+    print()
+    for case, fmt, regime, name, att, w in _cell_walks():
+        nq = SM.case_data(case)[1].shape[0]
+        keep = ~w["excluded"]
+        cap = SM.list_capacity(SM.RESERVE_NQ, int(keep.sum()))
+        lo, hi = SM.totals(w)
+        dlo, dhi = SM.totals(w, what="dead_")
+        width = hi - lo
+        line = "%-7s %-6s %-8s %-10s excluded %d retried %2d  lo %7d hi %7d width %.4f %%  dead [%d, %d]  longest list %d / %d" % (
+            case.name, fmt, regime, name, int(w["excluded"].sum()), int(w["retry"].sum()), lo, hi, 100.0 * width / max(lo, 1), dlo, dhi,
+            w["cand"].max(), w["retry_cand"].max())
+        assert w["excluded"].sum() <= 0.05 * nq, "(a) " + line
+        if lo >= 1000:
+            assert width <= 0.002 * lo, "(b) " + line
+        assert not w["overflow"].any() and w["cand"].max() <= cap, "(d) " + line
+        nretry = int(w["retry"][keep].sum())
+        assert nretry == 0 or w["retry_cand"].max() <= SM.list_capacity(SM.RESERVE_NQ, nretry), "(d) retry batch " + line
+        assert (w["hi"] + 62)[keep].sum(0).max() <= SM.HVS_GROUP * cap, "(d) survivor entries of a group " + line
+        if fmt != BM.FP16 and name in ("cap_kth", "after_p2", "mask"):
+            m = SM.case_walk(case, fmt, regime, SM.MUTANT_SCALE, attach=name)
+            mlo, mhi = SM.totals(m, keep)
+            line += "  band x %.2f: lo %7d = hi + %.1f widths" % (SM.MUTANT_SCALE, mlo, (mlo - hi) / max(width, 1))
+            assert mlo >= hi + 10 * width and width > 0, "(c') " + line
+            assert np.array_equal(m["retry"], w["retry"]) and not m["overflow"].any(), "(c') " + line
+        print(line)
+        if regime == "reckless" and name != "cap_mixed":
+            assert 0 < w["retry"].sum() < nq / 2, "(e') " + line
+        if name == "mask":
+            assert dhi > 0, "(g) " + line
+        if "cap_kind" in att:
+            assert (np.bincount(att["cap_kind"], minlength=8) >= 8).all(), "(h)"
+        if name == "after_deep":
+            exhausted = att["after"][1] == 0xFFFFFFFF
+            underfull = np.array([x.size < case.k for x in w["held_keys"]])
+            assert exhausted.sum() >= 4 and (underfull & ~exhausted).sum() >= 4, "(i) %d %d" % (exhausted.sum(), (underfull & ~exhausted).sum())
+
+
+def test_each_wrong_rule_is_seen():
+    """(f) Each wrong rule of selectivity_model.WRONG shows on at least one (case, format, regime) of the matrix: its sum bracket
+    is disjoint from the right rule's by at least 10 bracket widths, or its retry set differs."""
+    print()
+    where = {"cap": ("cap_kth", "cap_mixed", "cap_after", "all"), "after": ("after_p2", "after_deep", "cap_after", "all"), "mask": ("mask", "all")}
+    for wrong in SM.WRONG:
+        seen = []
+        for case, fmt, regime, name in SM.attach_cells():
+            if name not in where[wrong.split("_")[0]]:
+                continue
+            w = SM.case_walk(case, fmt, regime, attach=name)
+            x = SM.case_walk(case, fmt, regime, attach=name, wrong=wrong)
+            keep = ~w["excluded"]
+            (lo, hi), (xlo, xhi) = SM.totals(w), SM.totals(x, keep)
+            gap = max(xlo - hi, lo - xhi) / max(hi - lo, 1)
+            retry_differs = not np.array_equal(w["retry"][keep], x["retry"][keep])
+            if gap >= 10 or retry_differs:
+                seen.append("%s/%s/%s/%s: [%d, %d] against [%d, %d] (%.0f widths)%s" % (
+                    case.name, fmt, regime, name, xlo, xhi, lo, hi, gap, ", retry set differs: %d against %d" % (
+                        x["retry"][keep].sum(), w["retry"][keep].sum()) if retry_differs else ""))
+        print("%-18s seen in %2d cells, e.g. %s" % (wrong, len(seen), seen[0] if seen else "-"))
+        assert seen, wrong
