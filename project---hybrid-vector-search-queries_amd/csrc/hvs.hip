@@ -31,6 +31,15 @@
 namespace {
 
 thread_local std::string g_global_err;
+int fail(hvs_ctx* c, int code, const std::string& msg);  // (defined below, with staging_copy: the state structs call them)
+void staging_copy(void* dst, const void* src, size_t bytes);
+#define HVS_HIP(ctx, call)                                                                                    \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess)                                                                                  \
+            return fail(ctx, e_ == hipErrorOutOfMemory ? HVS_ENOMEM : HVS_EHIP,                                \
+                        std::string(#call) + ": " + hipGetErrorString(e_));                                    \
+    } while (0)
 
 }  // namespace
 
@@ -324,22 +333,156 @@ struct HvsCallState {
     }
 };
 
+// The host <-> device COPY PIPELINE of one GPU (who records and who waits for each event): two copy streams and three
+// rings of pinned staging slots, for hvs_query's queries and result rows (PipeCall) and for uploads of rows from pageable memory
+// (upload_rows).  Its fields are touched by its own functions and by PipeCall's, by nothing else.  The invariants:
+//   - ev_in[i] / ev_stage are recorded on s_in, ev_out[i] on s_out, ev_batch on a COMPUTE stream (after_compute)
+//   - a slot is overwritten only behind its event: h_in[i] by the host once ev_in[i] is done (stage_in), h_out_*[i] by a D2H only
+//     after the host has drained it, which waits for ev_out[i] (PipeCall::drain_one)
+//   - slot i has room for *_cap_q[i] queries (size_for: slots only grow) of 104 floats going in, of stage_k >= k entries coming out
+//     -- the copies are strided by the current k; outd_cap_q[i] <= out_cap_q[i]: the distance slots exist only after the first call
+//     that asked for distances; dma_warm is set at most once (warm_dma)
+struct HvsCopyPipe {
+    static constexpr uint32_t kStageQ = 65536;  // queries per staging slot
+    static constexpr int kRing = 4;             // (create() and destroy() spell the ring's events out)
+    hvs_ctx* owner = nullptr;  // (whose error text a failed call becomes)
+    hipStream_t s_in = nullptr, s_out = nullptr;
+    uint32_t in_cap_q[kRing] = {}, out_cap_q[kRing] = {}, outd_cap_q[kRing] = {};  // slot sizes in queries
+    float* h_in[kRing] = {};
+    uint32_t* h_out_ids[kRing] = {};
+    float* h_out_dists[kRing] = {};
+    hipEvent_t ev_in[kRing] = {}, ev_out[kRing] = {};
+    hipEvent_t ev_batch = nullptr, ev_stage = nullptr;
+    uint32_t stage_k = 0;   // k the pinned result slots were sized for
+    bool dma_warm = false;  // the copy engines of s_in / s_out have moved a DMA-sized piece
+    const char* create(hvs_ctx* c, hipError_t* e)  // nullptr, or the call that failed with *e
+    {
+        owner = c;
+        for (hipStream_t* s : {&s_in, &s_out})
+            if ((*e = hipStreamCreateWithFlags(s, hipStreamNonBlocking)) != hipSuccess) return "hipStreamCreate";
+        for (hipEvent_t* ev : {&ev_batch, &ev_stage, &ev_in[0], &ev_out[0], &ev_in[1], &ev_out[1], &ev_in[2], &ev_out[2], &ev_in[3], &ev_out[3]})
+            if ((*e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return "hipEventCreate";
+        return nullptr;
+    }
+    void sync() const { for (hipStream_t s : {s_in, s_out}) if (s) (void)hipStreamSynchronize(s); }
+    void destroy()
+    {
+        for (int i = 0; i < kRing; ++i)
+            (void)reslot(h_in[i], in_cap_q[i], 0u, 0u), (void)reslot(h_out_ids[i], out_cap_q[i], 0u, 0u), (void)reslot(h_out_dists[i], outd_cap_q[i], 0u, 0u);
+        for (hipEvent_t ev : {ev_in[0], ev_out[0], ev_in[1], ev_out[1], ev_in[2], ev_out[2], ev_in[3], ev_out[3], ev_batch, ev_stage})
+            if (ev) (void)hipEventDestroy(ev);
+        for (hipStream_t s : {s_in, s_out}) if (s) (void)hipStreamDestroy(s);
+    }
+    template <typename T>  // `slot` gets room for q queries of per_q entries each (q == 0: none), whatever it held
+    int reslot(T*& slot, uint32_t& cap_q, uint32_t q, size_t per_q)
+    {
+        if (slot) (void)hipHostFree(slot);
+        slot = nullptr, cap_q = 0u;
+        if (q) HVS_HIP(owner, hipHostMalloc(reinterpret_cast<void**>(&slot), (size_t)q * per_q * sizeof(T), hipHostMallocDefault));
+        cap_q = q;
+        return HVS_OK;
+    }
+    // Slots sized by the call: nq_in queries (or as many data rows) going in and nq_out result rows of k entries coming out use
+    // ceil(nq / 65536) slots of each ring, at most 4, each as large as its piece (whole slots: 27 + 26 + 26 MB, ~1 ms per 25 MB pinned)
+    int size_for(uint32_t k, bool dists, uint64_t nq_in, uint64_t nq_out)
+    {
+        if (stage_k < k) {  // k grew (hvs_set_k): the result slots are too small
+            for (int i = 0; i < kRing; ++i) (void)reslot(h_out_ids[i], out_cap_q[i], 0u, 0u), (void)reslot(h_out_dists[i], outd_cap_q[i], 0u, 0u);
+            stage_k = k;
+        }
+        auto slot_q = [](uint64_t nq, int i) -> uint32_t {  // queries slot i has to hold (0: the call does not reach it)
+            if (nq <= (uint64_t)i * kStageQ) return 0u;
+            const uint64_t piece = nq > (uint64_t)kRing * kStageQ ? kStageQ : std::min<uint64_t>(kStageQ, nq - (uint64_t)i * kStageQ);
+            return (uint32_t)std::min<uint64_t>(kStageQ, (piece + 4095u) / 4096u * 4096u);
+        };
+        for (int i = 0; i < kRing; ++i) {
+            const uint32_t qi = slot_q(nq_in, i), qo = slot_q(nq_out, i);
+            int rc = HVS_OK;
+            if (qi > in_cap_q[i] && (rc = reslot(h_in[i], in_cap_q[i], qi, HVS_QCOLS))) return rc;
+            if (qo > out_cap_q[i] && (rc = reslot(h_out_ids[i], out_cap_q[i], qo, stage_k))) return rc;
+            if (dists && qo > outd_cap_q[i] && (rc = reslot(h_out_dists[i], outd_cap_q[i], qo, stage_k))) return rc;
+        }
+        return HVS_OK;
+    }
+    int stage_in(float* dst, const float* src, size_t bytes, uint32_t piece)  // piece `piece` of a transfer, pageable, through slot piece % 4
+    {
+        const int i = (int)(piece % (uint32_t)kRing);
+        if (piece >= (uint32_t)kRing) HVS_HIP(owner, hipEventSynchronize(ev_in[i]));  // the slot's previous DMA is done
+        staging_copy(h_in[i], src, bytes);
+        HVS_HIP(owner, hipMemcpyAsync(dst, h_in[i], bytes, hipMemcpyHostToDevice, s_in));
+        HVS_HIP(owner, hipEventRecord(ev_in[i], s_in));
+        return HVS_OK;
+    }
+    int wait_in() { HVS_HIP(owner, hipStreamSynchronize(s_in)); return HVS_OK; }  // the host waits for s_in
+    int after_compute(hipStream_t compute, hipStream_t waiter)  // `waiter` waits for what `compute` has enqueued so far
+    {
+        HVS_HIP(owner, hipEventRecord(ev_batch, compute));
+        HVS_HIP(owner, hipStreamWaitEvent(waiter, ev_batch, 0));
+        return HVS_OK;
+    }
+    // The first operation on a stream creates its hardware queue (and the first copy in each direction its DMA path): a few ms that
+    // belong to hvs_create, not inside the first query (round 3's cold hvs_query of 10^4 queries took 8 ms for 2 ms of device work)
+    void warm_streams(hipStream_t lane0, hipStream_t lane1, uint32_t* d_two, uint32_t* h_two)
+    {
+        for (hipStream_t lane : {lane0, lane1}) {
+            (void)hipMemsetAsync(d_two, 0, 2 * sizeof(uint32_t), lane);
+            (void)hipStreamSynchronize(lane);
+        }
+        (void)hipMemcpyAsync(d_two, h_two, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s_in);
+        (void)hipStreamSynchronize(s_in);
+        (void)hipMemcpyAsync(h_two, d_two, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s_out);
+        (void)after_compute(lane0, s_out);
+        (void)hipStreamSynchronize(s_out);
+        (void)hipGetLastError();
+    }
+    // The first DMA-sized copy in each direction sets up its engine queue (a cold 4 MB D2H took 6 ms): in hvs_reserve, not in the first query
+    void warm_dma(uint32_t* d_ids, float* d_q, size_t call_bytes)
+    {
+        const size_t bytes = std::min<size_t>((size_t)1 << 20, std::min((size_t)out_cap_q[0] * stage_k * sizeof(uint32_t),
+                                                                      (size_t)in_cap_q[0] * HVS_QCOLS * sizeof(float)));
+        if (dma_warm || !h_out_ids[0] || !h_in[0] || !d_ids || !d_q || !bytes || call_bytes < bytes) return;
+        (void)hipMemcpyAsync(h_out_ids[0], d_ids, bytes, hipMemcpyDeviceToHost, s_out);
+        (void)hipMemcpyAsync(d_q, h_in[0], bytes, hipMemcpyHostToDevice, s_in);
+        (void)hipStreamSynchronize(s_out);
+        (void)hipStreamSynchronize(s_in);
+        (void)hipGetLastError();
+        dma_warm = true;
+    }
+};
+
+// What ONE batch of a call on two lanes waits for between its preparation and its seed, and records behind the filter launches of
+// its level before the last and of its last level.  All null (the default: retry batches, the planner probe): nothing of either.
+struct BatchGates { hipEvent_t wait_heavy = nullptr, record_pdone = nullptr, record_fdone = nullptr; };
+
+// The HAND-OVER between the two lanes of a call (HvsLane).  Slot b & 1 of the two event pairs belongs to batch b.
+//   - ev_fdone: end of the LAST level's filter launch of the lane's latest batch.  The next batch (other lane) runs its seed behind
+//     it -- its head then runs beside this batch's last re-scoring and final merge, not beside its filter launches (two crews of
+//     filter workgroups streaming different tiles through the same L2s: measured 12 % slower than one lane).
+//   - ev_pdone: likewise the end of the filter launch of the level BEFORE the last.  The next batch's preparation (query sort, slot
+//     layout, fragments, work-item lists -- memory- and latency-bound) starts behind it and runs beside this batch's re-scoring of
+//     that level; its compute-heavy part (exact seed, low filter levels) waits for ev_fdone (BatchGates::wait_heavy).
+//   - ev_lane: end of the spare lane's latest batch.  lanes_failed: no room for a second workspace (ensure_spare_lane); never cleared.
+struct HvsLaneGates {
+    bool lanes_failed = false;
+    hipEvent_t ev_lane = nullptr;
+    hipEvent_t ev_fdone[2] = {nullptr, nullptr}, ev_pdone[2] = {nullptr, nullptr};
+    hipError_t create()
+    {
+        hipError_t e = hipSuccess;
+        for (hipEvent_t* ev : {&ev_lane, &ev_fdone[0], &ev_fdone[1], &ev_pdone[0], &ev_pdone[1]})
+            if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) break;
+        return e;
+    }
+    void destroy() { for (hipEvent_t ev : {ev_lane, ev_fdone[0], ev_fdone[1], ev_pdone[0], ev_pdone[1]}) if (ev) (void)hipEventDestroy(ev); }
+    // batch b > 0 of a call on two lanes over K >= 1 filter levels: what its stream waits for before anything of it is enqueued
+    hipEvent_t start_of(size_t b, uint32_t K) const { return K >= 2u ? ev_pdone[(b - 1u) & 1u] : ev_fdone[(b - 1u) & 1u]; }
+    BatchGates of_batch(size_t b, bool have_prev) const { return {have_prev ? ev_fdone[(b - 1u) & 1u] : nullptr, ev_pdone[b & 1u], ev_fdone[b & 1u]}; }
+};
+
 struct hvs_ctx : HvsLane {
     int device = 0;
-    HvsLane spare;                 // the second lane (its buffers are allocated by the first call that has two batches)
-    bool lanes_failed = false;     // no room for a second workspace: calls stay on one lane
-    hipEvent_t ev_lane = nullptr;  // end of the spare lane's latest batch
-    // end of the LAST level's filter launch of the latest batch on the main / the spare lane: the next batch (other lane) starts
-    // behind it -- its head then runs beside this batch's last re-scoring and final merge, not beside its filter launches (two
-    // crews of filter workgroups streaming different tiles through the same L2s: measured 12 % slower than one lane)
-    hipEvent_t ev_fdone[2] = {nullptr, nullptr};
-    hipEvent_t ev_fdone_cur = nullptr;  // the one the batch being enqueued records (nullptr: none)
-    // likewise the end of the filter launch of the level BEFORE the last: the next batch's preparation (query sort, slot layout,
-    // fragments, work-item lists -- memory- and latency-bound) starts behind it and runs beside this batch's re-scoring of
-    // that level; its compute-heavy part (exact seed, low filter levels) waits for ev_fdone (`gate_heavy`)
-    hipEvent_t ev_pdone[2] = {nullptr, nullptr};
-    hipEvent_t ev_pdone_cur = nullptr;
-    hipEvent_t gate_heavy = nullptr;    // what the batch being enqueued waits for between its preparation and its seed
+    HvsLane spare;       // the second lane (its buffers are allocated by the first call that has two batches)
+    HvsLaneGates gates;  // the two lanes' hand-over events
     int engine = HVS_ENGINE_AUTO;
     bool scalar_order = false;  // baseline engine's summation order (exact engine only)
     uint32_t k = HVS_KNN;       // neighbours per query (hvs_set_k; the reference's KNN_LIMIT, optimized_impl.h:26)
@@ -382,19 +525,8 @@ struct hvs_ctx : HvsLane {
     bool guess_have[13] = {};       // [p] failure target 10^-p
     uint32_t guess_k = 0;
 
-    // host <-> device pipeline of hvs_query: copy streams + rings of pinned staging slots
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    static constexpr uint32_t kStageQ = 65536;  // queries per staging slot
-    static constexpr int kRing = 4;
-    uint32_t in_cap_q[kRing] = {0, 0, 0, 0}, out_cap_q[kRing] = {0, 0, 0, 0}, outd_cap_q[kRing] = {0, 0, 0, 0};  // slot sizes in queries
-    float* h_in[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t* h_out_ids[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    float* h_out_dists[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_in[kRing] = {nullptr, nullptr, nullptr, nullptr}, ev_out[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_batch = nullptr, ev_stage = nullptr;
+    HvsCopyPipe pipe;         // host <-> device pipeline of hvs_query and of uploads: copy streams + rings of pinned staging slots
     uint32_t reserve_nq = 0;  // hvs_reserve: queries per call the caller announced
-    uint32_t stage_k = 0;     // k the pinned result slots were sized for
-    bool dma_warm = false;    // the copy engines of s_in / s_out have moved a DMA-sized piece
     // planner probe (probe_format): the probe batch of 1024 queries stands for the large batches the format will serve, so it
     // runs with THEIR failure target -- and with their list capacity (HVS_FCAP entries per query and level): a format whose band
     // overflows that capacity fails in production too
@@ -644,14 +776,6 @@ int fail(hvs_ctx* c, int code, const std::string& msg)
     if (c) c->err = msg;
     return code;
 }
-
-#define HVS_HIP(ctx, call)                                                                                     \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? HVS_ENOMEM : HVS_EHIP,                                \
-                        std::string(#call) + ": " + hipGetErrorString(e_));                                    \
-    } while (0)
 
 template <typename T>
 int dev_alloc(hvs_ctx* c, T** p, size_t count)
@@ -1238,7 +1362,7 @@ int build_tiles(hvs_ctx* c, int fmt)
     return patch_tiles(c);  // (nothing while every row is live)
 }
 
-int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last);
+int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last, BatchGates gates = {});
 HvsGuessTable plan_guess(uint32_t k, bool proven, uint32_t pfail);
 
 bool is_filter_engine(int engine) { return engine == HVS_ENGINE_MFMA_FILTER || engine == HVS_ENGINE_MFMA_I8 || engine == HVS_ENGINE_MFMA_F16; }
@@ -1804,8 +1928,8 @@ uint32_t proven_batch_step(const hvs_ctx* c)
 }
 
 // One batch through the filter engine: the resident range [q0, q0 + nqb), or the nqb query indices in the device array
-// `list` (retry batches: `proven_last`, failures go to the exact engine).
-int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last)
+// `list` (retry batches: `proven_last`, failures go to the exact engine); `gates`: of a batch of a call on two lanes (HvsLaneGates).
+int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uint32_t* list, bool proven_last, BatchGates gates)
 {
     const int fmt = c->fmt.built;
     const uint32_t want_fcap = proven_last ? proven_fcap(c) : HVS_FCAP;
@@ -1829,7 +1953,7 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     const HvsGuessTable G = c->guess_tab[gslot];
     B.fail_code = proven_last ? HVS_FAIL_EXACT : HVS_FAIL_RETRY;
 
-    if (c->gate_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gate_heavy, 0));  // (two lanes: see hvs_ctx::ev_pdone)
+    if (gates.wait_heavy) HVS_HIP(c, hipStreamWaitEvent(c->stream, gates.wait_heavy, 0));  // (two lanes: see HvsLaneGates::ev_pdone)
     // level 0 by the exact kernel; small batches cut it into chunks so that enough waves are in flight
     const uint32_t l0blocks = L.off[1] - L.off[0];
     const uint32_t seed_waves = hvs_ceil_div(B.nslots, 64u);
@@ -1891,8 +2015,8 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             hipLaunchKernelGGL(filter_kernel, fgrid, dim3(64 * HVS_WG_WAVES), 0, c->stream, c->ord[0].tiles, c->ord[1].tiles, c->ord[0].nrm,
                                c->ord[1].nrm, c->ord[0].bpos, c->ord[1].bpos, L, level, B, W, c->call.d_counters);
             kernel_timer_end(c, ev);
-            if (level == L.K && c->ev_fdone_cur) HVS_HIP(c, hipEventRecord(c->ev_fdone_cur, c->stream));
-            if (level + 1u == L.K && c->ev_pdone_cur) HVS_HIP(c, hipEventRecord(c->ev_pdone_cur, c->stream));
+            if (level == L.K && gates.record_fdone) HVS_HIP(c, hipEventRecord(gates.record_fdone, c->stream));
+            if (level + 1u == L.K && gates.record_pdone) HVS_HIP(c, hipEventRecord(gates.record_pdone, c->stream));
         }
         with_cap_mask(c, [&](auto, auto MT) {
             with_after(c, [&](auto AT) {
@@ -2094,13 +2218,27 @@ RowCut cut_for(hvs_ctx* c, float sample_proportion)
     return RowCut{sn, sampled, of_rows};
 }
 
+// The spare lane's workspace for batches of up to nqb queries, with the spare lane swapped in (the caller's LaneGuard).  Without room
+// for it: HVS_OK and gates.lanes_failed.  (HVS_TEST_NO_SPARE=1: tests take the out-of-memory path without filling 288 GB)
+int ensure_spare_lane(hvs_ctx* c, uint32_t nqb)
+{
+    static const bool kTestNoSpare = env_u32("HVS_TEST_NO_SPARE", 0u, 0u, 1u) != 0u;
+    int rc = kTestNoSpare ? HVS_ENOMEM : ensure_filter_workspace(c, nqb);
+    if (!rc) rc = ensure_items(c);
+    if (rc != HVS_ENOMEM) return rc;
+    (void)hipGetLastError();
+    c->err.clear();
+    c->gates.lanes_failed = true;
+    return HVS_OK;
+}
+
 // Hooks of run_queries: `before(off, nqb)` is called before the kernels of a batch are enqueued (hvs_query makes the
 // compute stream wait for the batch's queries there: a batch never starts before its input is on the device);
 // `after(off, nqb, next_nqb)` after they have been enqueued (the host pipeline of hvs_query hangs its copies there);
 // queries [q0 + off, q0 + off + nqb) are complete on the stream at that point, except for overflowed ones
 // (resolve_overflow).
 template <typename Hooks>
-int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hooks, bool host_pipeline = false)
+int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hooks, bool host_pipeline = false)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
@@ -2130,7 +2268,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
     // Two lanes (HvsLane): every other batch of a filter-engine call runs on the spare lane's stream and workspace, so that
     // its preparation, seed and low levels share the chip with the previous batch's last re-scoring and final merge.  The
     // spare lane starts behind the call's counter resets (ev_q0) and the main stream joins it before the call ends.
-    bool two_lanes = mfma && kLanes && sched.size() >= 2 && !c->lanes_failed;
+    bool two_lanes = mfma && kLanes && sched.size() >= 2 && !c->gates.lanes_failed;
     bool spare_used = false;
     struct JoinOnError {  // a call that fails half-way leaves no kernels running on the spare lane behind the caller's back
         hvs_ctx* c;
@@ -2149,51 +2287,36 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks hook
             swap_lanes(c);
             lane.on = true;
             // the spare workspace is allocated here, ahead of the batch: without room for it the call stays on one lane
-            // (HVS_TEST_NO_SPARE=1: tests take the out-of-memory path without filling 288 GB)
-            static const bool kTestNoSpare = env_u32("HVS_TEST_NO_SPARE", 0u, 0u, 1u) != 0u;
-            int rcw = kTestNoSpare ? HVS_ENOMEM : ensure_filter_workspace(c, nqb);
-            if (!rcw) rcw = ensure_items(c);
-            if (rcw == HVS_ENOMEM) {
-                (void)hipGetLastError();
-                c->err.clear();
+            if (int rcw = ensure_spare_lane(c, nqb)) return rcw;
+            if (c->gates.lanes_failed) {
                 swap_lanes(c);
                 lane.on = false;
                 two_lanes = false;
-                c->lanes_failed = true;
-            } else if (rcw) {
-                return rcw;
             } else if (!spare_used) {
                 HVS_HIP(c, hipStreamWaitEvent(c->stream, c->call.ev_q0, 0));
                 spare_used = true;
             }
         }
-        if (two_lanes) {
-            // this batch's preparation starts behind the previous batch's (other lane) second-to-last filter launch, its seed
-            // behind the last one; it records its own two events
-            const bool have_prev = b > 0 && c->lv.K >= 1u;
-            if (have_prev) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->lv.K >= 2u ? c->ev_pdone[(b - 1u) & 1u] : c->ev_fdone[(b - 1u) & 1u], 0));
-            c->gate_heavy = have_prev ? c->ev_fdone[(b - 1u) & 1u] : nullptr;
-            c->ev_fdone_cur = c->ev_fdone[b & 1u];
-            c->ev_pdone_cur = c->ev_pdone[b & 1u];
-        }
+        // two lanes: preparation behind the previous batch's (other lane) second-to-last filter launch, seed behind its last one
+        const bool have_prev = two_lanes && b > 0 && c->lv.K >= 1u;
+        if (have_prev) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gates.start_of(b, c->lv.K), 0));
         int rc = hooks.before(off, nqb);
         if (!rc)
-            rc = mfma ? run_batch_mfma(c, q0 + off, nqb, sn, nullptr, false)
+            rc = mfma ? run_batch_mfma(c, q0 + off, nqb, sn, nullptr, false, two_lanes ? c->gates.of_batch(b, have_prev) : BatchGates{})
                       : (ranges ? run_batch_exact_ranges(c, q0 + off, nqb, sn) : run_batch_exact(c, q0 + off, nqb, sn));
-        c->ev_fdone_cur = c->ev_pdone_cur = c->gate_heavy = nullptr;
         if (rc) return rc;
         if ((rc = hooks.after(off, nqb, b + 1 < sched.size() ? sched[b + 1] : 0u))) return rc;
-        if (lane.on) HVS_HIP(c, hipEventRecord(c->ev_lane, c->stream));
+        if (lane.on) HVS_HIP(c, hipEventRecord(c->gates.ev_lane, c->stream));
         off += nqb;
     }
-    if (spare_used) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_lane, 0));
+    if (spare_used) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->gates.ev_lane, 0));
     const int rc = call_enqueued(c, nq, mfma, sn);
     join_on_error.ok = rc == HVS_OK;
     return rc;
 }
 
 template <typename Hooks>
-int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, Hooks hooks, bool host_pipeline = false)
+int run_queries(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion, Hooks&& hooks, bool host_pipeline = false)
 {
     return run_queries_cut(c, q0, nq, cut_for(c, sample_proportion), hooks, host_pipeline);
 }
@@ -2241,21 +2364,10 @@ int leaf_create(hvs_ctx** out, int device)
     }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipStreamCreateWithFlags(&c->spare.stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_lane, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    for (hipEvent_t& ev : c->ev_fdone)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    for (hipEvent_t& ev : c->ev_pdone)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = c->gates.create()) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreate(&c->call.ev_q0)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreate(&c->call.ev_q1)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    for (int i = 0; i < hvs_ctx::kRing; ++i) {
-        if ((e = hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    }
+    if (const char* what = c->pipe.create(c, &e)) return bail(what, e);
     if ((e = hipMalloc(reinterpret_cast<void**>(&c->call.d_counters), HVS_CNT_COUNT * sizeof(unsigned long long))) != hipSuccess)
         return bail("hipMalloc", e);
     if ((e = hipMalloc(reinterpret_cast<void**>(&c->call.d_ovf_count), 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
@@ -2263,20 +2375,7 @@ int leaf_create(hvs_ctx** out, int device)
     if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->call.h_ovf), 2 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
         return bail("hipHostMalloc", e);
     c->call.h_ovf[0] = c->call.h_ovf[1] = 0u;
-    // The first operation on a stream creates its hardware queue (and the first copy in each direction its DMA path): a few
-    // milliseconds that belong here, not inside the first query (round 3's cold hvs_query of 10^4 queries took 8 ms for 2 ms
-    // of device work).
-    (void)hipMemsetAsync(c->call.d_ovf_count, 0, 2 * sizeof(uint32_t), c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipMemsetAsync(c->call.d_ovf_count, 0, 2 * sizeof(uint32_t), c->spare.stream);
-    (void)hipStreamSynchronize(c->spare.stream);
-    (void)hipMemcpyAsync(c->call.d_ovf_count, c->call.h_ovf, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_in);
-    (void)hipStreamSynchronize(c->s_in);
-    (void)hipMemcpyAsync(c->call.h_ovf, c->call.d_ovf_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_out);
-    (void)hipEventRecord(c->ev_batch, c->stream);
-    (void)hipStreamWaitEvent(c->s_out, c->ev_batch, 0);
-    (void)hipStreamSynchronize(c->s_out);
-    (void)hipGetLastError();
+    c->pipe.warm_streams(c->stream, c->spare.stream, c->call.d_ovf_count, c->call.h_ovf);
     *out = c;
     return HVS_OK;
 }
@@ -2285,8 +2384,7 @@ void leaf_destroy(hvs_ctx* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->s_in) (void)hipStreamSynchronize(c->s_in);
-    if (c->s_out) (void)hipStreamSynchronize(c->s_out);
+    c->pipe.sync();
     if (c->spare.stream) (void)hipStreamSynchronize(c->spare.stream);
     free_index(c);  // (keeps ord[].lp: freed here)
     void* ptrs[] = {c->d_data, c->d_q, c->d_out_ids, c->d_out_dists, c->call.d_counters, c->d_bounds, c->d_quant,
@@ -2304,29 +2402,14 @@ void leaf_destroy(hvs_ctx* c)
     }
     free_lane(c->spare);
     free_lane(static_cast<HvsLane&>(*c));
-    if (c->ev_lane) (void)hipEventDestroy(c->ev_lane);
-    for (hipEvent_t ev : c->ev_fdone)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : c->ev_pdone)
-        if (ev) (void)hipEventDestroy(ev);
+    c->gates.destroy();
     if (c->call.h_ovf) (void)hipHostFree(c->call.h_ovf);
-    for (int i = 0; i < hvs_ctx::kRing; ++i) {
-        if (c->h_in[i]) (void)hipHostFree(c->h_in[i]);
-        if (c->h_out_ids[i]) (void)hipHostFree(c->h_out_ids[i]);
-        if (c->h_out_dists[i]) (void)hipHostFree(c->h_out_dists[i]);
-        if (c->ev_in[i]) (void)hipEventDestroy(c->ev_in[i]);
-        if (c->ev_out[i]) (void)hipEventDestroy(c->ev_out[i]);
-    }
-    if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
-    if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
     if (c->call.ev_q0) (void)hipEventDestroy(c->call.ev_q0);
     if (c->call.ev_q1) (void)hipEventDestroy(c->call.ev_q1);
     for (hipEvent_t e : c->call.ev_k) (void)hipEventDestroy(e);
-    if (c->s_in) (void)hipStreamDestroy(c->s_in);
-    if (c->s_out) (void)hipStreamDestroy(c->s_out);
+    c->pipe.destroy();
 }
 
-int ensure_staging(hvs_ctx* c, bool dists, uint64_t nq_in, uint64_t nq_out);
 int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq);
 
 // query / result buffers and the batch workspace for calls of up to nq queries (hvs_reserve, hvs_query): keeps the
@@ -2343,20 +2426,8 @@ int leaf_reserve(hvs_ctx* c, uint32_t nq)
     int rc = ensure_queries(c, nq);
     if (rc) return rc;
     // pinned staging of the host path (ids only: the distance slots follow the first call that asks for distances)
-    if ((rc = ensure_staging(c, false, nq, nq))) return rc;
-    if (!c->dma_warm && c->nq == 0u && c->h_out_ids[0] && c->h_in[0] && c->d_out_ids && c->d_q) {  // (no resident queries to overwrite)
-        // the first DMA-sized copy in each direction sets up its engine queue (a cold 4 MB D2H took 6 ms): here, not in the first query
-        const size_t bytes = std::min<size_t>((size_t)1 << 20, std::min((size_t)c->out_cap_q[0] * c->stage_k * sizeof(uint32_t),
-                                                                      (size_t)c->in_cap_q[0] * HVS_QCOLS * sizeof(float)));
-        if (bytes && (size_t)nq * c->k * sizeof(uint32_t) >= bytes) {
-            (void)hipMemcpyAsync(c->h_out_ids[0], c->d_out_ids, bytes, hipMemcpyDeviceToHost, c->s_out);
-            (void)hipMemcpyAsync(c->d_q, c->h_in[0], bytes, hipMemcpyHostToDevice, c->s_in);
-            (void)hipStreamSynchronize(c->s_out);
-            (void)hipStreamSynchronize(c->s_in);
-            (void)hipGetLastError();
-            c->dma_warm = true;
-        }
-    }
+    if ((rc = c->pipe.size_for(c->k, false, nq, nq))) return rc;
+    if (c->nq == 0u) c->pipe.warm_dma(c->d_out_ids, c->d_q, (size_t)nq * c->k * sizeof(uint32_t));  // (no resident queries to overwrite)
     // (the filter workspace only when a filter engine is going to run: 4096 <= n < 32768 under AUTO has an index for the
     // range scans of the exact engine, whose batches are kBatch queries)
     if (c->have_order && filter_engine_selected(c)) {
@@ -2371,17 +2442,10 @@ int leaf_reserve(hvs_ctx* c, uint32_t nq)
             const std::vector<uint32_t> sched = batch_schedule(nq, kBatchMfma, host != 0);
             for (size_t b = 1; b < sched.size(); b += 2) spare_nq = std::max(spare_nq, sched[b]);
         }
-        if (kLanes && spare_nq && !c->lanes_failed) {
+        if (kLanes && spare_nq && !c->gates.lanes_failed) {
             LaneGuard lane{c, true};
             swap_lanes(c);
-            rc = ensure_filter_workspace(c, spare_nq);
-            if (!rc) rc = ensure_items(c);
-            if (rc == HVS_ENOMEM) {
-                (void)hipGetLastError();
-                c->err.clear();
-                c->lanes_failed = true;
-                rc = HVS_OK;
-            }
+            rc = ensure_spare_lane(c, spare_nq);
         }
         return rc;
     }
@@ -2570,55 +2634,6 @@ bool host_pointer_is_pinned(const void* p)
     return a.type == hipMemoryTypeHost;
 }
 
-// Pinned staging slots of the host pipeline, sized by the call: a call of nq_in queries (or the same volume of data rows)
-// going in and nq_out result rows coming out uses ceil(nq / 65536) slots of each ring, at most 4, each as large as its
-// piece (whole slots are 27 + 26 + 26 MB; round 3 allocated all twelve inside the first call, 6 of the 8 ms a cold call of
-// 10^4 queries took).  Pinned allocations cost ~1 ms per 25 MB: hvs_reserve makes them ahead of the first call.
-int ensure_staging(hvs_ctx* c, bool dists, uint64_t nq_in, uint64_t nq_out)
-{
-    constexpr uint32_t SQ = hvs_ctx::kStageQ;
-    if (c->stage_k < c->k) {  // k grew (hvs_set_k): the result slots are too small
-        for (int i = 0; i < hvs_ctx::kRing; ++i) {
-            if (c->h_out_ids[i]) (void)hipHostFree(c->h_out_ids[i]);
-            if (c->h_out_dists[i]) (void)hipHostFree(c->h_out_dists[i]);
-            c->h_out_ids[i] = nullptr;
-            c->h_out_dists[i] = nullptr;
-            c->out_cap_q[i] = c->outd_cap_q[i] = 0u;
-        }
-        c->stage_k = c->k;
-    }
-    auto slot_q = [&](uint64_t nq, int i) -> uint32_t {  // queries slot i has to hold (0: the call does not reach it)
-        if (nq <= (uint64_t)i * SQ) return 0u;
-        const uint64_t piece = nq > (uint64_t)hvs_ctx::kRing * SQ ? SQ : std::min<uint64_t>(SQ, nq - (uint64_t)i * SQ);
-        return (uint32_t)std::min<uint64_t>(SQ, (piece + 4095u) / 4096u * 4096u);
-    };
-    for (int i = 0; i < hvs_ctx::kRing; ++i) {
-        const uint32_t qi = slot_q(nq_in, i), qo = slot_q(nq_out, i);
-        if (qi > c->in_cap_q[i]) {
-            if (c->h_in[i]) (void)hipHostFree(c->h_in[i]);
-            c->h_in[i] = nullptr;
-            c->in_cap_q[i] = 0u;
-            HVS_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_in[i]), (size_t)qi * HVS_QCOLS * sizeof(float), hipHostMallocDefault));
-            c->in_cap_q[i] = qi;
-        }
-        if (qo > c->out_cap_q[i]) {
-            if (c->h_out_ids[i]) (void)hipHostFree(c->h_out_ids[i]);
-            c->h_out_ids[i] = nullptr;
-            c->out_cap_q[i] = 0u;
-            HVS_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out_ids[i]), (size_t)qo * c->stage_k * sizeof(uint32_t), hipHostMallocDefault));
-            c->out_cap_q[i] = qo;
-        }
-        if (dists && qo > c->outd_cap_q[i]) {
-            if (c->h_out_dists[i]) (void)hipHostFree(c->h_out_dists[i]);
-            c->h_out_dists[i] = nullptr;
-            c->outd_cap_q[i] = 0u;
-            HVS_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out_dists[i]), (size_t)qo * c->stage_k * sizeof(float), hipHostMallocDefault));
-            c->outd_cap_q[i] = qo;
-        }
-    }
-    return HVS_OK;
-}
-
 // H2D of rows into c->d_data (or any device buffer), from pageable or pinned host memory.  Pageable sources go
 // through the pinned ring in 27 MB pieces so that the host copy of piece i+1 overlaps the DMA of piece i
 // (reference io.h:111-136 is replaced by the caller's bulk read; this replaces the staging an H2D of pageable memory
@@ -2631,20 +2646,12 @@ int upload_rows(hvs_ctx* c, float* dst, const float* src, size_t nfloats)
         return HVS_OK;
     }
     // (in units of query rows: 104 floats; data rows move through the same slots)
-    int rc = ensure_staging(c, false, (nfloats + HVS_QCOLS - 1u) / HVS_QCOLS, 0u);
-    if (rc) return rc;
-    const size_t slot = (size_t)hvs_ctx::kStageQ * HVS_QCOLS;  // floats per slot
+    int rc = c->pipe.size_for(c->k, false, (nfloats + HVS_QCOLS - 1u) / HVS_QCOLS, 0u);
+    const size_t slot = (size_t)HvsCopyPipe::kStageQ * HVS_QCOLS;  // floats per slot
     size_t off = 0;
-    for (int i = 0; off < nfloats; ++i, off += slot) {
-        const int k = i % hvs_ctx::kRing;
-        const size_t m = std::min(slot, nfloats - off);
-        if (i >= hvs_ctx::kRing) HVS_HIP(c, hipEventSynchronize(c->ev_in[k]));  // the slot's previous DMA is done
-        staging_copy(c->h_in[k], src + off, m * sizeof(float));
-        HVS_HIP(c, hipMemcpyAsync(dst + off, c->h_in[k], m * sizeof(float), hipMemcpyHostToDevice, c->s_in));
-        HVS_HIP(c, hipEventRecord(c->ev_in[k], c->s_in));
-    }
-    HVS_HIP(c, hipStreamSynchronize(c->s_in));
-    return HVS_OK;
+    for (uint32_t piece = 0; !rc && off < nfloats; ++piece, off += slot)
+        rc = c->pipe.stage_in(dst + off, src + off, std::min(slot, nfloats - off) * sizeof(float), piece);
+    return rc ? rc : c->pipe.wait_in();
 }
 
 // upload only (the multi-GPU root lets the other GPUs copy D from this one while it builds its index)
@@ -3229,6 +3236,109 @@ int fetch_rerun_rows(hvs_ctx* c, const PeerSink* sink, uint32_t* out_ids, float*
     return HVS_OK;
 }
 
+// One hvs_query's side of HvsCopyPipe: where the call stands in its pieces of 65536 queries, and the hooks of run_queries, which
+// runs the engine batch by batch on its own schedule.  Before the kernels of batch b are enqueued the compute stream is made to
+// wait for the batch's queries (staged here if the previous batch's hook has not done so): a batch never starts before its input
+// is on the device.  After they have been enqueued: batch b+1's queries are staged and sent, the results of everything BEFORE batch b
+// are sent out and drained, and s_out is told to wait for batch b.  A batch's host work hides under its own compute.
+struct PipeCall {
+    static constexpr uint32_t SQ = HvsCopyPipe::kStageQ, R = HvsCopyPipe::kRing;
+    hvs_ctx* c;
+    HvsCopyPipe& P;       // c->pipe
+    const float* q_rows;  // the caller's nq queries, and where their rows go: the caller's arrays or the peer sink
+    uint32_t nq;
+    uint32_t* out_ids;
+    float* out_dists;
+    const PeerSink* sink;
+    bool in_pinned, out_pinned;  // the copies skip the slots
+    HostTrace& tr;
+    uint32_t in_next = 0;                   // input pieces enqueued so far
+    uint32_t out_enq = 0, out_drained = 0;  // result pieces enqueued / drained (global numbering over the call)
+    uint32_t staged_q = 0;  // queries [0, staged_q) are enqueued on the copy-in stream and the compute stream waits for them
+    uint32_t npieces() const { return hvs_ceil_div(nq, SQ); }
+    int stage_in_until(uint32_t p1)  // --- copy-in: pieces [in_next, p1) -> device
+    {
+        for (; in_next < p1; ++in_next) {
+            const uint32_t q0 = in_next * SQ, m = std::min(SQ, nq - q0);
+            const size_t bytes = (size_t)m * HVS_QCOLS * sizeof(float);
+            float* dst = c->d_q + (size_t)q0 * HVS_QCOLS;
+            const float* src = q_rows + (size_t)q0 * HVS_QCOLS;
+            if (in_pinned)
+                HVS_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, P.s_in));
+            else if (int rc = P.stage_in(dst, src, bytes, in_next))
+                return rc;
+        }
+        return HVS_OK;
+    }
+    int drain_one()  // --- copy-out of result pieces: D2H on s_out into slot piece % 4, drained before piece + 4 is sent
+    {
+        const uint32_t i = out_drained % R, q0 = out_drained * SQ, m = std::min(SQ, nq - q0);
+        const size_t nb = (size_t)m * c->k * sizeof(uint32_t), at = (size_t)q0 * c->k;
+        HVS_HIP(c, hipEventSynchronize(P.ev_out[i]));
+        staging_copy(out_ids + at, P.h_out_ids[i], nb);
+        if (out_dists) staging_copy(out_dists + at, P.h_out_dists[i], nb);
+        ++out_drained;
+        return HVS_OK;
+    }
+    int copy_out_until(uint32_t p1)
+    {
+        hipStream_t s_out = P.s_out;
+        for (; out_enq < p1; ++out_enq) {
+            const uint32_t q0 = out_enq * SQ, m = std::min(SQ, nq - q0);
+            const size_t nb = (size_t)m * c->k * sizeof(uint32_t), at = (size_t)q0 * c->k;
+            if (sink) {
+                const size_t dst = ((size_t)sink->row0 + q0) * c->k;
+                HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_ids + dst, sink->ctx->device, c->d_out_ids + at, c->device, nb, s_out));
+                if (sink->want_dists)
+                    HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_dists + dst, sink->ctx->device, c->d_out_dists + at, c->device, nb, s_out));
+                continue;
+            }
+            if (out_pinned) {
+                HVS_HIP(c, hipMemcpyAsync(out_ids + at, c->d_out_ids + at, nb, hipMemcpyDeviceToHost, s_out));
+                if (out_dists) HVS_HIP(c, hipMemcpyAsync(out_dists + at, c->d_out_dists + at, nb, hipMemcpyDeviceToHost, s_out));
+                continue;
+            }
+            if (out_enq - out_drained >= R)
+                if (int rc = drain_one()) return rc;
+            const uint32_t i = out_enq % R;
+            HVS_HIP(c, hipMemcpyAsync(P.h_out_ids[i], c->d_out_ids + at, nb, hipMemcpyDeviceToHost, s_out));
+            if (out_dists) HVS_HIP(c, hipMemcpyAsync(P.h_out_dists[i], c->d_out_dists + at, nb, hipMemcpyDeviceToHost, s_out));
+            HVS_HIP(c, hipEventRecord(P.ev_out[i], s_out));
+        }
+        return HVS_OK;
+    }
+    int send_input(uint32_t upto_q, bool wait_here)
+    {
+        upto_q = std::min(nq, upto_q);
+        if (upto_q <= staged_q) {
+            // staged by the previous batch's hook, which made ITS lane's stream wait: this batch's stream waits itself
+            if (wait_here && staged_q) HVS_HIP(c, hipStreamWaitEvent(c->stream, P.ev_stage, 0));
+            return HVS_OK;
+        }
+        if (int rc = stage_in_until(std::min(npieces(), hvs_ceil_div(upto_q, SQ)))) return rc;
+        HVS_HIP(c, hipEventRecord(P.ev_stage, P.s_in));
+        if (wait_here) HVS_HIP(c, hipStreamWaitEvent(c->stream, P.ev_stage, 0));
+        if (staged_q == 0u) tr.mark("in0");
+        staged_q = std::min(nq, in_next * SQ);
+        return HVS_OK;
+    }
+    int before(uint32_t off, uint32_t nqb) { return send_input(off + nqb, true); }  // --- the hooks of run_queries
+    int after(uint32_t off, uint32_t nqb, uint32_t next_nqb)
+    {
+        int rc = next_nqb ? send_input(off + nqb + next_nqb, false) : HVS_OK;
+        if (!rc) rc = copy_out_until(off / SQ);  // whole pieces of the batches before this one
+        return rc ? rc : P.after_compute(c->stream, P.s_out);
+    }
+    int flush()  // --- behind the last batch: what is left goes out, and has arrived when this returns
+    {
+        int rc = copy_out_until(npieces());
+        while (!rc && !out_pinned && out_drained < out_enq) rc = drain_one();
+        tr.mark("drained");
+        if (!rc) HVS_HIP(c, hipStreamSynchronize(P.s_out));
+        return rc;
+    }
+};
+
 // `max_d2` (hvs_query_within): the queries' distance caps, nq floats of host memory -- 4 bytes per query, sent whole before the
 // pipeline starts.
 int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists,
@@ -3245,123 +3355,15 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     const bool in_pinned = host_pointer_is_pinned(q_rows);
     // (a peer sink behaves like a pinned destination: asynchronous copies straight from the result buffer, nothing to drain)
     const bool out_pinned = sink || (host_pointer_is_pinned(out_ids) && (!out_dists || host_pointer_is_pinned(out_dists)));
-    if ((rc = ensure_staging(c, out_dists != nullptr && !sink, in_pinned ? 0u : nq, out_pinned ? 0u : nq))) return rc;
+    if ((rc = c->pipe.size_for(c->k, out_dists != nullptr && !sink, in_pinned ? 0u : nq, out_pinned ? 0u : nq))) return rc;
     tr.mark("staging");
     c->nq = nq;
     if ((rc = attach_for_call(c, max_d2, after_d, after_i, nq))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too)
-    const bool sink_dists = sink && sink->want_dists;
-    constexpr uint32_t SQ = hvs_ctx::kStageQ;
-    constexpr int R = hvs_ctx::kRing;
-    const uint32_t npieces = hvs_ceil_div(nq, SQ);
-
-    // --- copy-in: pieces [p0, p1) -> device
-    uint32_t in_next = 0;  // pieces enqueued so far
-    auto stage_in_until = [&](uint32_t p1) -> int {
-        for (; in_next < p1; ++in_next) {
-            const uint32_t q0 = in_next * SQ, m = std::min(SQ, nq - q0);
-            const size_t bytes = (size_t)m * HVS_QCOLS * sizeof(float);
-            float* dst = c->d_q + (size_t)q0 * HVS_QCOLS;
-            if (in_pinned) {
-                HVS_HIP(c, hipMemcpyAsync(dst, q_rows + (size_t)q0 * HVS_QCOLS, bytes, hipMemcpyHostToDevice, c->s_in));
-            } else {
-                const int k = (int)(in_next % R);
-                if (in_next >= (uint32_t)R) HVS_HIP(c, hipEventSynchronize(c->ev_in[k]));
-                staging_copy(c->h_in[k], q_rows + (size_t)q0 * HVS_QCOLS, bytes);
-                HVS_HIP(c, hipMemcpyAsync(dst, c->h_in[k], bytes, hipMemcpyHostToDevice, c->s_in));
-                HVS_HIP(c, hipEventRecord(c->ev_in[k], c->s_in));
-            }
-        }
-        return HVS_OK;
-    };
-    // --- copy-out of queries [q0, q0 + m): D2H pieces on s_out (after `ready`), drained into the caller's arrays
-    uint32_t out_enq = 0, out_drained = 0;  // pieces (global numbering over the call)
-    auto drain_one = [&]() -> int {
-        const int k = (int)(out_drained % R);
-        HVS_HIP(c, hipEventSynchronize(c->ev_out[k]));
-        const uint32_t q0 = out_drained * SQ, m = std::min(SQ, nq - q0);
-        staging_copy(out_ids + (size_t)q0 * c->k, c->h_out_ids[k], (size_t)m * c->k * sizeof(uint32_t));
-        if (out_dists) staging_copy(out_dists + (size_t)q0 * c->k, c->h_out_dists[k], (size_t)m * c->k * sizeof(float));
-        ++out_drained;
-        return HVS_OK;
-    };
-    auto copy_out_until = [&](uint32_t p1) -> int {
-        for (; out_enq < p1; ++out_enq) {
-            const uint32_t q0 = out_enq * SQ, m = std::min(SQ, nq - q0);
-            const size_t nb = (size_t)m * c->k * sizeof(uint32_t);
-            if (sink) {
-                const size_t dst = ((size_t)sink->row0 + q0) * c->k;
-                HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_ids + dst, sink->ctx->device, c->d_out_ids + (size_t)q0 * c->k, c->device, nb, c->s_out));
-                if (sink_dists)
-                    HVS_HIP(c, hipMemcpyPeerAsync(sink->ctx->d_out_dists + dst, sink->ctx->device, c->d_out_dists + (size_t)q0 * c->k, c->device, nb,
-                                                  c->s_out));
-                continue;
-            }
-            if (out_pinned) {
-                HVS_HIP(c, hipMemcpyAsync(out_ids + (size_t)q0 * c->k, c->d_out_ids + (size_t)q0 * c->k, nb, hipMemcpyDeviceToHost, c->s_out));
-                if (out_dists)
-                    HVS_HIP(c, hipMemcpyAsync(out_dists + (size_t)q0 * c->k, c->d_out_dists + (size_t)q0 * c->k, nb, hipMemcpyDeviceToHost, c->s_out));
-                continue;
-            }
-            if (out_enq - out_drained >= (uint32_t)R) {
-                int rc2 = drain_one();
-                if (rc2) return rc2;
-            }
-            const int k = (int)(out_enq % R);
-            HVS_HIP(c, hipMemcpyAsync(c->h_out_ids[k], c->d_out_ids + (size_t)q0 * c->k, nb, hipMemcpyDeviceToHost, c->s_out));
-            if (out_dists)
-                HVS_HIP(c, hipMemcpyAsync(c->h_out_dists[k], c->d_out_dists + (size_t)q0 * c->k, nb, hipMemcpyDeviceToHost, c->s_out));
-            HVS_HIP(c, hipEventRecord(c->ev_out[k], c->s_out));
-        }
-        return HVS_OK;
-    };
-
-    // The engine runs batch by batch on run_queries' own schedule.  Before the kernels of batch b are enqueued the
-    // compute stream is made to wait for the batch's queries (staged here if the previous batch's hook has not done so:
-    // the first batch, or a schedule that changed) -- a batch never starts before its input is on the device.  After
-    // they have been enqueued (the GPU is busy with them): batch b+1's queries are staged and sent, the results of
-    // everything BEFORE batch b are sent out and drained, and the copy-out stream is told to wait for batch b.  The
-    // host work of a batch (two staging copies, ~0.2 s per 2^20 queries) hides under the batch's own compute.
-    uint32_t staged_q = 0;  // queries [0, staged_q) are enqueued on the copy-in stream and the compute stream waits for them
-    auto send_input = [&](uint32_t upto_q, bool wait_here) -> int {
-        upto_q = std::min(nq, upto_q);
-        if (upto_q <= staged_q) {
-            // staged by the previous batch's hook, which made ITS lane's stream wait: this batch's stream waits itself
-            if (wait_here && staged_q) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_stage, 0));
-            return HVS_OK;
-        }
-        int r2 = stage_in_until(std::min(npieces, hvs_ceil_div(upto_q, SQ)));
-        if (r2) return r2;
-        HVS_HIP(c, hipEventRecord(c->ev_stage, c->s_in));
-        if (wait_here) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_stage, 0));
-        if (staged_q == 0u) tr.mark("in0");
-        staged_q = std::min(nq, in_next * SQ);
-        return HVS_OK;
-    };
-    struct Hooks {
-        decltype(send_input)& send;
-        decltype(copy_out_until)& copy_out;
-        hvs_ctx* c;
-        uint32_t nq;
-        int before(uint32_t off, uint32_t nqb) const { return send(off + nqb, true); }
-        int after(uint32_t off, uint32_t nqb, uint32_t next_nqb) const
-        {
-            int r2;
-            if (next_nqb && (r2 = send(off + nqb + next_nqb, false))) return r2;
-            if ((r2 = copy_out(off / hvs_ctx::kStageQ))) return r2;  // whole pieces of the batches before this one
-            HVS_HIP(c, hipEventRecord(c->ev_batch, c->stream));
-            HVS_HIP(c, hipStreamWaitEvent(c->s_out, c->ev_batch, 0));
-            return HVS_OK;
-        }
-    };
-    const Hooks hooks{send_input, copy_out_until, c, nq};
+    PipeCall call{c, c->pipe, q_rows, nq, out_ids, out_dists, sink, in_pinned, out_pinned, tr};
     tr.mark("pointers");
-    if ((rc = run_queries(c, 0, nq, sample_proportion, hooks, true))) return rc;
+    if ((rc = run_queries(c, 0, nq, sample_proportion, call, true))) return rc;
     tr.mark("enqueued");
-    if ((rc = copy_out_until(npieces))) return rc;
-    while (!out_pinned && out_drained < out_enq)
-        if ((rc = drain_one())) return rc;
-    tr.mark("drained");
-    HVS_HIP(c, hipStreamSynchronize(c->s_out));
+    if ((rc = call.flush())) return rc;
     tr.mark("s_out");
     // queries answered a second time: re-run now, their rows fetched again
     const bool had_ovf = c->call.pending;
@@ -4813,9 +4815,7 @@ int hvs_stream_wait(hvs_ctx* c, void* stream)
     HVS_HIP(c, hipSetDevice(c->device));
     int rc = resolve_overflow(c);
     if (rc) return rc;
-    HVS_HIP(c, hipEventRecord(c->ev_batch, c->stream));
-    HVS_HIP(c, hipStreamWaitEvent(static_cast<hipStream_t>(stream), c->ev_batch, 0));
-    return HVS_OK;
+    return c->pipe.after_compute(c->stream, static_cast<hipStream_t>(stream));
 }
 
 int hvs_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids,
