@@ -275,8 +275,10 @@ struct HvsQuerySet {
     void drop_attached()  // caps off, cursors off, no results: they belonged to a set that is no longer the engines'
     {
         caps_set = after_set = false;
-        res_lo = res_hi = 0;
+        drop_results();
     }
+    // no query has a result row: the rows (under sets the merged rows too) hold ids of a row numbering that has gone
+    void drop_results() { res_lo = res_hi = 0; }
     // a call answered [q0, q0 + nq) of set `gen` with k slots: its range joins the ranges answered so far if it touches them
     void answered(uint32_t q0, uint32_t nq, uint32_t k, uint32_t gen)
     {
@@ -3738,6 +3740,7 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     // NOTE: a load does neither of the last two; whether that is meant is not recorded (hvs_mask_info.tiles_patched, hvs_last_timing)
     if (c->rs.d_mask_stat) HVS_HIP(c, hipMemsetAsync(c->rs.d_mask_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     call_forgotten(c);
+    c->qs.drop_results();  // (they hold old ids: hvs_set_after_from_results must not read them; queries, sets, caps and cursors stay)
     // one index over all rows -- or none, by the rule of a load (fewer than 4096 rows, or no room for one)
     if (c->n >= kIndexMinRows || is_filter_engine(c->engine)) return leaf_reindex(c, true);
     free_index(c);
