@@ -666,6 +666,49 @@ int hvs_in_stats(hvs_ctx *ctx, hvs_in_info *out);
 uint32_t hvs_in_plan(const float *q_rows /* nq x 104, may be NULL = all type 1 */, const uint32_t *set_offsets, const float *set_values, uint32_t nq,
                      uint32_t *sub_offsets /* nq+1 */, uint32_t *parent, float *value /* NaN-free but for "matches nothing"; both may be NULL */);
 
+/* ---- category sets from device memory: the plan is made on the GPU --------------------------------- */
+
+/*
+ * hvs_set_category_sets_device(ctx, d_set_offsets, d_set_values, nq, stream): hvs_set_category_sets for a CSR that lies in
+ * DEVICE memory -- a model's "allowed categories" per query, a join kernel's output.  Afterwards the context is in every respect
+ * the context after hvs_set_category_sets of the same bytes: the same expanded resident set and answers, the same
+ * hvs_download_queries, the same per-GPU slices on a replicated multi-GPU context, earlier results, caps and cursors dropped,
+ * the same hvs_in_stats but for the two times, the same lifetime.  The call is accepted exactly when the host call accepts the
+ * same bytes, and otherwise refused with HVS_EINVAL, nothing changing (sets already attached, results, caps and cursors stay in
+ * force): d_set_offsets[0] != 0, a descending pair of offsets anywhere, a set of more than HVS_IN_MAX_VALUES distinct categories
+ * on a query of any type, nq != the number of resident queries, 2^32 - 1 or more sub-queries counted as if every query tested
+ * C (as hvs_in_plan(NULL, ...) counts them; the kernels form that sum and the true one in 64 bits).  Both pointers NULL, or
+ * nq == 0: the sets are removed, as in the host call.  d_set_offsets == NULL with values given: HVS_EINVAL.  d_set_values ==
+ * NULL is valid exactly when d_set_offsets[nq] == 0.  No data set loaded: HVS_ESTATE; a row-partitioned context: HVS_ESTATE,
+ * not supported (yet).
+ *
+ * The buffers follow the rules of hvs_set_max_dist2_device / hvs_set_after_device: plain device memory of any visible GPU, both
+ * on the same one; `stream` = the stream that produced them (NULL: the null stream); host memory of any kind is HVS_EINVAL with
+ * the runtime's error cleared; the call blocks until the sets are attached; the buffers are only read -- offsets[nq] is trusted
+ * to be the length of the value array once every pair of offsets has been found ascending, and nothing past it is read -- and
+ * are the caller's again on return.
+ *
+ * What crosses PCIe: the set values never reach the host, and parent / value are never built there.  Three kernels make the
+ * plan -- per query, one wave normalises its raw values (any number of them) and counts the distinct categories; a scan turns
+ * the counts into sub_offsets; a second per-query pass writes parent and value, ascending --, bit for bit the plan of
+ * hvs_in_plan(q_rows, ...).  The host reads back a status block (flags and the two 64-bit sub-query sums), the offsets at the
+ * GPUs' slice boundaries (4 bytes per GPU, and offsets[nq]), and sub_offsets (4 bytes per user query) and one byte per query
+ * "answered through its set", because hvs_query_resident maps query ranges to sub-query ranges on the host.  A buffer on the
+ * context's own GPU is read in place; a GPU of a replicated context that does not hold the buffer copies its owner range's
+ * slice of the offsets, and the values that slice points into, device to device.  Every GPU plans first and none changes
+ * unless every plan is good: sets are attached on all GPUs or on none.
+ * hvs_in_info.expand_ms of a device attach is the device time of the plan kernels plus the expansion.
+ *
+ * hvs_download_in_plan: a diagnostic -- the plan as it lies on the device (whichever entry point attached the sets) copied to
+ * the host.  Returns nsub, the number of sub-queries; sub_offsets (nq + 1 entries of the USER's nq queries) is written whenever
+ * it is not NULL, parent and value (nsub entries each) only when cap >= nsub.  Single-GPU contexts only (HVS_EINVAL otherwise);
+ * HVS_ESTATE while no sets are attached.
+ */
+int hvs_set_category_sets_device(hvs_ctx *ctx, const uint32_t *d_set_offsets /* device, nq+1 */, const float *d_set_values /* device */,
+                                 uint32_t nq, void *stream);
+int hvs_download_in_plan(hvs_ctx *ctx, uint32_t *sub_offsets /* host, nuq+1, may be NULL */, uint32_t *parent,
+                         float *value /* host, cap entries each, may be NULL */, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

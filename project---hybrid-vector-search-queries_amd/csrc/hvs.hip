@@ -239,12 +239,21 @@ struct HvsInSet {
     unsigned long long* d_stat = nullptr;  // [0] under-full queries, [1] keys read: of the last merge
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;  // around the expansion / the last merge
     double expand_ms = 0.0;
+    // scratch of a plan made on the device (hvs_set_category_sets_device): nothing here is in force, in_commit takes from it
+    uint32_t *d_p_pack = nullptr, *d_p_sub_off = nullptr;  // p_cap, p_cap + 1: the count kernel's words, the scan's offsets
+    uint8_t* d_p_eff = nullptr;                            // p_cap
+    unsigned long long* d_p_stat = nullptr;                // [0] flags, [1] sub-queries, [2] sub-queries if every query tested C
+    uint32_t* d_p_off = nullptr;                           // a CSR on another GPU: this GPU's slice of the offsets, p_cap + 1 ...
+    float* d_p_vals = nullptr;                             // ... and of the values, pv_cap; both live for that call only (in_plan_release)
+    uint32_t p_cap = 0, p_off_cap = 0, pv_cap = 0;
     // last call
     bool call = false;                 // it ran under sets
     uint32_t call_set_queries = 0, call_sub = 0, call_max_set = 0;
     void free_device()
     {
         HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_m_ids, d_m_dists, d_stat);
+        HvsRowSet::drop(d_p_pack, d_p_sub_off, d_p_eff, d_p_stat, d_p_off, d_p_vals);
+        p_cap = p_off_cap = pv_cap = 0;
         user.free_device();
         for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
             if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
@@ -2965,8 +2974,8 @@ uint32_t in_plan_core(const float* types, const float* own_v, size_t stride, con
             const bool effective = has_c && off[p + 1] > off[p];
             cat.clear();
             for (uint32_t i = off[p]; i < off[p + 1]; ++i) {
-                const float s = vals[i];
-                if (s >= -2147483648.0f && s < 2147483648.0f) cat.push_back((float)(int32_t)s);  // (NaN fails both compares)
+                float named;
+                if (hvs_in_category(vals[i], &named)) cat.push_back(named);
             }
             std::sort(cat.begin(), cat.end());
             cat.erase(std::unique(cat.begin(), cat.end()), cat.end());
@@ -3013,19 +3022,148 @@ int in_detach(hvs_ctx* c)
     return HVS_OK;
 }
 
-// hvs_set_category_sets on one GPU: `off` = the caller's offsets of this GPU's `nuq` resident queries (off[0] need not be 0:
-// a slice of a multi-GPU context's CSR), `vals` the whole value array; validated by the caller (format, limits, nuq = the
-// resident queries).  The user's rows move aside (they may have come from device memory: their types are read back), the
-// plan is made, the engines' set becomes the expanded one.  A failure half-way (no room) leaves the context without sets, and
-// without resident queries if the query buffer itself could not grow.  On a replicated context the root then detaches every
-// other GPU too (hvs_set_category_sets): sets are attached on all GPUs or on none.
-int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
+// Attaching sets to one GPU's `nuq` user queries has two halves: a PLAN is made -- on the host from a host CSR (in_plan_host),
+// or by the plan kernels from a CSR in device memory (in_plan_device) --, which changes nothing a query or a later call reads,
+// and in_commit puts it in force.  sub_off and eff are on the host either way: hvs_query_resident maps query ranges to
+// sub-query ranges there.
+static_assert(HVS_INP_MAX_VALUES == HVS_IN_MAX_VALUES && HVS_IN_MAX_VALUES <= 64, "the plan kernels keep one category per lane of a wave");
+struct InPlan {
+    uint32_t nuq = 0, nsub = 0;
+    std::vector<uint32_t> sub_off;  // nuq + 1: becomes HvsInSet::h_sub_off
+    std::vector<uint8_t> eff;       // nuq: becomes HvsInSet::h_eff
+    // made on the host: the arrays the commit uploads
+    std::vector<uint32_t> set_off, parent;
+    std::vector<float> value;
+    // made on the device: sub_off is in HvsInSet::d_p_sub_off, eff in d_p_eff, and the fill kernel reads the CSR again
+    bool on_device = false;
+    const uint32_t* d_off = nullptr;  // this GPU's slice of the offsets, nuq + 1, in this GPU's memory
+    const float* d_vals = nullptr;    // the values the slice points into: entry i is d_vals[i - v0]
+    uint32_t v0 = 0, lo = 0;          // lo: the slice's first offset
+    uint64_t sub_if_all_c = 0;        // the sub-queries there would be if every query tested C (what the limit is taken over)
+    double plan_ms = 0.0;             // device time of the count and scan kernels
+};
+
+// what both halves need first: an earlier call's re-runs resolved and the stream idle, the events, the merge's counters
+int in_begin(hvs_ctx* c)
 {
-    HvsInSet& S = c->qs.in;
     int rc = begin_mutation(c);
     if (!rc) rc = in_ensure_events(c);
-    if (rc) return rc;
-    if (!S.d_stat && (rc = dev_alloc(c, &S.d_stat, (size_t)2))) return rc;
+    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)2);
+    return rc;
+}
+
+// The plan of a host CSR: `off` = the caller's offsets of this GPU's `nuq` resident queries (off[0] need not be 0: a slice of a
+// multi-GPU context's CSR), `vals` the whole value array; validated by the caller (format, limits, nuq = the resident queries).
+// The user's rows may have come from device memory: their types are read back.
+int in_plan_host(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq, InPlan* P)
+{
+    std::vector<float> tv(2u * (size_t)nuq);  // [type, v] of every user query
+    if (nuq)
+        HVS_HIP(c, hipMemcpy2D(tv.data(), 2u * sizeof(float), user_queries(c), HVS_QCOLS * sizeof(float), 2u * sizeof(float), nuq, hipMemcpyDeviceToHost));
+    P->nuq = nuq;
+    P->set_off.resize((size_t)nuq + 1u);
+    for (uint32_t p = 0; p <= nuq; ++p) P->set_off[p] = off[p] - off[0];
+    const float* v0 = vals ? vals + off[0] : nullptr;
+    P->sub_off.resize((size_t)nuq + 1u);
+    P->eff.resize(nuq);
+    P->nsub = in_plan_core(tv.data(), tv.data() + 1, 2u, P->set_off.data(), v0, nuq, P->sub_off.data(), nullptr, nullptr, P->eff.data());
+    if (P->nsub == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed sets");
+    P->parent.resize(P->nsub);
+    P->value.resize(P->nsub);
+    (void)in_plan_core(tv.data(), tv.data() + 1, 2u, P->set_off.data(), v0, nuq, nullptr, P->parent.data(), P->value.data(), nullptr);
+    return HVS_OK;
+}
+
+// The plan of a CSR in device memory of GPU `src_dev` (checked and waited for by the caller): `d_off` = the offsets of this
+// GPU's `nuq` resident queries, whose first and last, lo <= hi, the caller has read; `d_vals` the whole value array (nullptr:
+// none, hi == 0).  On this GPU's own memory the kernels read both in place; from another GPU the slice of the offsets and the
+// values [lo, hi) are copied here first.  What comes back to the host: the status block, sub_off and eff.  HVS_EINVAL for what
+// the host plan refuses in this slice; the sum over "every query tests C" is the caller's to judge (it is context-wide).
+int in_plan_device(hvs_ctx* c, const uint32_t* d_off, const float* d_vals, int src_dev, uint32_t lo, uint32_t hi, uint32_t nuq, InPlan* P)
+{
+    HvsInSet& S = c->qs.in;
+    int rc;
+    if (!S.d_p_stat || nuq > S.p_cap) {
+        S.p_cap = 0;
+        if ((rc = dev_alloc(c, &S.d_p_pack, (size_t)nuq)) || (rc = dev_alloc(c, &S.d_p_sub_off, (size_t)nuq + 1u)) ||
+            (rc = dev_alloc(c, &S.d_p_eff, (size_t)nuq)) || (rc = dev_alloc(c, &S.d_p_stat, (size_t)3)))
+            return rc;
+        S.p_cap = nuq;
+    }
+    P->on_device = true;
+    P->nuq = nuq;
+    P->lo = lo;
+    if (src_dev == c->device) {
+        P->d_off = d_off;
+        P->d_vals = d_vals;
+        P->v0 = 0u;
+    } else {
+        if (!S.d_p_off || nuq > S.p_off_cap) {
+            S.p_off_cap = 0;
+            if ((rc = dev_alloc(c, &S.d_p_off, (size_t)nuq + 1u))) return rc;
+            S.p_off_cap = nuq;
+        }
+        if (hi - lo > S.pv_cap) {
+            S.pv_cap = 0;
+            if ((rc = dev_alloc(c, &S.d_p_vals, (size_t)(hi - lo)))) return rc;
+            S.pv_cap = hi - lo;
+        }
+        if ((rc = copy_from_device(c, S.d_p_off, d_off, src_dev, ((size_t)nuq + 1u) * sizeof(uint32_t))) ||
+            (rc = copy_from_device(c, S.d_p_vals, d_vals ? d_vals + lo : nullptr, src_dev, d_vals ? (size_t)(hi - lo) * sizeof(float) : 0u)))
+            return rc;
+        P->d_off = S.d_p_off;
+        P->d_vals = d_vals && hi > lo ? S.d_p_vals : nullptr;
+        P->v0 = lo;
+    }
+    HVS_HIP(c, hipMemsetAsync(S.d_p_stat, 0, 3u * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
+    if (nuq)
+        hipLaunchKernelGGL(hvs_k_in_count, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, user_queries(c), P->d_off, P->d_vals, P->v0, lo, hi, nuq,
+                           S.d_p_pack, S.d_p_stat);
+    hipLaunchKernelGGL(hvs_k_in_scan, dim3(1), dim3(1024), 0, c->stream, S.d_p_pack, nuq, S.d_p_sub_off, S.d_p_eff, S.d_p_stat);
+    HVS_HIP(c, hipGetLastError());
+    HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
+    unsigned long long st[3] = {0, 0, 0};
+    HVS_HIP(c, hipMemcpyAsync(st, S.d_p_stat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
+    P->plan_ms = ms;
+    if (st[0] & HVS_INP_MALFORMED) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: malformed offsets");
+    if (st[0] & HVS_INP_TOO_MANY) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: a set of more than 64 distinct categories");
+    if (st[1] >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: too many sub-queries");
+    P->nsub = (uint32_t)st[1];
+    P->sub_if_all_c = st[2];
+    P->sub_off.resize((size_t)nuq + 1u);
+    P->eff.resize(nuq);
+    HVS_HIP(c, hipMemcpyAsync(P->sub_off.data(), S.d_p_sub_off, P->sub_off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (nuq) HVS_HIP(c, hipMemcpyAsync(P->eff.data(), S.d_p_eff, P->eff.size(), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return HVS_OK;
+}
+
+// The copies in_plan_device made of a CSR on another GPU are needed from the count to the fill only: the call that made them
+// gives them back, whichever way it ends (the rest of the scratch, 9 bytes per user query, stays for the next attach).
+int in_plan_release(hvs_ctx* c)
+{
+    HvsInSet& S = c->qs.in;
+    if (!S.d_p_off && !S.d_p_vals) return HVS_OK;
+    HVS_HIP(c, hipSetDevice(c->device));
+    HvsRowSet::drop(S.d_p_off, S.d_p_vals);
+    S.p_off_cap = S.pv_cap = 0;
+    return HVS_OK;
+}
+
+// A plan is put in force on its GPU: the user's rows move aside, the plan's arrays reach the device -- uploaded, or, for a plan
+// made there, written by the fill kernel --, and the engines' set becomes the expanded one.  A failure half-way (no room)
+// leaves the context without sets, and without resident queries if the query buffer itself could not grow.  On a replicated
+// context the root then detaches every other GPU too: sets are attached on all GPUs or on none.
+int in_commit(hvs_ctx* c, InPlan& P)
+{
+    HvsInSet& S = c->qs.in;
+    const uint32_t nuq = P.nuq, nsub = P.nsub;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));  // (a multi-GPU commit runs on a thread of its own: every buffer below is this GPU's)
     // the user's rows: already aside when sets are replaced
     if (!S.active) {
         if (!S.d_sub_off || nuq > S.uq_cap) {
@@ -3039,19 +3177,6 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
         HVS_HIP(c, hipStreamSynchronize(c->stream));
         S.nuq = nuq;
     }
-    std::vector<float> tv(2u * (size_t)nuq);  // [type, v] of every user query
-    if (nuq)
-        HVS_HIP(c, hipMemcpy2D(tv.data(), 2u * sizeof(float), S.d_uq, HVS_QCOLS * sizeof(float), 2u * sizeof(float), nuq, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> set_off((size_t)nuq + 1u);
-    for (uint32_t p = 0; p <= nuq; ++p) set_off[p] = off[p] - off[0];
-    const float* v0 = vals ? vals + off[0] : nullptr;
-    std::vector<uint32_t> sub_off((size_t)nuq + 1u);
-    std::vector<uint8_t> eff(nuq);
-    const uint32_t nsub = in_plan_core(tv.data(), tv.data() + 1, 2u, set_off.data(), v0, nuq, sub_off.data(), nullptr, nullptr, eff.data());
-    if (nsub == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed sets");
-    std::vector<uint32_t> parent(nsub);
-    std::vector<float> value(nsub);
-    (void)in_plan_core(tv.data(), tv.data() + 1, 2u, set_off.data(), v0, nuq, nullptr, parent.data(), value.data(), nullptr);
     // from here on the context changes
     auto lost = [&](int code) {
         sets_changed(c, false);
@@ -3067,12 +3192,18 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
     }
     if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
-    if (up(S.d_sub_off, sub_off.data(), sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
-        up(S.d_set_off, set_off.data(), set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-        up(S.d_parent, parent.data(), parent.size() * sizeof(uint32_t)) != hipSuccess ||
-        up(S.d_value, value.data(), value.size() * sizeof(float)) != hipSuccess)
+    if (P.on_device) {
+        if (hipMemcpyAsync(S.d_sub_off, S.d_p_sub_off, ((size_t)nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+            return lost(fail(c, HVS_EHIP, "hvs_set_category_sets_device: the copy of the plan failed"));
+    } else if (up(S.d_sub_off, P.sub_off.data(), P.sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
+               up(S.d_set_off, P.set_off.data(), P.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+               up(S.d_parent, P.parent.data(), P.parent.size() * sizeof(uint32_t)) != hipSuccess ||
+               up(S.d_value, P.value.data(), P.value.size() * sizeof(float)) != hipSuccess)
         return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
     (void)hipEventRecord(S.ev_x0, c->stream);
+    if (P.on_device && nuq)  // (parent, value and the rebased offsets; part of expand_ms, as plan_ms is)
+        hipLaunchKernelGGL(hvs_k_in_fill, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, S.d_uq, P.d_off, P.d_vals, P.v0, P.lo, nuq, S.d_sub_off,
+                           S.d_p_eff, S.d_set_off, S.d_parent, S.d_value);
     if (nsub) {
         const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
         hipLaunchKernelGGL(hvs_k_expand_in, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq),
@@ -3083,12 +3214,21 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
         return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: the expansion failed"));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
-    S.expand_ms = ms;
-    S.h_sub_off.swap(sub_off);
-    S.h_eff.swap(eff);
+    S.expand_ms = (double)ms + P.plan_ms;
+    S.h_sub_off.swap(P.sub_off);
+    S.h_eff.swap(P.eff);
     c->nq = nsub;
     sets_changed(c, true);
     return HVS_OK;
+}
+
+// hvs_set_category_sets on one GPU
+int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
+{
+    InPlan P;
+    int rc = in_begin(c);
+    if (!rc) rc = in_plan_host(c, off, vals, nuq, &P);
+    return rc ? rc : in_commit(c, P);
 }
 
 // hvs_query_resident under category sets: user queries [q0, q0 + nq) = sub-queries [sub_off[q0], sub_off[q0 + nq)), answered by
@@ -5145,7 +5285,7 @@ int hvs_set_category_sets(hvs_ctx* c, const uint32_t* set_offsets, const float* 
     const int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return in_attach(k, set_offsets + first, set_values, m); });
     if (rc && !c->kids.empty()) {
         // one GPU could not attach (no room): no GPU stays under sets -- the context answers plain queries on every GPU whose
-        // query buffer survived (in_attach), and the failing GPU's error is the call's
+        // query buffer survived (in_commit), and the failing GPU's error is the call's
         const std::string err = c->err;
         for (hvs_ctx* k : c->kids) (void)in_detach(k);
         (void)hipGetLastError();
@@ -5185,6 +5325,80 @@ int hvs_in_stats(hvs_ctx* c, hvs_in_info* out)
         sum.expand_ms = std::max(sum.expand_ms, m.expand_ms);
         sum.merge_ms = std::max(sum.merge_ms, m.merge_ms);
     });
+}
+
+int hvs_set_category_sets_device(hvs_ctx* c, const uint32_t* d_set_offsets, const float* d_set_values, uint32_t nq, void* stream)
+{
+    static const char* const fn = "hvs_set_category_sets_device";
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets_device: not supported (yet) on a row-partitioned context");
+    if (!d_set_offsets && !d_set_values) return on_every_leaf(c, in_detach);
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: d_set_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    if (nq == 0u) return on_every_leaf(c, in_detach);
+    int dev = 0;
+    if (int rc = check_device_buffers(c, d_set_offsets, d_set_values, stream, fn, &dev)) return rc;
+    // the slice boundaries: offsets[first query of every GPU] and offsets[nq] come to the host (4 bytes each)
+    const size_t N = std::max<size_t>(c->kids.size(), 1u);
+    std::vector<uint32_t> q0(N + 1u, 0u), bound(N + 1u, 0u);
+    for (size_t r = 0; r <= N; ++r) {
+        q0[r] = c->kids.empty() ? (r ? nq : 0u) : c->kid_q0[r];
+        HVS_HIP(c, hipMemcpy(&bound[r], d_set_offsets + q0[r], sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the current device is the buffers')
+    }
+    bool good = bound[0] == 0u && (bound[N] == 0u || d_set_values);
+    for (size_t r = 0; r < N; ++r) good = good && bound[r] <= bound[r + 1u];
+    if (!good) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: malformed offsets, or values missing");
+    // every GPU plans its slice; nothing is in force yet, so a refusal leaves every GPU as it was
+    std::vector<InPlan> plans(N);
+    auto slot = [&](const hvs_ctx* k) { return c->kids.empty() ? (size_t)0 : (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin()); };
+    struct ReleaseCopies {  // (a GPU that does not hold the buffers copied its slice: given back however the call ends)
+        hvs_ctx* c;
+        ~ReleaseCopies()
+        {
+            if (c->kids.empty()) (void)in_plan_release(c);
+            for (hvs_ctx* k : c->kids) (void)in_plan_release(k);
+        }
+    } release{c};
+    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) {
+        const size_t r = slot(k);
+        const int rc2 = in_begin(k);
+        return rc2 ? rc2 : in_plan_device(k, d_set_offsets + first, d_set_values, dev, bound[r], bound[r + 1u], m, &plans[r]);
+    });
+    if (rc) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    // the limit is the host call's: the sub-queries there would be if every query tested C, over the whole context
+    uint64_t all_c = 0;
+    for (const InPlan& P : plans) all_c += P.sub_if_all_c;
+    if (all_c >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: too many sub-queries");
+    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t, uint32_t) { return in_commit(k, plans[slot(k)]); });
+    if (rc && !c->kids.empty()) {
+        // as in hvs_set_category_sets: no GPU stays under sets, and the failing GPU's error is the call's
+        const std::string err = c->err;
+        for (hvs_ctx* k : c->kids) (void)in_detach(k);
+        (void)hipGetLastError();
+        c->err = err;
+    }
+    return rc;
+}
+
+int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, float* value, uint32_t cap)
+{
+    if (!c) return HVS_EINVAL;
+    if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_in_plan: single-GPU contexts only");
+    const HvsInSet& S = c->qs.in;
+    if (!S.active) return fail(c, HVS_ESTATE, "hvs_download_in_plan: no category sets are attached");
+    const uint32_t nsub = c->nq;
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (sub_offsets) HVS_HIP(c, hipMemcpyAsync(sub_offsets, S.d_sub_off, ((size_t)S.nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (cap >= nsub && nsub) {
+        if (parent) HVS_HIP(c, hipMemcpyAsync(parent, S.d_parent, (size_t)nsub * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (value) HVS_HIP(c, hipMemcpyAsync(value, S.d_value, (size_t)nsub * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return (int)nsub;
 }
 
 // ---- live-row mask ---------------------------------------------------------------------------

@@ -791,6 +791,15 @@ __host__ __device__ __forceinline__ bool hvs_in_type_has_c(float t)
     const uint32_t type = (uint32_t)(int32_t)t;
     return type == 1u || type == 3u;
 }
+// the engines' reading of a set value (reference optimized_parallel.hpp:93-96): the category its int32 truncation names, as the
+// float C is compared with; false for a value that names none (NaN fails both compares, +-inf and |s| >= 2^31 one of them).  The
+// result is never -0.0: equal categories have equal bits.  The host plan (hvs_in_plan) and the device plan call this one function.
+__host__ __device__ __forceinline__ bool hvs_in_category(float s, float* cat)
+{
+    if (!(s >= -2147483648.0f && s < 2147483648.0f)) return false;
+    *cat = (float)(int32_t)s;
+    return true;
+}
 
 // Sub-query j = the 104 floats of user query parent[j], bit for bit, with float 1 (v) replaced by value[j] -- only where the
 // parent tests C (type 1 or 3) and carries a non-empty set (set_off[p + 1] > set_off[p], the caller's CSR offsets); every
@@ -890,5 +899,179 @@ __global__ __launch_bounds__(256) void hvs_k_merge_in(const uint32_t* __restrict
         }
         out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
         if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan made on the device (hvs_set_category_sets_device): what hvs_in_plan(q_rows, ...) computes, bit for bit,
+// from a CSR that lies in device memory -- the set values never reach the host.  One GPU plans its `nuq` user queries from its
+// slice of the offsets, off[0 .. nuq], which index the values as vals[i - v0] (v0 = 0: the caller's own array read in place;
+// v0 = lo: a copy of the slice's values [lo, hi)).  Three kernels: hvs_k_in_count (one wave per query: sub-query counts and
+// flags), hvs_k_in_scan (sub_off and the two 64-bit totals), and, once the host has accepted the plan, hvs_k_in_fill (one wave
+// per query: parent, value and the rebased offsets hvs_k_expand_in reads).  Count and fill both build a query's distinct list:
+// nothing of size nq x 64 is kept between them.
+// ---------------------------------------------------------------------------------------------
+#define HVS_INP_MALFORMED 1ull  // stat[0]: an offset pair that descends or leaves [lo, hi], or values missing
+#define HVS_INP_TOO_MANY 2ull   // stat[0]: a set of more than HVS_IN_MAX_VALUES distinct categories
+#define HVS_INP_MAX_VALUES 64u  // = HVS_IN_MAX_VALUES of the C ABI (asserted where both are seen): one lane of a wave per category
+
+// The distinct categories of the raw values [a, b) in the order they first appear, one wave: lane j ends up holding the j-th
+// in `mine` (j < the count returned; at most 64, so the list lives in the wave's registers).  The values are walked 64 at a
+// time, whatever b - a is: a lane's value is dropped if it names no category or one the list has, and the rest enter the list
+// leader by leader -- the lowest fresh lane appends its category and retires every lane that holds the same one.  Returns
+// HVS_INP_MAX_VALUES + 1 as soon as a 65th category appears.  a, b and the result are wave-uniform.
+__device__ __forceinline__ uint32_t hvs_in_distinct(const float* __restrict__ vals, uint32_t v0, uint32_t a, uint32_t b, uint32_t lane, float& mine)
+{
+    uint32_t n = 0;
+    mine = 0.0f;
+    for (uint64_t base = a; base < b; base += 64u) {  // (64 bits: b may lie within 64 of 2^32)
+        const uint64_t i = base + lane;
+        float cat = 0.0f;
+        bool fresh = i < b && hvs_in_category(vals[(size_t)(i - v0)], &cat);
+        for (uint32_t j = 0; j < n; ++j) {
+            const float have = __shfl(mine, (int)j);
+            if (have == cat) fresh = false;
+        }
+        uint64_t m = __ballot(fresh);
+        while (m) {
+            if (n == HVS_INP_MAX_VALUES) return HVS_INP_MAX_VALUES + 1u;
+            const float lead = __shfl(cat, __ffsll((long long)m) - 1);
+            if (lane == n) mine = lead;
+            ++n;
+            if (cat == lead) fresh = false;
+            m = __ballot(fresh);
+        }
+    }
+    return n;
+}
+
+// Count.  Query p (one wave, four per workgroup) reads its type from the user's rows Qu and its raw range [off[p], off[p + 1]);
+// the range must ascend and stay inside the slice's [lo, hi] -- an ascending CSR does, and one that does not is refused before a
+// value outside the caller's array could be read.  pack[p] = m | mc << 8 | eff << 16: m sub-queries (effective ?
+// max(distinct, 1) : 1), mc the same under "every query tests C" (what the host call's limit is taken over), eff as
+// hvs_in_plan has it.  The size limit is the set's own, whatever the query's type.  Flags are OR-ed into stat[0].
+__global__ __launch_bounds__(256) void hvs_k_in_count(const float* __restrict__ Qu, const uint32_t* __restrict__ off, const float* __restrict__ vals,
+                                                      uint32_t v0, uint32_t lo, uint32_t hi, uint32_t nuq, uint32_t* __restrict__ pack,
+                                                      unsigned long long* __restrict__ stat)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (p >= nuq) return;  // wave-uniform
+    const uint32_t a = off[p], b = off[p + 1u];
+    unsigned long long flags = 0ull;
+    uint32_t n = 0;
+    if (!(lo <= a && a <= b && b <= hi) || (b > a && !vals)) {
+        flags = HVS_INP_MALFORMED;
+    } else {
+        float mine;
+        n = hvs_in_distinct(vals, v0, a, b, lane, mine);
+        if (n > HVS_INP_MAX_VALUES) flags = HVS_INP_TOO_MANY;
+    }
+    if (lane == 0u) {
+        const bool nonempty = !flags && b > a;
+        const bool eff = nonempty && hvs_in_type_has_c(Qu[(size_t)p * HVS_QCOLS]);
+        const uint32_t mc = nonempty && n > 1u ? n : 1u;
+        pack[p] = (eff ? mc : 1u) | mc << 8 | (eff ? 1u : 0u) << 16;
+        if (flags) atomicOr(&stat[0], flags);
+    }
+}
+
+// Scan.  sub_off[0 .. nuq] = the exclusive prefix of the counts, eff[p] unpacked, stat[1] = the sub-queries, stat[2] = their
+// number if every query tested C -- both sums in 64 bits (sub_off holds the low words; the host refuses what does not fit).  One
+// workgroup of 1024 walks the queries in tiles of 4096, carrying the running sums, as hvs_k_item_scan is one workgroup: nothing
+// waits for another workgroup, and the work is a few bytes per query.
+__global__ __launch_bounds__(1024) void hvs_k_in_scan(const uint32_t* __restrict__ pack, uint32_t nuq, uint32_t* __restrict__ sub_off,
+                                                      uint8_t* __restrict__ eff, unsigned long long* __restrict__ stat)
+{
+    __shared__ uint32_t swave[16], swave_c[16];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    unsigned long long run = 0ull, run_c = 0ull;
+    for (uint64_t base = 0; base < nuq; base += 4096u) {
+        const uint64_t i0 = base + threadIdx.x * 4u;
+        uint32_t m[4], sum = 0, sum_c = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t pk = i0 + j < nuq ? pack[i0 + j] : 0u;
+            m[j] = pk & 0xFFu;
+            sum += m[j];
+            sum_c += (pk >> 8) & 0xFFu;
+            if (i0 + j < nuq) eff[i0 + j] = (uint8_t)((pk >> 16) & 1u);
+        }
+        uint32_t inc = sum;  // inclusive scan over the wave
+        for (uint32_t o = 1; o < 64u; o <<= 1) {
+            const uint32_t t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        for (uint32_t o = 32; o; o >>= 1) sum_c += __shfl_xor(sum_c, (int)o);
+        if (lane == 63u) {
+            swave[w] = inc;
+            swave_c[w] = sum_c;
+        }
+        __syncthreads();
+        uint32_t before = 0, tile = 0, tile_c = 0;  // (a tile holds at most 4096 x 64 sub-queries)
+        for (uint32_t x = 0; x < 16u; ++x) {
+            before += x < w ? swave[x] : 0u;
+            tile += swave[x];
+            tile_c += swave_c[x];
+        }
+        __syncthreads();  // (the next tile overwrites the waves' sums)
+        unsigned long long at = run + before + (inc - sum);
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j)
+            if (i0 + j < nuq) {
+                sub_off[i0 + j] = (uint32_t)at;
+                at += m[j];
+            }
+        run += tile;
+        run_c += tile_c;
+    }
+    if (threadIdx.x == 0u) {
+        sub_off[nuq] = (uint32_t)run;
+        stat[1] = run;
+        stat[2] = run_c;
+    }
+}
+
+// Fill.  Query p (one wave) writes its sub-queries [sub_off[p], sub_off[p + 1]): parent = p, and value = its own v where its
+// set is not effective, else its distinct categories ascending -- rebuilt here and rank-sorted (they are distinct: the ranks
+// are the places) --, or the canonical NaN where no value names a category.  set_off[0 .. nuq] = the offsets as seen from lo
+// (what hvs_k_expand_in reads).  Runs on a plan the host has accepted: the ranges are good and no set is too large.
+__global__ __launch_bounds__(256) void hvs_k_in_fill(const float* __restrict__ Qu, const uint32_t* __restrict__ off, const float* __restrict__ vals,
+                                                     uint32_t v0, uint32_t lo, uint32_t nuq, const uint32_t* __restrict__ sub_off,
+                                                     const uint8_t* __restrict__ eff, uint32_t* __restrict__ set_off, uint32_t* __restrict__ parent,
+                                                     float* __restrict__ value)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (p >= nuq) return;  // wave-uniform
+    const uint32_t a = off[p], b = off[p + 1u];
+    const size_t s0 = sub_off[p];
+    const uint32_t m = sub_off[p + 1u] - sub_off[p];
+    if (lane == 0u) {
+        set_off[p] = a - lo;
+        if (p == nuq - 1u) set_off[nuq] = b - lo;
+    }
+    if (!eff[p]) {
+        if (lane == 0u && m == 1u) {
+            parent[s0] = p;
+            value[s0] = Qu[(size_t)p * HVS_QCOLS + 1u];
+        }
+        return;
+    }
+    float mine;
+    const uint32_t n = hvs_in_distinct(vals, v0, a, b, lane, mine);
+    if (n == 0u) {
+        if (lane == 0u && m == 1u) {
+            parent[s0] = p;
+            value[s0] = __uint_as_float(0x7FC00000u);
+        }
+        return;
+    }
+    if (n != m) return;  // (cannot happen: the count ran the same code on the same bytes; nothing outside the query's range is written)
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < n; ++j) rank += __shfl(mine, (int)j) < mine ? 1u : 0u;
+    if (lane < n) {
+        parent[s0 + lane] = p;
+        value[s0 + rank] = mine;
     }
 }

@@ -271,6 +271,8 @@ def library():
         "hvs_query_in": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
         "hvs_in_stats": (C.c_int, [vp, C.POINTER(InInfo)]),
         "hvs_in_plan": (C.c_uint32, [_f32p, _u32p, _f32p, C.c_uint32, _u32p, _u32p, _f32p]),
+        "hvs_set_category_sets_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "hvs_download_in_plan": (C.c_int, [vp, _u32p, _u32p, _f32p, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -808,16 +810,47 @@ class Engine:
             self.set_padding(was)
 
     # --- category sets (include/hvs.h "category sets")
-    def set_category_sets(self, sets):
+    def set_category_sets(self, sets, stream=None):
         """Attach one category set per resident query -- a list of per-query sequences of category values (an empty one leaves
         the query as it is), or an (offsets, values) CSR pair -- or None to remove the sets.  A query of type 1 or 3 with a
-        non-empty set then matches the rows whose C is any of its values.  Caps and cursors are attached afterwards."""
+        non-empty set then matches the rows whose C is any of its values.  Caps and cursors are attached afterwards.
+        A pair of GPU tensors -- offsets int32 / uint32 with nq + 1 entries, values float32 or None, both contiguous -- goes
+        to hvs_set_category_sets_device: the plan is made on the GPU and the values never reach the host (`stream` as for
+        set_queries_device)."""
         if sets is None:
             self._ck(self._lib.hvs_set_category_sets(self._h, None, None, 0))
+            return
+        if isinstance(sets, tuple) and len(sets) == 2 and any(hasattr(x, "data_ptr") and hasattr(x, "shape") for x in sets):
+            self.set_category_sets_device(sets[0], sets[1], stream=stream)
             return
         off, vals = _sets_csr(sets)
         self._ck(self._lib.hvs_set_category_sets(self._h, _up(off) if off.size else None, _fp(vals) if vals.size else None,
                                                  max(off.size, 1) - 1))
+
+    def set_category_sets_device(self, offsets, values, nq=None, stream=None):
+        """hvs_set_category_sets_device: the CSR from device memory -- two GPU tensors (see set_category_sets), or two raw
+        pointers (0 / None = NULL) with `nq`."""
+        if hasattr(offsets, "data_ptr") or hasattr(values, "data_ptr"):
+            po, n = _device_u32(offsets, "set_category_sets")
+            pv = 0 if values is None else _device_rows(values, None, 1, "set_category_sets")[0]
+            nq = max(n, 1) - 1 if nq is None else int(nq)
+        else:
+            if nq is None:
+                raise HvsError(-1, "set_category_sets: raw pointers need the number of queries")
+            po, pv, nq = int(offsets or 0), int(values or 0), int(nq)
+        self._ck(self._lib.hvs_set_category_sets_device(self._h, C.c_void_p(po) if po else None, C.c_void_p(pv) if pv else None, nq,
+                                                        _stream_ptr(stream)))
+
+    def in_plan_device(self):
+        """hvs_download_in_plan: (nsub, sub_offsets, parent, value) of the plan as it lies on the device, whichever way the
+        sets were attached (one-GPU contexts)."""
+        nsub = self._lib.hvs_download_in_plan(self._h, None, None, None, 0)
+        self._ck(min(nsub, 0))
+        # every user query has a sub-query, so nsub + 1 entries hold sub_offsets whatever nq is; the last parent names the last query
+        sub, parent, value = np.zeros(nsub + 1, np.uint32), np.empty(nsub, np.uint32), np.empty(nsub, np.float32)
+        self._ck(min(self._lib.hvs_download_in_plan(self._h, _up(sub), _up(parent), _fp(value), nsub), 0))
+        nq = int(parent[-1]) + 1 if nsub else 0
+        return int(nsub), sub[:nq + 1].copy(), parent, value
 
     def query_in(self, q_rows, sets, sample_proportion=1.0, want_dists=True):
         """hvs_query_in: host rows and their category sets in, host ids (and distances) out; sets = None is query()."""
