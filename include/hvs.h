@@ -709,6 +709,86 @@ int hvs_set_category_sets_device(hvs_ctx *ctx, const uint32_t *d_set_offsets /* 
 int hvs_download_in_plan(hvs_ctx *ctx, uint32_t *sub_offsets /* host, nuq+1, may be NULL */, uint32_t *parent,
                          float *value /* host, cap entries each, may be NULL */, uint32_t cap);
 
+/* ---- per-query exclusion lists: the k nearest rows not in an id list -------------------------------- */
+/*
+ * An exclusion list is a set of row ids attached to ONE resident query: "not these rows" -- items already owned, everything shown
+ * so far, the row the query was made from (hvs_set_queries_from_rows does not remove self-matches: a list of one id does).  The
+ * lists of all resident queries are given at once in CSR form: excl_offsets[nq + 1] (u32, ascending, [0] == 0) and
+ * excl_ids[excl_offsets[nq]] (u32).
+ *
+ * A row takes part in query q's answer only if it passes q's predicate (or its category set), lies in the sampled prefix, is
+ * live, is within the cap if caps are set, is after the cursor if cursors are set, AND ITS ID IS NOT IN q's LIST.  Everything
+ * else is as if the listed rows did not match: the slots they leave are filled by the usual padding rule (rows n-1, n-2, ... or
+ * the last live ids; with hvs_set_padding(ctx, 0) they are empty, 0xFFFFFFFF / +inf).  Pad rows need not be outside the list,
+ * as they need not pass the predicate or lie within a cap: a query whose list names a pad row may still be padded with it.
+ * Ids, distance bits, the (dist asc, id asc) tie rule and hvs_timing.pairs do not change: `pairs` keeps counting
+ * predicate-passing rows and does not look at lists.
+ *
+ * The law: with full(q) the matched keys of q in key order, the answer with padding off is the first k keys of full(q) whose id
+ * is not listed, taken after cap and cursor, then empty slots.  Excluding the ids of pages 1..P of a query therefore gives
+ * exactly page P+1 of a cursor walk -- ties and duplicate rows included, because the id decides.
+ *
+ * Ids.  An id is a row id of D as it is WHEN THE QUERY RUNS: a list is not a row reference.  An id that names no row -- >= n,
+ * behind the sampled prefix, a dead row -- excludes nothing (an id >= n of today excludes the row an append gives that id).
+ * 0xFFFFFFFF is ignored, so a result row with empty slots can be fed back as it is.  Duplicates and any order are fine.  No id
+ * is validated and none can make the call fail: ids are only ever compared with row ids.
+ *
+ * Limits.  At most HVS_EXCLUDE_MAX raw entries per query (the offsets alone decide).  A longer list, offsets[0] != 0, a
+ * descending pair of offsets, or nq != the number of resident queries: HVS_EINVAL, and nothing changes -- lists already attached,
+ * results, caps and cursors stay in force.  No data loaded: HVS_ESTATE.
+ *
+ * Lifetime.  Lists belong to the resident query set exactly as caps and cursors do: every call that replaces the set removes
+ * them (hvs_upload_queries, hvs_gen_queries, hvs_set_queries_device, hvs_set_queries_from_rows, hvs_query*), and so does
+ * attaching or removing category sets.  Under category sets they stay one per USER query; each sub-query reads its parent's.
+ * Both pointers NULL removes them.  Earlier results stay in place.  "No lists" is expressed by not setting them: while none are
+ * set every call runs exactly the kernels it runs without this feature, with the same arguments.
+ *
+ * Lists compose with every engine, both distance orders, every k, caps, cursors (hvs_set_after_from_results included), the mask,
+ * appended and updated rows, and category sets.  All three context kinds: a replicated context cuts the CSR by the owner
+ * ranges; a row-partitioned one puts all lists on every part, each part keeping the ids of its row range as local ids (the last
+ * part's range is open-ended).  The D-sharded recipe (sharding.py) knows nothing of lists.
+ *
+ * hvs_set_exclude_ids: from HOST memory.  hvs_set_exclude_ids_device: from DEVICE memory by the rules of hvs_set_after_device --
+ * plain device memory of any visible GPU, both buffers on the same one; host memory of any kind is HVS_EINVAL with the runtime's
+ * error cleared; the call blocks until the lists are attached.  It is accepted exactly when the host call accepts the same
+ * bytes: a kernel checks the offsets and the host reads a status block back; offsets[nq] is trusted as the id array's length only
+ * once every pair has been found ascending, and nothing past it is read.  Both entry points put the raw CSR on the device and
+ * normalise it there (per list: drop 0xFFFFFFFF and, on a part, ids outside its rows; sort; drop duplicates), in place: the
+ * list of query q starts at offsets[q].
+ * hvs_query_excluding: hvs_query_after plus lists (host memory), sent whole before the pipeline starts; both list pointers NULL
+ * is exactly hvs_query_after.
+ * hvs_exclude_stats: figures of the last call.  excluding_queries: the call's queries while lists are set; kept_slots and
+ * underfull_queries: from the final kernels, with the row-partitioned and sub-query rules of hvs_within_stats; refused_keys:
+ * keys that reached an admission point and were dropped because they were listed -- a diagnostic whose exact value depends on
+ * the thresholds of the run.  All zero for a call without lists.
+ * hvs_download_exclude_plan: a diagnostic, single-GPU contexts only (HVS_EINVAL otherwise; HVS_ESTATE while no lists are
+ * attached) -- the normalised lists as they lie on the device.  begin / count (nq entries each) are written when not NULL, ids
+ * only when cap >= the id array's length, which is returned; entries of a list's raw extent behind its count are 0xFFFFFFFF.
+ * hvs_exclude_plan: the arithmetic of the normalisation on the host, no GPU and no context: for rows [row0, row0 + n_rows) (a
+ * single or replicated context: 0, 0xFFFFFFFF) writes begin[q] = offsets[q], count[q] and the normalised ids at
+ * out_ids[begin[q] ..], the rest of the raw extent 0xFFFFFFFF; any output may be NULL, and with ids NULL only the offsets are
+ * checked.  Returns the number of ids kept, or 0xFFFFFFFF for malformed offsets or an over-long list.  The device reproduces
+ * it bit for bit.
+ */
+#define HVS_EXCLUDE_MAX 1024
+typedef struct hvs_exclude_info {
+    uint32_t excluding_queries;
+    uint32_t underfull_queries;
+    uint64_t kept_slots;
+    uint64_t refused_keys;
+} hvs_exclude_info;
+int hvs_set_exclude_ids(hvs_ctx *ctx, const uint32_t *excl_offsets /* host, nq+1 */, const uint32_t *excl_ids /* host */, uint32_t nq);
+int hvs_set_exclude_ids_device(hvs_ctx *ctx, const uint32_t *d_offsets /* device, nq+1 */, const uint32_t *d_ids /* device */, uint32_t nq,
+                               void *stream);
+int hvs_query_excluding(hvs_ctx *ctx, const float *q_rows, const uint32_t *excl_offsets, const uint32_t *excl_ids, const float *after_dists,
+                        const uint32_t *after_ids, const float *max_d2 /* the last three may be NULL */, uint32_t nq, float sample_proportion,
+                        uint32_t *out_ids, float *out_dists);
+int hvs_exclude_stats(hvs_ctx *ctx, hvs_exclude_info *out);
+int hvs_download_exclude_plan(hvs_ctx *ctx, uint32_t *begin, uint32_t *count /* host, nq each, may be NULL */, uint32_t *ids /* host, cap */,
+                              uint32_t cap);
+uint32_t hvs_exclude_plan(const uint32_t *offsets, const uint32_t *ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t *begin,
+                          uint32_t *count, uint32_t *out_ids);
+
 #ifdef __cplusplus
 }
 #endif

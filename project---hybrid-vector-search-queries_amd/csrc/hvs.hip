@@ -210,10 +210,13 @@ struct HvsPerQuery {
     float* d_after_dist = nullptr;
     uint32_t* d_after_id = nullptr;
     uint32_t caps_cap = 0, after_cap = 0;  // entries d_max_d2 / each of the three cursor arrays has room for
+    // exclusion lists: where query q's normalised list lies in HvsQuerySet::d_ex_ids, and its length
+    uint32_t *d_ex_begin = nullptr, *d_ex_count = nullptr;
+    uint32_t excl_cap = 0;  // entries each of the two has room for
     void free_device()
     {
-        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id);
-        caps_cap = after_cap = 0;
+        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id, d_ex_begin, d_ex_count);
+        caps_cap = after_cap = excl_cap = 0;
     }
 };
 
@@ -276,14 +279,29 @@ struct HvsQuerySet {
     HvsPerQuery eng;           // what the launches read: one entry per resident query (under sets: per sub-query)
     bool caps_set = false, after_set = false;
     bool call_capped = false, call_after = false;  // the last call ran with caps / with cursors (hvs_within_stats, hvs_after_stats)
+    // Exclusion lists.  d_ex_ids holds every query's normalised list (under category sets too: sub-queries read
+    // their parent's through eng.d_ex_begin / d_ex_count); d_ex_off / d_ex_status are where a caller's offsets are checked before
+    // anything is replaced.  While excl_set is false no launch reads any of it.  While excl_set and not after_set,
+    // eng.d_after_lo holds zeros for every resident query (zero_after_lo): the list forms are cursor forms.
+    bool excl_set = false, call_excl = false;
+    uint32_t *d_ex_ids = nullptr, *d_ex_off = nullptr, *d_ex_status = nullptr;
+    uint32_t ex_ids_cap = 0, ex_off_cap = 0;  // entries
+    uint32_t ex_nq = 0, ex_total = 0;         // of the lists in force: the user's queries, entries of d_ex_ids (hvs_download_exclude_plan)
+    uint32_t st_flags = 0, st_base = 0, st_total = 0;  // of the offsets staged last (leaf_exclude_stage): HVS_EXCL_BAD_*, offsets[0], ids behind them
     uint32_t res_lo = 0, res_hi = 0, res_k = 0;
     uint32_t set_gen = 0;      // counts the resident sets this GPU has held
     uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
     HvsInSet in;               // category sets of the resident queries
-    void free_device() { eng.free_device(), in.free_device(); }
-    void drop_attached()  // caps off, cursors off, no results: they belonged to a set that is no longer the engines'
+    void free_device()
     {
-        caps_set = after_set = false;
+        eng.free_device(), in.free_device();
+        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status);
+        ex_ids_cap = ex_off_cap = 0;
+        excl_set = false;
+    }
+    void drop_attached()  // caps off, cursors off, lists off, no results: they belonged to a set that is no longer the engines'
+    {
+        caps_set = after_set = excl_set = false;
         drop_results();
     }
     // no query has a result row: the rows (under sets the merged rows too) hold ids of a row numbering that has gone
@@ -573,6 +591,9 @@ bool masked(const hvs_ctx* c) { return c->rs.n_dead != 0u || !c->rs.h_stale.empt
 bool capped(const hvs_ctx* c) { return c->qs.caps_set; }
 // ... carry result cursors: the AFTER kernels run (with_capped_after)
 bool has_after(const hvs_ctx* c) { return c->qs.after_set; }
+// ... carry exclusion lists: the EXCL forms of the AFTER kernels run (with_after)
+bool has_excl(const hvs_ctx* c) { return c->qs.excl_set; }
+HvsExcl excl_arg(const hvs_ctx* c) { return HvsExcl{c->qs.eng.d_ex_begin, c->qs.eng.d_ex_count, c->qs.d_ex_ids}; }
 // the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
 uint32_t user_nq(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.nuq : c->nq; }
 const float* user_queries(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_uq : c->d_q; }
@@ -622,12 +643,16 @@ uint32_t k_changed(hvs_ctx* c)
 // the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
 struct DetachedForProbe {
     HvsQuerySet& s;
-    const bool caps, after;
-    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set) { s.caps_set = s.after_set = false; }
+    const bool caps, after, excl;
+    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set)
+    {
+        s.caps_set = s.after_set = s.excl_set = false;
+    }
     ~DetachedForProbe()
     {
         s.caps_set = caps;
         s.after_set = after;
+        s.excl_set = excl;
     }
 };
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
@@ -996,23 +1021,23 @@ void with_capped(const hvs_ctx* c, F f)
 
 // ... and for the kernels that also have a cursor form: `f` gets (capped, after); after only while the resident
 // queries carry cursors
-template <typename F>
-void with_capped_after(const hvs_ctx* c, F f)
-{
-    with_capped(c, [&](auto WT) {
-        if (has_after(c))
-            f(WT, std::true_type{});
-        else
-            f(WT, std::false_type{});
-    });
-}
+// ... and, on the cursor forms only, a list form: `f` gets (after, excl) with excl only while the resident queries
+// carry exclusion lists; lists without cursors run the cursor form with an after_lo of zeros (zero_after_lo), which admits
+// every key, so the plain and the cursor forms are launched exactly as they were while no lists are set
 template <typename F>
 void with_after(const hvs_ctx* c, F f)
 {
-    if (has_after(c))
-        f(std::true_type{});
+    if (has_excl(c))
+        f(std::true_type{}, std::true_type{});
+    else if (has_after(c))
+        f(std::true_type{}, std::false_type{});
     else
-        f(std::false_type{});
+        f(std::false_type{}, std::false_type{});
+}
+template <typename F>
+void with_capped_after(const hvs_ctx* c, F f)
+{
+    with_capped(c, [&](auto WT) { with_after(c, [&](auto AT, auto XT) { f(WT, AT, XT); }); });
 }
 
 // the k best of every query's candidate lists to the output rows (hvs_k_select): `nsel` queries named by `qlist`, each with
@@ -1020,10 +1045,10 @@ void with_after(const hvs_ctx* c, F f)
 void launch_select(hvs_ctx* c, const uint32_t* qlist, uint32_t nsel, uint32_t stride, uint32_t nchunks, uint64_t* cand, uint32_t* cnt)
 {
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_capped_after(c, [&](auto WT, auto AT) {
-            hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+        with_capped_after(c, [&](auto WT, auto AT, auto XT) {
+            hipLaunchKernelGGL((hvs_k_select<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value, decltype(XT)::value>),
                                dim3((nsel + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, qlist, nsel, stride, nchunks, cand, cnt,
-                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo);
+                               c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, c->k, c->rs.d_pad_ids, c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
 }
@@ -1138,11 +1163,11 @@ int run_batch_exact(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const ui
         unsigned long long* stat = exact_batch_counters(c, count_stats);
         const dim3 grid(p.nq_pad / 256u, p.nchunks);
         with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-            with_capped_after(c, [&](auto WT, auto AT) {
+            with_capped_after(c, [&](auto WT, auto AT, auto XT) {
                 hipLaunchKernelGGL(
-                    (hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+                    (hvs_k_scan_exact_lds<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value, decltype(XT)::value>),
                     grid, dim3(256), 0, c->stream, c->d_data, c->d_q, qorder, nqb, p.nq_pad, sn, p.rows_per_chunk, c->d_cand, c->d_cand_cnt, stat,
-                    c->k, c->rs.d_live, c->qs.eng.d_max_d2, c->qs.eng.d_after_lo);
+                    c->k, c->rs.d_live, c->qs.eng.d_max_d2, c->qs.eng.d_after_lo, excl_arg(c));
             });
         });
     }
@@ -1734,10 +1759,10 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_after(c, [&](auto AT) {
-            hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
+        with_after(c, [&](auto AT, auto XT) {
+            hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value, decltype(XT)::value>),
                                dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->n_indexed, sn, c->call.d_counters,
-                               count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
+                               count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
 }
@@ -1748,10 +1773,10 @@ void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_after(c, [&](auto AT) {
-            hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value>),
+        with_after(c, [&](auto AT, auto XT) {
+            hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value, decltype(XT)::value>),
                                dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, c->rs.d_stale_ids, m,
-                               c->call.d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo);
+                               c->call.d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
 }
@@ -1806,11 +1831,11 @@ int run_batch_exact_ranges(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn)
     const int ev = kernel_timer_begin(c);
     const dim3 grid((slot_end + 255u) / 256u, nchunks);
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
-        with_capped_after(c, [&](auto WT, auto AT) {
+        with_capped_after(c, [&](auto WT, auto AT, auto XT) {
             hipLaunchKernelGGL(
-                (hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>), grid,
+                (hvs_k_scan_ranges<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value, decltype(XT)::value>), grid,
                 dim3(256), 0, c->stream, c->d_data, sn, c->d_q, B, c->ord[0].perm, c->ord[1].perm, nchunks, slot_begin, slot_end, c->d_cand,
-                c->d_cand_cnt, c->call.d_counters, index_mask(c), c->qs.eng.d_after_lo);
+                c->d_cand_cnt, c->call.d_counters, index_mask(c), c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
     kernel_timer_end(c, ev);
@@ -1971,11 +1996,11 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
     uint32_t seed_chunks = 1u;
     if (l0blocks <= B.fcap / 32u && seed_waves < kSeedWaves) seed_chunks = std::min(l0blocks, hvs_ceil_div(kSeedWaves, seed_waves));
     with_cap_mask(c, [&](auto CAPT, auto MT) {
-        with_capped_after(c, [&](auto WT, auto AT) {
-            hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+        with_capped_after(c, [&](auto WT, auto AT, auto XT) {
+            hipLaunchKernelGGL((hvs_k_seed_exact<decltype(CAPT)::value, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value, decltype(XT)::value>),
                                dim3((B.nslots + 255u) / 256u, std::max(1u, seed_chunks)), dim3(256), 0, c->stream, c->d_data, n, sn, c->d_q, B,
                                c->ord[0].perm, c->ord[1].perm, c->ord[0].bpos, c->ord[1].bpos, L, c->call.d_counters, std::max(1u, seed_chunks),
-                               index_mask(c), c->qs.eng.d_after_lo);
+                               index_mask(c), c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
     // merge behind a level: top-k, and the threshold of level `next` (its order statistic from the guess plan)
@@ -1983,16 +2008,16 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
         with_cap_mask(c, [&](auto CAPT, auto MT) {
             constexpr int CAP = decltype(CAPT)::value;
             if (final)  // (only the final merge pads and drops keys beyond a cap: the merges in front of it have no masked or capped form)
-                with_capped_after(c, [&](auto WT, auto AT) {
-                    hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value>),
+                with_capped_after(c, [&](auto WT, auto AT, auto XT) {
+                    hipLaunchKernelGGL((hvs_k_merge<true, CAP, decltype(MT)::value, decltype(WT)::value, decltype(AT)::value, decltype(XT)::value>),
                                        dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B, c->d_bounds,
                                        c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids, c->qs.eng.d_max_d2,
-                                       c->call.d_counters, c->qs.eng.d_after_lo);
+                                       c->call.d_counters, c->qs.eng.d_after_lo, excl_arg(c));
                 });
             else
                 hipLaunchKernelGGL((hvs_k_merge<false, CAP, false>), dim3((B.nslots + 3u) / 4u), dim3(256), 0, c->stream, c->d_data, c->n, c->d_q, B,
                                    c->d_bounds, c->padding ? 1 : 0, c->d_out_ids, c->d_out_dists, fmt, c->d_quant, L, next, G, c->rs.d_pad_ids,
-                                   c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo);
+                                   c->qs.eng.d_max_d2, c->call.d_counters, c->qs.eng.d_after_lo, HvsExcl{});
         });
     };
     // Rows behind the index: scanned exactly once per batch, in front of the final merge, into the lists the
@@ -2030,11 +2055,16 @@ int run_batch_mfma(hvs_ctx* c, uint32_t q0, uint32_t nqb, uint32_t sn, const uin
             if (level + 1u == L.K && gates.record_pdone) HVS_HIP(c, hipEventRecord(gates.record_pdone, c->stream));
         }
         with_cap_mask(c, [&](auto, auto MT) {
-            with_after(c, [&](auto AT) {
+            with_after(c, [&](auto AT, auto XT) {
                 constexpr bool M = decltype(MT)::value;
                 // (while rows are stale the front end gets both masks and tells stale from dead: HVS_RESCORE_TWO_MASKS)
                 const uint32_t nn = c->rs.h_stale.empty() ? n : (n | HVS_RESCORE_TWO_MASKS);
-                if constexpr (decltype(AT)::value) {
+                if constexpr (decltype(XT)::value) {
+                    const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M, const uint64_t*, HvsExcl> : hvs_k_rescore<false, M, const uint64_t*, HvsExcl>;
+                    hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
+                                       c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->call.d_counters, index_mask(c),
+                                       static_cast<const uint64_t*>(c->qs.eng.d_after_lo), excl_arg(c));
+                } else if constexpr (decltype(AT)::value) {
                     const auto rescore = fmt == HVS_FMT_I8X16 ? hvs_k_rescore<true, M, const uint64_t*> : hvs_k_rescore<false, M, const uint64_t*>;  // (entry format)
                     hipLaunchKernelGGL(rescore, dim3(rescore_blocks, B.ngroups), dim3(64 * HVS_RESCORE_WAVES), 0, c->stream, c->d_data, nn, sn,
                                        c->d_q, B, c->ord[0].perm, c->ord[1].perm, c->call.d_counters, index_mask(c),
@@ -2271,6 +2301,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     }
     c->qs.call_capped = capped(c);
     c->qs.call_after = has_after(c);
+    c->qs.call_excl = has_excl(c);
     c->qs.in.call = false;  // (in_run sets it once the merge is enqueued)
     c->qs.answered(q0, nq, c->k, c->qs.set_gen);
     if (int rc = call_begin(c)) return rc;
@@ -2421,7 +2452,8 @@ void leaf_destroy(hvs_ctx* c)
     c->pipe.destroy();
 }
 
-int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq);
+int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq, const uint32_t* ex_off = nullptr,
+                    const uint32_t* ex_ids = nullptr);
 
 // query / result buffers and the batch workspace for calls of up to nq queries (hvs_reserve, hvs_query): keeps the
 // ~34 GB of per-batch state of a 2^21-query batch out of the first query's own time
@@ -2805,6 +2837,104 @@ int ensure_after(hvs_ctx* c, uint32_t nq)
     return per_query_room(c, c->qs.eng, kCursors, nq);
 }
 
+// Exclusion lists without cursors run the cursor forms of the kernels: an after_lo of zeros, one per resident
+// query, admits every key.  Called whenever lists are (or stay) set while cursors are not.
+int zero_after_lo(hvs_ctx* c)
+{
+    if (int rc = ensure_after(c, std::max(c->nq, 1u))) return rc;
+    HVS_HIP(c, hipMemsetAsync(c->qs.eng.d_after_lo, 0, (size_t)c->qs.eng.after_cap * sizeof(uint64_t), c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return HVS_OK;
+}
+
+// ---- exclusion lists: two steps per GPU, so that a refusal on any GPU leaves every GPU as it was ----
+// Step 1: `count` + 1 offsets from `off` (host memory, src_dev < 0, or device memory of GPU src_dev) into the staging array and
+// through hvs_k_check_exclude.  `first`: they are the head of the caller's array.  Leaves the flags, the first offset and the
+// number of ids behind it in the query set's st_* fields; nothing that is in force is touched.
+int leaf_exclude_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t count, bool first)
+{
+    HvsQuerySet& s = c->qs;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));
+    if ((rc = resolve_overflow(c))) return rc;  // (an earlier call's re-runs: under the lists they were asked under)
+    if (count + 1u > s.ex_off_cap) {
+        s.ex_off_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_ex_off, (size_t)count + 1u))) return rc;
+        s.ex_off_cap = count + 1u;
+    }
+    if (!s.d_ex_status && (rc = dev_alloc(c, &s.d_ex_status, (size_t)4))) return rc;
+    if (src_dev < 0)
+        HVS_HIP(c, hipMemcpyAsync(s.d_ex_off, off, ((size_t)count + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    else if ((rc = copy_from_device(c, s.d_ex_off, off, src_dev, ((size_t)count + 1u) * sizeof(uint32_t))))
+        return rc;
+    HVS_HIP(c, hipMemsetAsync(s.d_ex_status, 0, 4 * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(hvs_k_check_exclude, dim3(hvs_ceil_div(std::max(count, 1u), 256u)), dim3(256), 0, c->stream, s.d_ex_off, count, first ? 1 : 0,
+                       s.d_ex_status);
+    HVS_HIP(c, hipGetLastError());
+    uint32_t h[4] = {0, 0, 0, 0};
+    HVS_HIP(c, hipMemcpyAsync(h, s.d_ex_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    s.st_flags = h[0];
+    s.st_base = h[1];
+    s.st_total = h[0] ? 0u : h[2] - h[1];  // (offsets[count] is the id array's length only once every pair is ascending)
+    return HVS_OK;
+}
+// Step 2 (every GPU's offsets were accepted): the ids behind the staged offsets -- `ids` is the caller's array -- are copied
+// and normalised for rows [row0, row0 + n_rows) by hvs_k_norm_exclude; under category sets they are the user's, and every
+// sub-query takes its parent's pair.
+int leaf_exclude_commit(hvs_ctx* c, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0, uint32_t n_rows)
+{
+    HvsQuerySet& s = c->qs;
+    const bool sets = s.in.active;
+    HvsPerQuery& dst = sets ? s.in.user : s.eng;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));
+    s.excl_set = false;  // (the buffers are about to change)
+    auto room = [&](HvsPerQuery& v, uint32_t n) -> int {
+        if (n <= v.excl_cap) return HVS_OK;
+        v.excl_cap = 0;
+        if ((rc = dev_alloc(c, &v.d_ex_begin, (size_t)n)) || (rc = dev_alloc(c, &v.d_ex_count, (size_t)n))) return rc;
+        v.excl_cap = n;
+        return HVS_OK;
+    };
+    if ((rc = room(dst, std::max(count, 1u))) || (sets && (rc = room(s.eng, std::max(c->nq, 1u))))) return rc;
+    const uint32_t total = s.st_total;
+    if (std::max(total, 1u) > s.ex_ids_cap) {
+        s.ex_ids_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_ex_ids, (size_t)std::max(total, 1u)))) return rc;
+        s.ex_ids_cap = std::max(total, 1u);
+    }
+    if (total) {
+        if (src_dev < 0)
+            HVS_HIP(c, hipMemcpyAsync(s.d_ex_ids, ids + s.st_base, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else if ((rc = copy_from_device(c, s.d_ex_ids, ids + s.st_base, src_dev, (size_t)total * sizeof(uint32_t))))
+            return rc;
+    }
+    if (count) {
+        hipLaunchKernelGGL(hvs_k_norm_exclude, dim3(hvs_ceil_div(count, 4u)), dim3(256), 0, c->stream, s.d_ex_off, count, s.d_ex_ids, row0, n_rows,
+                           dst.d_ex_begin, dst.d_ex_count);
+        HVS_HIP(c, hipGetLastError());
+        if (sets && c->nq) {
+            hipLaunchKernelGGL(hvs_k_expand_exclude, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, s.in.d_parent, c->nq, dst.d_ex_begin,
+                               dst.d_ex_count, s.eng.d_ex_begin, s.eng.d_ex_count);
+            HVS_HIP(c, hipGetLastError());
+        }
+    }
+    if (!s.after_set && (rc = zero_after_lo(c))) return rc;
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
+    s.ex_nq = count;
+    s.ex_total = total;
+    s.excl_set = true;
+    return HVS_OK;
+}
+int leaf_exclude_remove(hvs_ctx* c)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (int rc = resolve_overflow(c)) return rc;
+    c->qs.excl_set = false;
+    return HVS_OK;
+}
+
 // The one way caps or cursors reach the resident queries of one GPU: `count` values from `src` (count = the user's resident
 // queries: checked by the caller) are attached, or the values are removed.  Under category sets they are the user's, one per user
 // query: copied and normalised on the user's side (HvsInSet::user), then every sub-query takes its parent's.  `row0` (cursors):
@@ -2820,6 +2950,7 @@ int leaf_attach(hvs_ctx* c, PerQuery what, const PerQuerySource& src, uint32_t c
         if ((rc = resolve_overflow(c))) return rc;  // (for LastSlot: the last slots of re-run queries too)
         if (src.kind == PerQuerySource::Remove) {
             (caps ? s.caps_set : s.after_set) = false;
+            if (!caps && s.excl_set) return zero_after_lo(c);  // (the list forms are cursor forms: they go on reading after_lo)
             return HVS_OK;
         }
         if (!caps && (rc = ensure_after(c, std::max(std::max(count, sets ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
@@ -3484,7 +3615,8 @@ struct PipeCall {
 // `max_d2` (hvs_query_within): the queries' distance caps, nq floats of host memory -- 4 bytes per query, sent whole before the
 // pipeline starts.
 int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists,
-               const PeerSink* sink = nullptr, const float* max_d2 = nullptr, const float* after_d = nullptr, const uint32_t* after_i = nullptr)
+               const PeerSink* sink = nullptr, const float* max_d2 = nullptr, const float* after_d = nullptr, const uint32_t* after_i = nullptr,
+               const uint32_t* ex_off = nullptr, const uint32_t* ex_ids = nullptr)
 {
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if (nq == 0) return HVS_OK;
@@ -3500,7 +3632,7 @@ int leaf_query(hvs_ctx* c, const float* q_rows, uint32_t nq, float sample_propor
     if ((rc = c->pipe.size_for(c->k, out_dists != nullptr && !sink, in_pinned ? 0u : nq, out_pinned ? 0u : nq))) return rc;
     tr.mark("staging");
     c->nq = nq;
-    if ((rc = attach_for_call(c, max_d2, after_d, after_i, nq))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too)
+    if ((rc = attach_for_call(c, max_d2, after_d, after_i, nq, ex_off, ex_ids))) return rc;  // (hvs_query_after: 8 bytes per query, sent whole too; lists likewise)
     PipeCall call{c, c->pipe, q_rows, nq, out_ids, out_dists, sink, in_pinned, out_pinned, tr};
     tr.mark("pointers");
     if ((rc = run_queries(c, 0, nq, sample_proportion, call, true))) return rc;
@@ -4047,10 +4179,59 @@ int attach_everywhere(hvs_ctx* c, PerQuery what, const float* f, const uint32_t*
     });
 }
 // hvs_query_after / hvs_query_within: the call's caps and cursors (host memory, `nq` each; nullptr: none) onto the queries just installed
-int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq)
+// The caller's exclusion lists (CSR: `nq` + 1 offsets, the ids; host memory, src_dev < 0, or device memory of GPU src_dev) to
+// every leaf, or, both nullptr, off every leaf.  A replicated context cuts the CSR by the owner ranges -- a leaf takes its
+// queries' offsets and the ids between them; a row-partitioned one gives every part all of it and the part's row window (the
+// last part's is open-ended: an id behind the rows of today names a row that an append may bring).  `first`: `off` is the head
+// of the caller's array (a leaf of a replicated hvs_query_excluding gets a slice that the root has checked).  Every leaf's
+// offsets are checked before any leaf's lists are replaced: HVS_EINVAL leaves every GPU as it was.
+int exclude_everywhere(hvs_ctx* c, const uint32_t* off, const uint32_t* ids, int src_dev, uint32_t nq, bool first, const char* fn)
+{
+    if (!off) return on_every_leaf(c, leaf_exclude_remove);
+    struct Share {
+        hvs_ctx* k;
+        uint32_t q0, m, row0, n_rows;
+    };
+    std::vector<Share> sh;
+    if (c->kids.empty())
+        sh.push_back({c, 0u, nq, 0u, 0xFFFFFFFFu});
+    else {
+        const uint32_t N = (uint32_t)c->kids.size();
+        const bool cut = c->kid_q0.size() == N + 1u;
+        for (uint32_t r = 0; r < N; ++r) {
+            if (c->partitioned) {
+                const uint32_t row0 = c->part_row0.size() > r + 1u ? c->part_row0[r] : 0u;
+                sh.push_back({c->kids[r], 0u, nq, row0, r + 1u == N ? 0xFFFFFFFFu - row0 : c->part_row0[r + 1] - row0});
+            } else
+                sh.push_back({c->kids[r], cut ? c->kid_q0[r] : 0u, cut ? c->kid_q0[r + 1] - c->kid_q0[r] : 0u, 0u, 0xFFFFFFFFu});
+        }
+    }
+    auto each = [&](auto f) -> int {
+        if (c->kids.empty()) return f(sh[0]);
+        return for_each_leaf(c, [&](uint32_t r) { return f(sh[r]); });
+    };
+    int rc = each([&](const Share& s) { return leaf_exclude_stage(s.k, off + s.q0, src_dev, s.m, first && s.q0 == 0u); });
+    if (rc) return rc;
+    uint32_t flags = 0;
+    for (const Share& s : sh) flags |= s.k->qs.st_flags;
+    if (flags)
+        return fail(c, HVS_EINVAL,
+                    std::string(fn) + (flags & HVS_EXCL_BAD_FIRST   ? ": excl_offsets[0] is not 0"
+                                       : flags & HVS_EXCL_BAD_ORDER ? ": excl_offsets are not ascending"
+                                                                    : ": a list has more than HVS_EXCLUDE_MAX entries"));
+    rc = each([&](const Share& s) { return leaf_exclude_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows); });
+    if (rc)  // (a copy or an allocation failed: some GPUs may hold the new lists and some the old -- none is in force)
+        for (const Share& s : sh) s.k->qs.excl_set = false;
+    return rc;
+}
+// hvs_query_after / hvs_query_within / hvs_query_excluding: the call's caps, cursors and lists (host memory, `nq` each, the lists
+// as a CSR whose offsets the caller has checked; nullptr: none) onto the queries just installed
+int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const uint32_t* after_i, uint32_t nq, const uint32_t* ex_off,
+                    const uint32_t* ex_ids)
 {
     int rc = max_d2 ? attach_everywhere(c, PerQuery::Caps, max_d2, nullptr, -1, nq) : HVS_OK;
     if (!rc && after_d) rc = attach_everywhere(c, PerQuery::Cursors, after_d, after_i, -1, nq);
+    if (!rc && ex_off) rc = exclude_everywhere(c, ex_off, ex_ids, -1, nq, false, "hvs_query_excluding");
     return rc;
 }
 
@@ -4183,6 +4364,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     c->part_timing_valid = false;
     c->qs.call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
     c->qs.call_after = has_after(c->kids[0]);  // (likewise the cursors)
+    c->qs.call_excl = has_excl(c->kids[0]);    // (and the lists)
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -4405,6 +4587,19 @@ int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
     out->after_slots = v[0];
     out->underfull_queries = (uint32_t)v[1];
     out->exhausted_queries = (uint32_t)v[2];  // (under category sets: counted per sub-query, as the slots are)
+    return in_underfull(c, &out->underfull_queries);
+}
+
+int leaf_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
+{
+    unsigned long long v[3] = {0, 0, 0}, sink[1] = {0};
+    int rc = leaf_call_counters(c, out, c->qs.call_excl, HVS_CNT_EXCL_SLOTS, v);
+    if (rc || !c->qs.call_excl) return rc;
+    if ((rc = call_counters(c, HVS_CNT_RERUN_SINK_EXCL_REFUSED, sink))) return rc;  // (the exact engine's re-runs count through the sink)
+    out->excluding_queries = c->call.timing.nq;
+    out->kept_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    out->refused_keys = v[2] + sink[0];
     return in_underfull(c, &out->underfull_queries);
 }
 
@@ -4976,16 +5171,26 @@ int hvs_query_within(hvs_ctx* c, const float* q_rows, const float* max_d2, uint3
 int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const uint32_t* after_i, const float* max_d2, uint32_t nq,
                     float sample_proportion, uint32_t* out_ids, float* out_dists)
 {
+    return hvs_query_excluding(c, q_rows, nullptr, nullptr, after_d, after_i, max_d2, nq, sample_proportion, out_ids, out_dists);
+}
+
+int hvs_query_excluding(hvs_ctx* c, const float* q_rows, const uint32_t* ex_off, const uint32_t* ex_ids, const float* after_d, const uint32_t* after_i,
+                        const float* max_d2, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists)
+{
     if (!c) return HVS_EINVAL;
     if ((after_d == nullptr) != (after_i == nullptr)) return fail(c, HVS_EINVAL, "hvs_query_after: one of after_dists / after_ids is NULL");
-    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists, nullptr, max_d2, after_d, after_i);
+    if ((ex_off == nullptr) != (ex_ids == nullptr)) return fail(c, HVS_EINVAL, "hvs_query_excluding: one of excl_offsets / excl_ids is NULL");
+    // (the lists are the caller's host memory: refused here, before the resident set is replaced)
+    if (ex_off && hvs_exclude_plan(ex_off, nullptr, nq, 0u, 0xFFFFFFFFu, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
+        return fail(c, HVS_EINVAL, "hvs_query_excluding: excl_offsets are malformed, or a list has more than HVS_EXCLUDE_MAX entries");
+    if (c->kids.empty()) return leaf_query(c, q_rows, nq, sample_proportion, out_ids, out_dists, nullptr, max_d2, after_d, after_i, ex_off, ex_ids);
     if (nq == 0) return HVS_OK;
     if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query: q_rows / out_ids is NULL");
     const auto t0 = std::chrono::steady_clock::now();
     if (c->partitioned) {
         // all queries to every part over its own link, the resident call, each owner's merged slice home
         int rc = hvs_upload_queries(c, q_rows, nq);
-        if (!rc) rc = attach_for_call(c, max_d2, after_d, after_i, nq);
+        if (!rc) rc = attach_for_call(c, max_d2, after_d, after_i, nq, ex_off, ex_ids);
         if (!rc) rc = part_run(c, 0u, nq, sample_proportion);
         if (!rc) rc = part_download_results(c, 0u, nq, out_ids, out_dists);
         c->call.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -5001,7 +5206,7 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
             if (m == 0u) return call_forgotten(c->kids[r]);
             return leaf_query(c->kids[r], q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, out_ids + (size_t)a * c->k,
                               out_dists ? out_dists + (size_t)a * c->k : nullptr, nullptr, max_d2 ? max_d2 + a : nullptr,
-                              after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr);
+                              after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr, ex_off ? ex_off + a : nullptr, ex_ids);
         });
     } else {
         // peer gather (A/B partner of the direct path): every GPU runs the same host pipeline on its slice of the caller's
@@ -5020,13 +5225,13 @@ int hvs_query_after(hvs_ctx* c, const float* q_rows, const float* after_d, const
                 if (r == 0u) {  // its results are already where the gather wants them: plain resident run of its slice
                     int r2 = leaf_upload_queries(k, q_rows, m);
                     if (r2) return r2;
-                    if ((r2 = attach_for_call(k, max_d2, after_d, after_i, m))) return r2;
+                    if ((r2 = attach_for_call(k, max_d2, after_d, after_i, m, ex_off, ex_ids))) return r2;
                     if ((r2 = run_queries(k, 0, m, sample_proportion, NoHook{}))) return r2;
                     return leaf_sync(k);
                 }
                 const PeerSink sink{k0, a, out_dists != nullptr};
                 return leaf_query(k, q_rows + (size_t)a * HVS_QCOLS, m, sample_proportion, nullptr, nullptr, &sink, max_d2 ? max_d2 + a : nullptr,
-                                  after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr);
+                                  after_d ? after_d + a : nullptr, after_i ? after_i + a : nullptr, ex_off ? ex_off + a : nullptr, ex_ids);
             });
         if (!rc) {
             (void)hipSetDevice(k0->device);
@@ -5259,6 +5464,96 @@ void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_
     const uint64_t lo = hvs_after_lo(after_dist, after_id, 0u);
     const uint32_t after = plan_row(ids, dists, m, k, [&](const PlanSlot& s) { return s.key >= lo; }, pad_ids, pad_dists, padding, out_ids, out_dists);
     if (n_after) *n_after = after;
+}
+
+// ---- per-query exclusion lists (include/hvs.h "per-query exclusion lists") -------
+
+static_assert(HVS_EXCLUDE_MAX == HVS_EXCLUDE_MAX_, "the kernels' list capacity is the contract's");
+
+uint32_t hvs_exclude_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t* begin, uint32_t* count,
+                          uint32_t* out_ids)
+{
+    if (!offsets || offsets[0] != 0u) return 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (offsets[q + 1] < offsets[q] || offsets[q + 1] - offsets[q] > HVS_EXCLUDE_MAX) return 0xFFFFFFFFu;
+    uint32_t kept_all = 0;
+    std::vector<uint32_t> row;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t a = offsets[q], len = offsets[q + 1] - a;
+        uint32_t kept = 0;
+        if (ids) {
+            row.clear();
+            for (uint32_t e = 0; e < len; ++e)
+                if (hvs_exclude_keeps(ids[a + e], row0, n_rows)) row.push_back(ids[a + e] - row0);
+            std::sort(row.begin(), row.end());
+            row.erase(std::unique(row.begin(), row.end()), row.end());
+            kept = (uint32_t)row.size();
+            if (out_ids) {
+                std::copy(row.begin(), row.end(), out_ids + a);
+                std::fill(out_ids + a + kept, out_ids + a + len, 0xFFFFFFFFu);
+            }
+        }
+        if (begin) begin[q] = a;
+        if (count) count[q] = kept;
+        kept_all += kept;
+    }
+    return kept_all;
+}
+
+int hvs_set_exclude_ids(hvs_ctx* c, const uint32_t* excl_offsets, const uint32_t* excl_ids, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, "hvs_set_exclude_ids")) return HVS_ESTATE;
+    if (!excl_offsets && !excl_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, "hvs_set_exclude_ids");
+    if (!excl_offsets || !excl_ids) return fail(c, HVS_EINVAL, "hvs_set_exclude_ids: one of excl_offsets / excl_ids is NULL");
+    if (int rc = check_resident_count(c, nq, "hvs_set_exclude_ids")) return rc;
+    return exclude_everywhere(c, excl_offsets, excl_ids, -1, nq, true, "hvs_set_exclude_ids");
+}
+
+int hvs_set_exclude_ids_device(hvs_ctx* c, const uint32_t* d_offsets, const uint32_t* d_ids, uint32_t nq, void* stream)
+{
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, "hvs_set_exclude_ids_device")) return HVS_ESTATE;
+    if (!d_offsets && !d_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, "hvs_set_exclude_ids_device");
+    if (!d_offsets || !d_ids) return fail(c, HVS_EINVAL, "hvs_set_exclude_ids_device: one of d_offsets / d_ids is NULL");
+    int dev = 0, rc = check_resident_count(c, nq, "hvs_set_exclude_ids_device");
+    if (!rc) rc = check_device_buffers(c, d_offsets, d_ids, stream, "hvs_set_exclude_ids_device", &dev);
+    return rc ? rc : exclude_everywhere(c, d_offsets, d_ids, dev, nq, true, "hvs_set_exclude_ids_device");
+}
+
+int hvs_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
+{
+    return call_stats<hvs_exclude_info>(
+        c, out, leaf_exclude_stats,
+        [](hvs_exclude_info& sum, const hvs_exclude_info& m) {
+            sum.excluding_queries += m.excluding_queries;
+            sum.underfull_queries += m.underfull_queries;
+            sum.kept_slots += m.kept_slots;
+            sum.refused_keys += m.refused_keys;
+        },
+        [&](hvs_exclude_info& sum) {
+            // the rules of hvs_within_stats: slots and refused keys summed over the parts, the queries the call's, under-full from the merge
+            sum.excluding_queries = c->qs.call_excl ? c->part_call_nq : 0u;
+            sum.underfull_queries = c->qs.call_excl ? c->pinfo.padded_queries : 0u;
+        });
+}
+
+int hvs_download_exclude_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
+{
+    if (!c) return HVS_EINVAL;
+    if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_exclude_plan: single-GPU contexts only");
+    const HvsQuerySet& s = c->qs;
+    if (!s.excl_set) return fail(c, HVS_ESTATE, "hvs_download_exclude_plan: no exclusion lists are attached");
+    const HvsPerQuery& v = s.in.active ? s.in.user : s.eng;
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (s.ex_nq) {
+        if (begin) HVS_HIP(c, hipMemcpyAsync(begin, v.d_ex_begin, (size_t)s.ex_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (count) HVS_HIP(c, hipMemcpyAsync(count, v.d_ex_count, (size_t)s.ex_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (ids && cap >= s.ex_total && s.ex_total)
+        HVS_HIP(c, hipMemcpyAsync(ids, s.d_ex_ids, (size_t)s.ex_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return (int)s.ex_total;
 }
 
 // ---- category sets (include/hvs.h "category sets") -------------------------------

@@ -43,7 +43,14 @@ enum HvsCounter : int {
     HVS_CNT_AFTER_UNDERFULL = 17,   // ... queries left with fewer than k                  -> hvs_after_info.underfull_queries
     HVS_CNT_AFTER_EXHAUSTED = 18,   // ... cursors behind every key                        -> hvs_after_info.exhausted_queries
     HVS_CNT_UNUSED_19 = 19,
-    HVS_CNT_COUNT = 20
+    HVS_CNT_EXCL_SLOTS = 20,        // exclusion lists: slots kept                         -> hvs_exclude_info.kept_slots
+    HVS_CNT_EXCL_UNDERFULL = 21,    // ... queries left with fewer than k                  -> hvs_exclude_info.underfull_queries
+    HVS_CNT_EXCL_REFUSED = 22,      // ... keys dropped at an admission point for being listed -> hvs_exclude_info.refused_keys
+    HVS_CNT_UNUSED_23 = 23,
+    // (slots 24..27 are 20..23 as seen from HVS_CNT_RERUN_SINK: an exact re-run's refused keys land in slot 26, which
+    // hvs_exclude_stats adds to slot 22 -- the re-run is the pass that gave the query's answer)
+    HVS_CNT_RERUN_SINK_EXCL_REFUSED = 26,
+    HVS_CNT_COUNT = 28
 };
 // the host reads these as runs (one copy each), and hvs_scan_rows_into_lists writes slots CNT and CNT + 1
 static_assert(HVS_CNT_SCANNED == HVS_CNT_PAIRS + 1 && HVS_CNT_RESCORED == HVS_CNT_PAIRS + 2, "hvs_timing's three counts are one run");
@@ -52,6 +59,9 @@ static_assert(HVS_CNT_TAIL_KEYS == HVS_CNT_TAIL_PAIRS + 1, "hvs_scan_rows_into_l
 static_assert(HVS_CNT_STALE_KEYS == HVS_CNT_STALE_PAIRS + 1 && HVS_CNT_STALE_SURVIVORS == HVS_CNT_STALE_PAIRS + 2, "one run, and CNT + 1");
 static_assert(HVS_CNT_WITHIN_UNDERFULL == HVS_CNT_WITHIN_SLOTS + 1, "hvs_within_stats reads one run");
 static_assert(HVS_CNT_AFTER_UNDERFULL == HVS_CNT_AFTER_SLOTS + 1 && HVS_CNT_AFTER_EXHAUSTED == HVS_CNT_AFTER_SLOTS + 2, "hvs_after_stats reads one run");
+static_assert(HVS_CNT_EXCL_UNDERFULL == HVS_CNT_EXCL_SLOTS + 1 && HVS_CNT_EXCL_REFUSED == HVS_CNT_EXCL_SLOTS + 2, "hvs_exclude_stats reads one run");
+static_assert(HVS_CNT_RERUN_SINK_EXCL_REFUSED == HVS_CNT_RERUN_SINK + HVS_CNT_EXCL_REFUSED && HVS_CNT_RERUN_SINK_EXCL_REFUSED < HVS_CNT_COUNT,
+              "a kernel that counts through the sink base stays inside the block");
 
 // ---------------------------------------------------------------------------------------------
 // Query parameters: reference include/optimized_parallel.hpp:93-96

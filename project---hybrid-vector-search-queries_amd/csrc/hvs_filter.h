@@ -1374,7 +1374,9 @@ __global__ __launch_bounds__(4 * HVS_GROUP) void hvs_k_prep(const float* __restr
 // AFTER (result cursors; `after_lo` is not read otherwise): only keys >= after_lo[query] are admitted.  The chunked
 // form cannot reserve a block's places from the ranges alone then -- how many of a block's rows lie behind the cursor is known
 // only once their distances are --, so it takes one place per admitted key with an atomic of its own.
-template <int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
+// EXCL (a cursor form only, exclusion lists; `excl` is not read otherwise): ... and only keys of rows that the
+// query's list does not name; the chunked form keeps taking one place per admitted key.
+template <int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restrict__ D, uint32_t n, uint32_t sn,
                                                            const float* __restrict__ Q, HvsBatch B,
                                                            const uint32_t* __restrict__ perm_ct,
@@ -1382,13 +1384,16 @@ __global__ __launch_bounds__(256, 3) void hvs_k_seed_exact(const float* __restri
                                                            const uint32_t* __restrict__ bpos_ct,
                                                            const uint32_t* __restrict__ bpos_t, HvsLevels L,
                                                            unsigned long long* __restrict__ counters, uint32_t nchunks,
-                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
+                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo,
+                                                           HvsExcl excl)
 {
+    static_assert(!EXCL || AFTER, "the list forms exist on the cursor forms only");
     __shared__ float4 srow[4][HVS_SEED_STAGE][26];  // per wave: 16 data rows as 16-byte aligned images x0..x99 (+ pad)
     // nchunks > 1 (small batches, level 0 of at most 1024 rows): grid.y waves share one 64-slot group, each
     // takes every nchunks-th level-0 block and appends to the slots' lists with atomics -- a single wave per
     // group walks ~1000 randomly placed rows one after the other and is latency-bound (2 ms at 10^4 queries)
     const uint32_t lane = threadIdx.x & 63u;
+    if constexpr (EXCL) hvs_refused_begin(lane);
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t slot = w * 64u + lane;
     if (w * 64u >= B.nslots) return;
@@ -1485,7 +1490,11 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
             if constexpr (AFTER) {
                 if (nchunks > 1u) {  // wave-uniform: one place per key behind the cursor (see AFTER above)
                     const uint64_t key = hvs_make_key(dist, id);
-                    if (pass && key >= key_lo) {
+                    bool admit = pass && key >= key_lo;
+                    if constexpr (EXCL) {
+                        if (admit && hvs_refuse_listed(excl, qi, id)) admit = false;
+                    }
+                    if (admit) {
                         const uint32_t at = atomicAdd(&B.candcnt[slot], 1u);
                         if (at < B.fcap)
                             mylist[at] = key;
@@ -1494,7 +1503,11 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
                     }
                     continue;
                 }
-                if (pass && dist <= tau && hvs_make_key(dist, id) >= key_lo) {
+                bool admit = pass && dist <= tau && hvs_make_key(dist, id) >= key_lo;
+                if constexpr (EXCL) {
+                    if (admit && hvs_refuse_listed(excl, qi, id)) admit = false;
+                }
+                if (admit) {
                     mylist[cnt] = hvs_make_key(dist, id);
                     ++cnt;
                 }
@@ -1527,6 +1540,7 @@ HVS_PRAGMA(unroll HVS_SEED_UNROLL)
         }
     }
     if (nchunks == 1u) B.candcnt[slot] = cnt;
+    if constexpr (EXCL) hvs_count_refused(lane, counters);
     if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
 }
 
@@ -1548,7 +1562,8 @@ struct HvsUniformRowF2 {
 // hvs_k_prep<true> put it (nothing lowers it in the exact engine).  The lane's own threshold keeps its "NaN admits every row
 // until the first cut" start: the cap is a second test, not its initial value.
 // AFTER: ... and `key >= after_lo[query]` (result cursors; `after_lo` is not read otherwise)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
+// EXCL (a cursor form only): ... and the row's id is not in the query's exclusion list (`excl` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restrict__ D, uint32_t sn,
                                                             const float* __restrict__ Q, HvsBatch B,
                                                             const uint32_t* __restrict__ perm_ct,
@@ -1556,9 +1571,12 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
                                                             uint32_t slot_begin, uint32_t slot_end, uint64_t* __restrict__ cand,
                                                             uint32_t* __restrict__ cand_cnt,
                                                             unsigned long long* __restrict__ counters,
-                                                            const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
+                                                            const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo,
+                                                            HvsExcl excl)
 {
+    static_assert(!EXCL || AFTER, "the list forms exist on the cursor forms only");
     const uint32_t lane = threadIdx.x & 63u;
+    if constexpr (EXCL) hvs_refused_begin(lane);
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t slot = w * 64u + lane;
     if (w * 64u >= slot_end || w * 64u + 64u <= slot_begin) return;
@@ -1623,6 +1641,9 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         bool admit = pass && !(dist > tau);  // ids are not monotone along a position range: keep ties, the keys sort them out
         if constexpr (CAPPED) admit = admit && dist <= cap;
         if constexpr (AFTER) admit = admit && hvs_make_key(dist, id) >= key_lo;
+        if constexpr (EXCL) {
+            if (admit && hvs_refuse_listed(excl, qi, id)) admit = false;
+        }
         if (admit) {
             mylist[cnt] = hvs_make_key(dist, id);
             ++cnt;
@@ -1644,6 +1665,7 @@ __global__ __launch_bounds__(256, 3) void hvs_k_scan_ranges(const float* __restr
         }
     }
     if (have_q) cand_cnt[(size_t)chunk * B.nslots + slot] = cnt;
+    if constexpr (EXCL) hvs_count_refused(lane, counters);
     if (lane == 0u) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
 }
 
@@ -2725,8 +2747,12 @@ __global__ __launch_bounds__(64 * HVS_WG_WAVES, HVS_FILTER_OCC) void hvs_k_filte
 // slot's query -- beside the threshold test, which it does not replace.  The kernel reads its launch dimensions, which lie
 // behind the arguments, so one more argument would move them for the plain form too: the cursor form takes `after_lo` as the
 // one member of the argument pack AFTER (const uint64_t*), and the plain form, with an empty pack, keeps its argument block.
-template <typename T>
-__device__ __forceinline__ T hvs_only_arg(T a) { return a; }
+// The list form (exclusion lists) is the cursor form with a second member, the HvsExcl: a key that the threshold
+// and the cursor admit is appended only if its row is not in the list of its slot's query.
+template <typename T, typename... R>
+__device__ __forceinline__ T hvs_only_arg(T a, R...) { return a; }
+template <typename T, typename U>
+__device__ __forceinline__ U hvs_second_arg(T, U b) { return b; }
 template <bool E16, bool MASKED, typename... AFTER>
 __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const float* __restrict__ D, uint32_t n, uint32_t sn, const float* __restrict__ Q,
                                                      HvsBatch B, const uint32_t* __restrict__ perm_ct,
@@ -2734,7 +2760,8 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
                                                      unsigned long long* __restrict__ counters,
                                                      const uint32_t* __restrict__ live, AFTER... after_lo)
 {
-    static_assert(sizeof...(AFTER) <= 1, "AFTER is empty, or the cursors' const uint64_t*");
+    static_assert(sizeof...(AFTER) <= 2, "AFTER is empty, the cursors' const uint64_t*, or that and the lists' HvsExcl");
+    if constexpr (sizeof...(AFTER) == 2) hvs_refused_begin(threadIdx.x & 63u);
     // the group's 128 query vectors are staged in LDS once per block (51 KB)
     __shared__ float sq[HVS_GROUP][HVS_NDIM];
     __shared__ uint64_t slist[HVS_RESCORE_WAVES][64];  // wave-private (slot << 32 | position) pairs of one round
@@ -2859,6 +2886,9 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
                         const uint64_t* __restrict__ lo = hvs_only_arg(after_lo...);
                         const uint32_t qa = B.qid[slot[u]];
                         pend[u] = qa != 0xFFFFFFFFu && pend_key[u] >= lo[qa];
+                        if constexpr (sizeof...(AFTER) == 2) {
+                            if (pend[u] && hvs_refuse_listed(hvs_second_arg(after_lo...), qa, id[u])) pend[u] = false;
+                        }
                     }
                 }
                 if (pend[u]) pend_k[u] = atomicAdd(&B.candcnt[slot[u]], 1u);  // (result used by the next retire)
@@ -2930,6 +2960,7 @@ __global__ __launch_bounds__(64 * HVS_RESCORE_WAVES) void hvs_k_rescore(const fl
         for (int o = 32; o > 0; o >>= 1) nstale += __shfl_xor(nstale, o);
         if (lane == 0u && nstale) atomicAdd(&counters[HVS_CNT_STALE_SURVIVORS], (unsigned long long)nstale);
     }
+    if constexpr (sizeof...(AFTER) == 2) hvs_count_refused(threadIdx.x & 63u, counters);
 }
 
 // Order statistic of a guessed threshold as a function of the fraction F of the query's rows seen so far (host:
@@ -3041,14 +3072,18 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 // AFTER (FINAL only, result cursors; `after_lo` is not read otherwise).  Every list the levels filled holds keys behind
 // the query's cursor only (seed, re-scoring, tail and stale scans test it at admission), so "the range's rows" above reads "the
 // range's rows behind the cursor" throughout and the verification is the plain one.  hvs_keep_after tests once more and counts.
-template <bool FINAL, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
+// EXCL (FINAL and a cursor form only, exclusion lists; `excl` is not read otherwise): the same with "rows that the
+// query's list does not name"; hvs_keep_unlisted tests once more and counts.
+template <bool FINAL, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, uint32_t n, const float* __restrict__ Q,
                                                    HvsBatch B, const HvsBounds* __restrict__ bounds, int pad,
                                                    uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, int fmt,
                                                    const HvsQuant* __restrict__ qz, HvsLevels L, uint32_t level_next,
                                                    HvsGuessTable G, const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps,
-                                                   unsigned long long* __restrict__ counters, const uint64_t* __restrict__ after_lo)
+                                                   unsigned long long* __restrict__ counters, const uint64_t* __restrict__ after_lo,
+                                                   HvsExcl excl)
 {
+    static_assert(!EXCL || (AFTER && FINAL), "the list forms exist on the final cursor forms only");
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
     const uint32_t lane = threadIdx.x & 63u;
@@ -3146,6 +3181,7 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
         uint32_t failed = lane == 0u ? B.overflow[slot] : 0u;
         failed = (uint32_t)__shfl((int)failed, 0);
         cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, failed == 0u);
+        if constexpr (EXCL) cnt = hvs_keep_unlisted(buf, cnt, excl, qi, knn, lane, counters, failed == 0u);
     }
     // ---- final: pad, rank-sort, write
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
@@ -3238,15 +3274,19 @@ struct HvsTailOut {
 // round trip per block -- the ids of a block are fetched one block earlier than its rows, so the dependent pair id -> row is
 // never paid in sequence inside the loop --, double-buffered like the contiguous form, the ids kept in LDS beside the rows.
 // AFTER (result cursors; `after_lo` is not read otherwise): a key is wanted only if it is >= after_lo[query].
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool LIST, int CNT, bool AFTER = false>
+// EXCL (a cursor form only, exclusion lists; `excl` is not read otherwise): ... and its row is not in the query's list.
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool LIST, int CNT, bool AFTER = false, bool EXCL = false>
 __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict__ D, const float* __restrict__ Q, const HvsBatch B,
                                                          const HvsTailOut O, const uint32_t* __restrict__ ids, uint32_t tail_lo,
                                                          uint32_t tail_hi, unsigned long long* __restrict__ counters, int count,
-                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo = nullptr)
+                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo = nullptr,
+                                                         HvsExcl excl = HvsExcl{})
 {
+    static_assert(!EXCL || AFTER, "the list forms exist on the cursor forms only");
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     __shared__ uint32_t sid[LIST ? 2 : 1][LIST ? HVS_LDS_ROWS : 1];  // (LIST) ids of the staged rows
     const uint32_t lane = threadIdx.x & 63u;
+    if constexpr (EXCL) hvs_refused_begin(lane);
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t slot = w * 64u + lane;
     const bool wave_active = w * 64u < B.nslots;  // inactive waves still help staging and meet the barriers
@@ -3364,6 +3404,9 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
                 }
                 bool want = pass && takes && !(dist > tau);
                 if constexpr (AFTER) want = want && hvs_make_key(dist, id) >= key_lo;
+                if constexpr (EXCL) {
+                    if (want && hvs_refuse_listed(excl, qi, id)) want = false;
+                }
                 // a key that finds its segment full: the wave cuts the segment first (or flags the query when it cannot)
                 uint64_t full = __ballot(want && cnt == segcap);
                 if (full != 0ull) {
@@ -3402,6 +3445,9 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
         buf ^= 1u;
     }
     if (owns) O.counts[slot] = s0 + cnt;
+    if constexpr (EXCL) {
+        if (wave_active) hvs_count_refused(lane, counters);  // (wave-uniform)
+    }
     if (count && wave_active) {
         const uint64_t hm = __ballot(have_q);
 #pragma unroll
@@ -3418,13 +3464,14 @@ __device__ __forceinline__ void hvs_scan_rows_into_lists(const float* __restrict
 // per SIMD, so here it is also workgroups per CU -- a change of the block size changes the register budget with it.  Two,
 // where hvs_k_scan_exact_lds has three: beside the exact engine's row loop a lane keeps its segment's place, room and fill,
 // which at three -- 168 registers -- spilled 4 to 8 of them; the kernel runs once per batch over a few thousand rows)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false>
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restrict__ D, const float* __restrict__ Q,
                                                                          HvsBatch B, HvsTailOut O, uint32_t tail_lo, uint32_t tail_hi,
                                                                          unsigned long long* __restrict__ counters, int count,
-                                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
+                                                                         const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo,
+                                                                         HvsExcl excl)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, HVS_CNT_TAIL_PAIRS, AFTER>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live, after_lo);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, false, HVS_CNT_TAIL_PAIRS, AFTER, EXCL>(D, Q, B, O, nullptr, tail_lo, tail_hi, counters, count, live, after_lo, excl);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3436,11 +3483,12 @@ __global__ __launch_bounds__(256, 2) void hvs_k_scan_tail(const float* __restric
 // row is dead to the index only) on that id.
 // counters (`count` != 0): HVS_CNT_PAIRS passing pairs, HVS_CNT_STALE_PAIRS pairs evaluated, HVS_CNT_STALE_KEYS keys admitted.
 // ---------------------------------------------------------------------------------------------
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false>
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256, 2) void hvs_k_scan_stale(const float* __restrict__ D, const float* __restrict__ Q, HvsBatch B,
                                                            HvsTailOut O, const uint32_t* __restrict__ stale_ids, uint32_t m,
                                                            unsigned long long* __restrict__ counters, int count,
-                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo)
+                                                           const uint32_t* __restrict__ live, const uint64_t* __restrict__ after_lo,
+                                                           HvsExcl excl)
 {
-    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, HVS_CNT_STALE_PAIRS, AFTER>(D, Q, B, O, stale_ids, 0u, m, counters, count, live, after_lo);
+    hvs_scan_rows_into_lists<SCALAR_ORDER, CAP, MASKED, true, HVS_CNT_STALE_PAIRS, AFTER, EXCL>(D, Q, B, O, stale_ids, 0u, m, counters, count, live, after_lo, excl);
 }

@@ -193,6 +193,158 @@ __global__ void hvs_k_after_from_results(const uint32_t* __restrict__ out_ids, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-query exclusion lists (hvs_set_exclude_ids / hvs_query_excluding): a set of row ids per resident query; a
+// row takes part in the query's answer only if its id is not in the set.  The caller's CSR is put on the device as it is
+// (hvs_k_check_exclude looks at the offsets, the host reads the status block back and refuses before anything changes), then
+// hvs_k_norm_exclude sorts every list and drops what cannot name a row, IN PLACE: the normalised list of query q lies at
+// ids[begin[q] .. begin[q] + count[q]), ascending and without duplicates, begin[q] = offsets[q] - offsets[0].  hvs_exclude_norm_row
+// is the arithmetic of one list on the host (hvs_exclude_plan), which the kernel reproduces bit for bit.
+// Kernels that honour lists are the EXCL = true instantiations of the CURSOR forms (EXCL requires AFTER: lists without cursors
+// run them with an after_lo of zeros, which admits every key).  Like a cursor a list is tested at EVERY admission into a
+// candidate list -- the keys it refuses are in the middle of the key order, not at its end -- but only for a key that every
+// other test has admitted (hvs_refuse_listed), so it costs nothing per scanned row.  A listed id is only ever compared with a
+// row's id: nothing is indexed with it.
+// ---------------------------------------------------------------------------------------------
+#define HVS_EXCLUDE_MAX_ 1024u  // (= HVS_EXCLUDE_MAX of include/hvs.h; hvs.hip asserts it)
+#define HVS_EXCL_BAD_FIRST 1u   // status flags: offsets[0] != 0
+#define HVS_EXCL_BAD_ORDER 2u   // ... a descending pair of offsets
+#define HVS_EXCL_BAD_LONG 4u    // ... a list of more than HVS_EXCLUDE_MAX entries
+struct HvsExcl {
+    const uint32_t* __restrict__ begin;  // per resident query (under category sets: per sub-query, its parent's pair)
+    const uint32_t* __restrict__ count;
+    const uint32_t* __restrict__ ids;
+};
+// an id takes part in a list normalised for rows [row0, row0 + n_rows): not the empty slot's id, and inside the window
+__host__ __device__ __forceinline__ bool hvs_exclude_keeps(uint32_t id, uint32_t row0, uint32_t n_rows)
+{
+    return id != 0xFFFFFFFFu && id >= row0 && (uint64_t)id < (uint64_t)row0 + n_rows;
+}
+// status[0] |= flags, status[1] = offsets[0], status[2] = offsets[nq] (to be trusted only if no flag is set).  `first`: the
+// offsets are the head of the caller's array (a slice further in starts anywhere).
+__global__ void hvs_k_check_exclude(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t flags = 0u;
+    if (q == 0u) {
+        if (first && off[0] != 0u) flags |= HVS_EXCL_BAD_FIRST;
+        status[1] = off[0];
+        status[2] = off[nq];
+    }
+    if (q < nq) {
+        const uint32_t a = off[q], b = off[q + 1u];
+        if (b < a)
+            flags |= HVS_EXCL_BAD_ORDER;
+        else if (b - a > HVS_EXCLUDE_MAX_)
+            flags |= HVS_EXCL_BAD_LONG;
+    }
+    if (flags) atomicOr(&status[0], flags);
+}
+// One wave per query, four queries per block, the list in LDS (4 KB per wave): ids that name no row of the window leave as
+// 0xFFFFFFFF (which sorts last), the rest minus row0 are sorted by a bitonic network over the next power of two >= 64, then
+// the first of every run of equal ids is kept by a ballot compaction and written back over the raw list; what is left of the
+// raw length is filled with 0xFFFFFFFF, so that the whole id array is defined.  The offsets were checked: len <= 1024.
+__global__ __launch_bounds__(256) void hvs_k_norm_exclude(const uint32_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ ids,
+                                                          uint32_t row0, uint32_t n_rows, uint32_t* __restrict__ begin,
+                                                          uint32_t* __restrict__ count)
+{
+    __shared__ uint32_t sids[4][HVS_EXCLUDE_MAX_];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= nq) return;  // wave-uniform; waves never meet at a barrier
+    uint32_t* s = sids[threadIdx.x >> 6];
+    const uint32_t base = off[q] - off[0];
+    uint32_t len = off[q + 1u] - off[q];
+    if (len > HVS_EXCLUDE_MAX_) len = HVS_EXCLUDE_MAX_;  // (refused by the host before this launch; never trusted here)
+    uint32_t* __restrict__ mine = ids + base;
+    uint32_t P = 64u;
+    while (P < len) P <<= 1;
+    for (uint32_t e = lane; e < P; e += 64u) {
+        const uint32_t id = e < len ? mine[e] : 0xFFFFFFFFu;
+        s[e] = hvs_exclude_keeps(id, row0, n_rows) ? id - row0 : 0xFFFFFFFFu;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (uint32_t k = 2u; k <= P; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            for (uint32_t i = lane; i < P; i += 64u) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t a = s[i], b = s[l];
+                    if ((a > b) == ((i & k) == 0u)) {
+                        s[i] = b;
+                        s[l] = a;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+    }
+    uint32_t kept = 0;
+    for (uint32_t off0 = 0; off0 < len; off0 += 64u) {  // (wave-uniform; s[e] for e >= len is 0xFFFFFFFF after the sort)
+        const uint32_t e = off0 + lane;
+        const uint32_t id = e < len ? s[e] : 0xFFFFFFFFu;
+        const bool in = id != 0xFFFFFFFFu && (e == 0u || s[e - 1u] != id);
+        const uint64_t m = __ballot(in);
+        if (in) mine[kept + hvs_prefix_count(m)] = id;
+        kept += (uint32_t)__popcll(m);
+    }
+    for (uint32_t e = kept + lane; e < len; e += 64u) mine[e] = 0xFFFFFFFFu;
+    if (lane == 0u) {
+        begin[q] = base;
+        count[q] = kept;
+    }
+}
+// under category sets every sub-query reads its parent's list: the pair is copied, the ids are not
+__global__ void hvs_k_expand_exclude(const uint32_t* __restrict__ parent, uint32_t nsub, const uint32_t* __restrict__ ubegin,
+                                     const uint32_t* __restrict__ ucount, uint32_t* __restrict__ begin, uint32_t* __restrict__ count)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nsub) return;
+    begin[i] = ubegin[parent[i]];
+    count[i] = ucount[parent[i]];
+}
+// the admission test: is `id` in the ascending list ids[0 .. count)?  A branch-light lower bound over at most 1024 entries.
+__device__ __forceinline__ bool hvs_excluded(const uint32_t* __restrict__ ids, uint32_t count, uint32_t id)
+{
+    if (count == 0u) return false;
+    uint32_t lo = 0u, n = count;  // the last entry <= id, if there is one, lies in [lo, lo + n)
+    while (n > 1u) {
+        const uint32_t half = n >> 1;
+        lo = ids[lo + half] <= id ? lo + half : lo;
+        n -= half;
+    }
+    return ids[lo] == id;
+}
+// ... for a key of query `qi` that every other test has admitted.  Refused keys are counted per wave in LDS and handed over
+// once at the end of the kernel (one atomic per refused key on the one global counter cost as much again as the whole call at
+// 10^8 refused keys).  The LDS words belong to hvs_refused_slot, so they exist in the kernels that call it -- the list forms --
+// and in no other: the plain and the cursor forms declare nothing for this and keep their code to the instruction.
+// hvs_refused_begin: first thing in a list form; hvs_count_refused: where the wave has converged at its end.
+__device__ __forceinline__ uint32_t* hvs_refused_slot()
+{
+    __shared__ uint32_t sref[16];  // one word per wave of the workgroup
+    return &sref[threadIdx.x >> 6];
+}
+__device__ __forceinline__ void hvs_refused_begin(uint32_t lane)
+{
+    if (lane == 0u) *hvs_refused_slot() = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (LDS operations of one wave execute in order)
+}
+__device__ __forceinline__ bool hvs_refuse_listed(const HvsExcl& x, uint32_t qi, uint32_t id)
+{
+    if (!hvs_excluded(x.ids + x.begin[qi], x.count[qi], id)) return false;
+    atomicAdd(hvs_refused_slot(), 1u);
+    return true;
+}
+__device__ __forceinline__ void hvs_count_refused(uint32_t lane, unsigned long long* __restrict__ counters)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (lane == 0u) {
+        const uint32_t n = *hvs_refused_slot();
+        if (n) atomicAdd(&counters[HVS_CNT_EXCL_REFUSED], (unsigned long long)n);  // (hvs_exclude_info.refused_keys)
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Synthetic inputs generated in HBM (include/hvs_gen.h), one thread per element.
 // ---------------------------------------------------------------------------------------------
 // `first_row`: out[0] is element 0 of that row of the stream (a part of a row-partitioned context generates its own rows)
@@ -354,15 +506,18 @@ struct HvsLdsRow1 {
 // `sn` is then the cut id of the sampled live prefix (hvs_mask_plan)
 // CAPPED: admission gains `dist <= caps[query]` beside the threshold test (`caps` is not read otherwise)
 // AFTER: ... and `key >= after_lo[query]` (result cursors; `after_lo` is not read otherwise)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
+// EXCL (a cursor form only): ... and the row's id is not in the query's exclusion list (`excl` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
     const float* __restrict__ D, const float* __restrict__ Q, const uint32_t* __restrict__ qorder, uint32_t nq,
     uint32_t nq_pad, uint32_t sn, uint32_t rows_per_chunk, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt,
     unsigned long long* __restrict__ counters, uint32_t knn, const uint32_t* __restrict__ live, const float* __restrict__ caps,
-    const uint64_t* __restrict__ after_lo)
+    const uint64_t* __restrict__ after_lo, HvsExcl excl)
 {
+    static_assert(!EXCL || AFTER, "the list forms exist on the cursor forms only");
     __shared__ float4 srow[2][HVS_LDS_ROWS * HVS_LDS_ROW_F / 4];
     const uint32_t lane = threadIdx.x & 63u;
+    if constexpr (EXCL) hvs_refused_begin(lane);
     const uint32_t qwave = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t slot = qwave * 64u + lane;
     const uint32_t chunk = blockIdx.y;
@@ -470,6 +625,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
                 bool admit = pass && !(dist >= tau);
                 if constexpr (CAPPED) admit = admit && dist <= cap;
                 if constexpr (AFTER) admit = admit && hvs_make_key(dist, j0 + r) >= lo;
+                if constexpr (EXCL) {
+                    if (admit && hvs_refuse_listed(excl, qi, j0 + r)) admit = false;
+                }
                 if (admit) {
                     mylist[cnt] = hvs_make_key(dist, j0 + r);
                     ++cnt;
@@ -496,6 +654,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
         buf ^= 1u;
     }
     if (have_q) cand_cnt[(size_t)chunk * nq_pad + slot] = cnt;
+    if constexpr (EXCL) {
+        if (wave_active) hvs_count_refused(lane, counters);  // (wave-uniform)
+    }
     if (wave_active && lane == 0u) {
         atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)npass);
         atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)nscan);
@@ -562,17 +723,45 @@ __device__ __forceinline__ uint32_t hvs_keep_after(uint64_t* buf, uint32_t cnt, 
     return kept;
 }
 
+// The final kernels' share of the exclusion lists (hvs_k_select, hvs_k_merge with EXCL): as for the cursors every stage in front
+// admits unlisted keys only, so this drops nothing -- it tests defensively and counts for hvs_exclude_info:
+// HVS_CNT_EXCL_SLOTS += slots kept, HVS_CNT_EXCL_UNDERFULL += 1 for an under-full query.
+__device__ __forceinline__ uint32_t hvs_keep_unlisted(uint64_t* buf, uint32_t cnt, const HvsExcl& x, uint32_t qi, uint32_t knn, uint32_t lane,
+                                                      unsigned long long* __restrict__ counters, bool count)
+{
+    const uint32_t* __restrict__ lst = x.ids + x.begin[qi];
+    const uint32_t n = x.count[qi];
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    uint32_t kept = 0;
+    for (uint32_t off = 0; off < cnt; off += 64u) {  // (wave-uniform; a chunk's keys land at or below their own places)
+        const uint32_t e = off + lane;
+        const uint64_t key = e < cnt ? buf[e] : 0ull;
+        const bool in = e < cnt && !hvs_excluded(lst, n, hvs_key_id(key));
+        const uint64_t m = __ballot(in);
+        if (in) buf[kept + hvs_prefix_count(m)] = key;
+        kept += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (count && lane == 0u) {
+        if (kept) atomicAdd(&counters[HVS_CNT_EXCL_SLOTS], (unsigned long long)kept);
+        if (kept < knn) atomicAdd(&counters[HVS_CNT_EXCL_UNDERFULL], 1ull);
+    }
+    return kept;
+}
+
 // MASKED: the padding ids come from `pad_ids` (the last k live rows, descending) instead of n - 1, n - 2, ...
 // CAPPED: keys beyond caps[query] leave before the padding (hvs_keep_within; `caps` and `counters` are not read otherwise)
 // AFTER: keys in front of after_lo[query] likewise (hvs_keep_after; `after_lo` is not read otherwise)
-template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false>
+// EXCL (a cursor form only): keys of listed rows likewise (hvs_keep_unlisted; `excl` is not read otherwise)
+template <bool SCALAR_ORDER, int CAP, bool MASKED, bool CAPPED = false, bool AFTER = false, bool EXCL = false>
 __global__ __launch_bounds__(256) void hvs_k_select(
     const float* __restrict__ D, uint32_t n, const float* __restrict__ Q, const uint32_t* __restrict__ qorder,
     uint32_t nq, uint32_t nq_pad, uint32_t nchunks, const uint64_t* __restrict__ cand,
     const uint32_t* __restrict__ cand_cnt, int pad, uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
     const uint32_t* __restrict__ pad_ids, const float* __restrict__ caps, unsigned long long* __restrict__ counters,
-    const uint64_t* __restrict__ after_lo)
+    const uint64_t* __restrict__ after_lo, HvsExcl excl)
 {
+    static_assert(!EXCL || AFTER, "the list forms exist on the cursor forms only");
     __shared__ uint64_t sbuf[4][CAP];
     __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
     const uint32_t lane = threadIdx.x & 63u;
@@ -607,6 +796,7 @@ __global__ __launch_bounds__(256) void hvs_k_select(
     }
     if constexpr (CAPPED) cnt = hvs_keep_within(buf, cnt, caps[qi], knn, lane, counters, true);
     if constexpr (AFTER) cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, true);
+    if constexpr (EXCL) cnt = hvs_keep_unlisted(buf, cnt, excl, qi, knn, lane, counters, true);
     // padding: fewer than 100 matching rows in [0,sn)
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
     for (uint32_t base = cnt; base < knn; base += 64u) {

@@ -109,7 +109,17 @@ class InInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ExcludeInfo(C.Structure):
+    """hvs_exclude_info (include/hvs.h)."""
+    _fields_ = [("excluding_queries", C.c_uint32), ("underfull_queries", C.c_uint32), ("kept_slots", C.c_uint64),
+                ("refused_keys", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
+EXCLUDE_MAX = 1024
 
 
 def library_path():
@@ -273,6 +283,12 @@ def library():
         "hvs_in_plan": (C.c_uint32, [_f32p, _u32p, _f32p, C.c_uint32, _u32p, _u32p, _f32p]),
         "hvs_set_category_sets_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "hvs_download_in_plan": (C.c_int, [vp, _u32p, _u32p, _f32p, C.c_uint32]),
+        "hvs_set_exclude_ids": (C.c_int, [vp, _u32p, _u32p, C.c_uint32]),
+        "hvs_set_exclude_ids_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "hvs_query_excluding": (C.c_int, [vp, _f32p, _u32p, _u32p, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_exclude_stats": (C.c_int, [vp, C.POINTER(ExcludeInfo)]),
+        "hvs_download_exclude_plan": (C.c_int, [vp, _u32p, _u32p, _u32p, C.c_uint32]),
+        "hvs_exclude_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -406,6 +422,40 @@ def within_plan(ids, dists, max_d2, pad_ids=None, pad_dists=None, padding=True):
     library().hvs_within_plan(_up(ids), _fp(dists), k, C.c_float(max_d2), _up(pad_ids) if padding else None,
                               _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids), _fp(out_d), C.byref(n_in))
     return out_ids, out_d, int(n_in.value)
+
+
+def _exclude_csr(lists):
+    """Exclusion lists as a CSR pair of uint32 arrays: a LIST of per-query id sequences, or an (offsets, ids) TUPLE."""
+    if isinstance(lists, tuple) and len(lists) == 2:
+        off = np.ascontiguousarray(lists[0], np.uint32).ravel()
+        ids = np.ascontiguousarray(lists[1], np.uint32).ravel()
+    else:
+        rows = [np.asarray(r, np.uint32).ravel() for r in lists]
+        off = np.zeros(len(rows) + 1, np.uint32)
+        if rows:
+            off[1:] = np.cumsum([r.size for r in rows])
+        ids = np.ascontiguousarray(np.concatenate(rows) if rows else np.empty(0, np.uint32), np.uint32)
+    if off.size == 0:
+        raise HvsError(-1, "exclusion lists: the offsets need nq + 1 entries")
+    if ids.size == 0:
+        ids = np.zeros(1, np.uint32)  # (a valid pointer for an empty id array)
+    return off, ids
+
+
+def exclude_plan(lists, row0=0, n_rows=0xFFFFFFFF):
+    """hvs_exclude_plan: exclusion lists (a list of per-query id sequences, or an (offsets, ids) pair) normalised for rows
+    [row0, row0 + n_rows) -> (kept, begin, count, ids), or None when the offsets are refused (nothing is written then)."""
+    off, ids = _exclude_csr(lists)
+    nq = off.size - 1
+    begin, count = np.full(nq + 1, 0xFFFFFFFF, np.uint32), np.full(nq + 1, 0xFFFFFFFF, np.uint32)
+    total = int(off[-1]) if nq and off[-1] >= off[0] and off[-1] <= ids.size else 0
+    out = np.full(total + 1, 0xFFFFFFFF, np.uint32)
+    kept = library().hvs_exclude_plan(_up(off), _up(ids), nq, int(row0), int(n_rows), _up(begin), _up(count), _up(out))
+    if kept == 0xFFFFFFFF:
+        if (begin != 0xFFFFFFFF).any() or (count != 0xFFFFFFFF).any() or (out != 0xFFFFFFFF).any():
+            raise HvsError(-1, "hvs_exclude_plan wrote its outputs although it refused the lists")
+        return None
+    return int(kept), begin[:nq].copy(), count[:nq].copy(), out[:total].copy()
 
 
 def after_plan(ids, dists, k, after_dist, after_id, pad_ids=None, pad_dists=None, padding=True):
@@ -697,11 +747,12 @@ class Engine:
         self._ck(self._lib.hvs_trim_rows(self._h))
 
     # --- the vec_query seam
-    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None):
+    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None, exclude=None):
         """hvs_query: host rows in, host ids (and distances) out.  `out_ids` / `out_dists`: caller-provided arrays
         (e.g. views of pinned memory) to be filled instead of fresh ones.  `max_dist2`: one squared-distance cap per query
         (hvs_query_within: the k nearest rows within it); None = no caps.  `after`: (dists, ids), one result cursor per query
-        (hvs_query_after: the k nearest rows after that key); None = no cursors."""
+        (hvs_query_after: the k nearest rows after that key); None = no cursors.  `exclude`: one exclusion list per query, a
+        list of id sequences or an (offsets, ids) pair (hvs_query_excluding: the k nearest rows not in it); None = no lists."""
         q = np.ascontiguousarray(q_rows, np.float32)
         if q.ndim != 2 or q.shape[1] != QCOLS:
             raise HvsError(-1, "query rows must be nq x 104 float32")
@@ -717,11 +768,21 @@ class Engine:
             caps = np.ascontiguousarray(max_dist2, np.float32).ravel()
             if caps.size != nq:
                 raise HvsError(-1, "max_dist2 must hold one float32 per query")
+        ad = ai = None
         if after is not None:
             ad = np.ascontiguousarray(after[0], np.float32).ravel()
             ai = np.ascontiguousarray(after[1], np.uint32).ravel()
             if ad.size != nq or ai.size != nq:
                 raise HvsError(-1, "after must be (dists, ids) with one entry per query each")
+        if exclude is not None:
+            eo, ei = _exclude_csr(exclude)
+            if eo.size != nq + 1:
+                raise HvsError(-1, "exclude must hold one list per query")
+            self._ck(self._lib.hvs_query_excluding(self._h, _fp(q), _up(eo), _up(ei), _fp(ad) if ad is not None else None,
+                                                   _up(ai) if ai is not None else None, _fp(caps) if caps is not None else None, nq,
+                                                   sample_proportion, _up(ids), _fp(d) if d is not None else None))
+            self._excl_nq = nq
+        elif after is not None:
             self._ck(self._lib.hvs_query_after(self._h, _fp(q), _fp(ad), _up(ai), _fp(caps) if caps is not None else None, nq,
                                                sample_proportion, _up(ids), _fp(d) if d is not None else None))
         elif caps is None:
@@ -808,6 +869,47 @@ class Engine:
             return out_i, out_d
         finally:
             self.set_padding(was)
+
+    # --- per-query exclusion lists (include/hvs.h "per-query exclusion lists")
+    def set_exclude_ids(self, lists, stream=None):
+        """Attach one exclusion list per resident query: a list of per-query id sequences or an (offsets, ids) pair of host
+        arrays (hvs_set_exclude_ids), an (offsets, ids) pair of GPU tensors (hvs_set_exclude_ids_device: int32 / uint32,
+        contiguous, offsets with nq + 1 entries; `stream` as for set_queries_device), or None to remove the lists.  Any call
+        that replaces the resident queries, and attaching or removing category sets, removes them too."""
+        if lists is None:
+            self._ck(self._lib.hvs_set_exclude_ids(self._h, None, None, 0))
+        elif isinstance(lists, tuple) and len(lists) == 2 and all(hasattr(x, "data_ptr") and hasattr(x, "shape") for x in lists):
+            po, n = _device_u32(lists[0], "set_exclude_ids")
+            pi, _ = _device_u32(lists[1], "set_exclude_ids")
+            self.set_exclude_ids_device(po, pi, max(n, 1) - 1, stream=stream)
+        else:
+            off, ids = _exclude_csr(lists)
+            self._ck(self._lib.hvs_set_exclude_ids(self._h, _up(off), _up(ids), off.size - 1))
+            self._excl_nq = off.size - 1
+
+    def set_exclude_ids_device(self, offsets_ptr, ids_ptr, nq, stream=None):
+        """hvs_set_exclude_ids_device from two raw pointers (0 / None = NULL) and the number of queries."""
+        po, pi = int(offsets_ptr or 0), int(ids_ptr or 0)
+        self._ck(self._lib.hvs_set_exclude_ids_device(self._h, C.c_void_p(po) if po else None, C.c_void_p(pi) if pi else None, int(nq),
+                                                      _stream_ptr(stream)))
+        self._excl_nq = int(nq)
+
+    def exclude_stats(self):
+        """hvs_exclude_stats: queries run under lists, under-full ones, non-pad slots and refused keys of the last call."""
+        e = ExcludeInfo()
+        self._ck(self._lib.hvs_exclude_stats(self._h, C.byref(e)))
+        return e
+
+    def exclude_plan_device(self, nq=None):
+        """hvs_download_exclude_plan: (total, begin, count, ids) of the normalised lists of the resident queries as they lie
+        on the device, whichever way they were attached (one-GPU contexts).  `nq`: the number of resident queries (None: that
+        of the last set_exclude_ids / query(exclude=) of this object)."""
+        nq = getattr(self, "_excl_nq", 0) if nq is None else nq
+        total = self._lib.hvs_download_exclude_plan(self._h, None, None, None, 0)
+        self._ck(min(total, 0))
+        begin, count, ids = np.empty(int(nq), np.uint32), np.empty(int(nq), np.uint32), np.empty(max(total, 1), np.uint32)
+        self._ck(min(self._lib.hvs_download_exclude_plan(self._h, _up(begin), _up(count), _up(ids), total), 0))
+        return int(total), begin, count, ids[:total].copy()
 
     # --- category sets (include/hvs.h "category sets")
     def set_category_sets(self, sets, stream=None):
