@@ -5102,10 +5102,20 @@ int hvs_query_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_propor
 {
     if (!c) return HVS_EINVAL;
     if (c->partitioned) return part_run(c, q0, nq, sample_proportion);
-    if (!c->kids.empty())
-        return for_each_resident_part(c, q0, nq, [&](hvs_ctx* k, uint32_t lq0, uint32_t m, uint32_t) {
-            return leaf_run_resident(k, lq0, m, sample_proportion);
+    if (!c->kids.empty()) {
+        if (c->kid_q0.size() != c->kids.size() + 1u || (uint64_t)q0 + nq > c->kid_q0.back())
+            return fail(c, HVS_EINVAL, "query range outside the resident query set");
+        if (nq == 0u) return HVS_OK;
+        // a GPU that holds none of the range's queries takes no part in this call: what it counted for an earlier call is not
+        // this call's (call_stats sums the leaves whose call is valid), as in hvs_query for a GPU that got no queries
+        return for_each_leaf(c, [&](uint32_t r) -> int {
+            hvs_ctx* k = c->kids[r];
+            const uint32_t a = std::max(q0, c->kid_q0[r]), b = std::min(q0 + nq, c->kid_q0[r + 1]);
+            if (a < b) return leaf_run_resident(k, a - c->kid_q0[r], b - a, sample_proportion);
+            const int rc = resolve_overflow(k);  // (an earlier call's re-runs, if it was never waited for)
+            return rc ? rc : call_forgotten(k);
         });
+    }
     return leaf_run_resident(c, q0, nq, sample_proportion);
 }
 

@@ -41,7 +41,7 @@ and `hi` est >= theta - mu_q, theta rounded down to f32 as the kernel does.
 Grid edges.  The device takes log2((b - a) / seen) with __log2f; a query whose 8 log2(.) - 0.02 lies within 1e-3 of an integer
 at any level where the guess table is consulted is `excluded`: the model cannot say which grid point the device read.
 
-Attachments (walk's caps=, after=, live=; all None: the walk above, to the unit).  Each rule with the code it restates:
+Attachments (walk's caps=, after=, live=, excl=; all None: the walk above, to the unit).  Each rule with the code it restates:
 
 Caps.
 * hvs_k_norm_caps stores hvs_norm_cap(cap) (`c >= 0.0f ? c : HVS_CAP_NOTHING`): a NaN or negative cap is -1.  hvs_k_prep<true>
@@ -85,10 +85,29 @@ Mask.
   (`c->d_data, n, o.perm`, no mask) and patch_tiles runs behind it; set_quant's hvs_k_minmax / hvs_k_quant_params walk all
   indexed rows likewise.  bound_model is therefore fed all rows, whatever the mask.
 
+Lists (walk's excl=, one raw id array per query).
+* Normalisation is tests/exclude_model.py's (normalise: 0xFFFFFFFF dropped, np.unique of the rest), not the library's.
+* Admission is the old test AND "id not listed", evaluated last (hvs_refuse_listed: "only for a key that every other test has
+  admitted").  Chunked hvs_k_seed_exact (nchunks > 1, both passes of a 112-query batch): `bool admit = pass && key >= key_lo;` then
+  `if (admit && hvs_refuse_listed(excl, qi, id)) admit = false;` behind `if (id >= sn) continue;` and the liveness test -- no tau
+  test.  hvs_k_rescore: `pend[u] = ok[u] && t4 == 0u && dist <= B.tau[slot[u]];`, then `pend_key[u] >= lo[qa]`, then
+  `if (pend[u] && hvs_refuse_listed(hvs_second_arg(after_lo...), qa, id[u])) pend[u] = false;`.  Final merge: hvs_keep_unlisted
+  behind hvs_keep_within and hvs_keep_after; it drops and counts slots, it refuses nothing.
+* Lists without cursors run the cursor forms with an after_lo of zeros (`zero_after_lo`, "which admits every key"): cand[0] counts
+  every unlisted row of the range at level 0 (one place per admitted key), as under cursors.
+* rescored_pairs is counted before admission (`npairs += cnt` in front of score_list), unchanged.  hvs_guess_m sees ra, rb only:
+  F is not thinned by the lists.  The retry pass runs the same list forms: proven over unlisted keys.
+* `refused` [nq], first pass plus retry pass: what hvs_refuse_listed counts (hvs_exclude_info.refused_keys) -- keys in the range,
+  `id < sn`, live, behind the cursor, `dist <= tau` at levels >= 1 (every such row is a survivor: the bound of
+  tests/test_filter_bounds.py; level 0 of the chunked seed takes no tau test), whose id is listed.  A query that the exact engine
+  answers contributes nothing here (its refusals are counted through HVS_CNT_RERUN_SINK: slot 26).
+
 Wrong rules (walk's wrong=, one of WRONG; tests/test_selectivity_model_cpu.py shows that each would be seen): cap_ignored (tau
 starts at +inf, the final kernel still drops), cap_retry_from_inf, cap_check_inf (`tau == +inf` in the capped check),
 cap_level1_only (theta falls back to "keep everything" behind a merge that returned early), after_in_lists, after_F_behind,
-mask_unpatched, mask_F_live, mask_in_stat.
+mask_unpatched, mask_F_live, mask_in_stat, excl_in_lists (listed keys enter the lists and the order statistics, only the final
+kernel drops them), excl_seed_only (level 0 refuses, hvs_k_rescore does not), excl_retry_dropped (the retry pass runs without
+lists).
 """
 from __future__ import annotations
 
@@ -359,7 +378,7 @@ HVS_CAP_NOTHING = np.float32(-1.0)
 HVS_AFTER_NOTHING = 0xFFFFFFFFFFFFFFFF
 NAN_BITS = 0x7FC00000
 WRONG = ("cap_ignored", "cap_retry_from_inf", "cap_check_inf", "cap_level1_only", "after_in_lists", "after_F_behind", "mask_unpatched",
-         "mask_F_live", "mask_in_stat")
+         "mask_F_live", "mask_in_stat", "excl_in_lists", "excl_seed_only", "excl_retry_dropped")
 
 
 def norm_cap(c):
@@ -394,13 +413,16 @@ def _f32_bits(x):
     return int(np.array([x], np.float32).view(np.uint32)[0])
 
 
-def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None, live=None, wrong=None, retry=False):
-    """One batch's walk of query q: dict(lo, hi, dead_lo, dead_hi [K], cand [K + 1], fails, overflow, edge, keys).
-    cap: the query's cap as the caller gave it, or None; lo_key: hvs_after_lo of its cursor, or None; live: bool [n], or None."""
+def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None, live=None, wrong=None, retry=False, listed=None):
+    """One batch's walk of query q: dict(lo, hi, dead_lo, dead_hi [K], cand [K + 1], fails, overflow, edge, keys, refused).
+    cap: the query's cap as the caller gave it, or None; lo_key: hvs_after_lo of its cursor, or None; live: bool [n], or None;
+    listed: the query's normalised exclusion list (ascending ids), or None."""
     ordn, a, b = P.ranges[q]
     K = L.K
     out = dict(lo=np.zeros(K, np.int64), hi=np.zeros(K, np.int64), dead_lo=np.zeros(K, np.int64), dead_hi=np.zeros(K, np.int64),
-               cand=np.zeros(K + 1, np.int64), fails=False, overflow=False, edge=False, keys=np.empty(0, np.uint64))
+               cand=np.zeros(K + 1, np.int64), fails=False, overflow=False, edge=False, keys=np.empty(0, np.uint64), refused=0)
+    if retry and wrong == "excl_retry_dropped":
+        listed = None
     if P.hopeless[q] or b <= a:
         return out
     ids = (P.ord.perm_t if ordn else P.ord.perm_ct)[a:b]
@@ -416,6 +438,7 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
     behind = np.ones(ids.size, bool) if lo_key is None else keys >= np.uint64(lo_key)
     if wrong != "after_in_lists":
         adm = adm & behind
+    named = np.zeros(ids.size, bool) if listed is None else np.isin(ids, listed)       # hvs_excluded
     capf = None if cap is None else norm_cap(cap)
     walk_cap = capf                                       # the cap as far as thresholds and the final check know it
     if wrong == "cap_ignored" or (retry and wrong == "cap_retry_from_inf"):
@@ -434,9 +457,15 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
             d_at = score[at & ~alive]
             out["dead_lo"][j - 1] = int((d_at >= th + w).sum())
             out["dead_hi"][j - 1] = int((d_at >= th - w).sum())
-        within = at & adm & (dist <= tau)
+        # every test in front of the list, then the list (level 0: the chunked seed takes no threshold test)
+        refuses = wrong != "excl_in_lists" and not (j > 0 and wrong == "excl_seed_only")
+        asked = at & adm if j == 0 else at & adm & (dist <= tau)
+        if refuses:
+            out["refused"] += int((asked & named).sum())
+        adm_j = adm & ~named if refuses else adm
+        within = at & adm_j & (dist <= tau)
         # level 0: the chunked seed (a batch of 112 queries: seed_chunks > 1) appends without a threshold test
-        out["cand"][j] = int((at & adm).sum()) if j == 0 else int(within.sum())
+        out["cand"][j] = int((at & adm_j).sum()) if j == 0 else int(within.sum())
         out["overflow"] |= out["cand"][j] > fcap
         held = np.sort(np.concatenate([held, keys[within]]))[:k]
         if j < K:
@@ -463,8 +492,17 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
         held = held[key_dists(held) <= capf]
     if lo_key is not None:              # hvs_keep_after
         held = held[held >= np.uint64(lo_key)]
+    if listed is not None:              # hvs_keep_unlisted
+        held = held[~np.isin(key_ids(held), listed)]
     out["keys"] = held
     return out
+
+
+def normalised(raw):
+    """One query's list as the kernels read it: exclude_model.normalise (0xFFFFFFFF dropped, ascending, no duplicates)."""
+    import exclude_model as XM
+    _, _, count, ids = XM.normalise([np.asarray(raw, np.uint32)])
+    return ids[:int(count[0])]
 
 
 def mask_cut(live, sp, n):
@@ -480,7 +518,7 @@ def mask_cut(live, sp, n):
 
 
 def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS_FCAP, prep=None, plan=None, caps=None, after=None,
-         live=None, wrong=None):
+         live=None, wrong=None, excl=None):
     """The model of one call.  Returns a dict of per-query arrays:
       lo, hi [nq, K]      survivor bracket per level of the first pass;      cand [nq, K + 1] keys appended per level
       dead_lo, dead_hi    the part of lo, hi that dead rows make up (hvs_mask_info.dead_survivors)
@@ -489,8 +527,10 @@ def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS
       excluded [nq]       on a grid edge of the guess table;                 exact [nq] answered by the exact engine
       held                list of the final held distances per query (the k smallest of its range when verified)
       held_keys           ... as keys (distance bits << 32 | id): the answer's matched slots, in key order
+      refused [nq]        keys the lists refused at an admission point, first pass plus retry pass (hvs_exclude_info.refused_keys)
     guess: "proven" (HVS_GUESS_MID=256) or "guess" with `pfail` (None: the batch's default) and `mid` (HVS_GUESS_MID).
-    caps [nq] f32, after = (dists [nq], ids [nq]), live bool [n]: the attachments; wrong: one of WRONG (the CPU test only)."""
+    caps [nq] f32, after = (dists [nq], ids [nq]), live bool [n], excl = one raw id array per query: the attachments; wrong: one
+    of WRONG (the CPU test only)."""
     assert wrong is None or wrong in WRONG, wrong
     P = prep if prep is not None else Prepared(fmt, nodes, queries)
     L = levels(P.n, plan=plan)
@@ -503,20 +543,22 @@ def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS
     res = dict(lo=z(nq, K), hi=z(nq, K), cand=z(nq, K + 1), retry_lo=z(nq, K), retry_hi=z(nq, K), retry_cand=z(nq, K + 1),
                dead_lo=z(nq, K), dead_hi=z(nq, K), retry_dead_lo=z(nq, K), retry_dead_hi=z(nq, K),
                fails=np.zeros(nq, bool), overflow=np.zeros(nq, bool), excluded=np.zeros(nq, bool), exact=P.hopeless.copy(), held=[],
-               held_keys=[], K=K, sn=sn)
+               held_keys=[], K=K, sn=sn, refused=z(nq))
     for q in range(nq):
         att = dict(cap=None if caps is None else caps[q], lo_key=None if after is None else after_lo(after[0][q], after[1][q]),
-                   live=live, wrong=wrong)
+                   live=live, wrong=wrong, listed=None if excl is None else normalised(excl[q]))
         r = _pass(P, L, q, k, sn, guess, pfail, mid, band_scale, fcap, **att)
         for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
             res[name][q] = r[name]
         res["fails"][q], res["overflow"][q], res["excluded"][q] = r["fails"], r["overflow"], r["edge"]
+        res["refused"][q] = r["refused"]
         keys = r["keys"]
         if r["fails"] or r["overflow"]:     # retry batch: proven at every level (plan_guess(k, true, .)), longer lists
             r2 = _pass(P, L, q, k, sn, "proven", pfail, mid, band_scale, 1 << 30, retry=True, **att)
             assert wrong is not None or not r2["fails"], "a proven threshold cannot fail its check"
             for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
                 res["retry_" + name][q] = r2[name]
+            res["refused"][q] += r2["refused"]
             keys = r2["keys"]
         res["held_keys"].append(keys)
         res["held"].append(key_dists(keys))
@@ -633,13 +675,16 @@ def case_walk(case, fmt, regime, band_scale=1.0, attach=None, wrong=None):
         att = attachment(case, attach) if attach else {}
         _walk_cache[key] = walk(fmt, nodes, queries, case.k, case.sp, r["guess"], r["pfail"], r["mid"], band_scale,
                                 list_capacity(RESERVE_NQ, queries.shape[0]), prep=case_prep(case, fmt), caps=att.get("caps"),
-                                after=att.get("after"), live=att.get("live"), wrong=wrong)
+                                after=att.get("after"), live=att.get("live"), wrong=wrong, excl=att.get("excl"))
     return _walk_cache[key]
 
 
 # --------------------------------------------------------------------------- attachments of the cases
 
 ATTACH = ("cap_kth", "cap_mixed", "after_p2", "after_deep", "mask", "cap_after", "all")
+EXCL_ATTACH = ("ex_p1", "ex_deep", "ex_scatter", "ex_all")          # the attachments with exclusion lists
+ATTACH = ATTACH + EXCL_ATTACH
+EXCLUDE_MAX = 1024
 # what the GPU test runs under attachments: (case, formats, attachments, regimes, HVS_I8_SHAPE, the band x 1.25 build)
 ATTACH_MATRIX = [
     ("v1_32k", ALL_I8, ATTACH, ("proven", "default", "reckless"), "16", False),
@@ -648,6 +693,14 @@ ATTACH_MATRIX = [
     ("half", (BM.PLAIN_I8,), ("mask", "all"), ("default",), "16", False),
     ("f16", (BM.FP16,), ("cap_kth", "after_p2", "mask"), ("default",), "16", False),
     ("v1_32k", (BM.PLAIN_I8, BM.BF16), ("cap_kth", "after_p2", "mask"), ("default",), "16", True),
+    ("v1_32k", ALL_I8, EXCL_ATTACH, ("proven", "default", "reckless"), "16", False),
+    ("v1_32k", (BM.PLAIN_I8,), ("ex_p1",), ("default",), "32", False),
+    ("v1_70k", (BM.PLAIN_I8,), ("ex_p1", "ex_scatter", "ex_all"), ("default", "reckless"), "16", False),
+    ("half", (BM.PLAIN_I8,), ("ex_deep",), ("default",), "16", False),
+    ("f16", (BM.FP16,), ("ex_p1",), ("default",), "16", False),
+    # the four far queries of `out` go to the exact engine: the re-run sink's refused keys (counter slot 26) are in the sum
+    ("out", (BM.PLAIN_I8,), ("ex_p1",), ("proven", "reckless"), "16", False),
+    ("v1_32k", (BM.PLAIN_I8, BM.BF16), ("ex_p1",), ("default",), "16", True),
 ]
 
 
@@ -694,14 +747,18 @@ def case_fulls(case, live=None):
 
 def expected_keys(case, att):
     """The matched slots of the answers under an attachment, by the laws of tests/within_model.py and tests/after_model.py on
-    full(q) of the live rows: the cap first (after_model.cap_full), then the first k keys behind the cursor (after_model.page)."""
+    full(q) of the live rows: the cap first (after_model.cap_full), then the listed ids dropped (exclude_model.drop_listed), then
+    the first k keys behind the cursor (after_model.page) -- the law of tests/exclude_model.py."""
     import after_model as AM
+    import exclude_model as XM
     fulls = case_fulls(case, att.get("live"))
     out = []
     for q, keys in enumerate(fulls):
         full = (key_ids(keys), key_dists(keys))
         if "caps" in att:
             full = AM.cap_full(full, att["caps"][q])
+        if "excl" in att:
+            full = XM.drop_listed(full, att["excl"][q])
         cur = (att["after"][0][q], att["after"][1][q]) if "after" in att else None
         ids, d, take = AM.page(full, cur, case.k)
         out.append(make_keys(d[:take], ids[:take]))
@@ -710,8 +767,8 @@ def expected_keys(case, att):
 
 def expected_answers(case, att):
     """The padded answers under an attachment, as the library returns them with padding on: expected_keys' matched slots, the
-    empty ones filled from the pad rows (n - 1, n - 2, ..., or the last k live rows under a mask: hvs_mask_plan), all k in key
-    order.  -> (ids [nq, k], dists [nq, k], matched [nq])"""
+    empty ones filled from the pad rows (n - 1, n - 2, ..., or the last k live rows under a mask: hvs_mask_plan; a pad row may be
+    listed), all k in key order.  -> (ids [nq, k], dists [nq, k], matched [nq])"""
     import after_model as AM
     k, live = case.k, att.get("live")
     dist = case_prep(case, case.fmts[0]).dist
@@ -725,14 +782,20 @@ def expected_answers(case, att):
 
 
 def attachment(case, name):
-    """The attachment `name` of a case: dict with some of caps [nq] f32, after = (dists [nq] f32, ids [nq] u32), live [n] bool --
-    and, for the conditions of tests/test_selectivity_model_cpu.py, cap_kind [nq] (index into CAP_KINDS).  Everything is derived
+    """The attachment `name` of a case: dict with some of caps [nq] f32, after = (dists [nq] f32, ids [nq] u32), live [n] bool, excl
+    = one raw u32 id array per query -- and, for the conditions of tests/test_selectivity_model_cpu.py, cap_kind [nq] (index into CAP_KINDS).  Everything is derived
     from full(q) of the unmasked case (the oracle's exact-order distances, every matched key and not only the nearest 256: key
     3 k of after_deep lies behind them) and from the fixed seed MASK_SEED.
 
     Changed against the plain reading, and why: `all` takes the (3 k)-th matched distance as its cap instead of the k-th.  With
     the k-th, no key behind the page-2 cursor lies within the cap (but for ties): no list ever takes a key, tau never leaves the
-    cap, and nothing can be retried -- condition (e') could not hold and the run would check nothing of the three together."""
+    cap, and nothing can be retried -- condition (e') could not hold and the run would check nothing of the three together.
+
+    The lists.  ex_p1: the ids of keys 1..k of full(q) -- what after_p2 answers.  ex_deep: by q % 4 keys 1..3k, keys 1..k, keys
+    1..1024 (the whole neighbourhood of the 150-400 row queries, whose answers are then empty), none; the raw lists are
+    reversed, get one 0xFFFFFFFF and one id >= n appended and carry their ids a second time, each as far as the 1024 raw entries
+    of HVS_EXCLUDE_MAX allow (a list of 1024 keys is full as it is).  ex_scatter: every second key of keys 1..6k.  ex_all: `all`
+    plus every second key, of the live rows, behind its cursor and within its cap."""
     key = (case.name, name)
     if key in _attach_cache:
         return _attach_cache[key]
@@ -788,6 +851,27 @@ def attachment(case, name):
         att["caps"], att["cap_kind"] = caps_mixed()
     if name == "all":
         att["caps"] = caps_kth(ALL_CAP_RANK * k)
+    if name == "ex_all":
+        att.update(attachment(case, "all"))
+        live_fulls = case_fulls(case, att["live"])
+        lists = []
+        for q in range(nq):
+            keys_ = live_fulls[q]
+            sel = (key_dists(keys_) <= norm_cap(att["caps"][q])) & (keys_ >= np.uint64(after_lo(att["after"][0][q], att["after"][1][q])))
+            lists.append(np.ascontiguousarray(key_ids(keys_[sel])[::2][:EXCLUDE_MAX]))
+        att["excl"] = lists
+    if name == "ex_p1":
+        att["excl"] = [key_ids(fulls[q][:k]) for q in range(nq)]
+    if name == "ex_scatter":
+        att["excl"] = [key_ids(fulls[q][:6 * k:2]) for q in range(nq)]
+    if name == "ex_deep":
+        lists = []
+        for q in range(nq):
+            raw = key_ids(fulls[q][:(3 * k, k, EXCLUDE_MAX, 0)[q % 4]])[::-1]
+            extra = np.array([0xFFFFFFFF, case.n + 7], np.uint32)[:max(0, EXCLUDE_MAX - raw.size)]
+            raw = np.concatenate([raw, extra])
+            lists.append(np.ascontiguousarray(np.concatenate([raw, raw[:EXCLUDE_MAX - raw.size]]), np.uint32))
+        att["excl"] = lists
     if name in ("after_p2", "cap_after", "all"):
         att["after"] = cursors(lambda q: cursor(q, k))
     if name == "after_deep":

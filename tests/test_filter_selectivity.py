@@ -111,6 +111,50 @@ keeps every theta finite)
 Band x 1.25 build under attachments, default thresholds, measured and [sum lo, sum hi] of the model with that band:
   v1_32k  i8      cap_kth      14791 [14790, 14791]      after_p2  54133 [54128, 54137]      mask  60635 [60633, 60636]
   v1_32k  bf16    cap_kth      12668 [12660, 12681]      after_p2  47893 [47863, 47924]      mask  54460 [54434, 54485]
+
+Exclusion lists (selectivity_model.EXCL_ATTACH; the walk's rules: that module's docstring, "Lists").  A list is tested
+at every admission point and once more in the final kernel, so an admission test missing in hvs_k_rescore or in the seed, a retry
+batch that runs without the lists, an order statistic drawn from lists that still hold listed keys, or a refused-keys counter that
+drops a pass all return identical bits.  The lists come as a CSR in .npy files and go through Engine.query(exclude=), cut to the
+queries sent.  Per cell, in this order: answers equal to selectivity_model.expected_answers (the law of tests/exclude_model.py) in
+ids and distance bits, the engine and the rotation flag as asked; hvs_exclude_info -- excluding_queries = queries sent, kept_slots
+and underfull_queries as those answers imply, and under ex_all the caps' and cursors' own counts; retry and exact lists exactly;
+rescored_pairs in [sum lo, sum hi] and dead_survivors in its bracket; refused_keys EQUAL to the model's sum of `refused` -- in
+the `out` cells, whose four far queries the exact engine answers, strictly above the filter-answered queries' sum (the re-run
+sink's refused keys, counter slot 26); and the ex_p1 cell's rescored_pairs and retry list equal to those MEASURED for after_p2
+in the same child on the same engine: excluding page 1 re-scores the pairs the page-2 cursor re-scores.
+
+Measured against modelled (MI355X), rescored_pairs [sum lo, sum hi], retried queries in parentheses:
+  case    format  attachment  proven                      default                    reckless (retried)
+  v1_32k  i8      ex_p1       204390 [204388, 204393]     51680 [51676, 51681]        76243 [76240, 76244] (22)
+  v1_32k  i8      ex_deep     229891 [229888, 229897]     79650 [79644, 79655]        87407 [87406, 87410] (12)
+  v1_32k  i8      ex_scatter  224738 [224732, 224741]     65148 [65147, 65151]        77509 [77509, 77509] (18)
+  v1_32k  i8      ex_all       31291 [ 31291,  31293]     31291 [31291, 31293]        31545 [31545, 31547] (1)
+  v1_32k  i8_rot  ex_p1       241478 [241456, 241505]     70381 [70369, 70393]        96826 [96811, 96836] (22)
+  v1_32k  i8_rot  ex_deep     272348 [272318, 272375]    105114 [105094, 105142]     112653 [112638, 112666] (12)
+  v1_32k  i8_rot  ex_scatter  267140 [267114, 267170]     87402 [87384, 87409]       100364 [100355, 100379] (18)
+  v1_32k  i8_rot  ex_all       43730 [ 43723,  43740]     43730 [43723, 43740]        44109 [44102, 44119] (1)
+  v1_32k  bf16    ex_p1       193814 [193757, 193864]     46855 [46824, 46882]        70815 [70777, 70844] (22)
+  v1_32k  bf16    ex_deep     217827 [217768, 217911]     72822 [72786, 72859]        80610 [80579, 80656] (12)
+  v1_32k  bf16    ex_scatter  212964 [212908, 213027]     59207 [59166, 59235]        71354 [71323, 71388] (18)
+  v1_32k  bf16    ex_all       28018 [ 28001,  28036]     28018 [28001, 28036]        28244 [28227, 28262] (1)
+  v1_70k  i8      ex_p1       -                           54554 [54552, 54555]        80078 [80076, 80084] (22)
+  v1_70k  i8      ex_scatter  -                           68558 [68556, 68561]        75807 [75804, 75811] (15)
+  v1_70k  i8      ex_all      -                           32960 [32959, 32961]        35589 [35588, 35590] (10)
+  half    i8      ex_deep     -                          149915 [149912, 149916]      -
+  f16     f16     ex_p1       -                           45212 [45191, 45237]        -
+  out     i8      ex_p1       199158 [199155, 199161]     -                           66680 [66677, 66682] (18)
+(every ex_p1 figure is the after_p2 figure of the tables above, measured in the same child; proven and default retried none; the
+32x32x32 layout gave 51680 under ex_p1 as well.  Under ex_all 85 unlisted keys or fewer lie within the cap, so at n = 32768 no
+threshold ever leaves it under proven and default thresholds and one query is retried under reckless ones; n = 70001 retries 10.)
+refused_keys, measured = modelled in every cell (proven / default / reckless; the same in all three formats of v1_32k):
+  v1_32k  ex_p1 11200 / 11200 / 13400    ex_deep 36796 / 36796 / 40968    ex_scatter 31072 / 23105 / 21067    ex_all 8778 / 8778 / 8846
+  v1_70k  ex_p1 - / 11200 / 13400        ex_scatter - / 23268 / 20104     ex_all - / 8941 / 9592
+  half    ex_deep 35710 (default)        f16  ex_p1 11200 (default)
+  out     ex_p1 11200 (proven) and 13000 (reckless) against 10800 and 12600 of the 108 filter-answered queries: the four far
+          queries' 100 listed rows each were refused by the exact engine's re-run, and counted through the sink
+Band x 1.25 build under ex_p1, default thresholds (refused_keys 11200 as in production):
+  v1_32k  i8      54133 [54128, 54137]      bf16    47893 [47863, 47924]
 """
 import importlib
 import os
@@ -290,22 +334,24 @@ for data, engine, rot, k, sp, cells in spec['engines']:
         for tag in cells:      # (the cells with a mask come last: the mask is set once and stays)
             get = lambda part: np.load(os.path.join(spec['dir'], tag + '.' + part + '.npy')) if os.path.exists(os.path.join(spec['dir'], tag + '.' + part + '.npy')) else None
             keep, caps, after_d, after_i, live = get('keep'), get('caps'), get('after_d'), get('after_i'), get('live')
+            ex_off, ex_ids = get('ex_off'), get('ex_ids')
+            lists = None if ex_off is None else [ex_ids[ex_off[q]:ex_off[q + 1]] for q in keep]      # the CSR cut to `keep`
             assert not (masked and live is None)
             if live is not None and not masked:
                 e.set_row_mask(live)
                 masked = True
             ids, d = e.query(z['queries'][keep], sp, max_dist2=None if caps is None else caps[keep],
-                             after=None if after_d is None else (after_d[keep], after_i[keep]))
+                             after=None if after_d is None else (after_d[keep], after_i[keep]), exclude=lists)
             t = e.last_timing()
             reruns = [e.last_reruns(0).tolist(), e.last_reruns(1).tolist()]
-            m, w, a = e.mask_stats(), e.within_stats(), e.after_stats()
+            m, w, a, x = e.mask_stats(), e.within_stats(), e.after_stats(), e.exclude_stats()
             np.savez(os.path.join(spec['out'], tag + '.npz'), ids=ids, dists=d)
             out[tag] = dict(engine=int(t.engine), fallback=int(t.fallback_queries), retry=int(t.retry_queries), flags=int(t.flags),
                             rescored=int(t.rescored_pairs), exact_list=reruns[0], retry_list=reruns[1], dead_survivors=int(m.dead_survivors),
-                            n_dead=int(m.n_dead), within=w.as_dict(), after=a.as_dict())
+                            n_dead=int(m.n_dead), within=w.as_dict(), after=a.as_dict(), exclude=x.as_dict())
 print('RESULT ' + json.dumps(out))
 """
-_MASK_LAST = {name: (name in ("mask", "all"), i) for i, name in enumerate(SM.ATTACH)}
+_MASK_LAST = {name: (name in ("mask", "all", "ex_all"), i) for i, name in enumerate(SM.ATTACH)}
 
 
 def _run_attached(work_dir, regime, shape, lib=None):
@@ -329,6 +375,11 @@ def _run_attached(work_dir, regime, shape, lib=None):
             np.save(work_dir / (tag + ".after_i.npy"), att["after"][1])
         if "live" in att:
             np.save(work_dir / (tag + ".live.npy"), att["live"])
+        if "excl" in att:
+            import exclude_model as XM
+            off, ex_ids = XM.csr(att["excl"])
+            np.save(work_dir / (tag + ".ex_off.npy"), off)
+            np.save(work_dir / (tag + ".ex_ids.npy"), ex_ids)
         engine, rot = ENGINE[fmt]
         engines.setdefault((case.name, engine, rot, case.k, case.sp), []).append(tag)
         runs.append((case, fmt, name, att, keep, w, tag))
@@ -371,6 +422,41 @@ def _check_attached_answers(case, fmt, name, att, keep, ids, dists, t):
         assert (t["after"]["after_slots"], t["after"]["underfull_queries"], t["after"]["exhausted_queries"]) == (slots, underfull, exhausted), \
             (where, t["after"], slots, underfull, exhausted)
     assert t["n_dead"] == (int((~att["live"]).sum()) if "live" in att else 0), (where, t["n_dead"])
+    x = t["exclude"]
+    if "excl" in att:
+        assert (x["excluding_queries"], x["kept_slots"], x["underfull_queries"]) == (keep.size, slots, underfull), (where, x, keep.size, slots, underfull)
+    else:
+        assert x == dict(excluding_queries=0, underfull_queries=0, kept_slots=0, refused_keys=0), (where, x)
+
+
+def _check_refused(case, fmt, name, att, keep, w, t, bad):
+    """hvs_exclude_info.refused_keys against the model's `refused`: equal where the filter answers every query; with an exact
+    fallback (the `out` cells) at least the filter-answered queries' sum and strictly above it -- the fallback queries list
+    matched rows, which only the re-run sink (counter slot 26) can have refused."""
+    if "excl" not in att:
+        return ""
+    got, want = t["exclude"]["refused_keys"], int(w["refused"][keep].sum())
+    sink = bool(w["exact"][keep].any())
+    if (got <= want) if sink else (got != want):
+        bad.append((case.name, fmt, name, "refused_keys", got, "above" if sink else "equal to", want))
+    return "  refused %6d (model %s%d)" % (got, "> " if sink else "", want)
+
+
+def _check_page2_twin(results, bad):
+    """DESIGN 3.14's "the same re-scored pairs": in one child, on one engine, the ex_p1 cell re-scores exactly the pairs the
+    after_p2 cell does and retries the same queries -- measured against measured."""
+    cells = {(case.name, fmt, name): (keep, t) for case, fmt, name, att, keep, w, ids, dists, t in results}
+    twins = 0
+    for (cname, fmt, name), (keep, t) in cells.items():
+        if name == "ex_p1" and (cname, fmt, "after_p2") in cells:
+            keep2, t2 = cells[(cname, fmt, "after_p2")]
+            twins += 1
+            same_sent = np.array_equal(keep, keep2)
+            print("%-7s %-6s ex_p1 rescored %7d retried %s  after_p2 rescored %7d retried %s" % (
+                cname, fmt, t["rescored"], sorted(t["retry_list"]), t2["rescored"], sorted(t2["retry_list"])))
+            if not (same_sent and t["rescored"] == t2["rescored"] and sorted(t["retry_list"]) == sorted(t2["retry_list"])):
+                bad.append((cname, fmt, "ex_p1 against after_p2", t["rescored"], t2["rescored"], sorted(t["retry_list"]), sorted(t2["retry_list"])))
+    return twins
 
 
 def _attached_line(label, case, fmt, name, t, lo, hi, dlo, dhi, keep, w, ok):
@@ -381,8 +467,9 @@ def _attached_line(label, case, fmt, name, t, lo, hi, dlo, dhi, keep, w, ok):
 
 @pytest.mark.parametrize("regime,shape", [("proven", "16"), ("default", "16"), ("reckless", "16"), ("default", "32")])
 def test_attached_counts_lie_in_the_model_bracket(work_dir, regime, shape):
-    """Caps, cursors and a row mask (selectivity_model.ATTACH over ATTACH_MATRIX): answers first, then retry and exact lists
-    exactly, rescored_pairs and dead_survivors inside the model's brackets."""
+    """Caps, cursors, a row mask and exclusion lists (selectivity_model.ATTACH over ATTACH_MATRIX): answers and the features' own
+    counts first, then retry and exact lists exactly, rescored_pairs and dead_survivors inside the model's brackets, refused_keys
+    equal to the model's, and the ex_p1 cells against the after_p2 cells measured in the same child."""
     results = _run_attached(work_dir, regime, shape)
     for case, fmt, name, att, keep, w, ids, dists, t in results:
         _check_attached_answers(case, fmt, name, att, keep, ids, dists, t)
@@ -390,15 +477,18 @@ def test_attached_counts_lie_in_the_model_bracket(work_dir, regime, shape):
     for case, fmt, name, att, keep, w, ids, dists, t in results:
         (lo, hi), (dlo, dhi) = SM.totals(w), SM.totals(w, what="dead_")
         inside = lo <= t["rescored"] <= hi and dlo <= t["dead_survivors"] <= dhi
-        print(_attached_line("%s I8_SHAPE=%s" % (regime, shape), case, fmt, name, t, lo, hi, dlo, dhi, keep, w, inside))
+        print(_attached_line("%s I8_SHAPE=%s" % (regime, shape), case, fmt, name, t, lo, hi, dlo, dhi, keep, w, inside)
+              + _check_refused(case, fmt, name, att, keep, w, t, bad))
         _check_reruns(case, fmt + "/" + name, regime, keep, w, t)
         if not inside:
             bad.append((case.name, fmt, name, t["rescored"], lo, hi, t["dead_survivors"], dlo, dhi))
+    twins = _check_page2_twin(results, bad)
+    assert twins >= 1, "no (ex_p1, after_p2) pair in this child"
     assert not bad, bad
 
 
 def test_a_band_too_wide_is_seen_under_attachments(work_dir, wide_band_lib):
-    """The band x 1.25 build under cap_kth, after_p2 and mask: right answers, above the production bracket, inside the model's
+    """The band x 1.25 build under cap_kth, after_p2, mask and ex_p1: right answers, above the production bracket, inside the model's
     bracket for that band."""
     results = _run_attached(work_dir, "default", "16", lib=wide_band_lib)
     for case, fmt, name, att, keep, w, ids, dists, t in results:
@@ -409,10 +499,12 @@ def test_a_band_too_wide_is_seen_under_attachments(work_dir, wide_band_lib):
         lo, hi = SM.totals(w)
         (mlo, mhi), (dlo, dhi) = SM.totals(m, ~w["excluded"]), SM.totals(m, ~w["excluded"], what="dead_")
         ok = hi < t["rescored"] and mlo <= t["rescored"] <= mhi and dlo <= t["dead_survivors"] <= dhi
-        print(_attached_line("band x %.2f" % SM.MUTANT_SCALE, case, fmt, name, t, mlo, mhi, dlo, dhi, keep, m, ok) + "  production model [%d, %d]" % (lo, hi))
+        print(_attached_line("band x %.2f" % SM.MUTANT_SCALE, case, fmt, name, t, mlo, mhi, dlo, dhi, keep, m, ok) + "  production model [%d, %d]" % (lo, hi)
+              + _check_refused(case, fmt, name, att, keep, m, t, bad))
         _check_reruns(case, fmt + "/" + name, "default", keep, m, t)
         if not ok:
             bad.append((case.name, fmt, name, t["rescored"], (lo, hi), (mlo, mhi)))
+    assert _check_page2_twin(results, bad) == 2
     assert not bad, bad
 
 

@@ -18,6 +18,10 @@ treatment: the walk without attachments is the committed one to the unit, its he
 host models give, (a), (b), (d) hold, and (c'), (e'), (g), (h), (i) of test_conditions_of_the_attached_gpu_cases; (f) each
 wrong reading of the code that selectivity_model.WRONG names would leave the bracket or change the retry set somewhere.
 The Prepared objects and walks come from selectivity_model's caches, shared by all tests of the module.
+
+Exclusion lists (selectivity_model.EXCL_ATTACH) are the fourth attachment: their cells meet (a), (b), (d), (c') and
+(e') -- (e") for the lists -- like the others, and test_conditions_of_the_list_cells adds (j) the walk under ex_p1 IS the walk
+under after_p2, array for array, and (k) what the model says of `refused_keys`.
 """
 import os
 import subprocess
@@ -215,10 +219,11 @@ def test_no_attachment_is_the_committed_walk():
         assert all(np.array_equal(x, y) for x, y in zip(same["held_keys"], w["held_keys"]))
 
 
-def _cell_walks():
-    """[(case, fmt, regime, attachment name, attachment, walk)] of every cell the GPU test runs under attachments."""
+def _cell_walks(with_exact=False):
+    """[(case, fmt, regime, attachment name, attachment, walk)] of every cell the GPU test runs under attachments; with_exact: also
+    the cells of a case that sends queries to the exact engine (`out`)."""
     return [(case, fmt, regime, name, SM.attachment(case, name), SM.case_walk(case, fmt, regime, attach=name))
-            for case, fmt, regime, name in SM.attach_cells()]
+            for case, fmt, regime, name in SM.attach_cells() if with_exact or not SM.case_prep(case, fmt).hopeless.any()]
 
 
 def test_attached_walks_are_consistent():
@@ -259,13 +264,14 @@ def test_conditions_of_the_attached_gpu_cases():
     """Conditions (a), (b), (d) as above and (c'), (e'), (g), (h), (i) of the attachments, for every attached cell of the GPU test:
 
       (c') the band x 1.25 lifts sum lo by at least 10 bracket widths above the production sum hi, for the non-FP16 formats under
-           cap_kth, after_p2 and mask;
-      (e') under `reckless` every attachment except cap_mixed retries more than 0 and fewer than half of the queries;
+           cap_kth, after_p2, mask and ex_p1, with the same retry set;
+      (e') under `reckless` every attachment except cap_mixed -- every list attachment: (e") -- retries more than 0 and fewer than
+           half of the queries;
       (g)  under `mask`, in every regime, some dead row is a survivor (sum dead_hi > 0): `dead_survivors` is not asserted to be 0;
       (h)  cap_mixed has at least 8 queries of each of its eight kinds;
       (i)  after_deep has at least 4 exhausted cursors and at least 4 more queries whose page behind the cursor is under-full."""
     print()
-    for case, fmt, regime, name, att, w in _cell_walks():
+    for case, fmt, regime, name, att, w in _cell_walks(with_exact=True):
         nq = SM.case_data(case)[1].shape[0]
         keep = ~w["excluded"]
         cap = SM.list_capacity(SM.RESERVE_NQ, int(keep.sum()))
@@ -282,7 +288,7 @@ def test_conditions_of_the_attached_gpu_cases():
         nretry = int(w["retry"][keep].sum())
         assert nretry == 0 or w["retry_cand"].max() <= SM.list_capacity(SM.RESERVE_NQ, nretry), "(d) retry batch " + line
         assert (w["hi"] + 62)[keep].sum(0).max() <= SM.HVS_GROUP * cap, "(d) survivor entries of a group " + line
-        if fmt != BM.FP16 and name in ("cap_kth", "after_p2", "mask"):
+        if fmt != BM.FP16 and name in ("cap_kth", "after_p2", "mask", "ex_p1"):
             m = SM.case_walk(case, fmt, regime, SM.MUTANT_SCALE, attach=name)
             mlo, mhi = SM.totals(m, keep)
             line += "  band x %.2f: lo %7d = hi + %.1f widths" % (SM.MUTANT_SCALE, mlo, (mlo - hi) / max(width, 1))
@@ -305,11 +311,14 @@ def test_each_wrong_rule_is_seen():
     """(f) Each wrong rule of selectivity_model.WRONG shows on at least one (case, format, regime) of the matrix: its sum bracket
     is disjoint from the right rule's by at least 10 bracket widths, or its retry set differs."""
     print()
-    where = {"cap": ("cap_kth", "cap_mixed", "cap_after", "all"), "after": ("after_p2", "after_deep", "cap_after", "all"), "mask": ("mask", "all")}
+    where = {"cap": ("cap_kth", "cap_mixed", "cap_after", "all"), "after": ("after_p2", "after_deep", "cap_after", "all"), "mask": ("mask", "all"),
+             "excl": SM.EXCL_ATTACH}
+    # a list rule must show in the regime where the GPU test would meet it: with thresholds as shipped, resp. where queries are retried
+    must_show_under = {"excl_in_lists": "default", "excl_seed_only": "default", "excl_retry_dropped": "reckless"}
     for wrong in SM.WRONG:
         seen = []
         for case, fmt, regime, name in SM.attach_cells():
-            if name not in where[wrong.split("_")[0]]:
+            if name not in where[wrong.split("_")[0]] or regime != must_show_under.get(wrong, regime):
                 continue
             w = SM.case_walk(case, fmt, regime, attach=name)
             x = SM.case_walk(case, fmt, regime, attach=name, wrong=wrong)
@@ -323,3 +332,57 @@ def test_each_wrong_rule_is_seen():
                         x["retry"][keep].sum(), w["retry"][keep].sum()) if retry_differs else ""))
         print("%-18s seen in %2d cells, e.g. %s" % (wrong, len(seen), seen[0] if seen else "-"))
         assert seen, wrong
+
+
+# --------------------------------------------------------------------------- the fourth attachment: exclusion lists
+
+def test_list_cells_with_an_exact_fallback_are_consistent():
+    """The `out` cells (four far queries without a usable INT8 bound): what test_attached_walks_are_consistent asks, of the queries
+    the filter answers; the far ones take no part in any level and the model counts nothing for them."""
+    cells = [c for c in _cell_walks(with_exact=True) if c[5]["exact"].any()]
+    assert len(cells) == 2 and all(c[0].name == "out" and c[3] == "ex_p1" for c in cells)
+    for case, fmt, regime, name, att, w in cells:
+        for p in ("", "retry_"):
+            assert (w[p + "lo"] <= w[p + "hi"]).all() and not w[p + "dead_hi"].any()
+        if regime == "proven":
+            assert not w["retry"].any()
+        assert int(w["exact"].sum()) == 4 and not (w["retry"] & w["exact"]).any()
+        assert not w["refused"][w["exact"]].any() and not w["hi"][w["exact"]].any()
+        fulls = SM.case_fulls(case)
+        assert all(fulls[q].size >= case.k for q in np.flatnonzero(w["exact"])), "the far queries list matched rows: the sink must refuse"
+        for q, (got, exp) in enumerate(zip(w["held_keys"], SM.expected_keys(case, att))):
+            assert w["exact"][q] or np.array_equal(got, exp), (regime, q, got.size, exp.size)
+
+
+def test_conditions_of_the_list_cells():
+    """(j) for every case, format and regime the walk under ex_p1 equals the walk under after_p2 in lo, hi, cand, fails, overflow,
+           both retry brackets and the held keys: excluding page 1 re-scores what the page-2 cursor re-scores (DESIGN 3.14);
+       (k) `refused` summed over a cell is positive for every list attachment, and under ex_p1 with proven thresholds it is k times
+           the number of queries with at least k matches plus the match counts of the others (each listed key is asked for once:
+           tau never falls below the k-th unlisted key, which lies behind all of them);
+       the raw lists of ex_deep put the sort and the de-duplication in the path of those counts."""
+    print()
+    for case in SM.CASES:
+        fulls = SM.case_fulls(case)
+        for fmt in case.fmts:
+            exact = SM.case_prep(case, fmt).hopeless
+            for regime in case.regimes:
+                a, x = SM.case_walk(case, fmt, regime, attach="after_p2"), SM.case_walk(case, fmt, regime, attach="ex_p1")
+                for name in ("lo", "hi", "cand", "fails", "overflow", "retry", "retry_lo", "retry_hi", "retry_cand", "excluded"):
+                    assert np.array_equal(a[name], x[name]), ("(j)", case.name, fmt, regime, name)
+                assert all(np.array_equal(p, q) for p, q in zip(a["held_keys"], x["held_keys"])), ("(j)", case.name, fmt, regime)
+                assert not a["refused"].any()
+                if regime == "proven":
+                    want = sum(min(case.k, fulls[q].size) for q in range(len(fulls)) if not exact[q])
+                    assert int(x["refused"].sum()) == want > 0, ("(k)", case.name, fmt, int(x["refused"].sum()), want)
+    for case, fmt, regime, name, att, w in _cell_walks(with_exact=True):
+        if name in SM.EXCL_ATTACH:
+            print("%-7s %-6s %-8s %-10s refused %6d  listed %6d" % (case.name, fmt, regime, name, int(w["refused"].sum()), sum(x.size for x in att["excl"])))
+            assert w["refused"].sum() > 0, ("(k)", case.name, fmt, regime, name)
+    raw = SM.attachment(SM.CASES[0], "ex_deep")["excl"]
+    import exclude_model as XM
+    assert all(r.size <= XM.EXCLUDE_MAX for r in raw)
+    doubled = sum(np.unique(r).size < r.size for r in raw)
+    descending = sum(r.size > 3 and r[0] != 0xFFFFFFFF and (np.diff(SM.key_ids(SM.case_fulls(SM.CASES[0])[q][:3])[::-1]) != 0).all() for q, r in enumerate(raw))
+    assert doubled >= 70 and descending >= 70 and sum((r == 0xFFFFFFFF).any() for r in raw) >= 70, (doubled, descending)
+    assert sum(r.size == XM.EXCLUDE_MAX for r in raw) >= 20
