@@ -789,6 +789,103 @@ int hvs_download_exclude_plan(hvs_ctx *ctx, uint32_t *begin, uint32_t *count /* 
 uint32_t hvs_exclude_plan(const uint32_t *offsets, const uint32_t *ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t *begin,
                           uint32_t *count, uint32_t *out_ids);
 
+/* ---- multi-vector queries: the k rows nearest to any of several vectors ----------------------------- */
+/*
+ * A user with three interests, an item with several embeddings, a text expanded into paraphrases: a query described by SEVERAL
+ * vectors, asking for "the k rows that pass my predicate and are nearest to ANY of these vectors".  Extra vectors are attached
+ * to the resident queries in CSR form: vec_offsets[nq + 1] (u32, ascending, [0] == 0) and vecs[vec_offsets[nq]][100] (f32).
+ *
+ * Definition.  User query q has the vector list V(q): its own 100 floats as vector 0, followed by its m(q) = vec_offsets[q + 1] -
+ * vec_offsets[q] extras.  The key of a row for q is the SMALLEST key (distance bits, id) over the vectors of V(q), in the
+ * engines' own key order (+inf after every finite value, the canonical NaN after +inf); each distance is the engine's
+ * exact-order f32 distance to that one vector, bit for bit what a plain query with that vector reports.  The answer is the first
+ * k rows in that key order among the rows that pass q's predicate, lie in the sampled prefix, are live, have `min distance <=
+ * cap` if caps are set ("some vector within the cap") and are not in q's exclusion list.  Every id appears at most once among
+ * the non-pad slots.  Then the usual padding (rows n-1, n-2, ... or the last live ids), a pad row reporting its smallest
+ * distance over V(q); with hvs_set_padding(ctx, 0) the unmatched slots are 0xFFFFFFFF / +inf.  A query with m(q) == 0 is the
+ * plain query: the same ids and distance bits as without the feature.
+ *
+ * How: q runs as 1 + m(q) ordinary SUB-QUERIES with padding off -- sub-query j is q's 104 floats with floats 4..103 replaced by
+ * vector j -- on the expanded resident set that category sets use, and one kernel merges the sub-lists BY ID (per id the
+ * smallest key), takes the k smallest and pads once.  That is exact: a row of the answer that attains its minimum at vector j
+ * could only be missing from sub-list j if k rows had a smaller key under vector j, hence a smaller minimum key -- so every row
+ * of the answer is in some sub-list with its true key, and a row outside the answer only ever shows a key at or above its true
+ * one.
+ *
+ * Composes with every engine, both distance orders, every k, sample_proportion, padding on and off, caps, exclusion lists, the
+ * live-row mask, appended and updated rows and compaction; caps and lists stay one per USER query, each sub-query reads its
+ * parent's.  One GPU and replicated multi-GPU contexts (each GPU takes its owner range's slice of the CSR); a row-partitioned
+ * context returns HVS_ESTATE and changes nothing.  The paging law of the exclusion lists holds: excluding the ids of pages 1..P
+ * yields page P+1.
+ * Does NOT compose, and says so:
+ *  - cursors: a sub-query would test (d_j, id) > cursor per vector, and a row whose minimum key lies before the cursor would come
+ *    back under another vector.  While vectors are attached hvs_set_after, hvs_set_after_device and hvs_set_after_from_results
+ *    return HVS_ESTATE and change nothing (removing cursors, both pointers NULL, stays a no-op that succeeds).
+ *  - category sets: there is one expanded set per context.  Attaching vectors removes category sets and attaching category sets
+ *    removes vectors; the cross product is a later step.
+ *
+ * Lifetime: that of category sets.  Vectors belong to the resident query set: hvs_upload_queries, hvs_gen_queries,
+ * hvs_set_queries_device, hvs_set_queries_from_rows and hvs_query* remove them, and so does hvs_set_query_vectors(ctx, NULL,
+ * NULL, 0) (a no-op while none are attached).  Attaching or removing vectors drops earlier results and removes caps, cursors and
+ * exclusion lists: attach those afterwards.  hvs_download_queries keeps returning the user's rows; hvs_reserve(nq) sizes for the
+ * sub-queries; hvs_last_timing reports the user's nq and a query_ms that includes the merge; hvs_timing.pairs counts (vector,
+ * row) pairs, the sub-queries' sum; hvs_last_reruns speaks sub-query indices; hvs_within_stats and hvs_exclude_stats follow the
+ * sub-query rules they have under sets; hvs_in_stats reports zeros.  While no vectors are attached every call runs exactly the
+ * kernels it runs without these functions, with exactly the same arguments.
+ *
+ * Limits.  At most HVS_VECTORS_MAX_EXTRA extras per query (64 sub-lists per merge), at most 2^32 - 2 sub-queries in all.  A
+ * longer list, vec_offsets[0] != 0, a descending pair of offsets, or nq != the number of resident queries: HVS_EINVAL, and nothing
+ * changes -- vectors already attached, results, caps and lists stay in force.  No data set loaded: HVS_ESTATE.  Vector components
+ * are not validated: NaN and inf components give NaN or +inf distances, which sort by the key order as for a plain query.
+ *
+ * hvs_set_query_vectors: the CSR from HOST memory; both pointers NULL (or nq == 0) removes the vectors; vecs == NULL is valid
+ * exactly when vec_offsets[nq] == 0.
+ * hvs_set_query_vectors_device: the same from DEVICE memory by the rules of hvs_set_exclude_ids_device -- plain device memory of
+ * any visible GPU, both buffers on the same one; host memory of any kind is HVS_EINVAL with the runtime's error cleared; the call
+ * blocks until the vectors are attached.  It is accepted exactly when the host call accepts the same bytes: a kernel checks the
+ * offsets and the host reads a status block back; offsets[nq] is trusted as the vector array's length only once every pair has
+ * been found ascending, and nothing past it is read.  The vectors never cross PCIe; the host reads the offsets back (4 bytes per
+ * query), because hvs_query_resident maps query ranges to sub-query ranges there.  The plan needs no scan: sub_off[q] =
+ * offsets[q] + q.
+ * hvs_query_vectors: hvs_upload_queries + hvs_set_query_vectors + hvs_query_resident + hvs_download_results in one call, the
+ * steps one after the other (like hvs_query_in).  Both vector pointers NULL: exactly hvs_query.
+ * hvs_vectors_stats: figures of the last call (after hvs_sync); HVS_ESTATE where hvs_last_timing has none to report; all zero when
+ * the last call ran without vectors.  merged_keys: the non-empty slots of the sub-lists.  duplicate_keys: the keys the merge
+ * dropped because its buffer held the same id with a key at least as small.  The merge streams the lists in order, 64 slots at a
+ * time, through a buffer of CAP = 256 (k <= 128) or 512 keys; before a step that might not fit (held + 64 > CAP) it de-duplicates
+ * the buffer and, if the step still might not fit, cuts it to the k smallest keys; it de-duplicates once more at the end.  A row
+ * cut away and read again later therefore counts as new: duplicate_keys = merged_keys - distinct ids whenever no cut dropped a
+ * row that returns (always when the lists' keys fit the buffer).  Multi-GPU contexts: counters summed, max_vectors the largest,
+ * the two times the slowest GPU's.
+ * hvs_vectors_plan: the merge's arithmetic for ONE query on the host, no GPU and no context: m unpadded lists of k slots each
+ * (ids, dists: m x k, empty slots 0xFFFFFFFF / +inf), pad_ids / pad_dists (k each; the distances already the minimum over the
+ * vectors; both may be NULL with padding == 0) and `padding`.  Writes the merged row (out_ids, out_dists: k slots; out_dists may
+ * be NULL) and *n_duplicates (may be NULL) = non-empty slots - distinct ids, and returns the number of non-pad slots.
+ * hvs_vectors_check: the offsets' arithmetic on the host: nsub = offsets[nq] + nq, or 0xFFFFFFFF for offsets == NULL, offsets[0] !=
+ * 0, a descending pair, a list of more than HVS_VECTORS_MAX_EXTRA, or more than 2^32 - 2 sub-queries.  The device check
+ * reproduces it.
+ */
+#define HVS_VECTORS_MAX_EXTRA 63
+typedef struct hvs_vectors_info {
+    uint32_t multi_queries;     /* queries of the last call with at least one extra vector                   */
+    uint32_t sub_queries;       /* sub-queries the engines answered for the call's queries                   */
+    uint32_t max_vectors;       /* most vectors (1 + extras) of one query of the call                        */
+    uint32_t underfull_queries; /* queries with fewer than k distinct rows in all their sub-lists together   */
+    uint64_t merged_keys;       /* non-empty slots of the sub-lists the merge read                           */
+    uint64_t duplicate_keys;    /* ... of which dropped because the id was held with a key at least as small */
+    double   expand_ms;         /* device time of the expansion when the vectors were attached               */
+    double   merge_ms;          /* device time of the call's merge kernel                                    */
+} hvs_vectors_info;
+int hvs_set_query_vectors(hvs_ctx *ctx, const uint32_t *vec_offsets /* host, nq+1 */, const float *vecs /* host, x 100 */, uint32_t nq);
+int hvs_set_query_vectors_device(hvs_ctx *ctx, const uint32_t *d_offsets /* device, nq+1 */, const float *d_vecs /* device, x 100 */,
+                                 uint32_t nq, void *stream);
+int hvs_query_vectors(hvs_ctx *ctx, const float *q_rows, const uint32_t *vec_offsets, const float *vecs, uint32_t nq,
+                      float sample_proportion, uint32_t *out_ids, float *out_dists);
+int hvs_vectors_stats(hvs_ctx *ctx, hvs_vectors_info *out);
+uint32_t hvs_vectors_plan(const uint32_t *ids, const float *dists, uint32_t m, uint32_t k, const uint32_t *pad_ids,
+                          const float *pad_dists, int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_duplicates);
+uint32_t hvs_vectors_check(const uint32_t *offsets, uint32_t nq);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,7 +227,11 @@ struct HvsPerQuery {
 // result rows.  Every resident index of the C ABI is a user index; in_* functions below translate.  Not active: nothing here is
 // read, and the buffers are kept for the next attach.
 struct HvsInSet {
+    // The expanded set has two clients: category sets, and extra query vectors.  Everything that ties user queries
+    // to sub-query ranges below is shared; the clients differ in the expand kernel, the merge kernel and their stats.
+    enum Kind { Sets, Vectors };
     bool active = false;
+    Kind kind = Sets;                  // (while active) what the sub-queries of a user query are
     uint32_t nuq = 0;
     std::vector<uint32_t> h_sub_off;   // nuq + 1
     std::vector<uint8_t> h_eff;        // nuq: the query is answered through its set (tests C, non-empty set)
@@ -235,11 +239,18 @@ struct HvsInSet {
     uint32_t *d_sub_off = nullptr, *d_set_off = nullptr, *d_parent = nullptr;  // nuq + 1, nuq + 1 (the caller's CSR offsets), nsub
     float* d_value = nullptr;          // nsub
     uint32_t uq_cap = 0, sub_cap = 0;  // user queries / sub-queries the buffers above have room for
+    // extra vectors: this GPU's slice of the caller's CSR -- the offsets as they came (staged and checked before anything is
+    // replaced, like HvsQuerySet::d_ex_off), the status block of the check, and the vectors, 100 floats each
+    uint32_t *d_v_off = nullptr, *d_v_status = nullptr;
+    float* d_vecs = nullptr;
+    uint32_t v_off_cap = 0;            // user queries d_v_off has room for (+ 1 entry)
+    size_t vecs_cap = 0;               // vectors d_vecs has room for
+    uint32_t v_flags = 0, v_base = 0, v_total = 0;  // of the offsets staged last: HVS_VEC_BAD_*, offsets[0], offsets[nq]
     HvsPerQuery user;                  // the user's caps and cursors: room for uq_cap each, allocated at attach
     uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
     float* d_m_dists = nullptr;
     size_t m_cap = 0;                  // entries
-    unsigned long long* d_stat = nullptr;  // [0] under-full queries, [1] keys read: of the last merge
+    unsigned long long* d_stat = nullptr;  // [0] under-full queries, [1] keys read, [2] (vectors) duplicates dropped: of the last merge
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;  // around the expansion / the last merge
     double expand_ms = 0.0;
     // scratch of a plan made on the device (hvs_set_category_sets_device): nothing here is in force, in_commit takes from it
@@ -250,13 +261,16 @@ struct HvsInSet {
     float* d_p_vals = nullptr;                             // ... and of the values, pv_cap; both live for that call only (in_plan_release)
     uint32_t p_cap = 0, p_off_cap = 0, pv_cap = 0;
     // last call
-    bool call = false;                 // it ran under sets
+    bool call = false;                 // it ran on an expanded set ...
+    Kind call_kind = Sets;             // ... of this kind
     uint32_t call_set_queries = 0, call_sub = 0, call_max_set = 0;
     void free_device()
     {
         HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_m_ids, d_m_dists, d_stat);
         HvsRowSet::drop(d_p_pack, d_p_sub_off, d_p_eff, d_p_stat, d_p_off, d_p_vals);
-        p_cap = p_off_cap = pv_cap = 0;
+        HvsRowSet::drop(d_v_off, d_v_status, d_vecs);
+        p_cap = p_off_cap = pv_cap = v_off_cap = 0;
+        vecs_cap = 0;
         user.free_device();
         for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
             if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
@@ -3152,6 +3166,9 @@ int in_detach(hvs_ctx* c)
     sets_changed(c, false);
     return HVS_OK;
 }
+// ... of one client only: removing category sets leaves extra vectors alone, and the other way round
+int sets_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Sets ? HVS_OK : in_detach(c); }
+int vectors_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Vectors ? HVS_OK : in_detach(c); }
 
 // Attaching sets to one GPU's `nuq` user queries has two halves: a PLAN is made -- on the host from a host CSR (in_plan_host),
 // or by the plan kernels from a CSR in device memory (in_plan_device) --, which changes nothing a query or a later call reads,
@@ -3172,6 +3189,12 @@ struct InPlan {
     uint32_t v0 = 0, lo = 0;          // lo: the slice's first offset
     uint64_t sub_if_all_c = 0;        // the sub-queries there would be if every query tested C (what the limit is taken over)
     double plan_ms = 0.0;             // device time of the count and scan kernels
+    // extra vectors (kind == Vectors): the slice's offsets are staged and checked in HvsInSet::d_v_off (vec_stage); `vecs` = the
+    // first vector of the slice, nsub - nuq of them, in host memory (vec_dev < 0) or on GPU vec_dev.  The fill kernel writes
+    // sub_off and parent from the staged offsets: nothing of size nsub is built on the host.
+    HvsInSet::Kind kind = HvsInSet::Sets;
+    const float* vecs = nullptr;
+    int vec_dev = -1;
 };
 
 // what both halves need first: an earlier call's re-runs resolved and the stream idle, the events, the merge's counters
@@ -3179,7 +3202,7 @@ int in_begin(hvs_ctx* c)
 {
     int rc = begin_mutation(c);
     if (!rc) rc = in_ensure_events(c);
-    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)2);
+    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)3);
     return rc;
 }
 
@@ -3322,8 +3345,27 @@ int in_commit(hvs_ctx* c, InPlan& P)
         S.sub_cap = nsub;
     }
     if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
+    const bool vectors = P.kind == HvsInSet::Vectors;
+    const char* const what = vectors ? "hvs_set_query_vectors" : "hvs_set_category_sets";
+    if (vectors) {
+        const size_t nvec = (size_t)nsub - nuq;
+        if (nvec > S.vecs_cap) {
+            S.vecs_cap = 0;
+            if ((rc = dev_alloc(c, &S.d_vecs, nvec * HVS_NDIM))) return lost(rc);
+            S.vecs_cap = nvec;
+        }
+        if (nvec) {
+            if (P.vec_dev >= 0)
+                rc = copy_from_device(c, S.d_vecs, P.vecs, P.vec_dev, nvec * HVS_NDIM * sizeof(float));
+            else if (hipMemcpyAsync(S.d_vecs, P.vecs, nvec * HVS_NDIM * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                rc = fail(c, HVS_EHIP, "hvs_set_query_vectors: upload of the vectors failed");
+            if (rc) return lost(rc);
+        }
+    }
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
-    if (P.on_device) {
+    if (vectors) {
+        // (nothing to upload: hvs_k_fill_vectors below writes sub_off and parent from the staged offsets)
+    } else if (P.on_device) {
         if (hipMemcpyAsync(S.d_sub_off, S.d_p_sub_off, ((size_t)nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
             return lost(fail(c, HVS_EHIP, "hvs_set_category_sets_device: the copy of the plan failed"));
     } else if (up(S.d_sub_off, P.sub_off.data(), P.sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
@@ -3332,23 +3374,32 @@ int in_commit(hvs_ctx* c, InPlan& P)
                up(S.d_value, P.value.data(), P.value.size() * sizeof(float)) != hipSuccess)
         return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
     (void)hipEventRecord(S.ev_x0, c->stream);
-    if (P.on_device && nuq)  // (parent, value and the rebased offsets; part of expand_ms, as plan_ms is)
+    if (vectors) {
+        hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(nuq + 1u, 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, S.d_sub_off, S.d_parent);
+        if (nsub) {
+            const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
+            hipLaunchKernelGGL(hvs_k_expand_vectors, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
+                               reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off, reinterpret_cast<const float4*>(S.d_vecs), nsub,
+                               reinterpret_cast<float4*>(c->d_q));
+        }
+    } else if (P.on_device && nuq)  // (parent, value and the rebased offsets; part of expand_ms, as plan_ms is)
         hipLaunchKernelGGL(hvs_k_in_fill, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, S.d_uq, P.d_off, P.d_vals, P.v0, P.lo, nuq, S.d_sub_off,
                            S.d_p_eff, S.d_set_off, S.d_parent, S.d_value);
-    if (nsub) {
+    if (nsub && !vectors) {
         const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
         hipLaunchKernelGGL(hvs_k_expand_in, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq),
                            S.d_parent, S.d_value, S.d_set_off, nsub, reinterpret_cast<float4*>(c->d_q));
     }
     (void)hipEventRecord(S.ev_x1, c->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)  // (the host arrays go with this scope)
-        return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: the expansion failed"));
+        return lost(fail(c, HVS_EHIP, std::string(what) + ": the expansion failed"));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
     S.expand_ms = (double)ms + P.plan_ms;
     S.h_sub_off.swap(P.sub_off);
     S.h_eff.swap(P.eff);
     c->nq = nsub;
+    S.kind = P.kind;
     sets_changed(c, true);
     return HVS_OK;
 }
@@ -3360,6 +3411,65 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
     int rc = in_begin(c);
     if (!rc) rc = in_plan_host(c, off, vals, nuq, &P);
     return rc ? rc : in_commit(c, P);
+}
+
+// ---- extra query vectors (include/hvs.h "multi-vector queries"): the second client of the expanded set ----
+static_assert(HVS_VEC_MAX_EXTRA_ == HVS_VECTORS_MAX_EXTRA && HVS_VECTORS_MAX_EXTRA + 1 <= 64, "a merge streams at most 64 sub-lists");
+
+// hvs_vectors_check's arithmetic
+uint32_t vec_check_core(const uint32_t* off, uint32_t nq)
+{
+    if (!off || off[0] != 0u) return 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (off[q + 1] < off[q] || off[q + 1] - off[q] > HVS_VECTORS_MAX_EXTRA) return 0xFFFFFFFFu;
+    const uint64_t nsub = (uint64_t)off[nq] + nq;
+    return nsub >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nsub;
+}
+
+// The plan of one GPU's slice of the CSR, first half: the slice's offsets -- `nuq` + 1 entries from host memory (src_dev < 0) or
+// from GPU src_dev -- are staged in d_v_off and checked there (hvs_k_check_vectors; `first`: the slice is the head of the
+// caller's array), and the host reads the status block back: v_flags / v_base / v_total.  Good offsets come back to the host
+// too (4 bytes per query): sub_off[q] = off[q] - off[0] + q, and hvs_query_resident maps query ranges to sub-query ranges there.
+// Nothing that a query or a later call reads changes; the caller judges the flags of all GPUs before any commit.
+int vec_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
+{
+    HvsInSet& S = c->qs.in;
+    int rc = in_begin(c);
+    if (rc) return rc;
+    if (!S.d_v_off || nuq > S.v_off_cap) {
+        S.v_off_cap = 0;
+        if ((rc = dev_alloc(c, &S.d_v_off, (size_t)nuq + 1u))) return rc;
+        S.v_off_cap = nuq;
+    }
+    if (!S.d_v_status && (rc = dev_alloc(c, &S.d_v_status, (size_t)4))) return rc;
+    const size_t bytes = ((size_t)nuq + 1u) * sizeof(uint32_t);
+    if (src_dev < 0)
+        HVS_HIP(c, hipMemcpyAsync(S.d_v_off, off, bytes, hipMemcpyHostToDevice, c->stream));
+    else if ((rc = copy_from_device(c, S.d_v_off, off, src_dev, bytes)))
+        return rc;
+    HVS_HIP(c, hipMemsetAsync(S.d_v_status, 0, 4 * sizeof(uint32_t), c->stream));
+    HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
+    hipLaunchKernelGGL(hvs_k_check_vectors, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
+    HVS_HIP(c, hipGetLastError());
+    HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
+    uint32_t h[4] = {0, 0, 0, 0};
+    HVS_HIP(c, hipMemcpyAsync(h, S.d_v_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    S.v_flags = h[0], S.v_base = h[1], S.v_total = h[2];
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
+    P->kind = HvsInSet::Vectors;
+    P->nuq = nuq;
+    P->plan_ms = ms;
+    if (S.v_flags) return HVS_OK;
+    std::vector<uint32_t> o((size_t)nuq + 1u);
+    HVS_HIP(c, hipMemcpy(o.data(), S.d_v_off, bytes, hipMemcpyDeviceToHost));
+    P->sub_off.resize((size_t)nuq + 1u);
+    P->eff.resize(nuq);
+    for (uint32_t q = 0; q <= nuq; ++q) P->sub_off[q] = o[q] - o[0] + q;
+    for (uint32_t q = 0; q < nuq; ++q) P->eff[q] = o[q + 1] > o[q] ? 1u : 0u;
+    P->nsub = P->sub_off[nuq];
+    return HVS_OK;
 }
 
 // hvs_query_resident under category sets: user queries [q0, q0 + nq) = sub-queries [sub_off[q0], sub_off[q0 + nq)), answered by
@@ -3389,14 +3499,19 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         if ((rc = run_queries(c, s0, s1 - s0, sample_proportion, NoHook{}))) return rc;
         if ((rc = resolve_overflow(c))) return rc;
     }
-    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, 2 * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, 3 * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipEventRecord(S.ev_m0, c->stream));
     if (nq) {
         with_cap(c->cap, [&](auto CAPT) {
             auto launch = [&](auto ST) {
-                hipLaunchKernelGGL((hvs_k_merge_in<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream, S.d_sub_off,
-                                   q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, S.d_uq, c->padding ? 1 : 0,
-                                   masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
+                if (S.kind == HvsInSet::Vectors)  // (merges by id, and pads from the EXPANDED rows: a pad row's smallest distance)
+                    hipLaunchKernelGGL((hvs_k_merge_vectors<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
+                                       S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, c->d_q, c->padding ? 1 : 0,
+                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
+                else
+                    hipLaunchKernelGGL((hvs_k_merge_in<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream, S.d_sub_off,
+                                       q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, S.d_uq, c->padding ? 1 : 0,
+                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
             };
             if (c->scalar_order)
                 launch(std::true_type{});
@@ -3409,6 +3524,7 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));  // (the merge belongs to the call's device time)
     c->call.timing.nq = nq;  // (the user's)
     S.call = true;
+    S.call_kind = S.kind;
     S.call_sub = s1 - s0;
     S.call_set_queries = S.call_max_set = 0;
     for (uint32_t p = q0; p < q0 + nq; ++p) {
@@ -3423,17 +3539,46 @@ int leaf_run_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proport
     return c->qs.in.active ? in_run(c, q0, nq, sample_proportion) : run_queries(c, q0, nq, sample_proportion, NoHook{});
 }
 
+// the last call's merge on one GPU (it ran on an expanded set: S.call): its three counters and its device time
+int leaf_merge_stats(hvs_ctx* c, unsigned long long (&v)[3], float* ms)
+{
+    const HvsInSet& S = c->qs.in;
+    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    HVS_HIP(c, hipEventElapsedTime(ms, S.ev_m0, S.ev_m1));
+    return HVS_OK;
+}
+
+int leaf_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
+{
+    int rc = call_required(c);
+    if (rc) return rc;
+    *out = hvs_vectors_info{};
+    const HvsInSet& S = c->qs.in;
+    if (!S.call || S.call_kind != HvsInSet::Vectors) return HVS_OK;
+    unsigned long long v[3] = {0, 0, 0};
+    float ms = 0.f;
+    if ((rc = leaf_merge_stats(c, v, &ms))) return rc;
+    out->multi_queries = S.call_set_queries;
+    out->sub_queries = S.call_sub;
+    out->max_vectors = S.call_max_set;
+    out->underfull_queries = (uint32_t)v[0];
+    out->merged_keys = v[1];
+    out->duplicate_keys = v[2];
+    out->expand_ms = S.expand_ms;
+    out->merge_ms = ms;
+    return HVS_OK;
+}
+
 int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
 {
     int rc = call_required(c);
     if (rc) return rc;
     *out = hvs_in_info{};
     const HvsInSet& S = c->qs.in;
-    if (!S.call) return HVS_OK;
-    unsigned long long v[2] = {0, 0};
-    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    if (!S.call || S.call_kind != HvsInSet::Sets) return HVS_OK;
+    unsigned long long v[3] = {0, 0, 0};
     float ms = 0.f;
-    HVS_HIP(c, hipEventElapsedTime(&ms, S.ev_m0, S.ev_m1));
+    if ((rc = leaf_merge_stats(c, v, &ms))) return rc;
     out->set_queries = S.call_set_queries;
     out->sub_queries = S.call_sub;
     out->max_set = S.call_max_set;
@@ -4235,6 +4380,50 @@ int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const
     return rc;
 }
 
+// hvs_set_query_vectors* on every GPU: the CSR from host memory (src_dev < 0) or from GPU src_dev (checked and waited for by the
+// caller).  A replicated context cuts it by the owner ranges.  Every GPU stages and checks its slice first and none changes
+// unless every slice is good and the sub-queries of the whole context can be counted in 32 bits: HVS_EINVAL leaves every GPU
+// as it was.  A failed commit (no room) leaves no GPU on an expanded set, as for category sets.
+int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int src_dev, uint32_t nq, const char* fn)
+{
+    const size_t N = std::max<size_t>(c->kids.size(), 1u);
+    std::vector<InPlan> plans(N);
+    auto slot = [&](const hvs_ctx* k) { return c->kids.empty() ? (size_t)0 : (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin()); };
+    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return vec_stage(k, off + first, src_dev, m, first == 0u, &plans[slot(k)]); });
+    if (rc) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    uint32_t flags = 0;
+    uint64_t total = 0;
+    auto judge = [&](const hvs_ctx* k) {
+        flags |= k->qs.in.v_flags;
+        total = std::max<uint64_t>(total, k->qs.in.v_total);  // (ascending offsets: the last slice's end)
+    };
+    if (c->kids.empty()) judge(c);
+    for (const hvs_ctx* k : c->kids) judge(k);
+    if (flags)
+        return fail(c, HVS_EINVAL,
+                    std::string(fn) + (flags & HVS_VEC_BAD_FIRST   ? ": vec_offsets[0] is not 0"
+                                       : flags & HVS_VEC_BAD_ORDER ? ": vec_offsets are not ascending"
+                                                                   : ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"));
+    if (total + nq >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": too many sub-queries");
+    if (total && !vecs) return fail(c, HVS_EINVAL, std::string(fn) + ": vecs is NULL");
+    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t, uint32_t) {
+        InPlan& P = plans[slot(k)];
+        P.vecs = vecs ? vecs + (size_t)k->qs.in.v_base * HVS_NDIM : nullptr;
+        P.vec_dev = src_dev;
+        return in_commit(k, P);
+    });
+    if (rc && !c->kids.empty()) {
+        const std::string err = c->err;
+        for (hvs_ctx* k : c->kids) (void)in_detach(k);
+        (void)hipGetLastError();
+        c->err = err;
+    }
+    return rc;
+}
+
 // the leaf whose row-set state speaks for the whole context (rows, mask and index are replicated)
 const hvs_ctx* mask_leaf(const hvs_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
 // ... for an entry point `fn` that needs a data set; nullptr (HVS_ESTATE, with the error text set) when there is none
@@ -4530,6 +4719,14 @@ uint32_t resident_count(const hvs_ctx* c)
     if (c->kids.empty()) return user_nq(c);
     return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
 }
+// extra vectors are attached (on every GPU or on none): cursors are refused meanwhile
+bool vectors_attached(const hvs_ctx* c)
+{
+    const hvs_ctx* k = c->kids.empty() ? c : c->kids[0];
+    return k->qs.in.active && k->qs.in.kind == HvsInSet::Vectors;
+}
+#define HVS_NO_CURSORS_ON_VECTORS(c, fn) \
+    if (vectors_attached(c)) return fail((c), HVS_ESTATE, fn ": cursors do not compose with extra query vectors (a row would come back under another vector)")
 // what the four entry points that attach per-query values check alike: `nq` is the number of resident queries ...
 int check_resident_count(hvs_ctx* c, uint32_t nq, const char* fn)
 {
@@ -4561,9 +4758,10 @@ int leaf_call_counters(hvs_ctx* c, Info* out, bool on, int first, unsigned long 
 int in_underfull(hvs_ctx* c, uint32_t* underfull)
 {
     if (!c->qs.in.call) return HVS_OK;
-    hvs_in_info I{};
-    const int rc = leaf_in_stats(c, &I);
-    if (!rc) *underfull = I.underfull_queries;
+    unsigned long long v[3] = {0, 0, 0};
+    float ms = 0.f;
+    const int rc = leaf_merge_stats(c, v, &ms);
+    if (!rc) *underfull = (uint32_t)v[0];
     return rc;
 }
 
@@ -5376,6 +5574,7 @@ int hvs_set_after(hvs_ctx* c, const float* after_dists, const uint32_t* after_id
 {
     if (!c) return HVS_EINVAL;
     if (!after_dists && !after_ids) return attach_everywhere(c, PerQuery::Cursors, nullptr, nullptr, -1, 0u);
+    HVS_NO_CURSORS_ON_VECTORS(c, "hvs_set_after");
     if (!after_dists || !after_ids) return fail(c, HVS_EINVAL, "hvs_set_after: one of after_dists / after_ids is NULL");
     if (int rc = check_resident_count(c, nq, "hvs_set_after")) return rc;
     return attach_everywhere(c, PerQuery::Cursors, after_dists, after_ids, -1, nq);
@@ -5385,6 +5584,7 @@ int hvs_set_after_device(hvs_ctx* c, const float* d_after_dists, const uint32_t*
 {
     if (!c) return HVS_EINVAL;
     if (!d_after_dists && !d_after_ids) return attach_everywhere(c, PerQuery::Cursors, nullptr, nullptr, -1, 0u);
+    HVS_NO_CURSORS_ON_VECTORS(c, "hvs_set_after_device");
     if (!d_after_dists || !d_after_ids) return fail(c, HVS_EINVAL, "hvs_set_after_device: one of d_after_dists / d_after_ids is NULL");
     int dev = 0, rc = check_resident_count(c, nq, "hvs_set_after_device");
     if (!rc && nq) rc = check_device_buffers(c, d_after_dists, d_after_ids, stream, "hvs_set_after_device", &dev);  // (an empty set reads nothing)
@@ -5394,6 +5594,7 @@ int hvs_set_after_device(hvs_ctx* c, const float* d_after_dists, const uint32_t*
 int hvs_set_after_from_results(hvs_ctx* c)
 {
     if (!c) return HVS_EINVAL;
+    HVS_NO_CURSORS_ON_VECTORS(c, "hvs_set_after_from_results");
     if (c->padding) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: padding is on (the last slot may be a pad row)");
     if (c->kids.empty()) {
         if (!leaf_has_all_results(c)) return fail(c, HVS_ESTATE, "hvs_set_after_from_results: no results for all resident queries");
@@ -5578,11 +5779,11 @@ int hvs_set_category_sets(hvs_ctx* c, const uint32_t* set_offsets, const float* 
 {
     if (!c) return HVS_EINVAL;
     if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets: not supported (yet) on a row-partitioned context");
-    if (!set_offsets && !set_values) return on_every_leaf(c, in_detach);
+    if (!set_offsets && !set_values) return on_every_leaf(c, sets_detach);
     if (!loaded_leaf(c, "hvs_set_category_sets")) return HVS_ESTATE;
     if (!set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets: set_offsets is NULL");
     if (int rc = check_resident_count(c, nq, "hvs_set_category_sets")) return rc;
-    if (nq == 0u) return on_every_leaf(c, in_detach);
+    if (nq == 0u) return on_every_leaf(c, sets_detach);
     // format and limits hold whatever the queries' types; the sub-query count is the largest when every query tests C
     if (hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
         return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
@@ -5637,11 +5838,11 @@ int hvs_set_category_sets_device(hvs_ctx* c, const uint32_t* d_set_offsets, cons
     static const char* const fn = "hvs_set_category_sets_device";
     if (!c) return HVS_EINVAL;
     if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets_device: not supported (yet) on a row-partitioned context");
-    if (!d_set_offsets && !d_set_values) return on_every_leaf(c, in_detach);
+    if (!d_set_offsets && !d_set_values) return on_every_leaf(c, sets_detach);
     if (!loaded_leaf(c, fn)) return HVS_ESTATE;
     if (!d_set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: d_set_offsets is NULL");
     if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, in_detach);
+    if (nq == 0u) return on_every_leaf(c, sets_detach);
     int dev = 0;
     if (int rc = check_device_buffers(c, d_set_offsets, d_set_values, stream, fn, &dev)) return rc;
     // the slice boundaries: offsets[first query of every GPU] and offsets[nq] come to the host (4 bytes each)
@@ -5694,7 +5895,7 @@ int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, fl
     if (!c) return HVS_EINVAL;
     if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_in_plan: single-GPU contexts only");
     const HvsInSet& S = c->qs.in;
-    if (!S.active) return fail(c, HVS_ESTATE, "hvs_download_in_plan: no category sets are attached");
+    if (!S.active || S.kind != HvsInSet::Sets) return fail(c, HVS_ESTATE, "hvs_download_in_plan: no category sets are attached");
     const uint32_t nsub = c->nq;
     HVS_HIP(c, hipSetDevice(c->device));
     if (sub_offsets) HVS_HIP(c, hipMemcpyAsync(sub_offsets, S.d_sub_off, ((size_t)S.nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -5704,6 +5905,93 @@ int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, fl
     }
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return (int)nsub;
+}
+
+// ---- multi-vector queries (include/hvs.h "multi-vector queries") -----------------
+
+uint32_t hvs_vectors_check(const uint32_t* offsets, uint32_t nq) { return vec_check_core(offsets, nq); }
+
+uint32_t hvs_vectors_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_t k, const uint32_t* pad_ids, const float* pad_dists, int padding,
+                          uint32_t* out_ids, float* out_dists, uint32_t* n_duplicates)
+{
+    if (m && k && (!ids || !dists)) return 0u;
+    std::vector<PlanSlot> all;
+    for (size_t j = 0; j < (size_t)m * k; ++j)
+        if (ids[j] != 0xFFFFFFFFu) all.push_back(plan_slot(dists[j], ids[j]));
+    // by (id, key): the first of every run of one id is the row's smallest key
+    std::sort(all.begin(), all.end(), [](const PlanSlot& a, const PlanSlot& b) { return a.id != b.id ? a.id < b.id : a.key < b.key; });
+    std::vector<PlanSlot> rows;
+    for (const PlanSlot& s : all)
+        if (rows.empty() || rows.back().id != s.id) rows.push_back(s);
+    if (n_duplicates) *n_duplicates = (uint32_t)(all.size() - rows.size());
+    std::sort(rows.begin(), rows.end(), [](const PlanSlot& a, const PlanSlot& b) { return a.key < b.key; });
+    std::vector<uint32_t> rid(rows.size());
+    std::vector<float> rd(rows.size());
+    for (size_t j = 0; j < rows.size(); ++j) rid[j] = rows[j].id, rd[j] = rows[j].dist;
+    return plan_row(rid.data(), rd.data(), (uint32_t)rows.size(), k, [](const PlanSlot&) { return true; }, pad_ids, pad_dists, padding, out_ids, out_dists);
+}
+
+int hvs_set_query_vectors(hvs_ctx* c, const uint32_t* vec_offsets, const float* vecs, uint32_t nq)
+{
+    static const char* const fn = "hvs_set_query_vectors";
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_vectors: not supported (yet) on a row-partitioned context");
+    if (!vec_offsets && !vecs) return on_every_leaf(c, vectors_detach);
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!vec_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_vectors: vec_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    if (nq == 0u) return on_every_leaf(c, vectors_detach);
+    return vectors_everywhere(c, vec_offsets, vecs, -1, nq, fn);
+}
+
+int hvs_set_query_vectors_device(hvs_ctx* c, const uint32_t* d_offsets, const float* d_vecs, uint32_t nq, void* stream)
+{
+    static const char* const fn = "hvs_set_query_vectors_device";
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_vectors_device: not supported (yet) on a row-partitioned context");
+    if (!d_offsets && !d_vecs) return on_every_leaf(c, vectors_detach);
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_vectors_device: d_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    if (nq == 0u) return on_every_leaf(c, vectors_detach);
+    int dev = 0;
+    if (int rc = check_device_buffers(c, d_offsets, d_vecs, stream, fn, &dev)) return rc;
+    return vectors_everywhere(c, d_offsets, d_vecs, dev, nq, fn);
+}
+
+int hvs_query_vectors(hvs_ctx* c, const float* q_rows, const uint32_t* vec_offsets, const float* vecs, uint32_t nq, float sample_proportion,
+                      uint32_t* out_ids, float* out_dists)
+{
+    if (!c) return HVS_EINVAL;
+    if (!vec_offsets && !vecs) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_vectors: not supported (yet) on a row-partitioned context");
+    if (!loaded_leaf(c, "hvs_query_vectors")) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_vectors: q_rows / out_ids is NULL");
+    // checked before the resident set is replaced: a refused call changes nothing
+    const uint32_t nsub = vec_check_core(vec_offsets, nq);
+    if (nsub == 0xFFFFFFFFu || (nsub > nq && !vecs))
+        return fail(c, HVS_EINVAL, "hvs_query_vectors: malformed offsets, more than HVS_VECTORS_MAX_EXTRA extra vectors on a query, or too many sub-queries");
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc) rc = hvs_set_query_vectors(c, vec_offsets, vecs, nq);
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+
+int hvs_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
+{
+    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_vectors_stats: not supported (yet) on a row-partitioned context");
+    return call_stats<hvs_vectors_info>(c, out, leaf_vectors_stats, [](hvs_vectors_info& sum, const hvs_vectors_info& m) {
+        sum.multi_queries += m.multi_queries;
+        sum.sub_queries += m.sub_queries;
+        sum.max_vectors = std::max(sum.max_vectors, m.max_vectors);
+        sum.underfull_queries += m.underfull_queries;
+        sum.merged_keys += m.merged_keys;
+        sum.duplicate_keys += m.duplicate_keys;
+        sum.expand_ms = std::max(sum.expand_ms, m.expand_ms);
+        sum.merge_ms = std::max(sum.merge_ms, m.merge_ms);
+    });
 }
 
 // ---- live-row mask ---------------------------------------------------------------------------

@@ -1265,3 +1265,220 @@ __global__ __launch_bounds__(256) void hvs_k_in_fill(const float* __restrict__ Q
         value[s0 + rank] = mine;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Multi-vector queries (hvs_set_query_vectors / hvs_query_vectors): user query q carries m(q) EXTRA vectors beside
+// its own, given in CSR form (off[nq + 1], vecs[off[nq]][100]), and asks for the k rows with the smallest MINIMUM key over its
+// 1 + m(q) vectors.  It is answered as 1 + m(q) ordinary sub-queries with padding off -- the second client of the expanded
+// resident set category sets built --, and hvs_k_merge_vectors merges their lists BY ID: the sub-lists are not disjoint.
+// The plan needs no scan: sub_off[q] = off[q] + q, and sub-query j of parent p reads extra vector j - p - 1 (j > sub_off[p]).
+// ---------------------------------------------------------------------------------------------
+#define HVS_VEC_MAX_EXTRA_ 63u  // (= HVS_VECTORS_MAX_EXTRA of include/hvs.h; hvs.hip asserts it)
+#define HVS_VEC_BAD_FIRST 1u    // status flags: offsets[0] != 0
+#define HVS_VEC_BAD_ORDER 2u    // ... a descending pair of offsets
+#define HVS_VEC_BAD_LONG 4u     // ... more than HVS_VECTORS_MAX_EXTRA extras on one query
+
+// status[0] |= flags, status[1] = offsets[0], status[2] = offsets[nq] (to be trusted only if no flag is set).  `first`: the
+// offsets are the head of the caller's array (a slice further in starts anywhere).  After hvs_k_check_exclude.
+__global__ void hvs_k_check_vectors(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t flags = 0u;
+    if (q == 0u) {
+        if (first && off[0] != 0u) flags |= HVS_VEC_BAD_FIRST;
+        status[1] = off[0];
+        status[2] = off[nq];
+    }
+    if (q < nq) {
+        const uint32_t a = off[q], b = off[q + 1u];
+        if (b < a)
+            flags |= HVS_VEC_BAD_ORDER;
+        else if (b - a > HVS_VEC_MAX_EXTRA_)
+            flags |= HVS_VEC_BAD_LONG;
+    }
+    if (flags) atomicOr(&status[0], flags);
+}
+
+// The plan of checked offsets (one GPU's slice, off[0] = lo): sub_off[q] = off[q] - lo + q, parent = q for the query's
+// 1 + m(q) <= 64 sub-queries.  One thread per user query (thread nq writes the last offset).
+__global__ void hvs_k_fill_vectors(const uint32_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ sub_off, uint32_t* __restrict__ parent)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q > nq) return;
+    const uint32_t lo = off[0];
+    const uint32_t s0 = off[q] - lo + q;
+    sub_off[q] = s0;
+    if (q == nq) return;
+    uint32_t m = off[q + 1u] - off[q];
+    if (m > HVS_VEC_MAX_EXTRA_) m = HVS_VEC_MAX_EXTRA_;  // (refused by the host before this launch; never trusted here)
+    for (uint32_t j = 0; j <= m; ++j) parent[s0 + j] = q;
+}
+
+// Sub-query j = the 26 float4s of user query parent[j]; float4s 1..25 (the vector) come from extra vector j - p - 1 of `vecs`
+// (this GPU's slice of the extras, 25 float4s each) when j is not the parent's first sub-query.  One thread per float4,
+// consecutive threads consecutive float4s, like hvs_k_expand_in.
+__global__ __launch_bounds__(256) void hvs_k_expand_vectors(const float4* __restrict__ Qu, const uint32_t* __restrict__ parent,
+                                                           const uint32_t* __restrict__ sub_off, const float4* __restrict__ vecs, uint32_t nsub,
+                                                           float4* __restrict__ Qx)
+{
+    static_assert(HVS_QCOLS % 4u == 0u && HVS_NDIM % 4u == 0u && HVS_QCOLS == HVS_NDIM + 4u, "rows are moved in 16-byte pieces");
+    constexpr uint32_t P = HVS_QCOLS / 4u, V = HVS_NDIM / 4u;
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (uint64_t)nsub * P) return;
+    const uint32_t j = (uint32_t)(e / P), c = (uint32_t)(e - (uint64_t)j * P);
+    const uint32_t p = parent[j];
+    const bool own = c == 0u || j == sub_off[p];
+    Qx[e] = own ? Qu[(size_t)p * P + c] : vecs[(size_t)(j - p - 1u) * V + (c - 1u)];
+}
+
+// The wave's key buffer buf[0 .. cnt) de-duplicated BY ID, in place: per id the smallest key stays, and one of two equal
+// keys.  How: the keys are rotated to (id << 32 | distance bits) and sorted by a bitonic network over the next power of two
+// >= 64 (the tail filled with ~0, which no key is: an id of 0xFFFFFFFF names no row) -- equal ids are then neighbours, the
+// smallest distance first --, and the first of every run is kept by a ballot compaction that rotates it back.  P log2(P)
+// (log2(P) + 1) / 4 compare-exchanges over 64 lanes: 36 rounds of 2 per lane at P = 256, 45 of 4 at P = 512 (an all-pairs
+// scan would read P keys per key: 1024 / 4096 LDS reads per lane).  The buffer is left in id order, which the radix select
+// and the rank sort behind it do not mind.  Returns the keys left.  Wave-uniform: all 64 lanes call it.
+template <int CAP>
+__device__ __forceinline__ uint32_t hvs_wave_dedup_ids(uint64_t* buf, uint32_t cnt, uint32_t lane)
+{
+    uint32_t P = 64u;
+    while (P < cnt) P <<= 1;  // (cnt <= CAP, a power of two: P <= CAP)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (uint32_t e = lane; e < P; e += 64u) {
+        const uint64_t k = e < cnt ? buf[e] : ~0ull;
+        buf[e] = (k << 32) | (k >> 32);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (uint32_t k = 2u; k <= P; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            for (uint32_t i = lane; i < P; i += 64u) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint64_t a = buf[i], b = buf[l];
+                    if ((a > b) == ((i & k) == 0u)) {
+                        buf[i] = b;
+                        buf[l] = a;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+    }
+    uint32_t kept = 0;
+    uint32_t prev_id = 0xFFFFFFFFu;  // id in front of the chunk (no key has it: the first entry is always kept)
+    for (uint32_t off = 0; off < cnt; off += 64u) {  // (wave-uniform; a chunk's keys land at or below their own places)
+        const uint32_t e = off + lane;
+        const uint64_t r = e < cnt ? buf[e] : ~0ull;
+        const uint32_t id = (uint32_t)(r >> 32);
+        const uint32_t left = (uint32_t)__shfl_up((int)id, 1);
+        const uint32_t before = lane == 0u ? prev_id : left;
+        prev_id = (uint32_t)__shfl((int)id, 63);  // (read before this chunk's stores may overwrite the entry)
+        const bool in = e < cnt && id != before;
+        const uint64_t m = __ballot(in);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        if (in) buf[kept + hvs_prefix_count(m)] = (r << 32) | (r >> 32);
+        kept += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    return kept;
+}
+
+// hvs_k_merge_vectors -- per user query (one wave, four per workgroup): the result rows of its 1 + m sub-queries, rows
+// [sub_off[q], sub_off[q + 1]) x knn of the engines' result buffer (padding off: 0xFFFFFFFF = empty slot, ids global), are
+// streamed through the wave's key buffer, 64 slots at a time.  The same row turns up in several lists with different keys, so
+// this is not hvs_k_merge_in: whenever the next 64 slots might not fit (held + 64 > CAP) the buffer is first DE-DUPLICATED by id
+// (hvs_wave_dedup_ids), and only if they still might not fit cut back to its knn smallest keys -- a cut over duplicates could
+// keep two keys of one row and drop a row the answer needs; after de-duplication a dropped row has knn distinct rows in front of
+// it, whose keys only shrink as more lists arrive, and a later, smaller key of the dropped row is gathered again.  knn + 64 <=
+// CAP, so the step then fits.  Once more at the end: de-duplicate, then select -- the keys are distinct whenever
+// hvs_wave_select_prune runs, the exact duplicate (equal vectors) included.  Caps and exclusion lists were applied by the
+// sub-queries.  Padding as hvs_k_merge_in: slot cnt + s takes row n - 1 - s or pad_ids[s], with the smallest key over the
+// query's vectors, read from the EXPANDED rows Qx[sub_off[q] .. sub_off[q + 1]); pad == 0 leaves the largest key.
+// stat[0] += 1 for an under-full query, stat[1] += keys read, stat[2] += keys dropped because the buffer held the id with a key
+// at least as small.  Queries [q0, q0 + nq) of the user's set.
+template <bool SCALAR_ORDER, int CAP>
+__global__ __launch_bounds__(256) void hvs_k_merge_vectors(const uint32_t* __restrict__ sub_off, uint32_t q0, uint32_t nq, const uint32_t* __restrict__ sub_ids,
+                                                           const float* __restrict__ sub_dists, const float* __restrict__ D, uint32_t n,
+                                                           const float* __restrict__ Qx, int pad, const uint32_t* __restrict__ pad_ids,
+                                                           uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+                                                           unsigned long long* __restrict__ stat)
+{
+    __shared__ uint64_t sbuf[4][CAP];
+    __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 4u + w;
+    if (i >= nq) return;  // wave-uniform; waves never meet at a barrier
+    const uint32_t q = q0 + i;
+    uint64_t* buf = sbuf[w];
+    const uint32_t s0 = sub_off[q], s1 = sub_off[q + 1u];
+    uint32_t cnt = 0, seen = 0, dups = 0;
+    for (uint32_t s = s0; s < s1; ++s) {
+        const uint32_t* __restrict__ ids = sub_ids + (size_t)s * knn;
+        const float* __restrict__ dists = sub_dists + (size_t)s * knn;
+        for (uint32_t off = 0; off < knn; off += 64u) {
+            if (cnt + 64u > (uint32_t)CAP) {
+                const uint32_t left = hvs_wave_dedup_ids<CAP>(buf, cnt, lane);
+                dups += cnt - left;
+                cnt = left;
+                if (cnt + 64u > (uint32_t)CAP) {  // (cnt > knn: knn + 64 <= CAP)
+                    hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+                    cnt = knn;
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                }
+            }
+            const uint32_t e = off + lane;
+            const uint32_t id = e < knn ? ids[e] : 0xFFFFFFFFu;
+            const bool have = id != 0xFFFFFFFFu;
+            const uint64_t m = __ballot(have);
+            if (have) buf[cnt + hvs_prefix_count(m)] = hvs_make_key(dists[e], id);
+            cnt += (uint32_t)__popcll(m);
+            seen += (uint32_t)__popcll(m);
+        }
+    }
+    if (s1 - s0 > 1u) {  // (one list holds every id once)
+        const uint32_t left = hvs_wave_dedup_ids<CAP>(buf, cnt, lane);
+        dups += cnt - left;
+        cnt = left;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (lane == 0u) {
+        if (cnt < knn) atomicAdd(&stat[0], 1ull);
+        if (seen) atomicAdd(&stat[1], (unsigned long long)seen);
+        if (dups) atomicAdd(&stat[2], (unsigned long long)dups);
+    }
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) {
+            uint64_t key = ~0ull;
+            if (pad) {
+                const uint32_t s = e - cnt;  // (< knn <= live rows: host)
+                const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
+                const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
+                for (uint32_t j = s0; j < s1; ++j) {
+                    const float* __restrict__ qv = Qx + (size_t)j * HVS_QCOLS + 4;
+                    const uint64_t kj = hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
+                    key = kj < key ? kj : key;
+                }
+            }
+            buf[e] = key;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

@@ -16,6 +16,7 @@ _HDR = os.path.join(_REPO, "include", "hvs.h")
 
 ENGINE_AUTO, ENGINE_EXACT_SCAN, ENGINE_MFMA_FILTER, ENGINE_MFMA_I8, ENGINE_MFMA_F16 = 0, 1, 2, 3, 4
 K, DCOLS, QCOLS = 100, 102, 104
+NDIM = 100  # floats of a vector (a query row: 4 attribute floats + NDIM)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -118,8 +119,18 @@ class ExcludeInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class VectorsInfo(C.Structure):
+    """hvs_vectors_info (include/hvs.h)."""
+    _fields_ = [("multi_queries", C.c_uint32), ("sub_queries", C.c_uint32), ("max_vectors", C.c_uint32), ("underfull_queries", C.c_uint32),
+                ("merged_keys", C.c_uint64), ("duplicate_keys", C.c_uint64), ("expand_ms", C.c_double), ("merge_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
+VECTORS_MAX_EXTRA = 63
 
 
 def library_path():
@@ -289,6 +300,12 @@ def library():
         "hvs_exclude_stats": (C.c_int, [vp, C.POINTER(ExcludeInfo)]),
         "hvs_download_exclude_plan": (C.c_int, [vp, _u32p, _u32p, _u32p, C.c_uint32]),
         "hvs_exclude_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
+        "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
+        "hvs_set_query_vectors_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "hvs_query_vectors": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_vectors_stats": (C.c_int, [vp, C.POINTER(VectorsInfo)]),
+        "hvs_vectors_plan": (C.c_uint32, [_u32p, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
+        "hvs_vectors_check": (C.c_uint32, [_u32p, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -517,6 +534,52 @@ def in_plan(q_rows, sets, want=True):
             or value[nsub] != np.float32(-12345.0):
         raise HvsError(-1, "hvs_in_plan wrote past its outputs")
     return int(nsub), sub[:nq + 1].copy(), parent[:nsub].copy(), value[:nsub].copy()
+
+
+def _vectors_csr(vectors):
+    """Extra query vectors as (offsets uint32[nq + 1], vecs float32[total, 100]): from a LIST of per-query [m_i, 100] arrays
+    (an empty one leaves the query plain), or a TUPLE (offsets, vecs) passed through as it is (so that a malformed CSR reaches
+    the library)."""
+    if isinstance(vectors, tuple) and len(vectors) == 2:
+        off = np.ascontiguousarray(vectors[0], np.uint32).ravel()
+        vecs = np.ascontiguousarray(vectors[1], np.float32).reshape(-1, NDIM)
+        return off, vecs
+    rows = [np.asarray(v, np.float32).reshape(-1, NDIM) for v in vectors]
+    off = np.zeros(len(rows) + 1, np.uint32)
+    if rows:
+        off[1:] = np.cumsum([r.shape[0] for r in rows], dtype=np.uint64)
+    vecs = np.ascontiguousarray(np.concatenate(rows) if rows else np.empty((0, NDIM)), np.float32)
+    return off, vecs
+
+
+def vectors_check(offsets):
+    """hvs_vectors_check: the sub-queries nsub = offsets[nq] + nq of vector offsets (nq + 1 entries), or None when they are refused
+    (offsets[0] != 0, a descending pair, more than VECTORS_MAX_EXTRA extras on a query, too many sub-queries)."""
+    off = np.ascontiguousarray(offsets, np.uint32).ravel()
+    if off.size == 0:
+        raise HvsError(-1, "vectors_check: the offsets need nq + 1 entries")
+    nsub = library().hvs_vectors_check(_up(off), off.size - 1)
+    return None if nsub == 0xFFFFFFFF else int(nsub)
+
+
+def vectors_plan(ids, dists, pad_ids=None, pad_dists=None, padding=True):
+    """hvs_vectors_plan: the unpadded answer rows of ONE query's vectors (m x k ids and distances; empty slots 0xFFFFFFFF / +inf)
+    -> (ids, dists, n_rows, n_duplicates) of the merged row: per id the smallest key, the first k, padded from pad_ids /
+    pad_dists (the first k padding rows, the distances already the minimum over the vectors) when `padding`."""
+    ids = np.ascontiguousarray(ids, np.uint32)
+    dists = np.ascontiguousarray(dists, np.float32)
+    if ids.ndim != 2 or dists.shape != ids.shape:
+        raise HvsError(-1, "vectors_plan: ids and dists must be m x k each")
+    m, k = ids.shape
+    if padding:
+        pad_ids = np.ascontiguousarray(pad_ids, np.uint32).ravel()
+        pad_dists = np.ascontiguousarray(pad_dists, np.float32).ravel()
+        if pad_ids.size < k or pad_dists.size < k:
+            raise HvsError(-1, "vectors_plan: padding needs k pad ids and k pad distances")
+    out_ids, out_d, dup = np.empty(k, np.uint32), np.empty(k, np.float32), C.c_uint32(0)
+    kept = library().hvs_vectors_plan(_up(ids) if m else None, _fp(dists) if m else None, m, k, _up(pad_ids) if padding else None,
+                                      _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids), _fp(out_d), C.byref(dup))
+    return out_ids, out_d, int(kept), int(dup.value)
 
 
 def _device_u32(x, what):
@@ -974,6 +1037,55 @@ class Engine:
         """hvs_in_stats: queries answered through their sets, sub-queries, under-full queries, merge time of the last call."""
         s = InInfo()
         self._ck(self._lib.hvs_in_stats(self._h, C.byref(s)))
+        return s
+
+    # --- multi-vector queries (include/hvs.h "multi-vector queries")
+    def set_query_vectors(self, vectors, stream=None):
+        """Attach extra vectors to the resident queries -- a list of per-query [m_i, 100] arrays (an empty one leaves the query
+        plain) or an (offsets, vecs) CSR pair of host arrays --, or None to remove them.  A query then asks for the k rows
+        nearest to ANY of its vectors (its own and the extras), each row once.  Caps and exclusion lists are attached
+        afterwards; cursors are refused meanwhile.  A pair of GPU tensors -- offsets int32 / uint32 with nq + 1 entries, vecs
+        float32 [total, 100] or None, both contiguous -- goes to hvs_set_query_vectors_device: the vectors never reach the host
+        (`stream` as for set_queries_device)."""
+        if vectors is None:
+            self._ck(self._lib.hvs_set_query_vectors(self._h, None, None, 0))
+            return
+        if isinstance(vectors, tuple) and len(vectors) == 2 and any(hasattr(x, "data_ptr") and hasattr(x, "shape") for x in vectors):
+            po, n = _device_u32(vectors[0], "set_query_vectors")
+            pv = 0 if vectors[1] is None else _device_rows(vectors[1], None, NDIM, "set_query_vectors")[0]
+            self.set_query_vectors_device(po, pv, max(n, 1) - 1, stream=stream)
+            return
+        off, vecs = _vectors_csr(vectors)
+        self._ck(self._lib.hvs_set_query_vectors(self._h, _up(off) if off.size else None, _fp(vecs) if vecs.size else None,
+                                                 max(off.size, 1) - 1))
+
+    def set_query_vectors_device(self, offsets_ptr, vecs_ptr, nq, stream=None):
+        """hvs_set_query_vectors_device from two raw pointers (0 / None = NULL) and the number of queries."""
+        po, pv = int(offsets_ptr or 0), int(vecs_ptr or 0)
+        self._ck(self._lib.hvs_set_query_vectors_device(self._h, C.c_void_p(po) if po else None, C.c_void_p(pv) if pv else None, int(nq),
+                                                        _stream_ptr(stream)))
+
+    def query_vectors(self, q_rows, vectors, sample_proportion=1.0, want_dists=True):
+        """hvs_query_vectors: host rows and their extra vectors in, host ids (and distances) out; vectors = None is query()."""
+        q = np.ascontiguousarray(q_rows, np.float32)
+        if q.ndim != 2 or q.shape[1] != QCOLS:
+            raise HvsError(-1, "query rows must be nq x 104 float32")
+        nq, K = q.shape[0], self.k
+        ids = np.empty((nq, K), np.uint32)
+        d = np.empty((nq, K), np.float32) if want_dists else None
+        off, vecs = (None, None) if vectors is None else _vectors_csr(vectors)
+        if off is not None and off.size != nq + 1:
+            raise HvsError(-1, "query_vectors: one vector list per query")
+        self._ck(self._lib.hvs_query_vectors(self._h, _fp(q), _up(off) if off is not None else None,
+                                             _fp(vecs) if vecs is not None and vecs.size else None, nq, sample_proportion, _up(ids),
+                                             _fp(d) if want_dists else None))
+        return (ids, d) if want_dists else ids
+
+    def vector_stats(self):
+        """hvs_vectors_stats: multi-vector queries, sub-queries, under-full queries, merged and duplicate keys, merge time of the
+        last call."""
+        s = VectorsInfo()
+        self._ck(self._lib.hvs_vectors_stats(self._h, C.byref(s)))
         return s
 
     # --- resident variant
