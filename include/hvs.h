@@ -886,6 +886,100 @@ uint32_t hvs_vectors_plan(const uint32_t *ids, const float *dists, uint32_t m, u
                           const float *pad_dists, int padding, uint32_t *out_ids, float *out_dists, uint32_t *n_duplicates);
 uint32_t hvs_vectors_check(const uint32_t *offsets, uint32_t nq);
 
+/* ---- query clauses: the k nearest rows matching any of several clauses ------------------------------ */
+/*
+ * "C in {3, 7} and near any of my three interest vectors"; "T in last week OR in the same week last year"; "(C = 1 and T < t0)
+ * or C = 2": a query that is an OR of CLAUSES, each a predicate [type, v, l, r] -- exactly the first four floats of a Q row --
+ * plus, optionally, a vector of its own.  Extra clauses are attached to the resident queries in CSR form: clause_offsets[nq + 1]
+ * (u32, ascending, [0] == 0), clause_attrs[clause_offsets[nq]][4] (f32) and clause_vecs, either NULL ("predicate-only clauses")
+ * or [clause_offsets[nq]][100] (f32).
+ *
+ * Definition.  User query q has the clause list K(q): clause 0 is q's own row, its four attribute floats and its vector; then
+ * come its m(q) = clause_offsets[q + 1] - clause_offsets[q] extras, extra j with attributes clause_attrs[j] and the vector
+ * clause_vecs[j], or q's own vector when clause_vecs == NULL.  A row PASSES clause c if it passes c's predicate exactly as a plain
+ * query with those four floats would (an invalid type keeps whatever meaning it has for a plain query).  The key of a row for q
+ * is the SMALLEST key (distance bits, id) over the clauses it passes, in the engines' own key order; each distance is the
+ * engine's exact-order f32 distance to that clause's vector.  The answer is the first k rows in key order among the rows that
+ * pass at least one clause, lie in the sampled prefix, are live, have `min key's distance <= cap` if caps are set, are not in
+ * q's exclusion list and, where cursors are allowed (below), have a key strictly after the cursor.  Every id appears at most once
+ * among the non-pad slots.  The usual padding is applied ONCE, a pad row reporting its smallest distance over the vectors of
+ * K(q); with hvs_set_padding(ctx, 0) the unmatched slots are 0xFFFFFFFF / +inf.  A query with m(q) == 0 is the plain query, bit
+ * for bit.
+ *
+ * How: q runs as 1 + m(q) ordinary SUB-QUERIES with padding off on the expanded resident set that category sets and extra vectors
+ * use (its third client), and one kernel merges the sub-lists by id.  Exact by the argument of the multi-vector queries with
+ * "vector j" read as "clause j": a row of the answer that attains its minimum at clause j is in sub-list j -- otherwise k rows
+ * passing clause j would have smaller keys, hence smaller minimum keys --, and a row outside the answer only ever shows a key at
+ * or above its true one.  The merged row's arithmetic for one query is hvs_vectors_plan's: the smallest key per id,
+ * the k smallest, pad once; there is no second copy of it.
+ *
+ * hvs_timing.pairs counts (clause, row) pairs, the sub-queries' sum: a row passing two clauses counts twice.
+ *
+ * Cursors.  With predicate-only clauses every row has ONE key whichever clause admits it, so each sub-query applies the cursor
+ * itself and the merge by id drops the equal duplicates: hvs_set_after, hvs_set_after_device and hvs_set_after_from_results work
+ * (the last one reads the merged rows), and the paging law of the cursors holds.  With clause_vecs != NULL (and at least one extra
+ * clause in the whole CSR: without any, the pointer means nothing) they return HVS_ESTATE and change nothing, for the reason given for extra vectors; paging goes through exclusion lists there.
+ *
+ * Composes with every engine, both distance orders, every k, sample_proportion, padding on and off, caps, exclusion lists, the
+ * live-row mask, appended and updated rows and compaction; caps, cursors and lists stay one per USER query, each sub-query reads
+ * its parent's.  One GPU and replicated multi-GPU contexts (each GPU takes its owner range's slice of the CSR; attached on all
+ * GPUs or on none); a row-partitioned context returns HVS_ESTATE and changes nothing.
+ *
+ * Lifetime: that of extra vectors.  There is one expanded set per context: attaching clauses replaces category sets or vectors,
+ * attaching category sets or vectors replaces clauses, and removing one client is a no-op while another is attached.  Clauses
+ * belong to the resident query set: hvs_upload_queries, hvs_gen_queries, hvs_set_queries_device, hvs_set_queries_from_rows and
+ * hvs_query* remove them, and so does hvs_set_query_clauses(ctx, NULL, NULL, NULL, 0).  Attaching or removing clauses drops
+ * earlier results and removes caps, cursors and exclusion lists: attach those afterwards.  hvs_download_queries keeps returning
+ * the user's rows; hvs_reserve(nq) sizes for the sub-queries; hvs_last_timing reports the user's nq and a query_ms that includes
+ * the merge; hvs_last_reruns speaks sub-query indices; hvs_in_stats and hvs_vectors_stats report zeros after a clause call.  While
+ * no clauses are attached every call runs exactly the kernels it runs without these functions, with exactly the same arguments.
+ *
+ * Limits.  At most HVS_CLAUSES_MAX_EXTRA extras per query (256 lists per merge), at most 2^32 - 2 sub-queries in all.  A longer
+ * list, clause_offsets[0] != 0, a descending pair of offsets, nq != the number of resident queries, or clause_attrs == NULL while
+ * clause_offsets[nq] > 0: HVS_EINVAL, and nothing changes -- clauses already attached, results, caps, cursors and lists stay in
+ * force.  No data set loaded: HVS_ESTATE.  Attribute and vector values are not validated.
+ *
+ * hvs_set_query_clauses: the CSR from HOST memory; all pointers NULL (or nq == 0) removes the clauses.
+ * hvs_set_query_clauses_device: the same from DEVICE memory by the rules of hvs_set_query_vectors_device -- plain device memory of
+ * any visible GPU, all buffers on the same one; host memory of any kind is HVS_EINVAL with the runtime's error cleared; the call
+ * blocks until the clauses are attached.  It is accepted exactly when the host call accepts the same bytes.  Attributes and
+ * vectors never cross PCIe: the host reads back the status block and the offsets only.
+ * hvs_query_clauses: hvs_upload_queries + hvs_set_query_clauses + hvs_query_resident + hvs_download_results in one call, the steps
+ * one after the other.  All clause pointers NULL: exactly hvs_query.
+ * hvs_clauses_stats: figures of the last call (after hvs_sync); HVS_ESTATE where hvs_last_timing has none to report; all zero when
+ * the last call ran without clauses.  The merge streams a query's lists in sub-query order, 64 slots (a CHUNK) at a time, through a
+ * buffer of CAP = 256 (k <= 128) or 512 keys.  Before a chunk that might not fit (held + 64 > CAP) it de-duplicates the buffer by
+ * id and, if the chunk still might not fit, CUTS it to the k smallest keys; the largest key kept becomes the threshold.  A loaded
+ * key is admitted only if it is strictly below the threshold, and after a chunk in which some slot was empty or not below the
+ * threshold the rest of that list is not loaded (lists ascend).  It de-duplicates once more at the end.  read_keys: the non-empty
+ * slots loaded.  duplicate_keys: keys a de-duplication dropped.  bounded_keys: keys loaded and not admitted.  skipped_chunks:
+ * chunks never loaded.  Multi-GPU contexts: counters summed, max_clauses the largest, the two times the slowest GPU's.
+ * hvs_clauses_check: the offsets' arithmetic on the host, no GPU: nsub = offsets[nq] + nq, or 0xFFFFFFFF for offsets == NULL,
+ * offsets[0] != 0, a descending pair, a list of more than HVS_CLAUSES_MAX_EXTRA, or more than 2^32 - 2 sub-queries.  The device
+ * check reproduces it.
+ */
+#define HVS_CLAUSES_MAX_EXTRA 255
+typedef struct hvs_clauses_info {
+    uint32_t clause_queries;    /* queries of the last call with at least one extra clause                    */
+    uint32_t sub_queries;       /* sub-queries the engines answered for the call's queries                    */
+    uint32_t max_clauses;       /* most clauses (1 + extras) of one query of the call                         */
+    uint32_t underfull_queries; /* queries with fewer than k distinct rows in all their sub-lists together    */
+    uint64_t read_keys;         /* non-empty slots the merge loaded                                           */
+    uint64_t duplicate_keys;    /* keys dropped at a de-duplication                                           */
+    uint64_t bounded_keys;      /* keys loaded and not admitted because they were not below the threshold     */
+    uint64_t skipped_chunks;    /* 64-slot chunks never loaded                                                */
+    double   expand_ms;         /* device time of the expansion when the clauses were attached                */
+    double   merge_ms;          /* device time of the call's merge kernel                                     */
+} hvs_clauses_info;
+int hvs_set_query_clauses(hvs_ctx *ctx, const uint32_t *clause_offsets /* host, nq+1 */, const float *clause_attrs /* host, x 4 */,
+                          const float *clause_vecs /* host, x 100, may be NULL */, uint32_t nq);
+int hvs_set_query_clauses_device(hvs_ctx *ctx, const uint32_t *d_offsets /* device, nq+1 */, const float *d_attrs /* device, x 4 */,
+                                 const float *d_vecs /* device, x 100, may be NULL */, uint32_t nq, void *stream);
+int hvs_query_clauses(hvs_ctx *ctx, const float *q_rows, const uint32_t *clause_offsets, const float *clause_attrs,
+                      const float *clause_vecs, uint32_t nq, float sample_proportion, uint32_t *out_ids, float *out_dists);
+int hvs_clauses_stats(hvs_ctx *ctx, hvs_clauses_info *out);
+uint32_t hvs_clauses_check(const uint32_t *offsets, uint32_t nq);
+
 #ifdef __cplusplus
 }
 #endif

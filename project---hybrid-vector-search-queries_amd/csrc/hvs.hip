@@ -227,9 +227,10 @@ struct HvsPerQuery {
 // result rows.  Every resident index of the C ABI is a user index; in_* functions below translate.  Not active: nothing here is
 // read, and the buffers are kept for the next attach.
 struct HvsInSet {
-    // The expanded set has two clients: category sets, and extra query vectors.  Everything that ties user queries
-    // to sub-query ranges below is shared; the clients differ in the expand kernel, the merge kernel and their stats.
-    enum Kind { Sets, Vectors };
+    // The expanded set has three clients: category sets, extra query vectors, and extra clauses.  Everything
+    // that ties user queries to sub-query ranges below is shared; the clients differ in staging and check, the fill and expand
+    // kernels, the merge kernel and their stats.
+    enum Kind { Sets, Vectors, Clauses };
     bool active = false;
     Kind kind = Sets;                  // (while active) what the sub-queries of a user query are
     uint32_t nuq = 0;
@@ -246,11 +247,18 @@ struct HvsInSet {
     uint32_t v_off_cap = 0;            // user queries d_v_off has room for (+ 1 entry)
     size_t vecs_cap = 0;               // vectors d_vecs has room for
     uint32_t v_flags = 0, v_base = 0, v_total = 0;  // of the offsets staged last: HVS_VEC_BAD_*, offsets[0], offsets[nq]
+    // extra clauses: staged and checked in d_v_off / d_v_status as the vectors' offsets are; their [type, v, l, r], 4 floats each,
+    // and, where they bring vectors of their own (clause_vecs, while active), those in d_vecs
+    float* d_attrs = nullptr;
+    size_t attrs_cap = 0;              // clauses d_attrs has room for
+    bool clause_vecs = false;
     HvsPerQuery user;                  // the user's caps and cursors: room for uq_cap each, allocated at attach
     uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
     float* d_m_dists = nullptr;
     size_t m_cap = 0;                  // entries
-    unsigned long long* d_stat = nullptr;  // [0] under-full queries, [1] keys read, [2] (vectors) duplicates dropped: of the last merge
+    // of the last merge: [0] under-full queries, [1] keys read, [2] (vectors, clauses) duplicates dropped, (clauses) [3] keys
+    // not below the threshold, [4] chunks never loaded
+    unsigned long long* d_stat = nullptr;
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;  // around the expansion / the last merge
     double expand_ms = 0.0;
     // scratch of a plan made on the device (hvs_set_category_sets_device): nothing here is in force, in_commit takes from it
@@ -268,9 +276,9 @@ struct HvsInSet {
     {
         HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_m_ids, d_m_dists, d_stat);
         HvsRowSet::drop(d_p_pack, d_p_sub_off, d_p_eff, d_p_stat, d_p_off, d_p_vals);
-        HvsRowSet::drop(d_v_off, d_v_status, d_vecs);
+        HvsRowSet::drop(d_v_off, d_v_status, d_vecs, d_attrs);
         p_cap = p_off_cap = pv_cap = v_off_cap = 0;
-        vecs_cap = 0;
+        vecs_cap = attrs_cap = 0;
         user.free_device();
         for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
             if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
@@ -3169,6 +3177,7 @@ int in_detach(hvs_ctx* c)
 // ... of one client only: removing category sets leaves extra vectors alone, and the other way round
 int sets_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Sets ? HVS_OK : in_detach(c); }
 int vectors_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Vectors ? HVS_OK : in_detach(c); }
+int clauses_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Clauses ? HVS_OK : in_detach(c); }
 
 // Attaching sets to one GPU's `nuq` user queries has two halves: a PLAN is made -- on the host from a host CSR (in_plan_host),
 // or by the plan kernels from a CSR in device memory (in_plan_device) --, which changes nothing a query or a later call reads,
@@ -3192,8 +3201,11 @@ struct InPlan {
     // extra vectors (kind == Vectors): the slice's offsets are staged and checked in HvsInSet::d_v_off (vec_stage); `vecs` = the
     // first vector of the slice, nsub - nuq of them, in host memory (vec_dev < 0) or on GPU vec_dev.  The fill kernel writes
     // sub_off and parent from the staged offsets: nothing of size nsub is built on the host.
+    // Extra clauses (kind == Clauses) likewise; `attrs` = the slice's first clause, 4 floats each, where `vecs` is; vecs ==
+    // nullptr: predicate-only clauses.
     HvsInSet::Kind kind = HvsInSet::Sets;
     const float* vecs = nullptr;
+    const float* attrs = nullptr;
     int vec_dev = -1;
 };
 
@@ -3202,7 +3214,7 @@ int in_begin(hvs_ctx* c)
 {
     int rc = begin_mutation(c);
     if (!rc) rc = in_ensure_events(c);
-    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)3);
+    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)5);
     return rc;
 }
 
@@ -3345,9 +3357,25 @@ int in_commit(hvs_ctx* c, InPlan& P)
         S.sub_cap = nsub;
     }
     if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
-    const bool vectors = P.kind == HvsInSet::Vectors;
-    const char* const what = vectors ? "hvs_set_query_vectors" : "hvs_set_category_sets";
-    if (vectors) {
+    const bool clauses = P.kind == HvsInSet::Clauses;
+    const bool vectors = P.kind == HvsInSet::Vectors || clauses;  // (the CSR clients: staged offsets, the fill kernel plans)
+    const char* const what = clauses ? "hvs_set_query_clauses" : vectors ? "hvs_set_query_vectors" : "hvs_set_category_sets";
+    if (clauses) {
+        const size_t ncl = (size_t)nsub - nuq;
+        if (ncl > S.attrs_cap) {
+            S.attrs_cap = 0;
+            if ((rc = dev_alloc(c, &S.d_attrs, ncl * 4u))) return lost(rc);
+            S.attrs_cap = ncl;
+        }
+        if (ncl) {
+            if (P.vec_dev >= 0)
+                rc = copy_from_device(c, S.d_attrs, P.attrs, P.vec_dev, ncl * 4u * sizeof(float));
+            else if (hipMemcpyAsync(S.d_attrs, P.attrs, ncl * 4u * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                rc = fail(c, HVS_EHIP, "hvs_set_query_clauses: upload of the clauses failed");
+            if (rc) return lost(rc);
+        }
+    }
+    if (vectors && (!clauses || P.vecs)) {
         const size_t nvec = (size_t)nsub - nuq;
         if (nvec > S.vecs_cap) {
             S.vecs_cap = 0;
@@ -3358,7 +3386,7 @@ int in_commit(hvs_ctx* c, InPlan& P)
             if (P.vec_dev >= 0)
                 rc = copy_from_device(c, S.d_vecs, P.vecs, P.vec_dev, nvec * HVS_NDIM * sizeof(float));
             else if (hipMemcpyAsync(S.d_vecs, P.vecs, nvec * HVS_NDIM * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                rc = fail(c, HVS_EHIP, "hvs_set_query_vectors: upload of the vectors failed");
+                rc = fail(c, HVS_EHIP, std::string(what) + ": upload of the vectors failed");
             if (rc) return lost(rc);
         }
     }
@@ -3374,7 +3402,15 @@ int in_commit(hvs_ctx* c, InPlan& P)
                up(S.d_value, P.value.data(), P.value.size() * sizeof(float)) != hipSuccess)
         return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
     (void)hipEventRecord(S.ev_x0, c->stream);
-    if (vectors) {
+    if (clauses) {
+        hipLaunchKernelGGL(hvs_k_fill_clauses, dim3(hvs_ceil_div(nuq + 1u, 4u)), dim3(256), 0, c->stream, S.d_v_off, nuq, S.d_sub_off, S.d_parent);
+        if (nsub) {
+            const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
+            hipLaunchKernelGGL(hvs_k_expand_clauses, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
+                               reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off, reinterpret_cast<const float4*>(S.d_attrs),
+                               P.vecs ? reinterpret_cast<const float4*>(S.d_vecs) : nullptr, nsub, reinterpret_cast<float4*>(c->d_q));
+        }
+    } else if (vectors) {
         hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(nuq + 1u, 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, S.d_sub_off, S.d_parent);
         if (nsub) {
             const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
@@ -3400,6 +3436,7 @@ int in_commit(hvs_ctx* c, InPlan& P)
     S.h_eff.swap(P.eff);
     c->nq = nsub;
     S.kind = P.kind;
+    S.clause_vecs = clauses && P.vecs;
     sets_changed(c, true);
     return HVS_OK;
 }
@@ -3415,13 +3452,15 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
 
 // ---- extra query vectors (include/hvs.h "multi-vector queries"): the second client of the expanded set ----
 static_assert(HVS_VEC_MAX_EXTRA_ == HVS_VECTORS_MAX_EXTRA && HVS_VECTORS_MAX_EXTRA + 1 <= 64, "a merge streams at most 64 sub-lists");
+// ... and extra clauses (include/hvs.h "query clauses"), the third: staged, checked and planned as the vectors are
+static_assert(HVS_CLAUSE_MAX_EXTRA_ == HVS_CLAUSES_MAX_EXTRA && HVS_CLAUSES_MAX_EXTRA + 1 == 256, "hvs_k_merge_clauses streams at most 256 sub-lists");
 
 // hvs_vectors_check's arithmetic
-uint32_t vec_check_core(const uint32_t* off, uint32_t nq)
+uint32_t vec_check_core(const uint32_t* off, uint32_t nq, uint32_t max_extra = HVS_VECTORS_MAX_EXTRA)
 {
     if (!off || off[0] != 0u) return 0xFFFFFFFFu;
     for (uint32_t q = 0; q < nq; ++q)
-        if (off[q + 1] < off[q] || off[q + 1] - off[q] > HVS_VECTORS_MAX_EXTRA) return 0xFFFFFFFFu;
+        if (off[q + 1] < off[q] || off[q + 1] - off[q] > max_extra) return 0xFFFFFFFFu;
     const uint64_t nsub = (uint64_t)off[nq] + nq;
     return nsub >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nsub;
 }
@@ -3431,7 +3470,8 @@ uint32_t vec_check_core(const uint32_t* off, uint32_t nq)
 // caller's array), and the host reads the status block back: v_flags / v_base / v_total.  Good offsets come back to the host
 // too (4 bytes per query): sub_off[q] = off[q] - off[0] + q, and hvs_query_resident maps query ranges to sub-query ranges there.
 // Nothing that a query or a later call reads changes; the caller judges the flags of all GPUs before any commit.
-int vec_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
+// `kind`: Vectors, or Clauses -- the same staging with the clauses' limit (hvs_k_check_clauses).
+int vec_stage(hvs_ctx* c, HvsInSet::Kind kind, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
 {
     HvsInSet& S = c->qs.in;
     int rc = in_begin(c);
@@ -3449,7 +3489,10 @@ int vec_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t nuq, bool f
         return rc;
     HVS_HIP(c, hipMemsetAsync(S.d_v_status, 0, 4 * sizeof(uint32_t), c->stream));
     HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
-    hipLaunchKernelGGL(hvs_k_check_vectors, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
+    if (kind == HvsInSet::Clauses)
+        hipLaunchKernelGGL(hvs_k_check_clauses, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
+    else
+        hipLaunchKernelGGL(hvs_k_check_vectors, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
     HVS_HIP(c, hipGetLastError());
     HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
     uint32_t h[4] = {0, 0, 0, 0};
@@ -3458,7 +3501,7 @@ int vec_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t nuq, bool f
     S.v_flags = h[0], S.v_base = h[1], S.v_total = h[2];
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
-    P->kind = HvsInSet::Vectors;
+    P->kind = kind;
     P->nuq = nuq;
     P->plan_ms = ms;
     if (S.v_flags) return HVS_OK;
@@ -3499,12 +3542,16 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         if ((rc = run_queries(c, s0, s1 - s0, sample_proportion, NoHook{}))) return rc;
         if ((rc = resolve_overflow(c))) return rc;
     }
-    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, 3 * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, (S.kind == HvsInSet::Clauses ? 5 : 3) * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipEventRecord(S.ev_m0, c->stream));
     if (nq) {
         with_cap(c->cap, [&](auto CAPT) {
             auto launch = [&](auto ST) {
-                if (S.kind == HvsInSet::Vectors)  // (merges by id, and pads from the EXPANDED rows: a pad row's smallest distance)
+                if (S.kind == HvsInSet::Clauses)  // (as the next one, for up to 256 lists, under a threshold)
+                    hipLaunchKernelGGL((hvs_k_merge_clauses<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
+                                       S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, c->d_q, c->padding ? 1 : 0,
+                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
+                else if (S.kind == HvsInSet::Vectors)  // (merges by id, and pads from the EXPANDED rows: a pad row's smallest distance)
                     hipLaunchKernelGGL((hvs_k_merge_vectors<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
                                        S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, c->d_q, c->padding ? 1 : 0,
                                        masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
@@ -3564,6 +3611,30 @@ int leaf_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
     out->underfull_queries = (uint32_t)v[0];
     out->merged_keys = v[1];
     out->duplicate_keys = v[2];
+    out->expand_ms = S.expand_ms;
+    out->merge_ms = ms;
+    return HVS_OK;
+}
+
+int leaf_clauses_stats(hvs_ctx* c, hvs_clauses_info* out)
+{
+    int rc = call_required(c);
+    if (rc) return rc;
+    *out = hvs_clauses_info{};
+    const HvsInSet& S = c->qs.in;
+    if (!S.call || S.call_kind != HvsInSet::Clauses) return HVS_OK;
+    unsigned long long v[5] = {0, 0, 0, 0, 0};
+    float ms = 0.f;
+    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    HVS_HIP(c, hipEventElapsedTime(&ms, S.ev_m0, S.ev_m1));
+    out->clause_queries = S.call_set_queries;
+    out->sub_queries = S.call_sub;
+    out->max_clauses = S.call_max_set;
+    out->underfull_queries = (uint32_t)v[0];
+    out->read_keys = v[1];
+    out->duplicate_keys = v[2];
+    out->bounded_keys = v[3];
+    out->skipped_chunks = v[4];
     out->expand_ms = S.expand_ms;
     out->merge_ms = ms;
     return HVS_OK;
@@ -4384,12 +4455,15 @@ int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const
 // caller).  A replicated context cuts it by the owner ranges.  Every GPU stages and checks its slice first and none changes
 // unless every slice is good and the sub-queries of the whole context can be counted in 32 bits: HVS_EINVAL leaves every GPU
 // as it was.  A failed commit (no room) leaves no GPU on an expanded set, as for category sets.
-int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int src_dev, uint32_t nq, const char* fn)
+// `kind` = Clauses: hvs_set_query_clauses*, the same protocol; `attrs` = the clauses' [type, v, l, r], where `vecs` is.
+int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int src_dev, uint32_t nq, const char* fn,
+                       HvsInSet::Kind kind = HvsInSet::Vectors, const float* attrs = nullptr)
 {
+    const bool clauses = kind == HvsInSet::Clauses;
     const size_t N = std::max<size_t>(c->kids.size(), 1u);
     std::vector<InPlan> plans(N);
     auto slot = [&](const hvs_ctx* k) { return c->kids.empty() ? (size_t)0 : (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin()); };
-    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return vec_stage(k, off + first, src_dev, m, first == 0u, &plans[slot(k)]); });
+    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return vec_stage(k, kind, off + first, src_dev, m, first == 0u, &plans[slot(k)]); });
     if (rc) {
         (void)hipGetLastError();
         return rc;
@@ -4404,14 +4478,18 @@ int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int s
     for (const hvs_ctx* k : c->kids) judge(k);
     if (flags)
         return fail(c, HVS_EINVAL,
-                    std::string(fn) + (flags & HVS_VEC_BAD_FIRST   ? ": vec_offsets[0] is not 0"
-                                       : flags & HVS_VEC_BAD_ORDER ? ": vec_offsets are not ascending"
+                    std::string(fn) + (flags & HVS_VEC_BAD_FIRST   ? (clauses ? ": clause_offsets[0] is not 0" : ": vec_offsets[0] is not 0")
+                                       : flags & HVS_VEC_BAD_ORDER ? (clauses ? ": clause_offsets are not ascending" : ": vec_offsets are not ascending")
+                                       : clauses                   ? ": a query has more than HVS_CLAUSES_MAX_EXTRA extra clauses"
                                                                    : ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"));
     if (total + nq >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": too many sub-queries");
-    if (total && !vecs) return fail(c, HVS_EINVAL, std::string(fn) + ": vecs is NULL");
+    if (total && clauses && !attrs) return fail(c, HVS_EINVAL, std::string(fn) + ": clause_attrs is NULL");
+    if (total && !clauses && !vecs) return fail(c, HVS_EINVAL, std::string(fn) + ": vecs is NULL");
     rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t, uint32_t) {
         InPlan& P = plans[slot(k)];
-        P.vecs = vecs ? vecs + (size_t)k->qs.in.v_base * HVS_NDIM : nullptr;
+        // (clauses without a single extra have no clause vectors whatever the pointer: every row has one key, cursors stay allowed)
+        P.vecs = vecs && !(clauses && total == 0u) ? vecs + (size_t)k->qs.in.v_base * HVS_NDIM : nullptr;
+        P.attrs = attrs ? attrs + (size_t)k->qs.in.v_base * 4u : nullptr;
         P.vec_dev = src_dev;
         return in_commit(k, P);
     });
@@ -4719,14 +4797,15 @@ uint32_t resident_count(const hvs_ctx* c)
     if (c->kids.empty()) return user_nq(c);
     return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
 }
-// extra vectors are attached (on every GPU or on none): cursors are refused meanwhile
+// extra vectors are attached (on every GPU or on none), or clauses with vectors of their own: cursors are refused meanwhile
+// (DESIGN 3.15, 3.16); predicate-only clauses give a row ONE key, and cursors go through leaf_attach as under category sets
 bool vectors_attached(const hvs_ctx* c)
 {
     const hvs_ctx* k = c->kids.empty() ? c : c->kids[0];
-    return k->qs.in.active && k->qs.in.kind == HvsInSet::Vectors;
+    return k->qs.in.active && (k->qs.in.kind == HvsInSet::Vectors || (k->qs.in.kind == HvsInSet::Clauses && k->qs.in.clause_vecs));
 }
 #define HVS_NO_CURSORS_ON_VECTORS(c, fn) \
-    if (vectors_attached(c)) return fail((c), HVS_ESTATE, fn ": cursors do not compose with extra query vectors (a row would come back under another vector)")
+    if (vectors_attached(c)) return fail((c), HVS_ESTATE, fn ": cursors do not compose with extra query vectors or clause vectors (a row would come back under another vector)")
 // what the four entry points that attach per-query values check alike: `nq` is the number of resident queries ...
 int check_resident_count(hvs_ctx* c, uint32_t nq, const char* fn)
 {
@@ -5989,6 +6068,79 @@ int hvs_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
         sum.underfull_queries += m.underfull_queries;
         sum.merged_keys += m.merged_keys;
         sum.duplicate_keys += m.duplicate_keys;
+        sum.expand_ms = std::max(sum.expand_ms, m.expand_ms);
+        sum.merge_ms = std::max(sum.merge_ms, m.merge_ms);
+    });
+}
+
+// ---- query clauses (include/hvs.h "query clauses") --------------------------------
+
+uint32_t hvs_clauses_check(const uint32_t* offsets, uint32_t nq) { return vec_check_core(offsets, nq, HVS_CLAUSES_MAX_EXTRA); }
+
+int hvs_set_query_clauses(hvs_ctx* c, const uint32_t* clause_offsets, const float* clause_attrs, const float* clause_vecs, uint32_t nq)
+{
+    static const char* const fn = "hvs_set_query_clauses";
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_clauses: not supported (yet) on a row-partitioned context");
+    if (!clause_offsets && !clause_attrs && !clause_vecs) return on_every_leaf(c, clauses_detach);
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!clause_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_clauses: clause_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    if (nq == 0u) return on_every_leaf(c, clauses_detach);
+    return vectors_everywhere(c, clause_offsets, clause_vecs, -1, nq, fn, HvsInSet::Clauses, clause_attrs);
+}
+
+int hvs_set_query_clauses_device(hvs_ctx* c, const uint32_t* d_offsets, const float* d_attrs, const float* d_vecs, uint32_t nq, void* stream)
+{
+    static const char* const fn = "hvs_set_query_clauses_device";
+    if (!c) return HVS_EINVAL;
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_clauses_device: not supported (yet) on a row-partitioned context");
+    if (!d_offsets && !d_attrs && !d_vecs) return on_every_leaf(c, clauses_detach);
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_clauses_device: d_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    if (nq == 0u) return on_every_leaf(c, clauses_detach);
+    int dev = 0, dev3 = 0;
+    if (d_vecs) {  // (the third buffer first: check_device_buffers ends with the wait for the producer)
+        if (int rc = device_of_buffer(c, d_vecs, fn, &dev3)) return rc;
+    }
+    if (int rc = check_device_buffers(c, d_offsets, d_attrs, stream, fn, &dev)) return rc;
+    if (d_vecs && dev3 != dev) return fail(c, HVS_EINVAL, "hvs_set_query_clauses_device: the buffers are on different GPUs");
+    return vectors_everywhere(c, d_offsets, d_vecs, dev, nq, fn, HvsInSet::Clauses, d_attrs);
+}
+
+int hvs_query_clauses(hvs_ctx* c, const float* q_rows, const uint32_t* clause_offsets, const float* clause_attrs, const float* clause_vecs,
+                      uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists)
+{
+    if (!c) return HVS_EINVAL;
+    if (!clause_offsets && !clause_attrs && !clause_vecs) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
+    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_clauses: not supported (yet) on a row-partitioned context");
+    if (!loaded_leaf(c, "hvs_query_clauses")) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_clauses: q_rows / out_ids is NULL");
+    // checked before the resident set is replaced: a refused call changes nothing
+    const uint32_t nsub = hvs_clauses_check(clause_offsets, nq);
+    if (nsub == 0xFFFFFFFFu || (nsub > nq && !clause_attrs))
+        return fail(c, HVS_EINVAL, "hvs_query_clauses: malformed offsets, more than HVS_CLAUSES_MAX_EXTRA extra clauses on a query, too many sub-queries, or clause_attrs is NULL");
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc) rc = hvs_set_query_clauses(c, clause_offsets, clause_attrs, clause_vecs, nq);
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+
+int hvs_clauses_stats(hvs_ctx* c, hvs_clauses_info* out)
+{
+    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_clauses_stats: not supported (yet) on a row-partitioned context");
+    return call_stats<hvs_clauses_info>(c, out, leaf_clauses_stats, [](hvs_clauses_info& sum, const hvs_clauses_info& m) {
+        sum.clause_queries += m.clause_queries;
+        sum.sub_queries += m.sub_queries;
+        sum.max_clauses = std::max(sum.max_clauses, m.max_clauses);
+        sum.underfull_queries += m.underfull_queries;
+        sum.read_keys += m.read_keys;
+        sum.duplicate_keys += m.duplicate_keys;
+        sum.bounded_keys += m.bounded_keys;
+        sum.skipped_chunks += m.skipped_chunks;
         sum.expand_ms = std::max(sum.expand_ms, m.expand_ms);
         sum.merge_ms = std::max(sum.merge_ms, m.merge_ms);
     });

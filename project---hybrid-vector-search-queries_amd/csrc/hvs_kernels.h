@@ -1482,3 +1482,197 @@ __global__ __launch_bounds__(256) void hvs_k_merge_vectors(const uint32_t* __res
         if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Query clauses (hvs_set_query_clauses / hvs_query_clauses): user query q carries m(q) EXTRA clauses beside its own
+// row, in CSR form (off[nq + 1], attrs[off[nq]][4] = [type, v, l, r], and optionally vecs[off[nq]][100]), and asks for the k
+// rows with the smallest MINIMUM key over the clauses they pass.  It is answered as 1 + m(q) <= 256 ordinary sub-queries with
+// padding off -- the third client of the expanded resident set --, and hvs_k_merge_clauses merges their lists by id.  The plan is
+// that of the extra vectors: sub_off[q] = off[q] + q, and sub-query j of parent p reads extra clause j - p - 1 (j > sub_off[p]).
+// ---------------------------------------------------------------------------------------------
+#define HVS_CLAUSE_MAX_EXTRA_ 255u  // (= HVS_CLAUSES_MAX_EXTRA of include/hvs.h; hvs.hip asserts it)
+
+// hvs_k_check_vectors with the clauses' limit: the same status block and the same flags (HVS_VEC_BAD_*).
+__global__ void hvs_k_check_clauses(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t flags = 0u;
+    if (q == 0u) {
+        if (first && off[0] != 0u) flags |= HVS_VEC_BAD_FIRST;
+        status[1] = off[0];
+        status[2] = off[nq];
+    }
+    if (q < nq) {
+        const uint32_t a = off[q], b = off[q + 1u];
+        if (b < a)
+            flags |= HVS_VEC_BAD_ORDER;
+        else if (b - a > HVS_CLAUSE_MAX_EXTRA_)
+            flags |= HVS_VEC_BAD_LONG;
+    }
+    if (flags) atomicOr(&status[0], flags);
+}
+
+// The plan of checked offsets (one GPU's slice, off[0] = lo): sub_off[q] = off[q] - lo + q, parent = q for the query's
+// 1 + m(q) <= 256 sub-queries.  One WAVE per user query (four per workgroup; wave nq writes the last offset): a thread per query,
+// as hvs_k_fill_vectors has it, would write up to 256 scattered words; a thread per sub-query would have to search sub_off, which
+// this very kernel writes, so it would take a second launch.  A wave needs neither: its 64 lanes store the parent's index to
+// consecutive words, four stores at the most.
+__global__ __launch_bounds__(256) void hvs_k_fill_clauses(const uint32_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ sub_off,
+                                                         uint32_t* __restrict__ parent)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q > nq) return;  // wave-uniform
+    const uint32_t lo = off[0];
+    const uint32_t s0 = off[q] - lo + q;
+    if (lane == 0u) sub_off[q] = s0;
+    if (q == nq) return;
+    uint32_t m = off[q + 1u] - off[q];
+    if (m > HVS_CLAUSE_MAX_EXTRA_) m = HVS_CLAUSE_MAX_EXTRA_;  // (refused by the host before this launch; never trusted here)
+    for (uint32_t j = lane; j <= m; j += 64u) parent[s0 + j] = q;
+}
+
+// Sub-query j = 26 float4s.  Float4 0 ([type, v, l, r]) is the parent's for the parent's first sub-query, else extra clause
+// j - p - 1 of `attrs`; float4s 1..25 (the vector) are the parent's for its first sub-query and whenever `vecs` is null
+// (predicate-only clauses), else extra vector j - p - 1 of `vecs` (25 float4s each).  attrs and vecs: this GPU's slice of the
+// extras.  One thread per float4, consecutive threads consecutive float4s, like hvs_k_expand_vectors.
+__global__ __launch_bounds__(256) void hvs_k_expand_clauses(const float4* __restrict__ Qu, const uint32_t* __restrict__ parent,
+                                                           const uint32_t* __restrict__ sub_off, const float4* __restrict__ attrs,
+                                                           const float4* __restrict__ vecs, uint32_t nsub, float4* __restrict__ Qx)
+{
+    static_assert(HVS_QCOLS % 4u == 0u && HVS_NDIM % 4u == 0u && HVS_QCOLS == HVS_NDIM + 4u, "rows are moved in 16-byte pieces");
+    constexpr uint32_t P = HVS_QCOLS / 4u, V = HVS_NDIM / 4u;
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (uint64_t)nsub * P) return;
+    const uint32_t j = (uint32_t)(e / P), c = (uint32_t)(e - (uint64_t)j * P);
+    const uint32_t p = parent[j];
+    const bool first = j == sub_off[p];
+    float4 v;
+    if (c == 0u)
+        v = first ? Qu[(size_t)p * P] : attrs[j - p - 1u];
+    else
+        v = first || !vecs ? Qu[(size_t)p * P + c] : vecs[(size_t)(j - p - 1u) * V + (c - 1u)];
+    Qx[e] = v;
+}
+
+// hvs_k_merge_clauses -- hvs_k_merge_vectors for up to 256 lists per user query (one wave, four per workgroup): the result rows
+// of its sub-queries, rows [sub_off[q], sub_off[q + 1]) x knn of the engines' result buffer (padding off: 0xFFFFFFFF = empty slot,
+// ids global), are streamed in sub-query order through the wave's key buffer, 64 slots at a time; the buffer is de-duplicated
+// by id (hvs_wave_dedup_ids) before any cut and once more before the final select, exactly as there, and for the reasons given
+// there.  What is new is a wave-uniform THRESHOLD tau, "no key" (~0, which no key is) to begin with, under this invariant:
+//     whenever tau is set, the buffer holds knn distinct ids whose keys are <= tau.
+// Every cut (hvs_wave_select_prune to knn after a de-duplication) sets tau to the largest key kept, which establishes it.  A
+// loaded key is admitted only if it is STRICTLY below tau; a key equal to tau is the very entry held (a key names its id).
+// That keeps the invariant -- the knn rows behind tau stay in the buffer until a cut, a de-duplication only replaces a key by a
+// smaller one of the same id, and a cut over >= knn distinct ids with keys <= tau yields a tau no larger -- and it loses
+// nothing: a row whose smallest key is >= tau has knn other rows in front of it now and for ever, since their keys only shrink;
+// a row of the answer, whose smallest key is below every tau there ever is, is admitted whenever that key arrives.
+// Sub-lists ascend in key order, non-finite distances behind the finite ones and empty slots last, so once a chunk held a slot
+// that was empty or not below tau, nothing further in that list can be admitted: its remaining chunks are not loaded (tau only
+// falls).  tau lives in scalar registers (hvs_wave_select_prune returns it wave-uniform), and the admission test is part of
+// the ballot that compacts the chunk.  No LDS beyond the key buffer and the select's histogram.
+// Padding and the final rank sort are hvs_k_merge_vectors': a pad row's key is its smallest over the query's EXPANDED rows.
+// (With predicate-only clauses these rows all carry the parent's vector, and a pad slot computes the same distance up to 256
+// times: the kernel is not told which kind it merges.  That costs only under-full queries with padding on.)  The tail from the
+// counters on is hvs_k_merge_vectors' text, kept as a copy because that kernel's instruction stream must not move.
+// stat[0] += 1 for an under-full query, stat[1] += non-empty slots loaded, stat[2] += keys dropped by a de-duplication,
+// stat[3] += keys loaded and not admitted, stat[4] += 64-slot chunks never loaded.  Queries [q0, q0 + nq) of the user's set.
+template <bool SCALAR_ORDER, int CAP>
+__global__ __launch_bounds__(256) void hvs_k_merge_clauses(const uint32_t* __restrict__ sub_off, uint32_t q0, uint32_t nq, const uint32_t* __restrict__ sub_ids,
+                                                           const float* __restrict__ sub_dists, const float* __restrict__ D, uint32_t n,
+                                                           const float* __restrict__ Qx, int pad, const uint32_t* __restrict__ pad_ids,
+                                                           uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+                                                           unsigned long long* __restrict__ stat)
+{
+    __shared__ uint64_t sbuf[4][CAP];
+    __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 4u + w;
+    if (i >= nq) return;  // wave-uniform; waves never meet at a barrier
+    const uint32_t q = q0 + i;
+    uint64_t* buf = sbuf[w];
+    const uint32_t s0 = sub_off[q], s1 = sub_off[q + 1u];
+    const uint32_t chunks = (knn + 63u) / 64u;
+    uint64_t tau = ~0ull;
+    uint32_t cnt = 0, seen = 0, dups = 0, bounded = 0, skipped = 0;
+    for (uint32_t s = s0; s < s1; ++s) {
+        const uint32_t* __restrict__ ids = sub_ids + (size_t)s * knn;
+        const float* __restrict__ dists = sub_dists + (size_t)s * knn;
+        for (uint32_t ch = 0; ch < chunks; ++ch) {
+            if (cnt + 64u > (uint32_t)CAP) {
+                const uint32_t left = hvs_wave_dedup_ids<CAP>(buf, cnt, lane);
+                dups += cnt - left;
+                cnt = left;
+                if (cnt + 64u > (uint32_t)CAP) {  // (cnt > knn: knn + 64 <= CAP)
+                    const uint64_t kth = hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+                    tau = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(kth >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)kth);
+                    cnt = knn;
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                }
+            }
+            const uint32_t e = ch * 64u + lane;
+            const bool slot = e < knn;
+            const uint32_t id = slot ? ids[e] : 0xFFFFFFFFu;
+            const bool have = id != 0xFFFFFFFFu;
+            const uint64_t key = have ? hvs_make_key(dists[e], id) : ~0ull;
+            const bool admit = key < tau;  // (false for an empty slot: tau <= ~0)
+            const uint64_t hm = __ballot(have), m = __ballot(admit);
+            if (admit) buf[cnt + hvs_prefix_count(m)] = key;
+            cnt += (uint32_t)__popcll(m);
+            seen += (uint32_t)__popcll(hm);
+            bounded += (uint32_t)__popcll(hm & ~m);
+            if (m != __ballot(slot)) {  // (a slot of the chunk was empty or not below tau: so is everything behind it)
+                skipped += chunks - 1u - ch;
+                break;
+            }
+        }
+    }
+    if (s1 - s0 > 1u) {  // (one list holds every id once)
+        const uint32_t left = hvs_wave_dedup_ids<CAP>(buf, cnt, lane);
+        dups += cnt - left;
+        cnt = left;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (lane == 0u) {
+        if (cnt < knn) atomicAdd(&stat[0], 1ull);
+        if (seen) atomicAdd(&stat[1], (unsigned long long)seen);
+        if (dups) atomicAdd(&stat[2], (unsigned long long)dups);
+        if (bounded) atomicAdd(&stat[3], (unsigned long long)bounded);
+        if (skipped) atomicAdd(&stat[4], (unsigned long long)skipped);
+    }
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) {
+            uint64_t key = ~0ull;
+            if (pad) {
+                const uint32_t s = e - cnt;  // (< knn <= live rows: host)
+                const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
+                const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
+                for (uint32_t j = s0; j < s1; ++j) {
+                    const float* __restrict__ qv = Qx + (size_t)j * HVS_QCOLS + 4;
+                    const uint64_t kj = hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
+                    key = kj < key ? kj : key;
+                }
+            }
+            buf[e] = key;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

@@ -128,9 +128,20 @@ class VectorsInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ClausesInfo(C.Structure):
+    """hvs_clauses_info (include/hvs.h)."""
+    _fields_ = [("clause_queries", C.c_uint32), ("sub_queries", C.c_uint32), ("max_clauses", C.c_uint32), ("underfull_queries", C.c_uint32),
+                ("read_keys", C.c_uint64), ("duplicate_keys", C.c_uint64), ("bounded_keys", C.c_uint64), ("skipped_chunks", C.c_uint64),
+                ("expand_ms", C.c_double), ("merge_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
 VECTORS_MAX_EXTRA = 63
+CLAUSES_MAX_EXTRA = 255
 
 
 def library_path():
@@ -306,6 +317,11 @@ def library():
         "hvs_vectors_stats": (C.c_int, [vp, C.POINTER(VectorsInfo)]),
         "hvs_vectors_plan": (C.c_uint32, [_u32p, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p, C.c_int, _u32p, _f32p, _u32p]),
         "hvs_vectors_check": (C.c_uint32, [_u32p, C.c_uint32]),
+        "hvs_set_query_clauses": (C.c_int, [vp, _u32p, _f32p, _f32p, C.c_uint32]),
+        "hvs_set_query_clauses_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp]),
+        "hvs_query_clauses": (C.c_int, [vp, _f32p, _u32p, _f32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_clauses_stats": (C.c_int, [vp, C.POINTER(ClausesInfo)]),
+        "hvs_clauses_check": (C.c_uint32, [_u32p, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -580,6 +596,86 @@ def vectors_plan(ids, dists, pad_ids=None, pad_dists=None, padding=True):
     kept = library().hvs_vectors_plan(_up(ids) if m else None, _fp(dists) if m else None, m, k, _up(pad_ids) if padding else None,
                                       _fp(pad_dists) if padding else None, int(bool(padding)), _up(out_ids), _fp(out_d), C.byref(dup))
     return out_ids, out_d, int(kept), int(dup.value)
+
+
+def _clauses_csr(clauses, vectors=None):
+    """Extra clauses as (offsets uint32[nq + 1], attrs float32[total, 4], vecs float32[total, 100] or None): `clauses` a LIST of
+    per-query lists of [type, v, l, r] (an empty one leaves the query plain) with `vectors` None (predicate-only clauses) or a
+    list of per-query [m_i, 100] arrays, one vector per clause; or a TUPLE (offsets, attrs) -- `vectors` then the vector array
+    or None -- passed through as it is (so that a malformed CSR reaches the library)."""
+    if isinstance(clauses, tuple) and len(clauses) == 2:
+        off = np.ascontiguousarray(clauses[0], np.uint32).ravel()
+        attrs = np.ascontiguousarray(clauses[1], np.float32).reshape(-1, 4)
+        vecs = None if vectors is None else np.ascontiguousarray(vectors, np.float32).reshape(-1, NDIM)
+        return off, attrs, vecs
+    rows = [np.asarray(a, np.float32).reshape(-1, 4) for a in clauses]
+    off = np.zeros(len(rows) + 1, np.uint32)
+    if rows:
+        off[1:] = np.cumsum([r.shape[0] for r in rows], dtype=np.uint64)
+    attrs = np.ascontiguousarray(np.concatenate(rows) if rows else np.empty((0, 4)), np.float32)
+    vecs = None
+    if vectors is not None:
+        vr = [np.asarray(v, np.float32).reshape(-1, NDIM) for v in vectors]
+        if [v.shape[0] for v in vr] != [r.shape[0] for r in rows]:
+            raise HvsError(-1, "clauses: one vector per clause, or vectors=None")
+        vecs = np.ascontiguousarray(np.concatenate(vr) if vr else np.empty((0, NDIM)), np.float32)
+    return off, attrs, vecs
+
+
+def clauses_check(offsets):
+    """hvs_clauses_check: the sub-queries nsub = offsets[nq] + nq of clause offsets (nq + 1 entries), or None when they are refused
+    (offsets[0] != 0, a descending pair, more than CLAUSES_MAX_EXTRA extras on a query, too many sub-queries)."""
+    off = np.ascontiguousarray(offsets, np.uint32).ravel()
+    if off.size == 0:
+        raise HvsError(-1, "clauses_check: the offsets need nq + 1 entries")
+    nsub = library().hvs_clauses_check(_up(off), off.size - 1)
+    return None if nsub == 0xFFFFFFFF else int(nsub)
+
+
+def product_clauses(q_rows, sets, vectors=None):
+    """The cross product of category sets and extra vectors as clauses, built on the host: (q_out, offsets, attrs, vecs) for
+    Engine.query_clauses(q_out, (offsets, attrs), vecs).  `sets` as for in_plan, `vectors` as for set_query_vectors (a list of
+    per-query [m_i, 100] arrays, or None: no extras).  A query of type 1 / 3 with a non-empty set of c distinct categories
+    (normalised and ordered as in_plan does) and m extras gets the c (1 + m) clauses [type, category, l, r] x vector, category by
+    category, the query's own vector first; the first of them takes the place of clause 0, so q_out's own v is the first
+    category.  A query that does not test C, or whose set is empty, gets its 1 + m vector clauses.  vecs is None when no query
+    has an extra vector (predicate-only clauses: cursors stay allowed).  More than 1 + CLAUSES_MAX_EXTRA clauses on a query: an
+    HvsError."""
+    q = np.ascontiguousarray(q_rows, np.float32)
+    if q.ndim != 2 or q.shape[1] != QCOLS:
+        raise HvsError(-1, "product_clauses: query rows must be nq x 104 float32")
+    nq = q.shape[0]
+    plan = in_plan(q, sets)
+    if plan is None:
+        raise HvsError(-1, "product_clauses: the category sets are refused (see in_plan)")
+    _, sub_off, _, value = plan
+    set_off = _sets_csr(sets)[0]
+    extras = [np.empty((0, NDIM), np.float32)] * nq if vectors is None else [np.asarray(v, np.float32).reshape(-1, NDIM) for v in vectors]
+    if len(extras) != nq:
+        raise HvsError(-1, "product_clauses: one vector list per query")
+    with_vecs = any(v.shape[0] for v in extras)
+    q_out = q.copy()
+    attrs, vecs, off = [], [], np.zeros(nq + 1, np.uint32)
+    for p in range(nq):
+        t = q[p, 0]
+        tests_c = bool(t > -1.0 and t < 4.0 and int(t) in (1, 3)) and set_off[p + 1] > set_off[p]
+        cats = value[sub_off[p]:sub_off[p + 1]] if tests_c else q[p, 1:2]
+        own = np.concatenate([q[p:p + 1, 4:], extras[p]])
+        if len(cats) * own.shape[0] > 1 + CLAUSES_MAX_EXTRA:
+            raise HvsError(-1, f"product_clauses: query {p} would have {len(cats) * own.shape[0]} clauses, more than {1 + CLAUSES_MAX_EXTRA}")
+        first = True
+        for cat in cats:
+            for v in own:
+                if first:
+                    q_out[p, 1] = cat
+                    first = False
+                    continue
+                attrs.append([q[p, 0], cat, q[p, 2], q[p, 3]])
+                vecs.append(v)
+        off[p + 1] = len(attrs)
+    attrs = np.ascontiguousarray(np.asarray(attrs, np.float32).reshape(-1, 4))
+    vecs = np.ascontiguousarray(np.asarray(vecs, np.float32).reshape(-1, NDIM)) if with_vecs else None
+    return q_out, off, attrs, vecs
 
 
 def _device_u32(x, what):
@@ -1086,6 +1182,58 @@ class Engine:
         last call."""
         s = VectorsInfo()
         self._ck(self._lib.hvs_vectors_stats(self._h, C.byref(s)))
+        return s
+
+    # --- query clauses (include/hvs.h "query clauses")
+    def set_query_clauses(self, clauses, vectors=None, stream=None):
+        """Attach extra clauses to the resident queries -- per query a list of [type, v, l, r] (an empty one leaves the query
+        plain), or an (offsets, attrs) CSR pair of host arrays; `vectors` None (predicate-only clauses: every clause searches the
+        query's own vector, cursors stay allowed) or one vector per clause --, or None to remove them.  A query then asks for the
+        k rows with the smallest minimum key over the clauses they pass, each row once.  Caps, cursors and exclusion lists are
+        attached afterwards.  A pair of GPU tensors (offsets int32 / uint32 with nq + 1 entries, attrs float32 [total, 4]) and
+        `vectors` None or a GPU tensor float32 [total, 100] go to hvs_set_query_clauses_device: attributes and vectors never
+        reach the host (`stream` as for set_queries_device)."""
+        if clauses is None:
+            self._ck(self._lib.hvs_set_query_clauses(self._h, None, None, None, 0))
+            return
+        if isinstance(clauses, tuple) and len(clauses) == 2 and any(hasattr(x, "data_ptr") and hasattr(x, "shape") for x in clauses):
+            po, n = _device_u32(clauses[0], "set_query_clauses")
+            pa = 0 if clauses[1] is None else _device_rows(clauses[1], None, 4, "set_query_clauses")[0]
+            pv = 0 if vectors is None else _device_rows(vectors, None, NDIM, "set_query_clauses")[0]
+            self.set_query_clauses_device(po, pa, pv, max(n, 1) - 1, stream=stream)
+            return
+        off, attrs, vecs = _clauses_csr(clauses, vectors)
+        self._ck(self._lib.hvs_set_query_clauses(self._h, _up(off) if off.size else None, _fp(attrs) if attrs.size else None,
+                                                 _fp(vecs) if vecs is not None and vecs.size else None, max(off.size, 1) - 1))
+
+    def set_query_clauses_device(self, offsets_ptr, attrs_ptr, vecs_ptr, nq, stream=None):
+        """hvs_set_query_clauses_device from three raw pointers (0 / None = NULL) and the number of queries."""
+        po, pa, pv = int(offsets_ptr or 0), int(attrs_ptr or 0), int(vecs_ptr or 0)
+        self._ck(self._lib.hvs_set_query_clauses_device(self._h, C.c_void_p(po) if po else None, C.c_void_p(pa) if pa else None,
+                                                        C.c_void_p(pv) if pv else None, int(nq), _stream_ptr(stream)))
+
+    def query_clauses(self, q_rows, clauses, vectors=None, sample_proportion=1.0, want_dists=True):
+        """hvs_query_clauses: host rows and their extra clauses in, host ids (and distances) out; clauses = None is query()."""
+        q = np.ascontiguousarray(q_rows, np.float32)
+        if q.ndim != 2 or q.shape[1] != QCOLS:
+            raise HvsError(-1, "query rows must be nq x 104 float32")
+        nq, K = q.shape[0], self.k
+        ids = np.empty((nq, K), np.uint32)
+        d = np.empty((nq, K), np.float32) if want_dists else None
+        off, attrs, vecs = (None, None, None) if clauses is None else _clauses_csr(clauses, vectors)
+        if off is not None and off.size != nq + 1:
+            raise HvsError(-1, "query_clauses: one clause list per query")
+        self._ck(self._lib.hvs_query_clauses(self._h, _fp(q), _up(off) if off is not None else None,
+                                             _fp(attrs) if attrs is not None and attrs.size else None,
+                                             _fp(vecs) if vecs is not None and vecs.size else None, nq, sample_proportion, _up(ids),
+                                             _fp(d) if want_dists else None))
+        return (ids, d) if want_dists else ids
+
+    def clause_stats(self):
+        """hvs_clauses_stats: clause queries, sub-queries, under-full queries, the merge's four key counters and its time, of the
+        last call."""
+        s = ClausesInfo()
+        self._ck(self._lib.hvs_clauses_stats(self._h, C.byref(s)))
         return s
 
     # --- resident variant
