@@ -980,6 +980,79 @@ int hvs_query_clauses(hvs_ctx *ctx, const float *q_rows, const uint32_t *clause_
 int hvs_clauses_stats(hvs_ctx *ctx, hvs_clauses_info *out);
 uint32_t hvs_clauses_check(const uint32_t *offsets, uint32_t nq);
 
+/* ---- per-query candidate lists: the k nearest rows among an id list --------------------------------- */
+/*
+ * A candidate list is a set of row ids attached to ONE resident query: "search only among THESE rows" -- the hits of a keyword
+ * stage to be re-ranked, a user's saved items, the rows an access-control list admits.  The lists of all resident queries are
+ * given at once in CSR form: cand_offsets[nq + 1] (u32, ascending, [0] == 0) and cand_ids[cand_offsets[nq]] (u32).
+ *
+ * A row takes part in query q's answer only if ITS ID IS IN q's LIST and it also passes q's predicate (as a plain query reads
+ * the four attribute floats; an invalid type matches nothing), lies in the sampled prefix, is live, is within the cap if caps
+ * are set, is after the cursor if cursors are set, and is not in q's exclusion list if exclusion lists are set.
+ *
+ * The law: with full(q) the matched keys of q in key order, the answer with padding off is the first k keys of full(q) whose id
+ * is listed, taken after cap, exclusion and cursor, then empty slots (0xFFFFFFFF / +inf).  With padding on the usual rule fills
+ * the rest ONCE: rows n-1, n-2, ..., or the last live ids under a mask; pad rows need not be listed.  Ids, distance bits (the
+ * engines' exact-order function in the context's distance order) and the (dist asc, id asc) tie rule are those of every other
+ * call.  AN EMPTY LIST MATCHES NOTHING; "no restriction" is expressed by attaching no lists.
+ *
+ * Ids.  The rules of exclusion lists: an id is a row id of D as it is WHEN THE QUERY RUNS; an id that names no row -- >= n,
+ * behind the sampled prefix, a dead row -- contributes nothing; 0xFFFFFFFF is ignored, so a result row with empty slots can be
+ * fed in as it is; duplicates count once; any order is fine.  Nothing is validated beyond the offsets: no id can make a call
+ * fail, and none is used as an index unchecked.
+ *
+ * Limits.  At most HVS_CANDIDATES_MAX raw entries per query (the offsets alone decide).  A longer list, offsets[0] != 0, a
+ * descending pair of offsets, nq != the number of resident queries, or cand_ids == NULL with offsets[nq] > 0: HVS_EINVAL, and
+ * nothing changes -- lists already attached, results, caps and cursors stay in force.  No data loaded: HVS_ESTATE.  Both
+ * pointers NULL removes the lists.
+ *
+ * Lifetime.  That of exclusion lists: every call that replaces the resident set removes them, and so does attaching or removing
+ * category sets, query vectors or clauses.  Earlier results stay in place.  While no lists are attached every call runs exactly
+ * the kernels it runs without this feature, with the same arguments.
+ *
+ * Composes with every k, both distance orders, the padding setting, sample_proportion, caps, cursors (hvs_set_after_from_results
+ * included), exclusion lists, the mask, appended rows, updated rows and compaction: the scan reads D as it is, so nothing is
+ * stale and no tail exists for it.  hvs_set_engine has no effect on such a call: there is one way to answer it, a gather of the
+ * listed rows (hvs_timing.engine reports HVS_ENGINE_EXACT_SCAN).  Does NOT compose (yet) with the expanded resident set: while
+ * category sets, query vectors or clauses are attached hvs_set_candidate_ids* returns HVS_ESTATE and nothing changes.
+ * All three context kinds: a replicated context cuts the CSR by the owner ranges; a row-partitioned one puts all lists on every
+ * part, each part keeping the ids of its row window as local ids (the last part's window is open-ended) and answering with
+ * padding off; the merge of the parts pads.
+ *
+ * hvs_set_candidate_ids: from HOST memory.  hvs_set_candidate_ids_device: from DEVICE memory by the rules of
+ * hvs_set_exclude_ids_device; it is accepted exactly when the host call accepts the same bytes.
+ * hvs_query_among: upload + attach (max_d2, may be NULL: caps) + resident run + download; it is not a pipeline.
+ * hvs_candidates_stats: figures of the last call, all zero for a call without lists.  listed_queries: the call's queries;
+ * scanned_ids: the normalised entries of their lists; passing_ids: distinct listed rows in the prefix that are live and pass
+ * the predicate; kept_slots and underfull_queries: non-pad slots written and queries with fewer than k of them (row-partitioned:
+ * the rules of hvs_exclude_stats); scan_ms: device time of the scan kernel.  hvs_last_timing after such a call reports
+ * pairs = passing_ids, scanned_pairs = scanned_ids, rescored_pairs = retry_queries = fallback_queries = 0 and main_kernel_ms =
+ * the scan kernel's.  hvs_within_stats, hvs_after_stats and hvs_exclude_stats report the kept slots and under-full queries of
+ * such a call where their feature is attached; exhausted cursors and refused keys are not counted by it.
+ * hvs_download_candidates_plan: the diagnostic twin of hvs_download_exclude_plan, single-GPU contexts only.
+ * hvs_candidates_plan: the arithmetic of the normalisation on the host, no GPU and no context; layout and return convention are
+ * those of hvs_exclude_plan, the limit is HVS_CANDIDATES_MAX.  The device reproduces it bit for bit.
+ */
+#define HVS_CANDIDATES_MAX 8192
+typedef struct hvs_candidates_info {
+    uint32_t listed_queries;
+    uint32_t underfull_queries;
+    uint64_t scanned_ids;
+    uint64_t passing_ids;
+    uint64_t kept_slots;
+    double scan_ms;
+} hvs_candidates_info;
+int hvs_set_candidate_ids(hvs_ctx *ctx, const uint32_t *cand_offsets /* host, nq+1 */, const uint32_t *cand_ids /* host */, uint32_t nq);
+int hvs_set_candidate_ids_device(hvs_ctx *ctx, const uint32_t *d_offsets /* device, nq+1 */, const uint32_t *d_ids /* device */, uint32_t nq,
+                                 void *stream);
+int hvs_query_among(hvs_ctx *ctx, const float *q_rows, const uint32_t *cand_offsets, const uint32_t *cand_ids,
+                    const float *max_d2 /* may be NULL */, uint32_t nq, float sample_proportion, uint32_t *out_ids, float *out_dists);
+int hvs_candidates_stats(hvs_ctx *ctx, hvs_candidates_info *out);
+int hvs_download_candidates_plan(hvs_ctx *ctx, uint32_t *begin, uint32_t *count /* host, nq each, may be NULL */, uint32_t *ids /* host, cap */,
+                                 uint32_t cap);
+uint32_t hvs_candidates_plan(const uint32_t *offsets, const uint32_t *ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t *begin,
+                             uint32_t *count, uint32_t *out_ids);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,13 @@ struct HvsQuerySet {
     uint32_t ex_ids_cap = 0, ex_off_cap = 0;  // entries
     uint32_t ex_nq = 0, ex_total = 0;         // of the lists in force: the user's queries, entries of d_ex_ids (hvs_download_exclude_plan)
     uint32_t st_flags = 0, st_base = 0, st_total = 0;  // of the offsets staged last (leaf_exclude_stage): HVS_EXCL_BAD_*, offsets[0], ids behind them
+    // Candidate lists: d_cd_ids holds every query's normalised list, d_cd_begin / d_cd_count where it lies.  A
+    // caller's offsets are checked in d_ex_off / d_ex_status too (a staging area: nothing in force lies there).  While cand_set
+    // is false no launch reads any of it; while it is true hvs_k_scan_candidates answers every call.  Never set while in.active.
+    bool cand_set = false, call_cand = false;
+    uint32_t *d_cd_ids = nullptr, *d_cd_begin = nullptr, *d_cd_count = nullptr;
+    uint32_t cd_ids_cap = 0, cd_q_cap = 0;  // entries of d_cd_ids / of each of the other two
+    uint32_t cd_nq = 0, cd_total = 0;       // of the lists in force: the queries, entries of d_cd_ids (hvs_download_candidates_plan)
     uint32_t res_lo = 0, res_hi = 0, res_k = 0;
     uint32_t set_gen = 0;      // counts the resident sets this GPU has held
     uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
@@ -317,13 +324,13 @@ struct HvsQuerySet {
     void free_device()
     {
         eng.free_device(), in.free_device();
-        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status);
-        ex_ids_cap = ex_off_cap = 0;
-        excl_set = false;
+        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status, d_cd_ids, d_cd_begin, d_cd_count);
+        ex_ids_cap = ex_off_cap = cd_ids_cap = cd_q_cap = 0;
+        excl_set = cand_set = false;
     }
     void drop_attached()  // caps off, cursors off, lists off, no results: they belonged to a set that is no longer the engines'
     {
-        caps_set = after_set = excl_set = false;
+        caps_set = after_set = excl_set = cand_set = false;
         drop_results();
     }
     // no query has a result row: the rows (under sets the merged rows too) hold ids of a row numbering that has gone
@@ -616,6 +623,8 @@ bool has_after(const hvs_ctx* c) { return c->qs.after_set; }
 // ... carry exclusion lists: the EXCL forms of the AFTER kernels run (with_after)
 bool has_excl(const hvs_ctx* c) { return c->qs.excl_set; }
 HvsExcl excl_arg(const hvs_ctx* c) { return HvsExcl{c->qs.eng.d_ex_begin, c->qs.eng.d_ex_count, c->qs.d_ex_ids}; }
+// ... carry candidate lists: hvs_k_scan_candidates answers, whatever engine is selected (run_candidates)
+bool has_cand(const hvs_ctx* c) { return c->qs.cand_set; }
 // the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
 uint32_t user_nq(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.nuq : c->nq; }
 const float* user_queries(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_uq : c->d_q; }
@@ -665,16 +674,17 @@ uint32_t k_changed(hvs_ctx* c)
 // the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
 struct DetachedForProbe {
     HvsQuerySet& s;
-    const bool caps, after, excl;
-    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set)
+    const bool caps, after, excl, cand;
+    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set), cand(qs.cand_set)
     {
-        s.caps_set = s.after_set = s.excl_set = false;
+        s.caps_set = s.after_set = s.excl_set = s.cand_set = false;
     }
     ~DetachedForProbe()
     {
         s.caps_set = caps;
         s.after_set = after;
         s.excl_set = excl;
+        s.cand_set = cand;
     }
 };
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
@@ -2295,6 +2305,45 @@ int ensure_spare_lane(hvs_ctx* c, uint32_t nqb)
     return HVS_OK;
 }
 
+// Resident queries [q0, q0 + nq) while candidate lists are attached: one launch of hvs_k_scan_candidates, a wave per
+// query, straight into the result rows.  No engine, no index, no tile format and no re-run is involved: hvs_set_engine has no
+// effect on such a call.  It leaves behind what a call leaves behind.
+template <typename Hooks>
+int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hooks)
+{
+    HvsQuerySet& s = c->qs;
+    s.call_capped = capped(c);
+    s.call_after = has_after(c);
+    s.call_excl = has_excl(c);
+    s.call_cand = true;
+    s.in.call = false;
+    s.answered(q0, nq, c->k, s.set_gen);
+    int rc = call_begin(c);
+    if (rc) return rc;
+    if ((rc = hooks.before(0u, nq))) return rc;
+    if (nq) {
+        const int ev = kernel_timer_begin(c);
+        const HvsExcl cand{s.d_cd_begin, s.d_cd_count, s.d_cd_ids};
+        const HvsExcl excl = has_excl(c) ? excl_arg(c) : HvsExcl{nullptr, nullptr, nullptr};
+        with_cap(c->k <= 128u ? 256 : 512, [&](auto CAPT) {
+            auto launch = [&](auto ST) {
+                hipLaunchKernelGGL((hvs_k_scan_candidates<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
+                                   c->d_data, c->n, cut.sampled ? cut.sn : 0u, c->d_q, q0, nq, cand, masked(c) ? c->rs.d_live : nullptr,
+                                   capped(c) ? c->qs.eng.d_max_d2 : nullptr, has_after(c) ? c->qs.eng.d_after_lo : nullptr, excl, c->padding ? 1 : 0,
+                                   masked(c) ? c->rs.d_pad_ids : nullptr, c->d_out_ids, c->d_out_dists, c->k, c->call.d_counters);
+            };
+            if (c->scalar_order)
+                launch(std::true_type{});
+            else
+                launch(std::false_type{});
+        });
+        kernel_timer_end(c, ev);
+        HVS_HIP(c, hipGetLastError());
+    }
+    if ((rc = hooks.after(0u, nq, 0u))) return rc;
+    return call_enqueued(c, nq, false, cut.sn);
+}
+
 // Hooks of run_queries: `before(off, nqb)` is called before the kernels of a batch are enqueued (hvs_query makes the
 // compute stream wait for the batch's queries there: a batch never starts before its input is on the device);
 // `after(off, nqb, next_nqb)` after they have been enqueued (the host pipeline of hvs_query hangs its copies there);
@@ -2307,6 +2356,8 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
+    if (has_cand(c)) return run_candidates(c, q0, nq, cut, hooks);
+    c->qs.call_cand = false;
     const uint32_t sn = cut.sn, sampled = cut.sampled, of_rows = cut.of_rows;
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
@@ -2873,7 +2924,8 @@ int zero_after_lo(hvs_ctx* c)
 // Step 1: `count` + 1 offsets from `off` (host memory, src_dev < 0, or device memory of GPU src_dev) into the staging array and
 // through hvs_k_check_exclude.  `first`: they are the head of the caller's array.  Leaves the flags, the first offset and the
 // number of ids behind it in the query set's st_* fields; nothing that is in force is touched.
-int leaf_exclude_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t count, bool first)
+// `cand`: they are candidate lists' (DESIGN 3.17): the same staging area, hvs_k_check_candidates with its own length limit.
+int leaf_exclude_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t count, bool first, bool cand = false)
 {
     HvsQuerySet& s = c->qs;
     int rc;
@@ -2890,8 +2942,8 @@ int leaf_exclude_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t co
     else if ((rc = copy_from_device(c, s.d_ex_off, off, src_dev, ((size_t)count + 1u) * sizeof(uint32_t))))
         return rc;
     HVS_HIP(c, hipMemsetAsync(s.d_ex_status, 0, 4 * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(hvs_k_check_exclude, dim3(hvs_ceil_div(std::max(count, 1u), 256u)), dim3(256), 0, c->stream, s.d_ex_off, count, first ? 1 : 0,
-                       s.d_ex_status);
+    hipLaunchKernelGGL(cand ? hvs_k_check_candidates : hvs_k_check_exclude, dim3(hvs_ceil_div(std::max(count, 1u), 256u)), dim3(256), 0, c->stream,
+                       s.d_ex_off, count, first ? 1 : 0, s.d_ex_status);
     HVS_HIP(c, hipGetLastError());
     uint32_t h[4] = {0, 0, 0, 0};
     HVS_HIP(c, hipMemcpyAsync(h, s.d_ex_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -2954,6 +3006,50 @@ int leaf_exclude_remove(hvs_ctx* c)
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;
     c->qs.excl_set = false;
+    return HVS_OK;
+}
+
+// ---- candidate lists: staged by leaf_exclude_stage(cand), then, once every GPU's offsets were accepted, the ids
+// behind the staged offsets are copied and normalised in place for rows [row0, row0 + n_rows) by hvs_k_norm_candidates.
+int leaf_candidates_commit(hvs_ctx* c, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0, uint32_t n_rows)
+{
+    HvsQuerySet& s = c->qs;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));
+    s.cand_set = false;  // (the buffers are about to change)
+    if (std::max(count, 1u) > s.cd_q_cap) {
+        s.cd_q_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_cd_begin, (size_t)std::max(count, 1u))) || (rc = dev_alloc(c, &s.d_cd_count, (size_t)std::max(count, 1u)))) return rc;
+        s.cd_q_cap = std::max(count, 1u);
+    }
+    const uint32_t total = s.st_total;
+    if (std::max(total, 1u) > s.cd_ids_cap) {
+        s.cd_ids_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_cd_ids, (size_t)std::max(total, 1u)))) return rc;
+        s.cd_ids_cap = std::max(total, 1u);
+    }
+    if (total) {
+        if (src_dev < 0)
+            HVS_HIP(c, hipMemcpyAsync(s.d_cd_ids, ids + s.st_base, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else if ((rc = copy_from_device(c, s.d_cd_ids, ids + s.st_base, src_dev, (size_t)total * sizeof(uint32_t))))
+            return rc;
+    }
+    if (count) {
+        hipLaunchKernelGGL(hvs_k_norm_candidates, dim3(count), dim3(256), 0, c->stream, s.d_ex_off, count, s.d_cd_ids, row0, n_rows, s.d_cd_begin,
+                           s.d_cd_count);
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
+    s.cd_nq = count;
+    s.cd_total = total;
+    s.cand_set = true;
+    return HVS_OK;
+}
+int leaf_candidates_remove(hvs_ctx* c)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (int rc = resolve_overflow(c)) return rc;
+    c->qs.cand_set = false;
     return HVS_OK;
 }
 
@@ -4401,9 +4497,10 @@ int attach_everywhere(hvs_ctx* c, PerQuery what, const float* f, const uint32_t*
 // last part's is open-ended: an id behind the rows of today names a row that an append may bring).  `first`: `off` is the head
 // of the caller's array (a leaf of a replicated hvs_query_excluding gets a slice that the root has checked).  Every leaf's
 // offsets are checked before any leaf's lists are replaced: HVS_EINVAL leaves every GPU as it was.
-int exclude_everywhere(hvs_ctx* c, const uint32_t* off, const uint32_t* ids, int src_dev, uint32_t nq, bool first, const char* fn)
+// `cand`: the lists are candidate lists, which take the same road with their own check, limit and commit.
+int exclude_everywhere(hvs_ctx* c, const uint32_t* off, const uint32_t* ids, int src_dev, uint32_t nq, bool first, const char* fn, bool cand = false)
 {
-    if (!off) return on_every_leaf(c, leaf_exclude_remove);
+    if (!off) return on_every_leaf(c, cand ? leaf_candidates_remove : leaf_exclude_remove);
     struct Share {
         hvs_ctx* k;
         uint32_t q0, m, row0, n_rows;
@@ -4426,18 +4523,24 @@ int exclude_everywhere(hvs_ctx* c, const uint32_t* off, const uint32_t* ids, int
         if (c->kids.empty()) return f(sh[0]);
         return for_each_leaf(c, [&](uint32_t r) { return f(sh[r]); });
     };
-    int rc = each([&](const Share& s) { return leaf_exclude_stage(s.k, off + s.q0, src_dev, s.m, first && s.q0 == 0u); });
+    int rc = each([&](const Share& s) { return leaf_exclude_stage(s.k, off + s.q0, src_dev, s.m, first && s.q0 == 0u, cand); });
     if (rc) return rc;
     uint32_t flags = 0;
     for (const Share& s : sh) flags |= s.k->qs.st_flags;
     if (flags)
         return fail(c, HVS_EINVAL,
-                    std::string(fn) + (flags & HVS_EXCL_BAD_FIRST   ? ": excl_offsets[0] is not 0"
-                                       : flags & HVS_EXCL_BAD_ORDER ? ": excl_offsets are not ascending"
+                    std::string(fn) + (flags & HVS_EXCL_BAD_FIRST   ? (cand ? ": cand_offsets[0] is not 0" : ": excl_offsets[0] is not 0")
+                                       : flags & HVS_EXCL_BAD_ORDER ? (cand ? ": cand_offsets are not ascending" : ": excl_offsets are not ascending")
+                                       : cand                       ? ": a list has more than HVS_CANDIDATES_MAX entries"
                                                                     : ": a list has more than HVS_EXCLUDE_MAX entries"));
-    rc = each([&](const Share& s) { return leaf_exclude_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows); });
+    if (!ids)
+        for (const Share& s : sh)
+            if (s.k->qs.st_total) return fail(c, HVS_EINVAL, std::string(fn) + ": the id array is NULL and the offsets name entries");
+    rc = each([&](const Share& s) {
+        return cand ? leaf_candidates_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows) : leaf_exclude_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows);
+    });
     if (rc)  // (a copy or an allocation failed: some GPUs may hold the new lists and some the old -- none is in force)
-        for (const Share& s : sh) s.k->qs.excl_set = false;
+        for (const Share& s : sh) (cand ? s.k->qs.cand_set : s.k->qs.excl_set) = false;
     return rc;
 }
 // hvs_query_after / hvs_query_within / hvs_query_excluding: the call's caps, cursors and lists (host memory, `nq` each, the lists
@@ -4632,6 +4735,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     c->qs.call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
     c->qs.call_after = has_after(c->kids[0]);  // (likewise the cursors)
     c->qs.call_excl = has_excl(c->kids[0]);    // (and the lists)
+    c->qs.call_cand = has_cand(c->kids[0]);
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -4878,6 +4982,25 @@ int leaf_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
     out->underfull_queries = (uint32_t)v[1];
     out->refused_keys = v[2] + sink[0];
     return in_underfull(c, &out->underfull_queries);
+}
+
+int leaf_candidates_stats(hvs_ctx* c, hvs_candidates_info* out)
+{
+    unsigned long long v[2] = {0, 0}, t[2] = {0, 0};
+    int rc = leaf_call_counters(c, out, c->qs.call_cand, HVS_CNT_CAND_SLOTS, v);
+    if (rc || !c->qs.call_cand) return rc;
+    if ((rc = call_counters(c, HVS_CNT_PAIRS, t))) return rc;
+    out->listed_queries = c->call.timing.nq;
+    out->kept_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    out->passing_ids = t[0];
+    out->scanned_ids = t[1];
+    for (int i = 0; i < c->call.n_launch_events; ++i) {  // (the scan's launches are the call's timed ones)
+        float ms = 0.f;
+        HVS_HIP(c, hipEventElapsedTime(&ms, c->call.ev_k[2 * i], c->call.ev_k[2 * i + 1]));
+        out->scan_ms += ms;
+    }
+    return HVS_OK;
 }
 
 // ---- hvs_within_plan / hvs_after_plan: one row as the engines would leave it ----
@@ -5760,12 +5883,13 @@ void hvs_after_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_
 
 static_assert(HVS_EXCLUDE_MAX == HVS_EXCLUDE_MAX_, "the kernels' list capacity is the contract's");
 
-uint32_t hvs_exclude_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t* begin, uint32_t* count,
-                          uint32_t* out_ids)
+// the normalisation of per-query id lists of at most `limit` raw entries each: exclusion lists and candidate lists
+static uint32_t id_lists_plan(uint32_t limit, const uint32_t* offsets, const uint32_t* ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t* begin,
+                              uint32_t* count, uint32_t* out_ids)
 {
     if (!offsets || offsets[0] != 0u) return 0xFFFFFFFFu;
     for (uint32_t q = 0; q < nq; ++q)
-        if (offsets[q + 1] < offsets[q] || offsets[q + 1] - offsets[q] > HVS_EXCLUDE_MAX) return 0xFFFFFFFFu;
+        if (offsets[q + 1] < offsets[q] || offsets[q + 1] - offsets[q] > limit) return 0xFFFFFFFFu;
     uint32_t kept_all = 0;
     std::vector<uint32_t> row;
     for (uint32_t q = 0; q < nq; ++q) {
@@ -5788,6 +5912,12 @@ uint32_t hvs_exclude_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t
         kept_all += kept;
     }
     return kept_all;
+}
+
+uint32_t hvs_exclude_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t* begin, uint32_t* count,
+                          uint32_t* out_ids)
+{
+    return id_lists_plan(HVS_EXCLUDE_MAX, offsets, ids, nq, row0, n_rows, begin, count, out_ids);
 }
 
 int hvs_set_exclude_ids(hvs_ctx* c, const uint32_t* excl_offsets, const uint32_t* excl_ids, uint32_t nq)
@@ -5844,6 +5974,102 @@ int hvs_download_exclude_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint
         HVS_HIP(c, hipMemcpyAsync(ids, s.d_ex_ids, (size_t)s.ex_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return (int)s.ex_total;
+}
+
+// ---- per-query candidate lists (include/hvs.h "per-query candidate lists") -------
+
+static_assert(HVS_CANDIDATES_MAX == HVS_CANDIDATES_MAX_, "the kernels' list capacity is the contract's");
+
+uint32_t hvs_candidates_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t* begin,
+                             uint32_t* count, uint32_t* out_ids)
+{
+    return id_lists_plan(HVS_CANDIDATES_MAX, offsets, ids, nq, row0, n_rows, begin, count, out_ids);
+}
+
+// the expanded resident set (category sets, query vectors, clauses) is attached, on every GPU or on none
+static bool expanded_set_attached(const hvs_ctx* c) { return (c->kids.empty() ? c : c->kids[0])->qs.in.active; }
+
+int hvs_set_candidate_ids(hvs_ctx* c, const uint32_t* cand_offsets, const uint32_t* cand_ids, uint32_t nq)
+{
+    static const char* const fn = "hvs_set_candidate_ids";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!cand_offsets && !cand_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, fn, true);
+    if (expanded_set_attached(c))
+        return fail(c, HVS_ESTATE, std::string(fn) + ": candidate lists do not compose (yet) with category sets, query vectors or clauses");
+    if (!cand_offsets) return fail(c, HVS_EINVAL, std::string(fn) + ": cand_offsets is NULL");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    return exclude_everywhere(c, cand_offsets, cand_ids, -1, nq, true, fn, true);
+}
+
+int hvs_set_candidate_ids_device(hvs_ctx* c, const uint32_t* d_offsets, const uint32_t* d_ids, uint32_t nq, void* stream)
+{
+    static const char* const fn = "hvs_set_candidate_ids_device";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_offsets && !d_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, fn, true);
+    if (expanded_set_attached(c))
+        return fail(c, HVS_ESTATE, std::string(fn) + ": candidate lists do not compose (yet) with category sets, query vectors or clauses");
+    if (!d_offsets) return fail(c, HVS_EINVAL, std::string(fn) + ": d_offsets is NULL");
+    int dev = 0, rc = check_resident_count(c, nq, fn);
+    if (!rc) rc = check_device_buffers(c, d_offsets, d_ids, stream, fn, &dev);
+    return rc ? rc : exclude_everywhere(c, d_offsets, d_ids, dev, nq, true, fn, true);
+}
+
+int hvs_query_among(hvs_ctx* c, const float* q_rows, const uint32_t* cand_offsets, const uint32_t* cand_ids, const float* max_d2, uint32_t nq,
+                    float sample_proportion, uint32_t* out_ids, float* out_dists)
+{
+    static const char* const fn = "hvs_query_among";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, std::string(fn) + ": q_rows / out_ids is NULL");
+    // checked before the resident set is replaced: a refused call changes nothing
+    if (!cand_offsets || hvs_candidates_plan(cand_offsets, nullptr, nq, 0u, 0xFFFFFFFFu, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
+        return fail(c, HVS_EINVAL, std::string(fn) + ": cand_offsets are missing or malformed, or a list has more than HVS_CANDIDATES_MAX entries");
+    if (!cand_ids && cand_offsets[nq] > 0u) return fail(c, HVS_EINVAL, std::string(fn) + ": cand_ids is NULL");
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc && max_d2) rc = hvs_set_max_dist2(c, max_d2, nq);
+    if (!rc) rc = hvs_set_candidate_ids(c, cand_offsets, cand_ids, nq);
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+
+int hvs_candidates_stats(hvs_ctx* c, hvs_candidates_info* out)
+{
+    return call_stats<hvs_candidates_info>(
+        c, out, leaf_candidates_stats,
+        [](hvs_candidates_info& sum, const hvs_candidates_info& m) {
+            sum.listed_queries += m.listed_queries;
+            sum.underfull_queries += m.underfull_queries;
+            sum.scanned_ids += m.scanned_ids;
+            sum.passing_ids += m.passing_ids;
+            sum.kept_slots += m.kept_slots;
+            sum.scan_ms = std::max(sum.scan_ms, m.scan_ms);
+        },
+        [&](hvs_candidates_info& sum) {
+            // the rules of hvs_exclude_stats: ids and slots summed over the parts, the queries the call's, under-full from the merge
+            sum.listed_queries = c->qs.call_cand ? c->part_call_nq : 0u;
+            sum.underfull_queries = c->qs.call_cand ? c->pinfo.padded_queries : 0u;
+        });
+}
+
+int hvs_download_candidates_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
+{
+    if (!c) return HVS_EINVAL;
+    if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_candidates_plan: single-GPU contexts only");
+    const HvsQuerySet& s = c->qs;
+    if (!s.cand_set) return fail(c, HVS_ESTATE, "hvs_download_candidates_plan: no candidate lists are attached");
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (s.cd_nq) {
+        if (begin) HVS_HIP(c, hipMemcpyAsync(begin, s.d_cd_begin, (size_t)s.cd_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (count) HVS_HIP(c, hipMemcpyAsync(count, s.d_cd_count, (size_t)s.cd_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (ids && cap >= s.cd_total && s.cd_total)
+        HVS_HIP(c, hipMemcpyAsync(ids, s.d_cd_ids, (size_t)s.cd_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return (int)s.cd_total;
 }
 
 // ---- category sets (include/hvs.h "category sets") -------------------------------

@@ -50,7 +50,10 @@ enum HvsCounter : int {
     // (slots 24..27 are 20..23 as seen from HVS_CNT_RERUN_SINK: an exact re-run's refused keys land in slot 26, which
     // hvs_exclude_stats adds to slot 22 -- the re-run is the pass that gave the query's answer)
     HVS_CNT_RERUN_SINK_EXCL_REFUSED = 26,
-    HVS_CNT_COUNT = 28
+    HVS_CNT_UNUSED_27 = 27,
+    HVS_CNT_CAND_SLOTS = 28,        // candidate lists: slots kept                         -> hvs_candidates_info.kept_slots
+    HVS_CNT_CAND_UNDERFULL = 29,    // ... queries left with fewer than k                  -> hvs_candidates_info.underfull_queries
+    HVS_CNT_COUNT = 30
 };
 // the host reads these as runs (one copy each), and hvs_scan_rows_into_lists writes slots CNT and CNT + 1
 static_assert(HVS_CNT_SCANNED == HVS_CNT_PAIRS + 1 && HVS_CNT_RESCORED == HVS_CNT_PAIRS + 2, "hvs_timing's three counts are one run");
@@ -62,6 +65,7 @@ static_assert(HVS_CNT_AFTER_UNDERFULL == HVS_CNT_AFTER_SLOTS + 1 && HVS_CNT_AFTE
 static_assert(HVS_CNT_EXCL_UNDERFULL == HVS_CNT_EXCL_SLOTS + 1 && HVS_CNT_EXCL_REFUSED == HVS_CNT_EXCL_SLOTS + 2, "hvs_exclude_stats reads one run");
 static_assert(HVS_CNT_RERUN_SINK_EXCL_REFUSED == HVS_CNT_RERUN_SINK + HVS_CNT_EXCL_REFUSED && HVS_CNT_RERUN_SINK_EXCL_REFUSED < HVS_CNT_COUNT,
               "a kernel that counts through the sink base stays inside the block");
+static_assert(HVS_CNT_CAND_UNDERFULL == HVS_CNT_CAND_SLOTS + 1, "hvs_candidates_stats reads one run");
 
 // ---------------------------------------------------------------------------------------------
 // Query parameters: reference include/optimized_parallel.hpp:93-96

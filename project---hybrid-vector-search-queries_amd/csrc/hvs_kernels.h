@@ -1676,3 +1676,266 @@ __global__ __launch_bounds__(256) void hvs_k_merge_clauses(const uint32_t* __res
         if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Per-query candidate lists (hvs_set_candidate_ids / hvs_query_among): a set of row ids per resident query; a row
+// takes part in the query's answer only if its id IS in the set.  The mirror image of the exclusion lists above, and attached
+// the same way: the caller's CSR is put on the device as it is, hvs_k_check_candidates looks at the offsets, the host reads the
+// status block back and refuses before anything changes, then hvs_k_norm_candidates normalises every list IN PLACE by the rule
+// of hvs_k_norm_exclude (hvs_exclude_keeps for the part's window, minus row0, ascending, no duplicates, the rest of the raw
+// extent 0xFFFFFFFF) -- what hvs_candidates_plan does on the host, bit for bit.  The status flags are HVS_EXCL_BAD_*.
+// No engine answers such a query: the lists are short against D, so hvs_k_scan_candidates gathers the listed rows by id.
+// ---------------------------------------------------------------------------------------------
+#define HVS_CANDIDATES_MAX_ 8192u  // (= HVS_CANDIDATES_MAX of include/hvs.h; hvs.hip asserts it)
+__global__ void hvs_k_check_candidates(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t flags = 0u;
+    if (q == 0u) {
+        if (first && off[0] != 0u) flags |= HVS_EXCL_BAD_FIRST;
+        status[1] = off[0];
+        status[2] = off[nq];
+    }
+    if (q < nq) {
+        const uint32_t a = off[q], b = off[q + 1u];
+        if (b < a)
+            flags |= HVS_EXCL_BAD_ORDER;
+        else if (b - a > HVS_CANDIDATES_MAX_)
+            flags |= HVS_EXCL_BAD_LONG;
+    }
+    if (flags) atomicOr(&status[0], flags);
+}
+// One workgroup per query, the list in LDS (32 KB): a bitonic network over the next power of two >= 256, every thread of the
+// block on the same list (so the barriers are uniform); the first wave then keeps the first of every run of equal ids by a
+// ballot compaction and writes them back over the raw list.  The offsets were checked: len <= 8192.
+__global__ __launch_bounds__(256) void hvs_k_norm_candidates(const uint32_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ ids,
+                                                             uint32_t row0, uint32_t n_rows, uint32_t* __restrict__ begin,
+                                                             uint32_t* __restrict__ count)
+{
+    __shared__ uint32_t s[HVS_CANDIDATES_MAX_];
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    if (q >= nq) return;  // block-uniform
+    const uint32_t base = off[q] - off[0];
+    uint32_t len = off[q + 1u] - off[q];
+    if (len > HVS_CANDIDATES_MAX_) len = HVS_CANDIDATES_MAX_;  // (refused by the host before this launch; never trusted here)
+    uint32_t* __restrict__ mine = ids + base;
+    uint32_t P = 256u;
+    while (P < len) P <<= 1;
+    for (uint32_t e = t; e < P; e += 256u) {
+        const uint32_t id = e < len ? mine[e] : 0xFFFFFFFFu;
+        s[e] = hvs_exclude_keeps(id, row0, n_rows) ? id - row0 : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    for (uint32_t k = 2u; k <= P; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            for (uint32_t i = t; i < P; i += 256u) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t a = s[i], b = s[l];
+                    if ((a > b) == ((i & k) == 0u)) {
+                        s[i] = b;
+                        s[l] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (t >= 64u) return;  // (no barrier behind this line)
+    uint32_t kept = 0;
+    for (uint32_t off0 = 0; off0 < len; off0 += 64u) {  // (wave-uniform; s[e] for e >= len is 0xFFFFFFFF after the sort)
+        const uint32_t e = off0 + t;
+        const uint32_t id = e < len ? s[e] : 0xFFFFFFFFu;
+        const bool in = id != 0xFFFFFFFFu && (e == 0u || s[e - 1u] != id);
+        const uint64_t m = __ballot(in);
+        if (in) mine[kept + hvs_prefix_count(m)] = id;
+        kept += (uint32_t)__popcll(m);
+    }
+    for (uint32_t e = kept + t; e < len; e += 64u) mine[e] = 0xFFFFFFFFu;
+    if (t == 0u) {
+        begin[q] = base;
+        count[q] = kept;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// hvs_k_scan_candidates -- the whole answer of a query that carries a candidate list, one wave per query, four per
+// workgroup, written straight into the resident result rows.  The list is normalised: ascending, distinct, ids of this GPU's
+// rows.  A step takes ROWS listed ids.
+//   SIMD order: ROWS = 16, four lanes per row, the arithmetic of hvs_exact_dist_pk dealt out over the quad: lane t plays
+//     accumulators 2t, 2t+1 as one packed f32 pair -- dims (8b + 2t, 8b + 2t + 1) of the twelve full steps, and for t >= 2 dims
+//     96 + 2(t - 2), + 1 of the masked tail --, then (a0+a4, a1+a5) and (a2+a6, a3+a7) by an exchange with lane t ^ 2, the sum of
+//     the pair's halves, and a + b2 by an exchange with lane t ^ 1.  Every operation is the one hvs_exact_dist performs on the same
+//     operands (an f32 add commutes), so the bits are its bits.  A load instruction reads 16 rows x 32 contiguous bytes, and the
+//     four instructions of one 128-byte line follow each other.
+//   Scalar order: one dependent chain of 100 adds, so ROWS = 64, one lane per row, each lane reading its own row
+//     (hvs_scalar_order_dist, the very text the other exact kernels run).
+// The loop is software-pipelined two deep: while step i computes, the attributes C, T of step i + 1 and the ids of step i + 2
+// are in flight, so of the dependent chain id -> C, T -> vector only the vector's load is ever waited for.
+// Per row, in this order: `id < sn` (the sampled prefix, the row cut of a part, and what keeps every id inside D), the live bit
+// (`live` != nullptr: a mask is set), then C and T through hvs_row_passes.  A step in which no row passes computes no distance.
+// Per key, in this order: the cap (`caps`), the cursor (`after_lo`), the wave-uniform threshold tau, and the query's exclusion
+// list last (`excl.begin`; each != nullptr while attached): a listed row costs no binary search until everything else admits it.
+// Keys go to the wave's LDS buffer by ballot compaction; when the next step might not fit, hvs_wave_select_prune cuts to knn and
+// tau becomes the largest key kept.  The invariant is hvs_k_merge_clauses': whenever tau is set the buffer holds knn admitted
+// keys <= tau, and only keys strictly below tau are admitted; the keys are distinct because the ids are, so nothing is
+// de-duplicated.  A key that is refused has knn admitted keys in front of it, now and for ever.
+// The end of a query is hvs_k_select's: final cut, padding from D (or `pad_ids` under a mask), rank sort.
+// counters: HVS_CNT_PAIRS += listed rows that are in the prefix, live and pass the predicate; HVS_CNT_SCANNED += entries of the
+// normalised list; HVS_CNT_CAND_SLOTS += slots kept; HVS_CNT_CAND_UNDERFULL += 1 for an under-full query; and the slots /
+// under-full pairs of caps, cursors and exclusion lists where those are attached, as the final kernels count them.
+// A wave owns a whole list: a call of few queries with long lists runs as long as its longest wave.
+// ---------------------------------------------------------------------------------------------
+template <bool SCALAR_ORDER, int CAP>
+__global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __restrict__ D, uint32_t n, uint32_t sn, const float* __restrict__ Q,
+                                                             uint32_t q0, uint32_t nq, HvsExcl cand, const uint32_t* __restrict__ live,
+                                                             const float* __restrict__ caps, const uint64_t* __restrict__ after_lo,
+                                                             HvsExcl excl, int pad, const uint32_t* __restrict__ pad_ids,
+                                                             uint32_t* __restrict__ out_ids, float* __restrict__ out_dists, uint32_t knn,
+                                                             unsigned long long* __restrict__ counters)
+{
+    constexpr uint32_t ROWS = SCALAR_ORDER ? 64u : 16u;  // rows per step
+    constexpr uint32_t LPR = 64u / ROWS;                 // lanes per row
+    __shared__ uint64_t sbuf[4][CAP];
+    __shared__ uint32_t shist[4][256];  // digit histograms of the radix select
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 4u + w;
+    if (i >= nq) return;  // wave-uniform; waves never meet at a barrier
+    const uint32_t q = q0 + i;
+    uint64_t* buf = sbuf[w];
+    const HvsQParams p = hvs_parse_query(Q + (size_t)q * HVS_QCOLS);
+    const float* __restrict__ qv = Q + (size_t)q * HVS_QCOLS + 4;
+    const uint32_t* __restrict__ lst = cand.ids + cand.begin[q];
+    const uint32_t len = cand.count[q];
+    const float cap = caps ? caps[q] : 0.0f;
+    const uint64_t key_lo = after_lo ? after_lo[q] : 0ull;
+    const uint32_t* __restrict__ xl = excl.begin ? excl.ids + excl.begin[q] : nullptr;
+    const uint32_t xn = excl.begin ? excl.count[q] : 0u;
+    const uint32_t r = lane / LPR, t = lane % LPR;  // this lane's row of a step, and its place among the row's lanes
+    const bool first = t == 0u;                     // the lane that speaks for its row
+    hvs_f2 q2[13];                                  // (SIMD order) the query's pairs this lane's accumulators meet
+    if constexpr (!SCALAR_ORDER) {
+#pragma unroll
+        for (int b = 0; b < 12; ++b) q2[b] = *reinterpret_cast<const hvs_f2*>(qv + 8 * b + 2 * t);
+        q2[12] = t >= 2u ? *reinterpret_cast<const hvs_f2*>(qv + 96 + 2 * (t - 2u)) : hvs_f2{0.0f, 0.0f};
+    }
+    uint64_t tau = ~0ull;
+    uint32_t cnt = 0, npass = 0;
+    // the pipeline's two stages in front of the step: ids of the step after the next, id and attributes of the next
+    auto load_id = [&](uint32_t e) -> uint32_t { return e < len ? lst[e] : 0xFFFFFFFFu; };
+    auto load_ct = [&](uint32_t id) -> float2 {  // (`id < sn` keeps the address inside D; 0xFFFFFFFF is no row: sn <= n)
+        return id < sn ? *reinterpret_cast<const float2*>(D + (size_t)id * HVS_DCOLS) : float2{0.0f, 0.0f};
+    };
+    uint32_t id_a = load_id(r), id_b = load_id(ROWS + r);
+    float2 ct_a = load_ct(id_a);
+    for (uint32_t base = 0; base < len; base += ROWS) {  // wave-uniform
+        const uint32_t id = id_a;
+        const float2 ct = ct_a;
+        id_a = id_b;
+        ct_a = load_ct(id_a);
+        id_b = load_id(base + 2u * ROWS + r);
+        bool ok = id < sn;
+        if (live != nullptr && ok) ok = hvs_row_live(live, id);
+        ok = ok && hvs_row_passes(p, ct.x, ct.y);
+        const uint64_t pm = __ballot(ok && first);
+        if (pm == 0ull) continue;
+        npass += (uint32_t)__popcll(pm);
+        if (cnt + ROWS > (uint32_t)CAP) {  // (cnt > knn: knn + 64 <= CAP)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            const uint64_t kth = hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+            tau = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(kth >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)kth);
+            cnt = knn;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+        const float* __restrict__ dv = D + (size_t)(ok ? id : 0u) * HVS_DCOLS + 2;
+        float dist = 0.0f;
+        if constexpr (SCALAR_ORDER) {
+            if (ok) dist = hvs_scalar_order_dist(dv, qv);
+        } else {
+            hvs_f2 acc = hvs_f2{0.0f, 0.0f};
+            if (ok) {  // (the same for the four lanes of a row)
+                const hvs_f2* __restrict__ d2 = reinterpret_cast<const hvs_f2*>(dv);  // (8-byte aligned: 408 id + 8)
+#pragma unroll
+                for (int b = 0; b < 12; ++b) {
+                    hvs_f2 x = d2[4 * b + t] - q2[b];
+                    x = x * x;
+                    acc = acc + x;
+                }
+                if (t >= 2u) {  // the masked tail: dims 96..99 into accumulators 4..7
+                    hvs_f2 x = d2[46u + t] - q2[12];
+                    x = x * x;
+                    acc = acc + x;
+                }
+            }
+            hvs_f2 s;  // (a0+a4, a1+a5) on lanes 0 and 2, (a2+a6, a3+a7) on lanes 1 and 3
+            s.x = acc.x + __shfl_xor(acc.x, 2);
+            s.y = acc.y + __shfl_xor(acc.y, 2);
+            const float h = s.x + s.y;
+            dist = h + __shfl_xor(h, 1);
+        }
+        bool admit = false;
+        uint64_t key = ~0ull;
+        if (ok && first) {
+            key = hvs_make_key(dist, id);
+            admit = true;
+            if (caps != nullptr) admit = dist <= cap;
+            admit = admit && key >= key_lo && key < tau;
+            if (admit && xl != nullptr) admit = !hvs_excluded(xl, xn, id);
+        }
+        const uint64_t m = __ballot(admit);
+        if (admit) buf[cnt + hvs_prefix_count(m)] = key;
+        cnt += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (lane == 0u) {
+        const unsigned long long under = cnt < knn ? 1ull : 0ull;
+        if (npass) atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)npass);
+        if (len) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)len);
+        if (cnt) atomicAdd(&counters[HVS_CNT_CAND_SLOTS], (unsigned long long)cnt);
+        if (under) atomicAdd(&counters[HVS_CNT_CAND_UNDERFULL], under);
+        if (caps != nullptr) {
+            if (cnt) atomicAdd(&counters[HVS_CNT_WITHIN_SLOTS], (unsigned long long)cnt);
+            if (under) atomicAdd(&counters[HVS_CNT_WITHIN_UNDERFULL], under);
+        }
+        if (after_lo != nullptr) {
+            if (cnt) atomicAdd(&counters[HVS_CNT_AFTER_SLOTS], (unsigned long long)cnt);
+            if (under) atomicAdd(&counters[HVS_CNT_AFTER_UNDERFULL], under);
+        }
+        if (excl.begin != nullptr) {
+            if (cnt) atomicAdd(&counters[HVS_CNT_EXCL_SLOTS], (unsigned long long)cnt);
+            if (under) atomicAdd(&counters[HVS_CNT_EXCL_UNDERFULL], under);
+        }
+    }
+    // padding: fewer than knn admitted rows
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) {
+            uint64_t key = ~0ull;
+            if (pad) {
+                const uint32_t s = e - cnt;  // (< knn <= live rows: host)
+                const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
+                const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
+                key = hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
+            }
+            buf[e] = key;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

@@ -138,8 +138,18 @@ class ClausesInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CandidatesInfo(C.Structure):
+    """hvs_candidates_info (include/hvs.h)."""
+    _fields_ = [("listed_queries", C.c_uint32), ("underfull_queries", C.c_uint32), ("scanned_ids", C.c_uint64),
+                ("passing_ids", C.c_uint64), ("kept_slots", C.c_uint64), ("scan_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
+CANDIDATES_MAX = 8192
 VECTORS_MAX_EXTRA = 63
 CLAUSES_MAX_EXTRA = 255
 
@@ -311,6 +321,12 @@ def library():
         "hvs_exclude_stats": (C.c_int, [vp, C.POINTER(ExcludeInfo)]),
         "hvs_download_exclude_plan": (C.c_int, [vp, _u32p, _u32p, _u32p, C.c_uint32]),
         "hvs_exclude_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
+        "hvs_set_candidate_ids": (C.c_int, [vp, _u32p, _u32p, C.c_uint32]),
+        "hvs_set_candidate_ids_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "hvs_query_among": (C.c_int, [vp, _f32p, _u32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_candidates_stats": (C.c_int, [vp, C.POINTER(CandidatesInfo)]),
+        "hvs_download_candidates_plan": (C.c_int, [vp, _u32p, _u32p, _u32p, C.c_uint32]),
+        "hvs_candidates_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
         "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
         "hvs_set_query_vectors_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "hvs_query_vectors": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
@@ -487,6 +503,22 @@ def exclude_plan(lists, row0=0, n_rows=0xFFFFFFFF):
     if kept == 0xFFFFFFFF:
         if (begin != 0xFFFFFFFF).any() or (count != 0xFFFFFFFF).any() or (out != 0xFFFFFFFF).any():
             raise HvsError(-1, "hvs_exclude_plan wrote its outputs although it refused the lists")
+        return None
+    return int(kept), begin[:nq].copy(), count[:nq].copy(), out[:total].copy()
+
+
+def candidates_plan(lists, row0=0, n_rows=0xFFFFFFFF):
+    """hvs_candidates_plan: candidate lists (a list of per-query id sequences, or an (offsets, ids) pair) normalised for rows
+    [row0, row0 + n_rows) -> (kept, begin, count, ids), or None when the offsets are refused (nothing is written then)."""
+    off, ids = _exclude_csr(lists)
+    nq = off.size - 1
+    begin, count = np.full(nq + 1, 0xFFFFFFFF, np.uint32), np.full(nq + 1, 0xFFFFFFFF, np.uint32)
+    total = int(off[-1]) if nq and off[-1] >= off[0] and off[-1] <= ids.size else 0
+    out = np.full(total + 1, 0xFFFFFFFF, np.uint32)
+    kept = library().hvs_candidates_plan(_up(off), _up(ids), nq, int(row0), int(n_rows), _up(begin), _up(count), _up(out))
+    if kept == 0xFFFFFFFF:
+        if (begin != 0xFFFFFFFF).any() or (count != 0xFFFFFFFF).any() or (out != 0xFFFFFFFF).any():
+            raise HvsError(-1, "hvs_candidates_plan wrote its outputs although it refused the lists")
         return None
     return int(kept), begin[:nq].copy(), count[:nq].copy(), out[:total].copy()
 
@@ -906,12 +938,15 @@ class Engine:
         self._ck(self._lib.hvs_trim_rows(self._h))
 
     # --- the vec_query seam
-    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None, exclude=None):
+    def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None, exclude=None,
+              among=None):
         """hvs_query: host rows in, host ids (and distances) out.  `out_ids` / `out_dists`: caller-provided arrays
         (e.g. views of pinned memory) to be filled instead of fresh ones.  `max_dist2`: one squared-distance cap per query
         (hvs_query_within: the k nearest rows within it); None = no caps.  `after`: (dists, ids), one result cursor per query
         (hvs_query_after: the k nearest rows after that key); None = no cursors.  `exclude`: one exclusion list per query, a
-        list of id sequences or an (offsets, ids) pair (hvs_query_excluding: the k nearest rows not in it); None = no lists."""
+        list of id sequences or an (offsets, ids) pair (hvs_query_excluding: the k nearest rows not in it); None = no lists.
+        `among`: one candidate list per query in the same forms (hvs_query_among: the k nearest rows among it; with max_dist2
+        only); None = no lists."""
         q = np.ascontiguousarray(q_rows, np.float32)
         if q.ndim != 2 or q.shape[1] != QCOLS:
             raise HvsError(-1, "query rows must be nq x 104 float32")
@@ -933,7 +968,16 @@ class Engine:
             ai = np.ascontiguousarray(after[1], np.uint32).ravel()
             if ad.size != nq or ai.size != nq:
                 raise HvsError(-1, "after must be (dists, ids) with one entry per query each")
-        if exclude is not None:
+        if among is not None:
+            if after is not None or exclude is not None:
+                raise HvsError(-1, "among composes with max_dist2 only in one call: attach cursors or exclusion lists to the resident queries")
+            co, ci = _exclude_csr(among)
+            if co.size != nq + 1:
+                raise HvsError(-1, "among must hold one list per query")
+            self._ck(self._lib.hvs_query_among(self._h, _fp(q), _up(co), _up(ci), _fp(caps) if caps is not None else None, nq,
+                                               sample_proportion, _up(ids), _fp(d) if d is not None else None))
+            self._cand_nq = nq
+        elif exclude is not None:
             eo, ei = _exclude_csr(exclude)
             if eo.size != nq + 1:
                 raise HvsError(-1, "exclude must hold one list per query")
@@ -1068,6 +1112,48 @@ class Engine:
         self._ck(min(total, 0))
         begin, count, ids = np.empty(int(nq), np.uint32), np.empty(int(nq), np.uint32), np.empty(max(total, 1), np.uint32)
         self._ck(min(self._lib.hvs_download_exclude_plan(self._h, _up(begin), _up(count), _up(ids), total), 0))
+        return int(total), begin, count, ids[:total].copy()
+
+    # --- per-query candidate lists (include/hvs.h "per-query candidate lists")
+    def set_candidate_ids(self, lists, stream=None):
+        """Attach one candidate list per resident query: a list of per-query id sequences or an (offsets, ids) pair of host
+        arrays (hvs_set_candidate_ids), an (offsets, ids) pair of GPU tensors (hvs_set_candidate_ids_device: int32 / uint32,
+        contiguous, offsets with nq + 1 entries; `stream` as for set_queries_device), or None to remove the lists.  Any call
+        that replaces the resident queries, and attaching or removing category sets, query vectors or clauses, removes them too."""
+        if lists is None:
+            self._ck(self._lib.hvs_set_candidate_ids(self._h, None, None, 0))
+        elif isinstance(lists, tuple) and len(lists) == 2 and all(hasattr(x, "data_ptr") and hasattr(x, "shape") for x in lists):
+            po, n = _device_u32(lists[0], "set_candidate_ids")
+            pi, _ = _device_u32(lists[1], "set_candidate_ids")
+            self.set_candidate_ids_device(po, pi, max(n, 1) - 1, stream=stream)
+        else:
+            off, ids = _exclude_csr(lists)
+            self._ck(self._lib.hvs_set_candidate_ids(self._h, _up(off), _up(ids), off.size - 1))
+            self._cand_nq = off.size - 1
+
+    def set_candidate_ids_device(self, offsets_ptr, ids_ptr, nq, stream=None):
+        """hvs_set_candidate_ids_device from two raw pointers (0 / None = NULL) and the number of queries."""
+        po, pi = int(offsets_ptr or 0), int(ids_ptr or 0)
+        self._ck(self._lib.hvs_set_candidate_ids_device(self._h, C.c_void_p(po) if po else None, C.c_void_p(pi) if pi else None, int(nq),
+                                                        _stream_ptr(stream)))
+        self._cand_nq = int(nq)
+
+    def candidates_stats(self):
+        """hvs_candidates_stats: queries run under lists, under-full ones, scanned and passing ids, non-pad slots and the scan's
+        device time of the last call."""
+        e = CandidatesInfo()
+        self._ck(self._lib.hvs_candidates_stats(self._h, C.byref(e)))
+        return e
+
+    def candidates_plan_device(self, nq=None):
+        """hvs_download_candidates_plan: (total, begin, count, ids) of the normalised lists of the resident queries as they lie
+        on the device, whichever way they were attached (one-GPU contexts).  `nq`: the number of resident queries (None: that
+        of the last set_candidate_ids / query(among=) of this object)."""
+        nq = getattr(self, "_cand_nq", 0) if nq is None else nq
+        total = self._lib.hvs_download_candidates_plan(self._h, None, None, None, 0)
+        self._ck(min(total, 0))
+        begin, count, ids = np.empty(int(nq), np.uint32), np.empty(int(nq), np.uint32), np.empty(max(total, 1), np.uint32)
+        self._ck(min(self._lib.hvs_download_candidates_plan(self._h, _up(begin), _up(count), _up(ids), total), 0))
         return int(total), begin, count, ids[:total].copy()
 
     # --- category sets (include/hvs.h "category sets")
