@@ -1053,6 +1053,85 @@ int hvs_download_candidates_plan(hvs_ctx *ctx, uint32_t *begin, uint32_t *count 
 uint32_t hvs_candidates_plan(const uint32_t *offsets, const uint32_t *ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t *begin,
                              uint32_t *count, uint32_t *out_ids);
 
+/* ---- shared row sets: the k nearest rows inside a per-query bitmap ---------------------------------- */
+/*
+ * A row set is a bitmap over the rows of D that MANY queries share: the rows a tenant owns, the rows an access-control group may
+ * read.  The sets belong to the DATA SET: a context holds n_sets of them, 1 <= n_sets <= HVS_ROW_SETS_MAX, each in the layout
+ * of hvs_set_row_mask's live_bits -- ceil(n / 64) u64 words, row i at bit i & 63 of word i >> 6 -- one after the other.  Bits at
+ * or past n are ignored on input and read back clear.  The set INDICES belong to the RESIDENT QUERIES: one uint32_t per query, a
+ * set index < n_sets, or 0xFFFFFFFF for "no restriction".
+ *
+ * The law is that of exclusion lists with one clause swapped: a row takes part in query q's answer only if it passes every other
+ * test -- predicate, sampled prefix, live, cap, cursor, exclusion list, candidate list -- AND ITS BIT IS SET IN q's SET.  With
+ * padding off the answer is the first k keys of full(q) whose row is in the set, taken after cap, cursor and exclusion list (under
+ * a candidate list only the listed rows count), then empty slots (0xFFFFFFFF / +inf).  With padding on the usual rule fills the
+ * rest ONCE; pad rows need not be in the set.  Ids, distance bits, the (dist asc, id asc) tie rule, the sampled prefix and
+ * hvs_timing.pairs are unchanged: pairs do not look at sets, as they do not look at lists.  A query with 0xFFFFFFFF keeps its
+ * meaning; AN EMPTY SET MATCHES NOTHING.
+ *
+ * hvs_set_row_sets: n_sets bitmaps from HOST memory (bits == NULL: n_sets empty sets); n_sets == 0 removes the sets.  Replacing
+ * or removing the sets removes every query's index and drops the results.  n_sets > HVS_ROW_SETS_MAX, or sets of more than
+ * 2^32 - 1 u32 words altogether: HVS_EINVAL, and nothing changes.  No data loaded: HVS_ESTATE.
+ * hvs_set_row_sets_device: the same from DEVICE memory of one GPU, complete on `stream` (the rules of
+ * hvs_set_exclude_ids_device); a pointer that is not device memory: HVS_EINVAL.
+ * hvs_assign_row_sets: sets (member != 0) or clears the bits of ONE set for the rows named by a host id list, with atomicOr /
+ * atomicAnd on the device.  Ids >= n (0xFFFFFFFF among them) are ignored.  This is how appended rows get into a set, and how sets
+ * are built from a tenant-to-ids CSR.  set >= n_sets: HVS_EINVAL; no sets loaded: HVS_ESTATE.  Results of earlier calls stay.
+ * hvs_get_row_sets: the sets as they are, n_sets x ceil(n / 64) words to host memory.
+ * hvs_set_query_row_sets: one index per resident query from HOST memory; NULL removes the indices.  An index >= n_sets other than
+ * 0xFFFFFFFF, or nq != the number of resident queries: HVS_EINVAL; no sets loaded: HVS_ESTATE; either way nothing changes --
+ * indices already attached, sets, results, caps, cursors and lists stay in force.
+ * hvs_set_query_row_sets_device: from DEVICE memory; it is accepted exactly when the host call accepts the same bytes (a check
+ * kernel writes a status block on every GPU, and the host judges all of them before any GPU commits).
+ * hvs_query_in_row_sets: upload + attach + resident run + download; it is not a pipeline.
+ *
+ * Lifetime.  The BITMAPS survive new queries, hvs_set_k, an engine change, hvs_delete_rows, hvs_set_row_mask, hvs_update_rows and
+ * hvs_reindex: an id keeps its bits.  hvs_append_rows gives the new rows clear bits in every set (the bitmaps are sized for the
+ * capacity of D and re-strided when it grows); hvs_trim_rows shrinks them; hvs_compact renumbers them on the device exactly as
+ * hvs_row_sets_compact_plan does; hvs_load_data*, hvs_gen_data drop them.  The INDICES have the lifetime of exclusion lists:
+ * every call that replaces the resident set removes them, and so does attaching or removing category sets, query vectors or
+ * clauses; attached after those, every sub-query takes its parent's index.  While no indices are attached every call runs exactly
+ * the kernels it runs without this feature, with the same arguments.
+ *
+ * Composes with every engine and k, both distance orders, the padding setting, sample_proportion, caps, cursors, exclusion
+ * lists, candidate lists, the expanded resident set, the mask, appended and updated rows, and compaction.  All three context
+ * kinds: a replicated context holds all bitmaps on every GPU and cuts the indices by the owner ranges; a row-partitioned one
+ * holds the WHOLE bitmaps on every part, which tests bit (first row of the part + local id), answers with padding off and leaves
+ * the padding to the merge of the parts.  A row-partitioned context has no row-set operations, so hvs_assign_row_sets is the only
+ * mutation there; it goes to every part.
+ *
+ * hvs_row_sets_stats: n_sets, words_per_set (u64 words) and bytes (device memory of one GPU) of the sets loaded; and of the last
+ * call, all zero for a call without indices: restricted_queries (queries answered whose index is not 0xFFFFFFFF; under the
+ * expanded set counted per sub-query, as the slots are), refused_keys (keys that every other test admitted and the set refused,
+ * at any admission point: a lower bound is the number of such keys in front of the k-th kept one), kept_slots (non-pad slots
+ * written) and underfull_queries (queries with fewer than k of them; row-partitioned: the rules of hvs_exclude_stats).  Keys
+ * refused by a set and keys refused by an exclusion list are counted apart: hvs_exclude_stats reports what it reported before.
+ * hvs_row_sets_compact_plan: pure host arithmetic, no GPU and no context: the sets as they must be after hvs_compact under the
+ * mask live_bits (NULL: every row live), out[s][j] = bits[s][id of the j-th live row], in the layout of the input (n_sets x
+ * ceil(n / 64) words; bits at or past the number of live rows clear).  The device reproduces it bit for bit.
+ */
+#define HVS_ROW_SETS_MAX 256
+typedef struct hvs_row_sets_info {
+    uint32_t n_sets;
+    uint32_t words_per_set;
+    uint64_t bytes;
+    uint32_t restricted_queries;
+    uint32_t underfull_queries;
+    uint64_t refused_keys;
+    uint64_t kept_slots;
+} hvs_row_sets_info;
+int hvs_set_row_sets(hvs_ctx *ctx, const uint64_t *bits /* host, n_sets x ceil(n/64), or NULL = all sets empty */, uint32_t n_sets);
+int hvs_set_row_sets_device(hvs_ctx *ctx, const uint64_t *d_bits /* device, or NULL */, uint32_t n_sets, void *stream);
+int hvs_assign_row_sets(hvs_ctx *ctx, uint32_t set, const uint32_t *ids /* host */, uint32_t count, int member);
+int hvs_get_row_sets(hvs_ctx *ctx, uint64_t *bits /* host, n_sets x ceil(n/64) */);
+int hvs_set_query_row_sets(hvs_ctx *ctx, const uint32_t *set_of_query /* host, nq, or NULL */, uint32_t nq);
+int hvs_set_query_row_sets_device(hvs_ctx *ctx, const uint32_t *d_set_of_query /* device, nq, or NULL */, uint32_t nq, void *stream);
+int hvs_query_in_row_sets(hvs_ctx *ctx, const float *q_rows, const uint32_t *set_of_query, uint32_t nq, float sample_proportion,
+                          uint32_t *out_ids, float *out_dists);
+int hvs_row_sets_stats(hvs_ctx *ctx, hvs_row_sets_info *out);
+void hvs_row_sets_compact_plan(const uint64_t *bits, const uint64_t *live_bits /* may be NULL */, uint32_t n, uint32_t n_sets,
+                               uint64_t *out_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,15 +139,32 @@ struct HvsRowSet {
     uint32_t* d_cmp_rank = nullptr;
     float* d_trim = nullptr;
     hvs_compact_info cstat{};       // figures of the last hvs_compact since the last load
+    // -- shared row sets: n_sets bitmaps in d_sets, sets_words u32 words each (an even number: whole u64 words of
+    // the contract's layout), one bit per row.  While n_sets == 0 nothing here is read.  The invariants:
+    //   - sets_words >= 2 ceil(max(n_cap, rows) / 64), so every row D has room for has a word in every set
+    //   - the bits at or past the rows the sets cover (set_rows(): n, or the whole D's rows on a part of a row-partitioned
+    //     context, whose ids start at sets_row0) are clear: an appended row is in no set
+    uint32_t* d_sets = nullptr;
+    uint32_t n_sets = 0, sets_words = 0;
+    uint32_t sets_part_rows = 0, sets_row0 = 0;  // a part: the rows of the whole D and the part's first row (0, 0 otherwise)
+    uint32_t* d_sets_ids = nullptr;  // hvs_assign_row_sets' id list, kept between calls
+    uint32_t sets_ids_cap = 0;
+    uint32_t *d_cmp_sets = nullptr, *d_sets_next = nullptr;  // per-call: hvs_compact's bounce bitmap of one set; a re-strided copy
     // the device buffers this state owns, in two lists: the per-call ones, and all (D and HvsOrdering::lp are the context's)
     template <typename... P>
     static void drop(P*&... p) { (((void)(p ? hipFree(p) : hipSuccess), p = nullptr), ...); }
-    void free_call_buffers() { drop(d_cmp_bounce, d_cmp_rank, d_trim); }
+    void free_call_buffers() { drop(d_cmp_bounce, d_cmp_rank, d_trim, d_cmp_sets, d_sets_next); }
+    void drop_sets()
+    {
+        drop(d_sets);
+        n_sets = sets_words = sets_part_rows = sets_row0 = 0;
+    }
     void free_device()
     {
-        drop(d_live, d_pad_ids, d_mask_stat, d_stale_ids, d_ilive, d_mask_ids, d_upd_rows, d_upd_ids, d_upd_from);
+        drop(d_live, d_pad_ids, d_mask_stat, d_stale_ids, d_ilive, d_mask_ids, d_upd_rows, d_upd_ids, d_upd_from, d_sets_ids);
+        drop_sets();
         free_call_buffers();
-        live_cap = stale_cap = ilive_cap = mask_ids_cap = upd_cap = 0;
+        live_cap = stale_cap = ilive_cap = mask_ids_cap = upd_cap = sets_ids_cap = 0;
     }
 };
 
@@ -213,10 +230,13 @@ struct HvsPerQuery {
     // exclusion lists: where query q's normalised list lies in HvsQuerySet::d_ex_ids, and its length
     uint32_t *d_ex_begin = nullptr, *d_ex_count = nullptr;
     uint32_t excl_cap = 0;  // entries each of the two has room for
+    // shared row sets: query q's set index, or 0xFFFFFFFF for "no restriction"
+    uint32_t* d_set_of = nullptr;
+    uint32_t set_of_cap = 0;
     void free_device()
     {
-        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id, d_ex_begin, d_ex_count);
-        caps_cap = after_cap = excl_cap = 0;
+        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id, d_ex_begin, d_ex_count, d_set_of);
+        caps_cap = after_cap = excl_cap = set_of_cap = 0;
     }
 };
 
@@ -317,6 +337,15 @@ struct HvsQuerySet {
     uint32_t *d_cd_ids = nullptr, *d_cd_begin = nullptr, *d_cd_count = nullptr;
     uint32_t cd_ids_cap = 0, cd_q_cap = 0;  // entries of d_cd_ids / of each of the other two
     uint32_t cd_nq = 0, cd_total = 0;       // of the lists in force: the queries, entries of d_cd_ids (hvs_download_candidates_plan)
+    // Shared row sets: the per-query set indices, in eng.d_set_of (under the expanded set: per sub-query, the
+    // user's in in.user.d_set_of).  A caller's indices are checked in d_rs_stage / d_rs_status before anything is replaced.
+    // While rset_set is false no launch reads any of it.  While it is true the list forms of the kernels run (with_after):
+    // without exclusion lists they read d_rs_zero as every query's (begin, count) -- zeros, one per resident query -- and
+    // without cursors eng.d_after_lo holds zeros (zero_after_lo).
+    bool rset_set = false, call_rset = false;
+    uint32_t *d_rs_stage = nullptr, *d_rs_status = nullptr, *d_rs_zero = nullptr;
+    uint32_t rs_stage_cap = 0, rs_zero_cap = 0;  // entries
+    uint32_t st_rs_flags = 0;                    // of the indices staged last (leaf_query_sets_stage): 1 = an index names no set
     uint32_t res_lo = 0, res_hi = 0, res_k = 0;
     uint32_t set_gen = 0;      // counts the resident sets this GPU has held
     uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
@@ -324,13 +353,13 @@ struct HvsQuerySet {
     void free_device()
     {
         eng.free_device(), in.free_device();
-        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status, d_cd_ids, d_cd_begin, d_cd_count);
-        ex_ids_cap = ex_off_cap = cd_ids_cap = cd_q_cap = 0;
-        excl_set = cand_set = false;
+        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status, d_cd_ids, d_cd_begin, d_cd_count, d_rs_stage, d_rs_status, d_rs_zero);
+        ex_ids_cap = ex_off_cap = cd_ids_cap = cd_q_cap = rs_stage_cap = rs_zero_cap = 0;
+        excl_set = cand_set = rset_set = false;
     }
     void drop_attached()  // caps off, cursors off, lists off, no results: they belonged to a set that is no longer the engines'
     {
-        caps_set = after_set = excl_set = cand_set = false;
+        caps_set = after_set = excl_set = cand_set = rset_set = false;
         drop_results();
     }
     // no query has a result row: the rows (under sets the merged rows too) hold ids of a row numbering that has gone
@@ -622,7 +651,23 @@ bool capped(const hvs_ctx* c) { return c->qs.caps_set; }
 bool has_after(const hvs_ctx* c) { return c->qs.after_set; }
 // ... carry exclusion lists: the EXCL forms of the AFTER kernels run (with_after)
 bool has_excl(const hvs_ctx* c) { return c->qs.excl_set; }
-HvsExcl excl_arg(const hvs_ctx* c) { return HvsExcl{c->qs.eng.d_ex_begin, c->qs.eng.d_ex_count, c->qs.d_ex_ids}; }
+// ... carry set indices of shared row sets: the same forms run, with the set's bit as one more admission test
+bool has_rset(const hvs_ctx* c) { return c->qs.rset_set && c->rs.n_sets != 0u; }
+// what the list forms receive: the lists (or, while only set indices are attached, empty lists for every query: d_rs_zero) and
+// the sets (or none: set_of == nullptr)
+HvsExcl excl_arg(const hvs_ctx* c)
+{
+    const HvsQuerySet& s = c->qs;
+    HvsExcl x{s.eng.d_ex_begin, s.eng.d_ex_count, s.d_ex_ids, nullptr, nullptr, 0u, 0u};
+    if (!s.excl_set) x.begin = x.count = x.ids = s.d_rs_zero;
+    if (has_rset(c)) {
+        x.set_of = s.eng.d_set_of;
+        x.set_bits = c->rs.d_sets;
+        x.set_words = c->rs.sets_words;
+        x.row0 = c->rs.sets_row0;
+    }
+    return x;
+}
 // ... carry candidate lists: hvs_k_scan_candidates answers, whatever engine is selected (run_candidates)
 bool has_cand(const hvs_ctx* c) { return c->qs.cand_set; }
 // the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
@@ -674,10 +719,11 @@ uint32_t k_changed(hvs_ctx* c)
 // the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
 struct DetachedForProbe {
     HvsQuerySet& s;
-    const bool caps, after, excl, cand;
-    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set), cand(qs.cand_set)
+    const bool caps, after, excl, cand, rset;
+    explicit DetachedForProbe(HvsQuerySet& qs)
+        : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set), cand(qs.cand_set), rset(qs.rset_set)
     {
-        s.caps_set = s.after_set = s.excl_set = s.cand_set = false;
+        s.caps_set = s.after_set = s.excl_set = s.cand_set = s.rset_set = false;
     }
     ~DetachedForProbe()
     {
@@ -685,6 +731,7 @@ struct DetachedForProbe {
         s.after_set = after;
         s.excl_set = excl;
         s.cand_set = cand;
+        s.rset_set = rset;
     }
 };
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
@@ -1059,7 +1106,7 @@ void with_capped(const hvs_ctx* c, F f)
 template <typename F>
 void with_after(const hvs_ctx* c, F f)
 {
-    if (has_excl(c))
+    if (has_excl(c) || has_rset(c))  // (set indices of shared row sets ride in the list forms: DESIGN 3.18)
         f(std::true_type{}, std::true_type{});
     else if (has_after(c))
         f(std::true_type{}, std::false_type{});
@@ -2315,6 +2362,7 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     s.call_capped = capped(c);
     s.call_after = has_after(c);
     s.call_excl = has_excl(c);
+    s.call_rset = has_rset(c);
     s.call_cand = true;
     s.in.call = false;
     s.answered(q0, nq, c->k, s.set_gen);
@@ -2324,7 +2372,8 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     if (nq) {
         const int ev = kernel_timer_begin(c);
         const HvsExcl cand{s.d_cd_begin, s.d_cd_count, s.d_cd_ids};
-        const HvsExcl excl = has_excl(c) ? excl_arg(c) : HvsExcl{nullptr, nullptr, nullptr};
+        HvsExcl excl = excl_arg(c);  // (the scan tells "no lists" by a null `begin`; the sets ride along either way)
+        if (!has_excl(c)) excl.begin = excl.count = excl.ids = nullptr;
         with_cap(c->k <= 128u ? 256 : 512, [&](auto CAPT) {
             auto launch = [&](auto ST) {
                 hipLaunchKernelGGL((hvs_k_scan_candidates<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
@@ -2375,6 +2424,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     c->qs.call_capped = capped(c);
     c->qs.call_after = has_after(c);
     c->qs.call_excl = has_excl(c);
+    c->qs.call_rset = has_rset(c);
     c->qs.in.call = false;  // (in_run sets it once the merge is enqueued)
     c->qs.answered(q0, nq, c->k, c->qs.set_gen);
     if (int rc = call_begin(c)) return rc;
@@ -2684,6 +2734,9 @@ int begin_data(hvs_ctx* c, uint32_t n)
     if (rc) return rc;
     c->n = c->rs.n_cap = 0;
     if ((rc = reset_row_set(c))) return rc;
+    // ... and drops the shared row sets with the indices that name them: they described the rows that go
+    c->rs.drop_sets();
+    c->qs.rset_set = false;
     // a load, unlike a compaction, starts the figures of the data set over (the tail limit is a setting and stays) ...
     c->rs.reindexes = 0;
     c->rs.reindex_ms = 0.0;
@@ -3053,6 +3106,191 @@ int leaf_candidates_remove(hvs_ctx* c)
     return HVS_OK;
 }
 
+// ---- shared row sets ----
+// rows this GPU's bitmaps cover (a part of a row-partitioned context: the whole D's), and the u32 words of one set over `rows` rows
+uint32_t set_rows(const hvs_ctx* c) { return c->rs.sets_part_rows ? c->rs.sets_part_rows : c->n; }
+uint32_t set_words_for(uint32_t rows) { return (uint32_t)(mask_words(rows) * 2u); }
+dim3 set_grid(uint64_t words) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((words + 255u) / 256u, 1u), 65535u)); }
+
+// n_sets bitmaps of `words` words each into a fresh rs.d_sets_next, taken from `src` (src_words words each: device memory of this
+// GPU, or nullptr = all sets empty) with the bits at or past `rows` cleared.  Nothing in force changes.
+int sets_build_next(hvs_ctx* c, const uint32_t* src, uint32_t src_words, uint32_t n_sets, uint32_t words, uint32_t rows)
+{
+    HvsRowSet& s = c->rs;
+    HvsRowSet::drop(s.d_sets_next);
+    const size_t total = (size_t)n_sets * words;
+    HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&s.d_sets_next), std::max<size_t>(total, 1u) * sizeof(uint32_t)));
+    if (!src) {
+        HVS_HIP(c, hipMemsetAsync(s.d_sets_next, 0, total * sizeof(uint32_t), c->stream));
+    } else {
+        hipLaunchKernelGGL(hvs_k_row_sets_restride, set_grid(total), dim3(256), 0, c->stream, src, src_words, s.d_sets_next, words, n_sets, rows);
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    return HVS_OK;
+}
+// ... and d_sets_next takes d_sets' place
+void sets_swap_next(hvs_ctx* c, uint32_t n_sets, uint32_t words)
+{
+    HvsRowSet& s = c->rs;
+    HvsRowSet::drop(s.d_sets);
+    s.d_sets = s.d_sets_next;
+    s.d_sets_next = nullptr;
+    s.n_sets = n_sets;
+    s.sets_words = words;
+}
+// the sets as they are, re-strided to `words` words each (capacity growth, trim): prepare, then sets_swap_next
+int sets_restride_next(hvs_ctx* c, uint32_t words)
+{
+    return sets_build_next(c, c->rs.d_sets, c->rs.sets_words, c->rs.n_sets, words, set_rows(c));
+}
+
+// hvs_set_row_sets on one GPU, first half: the caller's bitmaps (host memory, src_dev < 0, or device memory of GPU src_dev;
+// nullptr: empty sets) over `rows` rows into d_sets_next.  `part_rows` != 0: this GPU is a part, the bitmaps cover the whole D.
+int leaf_row_sets_prepare(hvs_ctx* c, const uint64_t* bits, int src_dev, uint32_t n_sets, uint32_t part_rows)
+{
+    int rc = begin_mutation(c);
+    if (rc || n_sets == 0u) return rc;
+    const uint32_t rows = part_rows ? part_rows : c->n;
+    const uint32_t src_words = set_words_for(rows), words = set_words_for(part_rows ? part_rows : std::max(c->n, c->rs.n_cap));
+    uint32_t* staged = nullptr;
+    if (bits) {
+        const size_t bytes = (size_t)n_sets * src_words * sizeof(uint32_t);
+        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&staged), bytes));
+        if (src_dev < 0) {
+            const hipError_t e = hipMemcpyAsync(staged, bits, bytes, hipMemcpyHostToDevice, c->stream);
+            rc = e == hipSuccess ? HVS_OK : fail(c, HVS_EHIP, std::string("hvs_set_row_sets: ") + hipGetErrorString(e));
+        } else
+            rc = copy_from_device(c, staged, bits, src_dev, bytes);
+    }
+    if (!rc) rc = sets_build_next(c, staged, src_words, n_sets, words, rows);
+    if (staged) (void)hipFree(staged);
+    return rc;
+}
+// second half: the new sets are in force; the queries' indices named the old ones and go, and so do the results
+int leaf_row_sets_commit(hvs_ctx* c, uint32_t n_sets, uint32_t part_rows, uint32_t row0)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (n_sets == 0u)
+        c->rs.drop_sets();
+    else {
+        sets_swap_next(c, n_sets, set_words_for(part_rows ? part_rows : std::max(c->n, c->rs.n_cap)));
+        c->rs.sets_part_rows = part_rows;
+        c->rs.sets_row0 = row0;
+    }
+    c->qs.rset_set = false;
+    c->qs.drop_results();
+    return HVS_OK;
+}
+
+// hvs_assign_row_sets on one GPU: bits of set `set` (< n_sets: checked by the caller) from `count` host ids
+int leaf_assign_row_sets(hvs_ctx* c, uint32_t set, const uint32_t* ids, uint32_t count, int member)
+{
+    HvsRowSet& s = c->rs;
+    int rc = begin_mutation(c);  // (an earlier call's re-runs: under the sets they were asked under)
+    if (rc) return rc;
+    if (count > s.sets_ids_cap) {
+        s.sets_ids_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_sets_ids, (size_t)count))) return rc;
+        s.sets_ids_cap = count;
+    }
+    HVS_HIP(c, hipMemcpyAsync(s.d_sets_ids, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(hvs_k_row_sets_assign, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, s.d_sets_ids, count, set_rows(c),
+                       s.d_sets + (size_t)set * s.sets_words, member);
+    HVS_HIP(c, hipGetLastError());
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the ids are the caller's)
+    return HVS_OK;
+}
+
+int leaf_get_row_sets(hvs_ctx* c, uint64_t* bits)
+{
+    const HvsRowSet& s = c->rs;
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    const size_t width = (size_t)set_words_for(set_rows(c)) * sizeof(uint32_t);
+    if (width && s.n_sets)
+        HVS_HIP(c, hipMemcpy2D(bits, width, s.d_sets, (size_t)s.sets_words * sizeof(uint32_t), width, s.n_sets, hipMemcpyDeviceToHost));
+    return HVS_OK;
+}
+
+// The per-query set indices take the two steps of the exclusion lists, so that a refusal on any GPU leaves every GPU as it was.
+// Step 1: `count` indices from `idx` (host memory, src_dev < 0, or device memory of GPU src_dev) into the staging array and
+// through hvs_k_check_query_row_sets; the verdict is left in st_rs_flags and nothing that is in force is touched.
+int leaf_query_sets_stage(hvs_ctx* c, const uint32_t* idx, int src_dev, uint32_t count)
+{
+    HvsQuerySet& s = c->qs;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));
+    if ((rc = resolve_overflow(c))) return rc;  // (an earlier call's re-runs: under the indices they were asked under)
+    if (std::max(count, 1u) > s.rs_stage_cap) {
+        s.rs_stage_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_rs_stage, (size_t)std::max(count, 1u)))) return rc;
+        s.rs_stage_cap = std::max(count, 1u);
+    }
+    if (!s.d_rs_status && (rc = dev_alloc(c, &s.d_rs_status, (size_t)2))) return rc;
+    if (count) {
+        if (src_dev < 0)
+            HVS_HIP(c, hipMemcpyAsync(s.d_rs_stage, idx, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else if ((rc = copy_from_device(c, s.d_rs_stage, idx, src_dev, (size_t)count * sizeof(uint32_t))))
+            return rc;
+    }
+    HVS_HIP(c, hipMemsetAsync(s.d_rs_status, 0, 2 * sizeof(uint32_t), c->stream));
+    if (count) {
+        hipLaunchKernelGGL(hvs_k_check_query_row_sets, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, s.d_rs_stage, count, c->rs.n_sets,
+                           s.d_rs_status);
+        HVS_HIP(c, hipGetLastError());
+    }
+    uint32_t h[2] = {0, 0};
+    HVS_HIP(c, hipMemcpyAsync(h, s.d_rs_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    s.st_rs_flags = h[0];
+    return HVS_OK;
+}
+// Step 2 (every GPU's indices were accepted): the staged indices are the queries'; under the expanded set they are the user's, and
+// every sub-query takes its parent's.
+int leaf_query_sets_commit(hvs_ctx* c, uint32_t count)
+{
+    HvsQuerySet& s = c->qs;
+    const bool sets = s.in.active;
+    HvsPerQuery& dst = sets ? s.in.user : s.eng;
+    int rc;
+    HVS_HIP(c, hipSetDevice(c->device));
+    s.rset_set = false;  // (the buffers are about to change)
+    auto room = [&](HvsPerQuery& v, uint32_t n) -> int {
+        if (n <= v.set_of_cap) return HVS_OK;
+        v.set_of_cap = 0;
+        if ((rc = dev_alloc(c, &v.d_set_of, (size_t)n))) return rc;
+        v.set_of_cap = n;
+        return HVS_OK;
+    };
+    if ((rc = room(dst, std::max(count, 1u))) || (sets && (rc = room(s.eng, std::max(c->nq, 1u))))) return rc;
+    if (std::max(c->nq, 1u) > s.rs_zero_cap) {
+        s.rs_zero_cap = 0;
+        if ((rc = dev_alloc(c, &s.d_rs_zero, (size_t)std::max(c->nq, 1u)))) return rc;
+        s.rs_zero_cap = std::max(c->nq, 1u);
+    }
+    HVS_HIP(c, hipMemsetAsync(s.d_rs_zero, 0, (size_t)s.rs_zero_cap * sizeof(uint32_t), c->stream));
+    if (count) {
+        HVS_HIP(c, hipMemcpyAsync(dst.d_set_of, s.d_rs_stage, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        if (sets && c->nq) {
+            hipLaunchKernelGGL(hvs_k_expand_query_row_sets, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, s.in.d_parent, c->nq, dst.d_set_of,
+                               s.eng.d_set_of);
+            HVS_HIP(c, hipGetLastError());
+        }
+    }
+    if (!s.after_set && !s.excl_set && (rc = zero_after_lo(c))) return rc;  // (under lists without cursors it holds zeros already)
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    s.rset_set = true;
+    return HVS_OK;
+}
+int leaf_query_sets_remove(hvs_ctx* c)
+{
+    HVS_HIP(c, hipSetDevice(c->device));
+    if (int rc = resolve_overflow(c)) return rc;
+    c->qs.rset_set = false;
+    return HVS_OK;
+}
+
 // The one way caps or cursors reach the resident queries of one GPU: `count` values from `src` (count = the user's resident
 // queries: checked by the caller) are attached, or the values are removed.  Under category sets they are the user's, one per user
 // query: copied and normalised on the user's side (HvsInSet::user), then every sub-query takes its parent's.  `row0` (cursors):
@@ -3068,7 +3306,7 @@ int leaf_attach(hvs_ctx* c, PerQuery what, const PerQuerySource& src, uint32_t c
         if ((rc = resolve_overflow(c))) return rc;  // (for LastSlot: the last slots of re-run queries too)
         if (src.kind == PerQuerySource::Remove) {
             (caps ? s.caps_set : s.after_set) = false;
-            if (!caps && s.excl_set) return zero_after_lo(c);  // (the list forms are cursor forms: they go on reading after_lo)
+            if (!caps && (s.excl_set || s.rset_set)) return zero_after_lo(c);  // (the list forms are cursor forms: they go on reading after_lo)
             return HVS_OK;
         }
         if (!caps && (rc = ensure_after(c, std::max(std::max(count, sets ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
@@ -4057,7 +4295,14 @@ int leaf_reserve_rows(hvs_ctx* c, uint32_t n_cap)
     int rc = begin_mutation(c);
     if (rc) return rc;
     if (n_cap > s.n_cap) {
-        if ((rc = grow_keep(c, &c->d_data, (size_t)n_cap * HVS_DCOLS, (size_t)c->n * HVS_DCOLS, "hvs_reserve_rows: moving D: "))) return rc;
+        // (shared row sets, DESIGN 3.18: every set gets words for the new rows first, so that a failure leaves all as it was)
+        const bool restride = s.n_sets && !s.sets_part_rows && set_words_for(n_cap) > s.sets_words;
+        if (restride && (rc = sets_restride_next(c, set_words_for(n_cap)))) return rc;
+        if ((rc = grow_keep(c, &c->d_data, (size_t)n_cap * HVS_DCOLS, (size_t)c->n * HVS_DCOLS, "hvs_reserve_rows: moving D: "))) {
+            HvsRowSet::drop(s.d_sets_next);
+            return rc;
+        }
+        if (restride) sets_swap_next(c, s.n_sets, set_words_for(n_cap));
         s.n_cap = n_cap;
     }
     const size_t cap64 = mask_words(s.n_cap);
@@ -4254,6 +4499,8 @@ int leaf_compact_prepare(hvs_ctx* c, uint32_t first_dead, uint32_t chunk)
     const uint32_t bounce_rows = std::min(chunk, c->n - first_dead);
     HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_cmp_bounce), (size_t)bounce_rows * HVS_DCOLS * sizeof(float)));
     HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_cmp_rank), (((size_t)c->n + 31u) / 32u) * sizeof(uint32_t)));
+    if (c->rs.n_sets)  // (shared row sets, DESIGN 3.18: the bounce bitmap of one set)
+        HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_cmp_sets), (size_t)c->rs.sets_words * sizeof(uint32_t)));
     return HVS_OK;
 }
 
@@ -4270,6 +4517,17 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
         return rank[id >> 5] + (uint32_t)__builtin_popcount(mask_half(c->rs.h_live[id >> 6], id >> 5) & ((1u << (id & 31u)) - 1u));
     };
     HVS_HIP(c, hipMemcpyAsync(c->rs.d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // The shared row sets are renumbered first, while the mask and the rank table describe the old numbering: set
+    // by set the bits of the live rows are packed into the zeroed bounce bitmap and copied back over the set.
+    for (uint32_t st = 0; st < c->rs.n_sets; ++st) {
+        uint32_t* set = c->rs.d_sets + (size_t)st * c->rs.sets_words;
+        const size_t bytes = (size_t)c->rs.sets_words * sizeof(uint32_t);
+        HVS_HIP(c, hipMemsetAsync(c->rs.d_cmp_sets, 0, bytes, c->stream));
+        hipLaunchKernelGGL(hvs_k_row_sets_compact, dim3(hvs_ceil_div((uint32_t)rank.size(), 256u)), dim3(256), 0, c->stream, set, c->rs.d_live,
+                           c->rs.d_cmp_rank, (uint32_t)rank.size(), c->rs.d_cmp_sets, c->rs.sets_words);
+        HVS_HIP(c, hipGetLastError());
+        HVS_HIP(c, hipMemcpyAsync(set, c->rs.d_cmp_sets, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
     // HVS_TRACE: the gathers' and the copies' device time apart (an event between the two of every chunk)
     std::vector<hipEvent_t> ev_mid;
     HVS_HIP(c, hipEventRecord(c->call.ev_q0, c->stream));
@@ -4341,6 +4599,8 @@ int leaf_trim_prepare(hvs_ctx* c)
     if (rc) return rc;
     if (c->rs.n_cap == c->n) return HVS_OK;
     HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->rs.d_trim), (size_t)c->n * HVS_DCOLS * sizeof(float)));
+    if (c->rs.n_sets && !c->rs.sets_part_rows && set_words_for(c->n) < c->rs.sets_words)  // (the shared row sets shrink with D)
+        return sets_restride_next(c, set_words_for(c->n));
     return HVS_OK;
 }
 
@@ -4354,6 +4614,7 @@ int leaf_trim_commit(hvs_ctx* c)
     c->d_data = c->rs.d_trim;
     c->rs.d_trim = nullptr;
     c->rs.n_cap = c->n;
+    if (c->rs.d_sets_next) sets_swap_next(c, c->rs.n_sets, set_words_for(c->n));
     return HVS_OK;
 }
 
@@ -4735,6 +4996,7 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     c->qs.call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
     c->qs.call_after = has_after(c->kids[0]);  // (likewise the cursors)
     c->qs.call_excl = has_excl(c->kids[0]);    // (and the lists)
+    c->qs.call_rset = has_rset(c->kids[0]);    // (and the set indices)
     c->qs.call_cand = has_cand(c->kids[0]);
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
@@ -6070,6 +6332,211 @@ int hvs_download_candidates_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, u
         HVS_HIP(c, hipMemcpyAsync(ids, s.d_cd_ids, (size_t)s.cd_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     return (int)s.cd_total;
+}
+
+// ---- shared row sets (include/hvs.h "shared row sets") ---------------------------
+
+static_assert(HVS_ROW_SETS_MAX == HVS_ROW_SETS_MAX_, "the kernels' set count is the contract's");
+
+void hvs_row_sets_compact_plan(const uint64_t* bits, const uint64_t* live_bits, uint32_t n, uint32_t n_sets, uint64_t* out_bits)
+{
+    const size_t W = mask_words(n);
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        const uint64_t* in = bits + (size_t)s * W;
+        uint64_t* out = out_bits + (size_t)s * W;
+        std::fill(out, out + W, 0ull);
+        uint32_t j = 0;
+        for (size_t w = 0; w < W; ++w) {
+            const uint64_t set = masked_word(in, n, w);
+            for (uint64_t t = masked_word(live_bits, n, w); t; t &= t - 1ull, ++j)
+                if ((set >> __builtin_ctzll(t)) & 1ull) out[j >> 6] |= 1ull << (j & 63u);
+        }
+    }
+}
+
+// rows of the whole data set as the caller numbers them, and the sets loaded (on every GPU alike)
+static uint32_t sets_total_rows(const hvs_ctx* c) { return c->partitioned ? c->part_n : mask_leaf(c)->n; }
+static uint32_t sets_loaded(const hvs_ctx* c) { return mask_leaf(c)->rs.n_sets; }
+
+static int row_sets_everywhere(hvs_ctx* c, const uint64_t* bits, int src_dev, uint32_t n_sets, const char* fn)
+{
+    if (n_sets > HVS_ROW_SETS_MAX) return fail(c, HVS_EINVAL, std::string(fn) + ": more than HVS_ROW_SETS_MAX sets");
+    if (n_sets == 0u && bits) return fail(c, HVS_EINVAL, std::string(fn) + ": bits given for no sets");
+    if ((uint64_t)n_sets * set_words_for(sets_total_rows(c)) > 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": the sets have more than 2^32 - 1 words");
+    auto part_of = [&](const hvs_ctx* k, uint32_t* row0) -> uint32_t {  // a part: the whole D's rows and its first row
+        *row0 = 0u;
+        if (!c->partitioned) return 0u;
+        const size_t r = (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin());
+        *row0 = c->part_row0.size() > r ? c->part_row0[r] : 0u;
+        return c->part_n;
+    };
+    const int rc = two_phase(
+        c,
+        [&](hvs_ctx* k) {
+            uint32_t row0 = 0;
+            return leaf_row_sets_prepare(k, bits, src_dev, n_sets, part_of(k, &row0));
+        },
+        [&](hvs_ctx* k) {
+            uint32_t row0 = 0;
+            const uint32_t part_rows = part_of(k, &row0);
+            return leaf_row_sets_commit(k, n_sets, part_rows, row0);
+        },
+        free_call_scratch);
+    if (!rc && !c->kids.empty()) c->qs.drop_results();  // (a row-partitioned root keeps the range of merged rows itself)
+    return rc;
+}
+
+int hvs_set_row_sets(hvs_ctx* c, const uint64_t* bits, uint32_t n_sets)
+{
+    static const char* const fn = "hvs_set_row_sets";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    return row_sets_everywhere(c, bits, -1, n_sets, fn);
+}
+
+int hvs_set_row_sets_device(hvs_ctx* c, const uint64_t* d_bits, uint32_t n_sets, void* stream)
+{
+    static const char* const fn = "hvs_set_row_sets_device";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_bits) return row_sets_everywhere(c, nullptr, -1, n_sets, fn);
+    if (n_sets > HVS_ROW_SETS_MAX) return fail(c, HVS_EINVAL, std::string(fn) + ": more than HVS_ROW_SETS_MAX sets");
+    int dev = 0;
+    const int rc = check_device_buffers(c, d_bits, nullptr, stream, fn, &dev);
+    return rc ? rc : row_sets_everywhere(c, d_bits, dev, n_sets, fn);
+}
+
+int hvs_assign_row_sets(hvs_ctx* c, uint32_t set, const uint32_t* ids, uint32_t count, int member)
+{
+    static const char* const fn = "hvs_assign_row_sets";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    if (set >= sets_loaded(c)) return fail(c, HVS_EINVAL, std::string(fn) + ": set is not below n_sets");
+    if (count == 0u) return HVS_OK;
+    if (!ids) return fail(c, HVS_EINVAL, std::string(fn) + ": ids is NULL");
+    return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_assign_row_sets(k, set, ids, count, member); });
+}
+
+int hvs_get_row_sets(hvs_ctx* c, uint64_t* bits)
+{
+    static const char* const fn = "hvs_get_row_sets";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    if (!bits) return fail(c, HVS_EINVAL, std::string(fn) + ": bits is NULL");
+    hvs_ctx* k = c->kids.empty() ? c : c->kids[0];  // (every GPU holds all the sets)
+    const int rc = leaf_get_row_sets(k, bits);
+    return rc && k != c ? fail(c, rc, k->err) : rc;
+}
+
+// the caller's set indices (host memory, src_dev < 0, or device memory of GPU src_dev) to every GPU, or, nullptr, off every GPU.
+// A replicated context cuts them by the owner ranges, a row-partitioned one gives every part all of them.  Every GPU's share is
+// checked before any GPU's indices are replaced: HVS_EINVAL leaves every GPU as it was.
+static int query_sets_everywhere(hvs_ctx* c, const uint32_t* idx, int src_dev, uint32_t nq, const char* fn)
+{
+    if (!idx) return on_every_leaf(c, leaf_query_sets_remove);
+    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return leaf_query_sets_stage(k, idx + first, src_dev, m); });
+    if (rc) return rc;
+    uint32_t flags = c->kids.empty() ? c->qs.st_rs_flags : 0u;
+    for (const hvs_ctx* k : c->kids) flags |= k->qs.st_rs_flags;
+    if (flags) return fail(c, HVS_EINVAL, std::string(fn) + ": a set index is neither below n_sets nor 0xFFFFFFFF");
+    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t m, uint32_t) { return leaf_query_sets_commit(k, m); });
+    if (rc) {  // (an allocation failed: some GPUs may hold the new indices and some the old -- none is in force)
+        c->qs.rset_set = false;
+        for (hvs_ctx* k : c->kids) k->qs.rset_set = false;
+    }
+    return rc;
+}
+
+int hvs_set_query_row_sets(hvs_ctx* c, const uint32_t* set_of_query, uint32_t nq)
+{
+    static const char* const fn = "hvs_set_query_row_sets";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!set_of_query) return query_sets_everywhere(c, nullptr, -1, 0u, fn);
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    if (int rc = check_resident_count(c, nq, fn)) return rc;
+    return query_sets_everywhere(c, set_of_query, -1, nq, fn);
+}
+
+int hvs_set_query_row_sets_device(hvs_ctx* c, const uint32_t* d_set_of_query, uint32_t nq, void* stream)
+{
+    static const char* const fn = "hvs_set_query_row_sets_device";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (!d_set_of_query) return query_sets_everywhere(c, nullptr, -1, 0u, fn);
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    int dev = 0, rc = check_resident_count(c, nq, fn);
+    if (!rc) rc = check_device_buffers(c, d_set_of_query, nullptr, stream, fn, &dev);
+    return rc ? rc : query_sets_everywhere(c, d_set_of_query, dev, nq, fn);
+}
+
+int hvs_query_in_row_sets(hvs_ctx* c, const float* q_rows, const uint32_t* set_of_query, uint32_t nq, float sample_proportion, uint32_t* out_ids,
+                          float* out_dists)
+{
+    static const char* const fn = "hvs_query_in_row_sets";
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids || !set_of_query) return fail(c, HVS_EINVAL, std::string(fn) + ": q_rows / set_of_query / out_ids is NULL");
+    // checked before the resident set is replaced: a refused call changes nothing
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    for (uint32_t q = 0; q < nq; ++q)
+        if (set_of_query[q] != 0xFFFFFFFFu && set_of_query[q] >= sets_loaded(c))
+            return fail(c, HVS_EINVAL, std::string(fn) + ": a set index is neither below n_sets nor 0xFFFFFFFF");
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc) rc = hvs_set_query_row_sets(c, set_of_query, nq);
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+
+// figures of the last call on one GPU (zero unless it ran with set indices attached); the sets' own figures are the caller's to fill
+static int leaf_row_sets_stats(hvs_ctx* c, hvs_row_sets_info* out)
+{
+    *out = hvs_row_sets_info{};
+    int rc = leaf_sync(c);
+    if (rc || !c->call.valid || !c->qs.call_rset) return rc;
+    unsigned long long v[4] = {0, 0, 0, 0}, sink[1] = {0};
+    if ((rc = call_counters(c, HVS_CNT_SET_SLOTS, v))) return rc;
+    if ((rc = call_counters(c, HVS_CNT_RERUN_SINK_SET_REFUSED, sink))) return rc;  // (the exact engine's re-runs count through the sink)
+    out->kept_slots = v[0];
+    out->underfull_queries = (uint32_t)v[1];
+    out->refused_keys = v[2] + sink[0];
+    out->restricted_queries = (uint32_t)v[3];
+    return in_underfull(c, &out->underfull_queries);
+}
+
+int hvs_row_sets_stats(hvs_ctx* c, hvs_row_sets_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    hvs_row_sets_info sum{};
+    if (c->kids.empty()) {
+        if (int rc = leaf_row_sets_stats(c, &sum)) return rc;
+    } else {
+        bool first = true;
+        for (hvs_ctx* k : c->kids) {
+            hvs_row_sets_info m{};
+            if (int rc = leaf_row_sets_stats(k, &m)) return fail(c, rc, k->err);
+            sum.kept_slots += m.kept_slots;
+            sum.refused_keys += m.refused_keys;
+            // (row-partitioned: every part answers every query; the first part that took part speaks for the queries, and a
+            // query is under-full when the merge of the parts padded it, the rule of hvs_exclude_stats)
+            if (!c->partitioned || (first && k->call.valid && k->qs.call_rset)) {
+                sum.restricted_queries += m.restricted_queries;
+                first = first && !c->partitioned;
+            }
+            if (!c->partitioned) sum.underfull_queries += m.underfull_queries;
+        }
+        if (c->partitioned) sum.underfull_queries = c->qs.call_rset && c->part_timing_valid ? c->pinfo.padded_queries : 0u;
+    }
+    const hvs_ctx* L = mask_leaf(c);
+    sum.n_sets = L->rs.n_sets;
+    sum.words_per_set = L->rs.n_sets ? (uint32_t)mask_words(sets_total_rows(c)) : 0u;
+    sum.bytes = (uint64_t)L->rs.n_sets * L->rs.sets_words * sizeof(uint32_t);
+    *out = sum;
+    return HVS_OK;
 }
 
 // ---- category sets (include/hvs.h "category sets") -------------------------------

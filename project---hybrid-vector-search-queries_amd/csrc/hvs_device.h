@@ -53,7 +53,14 @@ enum HvsCounter : int {
     HVS_CNT_UNUSED_27 = 27,
     HVS_CNT_CAND_SLOTS = 28,        // candidate lists: slots kept                         -> hvs_candidates_info.kept_slots
     HVS_CNT_CAND_UNDERFULL = 29,    // ... queries left with fewer than k                  -> hvs_candidates_info.underfull_queries
-    HVS_CNT_COUNT = 30
+    HVS_CNT_SET_SLOTS = 30,         // shared row sets: slots kept                         -> hvs_row_sets_info.kept_slots
+    HVS_CNT_SET_UNDERFULL = 31,     // ... queries left with fewer than k                  -> hvs_row_sets_info.underfull_queries
+    HVS_CNT_SET_REFUSED = 32,       // ... keys dropped at an admission point for being outside the set -> hvs_row_sets_info.refused_keys
+    HVS_CNT_SET_RESTRICTED = 33,    // ... queries answered that carry a set index         -> hvs_row_sets_info.restricted_queries
+    // (slots 34..37 are 30..33 as seen from HVS_CNT_RERUN_SINK, as 24..27 are 20..23)
+    HVS_CNT_RERUN_SINK_SET_REFUSED = 36,
+    HVS_CNT_UNUSED_37 = 37,
+    HVS_CNT_COUNT = 38
 };
 // the host reads these as runs (one copy each), and hvs_scan_rows_into_lists writes slots CNT and CNT + 1
 static_assert(HVS_CNT_SCANNED == HVS_CNT_PAIRS + 1 && HVS_CNT_RESCORED == HVS_CNT_PAIRS + 2, "hvs_timing's three counts are one run");
@@ -66,6 +73,11 @@ static_assert(HVS_CNT_EXCL_UNDERFULL == HVS_CNT_EXCL_SLOTS + 1 && HVS_CNT_EXCL_R
 static_assert(HVS_CNT_RERUN_SINK_EXCL_REFUSED == HVS_CNT_RERUN_SINK + HVS_CNT_EXCL_REFUSED && HVS_CNT_RERUN_SINK_EXCL_REFUSED < HVS_CNT_COUNT,
               "a kernel that counts through the sink base stays inside the block");
 static_assert(HVS_CNT_CAND_UNDERFULL == HVS_CNT_CAND_SLOTS + 1, "hvs_candidates_stats reads one run");
+static_assert(HVS_CNT_SET_UNDERFULL == HVS_CNT_SET_SLOTS + 1 && HVS_CNT_SET_REFUSED == HVS_CNT_SET_SLOTS + 2 &&
+                  HVS_CNT_SET_RESTRICTED == HVS_CNT_SET_SLOTS + 3,
+              "hvs_row_sets_stats reads one run");
+static_assert(HVS_CNT_RERUN_SINK_SET_REFUSED == HVS_CNT_RERUN_SINK + HVS_CNT_SET_REFUSED && HVS_CNT_RERUN_SINK_SET_REFUSED < HVS_CNT_COUNT,
+              "a kernel that counts through the sink base stays inside the block");
 
 // ---------------------------------------------------------------------------------------------
 // Query parameters: reference include/optimized_parallel.hpp:93-96

@@ -213,7 +213,24 @@ struct HvsExcl {
     const uint32_t* __restrict__ begin;  // per resident query (under category sets: per sub-query, its parent's pair)
     const uint32_t* __restrict__ count;
     const uint32_t* __restrict__ ids;
+    // Shared row sets ride in the same parameter: set_of[q] is the set of resident query q (under the expanded set:
+    // of sub-query q, its parent's) or 0xFFFFFFFF for "no restriction"; nullptr while no query carries one.  Set s lies at
+    // set_bits[s * set_words ..), one bit per GLOBAL row (row i: bit i & 31 of word i >> 5), and the kernel's row ids start at
+    // global row `row0` (a part of a row-partitioned context; 0 otherwise).  The word index is formed in 64 bits.
+    const uint32_t* __restrict__ set_of;
+    const uint32_t* __restrict__ set_bits;
+    uint32_t set_words;
+    uint32_t row0;
 };
+// the set's admission test: is row `id` of this GPU in query qi's set?  One 4-byte load per key that everything else admitted.
+__device__ __forceinline__ bool hvs_in_row_set(const HvsExcl& x, uint32_t qi, uint32_t id)
+{
+    if (x.set_of == nullptr) return true;
+    const uint32_t s = x.set_of[qi];
+    if (s == 0xFFFFFFFFu) return true;
+    const uint32_t g = x.row0 + id;
+    return ((x.set_bits[(size_t)s * x.set_words + (g >> 5)] >> (g & 31u)) & 1u) != 0u;
+}
 // an id takes part in a list normalised for rows [row0, row0 + n_rows): not the empty slot's id, and inside the window
 __host__ __device__ __forceinline__ bool hvs_exclude_keeps(uint32_t id, uint32_t row0, uint32_t n_rows)
 {
@@ -324,15 +341,29 @@ __device__ __forceinline__ uint32_t* hvs_refused_slot()
     __shared__ uint32_t sref[16];  // one word per wave of the workgroup
     return &sref[threadIdx.x >> 6];
 }
+// (keys refused by a shared row set, DESIGN 3.18, are counted apart: a word per wave of their own)
+__device__ __forceinline__ uint32_t* hvs_set_refused_slot()
+{
+    __shared__ uint32_t ssetref[16];
+    return &ssetref[threadIdx.x >> 6];
+}
 __device__ __forceinline__ void hvs_refused_begin(uint32_t lane)
 {
-    if (lane == 0u) *hvs_refused_slot() = 0u;
+    if (lane == 0u) {
+        *hvs_refused_slot() = 0u;
+        *hvs_set_refused_slot() = 0u;
+    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (LDS operations of one wave execute in order)
 }
+// the list first (its refusals stay what they were), then the query's row set
 __device__ __forceinline__ bool hvs_refuse_listed(const HvsExcl& x, uint32_t qi, uint32_t id)
 {
-    if (!hvs_excluded(x.ids + x.begin[qi], x.count[qi], id)) return false;
-    atomicAdd(hvs_refused_slot(), 1u);
+    if (hvs_excluded(x.ids + x.begin[qi], x.count[qi], id)) {
+        atomicAdd(hvs_refused_slot(), 1u);
+        return true;
+    }
+    if (hvs_in_row_set(x, qi, id)) return false;
+    atomicAdd(hvs_set_refused_slot(), 1u);
     return true;
 }
 __device__ __forceinline__ void hvs_count_refused(uint32_t lane, unsigned long long* __restrict__ counters)
@@ -341,7 +372,86 @@ __device__ __forceinline__ void hvs_count_refused(uint32_t lane, unsigned long l
     if (lane == 0u) {
         const uint32_t n = *hvs_refused_slot();
         if (n) atomicAdd(&counters[HVS_CNT_EXCL_REFUSED], (unsigned long long)n);  // (hvs_exclude_info.refused_keys)
+        const uint32_t ns = *hvs_set_refused_slot();
+        if (ns) atomicAdd(&counters[HVS_CNT_SET_REFUSED], (unsigned long long)ns);  // (hvs_row_sets_info.refused_keys)
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Shared row sets (hvs_set_row_sets / hvs_set_query_row_sets): the small kernels.  The bitmaps are kept as u32
+// words, `words` of them per set (the same bytes as the contract's u64 words); every kernel here checks its indices against
+// the extents it is given and writes with plain vector stores or atomicOr / atomicAnd.
+// ---------------------------------------------------------------------------------------------
+#define HVS_ROW_SETS_MAX_ 256u  // (= HVS_ROW_SETS_MAX of include/hvs.h; hvs.hip asserts it)
+// status[0] |= 1 where an index is neither < n_sets nor 0xFFFFFFFF; status[1] += queries that carry a set
+__global__ void hvs_k_check_query_row_sets(const uint32_t* __restrict__ idx, uint32_t nq, uint32_t n_sets, uint32_t* __restrict__ status)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const uint32_t s = idx[q];
+    if (s == 0xFFFFFFFFu) return;
+    if (s >= n_sets)
+        atomicOr(&status[0], 1u);
+    else
+        atomicAdd(&status[1], 1u);
+}
+// under the expanded set every sub-query takes its parent's index
+__global__ void hvs_k_expand_query_row_sets(const uint32_t* __restrict__ parent, uint32_t nsub, const uint32_t* __restrict__ uidx,
+                                            uint32_t* __restrict__ idx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nsub) idx[i] = uidx[parent[i]];
+}
+// hvs_assign_row_sets: bits of ONE set (`bits`: its first word) from an id list; ids >= rows (0xFFFFFFFF among them) are ignored
+__global__ void hvs_k_row_sets_assign(const uint32_t* __restrict__ ids, uint32_t count, uint32_t rows, uint32_t* __restrict__ bits, int member)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t id = ids[i];
+    if (id >= rows) return;
+    if (member)
+        atomicOr(&bits[id >> 5], 1u << (id & 31u));
+    else
+        atomicAnd(&bits[id >> 5], ~(1u << (id & 31u)));
+}
+// n_sets bitmaps of src_words words each to dst_words words each: the words both have are copied, with the bits at or past
+// `rows` cleared; the rest of a destination set is zero.  (Load: src is the caller's array; capacity growth and trim: the old one.)
+__global__ void hvs_k_row_sets_restride(const uint32_t* __restrict__ src, uint32_t src_words, uint32_t* __restrict__ dst, uint32_t dst_words,
+                                        uint32_t n_sets, uint32_t rows)
+{
+    const uint64_t total = (uint64_t)n_sets * dst_words;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const uint32_t s = (uint32_t)(e / dst_words), w = (uint32_t)(e - (uint64_t)s * dst_words);
+        uint32_t v = 0u;
+        if (w < src_words && ((uint64_t)w << 5) < rows) {
+            v = src[(size_t)s * src_words + w];
+            if (rows - (w << 5) < 32u) v &= (1u << (rows - (w << 5))) - 1u;
+        }
+        dst[e] = v;
+    }
+}
+// the bits of `bits` at the set positions of `live`, packed towards bit 0 (pext)
+__host__ __device__ __forceinline__ uint32_t hvs_pack_bits(uint32_t bits, uint32_t live)
+{
+    uint32_t out = 0u, k = 0u;
+    for (uint32_t m = live; m; m &= m - 1u, ++k) out |= ((bits >> __builtin_ctz(m)) & 1u) << k;
+    return out;
+}
+// hvs_compact's share of ONE set: per 32-row word of the live-row mask (`live`, bits past n clear) the set's bits of the live
+// rows are packed and placed at bit rank[w] (live rows in front of the word) of the zeroed bounce bitmap `out` of out_words
+// words.  Two words at most take bits of one source word; atomicOr, because neighbours share them.
+__global__ void hvs_k_row_sets_compact(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ live, const uint32_t* __restrict__ rank,
+                                       uint32_t words, uint32_t* __restrict__ out, uint32_t out_words)
+{
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= words) return;
+    const uint32_t lv = live[w];
+    const uint32_t packed = hvs_pack_bits(bits[w], lv);
+    if (packed == 0u) return;
+    const uint32_t r = rank[w], o = r >> 5, sh = r & 31u;
+    if (o < out_words) atomicOr(&out[o], packed << sh);
+    if (sh && (packed >> (32u - sh)) && o + 1u < out_words) atomicOr(&out[o + 1u], packed >> (32u - sh));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -736,7 +846,7 @@ __device__ __forceinline__ uint32_t hvs_keep_unlisted(uint64_t* buf, uint32_t cn
     for (uint32_t off = 0; off < cnt; off += 64u) {  // (wave-uniform; a chunk's keys land at or below their own places)
         const uint32_t e = off + lane;
         const uint64_t key = e < cnt ? buf[e] : 0ull;
-        const bool in = e < cnt && !hvs_excluded(lst, n, hvs_key_id(key));
+        const bool in = e < cnt && !hvs_excluded(lst, n, hvs_key_id(key)) && hvs_in_row_set(x, qi, hvs_key_id(key));
         const uint64_t m = __ballot(in);
         if (in) buf[kept + hvs_prefix_count(m)] = key;
         kept += (uint32_t)__popcll(m);
@@ -745,6 +855,11 @@ __device__ __forceinline__ uint32_t hvs_keep_unlisted(uint64_t* buf, uint32_t cn
     if (count && lane == 0u) {
         if (kept) atomicAdd(&counters[HVS_CNT_EXCL_SLOTS], (unsigned long long)kept);
         if (kept < knn) atomicAdd(&counters[HVS_CNT_EXCL_UNDERFULL], 1ull);
+        if (x.set_of != nullptr) {  // (shared row sets, DESIGN 3.18: the same two figures for hvs_row_sets_info)
+            if (kept) atomicAdd(&counters[HVS_CNT_SET_SLOTS], (unsigned long long)kept);
+            if (kept < knn) atomicAdd(&counters[HVS_CNT_SET_UNDERFULL], 1ull);
+            if (x.set_of[qi] != 0xFFFFFFFFu) atomicAdd(&counters[HVS_CNT_SET_RESTRICTED], 1ull);
+        }
     }
     return kept;
 }
@@ -1821,7 +1936,7 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
         q2[12] = t >= 2u ? *reinterpret_cast<const hvs_f2*>(qv + 96 + 2 * (t - 2u)) : hvs_f2{0.0f, 0.0f};
     }
     uint64_t tau = ~0ull;
-    uint32_t cnt = 0, npass = 0;
+    uint32_t cnt = 0, npass = 0, nset = 0;  // (nset: keys refused by the query's row set)
     // the pipeline's two stages in front of the step: ids of the step after the next, id and attributes of the next
     auto load_id = [&](uint32_t e) -> uint32_t { return e < len ? lst[e] : 0xFFFFFFFFu; };
     auto load_ct = [&](uint32_t id) -> float2 {  // (`id < sn` keeps the address inside D; 0xFFFFFFFF is no row: sn <= n)
@@ -1882,6 +1997,7 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
             if (caps != nullptr) admit = dist <= cap;
             admit = admit && key >= key_lo && key < tau;
             if (admit && xl != nullptr) admit = !hvs_excluded(xl, xn, id);
+            if (admit && !hvs_in_row_set(excl, q, id)) admit = false, ++nset;
         }
         const uint64_t m = __ballot(admit);
         if (admit) buf[cnt + hvs_prefix_count(m)] = key;
@@ -1893,8 +2009,18 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
         cnt = knn;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
+    if (excl.set_of != nullptr) {  // (wave-uniform)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nset += __shfl_xor(nset, o);
+    }
     if (lane == 0u) {
         const unsigned long long under = cnt < knn ? 1ull : 0ull;
+        if (excl.set_of != nullptr) {
+            if (cnt) atomicAdd(&counters[HVS_CNT_SET_SLOTS], (unsigned long long)cnt);
+            if (under) atomicAdd(&counters[HVS_CNT_SET_UNDERFULL], under);
+            if (excl.set_of[q] != 0xFFFFFFFFu) atomicAdd(&counters[HVS_CNT_SET_RESTRICTED], 1ull);
+            if (nset) atomicAdd(&counters[HVS_CNT_SET_REFUSED], (unsigned long long)nset);
+        }
         if (npass) atomicAdd(&counters[HVS_CNT_PAIRS], (unsigned long long)npass);
         if (len) atomicAdd(&counters[HVS_CNT_SCANNED], (unsigned long long)len);
         if (cnt) atomicAdd(&counters[HVS_CNT_CAND_SLOTS], (unsigned long long)cnt);

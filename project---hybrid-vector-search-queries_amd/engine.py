@@ -147,9 +147,19 @@ class CandidatesInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class RowSetsInfo(C.Structure):
+    """hvs_row_sets_info (include/hvs.h)."""
+    _fields_ = [("n_sets", C.c_uint32), ("words_per_set", C.c_uint32), ("bytes", C.c_uint64), ("restricted_queries", C.c_uint32),
+                ("underfull_queries", C.c_uint32), ("refused_keys", C.c_uint64), ("kept_slots", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
 CANDIDATES_MAX = 8192
+ROW_SETS_MAX = 256
 VECTORS_MAX_EXTRA = 63
 CLAUSES_MAX_EXTRA = 255
 
@@ -327,6 +337,15 @@ def library():
         "hvs_candidates_stats": (C.c_int, [vp, C.POINTER(CandidatesInfo)]),
         "hvs_download_candidates_plan": (C.c_int, [vp, _u32p, _u32p, _u32p, C.c_uint32]),
         "hvs_candidates_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
+        "hvs_set_row_sets": (C.c_int, [vp, _u64p, C.c_uint32]),
+        "hvs_set_row_sets_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
+        "hvs_assign_row_sets": (C.c_int, [vp, C.c_uint32, _u32p, C.c_uint32, C.c_int]),
+        "hvs_get_row_sets": (C.c_int, [vp, _u64p]),
+        "hvs_set_query_row_sets": (C.c_int, [vp, _u32p, C.c_uint32]),
+        "hvs_set_query_row_sets_device": (C.c_int, [vp, vp, C.c_uint32, vp]),
+        "hvs_query_in_row_sets": (C.c_int, [vp, _f32p, _u32p, C.c_uint32, C.c_float, _u32p, _f32p]),
+        "hvs_row_sets_stats": (C.c_int, [vp, C.POINTER(RowSetsInfo)]),
+        "hvs_row_sets_compact_plan": (None, [_u64p, _u64p, C.c_uint32, C.c_uint32, _u64p]),
         "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
         "hvs_set_query_vectors_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "hvs_query_vectors": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
@@ -366,6 +385,38 @@ def unpack_row_mask(words, n):
     """The inverse of pack_row_mask."""
     words = np.ascontiguousarray(words, "<u8")
     return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def pack_row_sets(sets):
+    """bool array [n_sets][n] -> (n_sets, n, the n_sets x ceil(n / 64) uint64 words of hvs_set_row_sets)."""
+    sets = np.ascontiguousarray(sets, dtype=bool)
+    if sets.ndim != 2:
+        raise HvsError(-1, "row sets must be a bool array [n_sets][n]")
+    words = np.zeros((sets.shape[0], (sets.shape[1] + 63) // 64), np.uint64)
+    for s in range(sets.shape[0]):
+        words[s] = pack_row_mask(sets[s])
+    return sets.shape[0], sets.shape[1], words
+
+
+def row_sets_compact_plan(sets, live):
+    """hvs_row_sets_compact_plan: the sets (bool [n_sets][n]) as they must be after a compaction under the mask `live` (bool [n],
+    or None = every row live): a bool array [n_sets][live rows]."""
+    n_sets, n, words = pack_row_sets(sets)
+    lw = None
+    n_live = n
+    if live is not None:
+        live = np.ascontiguousarray(live, dtype=bool).ravel()
+        if live.size != n:
+            raise HvsError(-1, "live must hold one bool per row")
+        lw = pack_row_mask(live)
+        n_live = int(live.sum())
+    out = np.full_like(words, np.uint64(0xA5A5A5A5A5A5A5A5))
+    library().hvs_row_sets_compact_plan(words.ctypes.data_as(_u64p), lw.ctypes.data_as(_u64p) if lw is not None else None, n, n_sets,
+                                        out.ctypes.data_as(_u64p))
+    full = np.stack([unpack_row_mask(out[s], out.shape[1] * 64) for s in range(n_sets)]) if n_sets else np.zeros((0, 0), bool)
+    if n_sets and full[:, n_live:].any():
+        raise HvsError(-1, "hvs_row_sets_compact_plan left bits at or past the live rows")
+    return full[:, :n_live]
 
 
 def mask_plan(live, k, sample_proportion):
@@ -939,14 +990,15 @@ class Engine:
 
     # --- the vec_query seam
     def query(self, q_rows, sample_proportion=1.0, want_dists=True, out_ids=None, out_dists=None, max_dist2=None, after=None, exclude=None,
-              among=None):
+              among=None, row_set=None):
         """hvs_query: host rows in, host ids (and distances) out.  `out_ids` / `out_dists`: caller-provided arrays
         (e.g. views of pinned memory) to be filled instead of fresh ones.  `max_dist2`: one squared-distance cap per query
         (hvs_query_within: the k nearest rows within it); None = no caps.  `after`: (dists, ids), one result cursor per query
         (hvs_query_after: the k nearest rows after that key); None = no cursors.  `exclude`: one exclusion list per query, a
         list of id sequences or an (offsets, ids) pair (hvs_query_excluding: the k nearest rows not in it); None = no lists.
         `among`: one candidate list per query in the same forms (hvs_query_among: the k nearest rows among it; with max_dist2
-        only); None = no lists."""
+        only); None = no lists.  `row_set`: one set index per query, 0xFFFFFFFF = no restriction (hvs_query_in_row_sets: the k
+        nearest rows inside that shared row set; on its own in one call); None = no indices."""
         q = np.ascontiguousarray(q_rows, np.float32)
         if q.ndim != 2 or q.shape[1] != QCOLS:
             raise HvsError(-1, "query rows must be nq x 104 float32")
@@ -968,7 +1020,15 @@ class Engine:
             ai = np.ascontiguousarray(after[1], np.uint32).ravel()
             if ad.size != nq or ai.size != nq:
                 raise HvsError(-1, "after must be (dists, ids) with one entry per query each")
-        if among is not None:
+        if row_set is not None:
+            if after is not None or exclude is not None or among is not None or caps is not None:
+                raise HvsError(-1, "row_set stands alone in one call: attach caps, cursors or lists to the resident queries")
+            idx = np.ascontiguousarray(row_set, np.uint32).ravel()
+            if idx.size != nq:
+                raise HvsError(-1, "row_set must hold one set index per query")
+            self._ck(self._lib.hvs_query_in_row_sets(self._h, _fp(q), _up(idx), nq, sample_proportion, _up(ids),
+                                                     _fp(d) if d is not None else None))
+        elif among is not None:
             if after is not None or exclude is not None:
                 raise HvsError(-1, "among composes with max_dist2 only in one call: attach cursors or exclusion lists to the resident queries")
             co, ci = _exclude_csr(among)
@@ -1113,6 +1173,63 @@ class Engine:
         begin, count, ids = np.empty(int(nq), np.uint32), np.empty(int(nq), np.uint32), np.empty(max(total, 1), np.uint32)
         self._ck(min(self._lib.hvs_download_exclude_plan(self._h, _up(begin), _up(count), _up(ids), total), 0))
         return int(total), begin, count, ids[:total].copy()
+
+    # --- shared row sets (include/hvs.h "shared row sets")
+    def set_row_sets(self, sets, stream=None):
+        """Load the context's row sets: a bool array [n_sets][n], a uint64 array [n_sets][ceil(n / 64)] of packed words
+        (hvs_set_row_sets), a GPU tensor of packed words, int64 [n_sets][ceil(n / 64)] (hvs_set_row_sets_device; `stream` as for
+        set_queries_device), or None to remove the sets.  The queries' set indices go with the sets they named."""
+        if sets is None:
+            self._ck(self._lib.hvs_set_row_sets(self._h, None, 0))
+        elif hasattr(sets, "data_ptr") and hasattr(sets, "shape"):
+            import torch
+            if not isinstance(sets, torch.Tensor) or sets.dtype != torch.int64 or not sets.is_cuda or not sets.is_contiguous() or sets.dim() != 2:
+                raise HvsError(-1, "set_row_sets: the tensor must be int64 [n_sets][ceil(n / 64)], contiguous and on a GPU")
+            if sets.shape[1] != (self.n + 63) // 64:
+                raise HvsError(-1, "set_row_sets: every set needs ceil(n / 64) words")
+            self._ck(self._lib.hvs_set_row_sets_device(self._h, C.c_void_p(int(sets.data_ptr())), int(sets.shape[0]), _stream_ptr(stream)))
+        else:
+            a = np.asarray(sets)
+            if a.dtype == np.uint64:
+                words = np.ascontiguousarray(a)
+                if words.ndim != 2 or words.shape[1] != (self.n + 63) // 64:
+                    raise HvsError(-1, "set_row_sets: packed sets must be uint64 [n_sets][ceil(n / 64)]")
+                n_sets = words.shape[0]
+            else:
+                n_sets, n, words = pack_row_sets(a)
+                if n != self.n:
+                    raise HvsError(-1, "set_row_sets: every set needs one bool per row")
+            self._ck(self._lib.hvs_set_row_sets(self._h, words.ctypes.data_as(_u64p), n_sets))
+
+    def assign_row_sets(self, set, ids, member=True):
+        """hvs_assign_row_sets: put the rows `ids` into set `set` (member=False: take them out); ids >= n are ignored."""
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        self._ck(self._lib.hvs_assign_row_sets(self._h, int(set), _up(ids), ids.size, 1 if member else 0))
+
+    def row_sets(self):
+        """hvs_get_row_sets: the sets as a bool array [n_sets][n]."""
+        st, n = self.row_sets_stats(), self.n
+        words = np.zeros((st.n_sets, st.words_per_set), np.uint64)
+        self._ck(self._lib.hvs_get_row_sets(self._h, words.ctypes.data_as(_u64p)))
+        return np.stack([unpack_row_mask(words[s], n) for s in range(st.n_sets)])
+
+    def set_query_row_sets(self, idx, stream=None):
+        """Attach one set index per resident query (0xFFFFFFFF = no restriction): a host array (hvs_set_query_row_sets), an
+        int32 / uint32 GPU tensor (hvs_set_query_row_sets_device), or None to remove the indices."""
+        if idx is None:
+            self._ck(self._lib.hvs_set_query_row_sets(self._h, None, 0))
+        elif hasattr(idx, "data_ptr") and hasattr(idx, "shape"):
+            ptr, n = _device_u32(idx, "set_query_row_sets")
+            self._ck(self._lib.hvs_set_query_row_sets_device(self._h, C.c_void_p(ptr) if ptr else None, n, _stream_ptr(stream)))
+        else:
+            idx = np.ascontiguousarray(idx, np.uint32).ravel()
+            self._ck(self._lib.hvs_set_query_row_sets(self._h, _up(idx), idx.size))
+
+    def row_sets_stats(self):
+        """hvs_row_sets_stats: the sets loaded, and restricted / under-full queries, refused keys and non-pad slots of the last call."""
+        e = RowSetsInfo()
+        self._ck(self._lib.hvs_row_sets_stats(self._h, C.byref(e)))
+        return e
 
     # --- per-query candidate lists (include/hvs.h "per-query candidate lists")
     def set_candidate_ids(self, lists, stream=None):
