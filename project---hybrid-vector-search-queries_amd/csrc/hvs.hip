@@ -217,6 +217,32 @@ struct HvsPart {
 };
 constexpr uint32_t kPartTailRows = HVS_KMAX;  // rows of the tail replica: the most a query can be padded with
 
+// Per-query id lists and what reaches the resident queries the way they do (DESIGN 3.13a "staged attach"; 3.14, 3.17, 3.18).
+// A STAGING AREA: a caller's words (CSR offsets, set indices) as they came, the four-word status block of their check kernel and
+// what the host read back from it.  Nothing in force lies in one: leaf_stage fills it, the root judges every GPU's flags, and
+// only then does any GPU commit.
+struct HvsStage {
+    uint32_t *d_words = nullptr, *d_status = nullptr;
+    uint32_t cap = 0;                       // entries d_words has room for
+    uint32_t flags = 0, first = 0, end = 0;  // of the words staged last: the check's flags; (offsets) offsets[0], offsets[count]
+    uint32_t total() const { return flags ? 0u : end - first; }  // (the entries behind the offsets, once every pair is ascending)
+    void free_device() { HvsRowSet::drop(d_words, d_status), cap = 0; }
+};
+// where every query's normalised list lies in an id array, and its length
+struct HvsListIndex {
+    uint32_t *d_begin = nullptr, *d_count = nullptr;
+    uint32_t cap = 0;  // entries each of the two has room for
+    void free_device() { HvsRowSet::drop(d_begin, d_count), cap = 0; }
+};
+// the per-query id lists of one kind in force: every query's normalised list.  While `set` is false no launch reads d_ids.
+struct HvsIdLists {
+    uint32_t* d_ids = nullptr;
+    uint32_t ids_cap = 0;        // entries
+    uint32_t nq = 0, total = 0;  // of the lists in force: the user's queries, entries of d_ids (hvs_download_*_plan)
+    bool set = false, call = false;  // attached; the last call ran with them (hvs_exclude_stats, hvs_candidates_stats)
+    void free_device() { HvsRowSet::drop(d_ids), ids_cap = 0, set = false; }
+};
+
 // One value of each kind per query of a set: its distance cap, normalised by hvs_k_norm_caps, and its result cursor
 // -- the raw (distance, id) pair and d_after_lo = the cursor's key + 1, built from the pair by hvs_k_norm_after.
 // HvsQuerySet holds two of these: the engines' and, under category sets, the user's.  Caps and cursors are sized apart
@@ -227,16 +253,16 @@ struct HvsPerQuery {
     float* d_after_dist = nullptr;
     uint32_t* d_after_id = nullptr;
     uint32_t caps_cap = 0, after_cap = 0;  // entries d_max_d2 / each of the three cursor arrays has room for
-    // exclusion lists: where query q's normalised list lies in HvsQuerySet::d_ex_ids, and its length
-    uint32_t *d_ex_begin = nullptr, *d_ex_count = nullptr;
-    uint32_t excl_cap = 0;  // entries each of the two has room for
+    // exclusion lists: where query q's normalised list lies in HvsQuerySet::excl.d_ids, and its length
+    HvsListIndex ex;
     // shared row sets: query q's set index, or 0xFFFFFFFF for "no restriction"
     uint32_t* d_set_of = nullptr;
     uint32_t set_of_cap = 0;
     void free_device()
     {
-        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id, d_ex_begin, d_ex_count, d_set_of);
-        caps_cap = after_cap = excl_cap = set_of_cap = 0;
+        HvsRowSet::drop(d_max_d2, d_after_lo, d_after_dist, d_after_id, d_set_of);
+        ex.free_device();
+        caps_cap = after_cap = set_of_cap = 0;
     }
 };
 
@@ -261,16 +287,14 @@ struct HvsInSet {
     float* d_value = nullptr;          // nsub
     uint32_t uq_cap = 0, sub_cap = 0;  // user queries / sub-queries the buffers above have room for
     // extra vectors: this GPU's slice of the caller's CSR -- the offsets as they came (staged and checked before anything is
-    // replaced, like HvsQuerySet::d_ex_off), the status block of the check, and the vectors, 100 floats each
-    uint32_t *d_v_off = nullptr, *d_v_status = nullptr;
+    // replaced, like HvsQuerySet::off_stage; the fill kernels read them there), and the vectors, 100 floats each
+    HvsStage v_stage;
     float* d_vecs = nullptr;
-    uint32_t v_off_cap = 0;            // user queries d_v_off has room for (+ 1 entry)
-    size_t vecs_cap = 0;               // vectors d_vecs has room for
-    uint32_t v_flags = 0, v_base = 0, v_total = 0;  // of the offsets staged last: HVS_VEC_BAD_*, offsets[0], offsets[nq]
-    // extra clauses: staged and checked in d_v_off / d_v_status as the vectors' offsets are; their [type, v, l, r], 4 floats each,
+    size_t vecs_cap = 0;               // floats d_vecs has room for
+    // extra clauses: staged and checked in v_stage as the vectors' offsets are; their [type, v, l, r], 4 floats each,
     // and, where they bring vectors of their own (clause_vecs, while active), those in d_vecs
     float* d_attrs = nullptr;
-    size_t attrs_cap = 0;              // clauses d_attrs has room for
+    size_t attrs_cap = 0;              // floats d_attrs has room for
     bool clause_vecs = false;
     HvsPerQuery user;                  // the user's caps and cursors: room for uq_cap each, allocated at attach
     uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
@@ -296,8 +320,9 @@ struct HvsInSet {
     {
         HvsRowSet::drop(d_uq, d_sub_off, d_set_off, d_parent, d_value, d_m_ids, d_m_dists, d_stat);
         HvsRowSet::drop(d_p_pack, d_p_sub_off, d_p_eff, d_p_stat, d_p_off, d_p_vals);
-        HvsRowSet::drop(d_v_off, d_v_status, d_vecs, d_attrs);
-        p_cap = p_off_cap = pv_cap = v_off_cap = 0;
+        HvsRowSet::drop(d_vecs, d_attrs);
+        v_stage.free_device();
+        p_cap = p_off_cap = pv_cap = 0;
         vecs_cap = attrs_cap = 0;
         user.free_device();
         for (hipEvent_t* ev : {&ev_x0, &ev_x1, &ev_m0, &ev_m1})
@@ -321,45 +346,45 @@ struct HvsQuerySet {
     HvsPerQuery eng;           // what the launches read: one entry per resident query (under sets: per sub-query)
     bool caps_set = false, after_set = false;
     bool call_capped = false, call_after = false;  // the last call ran with caps / with cursors (hvs_within_stats, hvs_after_stats)
-    // Exclusion lists.  d_ex_ids holds every query's normalised list (under category sets too: sub-queries read
-    // their parent's through eng.d_ex_begin / d_ex_count); d_ex_off / d_ex_status are where a caller's offsets are checked before
-    // anything is replaced.  While excl_set is false no launch reads any of it.  While excl_set and not after_set,
-    // eng.d_after_lo holds zeros for every resident query (zero_after_lo): the list forms are cursor forms.
-    bool excl_set = false, call_excl = false;
-    uint32_t *d_ex_ids = nullptr, *d_ex_off = nullptr, *d_ex_status = nullptr;
-    uint32_t ex_ids_cap = 0, ex_off_cap = 0;  // entries
-    uint32_t ex_nq = 0, ex_total = 0;         // of the lists in force: the user's queries, entries of d_ex_ids (hvs_download_exclude_plan)
-    uint32_t st_flags = 0, st_base = 0, st_total = 0;  // of the offsets staged last (leaf_exclude_stage): HVS_EXCL_BAD_*, offsets[0], ids behind them
-    // Candidate lists: d_cd_ids holds every query's normalised list, d_cd_begin / d_cd_count where it lies.  A
-    // caller's offsets are checked in d_ex_off / d_ex_status too (a staging area: nothing in force lies there).  While cand_set
-    // is false no launch reads any of it; while it is true hvs_k_scan_candidates answers every call.  Never set while in.active.
-    bool cand_set = false, call_cand = false;
-    uint32_t *d_cd_ids = nullptr, *d_cd_begin = nullptr, *d_cd_count = nullptr;
-    uint32_t cd_ids_cap = 0, cd_q_cap = 0;  // entries of d_cd_ids / of each of the other two
-    uint32_t cd_nq = 0, cd_total = 0;       // of the lists in force: the queries, entries of d_cd_ids (hvs_download_candidates_plan)
+    // Exclusion lists.  excl.d_ids holds every query's normalised list (under category sets too: sub-queries read
+    // their parent's through eng.ex); off_stage is where a caller's offsets are checked before anything is replaced.  While
+    // excl.set is false no launch reads any of it.  While excl.set and not after_set, eng.d_after_lo holds zeros for every
+    // resident query (zero_after_lo): the list forms are cursor forms.
+    HvsIdLists excl;
+    // Candidate lists: cand.d_ids holds every query's normalised list, cand_at where it lies.  A caller's offsets
+    // are checked in off_stage too.  While cand.set is false no launch reads any of it; while it is true hvs_k_scan_candidates
+    // answers every call.  Never set while in.active.
+    HvsIdLists cand;
+    HvsListIndex cand_at;
+    HvsStage off_stage;  // the CSR offsets of exclusion and candidate lists; the normalisation kernels read them there
     // Shared row sets: the per-query set indices, in eng.d_set_of (under the expanded set: per sub-query, the
-    // user's in in.user.d_set_of).  A caller's indices are checked in d_rs_stage / d_rs_status before anything is replaced.
+    // user's in in.user.d_set_of).  A caller's indices are checked in idx_stage before anything is replaced.
     // While rset_set is false no launch reads any of it.  While it is true the list forms of the kernels run (with_after):
     // without exclusion lists they read d_rs_zero as every query's (begin, count) -- zeros, one per resident query -- and
     // without cursors eng.d_after_lo holds zeros (zero_after_lo).
     bool rset_set = false, call_rset = false;
-    uint32_t *d_rs_stage = nullptr, *d_rs_status = nullptr, *d_rs_zero = nullptr;
-    uint32_t rs_stage_cap = 0, rs_zero_cap = 0;  // entries
-    uint32_t st_rs_flags = 0;                    // of the indices staged last (leaf_query_sets_stage): 1 = an index names no set
+    HvsStage idx_stage;  // (flags: 1 = an index names no set)
+    uint32_t* d_rs_zero = nullptr;
+    uint32_t rs_zero_cap = 0;  // entries
     uint32_t res_lo = 0, res_hi = 0, res_k = 0;
     uint32_t set_gen = 0;      // counts the resident sets this GPU has held
     uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
     HvsInSet in;               // category sets of the resident queries
+    // every flag that says "this is attached to the resident queries", in one place: what drops, lends out or clears attachments
+    // goes through it (drop_attached, DetachedForProbe, leaf_detach_flag)
+    enum Attachment { kCapsOn, kCursorsOn, kExclOn, kCandOn, kRowSetsOn, kAttachments };
+    bool& attached(int a) { return *std::array<bool*, kAttachments>{{&caps_set, &after_set, &excl.set, &cand.set, &rset_set}}[(size_t)a]; }
     void free_device()
     {
         eng.free_device(), in.free_device();
-        HvsRowSet::drop(d_ex_ids, d_ex_off, d_ex_status, d_cd_ids, d_cd_begin, d_cd_count, d_rs_stage, d_rs_status, d_rs_zero);
-        ex_ids_cap = ex_off_cap = cd_ids_cap = cd_q_cap = rs_stage_cap = rs_zero_cap = 0;
-        excl_set = cand_set = rset_set = false;
+        excl.free_device(), cand.free_device(), cand_at.free_device(), off_stage.free_device(), idx_stage.free_device();
+        HvsRowSet::drop(d_rs_zero);
+        rs_zero_cap = 0;
+        rset_set = false;
     }
     void drop_attached()  // caps off, cursors off, lists off, no results: they belonged to a set that is no longer the engines'
     {
-        caps_set = after_set = excl_set = cand_set = rset_set = false;
+        for (int a = 0; a < kAttachments; ++a) attached(a) = false;
         drop_results();
     }
     // no query has a result row: the rows (under sets the merged rows too) hold ids of a row numbering that has gone
@@ -650,7 +675,7 @@ bool capped(const hvs_ctx* c) { return c->qs.caps_set; }
 // ... carry result cursors: the AFTER kernels run (with_capped_after)
 bool has_after(const hvs_ctx* c) { return c->qs.after_set; }
 // ... carry exclusion lists: the EXCL forms of the AFTER kernels run (with_after)
-bool has_excl(const hvs_ctx* c) { return c->qs.excl_set; }
+bool has_excl(const hvs_ctx* c) { return c->qs.excl.set; }
 // ... carry set indices of shared row sets: the same forms run, with the set's bit as one more admission test
 bool has_rset(const hvs_ctx* c) { return c->qs.rset_set && c->rs.n_sets != 0u; }
 // what the list forms receive: the lists (or, while only set indices are attached, empty lists for every query: d_rs_zero) and
@@ -658,8 +683,8 @@ bool has_rset(const hvs_ctx* c) { return c->qs.rset_set && c->rs.n_sets != 0u; }
 HvsExcl excl_arg(const hvs_ctx* c)
 {
     const HvsQuerySet& s = c->qs;
-    HvsExcl x{s.eng.d_ex_begin, s.eng.d_ex_count, s.d_ex_ids, nullptr, nullptr, 0u, 0u};
-    if (!s.excl_set) x.begin = x.count = x.ids = s.d_rs_zero;
+    HvsExcl x{s.eng.ex.d_begin, s.eng.ex.d_count, s.excl.d_ids, nullptr, nullptr, 0u, 0u};
+    if (!s.excl.set) x.begin = x.count = x.ids = s.d_rs_zero;
     if (has_rset(c)) {
         x.set_of = s.eng.d_set_of;
         x.set_bits = c->rs.d_sets;
@@ -669,7 +694,7 @@ HvsExcl excl_arg(const hvs_ctx* c)
     return x;
 }
 // ... carry candidate lists: hvs_k_scan_candidates answers, whatever engine is selected (run_candidates)
-bool has_cand(const hvs_ctx* c) { return c->qs.cand_set; }
+bool has_cand(const hvs_ctx* c) { return c->qs.cand.set; }
 // the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
 uint32_t user_nq(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.nuq : c->nq; }
 const float* user_queries(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_uq : c->d_q; }
@@ -719,19 +744,14 @@ uint32_t k_changed(hvs_ctx* c)
 // the planner probe runs its own queries through the context: caps and cursors belong to the caller's, and wait outside
 struct DetachedForProbe {
     HvsQuerySet& s;
-    const bool caps, after, excl, cand, rset;
-    explicit DetachedForProbe(HvsQuerySet& qs)
-        : s(qs), caps(qs.caps_set), after(qs.after_set), excl(qs.excl_set), cand(qs.cand_set), rset(qs.rset_set)
+    bool was[HvsQuerySet::kAttachments];
+    explicit DetachedForProbe(HvsQuerySet& qs) : s(qs)
     {
-        s.caps_set = s.after_set = s.excl_set = s.cand_set = s.rset_set = false;
+        for (int a = 0; a < HvsQuerySet::kAttachments; ++a) was[a] = s.attached(a), s.attached(a) = false;
     }
     ~DetachedForProbe()
     {
-        s.caps_set = caps;
-        s.after_set = after;
-        s.excl_set = excl;
-        s.cand_set = cand;
-        s.rset_set = rset;
+        for (int a = 0; a < HvsQuerySet::kAttachments; ++a) s.attached(a) = was[a];
     }
 };
 const uint32_t* index_mask(const hvs_ctx* c) { return c->rs.h_stale.empty() ? c->rs.d_live : c->rs.d_ilive; }
@@ -904,24 +924,26 @@ int dev_alloc(hvs_ctx* c, T** p, size_t count)
     return HVS_OK;
 }
 
-// room for n caps and / or n cursors in `v` (contents are not kept; a failure leaves the capacity at 0)
+// Room for n entries in *p -- and in every one of `more`, buffers that grow together under the one capacity -- whatever they
+// held: contents are NOT kept (grow_keep keeps them), a failure leaves the capacity at 0, and nothing happens while n fits.
+template <typename Cap, typename T, typename... More>
+int ensure_room(hvs_ctx* c, T** p, Cap& cap, size_t n, More**... more)
+{
+    if (n <= cap) return HVS_OK;
+    cap = 0;
+    int rc = dev_alloc(c, p, n);
+    ((rc = rc ? rc : dev_alloc(c, more, n)), ...);
+    if (!rc) cap = (Cap)n;
+    return rc;
+}
+
+// room for n caps and / or n cursors in `v`
 enum : unsigned { kCaps = 1u, kCursors = 2u };
 int per_query_room(hvs_ctx* c, HvsPerQuery& v, unsigned which, uint32_t n)
 {
-    int rc;
-    if ((which & kCaps) && n > v.caps_cap) {
-        v.caps_cap = 0;
-        if ((rc = dev_alloc(c, &v.d_max_d2, (size_t)n))) return rc;
-        v.caps_cap = n;
-    }
-    if ((which & kCursors) && n > v.after_cap) {
-        v.after_cap = 0;
-        if ((rc = dev_alloc(c, &v.d_after_lo, (size_t)n)) || (rc = dev_alloc(c, &v.d_after_dist, (size_t)n)) ||
-            (rc = dev_alloc(c, &v.d_after_id, (size_t)n)))
-            return rc;
-        v.after_cap = n;
-    }
-    return HVS_OK;
+    int rc = which & kCaps ? ensure_room(c, &v.d_max_d2, v.caps_cap, n) : HVS_OK;
+    if (!rc && (which & kCursors)) rc = ensure_room(c, &v.d_after_lo, v.after_cap, n, &v.d_after_dist, &v.d_after_id);
+    return rc;
 }
 
 // Device temporaries of one scope, freed when it ends, whichever way it ends.  `lend`: the temporary also stands in for one of
@@ -1947,26 +1969,13 @@ int ensure_items(hvs_ctx* c)
     const uint32_t nseg = S.first[L.K + 1];
     if (nquads > (1u << HVS_ITEM_QUAD_BITS)) return fail(c, HVS_EINVAL, "internal: too many query quads for the item code");
     int rc;
-    if (nquads > c->quads_cap) {
-        c->quads_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_qlo, (size_t)nquads))) return rc;
-        if ((rc = dev_alloc(c, &c->d_qhi, (size_t)nquads))) return rc;
-        c->quads_cap = nquads;
-    }
-    if (nseg + 1u > c->segs_cap) {
-        c->segs_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_segcnt, (size_t)nseg + 1u))) return rc;
-        if ((rc = dev_alloc(c, &c->d_segoff, (size_t)nseg + 1u))) return rc;
-        c->segs_cap = nseg + 1u;
-    }
+    if ((rc = ensure_room(c, &c->d_qlo, c->quads_cap, nquads, &c->d_qhi)) ||
+        (rc = ensure_room(c, &c->d_segcnt, c->segs_cap, (size_t)nseg + 1u, &c->d_segoff)))
+        return rc;
     if (!c->d_lvloff && (rc = dev_alloc(c, &c->d_lvloff, (size_t)32))) return rc;
     if (!c->d_cursor && (rc = dev_alloc(c, &c->d_cursor, (size_t)16))) return rc;
     const size_t worst = (size_t)nquads * (size_t)(nseg - S.first[1]);  // every quad meets every segment (type 0)
-    if (worst > c->items_cap) {
-        c->items_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_items, worst))) return rc;
-        c->items_cap = worst;
-    }
+    if ((rc = ensure_room(c, &c->d_items, c->items_cap, worst))) return rc;
     return HVS_OK;
 }
 
@@ -2361,9 +2370,9 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     HvsQuerySet& s = c->qs;
     s.call_capped = capped(c);
     s.call_after = has_after(c);
-    s.call_excl = has_excl(c);
+    s.excl.call = has_excl(c);
     s.call_rset = has_rset(c);
-    s.call_cand = true;
+    s.cand.call = true;
     s.in.call = false;
     s.answered(q0, nq, c->k, s.set_gen);
     int rc = call_begin(c);
@@ -2371,7 +2380,7 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     if ((rc = hooks.before(0u, nq))) return rc;
     if (nq) {
         const int ev = kernel_timer_begin(c);
-        const HvsExcl cand{s.d_cd_begin, s.d_cd_count, s.d_cd_ids};
+        const HvsExcl cand{s.cand_at.d_begin, s.cand_at.d_count, s.cand.d_ids};
         HvsExcl excl = excl_arg(c);  // (the scan tells "no lists" by a null `begin`; the sets ride along either way)
         if (!has_excl(c)) excl.begin = excl.count = excl.ids = nullptr;
         with_cap(c->k <= 128u ? 256 : 512, [&](auto CAPT) {
@@ -2406,7 +2415,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
     if (has_cand(c)) return run_candidates(c, q0, nq, cut, hooks);
-    c->qs.call_cand = false;
+    c->qs.cand.call = false;
     const uint32_t sn = cut.sn, sampled = cut.sampled, of_rows = cut.of_rows;
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
@@ -2423,7 +2432,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     }
     c->qs.call_capped = capped(c);
     c->qs.call_after = has_after(c);
-    c->qs.call_excl = has_excl(c);
+    c->qs.excl.call = has_excl(c);
     c->qs.call_rset = has_rset(c);
     c->qs.in.call = false;  // (in_run sets it once the merge is enqueued)
     c->qs.answered(q0, nq, c->k, c->qs.set_gen);
@@ -2895,6 +2904,14 @@ int copy_from_device(hvs_ctx* c, void* dst, const void* src, int src_dev, size_t
     return HVS_OK;
 }
 
+// a caller's array to this context's GPU, on its stream: from host memory (src_dev < 0) or from device memory of GPU src_dev
+int copy_in(hvs_ctx* c, void* dst, const void* src, int src_dev, size_t bytes)
+{
+    if (src_dev >= 0) return copy_from_device(c, dst, src, src_dev, bytes);
+    if (bytes) HVS_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return HVS_OK;
+}
+
 // hvs_load_data_device: leaf_load_data_from_peer with the caller's buffer in the place of a peer's D
 int leaf_load_data_device(hvs_ctx* c, const float* d_rows, int src_dev, uint32_t n)
 {
@@ -2973,136 +2990,107 @@ int zero_after_lo(hvs_ctx* c)
     return HVS_OK;
 }
 
-// ---- exclusion lists: two steps per GPU, so that a refusal on any GPU leaves every GPU as it was ----
-// Step 1: `count` + 1 offsets from `off` (host memory, src_dev < 0, or device memory of GPU src_dev) into the staging array and
-// through hvs_k_check_exclude.  `first`: they are the head of the caller's array.  Leaves the flags, the first offset and the
-// number of ids behind it in the query set's st_* fields; nothing that is in force is touched.
-// `cand`: they are candidate lists' (DESIGN 3.17): the same staging area, hvs_k_check_candidates with its own length limit.
-int leaf_exclude_stage(hvs_ctx* c, const uint32_t* off, int src_dev, uint32_t count, bool first, bool cand = false)
+// ---- the staged attach: two steps per GPU, so that a refusal on any GPU leaves every GPU as it was ----
+// Step 1, the same for every kind: `words` of the caller's (host memory, src_dev < 0, or device memory of GPU src_dev) into the
+// staging area `st` and through the kind's check kernel -- `check(st)` enqueues it --, and the status block back into st.flags /
+// first / end.  Nothing that is in force is touched.  An earlier call's re-runs are resolved first, under what they were asked
+// under; `expanded`: the words are a client's of the expanded set, which begins as every change of that set does (in_begin).
+int in_begin(hvs_ctx* c);
+template <typename Check>
+int leaf_stage(hvs_ctx* c, HvsStage& st, bool expanded, const uint32_t* src, int src_dev, uint32_t words, Check check)
 {
-    HvsQuerySet& s = c->qs;
     int rc;
-    HVS_HIP(c, hipSetDevice(c->device));
-    if ((rc = resolve_overflow(c))) return rc;  // (an earlier call's re-runs: under the lists they were asked under)
-    if (count + 1u > s.ex_off_cap) {
-        s.ex_off_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_ex_off, (size_t)count + 1u))) return rc;
-        s.ex_off_cap = count + 1u;
+    if (expanded)
+        rc = in_begin(c);
+    else {
+        HVS_HIP(c, hipSetDevice(c->device));
+        rc = resolve_overflow(c);
     }
-    if (!s.d_ex_status && (rc = dev_alloc(c, &s.d_ex_status, (size_t)4))) return rc;
-    if (src_dev < 0)
-        HVS_HIP(c, hipMemcpyAsync(s.d_ex_off, off, ((size_t)count + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    else if ((rc = copy_from_device(c, s.d_ex_off, off, src_dev, ((size_t)count + 1u) * sizeof(uint32_t))))
-        return rc;
-    HVS_HIP(c, hipMemsetAsync(s.d_ex_status, 0, 4 * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(cand ? hvs_k_check_candidates : hvs_k_check_exclude, dim3(hvs_ceil_div(std::max(count, 1u), 256u)), dim3(256), 0, c->stream,
-                       s.d_ex_off, count, first ? 1 : 0, s.d_ex_status);
-    HVS_HIP(c, hipGetLastError());
+    if (rc || (rc = ensure_room(c, &st.d_words, st.cap, std::max(words, 1u)))) return rc;
+    if (!st.d_status && (rc = dev_alloc(c, &st.d_status, (size_t)4))) return rc;
+    if ((rc = copy_in(c, st.d_words, src, src_dev, (size_t)words * sizeof(uint32_t)))) return rc;
+    HVS_HIP(c, hipMemsetAsync(st.d_status, 0, 4 * sizeof(uint32_t), c->stream));
+    if ((rc = check(st))) return rc;
     uint32_t h[4] = {0, 0, 0, 0};
-    HVS_HIP(c, hipMemcpyAsync(h, s.d_ex_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(h, st.d_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    s.st_flags = h[0];
-    s.st_base = h[1];
-    s.st_total = h[0] ? 0u : h[2] - h[1];  // (offsets[count] is the id array's length only once every pair is ascending)
+    st.flags = h[0], st.first = h[1], st.end = h[2];
     return HVS_OK;
 }
-// Step 2 (every GPU's offsets were accepted): the ids behind the staged offsets -- `ids` is the caller's array -- are copied
-// and normalised for rows [row0, row0 + n_rows) by hvs_k_norm_exclude; under category sets they are the user's, and every
-// sub-query takes its parent's pair.
-int leaf_exclude_commit(hvs_ctx* c, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0, uint32_t n_rows)
+// the check of `count` + 1 staged CSR offsets: no list longer than `limit`; `first`: they are the head of the caller's array
+int check_offsets(hvs_ctx* c, const HvsStage& st, uint32_t count, bool first, uint32_t limit)
 {
-    HvsQuerySet& s = c->qs;
-    const bool sets = s.in.active;
-    HvsPerQuery& dst = sets ? s.in.user : s.eng;
-    int rc;
-    HVS_HIP(c, hipSetDevice(c->device));
-    s.excl_set = false;  // (the buffers are about to change)
-    auto room = [&](HvsPerQuery& v, uint32_t n) -> int {
-        if (n <= v.excl_cap) return HVS_OK;
-        v.excl_cap = 0;
-        if ((rc = dev_alloc(c, &v.d_ex_begin, (size_t)n)) || (rc = dev_alloc(c, &v.d_ex_count, (size_t)n))) return rc;
-        v.excl_cap = n;
-        return HVS_OK;
-    };
-    if ((rc = room(dst, std::max(count, 1u))) || (sets && (rc = room(s.eng, std::max(c->nq, 1u))))) return rc;
-    const uint32_t total = s.st_total;
-    if (std::max(total, 1u) > s.ex_ids_cap) {
-        s.ex_ids_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_ex_ids, (size_t)std::max(total, 1u)))) return rc;
-        s.ex_ids_cap = std::max(total, 1u);
-    }
-    if (total) {
-        if (src_dev < 0)
-            HVS_HIP(c, hipMemcpyAsync(s.d_ex_ids, ids + s.st_base, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        else if ((rc = copy_from_device(c, s.d_ex_ids, ids + s.st_base, src_dev, (size_t)total * sizeof(uint32_t))))
-            return rc;
-    }
-    if (count) {
-        hipLaunchKernelGGL(hvs_k_norm_exclude, dim3(hvs_ceil_div(count, 4u)), dim3(256), 0, c->stream, s.d_ex_off, count, s.d_ex_ids, row0, n_rows,
-                           dst.d_ex_begin, dst.d_ex_count);
-        HVS_HIP(c, hipGetLastError());
-        if (sets && c->nq) {
-            hipLaunchKernelGGL(hvs_k_expand_exclude, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, s.in.d_parent, c->nq, dst.d_ex_begin,
-                               dst.d_ex_count, s.eng.d_ex_begin, s.eng.d_ex_count);
-            HVS_HIP(c, hipGetLastError());
-        }
-    }
-    if (!s.after_set && (rc = zero_after_lo(c))) return rc;
-    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
-    s.ex_nq = count;
-    s.ex_total = total;
-    s.excl_set = true;
-    return HVS_OK;
-}
-int leaf_exclude_remove(hvs_ctx* c)
-{
-    HVS_HIP(c, hipSetDevice(c->device));
-    if (int rc = resolve_overflow(c)) return rc;
-    c->qs.excl_set = false;
+    hipLaunchKernelGGL(hvs_k_check_offsets, dim3(hvs_ceil_div(std::max(count, 1u), 256u)), dim3(256), 0, c->stream, st.d_words, count, first ? 1 : 0,
+                       limit, st.d_status);
+    HVS_HIP(c, hipGetLastError());
     return HVS_OK;
 }
 
-// ---- candidate lists: staged by leaf_exclude_stage(cand), then, once every GPU's offsets were accepted, the ids
-// behind the staged offsets are copied and normalised in place for rows [row0, row0 + n_rows) by hvs_k_norm_candidates.
-int leaf_candidates_commit(hvs_ctx* c, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0, uint32_t n_rows)
+// ---- per-query id lists: exclusion lists and candidate lists ----
+// What tells the two kinds apart: the limit of the offsets' check, the normalisation kernel and its queries per workgroup, where
+// the lists and their index live, and what composes -- exclusion lists are the user's under the expanded set (every sub-query
+// takes its parent's pair) and are read by cursor forms (zero_after_lo); candidate lists are neither.
+struct ListKind {
+    uint32_t limit;
+    void (*norm)(const uint32_t*, uint32_t, uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*);
+    uint32_t queries_per_block;
+    HvsIdLists HvsQuerySet::*lists;
+    int flag;                // HvsQuerySet::Attachment
+    bool cursor_forms;       // expanded under in.active, zero_after_lo follows
+    const char *offsets, *too_long;  // of the refusals: the parameter's name, the limit's text
+};
+const ListKind kExcludeLists{HVS_EXCLUDE_MAX_, hvs_k_norm_exclude, 4u, &HvsQuerySet::excl, HvsQuerySet::kExclOn, true, "excl_offsets",
+                             ": a list has more than HVS_EXCLUDE_MAX entries"};
+const ListKind kCandidateLists{HVS_CANDIDATES_MAX_, hvs_k_norm_candidates, 1u, &HvsQuerySet::cand, HvsQuerySet::kCandOn, false, "cand_offsets",
+                               ": a list has more than HVS_CANDIDATES_MAX entries"};
+
+// Step 1 for lists: `count` + 1 offsets; `first`: they are the head of the caller's array
+int leaf_lists_stage(hvs_ctx* c, const ListKind& K, const uint32_t* off, int src_dev, uint32_t count, bool first)
+{
+    return leaf_stage(c, c->qs.off_stage, false, off, src_dev, count + 1u, [&](const HvsStage& st) { return check_offsets(c, st, count, first, K.limit); });
+}
+// Step 2 (every GPU's offsets were accepted): the ids behind the staged offsets -- `ids` is the caller's array -- are copied
+// and normalised in place for rows [row0, row0 + n_rows) by the kind's kernel; exclusion lists under category sets are the
+// user's, and every sub-query takes its parent's pair.
+int leaf_lists_commit(hvs_ctx* c, const ListKind& K, const uint32_t* ids, int src_dev, uint32_t count, uint32_t row0, uint32_t n_rows)
 {
     HvsQuerySet& s = c->qs;
+    HvsIdLists& L = s.*K.lists;
+    const bool sets = K.cursor_forms && s.in.active;
+    HvsListIndex& at = !K.cursor_forms ? s.cand_at : sets ? s.in.user.ex : s.eng.ex;
     int rc;
     HVS_HIP(c, hipSetDevice(c->device));
-    s.cand_set = false;  // (the buffers are about to change)
-    if (std::max(count, 1u) > s.cd_q_cap) {
-        s.cd_q_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_cd_begin, (size_t)std::max(count, 1u))) || (rc = dev_alloc(c, &s.d_cd_count, (size_t)std::max(count, 1u)))) return rc;
-        s.cd_q_cap = std::max(count, 1u);
-    }
-    const uint32_t total = s.st_total;
-    if (std::max(total, 1u) > s.cd_ids_cap) {
-        s.cd_ids_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_cd_ids, (size_t)std::max(total, 1u)))) return rc;
-        s.cd_ids_cap = std::max(total, 1u);
-    }
-    if (total) {
-        if (src_dev < 0)
-            HVS_HIP(c, hipMemcpyAsync(s.d_cd_ids, ids + s.st_base, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        else if ((rc = copy_from_device(c, s.d_cd_ids, ids + s.st_base, src_dev, (size_t)total * sizeof(uint32_t))))
-            return rc;
-    }
+    L.set = false;  // (the buffers are about to change)
+    if ((rc = ensure_room(c, &at.d_begin, at.cap, std::max(count, 1u), &at.d_count)) ||
+        (sets && (rc = ensure_room(c, &s.eng.ex.d_begin, s.eng.ex.cap, std::max(c->nq, 1u), &s.eng.ex.d_count))))
+        return rc;
+    const uint32_t total = s.off_stage.total();
+    if ((rc = ensure_room(c, &L.d_ids, L.ids_cap, std::max(total, 1u))) ||
+        (rc = copy_in(c, L.d_ids, ids + s.off_stage.first, src_dev, (size_t)total * sizeof(uint32_t))))
+        return rc;
     if (count) {
-        hipLaunchKernelGGL(hvs_k_norm_candidates, dim3(count), dim3(256), 0, c->stream, s.d_ex_off, count, s.d_cd_ids, row0, n_rows, s.d_cd_begin,
-                           s.d_cd_count);
+        hipLaunchKernelGGL(K.norm, dim3(hvs_ceil_div(count, K.queries_per_block)), dim3(256), 0, c->stream, s.off_stage.d_words, count, L.d_ids, row0, n_rows,
+                           at.d_begin, at.d_count);
         HVS_HIP(c, hipGetLastError());
+        if (sets && c->nq) {
+            hipLaunchKernelGGL(hvs_k_expand_exclude, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, s.in.d_parent, c->nq, at.d_begin, at.d_count,
+                               s.eng.ex.d_begin, s.eng.ex.d_count);
+            HVS_HIP(c, hipGetLastError());
+        }
     }
+    if (K.cursor_forms && !s.after_set && (rc = zero_after_lo(c))) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are the caller's again)
-    s.cd_nq = count;
-    s.cd_total = total;
-    s.cand_set = true;
+    L.nq = count;
+    L.total = total;
+    L.set = true;
     return HVS_OK;
 }
-int leaf_candidates_remove(hvs_ctx* c)
+// lists or set indices off one GPU's queries: an earlier call's re-runs are resolved under them, then the flag goes
+int leaf_detach_flag(hvs_ctx* c, int attachment)
 {
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;
-    c->qs.cand_set = false;
+    c->qs.attached(attachment) = false;
     return HVS_OK;
 }
 
@@ -3157,11 +3145,7 @@ int leaf_row_sets_prepare(hvs_ctx* c, const uint64_t* bits, int src_dev, uint32_
     if (bits) {
         const size_t bytes = (size_t)n_sets * src_words * sizeof(uint32_t);
         HVS_HIP(c, hipMalloc(reinterpret_cast<void**>(&staged), bytes));
-        if (src_dev < 0) {
-            const hipError_t e = hipMemcpyAsync(staged, bits, bytes, hipMemcpyHostToDevice, c->stream);
-            rc = e == hipSuccess ? HVS_OK : fail(c, HVS_EHIP, std::string("hvs_set_row_sets: ") + hipGetErrorString(e));
-        } else
-            rc = copy_from_device(c, staged, bits, src_dev, bytes);
+        rc = copy_in(c, staged, bits, src_dev, bytes);
     }
     if (!rc) rc = sets_build_next(c, staged, src_words, n_sets, words, rows);
     if (staged) (void)hipFree(staged);
@@ -3189,11 +3173,7 @@ int leaf_assign_row_sets(hvs_ctx* c, uint32_t set, const uint32_t* ids, uint32_t
     HvsRowSet& s = c->rs;
     int rc = begin_mutation(c);  // (an earlier call's re-runs: under the sets they were asked under)
     if (rc) return rc;
-    if (count > s.sets_ids_cap) {
-        s.sets_ids_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_sets_ids, (size_t)count))) return rc;
-        s.sets_ids_cap = count;
-    }
+    if ((rc = ensure_room(c, &s.d_sets_ids, s.sets_ids_cap, count))) return rc;
     HVS_HIP(c, hipMemcpyAsync(s.d_sets_ids, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(hvs_k_row_sets_assign, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, s.d_sets_ids, count, set_rows(c),
                        s.d_sets + (size_t)set * s.sets_words, member);
@@ -3213,38 +3193,16 @@ int leaf_get_row_sets(hvs_ctx* c, uint64_t* bits)
     return HVS_OK;
 }
 
-// The per-query set indices take the two steps of the exclusion lists, so that a refusal on any GPU leaves every GPU as it was.
-// Step 1: `count` indices from `idx` (host memory, src_dev < 0, or device memory of GPU src_dev) into the staging array and
-// through hvs_k_check_query_row_sets; the verdict is left in st_rs_flags and nothing that is in force is touched.
+// The per-query set indices take the two steps of the id lists.  Step 1: `count` indices into idx_stage and through
+// hvs_k_check_query_row_sets (flags: 1 = an index names no set).
 int leaf_query_sets_stage(hvs_ctx* c, const uint32_t* idx, int src_dev, uint32_t count)
 {
-    HvsQuerySet& s = c->qs;
-    int rc;
-    HVS_HIP(c, hipSetDevice(c->device));
-    if ((rc = resolve_overflow(c))) return rc;  // (an earlier call's re-runs: under the indices they were asked under)
-    if (std::max(count, 1u) > s.rs_stage_cap) {
-        s.rs_stage_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_rs_stage, (size_t)std::max(count, 1u)))) return rc;
-        s.rs_stage_cap = std::max(count, 1u);
-    }
-    if (!s.d_rs_status && (rc = dev_alloc(c, &s.d_rs_status, (size_t)2))) return rc;
-    if (count) {
-        if (src_dev < 0)
-            HVS_HIP(c, hipMemcpyAsync(s.d_rs_stage, idx, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        else if ((rc = copy_from_device(c, s.d_rs_stage, idx, src_dev, (size_t)count * sizeof(uint32_t))))
-            return rc;
-    }
-    HVS_HIP(c, hipMemsetAsync(s.d_rs_status, 0, 2 * sizeof(uint32_t), c->stream));
-    if (count) {
-        hipLaunchKernelGGL(hvs_k_check_query_row_sets, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, s.d_rs_stage, count, c->rs.n_sets,
-                           s.d_rs_status);
+    return leaf_stage(c, c->qs.idx_stage, false, idx, src_dev, count, [&](const HvsStage& st) {
+        if (!count) return HVS_OK;
+        hipLaunchKernelGGL(hvs_k_check_query_row_sets, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, st.d_words, count, c->rs.n_sets, st.d_status);
         HVS_HIP(c, hipGetLastError());
-    }
-    uint32_t h[2] = {0, 0};
-    HVS_HIP(c, hipMemcpyAsync(h, s.d_rs_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    s.st_rs_flags = h[0];
-    return HVS_OK;
+        return HVS_OK;
+    });
 }
 // Step 2 (every GPU's indices were accepted): the staged indices are the queries'; under the expanded set they are the user's, and
 // every sub-query takes its parent's.
@@ -3256,38 +3214,22 @@ int leaf_query_sets_commit(hvs_ctx* c, uint32_t count)
     int rc;
     HVS_HIP(c, hipSetDevice(c->device));
     s.rset_set = false;  // (the buffers are about to change)
-    auto room = [&](HvsPerQuery& v, uint32_t n) -> int {
-        if (n <= v.set_of_cap) return HVS_OK;
-        v.set_of_cap = 0;
-        if ((rc = dev_alloc(c, &v.d_set_of, (size_t)n))) return rc;
-        v.set_of_cap = n;
-        return HVS_OK;
-    };
-    if ((rc = room(dst, std::max(count, 1u))) || (sets && (rc = room(s.eng, std::max(c->nq, 1u))))) return rc;
-    if (std::max(c->nq, 1u) > s.rs_zero_cap) {
-        s.rs_zero_cap = 0;
-        if ((rc = dev_alloc(c, &s.d_rs_zero, (size_t)std::max(c->nq, 1u)))) return rc;
-        s.rs_zero_cap = std::max(c->nq, 1u);
-    }
+    if ((rc = ensure_room(c, &dst.d_set_of, dst.set_of_cap, std::max(count, 1u))) ||
+        (sets && (rc = ensure_room(c, &s.eng.d_set_of, s.eng.set_of_cap, std::max(c->nq, 1u)))) ||
+        (rc = ensure_room(c, &s.d_rs_zero, s.rs_zero_cap, std::max(c->nq, 1u))))
+        return rc;
     HVS_HIP(c, hipMemsetAsync(s.d_rs_zero, 0, (size_t)s.rs_zero_cap * sizeof(uint32_t), c->stream));
     if (count) {
-        HVS_HIP(c, hipMemcpyAsync(dst.d_set_of, s.d_rs_stage, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        HVS_HIP(c, hipMemcpyAsync(dst.d_set_of, s.idx_stage.d_words, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         if (sets && c->nq) {
             hipLaunchKernelGGL(hvs_k_expand_query_row_sets, dim3(hvs_ceil_div(c->nq, 256u)), dim3(256), 0, c->stream, s.in.d_parent, c->nq, dst.d_set_of,
                                s.eng.d_set_of);
             HVS_HIP(c, hipGetLastError());
         }
     }
-    if (!s.after_set && !s.excl_set && (rc = zero_after_lo(c))) return rc;  // (under lists without cursors it holds zeros already)
+    if (!s.after_set && !s.excl.set && (rc = zero_after_lo(c))) return rc;  // (under lists without cursors it holds zeros already)
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     s.rset_set = true;
-    return HVS_OK;
-}
-int leaf_query_sets_remove(hvs_ctx* c)
-{
-    HVS_HIP(c, hipSetDevice(c->device));
-    if (int rc = resolve_overflow(c)) return rc;
-    c->qs.rset_set = false;
     return HVS_OK;
 }
 
@@ -3306,7 +3248,7 @@ int leaf_attach(hvs_ctx* c, PerQuery what, const PerQuerySource& src, uint32_t c
         if ((rc = resolve_overflow(c))) return rc;  // (for LastSlot: the last slots of re-run queries too)
         if (src.kind == PerQuerySource::Remove) {
             (caps ? s.caps_set : s.after_set) = false;
-            if (!caps && (s.excl_set || s.rset_set)) return zero_after_lo(c);  // (the list forms are cursor forms: they go on reading after_lo)
+            if (!caps && (s.excl.set || s.rset_set)) return zero_after_lo(c);  // (the list forms are cursor forms: they go on reading after_lo)
             return HVS_OK;
         }
         if (!caps && (rc = ensure_after(c, std::max(std::max(count, sets ? c->nq : 0u), 1u)))) return rc;  // (under sets: room for every sub-query)
@@ -3314,11 +3256,7 @@ int leaf_attach(hvs_ctx* c, PerQuery what, const PerQuerySource& src, uint32_t c
     if (count) {
         const HvsPerQuery& dst = sets ? s.in.user : s.eng;
         const dim3 grid(hvs_ceil_div(count, 256u)), sub_grid(hvs_ceil_div(c->nq, 256u));
-        auto copy = [&](void* to, const void* from, size_t bytes) -> int {
-            if (src.kind == PerQuerySource::Device) return copy_from_device(c, to, from, src.dev, bytes);
-            HVS_HIP(c, hipMemcpyAsync(to, from, bytes, hipMemcpyHostToDevice, c->stream));
-            return HVS_OK;
-        };
+        auto copy = [&](void* to, const void* from, size_t bytes) { return copy_in(c, to, from, src.kind == PerQuerySource::Device ? src.dev : -1, bytes); };
         if (caps) {
             if ((rc = copy(dst.d_max_d2, src.f, (size_t)count * sizeof(float)))) return rc;
             hipLaunchKernelGGL(hvs_k_norm_caps, grid, dim3(256), 0, c->stream, dst.d_max_d2, count);
@@ -3384,11 +3322,7 @@ int leaf_set_queries_from_rows(hvs_ctx* c, const uint32_t* ids, uint32_t first_i
     if (rc) return rc;
     if (nq) {
         if (ids) {
-            if (nq > s.mask_ids_cap) {
-                s.mask_ids_cap = 0;
-                if ((rc = dev_alloc(c, &s.d_mask_ids, (size_t)nq))) return rc;
-                s.mask_ids_cap = nq;
-            }
+            if ((rc = ensure_room(c, &s.d_mask_ids, s.mask_ids_cap, nq))) return rc;
             HVS_HIP(c, hipMemcpyAsync(s.d_mask_ids, ids, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         }
         hipLaunchKernelGGL(hvs_k_queries_from_rows, dim3(hvs_ceil_div(nq, 4u * HVS_ROWQ_WAVE_ROWS)), dim3(256), 0, c->stream,
@@ -3532,7 +3466,7 @@ struct InPlan {
     uint32_t v0 = 0, lo = 0;          // lo: the slice's first offset
     uint64_t sub_if_all_c = 0;        // the sub-queries there would be if every query tested C (what the limit is taken over)
     double plan_ms = 0.0;             // device time of the count and scan kernels
-    // extra vectors (kind == Vectors): the slice's offsets are staged and checked in HvsInSet::d_v_off (vec_stage); `vecs` = the
+    // extra vectors (kind == Vectors): the slice's offsets are staged and checked in HvsInSet::v_stage (vec_stage); `vecs` = the
     // first vector of the slice, nsub - nuq of them, in host memory (vec_dev < 0) or on GPU vec_dev.  The fill kernel writes
     // sub_off and parent from the staged offsets: nothing of size nsub is built on the host.
     // Extra clauses (kind == Clauses) likewise; `attrs` = the slice's first clause, 4 floats each, where `vecs` is; vecs ==
@@ -3598,17 +3532,8 @@ int in_plan_device(hvs_ctx* c, const uint32_t* d_off, const float* d_vals, int s
         P->d_vals = d_vals;
         P->v0 = 0u;
     } else {
-        if (!S.d_p_off || nuq > S.p_off_cap) {
-            S.p_off_cap = 0;
-            if ((rc = dev_alloc(c, &S.d_p_off, (size_t)nuq + 1u))) return rc;
-            S.p_off_cap = nuq;
-        }
-        if (hi - lo > S.pv_cap) {
-            S.pv_cap = 0;
-            if ((rc = dev_alloc(c, &S.d_p_vals, (size_t)(hi - lo)))) return rc;
-            S.pv_cap = hi - lo;
-        }
-        if ((rc = copy_from_device(c, S.d_p_off, d_off, src_dev, ((size_t)nuq + 1u) * sizeof(uint32_t))) ||
+        if ((rc = ensure_room(c, &S.d_p_off, S.p_off_cap, (size_t)nuq + 1u)) || (rc = ensure_room(c, &S.d_p_vals, S.pv_cap, hi - lo)) ||
+            (rc = copy_from_device(c, S.d_p_off, d_off, src_dev, ((size_t)nuq + 1u) * sizeof(uint32_t))) ||
             (rc = copy_from_device(c, S.d_p_vals, d_vals ? d_vals + lo : nullptr, src_dev, d_vals ? (size_t)(hi - lo) * sizeof(float) : 0u)))
             return rc;
         P->d_off = S.d_p_off;
@@ -3685,44 +3610,20 @@ int in_commit(hvs_ctx* c, InPlan& P)
         else c->nq = 0;
         return code;
     };
-    if (nsub > S.sub_cap) {
-        S.sub_cap = 0;
-        if ((rc = dev_alloc(c, &S.d_parent, (size_t)nsub)) || (rc = dev_alloc(c, &S.d_value, (size_t)nsub))) return lost(rc);
-        S.sub_cap = nsub;
-    }
+    if ((rc = ensure_room(c, &S.d_parent, S.sub_cap, nsub, &S.d_value))) return lost(rc);
     if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
     const bool clauses = P.kind == HvsInSet::Clauses;
     const bool vectors = P.kind == HvsInSet::Vectors || clauses;  // (the CSR clients: staged offsets, the fill kernel plans)
     const char* const what = clauses ? "hvs_set_query_clauses" : vectors ? "hvs_set_query_vectors" : "hvs_set_category_sets";
     if (clauses) {
         const size_t ncl = (size_t)nsub - nuq;
-        if (ncl > S.attrs_cap) {
-            S.attrs_cap = 0;
-            if ((rc = dev_alloc(c, &S.d_attrs, ncl * 4u))) return lost(rc);
-            S.attrs_cap = ncl;
-        }
-        if (ncl) {
-            if (P.vec_dev >= 0)
-                rc = copy_from_device(c, S.d_attrs, P.attrs, P.vec_dev, ncl * 4u * sizeof(float));
-            else if (hipMemcpyAsync(S.d_attrs, P.attrs, ncl * 4u * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                rc = fail(c, HVS_EHIP, "hvs_set_query_clauses: upload of the clauses failed");
-            if (rc) return lost(rc);
-        }
+        if ((rc = ensure_room(c, &S.d_attrs, S.attrs_cap, ncl * 4u)) || (rc = copy_in(c, S.d_attrs, P.attrs, P.vec_dev, ncl * 4u * sizeof(float))))
+            return lost(rc);
     }
     if (vectors && (!clauses || P.vecs)) {
         const size_t nvec = (size_t)nsub - nuq;
-        if (nvec > S.vecs_cap) {
-            S.vecs_cap = 0;
-            if ((rc = dev_alloc(c, &S.d_vecs, nvec * HVS_NDIM))) return lost(rc);
-            S.vecs_cap = nvec;
-        }
-        if (nvec) {
-            if (P.vec_dev >= 0)
-                rc = copy_from_device(c, S.d_vecs, P.vecs, P.vec_dev, nvec * HVS_NDIM * sizeof(float));
-            else if (hipMemcpyAsync(S.d_vecs, P.vecs, nvec * HVS_NDIM * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                rc = fail(c, HVS_EHIP, std::string(what) + ": upload of the vectors failed");
-            if (rc) return lost(rc);
-        }
+        if ((rc = ensure_room(c, &S.d_vecs, S.vecs_cap, nvec * HVS_NDIM)) || (rc = copy_in(c, S.d_vecs, P.vecs, P.vec_dev, nvec * HVS_NDIM * sizeof(float))))
+            return lost(rc);
     }
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
     if (vectors) {
@@ -3737,7 +3638,7 @@ int in_commit(hvs_ctx* c, InPlan& P)
         return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
     (void)hipEventRecord(S.ev_x0, c->stream);
     if (clauses) {
-        hipLaunchKernelGGL(hvs_k_fill_clauses, dim3(hvs_ceil_div(nuq + 1u, 4u)), dim3(256), 0, c->stream, S.d_v_off, nuq, S.d_sub_off, S.d_parent);
+        hipLaunchKernelGGL(hvs_k_fill_clauses, dim3(hvs_ceil_div(nuq + 1u, 4u)), dim3(256), 0, c->stream, S.v_stage.d_words, nuq, S.d_sub_off, S.d_parent);
         if (nsub) {
             const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
             hipLaunchKernelGGL(hvs_k_expand_clauses, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
@@ -3745,7 +3646,7 @@ int in_commit(hvs_ctx* c, InPlan& P)
                                P.vecs ? reinterpret_cast<const float4*>(S.d_vecs) : nullptr, nsub, reinterpret_cast<float4*>(c->d_q));
         }
     } else if (vectors) {
-        hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(nuq + 1u, 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, S.d_sub_off, S.d_parent);
+        hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(nuq + 1u, 256u)), dim3(256), 0, c->stream, S.v_stage.d_words, nuq, S.d_sub_off, S.d_parent);
         if (nsub) {
             const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
             hipLaunchKernelGGL(hvs_k_expand_vectors, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
@@ -3800,47 +3701,30 @@ uint32_t vec_check_core(const uint32_t* off, uint32_t nq, uint32_t max_extra = H
 }
 
 // The plan of one GPU's slice of the CSR, first half: the slice's offsets -- `nuq` + 1 entries from host memory (src_dev < 0) or
-// from GPU src_dev -- are staged in d_v_off and checked there (hvs_k_check_vectors; `first`: the slice is the head of the
-// caller's array), and the host reads the status block back: v_flags / v_base / v_total.  Good offsets come back to the host
+// from GPU src_dev -- are staged in v_stage and checked there (leaf_stage, with an event pair around the check; `first`: the
+// slice is the head of the caller's array).  Good offsets come back to the host
 // too (4 bytes per query): sub_off[q] = off[q] - off[0] + q, and hvs_query_resident maps query ranges to sub-query ranges there.
 // Nothing that a query or a later call reads changes; the caller judges the flags of all GPUs before any commit.
-// `kind`: Vectors, or Clauses -- the same staging with the clauses' limit (hvs_k_check_clauses).
+// `kind`: Vectors, or Clauses -- the same staging with the clauses' limit.
 int vec_stage(hvs_ctx* c, HvsInSet::Kind kind, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
 {
     HvsInSet& S = c->qs.in;
-    int rc = in_begin(c);
-    if (rc) return rc;
-    if (!S.d_v_off || nuq > S.v_off_cap) {
-        S.v_off_cap = 0;
-        if ((rc = dev_alloc(c, &S.d_v_off, (size_t)nuq + 1u))) return rc;
-        S.v_off_cap = nuq;
-    }
-    if (!S.d_v_status && (rc = dev_alloc(c, &S.d_v_status, (size_t)4))) return rc;
     const size_t bytes = ((size_t)nuq + 1u) * sizeof(uint32_t);
-    if (src_dev < 0)
-        HVS_HIP(c, hipMemcpyAsync(S.d_v_off, off, bytes, hipMemcpyHostToDevice, c->stream));
-    else if ((rc = copy_from_device(c, S.d_v_off, off, src_dev, bytes)))
-        return rc;
-    HVS_HIP(c, hipMemsetAsync(S.d_v_status, 0, 4 * sizeof(uint32_t), c->stream));
-    HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
-    if (kind == HvsInSet::Clauses)
-        hipLaunchKernelGGL(hvs_k_check_clauses, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
-    else
-        hipLaunchKernelGGL(hvs_k_check_vectors, dim3(hvs_ceil_div(std::max(nuq, 1u), 256u)), dim3(256), 0, c->stream, S.d_v_off, nuq, first ? 1 : 0, S.d_v_status);
-    HVS_HIP(c, hipGetLastError());
-    HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
-    uint32_t h[4] = {0, 0, 0, 0};
-    HVS_HIP(c, hipMemcpyAsync(h, S.d_v_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    S.v_flags = h[0], S.v_base = h[1], S.v_total = h[2];
+    int rc = leaf_stage(c, S.v_stage, true, off, src_dev, nuq + 1u, [&](const HvsStage& st) {
+        HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
+        if (int rc2 = check_offsets(c, st, nuq, first, kind == HvsInSet::Clauses ? HVS_CLAUSE_MAX_EXTRA_ : HVS_VEC_MAX_EXTRA_)) return rc2;
+        HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
+        return HVS_OK;
+    });
+    if (rc) return rc;
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
     P->kind = kind;
     P->nuq = nuq;
     P->plan_ms = ms;
-    if (S.v_flags) return HVS_OK;
+    if (S.v_stage.flags) return HVS_OK;
     std::vector<uint32_t> o((size_t)nuq + 1u);
-    HVS_HIP(c, hipMemcpy(o.data(), S.d_v_off, bytes, hipMemcpyDeviceToHost));
+    HVS_HIP(c, hipMemcpy(o.data(), S.v_stage.d_words, bytes, hipMemcpyDeviceToHost));
     P->sub_off.resize((size_t)nuq + 1u);
     P->eff.resize(nuq);
     for (uint32_t q = 0; q <= nuq; ++q) P->sub_off[q] = o[q] - o[0] + q;
@@ -3860,11 +3744,7 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     HVS_HIP(c, hipSetDevice(c->device));
     int rc;
     if (nq == 0u) return run_queries(c, S.h_sub_off[q0], 0u, sample_proportion, NoHook{});  // (nothing to merge)
-    if (S.m_cap < (size_t)S.nuq * c->k) {
-        S.m_cap = 0;
-        if ((rc = dev_alloc(c, &S.d_m_ids, (size_t)S.nuq * c->k)) || (rc = dev_alloc(c, &S.d_m_dists, (size_t)S.nuq * c->k))) return rc;
-        S.m_cap = (size_t)S.nuq * c->k;
-    }
+    if ((rc = ensure_room(c, &S.d_m_ids, S.m_cap, (size_t)S.nuq * c->k, &S.d_m_dists))) return rc;
     const uint32_t s0 = S.h_sub_off[q0], s1 = S.h_sub_off[q0 + nq];
     {
         struct PaddingOff {  // a per-call override: the sub-queries' lists are partial answers
@@ -4252,11 +4132,7 @@ int leaf_apply_mask(hvs_ctx* c, const std::vector<uint64_t>& words, uint32_t n_l
     for (size_t i = 0; i < words.size(); ++i) revived = revived || (words[i] & ~s.h_live[i]) != 0ull;
     if (del_ids) {
         if (fresh) HVS_HIP(c, hipMemcpyAsync(s.d_live, s.h_live.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        if (del_count > s.mask_ids_cap) {
-            s.mask_ids_cap = 0;
-            if ((rc = dev_alloc(c, &s.d_mask_ids, (size_t)del_count))) return rc;
-            s.mask_ids_cap = del_count;
-        }
+        if ((rc = ensure_room(c, &s.d_mask_ids, s.mask_ids_cap, del_count))) return rc;
         HVS_HIP(c, hipMemcpyAsync(s.d_mask_ids, del_ids, (size_t)del_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(hvs_k_mask_delete, dim3(hvs_ceil_div(del_count, 256u)), dim3(256), 0, c->stream, s.d_mask_ids, del_count, s.d_live);
         HVS_HIP(c, hipGetLastError());
@@ -4430,12 +4306,7 @@ int leaf_update_prepare(hvs_ctx* c, uint32_t count, uint32_t n_stale_new)
         c->rs.stale_cap = want;
     }
     const size_t words2 = 4u * mask_words(c->n_indexed);  // two planes
-    if (words2 > c->rs.ilive_cap) {  // (only while no row is stale: n_indexed does not change while one is)
-        c->rs.ilive_cap = 0;
-        if ((rc = dev_alloc(c, &c->rs.d_ilive, words2))) return rc;
-        c->rs.ilive_cap = (uint32_t)words2;
-    }
-    return HVS_OK;
+    return ensure_room(c, &c->rs.d_ilive, c->rs.ilive_cap, words2);  // (only while no row is stale: n_indexed does not change while one is)
 }
 
 // second half: the rows (one staged H2D + hvs_k_scatter_rows), the stale list and what follows from it (index-validity mask,
@@ -4751,58 +4622,81 @@ int attach_everywhere(hvs_ctx* c, PerQuery what, const float* f, const uint32_t*
         return leaf_attach(k, what, caller_values(f ? f + first : f, u ? u + first : u, src_dev), m, row0);
     });
 }
-// hvs_query_after / hvs_query_within: the call's caps and cursors (host memory, `nq` each; nullptr: none) onto the queries just installed
-// The caller's exclusion lists (CSR: `nq` + 1 offsets, the ids; host memory, src_dev < 0, or device memory of GPU src_dev) to
-// every leaf, or, both nullptr, off every leaf.  A replicated context cuts the CSR by the owner ranges -- a leaf takes its
-// queries' offsets and the ids between them; a row-partitioned one gives every part all of it and the part's row window (the
-// last part's is open-ended: an id behind the rows of today names a row that an append may bring).  `first`: `off` is the head
-// of the caller's array (a leaf of a replicated hvs_query_excluding gets a slice that the root has checked).  Every leaf's
-// offsets are checked before any leaf's lists are replaced: HVS_EINVAL leaves every GPU as it was.
-// `cand`: the lists are candidate lists, which take the same road with their own check, limit and commit.
-int exclude_everywhere(hvs_ctx* c, const uint32_t* off, const uint32_t* ids, int src_dev, uint32_t nq, bool first, const char* fn, bool cand = false)
+// ---- the staged attach, root side ----
+// A leaf's share of a per-query array or CSR of `nq` queries: its queries [q0, q0 + m) and its row window.  A replicated context
+// cuts by the owner ranges; a row-partitioned one gives every part all of it and the part's rows (the last part's window is
+// open-ended: an id behind the rows of today names a row that an append may bring).
+struct Share {
+    hvs_ctx* k;
+    uint32_t q0, m, row0, n_rows;
+};
+std::vector<Share> shares_of(hvs_ctx* c, uint32_t nq)
 {
-    if (!off) return on_every_leaf(c, cand ? leaf_candidates_remove : leaf_exclude_remove);
-    struct Share {
-        hvs_ctx* k;
-        uint32_t q0, m, row0, n_rows;
-    };
     std::vector<Share> sh;
-    if (c->kids.empty())
-        sh.push_back({c, 0u, nq, 0u, 0xFFFFFFFFu});
-    else {
-        const uint32_t N = (uint32_t)c->kids.size();
-        const bool cut = c->kid_q0.size() == N + 1u;
-        for (uint32_t r = 0; r < N; ++r) {
-            if (c->partitioned) {
-                const uint32_t row0 = c->part_row0.size() > r + 1u ? c->part_row0[r] : 0u;
-                sh.push_back({c->kids[r], 0u, nq, row0, r + 1u == N ? 0xFFFFFFFFu - row0 : c->part_row0[r + 1] - row0});
-            } else
-                sh.push_back({c->kids[r], cut ? c->kid_q0[r] : 0u, cut ? c->kid_q0[r + 1] - c->kid_q0[r] : 0u, 0u, 0xFFFFFFFFu});
-        }
+    if (c->kids.empty()) sh.push_back({c, 0u, nq, 0u, 0xFFFFFFFFu});
+    const uint32_t N = (uint32_t)c->kids.size();
+    const bool cut = c->kid_q0.size() == N + 1u;
+    for (uint32_t r = 0; r < N; ++r) {
+        if (c->partitioned) {
+            const uint32_t row0 = c->part_row0.size() > r + 1u ? c->part_row0[r] : 0u;
+            sh.push_back({c->kids[r], 0u, nq, row0, r + 1u == N ? 0xFFFFFFFFu - row0 : c->part_row0[r + 1] - row0});
+        } else
+            sh.push_back({c->kids[r], cut ? c->kid_q0[r] : 0u, cut ? c->kid_q0[r + 1] - c->kid_q0[r] : 0u, 0u, 0xFFFFFFFFu});
     }
-    auto each = [&](auto f) -> int {
-        if (c->kids.empty()) return f(sh[0]);
-        return for_each_leaf(c, [&](uint32_t r) { return f(sh[r]); });
-    };
-    int rc = each([&](const Share& s) { return leaf_exclude_stage(s.k, off + s.q0, src_dev, s.m, first && s.q0 == 0u, cand); });
-    if (rc) return rc;
+    return sh;
+}
+template <typename F>  // f(share, its index) on every share, one host thread per GPU
+int on_shares(hvs_ctx* c, const std::vector<Share>& sh, F f)
+{
+    if (c->kids.empty()) return f(sh[0], (size_t)0);
+    return for_each_leaf(c, [&](uint32_t r) { return f(sh[r], (size_t)r); });
+}
+// Every share is staged (`stage(share, index)`: a leaf_stage into the area `area` names) and the root judges all GPUs' flags
+// before any GPU commits: HVS_EINVAL, with the text `why` has for the first flag set, leaves every GPU as it was.
+struct Refusal {
+    const char *bad_first, *bad_order, *bad_long;
+};
+template <typename Stage>
+int stage_and_judge(hvs_ctx* c, const std::vector<Share>& sh, const HvsStage& (*area)(const hvs_ctx*), const char* fn, const Refusal& why, Stage stage)
+{
+    if (int rc = on_shares(c, sh, stage)) {
+        (void)hipGetLastError();  // (HIP's last error is the failed call's: the next call must not trip over it)
+        return rc;
+    }
     uint32_t flags = 0;
-    for (const Share& s : sh) flags |= s.k->qs.st_flags;
-    if (flags)
-        return fail(c, HVS_EINVAL,
-                    std::string(fn) + (flags & HVS_EXCL_BAD_FIRST   ? (cand ? ": cand_offsets[0] is not 0" : ": excl_offsets[0] is not 0")
-                                       : flags & HVS_EXCL_BAD_ORDER ? (cand ? ": cand_offsets are not ascending" : ": excl_offsets are not ascending")
-                                       : cand                       ? ": a list has more than HVS_CANDIDATES_MAX entries"
-                                                                    : ": a list has more than HVS_EXCLUDE_MAX entries"));
+    for (const Share& s : sh) flags |= area(s.k).flags;
+    if (!flags) return HVS_OK;
+    return fail(c, HVS_EINVAL, std::string(fn) + (flags & HVS_OFF_BAD_FIRST ? why.bad_first : flags & HVS_OFF_BAD_ORDER ? why.bad_order : why.bad_long));
+}
+const HvsStage& off_stage_of(const hvs_ctx* k) { return k->qs.off_stage; }
+const HvsStage& idx_stage_of(const hvs_ctx* k) { return k->qs.idx_stage; }
+const HvsStage& v_stage_of(const hvs_ctx* k) { return k->qs.in.v_stage; }
+// ... and every share commits; a failed commit (a copy or an allocation: some GPUs may hold the new values and some the old)
+// leaves the attachment in force on none
+template <typename Commit>
+int commit_or_detach(hvs_ctx* c, const std::vector<Share>& sh, int attachment, Commit commit)
+{
+    const int rc = on_shares(c, sh, commit);
+    if (rc)
+        for (const Share& s : sh) s.k->qs.attached(attachment) = false;
+    return rc;
+}
+
+// The caller's id lists of kind K (CSR: `nq` + 1 offsets, the ids; host memory, src_dev < 0, or device memory of GPU src_dev) to
+// every leaf, or, `off` nullptr, off every leaf.  `first`: `off` is the head of the caller's array (a leaf of a replicated
+// hvs_query_excluding gets a slice that the root has checked).
+int lists_everywhere(hvs_ctx* c, const ListKind& K, const uint32_t* off, const uint32_t* ids, int src_dev, uint32_t nq, bool first, const char* fn)
+{
+    if (!off) return on_every_leaf(c, [&](hvs_ctx* k) { return leaf_detach_flag(k, K.flag); });
+    const std::vector<Share> sh = shares_of(c, nq);
+    const std::string name = std::string(": ") + K.offsets, not_zero = name + "[0] is not 0", not_ascending = name + " are not ascending";
+    int rc = stage_and_judge(c, sh, off_stage_of, fn, Refusal{not_zero.c_str(), not_ascending.c_str(), K.too_long},
+                             [&](const Share& s, size_t) { return leaf_lists_stage(s.k, K, off + s.q0, src_dev, s.m, first && s.q0 == 0u); });
+    if (rc) return rc;
     if (!ids)
         for (const Share& s : sh)
-            if (s.k->qs.st_total) return fail(c, HVS_EINVAL, std::string(fn) + ": the id array is NULL and the offsets name entries");
-    rc = each([&](const Share& s) {
-        return cand ? leaf_candidates_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows) : leaf_exclude_commit(s.k, ids, src_dev, s.m, s.row0, s.n_rows);
-    });
-    if (rc)  // (a copy or an allocation failed: some GPUs may hold the new lists and some the old -- none is in force)
-        for (const Share& s : sh) (cand ? s.k->qs.cand_set : s.k->qs.excl_set) = false;
-    return rc;
+            if (s.k->qs.off_stage.total()) return fail(c, HVS_EINVAL, std::string(fn) + ": the id array is NULL and the offsets name entries");
+    return commit_or_detach(c, sh, K.flag, [&](const Share& s, size_t) { return leaf_lists_commit(s.k, K, ids, src_dev, s.m, s.row0, s.n_rows); });
 }
 // hvs_query_after / hvs_query_within / hvs_query_excluding: the call's caps, cursors and lists (host memory, `nq` each, the lists
 // as a CSR whose offsets the caller has checked; nullptr: none) onto the queries just installed
@@ -4811,7 +4705,7 @@ int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const
 {
     int rc = max_d2 ? attach_everywhere(c, PerQuery::Caps, max_d2, nullptr, -1, nq) : HVS_OK;
     if (!rc && after_d) rc = attach_everywhere(c, PerQuery::Cursors, after_d, after_i, -1, nq);
-    if (!rc && ex_off) rc = exclude_everywhere(c, ex_off, ex_ids, -1, nq, false, "hvs_query_excluding");
+    if (!rc && ex_off) rc = lists_everywhere(c, kExcludeLists, ex_off, ex_ids, -1, nq, false, "hvs_query_excluding");
     return rc;
 }
 
@@ -4824,38 +4718,26 @@ int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int s
                        HvsInSet::Kind kind = HvsInSet::Vectors, const float* attrs = nullptr)
 {
     const bool clauses = kind == HvsInSet::Clauses;
-    const size_t N = std::max<size_t>(c->kids.size(), 1u);
-    std::vector<InPlan> plans(N);
-    auto slot = [&](const hvs_ctx* k) { return c->kids.empty() ? (size_t)0 : (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin()); };
-    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return vec_stage(k, kind, off + first, src_dev, m, first == 0u, &plans[slot(k)]); });
-    if (rc) {
-        (void)hipGetLastError();
-        return rc;
-    }
-    uint32_t flags = 0;
+    const std::vector<Share> sh = shares_of(c, nq);
+    std::vector<InPlan> plans(sh.size());
+    static const Refusal kVec{": vec_offsets[0] is not 0", ": vec_offsets are not ascending", ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"};
+    static const Refusal kClause{": clause_offsets[0] is not 0", ": clause_offsets are not ascending", ": a query has more than HVS_CLAUSES_MAX_EXTRA extra clauses"};
+    int rc = stage_and_judge(c, sh, v_stage_of, fn, clauses ? kClause : kVec, [&](const Share& s, size_t r) {
+        return vec_stage(s.k, kind, off + s.q0, src_dev, s.m, s.q0 == 0u, &plans[r]);
+    });
+    if (rc) return rc;
     uint64_t total = 0;
-    auto judge = [&](const hvs_ctx* k) {
-        flags |= k->qs.in.v_flags;
-        total = std::max<uint64_t>(total, k->qs.in.v_total);  // (ascending offsets: the last slice's end)
-    };
-    if (c->kids.empty()) judge(c);
-    for (const hvs_ctx* k : c->kids) judge(k);
-    if (flags)
-        return fail(c, HVS_EINVAL,
-                    std::string(fn) + (flags & HVS_VEC_BAD_FIRST   ? (clauses ? ": clause_offsets[0] is not 0" : ": vec_offsets[0] is not 0")
-                                       : flags & HVS_VEC_BAD_ORDER ? (clauses ? ": clause_offsets are not ascending" : ": vec_offsets are not ascending")
-                                       : clauses                   ? ": a query has more than HVS_CLAUSES_MAX_EXTRA extra clauses"
-                                                                   : ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"));
+    for (const Share& s : sh) total = std::max<uint64_t>(total, v_stage_of(s.k).end);  // (ascending offsets: the last slice's end)
     if (total + nq >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": too many sub-queries");
     if (total && clauses && !attrs) return fail(c, HVS_EINVAL, std::string(fn) + ": clause_attrs is NULL");
     if (total && !clauses && !vecs) return fail(c, HVS_EINVAL, std::string(fn) + ": vecs is NULL");
-    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t, uint32_t) {
-        InPlan& P = plans[slot(k)];
+    rc = on_shares(c, sh, [&](const Share& s, size_t r) {
+        InPlan& P = plans[r];
         // (clauses without a single extra have no clause vectors whatever the pointer: every row has one key, cursors stay allowed)
-        P.vecs = vecs && !(clauses && total == 0u) ? vecs + (size_t)k->qs.in.v_base * HVS_NDIM : nullptr;
-        P.attrs = attrs ? attrs + (size_t)k->qs.in.v_base * 4u : nullptr;
+        P.vecs = vecs && !(clauses && total == 0u) ? vecs + (size_t)v_stage_of(s.k).first * HVS_NDIM : nullptr;
+        P.attrs = attrs ? attrs + (size_t)v_stage_of(s.k).first * 4u : nullptr;
         P.vec_dev = src_dev;
-        return in_commit(k, P);
+        return in_commit(s.k, P);
     });
     if (rc && !c->kids.empty()) {
         const std::string err = c->err;
@@ -4948,17 +4830,8 @@ int part_ensure_buffers(hvs_ctx* root, uint32_t r, uint32_t own)
     HvsPart& P = k->part;
     const size_t need_m = (size_t)own * root->k, need_gx = need_m * (root->kids.size() - 1u);
     int rc;
-    if (need_m > P.m_cap) {
-        P.m_cap = 0;
-        if ((rc = dev_alloc(k, &P.d_m_ids, need_m)) || (rc = dev_alloc(k, &P.d_m_dists, need_m))) return rc;
-        P.m_cap = need_m;
-    }
-    if (need_gx > P.gx_cap) {
-        P.gx_cap = 0;
-        if ((rc = dev_alloc(k, &P.d_gx_ids, need_gx)) || (rc = dev_alloc(k, &P.d_gx_dists, need_gx))) return rc;
-        P.gx_cap = need_gx;
-    }
-    return HVS_OK;
+    if ((rc = ensure_room(k, &P.d_m_ids, P.m_cap, need_m, &P.d_m_dists))) return rc;
+    return ensure_room(k, &P.d_gx_ids, P.gx_cap, need_gx, &P.d_gx_dists);
 }
 
 // the plan of a data set of n rows in the root's books (no call has run on it yet)
@@ -4995,9 +4868,9 @@ int part_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
     c->part_timing_valid = false;
     c->qs.call_capped = capped(c->kids[0]);  // (every part holds all the caps, or none does)
     c->qs.call_after = has_after(c->kids[0]);  // (likewise the cursors)
-    c->qs.call_excl = has_excl(c->kids[0]);    // (and the lists)
+    c->qs.excl.call = has_excl(c->kids[0]);    // (and the lists)
     c->qs.call_rset = has_rset(c->kids[0]);    // (and the set indices)
-    c->qs.call_cand = has_cand(c->kids[0]);
+    c->qs.cand.call = has_cand(c->kids[0]);
     if (nq == 0u) return HVS_OK;
     uint32_t local_sn[16];
     if (hvs_partition_plan(c->part_n, N, K, sample_proportion, nullptr, nullptr, local_sn)) return fail(c, HVS_EINVAL, "partition plan");
@@ -5236,8 +5109,8 @@ int leaf_after_stats(hvs_ctx* c, hvs_after_info* out)
 int leaf_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
 {
     unsigned long long v[3] = {0, 0, 0}, sink[1] = {0};
-    int rc = leaf_call_counters(c, out, c->qs.call_excl, HVS_CNT_EXCL_SLOTS, v);
-    if (rc || !c->qs.call_excl) return rc;
+    int rc = leaf_call_counters(c, out, c->qs.excl.call, HVS_CNT_EXCL_SLOTS, v);
+    if (rc || !c->qs.excl.call) return rc;
     if ((rc = call_counters(c, HVS_CNT_RERUN_SINK_EXCL_REFUSED, sink))) return rc;  // (the exact engine's re-runs count through the sink)
     out->excluding_queries = c->call.timing.nq;
     out->kept_slots = v[0];
@@ -5249,8 +5122,8 @@ int leaf_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
 int leaf_candidates_stats(hvs_ctx* c, hvs_candidates_info* out)
 {
     unsigned long long v[2] = {0, 0}, t[2] = {0, 0};
-    int rc = leaf_call_counters(c, out, c->qs.call_cand, HVS_CNT_CAND_SLOTS, v);
-    if (rc || !c->qs.call_cand) return rc;
+    int rc = leaf_call_counters(c, out, c->qs.cand.call, HVS_CNT_CAND_SLOTS, v);
+    if (rc || !c->qs.cand.call) return rc;
     if ((rc = call_counters(c, HVS_CNT_PAIRS, t))) return rc;
     out->listed_queries = c->call.timing.nq;
     out->kept_slots = v[0];
@@ -6182,25 +6055,31 @@ uint32_t hvs_exclude_plan(const uint32_t* offsets, const uint32_t* ids, uint32_t
     return id_lists_plan(HVS_EXCLUDE_MAX, offsets, ids, nq, row0, n_rows, begin, count, out_ids);
 }
 
+// A caller's per-query arrays come from host memory or, through a *_device entry point, from device memory with the stream that
+// produced them.
+struct CallerSource {
+    const char* fn;
+    bool device;
+    void* stream;
+};
+// one body per host / _device pair: the checks in their order, then the kind's road to every GPU
+static int set_exclude_ids(hvs_ctx* c, const CallerSource& from, const char* null_text, const uint32_t* off, const uint32_t* ids, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, from.fn)) return HVS_ESTATE;
+    if (!off && !ids) return lists_everywhere(c, kExcludeLists, nullptr, nullptr, -1, 0u, true, from.fn);
+    if (!off || !ids) return fail(c, HVS_EINVAL, std::string(from.fn) + null_text);
+    int dev = -1, rc = check_resident_count(c, nq, from.fn);
+    if (!rc && from.device) rc = check_device_buffers(c, off, ids, from.stream, from.fn, &dev);
+    return rc ? rc : lists_everywhere(c, kExcludeLists, off, ids, dev, nq, true, from.fn);
+}
 int hvs_set_exclude_ids(hvs_ctx* c, const uint32_t* excl_offsets, const uint32_t* excl_ids, uint32_t nq)
 {
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, "hvs_set_exclude_ids")) return HVS_ESTATE;
-    if (!excl_offsets && !excl_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, "hvs_set_exclude_ids");
-    if (!excl_offsets || !excl_ids) return fail(c, HVS_EINVAL, "hvs_set_exclude_ids: one of excl_offsets / excl_ids is NULL");
-    if (int rc = check_resident_count(c, nq, "hvs_set_exclude_ids")) return rc;
-    return exclude_everywhere(c, excl_offsets, excl_ids, -1, nq, true, "hvs_set_exclude_ids");
+    return set_exclude_ids(c, {"hvs_set_exclude_ids", false, nullptr}, ": one of excl_offsets / excl_ids is NULL", excl_offsets, excl_ids, nq);
 }
-
 int hvs_set_exclude_ids_device(hvs_ctx* c, const uint32_t* d_offsets, const uint32_t* d_ids, uint32_t nq, void* stream)
 {
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, "hvs_set_exclude_ids_device")) return HVS_ESTATE;
-    if (!d_offsets && !d_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, "hvs_set_exclude_ids_device");
-    if (!d_offsets || !d_ids) return fail(c, HVS_EINVAL, "hvs_set_exclude_ids_device: one of d_offsets / d_ids is NULL");
-    int dev = 0, rc = check_resident_count(c, nq, "hvs_set_exclude_ids_device");
-    if (!rc) rc = check_device_buffers(c, d_offsets, d_ids, stream, "hvs_set_exclude_ids_device", &dev);
-    return rc ? rc : exclude_everywhere(c, d_offsets, d_ids, dev, nq, true, "hvs_set_exclude_ids_device");
+    return set_exclude_ids(c, {"hvs_set_exclude_ids_device", true, stream}, ": one of d_offsets / d_ids is NULL", d_offsets, d_ids, nq);
 }
 
 int hvs_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
@@ -6215,27 +6094,32 @@ int hvs_exclude_stats(hvs_ctx* c, hvs_exclude_info* out)
         },
         [&](hvs_exclude_info& sum) {
             // the rules of hvs_within_stats: slots and refused keys summed over the parts, the queries the call's, under-full from the merge
-            sum.excluding_queries = c->qs.call_excl ? c->part_call_nq : 0u;
-            sum.underfull_queries = c->qs.call_excl ? c->pinfo.padded_queries : 0u;
+            sum.excluding_queries = c->qs.excl.call ? c->part_call_nq : 0u;
+            sum.underfull_queries = c->qs.excl.call ? c->pinfo.padded_queries : 0u;
         });
 }
 
-int hvs_download_exclude_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
+// the lists in force as the device holds them: begin, count (nq each) and, where `cap` has room, the ids; returns their number
+static int download_lists_plan(hvs_ctx* c, const ListKind& K, const char* fn, const char* what, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
 {
     if (!c) return HVS_EINVAL;
-    if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_exclude_plan: single-GPU contexts only");
+    if (!c->kids.empty()) return fail(c, HVS_EINVAL, std::string(fn) + ": single-GPU contexts only");
     const HvsQuerySet& s = c->qs;
-    if (!s.excl_set) return fail(c, HVS_ESTATE, "hvs_download_exclude_plan: no exclusion lists are attached");
-    const HvsPerQuery& v = s.in.active ? s.in.user : s.eng;
+    const HvsIdLists& L = s.*K.lists;
+    if (!L.set) return fail(c, HVS_ESTATE, std::string(fn) + ": no " + what + " lists are attached");
+    const HvsListIndex& at = !K.cursor_forms ? s.cand_at : s.in.active ? s.in.user.ex : s.eng.ex;
     HVS_HIP(c, hipSetDevice(c->device));
-    if (s.ex_nq) {
-        if (begin) HVS_HIP(c, hipMemcpyAsync(begin, v.d_ex_begin, (size_t)s.ex_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (count) HVS_HIP(c, hipMemcpyAsync(count, v.d_ex_count, (size_t)s.ex_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (L.nq) {
+        if (begin) HVS_HIP(c, hipMemcpyAsync(begin, at.d_begin, (size_t)L.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (count) HVS_HIP(c, hipMemcpyAsync(count, at.d_count, (size_t)L.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
-    if (ids && cap >= s.ex_total && s.ex_total)
-        HVS_HIP(c, hipMemcpyAsync(ids, s.d_ex_ids, (size_t)s.ex_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (ids && cap >= L.total && L.total) HVS_HIP(c, hipMemcpyAsync(ids, L.d_ids, (size_t)L.total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
-    return (int)s.ex_total;
+    return (int)L.total;
+}
+int hvs_download_exclude_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
+{
+    return download_lists_plan(c, kExcludeLists, "hvs_download_exclude_plan", "exclusion", begin, count, ids, cap);
 }
 
 // ---- per-query candidate lists (include/hvs.h "per-query candidate lists") -------
@@ -6251,31 +6135,25 @@ uint32_t hvs_candidates_plan(const uint32_t* offsets, const uint32_t* ids, uint3
 // the expanded resident set (category sets, query vectors, clauses) is attached, on every GPU or on none
 static bool expanded_set_attached(const hvs_ctx* c) { return (c->kids.empty() ? c : c->kids[0])->qs.in.active; }
 
+static int set_candidate_ids(hvs_ctx* c, const CallerSource& from, const char* null_text, const uint32_t* off, const uint32_t* ids, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, from.fn)) return HVS_ESTATE;
+    if (!off && !ids) return lists_everywhere(c, kCandidateLists, nullptr, nullptr, -1, 0u, true, from.fn);
+    if (expanded_set_attached(c))
+        return fail(c, HVS_ESTATE, std::string(from.fn) + ": candidate lists do not compose (yet) with category sets, query vectors or clauses");
+    if (!off) return fail(c, HVS_EINVAL, std::string(from.fn) + null_text);
+    int dev = -1, rc = check_resident_count(c, nq, from.fn);
+    if (!rc && from.device) rc = check_device_buffers(c, off, ids, from.stream, from.fn, &dev);
+    return rc ? rc : lists_everywhere(c, kCandidateLists, off, ids, dev, nq, true, from.fn);
+}
 int hvs_set_candidate_ids(hvs_ctx* c, const uint32_t* cand_offsets, const uint32_t* cand_ids, uint32_t nq)
 {
-    static const char* const fn = "hvs_set_candidate_ids";
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!cand_offsets && !cand_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, fn, true);
-    if (expanded_set_attached(c))
-        return fail(c, HVS_ESTATE, std::string(fn) + ": candidate lists do not compose (yet) with category sets, query vectors or clauses");
-    if (!cand_offsets) return fail(c, HVS_EINVAL, std::string(fn) + ": cand_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    return exclude_everywhere(c, cand_offsets, cand_ids, -1, nq, true, fn, true);
+    return set_candidate_ids(c, {"hvs_set_candidate_ids", false, nullptr}, ": cand_offsets is NULL", cand_offsets, cand_ids, nq);
 }
-
 int hvs_set_candidate_ids_device(hvs_ctx* c, const uint32_t* d_offsets, const uint32_t* d_ids, uint32_t nq, void* stream)
 {
-    static const char* const fn = "hvs_set_candidate_ids_device";
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!d_offsets && !d_ids) return exclude_everywhere(c, nullptr, nullptr, -1, 0u, true, fn, true);
-    if (expanded_set_attached(c))
-        return fail(c, HVS_ESTATE, std::string(fn) + ": candidate lists do not compose (yet) with category sets, query vectors or clauses");
-    if (!d_offsets) return fail(c, HVS_EINVAL, std::string(fn) + ": d_offsets is NULL");
-    int dev = 0, rc = check_resident_count(c, nq, fn);
-    if (!rc) rc = check_device_buffers(c, d_offsets, d_ids, stream, fn, &dev);
-    return rc ? rc : exclude_everywhere(c, d_offsets, d_ids, dev, nq, true, fn, true);
+    return set_candidate_ids(c, {"hvs_set_candidate_ids_device", true, stream}, ": d_offsets is NULL", d_offsets, d_ids, nq);
 }
 
 int hvs_query_among(hvs_ctx* c, const float* q_rows, const uint32_t* cand_offsets, const uint32_t* cand_ids, const float* max_d2, uint32_t nq,
@@ -6312,26 +6190,14 @@ int hvs_candidates_stats(hvs_ctx* c, hvs_candidates_info* out)
         },
         [&](hvs_candidates_info& sum) {
             // the rules of hvs_exclude_stats: ids and slots summed over the parts, the queries the call's, under-full from the merge
-            sum.listed_queries = c->qs.call_cand ? c->part_call_nq : 0u;
-            sum.underfull_queries = c->qs.call_cand ? c->pinfo.padded_queries : 0u;
+            sum.listed_queries = c->qs.cand.call ? c->part_call_nq : 0u;
+            sum.underfull_queries = c->qs.cand.call ? c->pinfo.padded_queries : 0u;
         });
 }
 
 int hvs_download_candidates_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
 {
-    if (!c) return HVS_EINVAL;
-    if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_candidates_plan: single-GPU contexts only");
-    const HvsQuerySet& s = c->qs;
-    if (!s.cand_set) return fail(c, HVS_ESTATE, "hvs_download_candidates_plan: no candidate lists are attached");
-    HVS_HIP(c, hipSetDevice(c->device));
-    if (s.cd_nq) {
-        if (begin) HVS_HIP(c, hipMemcpyAsync(begin, s.d_cd_begin, (size_t)s.cd_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (count) HVS_HIP(c, hipMemcpyAsync(count, s.d_cd_count, (size_t)s.cd_nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (ids && cap >= s.cd_total && s.cd_total)
-        HVS_HIP(c, hipMemcpyAsync(ids, s.d_cd_ids, (size_t)s.cd_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HVS_HIP(c, hipStreamSynchronize(c->stream));
-    return (int)s.cd_total;
+    return download_lists_plan(c, kCandidateLists, "hvs_download_candidates_plan", "candidate", begin, count, ids, cap);
 }
 
 // ---- shared row sets (include/hvs.h "shared row sets") ---------------------------
@@ -6435,41 +6301,31 @@ int hvs_get_row_sets(hvs_ctx* c, uint64_t* bits)
 // checked before any GPU's indices are replaced: HVS_EINVAL leaves every GPU as it was.
 static int query_sets_everywhere(hvs_ctx* c, const uint32_t* idx, int src_dev, uint32_t nq, const char* fn)
 {
-    if (!idx) return on_every_leaf(c, leaf_query_sets_remove);
-    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return leaf_query_sets_stage(k, idx + first, src_dev, m); });
-    if (rc) return rc;
-    uint32_t flags = c->kids.empty() ? c->qs.st_rs_flags : 0u;
-    for (const hvs_ctx* k : c->kids) flags |= k->qs.st_rs_flags;
-    if (flags) return fail(c, HVS_EINVAL, std::string(fn) + ": a set index is neither below n_sets nor 0xFFFFFFFF");
-    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t m, uint32_t) { return leaf_query_sets_commit(k, m); });
-    if (rc) {  // (an allocation failed: some GPUs may hold the new indices and some the old -- none is in force)
-        c->qs.rset_set = false;
-        for (hvs_ctx* k : c->kids) k->qs.rset_set = false;
-    }
-    return rc;
+    if (!idx) return on_every_leaf(c, [](hvs_ctx* k) { return leaf_detach_flag(k, HvsQuerySet::kRowSetsOn); });
+    const std::vector<Share> sh = shares_of(c, nq);
+    static const char* const bad = ": a set index is neither below n_sets nor 0xFFFFFFFF";
+    int rc = stage_and_judge(c, sh, idx_stage_of, fn, Refusal{bad, bad, bad},
+                             [&](const Share& s, size_t) { return leaf_query_sets_stage(s.k, idx + s.q0, src_dev, s.m); });
+    return rc ? rc : commit_or_detach(c, sh, HvsQuerySet::kRowSetsOn, [&](const Share& s, size_t) { return leaf_query_sets_commit(s.k, s.m); });
 }
 
+static int set_query_row_sets(hvs_ctx* c, const CallerSource& from, const uint32_t* idx, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    if (!loaded_leaf(c, from.fn)) return HVS_ESTATE;
+    if (!idx) return query_sets_everywhere(c, nullptr, -1, 0u, from.fn);
+    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(from.fn) + ": no row sets are loaded (hvs_set_row_sets)");
+    int dev = -1, rc = check_resident_count(c, nq, from.fn);
+    if (!rc && from.device) rc = check_device_buffers(c, idx, nullptr, from.stream, from.fn, &dev);
+    return rc ? rc : query_sets_everywhere(c, idx, dev, nq, from.fn);
+}
 int hvs_set_query_row_sets(hvs_ctx* c, const uint32_t* set_of_query, uint32_t nq)
 {
-    static const char* const fn = "hvs_set_query_row_sets";
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!set_of_query) return query_sets_everywhere(c, nullptr, -1, 0u, fn);
-    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    return query_sets_everywhere(c, set_of_query, -1, nq, fn);
+    return set_query_row_sets(c, {"hvs_set_query_row_sets", false, nullptr}, set_of_query, nq);
 }
-
 int hvs_set_query_row_sets_device(hvs_ctx* c, const uint32_t* d_set_of_query, uint32_t nq, void* stream)
 {
-    static const char* const fn = "hvs_set_query_row_sets_device";
-    if (!c) return HVS_EINVAL;
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!d_set_of_query) return query_sets_everywhere(c, nullptr, -1, 0u, fn);
-    if (!sets_loaded(c)) return fail(c, HVS_ESTATE, std::string(fn) + ": no row sets are loaded (hvs_set_row_sets)");
-    int dev = 0, rc = check_resident_count(c, nq, fn);
-    if (!rc) rc = check_device_buffers(c, d_set_of_query, nullptr, stream, fn, &dev);
-    return rc ? rc : query_sets_everywhere(c, d_set_of_query, dev, nq, fn);
+    return set_query_row_sets(c, {"hvs_set_query_row_sets_device", true, stream}, d_set_of_query, nq);
 }
 
 int hvs_query_in_row_sets(hvs_ctx* c, const float* q_rows, const uint32_t* set_of_query, uint32_t nq, float sample_proportion, uint32_t* out_ids,

@@ -195,7 +195,7 @@ __global__ void hvs_k_after_from_results(const uint32_t* __restrict__ out_ids, c
 // ---------------------------------------------------------------------------------------------
 // Per-query exclusion lists (hvs_set_exclude_ids / hvs_query_excluding): a set of row ids per resident query; a
 // row takes part in the query's answer only if its id is not in the set.  The caller's CSR is put on the device as it is
-// (hvs_k_check_exclude looks at the offsets, the host reads the status block back and refuses before anything changes), then
+// (hvs_k_check_offsets looks at the offsets, the host reads the status block back and refuses before anything changes), then
 // hvs_k_norm_exclude sorts every list and drops what cannot name a row, IN PLACE: the normalised list of query q lies at
 // ids[begin[q] .. begin[q] + count[q]), ascending and without duplicates, begin[q] = offsets[q] - offsets[0].  hvs_exclude_norm_row
 // is the arithmetic of one list on the host (hvs_exclude_plan), which the kernel reproduces bit for bit.
@@ -206,9 +206,9 @@ __global__ void hvs_k_after_from_results(const uint32_t* __restrict__ out_ids, c
 // row's id: nothing is indexed with it.
 // ---------------------------------------------------------------------------------------------
 #define HVS_EXCLUDE_MAX_ 1024u  // (= HVS_EXCLUDE_MAX of include/hvs.h; hvs.hip asserts it)
-#define HVS_EXCL_BAD_FIRST 1u   // status flags: offsets[0] != 0
-#define HVS_EXCL_BAD_ORDER 2u   // ... a descending pair of offsets
-#define HVS_EXCL_BAD_LONG 4u    // ... a list of more than HVS_EXCLUDE_MAX entries
+#define HVS_OFF_BAD_FIRST 1u    // status flags of hvs_k_check_offsets: offsets[0] != 0
+#define HVS_OFF_BAD_ORDER 2u    // ... a descending pair of offsets
+#define HVS_OFF_BAD_LONG 4u     // ... a list longer than the kind's limit
 struct HvsExcl {
     const uint32_t* __restrict__ begin;  // per resident query (under category sets: per sub-query, its parent's pair)
     const uint32_t* __restrict__ count;
@@ -236,23 +236,24 @@ __host__ __device__ __forceinline__ bool hvs_exclude_keeps(uint32_t id, uint32_t
 {
     return id != 0xFFFFFFFFu && id >= row0 && (uint64_t)id < (uint64_t)row0 + n_rows;
 }
-// status[0] |= flags, status[1] = offsets[0], status[2] = offsets[nq] (to be trusted only if no flag is set).  `first`: the
-// offsets are the head of the caller's array (a slice further in starts anywhere).
-__global__ void hvs_k_check_exclude(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
+// The one check of a caller's CSR offsets, whatever they delimit (exclusion and candidate lists, extra vectors, extra clauses):
+// status[0] |= HVS_OFF_BAD_*, status[1] = offsets[0], status[2] = offsets[nq] (to be trusted only if no flag is set).  `first`:
+// the offsets are the head of the caller's array (a slice further in starts anywhere); `limit`: the longest list allowed.
+__global__ void hvs_k_check_offsets(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t limit, uint32_t* __restrict__ status)
 {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t flags = 0u;
     if (q == 0u) {
-        if (first && off[0] != 0u) flags |= HVS_EXCL_BAD_FIRST;
+        if (first && off[0] != 0u) flags |= HVS_OFF_BAD_FIRST;
         status[1] = off[0];
         status[2] = off[nq];
     }
     if (q < nq) {
         const uint32_t a = off[q], b = off[q + 1u];
         if (b < a)
-            flags |= HVS_EXCL_BAD_ORDER;
-        else if (b - a > HVS_EXCLUDE_MAX_)
-            flags |= HVS_EXCL_BAD_LONG;
+            flags |= HVS_OFF_BAD_ORDER;
+        else if (b - a > limit)
+            flags |= HVS_OFF_BAD_LONG;
     }
     if (flags) atomicOr(&status[0], flags);
 }
@@ -1389,30 +1390,6 @@ __global__ __launch_bounds__(256) void hvs_k_in_fill(const float* __restrict__ Q
 // The plan needs no scan: sub_off[q] = off[q] + q, and sub-query j of parent p reads extra vector j - p - 1 (j > sub_off[p]).
 // ---------------------------------------------------------------------------------------------
 #define HVS_VEC_MAX_EXTRA_ 63u  // (= HVS_VECTORS_MAX_EXTRA of include/hvs.h; hvs.hip asserts it)
-#define HVS_VEC_BAD_FIRST 1u    // status flags: offsets[0] != 0
-#define HVS_VEC_BAD_ORDER 2u    // ... a descending pair of offsets
-#define HVS_VEC_BAD_LONG 4u     // ... more than HVS_VECTORS_MAX_EXTRA extras on one query
-
-// status[0] |= flags, status[1] = offsets[0], status[2] = offsets[nq] (to be trusted only if no flag is set).  `first`: the
-// offsets are the head of the caller's array (a slice further in starts anywhere).  After hvs_k_check_exclude.
-__global__ void hvs_k_check_vectors(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
-{
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t flags = 0u;
-    if (q == 0u) {
-        if (first && off[0] != 0u) flags |= HVS_VEC_BAD_FIRST;
-        status[1] = off[0];
-        status[2] = off[nq];
-    }
-    if (q < nq) {
-        const uint32_t a = off[q], b = off[q + 1u];
-        if (b < a)
-            flags |= HVS_VEC_BAD_ORDER;
-        else if (b - a > HVS_VEC_MAX_EXTRA_)
-            flags |= HVS_VEC_BAD_LONG;
-    }
-    if (flags) atomicOr(&status[0], flags);
-}
 
 // The plan of checked offsets (one GPU's slice, off[0] = lo): sub_off[q] = off[q] - lo + q, parent = q for the query's
 // 1 + m(q) <= 64 sub-queries.  One thread per user query (thread nq writes the last offset).
@@ -1607,26 +1584,6 @@ __global__ __launch_bounds__(256) void hvs_k_merge_vectors(const uint32_t* __res
 // ---------------------------------------------------------------------------------------------
 #define HVS_CLAUSE_MAX_EXTRA_ 255u  // (= HVS_CLAUSES_MAX_EXTRA of include/hvs.h; hvs.hip asserts it)
 
-// hvs_k_check_vectors with the clauses' limit: the same status block and the same flags (HVS_VEC_BAD_*).
-__global__ void hvs_k_check_clauses(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
-{
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t flags = 0u;
-    if (q == 0u) {
-        if (first && off[0] != 0u) flags |= HVS_VEC_BAD_FIRST;
-        status[1] = off[0];
-        status[2] = off[nq];
-    }
-    if (q < nq) {
-        const uint32_t a = off[q], b = off[q + 1u];
-        if (b < a)
-            flags |= HVS_VEC_BAD_ORDER;
-        else if (b - a > HVS_CLAUSE_MAX_EXTRA_)
-            flags |= HVS_VEC_BAD_LONG;
-    }
-    if (flags) atomicOr(&status[0], flags);
-}
-
 // The plan of checked offsets (one GPU's slice, off[0] = lo): sub_off[q] = off[q] - lo + q, parent = q for the query's
 // 1 + m(q) <= 256 sub-queries.  One WAVE per user query (four per workgroup; wave nq writes the last offset): a thread per query,
 // as hvs_k_fill_vectors has it, would write up to 256 scattered words; a thread per sub-query would have to search sub_off, which
@@ -1795,31 +1752,13 @@ __global__ __launch_bounds__(256) void hvs_k_merge_clauses(const uint32_t* __res
 // ---------------------------------------------------------------------------------------------
 // Per-query candidate lists (hvs_set_candidate_ids / hvs_query_among): a set of row ids per resident query; a row
 // takes part in the query's answer only if its id IS in the set.  The mirror image of the exclusion lists above, and attached
-// the same way: the caller's CSR is put on the device as it is, hvs_k_check_candidates looks at the offsets, the host reads the
+// the same way: the caller's CSR is put on the device as it is, hvs_k_check_offsets looks at the offsets, the host reads the
 // status block back and refuses before anything changes, then hvs_k_norm_candidates normalises every list IN PLACE by the rule
 // of hvs_k_norm_exclude (hvs_exclude_keeps for the part's window, minus row0, ascending, no duplicates, the rest of the raw
-// extent 0xFFFFFFFF) -- what hvs_candidates_plan does on the host, bit for bit.  The status flags are HVS_EXCL_BAD_*.
+// extent 0xFFFFFFFF) -- what hvs_candidates_plan does on the host, bit for bit.
 // No engine answers such a query: the lists are short against D, so hvs_k_scan_candidates gathers the listed rows by id.
 // ---------------------------------------------------------------------------------------------
 #define HVS_CANDIDATES_MAX_ 8192u  // (= HVS_CANDIDATES_MAX of include/hvs.h; hvs.hip asserts it)
-__global__ void hvs_k_check_candidates(const uint32_t* __restrict__ off, uint32_t nq, int first, uint32_t* __restrict__ status)
-{
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t flags = 0u;
-    if (q == 0u) {
-        if (first && off[0] != 0u) flags |= HVS_EXCL_BAD_FIRST;
-        status[1] = off[0];
-        status[2] = off[nq];
-    }
-    if (q < nq) {
-        const uint32_t a = off[q], b = off[q + 1u];
-        if (b < a)
-            flags |= HVS_EXCL_BAD_ORDER;
-        else if (b - a > HVS_CANDIDATES_MAX_)
-            flags |= HVS_EXCL_BAD_LONG;
-    }
-    if (flags) atomicOr(&status[0], flags);
-}
 // One workgroup per query, the list in LDS (32 KB): a bitonic network over the next power of two >= 256, every thread of the
 // block on the same list (so the barriers are uniform); the first wave then keeps the first of every run of equal ids by a
 // ballot compaction and writes them back over the raw list.  The offsets were checked: len <= 8192.

@@ -1,6 +1,8 @@
 """What is attached to the resident queries, as a pure function (DESIGN 3.13a "Resident-query state"): the transition table
 of the host's HvsQuerySet restated over four facts -- category sets, distance caps, result cursors, and whether every resident
 query has a result row at the current k -- and a fifth beside them: whether the last call's figures can still be asked for.
+Three more facts take the staged attach (exclusion lists, candidate lists, per-query indices of the shared row sets), and the
+shared row sets themselves stand beside them: they are the data set's, not the queries'.
 tests/test_queryset_model_cpu.py pins the table row by row; tests/test_queryset_walk.py walks one GPU context through it and
 compares every answer with a fresh context given only what the model says is attached.
 
@@ -14,6 +16,13 @@ A call is a tuple:
     ("after_from_results",)    hvs_set_after_from_results (padding off)
     ("set_k", k)               hvs_set_k
     ("run", q0, nq)            hvs_query_resident
+    ("exclude", tag | None)    hvs_set_exclude_ids (None: remove)
+    ("bad_exclude",)           ... with offsets the library refuses (HVS_EINVAL)
+    ("candidates", tag | None) hvs_set_candidate_ids; HVS_ESTATE while category sets are attached
+    ("bad_candidates",)        ... with offsets the library refuses
+    ("row_sets", tag | None)   hvs_set_row_sets: the shared sets loaded, replaced or (None) removed
+    ("query_sets", tag | None) hvs_set_query_row_sets; HVS_ESTATE while no shared sets are loaded
+    ("bad_query_sets",)        ... with an index that names no set
 
 `step` returns the next state and the call's status: OK, EINVAL or ESTATE.  A refused call leaves the state as it was.
 
@@ -22,6 +31,10 @@ Three cells of the table that are easy to get wrong, read from the code:
   - caps and cursors survive hvs_set_k, the results do not;
   - attaching or removing caps or cursors leaves the result range alone (the rows are still those of the earlier call), so
     hvs_set_after_from_results may follow them.
+The lists' rows: a replaced resident set and category sets attached or detached drop all three kinds; replacing the shared sets
+drops the indices (they named the old sets) and the results, and nothing else; lists and indices leave the result range alone, as
+caps do; removing cursors under lists or indices leaves them in force; the state is checked before the values are, so a call
+that is both out of place and malformed is HVS_ESTATE.
 The result range is one interval: a call's range joins it when the two touch and replaces it otherwise.  (A multi-GPU context
 keeps one interval per GPU, in that GPU's own query numbers: the walks stay clear of sequences where that shows.  The library
 tells a k that changed by comparing the range's k with the current one, so k -> k' -> k without a call in between would find
@@ -34,7 +47,8 @@ FROM_RESULTS = "from results"   # cursors: the last slot of each query's current
 # queries: tag of the resident rows; nq: their number; sets / caps / cursors: tag of what is attached (None: nothing);
 # k: slots per result row; res: the answered interval (lo, hi) at this k, or None
 # timed: the last call's figures (hvs_last_timing, hvs_within_stats, ...) can be asked for
-State = namedtuple("State", "queries nq sets caps cursors k res timed", defaults=[True])
+# excl / cand / qsets: tag of the exclusion lists, candidate lists, set indices attached; rsets: tag of the shared row sets loaded
+State = namedtuple("State", "queries nq sets caps cursors k res timed excl cand qsets rsets", defaults=[True, None, None, None, None])
 
 
 def initial(k=100):
@@ -58,12 +72,12 @@ def step(s, call, nq_of=None):
     op = call[0]
     if op in ("upload", "query"):
         n = nq_of[call[1]] if nq_of else s.nq
-        s = s._replace(queries=call[1], nq=n, sets=None, caps=None, cursors=None, res=None)
+        s = s._replace(queries=call[1], nq=n, sets=None, caps=None, cursors=None, res=None, excl=None, cand=None, qsets=None)
         return (_answered(s, 0, n) if op == "query" else s), OK
     if op == "sets":
         if call[1] is None and s.sets is None:
             return s, OK
-        return s._replace(sets=call[1], caps=None, cursors=None, res=None, timed=False), OK
+        return s._replace(sets=call[1], caps=None, cursors=None, res=None, timed=False, excl=None, cand=None, qsets=None), OK
     if op == "bad_sets":
         return s, EINVAL
     if op == "caps":
@@ -78,4 +92,22 @@ def step(s, call, nq_of=None):
         if call[1] + call[2] > s.nq:
             return s, EINVAL
         return _answered(s, call[1], call[2]), OK
+    if op == "exclude":
+        return s._replace(excl=call[1]), OK
+    if op == "bad_exclude":
+        return s, EINVAL
+    if op in ("candidates", "bad_candidates"):
+        if op == "candidates" and call[1] is None:
+            return s._replace(cand=None), OK
+        if s.sets is not None:
+            return s, ESTATE
+        return (s._replace(cand=call[1]), OK) if op == "candidates" else (s, EINVAL)
+    if op == "row_sets":
+        return s._replace(rsets=call[1], qsets=None, res=None), OK
+    if op in ("query_sets", "bad_query_sets"):
+        if op == "query_sets" and call[1] is None:
+            return s._replace(qsets=None), OK
+        if s.rsets is None:
+            return s, ESTATE
+        return (s._replace(qsets=call[1]), OK) if op == "query_sets" else (s, EINVAL)
     raise ValueError(f"unknown call {call!r}")

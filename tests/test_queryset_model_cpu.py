@@ -102,6 +102,69 @@ def test_row_cursors_from_results():
     assert M.step(go(PLAIN_FULL, ("caps", "C"), ("after", "A")), ("after_from_results",), NQ)[1] == M.OK
 
 
+LISTED = EVERYTHING._replace(excl="E", qsets="I", rsets="R")        # what composes with category sets
+AMONG = PLAIN_FULL._replace(caps="C", cursors="A", excl="E", cand="K", qsets="I", rsets="R")
+
+
+def lists(s):
+    return (s.excl, s.cand, s.qsets, s.rsets)
+
+
+@pytest.mark.parametrize("call", [("upload", "Q2"), ("query", "short")])
+def test_row_resident_set_replaced_drops_the_lists(call):
+    assert lists(go(AMONG, call)) == (None, None, None, "R")    # (the shared sets are the data set's: they stay)
+    assert lists(go(LISTED, call)) == (None, None, None, "R")
+
+
+def test_row_sets_changed_drops_the_lists():
+    for call in (("sets", "S2"), ("sets", None)):
+        assert lists(go(LISTED, call)) == (None, None, None, "R")
+    assert lists(go(AMONG, ("sets", "S"))) == (None, None, None, "R")
+    assert go(AMONG, ("sets", None)) == AMONG                    # (detaching nothing: a no-op for the lists too)
+
+
+@pytest.mark.parametrize("fact, call", [("excl", "exclude"), ("cand", "candidates"), ("qsets", "query_sets")])
+def test_rows_lists_touch_only_themselves(fact, call):
+    assert go(AMONG, (call, "X")) == AMONG._replace(**{fact: "X"})
+    assert go(AMONG, (call, None)) == AMONG._replace(**{fact: None})
+    assert M.full(go(AMONG, (call, "X")))                        # the result range is left alone, as by caps
+
+
+def test_row_candidates_do_not_compose_with_the_expanded_set():
+    assert M.step(LISTED, ("candidates", "K"), NQ) == (LISTED, M.ESTATE)
+    assert M.step(LISTED, ("bad_candidates",), NQ) == (LISTED, M.ESTATE)   # the state is asked before the offsets
+    assert go(LISTED, ("candidates", None)) == LISTED            # removing is always allowed
+    assert go(LISTED, ("exclude", "E2"), ("query_sets", "I2")) == LISTED._replace(excl="E2", qsets="I2")
+
+
+def test_row_shared_sets_replaced():
+    for call in (("row_sets", "R2"), ("row_sets", None)):
+        s = go(AMONG, call)
+        assert lists(s) == ("E", "K", None, call[1]) and s.res is None     # the indices named the old sets; the results go
+        assert (s.sets, s.caps, s.cursors, s.timed) == (None, "C", "A", True)
+    none = PLAIN_FULL
+    assert M.step(none, ("query_sets", "I"), NQ) == (none, M.ESTATE)
+    assert M.step(none, ("bad_query_sets",), NQ) == (none, M.ESTATE)
+    assert go(none, ("query_sets", None)) == none
+
+
+def test_row_removing_cursors_leaves_the_lists():
+    assert go(AMONG, ("after", None)) == AMONG._replace(cursors=None)
+    assert go(LISTED, ("after", None), ("caps", None)) == LISTED._replace(cursors=None, caps=None)
+
+
+def test_row_refused_lists_change_nothing():
+    for s in (AMONG, PLAIN_FULL._replace(rsets="R")):
+        for call in (("bad_exclude",), ("bad_candidates",), ("bad_query_sets",)):
+            assert M.step(s, call, NQ) == (s, M.EINVAL)
+    assert M.step(LISTED, ("bad_exclude",), NQ) == (LISTED, M.EINVAL)
+
+
+def test_row_k_changed_keeps_the_lists():
+    s = go(AMONG, ("set_k", 100))
+    assert lists(s) == lists(AMONG) and s.res is None
+
+
 def test_unknown_call():
     with pytest.raises(ValueError):
         M.step(M.initial(), ("nonsense",))

@@ -2,7 +2,8 @@
 cursors and the result range, attached, replaced and dropped in a fixed order.  tests/queryset_model.py says after every call
 what is attached; every answer of the walked context must be array_equal -- ids and distance bits -- to that of a FRESH
 single-GPU context given exactly that, the three per-call figures must be zero or non-zero as the model says, and
-hvs_set_after_from_results must succeed exactly when the model says every query has a result row.
+hvs_set_after_from_results must succeed exactly when the model says every query has a result row.  A second walk does the same
+for what takes the staged attach: exclusion lists, candidate lists, the shared row sets and the queries' indices into them.
 
 Data: in_sets.small(), 901 rows and 80 queries; padding off throughout (hvs_set_after_from_results needs it)."""
 import importlib
@@ -53,6 +54,39 @@ WITH_SETS = [
     ("bad_sets",), ("run", 30, 40), ("sets", None), ("run", 0, 80),
     ("query", "Q"), ("after_from_results",), ("run", 0, 80),
 ]
+# the second walk: the lists' rows of the table (tests/queryset_model.py), on one GPU ...
+LISTS = [
+    ("upload", "Q"), ("exclude", "E1"), ("run", 0, 80),
+    ("bad_exclude",), ("run", 0, 80),                                      # a refusal changes nothing
+    ("after_from_results",), ("run", 0, 80), ("after", None), ("run", 0, 80),   # cursors come and go over the lists
+    ("query_sets", "I1"), ("bad_query_sets",),                             # no shared sets yet: the state is asked first
+    ("row_sets", "R1"), ("after_from_results",), ("query_sets", "I1"), ("run", 0, 80),   # loading the sets drops the results
+    ("bad_query_sets",), ("exclude", None), ("run", 10, 60),               # indices alone
+    ("candidates", "K1"), ("caps", "C1"), ("run", 0, 80),
+    ("bad_candidates",), ("after_from_results",), ("run", 0, 80),
+    ("row_sets", "R2"), ("after_from_results",), ("run", 0, 80),           # the sets replaced: indices and results go, the lists stay
+    ("query_sets", "I1"), ("exclude", "E2"), ("candidates", "K2"), ("run", 0, 80),   # all three
+    ("set_k", 100), ("run", 0, 80),
+    ("sets", "S"), ("run", 0, 80),                                         # sets_changed drops all three
+    ("candidates", "K1"), ("bad_candidates",), ("candidates", None),       # ... and refuses candidate lists while attached
+    ("exclude", "E1"), ("query_sets", "I1"), ("caps", "C2"), ("run", 0, 80),   # under the expanded set: the user's, per sub-query
+    ("bad_exclude",), ("bad_query_sets",), ("after_from_results",), ("run", 0, 80),
+    ("sets", None), ("run", 0, 80),
+    ("exclude", "E2"), ("query_sets", "I1"), ("candidates", "K1"),
+    ("upload", "Q2"), ("run", 0, 80),                                      # a replaced resident set drops all three
+    ("query_sets", "I1"), ("run", 0, 80), ("row_sets", None), ("run", 0, 80),
+]
+# ... and in a short form on the two-leaf contexts (SHORT_LISTS_SETS: not for a row-partitioned one)
+SHORT_LISTS = [
+    ("upload", "Q"), ("exclude", "E1"), ("run", 0, 80), ("bad_exclude",), ("after_from_results",), ("run", 0, 80),
+    ("row_sets", "R1"), ("query_sets", "I1"), ("after", None), ("run", 0, 80),
+    ("candidates", "K1"), ("bad_candidates",), ("bad_query_sets",), ("run", 0, 80),
+    ("row_sets", "R2"), ("run", 0, 80), ("upload", "Q2"), ("run", 0, 80),
+]
+SHORT_LISTS_SETS = [
+    ("exclude", "E2"), ("sets", "S"), ("run", 0, 80), ("candidates", "K1"),
+    ("exclude", "E1"), ("query_sets", "I1"), ("run", 0, 80), ("sets", None), ("run", 0, 80),
+]
 
 
 def prepared(eng, engine, nodes, k):
@@ -77,9 +111,23 @@ def make_values():
         return c
 
     sets = S.sets_of(names)
+    # lists: ids of the plain answers (so that they bite; empty slots, 0xFFFFFFFF, go in as they are) and random rows
+    rng = np.random.default_rng(23)
+    n, nq = len(nodes), len(queries)
+    pick = lambda m: np.sort(rng.choice(n, m, replace=False)).astype(np.uint32)
+    off = np.arange(nq + 1, dtype=np.uint32) * 2
+    too_long, descending = off.copy(), off.copy()
+    too_long[-1] = too_long[-2] + PKG.EXCLUDE_MAX + 1
+    descending[40] = descending[39] - 1
     return {"nodes": nodes, "Q": queries, "Q2": np.ascontiguousarray(queries[::-1]), "S": sets, "S2": sets[3:] + sets[:3],
             "C1": caps(4), "C2": caps(6), "A1": (d[:, 2].copy(), ids[:, 2].copy()),
-            "bad": sets[:-1] + [list(range(65))]}
+            "bad": sets[:-1] + [list(range(65))],
+            "E1": [ids[q, :3] for q in range(nq)], "E2": [np.concatenate([ids[q, 1:6], pick(q % 7)]) for q in range(nq)],
+            "K1": [pick(150 + q) for q in range(nq)], "K2": [np.concatenate([pick(40), ids[q, :4]]) for q in range(nq)],
+            "R1": rng.random((3, n)) < 0.4, "R2": rng.random((2, n)) < 0.7,
+            "I1": np.array([(0, 1, 0xFFFFFFFF)[q % 3] for q in range(nq)], np.uint32),
+            "bad_E": (too_long, np.zeros(int(too_long[-1]), np.uint32)), "bad_K": (descending, np.zeros(2 * nq, np.uint32)),
+            "bad_I": np.array([0] * (nq - 1) + [3], np.uint32)}
 
 
 @pytest.fixture(scope="module")
@@ -97,8 +145,16 @@ def fresh_answer(engine, V, s, cursors, q0, nq):
     """queries [q0, q0 + nq) on a single-GPU context that has seen nothing but what the model says is attached"""
     with prepared(PKG.Engine(0), engine, V["nodes"], s.k) as f:
         f.upload_queries(V[s.queries])
+        if s.rsets is not None:
+            f.set_row_sets(V[s.rsets])
         if s.sets is not None:
             f.set_category_sets(V[s.sets])
+        if s.excl is not None:
+            f.set_exclude_ids(V[s.excl])
+        if s.cand is not None:
+            f.set_candidate_ids(V[s.cand])
+        if s.qsets is not None:
+            f.set_query_row_sets(V[s.qsets])
         if s.caps is not None:
             f.set_max_dist2(V[s.caps])
         if s.cursors is not None:
@@ -106,6 +162,10 @@ def fresh_answer(engine, V, s, cursors, q0, nq):
         f.query_resident(q0, nq, 1.0)
         f.sync()
         return f.download_results(q0, nq)
+
+
+ATTACH = {"exclude": "set_exclude_ids", "candidates": "set_candidate_ids", "row_sets": "set_row_sets", "query_sets": "set_query_row_sets"}
+REFUSED = {"bad_exclude": "bad_E", "bad_candidates": "bad_K", "bad_query_sets": "bad_I"}
 
 
 def code_of(fn):
@@ -144,6 +204,10 @@ def walk(e, engine, V, calls, s=None, check_timing=True, check_sets=True):
             assert (rc == M.OK) == M.full(s), f"{what}: hvs_set_after_from_results returned {rc}"
         elif op == "set_k":
             rc = code_of(lambda: e.set_k(call[1]))
+        elif op in ATTACH:
+            rc = code_of(lambda: getattr(e, ATTACH[op])(None if call[1] is None else V[call[1]]))
+        elif op in REFUSED:
+            rc = code_of(lambda: getattr(e, ATTACH[op[4:]])(V[REFUSED[op]]))
         elif op == "run":
             q0, nq = call[1], call[2]
             rc = code_of(lambda: e.query_resident(q0, nq, 1.0))
@@ -166,6 +230,9 @@ def walk(e, engine, V, calls, s=None, check_timing=True, check_sets=True):
             if check_sets:
                 n = e.in_stats()
                 assert (n.sub_queries != 0) == (s.sets is not None), f"{what}: {n.as_dict()}"
+            x, k = e.exclude_stats(), e.candidates_stats()
+            assert (x.excluding_queries != 0) == (s.excl is not None), f"{what}: {x.as_dict()}"
+            assert (k.listed_queries != 0) == (s.cand is not None), f"{what}: {k.as_dict()}"
         if check_timing:
             assert (code_of(e.within_stats) == M.OK) == s.timed, what
     return s
@@ -176,6 +243,13 @@ def test_walk(values, engine):
     with prepared(PKG.Engine(0), engine, values["nodes"], 8) as e:
         s = walk(e, engine, values, WALK)
     assert (s.k, s.queries) == (100, "Q")
+
+
+@pytest.mark.parametrize("engine", [EXACT, AUTO])
+def test_walk_lists(values, engine):
+    with prepared(PKG.Engine(0), engine, values["nodes"], 8) as e:
+        s = walk(e, engine, values, LISTS)
+    assert (s.k, s.queries, s.rsets) == (100, "Q2", None)
 
 
 def need_two_gpus():
@@ -194,3 +268,14 @@ def test_walk_partitioned_in_two_parts(values):
     need_two_gpus()
     with prepared(PKG.Engine(devices=TWO_GPUS, partition=True), AUTO, values["nodes"], 8) as e:
         walk(e, AUTO, values, SHORT, check_timing=False, check_sets=False)
+
+
+@pytest.mark.parametrize("devices", [[0, 0], TWO_GPUS], ids=["two leaves on GPU 0", "two GPUs"])
+@pytest.mark.parametrize("partition", [False, True], ids=["replicated", "partitioned"])
+def test_walk_lists_on_two_leaves(values, partition, devices):
+    if max(devices) >= torch.cuda.device_count():
+        pytest.skip("needs two GPUs")
+    with prepared(PKG.Engine(devices=devices, partition=partition), AUTO, values["nodes"], 8) as e:
+        s = walk(e, AUTO, values, SHORT_LISTS, check_timing=False, check_sets=not partition)
+        if not partition:
+            walk(e, AUTO, values, SHORT_LISTS_SETS, s, check_timing=False)
