@@ -33,6 +33,7 @@ namespace {
 thread_local std::string g_global_err;
 int fail(hvs_ctx* c, int code, const std::string& msg);  // (defined below, with staging_copy: the state structs call them)
 void staging_copy(void* dst, const void* src, size_t bytes);
+struct ExpandedKind;  // (what tells the clients of the expanded resident set apart: below, with in_commit)
 #define HVS_HIP(ctx, call)                                                                                    \
     do {                                                                                                       \
         hipError_t e_ = (call);                                                                                \
@@ -278,7 +279,8 @@ struct HvsInSet {
     // kernels, the merge kernel and their stats.
     enum Kind { Sets, Vectors, Clauses };
     bool active = false;
-    Kind kind = Sets;                  // (while active) what the sub-queries of a user query are
+    const ExpandedKind* client = nullptr;  // (while active) what the sub-queries of a user query are
+    bool one_key_per_row = true;       // (while active) no row can come back under two keys: cursors may be attached
     uint32_t nuq = 0;
     std::vector<uint32_t> h_sub_off;   // nuq + 1
     std::vector<uint8_t> h_eff;        // nuq: the query is answered through its set (tests C, non-empty set)
@@ -292,16 +294,16 @@ struct HvsInSet {
     float* d_vecs = nullptr;
     size_t vecs_cap = 0;               // floats d_vecs has room for
     // extra clauses: staged and checked in v_stage as the vectors' offsets are; their [type, v, l, r], 4 floats each,
-    // and, where they bring vectors of their own (clause_vecs, while active), those in d_vecs
+    // and, where they bring vectors of their own, those in d_vecs
     float* d_attrs = nullptr;
     size_t attrs_cap = 0;              // floats d_attrs has room for
-    bool clause_vecs = false;
     HvsPerQuery user;                  // the user's caps and cursors: room for uq_cap each, allocated at attach
     uint32_t *d_m_ids = nullptr;       // merged answers, nuq x k
     float* d_m_dists = nullptr;
     size_t m_cap = 0;                  // entries
     // of the last merge: [0] under-full queries, [1] keys read, [2] (vectors, clauses) duplicates dropped, (clauses) [3] keys
-    // not below the threshold, [4] chunks never loaded
+    // not below the threshold, [4] chunks never loaded.  Every client's merge is given kStatWordsMin of them zeroed at least.
+    static constexpr uint32_t kStatWordsMin = 3u, kStatWordsMax = 5u;
     unsigned long long* d_stat = nullptr;
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;  // around the expansion / the last merge
     double expand_ms = 0.0;
@@ -314,7 +316,7 @@ struct HvsInSet {
     uint32_t p_cap = 0, p_off_cap = 0, pv_cap = 0;
     // last call
     bool call = false;                 // it ran on an expanded set ...
-    Kind call_kind = Sets;             // ... of this kind
+    const ExpandedKind* call_client = nullptr;  // ... of this client
     uint32_t call_set_queries = 0, call_sub = 0, call_max_set = 0;
     void free_device()
     {
@@ -369,7 +371,7 @@ struct HvsQuerySet {
     uint32_t res_lo = 0, res_hi = 0, res_k = 0;
     uint32_t set_gen = 0;      // counts the resident sets this GPU has held
     uint32_t res_gen = 0;      // set_gen of the set the range belongs to (a row-partitioned root: part 0's)
-    HvsInSet in;               // category sets of the resident queries
+    HvsInSet in;               // the expanded set of the resident queries and its client: sets, extra vectors or extra clauses
     // every flag that says "this is attached to the resident queries", in one place: what drops, lends out or clears attachments
     // goes through it (drop_attached, DetachedForProbe, leaf_detach_flag)
     enum Attachment { kCapsOn, kCursorsOn, kExclOn, kCandOn, kRowSetsOn, kAttachments };
@@ -695,7 +697,7 @@ HvsExcl excl_arg(const hvs_ctx* c)
 }
 // ... carry candidate lists: hvs_k_scan_candidates answers, whatever engine is selected (run_candidates)
 bool has_cand(const hvs_ctx* c) { return c->qs.cand.set; }
-// the resident set as the caller sees it (HvsInSet): under category sets the user's queries and the merged rows
+// the resident set as the caller sees it (HvsInSet): under an expanded set the user's queries and the merged rows
 uint32_t user_nq(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.nuq : c->nq; }
 const float* user_queries(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_uq : c->d_q; }
 const uint32_t* user_ids(const hvs_ctx* c) { return c->qs.in.active ? c->qs.in.d_m_ids : c->d_out_ids; }
@@ -723,9 +725,10 @@ void resident_set_replaced(hvs_ctx* c)
     c->qs.drop_attached();
     ++c->qs.set_gen;
 }
-// category sets attached (`on`), detached, or lost half-way through an attach: the engines' set changed under everything else
-// that was attached -- caps and cursors come after the sets, earlier results are dropped, the last call's figures with them
-void sets_changed(hvs_ctx* c, bool on)
+// the expanded set's client -- category sets, extra vectors or extra clauses -- attached (`on`), detached, or lost half-way
+// through an attach: the engines' set changed under everything else that was attached -- caps, cursors and lists come after
+// the client, earlier results are dropped, the last call's figures with them
+void expanded_changed(hvs_ctx* c, bool on)
 {
     c->qs.in.active = on;
     c->qs.drop_attached();
@@ -737,7 +740,7 @@ uint32_t k_changed(hvs_ctx* c)
 {
     const uint32_t had = c->res_cap;
     c->res_cap = 0;
-    c->qs.in.m_cap = 0;  // (the merged rows of category sets are re-allocated by the next call)
+    c->qs.in.m_cap = 0;  // (the merged rows of the expanded set, whichever client's, are re-allocated by the next call)
     call_forgotten(c);
     return had;
 }
@@ -3429,7 +3432,7 @@ int in_ensure_events(hvs_ctx* c)
     return HVS_OK;
 }
 
-// hvs_set_category_sets(NULL, NULL, 0) on one GPU: the resident set becomes the user's again (a no-op while no sets are attached)
+// The expanded set off one GPU, whichever client's it is: the resident set becomes the user's again (a no-op while none is attached)
 int in_detach(hvs_ctx* c)
 {
     HvsInSet& S = c->qs.in;
@@ -3439,42 +3442,78 @@ int in_detach(hvs_ctx* c)
     if (S.nuq) HVS_HIP(c, hipMemcpyAsync(c->d_q, S.d_uq, (size_t)S.nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HVS_HIP(c, hipStreamSynchronize(c->stream));
     c->nq = S.nuq;  // (nq_cap >= the sub-queries >= the user's queries)
-    sets_changed(c, false);
+    expanded_changed(c, false);
     return HVS_OK;
 }
-// ... of one client only: removing category sets leaves extra vectors alone, and the other way round
-int sets_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Sets ? HVS_OK : in_detach(c); }
-int vectors_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Vectors ? HVS_OK : in_detach(c); }
-int clauses_detach(hvs_ctx* c) { return c->qs.in.active && c->qs.in.kind != HvsInSet::Clauses ? HVS_OK : in_detach(c); }
+// ... of client K only: removing category sets leaves extra vectors alone, and the other way round
+int client_detach(hvs_ctx* c, const ExpandedKind& K) { return c->qs.in.active && c->qs.in.client != &K ? HVS_OK : in_detach(c); }
 
-// Attaching sets to one GPU's `nuq` user queries has two halves: a PLAN is made -- on the host from a host CSR (in_plan_host),
-// or by the plan kernels from a CSR in device memory (in_plan_device) --, which changes nothing a query or a later call reads,
-// and in_commit puts it in force.  sub_off and eff are on the host either way: hvs_query_resident maps query ranges to
-// sub-query ranges there.
+// Attaching a client to one GPU's `nuq` user queries has two halves: a PLAN is made, which changes nothing a query or a later
+// call reads, and in_commit puts it in force.  sub_off and eff are on the host whoever made the plan: hvs_query_resident maps
+// query ranges to sub-query ranges there.  The rest of a plan is one of three payloads, and each function below takes the one
+// it reads.
 static_assert(HVS_INP_MAX_VALUES == HVS_IN_MAX_VALUES && HVS_IN_MAX_VALUES <= 64, "the plan kernels keep one category per lane of a wave");
 struct InPlan {
     uint32_t nuq = 0, nsub = 0;
     std::vector<uint32_t> sub_off;  // nuq + 1: becomes HvsInSet::h_sub_off
     std::vector<uint8_t> eff;       // nuq: becomes HvsInSet::h_eff
-    // made on the host: the arrays the commit uploads
-    std::vector<uint32_t> set_off, parent;
-    std::vector<float> value;
-    // made on the device: sub_off is in HvsInSet::d_p_sub_off, eff in d_p_eff, and the fill kernel reads the CSR again
-    bool on_device = false;
-    const uint32_t* d_off = nullptr;  // this GPU's slice of the offsets, nuq + 1, in this GPU's memory
-    const float* d_vals = nullptr;    // the values the slice points into: entry i is d_vals[i - v0]
-    uint32_t v0 = 0, lo = 0;          // lo: the slice's first offset
-    uint64_t sub_if_all_c = 0;        // the sub-queries there would be if every query tested C (what the limit is taken over)
-    double plan_ms = 0.0;             // device time of the count and scan kernels
-    // extra vectors (kind == Vectors): the slice's offsets are staged and checked in HvsInSet::v_stage (vec_stage); `vecs` = the
-    // first vector of the slice, nsub - nuq of them, in host memory (vec_dev < 0) or on GPU vec_dev.  The fill kernel writes
-    // sub_off and parent from the staged offsets: nothing of size nsub is built on the host.
-    // Extra clauses (kind == Clauses) likewise; `attrs` = the slice's first clause, 4 floats each, where `vecs` is; vecs ==
-    // nullptr: predicate-only clauses.
-    HvsInSet::Kind kind = HvsInSet::Sets;
-    const float* vecs = nullptr;
-    const float* attrs = nullptr;
-    int vec_dev = -1;
+    double plan_ms = 0.0;           // device time of the plan: the count and scan kernels, or the check of staged offsets
+    // category sets planned on the host from a host CSR (in_plan_host): the arrays the commit uploads
+    struct Host {
+        std::vector<uint32_t> set_off, parent;
+        std::vector<float> value;
+    } host;
+    // category sets planned by the plan kernels from a CSR in device memory (in_plan_device; `made`): sub_off is in
+    // HvsInSet::d_p_sub_off, eff in d_p_eff, and the fill kernel reads the CSR again
+    struct Device {
+        bool made = false;
+        const uint32_t* d_off = nullptr;  // this GPU's slice of the offsets, nuq + 1, in this GPU's memory
+        const float* d_vals = nullptr;    // the values the slice points into: entry i is d_vals[i - v0]
+        uint32_t v0 = 0, lo = 0;          // lo: the slice's first offset
+        uint64_t sub_if_all_c = 0;        // the sub-queries there would be if every query tested C (what the limit is taken over)
+    } dev;
+    // extra vectors and extra clauses: the slice's offsets are staged and checked in HvsInSet::v_stage (csr_stage), and the fill
+    // kernel writes sub_off and parent from them: nothing of size nsub is built on the host.  `vecs` = the first vector of the
+    // slice, `attrs` = its first clause, 4 floats each: nsub - nuq of them, in host memory (src_dev < 0) or on GPU src_dev.
+    // Vectors have no attrs; vecs == nullptr: predicate-only clauses.
+    struct Staged {
+        const float* vecs = nullptr;
+        const float* attrs = nullptr;
+        int src_dev = -1;
+    } csr;
+};
+
+// What tells the three clients of the expanded set apart, and nothing else: category sets (3.13), extra query
+// vectors (3.15) and extra clauses (3.16).  The path they share -- in_begin, a plan, in_commit, in_run, the merge's figures,
+// client_detach -- reads one of the three instances below in_plan_release.
+struct Refusal {
+    const char *bad_first, *bad_order, *bad_long;
+};
+using MergeKernel = void (*)(const uint32_t*, uint32_t, uint32_t, const uint32_t*, const float*, const float*, uint32_t, const float*, int, const uint32_t*,
+                             uint32_t*, float*, uint32_t, unsigned long long*);
+struct ExpandedKind {
+    HvsInSet::Kind kind;
+    // the public names, as error texts have them: the setter and its offsets ([1]: of the _device form), the one-shot call and
+    // what it says of a CSR it refuses, the stats call
+    const char *set_fn[2], *offsets[2], *query_fn, *bad_query, *stats_fn;
+    // How the caller's CSR becomes a plan.  `staged`: its offsets are staged in HvsInSet::v_stage, checked there against `limit`
+    // extras per query and refused in the words of `why`, and its fill kernel plans (csr_stage, expanded_everywhere).  Not
+    // staged: planned from its values (in_plan_host, in_plan_device), and the next five do not apply.
+    bool staged;
+    uint32_t limit;
+    Refusal why;
+    const float* InPlan::Staged::*required;  // the array extras cannot do without ...
+    const char* required_null;               // ... and the refusal where it is missing
+    bool vecs_optional;                      // extras need not bring vectors
+    // in_commit's own two steps: what the client's kernels read reaches the device; its fill and expand launches
+    int (*payload)(hvs_ctx*, const InPlan&);
+    void (*expand)(hvs_ctx*, const InPlan&);
+    bool (*one_key_per_row)(const InPlan&);  // -> HvsInSet::one_key_per_row
+    // in_run's merge: the kernel for (summation order, list capacity); whether it pads from the user's rows or from the expanded
+    // ones; how many words of HvsInSet::d_stat it counts in
+    MergeKernel (*merge)(bool scalar_order, int cap);
+    bool merge_user_rows;
+    uint32_t stat_words;
 };
 
 // what both halves need first: an earlier call's re-runs resolved and the stream idle, the events, the merge's counters
@@ -3482,7 +3521,7 @@ int in_begin(hvs_ctx* c)
 {
     int rc = begin_mutation(c);
     if (!rc) rc = in_ensure_events(c);
-    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)5);
+    if (!rc && !c->qs.in.d_stat) rc = dev_alloc(c, &c->qs.in.d_stat, (size_t)HvsInSet::kStatWordsMax);
     return rc;
 }
 
@@ -3495,16 +3534,16 @@ int in_plan_host(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nu
     if (nuq)
         HVS_HIP(c, hipMemcpy2D(tv.data(), 2u * sizeof(float), user_queries(c), HVS_QCOLS * sizeof(float), 2u * sizeof(float), nuq, hipMemcpyDeviceToHost));
     P->nuq = nuq;
-    P->set_off.resize((size_t)nuq + 1u);
-    for (uint32_t p = 0; p <= nuq; ++p) P->set_off[p] = off[p] - off[0];
+    P->host.set_off.resize((size_t)nuq + 1u);
+    for (uint32_t p = 0; p <= nuq; ++p) P->host.set_off[p] = off[p] - off[0];
     const float* v0 = vals ? vals + off[0] : nullptr;
     P->sub_off.resize((size_t)nuq + 1u);
     P->eff.resize(nuq);
-    P->nsub = in_plan_core(tv.data(), tv.data() + 1, 2u, P->set_off.data(), v0, nuq, P->sub_off.data(), nullptr, nullptr, P->eff.data());
+    P->nsub = in_plan_core(tv.data(), tv.data() + 1, 2u, P->host.set_off.data(), v0, nuq, P->sub_off.data(), nullptr, nullptr, P->eff.data());
     if (P->nsub == 0xFFFFFFFFu) return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed sets");
-    P->parent.resize(P->nsub);
-    P->value.resize(P->nsub);
-    (void)in_plan_core(tv.data(), tv.data() + 1, 2u, P->set_off.data(), v0, nuq, nullptr, P->parent.data(), P->value.data(), nullptr);
+    P->host.parent.resize(P->nsub);
+    P->host.value.resize(P->nsub);
+    (void)in_plan_core(tv.data(), tv.data() + 1, 2u, P->host.set_off.data(), v0, nuq, nullptr, P->host.parent.data(), P->host.value.data(), nullptr);
     return HVS_OK;
 }
 
@@ -3524,26 +3563,26 @@ int in_plan_device(hvs_ctx* c, const uint32_t* d_off, const float* d_vals, int s
             return rc;
         S.p_cap = nuq;
     }
-    P->on_device = true;
+    P->dev.made = true;
     P->nuq = nuq;
-    P->lo = lo;
+    P->dev.lo = lo;
     if (src_dev == c->device) {
-        P->d_off = d_off;
-        P->d_vals = d_vals;
-        P->v0 = 0u;
+        P->dev.d_off = d_off;
+        P->dev.d_vals = d_vals;
+        P->dev.v0 = 0u;
     } else {
         if ((rc = ensure_room(c, &S.d_p_off, S.p_off_cap, (size_t)nuq + 1u)) || (rc = ensure_room(c, &S.d_p_vals, S.pv_cap, hi - lo)) ||
             (rc = copy_from_device(c, S.d_p_off, d_off, src_dev, ((size_t)nuq + 1u) * sizeof(uint32_t))) ||
             (rc = copy_from_device(c, S.d_p_vals, d_vals ? d_vals + lo : nullptr, src_dev, d_vals ? (size_t)(hi - lo) * sizeof(float) : 0u)))
             return rc;
-        P->d_off = S.d_p_off;
-        P->d_vals = d_vals && hi > lo ? S.d_p_vals : nullptr;
-        P->v0 = lo;
+        P->dev.d_off = S.d_p_off;
+        P->dev.d_vals = d_vals && hi > lo ? S.d_p_vals : nullptr;
+        P->dev.v0 = lo;
     }
     HVS_HIP(c, hipMemsetAsync(S.d_p_stat, 0, 3u * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
     if (nuq)
-        hipLaunchKernelGGL(hvs_k_in_count, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, user_queries(c), P->d_off, P->d_vals, P->v0, lo, hi, nuq,
+        hipLaunchKernelGGL(hvs_k_in_count, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, user_queries(c), P->dev.d_off, P->dev.d_vals, P->dev.v0, lo, hi, nuq,
                            S.d_p_pack, S.d_p_stat);
     hipLaunchKernelGGL(hvs_k_in_scan, dim3(1), dim3(1024), 0, c->stream, S.d_p_pack, nuq, S.d_p_sub_off, S.d_p_eff, S.d_p_stat);
     HVS_HIP(c, hipGetLastError());
@@ -3558,7 +3597,7 @@ int in_plan_device(hvs_ctx* c, const uint32_t* d_off, const float* d_vals, int s
     if (st[0] & HVS_INP_TOO_MANY) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: a set of more than 64 distinct categories");
     if (st[1] >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: too many sub-queries");
     P->nsub = (uint32_t)st[1];
-    P->sub_if_all_c = st[2];
+    P->dev.sub_if_all_c = st[2];
     P->sub_off.resize((size_t)nuq + 1u);
     P->eff.resize(nuq);
     HVS_HIP(c, hipMemcpyAsync(P->sub_off.data(), S.d_p_sub_off, P->sub_off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -3579,17 +3618,124 @@ int in_plan_release(hvs_ctx* c)
     return HVS_OK;
 }
 
-// A plan is put in force on its GPU: the user's rows move aside, the plan's arrays reach the device -- uploaded, or, for a plan
-// made there, written by the fill kernel --, and the engines' set becomes the expanded one.  A failure half-way (no room)
-// leaves the context without sets, and without resident queries if the query buffer itself could not grow.  On a replicated
-// context the root then detaches every other GPU too: sets are attached on all GPUs or on none.
-int in_commit(hvs_ctx* c, InPlan& P)
+// ---- the three clients' own steps (ExpandedKind::payload, expand, merge) and their descriptors ----
+// category sets: a host plan's arrays are uploaded; of a plan made on the device, sub_off is copied and the fill kernel writes
+// parent, value and the rebased offsets (part of expand_ms, as plan_ms is)
+int sets_payload(hvs_ctx* c, const InPlan& P)
+{
+    HvsInSet& S = c->qs.in;
+    if (P.dev.made) {
+        if (hipMemcpyAsync(S.d_sub_off, S.d_p_sub_off, ((size_t)P.nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+            return fail(c, HVS_EHIP, "hvs_set_category_sets_device: the copy of the plan failed");
+        return HVS_OK;
+    }
+    const InPlan::Host& H = P.host;
+    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    if (up(S.d_sub_off, P.sub_off.data(), P.sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_set_off, H.set_off.data(), H.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_parent, H.parent.data(), H.parent.size() * sizeof(uint32_t)) != hipSuccess ||
+        up(S.d_value, H.value.data(), H.value.size() * sizeof(float)) != hipSuccess)
+        return fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed");
+    return HVS_OK;
+}
+dim3 expand_grid(uint32_t nsub) { return dim3((uint32_t)(((uint64_t)nsub * (HVS_QCOLS / 4u) + 255u) / 256u)); }  // (a thread per float4 of a row)
+void sets_expand(hvs_ctx* c, const InPlan& P)
+{
+    const HvsInSet& S = c->qs.in;
+    const InPlan::Device& V = P.dev;
+    if (V.made && P.nuq)
+        hipLaunchKernelGGL(hvs_k_in_fill, dim3((P.nuq + 3u) / 4u), dim3(256), 0, c->stream, S.d_uq, V.d_off, V.d_vals, V.v0, V.lo, P.nuq, S.d_sub_off, S.d_p_eff,
+                           S.d_set_off, S.d_parent, S.d_value);
+    if (P.nsub)
+        hipLaunchKernelGGL(hvs_k_expand_in, expand_grid(P.nsub), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_value,
+                           S.d_set_off, P.nsub, reinterpret_cast<float4*>(c->d_q));
+}
+// extra vectors and extra clauses: the slice's extras -- `floats` of them from `src` -- into *buf; nothing else is uploaded,
+// the fill kernels write sub_off and parent from the staged offsets
+int extras_in(hvs_ctx* c, float** buf, size_t& cap, const float* src, int src_dev, size_t floats)
+{
+    const int rc = ensure_room(c, buf, cap, floats);
+    return rc ? rc : copy_in(c, *buf, src, src_dev, floats * sizeof(float));
+}
+int vectors_payload(hvs_ctx* c, const InPlan& P)
+{
+    HvsInSet& S = c->qs.in;
+    return extras_in(c, &S.d_vecs, S.vecs_cap, P.csr.vecs, P.csr.src_dev, ((size_t)P.nsub - P.nuq) * HVS_NDIM);
+}
+void vectors_expand(hvs_ctx* c, const InPlan& P)
+{
+    const HvsInSet& S = c->qs.in;
+    hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(P.nuq + 1u, 256u)), dim3(256), 0, c->stream, S.v_stage.d_words, P.nuq, S.d_sub_off, S.d_parent);
+    if (P.nsub)
+        hipLaunchKernelGGL(hvs_k_expand_vectors, expand_grid(P.nsub), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off,
+                           reinterpret_cast<const float4*>(S.d_vecs), P.nsub, reinterpret_cast<float4*>(c->d_q));
+}
+int clauses_payload(hvs_ctx* c, const InPlan& P)
+{
+    HvsInSet& S = c->qs.in;
+    const size_t ncl = (size_t)P.nsub - P.nuq;
+    const int rc = extras_in(c, &S.d_attrs, S.attrs_cap, P.csr.attrs, P.csr.src_dev, ncl * 4u);
+    return rc || !P.csr.vecs ? rc : extras_in(c, &S.d_vecs, S.vecs_cap, P.csr.vecs, P.csr.src_dev, ncl * HVS_NDIM);
+}
+void clauses_expand(hvs_ctx* c, const InPlan& P)
+{
+    const HvsInSet& S = c->qs.in;
+    hipLaunchKernelGGL(hvs_k_fill_clauses, dim3(hvs_ceil_div(P.nuq + 1u, 4u)), dim3(256), 0, c->stream, S.v_stage.d_words, P.nuq, S.d_sub_off, S.d_parent);
+    if (P.nsub)
+        hipLaunchKernelGGL(hvs_k_expand_clauses, expand_grid(P.nsub), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off,
+                           reinterpret_cast<const float4*>(S.d_attrs), P.csr.vecs ? reinterpret_cast<const float4*>(S.d_vecs) : nullptr, P.nsub,
+                           reinterpret_cast<float4*>(c->d_q));
+}
+// The merge kernels are templates over <scalar order, capacity> with one signature.  The dispatch over the two compile-time
+// constants is written here, once; a client's `pick(ST, CAPT)` names its kernel.  hvs_k_merge_vectors merges by id, and pads from
+// the EXPANDED rows (a pad row's smallest distance); hvs_k_merge_clauses likewise, for up to 256 lists, under a threshold.
+template <typename Pick>
+MergeKernel merge_kernel(bool scalar_order, int cap, Pick pick)
+{
+    MergeKernel k = nullptr;
+    with_cap(cap, [&](auto CAPT) { k = scalar_order ? pick(std::true_type{}, CAPT) : pick(std::false_type{}, CAPT); });
+    return k;
+}
+#define HVS_MERGE_OF(kernel) \
+    [](auto ST, auto CAPT) -> MergeKernel { return kernel<decltype(ST)::value, decltype(CAPT)::value>; }
+
+static_assert(HVS_VEC_MAX_EXTRA_ == HVS_VECTORS_MAX_EXTRA && HVS_VECTORS_MAX_EXTRA + 1 <= 64, "a merge streams at most 64 sub-lists");
+static_assert(HVS_CLAUSE_MAX_EXTRA_ == HVS_CLAUSES_MAX_EXTRA && HVS_CLAUSES_MAX_EXTRA + 1 == 256, "hvs_k_merge_clauses streams at most 256 sub-lists");
+const ExpandedKind kCategorySets{
+    HvsInSet::Sets, {"hvs_set_category_sets", "hvs_set_category_sets_device"}, {"set_offsets", "d_set_offsets"}, "hvs_query_in",
+    ": malformed offsets, a set of more than 64 distinct categories, or too many sub-queries", "hvs_in_stats",
+    false, 0u, {nullptr, nullptr, nullptr}, nullptr, nullptr, false,
+    sets_payload, sets_expand, [](const InPlan&) { return true; },  // (the sub-queries' categories are distinct: so are their rows)
+    [](bool order, int cap) { return merge_kernel(order, cap, HVS_MERGE_OF(hvs_k_merge_in)); }, true, 3u};
+const ExpandedKind kQueryVectors{
+    HvsInSet::Vectors, {"hvs_set_query_vectors", "hvs_set_query_vectors_device"}, {"vec_offsets", "d_offsets"}, "hvs_query_vectors",
+    ": malformed offsets, more than HVS_VECTORS_MAX_EXTRA extra vectors on a query, or too many sub-queries", "hvs_vectors_stats",
+    true, HVS_VEC_MAX_EXTRA_,
+    {": vec_offsets[0] is not 0", ": vec_offsets are not ascending", ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"},
+    &InPlan::Staged::vecs, ": vecs is NULL", false,
+    vectors_payload, vectors_expand, [](const InPlan&) { return false; },  // (a row comes back under every vector it is near to)
+    [](bool order, int cap) { return merge_kernel(order, cap, HVS_MERGE_OF(hvs_k_merge_vectors)); }, false, 3u};
+const ExpandedKind kQueryClauses{
+    HvsInSet::Clauses, {"hvs_set_query_clauses", "hvs_set_query_clauses_device"}, {"clause_offsets", "d_offsets"}, "hvs_query_clauses",
+    ": malformed offsets, more than HVS_CLAUSES_MAX_EXTRA extra clauses on a query, too many sub-queries, or clause_attrs is NULL", "hvs_clauses_stats",
+    true, HVS_CLAUSE_MAX_EXTRA_,
+    {": clause_offsets[0] is not 0", ": clause_offsets are not ascending", ": a query has more than HVS_CLAUSES_MAX_EXTRA extra clauses"},
+    &InPlan::Staged::attrs, ": clause_attrs is NULL", true,
+    clauses_payload, clauses_expand, [](const InPlan& P) { return !P.csr.vecs; },  // (predicate-only clauses give a row ONE key)
+    [](bool order, int cap) { return merge_kernel(order, cap, HVS_MERGE_OF(hvs_k_merge_clauses)); }, false, 5u};
+
+// A plan of client K is put in force on its GPU: the user's rows move aside, room is made for the sub-queries, what the
+// client's kernels read reaches the device (K.payload), they run between the two events (K.expand), and the engines' set
+// becomes the expanded one.  A failure half-way (no room) leaves the context without a client, and without resident queries
+// if the query buffer itself could not grow.  On a replicated context the root then detaches every other GPU too
+// (commit_everywhere_or_detach_all): a client is attached on all GPUs or on none.
+int in_commit(hvs_ctx* c, const ExpandedKind& K, InPlan& P)
 {
     HvsInSet& S = c->qs.in;
     const uint32_t nuq = P.nuq, nsub = P.nsub;
     int rc;
     HVS_HIP(c, hipSetDevice(c->device));  // (a multi-GPU commit runs on a thread of its own: every buffer below is this GPU's)
-    // the user's rows: already aside when sets are replaced
+    // the user's rows: already aside when a client is replaced
     if (!S.active) {
         if (!S.d_sub_off || nuq > S.uq_cap) {
             S.uq_cap = 0;
@@ -3604,7 +3750,7 @@ int in_commit(hvs_ctx* c, InPlan& P)
     }
     // from here on the context changes
     auto lost = [&](int code) {
-        sets_changed(c, false);
+        expanded_changed(c, false);
         if (c->nq_cap < nuq) c->nq = 0;
         else if (hipMemcpy(c->d_q, S.d_uq, (size_t)nuq * HVS_QCOLS * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess) c->nq = nuq;
         else c->nq = 0;
@@ -3612,67 +3758,21 @@ int in_commit(hvs_ctx* c, InPlan& P)
     };
     if ((rc = ensure_room(c, &S.d_parent, S.sub_cap, nsub, &S.d_value))) return lost(rc);
     if ((rc = ensure_queries(c, nsub))) return lost(rc);  // (the cursor arrays follow when cursors come: ensure_after)
-    const bool clauses = P.kind == HvsInSet::Clauses;
-    const bool vectors = P.kind == HvsInSet::Vectors || clauses;  // (the CSR clients: staged offsets, the fill kernel plans)
-    const char* const what = clauses ? "hvs_set_query_clauses" : vectors ? "hvs_set_query_vectors" : "hvs_set_category_sets";
-    if (clauses) {
-        const size_t ncl = (size_t)nsub - nuq;
-        if ((rc = ensure_room(c, &S.d_attrs, S.attrs_cap, ncl * 4u)) || (rc = copy_in(c, S.d_attrs, P.attrs, P.vec_dev, ncl * 4u * sizeof(float))))
-            return lost(rc);
-    }
-    if (vectors && (!clauses || P.vecs)) {
-        const size_t nvec = (size_t)nsub - nuq;
-        if ((rc = ensure_room(c, &S.d_vecs, S.vecs_cap, nvec * HVS_NDIM)) || (rc = copy_in(c, S.d_vecs, P.vecs, P.vec_dev, nvec * HVS_NDIM * sizeof(float))))
-            return lost(rc);
-    }
-    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
-    if (vectors) {
-        // (nothing to upload: hvs_k_fill_vectors below writes sub_off and parent from the staged offsets)
-    } else if (P.on_device) {
-        if (hipMemcpyAsync(S.d_sub_off, S.d_p_sub_off, ((size_t)nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-            return lost(fail(c, HVS_EHIP, "hvs_set_category_sets_device: the copy of the plan failed"));
-    } else if (up(S.d_sub_off, P.sub_off.data(), P.sub_off.size() * sizeof(uint32_t)) != hipSuccess ||
-               up(S.d_set_off, P.set_off.data(), P.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-               up(S.d_parent, P.parent.data(), P.parent.size() * sizeof(uint32_t)) != hipSuccess ||
-               up(S.d_value, P.value.data(), P.value.size() * sizeof(float)) != hipSuccess)
-        return lost(fail(c, HVS_EHIP, "hvs_set_category_sets: upload of the plan failed"));
+    if ((rc = K.payload(c, P))) return lost(rc);
     (void)hipEventRecord(S.ev_x0, c->stream);
-    if (clauses) {
-        hipLaunchKernelGGL(hvs_k_fill_clauses, dim3(hvs_ceil_div(nuq + 1u, 4u)), dim3(256), 0, c->stream, S.v_stage.d_words, nuq, S.d_sub_off, S.d_parent);
-        if (nsub) {
-            const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
-            hipLaunchKernelGGL(hvs_k_expand_clauses, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
-                               reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off, reinterpret_cast<const float4*>(S.d_attrs),
-                               P.vecs ? reinterpret_cast<const float4*>(S.d_vecs) : nullptr, nsub, reinterpret_cast<float4*>(c->d_q));
-        }
-    } else if (vectors) {
-        hipLaunchKernelGGL(hvs_k_fill_vectors, dim3(hvs_ceil_div(nuq + 1u, 256u)), dim3(256), 0, c->stream, S.v_stage.d_words, nuq, S.d_sub_off, S.d_parent);
-        if (nsub) {
-            const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
-            hipLaunchKernelGGL(hvs_k_expand_vectors, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream,
-                               reinterpret_cast<const float4*>(S.d_uq), S.d_parent, S.d_sub_off, reinterpret_cast<const float4*>(S.d_vecs), nsub,
-                               reinterpret_cast<float4*>(c->d_q));
-        }
-    } else if (P.on_device && nuq)  // (parent, value and the rebased offsets; part of expand_ms, as plan_ms is)
-        hipLaunchKernelGGL(hvs_k_in_fill, dim3((nuq + 3u) / 4u), dim3(256), 0, c->stream, S.d_uq, P.d_off, P.d_vals, P.v0, P.lo, nuq, S.d_sub_off,
-                           S.d_p_eff, S.d_set_off, S.d_parent, S.d_value);
-    if (nsub && !vectors) {
-        const uint64_t pieces = (uint64_t)nsub * (HVS_QCOLS / 4u);
-        hipLaunchKernelGGL(hvs_k_expand_in, dim3((uint32_t)((pieces + 255u) / 256u)), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(S.d_uq),
-                           S.d_parent, S.d_value, S.d_set_off, nsub, reinterpret_cast<float4*>(c->d_q));
-    }
+    K.expand(c, P);
     (void)hipEventRecord(S.ev_x1, c->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)  // (the host arrays go with this scope)
-        return lost(fail(c, HVS_EHIP, std::string(what) + ": the expansion failed"));
+        return lost(fail(c, HVS_EHIP, std::string(K.set_fn[0]) + ": the expansion failed"));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
     S.expand_ms = (double)ms + P.plan_ms;
     S.h_sub_off.swap(P.sub_off);
     S.h_eff.swap(P.eff);
     c->nq = nsub;
-    S.kind = P.kind;
-    S.clause_vecs = clauses && P.vecs;
-    sets_changed(c, true);
+    S.client = &K;
+    S.one_key_per_row = K.one_key_per_row(P);
+    expanded_changed(c, true);
     return HVS_OK;
 }
 
@@ -3682,16 +3782,11 @@ int in_attach(hvs_ctx* c, const uint32_t* off, const float* vals, uint32_t nuq)
     InPlan P;
     int rc = in_begin(c);
     if (!rc) rc = in_plan_host(c, off, vals, nuq, &P);
-    return rc ? rc : in_commit(c, P);
+    return rc ? rc : in_commit(c, kCategorySets, P);
 }
 
-// ---- extra query vectors (include/hvs.h "multi-vector queries"): the second client of the expanded set ----
-static_assert(HVS_VEC_MAX_EXTRA_ == HVS_VECTORS_MAX_EXTRA && HVS_VECTORS_MAX_EXTRA + 1 <= 64, "a merge streams at most 64 sub-lists");
-// ... and extra clauses (include/hvs.h "query clauses"), the third: staged, checked and planned as the vectors are
-static_assert(HVS_CLAUSE_MAX_EXTRA_ == HVS_CLAUSES_MAX_EXTRA && HVS_CLAUSES_MAX_EXTRA + 1 == 256, "hvs_k_merge_clauses streams at most 256 sub-lists");
-
-// hvs_vectors_check's arithmetic
-uint32_t vec_check_core(const uint32_t* off, uint32_t nq, uint32_t max_extra = HVS_VECTORS_MAX_EXTRA)
+// hvs_vectors_check's and hvs_clauses_check's arithmetic
+uint32_t vec_check_core(const uint32_t* off, uint32_t nq, uint32_t max_extra)
 {
     if (!off || off[0] != 0u) return 0xFFFFFFFFu;
     for (uint32_t q = 0; q < nq; ++q)
@@ -3700,26 +3795,24 @@ uint32_t vec_check_core(const uint32_t* off, uint32_t nq, uint32_t max_extra = H
     return nsub >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nsub;
 }
 
-// The plan of one GPU's slice of the CSR, first half: the slice's offsets -- `nuq` + 1 entries from host memory (src_dev < 0) or
-// from GPU src_dev -- are staged in v_stage and checked there (leaf_stage, with an event pair around the check; `first`: the
-// slice is the head of the caller's array).  Good offsets come back to the host
+// The plan of one GPU's slice of a staged client's CSR, first half: the slice's offsets -- `nuq` + 1 entries from host memory
+// (src_dev < 0) or from GPU src_dev -- are staged in v_stage and checked there against K.limit (leaf_stage, with an event pair
+// around the check; `first`: the slice is the head of the caller's array).  Good offsets come back to the host
 // too (4 bytes per query): sub_off[q] = off[q] - off[0] + q, and hvs_query_resident maps query ranges to sub-query ranges there.
 // Nothing that a query or a later call reads changes; the caller judges the flags of all GPUs before any commit.
-// `kind`: Vectors, or Clauses -- the same staging with the clauses' limit.
-int vec_stage(hvs_ctx* c, HvsInSet::Kind kind, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
+int csr_stage(hvs_ctx* c, const ExpandedKind& K, const uint32_t* off, int src_dev, uint32_t nuq, bool first, InPlan* P)
 {
     HvsInSet& S = c->qs.in;
     const size_t bytes = ((size_t)nuq + 1u) * sizeof(uint32_t);
     int rc = leaf_stage(c, S.v_stage, true, off, src_dev, nuq + 1u, [&](const HvsStage& st) {
         HVS_HIP(c, hipEventRecord(S.ev_x0, c->stream));
-        if (int rc2 = check_offsets(c, st, nuq, first, kind == HvsInSet::Clauses ? HVS_CLAUSE_MAX_EXTRA_ : HVS_VEC_MAX_EXTRA_)) return rc2;
+        if (int rc2 = check_offsets(c, st, nuq, first, K.limit)) return rc2;
         HVS_HIP(c, hipEventRecord(S.ev_x1, c->stream));
         return HVS_OK;
     });
     if (rc) return rc;
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, S.ev_x0, S.ev_x1);
-    P->kind = kind;
     P->nuq = nuq;
     P->plan_ms = ms;
     if (S.v_stage.flags) return HVS_OK;
@@ -3733,12 +3826,13 @@ int vec_stage(hvs_ctx* c, HvsInSet::Kind kind, const uint32_t* off, int src_dev,
     return HVS_OK;
 }
 
-// hvs_query_resident under category sets: user queries [q0, q0 + nq) = sub-queries [sub_off[q0], sub_off[q0 + nq)), answered by
-// the engines with padding off FOR THIS CALL (the user's setting is the merge's), their re-runs resolved (the call's one host
-// synchronisation, as part_run has), then one merge launch into the merged rows q0 .. q0 + nq.
+// hvs_query_resident under an expanded set: user queries [q0, q0 + nq) = sub-queries [sub_off[q0], sub_off[q0 + nq)), answered
+// by the engines with padding off FOR THIS CALL (the user's setting is the merge's), their re-runs resolved (the call's one host
+// synchronisation, as part_run has), then one launch of the client's merge into the merged rows q0 .. q0 + nq.
 int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
 {
     HvsInSet& S = c->qs.in;
+    const ExpandedKind& K = *S.client;
     if (!c->d_data) return fail(c, HVS_ESTATE, "no data set loaded (hvs_load_data / hvs_gen_data)");
     if ((uint64_t)q0 + nq > S.nuq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
@@ -3756,36 +3850,17 @@ int in_run(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proportion)
         if ((rc = run_queries(c, s0, s1 - s0, sample_proportion, NoHook{}))) return rc;
         if ((rc = resolve_overflow(c))) return rc;
     }
-    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, (S.kind == HvsInSet::Clauses ? 5 : 3) * sizeof(unsigned long long), c->stream));
+    HVS_HIP(c, hipMemsetAsync(S.d_stat, 0, K.stat_words * sizeof(unsigned long long), c->stream));
     HVS_HIP(c, hipEventRecord(S.ev_m0, c->stream));
-    if (nq) {
-        with_cap(c->cap, [&](auto CAPT) {
-            auto launch = [&](auto ST) {
-                if (S.kind == HvsInSet::Clauses)  // (as the next one, for up to 256 lists, under a threshold)
-                    hipLaunchKernelGGL((hvs_k_merge_clauses<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
-                                       S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, c->d_q, c->padding ? 1 : 0,
-                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
-                else if (S.kind == HvsInSet::Vectors)  // (merges by id, and pads from the EXPANDED rows: a pad row's smallest distance)
-                    hipLaunchKernelGGL((hvs_k_merge_vectors<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream,
-                                       S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, c->d_q, c->padding ? 1 : 0,
-                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
-                else
-                    hipLaunchKernelGGL((hvs_k_merge_in<decltype(ST)::value, decltype(CAPT)::value>), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream, S.d_sub_off,
-                                       q0, nq, c->d_out_ids, c->d_out_dists, c->d_data, c->n, S.d_uq, c->padding ? 1 : 0,
-                                       masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids, S.d_m_dists, c->k, S.d_stat);
-            };
-            if (c->scalar_order)
-                launch(std::true_type{});
-            else
-                launch(std::false_type{});
-        });
-        HVS_HIP(c, hipGetLastError());
-    }
+    hipLaunchKernelGGL(K.merge(c->scalar_order, c->cap), dim3((nq + 3u) / 4u), dim3(256), 0, c->stream, S.d_sub_off, q0, nq, c->d_out_ids, c->d_out_dists,
+                       c->d_data, c->n, K.merge_user_rows ? S.d_uq : c->d_q, c->padding ? 1 : 0, masked(c) ? c->rs.d_pad_ids : nullptr, S.d_m_ids,
+                       S.d_m_dists, c->k, S.d_stat);
+    HVS_HIP(c, hipGetLastError());
     HVS_HIP(c, hipEventRecord(S.ev_m1, c->stream));
     HVS_HIP(c, hipEventRecord(c->call.ev_q1, c->stream));  // (the merge belongs to the call's device time)
     c->call.timing.nq = nq;  // (the user's)
     S.call = true;
-    S.call_kind = S.kind;
+    S.call_client = S.client;
     S.call_sub = s1 - s0;
     S.call_set_queries = S.call_max_set = 0;
     for (uint32_t p = q0; p < q0 + nq; ++p) {
@@ -3800,78 +3875,53 @@ int leaf_run_resident(hvs_ctx* c, uint32_t q0, uint32_t nq, float sample_proport
     return c->qs.in.active ? in_run(c, q0, nq, sample_proportion) : run_queries(c, q0, nq, sample_proportion, NoHook{});
 }
 
-// the last call's merge on one GPU (it ran on an expanded set: S.call): its three counters and its device time
-int leaf_merge_stats(hvs_ctx* c, unsigned long long (&v)[3], float* ms)
+// the last call's merge on one GPU (it ran on an expanded set: S.call): the first `words` of its counters and its device time
+int leaf_merge_stats(hvs_ctx* c, unsigned long long* v, uint32_t words, float* ms)
 {
     const HvsInSet& S = c->qs.in;
-    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    HVS_HIP(c, hipMemcpy(v, S.d_stat, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     HVS_HIP(c, hipEventElapsedTime(ms, S.ev_m0, S.ev_m1));
     return HVS_OK;
 }
 
-int leaf_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
+// What the three clients' stats share on one GPU: the call is over, *out is zeroed, and, if the last call ran under client K,
+// the figures every info struct has -- some under names of its own: the queries with extras, the most sub-queries of one
+// query, the keys read -- are filled in.  `own(*out, v)` adds the client's other counters from the merge's words v.
+template <typename Info, typename Own>
+int leaf_client_stats(hvs_ctx* c, const ExpandedKind& K, Info* out, uint32_t Info::*queries, uint32_t Info::*most, uint64_t Info::*keys, Own own)
 {
     int rc = call_required(c);
     if (rc) return rc;
-    *out = hvs_vectors_info{};
+    *out = Info{};
     const HvsInSet& S = c->qs.in;
-    if (!S.call || S.call_kind != HvsInSet::Vectors) return HVS_OK;
-    unsigned long long v[3] = {0, 0, 0};
+    if (!S.call || S.call_client != &K) return HVS_OK;
+    unsigned long long v[HvsInSet::kStatWordsMax] = {};
     float ms = 0.f;
-    if ((rc = leaf_merge_stats(c, v, &ms))) return rc;
-    out->multi_queries = S.call_set_queries;
+    if ((rc = leaf_merge_stats(c, v, K.stat_words, &ms))) return rc;
+    out->*queries = S.call_set_queries;
     out->sub_queries = S.call_sub;
-    out->max_vectors = S.call_max_set;
+    out->*most = S.call_max_set;
     out->underfull_queries = (uint32_t)v[0];
-    out->merged_keys = v[1];
-    out->duplicate_keys = v[2];
+    out->*keys = v[1];
     out->expand_ms = S.expand_ms;
     out->merge_ms = ms;
+    own(*out, v);
     return HVS_OK;
 }
-
-int leaf_clauses_stats(hvs_ctx* c, hvs_clauses_info* out)
-{
-    int rc = call_required(c);
-    if (rc) return rc;
-    *out = hvs_clauses_info{};
-    const HvsInSet& S = c->qs.in;
-    if (!S.call || S.call_kind != HvsInSet::Clauses) return HVS_OK;
-    unsigned long long v[5] = {0, 0, 0, 0, 0};
-    float ms = 0.f;
-    HVS_HIP(c, hipMemcpy(v, S.d_stat, sizeof(v), hipMemcpyDeviceToHost));
-    HVS_HIP(c, hipEventElapsedTime(&ms, S.ev_m0, S.ev_m1));
-    out->clause_queries = S.call_set_queries;
-    out->sub_queries = S.call_sub;
-    out->max_clauses = S.call_max_set;
-    out->underfull_queries = (uint32_t)v[0];
-    out->read_keys = v[1];
-    out->duplicate_keys = v[2];
-    out->bounded_keys = v[3];
-    out->skipped_chunks = v[4];
-    out->expand_ms = S.expand_ms;
-    out->merge_ms = ms;
-    return HVS_OK;
-}
-
 int leaf_in_stats(hvs_ctx* c, hvs_in_info* out)
 {
-    int rc = call_required(c);
-    if (rc) return rc;
-    *out = hvs_in_info{};
-    const HvsInSet& S = c->qs.in;
-    if (!S.call || S.call_kind != HvsInSet::Sets) return HVS_OK;
-    unsigned long long v[3] = {0, 0, 0};
-    float ms = 0.f;
-    if ((rc = leaf_merge_stats(c, v, &ms))) return rc;
-    out->set_queries = S.call_set_queries;
-    out->sub_queries = S.call_sub;
-    out->max_set = S.call_max_set;
-    out->underfull_queries = (uint32_t)v[0];
-    out->merged_keys = v[1];
-    out->expand_ms = S.expand_ms;
-    out->merge_ms = ms;
-    return HVS_OK;
+    return leaf_client_stats(c, kCategorySets, out, &hvs_in_info::set_queries, &hvs_in_info::max_set, &hvs_in_info::merged_keys,
+                             [](hvs_in_info&, const unsigned long long*) {});
+}
+int leaf_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
+{
+    return leaf_client_stats(c, kQueryVectors, out, &hvs_vectors_info::multi_queries, &hvs_vectors_info::max_vectors, &hvs_vectors_info::merged_keys,
+                             [](hvs_vectors_info& o, const unsigned long long* v) { o.duplicate_keys = v[2]; });
+}
+int leaf_clauses_stats(hvs_ctx* c, hvs_clauses_info* out)
+{
+    return leaf_client_stats(c, kQueryClauses, out, &hvs_clauses_info::clause_queries, &hvs_clauses_info::max_clauses, &hvs_clauses_info::read_keys,
+                             [](hvs_clauses_info& o, const unsigned long long* v) { o.duplicate_keys = v[2], o.bounded_keys = v[3], o.skipped_chunks = v[4]; });
 }
 
 // The vec_query-equivalent region with host buffers on both sides (reference src/test.cpp:82-88), pipelined:
@@ -4653,9 +4703,6 @@ int on_shares(hvs_ctx* c, const std::vector<Share>& sh, F f)
 }
 // Every share is staged (`stage(share, index)`: a leaf_stage into the area `area` names) and the root judges all GPUs' flags
 // before any GPU commits: HVS_EINVAL, with the text `why` has for the first flag set, leaves every GPU as it was.
-struct Refusal {
-    const char *bad_first, *bad_order, *bad_long;
-};
 template <typename Stage>
 int stage_and_judge(hvs_ctx* c, const std::vector<Share>& sh, const HvsStage& (*area)(const hvs_ctx*), const char* fn, const Refusal& why, Stage stage)
 {
@@ -4709,36 +4756,14 @@ int attach_for_call(hvs_ctx* c, const float* max_d2, const float* after_d, const
     return rc;
 }
 
-// hvs_set_query_vectors* on every GPU: the CSR from host memory (src_dev < 0) or from GPU src_dev (checked and waited for by the
-// caller).  A replicated context cuts it by the owner ranges.  Every GPU stages and checks its slice first and none changes
-// unless every slice is good and the sub-queries of the whole context can be counted in 32 bits: HVS_EINVAL leaves every GPU
-// as it was.  A failed commit (no room) leaves no GPU on an expanded set, as for category sets.
-// `kind` = Clauses: hvs_set_query_clauses*, the same protocol; `attrs` = the clauses' [type, v, l, r], where `vecs` is.
-int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int src_dev, uint32_t nq, const char* fn,
-                       HvsInSet::Kind kind = HvsInSet::Vectors, const float* attrs = nullptr)
+// ---- the expanded set's clients, root side ----
+// Every share commits its plan (`commit(share, index)`: an in_commit).  A failed commit on a replicated context (no room:
+// in_commit left that GPU without a client) leaves no GPU under one: every GPU is detached, the context answers plain queries
+// on every GPU whose query buffer survived, and the failing GPU's error is the call's.
+template <typename Commit>
+int commit_everywhere_or_detach_all(hvs_ctx* c, const std::vector<Share>& sh, Commit commit)
 {
-    const bool clauses = kind == HvsInSet::Clauses;
-    const std::vector<Share> sh = shares_of(c, nq);
-    std::vector<InPlan> plans(sh.size());
-    static const Refusal kVec{": vec_offsets[0] is not 0", ": vec_offsets are not ascending", ": a query has more than HVS_VECTORS_MAX_EXTRA extra vectors"};
-    static const Refusal kClause{": clause_offsets[0] is not 0", ": clause_offsets are not ascending", ": a query has more than HVS_CLAUSES_MAX_EXTRA extra clauses"};
-    int rc = stage_and_judge(c, sh, v_stage_of, fn, clauses ? kClause : kVec, [&](const Share& s, size_t r) {
-        return vec_stage(s.k, kind, off + s.q0, src_dev, s.m, s.q0 == 0u, &plans[r]);
-    });
-    if (rc) return rc;
-    uint64_t total = 0;
-    for (const Share& s : sh) total = std::max<uint64_t>(total, v_stage_of(s.k).end);  // (ascending offsets: the last slice's end)
-    if (total + nq >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": too many sub-queries");
-    if (total && clauses && !attrs) return fail(c, HVS_EINVAL, std::string(fn) + ": clause_attrs is NULL");
-    if (total && !clauses && !vecs) return fail(c, HVS_EINVAL, std::string(fn) + ": vecs is NULL");
-    rc = on_shares(c, sh, [&](const Share& s, size_t r) {
-        InPlan& P = plans[r];
-        // (clauses without a single extra have no clause vectors whatever the pointer: every row has one key, cursors stay allowed)
-        P.vecs = vecs && !(clauses && total == 0u) ? vecs + (size_t)v_stage_of(s.k).first * HVS_NDIM : nullptr;
-        P.attrs = attrs ? attrs + (size_t)v_stage_of(s.k).first * 4u : nullptr;
-        P.vec_dev = src_dev;
-        return in_commit(s.k, P);
-    });
+    const int rc = on_shares(c, sh, commit);
     if (rc && !c->kids.empty()) {
         const std::string err = c->err;
         for (hvs_ctx* k : c->kids) (void)in_detach(k);
@@ -4746,6 +4771,30 @@ int vectors_everywhere(hvs_ctx* c, const uint32_t* off, const float* vecs, int s
         c->err = err;
     }
     return rc;
+}
+// The setters of a staged client K (hvs_set_query_vectors*, hvs_set_query_clauses*) on every GPU: the CSR -- `off` and the
+// extras `csr` -- from host memory (csr.src_dev < 0) or from GPU src_dev (checked and waited for by the caller).  A replicated
+// context cuts it by the owner ranges.  Every GPU stages and checks its slice first and none changes unless every slice is
+// good and the sub-queries of the whole context can be counted in 32 bits: HVS_EINVAL leaves every GPU as it was.
+int expanded_everywhere(hvs_ctx* c, const ExpandedKind& K, const uint32_t* off, InPlan::Staged csr, uint32_t nq, const char* fn)
+{
+    const std::vector<Share> sh = shares_of(c, nq);
+    std::vector<InPlan> plans(sh.size());
+    int rc = stage_and_judge(c, sh, v_stage_of, fn, K.why, [&](const Share& s, size_t r) {
+        return csr_stage(s.k, K, off + s.q0, csr.src_dev, s.m, s.q0 == 0u, &plans[r]);
+    });
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (const Share& s : sh) total = std::max<uint64_t>(total, v_stage_of(s.k).end);  // (ascending offsets: the last slice's end)
+    if (total + nq >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, std::string(fn) + ": too many sub-queries");
+    if (total && !(csr.*K.required)) return fail(c, HVS_EINVAL, std::string(fn) + K.required_null);
+    // (optional vectors without a single extra are no vectors whatever the pointer: every row has one key, cursors stay allowed)
+    if (K.vecs_optional && total == 0u) csr.vecs = nullptr;
+    return commit_everywhere_or_detach_all(c, sh, [&](const Share& s, size_t r) {
+        const size_t first = v_stage_of(s.k).first;
+        plans[r].csr = {csr.vecs ? csr.vecs + first * HVS_NDIM : nullptr, csr.attrs ? csr.attrs + first * 4u : nullptr, csr.src_dev};
+        return in_commit(s.k, K, plans[r]);
+    });
 }
 
 // the leaf whose row-set state speaks for the whole context (rows, mask and index are replicated)
@@ -5029,22 +5078,23 @@ int part_load(hvs_ctx* c, const float* rows, int src_dev, uint32_t n, uint64_t s
     return rc;
 }
 
-// ---- what the entry points of caps, cursors and category sets share ----
+// ---- what the entry points of caps, cursors, lists and the expanded set's clients share ----
 // resident queries of the whole context
 uint32_t resident_count(const hvs_ctx* c)
 {
     if (c->kids.empty()) return user_nq(c);
     return c->kid_q0.size() == c->kids.size() + 1u ? c->kid_q0.back() : 0u;
 }
-// extra vectors are attached (on every GPU or on none), or clauses with vectors of their own: cursors are refused meanwhile
-// (DESIGN 3.15, 3.16); predicate-only clauses give a row ONE key, and cursors go through leaf_attach as under category sets
-bool vectors_attached(const hvs_ctx* c)
+// May cursors be attached?  Not while the expanded set's client (attached on every GPU or on none) lets a row come back under
+// several keys -- extra vectors, or clauses with vectors of their own.  Under category sets and under
+// predicate-only clauses a row has ONE key, and cursors go through leaf_attach.
+bool cursors_refused(const hvs_ctx* c)
 {
     const hvs_ctx* k = c->kids.empty() ? c : c->kids[0];
-    return k->qs.in.active && (k->qs.in.kind == HvsInSet::Vectors || (k->qs.in.kind == HvsInSet::Clauses && k->qs.in.clause_vecs));
+    return k->qs.in.active && !k->qs.in.one_key_per_row;
 }
 #define HVS_NO_CURSORS_ON_VECTORS(c, fn) \
-    if (vectors_attached(c)) return fail((c), HVS_ESTATE, fn ": cursors do not compose with extra query vectors or clause vectors (a row would come back under another vector)")
+    if (cursors_refused(c)) return fail((c), HVS_ESTATE, fn ": cursors do not compose with extra query vectors or clause vectors (a row would come back under another vector)")
 // what the four entry points that attach per-query values check alike: `nq` is the number of resident queries ...
 int check_resident_count(hvs_ctx* c, uint32_t nq, const char* fn)
 {
@@ -5059,6 +5109,57 @@ int check_device_buffers(hvs_ctx* c, const void* a, const void* b, void* stream,
     if (!rc && b) rc = device_of_buffer(c, b, fn, &dev2);
     if (!rc && b && *dev != dev2) rc = fail(c, HVS_EINVAL, std::string(fn) + ": the two buffers are on different GPUs");
     return rc ? rc : wait_for_producer(c, *dev, stream);
+}
+
+// What the six setters of the expanded set's clients begin with (`device`: the _device form; `off`: the caller's offsets;
+// `none`: every pointer of the caller's is NULL).  kAttach: go on and attach.  Anything else is the call's result: a refusal,
+// or client K detached from every GPU -- no pointers, or no resident queries.
+enum : int { kAttach = 1 };
+int client_attach_begin(hvs_ctx* c, const ExpandedKind& K, bool device, const void* off, bool none, uint32_t nq)
+{
+    if (!c) return HVS_EINVAL;
+    const std::string fn = K.set_fn[device];
+    if (c->partitioned) return fail(c, HVS_ESTATE, fn + ": not supported (yet) on a row-partitioned context");
+    auto detach = [&] { return on_every_leaf(c, [&](hvs_ctx* k) { return client_detach(k, K); }); };
+    if (none) return detach();
+    if (!loaded_leaf(c, fn.c_str())) return HVS_ESTATE;
+    if (!off) return fail(c, HVS_EINVAL, fn + ": " + K.offsets[device] + " is NULL");
+    if (int rc = check_resident_count(c, nq, fn.c_str())) return rc;
+    return nq == 0u ? detach() : kAttach;
+}
+// The three one-shot calls (hvs_query_in, hvs_query_vectors, hvs_query_clauses).  `none`: every pointer of the CSR is NULL, a
+// plain hvs_query; `good()`: the client's host check of the CSR, made before the resident set is replaced -- a refused call
+// changes nothing; `set()`: the client's setter.  Then upload, set, run, download.
+template <typename Good, typename Set>
+int client_query(hvs_ctx* c, const ExpandedKind& K, bool none, const float* q_rows, uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists,
+                 Good good, Set set)
+{
+    if (!c) return HVS_EINVAL;
+    if (none) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
+    const std::string fn = K.query_fn;
+    if (c->partitioned) return fail(c, HVS_ESTATE, fn + ": not supported (yet) on a row-partitioned context");
+    if (!loaded_leaf(c, K.query_fn)) return HVS_ESTATE;
+    if (nq == 0u) return HVS_OK;
+    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, fn + ": q_rows / out_ids is NULL");
+    if (!good()) return fail(c, HVS_EINVAL, fn + K.bad_query);
+    int rc = hvs_upload_queries(c, q_rows, nq);
+    if (!rc) rc = set();
+    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
+    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
+    return rc;
+}
+// ... of a staged client: the offsets hold, and extras bring the array they cannot do without
+bool csr_good(const ExpandedKind& K, const uint32_t* off, const InPlan::Staged& csr, uint32_t nq)
+{
+    const uint32_t nsub = vec_check_core(off, nq, K.limit);
+    return nsub != 0xFFFFFFFFu && (nsub == nq || csr.*K.required);
+}
+// The three stats calls: refused on a row-partitioned context, else the leaves' figures combined by `add`
+template <typename Info, typename Add>
+int client_stats(hvs_ctx* c, const ExpandedKind& K, Info* out, int (*leaf_stats)(hvs_ctx*, Info*), Add add)
+{
+    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, std::string(K.stats_fn) + ": not supported (yet) on a row-partitioned context");
+    return call_stats<Info>(c, out, leaf_stats, add);
 }
 
 // What hvs_within_stats and hvs_after_stats start with on one GPU: the call is over, *out is zeroed, and, if the call ran with the
@@ -5076,9 +5177,9 @@ int leaf_call_counters(hvs_ctx* c, Info* out, bool on, int first, unsigned long 
 int in_underfull(hvs_ctx* c, uint32_t* underfull)
 {
     if (!c->qs.in.call) return HVS_OK;
-    unsigned long long v[3] = {0, 0, 0};
+    unsigned long long v[HvsInSet::kStatWordsMin] = {};
     float ms = 0.f;
-    const int rc = leaf_merge_stats(c, v, &ms);
+    const int rc = leaf_merge_stats(c, v, HvsInSet::kStatWordsMin, &ms);
     if (!rc) *underfull = (uint32_t)v[0];
     return rc;
 }
@@ -6405,52 +6506,27 @@ uint32_t hvs_in_plan(const float* q_rows, const uint32_t* set_offsets, const flo
 
 int hvs_set_category_sets(hvs_ctx* c, const uint32_t* set_offsets, const float* set_values, uint32_t nq)
 {
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets: not supported (yet) on a row-partitioned context");
-    if (!set_offsets && !set_values) return on_every_leaf(c, sets_detach);
-    if (!loaded_leaf(c, "hvs_set_category_sets")) return HVS_ESTATE;
-    if (!set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets: set_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, "hvs_set_category_sets")) return rc;
-    if (nq == 0u) return on_every_leaf(c, sets_detach);
+    const int go = client_attach_begin(c, kCategorySets, false, set_offsets, !set_offsets && !set_values, nq);
+    if (go != kAttach) return go;
     // format and limits hold whatever the queries' types; the sub-query count is the largest when every query tests C
     if (hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
         return fail(c, HVS_EINVAL, "hvs_set_category_sets: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
-    // owner ranges stay cut by user queries: each GPU takes its slice of the CSR
-    const int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) { return in_attach(k, set_offsets + first, set_values, m); });
-    if (rc && !c->kids.empty()) {
-        // one GPU could not attach (no room): no GPU stays under sets -- the context answers plain queries on every GPU whose
-        // query buffer survived (in_commit), and the failing GPU's error is the call's
-        const std::string err = c->err;
-        for (hvs_ctx* k : c->kids) (void)in_detach(k);
-        (void)hipGetLastError();
-        c->err = err;
-    }
-    return rc;
+    // owner ranges stay cut by user queries: each GPU takes its slice of the CSR, and plans and commits it in one pass
+    return commit_everywhere_or_detach_all(c, shares_of(c, nq), [&](const Share& s, size_t) { return in_attach(s.k, set_offsets + s.q0, set_values, s.m); });
 }
 
 int hvs_query_in(hvs_ctx* c, const float* q_rows, const uint32_t* set_offsets, const float* set_values, uint32_t nq, float sample_proportion,
                  uint32_t* out_ids, float* out_dists)
 {
-    if (!c) return HVS_EINVAL;
-    if (!set_offsets && !set_values) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_in: not supported (yet) on a row-partitioned context");
-    if (!loaded_leaf(c, "hvs_query_in")) return HVS_ESTATE;
-    if (nq == 0u) return HVS_OK;
-    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_in: q_rows / out_ids is NULL");
-    // checked before the resident set is replaced: a refused call changes nothing
-    if (!set_offsets || hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) == 0xFFFFFFFFu)
-        return fail(c, HVS_EINVAL, "hvs_query_in: malformed offsets, a set of more than 64 distinct categories, or too many sub-queries");
-    int rc = hvs_upload_queries(c, q_rows, nq);
-    if (!rc) rc = hvs_set_category_sets(c, set_offsets, set_values, nq);
-    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
-    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
-    return rc;
+    return client_query(
+        c, kCategorySets, !set_offsets && !set_values, q_rows, nq, sample_proportion, out_ids, out_dists,
+        [&] { return set_offsets && hvs_in_plan(nullptr, set_offsets, set_values, nq, nullptr, nullptr, nullptr) != 0xFFFFFFFFu; },
+        [&] { return hvs_set_category_sets(c, set_offsets, set_values, nq); });
 }
 
 int hvs_in_stats(hvs_ctx* c, hvs_in_info* out)
 {
-    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_in_stats: not supported (yet) on a row-partitioned context");
-    return call_stats<hvs_in_info>(c, out, leaf_in_stats, [](hvs_in_info& sum, const hvs_in_info& m) {
+    return client_stats(c, kCategorySets, out, leaf_in_stats, [](hvs_in_info& sum, const hvs_in_info& m) {
         sum.set_queries += m.set_queries;
         sum.sub_queries += m.sub_queries;
         sum.max_set = std::max(sum.max_set, m.max_set);
@@ -6464,40 +6540,31 @@ int hvs_in_stats(hvs_ctx* c, hvs_in_info* out)
 int hvs_set_category_sets_device(hvs_ctx* c, const uint32_t* d_set_offsets, const float* d_set_values, uint32_t nq, void* stream)
 {
     static const char* const fn = "hvs_set_category_sets_device";
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_category_sets_device: not supported (yet) on a row-partitioned context");
-    if (!d_set_offsets && !d_set_values) return on_every_leaf(c, sets_detach);
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!d_set_offsets) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: d_set_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, sets_detach);
+    const int go = client_attach_begin(c, kCategorySets, true, d_set_offsets, !d_set_offsets && !d_set_values, nq);
+    if (go != kAttach) return go;
     int dev = 0;
     if (int rc = check_device_buffers(c, d_set_offsets, d_set_values, stream, fn, &dev)) return rc;
     // the slice boundaries: offsets[first query of every GPU] and offsets[nq] come to the host (4 bytes each)
-    const size_t N = std::max<size_t>(c->kids.size(), 1u);
-    std::vector<uint32_t> q0(N + 1u, 0u), bound(N + 1u, 0u);
-    for (size_t r = 0; r <= N; ++r) {
-        q0[r] = c->kids.empty() ? (r ? nq : 0u) : c->kid_q0[r];
-        HVS_HIP(c, hipMemcpy(&bound[r], d_set_offsets + q0[r], sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the current device is the buffers')
-    }
+    const std::vector<Share> sh = shares_of(c, nq);
+    const size_t N = sh.size();
+    std::vector<uint32_t> bound(N + 1u, 0u);
+    for (size_t r = 0; r <= N; ++r)
+        HVS_HIP(c, hipMemcpy(&bound[r], d_set_offsets + (r < N ? sh[r].q0 : nq), sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the current device is the buffers')
     bool good = bound[0] == 0u && (bound[N] == 0u || d_set_values);
     for (size_t r = 0; r < N; ++r) good = good && bound[r] <= bound[r + 1u];
     if (!good) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: malformed offsets, or values missing");
     // every GPU plans its slice; nothing is in force yet, so a refusal leaves every GPU as it was
     std::vector<InPlan> plans(N);
-    auto slot = [&](const hvs_ctx* k) { return c->kids.empty() ? (size_t)0 : (size_t)(std::find(c->kids.begin(), c->kids.end(), k) - c->kids.begin()); };
     struct ReleaseCopies {  // (a GPU that does not hold the buffers copied its slice: given back however the call ends)
-        hvs_ctx* c;
+        const std::vector<Share>& sh;
         ~ReleaseCopies()
         {
-            if (c->kids.empty()) (void)in_plan_release(c);
-            for (hvs_ctx* k : c->kids) (void)in_plan_release(k);
+            for (const Share& s : sh) (void)in_plan_release(s.k);
         }
-    } release{c};
-    int rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t first, uint32_t m, uint32_t) {
-        const size_t r = slot(k);
-        const int rc2 = in_begin(k);
-        return rc2 ? rc2 : in_plan_device(k, d_set_offsets + first, d_set_values, dev, bound[r], bound[r + 1u], m, &plans[r]);
+    } release{sh};
+    int rc = on_shares(c, sh, [&](const Share& s, size_t r) {
+        const int rc2 = in_begin(s.k);
+        return rc2 ? rc2 : in_plan_device(s.k, d_set_offsets + s.q0, d_set_values, dev, bound[r], bound[r + 1u], s.m, &plans[r]);
     });
     if (rc) {
         (void)hipGetLastError();
@@ -6505,17 +6572,9 @@ int hvs_set_category_sets_device(hvs_ctx* c, const uint32_t* d_set_offsets, cons
     }
     // the limit is the host call's: the sub-queries there would be if every query tested C, over the whole context
     uint64_t all_c = 0;
-    for (const InPlan& P : plans) all_c += P.sub_if_all_c;
+    for (const InPlan& P : plans) all_c += P.dev.sub_if_all_c;
     if (all_c >= 0xFFFFFFFFull) return fail(c, HVS_EINVAL, "hvs_set_category_sets_device: too many sub-queries");
-    rc = for_each_share(c, nq, [&](hvs_ctx* k, uint32_t, uint32_t, uint32_t) { return in_commit(k, plans[slot(k)]); });
-    if (rc && !c->kids.empty()) {
-        // as in hvs_set_category_sets: no GPU stays under sets, and the failing GPU's error is the call's
-        const std::string err = c->err;
-        for (hvs_ctx* k : c->kids) (void)in_detach(k);
-        (void)hipGetLastError();
-        c->err = err;
-    }
-    return rc;
+    return commit_everywhere_or_detach_all(c, sh, [&](const Share& s, size_t r) { return in_commit(s.k, kCategorySets, plans[r]); });
 }
 
 int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, float* value, uint32_t cap)
@@ -6523,7 +6582,7 @@ int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, fl
     if (!c) return HVS_EINVAL;
     if (!c->kids.empty()) return fail(c, HVS_EINVAL, "hvs_download_in_plan: single-GPU contexts only");
     const HvsInSet& S = c->qs.in;
-    if (!S.active || S.kind != HvsInSet::Sets) return fail(c, HVS_ESTATE, "hvs_download_in_plan: no category sets are attached");
+    if (!S.active || S.client->kind != HvsInSet::Sets) return fail(c, HVS_ESTATE, "hvs_download_in_plan: no category sets are attached");
     const uint32_t nsub = c->nq;
     HVS_HIP(c, hipSetDevice(c->device));
     if (sub_offsets) HVS_HIP(c, hipMemcpyAsync(sub_offsets, S.d_sub_off, ((size_t)S.nuq + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -6537,7 +6596,7 @@ int hvs_download_in_plan(hvs_ctx* c, uint32_t* sub_offsets, uint32_t* parent, fl
 
 // ---- multi-vector queries (include/hvs.h "multi-vector queries") -----------------
 
-uint32_t hvs_vectors_check(const uint32_t* offsets, uint32_t nq) { return vec_check_core(offsets, nq); }
+uint32_t hvs_vectors_check(const uint32_t* offsets, uint32_t nq) { return vec_check_core(offsets, nq, HVS_VECTORS_MAX_EXTRA); }
 
 uint32_t hvs_vectors_plan(const uint32_t* ids, const float* dists, uint32_t m, uint32_t k, const uint32_t* pad_ids, const float* pad_dists, int padding,
                           uint32_t* out_ids, float* out_dists, uint32_t* n_duplicates)
@@ -6561,56 +6620,31 @@ uint32_t hvs_vectors_plan(const uint32_t* ids, const float* dists, uint32_t m, u
 
 int hvs_set_query_vectors(hvs_ctx* c, const uint32_t* vec_offsets, const float* vecs, uint32_t nq)
 {
-    static const char* const fn = "hvs_set_query_vectors";
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_vectors: not supported (yet) on a row-partitioned context");
-    if (!vec_offsets && !vecs) return on_every_leaf(c, vectors_detach);
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!vec_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_vectors: vec_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, vectors_detach);
-    return vectors_everywhere(c, vec_offsets, vecs, -1, nq, fn);
+    const int go = client_attach_begin(c, kQueryVectors, false, vec_offsets, !vec_offsets && !vecs, nq);
+    return go != kAttach ? go : expanded_everywhere(c, kQueryVectors, vec_offsets, {vecs, nullptr, -1}, nq, "hvs_set_query_vectors");
 }
 
 int hvs_set_query_vectors_device(hvs_ctx* c, const uint32_t* d_offsets, const float* d_vecs, uint32_t nq, void* stream)
 {
     static const char* const fn = "hvs_set_query_vectors_device";
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_vectors_device: not supported (yet) on a row-partitioned context");
-    if (!d_offsets && !d_vecs) return on_every_leaf(c, vectors_detach);
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!d_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_vectors_device: d_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, vectors_detach);
+    const int go = client_attach_begin(c, kQueryVectors, true, d_offsets, !d_offsets && !d_vecs, nq);
+    if (go != kAttach) return go;
     int dev = 0;
     if (int rc = check_device_buffers(c, d_offsets, d_vecs, stream, fn, &dev)) return rc;
-    return vectors_everywhere(c, d_offsets, d_vecs, dev, nq, fn);
+    return expanded_everywhere(c, kQueryVectors, d_offsets, {d_vecs, nullptr, dev}, nq, fn);
 }
 
 int hvs_query_vectors(hvs_ctx* c, const float* q_rows, const uint32_t* vec_offsets, const float* vecs, uint32_t nq, float sample_proportion,
                       uint32_t* out_ids, float* out_dists)
 {
-    if (!c) return HVS_EINVAL;
-    if (!vec_offsets && !vecs) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_vectors: not supported (yet) on a row-partitioned context");
-    if (!loaded_leaf(c, "hvs_query_vectors")) return HVS_ESTATE;
-    if (nq == 0u) return HVS_OK;
-    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_vectors: q_rows / out_ids is NULL");
-    // checked before the resident set is replaced: a refused call changes nothing
-    const uint32_t nsub = vec_check_core(vec_offsets, nq);
-    if (nsub == 0xFFFFFFFFu || (nsub > nq && !vecs))
-        return fail(c, HVS_EINVAL, "hvs_query_vectors: malformed offsets, more than HVS_VECTORS_MAX_EXTRA extra vectors on a query, or too many sub-queries");
-    int rc = hvs_upload_queries(c, q_rows, nq);
-    if (!rc) rc = hvs_set_query_vectors(c, vec_offsets, vecs, nq);
-    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
-    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
-    return rc;
+    return client_query(
+        c, kQueryVectors, !vec_offsets && !vecs, q_rows, nq, sample_proportion, out_ids, out_dists,
+        [&] { return csr_good(kQueryVectors, vec_offsets, {vecs, nullptr, -1}, nq); }, [&] { return hvs_set_query_vectors(c, vec_offsets, vecs, nq); });
 }
 
 int hvs_vectors_stats(hvs_ctx* c, hvs_vectors_info* out)
 {
-    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_vectors_stats: not supported (yet) on a row-partitioned context");
-    return call_stats<hvs_vectors_info>(c, out, leaf_vectors_stats, [](hvs_vectors_info& sum, const hvs_vectors_info& m) {
+    return client_stats(c, kQueryVectors, out, leaf_vectors_stats, [](hvs_vectors_info& sum, const hvs_vectors_info& m) {
         sum.multi_queries += m.multi_queries;
         sum.sub_queries += m.sub_queries;
         sum.max_vectors = std::max(sum.max_vectors, m.max_vectors);
@@ -6628,60 +6662,36 @@ uint32_t hvs_clauses_check(const uint32_t* offsets, uint32_t nq) { return vec_ch
 
 int hvs_set_query_clauses(hvs_ctx* c, const uint32_t* clause_offsets, const float* clause_attrs, const float* clause_vecs, uint32_t nq)
 {
-    static const char* const fn = "hvs_set_query_clauses";
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_clauses: not supported (yet) on a row-partitioned context");
-    if (!clause_offsets && !clause_attrs && !clause_vecs) return on_every_leaf(c, clauses_detach);
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!clause_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_clauses: clause_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, clauses_detach);
-    return vectors_everywhere(c, clause_offsets, clause_vecs, -1, nq, fn, HvsInSet::Clauses, clause_attrs);
+    const int go = client_attach_begin(c, kQueryClauses, false, clause_offsets, !clause_offsets && !clause_attrs && !clause_vecs, nq);
+    return go != kAttach ? go : expanded_everywhere(c, kQueryClauses, clause_offsets, {clause_vecs, clause_attrs, -1}, nq, "hvs_set_query_clauses");
 }
 
 int hvs_set_query_clauses_device(hvs_ctx* c, const uint32_t* d_offsets, const float* d_attrs, const float* d_vecs, uint32_t nq, void* stream)
 {
     static const char* const fn = "hvs_set_query_clauses_device";
-    if (!c) return HVS_EINVAL;
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_set_query_clauses_device: not supported (yet) on a row-partitioned context");
-    if (!d_offsets && !d_attrs && !d_vecs) return on_every_leaf(c, clauses_detach);
-    if (!loaded_leaf(c, fn)) return HVS_ESTATE;
-    if (!d_offsets) return fail(c, HVS_EINVAL, "hvs_set_query_clauses_device: d_offsets is NULL");
-    if (int rc = check_resident_count(c, nq, fn)) return rc;
-    if (nq == 0u) return on_every_leaf(c, clauses_detach);
+    const int go = client_attach_begin(c, kQueryClauses, true, d_offsets, !d_offsets && !d_attrs && !d_vecs, nq);
+    if (go != kAttach) return go;
     int dev = 0, dev3 = 0;
     if (d_vecs) {  // (the third buffer first: check_device_buffers ends with the wait for the producer)
         if (int rc = device_of_buffer(c, d_vecs, fn, &dev3)) return rc;
     }
     if (int rc = check_device_buffers(c, d_offsets, d_attrs, stream, fn, &dev)) return rc;
     if (d_vecs && dev3 != dev) return fail(c, HVS_EINVAL, "hvs_set_query_clauses_device: the buffers are on different GPUs");
-    return vectors_everywhere(c, d_offsets, d_vecs, dev, nq, fn, HvsInSet::Clauses, d_attrs);
+    return expanded_everywhere(c, kQueryClauses, d_offsets, {d_vecs, d_attrs, dev}, nq, fn);
 }
 
 int hvs_query_clauses(hvs_ctx* c, const float* q_rows, const uint32_t* clause_offsets, const float* clause_attrs, const float* clause_vecs,
                       uint32_t nq, float sample_proportion, uint32_t* out_ids, float* out_dists)
 {
-    if (!c) return HVS_EINVAL;
-    if (!clause_offsets && !clause_attrs && !clause_vecs) return hvs_query(c, q_rows, nq, sample_proportion, out_ids, out_dists);
-    if (c->partitioned) return fail(c, HVS_ESTATE, "hvs_query_clauses: not supported (yet) on a row-partitioned context");
-    if (!loaded_leaf(c, "hvs_query_clauses")) return HVS_ESTATE;
-    if (nq == 0u) return HVS_OK;
-    if (!q_rows || !out_ids) return fail(c, HVS_EINVAL, "hvs_query_clauses: q_rows / out_ids is NULL");
-    // checked before the resident set is replaced: a refused call changes nothing
-    const uint32_t nsub = hvs_clauses_check(clause_offsets, nq);
-    if (nsub == 0xFFFFFFFFu || (nsub > nq && !clause_attrs))
-        return fail(c, HVS_EINVAL, "hvs_query_clauses: malformed offsets, more than HVS_CLAUSES_MAX_EXTRA extra clauses on a query, too many sub-queries, or clause_attrs is NULL");
-    int rc = hvs_upload_queries(c, q_rows, nq);
-    if (!rc) rc = hvs_set_query_clauses(c, clause_offsets, clause_attrs, clause_vecs, nq);
-    if (!rc) rc = hvs_query_resident(c, 0u, nq, sample_proportion);
-    if (!rc) rc = hvs_download_results(c, 0u, nq, out_ids, out_dists);
-    return rc;
+    return client_query(
+        c, kQueryClauses, !clause_offsets && !clause_attrs && !clause_vecs, q_rows, nq, sample_proportion, out_ids, out_dists,
+        [&] { return csr_good(kQueryClauses, clause_offsets, {clause_vecs, clause_attrs, -1}, nq); },
+        [&] { return hvs_set_query_clauses(c, clause_offsets, clause_attrs, clause_vecs, nq); });
 }
 
 int hvs_clauses_stats(hvs_ctx* c, hvs_clauses_info* out)
 {
-    if (c && out && c->partitioned) return fail(c, HVS_ESTATE, "hvs_clauses_stats: not supported (yet) on a row-partitioned context");
-    return call_stats<hvs_clauses_info>(c, out, leaf_clauses_stats, [](hvs_clauses_info& sum, const hvs_clauses_info& m) {
+    return client_stats(c, kQueryClauses, out, leaf_clauses_stats, [](hvs_clauses_info& sum, const hvs_clauses_info& m) {
         sum.clause_queries += m.clause_queries;
         sum.sub_queries += m.sub_queries;
         sum.max_clauses = std::max(sum.max_clauses, m.max_clauses);

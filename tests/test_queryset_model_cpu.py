@@ -165,6 +165,76 @@ def test_row_k_changed_keeps_the_lists():
     assert lists(s) == lists(AMONG) and s.res is None
 
 
+# ---- the expanded set's three clients: the fact is (kind, tag) ----
+PREDICATES, WITH_VECTORS = ("P", False), ("W", True)                # clauses' tags say whether they bring vectors
+CLIENT_TAGS = {"sets": "S2", "vectors": "X", "clauses": PREDICATES}
+UNDER = {"sets": LISTED,                                            # everything that composes, under each client
+         "vectors": LISTED._replace(sets="X", kind="vectors", cursors=None),
+         "clauses": LISTED._replace(sets=PREDICATES, kind="clauses")}
+DROPPED = dict(caps=None, cursors=None, res=None, timed=False, excl=None, cand=None, qsets=None)
+
+
+def test_the_expanded_fact_is_kind_and_tag():
+    assert M.expanded(PLAIN_FULL) is None and M.expanded(EVERYTHING) == ("sets", "S")
+    assert M.expanded(UNDER["vectors"]) == ("vectors", "X") and M.expanded(UNDER["clauses"]) == ("clauses", PREDICATES)
+
+
+@pytest.mark.parametrize("was", M.CLIENTS)
+@pytest.mark.parametrize("client", M.CLIENTS)
+def test_row_a_client_attached_replaces_whichever_is(client, was):
+    tag = CLIENT_TAGS[client]
+    for s in (UNDER[was], AMONG):
+        assert go(s, (client, tag)) == s._replace(sets=tag, kind=client, **DROPPED)
+
+
+@pytest.mark.parametrize("was", M.CLIENTS)
+@pytest.mark.parametrize("client", M.CLIENTS)
+def test_row_a_client_detached(client, was):
+    s = UNDER[was]
+    if client == was:
+        assert go(s, (client, None)) == s._replace(sets=None, kind="sets", **DROPPED)
+    else:
+        assert go(s, (client, None)) == s                       # another client's detach: nothing dropped, the results stay
+    assert go(AMONG, (client, None)) == AMONG                   # ... and so while none is attached
+
+
+@pytest.mark.parametrize("client", M.CLIENTS)
+def test_row_a_refused_client_changes_nothing(client):
+    for s in (*UNDER.values(), AMONG, PLAIN_FULL, M.initial()):
+        assert M.step(s, ("bad_" + client,), NQ) == (s, M.EINVAL)
+        assert M.step(s, ("bad_" + client, "one list over the limit"), NQ) == (s, M.EINVAL)
+
+
+def test_row_cursors_under_the_clients():
+    several = (UNDER["vectors"], UNDER["vectors"]._replace(sets=WITH_VECTORS, kind="clauses"))
+    for s in several:
+        assert M.full(s)
+        assert M.step(s, ("after", "A2"), NQ) == (s, M.ESTATE)
+        assert M.step(s, ("after_from_results",), NQ) == (s, M.ESTATE)
+        t = s._replace(res=None)                                 # the state is asked before the values
+        assert M.step(t, ("after_from_results",), NQ) == (t, M.ESTATE)
+        assert go(s, ("after", None)) == s                       # removing is always allowed
+    for s in (UNDER["sets"], UNDER["clauses"]):
+        assert go(s, ("after", "A2")) == s._replace(cursors="A2")
+        assert go(s, ("after_from_results",)) == s._replace(cursors=M.FROM_RESULTS)
+
+
+@pytest.mark.parametrize("client", M.CLIENTS)
+def test_row_candidates_under_any_client(client):
+    s = UNDER[client]
+    assert M.step(s, ("candidates", "K"), NQ) == (s, M.ESTATE)
+    assert M.step(s, ("bad_candidates",), NQ) == (s, M.ESTATE)
+    assert go(s, ("candidates", None)) == s
+
+
+@pytest.mark.parametrize("client", M.CLIENTS)
+@pytest.mark.parametrize("call", [("upload", "Q2"), ("query", "short")])
+def test_row_resident_set_replaced_drops_the_client(call, client):
+    s = go(UNDER[client], call)
+    assert M.expanded(s) is None and s.kind == "sets"
+    assert (s.caps, s.cursors) == (None, None) and lists(s) == (None, None, None, "R")
+
+
 def test_unknown_call():
     with pytest.raises(ValueError):
         M.step(M.initial(), ("nonsense",))

@@ -4,6 +4,7 @@ what is attached; every answer of the walked context must be array_equal -- ids 
 single-GPU context given exactly that, the three per-call figures must be zero or non-zero as the model says, and
 hvs_set_after_from_results must succeed exactly when the model says every query has a result row.  A second walk does the same
 for what takes the staged attach: exclusion lists, candidate lists, the shared row sets and the queries' indices into them.
+A third walks the expanded set's three clients -- category sets, extra query vectors, extra clauses -- through each other.
 
 Data: in_sets.small(), 901 rows and 80 queries; padding off throughout (hvs_set_after_from_results needs it)."""
 import importlib
@@ -67,7 +68,7 @@ LISTS = [
     ("row_sets", "R2"), ("after_from_results",), ("run", 0, 80),           # the sets replaced: indices and results go, the lists stay
     ("query_sets", "I1"), ("exclude", "E2"), ("candidates", "K2"), ("run", 0, 80),   # all three
     ("set_k", 100), ("run", 0, 80),
-    ("sets", "S"), ("run", 0, 80),                                         # sets_changed drops all three
+    ("sets", "S"), ("run", 0, 80),                                         # expanded_changed drops all three
     ("candidates", "K1"), ("bad_candidates",), ("candidates", None),       # ... and refuses candidate lists while attached
     ("exclude", "E1"), ("query_sets", "I1"), ("caps", "C2"), ("run", 0, 80),   # under the expanded set: the user's, per sub-query
     ("bad_exclude",), ("bad_query_sets",), ("after_from_results",), ("run", 0, 80),
@@ -86,6 +87,37 @@ SHORT_LISTS = [
 SHORT_LISTS_SETS = [
     ("exclude", "E2"), ("sets", "S"), ("run", 0, 80), ("candidates", "K1"),
     ("exclude", "E1"), ("query_sets", "I1"), ("run", 0, 80), ("sets", None), ("run", 0, 80),
+]
+# the third walk: the clients' rows of the table, on one GPU ...
+P1, V1 = ("P1", False), ("V1", True)                                       # clauses' tags: (name, they bring vectors)
+CLIENTS = [
+    ("upload", "Q"), ("run", 0, 80), ("vectors", "X1"), ("after_from_results",), ("run", 0, 80),   # attached: the results are gone
+    ("after", "A1"), ("after_from_results",), ("after", None),             # a row has several keys: cursors refused, removal allowed
+    ("candidates", "K1"), ("bad_candidates",),                             # ... and candidate lists, under any client
+    ("bad_vectors", "long"), ("bad_vectors", "descending"), ("sets", None), ("clauses", None),
+    ("after_from_results",), ("run", 20, 30),                              # refusals and the others' detach: nothing dropped
+    ("caps", "C1"), ("exclude", "E1"), ("run", 0, 80),
+    ("clauses", P1), ("run", 0, 80),                                       # clauses replace vectors: caps and lists are gone
+    ("candidates", "K1"), ("after_from_results",), ("run", 0, 80),         # predicate-only: a row has one key, cursors allowed
+    ("vectors", None), ("sets", None), ("bad_clauses", "long"), ("bad_clauses", "descending"), ("bad_sets",), ("run", 0, 80),
+    ("clauses", V1), ("after_from_results",), ("run", 0, 80),              # clauses replace clauses; with vectors: cursors refused
+    ("after", "A1"), ("after_from_results",), ("exclude", "E2"), ("run", 10, 60),
+    ("sets", "S"), ("caps", "C2"), ("run", 0, 80), ("after_from_results",), ("run", 0, 80),   # sets replace clauses
+    ("bad_vectors", "long"), ("bad_clauses", "descending"), ("clauses", None), ("run", 0, 80),
+    ("vectors", "X2"), ("candidates", "K1"), ("run", 0, 80),               # vectors replace sets
+    ("vectors", None), ("after_from_results",), ("run", 0, 80),            # its own detach: dropped, plain answers
+    ("vectors", None), ("clauses", None), ("sets", None), ("after_from_results",), ("run", 0, 80),   # none attached: no-ops
+    ("clauses", V1), ("upload", "Q2"), ("run", 0, 80),                     # a replaced resident set drops the client
+    ("vectors", "X1"), ("query", "Q"), ("after_from_results",), ("run", 0, 80),
+    ("clauses", P1), ("run", 0, 80), ("clauses", None), ("run", 0, 80),
+]
+# ... and in a short form on the replicated two-leaf contexts
+SHORT_CLIENTS = [
+    ("upload", "Q"), ("vectors", "X1"), ("run", 0, 80), ("after", "A1"), ("bad_vectors", "long"), ("sets", None), ("run", 20, 30),
+    ("clauses", P1), ("caps", "C1"), ("run", 0, 80), ("after_from_results",), ("bad_clauses", "descending"), ("vectors", None), ("run", 0, 80),
+    ("clauses", V1), ("after_from_results",), ("candidates", "K1"), ("run", 0, 80),
+    ("sets", "S"), ("bad_sets",), ("run", 0, 80), ("vectors", "X2"), ("run", 0, 80), ("vectors", None), ("run", 0, 80),
+    ("clauses", V1), ("query", "Q"), ("after_from_results",), ("run", 0, 80),
 ]
 
 
@@ -119,7 +151,19 @@ def make_values():
     too_long, descending = off.copy(), off.copy()
     too_long[-1] = too_long[-2] + PKG.EXCLUDE_MAX + 1
     descending[40] = descending[39] - 1
-    return {"nodes": nodes, "Q": queries, "Q2": np.ascontiguousarray(queries[::-1]), "S": sets, "S2": sets[3:] + sets[:3],
+    # the clients' values: extra vectors are rows of D; a refused CSR has one list over the limit, or one descending offset
+    rows = lambda m: nodes[rng.integers(0, n, m), 2:].copy()
+    preds = np.array([[2, 0, 0.2, 0.6], [1, 3, -1, -1]], np.float32)
+    one, bad = np.arange(nq + 1, dtype=np.uint32), {}
+    for kind, limit, width in (("vectors", PKG.VECTORS_MAX_EXTRA, 100), ("clauses", PKG.CLAUSES_MAX_EXTRA, 4)):
+        too_many, down = one.copy(), one.copy()
+        too_many[30:] += limit
+        down[40] = down[39] - 1
+        bad[kind] = {"long": (too_many, np.zeros((int(too_many[-1]), width), np.float32)), "descending": (down, np.zeros((nq, width), np.float32))}
+    clients = {"X1": [rows(q % 4) for q in range(nq)], "X2": [rows((q + 2) % 4) for q in range(nq)],
+               P1: ([preds[:q % 3] for q in range(nq)], None), V1: ([preds[q % 2:q % 2 + 1] for q in range(nq)], [rows(1) for q in range(nq)]),
+               "bad_vectors": bad["vectors"], "bad_clauses": bad["clauses"]}
+    return {**clients, "nodes": nodes, "Q": queries, "Q2": np.ascontiguousarray(queries[::-1]), "S": sets, "S2": sets[3:] + sets[:3],
             "C1": caps(4), "C2": caps(6), "A1": (d[:, 2].copy(), ids[:, 2].copy()),
             "bad": sets[:-1] + [list(range(65))],
             "E1": [ids[q, :3] for q in range(nq)], "E2": [np.concatenate([ids[q, 1:6], pick(q % 7)]) for q in range(nq)],
@@ -148,7 +192,7 @@ def fresh_answer(engine, V, s, cursors, q0, nq):
         if s.rsets is not None:
             f.set_row_sets(V[s.rsets])
         if s.sets is not None:
-            f.set_category_sets(V[s.sets])
+            attach_client(f, s.kind, V[s.sets])
         if s.excl is not None:
             f.set_exclude_ids(V[s.excl])
         if s.cand is not None:
@@ -162,6 +206,14 @@ def fresh_answer(engine, V, s, cursors, q0, nq):
         f.query_resident(q0, nq, 1.0)
         f.sync()
         return f.download_results(q0, nq)
+
+
+def attach_client(e, kind, value):
+    """the setter of the expanded set's client `kind`; value None: its detach"""
+    if kind == "clauses":
+        e.set_query_clauses(*(value or (None,)))
+    else:
+        (e.set_category_sets if kind == "sets" else e.set_query_vectors)(value)
 
 
 ATTACH = {"exclude": "set_exclude_ids", "candidates": "set_candidate_ids", "row_sets": "set_row_sets", "query_sets": "set_query_row_sets"}
@@ -190,10 +242,14 @@ def walk(e, engine, V, calls, s=None, check_timing=True, check_sets=True):
             else:
                 got = e.query(V[call[1]], 1.0)
                 rc, q0, nq = M.OK, 0, nq_of[call[1]]
-        elif op == "sets":
-            rc = code_of(lambda: e.set_category_sets(None if call[1] is None else V[call[1]]))
+        elif op in M.CLIENTS:
+            rc = code_of(lambda: attach_client(e, op, None if call[1] is None else V[call[1]]))
         elif op == "bad_sets":
             rc = code_of(lambda: e.set_category_sets(V["bad"]))
+        elif op == "bad_vectors":
+            rc = code_of(lambda: e.set_query_vectors(V[op][call[1]]))
+        elif op == "bad_clauses":
+            rc = code_of(lambda: e.set_query_clauses(V[op][call[1]]))
         elif op == "caps":
             rc = code_of(lambda: e.set_max_dist2(None if call[1] is None else V[call[1]]))
         elif op == "after":
@@ -201,7 +257,7 @@ def walk(e, engine, V, calls, s=None, check_timing=True, check_sets=True):
         elif op == "after_from_results":
             rows = e.download_results(0, s.nq) if M.full(s) else None      # (reads only: the cursors a success attaches)
             rc = code_of(e.set_after_from_results)
-            assert (rc == M.OK) == M.full(s), f"{what}: hvs_set_after_from_results returned {rc}"
+            assert (rc == M.OK) == (M.full(s) and not M.many_keys(s)), f"{what}: hvs_set_after_from_results returned {rc}"
         elif op == "set_k":
             rc = code_of(lambda: e.set_k(call[1]))
         elif op in ATTACH:
@@ -228,8 +284,8 @@ def walk(e, engine, V, calls, s=None, check_timing=True, check_sets=True):
             assert (w.capped_queries != 0) == (s.caps is not None), f"{what}: {w.as_dict()}"
             assert (a.cursor_queries != 0) == (s.cursors is not None), f"{what}: {a.as_dict()}"
             if check_sets:
-                n = e.in_stats()
-                assert (n.sub_queries != 0) == (s.sets is not None), f"{what}: {n.as_dict()}"
+                for kind, n in (("sets", e.in_stats()), ("vectors", e.vector_stats()), ("clauses", e.clause_stats())):
+                    assert (n.sub_queries != 0) == (M.expanded(s) is not None and s.kind == kind), f"{what}: {kind} {n.as_dict()}"
             x, k = e.exclude_stats(), e.candidates_stats()
             assert (x.excluding_queries != 0) == (s.excl is not None), f"{what}: {x.as_dict()}"
             assert (k.listed_queries != 0) == (s.cand is not None), f"{what}: {k.as_dict()}"
@@ -279,3 +335,36 @@ def test_walk_lists_on_two_leaves(values, partition, devices):
         s = walk(e, AUTO, values, SHORT_LISTS, check_timing=False, check_sets=not partition)
         if not partition:
             walk(e, AUTO, values, SHORT_LISTS_SETS, s, check_timing=False)
+
+
+@pytest.mark.parametrize("engine", [EXACT, AUTO])
+def test_walk_clients(values, engine):
+    with prepared(PKG.Engine(0), engine, values["nodes"], 8) as e:
+        s = walk(e, engine, values, CLIENTS)
+    assert (s.k, s.queries, M.expanded(s)) == (8, "Q", None)
+
+
+@pytest.mark.parametrize("devices", [[0, 0], TWO_GPUS], ids=["two leaves on GPU 0", "two GPUs"])
+def test_walk_clients_on_two_leaves(values, devices):
+    if max(devices) >= torch.cuda.device_count():
+        pytest.skip("needs two GPUs")
+    with prepared(PKG.Engine(devices=devices), AUTO, values["nodes"], 8) as e:
+        s = walk(e, AUTO, values, SHORT_CLIENTS, check_timing=False)
+    assert M.expanded(s) is None
+
+
+def test_partitioned_refuses_the_clients(values):
+    """a row-partitioned context refuses all three clients (HVS_ESTATE) and is left as it was"""
+    with prepared(PKG.Engine(devices=[0, 0], partition=True), AUTO, values["nodes"], 8) as e:
+        e.upload_queries(values["Q"])
+        e.query_resident(0, 80, 1.0)
+        e.sync()
+        before = e.download_results(0, 80)
+        for kind, tag in (("sets", "S"), ("vectors", "X1"), ("clauses", V1)):
+            assert code_of(lambda: attach_client(e, kind, values[tag])) == M.ESTATE, kind
+        same(e.download_results(0, 80), before, "the results the refusals left")
+        assert code_of(e.set_after_from_results) == M.OK                   # ... with every query's row still there
+        e.query_resident(0, 80, 1.0)
+        e.sync()
+        same(e.download_results(0, 80), fresh_answer(AUTO, values, M.State("Q", 80, None, None, M.FROM_RESULTS, 8, (0, 80)),
+                                                     (before[1][:, 7].copy(), before[0][:, 7].copy()), 0, 80), "page 2 after the refusals")
