@@ -1103,7 +1103,9 @@ uint32_t hvs_candidates_plan(const uint32_t *offsets, const uint32_t *ids, uint3
  * hvs_row_sets_stats: n_sets, words_per_set (u64 words) and bytes (device memory of one GPU) of the sets loaded; and of the last
  * call, all zero for a call without indices: restricted_queries (queries answered whose index is not 0xFFFFFFFF; under the
  * expanded set counted per sub-query, as the slots are), refused_keys (keys that every other test admitted and the set refused,
- * at any admission point: a lower bound is the number of such keys in front of the k-th kept one), kept_slots (non-pad slots
+ * at any admission point: a lower bound is the number of such keys in front of the k-th kept one; for the thresholds of the run
+ * the exact value is pinned by the host model of tests/selectivity_model.py, "Row sets", which tests/test_filter_selectivity.py
+ * asserts equal on every filter engine -- a key that is listed AND outside the set counts for the list alone), kept_slots (non-pad slots
  * written) and underfull_queries (queries with fewer than k of them; row-partitioned: the rules of hvs_exclude_stats).  Keys
  * refused by a set and keys refused by an exclusion list are counted apart: hvs_exclude_stats reports what it reported before.
  * hvs_row_sets_compact_plan: pure host arithmetic, no GPU and no context: the sets as they must be after hvs_compact under the

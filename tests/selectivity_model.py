@@ -41,7 +41,7 @@ and `hi` est >= theta - mu_q, theta rounded down to f32 as the kernel does.
 Grid edges.  The device takes log2((b - a) / seen) with __log2f; a query whose 8 log2(.) - 0.02 lies within 1e-3 of an integer
 at any level where the guess table is consulted is `excluded`: the model cannot say which grid point the device read.
 
-Attachments (walk's caps=, after=, live=, excl=; all None: the walk above, to the unit).  Each rule with the code it restates:
+Attachments (walk's caps=, after=, live=, excl=, sets=; all None: the walk above, to the unit).  Each rule with the code it restates:
 
 Caps.
 * hvs_k_norm_caps stores hvs_norm_cap(cap) (`c >= 0.0f ? c : HVS_CAP_NOTHING`): a NaN or negative cap is -1.  hvs_k_prep<true>
@@ -102,12 +102,40 @@ Lists (walk's excl=, one raw id array per query).
   tests/test_filter_bounds.py; level 0 of the chunked seed takes no tau test), whose id is listed.  A query that the exact engine
   answers contributes nothing here (its refusals are counted through HVS_CNT_RERUN_SINK: slot 26).
 
+Row sets (walk's sets= (member bool [n_sets, n], idx u32 [nq]); idx[q] == 0xFFFFFFFF: no restriction, _pass gets None).
+* Admission is the old test AND "member", evaluated after the list and only for a key that tau, cap, cursor and list have admitted
+  (hvs_refuse_listed: "the list first (its refusals stay what they were), then the query's row set" -- `if (hvs_excluded(...)) {
+  atomicAdd(hvs_refused_slot(), 1u); return true; }  if (hvs_in_row_set(x, qi, id)) return false;  atomicAdd(hvs_set_refused_slot(),
+  1u); return true;`).  The places are the lists': the chunked hvs_k_seed_exact at level 0, no tau test (`bool admit = pass && key >=
+  key_lo;` then `if (admit && hvs_refuse_listed(excl, qi, id)) admit = false;`), hvs_k_rescore behind `dist <= B.tau[slot[u]]` and
+  the cursor (`if (pend[u] && hvs_refuse_listed(hvs_second_arg(after_lo...), qa, id[u])) pend[u] = false;`), and hvs_keep_unlisted
+  in the final kernel (`!hvs_excluded(lst, n, hvs_key_id(key)) && hvs_in_row_set(x, qi, hvs_key_id(key))`), which drops non-members
+  too and refuses nothing.
+* `set_refused` [nq], kept apart from `refused`, first pass plus retry pass: what hvs_set_refused_slot collects and hvs_count_refused
+  hands to HVS_CNT_SET_REFUSED (hvs_row_sets_info.refused_keys) -- keys in the range, `id < sn`, live, behind the cursor, `dist <=
+  tau` at levels >= 1, not listed, and outside the query's set.  A key that is listed AND outside the set goes to `refused` only
+  (`both` counts those: the order of the two tests is visible in them alone).
+* rescored_pairs is counted before admission (`npairs += cnt` in front of score_list), unchanged.  hvs_guess_m and
+  hvs_rows_seen_before see ra, rb only: F is not thinned by the set -- a level's order statistic is drawn for "k matches" of the
+  whole range, and a sparse set holds fewer than m keys at the level (tau stands) or an m-th key far out.
+* The retry pass runs the same forms with the same argument (excl_arg: `if (has_rset(c)) { x.set_of = s.eng.d_set_of; ...`, and
+  `set_of` is indexed by the resident query, B.qid, like the lists): proven over the member keys.
+* Sets without lists run the EXCL forms with empty lists for every query (`if (!s.excl.set) x.begin = x.count = x.ids =
+  s.d_rs_zero;`) and, without cursors, an after_lo of zeros (zero_after_lo): cand[0] counts one place per admitted member, as
+  under lists.  A query whose index is 0xFFFFFFFF runs the same forms (`if (s == 0xFFFFFFFFu) return true;`) and walks as without sets.
+* A dead non-member fails the liveness test first (`if (!hvs_row_live(live, id)) continue;`, `ok[u] = ok[u] && !dead`) and is not
+  refused; its tile entry stays patched, the tiles carry no membership.
+* A query that the exact engine answers contributes nothing here (its refusals are counted through the sink: slot 36,
+  HVS_CNT_RERUN_SINK_SET_REFUSED, which leaf_row_sets_stats adds to slot 32).
+
 Wrong rules (walk's wrong=, one of WRONG; tests/test_selectivity_model_cpu.py shows that each would be seen): cap_ignored (tau
 starts at +inf, the final kernel still drops), cap_retry_from_inf, cap_check_inf (`tau == +inf` in the capped check),
 cap_level1_only (theta falls back to "keep everything" behind a merge that returned early), after_in_lists, after_F_behind,
 mask_unpatched, mask_F_live, mask_in_stat, excl_in_lists (listed keys enter the lists and the order statistics, only the final
 kernel drops them), excl_seed_only (level 0 refuses, hvs_k_rescore does not), excl_retry_dropped (the retry pass runs without
-lists).
+lists); set_in_lists, set_seed_only, set_retry_dropped (the same three of the sets), set_before_list (the set is tested in front of
+the list: a listed non-member is booked on the set's counter), set_F_members (hvs_guess_m is fed the members in the range and the
+members seen -- what DESIGN 9 item 11 proposes).
 """
 from __future__ import annotations
 
@@ -377,8 +405,10 @@ HVS_I8_PAD_NORM = -(1 << 30)
 HVS_CAP_NOTHING = np.float32(-1.0)
 HVS_AFTER_NOTHING = 0xFFFFFFFFFFFFFFFF
 NAN_BITS = 0x7FC00000
+SET_NONE = 0xFFFFFFFF
 WRONG = ("cap_ignored", "cap_retry_from_inf", "cap_check_inf", "cap_level1_only", "after_in_lists", "after_F_behind", "mask_unpatched",
-         "mask_F_live", "mask_in_stat", "excl_in_lists", "excl_seed_only", "excl_retry_dropped")
+         "mask_F_live", "mask_in_stat", "excl_in_lists", "excl_seed_only", "excl_retry_dropped", "set_in_lists", "set_seed_only",
+         "set_retry_dropped", "set_before_list", "set_F_members")
 
 
 def norm_cap(c):
@@ -413,20 +443,27 @@ def _f32_bits(x):
     return int(np.array([x], np.float32).view(np.uint32)[0])
 
 
-def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None, live=None, wrong=None, retry=False, listed=None):
-    """One batch's walk of query q: dict(lo, hi, dead_lo, dead_hi [K], cand [K + 1], fails, overflow, edge, keys, refused).
-    cap: the query's cap as the caller gave it, or None; lo_key: hvs_after_lo of its cursor, or None; live: bool [n], or None;
-    listed: the query's normalised exclusion list (ascending ids), or None."""
+def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None, live=None, wrong=None, retry=False, listed=None,
+          member=None):
+    """One batch's walk of query q: dict(lo, hi, dead_lo, dead_hi [K], cand [K + 1], fails, overflow, edge, keys, refused,
+    set_refused, both).  cap: the query's cap as the caller gave it, or None; lo_key: hvs_after_lo of its cursor, or None; live: bool
+    [n], or None; listed: the query's normalised exclusion list (ascending ids), or None; member: bool [n], the query's row set, or
+    None."""
     ordn, a, b = P.ranges[q]
     K = L.K
     out = dict(lo=np.zeros(K, np.int64), hi=np.zeros(K, np.int64), dead_lo=np.zeros(K, np.int64), dead_hi=np.zeros(K, np.int64),
-               cand=np.zeros(K + 1, np.int64), fails=False, overflow=False, edge=False, keys=np.empty(0, np.uint64), refused=0)
+               cand=np.zeros(K + 1, np.int64), fails=False, overflow=False, edge=False, keys=np.empty(0, np.uint64), refused=0,
+               set_refused=0, both=0, ent=np.zeros(K, np.int64))
     if retry and wrong == "excl_retry_dropped":
         listed = None
+    if retry and wrong == "set_retry_dropped":
+        member = None
     if P.hopeless[q] or b <= a:
         return out
     ids = (P.ord.perm_t if ordn else P.ord.perm_ct)[a:b]
-    lvl = L.block_level(np.arange(a, b) // 32)
+    pos = np.arange(a, b)
+    lvl = L.block_level(pos // 32)
+    lane_rows = (pos // 32) * 4 + (pos % 16) // 4            # hvs_entry16_pos: the 8 rows one I8X16 survivor entry can name
     dist, score = P.dist[q, ids], P.score[q, ids]
     keys = make_keys(dist, ids)
     alive = np.ones(ids.size, bool) if live is None else live[ids]
@@ -439,6 +476,7 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
     if wrong != "after_in_lists":
         adm = adm & behind
     named = np.zeros(ids.size, bool) if listed is None else np.isin(ids, listed)       # hvs_excluded
+    outside = np.zeros(ids.size, bool) if member is None else ~member[ids]              # !hvs_in_row_set
     capf = None if cap is None else norm_cap(cap)
     walk_cap = capf                                       # the cap as far as thresholds and the final check know it
     if wrong == "cap_ignored" or (retry and wrong == "cap_retry_from_inf"):
@@ -454,15 +492,24 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
             s_at = score[at]
             out["lo"][j - 1] = int((s_at >= th + w).sum())
             out["hi"][j - 1] = int((s_at >= th - w).sum())
+            out["ent"][j - 1] = np.unique(lane_rows[at][s_at >= th - w]).size
             d_at = score[at & ~alive]
             out["dead_lo"][j - 1] = int((d_at >= th + w).sum())
             out["dead_hi"][j - 1] = int((d_at >= th - w).sum())
         # every test in front of the list, then the list (level 0: the chunked seed takes no threshold test)
         refuses = wrong != "excl_in_lists" and not (j > 0 and wrong == "excl_seed_only")
+        set_refuses = wrong != "set_in_lists" and not (j > 0 and wrong == "set_seed_only")
         asked = at & adm if j == 0 else at & adm & (dist <= tau)
-        if refuses:
-            out["refused"] += int((asked & named).sum())
-        adm_j = adm & ~named if refuses else adm
+        by_list = named if refuses else np.zeros(ids.size, bool)
+        by_set = outside if set_refuses else np.zeros(ids.size, bool)
+        if wrong == "set_before_list":
+            by_list = by_list & ~by_set
+        else:                           # hvs_refuse_listed: the list first, then the query's row set
+            by_set = by_set & ~by_list
+        out["refused"] += int((asked & by_list).sum())
+        out["set_refused"] += int((asked & by_set).sum())
+        out["both"] += int((asked & named & outside).sum())
+        adm_j = adm & ~by_list & ~by_set
         within = at & adm_j & (dist <= tau)
         # level 0: the chunked seed (a batch of 112 queries: seed_chunks > 1) appends without a threshold test
         out["cand"][j] = int((at & adm_j).sum()) if j == 0 else int(within.sum())
@@ -476,6 +523,8 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
                     counted = (int(alive.sum()), int((alive & (lvl < j + 1)).sum()))
                 elif wrong == "after_F_behind":
                     counted = (int(behind.sum()), int((behind & (lvl < j + 1)).sum()))
+                elif wrong == "set_F_members" and member is not None:
+                    counted = (int((~outside).sum()), int((~outside & (lvl < j + 1)).sum()))
                 m, edge = guess_m(L, j + 1, a, b, k, guess, pfail, mid, counted)
                 out["edge"] |= edge
                 if held.size >= m:
@@ -494,6 +543,8 @@ def _pass(P, L, q, k, sn, guess, pfail, mid, scale, fcap, cap=None, lo_key=None,
         held = held[held >= np.uint64(lo_key)]
     if listed is not None:              # hvs_keep_unlisted
         held = held[~np.isin(key_ids(held), listed)]
+    if member is not None:              # ... which tests the row set too
+        held = held[member[key_ids(held)]]
     out["keys"] = held
     return out
 
@@ -518,19 +569,23 @@ def mask_cut(live, sp, n):
 
 
 def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS_FCAP, prep=None, plan=None, caps=None, after=None,
-         live=None, wrong=None, excl=None):
+         live=None, wrong=None, excl=None, sets=None):
     """The model of one call.  Returns a dict of per-query arrays:
       lo, hi [nq, K]      survivor bracket per level of the first pass;      cand [nq, K + 1] keys appended per level
       dead_lo, dead_hi    the part of lo, hi that dead rows make up (hvs_mask_info.dead_survivors)
+      ent [nq, K]         survivor entries of the rows counted in `hi`, at most: an entry (hvs_entry16_make; the 16-row entries of the
+                          other formats are unions of two) names 8 rows of a block, so a run of survivors takes an eighth of its length
       fails [nq]          the final check sends the query to a retry batch;  overflow [nq] a list above `fcap` does
       retry_lo, retry_hi, retry_dead_lo, retry_dead_hi   the same brackets for the retry pass of the retried queries (zero elsewhere)
       excluded [nq]       on a grid edge of the guess table;                 exact [nq] answered by the exact engine
       held                list of the final held distances per query (the k smallest of its range when verified)
       held_keys           ... as keys (distance bits << 32 | id): the answer's matched slots, in key order
       refused [nq]        keys the lists refused at an admission point, first pass plus retry pass (hvs_exclude_info.refused_keys)
+      set_refused [nq]    keys the row sets refused there (hvs_row_sets_info.refused_keys);  both [nq] keys asked for that are listed
+                          AND outside the set (in `refused`, not in `set_refused`)
     guess: "proven" (HVS_GUESS_MID=256) or "guess" with `pfail` (None: the batch's default) and `mid` (HVS_GUESS_MID).
-    caps [nq] f32, after = (dists [nq], ids [nq]), live bool [n], excl = one raw id array per query: the attachments; wrong: one
-    of WRONG (the CPU test only)."""
+    caps [nq] f32, after = (dists [nq], ids [nq]), live bool [n], excl = one raw id array per query, sets = (member bool [n_sets, n],
+    idx u32 [nq], 0xFFFFFFFF = no restriction): the attachments; wrong: one of WRONG (the CPU test only)."""
     assert wrong is None or wrong in WRONG, wrong
     P = prep if prep is not None else Prepared(fmt, nodes, queries)
     L = levels(P.n, plan=plan)
@@ -541,24 +596,27 @@ def walk(fmt, nodes, queries, k, sp, guess, pfail, mid, band_scale=1.0, fcap=HVS
     nq, K = P.nq, L.K
     z = lambda *s: np.zeros(s, np.int64)
     res = dict(lo=z(nq, K), hi=z(nq, K), cand=z(nq, K + 1), retry_lo=z(nq, K), retry_hi=z(nq, K), retry_cand=z(nq, K + 1),
-               dead_lo=z(nq, K), dead_hi=z(nq, K), retry_dead_lo=z(nq, K), retry_dead_hi=z(nq, K),
+               dead_lo=z(nq, K), dead_hi=z(nq, K), retry_dead_lo=z(nq, K), retry_dead_hi=z(nq, K), ent=z(nq, K), retry_ent=z(nq, K),
                fails=np.zeros(nq, bool), overflow=np.zeros(nq, bool), excluded=np.zeros(nq, bool), exact=P.hopeless.copy(), held=[],
-               held_keys=[], K=K, sn=sn, refused=z(nq))
+               held_keys=[], K=K, sn=sn, refused=z(nq), set_refused=z(nq), both=z(nq))
     for q in range(nq):
         att = dict(cap=None if caps is None else caps[q], lo_key=None if after is None else after_lo(after[0][q], after[1][q]),
-                   live=live, wrong=wrong, listed=None if excl is None else normalised(excl[q]))
+                   live=live, wrong=wrong, listed=None if excl is None else normalised(excl[q]),
+                   member=None if sets is None or int(sets[1][q]) == SET_NONE else np.asarray(sets[0][int(sets[1][q])], bool))
         r = _pass(P, L, q, k, sn, guess, pfail, mid, band_scale, fcap, **att)
-        for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
+        for name in ("lo", "hi", "cand", "dead_lo", "dead_hi", "ent"):
             res[name][q] = r[name]
         res["fails"][q], res["overflow"][q], res["excluded"][q] = r["fails"], r["overflow"], r["edge"]
-        res["refused"][q] = r["refused"]
+        for name in ("refused", "set_refused", "both"):
+            res[name][q] = r[name]
         keys = r["keys"]
         if r["fails"] or r["overflow"]:     # retry batch: proven at every level (plan_guess(k, true, .)), longer lists
             r2 = _pass(P, L, q, k, sn, "proven", pfail, mid, band_scale, 1 << 30, retry=True, **att)
             assert wrong is not None or not r2["fails"], "a proven threshold cannot fail its check"
-            for name in ("lo", "hi", "cand", "dead_lo", "dead_hi"):
+            for name in ("lo", "hi", "cand", "dead_lo", "dead_hi", "ent"):
                 res["retry_" + name][q] = r2[name]
-            res["refused"][q] += r2["refused"]
+            for name in ("refused", "set_refused", "both"):
+                res[name][q] += r2[name]
             keys = r2["keys"]
         res["held_keys"].append(keys)
         res["held"].append(key_dists(keys))
@@ -675,7 +733,7 @@ def case_walk(case, fmt, regime, band_scale=1.0, attach=None, wrong=None):
         att = attachment(case, attach) if attach else {}
         _walk_cache[key] = walk(fmt, nodes, queries, case.k, case.sp, r["guess"], r["pfail"], r["mid"], band_scale,
                                 list_capacity(RESERVE_NQ, queries.shape[0]), prep=case_prep(case, fmt), caps=att.get("caps"),
-                                after=att.get("after"), live=att.get("live"), wrong=wrong, excl=att.get("excl"))
+                                after=att.get("after"), live=att.get("live"), wrong=wrong, excl=att.get("excl"), sets=att.get("sets"))
     return _walk_cache[key]
 
 
@@ -683,8 +741,13 @@ def case_walk(case, fmt, regime, band_scale=1.0, attach=None, wrong=None):
 
 ATTACH = ("cap_kth", "cap_mixed", "after_p2", "after_deep", "mask", "cap_after", "all")
 EXCL_ATTACH = ("ex_p1", "ex_deep", "ex_scatter", "ex_all")          # the attachments with exclusion lists
-ATTACH = ATTACH + EXCL_ATTACH
+RSET_ATTACH = ("rs_half", "rs_sparse", "rs_ranges", "rs_edges", "rs_page1", "rs_list", "rs_all")    # ... with shared row sets
+ATTACH = ATTACH + EXCL_ATTACH + RSET_ATTACH
 EXCLUDE_MAX = 1024
+ROW_SETS_MAX = 256
+RSET_SEED = {"rs_half": 1801, "rs_sparse": 1802}      # the random sets: four bitmaps from a fixed seed each
+RSET_SHARE = {"rs_half": 0.5, "rs_sparse": 0.1}
+RSET_RANGE_ROWS = 2048                                # rs_ranges: set s holds the rows with (id // 2048) % 4 == s
 # what the GPU test runs under attachments: (case, formats, attachments, regimes, HVS_I8_SHAPE, the band x 1.25 build)
 ATTACH_MATRIX = [
     ("v1_32k", ALL_I8, ATTACH, ("proven", "default", "reckless"), "16", False),
@@ -701,6 +764,16 @@ ATTACH_MATRIX = [
     # the four far queries of `out` go to the exact engine: the re-run sink's refused keys (counter slot 26) are in the sum
     ("out", (BM.PLAIN_I8,), ("ex_p1",), ("proven", "reckless"), "16", False),
     ("v1_32k", (BM.PLAIN_I8, BM.BF16), ("ex_p1",), ("default",), "16", True),
+    ("v1_32k", ALL_I8, RSET_ATTACH, ("proven", "default", "reckless"), "16", False),
+    ("v1_32k", (BM.PLAIN_I8,), ("rs_half",), ("default",), "32", False),
+    ("v1_70k", (BM.PLAIN_I8,), ("rs_sparse", "rs_ranges", "rs_all"), ("default", "reckless"), "16", False),
+    # (n = 32768 is a multiple of 64: only here does the all-ones set of rs_edges have bits past n to be dirty)
+    ("v1_70k", (BM.PLAIN_I8,), ("rs_edges",), ("default",), "16", False),
+    ("half", (BM.PLAIN_I8,), ("rs_half",), ("default",), "16", False),
+    ("f16", (BM.FP16,), ("rs_half",), ("default",), "16", False),
+    # the far queries' set refusals reach hvs_row_sets_info through the re-run sink (counter slot 36)
+    ("out", (BM.PLAIN_I8,), ("rs_half",), ("proven", "reckless"), "16", False),
+    ("v1_32k", (BM.PLAIN_I8, BM.BF16), ("rs_half",), ("default",), "16", True),
 ]
 
 
@@ -722,6 +795,7 @@ CAP_KINDS = ("below_nearest", "quarter", "above_quarter", "kth", "inf", "3e38", 
 EXHAUSTED = (np.float32(np.inf), np.uint32(0xFFFFFFFF))
 MASK_SEED, MASK_SHARE, MASK_NEAR_QUERIES, MASK_BLOCK_QUERIES = 4242, 0.15, range(0, 16), range(64, 72)
 ALL_CAP_RANK = 3             # `all`: the cap is the (3 k)-th matched distance, see attachment()
+RS_ALL_CAP_RANK = 8          # `rs_all`: the (8 k)-th, see attachment()
 
 _full_cache, _attach_cache = {}, {}
 
@@ -748,17 +822,23 @@ def case_fulls(case, live=None):
 def expected_keys(case, att):
     """The matched slots of the answers under an attachment, by the laws of tests/within_model.py and tests/after_model.py on
     full(q) of the live rows: the cap first (after_model.cap_full), then the listed ids dropped (exclude_model.drop_listed), then
-    the first k keys behind the cursor (after_model.page) -- the law of tests/exclude_model.py."""
+    the first k keys behind the cursor (after_model.page) -- the law of tests/exclude_model.py.  Under row sets the dropped ids are
+    those of tests/row_sets_model.py's law: the rows outside the query's set together with its list (row_sets_model.complements);
+    the walk has no part in it."""
     import after_model as AM
     import exclude_model as XM
+    import row_sets_model as RM
     fulls = case_fulls(case, att.get("live"))
+    dropped = att.get("excl")
+    if "sets" in att:
+        dropped = RM.complements(att["sets"][0], att["sets"][1], att.get("excl"))
     out = []
     for q, keys in enumerate(fulls):
         full = (key_ids(keys), key_dists(keys))
         if "caps" in att:
             full = AM.cap_full(full, att["caps"][q])
-        if "excl" in att:
-            full = XM.drop_listed(full, att["excl"][q])
+        if dropped is not None:
+            full = XM.drop_listed(full, dropped[q])
         cur = (att["after"][0][q], att["after"][1][q]) if "after" in att else None
         ids, d, take = AM.page(full, cur, case.k)
         out.append(make_keys(d[:take], ids[:take]))
@@ -781,9 +861,68 @@ def expected_answers(case, att):
     return ids, d, taken
 
 
+def row_sets_of(case, name, fulls):
+    """dict(sets = (member bool [n_sets, n], idx u32 [nq])) of a row-set attachment (attachment() has the laws)."""
+    n, nq, k = case.n, len(fulls), case.k
+    ids = np.arange(n)
+    by_five = (np.arange(nq) % 5).astype(np.uint32)          # query q takes set q % 5, 4 = no restriction: neighbours differ
+    by_five[by_five == 4] = SET_NONE
+    if name in ("rs_half", "rs_sparse", "rs_list", "rs_all"):
+        base = "rs_sparse" if name == "rs_sparse" else "rs_half"
+        member = np.random.default_rng(RSET_SEED[base]).random((4, n)) < RSET_SHARE[base]
+        idx = by_five
+    elif name == "rs_ranges":
+        member = np.stack([(ids // RSET_RANGE_ROWS) % 4 == s for s in range(4)])
+        idx = by_five
+    elif name == "rs_edges":
+        member = np.stack([np.zeros(n, bool), np.ones(n, bool)])
+        idx = (np.arange(nq) % 3).astype(np.uint32)          # the empty set, all rows, no restriction
+        idx[idx == 2] = SET_NONE
+    else:
+        assert name == "rs_page1" and nq <= ROW_SETS_MAX, name
+        member = np.ones((nq, n), bool)
+        for q in range(nq):
+            member[q, key_ids(fulls[q][:k])] = False
+        idx = np.arange(nq, dtype=np.uint32)
+    return dict(sets=(np.ascontiguousarray(member), idx))
+
+
+def packed_sets(case, name):
+    """The sets of a row-set attachment as hvs_set_row_sets takes them: u64 [n_sets, ceil(n / 64)], bit i & 63 of word i >> 6 = row
+    i.  The all-ones set of rs_edges has every bit past n set as well ("bits at or past n ignored, read back clear")."""
+    member = attachment(case, name)["sets"][0]
+    n_sets, n = member.shape
+    bits = np.zeros((n_sets, -(-n // 64) * 64), np.uint8)
+    bits[:, :n] = member
+    if name == "rs_edges":
+        bits[1, n:] = 1
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u8").astype(np.uint64))
+
+
+def case_set_table(case):
+    """Every row set the case's cells of ATTACH_MATRIX use, as one table for one hvs_set_row_sets per engine: (words u64 [n_sets,
+    ceil(n / 64)], base) with base[attachment] = the table index of the attachment's set 0; rs_list and rs_all read rs_half's."""
+    used = sorted({("rs_half" if att in ("rs_list", "rs_all") else att) for c, _, _, att in attach_cells() if c.name == case.name and att in RSET_ATTACH},
+                  key=RSET_ATTACH.index)
+    words, base, at = [], {}, 0
+    for att in used:
+        words.append(packed_sets(case, att))
+        base[att] = at
+        at += words[-1].shape[0]
+    assert 0 < at <= ROW_SETS_MAX, (case.name, at)
+    base["rs_list"] = base["rs_all"] = base.get("rs_half")
+    return np.concatenate(words), base
+
+
+def table_indices(case, name):
+    """The set indices of attachment `name` into case_set_table(case)'s table; 0xFFFFFFFF stays."""
+    idx = attachment(case, name)["sets"][1]
+    return np.where(idx == SET_NONE, np.uint32(SET_NONE), idx + np.uint32(case_set_table(case)[1][name])).astype(np.uint32)
+
+
 def attachment(case, name):
     """The attachment `name` of a case: dict with some of caps [nq] f32, after = (dists [nq] f32, ids [nq] u32), live [n] bool, excl
-    = one raw u32 id array per query -- and, for the conditions of tests/test_selectivity_model_cpu.py, cap_kind [nq] (index into CAP_KINDS).  Everything is derived
+    = one raw u32 id array per query, sets = (member bool [n_sets, n], idx u32 [nq]) -- and, for the conditions of tests/test_selectivity_model_cpu.py, cap_kind [nq] (index into CAP_KINDS).  Everything is derived
     from full(q) of the unmasked case (the oracle's exact-order distances, every matched key and not only the nearest 256: key
     3 k of after_deep lies behind them) and from the fixed seed MASK_SEED.
 
@@ -795,7 +934,19 @@ def attachment(case, name):
     1..1024 (the whole neighbourhood of the 150-400 row queries, whose answers are then empty), none; the raw lists are
     reversed, get one 0xFFFFFFFF and one id >= n appended and carry their ids a second time, each as far as the 1024 raw entries
     of HVS_EXCLUDE_MAX allow (a list of 1024 keys is full as it is).  ex_scatter: every second key of keys 1..6k.  ex_all: `all`
-    plus every second key, of the live rows, behind its cursor and within its cap."""
+    plus every second key, of the live rows, behind its cursor and within its cap.
+
+    The row sets (row_sets_of).  rs_half / rs_sparse: four random bitmaps at f = 0.5 / 0.1 from the seeds RSET_SEED, query q takes
+    set q % 5 with 4 = 0xFFFFFFFF.  rs_ranges: set s holds the rows with (id // 2048) % 4 == s -- a tenant's id ranges; the same
+    indices.  rs_edges: set 0 empty, set 1 all rows (shipped with dirty bits past n: packed_sets), query q takes q % 3 with 2 =
+    0xFFFFFFFF.  rs_page1: one set per query, the complement of the ids ex_p1 lists.  rs_list: rs_half with the lists of
+    ex_scatter.  rs_all: rs_half with the cursor, the mask and the list rule of ex_all.
+
+    Changed against the plain reading, and why: rs_all takes the (8 k)-th matched distance as its cap where ex_all takes the (3 k)-th,
+    and builds its lists by ex_all's rule for that cap.  Under ex_all 85 unlisted keys or fewer lie within the cap; rs_half leaves
+    half of them, fewer than the smallest order statistic of most levels, so no threshold leaves the cap and `reckless` retries
+    nobody at n = 32768 (2 queries at n = 70001): the retry pass under all five attachments together would never run.  At 8 k some
+    230 unlisted members lie within the cap and `reckless` retries 11 resp. 14 queries."""
     key = (case.name, name)
     if key in _attach_cache:
         return _attach_cache[key]
@@ -851,8 +1002,10 @@ def attachment(case, name):
         att["caps"], att["cap_kind"] = caps_mixed()
     if name == "all":
         att["caps"] = caps_kth(ALL_CAP_RANK * k)
-    if name == "ex_all":
+    if name in ("ex_all", "rs_all"):
         att.update(attachment(case, "all"))
+        if name == "rs_all":
+            att["caps"] = caps_kth(RS_ALL_CAP_RANK * k)
         live_fulls = case_fulls(case, att["live"])
         lists = []
         for q in range(nq):
@@ -878,6 +1031,10 @@ def attachment(case, name):
         att["after"] = cursors(lambda q: (cursor(q, 3 * k), cursor(q, k), EXHAUSTED, (f32(0.0), np.uint32(0)))[q % 4])
     if name in ("mask", "all"):
         att["live"] = mask()
+    if name in RSET_ATTACH:
+        att.update(row_sets_of(case, name, fulls))
+        if name == "rs_list":
+            att["excl"] = attachment(case, "ex_scatter")["excl"]
     assert att, name
     _attach_cache[key] = att
     return att

@@ -155,6 +155,78 @@ refused_keys, measured = modelled in every cell (proven / default / reckless; th
           queries' 100 listed rows each were refused by the exact engine's re-run, and counted through the sink
 Band x 1.25 build under ex_p1, default thresholds (refused_keys 11200 as in production):
   v1_32k  i8      54133 [54128, 54137]      bf16    47893 [47863, 47924]
+
+Shared row sets (selectivity_model.RSET_ATTACH; the walk's rules: that module's docstring, "Row sets").  The tiles
+carry no membership, so a set costs selectivity and nothing else: a set test missing in hvs_k_rescore but present in the seed, a
+retry batch that runs without `set_of`, non-members that enter the lists and the order statistics and leave in hvs_keep_unlisted
+only, a sub-pass whose refusals are not handed over, refusals booked on the list's counter instead of the set's -- all return
+identical bits.  Every set of a case lies in one table (selectivity_model.case_set_table: at n = 32768 the 4 + 4 + 4 + 2 sets of
+rs_half, rs_sparse, rs_ranges, rs_edges and the 112 of rs_page1), shipped as packed words in one .npy file and loaded once per
+engine (Engine.set_row_sets); a cell's indices go through Engine.query(row_set=), cut to the queries sent -- under rs_list and
+rs_all, where `row_set=` cannot stand beside the others in one call, through upload_queries, the attach calls and
+query_resident.  Per cell, in this order: answers equal to selectivity_model.expected_answers (the law of
+tests/row_sets_model.py), engine and rotation flag as asked; hvs_row_sets_info -- restricted_queries = the queries sent whose index
+is not 0xFFFFFFFF, kept_slots and underfull_queries as those answers imply (all zero in a cell without sets); hvs_exclude_info all
+zero without lists; retry and exact lists exactly; rescored_pairs in [sum lo, sum hi], dead_survivors in its bracket;
+hvs_row_sets_info.refused_keys EQUAL to the model's sum of `set_refused`, in the `out` cells strictly above the filter-answered
+queries' sum (the sink, counter slot 36), and under rs_list and rs_all hvs_exclude_info.refused_keys equal to `refused` as well;
+the rs_page1 cell's rescored_pairs, retry list and refused keys equal to those MEASURED for ex_p1 in the same child on the same
+engine.
+
+Measured against modelled (MI355X), rescored_pairs [sum lo, sum hi], retried queries in parentheses:
+  case    format  attachment  proven                      default                    reckless (retried)
+  v1_32k  i8      rs_half     303608 [ 303602,  303610]    68469 [  68467,   68472]   117213 [ 117208,  117216] (31)
+  v1_32k  i8      rs_sparse   679433 [ 679420,  679437]   265342 [ 265339,  265345]   238907 [ 238903,  238915] (17)
+  v1_32k  i8      rs_ranges   474700 [ 474694,  474705]   120620 [ 120618,  120625]   125526 [ 125518,  125527] (16)
+  v1_32k  i8      rs_edges    791327 [ 791324,  791328]   688287 [ 688284,  688287]   699384 [ 699382,  699385] (13)
+  v1_32k  i8      rs_page1    204390 [ 204388,  204393]    51680 [  51676,   51681]    76243 [  76240,   76244] (22)
+  v1_32k  i8      rs_list     332140 [ 332132,  332146]    98709 [  98707,   98711]   134045 [ 134042,  134047] (23)
+  v1_32k  i8      rs_all       76609 [  76607,   76610]    73742 [  73740,   73743]    73933 [  73930,   73936] (11)
+  v1_32k  i8_rot  rs_half     347160 [ 347140,  347197]    90533 [  90516,   90551]   141985 [ 141972,  142006] (31)
+  v1_32k  i8_rot  rs_sparse   732929 [ 732885,  732968]   317335 [ 317295,  317356]   284768 [ 284720,  284809] (17)
+  v1_32k  i8_rot  rs_ranges   521767 [ 521741,  521814]   154035 [ 154015,  154071]   154075 [ 154050,  154103] (16)
+  v1_32k  i8_rot  rs_edges    814186 [ 814169,  814210]   698100 [ 698091,  698108]   709259 [ 709256,  709272] (13)
+  v1_32k  i8_rot  rs_page1    241478 [ 241456,  241505]    70381 [  70369,   70393]    96826 [  96811,   96836] (22)
+  v1_32k  i8_rot  rs_list     381845 [ 381812,  381881]   129400 [ 129382,  129425]   166104 [ 166083,  166124] (23)
+  v1_32k  i8_rot  rs_all      102086 [ 102075,  102107]    98475 [  98465,   98495]    99147 [  99132,   99175] (11)
+  v1_32k  bf16    rs_half     291067 [ 290992,  291151]    62619 [  62577,   62642]   110588 [ 110545,  110621] (31)
+  v1_32k  bf16    rs_sparse   663651 [ 663556,  663731]   250585 [ 250502,  250668]   226070 [ 226001,  226144] (17)
+  v1_32k  bf16    rs_ranges   460861 [ 460768,  460944]   111526 [ 111468,  111581]   117962 [ 117925,  118001] (16)
+  v1_32k  bf16    rs_edges    784684 [ 784645,  784726]   685700 [ 685690,  685714]   696792 [ 696776,  696810] (13)
+  v1_32k  bf16    rs_page1    193814 [ 193757,  193864]    46855 [  46824,   46882]    70815 [  70777,   70844] (22)
+  v1_32k  bf16    rs_list     317827 [ 317736,  317901]    90389 [  90346,   90441]   125114 [ 125067,  125160] (23)
+  v1_32k  bf16    rs_all       69761 [  69725,   69795]    67173 [  67146,   67202]    67281 [  67248,   67317] (11)
+  v1_70k  i8      rs_sparse  -                            302362 [ 302343,  302369]   358702 [ 358696,  358707] (17)
+  v1_70k  i8      rs_ranges  -                            129214 [ 129209,  129216]   150646 [ 150642,  150652] (15)
+  v1_70k  i8      rs_edges   -                           1475759 [1475757, 1475760]  -
+  v1_70k  i8      rs_all     -                             77747 [  77744,   77749]    78083 [  78077,   78088] (14)
+  half    i8      rs_half    -                            126789 [ 126789,  126792]  -
+  f16     f16     rs_half    -                             61620 [  61597,   61649]  -
+  out     i8      rs_half     292595 [ 292591,  292598]  -                            108018 [ 108015,  108020] (28)
+(every rs_page1 figure is the ex_p1 and after_p2 figure of the tables above, measured in the same child; proven and default
+retried none -- the retry behaviour of sparse sets shows under `reckless`; the 32x32x32 layout gave the 16x16x64 counts in all seven
+default cells of v1_32k i8.  v1_70k / rs_edges is a row of its own in the matrix: n = 32768 is a multiple of 64, and only at n = 70001
+does the all-ones set have its 15 bits past n to be dirty.  rs_all takes the (8 k)-th matched distance as its cap where ex_all
+takes the (3 k)-th -- selectivity_model.attachment says why.  No disagreement was met: no cell needed a rule the model lacked, and
+no group's survivor entries came near `gcap` -- a run of survivors takes an eighth of its length in entries, condition (q).)
+Row sets' refused_keys, measured = modelled in every cell (proven / default / reckless; the same in all three formats of v1_32k),
+with hvs_exclude_info.refused_keys in parentheses where lists are attached, measured = modelled as well:
+  v1_32k  rs_half  135190 / 38762 / 62910      rs_sparse 576401 / 231898 / 209817      rs_ranges 329541 / 92405 / 96304
+  v1_32k  rs_edges 672311 / 672311 / 672311 (the 38 empty-set queries' ranges, once)     rs_page1 11200 / 11200 / 13400 (= ex_p1's)
+  v1_32k  rs_list  132642 (31072) / 37243 (29375) / 55151 (30137)      rs_all 17003 (28352) / 16983 (27161) / 17655 (26850)
+  v1_70k  rs_sparse - / 257056 / 317426    rs_ranges - / 97332 / 115355    rs_edges - / 1459871 / -    rs_all - / 19155 (27566) / 20489 (26932)
+  half    rs_half  30549 (default)         f16  rs_half 39323 (default)
+  out     rs_half  151082 (proven) and 80214 (reckless) against 128620 and 57752 of the 108 filter-answered queries: three of the
+          four far queries carry a set, the exact engine's re-run refused their rows and counted them through the sink
+Band x 1.25 build under rs_half, default thresholds (refused_keys 38762 as in production):
+  v1_32k  i8      71316 [71314, 71317]      bf16    63837 [63803, 63863]
+CPU figures of the set cells' conditions (tests/test_selectivity_model_cpu.py, (l) to (s)): keys asked for that are listed AND
+outside the set, rs_list 12595 / 12580 / 13061; queries with fewer than k members to answer with under rs_ranges 10 of 112 at n =
+32768 and 13 at n = 70001 (none with no member at all: the narrow type-3 ranges hold 150-400 rows of random ids, a quarter of them
+in the set), under rs_edges 38 with none; longest list 1840 keys of 4096; at most 149894 survivor entries at one level of 524288
+(v1_70k / rs_edges; rs_sparse proven 135961 in the rotated format); wrong rules against the right one at v1_32k i8: set_in_lists [39470, 39473] and set_seed_only [55182, 55187]
+against [68467, 68472] (default), set_retry_dropped [88120, 88128] against [117208, 117216] (reckless), set_F_members [67952, 67957]
+against [68467, 68472], set_before_list refused / set_refused 18477 / 145237 against 31072 / 132642 (rs_list, proven).
 """
 import importlib
 import os
@@ -331,27 +403,44 @@ for data, engine, rot, k, sp, cells in spec['engines']:
         e.load_data(z['nodes'])
         e.reserve(spec['reserve'])
         masked = False
+        if os.path.exists(os.path.join(spec['dir'], data + '.sets.npy')):      # the case's row sets, all of them, once per engine
+            e.set_row_sets(np.load(os.path.join(spec['dir'], data + '.sets.npy')))
         for tag in cells:      # (the cells with a mask come last: the mask is set once and stays)
             get = lambda part: np.load(os.path.join(spec['dir'], tag + '.' + part + '.npy')) if os.path.exists(os.path.join(spec['dir'], tag + '.' + part + '.npy')) else None
             keep, caps, after_d, after_i, live = get('keep'), get('caps'), get('after_d'), get('after_i'), get('live')
-            ex_off, ex_ids = get('ex_off'), get('ex_ids')
+            ex_off, ex_ids, set_idx = get('ex_off'), get('ex_ids'), get('set_idx')
             lists = None if ex_off is None else [ex_ids[ex_off[q]:ex_off[q + 1]] for q in keep]      # the CSR cut to `keep`
             assert not (masked and live is None)
             if live is not None and not masked:
                 e.set_row_mask(live)
                 masked = True
-            ids, d = e.query(z['queries'][keep], sp, max_dist2=None if caps is None else caps[keep],
-                             after=None if after_d is None else (after_d[keep], after_i[keep]), exclude=lists)
+            if set_idx is None:
+                ids, d = e.query(z['queries'][keep], sp, max_dist2=None if caps is None else caps[keep],
+                                 after=None if after_d is None else (after_d[keep], after_i[keep]), exclude=lists)
+            elif caps is None and after_d is None and lists is None:
+                ids, d = e.query(z['queries'][keep], sp, row_set=set_idx[keep])
+            else:                  # (row_set= stands alone in one call: the others are attached to the resident queries)
+                e.upload_queries(z['queries'][keep])
+                if caps is not None:
+                    e.set_max_dist2(caps[keep])
+                if after_d is not None:
+                    e.set_after(after_d[keep], after_i[keep])
+                if lists is not None:
+                    e.set_exclude_ids(lists)
+                e.set_query_row_sets(set_idx[keep])
+                e.query_resident(0, keep.size, sp)
+                e.sync()
+                ids, d = e.download_results(0, keep.size)
             t = e.last_timing()
             reruns = [e.last_reruns(0).tolist(), e.last_reruns(1).tolist()]
-            m, w, a, x = e.mask_stats(), e.within_stats(), e.after_stats(), e.exclude_stats()
+            m, w, a, x, r = e.mask_stats(), e.within_stats(), e.after_stats(), e.exclude_stats(), e.row_sets_stats()
             np.savez(os.path.join(spec['out'], tag + '.npz'), ids=ids, dists=d)
             out[tag] = dict(engine=int(t.engine), fallback=int(t.fallback_queries), retry=int(t.retry_queries), flags=int(t.flags),
                             rescored=int(t.rescored_pairs), exact_list=reruns[0], retry_list=reruns[1], dead_survivors=int(m.dead_survivors),
-                            n_dead=int(m.n_dead), within=w.as_dict(), after=a.as_dict(), exclude=x.as_dict())
+                            n_dead=int(m.n_dead), within=w.as_dict(), after=a.as_dict(), exclude=x.as_dict(), row_sets=r.as_dict())
 print('RESULT ' + json.dumps(out))
 """
-_MASK_LAST = {name: (name in ("mask", "all", "ex_all"), i) for i, name in enumerate(SM.ATTACH)}
+_MASK_LAST = {name: (name in ("mask", "all", "ex_all", "rs_all"), i) for i, name in enumerate(SM.ATTACH)}
 
 
 def _run_attached(work_dir, regime, shape, lib=None):
@@ -380,6 +469,10 @@ def _run_attached(work_dir, regime, shape, lib=None):
             off, ex_ids = XM.csr(att["excl"])
             np.save(work_dir / (tag + ".ex_off.npy"), off)
             np.save(work_dir / (tag + ".ex_ids.npy"), ex_ids)
+        if "sets" in att:
+            if not (work_dir / (case.name + ".sets.npy")).exists():
+                np.save(work_dir / (case.name + ".sets.npy"), SM.case_set_table(case)[0])
+            np.save(work_dir / (tag + ".set_idx.npy"), SM.table_indices(case, name))
         engine, rot = ENGINE[fmt]
         engines.setdefault((case.name, engine, rot, case.k, case.sp), []).append(tag)
         runs.append((case, fmt, name, att, keep, w, tag))
@@ -422,6 +515,12 @@ def _check_attached_answers(case, fmt, name, att, keep, ids, dists, t):
         assert (t["after"]["after_slots"], t["after"]["underfull_queries"], t["after"]["exhausted_queries"]) == (slots, underfull, exhausted), \
             (where, t["after"], slots, underfull, exhausted)
     assert t["n_dead"] == (int((~att["live"]).sum()) if "live" in att else 0), (where, t["n_dead"])
+    r = t["row_sets"]
+    if "sets" in att:
+        restricted = int((att["sets"][1][keep] != SM.SET_NONE).sum())
+        assert (r["restricted_queries"], r["kept_slots"], r["underfull_queries"]) == (restricted, slots, underfull), (where, r, restricted, slots, underfull)
+    else:
+        assert (r["restricted_queries"], r["kept_slots"], r["underfull_queries"], r["refused_keys"]) == (0, 0, 0, 0), (where, r)
     x = t["exclude"]
     if "excl" in att:
         assert (x["excluding_queries"], x["kept_slots"], x["underfull_queries"]) == (keep.size, slots, underfull), (where, x, keep.size, slots, underfull)
@@ -432,30 +531,43 @@ def _check_attached_answers(case, fmt, name, att, keep, ids, dists, t):
 def _check_refused(case, fmt, name, att, keep, w, t, bad):
     """hvs_exclude_info.refused_keys against the model's `refused`: equal where the filter answers every query; with an exact
     fallback (the `out` cells) at least the filter-answered queries' sum and strictly above it -- the fallback queries list
-    matched rows, which only the re-run sink (counter slot 26) can have refused."""
-    if "excl" not in att:
-        return ""
-    got, want = t["exclude"]["refused_keys"], int(w["refused"][keep].sum())
+    matched rows, which only the re-run sink (counter slot 26) can have refused.
+    Under row sets hvs_row_sets_info.refused_keys against the model's `set_refused` by the same rule (the sink's slot 36)."""
     sink = bool(w["exact"][keep].any())
-    if (got <= want) if sink else (got != want):
-        bad.append((case.name, fmt, name, "refused_keys", got, "above" if sink else "equal to", want))
-    return "  refused %6d (model %s%d)" % (got, "> " if sink else "", want)
+    line = ""
+    for part, stats, model in (("excl", "exclude", "refused"), ("sets", "row_sets", "set_refused")):
+        if part not in att:
+            continue
+        got, want = t[stats]["refused_keys"], int(w[model][keep].sum())
+        if (got <= want) if sink else (got != want):
+            bad.append((case.name, fmt, name, stats + " refused_keys", got, "above" if sink else "equal to", want))
+        line += "  %s %6d (model %s%d)" % (model, got, "> " if sink else "", want)
+    return line
 
 
 def _check_page2_twin(results, bad):
     """DESIGN 3.14's "the same re-scored pairs": in one child, on one engine, the ex_p1 cell re-scores exactly the pairs the
-    after_p2 cell does and retries the same queries -- measured against measured."""
+    after_p2 cell does and retries the same queries -- measured against measured.  The rs_page1 cell, whose sets are the complements
+    of ex_p1's lists, against the ex_p1 cell likewise, and its refused keys (the set's counter) equal to ex_p1's (the list's).
+    Returns the number of (ex_p1, after_p2) pairs; every rs_page1 cell must have found its ex_p1."""
     cells = {(case.name, fmt, name): (keep, t) for case, fmt, name, att, keep, w, ids, dists, t in results}
     twins = 0
     for (cname, fmt, name), (keep, t) in cells.items():
-        if name == "ex_p1" and (cname, fmt, "after_p2") in cells:
-            keep2, t2 = cells[(cname, fmt, "after_p2")]
-            twins += 1
-            same_sent = np.array_equal(keep, keep2)
-            print("%-7s %-6s ex_p1 rescored %7d retried %s  after_p2 rescored %7d retried %s" % (
-                cname, fmt, t["rescored"], sorted(t["retry_list"]), t2["rescored"], sorted(t2["retry_list"])))
-            if not (same_sent and t["rescored"] == t2["rescored"] and sorted(t["retry_list"]) == sorted(t2["retry_list"])):
-                bad.append((cname, fmt, "ex_p1 against after_p2", t["rescored"], t2["rescored"], sorted(t["retry_list"]), sorted(t2["retry_list"])))
+        other = {"ex_p1": "after_p2", "rs_page1": "ex_p1"}.get(name)
+        if other is None:
+            continue
+        if (cname, fmt, other) not in cells:
+            assert name != "rs_page1", (cname, fmt, "an rs_page1 cell without its ex_p1 cell in the child")
+            continue
+        keep2, t2 = cells[(cname, fmt, other)]
+        twins += name == "ex_p1"
+        same_sent = np.array_equal(keep, keep2)
+        print("%-7s %-6s %s rescored %7d retried %s  %s rescored %7d retried %s" % (
+            cname, fmt, name, t["rescored"], sorted(t["retry_list"]), other, t2["rescored"], sorted(t2["retry_list"])))
+        if not (same_sent and t["rescored"] == t2["rescored"] and sorted(t["retry_list"]) == sorted(t2["retry_list"])):
+            bad.append((cname, fmt, name + " against " + other, t["rescored"], t2["rescored"], sorted(t["retry_list"]), sorted(t2["retry_list"])))
+        if name == "rs_page1" and t["row_sets"]["refused_keys"] != t2["exclude"]["refused_keys"]:
+            bad.append((cname, fmt, "rs_page1's set refusals against ex_p1's list refusals", t["row_sets"]["refused_keys"], t2["exclude"]["refused_keys"]))
     return twins
 
 
@@ -467,9 +579,10 @@ def _attached_line(label, case, fmt, name, t, lo, hi, dlo, dhi, keep, w, ok):
 
 @pytest.mark.parametrize("regime,shape", [("proven", "16"), ("default", "16"), ("reckless", "16"), ("default", "32")])
 def test_attached_counts_lie_in_the_model_bracket(work_dir, regime, shape):
-    """Caps, cursors, a row mask and exclusion lists (selectivity_model.ATTACH over ATTACH_MATRIX): answers and the features' own
-    counts first, then retry and exact lists exactly, rescored_pairs and dead_survivors inside the model's brackets, refused_keys
-    equal to the model's, and the ex_p1 cells against the after_p2 cells measured in the same child."""
+    """Caps, cursors, a row mask, exclusion lists and shared row sets (selectivity_model.ATTACH over ATTACH_MATRIX): answers and the
+    features' own counts first, then retry and exact lists exactly, rescored_pairs and dead_survivors inside the model's brackets,
+    both refused_keys equal to the model's, and the ex_p1 cells against the after_p2 cells, the rs_page1 cells against the ex_p1
+    cells, measured in the same child."""
     results = _run_attached(work_dir, regime, shape)
     for case, fmt, name, att, keep, w, ids, dists, t in results:
         _check_attached_answers(case, fmt, name, att, keep, ids, dists, t)
@@ -488,7 +601,7 @@ def test_attached_counts_lie_in_the_model_bracket(work_dir, regime, shape):
 
 
 def test_a_band_too_wide_is_seen_under_attachments(work_dir, wide_band_lib):
-    """The band x 1.25 build under cap_kth, after_p2, mask and ex_p1: right answers, above the production bracket, inside the model's
+    """The band x 1.25 build under cap_kth, after_p2, mask, ex_p1 and rs_half: right answers, above the production bracket, inside the model's
     bracket for that band."""
     results = _run_attached(work_dir, "default", "16", lib=wide_band_lib)
     for case, fmt, name, att, keep, w, ids, dists, t in results:

@@ -22,6 +22,11 @@ The Prepared objects and walks come from selectivity_model's caches, shared by a
 Exclusion lists (selectivity_model.EXCL_ATTACH) are the fourth attachment: their cells meet (a), (b), (d), (c') and
 (e') -- (e") for the lists -- like the others, and test_conditions_of_the_list_cells adds (j) the walk under ex_p1 IS the walk
 under after_p2, array for array, and (k) what the model says of `refused_keys`.
+
+Shared row sets (selectivity_model.RSET_ATTACH) are the fifth: their cells meet (a), (b), (d), (e') and the walks'
+consistency like the others, and the tests at the end of this module add (l) sets that restrict no query are the committed walk,
+(m) the laws of the empty and the all-ones set, (n) the walk under rs_page1 IS the walk under ex_p1 with the set's counter in
+place of the list's, (o) to (s) of test_conditions_of_the_set_cells; the five wrong rules of the sets are part of (f).
 """
 import os
 import subprocess
@@ -231,7 +236,7 @@ def test_attached_walks_are_consistent():
     held keys are bit for bit what the laws of tests/within_model.py and tests/after_model.py give on full(q) of the live rows
     (SM.expected_keys) -- also behind a failed guess and its retry.  Under `mask` alone the distances also equal the oracle's
     answer on D[live] wherever k live rows match (ids mapped back through `live`)."""
-    oracle_checked = set()
+    oracle_checked, expected = set(), {}
     for case, fmt, regime, name, att, w in _cell_walks():
         for p in ("", "retry_"):
             assert (w[p + "lo"] <= w[p + "hi"]).all() and (w[p + "dead_lo"] <= w[p + "dead_hi"]).all(), (case.name, fmt, regime, name)
@@ -241,7 +246,9 @@ def test_attached_walks_are_consistent():
         if regime == "proven":
             assert not w["retry"].any(), (case.name, fmt, name)
         assert not w["exact"].any()
-        want = SM.expected_keys(case, att)
+        if (case.name, name) not in expected:
+            expected[(case.name, name)] = SM.expected_keys(case, att)
+        want = expected[(case.name, name)]
         for q, (got, exp) in enumerate(zip(w["held_keys"], want)):
             assert np.array_equal(got, exp), (case.name, fmt, regime, name, q, got.size, exp.size)
         if name == "mask" and case.sp == 1.0 and case.name not in oracle_checked:
@@ -287,7 +294,8 @@ def test_conditions_of_the_attached_gpu_cases():
         assert not w["overflow"].any() and w["cand"].max() <= cap, "(d) " + line
         nretry = int(w["retry"][keep].sum())
         assert nretry == 0 or w["retry_cand"].max() <= SM.list_capacity(SM.RESERVE_NQ, nretry), "(d) retry batch " + line
-        assert (w["hi"] + 62)[keep].sum(0).max() <= SM.HVS_GROUP * cap, "(d) survivor entries of a group " + line
+        if name not in SM.RSET_ATTACH:      # (the set cells: (q) of test_conditions_of_the_set_cells counts entries, not survivors)
+            assert (w["hi"] + 62)[keep].sum(0).max() <= SM.HVS_GROUP * cap, "(d) survivor entries of a group " + line
         if fmt != BM.FP16 and name in ("cap_kth", "after_p2", "mask", "ex_p1"):
             m = SM.case_walk(case, fmt, regime, SM.MUTANT_SCALE, attach=name)
             mlo, mhi = SM.totals(m, keep)
@@ -312,21 +320,33 @@ def test_each_wrong_rule_is_seen():
     is disjoint from the right rule's by at least 10 bracket widths, or its retry set differs."""
     print()
     where = {"cap": ("cap_kth", "cap_mixed", "cap_after", "all"), "after": ("after_p2", "after_deep", "cap_after", "all"), "mask": ("mask", "all"),
-             "excl": SM.EXCL_ATTACH}
+             "excl": SM.EXCL_ATTACH, "set": SM.RSET_ATTACH}
     # a list rule must show in the regime where the GPU test would meet it: with thresholds as shipped, resp. where queries are retried
-    must_show_under = {"excl_in_lists": "default", "excl_seed_only": "default", "excl_retry_dropped": "reckless"}
+    must_show_under = {"excl_in_lists": "default", "excl_seed_only": "default", "excl_retry_dropped": "reckless",
+                       "set_in_lists": "default", "set_seed_only": "default", "set_retry_dropped": "reckless"}
     for wrong in SM.WRONG:
         seen = []
         for case, fmt, regime, name in SM.attach_cells():
             if name not in where[wrong.split("_")[0]] or regime != must_show_under.get(wrong, regime):
                 continue
+            if wrong == "set_before_list" and name not in ("rs_list", "rs_all"):
+                continue
+            if wrong.startswith("set_") and len(seen) >= 2:      # (seen: the other cells' walks under the rule are left out)
+                break
             w = SM.case_walk(case, fmt, regime, attach=name)
             x = SM.case_walk(case, fmt, regime, attach=name, wrong=wrong)
             keep = ~w["excluded"]
             (lo, hi), (xlo, xhi) = SM.totals(w), SM.totals(x, keep)
             gap = max(xlo - hi, lo - xhi) / max(hi - lo, 1)
             retry_differs = not np.array_equal(w["retry"][keep], x["retry"][keep])
-            if gap >= 10 or retry_differs:
+            if wrong == "set_before_list":
+                # the order of the two tests moves no key and no threshold: it shows in the two refused-keys sums, which the GPU
+                # test compares for equality
+                sums = [(int(v["refused"][keep].sum()), int(v["set_refused"][keep].sum())) for v in (x, w)]
+                assert (xlo, xhi) == (lo, hi) and not retry_differs
+                if sums[0][0] != sums[1][0] and sums[0][1] != sums[1][1]:
+                    seen.append("%s/%s/%s/%s: refused, set_refused %s against %s" % (case.name, fmt, regime, name, sums[0], sums[1]))
+            elif gap >= 10 or retry_differs:
                 seen.append("%s/%s/%s/%s: [%d, %d] against [%d, %d] (%.0f widths)%s" % (
                     case.name, fmt, regime, name, xlo, xhi, lo, hi, gap, ", retry set differs: %d against %d" % (
                         x["retry"][keep].sum(), w["retry"][keep].sum()) if retry_differs else ""))
@@ -340,8 +360,9 @@ def test_list_cells_with_an_exact_fallback_are_consistent():
     """The `out` cells (four far queries without a usable INT8 bound): what test_attached_walks_are_consistent asks, of the queries
     the filter answers; the far ones take no part in any level and the model counts nothing for them."""
     cells = [c for c in _cell_walks(with_exact=True) if c[5]["exact"].any()]
-    assert len(cells) == 2 and all(c[0].name == "out" and c[3] == "ex_p1" for c in cells)
+    assert sorted((c[0].name, c[2], c[3]) for c in cells) == [("out", rg, name) for rg in ("proven", "reckless") for name in ("ex_p1", "rs_half")]
     for case, fmt, regime, name, att, w in cells:
+        assert not w["set_refused"][w["exact"]].any() and (name != "rs_half" or (att["sets"][1][w["exact"]] != SM.SET_NONE).any())
         for p in ("", "retry_"):
             assert (w[p + "lo"] <= w[p + "hi"]).all() and not w[p + "dead_hi"].any()
         if regime == "proven":
@@ -386,3 +407,125 @@ def test_conditions_of_the_list_cells():
     descending = sum(r.size > 3 and r[0] != 0xFFFFFFFF and (np.diff(SM.key_ids(SM.case_fulls(SM.CASES[0])[q][:3])[::-1]) != 0).all() for q, r in enumerate(raw))
     assert doubled >= 70 and descending >= 70 and sum((r == 0xFFFFFFFF).any() for r in raw) >= 70, (doubled, descending)
     assert sum(r.size == XM.EXCLUDE_MAX for r in raw) >= 20
+
+
+# --------------------------------------------------------------------------- the fifth attachment: shared row sets
+
+def _set_cells():
+    return [c for c in _cell_walks(with_exact=True) if c[3] in SM.RSET_ATTACH]
+
+
+def test_unrestricted_sets_are_the_committed_walk():
+    """(l) sets=None is the committed walk (test_no_attachment_is_the_committed_walk pins its totals); sets whose every index is
+    0xFFFFFFFF -- the EXCL forms with `if (s == 0xFFFFFFFFu) return true;` -- reproduce it array for array and refuse nothing."""
+    case = SM.CASES[0]
+    nodes, queries = SM.case_data(case)
+    nq = queries.shape[0]
+    member = np.random.default_rng(7).random((3, case.n)) < 0.3
+    for regime in ("proven", "default", "reckless"):
+        w = SM.case_walk(case, BM.PLAIN_I8, regime)
+        r = SM.REGIMES[regime]
+        same = SM.walk(BM.PLAIN_I8, nodes, queries, case.k, case.sp, r["guess"], r["pfail"], r["mid"], 1.0, SM.list_capacity(SM.RESERVE_NQ, nq),
+                       prep=SM.case_prep(case, BM.PLAIN_I8), sets=(member, np.full(nq, SM.SET_NONE, np.uint32)))
+        for name in ("lo", "hi", "cand", "ent", "retry_lo", "retry_hi", "retry_cand", "retry", "fails", "excluded"):
+            assert np.array_equal(same[name], w[name]), (regime, name)
+        assert all(np.array_equal(x, y) for x, y in zip(same["held_keys"], w["held_keys"]))
+        assert not same["set_refused"].any() and not same["refused"].any() and not w["set_refused"].any()
+
+
+def test_laws_of_the_edge_sets():
+    """(m) rs_edges, every cell: a query on the all-ones set (shipped with dirty bits past n) or without a restriction walks exactly
+    as without an attachment; a query on the empty set admits nothing -- no list takes a key, tau never moves, nothing is retried,
+    every row of the range is a survivor at every level >= 1 -- and its set_refused is the rows of the range in the sampled prefix,
+    once (one pass)."""
+    cells = [c for c in _set_cells() if c[3] == "rs_edges"]
+    assert {c[0].name for c in cells} == {"v1_32k", "v1_70k"}
+    for case, fmt, regime, name, att, w in cells:
+        P, L = SM.case_prep(case, fmt), SM.levels(case.n)
+        plain = SM.case_walk(case, fmt, regime)
+        idx = att["sets"][1]
+        empty, free = idx == 0, idx != 0
+        assert empty.sum() >= 30 and (idx == 1).sum() >= 30 and (idx == SM.SET_NONE).sum() >= 30
+        for field in ("lo", "hi", "cand", "ent", "retry_lo", "retry_hi", "retry_cand", "retry", "fails"):
+            assert np.array_equal(w[field][free], plain[field][free]), (case.name, fmt, regime, field)
+        assert all(np.array_equal(w["held_keys"][q], plain["held_keys"][q]) for q in np.flatnonzero(free))
+        assert not w["set_refused"][free].any()
+        assert not w["cand"][empty].any() and not w["retry"][empty].any() and not w["retry_hi"][empty].any()
+        for q in np.flatnonzero(empty):
+            ordn, a, b = P.ranges[q]
+            ids = (P.ord.perm_t if ordn else P.ord.perm_ct)[a:b]
+            rows = np.bincount(L.block_level(np.arange(a, b) // 32), minlength=L.K + 1)
+            assert np.array_equal(w["lo"][q], rows[1:]) and np.array_equal(w["hi"][q], rows[1:]), (case.name, fmt, regime, q)
+            assert w["held_keys"][q].size == 0 and w["set_refused"][q] == int((ids < w["sn"]).sum()) > 0, (case.name, fmt, regime, q)
+        words = SM.packed_sets(case, "rs_edges")
+        bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")
+        assert not bits[0].any() and bits[1].all()
+        assert case.n % 64 == 0 or bits.shape[1] > case.n, "the 70001-row case has bits past n"
+    assert SM.packed_sets(SM.case_by_name("v1_70k"), "rs_edges").shape[1] * 64 - 70001 == 15
+
+
+def test_rs_page1_is_the_twin_of_ex_p1():
+    """(n) for every case, format and regime the walk under rs_page1 -- one set per query, the complement of its page 1 -- equals the
+    walk under ex_p1 (and so under after_p2: (j)) in lo, hi, cand, fails, overflow, both retry brackets and the held keys, and the
+    set refuses key for key what the list refuses."""
+    for case in SM.CASES:
+        for fmt in case.fmts:
+            for regime in case.regimes:
+                x, s = SM.case_walk(case, fmt, regime, attach="ex_p1"), SM.case_walk(case, fmt, regime, attach="rs_page1")
+                for name in ("lo", "hi", "cand", "ent", "fails", "overflow", "retry", "retry_lo", "retry_hi", "retry_cand", "excluded"):
+                    assert np.array_equal(x[name], s[name]), ("(n)", case.name, fmt, regime, name)
+                assert all(np.array_equal(p, q) for p, q in zip(x["held_keys"], s["held_keys"])), ("(n)", case.name, fmt, regime)
+                assert np.array_equal(s["set_refused"], x["refused"]) and not s["refused"].any() and not x["set_refused"].any()
+                assert s["set_refused"].sum() > 0
+
+
+def test_conditions_of_the_set_cells():
+    """Per cell of the GPU test with row sets, beside (a), (b), (d), (e') of test_conditions_of_the_attached_gpu_cases:
+
+      (o) set_refused summed over the cell is positive; under `reckless` at least 6 queries are retried and at least 6 are not; in
+          rs_ranges at least 4 queries have fewer than k members to answer with and at least 4 have k;
+      (p) the queries left out (`excluded`) are exactly those of the case without an attachment: the grid edge depends on the
+          range only;
+      (q) no query overflows its list at list_capacity(RESERVE_NQ, 112), and the survivor entries of all queries together (`ent`
+          + 8 per query and level for the rows of the two edge blocks outside its range) stay within HVS_GROUP lists -- the
+          empty-set queries' runs of survivors take an eighth of their length in entries;
+      (r) rs_list: both counters positive and at least 100 keys asked for that are listed AND outside the set;
+      (s) in the cells of the band x 1.25 build the model's bracket for that band lies strictly above the production bracket."""
+    print()
+    seen = set()
+    for case, fmt, regime, name, att, w in _set_cells():
+        seen.add(name)
+        keep = ~w["excluded"]
+        plain = SM.case_walk(case, fmt, regime)
+        cap = SM.list_capacity(SM.RESERVE_NQ, int(keep.sum()))
+        members = np.array([x.size for x in SM.expected_keys(case, att)])
+        answered = keep & ~w["exact"]
+        line = "%-7s %-6s %-8s %-9s retried %2d  set_refused %7d refused %6d both %5d  entries %6d / %6d  under-full %3d empty %2d  longest list %4d / %4d" % (
+            case.name, fmt, regime, name, int(w["retry"][keep].sum()), int(w["set_refused"][keep].sum()), int(w["refused"][keep].sum()),
+            int(w["both"][keep].sum()), (w["ent"] + 8)[keep].sum(0).max(), (w["retry_ent"] + 8)[w["retry"] & keep].sum(0).max(initial=0),
+            int((members < case.k).sum()), int((members == 0).sum()), w["cand"].max(), w["retry_cand"].max())
+        print(line)
+        assert w["set_refused"][keep].sum() > 0 and not w["set_refused"][w["exact"]].any(), "(o) " + line
+        if regime == "reckless":
+            assert w["retry"][answered].sum() >= 6 and (~w["retry"])[answered].sum() >= 6, "(o) " + line
+        if name == "rs_ranges":
+            assert (members < case.k).sum() >= 4 and (members >= case.k).sum() >= 4, "(o) " + line
+        assert np.array_equal(w["excluded"], plain["excluded"]), "(p) " + line
+        assert not w["overflow"].any() and w["cand"].max() <= cap == 4096, "(q) " + line
+        assert (w["ent"] + 8)[keep].sum(0).max() <= SM.HVS_GROUP * cap, "(q) " + line
+        nretry = int(w["retry"][keep].sum())
+        if nretry:
+            assert (w["retry_ent"] + 8)[w["retry"] & keep].sum(0).max() <= SM.HVS_GROUP * SM.list_capacity(SM.RESERVE_NQ, nretry), "(q) " + line
+        if "excl" in att:
+            assert w["refused"][keep].sum() > 0, "(r) " + line
+        if name == "rs_list":
+            assert w["both"][keep].sum() >= 100, "(r) " + line
+    assert seen == set(SM.RSET_ATTACH)
+    wide = [c for c in SM.attach_cells(wide=True) if c[3] in SM.RSET_ATTACH]
+    assert len(wide) == 2
+    for case, fmt, regime, name in wide:
+        w, m = SM.case_walk(case, fmt, regime, attach=name), SM.case_walk(case, fmt, regime, SM.MUTANT_SCALE, attach=name)
+        (lo, hi), (mlo, mhi) = SM.totals(w), SM.totals(m, ~w["excluded"])
+        print("%-7s %-6s %-8s %-9s production [%d, %d]  band x %.2f [%d, %d]" % (case.name, fmt, regime, name, lo, hi, SM.MUTANT_SCALE, mlo, mhi))
+        assert mlo > hi, "(s)"
+        assert np.array_equal(m["retry"], w["retry"]) and np.array_equal(m["set_refused"], w["set_refused"])
