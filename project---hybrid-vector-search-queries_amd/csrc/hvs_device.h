@@ -417,3 +417,95 @@ __device__ __forceinline__ uint64_t hvs_wave_select_prune(uint64_t* list, uint32
     }
     return prefix;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The tail of the merge family: one wave holds up to CAP keys (dist bits << 32 | id) of one query in its LDS buffer
+// `buf`, with `hist` the 256 words of hvs_wave_select_prune.  A kernel gathers in its own way and ends with the same four steps:
+// hvs_wave_final_cut, its counters, hvs_wave_pad, hvs_wave_rank_write; while it gathers, hvs_wave_make_room keeps the next
+// step's slots free.  All 64 lanes call each function under wave-uniform control flow; the workgroup fences stand where the
+// LDS accesses around them need them (a wave's lanes read what other lanes of the wave wrote).  The pointer parameters carry
+// no __restrict__: the kernels' own qualifiers reach the inlined code, and a second set of alias scopes moved register counts.
+// ---------------------------------------------------------------------------------------------
+// a wave-uniform 64-bit value, moved to scalar registers
+__device__ __forceinline__ uint64_t hvs_wave_uniform(uint64_t v)
+{
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+// In front of a step that appends up to `step` keys: when they might not fit, the buffer is cut back to its knn smallest keys
+// (knn + step <= CAP, keys distinct).  Returns the keys held; where it cut and `kth` is given, *kth is the largest key kept.
+template <int CAP>
+__device__ __forceinline__ uint32_t hvs_wave_make_room(uint64_t* buf, uint32_t* hist, uint32_t cnt, uint32_t step, uint32_t knn, uint32_t lane,
+                                                       uint64_t* kth = nullptr)
+{
+    if (cnt + step > (uint32_t)CAP) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        const uint64_t k = hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, hist);
+        if (kth) *kth = hvs_wave_uniform(k);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    return cnt;
+}
+
+// After the gather: the knn smallest of the keys held (distinct) stay.  Returns their number, <= knn.
+template <int CAP>
+__device__ __forceinline__ uint32_t hvs_wave_final_cut(uint64_t* buf, uint32_t* hist, uint32_t cnt, uint32_t knn, uint32_t lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (cnt > knn) {
+        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, hist);
+        cnt = knn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    return cnt;
+}
+
+// The reference's padding (optimized_parallel.hpp:149-157): an answer of cnt < knn matched rows is filled up from the END of D,
+// rows n - 1, n - 2, ... whatever their predicate and whether or not they are among the matched ones, with distances by the
+// same exact-order function.  Slot cnt + s takes key_of(s), s = 0 .. knn - cnt - 1 -- the kernel says which row that is and
+// how its distance is read --, or with pad == 0 (partial answers that are merged later) the largest key, which no row has.
+template <typename KeyOf>
+__device__ __forceinline__ void hvs_wave_pad(uint64_t* buf, uint32_t cnt, uint32_t knn, int pad, uint32_t lane, KeyOf key_of)
+{
+    for (uint32_t base = cnt; base < knn; base += 64u) {
+        const uint32_t e = base + lane;
+        if (e < knn) buf[e] = pad ? key_of(e - cnt) : ~0ull;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+
+// The two common pad keys of row `id` of D: against one query vector, and the smallest over the query rows [s0, s1) of Qx.
+template <bool SCALAR_ORDER>
+__device__ __forceinline__ uint64_t hvs_row_key(const float* D, uint32_t id, const float* qv)
+{
+    const float* dv = D + (size_t)id * HVS_DCOLS + 2;
+    return hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
+}
+template <bool SCALAR_ORDER>
+__device__ __forceinline__ uint64_t hvs_row_key_min(const float* D, uint32_t id, const float* Qx, uint32_t s0, uint32_t s1)
+{
+    uint64_t key = ~0ull;
+    for (uint32_t j = s0; j < s1; ++j) {
+        const uint64_t kj = hvs_row_key<SCALAR_ORDER>(D, id, Qx + (size_t)j * HVS_QCOLS + 4);
+        key = kj < key ? kj : key;
+    }
+    return key;
+}
+
+// Rank sort of exactly knn keys in the canonical order (dist ascending, id ascending; duplicates are possible after padding:
+// ties broken by slot), written to result row `row`: ids, and distances where out_dists is not null (+inf for the key ~0).
+__device__ __forceinline__ void hvs_wave_rank_write(const uint64_t* buf, uint32_t knn, uint32_t lane, uint32_t row,
+                                                    uint32_t* out_ids, float* out_dists)
+{
+    for (uint32_t e = lane; e < knn; e += 64u) {
+        const uint64_t ke = buf[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < knn; ++j) {
+            const uint64_t kj = buf[j];
+            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
+        }
+        out_ids[(size_t)row * knn + rank] = hvs_key_id(ke);
+        if (out_dists) out_dists[(size_t)row * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
+    }
+}

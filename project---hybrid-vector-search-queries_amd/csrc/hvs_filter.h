@@ -3018,7 +3018,7 @@ __device__ __forceinline__ uint32_t hvs_guess_m(const HvsLevels& L, const HvsGue
 // ---------------------------------------------------------------------------------------------
 // hvs_k_merge -- per slot (one wave): top-k := k smallest keys of (top U cand); the threshold tau of the NEXT level
 // and the filter threshold theta that belongs to it.  With `final` it verifies the answer, pads from the end of D
-// (optimized_parallel.hpp:149-157), rank-sorts and writes the answer at the query's own index.
+// (hvs_wave_pad), rank-sorts and writes the answer at the query's own index (hvs_wave_rank_write).
 //
 // Guessed thresholds.  A level multiplies the rows a query has seen by its radix r.  With the PROVEN threshold (tau =
 // the k-th smallest distance seen so far, what the reference's Knn::check_add compares against, optimized_impl.h:301)
@@ -3106,22 +3106,12 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
     for (uint32_t e = lane; e < cnt; e += 64u) buf[e] = B.top[(size_t)slot * B.topcap + e];
     const uint64_t* __restrict__ lst = B.cand + (size_t)slot * B.fcap;
     for (uint32_t off = 0; off < m; off += 64u) {
-        if (cnt + 64u > (uint32_t)CAP) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-            cnt = knn;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
+        cnt = hvs_wave_make_room<CAP>(buf, shist[w], cnt, 64u, knn, lane);
         const uint32_t take = (m - off) < 64u ? (m - off) : 64u;
         if (lane < take) buf[cnt + lane] = lst[off + lane];
         cnt += take;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
     // largest distance held, as key bits (finite < +inf < NaN, the order of the keys)
     uint32_t dmax_bits = 0u;
     for (uint32_t e = lane; e < cnt; e += 64u) {
@@ -3183,29 +3173,10 @@ __global__ __launch_bounds__(256) void hvs_k_merge(const float* __restrict__ D, 
         cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, failed == 0u);
         if constexpr (EXCL) cnt = hvs_keep_unlisted(buf, cnt, excl, qi, knn, lane, counters, failed == 0u);
     }
-    // ---- final: pad, rank-sort, write
+    // ---- final: pad (pad == 0, partial answers of a data shard: empty slots hold the largest key), rank-sort, write
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            uint32_t id = n - 1u - (e - cnt);
-            if constexpr (MASKED) id = pad_ids[e - cnt];
-            const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
-            // padding off (partial answers of a data shard): empty slots hold the largest key
-            buf[e] = pad ? hvs_make_key(hvs_exact_dist(dv, qv), id) : ~0ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)qi * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)qi * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) { return hvs_row_key<false>(D, MASKED ? pad_ids[s] : n - 1u - s, qv); });
+    hvs_wave_rank_write(buf, knn, lane, qi, out_ids, out_dists);
 }
 
 // result rows of the queries in `list`, packed: dst[i][0..k) = src[list[i]][0..k)  (ids, or distances as bit patterns)

@@ -777,10 +777,9 @@ __global__ __launch_bounds__(256, HVS_LDS_SCAN_WGS) void hvs_k_scan_exact_lds(
 // ---------------------------------------------------------------------------------------------
 // hvs_k_select -- per query: merge the per-chunk candidate lists (the counterpart of
 // Knn::merge, optimized_impl.h:337-385 + optimized_parallel.hpp:142-146), pad with the last
-// rows of D when fewer than 100 rows matched (optimized_parallel.hpp:149-157: rows n-1, n-2,
-// ... regardless of predicate or duplicates, distances by the same exact-order kernel) and
-// emit ids in ascending (dist, id) order (get_knn_sorted, optimized_impl.h:392-415).
-// One wave per query, 4 queries per 256-thread block, a 256-key LDS buffer per wave.
+// rows of D when fewer than knn rows matched (hvs_wave_pad) and emit ids in ascending
+// (dist, id) order (hvs_wave_rank_write; get_knn_sorted, optimized_impl.h:392-415).
+// One wave per query, 4 queries per 256-thread block, a CAP-key LDS buffer per wave.
 // ---------------------------------------------------------------------------------------------
 // The final kernels' share of the caps (hvs_k_select, hvs_k_merge with CAPPED): of the wave's keys buf[0 .. cnt) -- the k
 // smallest the query's rows gave -- those with `dist <= cap` are kept, packed in place in their order; returns their number.
@@ -893,17 +892,14 @@ __global__ __launch_bounds__(256) void hvs_k_select(
         const uint32_t m = cand_cnt[(size_t)c * nq_pad + slot];
         const uint64_t* __restrict__ lst = cand + ((size_t)c * nq_pad + slot) * CAP;
         for (uint32_t off = 0; off < m; off += 64u) {
-            if (cnt + 64u > (uint32_t)CAP) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-                cnt = knn;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            }
+            cnt = hvs_wave_make_room<CAP>(buf, shist[w], cnt, 64u, knn, lane);
             const uint32_t take = (m - off) < 64u ? (m - off) : 64u;
             if (lane < take) buf[cnt + lane] = lst[off + lane];
             cnt += take;
         }
     }
+    // hvs_wave_final_cut, written out: with the call here the compiler lays this kernel's blocks out in another order, and 34 of
+    // its 48 instantiations change their register counts (profiles/merge_tail_kernel_diff.txt)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (cnt > knn) {
         hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
@@ -913,39 +909,20 @@ __global__ __launch_bounds__(256) void hvs_k_select(
     if constexpr (CAPPED) cnt = hvs_keep_within(buf, cnt, caps[qi], knn, lane, counters, true);
     if constexpr (AFTER) cnt = hvs_keep_after(buf, cnt, after_lo[qi], knn, lane, counters, true);
     if constexpr (EXCL) cnt = hvs_keep_unlisted(buf, cnt, excl, qi, knn, lane, counters, true);
-    // padding: fewer than 100 matching rows in [0,sn)
+    // fewer than knn matching rows in [0,sn): row n - 1 - s, or the s-th of the last live rows
     const float* __restrict__ qv = Q + (size_t)qi * HVS_QCOLS + 4;
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            uint32_t id = n - 1u - (e - cnt);
-            if constexpr (MASKED) id = pad_ids[e - cnt];
-            const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
-            buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id) : ~0ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly 100 keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)qi * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)qi * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) { return hvs_row_key<SCALAR_ORDER>(D, MASKED ? pad_ids[s] : n - 1u - s, qv); });
+    hvs_wave_rank_write(buf, knn, lane, qi, out_ids, out_dists);
 }
 
 // ---------------------------------------------------------------------------------------------
 // hvs_k_merge_shards -- D-sharded mode: the multi-GPU counterpart of Knn::merge
 // (optimized_impl.h:337-385).  Every shard (GPU) answered ALL queries on its own rows with padding off:
 // ids are shard-local (0xFFFFFFFF = empty slot), lists sorted by (dist, id).  Per query (one wave): the
-// nshards x 100 keys (dist bits << 32 | global id) are reduced to the 100 smallest; when fewer than 100 rows
+// nshards x knn keys (dist bits << 32 | global id) are reduced to the knn smallest; when fewer than knn rows
 // matched anywhere, rows n_total-1, n_total-2, ... are appended with their exact-order distances
-// (optimized_parallel.hpp:149-157; `pad_dists[q][s]` = distance of query q to row n_total-1-s), and the 100
-// keys leave in ascending (dist, id) order.  ids_all / dists_all: [nshards][nq][100] as all_gather lays them out.
+// (hvs_wave_pad; `pad_dists[q][s]` = distance of query q to row n_total-1-s), and the knn
+// keys leave in ascending (dist, id) order.  ids_all / dists_all: [nshards][nq][knn] as all_gather lays them out.
 // ---------------------------------------------------------------------------------------------
 struct HvsShardRows {
     uint64_t row0[16];  // first global row of each shard
@@ -953,18 +930,14 @@ struct HvsShardRows {
 
 // One part's result row of one query -- `knn` slots, ids local to the part (0xFFFFFFFF = empty slot) -- appended to the wave's
 // key buffer as (dist bits << 32 | row0 + id); `cnt` keys are held, the new count is returned.  The buffer is cut back to its
-// knn smallest keys whenever the next 64 slots might not fit.  Shared by the two merges over row parts below.
+// knn smallest keys whenever the next 64 slots might not fit (hvs_wave_make_room).  Shared by the two merges over row parts
+// below and by hvs_k_merge_in.
 template <int CAP>
 __device__ __forceinline__ uint32_t hvs_gather_list_keys(uint64_t* buf, uint32_t* hist, uint32_t cnt, const uint32_t* __restrict__ ids,
                                                          const float* __restrict__ dists, uint64_t row0, uint32_t knn, uint32_t lane)
 {
     for (uint32_t off = 0; off < knn; off += 64u) {
-        if (cnt + 64u > (uint32_t)CAP) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, hist);
-            cnt = knn;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
+        cnt = hvs_wave_make_room<CAP>(buf, hist, cnt, 64u, knn, lane);
         const uint32_t e = off + lane;
         const uint32_t id = e < knn ? ids[e] : 0xFFFFFFFFu;
         const bool have = id != 0xFFFFFFFFu;
@@ -994,28 +967,11 @@ __global__ __launch_bounds__(256) void hvs_k_merge_shards(const uint32_t* __rest
         const size_t base = ((size_t)s * nq + q) * knn;
         cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, ids_all + base, dists_all + base, rows.row0[s], knn, lane);
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
-    for (uint32_t b = cnt; b < knn; b += 64u) {
-        const uint32_t e = b + lane;
-        if (e < knn) buf[e] = hvs_make_key(pad_dists[(size_t)q * knn + (e - cnt)], n_total - 1u - (e - cnt));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly 100 keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)q * knn + rank] = hvs_key_dist(ke);
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
+    // padding is always on here and every pad slot takes a row's key, so the key ~0 that hvs_wave_rank_write turns into +inf
+    // never reaches it: the distances leave as their bits
+    hvs_wave_pad(buf, cnt, knn, 1, lane, [=](uint32_t s) { return hvs_make_key(pad_dists[(size_t)q * knn + s], n_total - 1u - s); });
+    hvs_wave_rank_write(buf, knn, lane, q, out_ids, out_dists);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1026,7 +982,7 @@ __global__ __launch_bounds__(256) void hvs_k_merge_shards(const uint32_t* __rest
 // rows were copied into) and its first global row.  Per query (one wave): the keys (dist bits << 32 | global id) of all parts
 // are reduced to the knn smallest -- the global top-k, because every part's list holds its own knn smallest keys.  Only a
 // query with fewer than knn keys pays for distances: slot cnt + s takes global row n_total - 1 - s, duplicates of matched
-// rows included, as hvs_k_select / hvs_k_merge pad on one GPU (optimized_parallel.hpp:149-157), with the distance computed
+// rows included, as hvs_k_select / hvs_k_merge pad on one GPU (hvs_wave_pad), with the distance computed
 // here from `tail` -- the part's replica of the last `tail_rows` rows of the whole D (tail_rows >= knn: host) -- by the engines'
 // own exact-order function; pad == 0 leaves the largest key there.  `padded` counts the under-full queries either way.
 // ---------------------------------------------------------------------------------------------
@@ -1053,34 +1009,14 @@ __global__ __launch_bounds__(256) void hvs_k_merge_parts(HvsPartLists parts, uin
     for (uint32_t s = 0; s < nparts; ++s)
         cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, parts.ids[s] + (size_t)q * knn, parts.dists[s] + (size_t)q * knn, parts.row0[s], knn,
                                         lane);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
     if (cnt < knn && lane == 0u) atomicAdd(padded, 1ull);
     const float* __restrict__ qv = Q + (size_t)q * HVS_QCOLS + 4;
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            const uint32_t s = e - cnt;  // (< knn <= tail_rows)
-            const float* __restrict__ dv = tail + (size_t)(tail_rows - 1u - s) * HVS_DCOLS + 2;
-            buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), n_total - 1u - s) : ~0ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) {  // global row n_total - 1 - s, read from the tail replica (s < knn <= tail_rows)
+        const float* __restrict__ dv = tail + (size_t)(tail_rows - 1u - s) * HVS_DCOLS + 2;
+        return hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), n_total - 1u - s);
+    });
+    hvs_wave_rank_write(buf, knn, lane, q, out_ids, out_dists);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1145,9 +1081,9 @@ __global__ __launch_bounds__(256) void hvs_k_expand_per_query(const uint32_t* __
 // sub_off[q + 1]) x knn of the engines' own result buffer (padding off: 0xFFFFFFFF = empty slot, ids global), are streamed
 // through the wave's key buffer (hvs_gather_list_keys cuts it back to the knn smallest whenever the next 64 slots might not
 // fit: that is how 64 lists pass through 256 / 512 keys) and reduced to the knn smallest keys.  The keys are distinct: the
-// sub-queries' categories are (hvs_in_plan de-duplicates).  Caps and cursors were applied by the sub-queries.  Padding as
-// hvs_k_select does it on one GPU: slot cnt + s takes row n - 1 - s, or pad_ids[s] (the last live ids) where pad_ids is not
-// null, with the distance computed here from D by the engines' own exact-order function; pad == 0 leaves the largest key.
+// sub-queries' categories are (hvs_in_plan de-duplicates).  Caps and cursors were applied by the sub-queries.  Padding
+// (hvs_wave_pad): slot cnt + s takes row n - 1 - s, or pad_ids[s] (the last live ids) where pad_ids is not null, with the
+// distance computed here from D by the engines' own exact-order function.
 // stat[0] += 1 for an under-full query, stat[1] += keys gathered.  Queries [q0, q0 + nq) of the user's set; Q: the user's rows.
 template <bool SCALAR_ORDER, int CAP>
 __global__ __launch_bounds__(256) void hvs_k_merge_in(const uint32_t* __restrict__ sub_off, uint32_t q0, uint32_t nq, const uint32_t* __restrict__ sub_ids,
@@ -1174,38 +1110,15 @@ __global__ __launch_bounds__(256) void hvs_k_merge_in(const uint32_t* __restrict
             seen += (uint32_t)__popcll(__ballot(off + lane < knn && ids[off + lane] != 0xFFFFFFFFu));
         cnt = hvs_gather_list_keys<CAP>(buf, shist[w], cnt, ids, sub_dists + (size_t)s * knn, 0ull, knn, lane);
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
     if (lane == 0u) {
         if (cnt < knn) atomicAdd(&stat[0], 1ull);
         if (seen) atomicAdd(&stat[1], (unsigned long long)seen);
     }
     const float* __restrict__ qv = Q + (size_t)q * HVS_QCOLS + 4;
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            const uint32_t s = e - cnt;  // (< knn <= live rows: host)
-            const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
-            const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
-            buf[e] = pad ? hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id) : ~0ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    // (s < knn <= live rows: host)
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) { return hvs_row_key<SCALAR_ORDER>(D, pad_ids ? pad_ids[s] : n - 1u - s, qv); });
+    hvs_wave_rank_write(buf, knn, lane, q, out_ids, out_dists);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1479,13 +1392,13 @@ __device__ __forceinline__ uint32_t hvs_wave_dedup_ids(uint64_t* buf, uint32_t c
 // [sub_off[q], sub_off[q + 1]) x knn of the engines' result buffer (padding off: 0xFFFFFFFF = empty slot, ids global), are
 // streamed through the wave's key buffer, 64 slots at a time.  The same row turns up in several lists with different keys, so
 // this is not hvs_k_merge_in: whenever the next 64 slots might not fit (held + 64 > CAP) the buffer is first DE-DUPLICATED by id
-// (hvs_wave_dedup_ids), and only if they still might not fit cut back to its knn smallest keys -- a cut over duplicates could
-// keep two keys of one row and drop a row the answer needs; after de-duplication a dropped row has knn distinct rows in front of
-// it, whose keys only shrink as more lists arrive, and a later, smaller key of the dropped row is gathered again.  knn + 64 <=
-// CAP, so the step then fits.  Once more at the end: de-duplicate, then select -- the keys are distinct whenever
-// hvs_wave_select_prune runs, the exact duplicate (equal vectors) included.  Caps and exclusion lists were applied by the
-// sub-queries.  Padding as hvs_k_merge_in: slot cnt + s takes row n - 1 - s or pad_ids[s], with the smallest key over the
-// query's vectors, read from the EXPANDED rows Qx[sub_off[q] .. sub_off[q + 1]); pad == 0 leaves the largest key.
+// (hvs_wave_dedup_ids), and only if they still might not fit cut back to its knn smallest keys
+// -- a cut over duplicates could keep two keys of one row and drop a row the answer needs; after de-duplication a dropped row
+// has knn distinct rows in front of it, whose keys only shrink as more lists arrive, and a later, smaller key of the dropped
+// row is gathered again.  knn + 64 <= CAP, so the step then fits.  Once more at the end: de-duplicate, then select -- the keys
+// are distinct whenever hvs_wave_select_prune runs, the exact duplicate (equal vectors) included.  Caps and exclusion lists
+// were applied by the sub-queries.  Padding as hvs_k_merge_in: slot cnt + s takes row n - 1 - s or pad_ids[s], with the
+// smallest key over the query's vectors, read from the EXPANDED rows Qx[sub_off[q] .. sub_off[q + 1]) (hvs_row_key_min).
 // stat[0] += 1 for an under-full query, stat[1] += keys read, stat[2] += keys dropped because the buffer held the id with a key
 // at least as small.  Queries [q0, q0 + nq) of the user's set.
 template <bool SCALAR_ORDER, int CAP>
@@ -1533,46 +1446,15 @@ __global__ __launch_bounds__(256) void hvs_k_merge_vectors(const uint32_t* __res
         dups += cnt - left;
         cnt = left;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
     if (lane == 0u) {
         if (cnt < knn) atomicAdd(&stat[0], 1ull);
         if (seen) atomicAdd(&stat[1], (unsigned long long)seen);
         if (dups) atomicAdd(&stat[2], (unsigned long long)dups);
     }
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            uint64_t key = ~0ull;
-            if (pad) {
-                const uint32_t s = e - cnt;  // (< knn <= live rows: host)
-                const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
-                const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
-                for (uint32_t j = s0; j < s1; ++j) {
-                    const float* __restrict__ qv = Qx + (size_t)j * HVS_QCOLS + 4;
-                    const uint64_t kj = hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
-                    key = kj < key ? kj : key;
-                }
-            }
-            buf[e] = key;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    // (s < knn <= live rows: host)
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) { return hvs_row_key_min<SCALAR_ORDER>(D, pad_ids ? pad_ids[s] : n - 1u - s, Qx, s0, s1); });
+    hvs_wave_rank_write(buf, knn, lane, q, out_ids, out_dists);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1645,8 +1527,10 @@ __global__ __launch_bounds__(256) void hvs_k_expand_clauses(const float4* __rest
 // the ballot that compacts the chunk.  No LDS beyond the key buffer and the select's histogram.
 // Padding and the final rank sort are hvs_k_merge_vectors': a pad row's key is its smallest over the query's EXPANDED rows.
 // (With predicate-only clauses these rows all carry the parent's vector, and a pad slot computes the same distance up to 256
-// times: the kernel is not told which kind it merges.  That costs only under-full queries with padding on.)  The tail from the
-// counters on is hvs_k_merge_vectors' text, kept as a copy because that kernel's instruction stream must not move.
+// times: the kernel is not told which kind it merges.  That costs only under-full queries with padding on.)  From the final cut
+// on, the text is what hvs_wave_final_cut, hvs_wave_pad with hvs_row_key_min and hvs_wave_rank_write hold (hvs_device.h),
+// written out: with the calls this kernel's code came out 17 to 21 instructions shorter and, in one of the six timings that
+// run it, 0.001 ms outside the old code's range on the slow side (profiles/merge_tail_rate.txt).  A fix to the tail goes here too.
 // stat[0] += 1 for an under-full query, stat[1] += non-empty slots loaded, stat[2] += keys dropped by a de-duplication,
 // stat[3] += keys loaded and not admitted, stat[4] += 64-slot chunks never loaded.  Queries [q0, q0 + nq) of the user's set.
 template <bool SCALAR_ORDER, int CAP>
@@ -1834,7 +1718,7 @@ __global__ __launch_bounds__(256) void hvs_k_norm_candidates(const uint32_t* __r
 // tau becomes the largest key kept.  The invariant is hvs_k_merge_clauses': whenever tau is set the buffer holds knn admitted
 // keys <= tau, and only keys strictly below tau are admitted; the keys are distinct because the ids are, so nothing is
 // de-duplicated.  A key that is refused has knn admitted keys in front of it, now and for ever.
-// The end of a query is hvs_k_select's: final cut, padding from D (or `pad_ids` under a mask), rank sort.
+// The end of a query is the merge family's: hvs_wave_final_cut, padding from D (or `pad_ids` under a mask), hvs_wave_rank_write.
 // counters: HVS_CNT_PAIRS += listed rows that are in the prefix, live and pass the predicate; HVS_CNT_SCANNED += entries of the
 // normalised list; HVS_CNT_CAND_SLOTS += slots kept; HVS_CNT_CAND_UNDERFULL += 1 for an under-full query; and the slots /
 // under-full pairs of caps, cursors and exclusion lists where those are attached, as the final kernels count them.
@@ -1895,13 +1779,7 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
         const uint64_t pm = __ballot(ok && first);
         if (pm == 0ull) continue;
         npass += (uint32_t)__popcll(pm);
-        if (cnt + ROWS > (uint32_t)CAP) {  // (cnt > knn: knn + 64 <= CAP)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            const uint64_t kth = hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-            tau = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(kth >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)kth);
-            cnt = knn;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
+        cnt = hvs_wave_make_room<CAP>(buf, shist[w], cnt, ROWS, knn, lane, &tau);  // (a cut sets tau; knn + 64 <= CAP)
         const float* __restrict__ dv = D + (size_t)(ok ? id : 0u) * HVS_DCOLS + 2;
         float dist = 0.0f;
         if constexpr (SCALAR_ORDER) {
@@ -1942,12 +1820,7 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
         if (admit) buf[cnt + hvs_prefix_count(m)] = key;
         cnt += (uint32_t)__popcll(m);
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (cnt > knn) {
-        hvs_wave_select_prune<CAP / 64>(buf, cnt, knn, lane, shist[w]);
-        cnt = knn;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    cnt = hvs_wave_final_cut<CAP>(buf, shist[w], cnt, knn, lane);
     if (excl.set_of != nullptr) {  // (wave-uniform)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nset += __shfl_xor(nset, o);
@@ -1977,30 +1850,7 @@ __global__ __launch_bounds__(256) void hvs_k_scan_candidates(const float* __rest
             if (under) atomicAdd(&counters[HVS_CNT_EXCL_UNDERFULL], under);
         }
     }
-    // padding: fewer than knn admitted rows
-    for (uint32_t base = cnt; base < knn; base += 64u) {
-        const uint32_t e = base + lane;
-        if (e < knn) {
-            uint64_t key = ~0ull;
-            if (pad) {
-                const uint32_t s = e - cnt;  // (< knn <= live rows: host)
-                const uint32_t id = pad_ids ? pad_ids[s] : n - 1u - s;
-                const float* __restrict__ dv = D + (size_t)id * HVS_DCOLS + 2;
-                key = hvs_make_key(SCALAR_ORDER ? hvs_scalar_order_dist(dv, qv) : hvs_exact_dist(dv, qv), id);
-            }
-            buf[e] = key;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // rank sort of exactly knn keys (duplicates possible after padding: ties broken by slot)
-    for (uint32_t e = lane; e < knn; e += 64u) {
-        const uint64_t ke = buf[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < knn; ++j) {
-            const uint64_t kj = buf[j];
-            rank += (kj < ke || (kj == ke && j < e)) ? 1u : 0u;
-        }
-        out_ids[(size_t)q * knn + rank] = hvs_key_id(ke);
-        if (out_dists) out_dists[(size_t)q * knn + rank] = ke == ~0ull ? __builtin_inff() : hvs_key_dist(ke);
-    }
+    // fewer than knn admitted rows (s < knn <= live rows: host)
+    hvs_wave_pad(buf, cnt, knn, pad, lane, [=](uint32_t s) { return hvs_row_key<SCALAR_ORDER>(D, pad_ids ? pad_ids[s] : n - 1u - s, qv); });
+    hvs_wave_rank_write(buf, knn, lane, q, out_ids, out_dists);
 }

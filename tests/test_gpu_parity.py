@@ -440,8 +440,10 @@ def test_data_sharded_mode_virtual_ranks(engine):
 
 def test_data_sharded_device_merge_matches_host_merge():
     """hvs_merge_shards_device (the GPU analogue of Knn::merge for row shards) on the layout an all_gather
-    produces, [shard][query][100], against sharding.merge_data_shards.  Runs in a subprocess that imports torch
-    BEFORE the library (one HIP runtime per process, as bench.py does)."""
+    produces, [shard][query][100], against sharding.merge_data_shards; then once more at k = 256 (3 shards of 1024
+    rows, 64 queries, oracle parity under oracle_k(256) as well): the CAP = 512 instantiation of hvs_k_merge_shards,
+    which the 768 keys of a query that every shard answers in full pass through.  Runs in a subprocess that imports
+    torch BEFORE the library (one HIP runtime per process, as bench.py does)."""
     import subprocess
     import sys
     code = r"""
@@ -482,6 +484,41 @@ with PKG.Engine(0) as e:
         pass
 ref, _ = T.oracle_query(nodes, queries)
 T.check_parity(nodes, queries, out_i.cpu().numpy().view(np.uint32), ref, got_dists=out_d.cpu().numpy())
+# k = 256: the 512-key buffer.  3 lists x 256 slots = 768 keys of a query that every shard answers in full pass through it,
+# so the buffer is cut in mid-gather, cut again at the end, and query 1 (no row has its category) is padded entirely from pad_dists
+k, n, nq = 256, 3072, 64
+nodes = T.gen_data(n, 43, T.GEN_V1, 40); queries = T.gen_queries(nq, 44, T.GEN_V1, 40)
+queries[1, :4] = [1, 999, -1, -1]
+parts = []
+for r in range(world):
+    r0, r1 = sharding.row_shard_range(n, r, world)
+    assert r1 - r0 == 1024
+    with PKG.Engine(0) as e:
+        e.set_k(k); e.set_padding(False); e.load_data(nodes[r0:r1])
+        ids, dists = e.query(queries, 1.0)
+    parts.append((ids, dists, r0))
+full = np.all([(p[0] != 0xFFFFFFFF).all(axis=1) for p in parts], axis=0)
+assert full.any(), 'some query must bring 768 keys'
+assert all((p[0][1] == 0xFFFFFFFF).all() for p in parts), 'query 1 must match nothing'
+with PKG.Engine(0) as e:
+    e.set_k(k); e.load_data(nodes[n - k:])
+    pad = sharding.tail_pad_dists(lambda q: e.query(q, 1.0), queries)
+ids, dists = sharding.merge_data_shards(parts, n, pad)
+assert ids.shape == (nq, k) and np.array_equal(np.sort(ids[1]), np.arange(n - k, n))
+ids_all = torch.from_numpy(np.stack([p[0] for p in parts]).view(np.int32)).cuda()
+d_all = torch.from_numpy(np.stack([p[1] for p in parts])).cuda()
+pad_t = torch.from_numpy(np.ascontiguousarray(pad, np.float32)).cuda()
+out_i = torch.empty((nq, k), dtype=torch.int32, device='cuda'); out_d = torch.empty((nq, k), dtype=torch.float32, device='cuda')
+torch.cuda.synchronize()
+with PKG.Engine(0) as e:
+    e.set_k(k)
+    e.merge_shards_device(ids_all.data_ptr(), d_all.data_ptr(), [p[2] for p in parts], nq, n, pad_t.data_ptr(), out_i.data_ptr(), out_d.data_ptr())
+    e.sync()
+    assert np.array_equal(out_i.cpu().numpy().view(np.uint32), ids)
+    assert np.array_equal(out_d.cpu().numpy().view(np.uint32), dists.view(np.uint32))
+with T.oracle_k(k):
+    ref, _ = T.oracle_query(nodes, queries)
+    T.check_parity(nodes, queries, out_i.cpu().numpy().view(np.uint32), ref, got_dists=out_d.cpu().numpy())
 print('SUBPROCESS-OK')
 """
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=T.REPO)
