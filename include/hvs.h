@@ -1134,6 +1134,73 @@ int hvs_row_sets_stats(hvs_ctx *ctx, hvs_row_sets_info *out);
 void hvs_row_sets_compact_plan(const uint64_t *bits, const uint64_t *live_bits /* may be NULL */, uint32_t n, uint32_t n_sets,
                                uint64_t *out_bits);
 
+/* ---- scanned row sets -------------------------------------------------------------------------------------
+ * A shared row set is exact at every density, but the engines know nothing of membership: a sparse set leaves the filter's
+ * guessed thresholds without matches and the call falls to retries and the exact engine.  A SCANNED SET is answered the other
+ * way round: its members are gathered by id and the exact-order distance is evaluated on each, a lane per query over rows a
+ * workgroup gathers once (hvs_k_scan_set_members, hvs_k_merge_set_chunks).
+ *
+ * hvs_set_row_set_scan_limit: a loaded set whose population is <= rows is a scanned set; on a row-partitioned context the
+ * population is counted per part, over the part's window.  0 (the default) means never: every call then runs the kernels it ran
+ * before, with the same arguments.  The limit is context state like hvs_set_tail_limit and survives what that survives; no value
+ * is chosen automatically.  hvs_get_row_set_scan_limit reads it back.
+ *
+ * A call takes the path when the limit is non-zero, set indices are attached, the expanded resident set (category sets, query
+ * vectors, clauses) is NOT attached, no candidate lists are attached (they keep precedence) and EVERY resident query of the GPU
+ * carries the index of a scanned set.  One query at 0xFFFFFFFF or on a denser set sends the whole resident set down the other
+ * path.  This is judged once per change of the indices, the bitmaps or the limit, not per call -- LAZILY: those calls only mark
+ * the state stale, and the first query call behind them rebuilds the member lists (device state beside the bitmaps; stale after
+ * hvs_set_row_sets*, hvs_assign_row_sets, hvs_compact, a load or a new limit), sorts the call's range of queries by set and
+ * decides, which costs a few small launches and up to three waits for the stream inside that call.  The grouping is kept for ONE
+ * (first query, count, k, HVS_SET_SCAN_CHUNK): a caller that alternates between ranges of the resident set pays it on every
+ * call; whole-set calls, the intended use, pay it once.  The partial lists of the scan (queries x chunks x CAP keys of 8 bytes,
+ * CAP = 256 for k <= 128, else 512) are allocated by the first scanned call and given back by hvs_set_row_set_scan_limit(ctx, 0).
+ *
+ * The answer is the answer of DESIGN 3.18: the same ids and distance bits, whatever is attached (caps, cursors, exclusion
+ * lists, the mask, the padding setting, both distance orders, every k, all three context kinds).  hvs_set_engine has no effect
+ * on such a call: hvs_timing.engine is HVS_ENGINE_EXACT_SCAN and retry_queries, fallback_queries and rescored_pairs are 0.
+ * THE ONE DIFFERENCE from 3.18's contract: hvs_timing.pairs counts the MEMBER rows that are in the sampled prefix, live and pass
+ * the predicate, per query -- rows outside the set are never looked at.  hvs_row_sets_info reports restricted_queries, kept_slots
+ * and underfull_queries as it would have; refused_keys is 0, because nothing outside the set is ever offered.
+ *
+ * hvs_row_set_scan_stats: scanned_sets and member_bytes (the member lists of this GPU; of a multi-GPU context: summed), and of
+ * the last call: scanned_queries (0 if the path was not taken, and then the four figures behind it are 0 too), items,
+ * member_chunks (chunks summed over the sets that have queries), scanned_pairs (member rows x queries a wave evaluated) and
+ * passing_pairs (= hvs_timing.pairs).
+ *
+ * hvs_row_set_scan_plan: pure host arithmetic, no GPU and no context -- the library calls it to make its launch.  For set s with
+ * queries_per_set[s] > 0 queries (sorted by set, so its group is places [G, G + queries) with G the sum of the groups in front)
+ * and rows_per_set[s] members: tiles = ceil(queries / 256) and chunks of `rows` members each, where
+ *     rows = chunk_rows                                           if chunk_rows != 0 (the environment's HVS_SET_SCAN_CHUNK),
+ *     else want = ceil(workgroups / T), T = the tiles of all sets; rows = max(ceil(members / want), 16 * k), rounded up to a
+ *     multiple of 16
+ * and chunks = max(1, ceil(members / rows)): a call of few queries on a large set is cut until it fills `workgroups`
+ * workgroups, but never into chunks of fewer than 16 * k rows (each chunk hands a partial list of fewer than CAP keys per query
+ * to the merge, which cuts to k).  Items are
+ * written set by set, tile by tile, chunk by chunk: {set, q_begin, q_end (places in the sorted order), m_begin, m_end (places in
+ * the set's member list), slot}; the query at place q_begin + j leaves its partial list in slot `slot + j`, and slots are handed
+ * out densely in item order.  Returns the number of items; at most max_items are written (items may be NULL); *slots, where not
+ * NULL, is the number of partial-list slots.  A set without queries has no item; a set without members has one per tile, empty.
+ */
+typedef struct hvs_row_set_scan_info {
+    uint32_t scanned_sets;
+    uint32_t scanned_queries;
+    uint64_t member_bytes;
+    uint32_t items;
+    uint32_t member_chunks;
+    uint64_t scanned_pairs;
+    uint64_t passing_pairs;
+} hvs_row_set_scan_info;
+typedef struct hvs_row_set_scan_item {
+    uint32_t set, q_begin, q_end, m_begin, m_end, slot;
+} hvs_row_set_scan_item;
+int hvs_set_row_set_scan_limit(hvs_ctx *ctx, uint32_t rows);
+uint32_t hvs_get_row_set_scan_limit(hvs_ctx *ctx);
+int hvs_row_set_scan_stats(hvs_ctx *ctx, hvs_row_set_scan_info *out);
+uint32_t hvs_row_set_scan_plan(const uint32_t *queries_per_set, const uint32_t *rows_per_set, uint32_t n_sets, uint32_t k,
+                               uint32_t chunk_rows, uint32_t workgroups, hvs_row_set_scan_item *items, uint32_t max_items,
+                               uint64_t *slots);
+
 #ifdef __cplusplus
 }
 #endif

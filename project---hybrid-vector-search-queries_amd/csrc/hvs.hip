@@ -27,6 +27,7 @@
 #include "../../include/hvs.h"
 #include "hvs_kernels.h"
 #include "hvs_filter.h"
+#include "hvs_set_scan.h"
 
 namespace {
 
@@ -151,6 +152,17 @@ struct HvsRowSet {
     uint32_t* d_sets_ids = nullptr;  // hvs_assign_row_sets' id list, kept between calls
     uint32_t sets_ids_cap = 0;
     uint32_t *d_cmp_sets = nullptr, *d_sets_next = nullptr;  // per-call: hvs_compact's bounce bitmap of one set; a re-strided copy
+    // -- scanned sets: a set of at most scan_limit members (of this GPU's rows) has a member list -- ascending local
+    // ids at d_scan_members[h_scan_mem_off[s] ..), h_scan_pop[s] of them; mem_off 0xFFFFFFFF: not scanned.  While scan_lists_valid
+    // is false none of it is read: whatever changes a bit of d_sets, the rows it describes or the limit clears the flag, and the
+    // first call that could take the path rebuilds the lists (scan_lists_build).
+    uint32_t scan_limit = 0;        // hvs_set_row_set_scan_limit (0: never); a setting, kept by every reset
+    bool scan_lists_valid = false;
+    uint32_t *d_scan_members = nullptr, *d_scan_pop = nullptr, *d_scan_mem_off = nullptr, *d_scan_blk = nullptr;
+    uint32_t scan_members_cap = 0, scan_tab_cap = 0, scan_blk_cap = 0;
+    std::vector<uint32_t> h_scan_pop, h_scan_mem_off;
+    uint32_t scan_sets = 0;         // sets that have a member list
+    uint64_t scan_entries = 0;      // entries of all member lists
     // the device buffers this state owns, in two lists: the per-call ones, and all (D and HvsOrdering::lp are the context's)
     template <typename... P>
     static void drop(P*&... p) { (((void)(p ? hipFree(p) : hipSuccess), p = nullptr), ...); }
@@ -159,10 +171,13 @@ struct HvsRowSet {
     {
         drop(d_sets);
         n_sets = sets_words = sets_part_rows = sets_row0 = 0;
+        scan_lists_valid = false;
     }
     void free_device()
     {
         drop(d_live, d_pad_ids, d_mask_stat, d_stale_ids, d_ilive, d_mask_ids, d_upd_rows, d_upd_ids, d_upd_from, d_sets_ids);
+        drop(d_scan_members, d_scan_pop, d_scan_mem_off, d_scan_blk);
+        scan_members_cap = scan_tab_cap = scan_blk_cap = 0;
         drop_sets();
         free_call_buffers();
         live_cap = stale_cap = ilive_cap = mask_ids_cap = upd_cap = sets_ids_cap = 0;
@@ -407,6 +422,39 @@ struct HvsQuerySet {
     bool covers(uint32_t nq, uint32_t k) const { return res_k == k && res_lo == 0u && res_hi >= nq; }
 };
 
+// The query side of the scanned sets on one GPU: resident queries [q0, q0 + nq) counting-sorted by set index
+// (d_order, d_goff), the item table of hvs_row_set_scan_plan for them and the partial lists the items write.  `valid`: all of it
+// describes the indices, member lists, k and chunk setting in force; `taken`: every one of those queries carries the index of a
+// scanned set, so a call over them takes the path.  Cleared where the indices are committed and where the member lists are rebuilt.
+struct HvsSetScan {
+    uint32_t *d_order = nullptr, *d_goff = nullptr, *d_hist = nullptr, *d_set_item0 = nullptr, *d_set_chunks = nullptr, *d_list_cnt = nullptr;
+    HvsScanItem* d_items = nullptr;
+    uint64_t* d_lists = nullptr;
+    uint32_t order_cap = 0, goff_cap = 0, hist_cap = 0, tab_cap = 0, items_cap = 0, cnt_cap = 0;
+    size_t lists_cap = 0;
+    bool valid = false, taken = false;
+    uint32_t q0 = 0, nq = 0, k = 0, chunk = 0;  // what the grouping and the plan were made for
+    uint32_t n_items = 0, chunks = 0;
+    bool call = false;  // the last call took the path ...
+    uint32_t call_nq = 0, call_items = 0, call_chunks = 0;  // ... with these
+    void drop_lists()  // (the next call that takes the path groups and allocates again; the last call's figures stay)
+    {
+        HvsRowSet::drop(d_list_cnt);
+        HvsRowSet::drop(d_lists);
+        cnt_cap = 0, lists_cap = 0;
+        valid = false;
+    }
+    void free_device()
+    {
+        HvsRowSet::drop(d_order, d_goff, d_hist, d_set_item0, d_set_chunks, d_list_cnt);
+        HvsRowSet::drop(d_items);
+        HvsRowSet::drop(d_lists);
+        order_cap = goff_cap = hist_cap = tab_cap = items_cap = cnt_cap = 0;
+        lists_cap = 0;
+        valid = call = false;
+    }
+};
+
 // What a call LEAVES BEHIND on one GPU until the next one: the device counters its kernels added to, the queries
 // it could not answer with their re-runs, and the report that hvs_last_timing and the *_stats calls read.  The invariants:
 //   - `valid`: a call has been enqueued (call_enqueued) since the last event that forgets it (call_forgotten, or a later call that
@@ -618,6 +666,7 @@ struct hvs_ctx : HvsLane {
     uint32_t res_cap = 0;
     HvsQuerySet qs;
     HvsCallState call;  // what the last call left behind: counters, re-run lists, the report
+    HvsSetScan scan;    // scanned sets: the resident queries grouped by set, the item table, the partial lists
 
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
@@ -2405,6 +2454,157 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     return call_enqueued(c, nq, false, cut.sn);
 }
 
+// ---- scanned sets ----
+static_assert(sizeof(HvsScanItem) == sizeof(hvs_row_set_scan_item) && offsetof(HvsScanItem, slot) == offsetof(hvs_row_set_scan_item, slot),
+              "the kernels' item is the contract's");
+// The member lists of this GPU: populations of all sets over the window of its rows (hvs_k_row_set_popcount; the <= 256 counts
+// come back to the host, which decides which sets are scanned and sizes the buffer), then hvs_k_row_set_fill.
+int scan_lists_build(hvs_ctx* c)
+{
+    HvsRowSet& s = c->rs;
+    const uint32_t ns = s.n_sets;
+    const uint64_t g0 = s.sets_row0, g1 = std::min<uint64_t>(g0 + c->n, 0xFFFFFFFFull);
+    const uint32_t w0 = (uint32_t)(g0 >> 5), w1 = (uint32_t)std::min<uint64_t>((g1 + 31u) >> 5, s.sets_words);
+    const uint32_t nb = std::max(1u, hvs_ceil_div(w1 > w0 ? w1 - w0 : 0u, HVS_SETSCAN_SPAN));
+    int rc;
+    if ((rc = ensure_room(c, &s.d_scan_pop, s.scan_tab_cap, HVS_ROW_SETS_MAX, &s.d_scan_mem_off)) ||
+        (rc = ensure_room(c, &s.d_scan_blk, s.scan_blk_cap, (size_t)ns * nb)))
+        return rc;
+    HVS_HIP(c, hipMemsetAsync(s.d_scan_pop, 0, HVS_ROW_SETS_MAX * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(hvs_k_row_set_popcount, dim3(nb, ns), dim3(256), 0, c->stream, s.d_sets, s.sets_words, w0, w1, (uint32_t)g0, (uint32_t)g1,
+                       s.d_scan_blk, s.d_scan_pop);
+    HVS_HIP(c, hipGetLastError());
+    s.h_scan_pop.assign(ns, 0u);
+    HVS_HIP(c, hipMemcpyAsync(s.h_scan_pop.data(), s.d_scan_pop, (size_t)ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    s.h_scan_mem_off.assign(ns, 0xFFFFFFFFu);
+    uint64_t total = 0;
+    s.scan_sets = 0;
+    for (uint32_t i = 0; i < ns; ++i)
+        if (s.h_scan_pop[i] <= s.scan_limit && total + s.h_scan_pop[i] < 0xFFFFFFFFull) {
+            s.h_scan_mem_off[i] = (uint32_t)total;
+            total += s.h_scan_pop[i];
+            ++s.scan_sets;
+        }
+    s.scan_entries = total;
+    if ((rc = ensure_room(c, &s.d_scan_members, s.scan_members_cap, std::max<uint64_t>(total, 1u)))) return rc;
+    HVS_HIP(c, hipMemcpyAsync(s.d_scan_mem_off, s.h_scan_mem_off.data(), (size_t)ns * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (total) {
+        hipLaunchKernelGGL(hvs_k_row_set_fill, dim3(nb, ns), dim3(256), 0, c->stream, s.d_sets, s.sets_words, w0, w1, (uint32_t)g0, (uint32_t)g1,
+                           s.d_scan_blk, s.d_scan_mem_off, s.d_scan_pop, s.d_scan_members, (uint32_t)s.scan_members_cap);
+        HVS_HIP(c, hipGetLastError());
+    }
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (h_scan_mem_off is read by the copy)
+    s.scan_lists_valid = true;
+    c->scan.valid = false;
+    return HVS_OK;
+}
+
+// Resident queries [q0, q0 + nq) sorted by set index on the device; the group sizes come back (<= 258 words) and decide whether
+// the range takes the path; if it does, the item table of hvs_row_set_scan_plan goes up and the partial lists get their room.
+int scan_group(hvs_ctx* c, uint32_t q0, uint32_t nq, uint32_t chunk)
+{
+    HvsSetScan& g = c->scan;
+    const HvsRowSet& s = c->rs;
+    const uint32_t ns = s.n_sets, nb = hvs_ceil_div(nq, HVS_GROUP_SPAN);
+    int rc;
+    g.valid = false;
+    if ((rc = ensure_room(c, &g.d_order, g.order_cap, nq)) || (rc = ensure_room(c, &g.d_goff, g.goff_cap, HVS_GROUP_BINS + 1u)) ||
+        (rc = ensure_room(c, &g.d_hist, g.hist_cap, (size_t)nb * HVS_GROUP_BINS)) ||
+        (rc = ensure_room(c, &g.d_set_item0, g.tab_cap, HVS_ROW_SETS_MAX, &g.d_set_chunks)))
+        return rc;
+    hvs_launch_group_queries(c->stream, c->qs.eng.d_set_of, q0, nq, ns, g.d_hist, g.d_goff, g.d_order);
+    HVS_HIP(c, hipGetLastError());
+    std::vector<uint32_t> goff(ns + 2u);
+    HVS_HIP(c, hipMemcpyAsync(goff.data(), g.d_goff, goff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> group(ns);
+    bool taken = goff[ns + 1u] == goff[ns];  // (no query without a set)
+    for (uint32_t i = 0; i < ns; ++i) {
+        group[i] = goff[i + 1u] - goff[i];
+        if (group[i] && s.h_scan_mem_off[i] == 0xFFFFFFFFu) taken = false;  // (a query on a denser set)
+    }
+    g.q0 = q0, g.nq = nq, g.k = c->k, g.chunk = chunk;
+    g.taken = false;
+    if (!taken) return g.valid = true, HVS_OK;
+    const uint32_t wgs = 2u * (uint32_t)c->num_cus;
+    uint64_t slots = 0;
+    const uint32_t n_items = hvs_row_set_scan_plan(group.data(), s.h_scan_pop.data(), ns, c->k, chunk, wgs, nullptr, 0u, &slots);
+    if (slots >= 0xFFFFFFFFull) return fail(c, HVS_ENOMEM, "scanned sets: more than 2^32 - 1 partial lists (shorten the call or raise HVS_SET_SCAN_CHUNK)");
+    std::vector<hvs_row_set_scan_item> items(std::max(n_items, 1u));
+    (void)hvs_row_set_scan_plan(group.data(), s.h_scan_pop.data(), ns, c->k, chunk, wgs, items.data(), n_items, nullptr);
+    std::vector<uint32_t> item0(HVS_ROW_SETS_MAX, 0u), chunks(HVS_ROW_SETS_MAX, 0u);
+    g.chunks = 0;
+    for (uint32_t i = n_items; i-- > 0u;) item0[items[i].set] = i;  // (the first item of every set)
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].q_begin == items[item0[items[i].set]].q_begin) ++chunks[items[i].set];  // (the items of the set's first tile)
+    for (uint32_t i = 0; i < ns; ++i) g.chunks += chunks[i];
+    const int cap = c->k <= 128u ? 256 : 512;
+    if ((rc = ensure_room(c, &g.d_items, g.items_cap, std::max(n_items, 1u))) || (rc = ensure_room(c, &g.d_list_cnt, g.cnt_cap, std::max<uint64_t>(slots, 1u))) ||
+        (rc = ensure_room(c, &g.d_lists, g.lists_cap, std::max<uint64_t>(slots, 1u) * (size_t)cap)))
+        return rc;
+    HVS_HIP(c, hipMemcpyAsync(g.d_items, items.data(), (size_t)n_items * sizeof(HvsScanItem), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(g.d_set_item0, item0.data(), HVS_ROW_SETS_MAX * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipMemcpyAsync(g.d_set_chunks, chunks.data(), HVS_ROW_SETS_MAX * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HVS_HIP(c, hipStreamSynchronize(c->stream));  // (the three tables are on this stack)
+    g.n_items = n_items;
+    g.taken = true;
+    g.valid = true;  // (only now: a step that failed above leaves the grouping to be made again)
+    return HVS_OK;
+}
+
+// Does a call over resident queries [q0, q0 + nq) take the path?  Nothing but host tests while the limit is 0, no indices are
+// attached or the expanded set is; otherwise the member lists and the grouping are brought up to date first, which costs
+// launches only after something changed them (the bitmaps, the limit, the indices, k, HVS_SET_SCAN_CHUNK or the range).
+int set_scan_prepare(hvs_ctx* c, uint32_t q0, uint32_t nq, bool* take)
+{
+    *take = false;
+    if (c->rs.scan_limit == 0u || !has_rset(c) || c->qs.in.active || nq == 0u) return HVS_OK;
+    const uint32_t chunk = env_u32("HVS_SET_SCAN_CHUNK", 0u, 0u, 0xFFFFFFFFu);  // (read per call, like HVS_COMPACT_CHUNK)
+    int rc = HVS_OK;
+    if (!c->rs.scan_lists_valid && (rc = scan_lists_build(c))) return rc;
+    const HvsSetScan& g = c->scan;
+    if (!(g.valid && g.q0 == q0 && g.nq == nq && g.k == c->k && g.chunk == chunk) && (rc = scan_group(c, q0, nq, chunk))) return rc;
+    *take = g.taken;
+    return HVS_OK;
+}
+
+// Resident queries [q0, q0 + nq), every one on a scanned set (set_scan_prepare said so): hvs_k_scan_set_members over the item
+// table, then hvs_k_merge_set_chunks, a wave per query, straight into the result rows.  As under candidate lists no engine, no
+// index and no re-run is involved, and the call leaves behind what a call leaves behind.
+template <typename Hooks>
+int run_set_scan(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hooks)
+{
+    HvsQuerySet& s = c->qs;
+    HvsSetScan& g = c->scan;
+    s.call_capped = capped(c);
+    s.call_after = has_after(c);
+    s.excl.call = has_excl(c);
+    s.call_rset = true;
+    s.cand.call = false;
+    s.in.call = false;
+    s.answered(q0, nq, c->k, s.set_gen);
+    int rc = call_begin(c);
+    if (rc) return rc;
+    if ((rc = hooks.before(0u, nq))) return rc;
+    const int ev = kernel_timer_begin(c);
+    const HvsExcl lists = excl_arg(c);  // (the scan tells "no lists" by null pointers; a member needs no set test)
+    const bool ex = has_excl(c);
+    const HvsSetScanArgs a{c->d_data, c->n, cut.sampled ? std::min(cut.sn, c->n) : 0u, c->d_q, g.d_order, nq, g.d_items, c->rs.d_scan_mem_off,
+                           c->rs.d_scan_members, masked(c) ? c->rs.d_live : nullptr, capped(c) ? s.eng.d_max_d2 : nullptr,
+                           has_after(c) ? s.eng.d_after_lo : nullptr, ex ? lists.begin : nullptr, ex ? lists.count : nullptr, ex ? lists.ids : nullptr,
+                           s.eng.d_set_of, c->rs.n_sets, g.d_goff, g.d_set_item0, g.d_set_chunks, g.d_lists, g.d_list_cnt, c->padding ? 1 : 0,
+                           masked(c) ? c->rs.d_pad_ids : nullptr, c->d_out_ids, c->d_out_dists, c->k, c->call.d_counters};
+    const int cap = c->k <= 128u ? 256 : 512;
+    hvs_launch_set_scan(c->stream, c->scalar_order, cap, g.n_items, a);
+    kernel_timer_end(c, ev);
+    HVS_HIP(c, hipGetLastError());
+    if ((rc = hooks.after(0u, nq, 0u))) return rc;
+    g.call = true;
+    g.call_nq = nq, g.call_items = g.n_items, g.call_chunks = g.chunks;
+    return call_enqueued(c, nq, false, cut.sn);
+}
+
 // Hooks of run_queries: `before(off, nqb)` is called before the kernels of a batch are enqueued (hvs_query makes the
 // compute stream wait for the batch's queries there: a batch never starts before its input is on the device);
 // `after(off, nqb, next_nqb)` after they have been enqueued (the host pipeline of hvs_query hangs its copies there);
@@ -2417,8 +2617,12 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
+    c->scan.call = false;
     if (has_cand(c)) return run_candidates(c, q0, nq, cut, hooks);
     c->qs.cand.call = false;
+    bool scan_sets = false;  // (every query of the range carries the index of a scanned set)
+    if (int rc = set_scan_prepare(c, q0, nq, &scan_sets)) return rc;
+    if (scan_sets) return run_set_scan(c, q0, nq, cut, hooks);
     const uint32_t sn = cut.sn, sampled = cut.sampled, of_rows = cut.of_rows;
     // The index orders ALL rows: with a sampled prefix [0,sn) the filter still proposes rows >= sn and the
     // exact stages drop them, so its candidate lists grow by n/sn -- used down to sn = n/4, below that
@@ -2570,6 +2774,7 @@ void leaf_destroy(hvs_ctx* c)
         if (p) (void)hipFree(p);
     c->rs.free_device();
     c->qs.free_device();
+    c->scan.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     {
         HvsPart& P = c->part;
@@ -3127,6 +3332,7 @@ void sets_swap_next(hvs_ctx* c, uint32_t n_sets, uint32_t words)
     HvsRowSet::drop(s.d_sets);
     s.d_sets = s.d_sets_next;
     s.d_sets_next = nullptr;
+    s.scan_lists_valid = false;
     s.n_sets = n_sets;
     s.sets_words = words;
 }
@@ -3178,6 +3384,7 @@ int leaf_assign_row_sets(hvs_ctx* c, uint32_t set, const uint32_t* ids, uint32_t
     if (rc) return rc;
     if ((rc = ensure_room(c, &s.d_sets_ids, s.sets_ids_cap, count))) return rc;
     HVS_HIP(c, hipMemcpyAsync(s.d_sets_ids, ids, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    s.scan_lists_valid = false;  // (a bit changes: the member lists go)
     hipLaunchKernelGGL(hvs_k_row_sets_assign, dim3(hvs_ceil_div(count, 256u)), dim3(256), 0, c->stream, s.d_sets_ids, count, set_rows(c),
                        s.d_sets + (size_t)set * s.sets_words, member);
     HVS_HIP(c, hipGetLastError());
@@ -3217,6 +3424,7 @@ int leaf_query_sets_commit(hvs_ctx* c, uint32_t count)
     int rc;
     HVS_HIP(c, hipSetDevice(c->device));
     s.rset_set = false;  // (the buffers are about to change)
+    c->scan.valid = false;  // (scanned sets, DESIGN 3.19: the grouping is of the old indices)
     if ((rc = ensure_room(c, &dst.d_set_of, dst.set_of_cap, std::max(count, 1u))) ||
         (sets && (rc = ensure_room(c, &s.eng.d_set_of, s.eng.set_of_cap, std::max(c->nq, 1u)))) ||
         (rc = ensure_room(c, &s.d_rs_zero, s.rs_zero_cap, std::max(c->nq, 1u))))
@@ -4440,6 +4648,7 @@ int leaf_compact_commit(hvs_ctx* c, const std::vector<uint32_t>& rank, uint32_t 
     HVS_HIP(c, hipMemcpyAsync(c->rs.d_cmp_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     // The shared row sets are renumbered first, while the mask and the rank table describe the old numbering: set
     // by set the bits of the live rows are packed into the zeroed bounce bitmap and copied back over the set.
+    c->rs.scan_lists_valid = false;  // (the member lists name the old ids)
     for (uint32_t st = 0; st < c->rs.n_sets; ++st) {
         uint32_t* set = c->rs.d_sets + (size_t)st * c->rs.sets_words;
         const size_t bytes = (size_t)c->rs.sets_words * sizeof(uint32_t);
@@ -6494,6 +6703,97 @@ int hvs_row_sets_stats(hvs_ctx* c, hvs_row_sets_info* out)
     sum.bytes = (uint64_t)L->rs.n_sets * L->rs.sets_words * sizeof(uint32_t);
     *out = sum;
     return HVS_OK;
+}
+
+// ---- scanned row sets (include/hvs.h "scanned row sets") --------------------------
+
+int hvs_set_row_set_scan_limit(hvs_ctx* c, uint32_t rows)
+{
+    if (!c) return HVS_EINVAL;
+    // (the sets that are scanned change with the limit: the member lists are rebuilt by the next call that could use them)
+    // limit 0: the path cannot be taken, so the partial lists (slots x CAP keys, the one large buffer of the feature) are given back
+    return on_every_leaf(c, [&](hvs_ctx* k) -> int {
+        k->rs.scan_limit = rows;
+        k->rs.scan_lists_valid = false;
+        if (rows == 0u && k->scan.d_lists) {
+            HVS_HIP(k, hipSetDevice(k->device));
+            HVS_HIP(k, hipStreamSynchronize(k->stream));
+            k->scan.drop_lists();
+        }
+        return HVS_OK;
+    });
+}
+
+uint32_t hvs_get_row_set_scan_limit(hvs_ctx* c) { return c ? mask_leaf(c)->rs.scan_limit : 0u; }
+
+// one GPU's figures; the member lists are brought up to date first, so that the sets' figures are those of the limit in force
+static int leaf_row_set_scan_stats(hvs_ctx* c, hvs_row_set_scan_info* out)
+{
+    *out = hvs_row_set_scan_info{};
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    if (c->rs.scan_limit && c->rs.n_sets) {
+        if (!c->rs.scan_lists_valid && (rc = scan_lists_build(c))) return rc;
+        out->scanned_sets = c->rs.scan_sets;
+        out->member_bytes = c->rs.scan_entries * sizeof(uint32_t);
+    }
+    if (!c->call.valid || !c->scan.call) return HVS_OK;
+    unsigned long long v[2] = {0, 0};
+    if ((rc = call_counters(c, HVS_CNT_PAIRS, v))) return rc;
+    out->scanned_queries = c->scan.call_nq;
+    out->items = c->scan.call_items;
+    out->member_chunks = c->scan.call_chunks;
+    out->passing_pairs = v[0];
+    out->scanned_pairs = v[1];
+    return HVS_OK;
+}
+
+int hvs_row_set_scan_stats(hvs_ctx* c, hvs_row_set_scan_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_row_set_scan_stats(c, out);
+    hvs_row_set_scan_info sum{};
+    for (hvs_ctx* k : c->kids) {
+        hvs_row_set_scan_info m{};
+        HVS_HIP(c, hipSetDevice(k->device));
+        if (int rc = leaf_row_set_scan_stats(k, &m)) return fail(c, rc, k->err);
+        sum.scanned_sets += m.scanned_sets;
+        sum.member_bytes += m.member_bytes;
+        // (row-partitioned: every part answers every query)
+        sum.scanned_queries = c->partitioned ? std::max(sum.scanned_queries, m.scanned_queries) : sum.scanned_queries + m.scanned_queries;
+        sum.items += m.items;
+        sum.member_chunks += m.member_chunks;
+        sum.scanned_pairs += m.scanned_pairs;
+        sum.passing_pairs += m.passing_pairs;
+    }
+    *out = sum;
+    return HVS_OK;
+}
+
+uint32_t hvs_row_set_scan_plan(const uint32_t* queries_per_set, const uint32_t* rows_per_set, uint32_t n_sets, uint32_t k, uint32_t chunk_rows,
+                               uint32_t workgroups, hvs_row_set_scan_item* items, uint32_t max_items, uint64_t* slots)
+{
+    uint64_t tiles = 0;
+    for (uint32_t s = 0; s < n_sets; ++s) tiles += (queries_per_set[s] + 255ull) / 256u;
+    const uint64_t want = tiles ? std::max<uint64_t>(1u, (workgroups + tiles - 1u) / tiles) : 1u;
+    uint64_t n_items = 0, slot = 0, first = 0;
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        const uint64_t q = queries_per_set[s], p = rows_per_set[s];
+        if (!q) continue;
+        const uint64_t rows = chunk_rows ? chunk_rows : (std::max<uint64_t>((p + want - 1u) / want, 16ull * k) + 15u) / 16u * 16u;
+        const uint64_t chunks = std::max<uint64_t>(1u, (p + rows - 1u) / rows);
+        for (uint64_t qb = first; qb < first + q; qb += 256u) {
+            const uint64_t qe = std::min(first + q, qb + 256u);
+            for (uint64_t ch = 0; ch < chunks; ++ch, ++n_items) {
+                if (items && n_items < max_items)
+                    items[n_items] = hvs_row_set_scan_item{s, (uint32_t)qb, (uint32_t)qe, (uint32_t)(ch * rows), (uint32_t)std::min(p, (ch + 1u) * rows), (uint32_t)slot};
+                slot += qe - qb;
+            }
+        }
+        first += q;
+    }
+    if (slots) *slots = slot;
+    return (uint32_t)std::min<uint64_t>(n_items, 0xFFFFFFFFull);
 }
 
 // ---- category sets (include/hvs.h "category sets") -------------------------------

@@ -156,6 +156,15 @@ class RowSetsInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class RowSetScanInfo(C.Structure):
+    """hvs_row_set_scan_info (include/hvs.h)."""
+    _fields_ = [("scanned_sets", C.c_uint32), ("scanned_queries", C.c_uint32), ("member_bytes", C.c_uint64), ("items", C.c_uint32),
+                ("member_chunks", C.c_uint32), ("scanned_pairs", C.c_uint64), ("passing_pairs", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
 CANDIDATES_MAX = 8192
@@ -346,6 +355,10 @@ def library():
         "hvs_query_in_row_sets": (C.c_int, [vp, _f32p, _u32p, C.c_uint32, C.c_float, _u32p, _f32p]),
         "hvs_row_sets_stats": (C.c_int, [vp, C.POINTER(RowSetsInfo)]),
         "hvs_row_sets_compact_plan": (None, [_u64p, _u64p, C.c_uint32, C.c_uint32, _u64p]),
+        "hvs_set_row_set_scan_limit": (C.c_int, [vp, C.c_uint32]),
+        "hvs_get_row_set_scan_limit": (C.c_uint32, [vp]),
+        "hvs_row_set_scan_stats": (C.c_int, [vp, C.POINTER(RowSetScanInfo)]),
+        "hvs_row_set_scan_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p]),
         "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
         "hvs_set_query_vectors_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "hvs_query_vectors": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
@@ -417,6 +430,20 @@ def row_sets_compact_plan(sets, live):
     if n_sets and full[:, n_live:].any():
         raise HvsError(-1, "hvs_row_sets_compact_plan left bits at or past the live rows")
     return full[:, :n_live]
+
+
+def row_set_scan_plan(queries_per_set, rows_per_set, k, chunk_rows=0, workgroups=512):
+    """hvs_row_set_scan_plan: the item table of a scanned-set call as an (items, 6) uint32 array of (set, q_begin, q_end,
+    m_begin, m_end, slot), and the number of partial-list slots."""
+    q = np.ascontiguousarray(queries_per_set, dtype=np.uint32)
+    r = np.ascontiguousarray(rows_per_set, dtype=np.uint32)
+    if q.shape != r.shape or q.ndim != 1:
+        raise ValueError("queries_per_set and rows_per_set are two vectors of one length")
+    slots = C.c_uint64(0)
+    n = library().hvs_row_set_scan_plan(_up(q), _up(r), q.size, k, chunk_rows, workgroups, None, 0, C.byref(slots))
+    items = np.zeros((max(n, 1), 6), dtype=np.uint32)
+    library().hvs_row_set_scan_plan(_up(q), _up(r), q.size, k, chunk_rows, workgroups, _up(items), n, None)
+    return items[:n], slots.value
 
 
 def mask_plan(live, k, sample_proportion):
@@ -1232,6 +1259,18 @@ class Engine:
         return e
 
     # --- per-query candidate lists (include/hvs.h "per-query candidate lists")
+    def set_row_set_scan_limit(self, rows):
+        """A loaded row set of at most `rows` members (per GPU) is answered by scanning its members (0: never; include/hvs.h)."""
+        self._ck(self._lib.hvs_set_row_set_scan_limit(self._h, int(rows)))
+
+    def row_set_scan_limit(self):
+        return int(self._lib.hvs_get_row_set_scan_limit(self._h))
+
+    def row_set_scan_stats(self):
+        info = RowSetScanInfo()
+        self._ck(self._lib.hvs_row_set_scan_stats(self._h, C.byref(info)))
+        return info
+
     def set_candidate_ids(self, lists, stream=None):
         """Attach one candidate list per resident query: a list of per-query id sequences or an (offsets, ids) pair of host
         arrays (hvs_set_candidate_ids), an (offsets, ids) pair of GPU tensors (hvs_set_candidate_ids_device: int32 / uint32,
