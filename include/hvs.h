@@ -1053,6 +1053,52 @@ int hvs_download_candidates_plan(hvs_ctx *ctx, uint32_t *begin, uint32_t *count 
 uint32_t hvs_candidates_plan(const uint32_t *offsets, const uint32_t *ids, uint32_t nq, uint32_t row0, uint32_t n_rows, uint32_t *begin,
                              uint32_t *count, uint32_t *out_ids);
 
+/* ---- split candidate scans ------------------------------------------------------------------------------
+ * hvs_k_scan_candidates gives a whole list to one wave, so a call of a few queries with long lists uses a few of the chip's
+ * SIMDs, and a call of uneven lists ends with its longest waves.  A SPLIT call cuts every normalised list into pieces of
+ * chunk_ids entries; one wave scans a piece (hvs_k_scan_candidate_items) and, where a query has several, leaves its <= k nearest
+ * keys in a partial list; one wave per such query merges them (hvs_k_merge_candidate_items).  A query of one piece is finished by
+ * the wave that scanned it, exactly as before.
+ *
+ * hvs_set_candidate_split: 0 (the default) means never: every call then runs the kernels it ran before, with the same arguments.
+ * Otherwise a multiple of 64 in [64, HVS_CANDIDATES_MAX]; anything else is HVS_EINVAL and nothing changes.  Context state like
+ * hvs_set_tail_limit and hvs_set_row_set_scan_limit, it survives what they survive; every context kind accepts it, and each GPU
+ * or part plans over its own normalised lists.  No value is chosen automatically.
+ *
+ * A call that would run hvs_k_scan_candidates takes the path when chunk_ids != 0, at least one normalised list of the call's
+ * range is longer than chunk_ids, and NO ROW-SET INDICES are attached (see below).  Otherwise it is the unsplit launch, unchanged.
+ * The plan (items, first item of every query, the split queries) is made on the device from the lists' counts and kept for ONE
+ * (first query, count, chunk, attached lists): a repeated call costs host tests only; a new range, a new chunk or
+ * hvs_set_candidate_ids* makes the next call plan again, which costs three small launches and one wait for the stream.  The
+ * partial lists (items x k keys of 8 bytes) are allocated by the first split call -- HVS_ENOMEM leaves the context as it was --
+ * and given back by hvs_set_candidate_split(ctx, 0).
+ *
+ * The answer is the unsplit call's bit for bit: ids, distance bits, the (dist asc, id asc) tie rule, padding and empty slots,
+ * hvs_timing.pairs and scanned_pairs, hvs_candidates_stats, and the slots / under-full counts hvs_within_stats, hvs_after_stats
+ * and hvs_exclude_stats report.  hvs_timing.main_kernel_ms and hvs_candidates_info.scan_ms SPAN ALL LAUNCHES OF THE PATH, the scan
+ * over the items and the merge.  Every piece prunes under a threshold of its own.  That is why a call with row-set indices is
+ * not split: hvs_row_sets_info.refused_keys counts keys that every other test admitted, the threshold among them, so it depends
+ * on the thresholds ONE wave went through on the whole list, which pieces scanned side by side cannot reproduce.
+ *
+ * hvs_candidates_split_plan: pure host arithmetic, no GPU and no context; the device plans by the same rule.  Query q has
+ * pieces = max(1, ceil(counts[q] / chunk_ids)) items (chunk_ids == 0: one), piece p covering entries [p * chunk_ids,
+ * min(counts[q], (p + 1) * chunk_ids)) of the normalised list; first_item[q] (nq + 1 entries, may be NULL) is the first item of
+ * query q in query order, *split_queries (may be NULL) the queries with more than one piece.  Returns the number of items.
+ * hvs_candidates_split_stats, after hvs_sync or hvs_query: chunk_ids in force; ran: 1 if the last call took the path, else 0 and
+ * the three figures behind it are 0; split_queries, items; partial_bytes = items x k x 8.  Multi-GPU contexts: summed.
+ */
+typedef struct hvs_candidates_split_info {
+    uint32_t chunk_ids;
+    uint32_t ran;
+    uint32_t split_queries;
+    uint32_t items;
+    uint64_t partial_bytes;
+} hvs_candidates_split_info;
+int hvs_set_candidate_split(hvs_ctx *ctx, uint32_t chunk_ids);
+int hvs_candidates_split_stats(hvs_ctx *ctx, hvs_candidates_split_info *out);
+uint32_t hvs_candidates_split_plan(const uint32_t *counts, uint32_t nq, uint32_t chunk_ids, uint32_t *first_item /* nq + 1, may be NULL */,
+                                   uint32_t *split_queries /* may be NULL */);
+
 /* ---- shared row sets: the k nearest rows inside a per-query bitmap ---------------------------------- */
 /*
  * A row set is a bitmap over the rows of D that MANY queries share: the rows a tenant owns, the rows an access-control group may

@@ -28,6 +28,7 @@
 #include "hvs_kernels.h"
 #include "hvs_filter.h"
 #include "hvs_set_scan.h"
+#include "hvs_cand_split.h"
 
 namespace {
 
@@ -157,6 +158,7 @@ struct HvsRowSet {
     // is false none of it is read: whatever changes a bit of d_sets, the rows it describes or the limit clears the flag, and the
     // first call that could take the path rebuilds the lists (scan_lists_build).
     uint32_t scan_limit = 0;        // hvs_set_row_set_scan_limit (0: never); a setting, kept by every reset
+    uint32_t cand_split = 0;        // hvs_set_candidate_split (0: never); a setting, kept by every reset
     bool scan_lists_valid = false;
     uint32_t *d_scan_members = nullptr, *d_scan_pop = nullptr, *d_scan_mem_off = nullptr, *d_scan_blk = nullptr;
     uint32_t scan_members_cap = 0, scan_tab_cap = 0, scan_blk_cap = 0;
@@ -455,6 +457,38 @@ struct HvsSetScan {
     }
 };
 
+// Split candidate scans on one GPU: the item plan of resident queries [q0, q0 + nq) for chunks of `chunk` entries
+// (d_items, d_first_item, d_split_q; made on the device from the normalised lists' counts) and the partial lists the pieces of
+// split queries write (n_items x k keys).  `valid`: the plan describes the lists and the chunk in force; cleared where candidate
+// lists are committed and where the chunk changes.  n_split == 0: no list of the range is longer than a chunk, the call is not split.
+struct HvsCandSplit {
+    HvsCandItem* d_items = nullptr;
+    uint32_t *d_blk = nullptr, *d_tot = nullptr, *d_first_item = nullptr, *d_split_q = nullptr, *d_partial_cnt = nullptr;
+    uint64_t* d_partial = nullptr;
+    uint32_t items_cap = 0, blk_cap = 0, tot_cap = 0, first_cap = 0, split_cap = 0, cnt_cap = 0;
+    size_t partial_cap = 0;
+    bool valid = false;
+    uint32_t q0 = 0, nq = 0, chunk = 0;  // what the plan was made for
+    uint32_t n_items = 0, n_split = 0;
+    bool call = false;  // the last call took the path ...
+    uint32_t call_items = 0, call_split = 0;  // ... with these
+    uint64_t call_bytes = 0;
+    void drop_partial()  // (the last call's figures stay)
+    {
+        HvsRowSet::drop(d_partial_cnt);
+        HvsRowSet::drop(d_partial);
+        cnt_cap = 0, partial_cap = 0;
+    }
+    void free_device()
+    {
+        HvsRowSet::drop(d_blk, d_tot, d_first_item, d_split_q);
+        HvsRowSet::drop(d_items);
+        drop_partial();
+        items_cap = blk_cap = tot_cap = first_cap = split_cap = 0;
+        valid = call = false;
+    }
+};
+
 // What a call LEAVES BEHIND on one GPU until the next one: the device counters its kernels added to, the queries
 // it could not answer with their re-runs, and the report that hvs_last_timing and the *_stats calls read.  The invariants:
 //   - `valid`: a call has been enqueued (call_enqueued) since the last event that forgets it (call_forgotten, or a later call that
@@ -667,6 +701,7 @@ struct hvs_ctx : HvsLane {
     HvsQuerySet qs;
     HvsCallState call;  // what the last call left behind: counters, re-run lists, the report
     HvsSetScan scan;    // scanned sets: the resident queries grouped by set, the item table, the partial lists
+    HvsCandSplit split; // split candidate scans: the item plan of a range of queries, the partial lists
 
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
@@ -2454,6 +2489,82 @@ int run_candidates(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hoo
     return call_enqueued(c, nq, false, cut.sn);
 }
 
+// ---- split candidate scans ----
+// Does a call under candidate lists over resident queries [q0, q0 + nq) take the split path?  Host tests only while the chunk is
+// 0, set indices are attached (hvs_row_sets_info.refused_keys depends on ONE wave's thresholds: such a call is never split) or the
+// plan in force is for this range, these lists and this chunk.  Otherwise the plan is made on the device: the counts of pieces
+// are scanned, two words come back (items, split queries), the tables get their room and are filled.  The partial lists get
+// their room here too, before the call changes anything.
+int cand_split_prepare(hvs_ctx* c, uint32_t q0, uint32_t nq, bool* take)
+{
+    *take = false;
+    const uint32_t chunk = c->rs.cand_split;
+    if (chunk == 0u || nq == 0u || has_rset(c)) return HVS_OK;
+    HvsCandSplit& g = c->split;
+    int rc;
+    if (!(g.valid && g.q0 == q0 && g.nq == nq && g.chunk == chunk)) {
+        g.valid = false;
+        const uint32_t nb = hvs_cand_split_blocks(nq);
+        if ((rc = ensure_room(c, &g.d_blk, g.blk_cap, 2u * (size_t)nb)) || (rc = ensure_room(c, &g.d_tot, g.tot_cap, 2u)) ||
+            (rc = ensure_room(c, &g.d_first_item, g.first_cap, (size_t)nq + 1u)))
+            return rc;
+        hvs_launch_cand_split_count(c->stream, c->qs.cand_at.d_count, q0, nq, chunk, g.d_blk, g.d_tot);
+        HVS_HIP(c, hipGetLastError());
+        uint32_t tot[2] = {0u, 0u};
+        HVS_HIP(c, hipMemcpyAsync(tot, g.d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        HVS_HIP(c, hipStreamSynchronize(c->stream));
+        if (tot[1]) {  // (no split query: the call is hvs_k_scan_candidates' and nothing more is needed)
+            if ((rc = ensure_room(c, &g.d_items, g.items_cap, tot[0])) || (rc = ensure_room(c, &g.d_split_q, g.split_cap, tot[1]))) return rc;
+            hvs_launch_cand_split_fill(c->stream, c->qs.cand_at.d_count, q0, nq, chunk, g.d_blk, g.d_items, tot[0], g.d_first_item, g.d_split_q, tot[1]);
+            HVS_HIP(c, hipGetLastError());
+        }
+        g.q0 = q0, g.nq = nq, g.chunk = chunk;
+        g.n_items = tot[0], g.n_split = tot[1];
+        g.valid = true;
+    }
+    if (g.n_split == 0u) return HVS_OK;
+    if ((rc = ensure_room(c, &g.d_partial, g.partial_cap, (size_t)g.n_items * c->k)) || (rc = ensure_room(c, &g.d_partial_cnt, g.cnt_cap, g.n_items)))
+        return rc;
+    *take = true;
+    return HVS_OK;
+}
+
+// Resident queries [q0, q0 + nq) under candidate lists with at least one list longer than the chunk (cand_split_prepare said so):
+// hvs_k_scan_candidate_items over the item table, then hvs_k_merge_candidate_items over the split queries, straight into the
+// result rows.  Everything else is run_candidates': the flags, the hooks, one timer around both launches, call_enqueued.
+template <typename Hooks>
+int run_candidates_split(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hooks)
+{
+    HvsQuerySet& s = c->qs;
+    HvsCandSplit& g = c->split;
+    s.call_capped = capped(c);
+    s.call_after = has_after(c);
+    s.excl.call = has_excl(c);
+    s.call_rset = false;
+    s.cand.call = true;
+    s.in.call = false;
+    s.answered(q0, nq, c->k, s.set_gen);
+    int rc = call_begin(c);
+    if (rc) return rc;
+    if ((rc = hooks.before(0u, nq))) return rc;
+    const int ev = kernel_timer_begin(c);
+    const bool ex = has_excl(c);
+    const HvsExcl cand{s.cand_at.d_begin, s.cand_at.d_count, s.cand.d_ids};
+    const HvsExcl excl{ex ? s.eng.ex.d_begin : nullptr, ex ? s.eng.ex.d_count : nullptr, ex ? s.excl.d_ids : nullptr, nullptr, nullptr, 0u, 0u};
+    const HvsCandSplitArgs a{c->d_data, c->n, cut.sampled ? cut.sn : 0u, c->d_q, q0, g.d_items, g.n_items, g.d_split_q, g.n_split, g.d_first_item, cand,
+                             masked(c) ? c->rs.d_live : nullptr, capped(c) ? s.eng.d_max_d2 : nullptr, has_after(c) ? s.eng.d_after_lo : nullptr, excl,
+                             c->padding ? 1 : 0, masked(c) ? c->rs.d_pad_ids : nullptr, c->d_out_ids, c->d_out_dists, c->k, g.d_partial, g.d_partial_cnt,
+                             c->call.d_counters};
+    hvs_launch_cand_split(c->stream, c->scalar_order, c->k <= 128u ? 256 : 512, a);
+    kernel_timer_end(c, ev);
+    HVS_HIP(c, hipGetLastError());
+    if ((rc = hooks.after(0u, nq, 0u))) return rc;
+    g.call = true;
+    g.call_items = g.n_items, g.call_split = g.n_split;
+    g.call_bytes = (uint64_t)g.n_items * c->k * sizeof(uint64_t);
+    return call_enqueued(c, nq, false, cut.sn);
+}
+
 // ---- scanned sets ----
 static_assert(sizeof(HvsScanItem) == sizeof(hvs_row_set_scan_item) && offsetof(HvsScanItem, slot) == offsetof(hvs_row_set_scan_item, slot),
               "the kernels' item is the contract's");
@@ -2618,7 +2729,12 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
     c->scan.call = false;
-    if (has_cand(c)) return run_candidates(c, q0, nq, cut, hooks);
+    c->split.call = false;
+    if (has_cand(c)) {
+        bool split = false;  // (a chunk is set and a list of the range is longer)
+        if (int rc = cand_split_prepare(c, q0, nq, &split)) return rc;
+        return split ? run_candidates_split(c, q0, nq, cut, hooks) : run_candidates(c, q0, nq, cut, hooks);
+    }
     c->qs.cand.call = false;
     bool scan_sets = false;  // (every query of the range carries the index of a scanned set)
     if (int rc = set_scan_prepare(c, q0, nq, &scan_sets)) return rc;
@@ -2775,6 +2891,7 @@ void leaf_destroy(hvs_ctx* c)
     c->rs.free_device();
     c->qs.free_device();
     c->scan.free_device();
+    c->split.free_device();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     {
         HvsPart& P = c->part;
@@ -3269,6 +3386,7 @@ int leaf_lists_commit(hvs_ctx* c, const ListKind& K, const uint32_t* ids, int sr
     int rc;
     HVS_HIP(c, hipSetDevice(c->device));
     L.set = false;  // (the buffers are about to change)
+    if (!K.cursor_forms) c->split.valid = false;  // (split candidate scans, DESIGN 3.17a: the plan is of the old lists)
     if ((rc = ensure_room(c, &at.d_begin, at.cap, std::max(count, 1u), &at.d_count)) ||
         (sets && (rc = ensure_room(c, &s.eng.ex.d_begin, s.eng.ex.cap, std::max(c->nq, 1u), &s.eng.ex.d_count))))
         return rc;
@@ -6508,6 +6626,72 @@ int hvs_candidates_stats(hvs_ctx* c, hvs_candidates_info* out)
 int hvs_download_candidates_plan(hvs_ctx* c, uint32_t* begin, uint32_t* count, uint32_t* ids, uint32_t cap)
 {
     return download_lists_plan(c, kCandidateLists, "hvs_download_candidates_plan", "candidate", begin, count, ids, cap);
+}
+
+// ---- split candidate scans (include/hvs.h "split candidate scans") ---------------
+
+int hvs_set_candidate_split(hvs_ctx* c, uint32_t chunk_ids)
+{
+    if (!c) return HVS_EINVAL;
+    if (chunk_ids != 0u && (chunk_ids % 64u != 0u || chunk_ids > HVS_CANDIDATES_MAX))
+        return fail(c, HVS_EINVAL, "hvs_set_candidate_split: chunk_ids must be 0 or a multiple of 64 in [64, HVS_CANDIDATES_MAX]");
+    // chunk 0: the path cannot be taken, so the partial lists (items x k keys, the one large buffer of the feature) are given back
+    return on_every_leaf(c, [&](hvs_ctx* k) -> int {
+        k->rs.cand_split = chunk_ids;
+        k->split.valid = false;
+        if (chunk_ids == 0u && k->split.d_partial) {
+            HVS_HIP(k, hipSetDevice(k->device));
+            HVS_HIP(k, hipStreamSynchronize(k->stream));
+            k->split.drop_partial();
+        }
+        return HVS_OK;
+    });
+}
+
+static int leaf_candidates_split_stats(hvs_ctx* c, hvs_candidates_split_info* out)
+{
+    *out = hvs_candidates_split_info{};
+    out->chunk_ids = c->rs.cand_split;
+    int rc = leaf_sync(c);
+    if (rc || !c->call.valid || !c->split.call) return rc;
+    out->ran = 1u;
+    out->split_queries = c->split.call_split;
+    out->items = c->split.call_items;
+    out->partial_bytes = c->split.call_bytes;
+    return HVS_OK;
+}
+
+int hvs_candidates_split_stats(hvs_ctx* c, hvs_candidates_split_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    if (c->kids.empty()) return leaf_candidates_split_stats(c, out);
+    hvs_candidates_split_info sum{};
+    for (hvs_ctx* k : c->kids) {
+        hvs_candidates_split_info m{};
+        HVS_HIP(c, hipSetDevice(k->device));
+        if (int rc = leaf_candidates_split_stats(k, &m)) return fail(c, rc, k->err);
+        sum.chunk_ids = m.chunk_ids;
+        sum.ran |= m.ran;
+        sum.split_queries += m.split_queries;
+        sum.items += m.items;
+        sum.partial_bytes += m.partial_bytes;
+    }
+    *out = sum;
+    return HVS_OK;
+}
+
+uint32_t hvs_candidates_split_plan(const uint32_t* counts, uint32_t nq, uint32_t chunk_ids, uint32_t* first_item, uint32_t* split_queries)
+{
+    uint32_t items = 0, split = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t p = chunk_ids ? hvs_cand_pieces(counts[q], chunk_ids) : 1u;
+        if (first_item) first_item[q] = items;
+        items += p;
+        split += p > 1u ? 1u : 0u;
+    }
+    if (first_item) first_item[nq] = items;
+    if (split_queries) *split_queries = split;
+    return items;
 }
 
 // ---- shared row sets (include/hvs.h "shared row sets") ---------------------------

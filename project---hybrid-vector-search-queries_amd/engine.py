@@ -147,6 +147,15 @@ class CandidatesInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CandidatesSplitInfo(C.Structure):
+    """hvs_candidates_split_info (include/hvs.h)."""
+    _fields_ = [("chunk_ids", C.c_uint32), ("ran", C.c_uint32), ("split_queries", C.c_uint32), ("items", C.c_uint32),
+                ("partial_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class RowSetsInfo(C.Structure):
     """hvs_row_sets_info (include/hvs.h)."""
     _fields_ = [("n_sets", C.c_uint32), ("words_per_set", C.c_uint32), ("bytes", C.c_uint64), ("restricted_queries", C.c_uint32),
@@ -355,6 +364,9 @@ def library():
         "hvs_query_in_row_sets": (C.c_int, [vp, _f32p, _u32p, C.c_uint32, C.c_float, _u32p, _f32p]),
         "hvs_row_sets_stats": (C.c_int, [vp, C.POINTER(RowSetsInfo)]),
         "hvs_row_sets_compact_plan": (None, [_u64p, _u64p, C.c_uint32, C.c_uint32, _u64p]),
+        "hvs_set_candidate_split": (C.c_int, [vp, C.c_uint32]),
+        "hvs_candidates_split_stats": (C.c_int, [vp, C.POINTER(CandidatesSplitInfo)]),
+        "hvs_candidates_split_plan": (C.c_uint32, [_u32p, C.c_uint32, C.c_uint32, _u32p, _u32p]),
         "hvs_set_row_set_scan_limit": (C.c_int, [vp, C.c_uint32]),
         "hvs_get_row_set_scan_limit": (C.c_uint32, [vp]),
         "hvs_row_set_scan_stats": (C.c_int, [vp, C.POINTER(RowSetScanInfo)]),
@@ -444,6 +456,18 @@ def row_set_scan_plan(queries_per_set, rows_per_set, k, chunk_rows=0, workgroups
     items = np.zeros((max(n, 1), 6), dtype=np.uint32)
     library().hvs_row_set_scan_plan(_up(q), _up(r), q.size, k, chunk_rows, workgroups, _up(items), n, None)
     return items[:n], slots.value
+
+
+def candidates_split_plan(counts, chunk_ids):
+    """hvs_candidates_split_plan: (items, first_item[nq + 1], split_queries) of a split candidate scan over normalised lists of
+    `counts` entries cut into chunks of `chunk_ids`."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    if cnt.ndim != 1:
+        raise ValueError("counts is a vector")
+    first = np.zeros(cnt.size + 1, dtype=np.uint32)
+    split = np.zeros(1, dtype=np.uint32)
+    items = library().hvs_candidates_split_plan(_up(cnt), cnt.size, int(chunk_ids), _up(first), _up(split))
+    return int(items), first, int(split[0])
 
 
 def mask_plan(live, k, sample_proportion):
@@ -1299,6 +1323,18 @@ class Engine:
         device time of the last call."""
         e = CandidatesInfo()
         self._ck(self._lib.hvs_candidates_stats(self._h, C.byref(e)))
+        return e
+
+    def set_candidate_split(self, chunk_ids):
+        """A call under candidate lists with a list longer than `chunk_ids` entries is scanned in pieces of that many, a wave
+        each (0: never; a multiple of 64 in [64, 8192]; include/hvs.h "split candidate scans")."""
+        self._ck(self._lib.hvs_set_candidate_split(self._h, int(chunk_ids)))
+
+    def candidates_split_stats(self):
+        """hvs_candidates_split_stats: the chunk in force and, of the last call, whether it was split, its split queries,
+        items and the bytes of partial lists."""
+        e = CandidatesSplitInfo()
+        self._ck(self._lib.hvs_candidates_split_stats(self._h, C.byref(e)))
         return e
 
     def candidates_plan_device(self, nq=None):
