@@ -1227,6 +1227,16 @@ void hvs_row_sets_compact_plan(const uint64_t *bits, const uint64_t *live_bits /
  * the set's member list), slot}; the query at place q_begin + j leaves its partial list in slot `slot + j`, and slots are handed
  * out densely in item order.  Returns the number of items; at most max_items are written (items may be NULL); *slots, where not
  * NULL, is the number of partial-list slots.  A set without queries has no item; a set without members has one per tile, empty.
+ *
+ * hvs_set_row_set_scan_filter: which kernel scans the members.  0 (the default): hvs_k_scan_set_members, the exact
+ * distance on every passing (query, member) pair; every call then launches exactly what it launched before.  1:
+ * hvs_k_scan_set_members_f16, which first bounds every pair of a block of 32 members from below with an FP16 matrix product and
+ * evaluates the exact distance only where the bound does not prove the pair beyond the query's threshold.  Any other value is
+ * HVS_EINVAL and nothing changes.  The mode never decides whether a call takes the scanned path, nor its plan, items, grouping
+ * or partial lists, and the answer is the same to the bit; hvs_timing.rescored_pairs then reports the pairs whose exact
+ * distance was evaluated (mode 0: 0, as before) and hvs_timing.scanned_pairs / hvs_row_set_scan_info.scanned_pairs the pairs a
+ * bound was computed for.  Context state beside the limit, it survives what the limit survives; every context kind accepts it.
+ * hvs_get_row_set_scan_filter reads it back.
  */
 typedef struct hvs_row_set_scan_info {
     uint32_t scanned_sets;
@@ -1242,6 +1252,8 @@ typedef struct hvs_row_set_scan_item {
 } hvs_row_set_scan_item;
 int hvs_set_row_set_scan_limit(hvs_ctx *ctx, uint32_t rows);
 uint32_t hvs_get_row_set_scan_limit(hvs_ctx *ctx);
+int hvs_set_row_set_scan_filter(hvs_ctx *ctx, uint32_t mode);
+uint32_t hvs_get_row_set_scan_filter(hvs_ctx *ctx);
 int hvs_row_set_scan_stats(hvs_ctx *ctx, hvs_row_set_scan_info *out);
 uint32_t hvs_row_set_scan_plan(const uint32_t *queries_per_set, const uint32_t *rows_per_set, uint32_t n_sets, uint32_t k,
                                uint32_t chunk_rows, uint32_t workgroups, hvs_row_set_scan_item *items, uint32_t max_items,

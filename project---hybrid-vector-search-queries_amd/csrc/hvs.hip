@@ -28,6 +28,7 @@
 #include "hvs_kernels.h"
 #include "hvs_filter.h"
 #include "hvs_set_scan.h"
+#include "hvs_set_scan_f16.h"
 #include "hvs_cand_split.h"
 
 namespace {
@@ -158,6 +159,7 @@ struct HvsRowSet {
     // is false none of it is read: whatever changes a bit of d_sets, the rows it describes or the limit clears the flag, and the
     // first call that could take the path rebuilds the lists (scan_lists_build).
     uint32_t scan_limit = 0;        // hvs_set_row_set_scan_limit (0: never); a setting, kept by every reset
+    uint32_t scan_filter = 0;       // hvs_set_row_set_scan_filter (0: the exact scan alone, 1: the FP16 bound in front); a setting
     uint32_t cand_split = 0;        // hvs_set_candidate_split (0: never); a setting, kept by every reset
     bool scan_lists_valid = false;
     uint32_t *d_scan_members = nullptr, *d_scan_pop = nullptr, *d_scan_mem_off = nullptr, *d_scan_blk = nullptr;
@@ -2707,7 +2709,7 @@ int run_set_scan(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& hooks
                            s.eng.d_set_of, c->rs.n_sets, g.d_goff, g.d_set_item0, g.d_set_chunks, g.d_lists, g.d_list_cnt, c->padding ? 1 : 0,
                            masked(c) ? c->rs.d_pad_ids : nullptr, c->d_out_ids, c->d_out_dists, c->k, c->call.d_counters};
     const int cap = c->k <= 128u ? 256 : 512;
-    hvs_launch_set_scan(c->stream, c->scalar_order, cap, g.n_items, a);
+    hvs_launch_set_scan_by(c->stream, c->rs.scan_filter, c->scalar_order, cap, g.n_items, a);
     kernel_timer_end(c, ev);
     HVS_HIP(c, hipGetLastError());
     if ((rc = hooks.after(0u, nq, 0u))) return rc;
@@ -6909,6 +6911,18 @@ int hvs_set_row_set_scan_limit(hvs_ctx* c, uint32_t rows)
 }
 
 uint32_t hvs_get_row_set_scan_limit(hvs_ctx* c) { return c ? mask_leaf(c)->rs.scan_limit : 0u; }
+
+// (nothing is cached per mode: the items, the grouping and the partial lists are the same, only the scan kernel differs)
+int hvs_set_row_set_scan_filter(hvs_ctx* c, uint32_t mode)
+{
+    if (!c || mode > 1u) return HVS_EINVAL;
+    return on_every_leaf(c, [&](hvs_ctx* k) -> int {
+        k->rs.scan_filter = mode;
+        return HVS_OK;
+    });
+}
+
+uint32_t hvs_get_row_set_scan_filter(hvs_ctx* c) { return c ? mask_leaf(c)->rs.scan_filter : 0u; }
 
 // one GPU's figures; the member lists are brought up to date first, so that the sets' figures are those of the limit in force
 static int leaf_row_set_scan_stats(hvs_ctx* c, hvs_row_set_scan_info* out)

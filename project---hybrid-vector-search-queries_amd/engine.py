@@ -369,6 +369,8 @@ def library():
         "hvs_candidates_split_plan": (C.c_uint32, [_u32p, C.c_uint32, C.c_uint32, _u32p, _u32p]),
         "hvs_set_row_set_scan_limit": (C.c_int, [vp, C.c_uint32]),
         "hvs_get_row_set_scan_limit": (C.c_uint32, [vp]),
+        "hvs_set_row_set_scan_filter": (C.c_int, [vp, C.c_uint32]),
+        "hvs_get_row_set_scan_filter": (C.c_uint32, [vp]),
         "hvs_row_set_scan_stats": (C.c_int, [vp, C.POINTER(RowSetScanInfo)]),
         "hvs_row_set_scan_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p]),
         "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
@@ -1289,6 +1291,14 @@ class Engine:
 
     def row_set_scan_limit(self):
         return int(self._lib.hvs_get_row_set_scan_limit(self._h))
+
+    def set_row_set_scan_filter(self, mode):
+        """Which kernel scans a scanned set's members: 0 the exact distance on every pair (default), 1 an FP16 matrix bound
+        in front of it; the answers are the same to the bit (hvs_set_row_set_scan_filter, include/hvs.h)."""
+        self._ck(self._lib.hvs_set_row_set_scan_filter(self._h, int(mode)))
+
+    def row_set_scan_filter(self):
+        return int(self._lib.hvs_get_row_set_scan_filter(self._h))
 
     def row_set_scan_stats(self):
         info = RowSetScanInfo()
