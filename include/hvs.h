@@ -1259,6 +1259,37 @@ uint32_t hvs_row_set_scan_plan(const uint32_t *queries_per_set, const uint32_t *
                                uint32_t chunk_rows, uint32_t workgroups, hvs_row_set_scan_item *items, uint32_t max_items,
                                uint64_t *slots);
 
+/*
+ * Tail filter: which kernels scan the rows behind the index -- the tail (hvs_append_rows) and the stale rows
+ * (hvs_update_rows) -- for the batches that walk the index.  0 (the default): hvs_k_scan_tail and hvs_k_scan_stale, the exact
+ * distance on every (query, row) pair; every call then launches exactly what it launched before, with the same arguments.
+ * 1: a call that has such rows first writes them out as half-precision operand blocks of 32 rows (hvs_k_build_behind_operands;
+ * once per call and GPU, nothing is kept between calls), and the launches that hand out lists under thresholds -- the filter
+ * engines' scan in front of the final merge, the exact engine's range scan under distance caps -- take hvs_k_scan_behind_f16,
+ * which bounds every pair of a block from below with an FP16 matrix product and evaluates the exact distance only where the
+ * bound does not prove the pair beyond the query's threshold.  Pairs-only launches and launches without thresholds stay as
+ * they are.  Any other value is HVS_EINVAL and nothing changes.  Ids, distance bits, candidate lists, re-runs and every
+ * existing counter (hvs_timing, hvs_append_info, hvs_update_info) are the same in both modes.  Context state like
+ * hvs_set_tail_limit: kept by loads, re-indexes and compactions, replicated to every GPU; a row-partitioned context, which has
+ * no tail, accepts and stores it.  Mode 0 frees the operand buffer.  hvs_get_tail_filter reads the mode back.
+ *
+ * hvs_tail_filter_stats: blocks = operand blocks the last call built (tail and stale rows; 0: it built none), operand_bytes =
+ * the buffer as it stands (several GPUs: summed, as blocks and the pairs are), bound_pairs = pairs of the last call a bound was
+ * computed for, exact_pairs = pairs of them whose exact distance was evaluated (re-run batches apart, as tail_pairs).
+ * hvs_tail_filter_build_ms: device time of the last call's operand build in ms (several GPUs: the longest; 0: none was built).
+ */
+typedef struct hvs_tail_filter_info {
+    uint32_t mode;          /* 0 / 1 */
+    uint32_t blocks;        /* 32-row operand blocks built for the last call (tail + stale) */
+    uint64_t operand_bytes; /* the buffer on this GPU (multi-GPU: summed) */
+    uint64_t bound_pairs;   /* last call */
+    uint64_t exact_pairs;   /* last call */
+} hvs_tail_filter_info;
+int hvs_set_tail_filter(hvs_ctx *ctx, uint32_t mode);
+uint32_t hvs_get_tail_filter(hvs_ctx *ctx);
+int hvs_tail_filter_stats(hvs_ctx *ctx, hvs_tail_filter_info *out);
+double hvs_tail_filter_build_ms(hvs_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@
 #include "hvs_set_scan.h"
 #include "hvs_set_scan_f16.h"
 #include "hvs_cand_split.h"
+#include "hvs_tail_f16.h"
 
 namespace {
 
@@ -161,6 +162,7 @@ struct HvsRowSet {
     uint32_t scan_limit = 0;        // hvs_set_row_set_scan_limit (0: never); a setting, kept by every reset
     uint32_t scan_filter = 0;       // hvs_set_row_set_scan_filter (0: the exact scan alone, 1: the FP16 bound in front); a setting
     uint32_t cand_split = 0;        // hvs_set_candidate_split (0: never); a setting, kept by every reset
+    uint32_t tail_filter = 0;       // hvs_set_tail_filter (0: the exact scans of tail and stale rows, 1: the FP16 bound in front); a setting
     bool scan_lists_valid = false;
     uint32_t *d_scan_members = nullptr, *d_scan_pop = nullptr, *d_scan_mem_off = nullptr, *d_scan_blk = nullptr;
     uint32_t scan_members_cap = 0, scan_tab_cap = 0, scan_blk_cap = 0;
@@ -459,6 +461,33 @@ struct HvsSetScan {
     }
 };
 
+// The operand blocks of the rows behind the index (hvs_tail_f16.h) on one GPU: the tail's blocks, then the stale
+// rows'.  Built by every call that runs with hvs_set_tail_filter(ctx, 1) and has such rows, ahead of its first batch (behind_build);
+// nothing is kept from call to call but the room.  `ready`: the blocks describe the rows as they are -- set by the build, cleared
+// where a call begins, where rows are about to change (begin_mutation) and in front of the planner probe; while it is false the
+// launch sites take the unfiltered kernels.  The call's re-runs (resolve_overflow) read the blocks its build left.
+struct HvsBehindOps {
+    uint4* d_ops = nullptr;
+    size_t cap = 0;  // uint4 entries d_ops has room for
+    bool ready = false;
+    uint32_t tail_rows = 0, tail_blocks = 0, stale_rows = 0, stale_blocks = 0;  // of the blocks built last
+    hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;  // around the build kernel of the last call that built
+    bool call = false;  // the last call built blocks
+    void free_device()
+    {
+        HvsRowSet::drop(d_ops);
+        cap = 0;
+        ready = call = false;
+        tail_rows = tail_blocks = stale_rows = stale_blocks = 0;
+    }
+    void destroy()
+    {
+        free_device();
+        for (hipEvent_t* ev : {&ev_b0, &ev_b1})
+            if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
+    }
+};
+
 // Split candidate scans on one GPU: the item plan of resident queries [q0, q0 + nq) for chunks of `chunk` entries
 // (d_items, d_first_item, d_split_q; made on the device from the normalised lists' counts) and the partial lists the pieces of
 // split queries write (n_items x k keys).  `valid`: the plan describes the lists and the chunk in force; cleared where candidate
@@ -704,6 +733,7 @@ struct hvs_ctx : HvsLane {
     HvsCallState call;  // what the last call left behind: counters, re-run lists, the report
     HvsSetScan scan;    // scanned sets: the resident queries grouped by set, the item table, the partial lists
     HvsCandSplit split; // split candidate scans: the item plan of a range of queries, the partial lists
+    HvsBehindOps behind; // rows behind the index under the FP16 bound: the call's operand blocks
 
     // ---- MFMA engine: index over D (two orderings) ...
     // Two facts: `have_order` -- keys and perm of both orderings exist (the exact engine's range scans need no more) -- and
@@ -1649,6 +1679,7 @@ int probe_format(hvs_ctx* c, double* cost, double* inflation, double* failed)
     constexpr uint32_t P = 1024;
     *cost = 1.0e9;
     if (c->call.pending) return fail(c, HVS_ESTATE, "internal: planner probe while a call's re-runs are pending");  // (h_ovf and the counts are that call's)
+    c->behind.ready = false;  // (the probe's batch takes the unfiltered scans of the rows behind the index)
     // the probe has its own query / result / re-run buffers, in the context's fields while it runs: resident queries and
     // results of the caller stay untouched
     ScopedDevBufs own;
@@ -1945,9 +1976,26 @@ int prep_batch(hvs_ctx* c, uint32_t q0, uint32_t nqb, bool count_pairs, int fmt,
 // The tail of the batch in c->fb (hvs_k_scan_tail): ids [n_indexed, sn), if there are any.  `count`: the batch's pairs go
 // to the call's counters (not in re-run batches).
 bool have_tail(const hvs_ctx* c, uint32_t sn) { return c->have_order && sn > c->n_indexed; }
+// hvs_set_tail_filter(ctx, 1): a launch that hands out lists under thresholds takes hvs_k_scan_behind_f16 over the
+// operand blocks the call built; pairs-only launches and launches without thresholds have nothing a bound could refuse
+bool behind_filtered(const hvs_ctx* c, const HvsTailOut& out) { return c->rs.tail_filter == 1u && c->behind.ready && out.lists && out.tau; }
+template <int CNT>
+void launch_behind_f16(hvs_ctx* c, const uint4* ops, uint32_t nrows, const HvsTailOut& out, bool count)
+{
+    const HvsBatch& B = c->fb;
+    with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
+        with_after(c, [&](auto AT, auto XT) {
+            hipLaunchKernelGGL((hvs_k_scan_behind_f16<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, CNT, decltype(AT)::value, decltype(XT)::value>),
+                               dim3((B.nslots + 255u) / 256u), dim3(256), 0, c->stream, c->d_data, c->d_q, B, out, ops, nrows, c->call.d_counters,
+                               count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo, excl_arg(c));
+        });
+    });
+}
 void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
+    if (behind_filtered(c, out) && sn - c->n_indexed <= c->behind.tail_rows)
+        return launch_behind_f16<HVS_CNT_TAIL_PAIRS>(c, c->behind.d_ops, sn - c->n_indexed, out, count);
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         with_after(c, [&](auto AT, auto XT) {
             hipLaunchKernelGGL((hvs_k_scan_tail<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value, decltype(XT)::value>),
@@ -1962,6 +2010,8 @@ void launch_tail(hvs_ctx* c, uint32_t sn, const HvsTailOut& out, bool count)
 void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
 {
     const HvsBatch& B = c->fb;
+    if (behind_filtered(c, out) && m <= c->behind.stale_rows)
+        return launch_behind_f16<HVS_CNT_STALE_PAIRS>(c, c->behind.d_ops + (size_t)c->behind.tail_blocks * HVS_BEHIND_BLOCK_U4, m, out, count);
     with_order_cap_mask(c, [&](auto ST, auto CAPT, auto MT) {
         with_after(c, [&](auto AT, auto XT) {
             hipLaunchKernelGGL((hvs_k_scan_stale<decltype(ST)::value, decltype(CAPT)::value, decltype(MT)::value, decltype(AT)::value, decltype(XT)::value>),
@@ -1969,6 +2019,31 @@ void launch_stale(hvs_ctx* c, uint32_t m, const HvsTailOut& out, bool count)
                                c->call.d_counters, count ? 1 : 0, c->rs.d_live, c->qs.eng.d_after_lo, excl_arg(c));
         });
     });
+}
+
+// hvs_set_tail_filter(ctx, 1): the operand blocks of EVERY tail row and EVERY stale row of the context (a batch's sn selects a
+// prefix of each at scan time), by hvs_k_build_behind_operands on the main stream behind the call's counter resets and ahead of
+// its first batch; the spare lane waits for ev_b1 where it joins the call (run_queries_cut).  Nothing is kept across calls: the
+// rows may have changed in between, and reading them again costs 408 bytes a row.  The buffer grows with the rows there are.
+int behind_build(hvs_ctx* c)
+{
+    HvsBehindOps& o = c->behind;
+    o.ready = o.call = false;
+    if (c->rs.tail_filter != 1u || !c->have_order) return HVS_OK;
+    const uint32_t tail = tail_rows(c), stale = (uint32_t)c->rs.h_stale.size();
+    const uint32_t tb = hvs_ceil_div(tail, HVS_SCANF_ROWS), sb = hvs_ceil_div(stale, HVS_SCANF_ROWS);
+    if (tb + sb == 0u) return HVS_OK;
+    if (int rc = ensure_room(c, &o.d_ops, o.cap, (size_t)(tb + sb) * HVS_BEHIND_BLOCK_U4)) return rc;
+    for (hipEvent_t* ev : {&o.ev_b0, &o.ev_b1})
+        if (!*ev) HVS_HIP(c, hipEventCreate(ev));
+    HVS_HIP(c, hipEventRecord(o.ev_b0, c->stream));
+    hipLaunchKernelGGL(hvs_k_build_behind_operands, dim3(tb + sb), dim3(256), 0, c->stream, c->d_data, c->n, c->n_indexed, tail, c->rs.d_stale_ids, stale,
+                       o.d_ops);
+    HVS_HIP(c, hipGetLastError());
+    HVS_HIP(c, hipEventRecord(o.ev_b1, c->stream));
+    o.tail_rows = tail, o.tail_blocks = tb, o.stale_rows = stale, o.stale_blocks = sb;
+    o.ready = o.call = true;
+    return HVS_OK;
 }
 
 // Exact engine on top of the index.  Queries with a categorical predicate (types 1 and 3) scan only
@@ -2730,6 +2805,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     if ((uint64_t)q0 + nq > c->nq) return fail(c, HVS_EINVAL, "query range outside the resident query set");
     HVS_HIP(c, hipSetDevice(c->device));
     if (int rc = resolve_overflow(c)) return rc;  // an earlier call whose results were never fetched
+    c->behind.ready = c->behind.call = false;     // (its operand blocks described the rows as that call saw them)
     c->scan.call = false;
     c->split.call = false;
     if (has_cand(c)) {
@@ -2763,6 +2839,9 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
     c->qs.answered(q0, nq, c->k, c->qs.set_gen);
     if (int rc = call_begin(c)) return rc;
     const bool ranges = !mfma && c->have_order;  // exact engine: scan position ranges when the orderings exist
+    // (the launches that can take the filtered scan are the filter engines' and the capped range scan's)
+    if (mfma || (ranges && capped(c)))
+        if (int rc = behind_build(c)) return rc;
     const std::vector<uint32_t> sched = batch_schedule(nq, mfma ? kBatchMfma : kBatch, host_pipeline && mfma);
     // Two lanes (HvsLane): every other batch of a filter-engine call runs on the spare lane's stream and workspace, so that
     // its preparation, seed and low levels share the chip with the previous batch's last re-scoring and final merge.  The
@@ -2793,6 +2872,7 @@ int run_queries_cut(hvs_ctx* c, uint32_t q0, uint32_t nq, RowCut cut, Hooks&& ho
                 two_lanes = false;
             } else if (!spare_used) {
                 HVS_HIP(c, hipStreamWaitEvent(c->stream, c->call.ev_q0, 0));
+                if (c->behind.call) HVS_HIP(c, hipStreamWaitEvent(c->stream, c->behind.ev_b1, 0));  // (the operand blocks: built on the main stream)
                 spare_used = true;
             }
         }
@@ -2894,6 +2974,7 @@ void leaf_destroy(hvs_ctx* c)
     c->qs.free_device();
     c->scan.free_device();
     c->split.free_device();
+    c->behind.destroy();
     c->ord[0].lp = c->ord[1].lp = nullptr;
     {
         HvsPart& P = c->part;
@@ -2965,6 +3046,7 @@ int begin_mutation(hvs_ctx* c)
     int rc = resolve_overflow(c);
     if (rc) return rc;
     HVS_HIP(c, hipStreamSynchronize(c->stream));
+    c->behind.ready = false;  // (rows are about to change under the operand blocks of the rows behind the index)
     return HVS_OK;
 }
 
@@ -7354,6 +7436,81 @@ int hvs_set_tail_limit(hvs_ctx* c, uint32_t rows)
     c->rs.tail_limit = rows;
     for (hvs_ctx* k : c->kids) k->rs.tail_limit = rows;
     return HVS_OK;
+}
+
+// ---- rows behind the index under the FP16 bound (include/hvs.h "tail filter") ------
+
+// (mode 0 gives the operand blocks back: the call that left them is resolved first, its re-runs read them)
+int hvs_set_tail_filter(hvs_ctx* c, uint32_t mode)
+{
+    if (!c || mode > 1u) return HVS_EINVAL;
+    c->rs.tail_filter = mode;
+    return on_every_leaf(c, [&](hvs_ctx* k) -> int {
+        k->rs.tail_filter = mode;
+        if (mode == 0u && k->behind.d_ops) {
+            if (int rc = leaf_sync(k)) return rc;
+            k->behind.free_device();
+        }
+        return HVS_OK;
+    });
+}
+
+uint32_t hvs_get_tail_filter(hvs_ctx* c) { return c ? mask_leaf(c)->rs.tail_filter : 0u; }
+
+static int leaf_tail_filter_stats(hvs_ctx* c, hvs_tail_filter_info* out, double* build_ms)
+{
+    *out = hvs_tail_filter_info{};
+    *build_ms = 0.0;
+    int rc = leaf_sync(c);
+    if (rc) return rc;
+    out->mode = c->rs.tail_filter;
+    out->operand_bytes = (uint64_t)c->behind.cap * sizeof(uint4);
+    if (!c->call.valid || !c->behind.call) return HVS_OK;
+    out->blocks = c->behind.tail_blocks + c->behind.stale_blocks;
+    unsigned long long v[2];
+    if ((rc = call_counters(c, HVS_CNT_BEHIND_BOUND, v))) return rc;
+    out->bound_pairs = v[0];
+    out->exact_pairs = v[1];
+    float ms = 0.0f;
+    HVS_HIP(c, hipEventElapsedTime(&ms, c->behind.ev_b0, c->behind.ev_b1));
+    *build_ms = ms;
+    return HVS_OK;
+}
+
+// every GPU's figures summed (a replicated context builds the blocks on each GPU); the build time is the longest
+static int tail_filter_figures(hvs_ctx* c, hvs_tail_filter_info* out, double* build_ms)
+{
+    if (c->kids.empty()) return leaf_tail_filter_stats(c, out, build_ms);
+    hvs_tail_filter_info sum{};
+    *build_ms = 0.0;
+    for (hvs_ctx* k : c->kids) {
+        hvs_tail_filter_info m{};
+        double ms = 0.0;
+        HVS_HIP(c, hipSetDevice(k->device));
+        if (int rc = leaf_tail_filter_stats(k, &m, &ms)) return fail(c, rc, k->err);
+        sum.mode = m.mode;
+        sum.blocks += m.blocks;
+        sum.operand_bytes += m.operand_bytes;
+        sum.bound_pairs += m.bound_pairs;
+        sum.exact_pairs += m.exact_pairs;
+        *build_ms = std::max(*build_ms, ms);
+    }
+    *out = sum;
+    return HVS_OK;
+}
+
+int hvs_tail_filter_stats(hvs_ctx* c, hvs_tail_filter_info* out)
+{
+    if (!c || !out) return HVS_EINVAL;
+    double ms = 0.0;
+    return tail_filter_figures(c, out, &ms);
+}
+
+double hvs_tail_filter_build_ms(hvs_ctx* c)
+{
+    hvs_tail_filter_info info{};
+    double ms = 0.0;
+    return c && tail_filter_figures(c, &info, &ms) == HVS_OK ? ms : 0.0;
 }
 
 int hvs_append_stats(hvs_ctx* c, hvs_append_info* out)

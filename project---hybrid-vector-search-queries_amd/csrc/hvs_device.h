@@ -29,8 +29,10 @@ enum HvsCounter : int {
     // whose pairs were counted beforehand): their PAIRS and SCANNED land in slots 4 and 5, which nothing reads
     HVS_CNT_RERUN_SINK = 4,
     HVS_CNT_RERUN_SINK_SCANNED = 5,
-    HVS_CNT_UNUSED_6 = 6,
-    HVS_CNT_UNUSED_7 = 7,
+    // rows behind the index under hvs_set_tail_filter(ctx, 1), tail and stale rows together.  (Seen from
+    // HVS_CNT_RERUN_SINK these are RESCORED and slot 3, which no kernel that counts through the sink writes.)
+    HVS_CNT_BEHIND_BOUND = 6,       // pairs a bound was computed for                      -> hvs_tail_filter_info.bound_pairs
+    HVS_CNT_BEHIND_EXACT = 7,       // ... pairs whose exact distance was evaluated        -> hvs_tail_filter_info.exact_pairs
     HVS_CNT_DEAD_SURVIVORS = 8,     // survivors dropped because the row is dead           -> hvs_mask_info.dead_survivors
     HVS_CNT_TAIL_PAIRS = 9,         // rows behind the index: pairs evaluated              -> hvs_append_info.tail_pairs
     HVS_CNT_TAIL_KEYS = 10,         // ... keys admitted                                   -> hvs_append_info.tail_admitted
@@ -67,6 +69,7 @@ static_assert(HVS_CNT_SCANNED == HVS_CNT_PAIRS + 1 && HVS_CNT_RESCORED == HVS_CN
 static_assert(HVS_CNT_RERUN_SINK_SCANNED == HVS_CNT_RERUN_SINK + HVS_CNT_SCANNED, "the sink takes a batch's PAIRS and SCANNED");
 static_assert(HVS_CNT_TAIL_KEYS == HVS_CNT_TAIL_PAIRS + 1, "hvs_scan_rows_into_lists: keys admitted follow pairs evaluated");
 static_assert(HVS_CNT_STALE_KEYS == HVS_CNT_STALE_PAIRS + 1 && HVS_CNT_STALE_SURVIVORS == HVS_CNT_STALE_PAIRS + 2, "one run, and CNT + 1");
+static_assert(HVS_CNT_BEHIND_EXACT == HVS_CNT_BEHIND_BOUND + 1, "hvs_tail_filter_stats reads one run");
 static_assert(HVS_CNT_WITHIN_UNDERFULL == HVS_CNT_WITHIN_SLOTS + 1, "hvs_within_stats reads one run");
 static_assert(HVS_CNT_AFTER_UNDERFULL == HVS_CNT_AFTER_SLOTS + 1 && HVS_CNT_AFTER_EXHAUSTED == HVS_CNT_AFTER_SLOTS + 2, "hvs_after_stats reads one run");
 static_assert(HVS_CNT_EXCL_UNDERFULL == HVS_CNT_EXCL_SLOTS + 1 && HVS_CNT_EXCL_REFUSED == HVS_CNT_EXCL_SLOTS + 2, "hvs_exclude_stats reads one run");

@@ -174,6 +174,15 @@ class RowSetScanInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class TailFilterInfo(C.Structure):
+    """hvs_tail_filter_info (include/hvs.h)."""
+    _fields_ = [("mode", C.c_uint32), ("blocks", C.c_uint32), ("operand_bytes", C.c_uint64), ("bound_pairs", C.c_uint64),
+                ("exact_pairs", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 IN_MAX_VALUES = 64
 EXCLUDE_MAX = 1024
 CANDIDATES_MAX = 8192
@@ -373,6 +382,10 @@ def library():
         "hvs_get_row_set_scan_filter": (C.c_uint32, [vp]),
         "hvs_row_set_scan_stats": (C.c_int, [vp, C.POINTER(RowSetScanInfo)]),
         "hvs_row_set_scan_plan": (C.c_uint32, [_u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p]),
+        "hvs_set_tail_filter": (C.c_int, [vp, C.c_uint32]),
+        "hvs_get_tail_filter": (C.c_uint32, [vp]),
+        "hvs_tail_filter_stats": (C.c_int, [vp, C.POINTER(TailFilterInfo)]),
+        "hvs_tail_filter_build_ms": (C.c_double, [vp]),
         "hvs_set_query_vectors": (C.c_int, [vp, _u32p, _f32p, C.c_uint32]),
         "hvs_set_query_vectors_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "hvs_query_vectors": (C.c_int, [vp, _f32p, _u32p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p]),
@@ -1009,6 +1022,23 @@ class Engine:
         a = AppendInfo()
         self._ck(self._lib.hvs_append_stats(self._h, C.byref(a)))
         return a
+
+    def set_tail_filter(self, mode):
+        """Which kernels scan the rows behind the index (appended and updated rows): 0 the exact distance on every pair
+        (default), 1 an FP16 matrix bound in front of it; the answers are the same to the bit (hvs_set_tail_filter, include/hvs.h)."""
+        self._ck(self._lib.hvs_set_tail_filter(self._h, int(mode)))
+
+    def tail_filter(self):
+        return int(self._lib.hvs_get_tail_filter(self._h))
+
+    def tail_filter_stats(self):
+        info = TailFilterInfo()
+        self._ck(self._lib.hvs_tail_filter_stats(self._h, C.byref(info)))
+        return info
+
+    def tail_filter_build_ms(self):
+        """Device time of the last call's operand build under set_tail_filter(1), in ms (0: it built none)."""
+        return float(self._lib.hvs_tail_filter_build_ms(self._h))
 
     # --- row update (include/hvs.h "row update in place")
     def update_rows(self, ids, rows):
